@@ -14,9 +14,12 @@ tree); data: synthetic chair-like clouds (livingscenes_amd.synth).  fp32 through
 Multi-GPU: instances shard embarrassingly (weak scaling: every rank runs its own 64-instance batch); RCCL is used to
 broadcast the weights once and to gather a result checksum -- there is no data-path collective.
 
-Prints ONE JSON line (rank 0): metric/value/... + "roofline" (dominant kernel, hipEvent-timed per launch in a separate
-profiled pass of the same K steps) + "cpu_baseline" (the CPU oracle = the reference's PyTorch-CPU op sequence, timed on
-this host's cores on a bounded sample).
+A plain run sets up, warms up, times EXACTLY --steps steps (one block), writes the last step's outputs if --dump-outputs DIR is
+given, and prints ONE JSON line (rank 0): metric / value / unit / higher_is_better / dtype / ms_per_step + the run's configuration.
+--full adds everything else the benchmark measures or checks: the median-of-blocks protocol (--steps steps per block), GPU clock /
+power readings, the fused-multiply-add k-NN variant, the one-step-in-flight time, the bit-identity / sanity checks of the results,
+"roofline" (dominant kernel, hipEvent-timed per launch in a separate profiled pass of the same K steps) and "cpu_baseline" (the CPU
+oracle = the reference's PyTorch-CPU op sequence, timed on this host's cores on a bounded sample, with the timed codes checked against it).
 """
 import argparse
 import json
@@ -285,18 +288,38 @@ def fps_entry(level, avg_s, cfg, B, N):
                      f"{B} workgroups = {B / 256:.0%} of the CUs, on a side stream beside layers 0 - 1"}
 
 
+def dump_outputs(path, out):
+    """--dump-outputs: what a caller of the timed path receives from one step (Shape_Prior.encode's codes, sequential_matcher's
+    matches, the Kabsch poses) as <path>/<name>.npy -- float32 as computed, integer indices as float64 (exact); ~0.5 MB at the default
+    batch.  The inputs are seeded (synth), so two builds given the same arguments can be compared output for output."""
+    import numpy as np
+    emb, m, R, t = out
+    arrays = {**{"encode_" + k: v for k, v in emb.items()}, **{"match_" + k: v for k, v in m.items()}, "register_R": R, "register_t": t}
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        a = v.detach().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32 if a.dtype == np.float32 else np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="ranks = GPUs (one process each); default: the launcher's WORLD_SIZE, 1 without a launcher")
     ap.add_argument("--steps", type=int, default=480,
-                    help="timed steps PER BLOCK (a step is ~1.1 ms: one 20-step region is short enough for a single host hiccup or a cold "
-                         "allocator to halve the figure -- BENCH_r05 -- hence --blocks)")
+                    help="timed steps (PER BLOCK with --full or --blocks: a step is ~1.1 ms, and one 20-step region is short enough for a single host "
+                         "hiccup or a cold allocator to halve the figure -- BENCH_r05 -- hence the blocks of --full)")
     ap.add_argument("--warmup", type=int, default=48, help="untimed steps (raised to >= 3 per in-flight handle and >= --warmup-s of wall time)")
     ap.add_argument("--warmup-s", type=float, default=0.3, help="minimum wall time of the warm-up (clock ramp, every handle's first touches)")
     ap.add_argument("--blocks", type=int, default=0,
-                    help="0 = auto (9 when fewer than 48 steps are timed, 3 otherwise).  The K-step timed region (barrier + synchronize on both "
-                         "sides, MAX over ranks) is run this many times back to back; `value` / `ms_per_step` are the MEDIAN block, every block's "
-                         "time is in config.blocks_ms")
+                    help="0 = auto (1; with --full: 9 when fewer than 48 steps are timed, 3 otherwise).  The K-step timed region (barrier + "
+                         "synchronize on both sides, MAX over ranks) is run this many times back to back; `value` / `ms_per_step` are the MEDIAN "
+                         "block, every block's time is in config.blocks_ms")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the median-of-blocks protocol, clock / power readings, the FMA k-NN "
+                         "variant, the one-in-flight time, result checks, the profiled roofline pass and the CPU baseline with its oracle check "
+                         "(--no-profile / --no-fma-variant / --cpu-instances 0 still leave their part out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0: codes, matches, poses) as DIR/<name>.npy "
+                         "(float32; integer outputs as float64)")
     ap.add_argument("--batch", type=int, default=64, help="instances per step per GPU (two scenes of batch/2 objects)")
     ap.add_argument("--points", type=int, default=1024)
     ap.add_argument("--cpu-instances", type=int, default=8, help="bounded sample for the CPU baseline (0 = skip)")
@@ -434,12 +457,14 @@ def main():
     #   blocks    the contract's timed region -- barrier + synchronize, EXACTLY K steps, synchronize + barrier -- R times back to back; per block
     #             the MAX over ranks; `value` / `ms_per_step` = the MEDIAN block.  One slow block (a host hiccup is ~10 ms, a 20-step block ~25 ms)
     #             moves the median by nothing; every block's time is reported in `config.blocks_ms` (the driver keeps `config`).
-    n_blocks = args.blocks if args.blocks > 0 else (9 if args.steps < 48 else 3)
+    #   A plain run times ONE block of exactly K steps; the blocks are part of --full.
+    n_blocks = args.blocks if args.blocks > 0 else ((9 if args.steps < 48 else 3) if args.full else 1)
     r5_protocol = bool(os.environ.get("LS_BENCH_R5_PROTOCOL"))   # dev: round 5's region (ONE step of warm-up per handle, one block) to reproduce BENCH_r05
     if r5_protocol:
         n_blocks, args.warmup_s = 1, 0.0
     my_pci = pci[launcher_local % len(pci)] if pci else None
-    clk_idle = gpu_clock_power(local_rank, my_pci) if rank == 0 else None
+    probe_clocks = rank == 0 and args.full      # (sysfs, or a rocm-smi subprocess where sysfs is not readable: --full only)
+    clk_idle = gpu_clock_power(local_rank, my_pci) if probe_clocks else None
     with torch.no_grad():
         for st in streams:
             st.wait_stream(torch.cuda.current_stream(dev))
@@ -452,7 +477,7 @@ def main():
             n_warm += nfl
             torch.cuda.synchronize()
         warm_s = time.perf_counter() - t_w
-        clk_before = gpu_clock_power(local_rank, my_pci) if rank == 0 else None
+        clk_before = gpu_clock_power(local_rank, my_pci) if probe_clocks else None
         blocks = []      # (dt, dt_host, sorted completion times)
         for _ in range(n_blocks):
             barrier()
@@ -468,7 +493,9 @@ def main():
             torch.cuda.synchronize()
             dt_b = time.perf_counter() - t0
             blocks.append((dt_b, dt_host_b, sorted(ev0.elapsed_time(e) for e in step_done)))    # numbers only: no block's tensors are retained
-    clk_after = gpu_clock_power(local_rank, my_pci) if rank == 0 else None
+    clk_after = gpu_clock_power(local_rank, my_pci) if probe_clocks else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     # MAX over ranks per block, then the median block (by the all-rank time, so that every rank picks the same one)
     blk_t = torch.tensor([b_[0] for b_ in blocks], device=dev, dtype=torch.float64)
     if multi:
@@ -515,7 +542,7 @@ def main():
     # secondary figure (never `value`): the same K steps with LS_FLAG_CONTRACT_FMA, i.e. dist = fmaf(diff, diff, dist) as nvcc
     # compiles pytorch3d's knn.cu -- the rounding the reference's CUDA deployment runs with
     dt_fma = None
-    if not args.no_fma_variant:
+    if args.full and not args.no_fma_variant:
         for s_ in sps:
             s_.knn_flags = 1
         with torch.no_grad():
@@ -536,36 +563,45 @@ def main():
 
     # the un-profiled ONE-step-in-flight time (single stream, handle 0; the library's own side streams stay on): median of 3 x 20 steps.
     # Beside ms_per_step it says how much of the figure is the overlap of whole steps and how much is the single step.
-    one_ms = []
-    with torch.no_grad():
-        for _ in range(3):
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            with torch.cuda.stream(streams[0]):
-                for _i in range(20):
-                    step(sps[0])
-            torch.cuda.synchronize()
-            one_ms.append((time.perf_counter() - t1) / 20 * 1e3)
-    one_in_flight_ms = sorted(one_ms)[1]
+    one_in_flight_ms = None
+    if args.full:
+        one_ms = []
+        with torch.no_grad():
+            for _ in range(3):
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                with torch.cuda.stream(streams[0]):
+                    for _i in range(20):
+                        step(sps[0])
+                torch.cuda.synchronize()
+                one_ms.append((time.perf_counter() - t1) / 20 * 1e3)
+        one_in_flight_ms = sorted(one_ms)[1]
 
     emb, m, R, t = out
-    # every handle of the timed region saw the same batch: their last results must agree BIT FOR BIT (reproducibility with all the
-    # streams in flight); checked outside the timed region on every handle that ran
-    def same(a, b):
-        return all(torch.equal(a[0][k], b[0][k]) for k in ("z_so3", "z_inv", "s", "t")) and torch.equal(a[1]["matches0"], b[1]["matches0"]) \
-            and torch.equal(a[2], b[2]) and torch.equal(a[3], b[3])
-    ran = [r for r in last_main if r is not None]
-    handles_identical = all(same(ran[0], r) for r in ran[1:])
-    # sanity of the measured work (outside the timed region): matches are the identity permutation, poses are rotations
-    n_correct = int((m["matches0"].cpu() == torch.arange(n_obj)).sum())
-    det_ok = bool((torch.det(R.cpu()) > 0.99).all())
-    if multi:  # RCCL all-gather of the per-rank codes (4.1 KB each: latency-bound; outside the timed region)
-        allc = parallel.all_gather_codes(emb)
-        assert allc["z_inv"].shape[0] == B * world
+    check = None
+    if args.full:
+        # every handle of the timed region saw the same batch: their last results must agree BIT FOR BIT (reproducibility with all the
+        # streams in flight); checked outside the timed region on every handle that ran
+        def same(a, b):
+            return all(torch.equal(a[0][k], b[0][k]) for k in ("z_so3", "z_inv", "s", "t")) and torch.equal(a[1]["matches0"], b[1]["matches0"]) \
+                and torch.equal(a[2], b[2]) and torch.equal(a[3], b[3])
+        ran = [r for r in last_main if r is not None]
+        handles_identical = all(same(ran[0], r) for r in ran[1:])
+        # sanity of the measured work (outside the timed region): matches are the identity permutation, poses are rotations
+        n_correct = int((m["matches0"].cpu() == torch.arange(n_obj)).sum())
+        det_ok = bool((torch.det(R.cpu()) > 0.99).all())
+        if multi:  # RCCL all-gather of the per-rank codes (4.1 KB each: latency-bound; outside the timed region)
+            allc = parallel.all_gather_codes(emb)
+            assert allc["z_inv"].shape[0] == B * world
+        check = {"oracle_relerr": None, "rotations_proper": det_ok, "matches_identity": f"{n_correct}/{n_obj}",
+                 "handles_bit_identical": f"{handles_identical} ({len(ran)} handles, last step of each)",
+                 "note": "oracle_relerr: max-norm relative error of the timed codes against the CPU oracle on instances spread over the batch "
+                         "(tests/test_hip_fullbatch.py checks the same batch in pytest); weights are untrained, so the matcher is not expected "
+                         "to recover the identity permutation"}
 
     roof = None
     bf16x3 = os.environ.get("LS_GEMM_MODE") != "fp32"      # (False: exact fp32 MFMA chains, LS_GEMM_MODE=fp32)
-    if rank == 0 and not args.no_profile:
+    if rank == 0 and args.full and not args.no_profile:
         hip = sp.hip_model()
         prof_steps = min(args.steps, 24)      # per-launch hipEvent pairs: a bounded, serial pass on one stream
         hip.profile_begin()
@@ -676,8 +712,7 @@ def main():
                     "fewer instructions can shorten"}
 
     cpu = None
-    oracle_check = None
-    if rank == 0 and world == 1 and args.cpu_instances > 0:
+    if rank == 0 and world == 1 and args.full and args.cpu_instances > 0:
         from oracle import more, net  # the checker, timed as the CPU baseline ("port" of the reference's op sequence)
         import statistics
         nb = args.cpu_instances
@@ -715,6 +750,7 @@ def main():
         oracle_check["ok"] = all(v < 1e-4 for k, v in oracle_check.items() if k in ("z_so3", "z_inv", "s", "t"))
         ref_m = more.sequential_matcher(emb["z_inv"][:n_obj].cpu(), emb["z_inv"][n_obj:].cpu())
         oracle_check["matches_bit_exact_vs_oracle_on_hip_codes"] = bool(torch.equal(ref_m["matches0"], m["matches0"].cpu()))
+        check["oracle_relerr"] = oracle_check
 
     line = None
     if rank == 0:
@@ -746,15 +782,11 @@ def main():
                        "steps_in_flight": nfl, "protocol": f"median of {n_blocks} back-to-back blocks of {args.steps} steps (each: barrier + synchronize, K steps, "
                                                             f"synchronize + barrier; MAX over ranks per block) after {n_warm} warm-up steps / {warm_s:.2f} s",
                        **block_stats, **{"median_block_" + k: v for k, v in step_stats.items()},
-                       "ms_per_step_one_in_flight_unprofiled": round(one_in_flight_ms, 4),
+                       "ms_per_step_one_in_flight_unprofiled": None if one_in_flight_ms is None else round(one_in_flight_ms, 4),
                        "host_enqueue_ms_per_step": round(max([p_["host_enqueue_ms_per_step"] for p_ in per_rank] if per_rank else [dt_host / args.steps * 1e3]), 3),
                        "host_enqueue_basis": "max over ranks" if per_rank else "this rank", "hip_hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
                        "knn_arithmetic": "canonical (separately rounded mul/add)"},
-            "check": {"oracle_relerr": oracle_check, "rotations_proper": det_ok, "matches_identity": f"{n_correct}/{n_obj}",
-                      "handles_bit_identical": f"{handles_identical} ({len(ran)} handles, last step of each)",
-                      "note": "oracle_relerr: max-norm relative error of the timed codes against the CPU oracle on instances spread over the batch "
-                              "(tests/test_hip_fullbatch.py checks the same batch in pytest); weights are untrained, so the matcher is not expected "
-                              "to recover the identity permutation"},
+            "check": check,
             "step_stats": step_stats,
             "per_rank": per_rank,
             "variants": None if dt_fma is None else {

@@ -10,7 +10,7 @@ val() { python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitl
 echo "== release: attention kernel alone (us per launch, B = 64)"; python scripts/dev/attn_layers.py --modes 0 --reps 9 2>&1 | grep "^mode"
 echo "== fq_half (dir gathers dropped): attention kernel alone"; LS_LIB_PATH=$V/fq_half/liblivingscenes_hip.so python scripts/dev/attn_layers.py --modes 0 --reps 9 2>&1 | grep "^mode"
 for rep in 1 2; do
-echo -n "release steady 480 x3: "; python bench.py --no-profile --cpu-instances 0 --no-fma-variant 2>/dev/null | val
-echo -n "fq_half steady 480 x3: "; LS_LIB_PATH=$V/fq_half/liblivingscenes_hip.so python bench.py --no-profile --cpu-instances 0 --no-fma-variant 2>/dev/null | val
+echo -n "release steady 480 x3: "; python bench.py --full --no-profile --cpu-instances 0 --no-fma-variant 2>/dev/null | val
+echo -n "fq_half steady 480 x3: "; LS_LIB_PATH=$V/fq_half/liblivingscenes_hip.so python bench.py --full --no-profile --cpu-instances 0 --no-fma-variant 2>/dev/null | val
 done
 } 2>&1 | tee gpurun_out/r6/attn_halfwidth_ab.txt

@@ -1,10 +1,11 @@
 #!/bin/bash
 # dev (round 6): the driver's command and the in-flight depth on the 20-step protocol, block statistics per run.
-#   scripts/dev/bench_protocol.sh <tag> [depths...]      -> gpurun_out/r6/<tag>_*.json + one summary line per run
+#   scripts/dev/bench_protocol.sh <tag> [depths...]      -> ${LS_BENCH_OUT:-bench_out}/r6/<tag>_*.json + one summary line per run
 cd "${GRAFT_REPO_ROOT:-.}"
 tag=${1:-p}; shift
 depths=${@:-"8 12"}
-mkdir -p gpurun_out/r6
+out=${LS_BENCH_OUT:-bench_out}/r6
+mkdir -p $out
 sum() { python - "$1" "$2" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1]); c = d["config"]
@@ -14,11 +15,11 @@ print(sys.argv[1], "value", round(d["value"]), "ms/step", round(d["ms_per_step"]
 PY
 }
 # 1. the driver's exact command, first thing on the fresh box (cold image, cold clocks)
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/r6/${tag}_driver.json 2> gpurun_out/r6/${tag}_driver.err
-sum "${tag} driver-cmd" gpurun_out/r6/${tag}_driver.json
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/${tag}_driver.json 2> $out/${tag}_driver.err
+sum "${tag} driver-cmd" $out/${tag}_driver.json
 for rep in 1 2; do
   for d in $depths; do
-    python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-profile --cpu-instances 0 --no-fma-variant --inflight $d > gpurun_out/r6/${tag}_d${d}_${rep}.json 2>/dev/null
-    sum "${tag} depth=$d rep=$rep" gpurun_out/r6/${tag}_d${d}_${rep}.json
+    python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-profile --cpu-instances 0 --no-fma-variant --inflight $d > $out/${tag}_d${d}_${rep}.json 2>/dev/null
+    sum "${tag} depth=$d rep=$rep" $out/${tag}_d${d}_${rep}.json
   done
 done

@@ -1,7 +1,7 @@
 """Timing variants of liblivingscenes_hip.so (dev tool): gemm.hip rebuilt with -D<flags>, every other object reused.
 
     python scripts/dev/build_variants.py NAME[:file.hip[+file2.hip]]=-DFLAG[,-DFLAG2] ...   ->  livingscenes_amd/lib/variants/NAME/liblivingscenes_hip.so
-    LS_LIB_PATH=livingscenes_amd/lib/variants/NAME/liblivingscenes_hip.so python bench.py ...
+    LS_LIB_PATH=livingscenes_amd/lib/variants/NAME/liblivingscenes_hip.so python bench.py --full ...
 
 The variants compute WRONG results where a flag removes arithmetic; they exist to price one part of a kernel."""
 import os

@@ -5,9 +5,9 @@ cd "${GRAFT_REPO_ROOT:-.}"
 tag=${1:-r6_final}
 out=$PWD/gpurun_out/$tag
 mkdir -p $out
-python3 bench.py --gpus 1 --steps 20 --warmup 5 2>$out/driver.err | tail -1 > $out/bench_line_driver_protocol.json
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 2>$out/driver.err | tail -1 > $out/bench_line_driver_protocol.json
 bash scripts/bench_profile.sh $tag > $out/bench_profile.log 2>&1
-python bench.py --inflight 1 --steps 100 --cpu-instances 0 --no-fma-variant 2>/dev/null | tail -1 > $out/bench_line_one_in_flight.json
+python bench.py --full --inflight 1 --steps 100 --cpu-instances 0 --no-fma-variant 2>/dev/null | tail -1 > $out/bench_line_one_in_flight.json
 bash scripts/pmc_collect.sh $tag > $out/pmc_collect.log 2>&1
 for f in bench_line_driver_protocol bench_line bench_line_one_in_flight; do python - $out/$f.json <<'PY'
 import json, sys

@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-.}"; R=$PWD; mkdir -p gpurun_out
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/l2p
-timeout 600 rocprofv3 --pmc TCC_REQ_sum TCC_HIT_sum TCC_MISS_sum --kernel-trace -d /tmp/l2p -o p --output-format csv -- python $R/bench.py --inflight 1 --steps 8 --warmup 2 --no-profile --cpu-instances 0 --no-fma-variant > /tmp/l2p.log 2>&1 || tail -5 /tmp/l2p.log
+timeout 600 rocprofv3 --pmc TCC_REQ_sum TCC_HIT_sum TCC_MISS_sum --kernel-trace -d /tmp/l2p -o p --output-format csv -- python $R/bench.py --full --inflight 1 --steps 8 --warmup 2 --no-profile --cpu-instances 0 --no-fma-variant > /tmp/l2p.log 2>&1 || tail -5 /tmp/l2p.log
 f=$(find /tmp/l2p -name "*counter_collection.csv" | head -1)
 python - "$f" > $R/gpurun_out/l2_requests.txt <<'PY'
 import csv, sys, collections

@@ -10,9 +10,9 @@ val() { python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitl
 one() {   # tag, library ("" = release)
   [ -n "$2" ] && export LS_LIB_PATH=$V/$2/liblivingscenes_hip.so || unset LS_LIB_PATH
   echo "== $1"
-  echo -n "  steady 480 x3: "; python bench.py --no-profile --cpu-instances 0 --no-fma-variant 2>/dev/null | val
-  echo -n "  driver 20 x9:  "; python bench.py --steps 20 --warmup 5 --no-profile --cpu-instances 0 --no-fma-variant 2>/dev/null | val
-  echo -n "  one in flight: "; python bench.py --steps 100 --no-profile --cpu-instances 0 --no-fma-variant --inflight 1 2>/dev/null | val
+  echo -n "  steady 480 x3: "; python bench.py --full --no-profile --cpu-instances 0 --no-fma-variant 2>/dev/null | val
+  echo -n "  driver 20 x9:  "; python bench.py --full --steps 20 --warmup 5 --no-profile --cpu-instances 0 --no-fma-variant 2>/dev/null | val
+  echo -n "  one in flight: "; python bench.py --full --steps 100 --no-profile --cpu-instances 0 --no-fma-variant --inflight 1 2>/dev/null | val
   echo -n "  identity:      "; timeout 300 python scripts/dev/identity_loop.py 100 2>&1 | tail -1
 }
 {

@@ -1,12 +1,13 @@
 #!/bin/bash
 # dev: rocprofv3 --kernel-trace --stats of a short bench run (one step in flight unless told otherwise), the top kernels printed.
 # usage: scripts/dev/prof_kernels.sh <tag> [pattern] [bench args...]      -> gpurun_out/<tag>/kernel_stats_top.txt
+REPO=$(cd "$(dirname "$0")/../.." && pwd)
 tag=${1:-prof}; pat=${2:-.}; shift; shift
 out=$PWD/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-timeout 420 rocprofv3 --kernel-trace --stats -d $out/prof -o p --output-format csv -- python $GRAFT_REPO_ROOT/bench.py --steps 40 --warmup 8 --no-profile --cpu-instances 0 --no-fma-variant "$@" > $out/under_rocprof.log 2>&1 || tail -5 $out/under_rocprof.log
-cd $GRAFT_REPO_ROOT
+timeout 420 rocprofv3 --kernel-trace --stats -d $out/prof -o p --output-format csv -- python $REPO/bench.py --full --steps 40 --warmup 8 --no-profile --cpu-instances 0 --no-fma-variant "$@" > $out/under_rocprof.log 2>&1 || tail -5 $out/under_rocprof.log
+cd $REPO
 f=$(find $out/prof -name "*kernel_stats.csv" | head -1)
 [ -z "$f" ] && { echo "no kernel_stats.csv"; exit 1; }
 cp $f $out/kernel_stats.csv

@@ -4,7 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-.}"
 mkdir -p gpurun_out/r6
 line() { python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); c=d['config']; print('$1: value', round(d['value']), 'blocks_ms', c['blocks_ms'], 'max/min', c['block_max_over_min'])"; }
-B="python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-profile --cpu-instances 0 --no-fma-variant --blocks 40"
+B="python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-profile --cpu-instances 0 --no-fma-variant --blocks 40"
 {
 $B 2>/dev/null | line "quiet"
 ( while true; do rocm-smi --showuse --showmemuse --showpower --showclocks --showtemp --json > /dev/null 2>&1; done ) &

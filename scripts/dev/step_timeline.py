@@ -1,6 +1,6 @@
 """Timeline of ONE encode step from a rocprofv3 kernel trace of `bench.py --inflight 1`: every kernel in start order with its duration and
 the idle gap since the previous kernel ended on the device (all streams merged) -- where a single step's 2 ms go.
-   cd /tmp; rocprofv3 --kernel-trace -d /tmp/tl -o x --output-format csv -- python $REPO/bench.py --inflight 1 --steps 24 --warmup 12 --no-profile --cpu-instances 0 --no-fma-variant
+   cd /tmp; rocprofv3 --kernel-trace -d /tmp/tl -o x --output-format csv -- python $REPO/bench.py --full --inflight 1 --steps 24 --warmup 12 --no-profile --cpu-instances 0 --no-fma-variant
    python scripts/dev/step_timeline.py /tmp/tl [step_index]"""
 import csv, glob, sys
 root = sys.argv[1]

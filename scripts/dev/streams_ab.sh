@@ -6,8 +6,8 @@ mkdir -p gpurun_out/r6
 val() { python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d['value']), round(d['ms_per_step'],4))"; }
 run() {  # label, env..., -- bench args
   label=$1; shift
-  echo -n "$label steady: "; env "$@" python bench.py --no-profile --cpu-instances 0 --no-fma-variant $ARGS 2>/dev/null | val
-  echo -n "$label 20-step: "; env "$@" python bench.py --steps 20 --warmup 5 --no-profile --cpu-instances 0 --no-fma-variant $ARGS 2>/dev/null | val
+  echo -n "$label steady: "; env "$@" python bench.py --full --no-profile --cpu-instances 0 --no-fma-variant $ARGS 2>/dev/null | val
+  echo -n "$label 20-step: "; env "$@" python bench.py --full --steps 20 --warmup 5 --no-profile --cpu-instances 0 --no-fma-variant $ARGS 2>/dev/null | val
 }
 {
 for d in 12 16; do

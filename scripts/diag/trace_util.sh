@@ -1,7 +1,8 @@
 #!/bin/bash
 # GPU busy fraction / concurrency of the bench's timed region from a rocprofv3 kernel trace
+REPO=$(cd "$(dirname "$0")/../.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace -d /tmp/tr -o p --output-format csv -- python $GRAFT_REPO_ROOT/bench.py --steps 240 --warmup 24 --cpu-instances 0 --no-profile --no-fma-variant > /tmp/bench_tr.json 2>/dev/null
+rocprofv3 --kernel-trace -d /tmp/tr -o p --output-format csv -- python $REPO/bench.py --full --steps 240 --warmup 24 --cpu-instances 0 --no-profile --no-fma-variant > /tmp/bench_tr.json 2>/dev/null
 python - <<'PY'
 import csv,glob,json
 f=glob.glob("/tmp/tr/**/*kernel_trace.csv",recursive=True)[0]

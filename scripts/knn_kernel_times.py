@@ -1,5 +1,5 @@
 """Per-kernel, per-grid-size average durations of the k-NN launches in a rocprofv3 kernel trace of bench.py.
-Usage (GPU box): cd /tmp; rocprofv3 --kernel-trace -d /tmp/pb -o x --output-format csv -- python $REPO/bench.py --steps 48 ...
+Usage (GPU box): cd /tmp; rocprofv3 --kernel-trace -d /tmp/pb -o x --output-format csv -- python $REPO/bench.py --full --steps 48 ...
                  python $REPO/scripts/knn_kernel_times.py /tmp/pb [substring ...]"""
 import collections, csv, glob, sys
 root = sys.argv[1]

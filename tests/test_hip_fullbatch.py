@@ -209,7 +209,7 @@ def test_bench_gpus_2_runs_two_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(LS_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    (line,) = _run_json([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--no-profile",
+    (line,) = _run_json([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--full", "--no-profile",
                          "--cpu-instances", "0", "--no-fma-variant", "--inflight", "2"], env)
     assert line["n_gpus"] == 2 and line["ranks"] == 2 and line["steps"] == 4
     assert [r["rank"] for r in line["per_rank"]] == [0, 1] and all(r["objects"] == 64 * 4 for r in line["per_rank"])
@@ -231,6 +231,31 @@ def test_bench_gpus_2_runs_two_ranks():
     (one,) = _run_json([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--no-profile",
                         "--cpu-instances", "0", "--no-fma-variant", "--inflight", "2"], env1)
     assert one["n_gpus"] == 1 and one["rccl_ranks"] == 1 and one["collective_backend"] == "rccl" and len(one["per_rank"]) == 1
+
+
+def test_bench_plain_run_times_steps_and_dumps_outputs(fullbatch, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K` times exactly K steps in one block and runs none of the --full legs; --dump-outputs writes what
+    the last timed step returned, and on the bench batch that is what the full-batch worker computed: codes and matches bit for bit, poses
+    within TOL (the worker registers through kabsch_transformation_estimation, the bench through the fused ls_kabsch_codes_f32)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dump = tmp_path / "dump"
+    (line,) = _run_json([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+                         "--dump-outputs", str(dump)], env)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert line[k] is not None, k
+    assert line["steps"] == 4 and line["config"]["blocks"] == 1 and len(line["config"]["blocks_ms"]) == 1
+    assert abs(line["value"] - 64 * 4 / (line["ms_per_step"] * 4e-3)) < 1e-6 * line["value"]
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["variants"] is None and line["check"] is None
+    got = {p.stem: np.load(p) for p in dump.glob("*.npy")}
+    assert set(got) == {"encode_z_so3", "encode_z_inv", "encode_s", "encode_t", "match_matches0", "match_matches1", "register_R", "register_t"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values()) and sum(a.nbytes for a in got.values()) < 64 << 20
+    r = fullbatch
+    for k in ("z_so3", "z_inv", "s", "t"):
+        assert np.array_equal(got["encode_" + k], r["h0_" + k].astype(np.float32)), k
+    assert np.array_equal(got["match_matches0"], r["h0_m0"].astype(np.float64))
+    assert np.array_equal(got["match_matches1"], r["h0_m1"].astype(np.float64))
+    assert relerr(got["register_R"], r["h0_pose_R"]) < TOL
+    assert relerr(got["register_t"].reshape(-1), r["h0_pose_t"].reshape(-1)) < TOL
 
 
 def test_configs_sharded_gpus_2_runs_two_ranks():
