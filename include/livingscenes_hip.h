@@ -57,10 +57,11 @@ typedef enum {
 #define LS_MAX_LAYERS 8
 
 /* version of this C ABI: bumped whenever a signature or struct layout changes incompatibly (101: double-precision Adam hyper-parameters in
- * ls_adam_group / ls_adam_step_f32 / ls_se3_adam_step_f32, LS_OPT_EDGE_STAGED; 102: LS_OPT_EDGE_FUSE_Q / _T, LS_OPT_GLOB_FUSE, LS_OPT_DEBUG_EDGE; the
- * library reads no development switches from the environment any more).  ls_version() returns the value the LIBRARY was built with; a
+ * ls_adam_group / ls_adam_step_f32 / ls_se3_adam_step_f32, option 4 (LDS-staged attention); 102: LS_OPT_EDGE_FUSE_Q / _T, LS_OPT_GLOB_FUSE, LS_OPT_DEBUG_EDGE; the
+ * library reads no development switches from the environment any more; 104: option 4 retired with the staged attention path, refused like
+ * any unknown option).  ls_version() returns the value the LIBRARY was built with; a
  * binding compares it with the header it was written against and refuses a mismatch (livingscenes_amd/_lib.py: load). */
-#define LS_ABI_VERSION 103
+#define LS_ABI_VERSION 104
 int ls_version(void);
 const char* ls_last_error(void);
 /* number of HIP devices visible, or a negative ls_status */
@@ -115,8 +116,7 @@ int ls_fps_f32(const float* pts, const int32_t* lengths, int B, int N, int K, un
  * the call -- as long as the launch does not split K (split-K: M * N < 192 tiles of 128 x 128 and K >= 128 and a workspace is given;
  * it changes the fp32 summation order with M; ls_gemm_f32_ex with workspace = NULL never splits).
  * LS_GEMM_MODE=bf16x3 in the environment selects three-piece bf16 splits instead (six v_mfma_f32_32x32x16_bf16 per 16 k, ~1.5x the
- * time); LS_GEMM_BF16X3=0 the fp32-MFMA kernel (v_mfma_f32_32x32x2_f32, exact fp32 FMA chains); LS_GEMM_RANGE=0 the split
- * without the row scaling (A/B TIMING only: |a|, |w| < 65 504 required, operands below ~0.1 lose bits).
+ * time); LS_GEMM_MODE=fp32 the fp32-MFMA kernel (v_mfma_f32_32x32x2_f32, exact fp32 FMA chains).
  * K % 4 == 0, lda/ldw/ldc % 4 == 0; bias may be NULL; relu in {0,1}.  workspace: ls_gemm_workspace_bytes(M, N, K) bytes
  * (split-K slabs of under-filled long-K problems; 0 -> may be NULL). */
 size_t ls_gemm_workspace_bytes(int M, int N, int K);
@@ -255,10 +255,6 @@ void ls_model_destroy(ls_model_t* m);
 #define LS_OPT_ENCODE_GRAPH 3     /* [0, or LS_ENCODE_GRAPH in the environment] ls_encode replays a captured hipGraph of its ~170 launches (one per
                                      (workspace, B, N, flags, stream); needs a non-NULL stream; profiled / traced calls always enqueue directly).
                                      Off by default: on ROCm 7.2 the replay measured slower than direct enqueue (22.2k vs 29.6k obj/s, one step in flight) */
-#define LS_OPT_EDGE_STAGED 4      /* [0, or LS_EDGE_STAGED in the environment] attention layers 2 - 4 (vec_dgcnn_atten.py:205-219) with LDS-staged neighbour tiles
-                                     (edge_staged.hip): 0 = never (row gathers through L1: edge_attn_fq_kernel), 1 = when one workgroup per CU fills the chip
-                                     (B * Nd / 128 >= 128), 2 = whenever the layer shape fits.  The two kernels agree to ~1e-6 of the tensor maximum.  Off by
-                                     default: measured at B = 64 (round 5) 132 / 104 / 105 us against 96 / 107 / 82 us at layers 2 / 3 / 4 */
 #define LS_OPT_EDGE_FUSE_Q 5      /* [1] attention layers 2 - 4: the destination-side column groups computed inside the edge kernel (edge.hip: edge_attn_fq_kernel);
                                      0 = as table columns written by the table GEMM (the general path; also taken under LS_GEMM_MODE=bf16x3 / fp32) */
 #define LS_OPT_EDGE_FUSE_T 6      /* [1] the 32-point attention layers (released layers 5, 6) without a table (edge_fused.hip); 0 = table GEMM + edge kernel */

@@ -628,14 +628,6 @@ int edge_presplit_wq_launch(const float* Wq, int Co, int Cin, void* planes, hipS
     return LS_OK;
 }
 
-// Timing probe (round 6; WRONG results, dev builds only): -DLS_FQ_HALF_GATHER drops the gathers of the two `dir` column groups (the
-// neighbour's `lin` values stand in) -- the upper bound of what a half-width table could buy BEFORE paying for the per-edge C x C product that would have
-// to recompute the directions (profiles/r6_final/attn_halfwidth_ab.txt).
-#ifdef LS_FQ_HALF_GATHER
-#define LS_FQ_DIR(off, col, lin) (lin)
-#else
-#define LS_FQ_DIR(off, col, lin) ldrow(off, col)
-#endif
 template <int LPP, int CIN>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void edge_attn_fq_kernel(const float* __restrict__ T, int ldt, const float* __restrict__ cur,
                                                            const uint4* __restrict__ Wp, const int32_t* __restrict__ knn,
@@ -666,9 +658,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void e
 
     uint4 wfh[2][KS], wfl[2][KS];
     auto qload = [&](int cb) {
-#ifdef LS_FQ_SKIP_QGEMM      // timing probe (WRONG results): the three destination-side products skipped
-        return;
-#endif
         const uint4* wt = Wp + (size_t)(cb / 32) * KS * 128 + lane;
 #pragma unroll
         for (int u = 0; u < (MT == 2 ? 1 : 2); ++u) {      // (MT == 2: both M-tiles of a wave meet the same weight tile)
@@ -708,16 +697,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void e
     __syncthreads();
 
     // ---- destination-side product for one phase: slab[row][0 .. 2 Co) = x_rows . Wq[cb .. cb + 2 Co)^T
-    // Round 6: the three products cost 15 / 27 / 44 us of a 99 / 108 / 82 us launch (probe: -DLS_FQ_SKIP_QGEMM, profiles/r6_final/attn_qgemm_ab.txt) although
+    // Round 6: the three products cost 15 / 27 / 44 us of a 99 / 108 / 82 us launch (a probe that skipped them: profiles/r6_final/attn_qgemm_ab.txt) although
     // they are 72 MFMAs per wave: hipcc issued the weight-fragment loads of a phase two at a time with an s_waitcnt behind each pair -- four to five
     // DEPENDENT L2 round trips per phase with every wave of the workgroup waiting.  Now a phase's fragments (2 tiles x KS steps x (hi, lo) x 16 bytes per lane:
     // 32 - 64 registers, at a point where nothing else is live) are requested in ONE batch (qload), the MFMAs run behind a scheduling barrier (qmma), and the
     // caller puts independent work between the two: the row staging in front of the q product, the q activation in front of the k product, the soft-max in
     // front of the v product.  Same operands, same MFMA order: bit-identical.
     auto qmma = [&](int cb) {
-#ifdef LS_FQ_SKIP_QGEMM
-        return;
-#endif
         __builtin_amdgcn_sched_barrier(0);      // (the loads above stay above: left free, the scheduler sinks each pair to its first use again)
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -820,12 +806,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void e
         constexpr int DP = 2;
         F43 py[DP], pd[DP];
 #pragma unroll
-        for (int d = 0; d < DP; ++d) { const unsigned o = noff(d); py[d] = ldrow(o, 2 * Co); pd[d] = LS_FQ_DIR(o, 3 * Co, py[d]); }
+        for (int d = 0; d < DP; ++d) { const unsigned o = noff(d); py[d] = ldrow(o, 2 * Co); pd[d] = ldrow(o, 3 * Co); }
         const F43 ql = lds43(0), qd = lds43(Co);
 #pragma unroll
         for (int k = 0; k < EK; ++k) {
             F43 y = py[k % DP], kd = pd[k % DP];
-            if (k + DP < EK) { const unsigned o = noff(k + DP); py[k % DP] = ldrow(o, 2 * Co); pd[k % DP] = LS_FQ_DIR(o, 3 * Co, py[k % DP]); }
+            if (k + DP < EK) { const unsigned o = noff(k + DP); py[k % DP] = ldrow(o, 2 * Co); pd[k % DP] = ldrow(o, 3 * Co); }
             __builtin_amdgcn_sched_barrier(0);   // keep the prefetch ahead of this neighbour's arithmetic (the scheduler would sink it to its first use)
             y = add43(y, ql);
             kd = add43(kd, qd);
@@ -861,11 +847,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void e
         constexpr int DP = 2;
         F43 py[DP], pd[DP];
 #pragma unroll
-        for (int d = 0; d < DP; ++d) { const unsigned o = noff(d); py[d] = ldrow(o, 0); pd[d] = LS_FQ_DIR(o, Co, py[d]); }
+        for (int d = 0; d < DP; ++d) { const unsigned o = noff(d); py[d] = ldrow(o, 0); pd[d] = ldrow(o, Co); }
 #pragma unroll
         for (int k = 0; k < EK; ++k) {
             F43 y = py[k % DP], kd = pd[k % DP];
-            if (k + DP < EK) { const unsigned o = noff(k + DP); py[k % DP] = ldrow(o, 0); pd[k % DP] = LS_FQ_DIR(o, Co, py[k % DP]); }
+            if (k + DP < EK) { const unsigned o = noff(k + DP); py[k % DP] = ldrow(o, 0); pd[k % DP] = ldrow(o, Co); }
             __builtin_amdgcn_sched_barrier(0);
             y = add43(y, ql);
             kd = add43(kd, qd);
@@ -939,9 +925,8 @@ int edge_l0_launch(const float* pts, const int32_t* knn, const float* w0, int B,
 int edge_pool_launch(const float* T, int ldt, const float* Tq, int ldq, int NQ, int qvr, const int32_t* knn,
                      const int32_t* dst_rows, int B, int Nd, int Ns, int Co, float neg_slope, float* out, hipStream_t st) {
     const int total = B * Nd;
-    static const bool scalar_pool = dev_knob("LS_EDGE_POOL_SCALAR", 0) != 0;   // dev A/B: the one-channel-per-lane kernel (bit-identical)
     const bool off32 = edge_attn_fq_fits(B, Ns, ldt);
-    if (!scalar_pool && off32 && ldt % 4 == 0 && ldq % 4 == 0 && (Co == 32 || Co == 64)) {   // (the float4 kernel addresses the table by 32-bit byte offsets)
+    if (off32 && ldt % 4 == 0 && ldq % 4 == 0 && (Co == 32 || Co == 64)) {   // (the float4 kernel addresses the table by 32-bit byte offsets)
         if (Co == 32)
             hipLaunchKernelGGL((edge_pool_v4_kernel<8>), dim3(cdiv(total, 32)), dim3(256), 0, st, T, ldt, Tq, ldq, NQ, qvr, knn, dst_rows, Nd, Ns, 1.0f - neg_slope, out, total);
         else

@@ -204,16 +204,13 @@ struct FtJob { const uint4* a_planes; const int* a_exp; int mt0; int MT; int p; 
 //  batch, fence, then consume it; a run-time-trip-count loop of dependent global loads serialises.)
 // The GEMM phase: THREE M-tiles per unit of work and nothing resident.  Why: the first form kept a W tile in registers (128 VGPRs at
 // K = 256) -- 242 - 254 VGPRs per wave, i.e. the two workgroups of a CU own its whole register file while their waves sit through ~13 sequential L2
-// round trips per q / k phase pair, and LS_SKIP=hi32 shows that these layers cost 0.165 ms of the 1.21 ms step in steady state: nothing can be
+// round trips per q / k phase pair, and a marginal-cost run showed that these layers cost 0.165 ms of the 1.21 ms step in steady state: nothing can be
 // resident beside them.  Here a unit = (job, head, three consecutive M-tiles = the 96 feature rows of 32 points): three independent accumulators,
 // and per batch of two k-steps 12 A fragments + 4 W fragments (64 VGPRs) are requested, awaited and consumed by 18 MFMAs.  Same products in the same
 // order per accumulator (ascending k: l_a h_w, h_a h_w, h_a l_w) => bit-identical slabs; the W tile is streamed once per unit, as before once per
 // (job, head); ~120 VGPRs.  Every job's M-tile count is a multiple of three by construction (96 or 384 rows).
 // (Order: the operand images are read-only no-alias memory and the loop stores nothing, so only data dependencies keep hipcc from hoisting all sixteen
 //  batches' loads to the top -- the batch's lane offset passes through a volatile asm, and so do the accumulators after its MFMAs: edge.hip, pool kernel.)
-#ifndef LS_FT_KB
-#define LS_FT_KB 2
-#endif
 // one unit of work: MPU consecutive M-tiles (first: tile `tile0` of the job) x one weight tile -> the job's slab
 template <int KS, int MPU>
 __device__ __forceinline__ void ft_gemm_unit(const FtJob<KS>& jb, int tile0, int hl, int T, const uint4* __restrict__ wplanes, const int* __restrict__ wexp, int lane) {
@@ -226,7 +223,7 @@ __device__ __forceinline__ void ft_gemm_unit(const FtJob<KS>& jb, int tile0, int
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
     unsigned voff = (unsigned)lane * 16u;
-    constexpr int KB = LS_FT_KB;   // k-steps per batch
+    constexpr int KB = 2;   // k-steps per batch
     struct Stage { fh8_t ah[MPU][KB], al[MPU][KB], bh[KB], bl[KB]; };
     auto load_stage = [&](Stage& sg, int k0) {
         asm volatile("" : "+v"(voff));
@@ -312,9 +309,8 @@ __device__ __forceinline__ void ft_gemm_phase_g3(const FtJob<KS> (&jobs)[NJ], co
 // the L1 does not merge the four waves' misses, so the layer-6 kernels ask the L2 for 8.4 M requests per step, 8 % of everything it serves (profiles/r5_final/
 // l2_requests_per_kernel.txt).  Here the four waves fetch a quarter of the batch each (three fragments) into a double-buffered 24 KB ring, one barrier per batch; the W
 // fragments stay per wave.  Same products in the same order per accumulator: bit-identical slabs.  (All four waves run the loop -- a wave without a unit only feeds the ring.)
-#ifndef LS_FT_SHARE
-#define LS_FT_SHARE 1      // (0: every wave streams its own A copy -- dev A/B: attention layer 6 101 -> 97 us one step in flight, bench +0.1 .. +1.4 % on the same box, L2 requests of the layer-6 kernels -50 %)
-#endif
+// (Measured against every wave streaming its own A copy: attention layer 6 101 -> 97 us one step in flight, bench +0.1 .. +1.4 %, L2 requests of the
+// layer-6 kernels -50 %.)
 template <int KS, int HG, int NJ>
 __device__ __forceinline__ void ft_gemm_phase_shared(const FtJob<KS> (&jobs)[NJ], const uint4* __restrict__ wplanes, const int* __restrict__ wexp, int head0,
                                                      int wave, int lane, uint4* ring) {
@@ -401,7 +397,6 @@ __device__ __forceinline__ void ft_gemm_phase_shared(const FtJob<KS> (&jobs)[NJ]
         }
     }
 }
-#define LS_FT_PHASE ft_gemm_phase_g3
 
 // thread -> (point, head-local, quad lane, neighbour range) of the attention phases: 256 threads = 32 points x HG heads x 4 lanes x (2 / HG) neighbour halves
 template <int HG>
@@ -417,29 +412,29 @@ struct FtMap {
 };
 
 // ---------------------------------------------------------------------------------------------------------------- kernel 1: q and k
-// grid = (Co / 16 / HG) x B workgroups, instance major by default (edge_ft_attn_launch).
+// grid = (Co / 16 / HG) x B workgroups, instance major (edge_ft_attn_launch).
 // NS = source points per instance (32: destination set == source set, one A image; 128: destination points selected by dst_rows, own A image).
 template <int CIN, int NS, int HG>
 __global__ __launch_bounds__(256, 2) void edge_ft_qk_kernel(const uint4* __restrict__ a_p, const int* __restrict__ ae_p, const uint4* __restrict__ a_q,
                                                          const int* __restrict__ ae_q, const uint4* __restrict__ wplanes, const int* __restrict__ wexp,
                                                          const int32_t* __restrict__ knn, int B, int H, float oms, float* __restrict__ scores,
-                                                         float* __restrict__ sskp, float* __restrict__ ssqp, int inst_major) {
+                                                         float* __restrict__ sskp, float* __restrict__ ssqp) {
     constexpr int KS = CIN / 16, MTP = NS * 3 / 32, MTQ = FND * 3 / 32, SLD = HG * 32 + 4;
     __shared__ __attribute__((aligned(16))) float slab_q[FND * 3 * SLD];    // q phase: Qq (lin | dir); k phase: QK (lin | dir) of the destination points
     __shared__ __attribute__((aligned(16))) float slab_p[NS * 3 * SLD];     // k phase: PK (lin | dir) of the source points
-    __shared__ __attribute__((aligned(16))) uint4 a_ring[(LS_FT_SHARE && NS == 32) ? 2 * 12 * 64 : 1];   // shared A batches (ft_gemm_phase_shared)
+    __shared__ __attribute__((aligned(16))) uint4 a_ring[NS == 32 ? 2 * 12 * 64 : 1];   // shared A batches (ft_gemm_phase_shared)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int logical = xcd_remap(blockIdx.x, gridDim.x);
     const int ngroups = H / HG;
-    const int hg = inst_major ? logical % ngroups : logical / B, b = inst_major ? logical / ngroups : logical % B, head0 = hg * HG;
+    const int hg = logical % ngroups, b = logical / ngroups, head0 = hg * HG;
     const FtMap<HG> mp(tid);
     const int head = head0 + mp.hl;
 
     // ---- q = VecLNA_Q(dst_f[n]) of the workgroup's heads (vec_dgcnn_atten.py:207,210)
     {
         const FtJob<KS> jq[1] = {{a_q, ae_q, b * MTQ, MTQ, 4, slab_q, SLD}};
-        if constexpr (LS_FT_SHARE && NS == 32) ft_gemm_phase_shared<KS, HG, 1>(jq, wplanes, wexp, head0, wave, lane, a_ring);
-        else LS_FT_PHASE<KS, HG, 1>(jq, wplanes, wexp, head0, wave, lane);
+        if constexpr (NS == 32) ft_gemm_phase_shared<KS, HG, 1>(jq, wplanes, wexp, head0, wave, lane, a_ring);
+        else ft_gemm_phase_g3<KS, HG, 1>(jq, wplanes, wexp, head0, wave, lane);
     }
     __syncthreads();
     const int c4 = mp.hl * 32 + mp.ql * 4;
@@ -462,8 +457,8 @@ __global__ __launch_bounds__(256, 2) void edge_ft_qk_kernel(const uint4* __restr
     // ---- k = VecLNA_K(E[n, k]) = act(PK_lin[nbr] + QK_lin[n], PK_dir[nbr] + QK_dir[n])  (:206,209)
     {
         const FtJob<KS> jk[2] = {{a_p, ae_p, b * MTP, MTP, 1, slab_p, SLD}, {a_q, ae_q, b * MTQ, MTQ, 3, slab_q, SLD}};
-        if constexpr (LS_FT_SHARE && NS == 32) ft_gemm_phase_shared<KS, HG, 2>(jk, wplanes, wexp, head0, wave, lane, a_ring);
-        else LS_FT_PHASE<KS, HG, 2>(jk, wplanes, wexp, head0, wave, lane);
+        if constexpr (NS == 32) ft_gemm_phase_shared<KS, HG, 2>(jk, wplanes, wexp, head0, wave, lane, a_ring);
+        else ft_gemm_phase_g3<KS, HG, 2>(jk, wplanes, wexp, head0, wave, lane);
     }
     __syncthreads();
     {
@@ -514,26 +509,22 @@ __global__ __launch_bounds__(256) void edge_ft_norms_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------------------------------------------------------- kernel 2: soft-max and v
-#ifndef LS_FT_V_WPE
-#define LS_FT_V_WPE 2      // dev A/B: waves per SIMD the layer-6 instance (NS == 32, 52 KB of LDS) is compiled for
-#endif
 template <int CIN, int NS, int HG>
-__global__ __launch_bounds__(256, (NS == 32 ? LS_FT_V_WPE : 2)) void edge_ft_v_kernel(const uint4* __restrict__ a_p, const int* __restrict__ ae_p, const uint4* __restrict__ a_q,
+__global__ __launch_bounds__(256, 2) void edge_ft_v_kernel(const uint4* __restrict__ a_p, const int* __restrict__ ae_p, const uint4* __restrict__ a_q,
                                                         const int* __restrict__ ae_q, const uint4* __restrict__ wplanes, const int* __restrict__ wexp,
                                                         const int32_t* __restrict__ knn, int B, int H, float oms, float inv_sqrt_dk,
                                                         const float* __restrict__ scores, const float* __restrict__ invk, const float* __restrict__ invq,
-                                                        float* __restrict__ out, int Co, float* __restrict__ rowmax, int rm_parts, int inst_major,
-                                                        float* __restrict__ colsum) {
+                                                        float* __restrict__ out, int Co, float* __restrict__ rowmax, int rm_parts, float* __restrict__ colsum) {
     // colsum (nullable) [B][3][Co]: the sums of `out` over the instance's 32 points (ascending) -- the mean of the residual global conv
     // (vec_dgcnn_atten.py:223) without a second pass over `out` (glob_mean_gemv_kernel, pointwise.hip)
     constexpr int KS = CIN / 16, MTP = NS * 3 / 32, MTQ = FND * 3 / 32, SLD = HG * 32 + 4;
     __shared__ __attribute__((aligned(16))) float slab_q[FND * 3 * SLD];    // QV (lin | dir) of the destination points
     __shared__ __attribute__((aligned(16))) float slab_p[NS * 3 * SLD];     // PV (lin | dir) of the source points
-    __shared__ __attribute__((aligned(16))) uint4 a_ring[(LS_FT_SHARE && NS == 32) ? 2 * 12 * 64 : 1];
+    __shared__ __attribute__((aligned(16))) uint4 a_ring[NS == 32 ? 2 * 12 * 64 : 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int logical = xcd_remap(blockIdx.x, gridDim.x);
     const int ngroups = H / HG;
-    const int hg = inst_major ? logical % ngroups : logical / B, b = inst_major ? logical / ngroups : logical % B, head0 = hg * HG;
+    const int hg = logical % ngroups, b = logical / ngroups, head0 = hg * HG;
     const FtMap<HG> mp(tid);
     const int head = head0 + mp.hl;
 
@@ -558,8 +549,8 @@ __global__ __launch_bounds__(256, (NS == 32 ? LS_FT_V_WPE : 2)) void edge_ft_v_k
     // ---- v tables of the workgroup's heads
     {
         const FtJob<KS> jv[2] = {{a_p, ae_p, b * MTP, MTP, 0, slab_p, SLD}, {a_q, ae_q, b * MTQ, MTQ, 2, slab_q, SLD}};
-        if constexpr (LS_FT_SHARE && NS == 32) ft_gemm_phase_shared<KS, HG, 2>(jv, wplanes, wexp, head0, wave, lane, a_ring);
-        else LS_FT_PHASE<KS, HG, 2>(jv, wplanes, wexp, head0, wave, lane);
+        if constexpr (NS == 32) ft_gemm_phase_shared<KS, HG, 2>(jv, wplanes, wexp, head0, wave, lane, a_ring);
+        else ft_gemm_phase_g3<KS, HG, 2>(jv, wplanes, wexp, head0, wave, lane);
     }
     __syncthreads();
     // ---- soft-max over the 16 neighbours of (point, head) (:211-215); every lane of the (point, head) group computes it for itself
@@ -709,22 +700,21 @@ int edge_ft_attn_launch(const void* wplanes, const int32_t* knn, bool has_rows, 
     const dim3 grid((H / HG) * B);
     // workgroup order: instance major (an instance's head groups side by side on an XCD: its A image stays in that XCD's L2 and is read by all of
     // them) or head-group major (the 64 instances of one W slice side by side).  Measured (us per launch, q/k | v): layer 5 36.9 | 41.6 instance
-    // major vs 54.9 | 60.6 head major; layer 6 59.2 | 46.6 vs 65.9 | 48.1 -- the A fragments are the stream that matters.  LS_FT_ORDER=0 (dev library): head major.
-    static const int im = dev_knob("LS_FT_ORDER", 1);
+    // major vs 54.9 | 60.6 head major; layer 6 59.2 | 46.6 vs 65.9 | 48.1 -- the A fragments are the stream that matters: instance major.
     if (Cin == 128) {
-        hipLaunchKernelGGL((edge_ft_qk_kernel<128, 128, 1>), grid, dim3(256), 0, st, s.a_p, s.ae_p, s.a_q, s.ae_q, wp, we, knn, B, H, oms, s.scores, s.sskp, s.ssqp, im);
+        hipLaunchKernelGGL((edge_ft_qk_kernel<128, 128, 1>), grid, dim3(256), 0, st, s.a_p, s.ae_p, s.a_q, s.ae_q, wp, we, knn, B, H, oms, s.scores, s.sskp, s.ssqp);
         LS_LAUNCH_CHECK();
         hipLaunchKernelGGL(edge_ft_norms_kernel, dim3(B), dim3(256), 0, st, s.sskp, s.ssqp, H, s.invk, s.invq);
         LS_LAUNCH_CHECK();
         hipLaunchKernelGGL((edge_ft_v_kernel<128, 128, 1>), grid, dim3(256), 0, st, s.a_p, s.ae_p, s.a_q, s.ae_q, wp, we, knn, B, H, oms, isd, s.scores, s.invk,
-                           s.invq, out, Co, rowmax, H / HG, im, colsum);
+                           s.invq, out, Co, rowmax, H / HG, colsum);
     } else {
-        hipLaunchKernelGGL((edge_ft_qk_kernel<256, 32, 2>), grid, dim3(256), 0, st, s.a_p, s.ae_p, s.a_q, s.ae_q, wp, we, knn, B, H, oms, s.scores, s.sskp, s.ssqp, im);
+        hipLaunchKernelGGL((edge_ft_qk_kernel<256, 32, 2>), grid, dim3(256), 0, st, s.a_p, s.ae_p, s.a_q, s.ae_q, wp, we, knn, B, H, oms, s.scores, s.sskp, s.ssqp);
         LS_LAUNCH_CHECK();
         hipLaunchKernelGGL(edge_ft_norms_kernel, dim3(B), dim3(256), 0, st, s.sskp, s.ssqp, H, s.invk, s.invq);
         LS_LAUNCH_CHECK();
         hipLaunchKernelGGL((edge_ft_v_kernel<256, 32, 2>), grid, dim3(256), 0, st, s.a_p, s.ae_p, s.a_q, s.ae_q, wp, we, knn, B, H, oms, isd, s.scores, s.invk,
-                           s.invq, out, Co, rowmax, H / HG, im, colsum);
+                           s.invq, out, Co, rowmax, H / HG, colsum);
     }
     LS_LAUNCH_CHECK();
     return LS_OK;

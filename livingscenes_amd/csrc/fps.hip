@@ -592,12 +592,6 @@ template <bool FMA>
 static int fps_mode(const float* pts, const int32_t* lengths, int B, int N, int K, int32_t* idx, float* po, void* ws, size_t ws_bytes,
                     hipStream_t st) {
     if (N <= 128) return launch_wave<2, FMA>(pts, lengths, B, N, K, idx, po, st);
-#ifdef LS_DEV_KNOBS      // dev A/B: the one-wave kernels for 256 .. 2048 points (same indices)
-    static const bool one_wave = dev_knob("LS_FPS_ONE_WAVE", 0) != 0;
-    if (one_wave && N <= 512) return launch_wave<8, FMA>(pts, lengths, B, N, K, idx, po, st);
-    if (one_wave && N <= 1024) return launch_wave<16, FMA>(pts, lengths, B, N, K, idx, po, st);
-    if (one_wave && N <= 2048) return launch_wave<32, FMA>(pts, lengths, B, N, K, idx, po, st);
-#endif
     if (N <= 256) return launch_quad<1, FMA>(pts, lengths, B, N, K, idx, po, st);
     if (N <= 512) return launch_quad<2, FMA>(pts, lengths, B, N, K, idx, po, st);
     if (N <= 1024) return launch_quad<4, FMA>(pts, lengths, B, N, K, idx, po, st);

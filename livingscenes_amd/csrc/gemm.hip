@@ -116,7 +116,6 @@ __device__ __forceinline__ float dpp_fmax(float v) {
 __device__ __forceinline__ float max8(float v) { return dpp_fmax<0x141>(dpp_fmax<0x4E>(dpp_fmax<0xB1>(v))); }
 __device__ __forceinline__ float max16(float v) { return dpp_fmax<0x140>(max8(v)); }
 // split of s * v (s: the row's power of two); the multiply is spelled as packed fp32 (v_pk_mul_f32: the file is built without SLP vectorisation)
-template <int WHICH>   // 0 = A operand, 1 = W operand (dev timing variants below)
 __device__ __forceinline__ void split2_f16s(const float4& v, float s, uint2& h, uint2& l) {
     const f32x2_t sv = {s, s};
     split2_f16_pair(f32x2_t{v.x, v.y} * sv, h.x, l.x);
@@ -193,27 +192,6 @@ __device__ __forceinline__ void store_half_tile(const float* stg, float* __restr
     }
 }
 
-// store_half_tile for the SLICE-MAJOR layout (GemmAux::slice_cols / slice_rows; edge_staged.hip): the half tile's 64 columns are 64 / sc slices, and the 32
-// rows x sc columns of one slice are CONTIGUOUS in memory (32 * sc floats: 1 KB at sc = 8) -- the lanes walk the half tile slice by slice, so every
-// store instruction writes whole lines.  gm0 % 32 == 0 and slice_rows % 32 == 0: the 32 rows belong to one instance.
-__device__ __forceinline__ void store_half_tile_sliced(const float* stg, float* __restrict__ out, int M, int N, int gm0, int gn0, int lane, int sc, int srows) {
-    const int bi = gm0 / srows, r0 = gm0 - bi * srows;
-    float* ob = out + (size_t)bi * srows * N + (size_t)r0 * sc;
-    const size_t sstride = (size_t)srows * sc;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        const int idx = u * 64 + lane;           // float4 index inside the half tile, slice-major: [slice][row][float4 of the row's sc columns]
-        int s_, rr, q;
-        if (sc == 8) { s_ = idx >> 6; rr = (idx >> 1) & 31; q = idx & 1; }
-        else { s_ = idx >> 5; rr = idx & 31; q = 0; }
-        const int gn = gn0 + s_ * sc + q * 4;
-        if (gm0 + rr < M && gn < N) {
-            const float4 v = *reinterpret_cast<const float4*>(&stg[rr * 68 + s_ * sc + q * 4]);
-            *reinterpret_cast<float4*>(ob + (size_t)(gn / sc) * sstride + (size_t)rr * sc + q * 4) = v;
-        }
-    }
-}
-
 // Optional row gather (down-sampled encoder layers): output row m = (b*gNd + n)*3 + x reads A row
 // (b*gNs + a_rows[b*gNd + n])*3 + x, i.e. the GEMM runs only on the FPS-selected points of each instance.
 // PIECES = 2 (opt-in, LS_SDF_BF16X2): a = a1 + a2 only, three MFMAs per 16 k (a1b1 + a1b2 + a2b1); products carry a 2^-16
@@ -260,7 +238,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
 #pragma unroll
     for (int h = 0; h < NST; ++h) { sa[h] = 1.f; sw[h] = 1.f; }
     __shared__ int rsc[H2 ? GM + GN : 1];   // inverse scales of the tile's 128 A rows, then of its 128 W rows
-    if constexpr (H2) { if (aux.noscale) rsc[tid] = 0; }   // (256 threads = GM + GN entries; otherwise the range block below writes every entry)
     long long arow[NST];  // source row of A for this thread's staged rows (-1 = out of range)
 #pragma unroll
     for (int h = 0; h < NST; ++h) {
@@ -294,10 +271,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
                 const int swz = r * 64 + (((sk >> 3) ^ ((r >> 2) & 3)) << 4) + ((sk >> 2) & 1) * 8;
                 uint2 p1, p2, p3;
                 if constexpr (H2) {
-                    split2_f16s<0>(ra[h], sa[h], p1, p2);
+                    split2_f16s(ra[h], sa[h], p1, p2);
                     *reinterpret_cast<uint2*>(Ap + swz) = p1;
                     *reinterpret_cast<uint2*>(Ap + PLANE + swz) = p2;
-                    split2_f16s<1>(rb[h], sw[h], p1, p2);
+                    split2_f16s(rb[h], sw[h], p1, p2);
                     *reinterpret_cast<uint2*>(Bp + swz) = p1;
                     *reinterpret_cast<uint2*>(Bp + PLANE + swz) = p2;
                     continue;
@@ -319,32 +296,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
 
     if constexpr (H2) {
         // operand range (see GemmAux): per-row powers of two from a pre-pass over this tile's rows, or from the caller's row maxima
-        if (!aux.noscale) {
-            float ma[NST], mw[NST];
+        float ma[NST], mw[NST];
 #pragma unroll
-            for (int h = 0; h < NST; ++h) { ma[h] = 0.f; mw[h] = 0.f; }
-            const bool pre_a = aux.a_rowmax == nullptr, pre_w = aux.w_rowmax == nullptr;
-            if (pre_a || pre_w)
-                for (int k0 = kbeg; k0 < kend; k0 += BK) {
-                    gload(k0);
+        for (int h = 0; h < NST; ++h) { ma[h] = 0.f; mw[h] = 0.f; }
+        const bool pre_a = aux.a_rowmax == nullptr, pre_w = aux.w_rowmax == nullptr;
+        if (pre_a || pre_w)
+            for (int k0 = kbeg; k0 < kend; k0 += BK) {
+                gload(k0);
 #pragma unroll
-                    for (int h = 0; h < NST; ++h) { ma[h] = amax4(ma[h], ra[h]); mw[h] = amax4(mw[h], rb[h]); }
-                }
-#pragma unroll
-            for (int h = 0; h < NST; ++h) {
-                const int r = sr0 + h * RSTEP;
-                if (pre_a) ma[h] = max8(ma[h]);
-                else {
-                    ma[h] = 0.f;
-                    if (arow[h] >= 0) for (int q = 0; q < aux.a_parts; ++q) ma[h] = fmaxf(ma[h], aux.a_rowmax[(size_t)arow[h] * aux.a_parts + q]);
-                }
-                if (pre_w) mw[h] = max8(mw[h]);
-                else mw[h] = n0 + r < N ? aux.w_rowmax[n0 + r] : 0.f;
-                float ia, iw;
-                pow2_scale(ma[h], sa[h], ia);
-                pow2_scale(mw[h], sw[h], iw);
-                if ((tid & 7) == 0) { rsc[r] = pow2_e(ia); rsc[GM + r] = pow2_e(iw); }
+                for (int h = 0; h < NST; ++h) { ma[h] = amax4(ma[h], ra[h]); mw[h] = amax4(mw[h], rb[h]); }
             }
+#pragma unroll
+        for (int h = 0; h < NST; ++h) {
+            const int r = sr0 + h * RSTEP;
+            if (pre_a) ma[h] = max8(ma[h]);
+            else {
+                ma[h] = 0.f;
+                if (arow[h] >= 0) for (int q = 0; q < aux.a_parts; ++q) ma[h] = fmaxf(ma[h], aux.a_rowmax[(size_t)arow[h] * aux.a_parts + q]);
+            }
+            if (pre_w) mw[h] = max8(mw[h]);
+            else mw[h] = n0 + r < N ? aux.w_rowmax[n0 + r] : 0.f;
+            float ia, iw;
+            pow2_scale(ma[h], sa[h], ia);
+            pow2_scale(mw[h], sw[h], iw);
+            if ((tid & 7) == 0) { rsc[r] = pow2_e(ia); rsc[GM + r] = pow2_e(iw); }
         }
     }
     gload(kbeg);
@@ -562,15 +537,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
         swz[h] = r * 64 + (((sk >> 3) ^ ((r >> 2) & 3)) << 4) + ((sk >> 2) & 1) * 8;
     }
     float sa[4] = {1.f, 1.f, 1.f, 1.f}, sw[4] = {1.f, 1.f, 1.f, 1.f};   // operand range: one exact power of two per staged row (GemmAux), set below
-    auto lstore2 = [&](char* plane_hi, const float4& v, float sc, int off) {   // A rows
+    auto lstore2 = [&](char* plane_hi, const float4& v, float sc, int off) {
         uint2 ph, pl;
-        split2_f16s<0>(v, sc, ph, pl);
-        *reinterpret_cast<uint2*>(plane_hi + off) = ph;
-        *reinterpret_cast<uint2*>(plane_hi + PLANE + off) = pl;
-    };
-    auto lstore2w = [&](char* plane_hi, const float4& v, float sc, int off) {   // W rows
-        uint2 ph, pl;
-        split2_f16s<1>(v, sc, ph, pl);
+        split2_f16s(v, sc, ph, pl);
         *reinterpret_cast<uint2*>(plane_hi + off) = ph;
         *reinterpret_cast<uint2*>(plane_hi + PLANE + off) = pl;
     };
@@ -580,48 +549,45 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
             if (part == 0) { *reinterpret_cast<float4*>(Bp + pswz[0]) = pb0; *reinterpret_cast<float4*>(Bp + pswz[1]) = pb1; }
             else { *reinterpret_cast<float4*>(Bp + pswz[2]) = pb2; *reinterpret_cast<float4*>(Bp + pswz[3]) = pb3; }
         } else {
-            lstore2w(Bp, rb[2 * part], sw[2 * part], swz[2 * part]);
-            lstore2w(Bp, rb[2 * part + 1], sw[2 * part + 1], swz[2 * part + 1]);
+            lstore2(Bp, rb[2 * part], sw[2 * part], swz[2 * part]);
+            lstore2(Bp, rb[2 * part + 1], sw[2 * part + 1], swz[2 * part + 1]);
         }
     };
     // operand range: one exact power of two per staged row (GemmAux), from the caller's row maxima or a pre-pass over the rows
-    if (aux.noscale) rsc[tid] = 0;
-    else {
-        float ma[4] = {0.f, 0.f, 0.f, 0.f}, mw[4] = {0.f, 0.f, 0.f, 0.f};
-        if (aux.a_rowmax) {
-#pragma unroll
-            for (int h = 0; h < 4; ++h) {
-                const float* rp = aux.a_rowmax + (size_t)((arow[h] - A) / lda) * aux.a_parts;
-                for (int q = 0; q < aux.a_parts; ++q) ma[h] = fmaxf(ma[h], rp[q]);
-            }
-        } else {
-            for (int k0 = kbeg; k0 < kend; k0 += 32) {
-                gload_a(k0);
-#pragma unroll
-                for (int h = 0; h < 4; ++h) ma[h] = amax4(ma[h], ra[h]);
-            }
-#pragma unroll
-            for (int h = 0; h < 4; ++h) ma[h] = max8(ma[h]);
-        }
-        if (aux.w_rowmax) {
-#pragma unroll
-            for (int h = 0; h < 4; ++h) mw[h] = aux.w_rowmax[(brow[h] - W) / ldw];
-        } else if constexpr (!WPL) {
-            for (int k0 = kbeg; k0 < kend; k0 += 32) {
-                gload_b(k0);
-#pragma unroll
-                for (int h = 0; h < 4; ++h) mw[h] = amax4(mw[h], rb[h]);
-            }
-#pragma unroll
-            for (int h = 0; h < 4; ++h) mw[h] = max8(mw[h]);
-        }
+    float ma[4] = {0.f, 0.f, 0.f, 0.f}, mw[4] = {0.f, 0.f, 0.f, 0.f};
+    if (aux.a_rowmax) {
 #pragma unroll
         for (int h = 0; h < 4; ++h) {
-            float ia, iw;
-            pow2_scale(ma[h], sa[h], ia);
-            pow2_scale(mw[h], sw[h], iw);
-            if ((tid & 7) == 0) { rsc[sr0 + h * 32] = pow2_e(ia); rsc[GM + sr0 + h * 32] = pow2_e(iw); }
+            const float* rp = aux.a_rowmax + (size_t)((arow[h] - A) / lda) * aux.a_parts;
+            for (int q = 0; q < aux.a_parts; ++q) ma[h] = fmaxf(ma[h], rp[q]);
         }
+    } else {
+        for (int k0 = kbeg; k0 < kend; k0 += 32) {
+            gload_a(k0);
+#pragma unroll
+            for (int h = 0; h < 4; ++h) ma[h] = amax4(ma[h], ra[h]);
+        }
+#pragma unroll
+        for (int h = 0; h < 4; ++h) ma[h] = max8(ma[h]);
+    }
+    if (aux.w_rowmax) {
+#pragma unroll
+        for (int h = 0; h < 4; ++h) mw[h] = aux.w_rowmax[(brow[h] - W) / ldw];
+    } else if constexpr (!WPL) {
+        for (int k0 = kbeg; k0 < kend; k0 += 32) {
+            gload_b(k0);
+#pragma unroll
+            for (int h = 0; h < 4; ++h) mw[h] = amax4(mw[h], rb[h]);
+        }
+#pragma unroll
+        for (int h = 0; h < 4; ++h) mw[h] = max8(mw[h]);
+    }
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        float ia, iw;
+        pow2_scale(ma[h], sa[h], ia);
+        pow2_scale(mw[h], sw[h], iw);
+        if ((tid & 7) == 0) { rsc[sr0 + h * 32] = pow2_e(ia); rsc[GM + sr0 + h * 32] = pow2_e(iw); }
     }
     const int lr = lane & 31;
     int offa[2], offb[2];   // byte offset of this lane's operand row inside a plane, per 32-row MFMA tile (slot XOR applied per half)
@@ -719,26 +685,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
 // redoes on data that 2 047 / 5 other workgroups also split), 32 KB of L1 fill and 96 KB of LDS traffic per 96 MFMAs.  A 256 x 256
 // tile halves the global bytes, the LDS writes and the split work per MFMA, the 4 x 2 wave tile takes a quarter off the LDS operand
 // reads.  The accumulators of a 4 x 2 wave tile fit only if the main and the cross terms share them: 128 VGPRs.
-// PP ("ping-pong", round 4, LS_GEMM_W2_PP=1; OFF by default): the two waves that share a SIMD (w and w + 4) run half a slab step apart.  A
-// step is cut into a MEMORY phase (the 12 ds_read_b128 of the step's operand fragments, the split + LDS stores of the next slab, the
-// global loads of the slab after it) and a COMPUTE phase (the step's 24 MFMAs and nothing else), with a workgroup barrier after each;
-// waves 4 - 7 pass one extra barrier before the loop and waves 0 - 3 one after it, so at any time one wave per SIMD is in its compute
-// phase while the other fills its registers.  Same products in the same order: bit-identical.  Buffer hand-over: slab s + 1 is written in
-// the four phases in which slab s is read (the last readers of the old content finished one barrier earlier) and first read after the
-// barrier that closes them.
-// MEASURED (decoder shape 262 144 x 768 x 768, scripts/dev/w2_variants.sh, w2_clock.sh; profiles/r4_final/gemm_w2_power.txt): 957 us
-// against 928 us for the in-step loop -- and the reason the answer is not "fewer stalls": this GEMM runs at the SOCKET POWER CAP.
-// rocm-smi while it runs back to back: 1 400 W (the TDP), shader clock 1.70 GHz (in-step) / 1.82 GHz (ping-pong) instead of 2.39 GHz;
-// the timing variants that remove the MFMAs, the LDS reads or the producer work run at 2.39 GHz and 975 - 1 255 W.  Under the cap the
-// firmware trades every removed stall for clock: ping-pong needs 10 % MORE cycles (four barriers per slab) at a 7 % higher clock.  What
-// is left to gain is energy per tile (fewer bytes moved per MFMA), not issue slots; "matrix pipe 55 % busy" is 55 % of the cycles of a
-// clock the matrix pipe itself pulled down.
-template <bool MASKED, int WPLM, bool PP>   // WPLM: 0 = W rows split here, 1 = pre-split planes staged through registers, 2 = planes by LDS-direct loads
+// This GEMM runs at the SOCKET POWER CAP (decoder shape 262 144 x 768 x 768, profiles/r4_final/gemm_w2_power.txt: 1 400 W, shader clock
+// 1.70 GHz instead of 2.39 GHz): the firmware trades every removed stall for clock, so what is left to gain is energy per tile (fewer bytes
+// moved per MFMA), not issue slots.  Measured and not kept (docs/history.md): ping-pong waves, W planes by LDS-direct loads, one persistent
+// workgroup per CU, v_mfma_f32_16x16x32_f16.
+template <bool MASKED, bool WPL>   // WPL: W from the pre-split planes (GemmAux::w_planes) instead of split here
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void gemm_w2_kernel(
     const float* __restrict__ A, int lda, const float* __restrict__ W, int ldw, const float* __restrict__ bias, float* __restrict__ out, int ldc,
     int M, int N, int K, int relu, int ntiles_n, int ntiles, const float* __restrict__ mask, GemmAux aux) {
-    constexpr bool WPL = WPLM != 0, WDIR = WPLM == 2;
-    static_assert(!(WDIR && PP), "the LDS-direct W path belongs to the in-step loop");
     constexpr int TM = 256, TN = 256;
     constexpr int STG = 32 * 68;
     constexpr int PLANE = TM * 64;         // one f16 plane: 256 rows x 32 k
@@ -748,7 +702,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void g
     int* rsc = reinterpret_cast<int*>(smem + 2 * BUF);          // inverse power-of-two scales: the tile's A rows, then its W rows
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 2, wn = wave & 3;
-    // a workgroup takes the tiles blockIdx.x, + gridDim.x, ... (default launch: one tile each; LS_GEMM_W2_PERSIST=1: one workgroup per CU);
+    // a workgroup takes the tiles blockIdx.x, + gridDim.x, ... (the launch gives it one tile);
     // the workgroups resident on an XCD cover a contiguous range of tiles, tiles of one M block next to each other
     for (int tile = xcd_remap(blockIdx.x, gridDim.x); tile < ntiles; tile += gridDim.x) {
     const int tm = tile / ntiles_n, tn = tile % ntiles_n;
@@ -801,40 +755,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void g
             pswz[u] = (c8 >> 2) * PLANE + r * 64 + (((c8 & 3) ^ ((r >> 2) & 3)) << 4);
         }
     }
-    // WDIR (round 4): the W planes go global -> LDS without passing through registers (global_load_lds_dwordx4: the wave's 64 lanes fill
-    // 1 KB of LDS starting at M0, lane l -> LDS slot l, so the slot swizzle is applied on the GLOBAL side: lane l of the instruction for
-    // plane p, rows r0 .. r0 + 15 fetches chunk (l & 3) ^ ((r >> 2) & 3) of row r = r0 + (l >> 2)).  Wave w owns rows 32 w .. 32 w + 31:
-    // four instructions per slab instead of four 16-byte register loads + four ds_write_b128, and 16 VGPRs fewer.  A slab's loads are
-    // issued during the slab BEFORE it (their buffer was released by the barrier just passed), right after that slab's A rows left their
-    // registers and right before the next A rows are requested, and awaited by s_waitcnt vmcnt(4) in front of the closing barrier -- the
-    // four younger loads are those A rows (a sched_barrier pins them above the wait).  The loads are INLINE ASM on purpose: told about an
-    // LDS-direct load (the builtin), hipcc answers every workgroup barrier and every use of a register load with s_waitcnt vmcnt(0) --
-    // i.e. waits for the A rows it has just requested, once per slab.  Unknown to the compiler they only make its own waits for the A
-    // rows wait for older loads as well, which by then have been awaited here.
-    unsigned doff[4];
-    const int wave_s = __builtin_amdgcn_readfirstlane(wave);
-    if constexpr (WDIR) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int r = wave * 32 + (u & 1) * 16 + (lane >> 2), pl = u >> 1;
-            doff[u] = (unsigned)min(n0 + r, N - 1) * ((unsigned)K * 4u) + pl * 64 + (((lane & 3) ^ ((r >> 2) & 3)) << 4);
-        }
-    }
-    const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-    auto dload_w = [&](char* Bp, int k0) {   // W slab k0 -> the planes at Bp.  Inline asm: see the ordering note above
-        const int ko = min(k0, K - 32);
-        const char* pk = static_cast<const char*>(aux.w_planes) + ko * 4;
-        const unsigned l0 = lds0 + (unsigned)(Bp - smem) + wave_s * (32 * 64);
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(l0 + (u >> 1) * PLANE + (u & 1) * (16 * 64)), "v"(doff[u]), "s"(pk) : "memory", "m0");
-#pragma clang diagnostic pop
-    };
     auto gload_b = [&](int k0) {
         const int ko = min(k0, K - 32);
-        if constexpr (WDIR) return;
         if constexpr (WPL) {
             const char* pk = static_cast<const char*>(aux.w_planes) + ko * 4;
 #pragma unroll
@@ -850,9 +772,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void g
         }
     };
     auto stage_w = [&](char* Bp, int h) {
-        if constexpr (WDIR) return;
         if constexpr (WPL) *reinterpret_cast<float4*>(Bp + pswz[h]) = h == 0 ? pb0 : (h == 1 ? pb1 : (h == 2 ? pb2 : pb3));   // (named registers: as an array these went to scratch)
-        else { uint2 ph, pl; split2_f16s<1>(rb[h], sw[h], ph, pl); *reinterpret_cast<uint2*>(Bp + swz[h]) = ph; *reinterpret_cast<uint2*>(Bp + PLANE + swz[h]) = pl; }
+        else { uint2 ph, pl; split2_f16s(rb[h], sw[h], ph, pl); *reinterpret_cast<uint2*>(Bp + swz[h]) = ph; *reinterpret_cast<uint2*>(Bp + PLANE + swz[h]) = pl; }
     };
     auto lstore2 = [&](char* plane_hi, const float4& v, int e, int off) {
         uint2 ph, pl;
@@ -861,44 +782,41 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void g
         *reinterpret_cast<uint2*>(plane_hi + off) = ph;
         *reinterpret_cast<uint2*>(plane_hi + PLANE + off) = pl;
     };
-    if (aux.noscale) rsc[tid] = 0;
-    else {
-        float ma[4] = {0.f, 0.f, 0.f, 0.f}, mw[4] = {0.f, 0.f, 0.f, 0.f};
-        if (aux.a_rowmax) {
-#pragma unroll
-            for (int h = 0; h < 4; ++h) {
-                const float* rp = aux.a_rowmax + (size_t)min(m0 + sr0 + h * 64, M - 1) * aux.a_parts;
-                for (int q = 0; q < aux.a_parts; ++q) ma[h] = fmaxf(ma[h], rp[q]);
-            }
-        } else {
-            for (int k0 = 0; k0 < K; k0 += 32) {
-                gload_a(k0);
-#pragma unroll
-                for (int h = 0; h < 4; ++h) ma[h] = amax4(ma[h], ra[h]);
-            }
-#pragma unroll
-            for (int h = 0; h < 4; ++h) ma[h] = max8(ma[h]);
-        }
-        if (aux.w_rowmax) {
-#pragma unroll
-            for (int h = 0; h < 4; ++h) mw[h] = aux.w_rowmax[min(n0 + sr0 + h * 64, N - 1)];
-        } else if constexpr (!WPL) {
-            for (int k0 = 0; k0 < K; k0 += 32) {
-                gload_b(k0);
-#pragma unroll
-                for (int h = 0; h < 4; ++h) mw[h] = amax4(mw[h], rb[h]);
-            }
-#pragma unroll
-            for (int h = 0; h < 4; ++h) mw[h] = max8(mw[h]);
-        }
+    float ma[4] = {0.f, 0.f, 0.f, 0.f}, mw[4] = {0.f, 0.f, 0.f, 0.f};
+    if (aux.a_rowmax) {
 #pragma unroll
         for (int h = 0; h < 4; ++h) {
-            float ia, iw, sah;
-            pow2_scale(ma[h], sah, ia);
-            pow2_scale(mw[h], sw[h], iw);
-            ea[h] = pow2_e(sah);
-            if ((tid & 7) == 0) { rsc[sr0 + h * 64] = pow2_e(ia); rsc[TM + sr0 + h * 64] = pow2_e(iw); }
+            const float* rp = aux.a_rowmax + (size_t)min(m0 + sr0 + h * 64, M - 1) * aux.a_parts;
+            for (int q = 0; q < aux.a_parts; ++q) ma[h] = fmaxf(ma[h], rp[q]);
         }
+    } else {
+        for (int k0 = 0; k0 < K; k0 += 32) {
+            gload_a(k0);
+#pragma unroll
+            for (int h = 0; h < 4; ++h) ma[h] = amax4(ma[h], ra[h]);
+        }
+#pragma unroll
+        for (int h = 0; h < 4; ++h) ma[h] = max8(ma[h]);
+    }
+    if (aux.w_rowmax) {
+#pragma unroll
+        for (int h = 0; h < 4; ++h) mw[h] = aux.w_rowmax[min(n0 + sr0 + h * 64, N - 1)];
+    } else if constexpr (!WPL) {
+        for (int k0 = 0; k0 < K; k0 += 32) {
+            gload_b(k0);
+#pragma unroll
+            for (int h = 0; h < 4; ++h) mw[h] = amax4(mw[h], rb[h]);
+        }
+#pragma unroll
+        for (int h = 0; h < 4; ++h) mw[h] = max8(mw[h]);
+    }
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        float ia, iw, sah;
+        pow2_scale(ma[h], sah, ia);
+        pow2_scale(mw[h], sw[h], iw);
+        ea[h] = pow2_e(sah);
+        if ((tid & 7) == 0) { rsc[sr0 + h * 64] = pow2_e(ia); rsc[TM + sr0 + h * 64] = pow2_e(iw); }
     }
     const int lr = lane & 31;
     int offa[4], offb[2], xa[4], xb[2];   // byte offset of this lane's operand row inside a plane per 32-row MFMA tile, and its slot XOR
@@ -907,20 +825,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void g
 #pragma unroll
     for (int j = 0; j < 2; ++j) { const int r = wn * 64 + j * 32 + lr; offb[j] = r * 64; xb[j] = (r >> 2) & 3; }
 
-    if constexpr (WDIR) dload_w(smem + 2 * PLANE, 0);
     gload_a(0); gload_b(0);
 #pragma unroll
     for (int h = 0; h < 4; ++h) { lstore2(smem, ra[h], ea[h], swz[h]); stage_w(smem + 2 * PLANE, h); }
     gload_a(32); gload_b(32);
-    if constexpr (WDIR) {   // vmcnt(4): everything but the A rows of slab 1
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_waitcnt(0x0f74);
-    }
     __syncthreads();
 
     int cur = 0;
-    const bool late_half = __builtin_amdgcn_readfirstlane(wave) >= 4;   // (waves w and w + 4 share a SIMD: the other pairings measured 1 064 - 1 083 us)
-    if constexpr (PP) { if (late_half) __builtin_amdgcn_s_barrier(); }
     for (int k0 = 0; k0 < K; k0 += 32, cur ^= 1) {
         const char* Ac = smem + cur * BUF;
         const char* Bc = Ac + 2 * PLANE;
@@ -937,87 +848,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void g
 #pragma unroll
                 for (int i = 0; i < 4; ++i) a[i][pc] = __builtin_bit_cast(f16x8_t, *reinterpret_cast<const uint4*>(Ac + pc * PLANE + offa[i] + ((q ^ xa[i]) << 4)));
             }
-            if constexpr (PP) {
-                // memory phase: the producer work of this half step, then the barrier; compute phase: MFMAs only
-                if (s2 == 0) {
-#pragma unroll
-                    for (int h = 0; h < 4; ++h) lstore2(An, ra[h], ea[h], swz[h]);
-                    gload_a(k0 + 64);
-                } else {
-#pragma unroll
-                    for (int h = 0; h < 4; ++h) stage_w(Bn, h);
-                    gload_b(k0 + 64);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): this wave's LDS stores have landed, its fragments have arrived
-                __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][1], b[j][0], acc[i][j], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][0], b[j][0], acc[i][j], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][0], b[j][1], acc[i][j], 0, 0, 0);
-                __builtin_amdgcn_s_setprio(0);
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_sched_barrier(0);
-                continue;
-            }
-#ifdef LS_W2_MFMA16
-            // dev TIMING variant (verdict r4 item 8a; wrong results -- the epilogue still assumes the 32 x 32 accumulator map): the same flops as
-            // v_mfma_f32_16x16x32_f16 -- a wave tile = 8 x 4 tiles of 16 x 16, one instruction per 32-k slab and product term; this half step takes the
-            // tiles of rows 64 s2 .. 64 s2 + 63.  Same LDS planes and operand bytes per slab (12 fragments of each piece), same accumulator registers.
-            {
-                typedef float f32x4w __attribute__((ext_vector_type(4)));
-                const int l15 = lane & 15, q4 = lane >> 4;
-                f16x8_t a16[4][2], b16[4][2];
-#pragma unroll
-                for (int pc = 0; pc < 2; ++pc) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { const int r = wn * 64 + j * 16 + l15; b16[j][pc] = __builtin_bit_cast(f16x8_t, *reinterpret_cast<const uint4*>(Bc + pc * PLANE + r * 64 + ((q4 ^ ((r >> 2) & 3)) << 4))); }
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) { const int r = wm * 128 + (4 * s2 + i) * 16 + l15; a16[i][pc] = __builtin_bit_cast(f16x8_t, *reinterpret_cast<const uint4*>(Ac + pc * PLANE + r * 64 + ((q4 ^ ((r >> 2) & 3)) << 4))); }
-                }
-                f32x4w c16[4][4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) c16[i][j][e] = acc[2 * s2 + (i >> 1)][j >> 1][((i & 1) * 2 + (j & 1)) * 4 + e];
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) c16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a16[i][1], b16[j][0], c16[i][j], 0, 0, 0);
-                if (s2 == 0) { lstore2(An, ra[0], ea[0], swz[0]); lstore2(An, ra[1], ea[1], swz[1]); }
-                else { stage_w(Bn, 0); stage_w(Bn, 1); }
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) c16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a16[i][0], b16[j][0], c16[i][j], 0, 0, 0);
-                if (s2 == 0) { lstore2(An, ra[2], ea[2], swz[2]); lstore2(An, ra[3], ea[3], swz[3]); gload_a(k0 + 64); }
-                else { stage_w(Bn, 2); stage_w(Bn, 3); gload_b(k0 + 64); }
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) c16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a16[i][0], b16[j][1], c16[i][j], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) acc[2 * s2 + (i >> 1)][j >> 1][((i & 1) * 2 + (j & 1)) * 4 + e] = c16[i][j][e];
-                continue;
-            }
-#endif
             // per accumulator and 16-k step: lo(a) hi(w), hi(a) hi(w), hi(a) lo(w) -- the order every unified-accumulator kernel uses
 #pragma unroll
             for (int i = 0; i < 4; ++i)
@@ -1029,24 +859,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void g
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][0], b[j][0], acc[i][j], 0, 0, 0);
-            if (s2 == 0) {
-                lstore2(An, ra[2], ea[2], swz[2]); lstore2(An, ra[3], ea[3], swz[3]);
-                if constexpr (WDIR) dload_w(Bn, k0 + 32);   // (after the A rows have been consumed, before the next ones are requested: see dload_w)
-                gload_a(k0 + 64);
-            }
+            if (s2 == 0) { lstore2(An, ra[2], ea[2], swz[2]); lstore2(An, ra[3], ea[3], swz[3]); gload_a(k0 + 64); }
             else { stage_w(Bn, 2); stage_w(Bn, 3); gload_b(k0 + 64); }
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][0], b[j][1], acc[i][j], 0, 0, 0);
         }
-        if constexpr (WDIR) {   // vmcnt(4): this slab's LDS-direct W loads have landed (younger: the A rows of slab + 2)
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_waitcnt(0x0f74);
-        }
-        if constexpr (!PP) __syncthreads();   // buffer cur^1 is complete, and every wave is done reading buffer cur
+        __syncthreads();   // buffer cur^1 is complete, and every wave is done reading buffer cur
     }
-    if constexpr (PP) { if (!late_half) __builtin_amdgcn_s_barrier(); }   // the barrier counts of the two halves match again
 
     // (Not kept: s_setprio(1) around the MFMA groups: 930 -> 1 055 us.  The operand fragments as an explicit four-sub-phase software pipeline -- every LDS read batch one sub-phase ahead of its
     // MFMAs, the barrier in front of the last sub-phase.  Unfenced, the scheduler sinks the loads back to their uses: same time; fenced
@@ -1162,57 +983,48 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
         const int r = sr0 + h * 32;
         swz[h] = r * 64 + (((sk >> 3) ^ ((r >> 2) & 3)) << 4) + ((sk >> 2) & 1) * 8;
     }
-    auto lstore2 = [&](char* plane_hi, const float4& v, float sc, int off) {   // A rows
+    auto lstore2 = [&](char* plane_hi, const float4& v, float sc, int off) {
         uint2 ph, pl;
-        split2_f16s<0>(v, sc, ph, pl);
-        *reinterpret_cast<uint2*>(plane_hi + off) = ph;
-        *reinterpret_cast<uint2*>(plane_hi + PLANE + off) = pl;
-    };
-    auto lstore2w = [&](char* plane_hi, const float4& v, float sc, int off) {   // W rows
-        uint2 ph, pl;
-        split2_f16s<1>(v, sc, ph, pl);
+        split2_f16s(v, sc, ph, pl);
         *reinterpret_cast<uint2*>(plane_hi + off) = ph;
         *reinterpret_cast<uint2*>(plane_hi + PLANE + off) = pl;
     };
     // operand range: one exact power of two per staged row (GemmAux), from the caller's row maxima or a pre-pass over the rows
     float sa[4] = {1.f, 1.f, 1.f, 1.f}, sw[4] = {1.f, 1.f, 1.f, 1.f};
-    if (aux.noscale) rsc[tid] = 0;
-    else {
-        float ma[4] = {0.f, 0.f, 0.f, 0.f}, mw[4] = {0.f, 0.f, 0.f, 0.f};
-        if (aux.a_rowmax) {
-#pragma unroll
-            for (int h = 0; h < 4; ++h) {
-                const float* rp = aux.a_rowmax + (size_t)((arow[h] - A) / lda) * aux.a_parts;
-                for (int q = 0; q < aux.a_parts; ++q) ma[h] = fmaxf(ma[h], rp[q]);
-            }
-        } else {
-            for (int k0 = kbeg; k0 < kend; k0 += 32) {
-                gload_a(k0);
-#pragma unroll
-                for (int h = 0; h < 4; ++h) ma[h] = amax4(ma[h], ra[h]);
-            }
-#pragma unroll
-            for (int h = 0; h < 4; ++h) ma[h] = max8(ma[h]);
-        }
-        if (aux.w_rowmax) {
-#pragma unroll
-            for (int h = 0; h < 4; ++h) mw[h] = aux.w_rowmax[(brow[h] - W) / ldw];
-        } else {
-            for (int k0 = kbeg; k0 < kend; k0 += 32) {
-                gload_b(k0);
-#pragma unroll
-                for (int h = 0; h < 4; ++h) mw[h] = amax4(mw[h], rb[h]);
-            }
-#pragma unroll
-            for (int h = 0; h < 4; ++h) mw[h] = max8(mw[h]);
-        }
+    float ma[4] = {0.f, 0.f, 0.f, 0.f}, mw[4] = {0.f, 0.f, 0.f, 0.f};
+    if (aux.a_rowmax) {
 #pragma unroll
         for (int h = 0; h < 4; ++h) {
-            float ia, iw;
-            pow2_scale(ma[h], sa[h], ia);
-            pow2_scale(mw[h], sw[h], iw);
-            if ((tid & 7) == 0) { rsc[sr0 + h * 32] = pow2_e(ia); rsc[GM + sr0 + h * 32] = pow2_e(iw); }
+            const float* rp = aux.a_rowmax + (size_t)((arow[h] - A) / lda) * aux.a_parts;
+            for (int q = 0; q < aux.a_parts; ++q) ma[h] = fmaxf(ma[h], rp[q]);
         }
+    } else {
+        for (int k0 = kbeg; k0 < kend; k0 += 32) {
+            gload_a(k0);
+#pragma unroll
+            for (int h = 0; h < 4; ++h) ma[h] = amax4(ma[h], ra[h]);
+        }
+#pragma unroll
+        for (int h = 0; h < 4; ++h) ma[h] = max8(ma[h]);
+    }
+    if (aux.w_rowmax) {
+#pragma unroll
+        for (int h = 0; h < 4; ++h) mw[h] = aux.w_rowmax[(brow[h] - W) / ldw];
+    } else {
+        for (int k0 = kbeg; k0 < kend; k0 += 32) {
+            gload_b(k0);
+#pragma unroll
+            for (int h = 0; h < 4; ++h) mw[h] = amax4(mw[h], rb[h]);
+        }
+#pragma unroll
+        for (int h = 0; h < 4; ++h) mw[h] = max8(mw[h]);
+    }
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        float ia, iw;
+        pow2_scale(ma[h], sa[h], ia);
+        pow2_scale(mw[h], sw[h], iw);
+        if ((tid & 7) == 0) { rsc[sr0 + h * 32] = pow2_e(ia); rsc[GM + sr0 + h * 32] = pow2_e(iw); }
     }
     const int lr = lane & 31;
     int offa[2], offb[2];   // byte offset of this lane's operand row inside a plane, per 32-row MFMA tile (slot XOR applied per half)
@@ -1222,7 +1034,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
 
     gload_a(kbeg); gload_b(kbeg);
 #pragma unroll
-    for (int h = 0; h < 4; ++h) { lstore2(smem, ra[h], sa[h], swz[h]); lstore2w(smem + 2 * PLANE, rb[h], sw[h], swz[h]); }
+    for (int h = 0; h < 4; ++h) { lstore2(smem, ra[h], sa[h], swz[h]); lstore2(smem + 2 * PLANE, rb[h], sw[h], swz[h]); }
     gload_a(kbeg + 32); gload_b(kbeg + 32);
     __syncthreads();
 
@@ -1249,13 +1061,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][1], b[j][0], acc[i][j], 0, 0, 0);
-            if (s2 == 0) { lstore2(An, ra[0], sa[0], swz[0]); lstore2(An, ra[1], sa[1], swz[1]); } else { lstore2w(Bn, rb[0], sw[0], swz[0]); lstore2w(Bn, rb[1], sw[1], swz[1]); }
+            if (s2 == 0) { lstore2(An, ra[0], sa[0], swz[0]); lstore2(An, ra[1], sa[1], swz[1]); } else { lstore2(Bn, rb[0], sw[0], swz[0]); lstore2(Bn, rb[1], sw[1], swz[1]); }
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][0], b[j][0], acc[i][j], 0, 0, 0);
             if (s2 == 0) { lstore2(An, ra[2], sa[2], swz[2]); lstore2(An, ra[3], sa[3], swz[3]); gload_a(k0 + 64); }
-            else { lstore2w(Bn, rb[2], sw[2], swz[2]); lstore2w(Bn, rb[3], sw[3], swz[3]); gload_b(k0 + 64); }
+            else { lstore2(Bn, rb[2], sw[2], swz[2]); lstore2(Bn, rb[3], sw[3], swz[3]); gload_b(k0 + 64); }
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1472,12 +1284,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
     }
     auto lstore2 = [&](char* base, int slab, const float4& v, float sc, int off) {
         uint2 ph, pl;
-        split2_f16s<0>(v, sc, ph, pl);
+        split2_f16s(v, sc, ph, pl);
         *reinterpret_cast<uint2*>(base + (2 * slab) * PLANE + off) = ph;
         *reinterpret_cast<uint2*>(base + (2 * slab + 1) * PLANE + off) = pl;
     };
-    const bool scaled = !aux.noscale;
-    if (!scaled) rsc[tid] = 0;
     // W tile, once (columns past N: clamped row, computed and never stored); each row scaled by its own power of two (GemmAux: the
     // whole K of a row is in this thread group's registers, so the row maximum costs three DPP steps)
     {
@@ -1491,14 +1301,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
             }
 #pragma unroll
         for (int h = 0; h < 4; ++h) {
-            float sw = 1.f;
-            if (scaled) {
-                float mw = 0.f, iw;
+            float sw, iw, mw = 0.f;
 #pragma unroll
-                for (int sl = 0; sl < NSL; ++sl) mw = amax4(mw, rw[sl][h]);
-                pow2_scale(max8(mw), sw, iw);
-                if ((tid & 7) == 0) rsc[GM + sr0 + h * 32] = pow2_e(iw);
-            }
+            for (int sl = 0; sl < NSL; ++sl) mw = amax4(mw, rw[sl][h]);
+            pow2_scale(max8(mw), sw, iw);
+            if ((tid & 7) == 0) rsc[GM + sr0 + h * 32] = pow2_e(iw);
 #pragma unroll
             for (int sl = 0; sl < NSL; ++sl) lstore2(Bp, sl, rw[sl][h], sw, swz[h]);
         }
@@ -1536,16 +1343,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
     for (; tm < ntiles_m; tm += per_n) {
         const int m0 = tm * GM;
         __syncthreads();                               // previous tile's staging and scale reads are done (and the W planes are written)
+        // (the row maxima below wait for this tile's loads: hoisted above the barrier, every wave would hold the barrier until its own loads land)
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int h = 0; h < 4; ++h) {
-            float sa = 1.f;
-            if (scaled) {
-                float ma = 0.f, ia;
+            float sa, ia, ma = 0.f;
 #pragma unroll
-                for (int sl = 0; sl < NSL; ++sl) ma = amax4(ma, ra[sl][h]);
-                pow2_scale(max8(ma), sa, ia);
-                if ((tid & 7) == 0) rsc[sr0 + h * 32] = pow2_e(ia);
-            }
+            for (int sl = 0; sl < NSL; ++sl) ma = amax4(ma, ra[sl][h]);
+            pow2_scale(max8(ma), sa, ia);
+            if ((tid & 7) == 0) rsc[sr0 + h * 32] = pow2_e(ia);
 #pragma unroll
             for (int sl = 0; sl < NSL; ++sl) lstore2(Ap, sl, ra[sl][h], sa, swz[h]);
         }
@@ -1611,8 +1417,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
             }
             __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
             __builtin_amdgcn_wave_barrier();
-            if (aux.slice_cols) store_half_tile_sliced(stg, out, M, N, m0 + wm * 64 + i * 32, n0 + wn * 64, lane, aux.slice_cols, aux.slice_rows);
-            else store_half_tile(stg, out, ldc, M, N, m0 + wm * 64 + i * 32, n0 + wn * 64, lane, full_tile, vec_ok, nullptr);
+            store_half_tile(stg, out, ldc, M, N, m0 + wm * 64 + i * 32, n0 + wn * 64, lane, full_tile, vec_ok, nullptr);
             __builtin_amdgcn_wave_barrier();
         }
     }
@@ -1652,12 +1457,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
     }
     auto lstore2 = [&](char* base, int slab, const float4& v, float sc, int off) {
         uint2 ph, pl;
-        split2_f16s<0>(v, sc, ph, pl);
+        split2_f16s(v, sc, ph, pl);
         *reinterpret_cast<uint2*>(base + (2 * slab) * PLANE + off) = ph;
         *reinterpret_cast<uint2*>(base + (2 * slab + 1) * PLANE + off) = pl;
     };
-    const bool scaled = !aux.noscale;
-    if (!scaled) rsc[tid] = 0;
     // W tile, once: staged row sr0 + 32 h = tile column (wn = h >> 1, lin | dir = h & 1, channel sr0)
     {
         float4 rw[NSL][4];
@@ -1670,18 +1473,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
         }
 #pragma unroll
         for (int h = 0; h < 4; ++h) {
-            float sw = 1.f;
-            if (scaled) {
-                float mw = 0.f, iw;
-                if (aux.w_rowmax) mw = aux.w_rowmax[wrow[h]];
-                else {
+            float sw, iw, mw = 0.f;
+            if (aux.w_rowmax) mw = aux.w_rowmax[wrow[h]];
+            else {
 #pragma unroll
-                    for (int sl = 0; sl < NSL; ++sl) mw = amax4(mw, rw[sl][h]);
-                    mw = max8(mw);
-                }
-                pow2_scale(mw, sw, iw);
-                if ((tid & 7) == 0) rsc[GM + sr0 + h * 32] = pow2_e(iw);
+                for (int sl = 0; sl < NSL; ++sl) mw = amax4(mw, rw[sl][h]);
+                mw = max8(mw);
             }
+            pow2_scale(mw, sw, iw);
+            if ((tid & 7) == 0) rsc[GM + sr0 + h * 32] = pow2_e(iw);
 #pragma unroll
             for (int sl = 0; sl < NSL; ++sl) lstore2(Bp, sl, rw[sl][h], sw, swz[h]);
         }
@@ -1710,19 +1510,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
         __syncthreads();                               // previous tile's staging and scale reads are done (and the W planes are written)
 #pragma unroll
         for (int h = 0; h < 4; ++h) {
-            float sa = 1.f;
-            if (scaled) {
-                float ma = 0.f, ia;
-                if (aux.a_rowmax) {
-                    for (int q = 0; q < aux.a_parts; ++q) ma = fmaxf(ma, aux.a_rowmax[(size_t)arow[h] * aux.a_parts + q]);
-                } else {
+            float sa, ia, ma = 0.f;
+            if (aux.a_rowmax) {
+                for (int q = 0; q < aux.a_parts; ++q) ma = fmaxf(ma, aux.a_rowmax[(size_t)arow[h] * aux.a_parts + q]);
+            } else {
 #pragma unroll
-                    for (int sl = 0; sl < NSL; ++sl) ma = amax4(ma, ra[sl][h]);
-                    ma = max8(ma);
-                }
-                pow2_scale(ma, sa, ia);
-                if ((tid & 7) == 0) rsc[sr0 + h * 32] = pow2_e(ia);
+                for (int sl = 0; sl < NSL; ++sl) ma = amax4(ma, ra[sl][h]);
+                ma = max8(ma);
             }
+            pow2_scale(ma, sa, ia);
+            if ((tid & 7) == 0) rsc[sr0 + h * 32] = pow2_e(ia);
 #pragma unroll
             for (int sl = 0; sl < NSL; ++sl) lstore2(Ap, sl, ra[sl][h], sa, swz[h]);
         }
@@ -1901,8 +1698,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             uint2 h0, l0, h1, l1;
-            split2_f16s<1>(wslot(wr, 4 * ks + 2 * kh), sw, h0, l0);
-            split2_f16s<1>(wslot(wr, 4 * ks + 2 * kh + 1), sw, h1, l1);
+            split2_f16s(wslot(wr, 4 * ks + 2 * kh), sw, h0, l0);
+            split2_f16s(wslot(wr, 4 * ks + 2 * kh + 1), sw, h1, l1);
             bh[j][ks] = __builtin_bit_cast(f16x8_t, make_uint4(h0.x, h0.y, h1.x, h1.y));
             bl[j][ks] = __builtin_bit_cast(f16x8_t, make_uint4(l0.x, l0.y, l1.x, l1.y));
         }
@@ -1943,10 +1740,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
         for (int x = 0; x < 3; ++x) { gl[x] = g[x * ldg]; gd[x] = g[x * ldg + C]; }
     }
     // ---- the M-tiles of this wave's stream
-#ifndef LS_VND_SKIP
-#define LS_VND_SKIP 0      // dev timing variants (wrong results): 1 = no epilogue, 2 = no MFMAs, 4 = no tiles, 8 = no LDS transpose
-#endif
-    if (LS_VND_SKIP & 4) { if (bh[0][0][0] == (_Float16)123.f && gl[0] == 5.f) out[0] = 1.f; return; }
     auto do_tile = [&](float4 v0_, float4 v1_, float4 v2_, float4 v3_, float4 v4_, float4 v5_, float rma, int tt) {
         const float4 rv[6] = {v0_, v1_, v2_, v3_, v4_, v5_};     // (by value: an array handed over by reference stayed in scratch memory)
         float sa, ia;
@@ -1967,18 +1760,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
             const int row = 4 * i + (lane >> 4);
-            if (!(LS_VND_SKIP & 8)) sg[row * 16 + ((lane & 15) ^ (row & 15))] = rv[i];
+            sg[row * 16 + ((lane & 15) ^ (row & 15))] = rv[i];
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             uint2 h0, l0, h1, l1;
-            const float4 v0 = (LS_VND_SKIP & 8) ? rv[ks] : sg[rofs * 16 + ((4 * ks + 2 * kh) ^ (rofs & 15))], v1 = (LS_VND_SKIP & 8) ? rv[ks + 1] : sg[rofs * 16 + ((4 * ks + 2 * kh + 1) ^ (rofs & 15))];
-            split2_f16s<0>(v0, sa, h0, l0);
-            split2_f16s<0>(v1, sa, h1, l1);
+            const float4 v0 = sg[rofs * 16 + ((4 * ks + 2 * kh) ^ (rofs & 15))], v1 = sg[rofs * 16 + ((4 * ks + 2 * kh + 1) ^ (rofs & 15))];
+            split2_f16s(v0, sa, h0, l0);
+            split2_f16s(v1, sa, h1, l1);
             const f16x8_t ah = __builtin_bit_cast(f16x8_t, make_uint4(h0.x, h0.y, h1.x, h1.y)), al = __builtin_bit_cast(f16x8_t, make_uint4(l0.x, l0.y, l1.x, l1.y));
-            if (LS_VND_SKIP & 2) { acc[0][ks] += (float)ah[0] + (float)al[1] + (float)bh[0][ks][0]; acc[1][ks] += (float)ah[2] + (float)bl[1][ks][0]; continue; }
 #pragma unroll
             for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[j][ks], acc[j], 0, 0, 0);
 #pragma unroll
@@ -1986,7 +1778,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
 #pragma unroll
             for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[j][ks], acc[j], 0, 0, 0);
         }
-        if (LS_VND_SKIP & 1) { if (acc[0][0] + acc[1][0] + acc[0][4] + acc[1][5] + acc[0][8] + acc[1][12] == 12345.f) out[tt] = 1.f; return; }
         // epilogue: accumulator rows 4 g + axis of this lane = point 2 g + kh of the tile
         const int p0 = (b * tiles_inst + tt) * 8;
 #pragma unroll
@@ -2072,13 +1863,13 @@ __global__ __launch_bounds__(256) void gemm_presplit_w_kernel(const float* __res
     float sc, inv;
     pow2_scale(rowmax[r], sc, inv);
     uint2 ph, pl;
-    split2_f16s<1>(*reinterpret_cast<const float4*>(W + (size_t)r * ldw + k), sc, ph, pl);
+    split2_f16s(*reinterpret_cast<const float4*>(W + (size_t)r * ldw + k), sc, ph, pl);
     char* line = planes + (size_t)r * ((size_t)K * 4) + (size_t)(k >> 5) * 128 + (k & 31) * 2;
     *reinterpret_cast<uint2*>(line) = ph;
     *reinterpret_cast<uint2*>(line + 64) = pl;
 }
 size_t gemm_w_planes_bytes(size_t rows, int K) { return rows * (size_t)K * 4; }
-// the kernels that read planes: gemm_h2_kernel<true, true>, gemm_w2_kernel<., true>.  Measured (scripts/diag/gemm_wide_probe.py): -5 % at
+// the kernels that read planes: gemm_h2_kernel<true, true>, gemm_w2_kernel<., true>.  Measured: -5 % at
 // the decoder shape (992 -> 941 us wide, 1198 -> 1128 us narrow), neutral at K = 512, +8 .. 15 % on the K = 128 / 256 tables: K >= 512 only
 bool gemm_w_planes_useful(int K) { return K >= 512 && K % 32 == 0; }
 int gemm_presplit_w_launch(const float* W, int rows, int K, int ldw, const float* rowmax, void* planes, hipStream_t st) {
@@ -2118,8 +1909,6 @@ size_t gemm_scratch_floats(int M, int N, int K) {
 int gemm_dispatch_full(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N, int K,
                        int relu, const int32_t* a_rows, int gNd, int gNs, float* scratch, hipStream_t st, bool latency_path = false,
                        int pieces = 3, const float* mask = nullptr, GemmAux aux = GemmAux()) {
-    static const bool range_off = dev_knob("LS_GEMM_RANGE", 1) == 0;   // dev A/B: the unscaled round-2 split
-    if (range_off) aux.noscale = 1;
     LS_REQUIRE(M > 0 && N > 0 && K > 0, "gemm: empty problem (M=%d N=%d K=%d)", M, N, K);
     LS_REQUIRE(K % 4 == 0 && lda % 4 == 0 && ldw % 4 == 0, "gemm: K, lda, ldw must be multiples of 4 (K=%d lda=%d ldw=%d)", K, lda, ldw);
     LS_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0, "gemm: A and W must be 16-byte aligned");
@@ -2148,10 +1937,8 @@ int gemm_dispatch_full(const float* A, int lda, const float* W, int ldw, const f
     const bool split = split_on && !latency_path;
     // how an fp32 product is formed on the 16-bit matrix cores: 22 = two f16 pieces (three MFMAs per 16 k, the
     // default), 3 = three bf16 pieces (six MFMAs, any fp32 range: LS_GEMM_MODE=bf16x3), 2 = two bf16 pieces (opt-in decode mode)
-    static const bool h2_unpipelined = dev_knob("LS_GEMM_H2_SIMPLE", 0) != 0;   // dev A/B: the two-barrier kernel
-    static const bool planes_off = dev_knob("LS_GEMM_WPLANES", 1) == 0;         // dev A/B: split W inside the kernel
-    const bool wpl = aux.w_planes && aux.w_rowmax && !aux.noscale && !planes_off && K % 32 == 0 && K > 64 && !h2_unpipelined;
-#define LS_H2_KERNEL ((h2_unpipelined || K <= 64) ? gemm_f32_kernel<true, 22> : (K % 32 == 0 ? (wpl ? gemm_h2_kernel<true, true> : gemm_h2_kernel<true, false>) : gemm_h2_kernel<false, false>))
+    const bool wpl = aux.w_planes && aux.w_rowmax && K % 32 == 0 && K > 64;
+#define LS_H2_KERNEL (K <= 64 ? gemm_f32_kernel<true, 22> : (K % 32 == 0 ? (wpl ? gemm_h2_kernel<true, true> : gemm_h2_kernel<true, false>) : gemm_h2_kernel<false, false>))
     const int default_pieces = gemm_mode() == 1 ? 3 : 22;
     if (pieces == 3) pieces = default_pieces;
     const int nsplit = (scratch && !mask) ? gemm_choose_splits(M, N, K) : 1;   // (a split launch writes no out_rowmax: callers check gemm_scratch_floats)
@@ -2175,21 +1962,12 @@ int gemm_dispatch_full(const float* A, int lda, const float* W, int ldw, const f
         LS_LAUNCH_CHECK();
         return LS_OK;
     }
-    static const bool persist = dev_knob("LS_GEMM_PERSIST", 1) != 0;   // dev A/B: K = 32 / 64 on the tiled kernel
-    // 256 x 256 tiles once they fill the chip (LS_GEMM_WIDE=0 / 1: never / always -- same arithmetic, bit-identical results)
-    static const int wide_mode = dev_knob("LS_GEMM_WIDE", -1);
-    // measured (scripts/diag/gemm_wide_probe.py): the wide kernel wins when its grid fills whole rounds of the 256 CUs (one workgroup per
-    // CU): 480 tiles 88 -> 73 us, 768 tiles 355 -> 280 us, 3072 tiles 1186 -> 1002 us; ties at 384 tiles, loses below one round
+    // 256 x 256 tiles once they fill the chip (same arithmetic, bit-identical results).  Measured: the wide kernel wins when its grid fills whole
+    // rounds of the 256 CUs (one workgroup per CU): 480 tiles 88 -> 73 us, 768 tiles 355 -> 280 us, 3072 tiles 1186 -> 1002 us; ties at 384 tiles, loses below one round
     const long long wtiles = (long long)cdiv(M, 256) * cdiv(N, 256);
-    const bool wide_on = wide_mode >= 0 ? wide_mode != 0 : (wtiles >= 1024 || (wtiles >= 256 && wtiles * 100 >= 85 * 256 * cdiv(wtiles, 256)));
-    const bool sliced = aux.slice_cols != 0;
-    if (sliced)
-        LS_REQUIRE(split && pieces == 22 && !mask && !a_rows && (K == 32 || K == 64) && nsplit == 1 && !aux.out_rowmax && !bias && (aux.slice_cols == 4 || aux.slice_cols == 8) &&
-                   aux.slice_rows % 32 == 0 && M % aux.slice_rows == 0 && N % aux.slice_cols == 0 && ((uintptr_t)out & 15) == 0,
-                   "gemm: slice-major output needs the K = 32 / 64 f16-split kernel (M=%d N=%d K=%d slice %d x %d)", M, N, K, aux.slice_rows, aux.slice_cols);
-    if (split && pieces == 22 && (sliced || (persist && tm >= 16 && !h2_unpipelined)) && !mask && (K == 32 || K == 64) && !aux.out_rowmax) {
-        static const int sk_wgs32 = dev_knob("LS_GEMM_PERSIST_WGS32", 512), sk_wgs64 = dev_knob("LS_GEMM_PERSIST_WGS64", 512);   // dev A/B
-        int per_n = cdiv(K == 32 ? sk_wgs32 : sk_wgs64, tn);   // resident workgroups per CU x 256, spread evenly over the N-tiles
+    const bool wide_on = wtiles >= 1024 || (wtiles >= 256 && wtiles * 100 >= 85 * 256 * cdiv(wtiles, 256));
+    if (split && pieces == 22 && tm >= 16 && !mask && (K == 32 || K == 64) && !aux.out_rowmax) {
+        int per_n = cdiv(512, tn);   // resident workgroups per CU x 256, spread evenly over the N-tiles
         if (per_n > tm) per_n = tm;
 #define LS_H2SK(KK, G) hipLaunchKernelGGL((gemm_h2_smallk_kernel<KK, G>), dim3(tn * per_n), dim3(256), 0, st, A, lda, W, ldw, bias, out, ldc, M, N, relu, tm, per_n, a_rows, gNd, gNs, aux)
         if (K == 32) { if (a_rows) LS_H2SK(32, true); else LS_H2SK(32, false); }
@@ -2205,30 +1983,14 @@ int gemm_dispatch_full(const float* A, int lda, const float* W, int ldw, const f
         LS_HIP_CHECK(hipGetDevice(&dev_ord));
         const unsigned long long dev_bit = 1ull << (dev_ord & 63);
         if (!(attr_devices.load(std::memory_order_acquire) & dev_bit)) {
-#define LS_W2_ATTR(MK, PL, PG) LS_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_w2_kernel<MK, PL, PG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
-            LS_W2_ATTR(false, 0, false); LS_W2_ATTR(true, 0, false); LS_W2_ATTR(false, 1, false); LS_W2_ATTR(true, 1, false);
-#ifdef LS_DEV_KNOBS
-            LS_W2_ATTR(false, 0, true); LS_W2_ATTR(true, 0, true); LS_W2_ATTR(false, 1, true); LS_W2_ATTR(true, 1, true);
-            LS_W2_ATTR(false, 2, false); LS_W2_ATTR(true, 2, false);
-#endif
+#define LS_W2_ATTR(MK, PL) LS_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_w2_kernel<MK, PL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
+            LS_W2_ATTR(false, false); LS_W2_ATTR(true, false); LS_W2_ATTR(false, true); LS_W2_ATTR(true, true);
 #undef LS_W2_ATTR
             attr_devices.fetch_or(dev_bit, std::memory_order_release);
         }
-        // dev variants (-DLS_DEV_KNOBS; all bit-identical to the default, all measured and not kept -- docs/history.md): LS_GEMM_W2_PERSIST=1 one workgroup
-        // per CU walking the tiles (942 - 944 vs 950 - 956 us at the decoder shape, 73 -> 79 us at 480 tiles); LS_GEMM_W2_PP=1 the two waves of a SIMD half
-        // a slab step apart (957 vs 928 us); LS_GEMM_W2_DIRECT=1 the W planes by LDS-direct loads (907 / 933 vs 915 / 925 us: the kernel is power-bound)
-        static const bool w2_persist = dev_knob("LS_GEMM_W2_PERSIST", 0) != 0;
-        const int w2_grid = w2_persist ? std::min(wtm * wtn, 256) : wtm * wtn;
-#define LS_W2(MK, PL, PG) hipLaunchKernelGGL((gemm_w2_kernel<MK, PL, PG>), dim3(w2_grid), dim3(512), lds, st, A, lda, W, ldw, bias, out, ldc, M, N, K, relu, wtn, wtm * wtn, mask, aux)
-#ifdef LS_DEV_KNOBS
-        static const bool w2_pp = dev_knob("LS_GEMM_W2_PP", 0) != 0, w2_direct = dev_knob("LS_GEMM_W2_DIRECT", 0) != 0;
-#define LS_W2P(MK, PL) do { if (w2_pp) LS_W2(MK, PL, true); else if (PL == 1 && w2_direct) LS_W2(MK, 2, false); else LS_W2(MK, PL, false); } while (0)
-#else
-#define LS_W2P(MK, PL) LS_W2(MK, PL, false)
-#endif
-        if (mask) { if (wpl) LS_W2P(true, 1); else LS_W2P(true, 0); }
-        else { if (wpl) LS_W2P(false, 1); else LS_W2P(false, 0); }
-#undef LS_W2P
+#define LS_W2(MK, PL) hipLaunchKernelGGL((gemm_w2_kernel<MK, PL>), dim3(wtm * wtn), dim3(512), lds, st, A, lda, W, ldw, bias, out, ldc, M, N, K, relu, wtn, wtm * wtn, mask, aux)
+        if (mask) { if (wpl) LS_W2(true, true); else LS_W2(true, false); }
+        else { if (wpl) LS_W2(false, true); else LS_W2(false, false); }
 #undef LS_W2
     } else if (split && pieces == 22)
         hipLaunchKernelGGL(LS_H2_KERNEL, dim3(tm * tn), dim3(256), 0, st, A, lda, W, ldw, bias, out, ldc, M, N, K, relu, tn, a_rows,
@@ -2274,17 +2036,14 @@ bool gemm_vn_supported(int M, int C, int K) {
 }
 // does gemm_vn_dispatch take the streaming kernel (gemm_vn_direct_kernel) for this problem?  Only then is GemmAux::cs honoured (model.hip: global_conv)
 bool gemm_vn_streams(int M, int C, int K, int lda, int npts, const GemmAux& aux) {
-    return gemm_vn_supported(M, C, K) && K == 64 && C == 64 && lda == K && npts % 8 == 0 && aux.a_rowmax && aux.a_parts > 0 && aux.w_rowmax && !aux.noscale &&
-           M >= 24 * 64 && dev_knob("LS_GLOB_DIRECT", 1) != 0;
+    return gemm_vn_supported(M, C, K) && K == 64 && C == 64 && lda == K && npts % 8 == 0 && aux.a_rowmax && aux.a_parts > 0 && aux.w_rowmax &&
+           M >= 24 * 64;
 }
 int gemm_vn_dispatch(const float* A, int lda, const float* W, int ldw, const float* G, int ldg, float* out, int M, int C, int K, int npts, float oms,
                      hipStream_t st, GemmAux aux) {
-    static const bool range_off = dev_knob("LS_GEMM_RANGE", 1) == 0;
-    if (range_off) aux.noscale = 1;
     LS_REQUIRE(gemm_vn_supported(M, C, K) && lda % 4 == 0 && ldw % 4 == 0, "gemm_vn: unsupported shape (M=%d C=%d K=%d)", M, C, K);
     const int tm = cdiv(M, 120), tn = C / 64;
-    const bool direct = true;   // (dev A/B: LS_GLOB_DIRECT=0 inside gemm_vn_streams)
-    if (direct && gemm_vn_streams(M, C, K, lda, npts, aux) && (G || aux.cs)) {
+    if (gemm_vn_streams(M, C, K, lda, npts, aux) && (G || aux.cs)) {
         const int B = M / (3 * npts), tiles_inst = npts / 8;
         int wpi = cdiv(512, B);                                   // ~512 workgroups (two per CU), every one inside one instance
         wpi = std::max(1, std::min(wpi, cdiv(tiles_inst, 2)));
@@ -2294,10 +2053,8 @@ int gemm_vn_dispatch(const float* A, int lda, const float* W, int ldw, const flo
         LS_LAUNCH_CHECK();
         return LS_OK;
     }
-    static const bool persist = dev_knob("LS_GLOB_PERSIST", 1) != 0;   // dev A/B: K = 32 / 64 on the tiled kernel
-    if (persist && (K == 32 || K == 64) && tm >= 16 && lda == K) {
-        static const int vn_wgs32 = dev_knob("LS_GLOB_PERSIST_WGS32", 512);   // dev A/B
-        int per_n = cdiv(K == 32 ? vn_wgs32 : 512, tn);   // resident workgroups per CU x 256
+    if ((K == 32 || K == 64) && tm >= 16 && lda == K) {
+        int per_n = cdiv(512, tn);   // resident workgroups per CU x 256
         if (per_n > tm) per_n = tm;
         if (K == 32) hipLaunchKernelGGL(gemm_vn_smallk_kernel<32>, dim3(tn * per_n), dim3(256), 0, st, A, lda, W, ldw, G, ldg, out, M, C, npts, oms, tm, per_n, tn, aux);
         else hipLaunchKernelGGL(gemm_vn_smallk_kernel<64>, dim3(tn * per_n), dim3(256), 0, st, A, lda, W, ldw, G, ldg, out, M, C, npts, oms, tm, per_n, tn, aux);

@@ -268,13 +268,9 @@ __device__ __noinline__ u64 kf_brute_row(const float* __restrict__ qrow, const f
 
 // Compiled for four waves per SIMD = two workgroups per CU (116 - 128 registers, no spills).  Measured (round 5): one workgroup per CU by LDS padding
 // 151 / 81 us at layers 1 / 2 against 110 / 71 us.
-#ifdef LS_KF_WPE_ALL            // dev A/B (scripts/dev/build_variants.py)
-#define LS_KF_WPE(TPW, FMA) LS_KF_WPE_ALL
-#else
-#define LS_KF_WPE(TPW, FMA) ((FMA) ? 3 : 4)      // (the fused-multiply-add variants -- LS_FLAG_CONTRACT_FMA, a secondary mode -- spill at four)
-#endif
+// (The fused-multiply-add variants -- LS_FLAG_CONTRACT_FMA, a secondary mode -- spill at four: three.)
 template <int CC, bool FMA, int TPW>
-__global__ __launch_bounds__(64 * KF_WAVES, LS_KF_WPE(TPW, FMA)) void knn_fused_kernel(const float* __restrict__ dstf, const float* __restrict__ srcf, const int32_t* __restrict__ dst_rows,
+__global__ __launch_bounds__(64 * KF_WAVES, FMA ? 3 : 4) void knn_fused_kernel(const float* __restrict__ dstf, const float* __restrict__ srcf, const int32_t* __restrict__ dst_rows,
                                                                   const unsigned short* __restrict__ dq, const unsigned short* __restrict__ sq,
                                                                   const float* __restrict__ nrm_dst, const float* __restrict__ nrm_src,
                                                                   const float* __restrict__ isc_dst, const float* __restrict__ isc_src, int Nd, int dst_n,
@@ -380,9 +376,7 @@ __global__ __launch_bounds__(64 * KF_WAVES, LS_KF_WPE(TPW, FMA)) void knn_fused_
             const float h0 = fmaxf(hm0, 0.0f), h1 = fmaxf(hm1, 0.0f);
             if (h0 < INFINITY) atomicMin(&L.hm[qr][slot], __float_as_uint(h0));
             if (h1 < INFINITY) atomicMin(&L.hm[qr + 1][slot], __float_as_uint(h1));
-#ifndef LS_KF_NOSB
             if ((r & 3) == 2) __builtin_amdgcn_sched_barrier(0);
-#endif
         }
     }
 #else
@@ -405,9 +399,7 @@ __global__ __launch_bounds__(64 * KF_WAVES, LS_KF_WPE(TPW, FMA)) void knn_fused_
             // ---- 2. threshold: (non-negative floats order like their bit patterns; +inf = "no candidate")
             const float h = fmaxf(hmin, 0.0f);
             if (h < INFINITY) atomicMin(&L.hm[qr][slot], __float_as_uint(h));
-#ifndef LS_KF_NOSB
             if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // (four rows' LDS reads in flight at a time: hoisted all sixteen, they cost 32 registers beside S)
-#endif
         }
     }
 #endif
@@ -419,9 +411,6 @@ __global__ __launch_bounds__(64 * KF_WAVES, LS_KF_WPE(TPW, FMA)) void knn_fused_
         if (lane == 0) L.T[qr] = __uint_as_float(tb);
     }
     __syncthreads();
-#if defined(LS_KF_STOP) && LS_KF_STOP == 1      // dev timing variants (wrong results): the kernel up to the threshold
-    if (L.T[0] != 12345.f) return;
-#endif
     // ---- 3. filter
     {
         unsigned mask[TPW];
@@ -469,9 +458,6 @@ __global__ __launch_bounds__(64 * KF_WAVES, LS_KF_WPE(TPW, FMA)) void knn_fused_
         if (c <= KF_LCAP && j < c) L.plist[L.base[qr] + j] = (unsigned)L.list[qr][j] | ((unsigned)qr << 16) | ((unsigned)j << 21);
     }
     __syncthreads();
-#if defined(LS_KF_STOP) && LS_KF_STOP == 2      // ... up to the flat pair list
-    if (L.T[0] != 12345.f) { if (tid == 0) idx_out[(size_t)b * Nd * K + q0] = L.plist[0]; return; }
-#endif
     {
         // Two pairs in flight per quad: the candidate row of step s + 1 is requested before the chain of step s runs (a step is ~2 us of L2
         // gather latency in front of ~600 cycles of dependent adds; a workgroup has ~5 steps).
@@ -506,12 +492,7 @@ __global__ __launch_bounds__(64 * KF_WAVES, LS_KF_WPE(TPW, FMA)) void knn_fused_
             }
             if (pr.v && qlast) L.keys[qr][slot] = make_key(d, cand, true);
         };
-#ifdef LS_KF_NOPIPE      // dev A/B: one pair per quad at a time
-        for (int p0 = 0; p0 < P; p0 += 16 * KF_WAVES) { Pair pa; fetch(p0, pa); finish(pa); }
-        if (false) {
-#else
         if (P > 0) {
-#endif
             Pair pa, pb;
             fetch(0, pa);
             for (int p0 = 0; p0 < P; p0 += 2 * 16 * KF_WAVES) {
@@ -527,9 +508,6 @@ __global__ __launch_bounds__(64 * KF_WAVES, LS_KF_WPE(TPW, FMA)) void knn_fused_
         }
     }
     __syncthreads();
-#if defined(LS_KF_STOP) && LS_KF_STOP == 3      // ... up to the exact distances
-    if (L.T[0] != 12345.f) { if (tid == 0) idx_out[(size_t)b * Nd * K + q0] = (int)L.keys[0][0]; return; }
-#endif
     // ---- 5. select: this wave's four queries, two per pass when both lists fit 32 lanes
     auto emit = [&](int qr, u64 k, int e) {
         const int q = q0 + qr;

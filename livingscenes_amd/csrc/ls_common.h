@@ -39,9 +39,8 @@ void set_error(const char* fmt, ...);
         }                                                                            \
     } while (0)
 
-// Development A/B switches: a library built with -DLS_DEV_KNOBS (scripts/dev/build_variants.py) reads them from the environment; in the RELEASE
-// library every knob is its default, a compile-time constant -- the release library reads nothing from the environment beyond what
-// ls_model_create documents (LS_ENCODE_GRAPH, LS_EDGE_STAGED, LS_SDF_BF16X2) and the process-wide arithmetic mode LS_GEMM_MODE (gemm.hip).
+// Environment: the library reads what ls_model_create documents (LS_ENCODE_GRAPH, LS_SDF_BF16X2) and the process-wide arithmetic mode
+// LS_GEMM_MODE (gemm.hip); a library built with -DLS_DEV_KNOBS also reads the race-hunting switches LS_FPS_SIDE and LS_DEBUG_LAYERS (model.hip).
 // Latency-bound kernels with one workgroup (or wave) per instance -- FPS, the 32-point k-NN, the heads, matcher, Kabsch -- share their CUs with the chip-filling
 // kernels of other steps in flight (and, inside one step, FPS runs beside layers 0 - 1): a raised wave priority makes the SIMD arbiter issue them first.
 #ifndef LS_PRIO
@@ -51,11 +50,6 @@ void set_error(const char* fmt, ...);
 #define LS_LATENCY_CRITICAL() __builtin_amdgcn_s_setprio(LS_PRIO)
 #else
 #define LS_LATENCY_CRITICAL()
-#endif
-#ifdef LS_DEV_KNOBS
-inline int dev_knob(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
-#else
-constexpr int dev_knob(const char*, int dflt) { return dflt; }
 #endif
 
 constexpr int kWave = 64;
@@ -135,11 +129,6 @@ struct GemmAux {
     const float* w_rowmax = nullptr;   // [N]
     const void* w_planes = nullptr;    // pre-split W (gemm_presplit_w_launch): row n = K / 32 lines [hi: 32 f16 | lo: 32 f16] of s_n W[n, :], s_n from w_rowmax (required)
     float* out_rowmax = nullptr;       // [M][2 * cdiv(N, 128)]: max|out[row, 64-column block]| written by the epilogue (un-split launches only)
-    int noscale = 0;                   // LS_GEMM_RANGE=0: the round-2 arithmetic (no row scaling; |a| < 65504 required), A/B timing
-    // SLICE-MAJOR output (edge_staged.hip): the M rows are instances of slice_rows rows; element (m, n) goes to
-    // out[(m / slice_rows) * slice_rows * N + (n / slice_cols) * slice_rows * slice_cols + (m % slice_rows) * slice_cols + n % slice_cols] -- per instance
-    // N / slice_cols contiguous slices of [slice_rows][slice_cols] floats.  slice_cols = 4 | 8, slice_rows % 32 == 0; K = 32 / 64 GEMMs only (gemm_h2_smallk_kernel)
-    int slice_cols = 0, slice_rows = 0;
     const float* cs = nullptr;         // gemm_vn_dispatch only: partial column sums of A ([instance][cs_rows][3][C], edge.hip: attn_colsum) -- the kernel forms the
     int cs_rows = 0;                   // mean part of the conv itself instead of reading G (gemm.hip: gemm_vn_direct_kernel); ignored where that kernel is not taken
 };

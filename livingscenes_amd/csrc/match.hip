@@ -375,8 +375,7 @@ int cosine_scores_launch(const float* m0, const float* m1, int n, int m, int D, 
 }
 int greedy_match_launch(float* S, int n, int m, long long* m0, long long* m1, hipStream_t st) {
     if ((long long)n * m <= 1024) {
-        static const bool one_wave = dev_knob("LS_GREEDY_ONE_WAVE", 0) != 0;   // dev A/B: the round-3 kernel
-        if (one_wave || n * m <= 64) hipLaunchKernelGGL(greedy_match_wave_kernel, dim3(1), dim3(64), 0, st, S, n, m, m0, m1);
+        if (n * m <= 64) hipLaunchKernelGGL(greedy_match_wave_kernel, dim3(1), dim3(64), 0, st, S, n, m, m0, m1);
         else hipLaunchKernelGGL(greedy_match_quad_kernel, dim3(1), dim3(256), 0, st, S, n, m, m0, m1);
         LS_LAUNCH_CHECK();
         return LS_OK;

@@ -54,15 +54,6 @@ int edge_ft_attn_launch(const void* wplanes, const int32_t* knn, bool has_rows, 
                         float* out, float* rowmax, hipStream_t st, float* colsum = nullptr);
 int edge_ft_rowmax_parts(int Co, int Cin);
 int edge_presplit_wq_launch(const float* Wq, int Co, int Cin, void* planes, hipStream_t st);
-// edge_staged.hip: attention layers 2 - 4 with LDS-staged neighbour tiles (slice-major table)
-int edge_st_variant(int Co, int Cin);
-int edge_st_cs(int variant);
-int edge_st_pts(int variant);
-size_t edge_st_q_bytes(int Co, int Cin);
-bool edge_st_fits(int Co, int Cin, int Ns, int Nd);
-int edge_st_prepare_launch(const float* W, int Co, int Cin, float* Wp, void* qplanes, hipStream_t st);
-int edge_attn_staged_launch(const float* T, const float* cur, int Cin, const void* qplanes, const int32_t* knn, const int32_t* dst_rows, int B, int Nd, int Ns,
-                            int Co, int head_c, float neg_slope, float* out, hipStream_t st, float* rowmax);
 int gemm_dispatch_gather(const float*, int, const float*, int, const float*, float*, int, int, int, int, int, const int32_t*, int, int, hipStream_t, GemmAux aux = GemmAux());
 int gemm_dispatch_ws(const float*, int, const float*, int, const float*, float*, int, int, int, int, int, float*, hipStream_t, GemmAux aux = GemmAux());
 int gemm_dispatch_small(const float*, int, const float*, int, const float*, float*, int, int, int, int, int, float*, hipStream_t);
@@ -118,15 +109,11 @@ struct ls_model {
     void* wt_planes[LS_MAX_LAYERS] = {};   // attention layers whose input has 128 / 256 channels (released layers 5, 6): ALL table weights as per-head f16
                                            // MFMA fragment tiles (edge_fused.hip); used when the call's point counts fit the fused kernels
     void* wq_planes[LS_MAX_LAYERS] = {};   // attention layers 2 - 4: destination-side weights as f16 MFMA fragments (edge.hip, edge_attn_fq_kernel)
-    float* wst_w[LS_MAX_LAYERS] = {};      // attention layers 2 - 4, LDS-staged path (edge_staged.hip): neighbour-side weight rows in slice order ...
-    void* wst_q[LS_MAX_LAYERS] = {};       // ... and the destination-side weights as per-Q-block f16 MFMA fragments
     bool fuse_q = true;                    // LS_OPT_EDGE_FUSE_Q: destination side of attention layers 2 - 4 inside the edge kernel (edge.hip: edge_attn_fq_kernel)
     bool fuse_t = true;                    // LS_OPT_EDGE_FUSE_T: table-free 32-point attention layers (edge_fused.hip)
     int glob_fuse = 1;                     // LS_OPT_GLOB_FUSE (0 / 1 / 2; 2 = 1 + the operator export ls_vn_lna_f32 chains exact row maxima like the encoder's producers do): residual global conv as mean + GEMV launch and GEMM + VN activation in one kernel (gemm.hip: gemm_vn_kernel)
     int debug_edge = 0;                    // LS_OPT_DEBUG_EDGE: ls_vn_edgeconv_* runs 0 = table GEMM + edge kernel, 1 = the table GEMM only, 2 = the edge kernel only on the
                                            // tables already in the workspace (per-operator counter passes: scripts/pmc_ops.py)
-    int edge_staged = 0;                   // LS_OPT_EDGE_STAGED: 0 = never (default: measured slower than the gather kernel), 1 = when the grid fills the chip
-                                           // (B * Nd / PTS >= 128 workgroups), 2 = whenever the shape fits
     float* dec_wt = nullptr;            // transposed decoder weights [kin_l][out_l], built by the first backward call
     size_t dec_wt_off[12] = {};
     // max|row| of every weight matrix a GEMM reads (gemm.hip, GemmAux::w_rowmax): saves the kernels their pre-pass over W
@@ -157,9 +144,6 @@ struct ls_model {
                                    // race hunting by comparing workspaces (scripts/diag/)
     bool fps_side = true;          // LS_FPS_SIDE=0 runs the FPS chain on the caller's stream (A/B timing, race hunting)
     bool overlap_gemm = true;      // LS_GEMM_OVERLAP=0 serialises the table GEMMs on the caller's stream (A/B timing)
-    unsigned skip_mask = 0;        // (always 0 unless built with -DLS_DEV_KNOBS) LS_SKIP=knn,attn,...: dev timing knob -- after LS_SKIP_AFTER (default 3) ls_encode calls on this handle the named
-    int skip_after = 3, calls = 0; // launches are skipped (their outputs keep the previous call's values): marginal cost of a kernel family
-                                   // with many steps in flight.  Results are then STALE: never set outside scripts/dev.
     bool profiling = false;
     std::vector<ProfRec> prof;          // pending (un-collected) event pairs
     std::vector<hipEvent_t> ev_pool;    // recycled events
@@ -361,7 +345,7 @@ static size_t edge_table_floats(const ls_model_desc& d, int i, int B, int Ns, in
     return rows ? (size_t)B * 3 * ((size_t)Ns * pc + (size_t)Nd * (nc - pc)) : (size_t)B * Ns * 3 * nc;
 }
 struct EdgeTables { const float* Tq; int ldp, ldq, NQ, qvr; const float* cur = nullptr; const void* Wq = nullptr; int Cin = 0;
-                    const void* Wt = nullptr; const void* Ws = nullptr; };   // Ws != null: slice-major table + staged kernel (edge_staged.hip), Ws = its Q planes   // Wt != null: no table at all (edge_fused.hip); the table area holds that path's scratch   // cur != null: destination side fused into the edge kernel
+                    const void* Wt = nullptr; };   // Wt != null: no table at all (edge_fused.hip); the table area holds that path's scratch   // cur != null: destination side fused into the edge kernel
 
 // where the table(s) of layer i live in T and how the edge kernel reads them (no launch)
 static bool edge_fused(const ls_model* m, int i) {
@@ -379,20 +363,10 @@ static bool edge_fused_t(const ls_model* m, int i, int B, int Ns, int Nd, bool h
     return edge_ft_supported(Co, Cin, Ns, Nd, d.atten_head_c, has_rows) &&
            edge_ft_scratch_bytes(B, Ns, Nd, Cin, Co, has_rows) <= edge_table_floats(d, i, B, Ns, Nd, has_rows) * sizeof(float);
 }
-// LDS-staged path of attention layers 2 - 4 (edge_staged.hip): one 1024-thread workgroup per CU streams its instance's table through the LDS, so
-// it pays once B * Nd / PTS workgroups fill the chip; below that the gather kernel (edge_attn_fq_kernel) has the shorter critical path
-static bool edge_staged(const ls_model* m, int i, int B, int Ns, int Nd) {
-    const ls_model_desc& d = m->d;
-    if (!m->edge_staged || !m->wst_q[i] || !edge_fused(m, i) || i < d.atten_start_layer || d.atten_head_c != 16) return false;
-    const int Cin = layer_cin(d, i), Co = d.feat_dim[i];
-    if (!edge_st_fits(Co, Cin, Ns, Nd)) return false;
-    return m->edge_staged >= 2 || (long long)B * (Nd / edge_st_pts(edge_st_variant(Co, Cin))) >= 128;
-}
 static EdgeTables edge_tables_layout(const ls_model* m, int i, const float* cur, const int32_t* dst_rows, int B, int Ns, int Nd, float* T) {
     const ls_model_desc& d = m->d;
     const int Cin = layer_cin(d, i), nc = layer_ncols(d, i), pc = layer_pcols(d, i);
     if (edge_fused_t(m, i, B, Ns, Nd, dst_rows != nullptr)) { EdgeTables e{nullptr, 0, 0, 0, 0, cur, nullptr, Cin}; e.Wt = m->wt_planes[i]; return e; }
-    if (edge_staged(m, i, B, Ns, Nd)) { EdgeTables e{nullptr, pc, 0, 0, 0, cur, nullptr, Cin}; e.Ws = m->wst_q[i]; return e; }
     // (the fused kernel gathers table rows by 32-bit byte offsets: a batch whose neighbour-side table reaches 4 GB takes the table path)
     if (edge_fused(m, i) && edge_attn_fq_fits(B, Ns, pc)) return EdgeTables{nullptr, pc, 0, 0, 0, cur, m->wq_planes[i], Cin};
     if (dst_rows) return EdgeTables{T + (size_t)B * Ns * 3 * pc, pc, nc - pc, Nd, 0};
@@ -412,12 +386,6 @@ static int edge_tables(ls_model* m, int i, const float* cur, const int32_t* dst_
     // attention layers 2 - 4 (fused): only the neighbour-side table; the destination side is computed inside the edge kernel (edge.hip)
     GemmAux ax = aux_w(m, W, nc, Cin);
     ax.a_rowmax = a_rowmax; ax.a_parts = a_parts;
-    if (et.Ws) {   // slice-major neighbour-side table from the slice-ordered weight rows (edge_staged.hip)
-        GemmAux as = aux_w(m, m->wst_w[i], pc, Cin);
-        as.a_rowmax = a_rowmax; as.a_parts = a_parts;
-        as.slice_cols = 2 * edge_st_cs(edge_st_variant(d.feat_dim[i], Cin)); as.slice_rows = Ns * 3;
-        return gemm_dispatch(cur, Cin, m->wst_w[i], Cin, nullptr, T, pc, B * Ns * 3, pc, Cin, 0, gs, as);
-    }
     if (et.cur) return gemm_dispatch(cur, Cin, W, Cin, nullptr, T, pc, B * Ns * 3, pc, Cin, 0, gs, ax);
     if (dst_rows) {
         // down-sampled layer: P table on all source points, Q table only on the FPS-selected destination points
@@ -449,10 +417,6 @@ static int edge_apply(ls_model* m, int i, const float* T, const EdgeTables& et, 
             if (rm_parts) *rm_parts = edge_ft_rowmax_parts(Co, et.Cin);
             if (cs_out) *cs_rows = 1;
             return edge_ft_attn_launch(et.Wt, knn, dst_rows != nullptr, B, Ns, Nd, et.Cin, Co, d.neg_slope, const_cast<float*>(T), out, rm_out, st, cs_out);
-        }
-        if (et.Ws) {
-            if (rm_written) *rm_written = rm_out != nullptr;
-            return edge_attn_staged_launch(T, et.cur, et.Cin, et.Ws, knn, dst_rows, B, Nd, Ns, Co, d.atten_head_c, d.neg_slope, out, st, rm_out);
         }
         if (et.cur) {
             if (rm_written) *rm_written = rm_out != nullptr;
@@ -680,14 +644,9 @@ int ls_model_create(const ls_model_desc* desc, const float* blob_host, ls_model_
     m->d = *desc;
     if (const char* ev = getenv("LS_ENCODE_GRAPH")) m->use_graph = atoi(ev) != 0;
     if (const char* ev = getenv("LS_SDF_BF16X2")) m->sdf_bf16x2 = atoi(ev) != 0;
-#ifdef LS_DEV_KNOBS   // only in the variant library scripts/dev/marginal_cost.sh builds (-DLS_DEV_KNOBS): the release library cannot be made to skip work
+#ifdef LS_DEV_KNOBS   // race hunting (scripts/diag), only in a library built with -DLS_DEV_KNOBS
     if (const char* ev = getenv("LS_FPS_SIDE")) m->fps_side = atoi(ev) != 0;
     if (const char* ev = getenv("LS_DEBUG_LAYERS")) m->debug_layers = atoi(ev);
-    if (const char* ev = getenv("LS_SKIP")) {
-        const char* names[] = {"knn", "attn", "pool", "l0", "tables", "glob", "fps", "tail", "prologue", "hi32"};   // hi32: the attention of the 32-point layers only (with their operand images)
-        for (int i = 0; i < 10; ++i) if (strstr(ev, names[i])) m->skip_mask |= 1u << i;
-        if (const char* ea = getenv("LS_SKIP_AFTER")) m->skip_after = atoi(ea);
-    }
 #endif
     hipError_t e = hipMalloc((void**)&m->blob, (size_t)desc->blob_floats * sizeof(float));
     if (e != hipSuccess) { delete m; set_error("hipMalloc(model blob): %s", hipGetErrorString(e)); return LS_ERR_HIP; }
@@ -720,21 +679,10 @@ int ls_model_create(const ls_model_desc* desc, const float* blob_host, ls_model_
         const int rc = edge_presplit_wq_launch(m->blob + desc->off_edge[i] + (size_t)layer_pcols(*desc, i) * Cin, Co, Cin, m->wq_planes[i], nullptr);
         if (rc != LS_OK || hipDeviceSynchronize() != hipSuccess) { ls_model_destroy(m); return LS_ERR_HIP; }
     }
-    if (const char* ev = getenv("LS_EDGE_STAGED")) m->edge_staged = atoi(ev);
-    for (int i = desc->atten_start_layer; i < desc->num_layers && i >= 1; ++i) {   // LDS-staged attention (edge_staged.hip): slice-ordered P rows + Q-block planes
-        const int Co = desc->feat_dim[i], Cin = layer_cin(*desc, i);
-        if (desc->atten_head_c != 16 || !edge_st_variant(Co, Cin) || !m->wq_planes[i]) continue;
-        e = hipMalloc((void**)&m->wst_w[i], (size_t)4 * Co * Cin * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc(&m->wst_q[i], edge_st_q_bytes(Co, Cin));
-        if (e != hipSuccess) { set_error("model_create: %s", hipGetErrorString(e)); ls_model_destroy(m); return LS_ERR_HIP; }
-        const int rc = edge_st_prepare_launch(m->blob + desc->off_edge[i], Co, Cin, m->wst_w[i], m->wst_q[i], nullptr);
-        if (rc != LS_OK || hipDeviceSynchronize() != hipSuccess) { ls_model_destroy(m); return LS_ERR_HIP; }
-    }
     {   // row maxima of every matrix the GEMMs read (GemmAux::w_rowmax)
         std::vector<WSpec> specs;
         const ls_model_desc& d = *desc;
         for (int i = 1; i < d.num_layers; ++i) specs.push_back({m->blob + d.off_edge[i], (size_t)layer_ncols(d, i), layer_cin(d, i)});
-        for (int i = 1; i < d.num_layers; ++i) if (m->wst_w[i]) specs.push_back({m->wst_w[i], (size_t)layer_pcols(d, i), layer_cin(d, i)});
         for (int i = d.res_global_start_layer; i < d.num_layers; ++i)
             if (i >= 0) specs.push_back({m->blob + d.off_glob[i], (size_t)4 * d.feat_dim[i], d.feat_dim[i]});
         if (d.num_layers >= 1) specs.push_back({m->blob + d.off_convc, align_up((size_t)d.c_dim + 1, 4), d.feat_dim[d.num_layers - 1]});
@@ -765,8 +713,6 @@ void ls_model_destroy(ls_model_t* m) {
     for (int i = 0; i < LS_MAX_LAYERS; ++i) {
         if (m->wq_planes[i]) (void)hipFree(m->wq_planes[i]);
         if (m->wt_planes[i]) (void)hipFree(m->wt_planes[i]);
-        if (m->wst_w[i]) (void)hipFree(m->wst_w[i]);
-        if (m->wst_q[i]) (void)hipFree(m->wst_q[i]);
     }
     if (m->side) (void)hipStreamDestroy(m->side);
     if (m->side2) (void)hipStreamDestroy(m->side2);
@@ -797,7 +743,6 @@ int ls_model_set_option(ls_model_t* m, int option, int value) {
         case LS_OPT_SDF_TRAIN_SPLITK: m->train_splitk = value != 0; return LS_OK;
         case LS_OPT_SDF_BF16X2: m->sdf_bf16x2 = value != 0; return LS_OK;
         case LS_OPT_ENCODE_GRAPH: m->use_graph = value != 0; return LS_OK;
-        case LS_OPT_EDGE_STAGED: LS_REQUIRE(value >= 0 && value <= 2, "model_set_option: LS_OPT_EDGE_STAGED takes 0, 1 or 2"); m->edge_staged = value; drop_graphs(m); return LS_OK;
         case LS_OPT_EDGE_FUSE_Q: m->fuse_q = value != 0; drop_graphs(m); return LS_OK;
         case LS_OPT_EDGE_FUSE_T: m->fuse_t = value != 0; drop_graphs(m); return LS_OK;
         case LS_OPT_GLOB_FUSE: LS_REQUIRE(value >= 0 && value <= 2, "model_set_option: LS_OPT_GLOB_FUSE takes 0, 1 or 2"); m->glob_fuse = value; drop_graphs(m); return LS_OK;
@@ -813,7 +758,6 @@ int ls_model_get_option(const ls_model_t* m, int option, int* value) {
         case LS_OPT_SDF_TRAIN_SPLITK: *value = m->train_splitk ? 1 : 0; return LS_OK;
         case LS_OPT_SDF_BF16X2: *value = m->sdf_bf16x2 ? 1 : 0; return LS_OK;
         case LS_OPT_ENCODE_GRAPH: *value = m->use_graph ? 1 : 0; return LS_OK;
-        case LS_OPT_EDGE_STAGED: *value = m->edge_staged; return LS_OK;
         case LS_OPT_EDGE_FUSE_Q: *value = m->fuse_q ? 1 : 0; return LS_OK;
         case LS_OPT_EDGE_FUSE_T: *value = m->fuse_t ? 1 : 0; return LS_OK;
         case LS_OPT_GLOB_FUSE: *value = m->glob_fuse; return LS_OK;
@@ -844,13 +788,10 @@ static int encode_enqueue(ls_model_t* m, const EncPlan& p, const float* x, int B
     float* pts0 = F(p.o_pts[0]);
     float* centroid = F(p.o_centroid);
     float* scale0 = F(p.o_scale0);
-    const unsigned skip = (m->skip_mask && m->calls++ >= m->skip_after) ? m->skip_mask : 0u;   // dev timing knob (LS_SKIP), see ls_model
-    enum { SK_KNN = 1, SK_ATTN = 2, SK_POOL = 4, SK_L0 = 8, SK_TABLES = 16, SK_GLOB = 32, SK_FPS = 64, SK_TAIL = 128, SK_PROLOGUE = 256, SK_HI32 = 512 };
 
     {
         PROF(LS_K_PROLOGUE, 0, st);
-        if (skip & SK_PROLOGUE) rc = LS_OK;
-        else if (pre_normalised) rc = transpose_cloud_launch(x, B, N, pts0, st);
+        if (pre_normalised) rc = transpose_cloud_launch(x, B, N, pts0, st);
         else rc = prologue_launch(x, B, N, pts0, centroid, scale0, F(p.o_pro), st);
     }
     if (rc != LS_OK) return rc;
@@ -867,8 +808,8 @@ static int encode_enqueue(ls_model_t* m, const EncPlan& p, const float* x, int B
             toff += (size_t)B * p.levelN[l + 1];
             {
                 PROF(LS_K_FPS, l, fs);
-                rc = (skip & SK_FPS) ? LS_OK : fps_dispatch(F(p.o_pts[l]), nullptr, B, p.levelN[l], p.levelN[l + 1], flags, idx, F(p.o_pts[l + 1]),
-                                                              p.fpsws_bytes ? (void*)(ws + p.o_fpsws) : nullptr, p.fpsws_bytes, fs);
+                rc = fps_dispatch(F(p.o_pts[l]), nullptr, B, p.levelN[l], p.levelN[l + 1], flags, idx, F(p.o_pts[l + 1]),
+                                  p.fpsws_bytes ? (void*)(ws + p.o_fpsws) : nullptr, p.fpsws_bytes, fs);
             }
             if (rc != LS_OK) return rc;
             if (m->fps_side) LS_HIP_CHECK(hipEventRecord(m->ev_fps[l], fs));
@@ -911,10 +852,10 @@ static int encode_enqueue(ls_model_t* m, const EncPlan& p, const float* x, int B
         bool msg_rm = false;
         int msg_rm_parts = 1, msg_cs_rows = 0;
         if (i == 0) {
-            { PROF(LS_K_KNN, i, st); rc = (skip & SK_KNN) ? LS_OK : knn_dispatch(pts0, pts0, nullptr, B, Nd, Ns, Ns, 1, 16, flags, knn, nullptr, ws + p.o_knns, nullptr, 0, 0, st); }
+            { PROF(LS_K_KNN, i, st); rc = knn_dispatch(pts0, pts0, nullptr, B, Nd, Ns, Ns, 1, 16, flags, knn, nullptr, ws + p.o_knns, nullptr, 0, 0, st); }
             if (rc != LS_OK) return rc;
             LS_REQUIRE(!attn, "encoder: attention at layer 0 unsupported (atten_start_layer >= 1)");
-            { PROF(LS_K_EDGE_L0, i, st); rc = (skip & SK_L0) ? LS_OK : edge_l0_launch(pts0, knn, W + d.off_l0, B, Ns, Co, d.neg_slope, mp, st); }
+            { PROF(LS_K_EDGE_L0, i, st); rc = edge_l0_launch(pts0, knn, W + d.off_l0, B, Ns, Co, d.neg_slope, mp, st); }
             if (rc != LS_OK) return rc;
         } else {
             const int Cin = p.Cin[i];
@@ -926,31 +867,28 @@ static int encode_enqueue(ls_model_t* m, const EncPlan& p, const float* x, int B
                 LS_HIP_CHECK(hipStreamWaitEvent(gs, m->ev_feat[i], 0));
             }
             EdgeTables et;
-            if ((skip & SK_TABLES) || ((skip & SK_HI32) && Nd == 32)) { et = edge_tables_layout(m, i, cur, dst_rows, B, Ns, Nd, T); rc = LS_OK; }
-            else rc = edge_tables(m, i, cur, dst_rows, B, Ns, Nd, T, gs, et, cur_rm, cur_rm_parts);
+            rc = edge_tables(m, i, cur, dst_rows, B, Ns, Nd, T, gs, et, cur_rm, cur_rm_parts);
             if (rc != LS_OK) return rc;
             if (m->overlap_gemm) LS_HIP_CHECK(hipEventRecord(m->ev_tab[i], gs));
             {   // (no hints: the fused k-NN kernel derives its thresholds from its own sweep -- knn_mfma.hip)
                 PROF(LS_K_KNN, i, st);
-                rc = (skip & SK_KNN) ? LS_OK : knn_dispatch(cur, cur, dst_rows, B, Nd, Ns, Ns, Cin, 16, flags, knn, nullptr, ws + p.o_knns, nullptr, 0, 0, st);
+                rc = knn_dispatch(cur, cur, dst_rows, B, Nd, Ns, Ns, Cin, 16, flags, knn, nullptr, ws + p.o_knns, nullptr, 0, 0, st);
             }
             if (rc != LS_OK) return rc;
-            if (m->profiling && m->knn_stats && !(skip & SK_KNN) && knn_would_sweep(Cin, Ns, flags)) {
+            if (m->profiling && m->knn_stats && knn_would_sweep(Cin, Ns, flags)) {
                 // (outside the launch's event bracket) how many candidates got a canonical distance: ls_profile_knn_stats
                 rc = knn_sweep_stats_launch(ws + p.o_knns, B, Nd, Ns, Ns, m->knn_stats + 2 * i, st);
                 if (rc != LS_OK) return rc;
             }
             if (m->overlap_gemm) LS_HIP_CHECK(hipStreamWaitEvent(st, m->ev_tab[i], 0));
-            if ((skip & ((i >= d.atten_start_layer) ? SK_ATTN : SK_POOL)) || ((skip & SK_HI32) && Nd == 32)) rc = LS_OK;
-            else rc = edge_apply(m, i, T, et, knn, dst_rows, B, Nd, Ns, mp, st, glob ? F(p.o_rm_msg) : nullptr, &msg_rm, &msg_rm_parts,
-                                 glob ? F(p.o_cs) : nullptr, &msg_cs_rows);
+            rc = edge_apply(m, i, T, et, knn, dst_rows, B, Nd, Ns, mp, st, glob ? F(p.o_rm_msg) : nullptr, &msg_rm, &msg_rm_parts,
+                            glob ? F(p.o_cs) : nullptr, &msg_cs_rows);
             if (rc != LS_OK) return rc;
         }
         cur_rm = nullptr; cur_rm_parts = 0;
         if (glob) {
             bool out_rm = false;
-            if (skip & SK_GLOB) rc = LS_OK;
-            else rc = global_conv(m, i, msg, B, Nd, F(p.o_g), F(p.o_G), F(p.o_TG), F(p.o_gws), nxt, st, msg_rm ? F(p.o_rm_msg) : nullptr,
+            rc = global_conv(m, i, msg, B, Nd, F(p.o_g), F(p.o_G), F(p.o_TG), F(p.o_gws), nxt, st, msg_rm ? F(p.o_rm_msg) : nullptr,
                              F(p.o_rm_out[i & 1]), &out_rm, msg_rm_parts, F(p.o_cs), msg_cs_rows);
             if (rc != LS_OK) return rc;
             if (out_rm) { cur_rm = F(p.o_rm_out[i & 1]); cur_rm_parts = Co / 32; }
@@ -960,7 +898,6 @@ static int encode_enqueue(ls_model_t* m, const EncPlan& p, const float* x, int B
     if (p.nlevels > 0 && !joined && m->fps_side) LS_HIP_CHECK(hipStreamWaitEvent(st, m->ev_join, 0));
 
     // ---- tail
-    if (skip & SK_TAIL) return LS_OK;
     return encoder_tail(m, cur, B, p.NP, F(p.o_Tc), F(p.o_gws), pre_normalised ? nullptr : centroid, pre_normalised ? nullptr : scale0,
                         z_so3, z_inv, s_out, t_out, st, cur_rm, cur_rm_parts);
 }

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """dev: the attention layers 2 - 4 of the bench batch (B = 64 x 1024 points, released widths) ALONE -- table GEMM once, then the attention kernel `reps`
-times (LS_OPT_DEBUG_EDGE = 2) -- under each LS_OPT_EDGE_STAGED mode given: hipEvent time per launch.  Run it under rocprofv3 --pmc for counters
+times (LS_OPT_DEBUG_EDGE = 2): hipEvent time per launch.  Run it under rocprofv3 --pmc for counters
 (scripts/dev/attn_counters.sh)."""
 import argparse
 import os
@@ -15,7 +15,6 @@ from livingscenes_amd import _lib, ops, packing, synth  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--modes", default="0,2")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--layers", default="2,3,4")
@@ -42,24 +41,20 @@ def main():
         msg = m.edgeconv(i, cur, knn_l[i], rows[i])
         cur = m.vn_lna_global(i, msg) if i >= g0 else msg
     torch.cuda.synchronize()
-    res = {}
-    for mode in [int(v) for v in args.modes.split(",")]:
-        m.set_option(_lib.OPT_EDGE_STAGED, mode)
-        for i in [int(v) for v in args.layers.split(",")]:
-            m.set_option(_lib.OPT_DEBUG_EDGE, 0)
-            ref = m.edgeconv(i, src[i], knn_l[i], rows[i])          # table + attention (also warms up)
-            m.set_option(_lib.OPT_DEBUG_EDGE, 2)                    # the attention kernel only, on the tables in the workspace
-            evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.reps)]
-            for a, b in evs:
-                a.record()
-                out = m.edgeconv(i, src[i], knn_l[i], rows[i])
-                b.record()
-            torch.cuda.synchronize()
-            m.set_option(_lib.OPT_DEBUG_EDGE, 0)
-            ts = sorted(a.elapsed_time(b) * 1e3 for a, b in evs)
-            res[(mode, i)] = ts[len(ts) // 2]
-            assert os.environ.get("LS_LIB_PATH") or torch.equal(out, ref)      # (timing-variant libraries compute garbage on purpose)
-            print(f"mode {mode} layer {i}: attention alone {ts[len(ts) // 2]:.1f} us (min {ts[0]:.1f})", flush=True)
+    for i in [int(v) for v in args.layers.split(",")]:
+        m.set_option(_lib.OPT_DEBUG_EDGE, 0)
+        ref = m.edgeconv(i, src[i], knn_l[i], rows[i])          # table + attention (also warms up)
+        m.set_option(_lib.OPT_DEBUG_EDGE, 2)                    # the attention kernel only, on the tables in the workspace
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.reps)]
+        for a, b in evs:
+            a.record()
+            out = m.edgeconv(i, src[i], knn_l[i], rows[i])
+            b.record()
+        torch.cuda.synchronize()
+        m.set_option(_lib.OPT_DEBUG_EDGE, 0)
+        ts = sorted(a.elapsed_time(b) * 1e3 for a, b in evs)
+        assert os.environ.get("LS_LIB_PATH") or torch.equal(out, ref)      # (variant libraries need not match the release bit for bit)
+        print(f"layer {i}: attention alone {ts[len(ts) // 2]:.1f} us (min {ts[0]:.1f})", flush=True)
 
 
 if __name__ == "__main__":

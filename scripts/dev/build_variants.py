@@ -1,9 +1,9 @@
-"""Timing variants of liblivingscenes_hip.so (dev tool): gemm.hip rebuilt with -D<flags>, every other object reused.
+"""Compiler-flag variants of liblivingscenes_hip.so (dev tool): gemm.hip (or the sources named) rebuilt with extra flags, every other object reused.
 
     python scripts/dev/build_variants.py NAME[:file.hip[+file2.hip]]=-DFLAG[,-DFLAG2] ...   ->  livingscenes_amd/lib/variants/NAME/liblivingscenes_hip.so
     LS_LIB_PATH=livingscenes_amd/lib/variants/NAME/liblivingscenes_hip.so python bench.py --full ...
 
-The variants compute WRONG results where a flag removes arithmetic; they exist to price one part of a kernel."""
+Examples: -DLS_DEV_KNOBS (model.hip: the race-hunting switches LS_FPS_SIDE / LS_DEBUG_LAYERS), -DLS_KF_PK=0 (knn_mfma.hip: scalar bounds)."""
 import os
 import subprocess
 import sys

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """dev: the residual global conv of layer 2 (B = 64 x 512 points x 64 channels) alone, 30 times, through the operator export with LS_OPT_GLOB_FUSE = 2
-(row maxima + mean + the streaming kernel).  Run under rocprofv3 --kernel-trace --stats for the kernel's own duration (scripts/dev/vnd_variants.sh)."""
+(row maxima + mean + the streaming kernel).  Run under rocprofv3 --kernel-trace --stats for the kernel's own duration."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..", "..")))

@@ -188,62 +188,3 @@ def test_table_free_32_point_layers_match_the_table_path():
         m.set_option(_lib.OPT_EDGE_FUSE_T, prev)
     for a, b in zip(codes[1], codes[0]):
         assert relerr(a, b) < 2e-5, relerr(a, b)
-
-
-@pytest.mark.parametrize("B", [2, 3])
-def test_staged_attention_layers_vs_oracle_and_the_gather_kernel(B):
-    """Attention layers 2 - 4 at the released widths through the LDS-staged kernel (edge_staged.hip: slice-major table, slices streamed through the
-    LDS, ls_model_set_option(LS_OPT_EDGE_STAGED, 2) = whenever the shape fits) against oracle.net (1e-4 of the tensor maximum) and against the
-    row-gather kernel (edge_attn_fq_kernel, option 0).  Same products and the same arithmetic per edge and channel; the head / norm sums run in a
-    different order (per-channel chains + lane trees instead of four-channel chains), so the two kernels agree to 2e-6, not bit for bit
-    (vec_dgcnn_atten.py:205-219)."""
-    from oracle import net
-    from livingscenes_amd import _lib
-    N = 1024
-    cfg = synth.default_encoder_cfg()
-    w = synth.make_encoder_weights(cfg, 3)
-    x = synth.make_instances(B, N, seed=5, rigid=False)
-    x = (x - x.mean(-1, keepdim=True)) / 1.2
-    tr = {}
-    net.encoder_forward(w, cfg, x, trace=tr)
-    m = _hip(cfg, w)
-    d = _dev()
-    ds = cfg["down_sample_layers"]
-    prev = m.get_option(_lib.OPT_EDGE_STAGED)
-    for i in (2, 3, 4):
-        src = rows(tr[f"src_f_{i}"]).to(d)
-        rows_i = tr[f"fps_idx_{i}"].to(torch.int32).to(d) if i in ds else None
-        knn = tr[f"knn_idx_{i}"].to(torch.int32).to(d)
-        m.set_option(_lib.OPT_EDGE_STAGED, 2)
-        staged = m.edgeconv(i, src, knn, rows_i).clone()
-        again = m.edgeconv(i, src, knn, rows_i).clone()
-        m.set_option(_lib.OPT_EDGE_STAGED, 0)
-        gathered = m.edgeconv(i, src, knn, rows_i).clone()
-        m.set_option(_lib.OPT_EDGE_STAGED, prev)
-        assert torch.equal(staged, again), f"layer {i}: the staged kernel is not reproducible"
-        assert relerr(staged, rows(tr[f"msg_f_{i}"])) < TOL, f"staged attention layer {i} vs oracle"
-        assert relerr(staged, gathered) < 2e-6, f"staged vs gather kernel, layer {i}: {relerr(staged, gathered)}"
-
-
-def test_staged_attention_inside_the_encoder_vs_oracle():
-    """ls_encode with the staged attention forced on (LS_OPT_EDGE_STAGED = 2; a 2-instance batch is far below the automatic threshold) against
-    oracle.net run on the DEVICE's k-NN graph (features that differ by round-off may flip a feature-space near-tie; the flips themselves are
-    audited by test_hip_parity.py::test_encoder_forward_vs_oracle): FPS identical, codes within 1e-4 of their maxima."""
-    from oracle import net
-    from livingscenes_amd import _lib
-    cfg = synth.default_encoder_cfg()
-    w = synth.make_encoder_weights(cfg, 1)
-    m = _hip(cfg, w)
-    B, N = 2, 1024
-    x = synth.make_instances(B, N, seed=9, rigid=False)
-    x = (x - x.mean(-1, keepdim=True)) / 1.1
-    prev = m.set_option(_lib.OPT_EDGE_STAGED, 2)
-    hz, hi, hs, ht, knn_l, fps_l = m.encode(x.to(_dev()), pre_normalised=True, trace=True)
-    m.set_option(_lib.OPT_EDGE_STAGED, prev)
-    tr = {}
-    graph = {i: knn_l[i].cpu() for i in range(1, cfg["num_layers"])}
-    center, scale, z_so3, z_inv = net.encoder_forward(w, cfg, x, trace=tr, graph=graph)
-    for j, i in enumerate(cfg["down_sample_layers"]):
-        assert np.array_equal(fps_l[j].cpu().numpy(), tr[f"fps_idx_{i}"].numpy().astype(np.int32)), f"fps level {j}"
-    assert relerr(hz, z_so3) < TOL and relerr(hi, z_inv) < TOL
-    assert relerr(hs, scale) < TOL and relerr(ht, center.squeeze(1)) < TOL

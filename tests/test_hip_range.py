@@ -88,8 +88,7 @@ def test_gemm_tile_shape_does_not_change_a_bit(N, K):
 def test_wide_gemm_with_presplit_planes_equals_the_in_kernel_split():
     """gemm_w2_kernel (256 x 256 tiles) with the W operand PRE-SPLIT once per weight matrix (GemmAux::w_planes, gemm_presplit_w_kernel) against the
     same kernel splitting W itself: same split function, same products in the same order -- same bytes out, incl. the emitted row maxima, at a
-    chip-filling shape with a ragged last tile row.  (The kernel's other loop forms -- ping-pong waves, LDS-direct planes, the persistent grid --
-    exist in the development library only: scripts/dev/build_variants.py -DLS_DEV_KNOBS.)"""
+    chip-filling shape with a ragged last tile row."""
     from livingscenes_amd import ops
     g = torch.Generator().manual_seed(5)
     M, N, K = 65536 + 77, 768, 768

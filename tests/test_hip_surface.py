@@ -70,7 +70,8 @@ def test_sdf_decode_two_piece_mode_stays_inside_the_tolerance():
 def test_model_options_are_read_back_from_the_library():
     """ls_model_get_option returns what the HANDLE holds: the environment's value as the C side parsed it (atoi: "false" and "" are 0 --
     a Python-side mirror with `!= "0"` called both 1), then whatever ls_model_set_option stored; set_option's "previous value" is that
-    read-back, so a temporary change restores exactly the state it found.  Unknown options are errors, not zeros."""
+    read-back, so a temporary change restores exactly the state it found.  Unknown options (incl. the retired 4) are errors, not zeros,
+    for get and set alike."""
     import os, subprocess, sys
     code = (
         "import torch\n"
@@ -86,11 +87,14 @@ def test_model_options_are_read_back_from_the_library():
         "prev = hip.set_option(_lib.OPT_SDF_BF16X2, 1 - want[1])\n"
         "assert prev == want[1] and hip.get_option(_lib.OPT_SDF_BF16X2) == 1 - want[1]\n"
         "assert hip.set_option(_lib.OPT_SDF_BF16X2, prev) == 1 - want[1] and hip.get_option(_lib.OPT_SDF_BF16X2) == want[1]\n"
-        "try:\n"
-        "    hip.get_option(99)\n"
-        "    raise SystemExit('unknown option accepted')\n"
-        "except _lib.LsError:\n"
-        "    pass\n")
+        "set_raw = lambda o: _lib.check(_lib.load().ls_model_set_option(hip._h, o, 0), 'ls_model_set_option')\n"
+        "for o in (4, 99):\n"   # 4: the retired staged-attention option
+        "    for f in (hip.get_option, set_raw):\n"
+        "        try:\n"
+        "            f(o)\n"
+        "            raise SystemExit(f'unknown option {o} accepted by {f}')\n"
+        "        except _lib.LsError:\n"
+        "            pass\n")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     base = {k: v for k, v in os.environ.items() if k not in ("LS_SDF_BF16X2", "LS_ENCODE_GRAPH")}
     for env, want in (({}, "1,0,0"), ({"LS_SDF_BF16X2": "1", "LS_ENCODE_GRAPH": "1"}, "1,1,1"), ({"LS_SDF_BF16X2": "false", "LS_ENCODE_GRAPH": ""}, "1,0,0")):
