@@ -59,9 +59,9 @@ typedef enum {
 /* version of this C ABI: bumped whenever a signature or struct layout changes incompatibly (101: double-precision Adam hyper-parameters in
  * ls_adam_group / ls_adam_step_f32 / ls_se3_adam_step_f32, option 4 (LDS-staged attention); 102: LS_OPT_EDGE_FUSE_Q / _T, LS_OPT_GLOB_FUSE, LS_OPT_DEBUG_EDGE; the
  * library reads no development switches from the environment any more; 104: option 4 retired with the staged attention path, refused like
- * any unknown option).  ls_version() returns the value the LIBRARY was built with; a
+ * any unknown option; 105: the mesh metrics ls_mesh_contains_f64 / ls_mesh_distance_f64 / ls_mesh_sample_f64).  ls_version() returns the value the LIBRARY was built with; a
  * binding compares it with the header it was written against and refuses a mismatch (livingscenes_amd/_lib.py: load). */
-#define LS_ABI_VERSION 104
+#define LS_ABI_VERSION 105
 int ls_version(void);
 const char* ls_last_error(void);
 /* number of HIP devices visible, or a negative ls_status */
@@ -453,6 +453,40 @@ int ls_marching_cubes_f64(const double* volume, int nx, int ny, int nz, double i
 int ls_simplify_mesh_f64_host(const double* vertices_host, long long nv, const long long* faces_host, long long nf, int target_faces,
                               double aggressiveness, int initial_border, double* vertices_out_host, long long* faces_out_host,
                               long long* counts_out_host);
+
+/* ------------------------------------------------------------------------------------------------
+ * Reconstruction metrics of the reference's evaluate.py (csrc/meshmetrics.hip) on ONE triangle mesh: vertices [nv,3] float64, faces [nf,3]
+ * int32 (indices in [0, nv)), points [n,3] float64.  nf == 0 is an empty mesh: it contains nothing and is infinitely far away.
+ * Data-dependent sizes follow ls_marching_cubes_f64: the binned ops list every triangle in the cells of a grid; a call with entries == NULL
+ * writes the number of entries to the DEVICE long long count_out and stops (points and outputs are not read); the caller allocates
+ * entries [count] int32 and repeats the call with cap_entries >= count (with a smaller cap the outputs are undefined; nothing at or past
+ * cap_entries is written).  workspace: the ls_*_workspace_bytes query of the op (a bound computable from the dimensions).
+ * ---------------------------------------------------------------------------------------------- */
+
+/* libmesh.check_mesh_contains(mesh, points, hash_resolution) (lib_shape_prior/core/models/utils/occnet_utils/utils/libmesh/inside_mesh.py:5-154,
+ * triangle_hash.pyx), as called by evaluate.py:45 compute_volumetric_iou: inside_out [n] uint8 (0 / 1), BIT-IDENTICAL to the reference
+ * (same float64 operations in the same order, same 2-D hash of hash_resolution^2 cells).  2 <= hash_resolution <= 4096. */
+size_t ls_mesh_contains_workspace_bytes(int nf, int hash_resolution);
+int ls_mesh_contains_f64(const double* vertices, int nv, const int32_t* faces, int nf, const double* points, long long n, int hash_resolution,
+                         uint8_t* inside_out, int32_t* entries, long long cap_entries, long long* count_out, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
+/* |pcu.signed_distance_to_mesh(points, V, F)| under a cap, for evaluate.py:100-106 compute_sdf_recall (which only tests |sdf| < thres):
+ * dist_out [n] float64 = the distance from point i to the closest point of any triangle (Ericson, Real-Time Collision Detection 5.1.5;
+ * triangles of zero area as their edges) when it is < max_dist, +inf otherwise.  max_dist > 0 and finite. */
+size_t ls_mesh_distance_workspace_bytes(int nf);
+int ls_mesh_distance_f64(const double* vertices, int nv, const int32_t* faces, int nf, const double* points, long long n, double max_dist,
+                         double* dist_out, int32_t* entries, long long cap_entries, long long* count_out, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
+/* trimesh.sample.sample_surface(mesh, count) as called at evaluate.py:25 compute_chamfer_distance: face = first index whose cumulative area
+ * (a device scan: rounding differs from numpy's sequential cumsum) reaches u0 * total, (r1, r2) folded into the triangle when r1 + r2 > 1,
+ * p = v0 + (r1 (v1 - v0) + r2 (v2 - v0)).  The uniforms are reproducible where trimesh's are not: u = (splitmix64(key + (j + 1) * 0x9E3779B97F4A7C15)
+ * >> 11) * 2^-53 with key = splitmix64(seed + 0x9E3779B97F4A7C15) and j = 3 i + {0, 1, 2} for (u0, r1, r2) of sample i.
+ * points_out [count,3] float64, face_out [count] int64 or NULL.  nf > 0, count > 0. */
+size_t ls_mesh_sample_workspace_bytes(int nf);
+int ls_mesh_sample_f64(const double* vertices, int nv, const int32_t* faces, int nf, long long count, unsigned long long seed,
+                       double* points_out, int64_t* face_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Live per-kernel timing (bench.py's roofline leg): while enabled, every kernel ls_encode / ls_sdf_decode

@@ -18,7 +18,7 @@ FLAG_KNN_VALU_ONLY = 4
 FLAG_KABSCH_RAW_WEIGHTS = 8
 OPT_SDF_TRAIN_SPLITK, OPT_SDF_BF16X2, OPT_ENCODE_GRAPH = 1, 2, 3   # (4: retired, refused by the library)
 OPT_EDGE_FUSE_Q, OPT_EDGE_FUSE_T, OPT_GLOB_FUSE, OPT_DEBUG_EDGE, OPT_GEMM_OVERLAP = 5, 6, 7, 8, 9
-ABI_VERSION = 104   # == LS_ABI_VERSION in include/livingscenes_hip.h: a library of another version is refused (argument layouts differ)
+ABI_VERSION = 105   # == LS_ABI_VERSION in include/livingscenes_hip.h: a library of another version is refused (argument layouts differ)
 KABSCH_OK, KABSCH_RANK1, KABSCH_RANK0, KABSCH_NONFINITE = 0, 1, 2, 3
 
 
@@ -151,6 +151,12 @@ SIGNATURES = {
     "ls_mcubes_workspace_bytes": (_SZ, [_I, _I, _I]),
     "ls_marching_cubes_f64": (_I, [_P, _I, _I, _I, ctypes.c_double, _P, ctypes.c_longlong, _P, ctypes.c_longlong, _P, _P, _SZ, _P]),
     "ls_simplify_mesh_f64_host": (_I, [_P, ctypes.c_longlong, _P, ctypes.c_longlong, _I, ctypes.c_double, _I, _P, _P, _P]),
+    "ls_mesh_contains_workspace_bytes": (_SZ, [_I, _I]),
+    "ls_mesh_contains_f64": (_I, [_P, _I, _P, _I, _P, ctypes.c_longlong, _I, _P, _P, ctypes.c_longlong, _P, _P, _SZ, _P]),
+    "ls_mesh_distance_workspace_bytes": (_SZ, [_I]),
+    "ls_mesh_distance_f64": (_I, [_P, _I, _P, _I, _P, ctypes.c_longlong, _D, _P, _P, ctypes.c_longlong, _P, _P, _SZ, _P]),
+    "ls_mesh_sample_workspace_bytes": (_SZ, [_I]),
+    "ls_mesh_sample_f64": (_I, [_P, _I, _P, _I, ctypes.c_longlong, ctypes.c_ulonglong, _P, _P, _P, _SZ, _P]),
     "ls_profile_begin": (_I, [_P]),
     "ls_profile_end": (_I, [_P, ctypes.POINTER(ProfileEntry), _I, ctypes.POINTER(ctypes.c_int)]),
 }

@@ -1,11 +1,17 @@
-"""Evaluation metrics of the reference's evaluate.py that the 3RScan relocalisation loop uses.
+"""Evaluation metrics of the reference's evaluate.py, under the reference's names and signatures.
 
 chamfer_distance_torch (/root/reference/evaluate.py:111-123): both clouds are compared after the PREDICTED transform -- the
 source moved by the prediction against the target, and the target against itself moved by prediction o inverse(ground truth) --
 as mean nearest-neighbour SQUARED distance in each direction, summed.  The reference materialises the [n, m] squared-distance
 matrix; here the nearest neighbours come from the library's raw-cloud k-NN (ls_knn_f32, K = 1: wave-per-query kernel), whose
 distance is the same (dx^2 + dy^2 + dz^2) chain.  HIP tensors only, like every operator of this package.
+
+The reconstruction metrics (evaluate.py:12-109: compute_chamfer_distance, compute_volumetric_iou, compute_sdf_recall, and libmesh's
+check_mesh_contains) run on the device without trimesh / point_cloud_utils / the Cython triangle hash (csrc/meshmetrics.hip).  A mesh is
+anything with ``.vertices`` [nv,3] and ``.faces`` [nf,3] (trimesh, mesh_extractor2.SimpleMesh, numpy arrays or torch tensors); a point
+cloud (gt_points) anything with ``.vertices``.  An empty mesh (no faces) contains nothing and is infinitely far away.
 """
+import numpy as np
 import torch
 
 from . import ops
@@ -24,3 +30,93 @@ def chamfer_distance_torch(src, ref, pred_tsfm, gt_tsfm):
     dist_src = _nn_sq_dist(src_transformed, ref)
     dist_ref = _nn_sq_dist(ref, ref_inv_transformed)
     return dist_src.mean(dim=1) + dist_ref.mean(dim=1)
+
+
+# ------------------------------------------------------------------------------------------------ reconstruction metrics
+def _device():
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _points(x, device):
+    """[n,3] float64 HIP tensor of numpy / torch points (or an object with .vertices)"""
+    x = getattr(x, "vertices", x)
+    t = x.detach() if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float64)))
+    return t.to(device=device, dtype=torch.float64).reshape(-1, 3).contiguous()
+
+
+def _device_mesh(mesh, device):
+    """(V [nv,3] float64, F [nf,3] int32) on the device; the int64 faces meshes carry are range-checked and narrowed here."""
+    V = _points(mesh.vertices, device)
+    f = mesh.faces
+    F = f.detach().to(device=device, dtype=torch.int64) if torch.is_tensor(f) else torch.from_numpy(np.asarray(f, dtype=np.int64)).to(device)
+    F = F.reshape(-1, 3)
+    nv = V.shape[0]
+    if nv >= 2 ** 31:
+        raise ValueError(f"mesh has {nv} vertices: the mesh operators index vertices with int32 (nv < 2^31)")
+    if F.numel() and (int(F.min()) < 0 or int(F.max()) >= nv):
+        raise ValueError(f"mesh faces index vertices outside [0, {nv})")
+    return V, F.to(torch.int32).contiguous()
+
+
+def check_mesh_contains(mesh, points, hash_resolution=512):
+    """libmesh.check_mesh_contains (occnet_utils/utils/libmesh/inside_mesh.py:5-8): bool [n] numpy array, bit-identical to the reference
+    (same float64 operations, same 2-D hash).  A flat mesh (zero extent on an axis) contains nothing, as in the reference."""
+    dev = _device()
+    P = _points(points, dev)
+    V, F = _device_mesh(mesh, dev)
+    if P.shape[0] == 0:
+        return np.zeros(0, dtype=bool)
+    return ops.mesh_contains(V, F, P, hash_resolution).cpu().numpy()
+
+
+def _sample(mesh, count, seed, device):
+    V, F = _device_mesh(mesh, device)
+    return ops.mesh_sample(V, F, count, seed)[0]
+
+
+def compute_chamfer_distance(gt_points, gen_mesh, offset, scale, num_mesh_samples=30000, seed=0):
+    """evaluate.py:12-40: (gt_to_gen, gen_to_gt) = mean squared nearest-neighbour distance from the points of ``gt_points.vertices`` to
+    ``num_mesh_samples`` area-weighted samples of ``gen_mesh`` (moved by ``/ scale - offset``), and back.
+
+    ``seed`` is the one argument the reference does not have: trimesh draws the samples from numpy's unseeded global generator, so the
+    reference's value changes from run to run; here the samples are a fixed function of ``seed`` (ls_mesh_sample_f64).  Both clouds are
+    centred on the middle of gt's bounding box in float64 before the fp32 nearest-neighbour search (ls_knn_f32, K = 1; distances do not
+    change, and scans sit metres from the origin), and the means are accumulated in float64."""
+    dev = _device()
+    gt = _points(gt_points, dev)
+    gen = _sample(gen_mesh, int(num_mesh_samples), seed, dev) / scale - offset
+    c = (gt.min(0).values + gt.max(0).values) / 2 if gt.shape[0] else torch.zeros(3, dtype=torch.float64, device=dev)
+    a = (gt - c).float().reshape(1, -1, 3, 1).contiguous()
+    b = (gen - c).float().reshape(1, -1, 3, 1).contiguous()
+    _, d_ab = ops.knn(a, b, 1, return_dist=True)
+    _, d_ba = ops.knn(b, a, 1, return_dist=True)
+    return float(d_ab.double().mean()), float(d_ba.double().mean())
+
+
+def mesh_distance(mesh, points, max_dist):
+    """[n] float64 numpy: distance from each point to ``mesh`` where it is < max_dist, +inf elsewhere (ls_mesh_distance_f64)."""
+    dev = _device()
+    P = _points(points, dev)
+    V, F = _device_mesh(mesh, dev)
+    if P.shape[0] == 0:
+        return np.zeros(0)
+    return ops.mesh_distance(V, F, P, max_dist).cpu().numpy()
+
+
+def compute_sdf_recall(mesh1, mesh2, thres=0.1):
+    """evaluate.py:100-106: share of ``mesh2.vertices`` whose distance to ``mesh1`` is < thres (|pcu.signed_distance_to_mesh| < thres:
+    the sign is never needed).  The reference also computes a Chamfer distance here (:104) and discards it; this one does not."""
+    d = mesh_distance(mesh1, mesh2.vertices, thres)
+    return float(np.isfinite(d).mean()) if len(d) else float("nan")
+
+
+def compute_volumetric_iou(mesh1, mesh2, voxel_size=1. / 16):
+    """evaluate.py:42-45: share of ``mesh2.vertices`` inside ``mesh1`` (check_mesh_contains); ``voxel_size`` is unused, as in the reference."""
+    inside = check_mesh_contains(mesh1, mesh2.vertices)
+    return float(inside.mean()) if len(inside) else float("nan")
+
+
+def get_threshold_percentage(dist, thresholds):
+    """evaluate.py:88-98: share of ``dist`` <= t for every t in ``thresholds``."""
+    dist = np.asarray(dist)
+    return [(dist <= t).mean() for t in thresholds]

@@ -3,7 +3,8 @@
 the same npz semantics ({'pc': [n_obj,N,3], 'transform': [n_obj,4,4]}; GT = rescan_T @ inv(ref_T), :129; GT match =
 identity permutation, :87; symmetry-folded RRE min(r, |180-r|, |90-r|), :140; recalls at 5/10 degrees, :160-168).
 All instances of a scene are encoded in ONE batch and all pairs registered in ONE batched call (the reference loops
-pair by pair with B=1 encoder calls, :130).  No dataset I/O: the real FlyingShape npz files are not in the tree."""
+pair by pair with B=1 encoder calls, :130).  No dataset I/O: the real FlyingShape npz files are not in the tree.
+The reconstruction legs (eval_reconstruction, eval_3rscan_reconstruction) score meshes with the device metrics of evaluate.py."""
 import numpy as np
 import torch
 
@@ -194,3 +195,93 @@ def eval_3rscan_relocalization(dataset, solver, optim=True):
             "recall[RRE<10deg]": float(100 * (rre < 10).mean()) if len(rre) else float("nan"),
             "rre_median[RRE<10deg]": med(rre, rre < 10), "rte_median[RRE<10deg]": med(rte, rre < 10),
             "chamfer_median": float(np.median(cd)) if len(cd) else float("nan"), "shape": shape_l}
+
+
+# ------------------------------------------------------------------------------------------------ reconstruction evaluation
+def _recon_summary(cd, recall, iou=None):
+    cd, recall = np.asarray(cd, np.float64), np.asarray(recall, np.float64)
+    out = {"chamfer_mean": float(cd.mean()) if len(cd) else float("nan"),
+           "sdf_recall@0.7": float((recall > 0.7).mean() * 100) if len(recall) else float("nan")}
+    if iou is not None:
+        iou = np.asarray(iou, np.float64)
+        out.update({"viou_recall@0.5": float((iou > 0.5).mean() * 100) if len(iou) else float("nan"),
+                    "viou_mean": float(iou.mean() * 100) if len(iou) else float("nan"),
+                    "viou_median": float(np.median(iou) * 100) if len(iou) else float("nan")})
+    return out
+
+
+@torch.no_grad()
+def eval_reconstruction(scenes, solver, gt_meshes):
+    """eval_flyingshape.py:176-213: every instance of every scene is encoded (one batch per scene), meshed from its code
+    (``solver._mesh_from_latent``), moved back into its canonical frame by the inverse of the instance pose, and scored against its
+    ground-truth mesh ``gt_meshes[scene][instance]``: cd1 + cd2 (compute_chamfer_distance), SDF recall at 0.05 of the GT vertices
+    (compute_sdf_recall), V-IoU (compute_volumetric_iou).  An empty predicted mesh scores recall 0 and V-IoU 0 and has no Chamfer entry.
+    ``scenes``: dicts with 'pc' [n,N,3] and 'transform' [n,4,4] (the reference's npz keys) or synth.make_scene_pair's 'ref' / 'ref_T'.
+    -> {'chamfer_mean', 'sdf_recall@0.7', 'viou_recall@0.5', 'viou_mean', 'viou_median' (percent, as logged), 'cd', 'sdf_recall', 'viou',
+    'n_objects', 'n_empty'}."""
+    from .evaluate import compute_chamfer_distance, compute_sdf_recall, compute_volumetric_iou
+    from .mesh_extractor2 import make_mesh
+    dev = next(solver.model.parameters()).device
+    cd_l, rec_l, iou_l, n_obj, n_empty = [], [], [], 0, 0
+    for sc, gts in zip(scenes, gt_meshes):
+        pc = torch.as_tensor(sc["pc"] if "pc" in sc else sc["ref"]).to(dev).float().transpose(-1, -2).contiguous()
+        pose = torch.as_tensor(sc["transform"] if "transform" in sc else sc["ref_T"]).double()
+        codes = solver.model.encode(pc)
+        for i in range(pc.shape[0]):
+            code = {k: codes[k][i][None].detach() for k in ("z_inv", "z_so3", "s", "t")}
+            pred = solver._mesh_from_latent(code)
+            inv = inverse(pose[i][None])[0].numpy()                                  # [3,4]
+            pred = make_mesh(np.asarray(pred.vertices, np.float64) @ inv[:, :3].T + inv[:, 3], pred.faces)
+            n_obj += 1
+            if pred.vertices.shape[0] != 0:
+                cd1, cd2 = compute_chamfer_distance(gts[i], pred, offset=0, scale=1)
+                cd_l.append(cd1 + cd2)
+                rec_l.append(compute_sdf_recall(pred, gts[i], 0.05))
+                iou_l.append(compute_volumetric_iou(pred, gts[i]))
+            else:
+                n_empty += 1
+                rec_l.append(0.0)
+                iou_l.append(0.0)
+    out = _recon_summary(cd_l, rec_l, iou_l)
+    out.update({"cd": cd_l, "sdf_recall": rec_l, "viou": iou_l, "n_objects": n_obj, "n_empty": n_empty})
+    return out
+
+
+def eval_3rscan_reconstruction(dataset, solver, optim=True):
+    """eval_3rscan.py:466-502 over a ``rscan.Dataset_3RScan``: every kept instance of every reference scan is encoded from its padded
+    cloud (``model.encode_fps``), its code refined against the cloud (``solver._optimize_code``, when ``optim``; a code whose loss never
+    improved stays as encoded), meshed (``solver._mesh_from_latent``) and scored against ``<root>/val_set_recon/<ref_id>/objectId_<k>.ply``:
+    one-way Chamfer cd1 = compute_chamfer_distance(gt, pred, 0, 1)[0] and SDF recall = compute_sdf_recall(pred, gt, 0.05).  An empty
+    predicted mesh scores recall 0 and has no Chamfer entry.  -> {'chamfer_1way_mean', 'sdf_recall@0.7' (percent): the two numbers the
+    reference logs, 'cd', 'sdf_recall' (per object), 'n_objects', 'n_empty'}."""
+    import os.path as osp
+    from .evaluate import compute_chamfer_distance, compute_sdf_recall
+    from .mesh_extractor2 import make_mesh
+    from .rscan import load_ply_mesh
+    recon_gt = osp.join(dataset.root_path, "val_set_recon")
+    cd_l, rec_l, n_obj, n_empty = [], [], 0, 0
+    for i_s, scene in enumerate(dataset.scene_list):
+        ref_id = scene["reference"]
+        ref, _ = dataset._get_scene(i_s)
+        if ref is None:
+            continue
+        for i in range(ref["pc"].shape[0]):
+            oid = int(ref["objectId"][i])
+            gt = make_mesh(*load_ply_mesh(osp.join(recon_gt, ref_id, f"objectId_{oid}.ply")))
+            with torch.no_grad():
+                codes = solver.model.encode_fps(ref["pc"][i][None], ref["pc_mask"][i][None])
+            if optim:
+                refined = solver._optimize_code(codes, ref["pc"][i], ref["pc_mask"][i])
+                codes = refined if refined is not None else codes
+            pred = solver._mesh_from_latent(codes)
+            n_obj += 1
+            if pred.vertices.shape[0] != 0:
+                cd1, _ = compute_chamfer_distance(gt, pred, offset=0, scale=1)
+                cd_l.append(cd1)
+                rec_l.append(compute_sdf_recall(pred, gt, 0.05))
+            else:
+                n_empty += 1
+                rec_l.append(0.0)
+    s = _recon_summary(cd_l, rec_l)
+    return {"chamfer_1way_mean": s["chamfer_mean"], "sdf_recall@0.7": s["sdf_recall@0.7"], "cd": cd_l, "sdf_recall": rec_l,
+            "n_objects": n_obj, "n_empty": n_empty}

@@ -516,3 +516,56 @@ class HipModel:
         call(dev, "ls_sdf_backward", self._h, ptr(query), ptr(z_so3), ptr(z_inv), ptr(s), ptr(t), B, M, ptr(sdf), ptr(g), ptr(ws),
                                      ws.numel(), ptr(gq), ptr(gso3), ptr(ginv), ptr(gs), ptr(gt), stream_ptr(dev))
         return gq, gso3, ginv, gs, gt
+
+
+# ------------------------------------------------------------------------------------------------ mesh metrics (csrc/meshmetrics.hip)
+def _mesh_dev(V, F):
+    """V [nv,3] float64, F [nf,3] int32 HIP tensors (the caller converted and range-checked them: evaluate._device_mesh)."""
+    if V.dtype != torch.float64 or F.dtype != torch.int32 or V.dim() != 2 or F.dim() != 2 or V.shape[1] != 3 or F.shape[1] != 3:
+        raise _lib.LsError("mesh operators take vertices [nv,3] float64 and faces [nf,3] int32")
+    return V.contiguous(), F.contiguous()
+
+
+def _binned(name, ws_bytes, V, F, points, extra, out):
+    """Sizing call (entries = NULL -> bin entry count on the device), allocation, real call -- ls_marching_cubes_f64's convention."""
+    dev = V.device
+    counts = torch.empty(1, dtype=torch.int64, device=dev)
+    ws = _scratch(ws_bytes, dev)
+    nbytes = 0 if ws is None else ws.numel()
+    head = (ptr(V), V.shape[0], ptr(F), F.shape[0], ptr(points), points.shape[0]) + tuple(extra)
+    call(dev, name, *head, ptr(out), None, 0, ptr(counts), ptr(ws), nbytes, stream_ptr(dev))
+    n_entries = int(counts.item())
+    entries = torch.empty(max(n_entries, 1), dtype=torch.int32, device=dev)
+    call(dev, name, *head, ptr(out), ptr(entries), entries.numel(), ptr(counts), ptr(ws), nbytes, stream_ptr(dev))
+    return out
+
+
+def mesh_contains(V, F, points, hash_resolution=512):
+    """libmesh.check_mesh_contains on the device: points [n,3] float64 -> bool [n] (bit-identical to the reference)."""
+    V, F = _mesh_dev(V, F)
+    points = points.to(torch.float64).contiguous()
+    out = torch.empty(points.shape[0], dtype=torch.bool, device=V.device)
+    ws_bytes = load().ls_mesh_contains_workspace_bytes(F.shape[0], int(hash_resolution))
+    return _binned("ls_mesh_contains_f64", ws_bytes, V, F, points, [int(hash_resolution)], out)
+
+
+def mesh_distance(V, F, points, max_dist):
+    """Unsigned point-to-mesh distance under a cap: points [n,3] float64 -> float64 [n], +inf where the distance is >= max_dist."""
+    V, F = _mesh_dev(V, F)
+    points = points.to(torch.float64).contiguous()
+    out = torch.empty(points.shape[0], dtype=torch.float64, device=V.device)
+    ws_bytes = load().ls_mesh_distance_workspace_bytes(F.shape[0])
+    return _binned("ls_mesh_distance_f64", ws_bytes, V, F, points, [float(max_dist)], out)
+
+
+def mesh_sample(V, F, count, seed=0):
+    """Area-weighted surface samples (trimesh.sample.sample_surface's algorithm, counter-based uniforms of `seed`):
+    -> points [count,3] float64, face index [count] int64."""
+    V, F = _mesh_dev(V, F)
+    dev = V.device
+    pts = torch.empty(int(count), 3, dtype=torch.float64, device=dev)
+    face = torch.empty(int(count), dtype=torch.int64, device=dev)
+    ws = _scratch(load().ls_mesh_sample_workspace_bytes(F.shape[0]), dev)
+    call(dev, "ls_mesh_sample_f64", ptr(V), V.shape[0], ptr(F), F.shape[0], int(count), ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)),
+         ptr(pts), ptr(face), ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev))
+    return pts, face

@@ -92,6 +92,135 @@ def load_ply_vertices(path):
         return np.stack([v["x"], v["y"], v["z"]], axis=1).astype(np.float32)
 
 
+def _ply_header(f, path):
+    """-> (format, [(element name, count, [(prop name, dtype code) | (prop name, ('list', count code, item code))])])"""
+    if f.readline().strip() != b"ply":
+        raise ValueError(f"{path}: not a PLY file")
+    fmt, elems = None, []
+    while True:
+        line = f.readline()
+        if not line:
+            raise ValueError(f"{path}: PLY header not terminated")
+        tok = line.decode("ascii", "replace").split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            elems.append((tok[1], int(tok[2]), []))
+        elif tok[0] == "property":
+            if not elems:
+                raise ValueError(f"{path}: property before any element")
+            if tok[1] == "list":
+                elems[-1][2].append((tok[4], ("list", _PLY_TYPES[tok[2]], _PLY_TYPES[tok[3]])))
+            else:
+                elems[-1][2].append((tok[2], _PLY_TYPES[tok[1]]))
+        elif tok[0] == "end_header":
+            break
+    if fmt not in ("ascii", "binary_little_endian", "binary_big_endian"):
+        raise ValueError(f"{path}: unsupported PLY format {fmt}")
+    return fmt, elems
+
+
+def _fan(polys):
+    """triangles of polygons given as index lists (fan around the first corner, as trimesh triangulates on load)"""
+    tris = [(p[0], p[k], p[k + 1]) for p in polys for k in range(1, len(p) - 1)]
+    return np.asarray(tris, dtype=np.int64).reshape(-1, 3)
+
+
+def load_ply_mesh(path):
+    """(vertices [nv,3] float64, faces [nf,3] int64) of a PLY mesh: ascii or binary in either byte order, any scalar vertex / face
+    properties besides x y z and the face index list (``list uchar int vertex_indices``, ``list uint8 uint32 vertex_index`` ...);
+    polygons with more than three corners are split into fans.  A file without faces gives faces [0,3]."""
+    with open(path, "rb") as f:
+        fmt, elems = _ply_header(f, path)
+        V, F = None, np.zeros((0, 3), np.int64)
+        if fmt == "ascii":
+            lines = (ln for ln in f.read().decode("ascii", "replace").splitlines() if ln.strip())
+            for name, n, props in elems:
+                rows = [next(lines).split() for _ in range(n)]
+                if name == "vertex":
+                    names = [p[0] for p in props]
+                    if any(isinstance(p[1], tuple) for p in props):
+                        raise ValueError(f"{path}: list property on vertices is not supported")
+                    a = np.asarray(rows, dtype=np.float64).reshape(n, len(props))
+                    V = np.stack([a[:, names.index(c)] for c in "xyz"], axis=1)
+                elif name == "face":
+                    polys = []
+                    for r in rows:
+                        pos = 0
+                        for pname, pt in props:   # the index list may sit among other face properties
+                            if isinstance(pt, tuple):
+                                cnt = int(r[pos])
+                                if pname in ("vertex_indices", "vertex_index"):
+                                    polys.append([int(v) for v in r[pos + 1:pos + 1 + cnt]])
+                                pos += 1 + cnt
+                            else:
+                                pos += 1
+                    F = _fan(polys)
+        else:
+            end = "<" if fmt == "binary_little_endian" else ">"
+            for name, n, props in elems:
+                lists = [p for p in props if isinstance(p[1], tuple)]
+                if not lists:
+                    dt = np.dtype([(pn, end + pt) for pn, pt in props])
+                    a = np.frombuffer(f.read(n * dt.itemsize), dtype=dt, count=n)
+                    if name == "vertex":
+                        V = np.stack([a["x"], a["y"], a["z"]], axis=1).astype(np.float64)
+                    continue
+                if name != "face" or len(lists) != 1:
+                    raise ValueError(f"{path}: list properties are supported on faces only (one index list)")
+                pre = [(pn, end + pt) for pn, pt in props[:props.index(lists[0])]]
+                post = [(pn, end + pt) for pn, pt in props[props.index(lists[0]) + 1:]]
+                cnt_t, idx_t = end + lists[0][1][1], end + lists[0][1][2]
+                # all triangles (what mesh tools write): one structured read
+                tri_dt = np.dtype(pre + [("cnt", cnt_t), ("idx", idx_t, (3,))] + post)
+                start = f.tell()
+                a = np.frombuffer(f.read(n * tri_dt.itemsize), dtype=tri_dt, count=n) if n else np.zeros(0, tri_dt)
+                if len(a) == n and (a["cnt"] == 3).all():
+                    F = a["idx"].astype(np.int64)
+                    continue
+                f.seek(start)   # general polygons: record by record
+                pre_b = int(sum(np.dtype(t).itemsize for _, t in pre))
+                post_b = int(sum(np.dtype(t).itemsize for _, t in post))
+                cnt_dt, idx_dt = np.dtype(cnt_t), np.dtype(idx_t)
+                polys = []
+                for _ in range(n):
+                    f.read(pre_b)
+                    c = int(np.frombuffer(f.read(cnt_dt.itemsize), dtype=cnt_dt)[0])
+                    polys.append(np.frombuffer(f.read(c * idx_dt.itemsize), dtype=idx_dt).astype(np.int64).tolist())
+                    f.read(post_b)
+                F = _fan(polys)
+        if V is None:
+            raise ValueError(f"{path}: no vertex element")
+        return V, F
+
+
+def write_ply_mesh(path, vertices, faces, binary="little", face_types=("uchar", "int")):
+    """PLY mesh writer (test fixtures): ``binary`` in {"little", "big", None (= ascii)}; double x y z, the faces as
+    ``list <face_types[0]> <face_types[1]> vertex_indices``."""
+    V = np.asarray(vertices, np.float64).reshape(-1, 3)
+    F = np.asarray(faces, np.int64).reshape(-1, 3)
+    fmt = {"little": "binary_little_endian", "big": "binary_big_endian", None: "ascii"}[binary]
+    hdr = ["ply", f"format {fmt} 1.0", "comment written by livingscenes_amd.rscan", f"element vertex {len(V)}", "property double x",
+           "property double y", "property double z", f"element face {len(F)}",
+           f"property list {face_types[0]} {face_types[1]} vertex_indices", "end_header"]
+    with open(path, "wb") as f:
+        f.write(("\n".join(hdr) + "\n").encode("ascii"))
+        if binary is None:
+            for v in V:
+                f.write((" ".join(repr(float(c)) for c in v) + "\n").encode("ascii"))
+            for t in F:
+                f.write(("3 " + " ".join(str(int(i)) for i in t) + "\n").encode("ascii"))
+            return
+        end = "<" if binary == "little" else ">"
+        f.write(V.astype(end + "f8").tobytes())
+        dt = np.dtype([("cnt", end + _PLY_TYPES[face_types[0]]), ("idx", end + _PLY_TYPES[face_types[1]], (3,))])
+        a = np.zeros(len(F), dtype=dt)
+        a["cnt"], a["idx"] = 3, F
+        f.write(a.tobytes())
+
+
 def _mat4(flat, device):
     """16 numbers, column-major -> [1,4,4] (eval_3rscan.py:171: reshape(1,4,4).transpose(-1,-2))"""
     return torch.tensor(flat, dtype=torch.float32, device=device).reshape(1, 4, 4).transpose(-1, -2).contiguous()

@@ -129,10 +129,8 @@ def _rand_rot(rng):
                      [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
 
 
-def canonical_shape(N, seed):
-    """A chair-like union of boxes sampled on its surfaces/volume: seat slab + back slab + 4 legs.
-    Per-seed proportions make instances distinguishable (needed for the matcher tests)."""
-    rng = _rng(seed, "shape")
+def _chair_boxes(rng):
+    """the boxes ((x0, x1), (y0, y1), (z0, z1)) of canonical_shape's chair: seat slab + back slab + 4 legs (6 draws of rng)"""
     pr = rng.random(6)
     w, d, h = 0.35 + 0.15 * pr[0], 0.35 + 0.15 * pr[1], 0.35 + 0.25 * pr[2]
     seat_t, back_h, leg_w = 0.04 + 0.04 * pr[3], 0.3 + 0.3 * pr[4], 0.03 + 0.03 * pr[5]
@@ -142,12 +140,45 @@ def canonical_shape(N, seed):
         for sy in (-1, 1):
             cx, cy = sx * (w - leg_w), sy * (d - leg_w)
             boxes.append(((cx - leg_w, cx + leg_w), (cy - leg_w, cy + leg_w), (-h, 0.0)))
+    return boxes
+
+
+def canonical_shape(N, seed):
+    """A chair-like union of boxes sampled on its surfaces/volume: seat slab + back slab + 4 legs.
+    Per-seed proportions make instances distinguishable (needed for the matcher tests)."""
+    rng = _rng(seed, "shape")
+    boxes = _chair_boxes(rng)
     vol = np.array([(b[0][1] - b[0][0]) * (b[1][1] - b[1][0]) * (b[2][1] - b[2][0]) + 1e-3 for b in boxes])
     which = rng.choice(len(boxes), size=N, p=vol / vol.sum())
     u = rng.random((N, 3))
     lo = np.array([[b[a][0] for a in range(3)] for b in boxes])[which]
     hi = np.array([[b[a][1] for a in range(3)] for b in boxes])[which]
     return (lo + u * (hi - lo)).astype(np.float64)
+
+
+def canonical_mesh(seed, res=48, device="cuda"):
+    """Watertight surface of canonical_shape(., seed)'s box union: marching cubes (the device kernel, mesh_extractor2.marching_cubes) of
+    the analytic signed distance min_b sdf_box_b on a res^3 lattice that reaches two cells past the union on every side.  (A union of
+    separately triangulated boxes would not be watertight: its inside test would be ill-defined where boxes overlap.)
+    -> mesh_extractor2.make_mesh(vertices [nv,3] float64, faces [nf,3] int64) in the canonical frame."""
+    import torch
+    from .mesh_extractor2 import make_mesh, marching_cubes
+    boxes = np.asarray(_chair_boxes(_rng(seed, "shape")), np.float64)     # [nb, 3, 2]
+    lo, hi = boxes[:, :, 0].min(0), boxes[:, :, 1].max(0)
+    step = (hi - lo).max() / (res - 5)
+    lo = lo - 2 * step
+    n = np.ceil((hi + 2 * step - lo) / step).astype(int) + 1
+    ax = [lo[a] + step * np.arange(n[a]) for a in range(3)]
+    g = np.stack(np.meshgrid(*ax, indexing="ij"), -1)                        # [nx,ny,nz,3]
+    sdf = np.full(g.shape[:3], np.inf)
+    for b in boxes:
+        c, e = (b[:, 0] + b[:, 1]) / 2, (b[:, 1] - b[:, 0]) / 2
+        q = np.abs(g - c) - e
+        d = np.linalg.norm(np.maximum(q, 0), axis=-1) + np.minimum(q.max(-1), 0)
+        sdf = np.minimum(sdf, d)
+    v, f = marching_cubes(torch.from_numpy(sdf).to(device), 0.0)
+    v = v.cpu().numpy()
+    return make_mesh(lo + (v - 0.5) * step, f.cpu().numpy())
 
 
 def make_instances(B, N=1024, seed=0, rigid=True):
