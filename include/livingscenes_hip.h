@@ -59,9 +59,10 @@ typedef enum {
 /* version of this C ABI: bumped whenever a signature or struct layout changes incompatibly (101: double-precision Adam hyper-parameters in
  * ls_adam_group / ls_adam_step_f32 / ls_se3_adam_step_f32, option 4 (LDS-staged attention); 102: LS_OPT_EDGE_FUSE_Q / _T, LS_OPT_GLOB_FUSE, LS_OPT_DEBUG_EDGE; the
  * library reads no development switches from the environment any more; 104: option 4 retired with the staged attention path, refused like
- * any unknown option; 105: the mesh metrics ls_mesh_contains_f64 / ls_mesh_distance_f64 / ls_mesh_sample_f64).  ls_version() returns the value the LIBRARY was built with; a
+ * any unknown option; 105: the mesh metrics ls_mesh_contains_f64 / ls_mesh_distance_f64 / ls_mesh_sample_f64; 106: ls_model_desc.dec_input and
+ * off_dec_xyz_t, the invariant decoder_type "deepsdf").  ls_version() returns the value the LIBRARY was built with; a
  * binding compares it with the header it was written against and refuses a mismatch (livingscenes_amd/_lib.py: load). */
-#define LS_ABI_VERSION 105
+#define LS_ABI_VERSION 106
 int ls_version(void);
 const char* ls_last_error(void);
 /* number of HIP devices visible, or a negative ls_status */
@@ -226,10 +227,11 @@ typedef struct {
     int32_t center_pred_scale;
     float scale_factor;
     float neg_slope;
-    /* decoder: DeepSDF_Decoder (deepsdf_decoder.py:12-57), decoder_type "inner_deepsdf" */
+    /* decoder: DeepSDF_Decoder (deepsdf_decoder.py:12-57) behind FieldWrapper (model_utils.py:236-251) */
     int32_t dec_num_linear;             /* number of linear layers (9), 0 = no decoder packed */
-    int32_t dec_width;                  /* hidden width (768) */
+    int32_t dec_width;                  /* hidden width (768 released, 512 invariant ablation) */
     int32_t dec_latent_in;              /* layer that re-concatenates the input (4), -1 = none */
+    int32_t dec_input;                  /* LS_DEC_INNER / LS_DEC_XYZ: what the code-fed layers read (below) */
     /* offsets (in floats) into the packed blob; layouts documented in livingscenes_amd/packing.py */
     int64_t off_l0;                     /* [6][feat_dim[0]] layer-0 folded rows */
     int64_t off_edge[LS_MAX_LAYERS];    /* layer i>=1: [ncols_i][feat_dim[i-1]] folded per-point weights */
@@ -243,9 +245,19 @@ typedef struct {
     int64_t off_dec_inv_t[12];          /* layers fed by the code (0 and latent_in): Wa^T [latent][out] */
     int64_t off_dec_so3_t[12];          /*   "    Wb^T [latent][out] */
     int64_t off_dec_len[12];            /*   "    w_len [out] */
+    int64_t off_dec_xyz_t[12];          /*   "    LS_DEC_XYZ only: W_xyz^T [3][out] (the columns that multiply the raw query) */
     int64_t blob_floats;
 } ls_model_desc;
 
+/* ls_model_desc.dec_input: the decoder's input u per query, and what the code-fed layers (0 and latent_in) fold per instance
+ *   LS_DEC_INNER  decoder_type "inner_deepsdf" (released): u = [z_inv | <q, z_so3_c>_c | |q|], q = (query - t) / s, width 2 c_dim + 1;
+ *                 off_dec_inv_t / off_dec_so3_t / off_dec_len hold the three column blocks of W
+ *   LS_DEC_XYZ    decoder_type "deepsdf" (invariant ablation): u = [z_inv | query], the RAW query, width c_dim + 3;
+ *                 off_dec_inv_t / off_dec_xyz_t hold the two column blocks; off_dec_so3_t / off_dec_len are unused.
+ *                 The SDF then does not depend on z_so3, s or t: the ls_sdf_* calls ignore them (they may be NULL), and ls_sdf_backward
+ *                 writes exact zeros to grad_z_so3, grad_s and grad_t where they are given (each may be NULL) */
+#define LS_DEC_INNER 0
+#define LS_DEC_XYZ 1
 int ls_model_create(const ls_model_desc* desc_host, const float* blob_host, ls_model_t** out);
 void ls_model_destroy(ls_model_t* m);
 /* per-handle switches (defaults in brackets) */

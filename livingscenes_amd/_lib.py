@@ -18,7 +18,8 @@ FLAG_KNN_VALU_ONLY = 4
 FLAG_KABSCH_RAW_WEIGHTS = 8
 OPT_SDF_TRAIN_SPLITK, OPT_SDF_BF16X2, OPT_ENCODE_GRAPH = 1, 2, 3   # (4: retired, refused by the library)
 OPT_EDGE_FUSE_Q, OPT_EDGE_FUSE_T, OPT_GLOB_FUSE, OPT_DEBUG_EDGE, OPT_GEMM_OVERLAP = 5, 6, 7, 8, 9
-ABI_VERSION = 105   # == LS_ABI_VERSION in include/livingscenes_hip.h: a library of another version is refused (argument layouts differ)
+DEC_INNER, DEC_XYZ = 0, 1   # ModelDesc.dec_input: decoder_type "inner_deepsdf" / "deepsdf" (LS_DEC_* in the header)
+ABI_VERSION = 106   # == LS_ABI_VERSION in include/livingscenes_hip.h: a library of another version is refused (argument layouts differ)
 KABSCH_OK, KABSCH_RANK1, KABSCH_RANK0, KABSCH_NONFINITE = 0, 1, 2, 3
 
 
@@ -43,6 +44,7 @@ class ModelDesc(ctypes.Structure):
         ("dec_num_linear", ctypes.c_int32),
         ("dec_width", ctypes.c_int32),
         ("dec_latent_in", ctypes.c_int32),
+        ("dec_input", ctypes.c_int32),
         ("off_l0", ctypes.c_int64),
         ("off_edge", ctypes.c_int64 * LS_MAX_LAYERS),
         ("off_glob", ctypes.c_int64 * LS_MAX_LAYERS),
@@ -55,6 +57,7 @@ class ModelDesc(ctypes.Structure):
         ("off_dec_inv_t", ctypes.c_int64 * 12),
         ("off_dec_so3_t", ctypes.c_int64 * 12),
         ("off_dec_len", ctypes.c_int64 * 12),
+        ("off_dec_xyz_t", ctypes.c_int64 * 12),
         ("blob_floats", ctypes.c_int64),
     ]
 

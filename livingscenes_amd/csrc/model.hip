@@ -73,20 +73,20 @@ int vn_act_rows_launch(const float*, int, const float*, int, int, int, int, floa
 int tail_launch(const float*, int, int, int, int, const float*, const float*, const float*, float, float, int, int, const float*,
                 const float*, float*, float*, float*, float*, hipStream_t);
 int sdf_prep_launch(const float*, const float*, const float*, const float*, const float*, const float*, int, int, int, float*,
-                    float*, hipStream_t);
+                    float*, bool, hipStream_t);
 int sdf_affine_launch(const float*, const float*, const float*, const float*, const float*, int, int, int, int, int, float*,
-                      hipStream_t, float* rowmax = nullptr);
+                      bool, hipStream_t, float* rowmax = nullptr);
 int sdf_out_launch(const float*, int, int, const float*, const float*, long long, float*, hipStream_t);
 int sdf_affine_rows_launch(const float*, const int32_t*, const float*, const float*, const float*, const float*, long long, int, int, int,
-                           float*, hipStream_t, float* rowmax = nullptr);
+                           float*, bool, hipStream_t, float* rowmax = nullptr);
 int sdf_out_bwd_launch(const float*, const float*, const float*, const float*, int, int, long long, float*, hipStream_t, float* rowmax = nullptr,
                        const float* wmax = nullptr);
 int relu_mask_launch(float*, const float*, long long, int, int, hipStream_t);
 int sdf_affine_bwd_launch(const float*, const float*, const float*, const float*, const float*, int, int, int, int, int, float*, float*,
-                          float*, bool, hipStream_t);
+                          float*, bool, bool, hipStream_t);
 int sdf_code_grad_launch(const float*, const float*, const float*, const float*, const float*, const float*, const float*, const float*,
-                         int, int, int, float*, float*, hipStream_t);
-int sdf_query_grad_launch(const float*, const float*, const float*, const float*, int, int, float*, float*, float*, hipStream_t);
+                         int, int, int, float*, float*, bool, hipStream_t);
+int sdf_query_grad_launch(const float*, const float*, const float*, const float*, int, int, float*, float*, float*, bool, hipStream_t);
 int transpose_launch(const float*, int, int, float*, hipStream_t);
 int cosine_scores_launch(const float*, const float*, int, int, int, float*, float*, hipStream_t);
 int greedy_match_launch(float*, int, int, long long*, long long*, hipStream_t);
@@ -640,6 +640,7 @@ int ls_icp_f32(const float* X, const float* Y, const float* R0, const float* T0,
 int ls_model_create(const ls_model_desc* desc, const float* blob_host, ls_model_t** out) {
     LS_REQUIRE(desc && blob_host && out, "model_create: null argument");
     LS_REQUIRE(desc->blob_floats > 0, "model_create: empty blob");
+    LS_REQUIRE(desc->dec_input == LS_DEC_INNER || desc->dec_input == LS_DEC_XYZ, "model_create: unknown dec_input %d", desc->dec_input);
     ls_model* m = new ls_model();
     m->d = *desc;
     if (const char* ev = getenv("LS_ENCODE_GRAPH")) m->use_graph = atoi(ev) != 0;
@@ -1068,11 +1069,18 @@ int ls_encoder_tail_f32(ls_model_t* m, const float* f, const float* centroid, co
 }
 
 // ------------------------------------------------------------------------------------------------ SDF decode
+static bool dec_xyz(const ls_model_desc& d) { return d.dec_input == LS_DEC_XYZ; }
+// width of the decoder input u: [z_inv | <q, z_so3> | |q|] (LS_DEC_INNER) or [z_inv | query] (LS_DEC_XYZ)
+static int dec_in_width(const ls_model_desc& d) { return dec_xyz(d) ? d.c_dim + 3 : 2 * d.c_dim + 1; }
 static int dec_out(const ls_model_desc& d, int l) {  // padded output width of linear layer l
     const int nl = d.dec_num_linear;
     if (l == nl - 1) return 1;
-    if (d.dec_latent_in >= 0 && l + 1 == d.dec_latent_in) return (int)align_up((size_t)(d.dec_width - (2 * d.c_dim + 1)), 4);
+    if (d.dec_latent_in >= 0 && l + 1 == d.dec_latent_in) return (int)align_up((size_t)(d.dec_width - dec_in_width(d)), 4);
     return d.dec_width;
+}
+// the per-instance table of the code-fed layer l that multiplies the query (sdf_prep_launch's so3_t argument)
+static const float* dec_q_table(const ls_model_t* m, int l) {
+    return m->blob + (dec_xyz(m->d) ? m->d.off_dec_xyz_t[l] : m->d.off_dec_so3_t[l]);
 }
 
 // split-K scratch (floats) that covers every GEMM of the decoder forward and backward at `rows` query rows
@@ -1164,26 +1172,27 @@ static int sdf_forward(ls_model_t* m, const SdfBuffers& sb, const float* query, 
     const long long rows = row_inst ? (long long)M : (long long)B * M;
     const ls_model_desc& d = m->d;
     const int w = d.dec_width, L = d.c_dim, nl = d.dec_num_linear, li = d.dec_latent_in;
+    const bool xyz = dec_xyz(d);   // LS_DEC_XYZ: z_so3, s and t are not read
     const float* W = m->blob;
     int rc;
     {
         PROF(LS_K_SDF_PREP, 0, st);
-        rc = sdf_prep_launch(W + d.off_dec_inv_t[0], W + d.off_dec_so3_t[0], W + d.off_dec_len[0], W + d.off_dec_b[0], z_so3,
-                             z_inv, B, L, w, sb.A0, sb.b0, st);
+        rc = sdf_prep_launch(W + d.off_dec_inv_t[0], dec_q_table(m, 0), W + d.off_dec_len[0], W + d.off_dec_b[0], z_so3,
+                             z_inv, B, L, w, sb.A0, sb.b0, xyz, st);
         if (rc == LS_OK && li >= 0)
-            rc = sdf_prep_launch(W + d.off_dec_inv_t[li], W + d.off_dec_so3_t[li], W + d.off_dec_len[li], W + d.off_dec_b[li],
-                                 z_so3, z_inv, B, L, w, sb.A4, sb.b4, st);
+            rc = sdf_prep_launch(W + d.off_dec_inv_t[li], dec_q_table(m, li), W + d.off_dec_len[li], W + d.off_dec_b[li],
+                                 z_so3, z_inv, B, L, w, sb.A4, sb.b4, xyz, st);
     }
     if (rc != LS_OK) return rc;
-    // layer 0: pure affine in (q, |q|)
+    // layer 0: pure affine in (q, |q|) (LS_DEC_XYZ: in the raw query)
     // operand range of the GEMMs (gemm.hip, GemmAux): every kernel that writes an activation also writes its row maxima, the GEMM that
     // reads it takes them instead of scanning its A rows; the weights carry theirs from ls_model_create
     const bool chain = !m->sdf_bf16x2;
     bool have = chain;   // sb.rm[ri] holds the row maxima of h[l - 1], rm_parts per row
     int ri = 0, rm_parts = sdf_affine_rowmax_parts(w);
     { PROF(LS_K_SDF_AFFINE, 0, st);
-      rc = row_inst ? sdf_affine_rows_launch(query, row_inst, s, t, sb.A0, sb.b0, rows, w, w, 0, sb.h[0], st, chain ? sb.rm[0] : nullptr)
-                    : sdf_affine_launch(query, s, t, sb.A0, sb.b0, B, M, w, w, 0, sb.h[0], st, chain ? sb.rm[0] : nullptr); }
+      rc = row_inst ? sdf_affine_rows_launch(query, row_inst, s, t, sb.A0, sb.b0, rows, w, w, 0, sb.h[0], xyz, st, chain ? sb.rm[0] : nullptr)
+                    : sdf_affine_launch(query, s, t, sb.A0, sb.b0, B, M, w, w, 0, sb.h[0], xyz, st, chain ? sb.rm[0] : nullptr); }
     if (rc != LS_OK) return rc;
     int kin = w;
     for (int l = 1; l < nl - 1; ++l) {
@@ -1200,8 +1209,8 @@ static int sdf_forward(ls_model_t* m, const SdfBuffers& sb, const float* query, 
             if (rc != LS_OK) return rc;
             PROF(LS_K_SDF_AFFINE, l, st);
             float* rmo = chain ? sb.rm[ri ^ 1] : nullptr;
-            rc = row_inst ? sdf_affine_rows_launch(query, row_inst, s, t, sb.A4, sb.b4, rows, w, w, 1, nxt, st, rmo)
-                          : sdf_affine_launch(query, s, t, sb.A4, sb.b4, B, M, w, w, 1, nxt, st, rmo);
+            rc = row_inst ? sdf_affine_rows_launch(query, row_inst, s, t, sb.A4, sb.b4, rows, w, w, 1, nxt, xyz, st, rmo)
+                          : sdf_affine_launch(query, s, t, sb.A4, sb.b4, B, M, w, w, 1, nxt, xyz, st, rmo);
             if (chain) { ri ^= 1; have = true; rm_parts = sdf_affine_rowmax_parts(w); }
         } else {
             PROF(LS_K_GEMM_SDF, l, st);
@@ -1222,7 +1231,7 @@ static int sdf_forward(ls_model_t* m, const SdfBuffers& sb, const float* query, 
 
 int ls_sdf_decode(ls_model_t* m, const float* query, const float* z_so3, const float* z_inv, const float* s, const float* t,
                   int B, int M, float* sdf, void* workspace, size_t workspace_bytes, void* stream) {
-    LS_REQUIRE(m && query && z_so3 && z_inv && s && t && sdf && workspace, "sdf_decode: null argument");
+    LS_REQUIRE(m && query && z_inv && sdf && workspace && (dec_xyz(m->d) || (z_so3 && s && t)), "sdf_decode: null argument");
     const ls_model_desc& d = m->d;
     LS_REQUIRE(d.dec_num_linear >= 3, "sdf_decode: model has no decoder packed");
     LS_REQUIRE(B > 0 && M > 0, "sdf_decode: empty problem");
@@ -1243,7 +1252,7 @@ size_t ls_sdf_rows_workspace_bytes(const ls_model_t* m, int B, long long R) {
 }
 int ls_sdf_decode_rows(ls_model_t* m, const float* query, const int32_t* row_inst, const float* z_so3, const float* z_inv, const float* s,
                        const float* t, int B, long long R, float* sdf, void* workspace, size_t workspace_bytes, void* stream) {
-    LS_REQUIRE(m && query && row_inst && z_so3 && z_inv && s && t && sdf && workspace, "sdf_decode_rows: null argument");
+    LS_REQUIRE(m && query && row_inst && z_inv && sdf && workspace && (dec_xyz(m->d) || (z_so3 && s && t)), "sdf_decode_rows: null argument");
     const ls_model_desc& d = m->d;
     LS_REQUIRE(d.dec_num_linear >= 3, "sdf_decode_rows: model has no decoder packed");
     LS_REQUIRE(B > 0 && R > 0 && R < (1ll << 31), "sdf_decode_rows: empty or oversized problem");
@@ -1269,7 +1278,7 @@ int ls_sdf_decode_rows(ls_model_t* m, const float* query, const int32_t* row_ins
 // forward that keeps every layer's activations in `workspace` for ls_sdf_backward
 int ls_sdf_decode_train(ls_model_t* m, const float* query, const float* z_so3, const float* z_inv, const float* s, const float* t,
                         int B, int M, float* sdf, void* workspace, size_t workspace_bytes, void* stream) {
-    LS_REQUIRE(m && query && z_so3 && z_inv && s && t && sdf && workspace, "sdf_decode_train: null argument");
+    LS_REQUIRE(m && query && z_inv && sdf && workspace && (dec_xyz(m->d) || (z_so3 && s && t)), "sdf_decode_train: null argument");
     const ls_model_desc& d = m->d;
     LS_REQUIRE(d.dec_num_linear >= 3, "sdf_decode_train: model has no decoder packed");
     LS_REQUIRE(B > 0 && M > 0, "sdf_decode_train: empty problem");
@@ -1301,18 +1310,27 @@ static int build_dec_wt(ls_model_t* m, hipStream_t st) {   // transposed main we
 
 // Gradients of sum(grad_sdf * sdf) w.r.t. the code and the query points, after ls_sdf_decode_train on the SAME arguments and
 // workspace.  grad_query is optional; grad_z_so3 / grad_z_inv may be omitted TOGETHER (pose refinement with a fixed code).
+// LS_DEC_XYZ: z_so3, s, t are not read and each of grad_z_so3, grad_s, grad_t may be NULL; where given they are set to exact zeros
+// (the SDF does not depend on them); need_code follows grad_z_inv alone.
 int ls_sdf_backward(ls_model_t* m, const float* query, const float* z_so3, const float* z_inv, const float* s, const float* t, int B,
                     int M, const float* sdf, const float* grad_sdf, void* workspace, size_t workspace_bytes, float* grad_query,
                     float* grad_z_so3, float* grad_z_inv, float* grad_s, float* grad_t, void* stream) {
-    LS_REQUIRE(m && query && z_so3 && z_inv && s && t && sdf && grad_sdf && workspace && grad_s && grad_t, "sdf_backward: null argument");
-    LS_REQUIRE((grad_z_so3 != nullptr) == (grad_z_inv != nullptr), "sdf_backward: grad_z_so3 and grad_z_inv are given or omitted together");
-    const bool need_code = grad_z_so3 != nullptr;   // a pose refinement with a fixed code skips the code-gradient reductions
+    LS_REQUIRE(m && query && z_inv && sdf && grad_sdf && workspace, "sdf_backward: null argument");
+    const bool xyz = dec_xyz(m->d);
+    LS_REQUIRE(xyz || (z_so3 && s && t && grad_s && grad_t), "sdf_backward: null argument");
+    LS_REQUIRE(xyz || (grad_z_so3 != nullptr) == (grad_z_inv != nullptr), "sdf_backward: grad_z_so3 and grad_z_inv are given or omitted together");
+    const bool need_code = grad_z_inv != nullptr;   // a pose refinement with a fixed code skips the code-gradient reductions
     const ls_model_desc& d = m->d;
     LS_REQUIRE(d.dec_num_linear >= 3, "sdf_backward: model has no decoder packed");
     LS_REQUIRE(B > 0 && M > 0, "sdf_backward: empty problem");
     const size_t need = ls_sdf_train_workspace_bytes(m, B, M);
     if (workspace_bytes < need) { set_error("sdf_backward: workspace %zu < required %zu", workspace_bytes, need); return LS_ERR_WORKSPACE; }
     hipStream_t st = (hipStream_t)stream;
+    if (xyz) {   // the invariant decoder does not read z_so3, s or t: their gradients are exact zeros
+        if (grad_z_so3) LS_HIP_CHECK(hipMemsetAsync(grad_z_so3, 0, (size_t)B * d.c_dim * 3 * sizeof(float), st));
+        if (grad_s) LS_HIP_CHECK(hipMemsetAsync(grad_s, 0, (size_t)B * sizeof(float), st));
+        if (grad_t) LS_HIP_CHECK(hipMemsetAsync(grad_t, 0, (size_t)B * 3 * sizeof(float), st));
+    }
     int rc = build_dec_wt(m, st);
     if (rc != LS_OK) return rc;
     const SdfBuffers sb = sdf_buffers(d, workspace, B, M, true, m->train_splitk);
@@ -1336,7 +1354,7 @@ int ls_sdf_backward(ls_model_t* m, const float* query, const float* z_so3, const
     for (int l = nl - 2; l >= 1; --l) {
         const int kin = outw[l - 1];          // input width of layer l (= padded output width of layer l-1)
         if (l == li) {
-            rc = sdf_affine_bwd_launch(query, s, t, dz, sb.A4, B, M, w, w, dq_started ? 1 : 0, sb.dA4, sb.db4, sb.dQ, need_code, st);
+            rc = sdf_affine_bwd_launch(query, s, t, dz, sb.A4, B, M, w, w, dq_started ? 1 : 0, sb.dA4, sb.db4, sb.dQ, need_code, xyz, st);
             if (rc != LS_OK) return rc;
             dq_started = true;
         }
@@ -1363,12 +1381,13 @@ int ls_sdf_backward(ls_model_t* m, const float* query, const float* z_so3, const
         if (rc != LS_OK) return rc;
         std::swap(dz, other);
     }
-    rc = sdf_affine_bwd_launch(query, s, t, dz, sb.A0, B, M, w, w, dq_started ? 1 : 0, sb.dA0, sb.db0, sb.dQ, need_code, st);
+    rc = sdf_affine_bwd_launch(query, s, t, dz, sb.A0, B, M, w, w, dq_started ? 1 : 0, sb.dA0, sb.db0, sb.dQ, need_code, xyz, st);
     if (rc != LS_OK) return rc;
-    if (need_code) rc = sdf_code_grad_launch(W + d.off_dec_so3_t[0], W + d.off_dec_inv_t[0], sb.dA0, sb.db0, li >= 0 ? W + d.off_dec_so3_t[li] : nullptr,
-                              li >= 0 ? W + d.off_dec_inv_t[li] : nullptr, sb.dA4, sb.db4, B, L, w, grad_z_so3, grad_z_inv, st);
+    if (need_code) rc = sdf_code_grad_launch(xyz ? nullptr : W + d.off_dec_so3_t[0], W + d.off_dec_inv_t[0], sb.dA0, sb.db0,
+                                             li >= 0 && !xyz ? W + d.off_dec_so3_t[li] : nullptr, li >= 0 ? W + d.off_dec_inv_t[li] : nullptr,
+                                             sb.dA4, sb.db4, B, L, w, grad_z_so3, grad_z_inv, xyz, st);
     if (rc != LS_OK) return rc;
-    return sdf_query_grad_launch(query, s, t, sb.dQ, B, M, grad_query, grad_t, grad_s, st);
+    return sdf_query_grad_launch(query, s, t, sb.dQ, B, M, grad_query, grad_t, grad_s, xyz, st);
 }
 
 // ------------------------------------------------------------------------------------------------ profiling

@@ -10,20 +10,36 @@
 // so per INSTANCE we fold a [out,3] matrix, an [out] vector and an [out] bias (sdf_prep_kernel) and the
 // per-query work of those layers is a rank-4 affine map (sdf_affine_kernel, HBM-bound) instead of a K=513 GEMM;
 // the 513-wide input tensor is never materialised.
+//
+// decoder_type "deepsdf" (the invariant ablation, model_utils.py:247-250; ls_model_desc.dec_input == LS_DEC_XYZ) feeds the same MLP
+// u = [z_inv | query] with the RAW query: W u + b = W_xyz query + (b + W_z z_inv).  The same per-instance rank-4 map serves with
+// A = [W_xyz | 0], applied to the query itself (no t, s, |q|); every kernel below that touches the query or the code comes in both kinds
+// (template flag XYZ), one arithmetic path per kind.
 #include "ls_common.h"
 
 namespace ls {
 
 // per (instance, code-fed layer): A [out][4] = {Wb z_so3 (3 cols), w_len}, beff [out] = b + Wa z_inv
 //   inv_t [L][out] = Wa^T, so3_t [L][out] = Wb^T, wlen [out], bias [out]; z_so3 [B,L,3]; z_inv [B,L]
+// XYZ: A [out][4] = {W_xyz (3 cols), 0}, beff as above; so3_t is W_xyz^T [3][out], wlen and z_so3 are not read
+template <bool XYZ>
 __global__ __launch_bounds__(256) void sdf_prep_kernel(const float* __restrict__ inv_t, const float* __restrict__ so3_t,
                                                        const float* __restrict__ wlen, const float* __restrict__ bias,
                                                        const float* __restrict__ z_so3, const float* __restrict__ z_inv,
                                                        int L, int out_dim, float* __restrict__ A, float* __restrict__ beff) {
     const int b = blockIdx.y, o = blockIdx.x * 256 + threadIdx.x;
     if (o >= out_dim) return;
-    const float* zs = z_so3 + (size_t)b * L * 3;
     const float* zi = z_inv + (size_t)b * L;
+    float* Ap = A + ((size_t)b * out_dim + o) * 4;
+    if constexpr (XYZ) {
+        float bb = bias[o];
+#pragma unroll 8
+        for (int c = 0; c < L; ++c) bb += inv_t[(size_t)c * out_dim + o] * zi[c];
+        Ap[0] = so3_t[o]; Ap[1] = so3_t[(size_t)out_dim + o]; Ap[2] = so3_t[(size_t)2 * out_dim + o]; Ap[3] = 0.f;
+        beff[(size_t)b * out_dim + o] = bb;
+        return;
+    }
+    const float* zs = z_so3 + (size_t)b * L * 3;
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, bb = bias[o];
 #pragma unroll 8   // sixteen weight loads in flight per thread (un-unrolled, a single-instance fold took 115 us: one L2 round trip per step)
     for (int c = 0; c < L; ++c) {
@@ -31,7 +47,6 @@ __global__ __launch_bounds__(256) void sdf_prep_kernel(const float* __restrict__
         a0 += ws * zs[c * 3]; a1 += ws * zs[c * 3 + 1]; a2 += ws * zs[c * 3 + 2];
         bb += inv_t[(size_t)c * out_dim + o] * zi[c];
     }
-    float* Ap = A + ((size_t)b * out_dim + o) * 4;
     Ap[0] = a0; Ap[1] = a1; Ap[2] = a2; Ap[3] = wlen[o];
     beff[(size_t)b * out_dim + o] = bb;
 }
@@ -54,12 +69,21 @@ __device__ __forceinline__ AffCols aff_load(const float* __restrict__ A, const f
     return c;
 }
 // one row: the lane's four outputs (stored), max|.| over the lane's 16-lane group = 64 columns (returned in every lane of the group)
+// (XYZ: no |q| column; `len` is not read)
+template <bool XYZ>
 __device__ __forceinline__ float aff_row(const AffCols& c, float qx, float qy, float qz, float len, bool on, int accumulate, float* __restrict__ hp) {
     float4 v;
-    v.x = c.a[0].x * qx + c.a[0].y * qy + c.a[0].z * qz + c.a[0].w * len + c.bb.x;
-    v.y = c.a[1].x * qx + c.a[1].y * qy + c.a[1].z * qz + c.a[1].w * len + c.bb.y;
-    v.z = c.a[2].x * qx + c.a[2].y * qy + c.a[2].z * qz + c.a[2].w * len + c.bb.z;
-    v.w = c.a[3].x * qx + c.a[3].y * qy + c.a[3].z * qz + c.a[3].w * len + c.bb.w;
+    if constexpr (XYZ) {
+        v.x = c.a[0].x * qx + c.a[0].y * qy + c.a[0].z * qz + c.bb.x;
+        v.y = c.a[1].x * qx + c.a[1].y * qy + c.a[1].z * qz + c.bb.y;
+        v.z = c.a[2].x * qx + c.a[2].y * qy + c.a[2].z * qz + c.bb.z;
+        v.w = c.a[3].x * qx + c.a[3].y * qy + c.a[3].z * qz + c.bb.w;
+    } else {
+        v.x = c.a[0].x * qx + c.a[0].y * qy + c.a[0].z * qz + c.a[0].w * len + c.bb.x;
+        v.y = c.a[1].x * qx + c.a[1].y * qy + c.a[1].z * qz + c.a[1].w * len + c.bb.y;
+        v.z = c.a[2].x * qx + c.a[2].y * qy + c.a[2].z * qz + c.a[2].w * len + c.bb.z;
+        v.w = c.a[3].x * qx + c.a[3].y * qy + c.a[3].z * qz + c.a[3].w * len + c.bb.w;
+    }
     if (on) {
         if (accumulate) { const float4 p = *reinterpret_cast<const float4*>(hp); v.x += p.x; v.y += p.y; v.z += p.z; v.w += p.w; }
         v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
@@ -72,6 +96,8 @@ __device__ __forceinline__ float aff_row(const AffCols& c, float qx, float qy, f
     m = dpp_fmax_rm<0x140, 0xF>(m);   // row_mirror
     return m;
 }
+// XYZ: q = query (raw; s and t are not read), no |q|
+template <bool XYZ>
 __global__ __launch_bounds__(256) void sdf_affine_kernel(const float* __restrict__ query, const float* __restrict__ s,
                                                          const float* __restrict__ t, const float* __restrict__ A,
                                                          const float* __restrict__ beff, int M, int out_dim, int ldh,
@@ -84,21 +110,26 @@ __global__ __launch_bounds__(256) void sdf_affine_kernel(const float* __restrict
     const int r0 = blockIdx.z * rows_per_block;
     const bool on = o < out_dim;      // (out_dim % 4 == 0: a lane's four columns are all inside or all outside)
     const AffCols c = aff_load(A, beff, b, out_dim, on ? o : 0);
-    const float sc = s[b], tx = t[b * 3], ty = t[b * 3 + 1], tz = t[b * 3 + 2];
+    float sc = 1.f, tx = 0.f, ty = 0.f, tz = 0.f;
+    if constexpr (!XYZ) { sc = s[b]; tx = t[b * 3]; ty = t[b * 3 + 1]; tz = t[b * 3 + 2]; }
     const int r1 = min(M, r0 + rows_per_block);
     for (int rb = r0; rb < r1; rb += 64) {
         const int rl = min(rb + lane, r1 - 1);
         const float* qp = query + ((size_t)b * M + rl) * 3;
-        const float qxl = (qp[0] - tx) / sc, qyl = (qp[1] - ty) / sc, qzl = (qp[2] - tz) / sc;
-        const float lenl = sqrtf(qxl * qxl + qyl * qyl + qzl * qzl);
+        float qxl, qyl, qzl, lenl = 0.f;
+        if constexpr (XYZ) { qxl = qp[0]; qyl = qp[1]; qzl = qp[2]; }
+        else {
+            qxl = (qp[0] - tx) / sc; qyl = (qp[1] - ty) / sc; qzl = (qp[2] - tz) / sc;
+            lenl = sqrtf(qxl * qxl + qyl * qyl + qzl * qzl);
+        }
         const int nr = min(64, r1 - rb);
         for (int j = wave; j < nr; j += 4) {
             const int r = rb + j;
             const float qx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qxl), j));
             const float qy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qyl), j));
             const float qz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qzl), j));
-            const float len = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lenl), j));
-            const float m = aff_row(c, qx, qy, qz, len, on, accumulate, h + ((size_t)b * M + r) * ldh + o);
+            const float len = XYZ ? 0.f : __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lenl), j));
+            const float m = aff_row<XYZ>(c, qx, qy, qz, len, on, accumulate, h + ((size_t)b * M + r) * ldh + o);
             if (rowmax && (lane & 15) == 15) rowmax[((size_t)b * M + r) * rm_parts + rm_part] = m;
         }
     }
@@ -106,6 +137,7 @@ __global__ __launch_bounds__(256) void sdf_affine_kernel(const float* __restrict
 
 // Ragged form: rows of SEVERAL instances packed back to back, row r belongs to instance row_inst[r] (batched MISE rounds, where
 // every instance contributes a different number of query points).  Same arithmetic as sdf_affine_kernel.
+template <bool XYZ>
 __global__ __launch_bounds__(256) void sdf_affine_rows_kernel(const float* __restrict__ query, const int32_t* __restrict__ row_inst,
                                                               const float* __restrict__ s, const float* __restrict__ t,
                                                               const float* __restrict__ A, const float* __restrict__ beff, long long R,
@@ -123,10 +155,14 @@ __global__ __launch_bounds__(256) void sdf_affine_rows_kernel(const float* __res
     for (long long rb = r0; rb < r1; rb += 64) {   // lane l normalises row rb + l, the row loop reads it back (see sdf_affine_kernel)
         const long long rl = min(rb + lane, r1 - 1);
         const int bl = row_inst[rl];
-        const float sc = s[bl], tx = t[bl * 3], ty = t[bl * 3 + 1], tz = t[bl * 3 + 2];
         const float* qp = query + (size_t)rl * 3;
-        const float qxl = (qp[0] - tx) / sc, qyl = (qp[1] - ty) / sc, qzl = (qp[2] - tz) / sc;
-        const float lenl = sqrtf(qxl * qxl + qyl * qyl + qzl * qzl);
+        float qxl, qyl, qzl, lenl = 0.f;
+        if constexpr (XYZ) { qxl = qp[0]; qyl = qp[1]; qzl = qp[2]; }
+        else {
+            const float sc = s[bl], tx = t[bl * 3], ty = t[bl * 3 + 1], tz = t[bl * 3 + 2];
+            qxl = (qp[0] - tx) / sc; qyl = (qp[1] - ty) / sc; qzl = (qp[2] - tz) / sc;
+            lenl = sqrtf(qxl * qxl + qyl * qyl + qzl * qzl);
+        }
         const int nr = (int)min((long long)64, r1 - rb);
         for (int j = wave; j < nr; j += 4) {
             const long long r = rb + j;
@@ -138,8 +174,8 @@ __global__ __launch_bounds__(256) void sdf_affine_rows_kernel(const float* __res
             const float qx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qxl), j));
             const float qy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qyl), j));
             const float qz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qzl), j));
-            const float len = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lenl), j));
-            const float m = aff_row(c, qx, qy, qz, len, on, accumulate, h + (size_t)r * ldh + o);
+            const float len = XYZ ? 0.f : __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lenl), j));
+            const float m = aff_row<XYZ>(c, qx, qy, qz, len, on, accumulate, h + (size_t)r * ldh + o);
             if (rowmax && (lane & 15) == 15) rowmax[(size_t)r * rm_parts + rm_part] = m;
         }
     }
@@ -172,6 +208,8 @@ __global__ __launch_bounds__(256) void sdf_out_kernel(const float* __restrict__ 
 //   z_l = A (q,|q|) + beff (+ W h)       dA = sum_m dz (q,|q|)^T,  dbeff = sum_m dz,  d(q,|q|) = A^T dz      (l = 0, latent_in)
 //   A = [Wb z_so3 | w_len], beff = b + Wa z_inv      dz_so3 = Wb^T dA[:, :3],  dz_inv = Wa^T dbeff
 //   q = (query - t) / s                  dq = d(q)[:3] + d|q| q/|q|,  dquery = dq / s,  dt = -sum_m dq / s,  ds = -sum_m <dq, q> / s
+// XYZ (A = [W_xyz | 0], q = query): dquery = d(q)[:3] = sum over the code-fed layers of W_xyz^T dz,  dz_inv = W_z^T sum_m dz,
+//   dz_so3 = ds = dt = 0 (written by the host as exact zeros; the z_so3 contraction is not launched)
 
 // dz[row][c] = g[row] (1 - sdf[row]^2) w[c] [h[row][c] > 0]
 __global__ __launch_bounds__(256) void sdf_out_bwd_kernel(const float* __restrict__ g, const float* __restrict__ sdf,
@@ -205,7 +243,8 @@ __global__ __launch_bounds__(256) void relu_mask_kernel(float* __restrict__ dh, 
     *reinterpret_cast<float4*>(dh + o) = d;
 }
 // code-fed layer, reductions over the queries of an instance: dA[b][o][0..3] = sum_m dz[b,m,o] (q_m, |q_m|), dbeff[b][o] = sum_m dz
-// (fixed summation order: bit-reproducible)
+// (fixed summation order: bit-reproducible).  XYZ: dbeff only (dA feeds nothing but the z_so3 gradient); query, s, t, dA not read / written
+template <bool XYZ>
 __global__ __launch_bounds__(256) void sdf_affine_bwd_cols_kernel(const float* __restrict__ query, const float* __restrict__ s,
                                                                   const float* __restrict__ t, const float* __restrict__ dz, int M,
                                                                   int out_dim, int ldh, float* __restrict__ dA, float* __restrict__ dbeff) {
@@ -214,6 +253,14 @@ __global__ __launch_bounds__(256) void sdf_affine_bwd_cols_kernel(const float* _
     const int b = blockIdx.y, lane = threadIdx.x & 63, slice = threadIdx.x >> 6;
     const int o = blockIdx.x * 64 + lane;
     const bool on = o < out_dim;
+    if constexpr (XYZ) {
+        float bb = 0.f;
+        for (int r = slice; r < M; r += 4) bb += on ? dz[((size_t)b * M + r) * ldh + o] : 0.f;
+        red[slice][lane][4] = bb;
+        __syncthreads();
+        if (slice == 0 && on) dbeff[(size_t)b * out_dim + o] = ((red[0][lane][4] + red[1][lane][4]) + red[2][lane][4]) + red[3][lane][4];
+        return;
+    }
     const float sc = s[b], tx = t[b * 3], ty = t[b * 3 + 1], tz = t[b * 3 + 2];
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, bb = 0.f;
     for (int r = slice; r < M; r += 4) {
@@ -257,6 +304,8 @@ __global__ __launch_bounds__(256) void sdf_affine_bwd_rows_kernel(const float* _
     }
 }
 // dz_so3[b][c][x] = sum over the code-fed layers of sum_o so3_t[c][o] dA[b][o][x]; dz_inv[b][c] likewise with inv_t / dbeff
+// XYZ: dz_inv only (so3_t*, dA*, g_so3 not read / written)
+template <bool XYZ>
 __global__ __launch_bounds__(256) void sdf_code_grad_kernel(const float* __restrict__ so3_t0, const float* __restrict__ inv_t0,
                                                             const float* __restrict__ dA0, const float* __restrict__ db0,
                                                             const float* __restrict__ so3_t1, const float* __restrict__ inv_t1,
@@ -272,15 +321,23 @@ __global__ __launch_bounds__(256) void sdf_code_grad_kernel(const float* __restr
         const float* inv_t = pass ? inv_t1 : inv_t0;
         const float* dA = pass ? dA1 : dA0;
         const float* db = pass ? db1 : db0;
-        if (!so3_t) continue;
+        if (!inv_t) continue;
         for (int o = lane; o < out_dim; o += 64) {
-            const float ws = so3_t[(size_t)c * out_dim + o], wi = inv_t[(size_t)c * out_dim + o];
-            const float4 a = *reinterpret_cast<const float4*>(dA + ((size_t)b * out_dim + o) * 4);
-            gx += ws * a.x; gy += ws * a.y; gz += ws * a.z;
+            const float wi = inv_t[(size_t)c * out_dim + o];
+            if constexpr (!XYZ) {
+                const float ws = so3_t[(size_t)c * out_dim + o];
+                const float4 a = *reinterpret_cast<const float4*>(dA + ((size_t)b * out_dim + o) * 4);
+                gx += ws * a.x; gy += ws * a.y; gz += ws * a.z;
+            }
             gi += wi * db[(size_t)b * out_dim + o];
         }
     }
-    gx = wave_sum(gx); gy = wave_sum(gy); gz = wave_sum(gz); gi = wave_sum(gi);
+    gi = wave_sum(gi);
+    if constexpr (XYZ) {
+        if (lane == 0) g_inv[(size_t)b * L + c] = gi;
+        return;
+    }
+    gx = wave_sum(gx); gy = wave_sum(gy); gz = wave_sum(gz);
     if (lane == 0) {
         float* p = g_so3 + ((size_t)b * L + c) * 3;
         p[0] = gx; p[1] = gy; p[2] = gz;
@@ -288,6 +345,13 @@ __global__ __launch_bounds__(256) void sdf_code_grad_kernel(const float* __restr
     }
 }
 // dq = dQ[:3] + dQ[3] q/|q| (0 at q = 0, as torch's norm backward); dquery = dq/s; per instance dt = -sum dq / s, ds = -sum <dq,q> / s
+// XYZ: dquery = dQ[:3] (B*M rows, one thread each; the caller zeroes g_t / g_s)
+__global__ __launch_bounds__(256) void sdf_query_grad_xyz_kernel(const float* __restrict__ dQ, long long rows, float* __restrict__ g_query) {
+    const long long row = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (row >= rows) return;
+    const float4 d = *reinterpret_cast<const float4*>(dQ + row * 4);
+    g_query[row * 3] = d.x; g_query[row * 3 + 1] = d.y; g_query[row * 3 + 2] = d.z;
+}
 __global__ __launch_bounds__(256) void sdf_query_grad_kernel(const float* __restrict__ query, const float* __restrict__ s,
                                                              const float* __restrict__ t, const float* __restrict__ dQ, int M,
                                                              float* __restrict__ g_query, float* __restrict__ g_t, float* __restrict__ g_s) {
@@ -340,10 +404,14 @@ int relu_mask_launch(float* dh, const float* h, long long rows, int cols, int ld
     return LS_OK;
 }
 int sdf_affine_bwd_launch(const float* query, const float* s, const float* t, const float* dz, const float* A, int B, int M, int out_dim,
-                          int ldh, int accumulate, float* dA, float* dbeff, float* dQ, bool need_code, hipStream_t st) {
+                          int ldh, int accumulate, float* dA, float* dbeff, float* dQ, bool need_code, bool xyz, hipStream_t st) {
     // the reductions over the queries feed only the CODE gradient (a pose refinement with a fixed code does not need them)
-    if (need_code)
-        hipLaunchKernelGGL(sdf_affine_bwd_cols_kernel, dim3(cdiv(out_dim, 64), B), dim3(256), 0, st, query, s, t, dz, M, out_dim, ldh, dA, dbeff);
+    if (need_code) {
+        if (xyz)
+            hipLaunchKernelGGL(sdf_affine_bwd_cols_kernel<true>, dim3(cdiv(out_dim, 64), B), dim3(256), 0, st, query, s, t, dz, M, out_dim, ldh, dA, dbeff);
+        else
+            hipLaunchKernelGGL(sdf_affine_bwd_cols_kernel<false>, dim3(cdiv(out_dim, 64), B), dim3(256), 0, st, query, s, t, dz, M, out_dim, ldh, dA, dbeff);
+    }
     hipLaunchKernelGGL(sdf_affine_bwd_rows_kernel, dim3(cdiv((long long)B * M, 4)), dim3(256), 0, st, dz, A, M, out_dim, ldh, accumulate,
                        (long long)B * M, dQ);
     LS_LAUNCH_CHECK();
@@ -351,14 +419,24 @@ int sdf_affine_bwd_launch(const float* query, const float* s, const float* t, co
 }
 int sdf_code_grad_launch(const float* so3_t0, const float* inv_t0, const float* dA0, const float* db0, const float* so3_t1,
                          const float* inv_t1, const float* dA1, const float* db1, int B, int L, int out_dim, float* g_so3, float* g_inv,
-                         hipStream_t st) {
-    hipLaunchKernelGGL(sdf_code_grad_kernel, dim3(cdiv(L, 4), B), dim3(256), 0, st, so3_t0, inv_t0, dA0, db0, so3_t1, inv_t1, dA1, db1, L,
-                       out_dim, g_so3, g_inv);
+                         bool xyz, hipStream_t st) {
+    if (xyz)
+        hipLaunchKernelGGL(sdf_code_grad_kernel<true>, dim3(cdiv(L, 4), B), dim3(256), 0, st, so3_t0, inv_t0, dA0, db0, so3_t1, inv_t1, dA1, db1, L,
+                           out_dim, g_so3, g_inv);
+    else
+        hipLaunchKernelGGL(sdf_code_grad_kernel<false>, dim3(cdiv(L, 4), B), dim3(256), 0, st, so3_t0, inv_t0, dA0, db0, so3_t1, inv_t1, dA1, db1, L,
+                           out_dim, g_so3, g_inv);
     LS_LAUNCH_CHECK();
     return LS_OK;
 }
 int sdf_query_grad_launch(const float* query, const float* s, const float* t, const float* dQ, int B, int M, float* g_query, float* g_t,
-                          float* g_s, hipStream_t st) {
+                          float* g_s, bool xyz, hipStream_t st) {
+    if (xyz) {
+        if (g_query)
+            hipLaunchKernelGGL(sdf_query_grad_xyz_kernel, dim3(cdiv((long long)B * M, 256)), dim3(256), 0, st, dQ, (long long)B * M, g_query);
+        LS_LAUNCH_CHECK();
+        return LS_OK;
+    }
     hipLaunchKernelGGL(sdf_query_grad_kernel, dim3(B), dim3(256), 0, st, query, s, t, dQ, M, g_query, g_t, g_s);
     LS_LAUNCH_CHECK();
     return LS_OK;
@@ -369,33 +447,46 @@ int transpose_launch(const float* W, int rows, int cols, float* Wt, hipStream_t 
     return LS_OK;
 }
 
+// xyz (LS_DEC_XYZ): so3_t = W_xyz^T [3][out]; wlen and z_so3 are not read
 int sdf_prep_launch(const float* inv_t, const float* so3_t, const float* wlen, const float* bias, const float* z_so3,
-                    const float* z_inv, int B, int L, int out_dim, float* A, float* beff, hipStream_t st) {
-    hipLaunchKernelGGL(sdf_prep_kernel, dim3(cdiv(out_dim, 256), B), dim3(256), 0, st, inv_t, so3_t, wlen, bias, z_so3, z_inv, L,
-                       out_dim, A, beff);
+                    const float* z_inv, int B, int L, int out_dim, float* A, float* beff, bool xyz, hipStream_t st) {
+    if (xyz)
+        hipLaunchKernelGGL(sdf_prep_kernel<true>, dim3(cdiv(out_dim, 256), B), dim3(256), 0, st, inv_t, so3_t, wlen, bias, z_so3, z_inv, L,
+                           out_dim, A, beff);
+    else
+        hipLaunchKernelGGL(sdf_prep_kernel<false>, dim3(cdiv(out_dim, 256), B), dim3(256), 0, st, inv_t, so3_t, wlen, bias, z_so3, z_inv, L,
+                           out_dim, A, beff);
     LS_LAUNCH_CHECK();
     return LS_OK;
 }
 int sdf_affine_launch(const float* query, const float* s, const float* t, const float* A, const float* beff, int B, int M,
-                      int out_dim, int ldh, int accumulate, float* h, hipStream_t st, float* rowmax) {
+                      int out_dim, int ldh, int accumulate, float* h, bool xyz, hipStream_t st, float* rowmax) {
     const int rpb = 64;
     LS_REQUIRE(out_dim % 4 == 0 && ldh % 4 == 0, "sdf_affine: width %d / row stride %d must be multiples of 4", out_dim, ldh);
     // gridDim.y / .z are limited to 65535: say so instead of a generic launch failure (direct C-ABI callers; ops.sdf_decode chunks)
     LS_REQUIRE(B <= 65535 && cdiv(M, rpb) <= 65535, "sdf_decode: B=%d or M=%d too large for one call (B <= 65535, M <= %d): split the queries", B, M,
                65535 * rpb);
-    hipLaunchKernelGGL(sdf_affine_kernel, dim3(cdiv(out_dim, 256), B, cdiv(M, rpb)), dim3(256), 0, st, query, s, t, A, beff, M,
-                       out_dim, ldh, accumulate, rpb, h, rowmax);
+    if (xyz)
+        hipLaunchKernelGGL(sdf_affine_kernel<true>, dim3(cdiv(out_dim, 256), B, cdiv(M, rpb)), dim3(256), 0, st, query, s, t, A, beff, M,
+                           out_dim, ldh, accumulate, rpb, h, rowmax);
+    else
+        hipLaunchKernelGGL(sdf_affine_kernel<false>, dim3(cdiv(out_dim, 256), B, cdiv(M, rpb)), dim3(256), 0, st, query, s, t, A, beff, M,
+                           out_dim, ldh, accumulate, rpb, h, rowmax);
     LS_LAUNCH_CHECK();
     return LS_OK;
 }
 int sdf_affine_rowmax_parts(int out_dim) { return 4 * cdiv(out_dim, 256); }
 int sdf_affine_rows_launch(const float* query, const int32_t* row_inst, const float* s, const float* t, const float* A, const float* beff,
-                           long long R, int out_dim, int ldh, int accumulate, float* h, hipStream_t st, float* rowmax) {
+                           long long R, int out_dim, int ldh, int accumulate, float* h, bool xyz, hipStream_t st, float* rowmax) {
     const int rpb = 64;
     LS_REQUIRE(out_dim % 4 == 0 && ldh % 4 == 0, "sdf_affine: width %d / row stride %d must be multiples of 4", out_dim, ldh);
     LS_REQUIRE(cdiv(R, rpb) <= 65535, "sdf_decode_rows: R=%lld rows too many for one call (<= %d): split the rows", R, 65535 * rpb);
-    hipLaunchKernelGGL(sdf_affine_rows_kernel, dim3(cdiv(out_dim, 256), (unsigned)cdiv(R, rpb)), dim3(256), 0, st, query, row_inst, s, t, A,
-                       beff, R, out_dim, ldh, accumulate, rpb, h, rowmax);
+    if (xyz)
+        hipLaunchKernelGGL(sdf_affine_rows_kernel<true>, dim3(cdiv(out_dim, 256), (unsigned)cdiv(R, rpb)), dim3(256), 0, st, query, row_inst, s, t,
+                           A, beff, R, out_dim, ldh, accumulate, rpb, h, rowmax);
+    else
+        hipLaunchKernelGGL(sdf_affine_rows_kernel<false>, dim3(cdiv(out_dim, 256), (unsigned)cdiv(R, rpb)), dim3(256), 0, st, query, row_inst, s, t,
+                           A, beff, R, out_dim, ldh, accumulate, rpb, h, rowmax);
     LS_LAUNCH_CHECK();
     return LS_OK;
 }

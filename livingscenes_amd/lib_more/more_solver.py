@@ -215,10 +215,12 @@ class More_Solver:
         t = code["t"].detach().float().reshape(P, 3).contiguous().clone()
         z_so3 = code["z_so3"].detach().float().contiguous().clone()
         s_ = code["s"].detach().float().contiguous()
-        opt = ops.Adam([(z_inv, 1e-5), (t, 1e-4), (z_so3, 5e-4)])            # more_solver.py:199-203
+        hip = self.model.hip_model()
+        # decoder_type "deepsdf": the SDF does not depend on t or z_so3, their .grad stays None and the reference's Adam never moves them
+        inv_only = hip.desc.dec_input == _lib.DEC_XYZ
+        opt = ops.Adam([(z_inv, 1e-5)] if inv_only else [(z_inv, 1e-5), (t, 1e-4), (z_so3, 5e-4)])   # more_solver.py:199-203
         min_loss = torch.full((P,), 100.0, device=dev)                        # :205
         improved = torch.zeros(P, dtype=torch.int32, device=dev)
-        hip = self.model.hip_model()
         prev_split = hip.set_option(_lib.OPT_SDF_TRAIN_SPLITK, 0)
         try:
             # per step: decoder forward (activations kept), MSE + its gradient + the best-loss bookkeeping, decoder backward w.r.t. the
@@ -227,7 +229,7 @@ class More_Solver:
                 sdf, saved = hip.sdf_decode_train(pc, z_so3, z_inv, s_, t)
                 _, gsdf = ops.mse(sdf, min_loss, improved)                       # MSELoss(sdf, 0) of every instance (:213), :219-221
                 _, gso3, ginv, _, gt = hip.sdf_backward(saved, gsdf, need_query_grad=False)
-                opt.step([ginv, gt, gso3], lr_scale=0.1 if i >= 160 else 1.0)   # MultiStepLR([160], 0.1) (:204)
+                opt.step([ginv] if inv_only else [ginv, gt, gso3], lr_scale=0.1 if i >= 160 else 1.0)   # MultiStepLR([160], 0.1) (:204)
         finally:
             hip.set_option(_lib.OPT_SDF_TRAIN_SPLITK, prev_split)
         with torch.no_grad():

@@ -12,7 +12,7 @@ import yaml
 from torch import distributions as dist
 from torch import nn
 
-from . import ops
+from . import _lib, ops
 from .deepsdf_decoder import DeepSDF_Decoder
 from .vec_dgcnn_atten import VecDGCNN_att
 
@@ -54,13 +54,17 @@ def fps(points, lengths=None, K=50, random_start_point=False):
     return pts, idx
 
 
+SUPPORTED_DECODER_TYPES = ("inner_deepsdf", "deepsdf")
+
+
 class FieldWrapper(nn.Module):
-    """model_utils.py:221-263.  forward(query, z_none, c, return_sdf) with the 'inner_deepsdf' decoder: the HIP library
-    folds (z_inv, z_so3, s, t) into the first / skip layers and runs the 768-wide MLP on the matrix cores."""
+    """model_utils.py:221-263.  forward(query, z_none, c, return_sdf) with a DeepSDF decoder: the HIP library folds the code into the
+    first / skip layers and runs the MLP on the matrix cores.  decoder_type 'inner_deepsdf' (released) reads (z_inv, z_so3, s, t);
+    'deepsdf' (the invariant ablation) reads z_inv and the raw query only -- z_so3, s and t get no gradient, as in the reference."""
 
     def __init__(self, decoder, decoder_type, sdf2occ_factor=-1.0):
         super().__init__()
-        assert decoder_type == "inner_deepsdf", "only the released decoder_type is implemented"
+        assert decoder_type in SUPPORTED_DECODER_TYPES, f"decoder_type must be one of {SUPPORTED_DECODER_TYPES}, got {decoder_type!r}"
         self.F = decoder
         self.sdf2occ_factor = sdf2occ_factor
         self.decoder_type = decoder_type
@@ -92,6 +96,8 @@ class _SdfDecode(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_sdf):
         gq, gso3, ginv, gs, gt = ctx.hip.sdf_backward(ctx.saved, grad_sdf.contiguous(), need_query_grad=ctx.need_q)
+        if ctx.hip.desc.dec_input == _lib.DEC_XYZ:   # decoder_type "deepsdf": z_so3, s, t do not reach the SDF (reference: .grad None)
+            return None, gq, None, ginv, None, None
         return None, gq, gso3, ginv, gs, gt.reshape(ctx.t_shape)
 
 
@@ -106,9 +112,10 @@ class Shape_Prior(nn.Module):
             self.field_cfg = yaml.full_load(f)
         self.decoder_type = cfg_with_default(self.field_cfg, ["model", "decoder_type"], "cbatchnorm")
         self.encoder_type = cfg_with_default(self.field_cfg, ["model", "encoder_type"], "sim3pointres")
-        if self.encoder_type != "vecdgcnn_atten" or self.decoder_type != "inner_deepsdf":
-            raise NotImplementedError(f"only encoder_type 'vecdgcnn_atten' + decoder_type 'inner_deepsdf' (the released "
-                                      f"config) are implemented, got {self.encoder_type!r} / {self.decoder_type!r}")
+        if self.encoder_type != "vecdgcnn_atten" or self.decoder_type not in SUPPORTED_DECODER_TYPES:
+            raise NotImplementedError(f"only encoder_type 'vecdgcnn_atten' with decoder_type 'inner_deepsdf' (the released config) or "
+                                      f"'deepsdf' (the invariant-decoder ablation) is implemented, got {self.encoder_type!r} / "
+                                      f"{self.decoder_type!r}")
         encoder = VecDGCNN_att(**self.field_cfg["model"]["encoder"])
         decoder = DeepSDF_Decoder(**self.field_cfg["model"]["decoder"])
         self.field_input_n = self.field_cfg["dataset"]["n_pcl"]
@@ -121,35 +128,42 @@ class Shape_Prior(nn.Module):
             raise NotImplementedError("cls_head is absent from the released config")
         self.cls_head = None
         self._finish(encoder, decoder, use_double,
-                     cfg_with_default(self.field_cfg, ["model", "sdf2occ_factor"], -1.0))
+                     cfg_with_default(self.field_cfg, ["model", "sdf2occ_factor"], -1.0), self.decoder_type)
         logging.info(f"Model {self.model_id} successfully loaded at epoch {field_loaded_ep}.")
         logging.info(f"Encoder with {count_param(self.encoder)} params")
         logging.info(f"Decoder with {count_param(self.decoder)} params")
 
-    def _finish(self, encoder, decoder, use_double, sdf2occ_factor):
+    def _finish(self, encoder, decoder, use_double, sdf2occ_factor, decoder_type):
         # model_utils.py:148-152: use_double evaluates the ENCODER in fp64 (inputs cast at :166) and hands float64 codes on.  The HIP
         # kernels are fp32 (the released config: configs/room4cates.yaml:15): with use_double the same fp32 path runs and the codes are
         # returned as float64 -- fp32 vs fp64 encoder outputs differ by ~1e-6 of max-norm (SURVEY.md 8c calibration), inside the 1e-4 bar.
         self.use_double = bool(use_double)
         if self.use_double:
             logging.warning("Shape_Prior(use_double=True): the MI355X encoder computes in fp32; codes are returned as float64")
+        # deepsdf_decoder.py:33: the input is [code | pe_dim]; FieldWrapper.forward (model_utils.py:241-250) fills pe_dim by type
+        pe_want = 3 if decoder_type == "deepsdf" else decoder.latent_size + 1
+        if decoder.pe_dim != pe_want:
+            raise ValueError(f"decoder_type {decoder_type!r} feeds a {pe_want}-wide query part, the decoder has pe_dim {decoder.pe_dim}")
         self.encoder = encoder
-        self.decoder = FieldWrapper(decoder, decoder_type="inner_deepsdf", sdf2occ_factor=sdf2occ_factor)
+        self.decoder = FieldWrapper(decoder, decoder_type=decoder_type, sdf2occ_factor=sdf2occ_factor)
         import weakref
         self.decoder._owner = weakref.ref(self)
 
     @classmethod
-    def from_state(cls, enc_cfg, dec_cfg, enc_w, dec_w, device="cuda", n_pcl=1024, model_id="chair", sdf2occ_factor=-1.0):
+    def from_state(cls, enc_cfg, dec_cfg, enc_w, dec_w, device="cuda", n_pcl=1024, model_id="chair", sdf2occ_factor=-1.0,
+                   decoder_type="inner_deepsdf"):
         """Build from in-memory config/state dicts (synthetic weights, tests, bench) without touching the file system."""
+        if decoder_type not in SUPPORTED_DECODER_TYPES:
+            raise NotImplementedError(f"decoder_type must be one of {SUPPORTED_DECODER_TYPES}, got {decoder_type!r}")
         self = cls.__new__(cls)
         nn.Module.__init__(self)
         self.model_id, self.field_cfg = model_id, {"model": {"encoder": enc_cfg, "decoder": dec_cfg}, "dataset": {"n_pcl": n_pcl}}
-        self.decoder_type, self.encoder_type, self.cls_head = "inner_deepsdf", "vecdgcnn_atten", None
+        self.decoder_type, self.encoder_type, self.cls_head = decoder_type, "vecdgcnn_atten", None
         encoder, decoder = VecDGCNN_att(**enc_cfg), DeepSDF_Decoder(**dec_cfg)
         encoder.load_state_dict(enc_w, strict=True)
         decoder.load_state_dict(dec_w, strict=True)
         self.field_input_n = n_pcl
-        self._finish(encoder, decoder, False, sdf2occ_factor)
+        self._finish(encoder, decoder, False, sdf2occ_factor, decoder_type)
         return self.to(device).eval()
 
     def hip_model(self):

@@ -8,6 +8,7 @@ All folds are computed in float64 and rounded once to fp32:
                          (csrc/edge.hip header; W = [W1 | W2] acts on cat([nbr-ctr, ctr]), vec_dgcnn_atten.py:160)
   * global conv          W = [Wa | Wb] acts on cat([f, mean f]) (vec_dgcnn_atten.py:222-225)
   * decoder code layers  W u + b with u = [z_inv | <q,z_so3> | |q|]  ->  Wa^T, Wb^T, w_len  (csrc/sdf.hip header)
+                         decoder_type "deepsdf": u = [z_inv | query]  ->  W_z^T, W_xyz^T             (desc.dec_input = DEC_XYZ)
 
 Blob layout (all row-major fp32, every tensor 4-float aligned):
   off_l0        [6][C0]            {W[:,0], W[:,1], W[:,2], (Wd W)[:,0], (Wd W)[:,1], (Wd W)[:,2]}   (layer 0: cross | nbr-ctr | ctr)
@@ -19,12 +20,13 @@ Blob layout (all row-major fp32, every tensor 4-float aligned):
   off_c_misc    [h + Cd + 1]       lin1 | shortcut | act2.lin_dir scalar
   off_dec_w[l]  [out_l][kin_l]     folded decoder weights (layer latent_in-1 padded to ceil4 rows, latent_in: only the h part)
   off_dec_b[l]  [out_l]
-  off_dec_inv_t/so3_t/len[l]       for l in {0, latent_in}: Wa^T [latent][out], Wb^T [latent][out], w_len [out]
+  off_dec_inv_t/so3_t/len[l]       for l in {0, latent_in}: Wa^T [latent][out], Wb^T [latent][out], w_len [out]   (DEC_INNER)
+  off_dec_inv_t/xyz_t[l]           for l in {0, latent_in}: W_z^T [latent][out], W_xyz^T [3][out]                   (DEC_XYZ; so3_t / len unset)
 """
 import numpy as np
 import torch
 
-from ._lib import LS_MAX_LAYERS, ModelDesc
+from ._lib import DEC_INNER, DEC_XYZ, LS_MAX_LAYERS, ModelDesc
 
 
 def _f64(t):
@@ -126,9 +128,13 @@ def pack_model(enc_w, enc_cfg, dec_w=None, dec_cfg=None):
 
     d.dec_num_linear = 0
     d.dec_latent_in = -1
+    d.dec_input = DEC_INNER
     if dec_w is not None:
         lat, pe = dec_cfg["latent_size"], dec_cfg["pe_dim"]
-        assert lat == cd and pe == cd + 1, "inner_deepsdf decoder: latent_size == c_dim and pe_dim == c_dim + 1"
+        xyz = pe == 3 and lat == cd          # decoder_type "deepsdf": the raw query after the code
+        assert xyz or (lat == cd and pe == cd + 1), \
+            "inner_deepsdf decoder: latent_size == c_dim and pe_dim == c_dim + 1; deepsdf decoder: latent_size == c_dim and pe_dim == 3"
+        d.dec_input = DEC_XYZ if xyz else DEC_INNER
         dims = list(dec_cfg["dims"])
         width = dims[0]
         assert all(x == width for x in dims), "uniform decoder width expected"
@@ -149,8 +155,11 @@ def pack_model(enc_w, enc_cfg, dec_w=None, dec_cfg=None):
 
         def code_layer(layer, wu, bias):
             d.off_dec_inv_t[layer] = blob.add(wu[:, :lat].T)
-            d.off_dec_so3_t[layer] = blob.add(wu[:, lat:2 * lat].T)
-            d.off_dec_len[layer] = blob.add(wu[:, 2 * lat])
+            if xyz:
+                d.off_dec_xyz_t[layer] = blob.add(wu[:, lat:lat + 3].T)
+            else:
+                d.off_dec_so3_t[layer] = blob.add(wu[:, lat:2 * lat].T)
+                d.off_dec_len[layer] = blob.add(wu[:, 2 * lat])
             d.off_dec_b[layer] = blob.add(bias)
 
         for layer in range(nl):

@@ -41,6 +41,21 @@ def small_decoder_cfg():
         latent_size=32, norm_layers=list(range(4)), pe_dim=33, use_tanh=False, weight_norm=True)
 
 
+def inv_decoder_cfg():
+    """decoder_type "deepsdf", the invariant-decoder ablation (lib_shape_prior/configs/decoder/dgcnn_attn_inv_deepsdf.yaml, model.decoder):
+    the code and the raw query, 8 x 512, skip at layer 4."""
+    return dict(
+        dims=[512] * 8, dropout=list(range(8)), dropout_prob=0.2, latent_dropout=False, latent_in=[4],
+        latent_size=256, norm_layers=list(range(8)), pe_dim=3, use_tanh=False, weight_norm=True)
+
+
+def small_inv_decoder_cfg():
+    """Reduced sibling of inv_decoder_cfg() for small_encoder_cfg() (c_dim 32)."""
+    return dict(
+        dims=[128] * 4, dropout=None, dropout_prob=0.0, latent_dropout=False, latent_in=[2],
+        latent_size=32, norm_layers=list(range(4)), pe_dim=3, use_tanh=False, weight_norm=True)
+
+
 def _rng(seed, name):
     return np.random.Generator(np.random.Philox(key=[int(seed) & 0xFFFFFFFF, zlib.crc32(name.encode())]))
 

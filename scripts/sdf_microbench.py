@@ -1,4 +1,5 @@
-"""SDF decoder throughput (BASELINE.json configs[4] style: dense query grids), queries/s and effective TFLOP/s."""
+"""SDF decoder throughput (BASELINE.json configs[4] style: dense query grids), queries/s and effective TFLOP/s.
+--decoder inv: the invariant decoder (decoder_type "deepsdf", synth.inv_decoder_cfg) instead of the released one."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch
@@ -6,10 +7,13 @@ from livingscenes_amd import synth
 from livingscenes_amd.model_utils import Shape_Prior
 ap = argparse.ArgumentParser()
 ap.add_argument("--B", type=int, default=8); ap.add_argument("--res", type=int, default=64); ap.add_argument("--iters", type=int, default=3)
+ap.add_argument("--decoder", choices=["released", "inv"], default="released")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
-ecfg, dcfg = synth.default_encoder_cfg(), synth.default_decoder_cfg()
-sp = Shape_Prior.from_state(ecfg, dcfg, synth.make_encoder_weights(ecfg, 0), synth.make_decoder_weights(dcfg, 0), device=dev)
+inv = a.decoder == "inv"
+ecfg, dcfg = synth.default_encoder_cfg(), (synth.inv_decoder_cfg() if inv else synth.default_decoder_cfg())
+sp = Shape_Prior.from_state(ecfg, dcfg, synth.make_encoder_weights(ecfg, 0), synth.make_decoder_weights(dcfg, 0), device=dev,
+                            decoder_type="deepsdf" if inv else "inner_deepsdf")
 emb = sp.encode(synth.make_instances(a.B, 1024, seed=0).to(dev))
 M = a.res ** 3
 lin = torch.linspace(-0.55, 0.55, a.res, device=dev)
@@ -22,4 +26,7 @@ for _ in range(a.iters):
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / a.iters
 nq = a.B * M
-print(f"sdf decode B={a.B} grid={a.res}^3: {dt*1e3:.2f} ms  {nq/dt/1e6:.2f} Mqueries/s  {nq*6.7e6/dt/1e12:.1f} TFLOP/s (6.7 MFLOP/query as executed; reference formulation 8.26)")
+# GEMM FLOP per query as executed: 2 x (hidden layer widths x their padded inputs) (+ the rank-4 code layers, negligible)
+fq = 3.15e6 if inv else 6.7e6
+print(f"sdf decode ({a.decoder}) B={a.B} grid={a.res}^3: {dt*1e3:.2f} ms  {nq/dt/1e6:.2f} Mqueries/s  {nq*fq/dt/1e12:.1f} TFLOP/s "
+      f"({fq/1e6:.2f} MFLOP/query as executed{'' if inv else '; reference formulation 8.26'})")
