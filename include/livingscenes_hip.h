@@ -60,9 +60,10 @@ typedef enum {
  * ls_adam_group / ls_adam_step_f32 / ls_se3_adam_step_f32, option 4 (LDS-staged attention); 102: LS_OPT_EDGE_FUSE_Q / _T, LS_OPT_GLOB_FUSE, LS_OPT_DEBUG_EDGE; the
  * library reads no development switches from the environment any more; 104: option 4 retired with the staged attention path, refused like
  * any unknown option; 105: the mesh metrics ls_mesh_contains_f64 / ls_mesh_distance_f64 / ls_mesh_sample_f64; 106: ls_model_desc.dec_input and
- * off_dec_xyz_t, the invariant decoder_type "deepsdf").  ls_version() returns the value the LIBRARY was built with; a
+ * off_dec_xyz_t, the invariant decoder_type "deepsdf"; 107: the ragged multi-mesh metrics ls_mesh_contains_batch_f64 /
+ * ls_mesh_distance_batch_f64 / ls_mesh_sample_batch_f64).  ls_version() returns the value the LIBRARY was built with; a
  * binding compares it with the header it was written against and refuses a mismatch (livingscenes_amd/_lib.py: load). */
-#define LS_ABI_VERSION 106
+#define LS_ABI_VERSION 107
 int ls_version(void);
 const char* ls_last_error(void);
 /* number of HIP devices visible, or a negative ls_status */
@@ -499,6 +500,32 @@ int ls_mesh_distance_f64(const double* vertices, int nv, const int32_t* faces, i
 size_t ls_mesh_sample_workspace_bytes(int nf);
 int ls_mesh_sample_f64(const double* vertices, int nv, const int32_t* faces, int nf, long long count, unsigned long long seed,
                        double* points_out, int64_t* face_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The three metrics on M meshes per call (ragged batches).  The meshes are stored back to back: mesh m owns vertices
+ * [vert_off[m], vert_off[m+1]), faces [face_off[m], face_off[m+1]) -- indices LOCAL to the mesh -- and points (samples: count_off)
+ * [pt_off[m], pt_off[m+1]).  The offsets are HOST int64 arrays of M + 1 entries starting at 0, never decreasing and ending at the totals
+ * (nv_total, nf_total, n_total / count_total); the entry checks them, and every argument check of the single-mesh op, per mesh (the error
+ * names the mesh), and copies them into its workspace on the stream.  hash_resolution and max_dist hold for the whole batch.  For every
+ * mesh the result is BIT-IDENTICAL to the single-mesh op on that mesh alone (an empty mesh contains nothing and is infinitely far away).
+ * The number of launches does not depend on M.  The binned ops follow the single ops' sizing convention with ONE entry count for the whole
+ * batch.  Workspace: contains holds hash_resolution^2 cells per mesh; distance gives mesh m a grid of at most a^3 cells, a = the largest
+ * integer <= 128 with a^3 <= 8 nf_m (at least 1), so at most 8 nf_total + M cells in all.  The sampler takes M seeds (device), zero
+ * samples for a mesh are allowed (a mesh with faces is then not scanned), samples of an empty mesh are refused; face_out is local to the
+ * mesh.  The *_workspace_bytes helpers return 0 for invalid arguments. */
+size_t ls_mesh_contains_batch_workspace_bytes(int M, long long nf_total, int hash_resolution);
+int ls_mesh_contains_batch_f64(int M, const double* vertices, long long nv_total, const long long* vert_off, const int32_t* faces, long long nf_total,
+                               const long long* face_off, const double* points, long long n_total, const long long* pt_off, int hash_resolution,
+                               uint8_t* inside_out, int32_t* entries, long long cap_entries, long long* count_out, void* workspace,
+                               size_t workspace_bytes, void* stream);
+size_t ls_mesh_distance_batch_workspace_bytes(int M, long long nf_total);
+int ls_mesh_distance_batch_f64(int M, const double* vertices, long long nv_total, const long long* vert_off, const int32_t* faces, long long nf_total,
+                               const long long* face_off, const double* points, long long n_total, const long long* pt_off, double max_dist,
+                               double* dist_out, int32_t* entries, long long cap_entries, long long* count_out, void* workspace,
+                               size_t workspace_bytes, void* stream);
+size_t ls_mesh_sample_batch_workspace_bytes(int M, long long nf_total);
+int ls_mesh_sample_batch_f64(int M, const double* vertices, long long nv_total, const long long* vert_off, const int32_t* faces, long long nf_total,
+                             const long long* face_off, long long count_total, const long long* count_off, const unsigned long long* seeds,
+                             double* points_out, int64_t* face_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Live per-kernel timing (bench.py's roofline leg): while enabled, every kernel ls_encode / ls_sdf_decode

@@ -19,7 +19,7 @@ FLAG_KABSCH_RAW_WEIGHTS = 8
 OPT_SDF_TRAIN_SPLITK, OPT_SDF_BF16X2, OPT_ENCODE_GRAPH = 1, 2, 3   # (4: retired, refused by the library)
 OPT_EDGE_FUSE_Q, OPT_EDGE_FUSE_T, OPT_GLOB_FUSE, OPT_DEBUG_EDGE, OPT_GEMM_OVERLAP = 5, 6, 7, 8, 9
 DEC_INNER, DEC_XYZ = 0, 1   # ModelDesc.dec_input: decoder_type "inner_deepsdf" / "deepsdf" (LS_DEC_* in the header)
-ABI_VERSION = 106   # == LS_ABI_VERSION in include/livingscenes_hip.h: a library of another version is refused (argument layouts differ)
+ABI_VERSION = 107   # == LS_ABI_VERSION in include/livingscenes_hip.h: a library of another version is refused (argument layouts differ)
 KABSCH_OK, KABSCH_RANK1, KABSCH_RANK0, KABSCH_NONFINITE = 0, 1, 2, 3
 
 
@@ -160,6 +160,12 @@ SIGNATURES = {
     "ls_mesh_distance_f64": (_I, [_P, _I, _P, _I, _P, ctypes.c_longlong, _D, _P, _P, ctypes.c_longlong, _P, _P, _SZ, _P]),
     "ls_mesh_sample_workspace_bytes": (_SZ, [_I]),
     "ls_mesh_sample_f64": (_I, [_P, _I, _P, _I, ctypes.c_longlong, ctypes.c_ulonglong, _P, _P, _P, _SZ, _P]),
+    "ls_mesh_contains_batch_workspace_bytes": (_SZ, [_I, ctypes.c_longlong, _I]),
+    "ls_mesh_contains_batch_f64": (_I, [_I, _P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _P, _I, _P, _P, ctypes.c_longlong, _P, _P, _SZ, _P]),
+    "ls_mesh_distance_batch_workspace_bytes": (_SZ, [_I, ctypes.c_longlong]),
+    "ls_mesh_distance_batch_f64": (_I, [_I, _P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _P, _D, _P, _P, ctypes.c_longlong, _P, _P, _SZ, _P]),
+    "ls_mesh_sample_batch_workspace_bytes": (_SZ, [_I, ctypes.c_longlong]),
+    "ls_mesh_sample_batch_f64": (_I, [_I, _P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _P, ctypes.c_longlong, _P, _P, _P, _P, _P, _SZ, _P]),
     "ls_profile_begin": (_I, [_P]),
     "ls_profile_end": (_I, [_P, ctypes.POINTER(ProfileEntry), _I, ctypes.POINTER(ctypes.c_int)]),
 }

@@ -11,6 +11,17 @@
 //                          folded barycentric pair; the uniforms come from a counter-based hash (splitmix64) of (seed, 3 i + k).
 // The binned ops follow ls_marching_cubes_f64's convention for data-dependent sizes: a call with entries == NULL writes the number of
 // bin entries to the device integer count_out and stops; the caller allocates that many and repeats the call.
+// ls_mesh_*_batch_f64 run the same device functions on M meshes stored back to back (host int64 offsets, checked on the host and copied to the
+// workspace): per-face / per-point kernels find their mesh by binary search of the offsets, the bounding boxes and the sampler's top-level scans
+// run one workgroup per mesh, so the number of launches does not depend on M.  Per mesh the result is bit-identical to the single op: contains
+// builds each mesh's own R^2 hash over its own box; distance gives each mesh a grid of at most a^3 cells, a^3 <= 8 nf (the minimum over a
+// superset of a point's candidate triangles is the same value, and its cell still lists every triangle closer than max_dist); the sampler
+// scans each mesh in its own blocks of SCAN_PER_BLOCK faces with its own top-level tree, as scan<double, double, true> does on that mesh.
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <vector>
+
 #include "ls_common.h"
 
 // bit-identity with numpy's float64 arithmetic: no contraction of a * b + c into an fma anywhere in this file
@@ -58,21 +69,27 @@ __device__ T block_scan_excl(T v, T* lds, T& total) {    // SCAN_T threads; excl
     return ex;
 }
 
+// the block sums of x[b * SCAN_PER_BLOCK ...] (block b of an n-element array), written to *blk_b
 template <typename In, typename T>
-__global__ __launch_bounds__(SCAN_T) void scan_reduce_kernel(const In* __restrict__ x, long long n, T* __restrict__ blk) {
+__device__ void scan_reduce_block(const In* __restrict__ x, long long n, long long b, T* __restrict__ blk_b) {
     __shared__ T lds[SCAN_T];
-    const long long base = (long long)blockIdx.x * SCAN_PER_BLOCK + (long long)threadIdx.x * SCAN_ITEMS;
+    const long long base = b * SCAN_PER_BLOCK + (long long)threadIdx.x * SCAN_ITEMS;
     T s = T(0);
     for (int k = 0; k < SCAN_ITEMS; ++k)
         if (base + k < n) s += (T)x[base + k];
     T total;
     block_scan_excl<T>(s, lds, total);
-    if (threadIdx.x == 0) blk[blockIdx.x] = total;
+    if (threadIdx.x == 0) *blk_b = total;
+}
+
+template <typename In, typename T>
+__global__ __launch_bounds__(SCAN_T) void scan_reduce_kernel(const In* __restrict__ x, long long n, T* __restrict__ blk) {
+    scan_reduce_block<In, T>(x, n, blockIdx.x, blk + blockIdx.x);
 }
 
 // exclusive scan of the nblk block sums in place; total_out (nullable) = sum of everything
 template <typename T>
-__global__ __launch_bounds__(1024) void scan_top_kernel(T* __restrict__ blk, int nblk, long long* __restrict__ total_out) {
+__device__ void scan_top_block(T* __restrict__ blk, int nblk, long long* __restrict__ total_out) {   // 1024 threads
     __shared__ T lds[1024];
     const int tid = threadIdx.x;
     const int per = (nblk + 1023) / 1024;
@@ -98,12 +115,16 @@ __global__ __launch_bounds__(1024) void scan_top_kernel(T* __restrict__ blk, int
     if (tid == 1023 && total_out) *total_out = (long long)lds[1023];
 }
 
-// out[i] = prefix of x: exclusive (INCL = false) or inclusive, the offsets of the block sums added
+template <typename T>
+__global__ __launch_bounds__(1024) void scan_top_kernel(T* __restrict__ blk, int nblk, long long* __restrict__ total_out) {
+    scan_top_block<T>(blk, nblk, total_out);
+}
+
+// out[i] = prefix of x over block b: exclusive (INCL = false) or inclusive, blk_b (the scanned sum of the blocks before b) added
 template <typename In, typename T, bool INCL>
-__global__ __launch_bounds__(SCAN_T) void scan_apply_kernel(const In* __restrict__ x, long long n, const T* __restrict__ blk,
-                                                            T* __restrict__ out) {
+__device__ void scan_apply_block(const In* __restrict__ x, long long n, long long b, T blk_b, T* __restrict__ out) {
     __shared__ T lds[SCAN_T];
-    const long long base = (long long)blockIdx.x * SCAN_PER_BLOCK + (long long)threadIdx.x * SCAN_ITEMS;
+    const long long base = b * SCAN_PER_BLOCK + (long long)threadIdx.x * SCAN_ITEMS;
     T v[SCAN_ITEMS];
     T s = T(0);
     for (int k = 0; k < SCAN_ITEMS; ++k) {
@@ -111,12 +132,18 @@ __global__ __launch_bounds__(SCAN_T) void scan_apply_kernel(const In* __restrict
         s += v[k];
     }
     T total;
-    T run = block_scan_excl<T>(s, lds, total) + blk[blockIdx.x];
+    T run = block_scan_excl<T>(s, lds, total) + blk_b;
     for (int k = 0; k < SCAN_ITEMS; ++k) {
         if (INCL) run += v[k];
         if (base + k < n) out[base + k] = run;
         if (!INCL) run += v[k];
     }
+}
+
+template <typename In, typename T, bool INCL>
+__global__ __launch_bounds__(SCAN_T) void scan_apply_kernel(const In* __restrict__ x, long long n, const T* __restrict__ blk,
+                                                            T* __restrict__ out) {
+    scan_apply_block<In, T, INCL>(x, n, blockIdx.x, blk[blockIdx.x], out);
 }
 
 template <typename In, typename T, bool INCL>
@@ -139,9 +166,10 @@ __device__ __forceinline__ bool corner(const double* __restrict__ V, int nv, con
 }
 
 // bounding box of the faces' corners (inside_mesh.py:13-20: unreferenced vertices do not count), the rescaling of the point-in-mesh test
-// (scale = (R-1)/(max-min), translate = 0.5 - scale*min) and, for max_dist > 0, the distance grid.  One workgroup.
-__global__ __launch_bounds__(1024) void bbox_kernel(const double* __restrict__ V, int nv, const int32_t* __restrict__ F, int nf, int R,
-                                                    double max_dist, Params* __restrict__ prm) {
+// (scale = (R-1)/(max-min), translate = 0.5 - scale*min) and, for max_dist > 0, the distance grid (at most axis_cap cells per axis).
+// One workgroup of 1024 threads.
+__device__ void bbox_block(const double* __restrict__ V, int nv, const int32_t* __restrict__ F, int nf, int R, double max_dist, int axis_cap,
+                           Params* __restrict__ prm) {
     __shared__ double slo[3][1024], shi[3][1024];
     __shared__ int sbad[1024];
     const int tid = threadIdx.x;
@@ -184,7 +212,7 @@ __global__ __launch_bounds__(1024) void bbox_kernel(const double* __restrict__ V
         if (max_dist > 0) {
             const double org = mn - max_dist, top = mx + max_dist;
             const double cells = (top - org) / max_dist;
-            const int g = cells >= (double)DIST_GRID_AXIS ? DIST_GRID_AXIS : (cells >= 1.0 ? (int)cells : 1);
+            const int g = cells >= (double)axis_cap ? axis_cap : (cells >= 1.0 ? (int)cells : 1);
             prm->org[a] = org;
             prm->top[a] = top;
             prm->g[a] = g;
@@ -192,6 +220,11 @@ __global__ __launch_bounds__(1024) void bbox_kernel(const double* __restrict__ V
         }
     }
     prm->valid = sbad[0] & 1 ? -1 : valid;
+}
+
+__global__ __launch_bounds__(1024) void bbox_kernel(const double* __restrict__ V, int nv, const int32_t* __restrict__ F, int nf, int R,
+                                                    double max_dist, Params* __restrict__ prm) {
+    bbox_block(V, nv, F, nf, R, max_dist, DIST_GRID_AXIS, prm);
 }
 
 // ------------------------------------------------------------------------------------------------ point in mesh (inside_mesh.py + triangle_hash.pyx)
@@ -206,19 +239,16 @@ __device__ __forceinline__ int hash_cell(double v, int R) {
 
 __device__ __forceinline__ double rescale(const Params& p, int a, double v) { return p.scale[a] * v + p.translate[a]; }
 
-__global__ __launch_bounds__(256) void contains_prep_kernel(const double* __restrict__ V, int nv, const int32_t* __restrict__ F, int nf, int R,
-                                                            const Params* __restrict__ prm, double* __restrict__ tri, Cells2* __restrict__ tcell,
-                                                            int* __restrict__ cell_count) {
-    const int f = blockIdx.x * 256 + threadIdx.x;
-    if (f >= nf || prm->valid != 1) return;
-    const Params p = *prm;
+// face f of a mesh with valid == 1: its rescaled corners (tri_f [9]), its hash cells, their counts
+__device__ __forceinline__ void contains_prep_face(const double* __restrict__ V, int nv, const int32_t* __restrict__ F, int f, int R, const Params& p,
+                                                   double* __restrict__ tri_f, Cells2* __restrict__ tcell_f, int* __restrict__ cell_count) {
     double t[3][3];
     for (int c = 0; c < 3; ++c) {
         double v[3];
         corner(V, nv, F, f, c, v);   // valid == 1: every index is in range
         for (int a = 0; a < 3; ++a) {
             t[c][a] = rescale(p, a, v[a]);
-            tri[(size_t)f * 9 + c * 3 + a] = t[c][a];
+            tri_f[c * 3 + a] = t[c][a];
         }
     }
     // Cython's min(a, b, c) / max(a, b, c): first operand, replaced by a strictly smaller / larger one
@@ -230,37 +260,46 @@ __global__ __launch_bounds__(256) void contains_prep_kernel(const double* __rest
         if (t[c][1] > mxy) mxy = t[c][1];
     }
     const Cells2 cl{hash_cell(mnx, R), hash_cell(mxx, R), hash_cell(mny, R), hash_cell(mxy, R)};
-    tcell[f] = cl;
+    *tcell_f = cl;
     for (int x = cl.x0; x <= cl.x1; ++x)
         for (int y = cl.y0; y <= cl.y1; ++y) atomicAdd(&cell_count[(size_t)x * R + y], 1);
 }
 
+__global__ __launch_bounds__(256) void contains_prep_kernel(const double* __restrict__ V, int nv, const int32_t* __restrict__ F, int nf, int R,
+                                                            const Params* __restrict__ prm, double* __restrict__ tri, Cells2* __restrict__ tcell,
+                                                            int* __restrict__ cell_count) {
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    if (f >= nf || prm->valid != 1) return;
+    const Params p = *prm;
+    contains_prep_face(V, nv, F, f, R, p, tri + (size_t)f * 9, tcell + f, cell_count);
+}
+
 // entries of cell c: entries[start[c] .. start[c] + count[c]); cursor (zeroed) counts the slots taken.  Nothing is written at or past cap.
+__device__ __forceinline__ void contains_fill_face(const Cells2 cl, int R, int32_t id, const long long* __restrict__ start, int* __restrict__ cursor,
+                                                   int32_t* __restrict__ entries, long long cap) {
+    for (int x = cl.x0; x <= cl.x1; ++x)
+        for (int y = cl.y0; y <= cl.y1; ++y) {
+            const size_t c = (size_t)x * R + y;
+            const long long o = start[c] + atomicAdd(&cursor[c], 1);
+            if (o < cap) entries[o] = id;
+        }
+}
+
 __global__ __launch_bounds__(256) void contains_fill_kernel(int nf, int R, const Params* __restrict__ prm, const Cells2* __restrict__ tcell,
                                                             const long long* __restrict__ start, int* __restrict__ cursor,
                                                             int32_t* __restrict__ entries, long long cap) {
     const int f = blockIdx.x * 256 + threadIdx.x;
     if (f >= nf || prm->valid != 1) return;
-    const Cells2 cl = tcell[f];
-    for (int x = cl.x0; x <= cl.x1; ++x)
-        for (int y = cl.y0; y <= cl.y1; ++y) {
-            const size_t c = (size_t)x * R + y;
-            const long long o = start[c] + atomicAdd(&cursor[c], 1);
-            if (o < cap) entries[o] = f;
-        }
+    contains_fill_face(tcell[f], R, f, start, cursor, entries, cap);
 }
 
-// one point against the triangles of its hash cell: parity of the strict 2-D hits above and below it (inside_mesh.py:39-154)
-__global__ __launch_bounds__(256) void contains_query_kernel(const double* __restrict__ P, long long n, int R, const Params* __restrict__ prm,
-                                                             const double* __restrict__ tri, const long long* __restrict__ start,
-                                                             const int* __restrict__ count, const int32_t* __restrict__ entries,
-                                                             const long long* __restrict__ total, long long cap, uint8_t* __restrict__ out) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const Params p = *prm;
+// one point (q [3]) against the triangles of its hash cell: parity of the strict 2-D hits above and below it (inside_mesh.py:39-154).
+// The mesh has valid == 1 and its bins are complete; entries index tri in rows of 9.
+__device__ bool contains_point(const double* __restrict__ q, int R, const Params& p, const double* __restrict__ tri,
+                               const long long* __restrict__ start, const int* __restrict__ count, const int32_t* __restrict__ entries) {
     bool inside = false;
-    if (p.valid == 1 && *total <= cap) {
-        const double px = rescale(p, 0, P[i * 3 + 0]), py = rescale(p, 1, P[i * 3 + 1]), pz = rescale(p, 2, P[i * 3 + 2]);
+    {
+        const double px = rescale(p, 0, q[0]), py = rescale(p, 1, q[1]), pz = rescale(p, 2, q[2]);
         const double Rd = (double)R;
         if (0 <= px && px <= Rd && 0 <= py && py <= Rd && 0 <= pz && pz <= Rd) {
             const int x = (int)px, y = (int)py;      // int(points[i, 0]) (triangle_hash.pyx:58-60); px, py in [0, R]
@@ -300,6 +339,17 @@ __global__ __launch_bounds__(256) void contains_query_kernel(const double* __res
             }
         }
     }
+    return inside;
+}
+
+__global__ __launch_bounds__(256) void contains_query_kernel(const double* __restrict__ P, long long n, int R, const Params* __restrict__ prm,
+                                                             const double* __restrict__ tri, const long long* __restrict__ start,
+                                                             const int* __restrict__ count, const int32_t* __restrict__ entries,
+                                                             const long long* __restrict__ total, long long cap, uint8_t* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const Params p = *prm;
+    const bool inside = p.valid == 1 && *total <= cap && contains_point(P + i * 3, R, p, tri, start, count, entries);
     out[i] = inside ? 1 : 0;
 }
 
@@ -312,16 +362,13 @@ __device__ __forceinline__ int grid_cell(const Params& p, int a, double v) {
     return min(max(i, 0), p.g[a] - 1);
 }
 
-__global__ __launch_bounds__(256) void dist_prep_kernel(const double* __restrict__ V, int nv, const int32_t* __restrict__ F, int nf, double max_dist,
-                                                        const Params* __restrict__ prm, double* __restrict__ tri, Cells3* __restrict__ tcell,
-                                                        int* __restrict__ cell_count) {
-    const int f = blockIdx.x * 256 + threadIdx.x;
-    if (f >= nf || prm->valid < 0) return;
-    const Params p = *prm;
+// face f of a mesh with valid >= 0: its corners (tri_f [9]), the grid cells its bounding box grown by max_dist touches, their counts
+__device__ __forceinline__ void dist_prep_face(const double* __restrict__ V, int nv, const int32_t* __restrict__ F, int f, double max_dist,
+                                               const Params& p, double* __restrict__ tri_f, Cells3* __restrict__ tcell_f, int* __restrict__ cell_count) {
     double t[3][3];
     for (int c = 0; c < 3; ++c) {
         corner(V, nv, F, f, c, t[c]);
-        for (int a = 0; a < 3; ++a) tri[(size_t)f * 9 + c * 3 + a] = t[c][a];
+        for (int a = 0; a < 3; ++a) tri_f[c * 3 + a] = t[c][a];
     }
     Cells3 cl;
     for (int a = 0; a < 3; ++a) {
@@ -329,10 +376,30 @@ __global__ __launch_bounds__(256) void dist_prep_kernel(const double* __restrict
         cl.lo[a] = grid_cell(p, a, mn - max_dist);
         cl.hi[a] = grid_cell(p, a, mx + max_dist);
     }
-    tcell[f] = cl;
+    *tcell_f = cl;
     for (int x = cl.lo[0]; x <= cl.hi[0]; ++x)
         for (int y = cl.lo[1]; y <= cl.hi[1]; ++y)
             for (int z = cl.lo[2]; z <= cl.hi[2]; ++z) atomicAdd(&cell_count[((size_t)x * p.g[1] + y) * p.g[2] + z], 1);
+}
+
+__global__ __launch_bounds__(256) void dist_prep_kernel(const double* __restrict__ V, int nv, const int32_t* __restrict__ F, int nf, double max_dist,
+                                                        const Params* __restrict__ prm, double* __restrict__ tri, Cells3* __restrict__ tcell,
+                                                        int* __restrict__ cell_count) {
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    if (f >= nf || prm->valid < 0) return;
+    const Params p = *prm;
+    dist_prep_face(V, nv, F, f, max_dist, p, tri + (size_t)f * 9, tcell + f, cell_count);
+}
+
+__device__ __forceinline__ void dist_fill_face(const Cells3 cl, int gy, int gz, int32_t id, const long long* __restrict__ start, int* __restrict__ cursor,
+                                               int32_t* __restrict__ entries, long long cap) {
+    for (int x = cl.lo[0]; x <= cl.hi[0]; ++x)
+        for (int y = cl.lo[1]; y <= cl.hi[1]; ++y)
+            for (int z = cl.lo[2]; z <= cl.hi[2]; ++z) {
+                const size_t c = ((size_t)x * gy + y) * gz + z;
+                const long long o = start[c] + atomicAdd(&cursor[c], 1);
+                if (o < cap) entries[o] = id;
+            }
 }
 
 __global__ __launch_bounds__(256) void dist_fill_kernel(int nf, const Params* __restrict__ prm, const Cells3* __restrict__ tcell,
@@ -340,15 +407,7 @@ __global__ __launch_bounds__(256) void dist_fill_kernel(int nf, const Params* __
                                                         long long cap) {
     const int f = blockIdx.x * 256 + threadIdx.x;
     if (f >= nf || prm->valid < 0) return;
-    const int gy = prm->g[1], gz = prm->g[2];
-    const Cells3 cl = tcell[f];
-    for (int x = cl.lo[0]; x <= cl.hi[0]; ++x)
-        for (int y = cl.lo[1]; y <= cl.hi[1]; ++y)
-            for (int z = cl.lo[2]; z <= cl.hi[2]; ++z) {
-                const size_t c = ((size_t)x * gy + y) * gz + z;
-                const long long o = start[c] + atomicAdd(&cursor[c], 1);
-                if (o < cap) entries[o] = f;
-            }
+    dist_fill_face(tcell[f], prm->g[1], prm->g[2], f, start, cursor, entries, cap);
 }
 
 __device__ __forceinline__ double dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
@@ -409,18 +468,14 @@ __device__ double point_triangle_d2(const double* p, const double* a, const doub
     return r;
 }
 
-__global__ __launch_bounds__(256) void dist_query_kernel(const double* __restrict__ P, long long n, double max_dist, const Params* __restrict__ prm,
-                                                         const double* __restrict__ tri, const long long* __restrict__ start,
-                                                         const int* __restrict__ count, const int32_t* __restrict__ entries,
-                                                         const long long* __restrict__ total, long long cap, double* __restrict__ out) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const Params p = *prm;
+// distance from q [3] to the mesh when < max_dist, +inf otherwise; binned = the mesh's bins are complete (valid >= 0, nothing past cap)
+__device__ double dist_point(const double* __restrict__ P3, double max_dist, const Params& p, bool binned, const double* __restrict__ tri,
+                             const long long* __restrict__ start, const int* __restrict__ count, const int32_t* __restrict__ entries) {
     double best = INFINITY;
-    const double q[3] = {P[i * 3 + 0], P[i * 3 + 1], P[i * 3 + 2]};
+    const double q[3] = {P3[0], P3[1], P3[2]};
     // outside [min - max_dist, max + max_dist] on an axis: farther than max_dist from every triangle
     const bool in_dom = q[0] >= p.org[0] && q[0] <= p.top[0] && q[1] >= p.org[1] && q[1] <= p.top[1] && q[2] >= p.org[2] && q[2] <= p.top[2];
-    if (p.valid >= 0 && *total <= cap && in_dom) {
+    if (binned && in_dom) {
         const size_t c = ((size_t)grid_cell(p, 0, q[0]) * p.g[1] + grid_cell(p, 1, q[1])) * p.g[2] + grid_cell(p, 2, q[2]);
         const long long s = start[c];
         const int m = count[c];
@@ -430,7 +485,17 @@ __global__ __launch_bounds__(256) void dist_query_kernel(const double* __restric
         }
     }
     const double d = sqrt(best);
-    out[i] = d < max_dist ? d : INFINITY;
+    return d < max_dist ? d : INFINITY;
+}
+
+__global__ __launch_bounds__(256) void dist_query_kernel(const double* __restrict__ P, long long n, double max_dist, const Params* __restrict__ prm,
+                                                         const double* __restrict__ tri, const long long* __restrict__ start,
+                                                         const int* __restrict__ count, const int32_t* __restrict__ entries,
+                                                         const long long* __restrict__ total, long long cap, double* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const Params p = *prm;
+    out[i] = dist_point(P + i * 3, max_dist, p, p.valid >= 0 && *total <= cap, tri, start, count, entries);
 }
 
 __global__ __launch_bounds__(256) void fill_f64_kernel(double* __restrict__ out, long long n, double v) {
@@ -450,23 +515,25 @@ __device__ __forceinline__ double uniform(unsigned long long key, unsigned long 
 }
 
 // trimesh Trimesh.area_faces: |cross(v1 - v0, v2 - v0)| / 2, components written as np.cross does
+__device__ __forceinline__ double face_area(const double* __restrict__ V, int nv, const int32_t* __restrict__ F, int f) {
+    double a[3], b[3], c[3];
+    if (!corner(V, nv, F, f, 0, a) || !corner(V, nv, F, f, 1, b) || !corner(V, nv, F, f, 2, c)) return 0.0;
+    const double ux = b[0] - a[0], uy = b[1] - a[1], uz = b[2] - a[2];
+    const double wx = c[0] - a[0], wy = c[1] - a[1], wz = c[2] - a[2];
+    const double cx = uy * wz - uz * wy, cy = uz * wx - ux * wz, cz = ux * wy - uy * wx;
+    return sqrt(cx * cx + cy * cy + cz * cz) / 2.0;
+}
+
 __global__ __launch_bounds__(256) void area_kernel(const double* __restrict__ V, int nv, const int32_t* __restrict__ F, int nf,
                                                    double* __restrict__ area) {
     const int f = blockIdx.x * 256 + threadIdx.x;
     if (f >= nf) return;
-    double a[3], b[3], c[3];
-    if (!corner(V, nv, F, f, 0, a) || !corner(V, nv, F, f, 1, b) || !corner(V, nv, F, f, 2, c)) { area[f] = 0.0; return; }
-    const double ux = b[0] - a[0], uy = b[1] - a[1], uz = b[2] - a[2];
-    const double wx = c[0] - a[0], wy = c[1] - a[1], wz = c[2] - a[2];
-    const double cx = uy * wz - uz * wy, cy = uz * wx - ux * wz, cz = ux * wy - uy * wx;
-    area[f] = sqrt(cx * cx + cy * cy + cz * cz) / 2.0;
+    area[f] = face_area(V, nv, F, f);
 }
 
-__global__ __launch_bounds__(256) void sample_kernel(const double* __restrict__ V, int nv, const int32_t* __restrict__ F, int nf,
-                                                     const double* __restrict__ cum, long long count, unsigned long long key,
-                                                     double* __restrict__ pts, int64_t* __restrict__ face_out) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
+// sample i of a mesh (cum: its inclusive cumulative face areas): point pts3 [3], local face index *face_i (face_i nullable)
+__device__ __forceinline__ void sample_one(const double* __restrict__ V, int nv, const int32_t* __restrict__ F, int nf, const double* __restrict__ cum,
+                                           unsigned long long key, long long i, double* __restrict__ pts3, int64_t* __restrict__ face_i) {
     const unsigned long long j = 3ull * (unsigned long long)i;
     const double pick = uniform(key, j) * cum[nf - 1];
     // np.searchsorted(cumsum, pick) (side 'left'): first face whose cumulative area reaches pick
@@ -481,8 +548,183 @@ __global__ __launch_bounds__(256) void sample_kernel(const double* __restrict__ 
     double a[3] = {0, 0, 0}, b[3] = {0, 0, 0}, c[3] = {0, 0, 0};
     const bool ok = corner(V, nv, F, lo, 0, a) && corner(V, nv, F, lo, 1, b) && corner(V, nv, F, lo, 2, c);
     for (int k = 0; k < 3; ++k)   // (tri_vectors * random_lengths).sum(axis=1) + tri_origins
-        pts[i * 3 + k] = ok ? (r1 * (b[k] - a[k]) + r2 * (c[k] - a[k])) + a[k] : NAN;
-    if (face_out) face_out[i] = lo;
+        pts3[k] = ok ? (r1 * (b[k] - a[k]) + r2 * (c[k] - a[k])) + a[k] : NAN;
+    if (face_i) *face_i = lo;
+}
+
+__global__ __launch_bounds__(256) void sample_kernel(const double* __restrict__ V, int nv, const int32_t* __restrict__ F, int nf,
+                                                     const double* __restrict__ cum, long long count, unsigned long long key,
+                                                     double* __restrict__ pts, int64_t* __restrict__ face_out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    sample_one(V, nv, F, nf, cum, key, i, pts + i * 3, face_out ? face_out + i : nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------ ragged batches of meshes
+// Mesh m of a batch owns V[vert_off[m] .. vert_off[m+1]), F[face_off[m] .. face_off[m+1]) (indices local to the mesh) and the points /
+// samples [pt_off[m] .. pt_off[m+1]).  The device copy of the offsets (offs) is OFF_ARRAYS arrays of M + 1 int64 back to back; OFF_AUX is
+// the mesh's first distance-grid cell (distance) or first scan block (sampler), OFF_AXIS the cells per axis of its distance grid at most.
+enum { OFF_V = 0, OFF_F, OFF_P, OFF_AUX, OFF_AXIS, OFF_ARRAYS };
+
+__device__ __forceinline__ const long long* off_arr(const long long* offs, int M, int k) { return offs + (size_t)k * (M + 1); }
+
+// the mesh m with off[m] <= i < off[m + 1] (i < off[M]; meshes with an empty range are never the owner)
+__device__ __forceinline__ int owner(const long long* __restrict__ off, int M, long long i) {
+    int lo = 0, hi = M - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= i) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+struct MeshRef {
+    const double* V;
+    int nv;
+    const int32_t* F;
+    int nf;
+    long long f0;   // global index of the mesh's first face
+};
+__device__ __forceinline__ MeshRef mesh_ref(const double* V, const int32_t* F, const long long* offs, int M, int m) {
+    const long long* vo = off_arr(offs, M, OFF_V);
+    const long long* fo = off_arr(offs, M, OFF_F);
+    return {V + vo[m] * 3, (int)(vo[m + 1] - vo[m]), F + fo[m] * 3, (int)(fo[m + 1] - fo[m]), fo[m]};
+}
+
+// one workgroup per mesh: its Params (max_dist > 0: its distance grid, at most offs[OFF_AXIS][m] cells per axis)
+__global__ __launch_bounds__(1024) void bbox_batch_kernel(const double* __restrict__ V, const int32_t* __restrict__ F, const long long* __restrict__ offs,
+                                                          int M, int R, double max_dist, Params* __restrict__ prm) {
+    const int m = blockIdx.x;
+    const MeshRef r = mesh_ref(V, F, offs, M, m);
+    bbox_block(r.V, r.nv, r.F, r.nf, R, max_dist, max_dist > 0 ? (int)off_arr(offs, M, OFF_AXIS)[m] : DIST_GRID_AXIS, prm + m);
+}
+
+// contains: mesh m's hash is cells [m R^2, (m + 1) R^2); bin entries are global face indices (rows of tri)
+__global__ __launch_bounds__(256) void contains_prep_batch_kernel(const double* __restrict__ V, const int32_t* __restrict__ F,
+                                                                  const long long* __restrict__ offs, int M, long long nf_total, int R,
+                                                                  const Params* __restrict__ prm, double* __restrict__ tri, Cells2* __restrict__ tcell,
+                                                                  int* __restrict__ cell_count) {
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= nf_total) return;
+    const int m = owner(off_arr(offs, M, OFF_F), M, g);
+    if (prm[m].valid != 1) return;
+    const Params p = prm[m];
+    const MeshRef r = mesh_ref(V, F, offs, M, m);
+    contains_prep_face(r.V, r.nv, r.F, (int)(g - r.f0), R, p, tri + (size_t)g * 9, tcell + g, cell_count + (size_t)m * R * R);
+}
+
+__global__ __launch_bounds__(256) void contains_fill_batch_kernel(const long long* __restrict__ offs, int M, long long nf_total, int R,
+                                                                  const Params* __restrict__ prm, const Cells2* __restrict__ tcell,
+                                                                  const long long* __restrict__ start, int* __restrict__ cursor,
+                                                                  int32_t* __restrict__ entries, long long cap) {
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= nf_total) return;
+    const int m = owner(off_arr(offs, M, OFF_F), M, g);
+    if (prm[m].valid != 1) return;
+    const size_t base = (size_t)m * R * R;
+    contains_fill_face(tcell[g], R, (int32_t)g, start + base, cursor + base, entries, cap);
+}
+
+__global__ __launch_bounds__(256) void contains_query_batch_kernel(const double* __restrict__ P, const long long* __restrict__ offs, int M,
+                                                                   long long n_total, int R, const Params* __restrict__ prm,
+                                                                   const double* __restrict__ tri, const long long* __restrict__ start,
+                                                                   const int* __restrict__ count, const int32_t* __restrict__ entries,
+                                                                   const long long* __restrict__ total, long long cap, uint8_t* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_total) return;
+    const int m = owner(off_arr(offs, M, OFF_P), M, i);
+    const long long* fo = off_arr(offs, M, OFF_F);
+    const Params p = prm[m];
+    const size_t base = (size_t)m * R * R;
+    const bool inside = fo[m + 1] > fo[m] && p.valid == 1 && *total <= cap && contains_point(P + i * 3, R, p, tri, start + base, count + base, entries);
+    out[i] = inside ? 1 : 0;
+}
+
+// distance: mesh m's grid is cells [offs[OFF_AUX][m], offs[OFF_AUX][m + 1])
+__global__ __launch_bounds__(256) void dist_prep_batch_kernel(const double* __restrict__ V, const int32_t* __restrict__ F, const long long* __restrict__ offs,
+                                                              int M, long long nf_total, double max_dist, const Params* __restrict__ prm,
+                                                              double* __restrict__ tri, Cells3* __restrict__ tcell, int* __restrict__ cell_count) {
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= nf_total) return;
+    const int m = owner(off_arr(offs, M, OFF_F), M, g);
+    if (prm[m].valid < 0) return;
+    const Params p = prm[m];
+    const MeshRef r = mesh_ref(V, F, offs, M, m);
+    dist_prep_face(r.V, r.nv, r.F, (int)(g - r.f0), max_dist, p, tri + (size_t)g * 9, tcell + g, cell_count + off_arr(offs, M, OFF_AUX)[m]);
+}
+
+__global__ __launch_bounds__(256) void dist_fill_batch_kernel(const long long* __restrict__ offs, int M, long long nf_total, const Params* __restrict__ prm,
+                                                              const Cells3* __restrict__ tcell, const long long* __restrict__ start,
+                                                              int* __restrict__ cursor, int32_t* __restrict__ entries, long long cap) {
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= nf_total) return;
+    const int m = owner(off_arr(offs, M, OFF_F), M, g);
+    if (prm[m].valid < 0) return;
+    const long long base = off_arr(offs, M, OFF_AUX)[m];
+    dist_fill_face(tcell[g], prm[m].g[1], prm[m].g[2], (int32_t)g, start + base, cursor + base, entries, cap);
+}
+
+__global__ __launch_bounds__(256) void dist_query_batch_kernel(const double* __restrict__ P, const long long* __restrict__ offs, int M, long long n_total,
+                                                               double max_dist, const Params* __restrict__ prm, const double* __restrict__ tri,
+                                                               const long long* __restrict__ start, const int* __restrict__ count,
+                                                               const int32_t* __restrict__ entries, const long long* __restrict__ total, long long cap,
+                                                               double* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_total) return;
+    const int m = owner(off_arr(offs, M, OFF_P), M, i);
+    const long long* fo = off_arr(offs, M, OFF_F);
+    if (fo[m + 1] == fo[m]) { out[i] = INFINITY; return; }   // an empty mesh is infinitely far away
+    const Params p = prm[m];
+    const long long base = off_arr(offs, M, OFF_AUX)[m];
+    out[i] = dist_point(P + i * 3, max_dist, p, p.valid >= 0 && *total <= cap, tri, start + base, count + base, entries);
+}
+
+// sampler: face areas of every mesh, then each mesh's inclusive scan exactly as scan<double, double, true> on that mesh alone -- its own
+// blocks of SCAN_PER_BLOCK faces (block sums blk[offs[OFF_AUX][m] ...]) and one top-level workgroup per mesh
+__global__ __launch_bounds__(256) void area_batch_kernel(const double* __restrict__ V, const int32_t* __restrict__ F, const long long* __restrict__ offs,
+                                                         int M, long long nf_total, double* __restrict__ area) {
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= nf_total) return;
+    const MeshRef r = mesh_ref(V, F, offs, M, owner(off_arr(offs, M, OFF_F), M, g));
+    area[g] = face_area(r.V, r.nv, r.F, (int)(g - r.f0));
+}
+
+__global__ __launch_bounds__(SCAN_T) void scan_reduce_batch_kernel(const double* __restrict__ area, const long long* __restrict__ offs, int M,
+                                                                   double* __restrict__ blk) {
+    const long long* bo = off_arr(offs, M, OFF_AUX);
+    const long long* fo = off_arr(offs, M, OFF_F);
+    const int m = owner(bo, M, blockIdx.x);
+    scan_reduce_block<double, double>(area + fo[m], fo[m + 1] - fo[m], blockIdx.x - bo[m], blk + blockIdx.x);
+}
+
+__global__ __launch_bounds__(1024) void scan_top_batch_kernel(double* __restrict__ blk, const long long* __restrict__ offs, int M) {
+    const long long* bo = off_arr(offs, M, OFF_AUX);
+    const int m = blockIdx.x;
+    const int nblk = (int)(bo[m + 1] - bo[m]);
+    if (nblk == 0) return;
+    scan_top_block<double>(blk + bo[m], nblk, nullptr);
+}
+
+__global__ __launch_bounds__(SCAN_T) void scan_apply_batch_kernel(const double* __restrict__ area, const long long* __restrict__ offs, int M,
+                                                                  const double* __restrict__ blk, double* __restrict__ cum) {
+    const long long* bo = off_arr(offs, M, OFF_AUX);
+    const long long* fo = off_arr(offs, M, OFF_F);
+    const int m = owner(bo, M, blockIdx.x);
+    scan_apply_block<double, double, true>(area + fo[m], fo[m + 1] - fo[m], blockIdx.x - bo[m], blk[blockIdx.x], cum + fo[m]);
+}
+
+__global__ __launch_bounds__(256) void sample_batch_kernel(const double* __restrict__ V, const int32_t* __restrict__ F, const long long* __restrict__ offs,
+                                                           int M, long long count_total, const double* __restrict__ cum,
+                                                           const unsigned long long* __restrict__ seeds, double* __restrict__ pts,
+                                                           int64_t* __restrict__ face_out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count_total) return;
+    const long long* co = off_arr(offs, M, OFF_P);
+    const int m = owner(co, M, i);
+    const MeshRef r = mesh_ref(V, F, offs, M, m);
+    sample_one(r.V, r.nv, r.F, r.nf, cum + r.f0, splitmix_mix(seeds[m] + 0x9E3779B97F4A7C15ull), i - co[m], pts + i * 3,
+               face_out ? face_out + i : nullptr);
 }
 
 }  // namespace mm
@@ -520,6 +762,78 @@ BinWs bin_layout(char* ws, int nf, long long cells, size_t cell_rec, size_t* byt
     w.blk = L.take<long long>(ws, (size_t)scan_blocks(cells));
     if (bytes) *bytes = L.off;
     return w;
+}
+
+// ---- ragged batches (host side)
+struct BatchWs {
+    long long* offs;
+    Params* prm;
+    double* tri;
+    void* tcell;
+    int* cell_count;
+    long long* start;
+    long long* blk;
+};
+BatchWs batch_bin_layout(char* ws, int M, long long nf_total, long long cells, size_t cell_rec, size_t* bytes) {
+    Layout L;
+    BatchWs w;
+    w.offs = L.take<long long>(ws, (size_t)OFF_ARRAYS * (M + 1));
+    w.prm = L.take<Params>(ws, (size_t)M);
+    w.tri = L.take<double>(ws, (size_t)nf_total * 9);
+    w.tcell = L.take<char>(ws, (size_t)nf_total * cell_rec);
+    w.cell_count = L.take<int>(ws, (size_t)cells);
+    w.start = L.take<long long>(ws, (size_t)cells);
+    w.blk = L.take<long long>(ws, (size_t)scan_blocks(cells));
+    if (bytes) *bytes = L.off;
+    return w;
+}
+
+// off[0] = 0, never decreasing, at most per_max per mesh, ending at total
+int check_ranges(const char* op, const char* what, int M, const long long* off, long long total, long long per_max) {
+    LS_REQUIRE(off, "%s: null %s", op, what);
+    LS_REQUIRE(off[0] == 0, "%s: %s[0] is %lld, not 0", op, what, off[0]);
+    for (int m = 0; m < M; ++m) {
+        LS_REQUIRE(off[m + 1] >= off[m], "%s: mesh %d: %s decreases (%lld -> %lld)", op, m, what, off[m], off[m + 1]);
+        LS_REQUIRE(off[m + 1] - off[m] <= per_max, "%s: mesh %d: %lld rows in %s, at most %lld per mesh", op, m, off[m + 1] - off[m], what, per_max);
+    }
+    LS_REQUIRE(off[M] == total, "%s: mesh %d: %s ends at %lld, which disagrees with the total %lld", op, M - 1, what, off[M], total);
+    return LS_OK;
+}
+
+// the argument checks of the single-mesh ops, per mesh
+int check_meshes(const char* op, int M, const double* V, long long nv_total, const long long* vert_off, const int32_t* F, long long nf_total,
+                 const long long* face_off) {
+    LS_REQUIRE(M >= 0 && nv_total >= 0 && nf_total >= 0, "%s: negative size (M %d, nv_total %lld, nf_total %lld)", op, M, nv_total, nf_total);
+    LS_REQUIRE(nf_total <= INT_MAX, "%s: %lld faces in the batch, at most %d", op, nf_total, INT_MAX);
+    int rc = check_ranges(op, "vert_off", M, vert_off, nv_total, INT_MAX);
+    if (rc != LS_OK) return rc;
+    rc = check_ranges(op, "face_off", M, face_off, nf_total, INT_MAX);
+    if (rc != LS_OK) return rc;
+    for (int m = 0; m < M; ++m)
+        LS_REQUIRE(face_off[m + 1] == face_off[m] || vert_off[m + 1] > vert_off[m], "%s: mesh %d: %lld faces and no vertices", op, m,
+                   face_off[m + 1] - face_off[m]);
+    LS_REQUIRE(nf_total == 0 || (V && F), "%s: null vertices / faces with nf_total = %lld", op, nf_total);
+    return LS_OK;
+}
+
+// the device copy of the offsets (aux, axis: nullable, zeros)
+std::vector<long long> pack_offsets(int M, const long long* vert_off, const long long* face_off, const long long* pt_off, const long long* aux,
+                                    const long long* axis) {
+    std::vector<long long> o((size_t)OFF_ARRAYS * (M + 1), 0);
+    const long long* src[OFF_ARRAYS] = {vert_off, face_off, pt_off, aux, axis};
+    for (int k = 0; k < OFF_ARRAYS; ++k)
+        if (src[k]) std::copy(src[k], src[k] + M + 1, o.begin() + (size_t)k * (M + 1));
+    return o;
+}
+
+// cells per axis of a mesh's distance grid in a batch: the largest a <= DIST_GRID_AXIS with a^3 <= 8 nf, at least 1 -- so the grids of
+// a batch hold at most 8 nf_total + M cells, where the single op always takes 128^3
+long long dist_axis_cap(long long nf) {
+    const long long t = 8 * nf;
+    long long a = (long long)std::cbrt((double)t);
+    while (a > 1 && a * a * a > t) --a;
+    while ((a + 1) * (a + 1) * (a + 1) <= t) ++a;
+    return std::min<long long>(std::max<long long>(a, 1), DIST_GRID_AXIS);
 }
 }  // namespace
 
@@ -647,6 +961,176 @@ int ls_mesh_sample_f64(const double* vertices, int nv, const int32_t* faces, int
     scan<double, double, true>(area, nf, blk, cum, nullptr, st);
     hipLaunchKernelGGL(sample_kernel, dim3(cdiv(count, 256)), dim3(256), 0, st, vertices, nv, faces, nf, cum, count,
                        splitmix_mix(seed + 0x9E3779B97F4A7C15ull), points_out, face_out);
+    LS_LAUNCH_CHECK();
+    return LS_OK;
+}
+
+// ---- ragged batches: every mesh's result is bit-identical to the single-mesh op on that mesh alone
+size_t ls_mesh_contains_batch_workspace_bytes(int M, long long nf_total, int hash_resolution) {
+    if (M < 0 || nf_total < 0 || nf_total > INT_MAX || hash_resolution < 2 || hash_resolution > MAX_HASH_RES) return 0;
+    size_t b;
+    batch_bin_layout(nullptr, M, nf_total, (long long)M * hash_resolution * hash_resolution, sizeof(Cells2), &b);
+    return b;
+}
+
+int ls_mesh_contains_batch_f64(int M, const double* vertices, long long nv_total, const long long* vert_off, const int32_t* faces, long long nf_total,
+                               const long long* face_off, const double* points, long long n_total, const long long* pt_off, int hash_resolution,
+                               uint8_t* inside_out, int32_t* entries, long long cap_entries, long long* count_out, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    const char* op = "mesh_contains_batch";
+    LS_REQUIRE(hash_resolution >= 2 && hash_resolution <= MAX_HASH_RES, "%s: hash_resolution must be in [2, %d], got %d", op, MAX_HASH_RES,
+               hash_resolution);
+    int rc = check_meshes(op, M, vertices, nv_total, vert_off, faces, nf_total, face_off);
+    if (rc != LS_OK) return rc;
+    LS_REQUIRE(n_total >= 0, "%s: negative n_total %lld", op, n_total);
+    rc = check_ranges(op, "pt_off", M, pt_off, n_total, LLONG_MAX);
+    if (rc != LS_OK) return rc;
+    LS_REQUIRE(count_out, "%s: null count_out", op);
+    LS_REQUIRE(cap_entries >= 0, "%s: negative cap_entries", op);
+    LS_REQUIRE(!entries || n_total == 0 || (points && inside_out), "%s: null points / inside_out with n_total = %lld", op, n_total);
+    hipStream_t st = (hipStream_t)stream;
+    if (nf_total == 0) {   // every mesh is empty: nothing is inside
+        LS_HIP_CHECK(hipMemsetAsync(count_out, 0, sizeof(long long), st));
+        if (entries && n_total > 0) LS_HIP_CHECK(hipMemsetAsync(inside_out, 0, (size_t)n_total, st));
+        return LS_OK;
+    }
+    const int R = hash_resolution;
+    if (!workspace || workspace_bytes < ls_mesh_contains_batch_workspace_bytes(M, nf_total, R)) {
+        set_error("%s: workspace too small (need ls_mesh_contains_batch_workspace_bytes(%d, %lld, %d))", op, M, nf_total, R);
+        return LS_ERR_WORKSPACE;
+    }
+    const long long cells = (long long)M * R * R;
+    BatchWs w = batch_bin_layout((char*)workspace, M, nf_total, cells, sizeof(Cells2), nullptr);
+    Cells2* tcell = (Cells2*)w.tcell;
+    const int fb = cdiv(nf_total, 256);
+    // pageable host memory: the copy has read the offsets when it returns
+    const std::vector<long long> offs = pack_offsets(M, vert_off, face_off, pt_off, nullptr, nullptr);
+    LS_HIP_CHECK(hipMemcpyAsync(w.offs, offs.data(), offs.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+    LS_HIP_CHECK(hipMemsetAsync(w.cell_count, 0, (size_t)cells * sizeof(int), st));
+    hipLaunchKernelGGL(bbox_batch_kernel, dim3(M), dim3(1024), 0, st, vertices, faces, w.offs, M, R, 0.0, w.prm);
+    hipLaunchKernelGGL(contains_prep_batch_kernel, dim3(fb), dim3(256), 0, st, vertices, faces, w.offs, M, nf_total, R, w.prm, w.tri, tcell,
+                       w.cell_count);
+    scan<int, long long, false>(w.cell_count, cells, w.blk, w.start, count_out, st);
+    LS_LAUNCH_CHECK();
+    if (!entries) return LS_OK;   // sizing call: one entry count for the whole batch
+    LS_HIP_CHECK(hipMemsetAsync(w.cell_count, 0, (size_t)cells * sizeof(int), st));
+    hipLaunchKernelGGL(contains_fill_batch_kernel, dim3(fb), dim3(256), 0, st, w.offs, M, nf_total, R, w.prm, tcell, w.start, w.cell_count, entries,
+                       cap_entries);
+    if (n_total > 0)
+        hipLaunchKernelGGL(contains_query_batch_kernel, dim3(cdiv(n_total, 256)), dim3(256), 0, st, points, w.offs, M, n_total, R, w.prm, w.tri,
+                           w.start, w.cell_count, entries, count_out, cap_entries, inside_out);
+    LS_LAUNCH_CHECK();
+    return LS_OK;
+}
+
+size_t ls_mesh_distance_batch_workspace_bytes(int M, long long nf_total) {
+    if (M < 0 || nf_total < 0 || nf_total > INT_MAX) return 0;
+    size_t b;
+    batch_bin_layout(nullptr, M, nf_total, 8 * nf_total + M, sizeof(Cells3), &b);
+    return b;
+}
+
+int ls_mesh_distance_batch_f64(int M, const double* vertices, long long nv_total, const long long* vert_off, const int32_t* faces, long long nf_total,
+                               const long long* face_off, const double* points, long long n_total, const long long* pt_off, double max_dist,
+                               double* dist_out, int32_t* entries, long long cap_entries, long long* count_out, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    const char* op = "mesh_distance_batch";
+    LS_REQUIRE(max_dist > 0 && max_dist < (double)INFINITY, "%s: max_dist must be positive and finite, got %g", op, max_dist);
+    int rc = check_meshes(op, M, vertices, nv_total, vert_off, faces, nf_total, face_off);
+    if (rc != LS_OK) return rc;
+    LS_REQUIRE(n_total >= 0, "%s: negative n_total %lld", op, n_total);
+    rc = check_ranges(op, "pt_off", M, pt_off, n_total, LLONG_MAX);
+    if (rc != LS_OK) return rc;
+    LS_REQUIRE(count_out, "%s: null count_out", op);
+    LS_REQUIRE(cap_entries >= 0, "%s: negative cap_entries", op);
+    LS_REQUIRE(!entries || n_total == 0 || (points && dist_out), "%s: null points / dist_out with n_total = %lld", op, n_total);
+    hipStream_t st = (hipStream_t)stream;
+    if (nf_total == 0) {   // every mesh is empty: infinitely far away
+        LS_HIP_CHECK(hipMemsetAsync(count_out, 0, sizeof(long long), st));
+        if (entries && n_total > 0) hipLaunchKernelGGL(fill_f64_kernel, dim3(cdiv(n_total, 256)), dim3(256), 0, st, dist_out, n_total, (double)INFINITY);
+        LS_LAUNCH_CHECK();
+        return LS_OK;
+    }
+    if (!workspace || workspace_bytes < ls_mesh_distance_batch_workspace_bytes(M, nf_total)) {
+        set_error("%s: workspace too small (need ls_mesh_distance_batch_workspace_bytes(%d, %lld))", op, M, nf_total);
+        return LS_ERR_WORKSPACE;
+    }
+    std::vector<long long> cell_off(M + 1, 0), axis(M + 1, 0);
+    for (int m = 0; m < M; ++m) {
+        axis[m] = dist_axis_cap(face_off[m + 1] - face_off[m]);
+        cell_off[m + 1] = cell_off[m] + axis[m] * axis[m] * axis[m];
+    }
+    const long long cells = cell_off[M];   // <= 8 nf_total + M
+    BatchWs w = batch_bin_layout((char*)workspace, M, nf_total, cells, sizeof(Cells3), nullptr);
+    Cells3* tcell = (Cells3*)w.tcell;
+    const int fb = cdiv(nf_total, 256);
+    const std::vector<long long> offs = pack_offsets(M, vert_off, face_off, pt_off, cell_off.data(), axis.data());
+    LS_HIP_CHECK(hipMemcpyAsync(w.offs, offs.data(), offs.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+    LS_HIP_CHECK(hipMemsetAsync(w.cell_count, 0, (size_t)cells * sizeof(int), st));
+    hipLaunchKernelGGL(bbox_batch_kernel, dim3(M), dim3(1024), 0, st, vertices, faces, w.offs, M, 2, max_dist, w.prm);
+    hipLaunchKernelGGL(dist_prep_batch_kernel, dim3(fb), dim3(256), 0, st, vertices, faces, w.offs, M, nf_total, max_dist, w.prm, w.tri, tcell,
+                       w.cell_count);
+    scan<int, long long, false>(w.cell_count, cells, w.blk, w.start, count_out, st);
+    LS_LAUNCH_CHECK();
+    if (!entries) return LS_OK;
+    LS_HIP_CHECK(hipMemsetAsync(w.cell_count, 0, (size_t)cells * sizeof(int), st));
+    hipLaunchKernelGGL(dist_fill_batch_kernel, dim3(fb), dim3(256), 0, st, w.offs, M, nf_total, w.prm, tcell, w.start, w.cell_count, entries,
+                       cap_entries);
+    if (n_total > 0)
+        hipLaunchKernelGGL(dist_query_batch_kernel, dim3(cdiv(n_total, 256)), dim3(256), 0, st, points, w.offs, M, n_total, max_dist, w.prm, w.tri,
+                           w.start, w.cell_count, entries, count_out, cap_entries, dist_out);
+    LS_LAUNCH_CHECK();
+    return LS_OK;
+}
+
+size_t ls_mesh_sample_batch_workspace_bytes(int M, long long nf_total) {
+    if (M < 0 || nf_total < 0 || nf_total > INT_MAX) return 0;
+    Layout L;
+    L.take<long long>(nullptr, (size_t)OFF_ARRAYS * (M + 1));
+    L.take<double>(nullptr, (size_t)nf_total);
+    L.take<double>(nullptr, (size_t)nf_total);
+    L.take<double>(nullptr, (size_t)(scan_blocks(nf_total) + M));   // sum over meshes of scan_blocks(nf_m)
+    return L.off;
+}
+
+int ls_mesh_sample_batch_f64(int M, const double* vertices, long long nv_total, const long long* vert_off, const int32_t* faces, long long nf_total,
+                             const long long* face_off, long long count_total, const long long* count_off, const unsigned long long* seeds,
+                             double* points_out, int64_t* face_out, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* op = "mesh_sample_batch";
+    int rc = check_meshes(op, M, vertices, nv_total, vert_off, faces, nf_total, face_off);
+    if (rc != LS_OK) return rc;
+    LS_REQUIRE(count_total >= 0, "%s: negative count_total %lld", op, count_total);
+    rc = check_ranges(op, "count_off", M, count_off, count_total, LLONG_MAX);
+    if (rc != LS_OK) return rc;
+    std::vector<long long> blk_off(M + 1, 0);
+    for (int m = 0; m < M; ++m) {
+        const long long nf = face_off[m + 1] - face_off[m], nv = vert_off[m + 1] - vert_off[m], count = count_off[m + 1] - count_off[m];
+        LS_REQUIRE(count == 0 || (nf > 0 && nv > 0), "%s: mesh %d: empty mesh (nv %lld, nf %lld) cannot give %lld samples", op, m, nv, nf, count);
+        LS_REQUIRE(nf <= SCAN_MAX_N, "%s: mesh %d: too many faces (%lld > %lld)", op, m, nf, SCAN_MAX_N);
+        blk_off[m + 1] = blk_off[m] + (count > 0 ? scan_blocks(nf) : 0);   // only the sampled meshes are scanned
+    }
+    if (count_total == 0) return LS_OK;
+    LS_REQUIRE(points_out && seeds, "%s: null points_out / seeds", op);
+    if (!workspace || workspace_bytes < ls_mesh_sample_batch_workspace_bytes(M, nf_total)) {
+        set_error("%s: workspace too small (need ls_mesh_sample_batch_workspace_bytes(%d, %lld))", op, M, nf_total);
+        return LS_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    Layout L;
+    char* ws = (char*)workspace;
+    long long* d_offs = L.take<long long>(ws, (size_t)OFF_ARRAYS * (M + 1));
+    double* area = L.take<double>(ws, (size_t)nf_total);
+    double* cum = L.take<double>(ws, (size_t)nf_total);
+    double* blk = L.take<double>(ws, (size_t)(scan_blocks(nf_total) + M));
+    const std::vector<long long> offs = pack_offsets(M, vert_off, face_off, count_off, blk_off.data(), nullptr);
+    LS_HIP_CHECK(hipMemcpyAsync(d_offs, offs.data(), offs.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+    const int nblk = (int)blk_off[M];   // > 0: some mesh is sampled, and it has faces
+    hipLaunchKernelGGL(area_batch_kernel, dim3(cdiv(nf_total, 256)), dim3(256), 0, st, vertices, faces, d_offs, M, nf_total, area);
+    hipLaunchKernelGGL(scan_reduce_batch_kernel, dim3(nblk), dim3(SCAN_T), 0, st, area, d_offs, M, blk);
+    hipLaunchKernelGGL(scan_top_batch_kernel, dim3(M), dim3(1024), 0, st, blk, d_offs, M);
+    hipLaunchKernelGGL(scan_apply_batch_kernel, dim3(nblk), dim3(SCAN_T), 0, st, area, d_offs, M, blk, cum);
+    hipLaunchKernelGGL(sample_batch_kernel, dim3(cdiv(count_total, 256)), dim3(256), 0, st, vertices, faces, d_offs, M, count_total, cum, seeds,
+                       points_out, face_out);
     LS_LAUNCH_CHECK();
     return LS_OK;
 }

@@ -116,6 +116,82 @@ def compute_volumetric_iou(mesh1, mesh2, voxel_size=1. / 16):
     return float(inside.mean()) if len(inside) else float("nan")
 
 
+# ------------------------------------------------------------------------------------------------ the same metrics on many meshes per call
+# Element i of every *_batch function equals the per-mesh function on pair i, bit for bit: one ragged device call per metric (csrc/meshmetrics.hip,
+# ls_mesh_*_batch_f64) and one host read per batch instead of one per mesh.
+def _device_meshes(meshes, device):
+    """_device_mesh for a list of meshes: the int64 faces are range-checked per mesh (one host read for the batch) before narrowing."""
+    out = []
+    for i, mesh in enumerate(meshes):
+        V = _points(mesh.vertices, device)
+        f = mesh.faces
+        F = f.detach().to(device=device, dtype=torch.int64) if torch.is_tensor(f) else torch.from_numpy(np.asarray(f, dtype=np.int64)).to(device)
+        if V.shape[0] >= 2 ** 31:
+            raise ValueError(f"mesh {i} has {V.shape[0]} vertices: the mesh operators index vertices with int32 (nv < 2^31)")
+        out.append((V, F.reshape(-1, 3)))
+    live = [i for i, (_, F) in enumerate(out) if F.numel()]
+    if live:
+        lim = torch.stack([torch.stack([out[i][1].min(), out[i][1].max()]) for i in live]).cpu().tolist()
+        for i, (lo, hi) in zip(live, lim):
+            if lo < 0 or hi >= out[i][0].shape[0]:
+                raise ValueError(f"mesh {i}: faces index vertices outside [0, {out[i][0].shape[0]})")
+    return [(V, F.to(torch.int32).contiguous()) for V, F in out]
+
+
+def _host_split(parts):
+    """per-mesh device results -> per-mesh numpy arrays, one device-to-host copy"""
+    if not parts:
+        return []
+    flat = torch.cat(parts).cpu().numpy()
+    return np.split(flat, np.cumsum([p.shape[0] for p in parts])[:-1])
+
+
+def check_mesh_contains_batch(meshes, points_list, hash_resolution=512):
+    """[check_mesh_contains(m, p, hash_resolution) for m, p in zip(meshes, points_list)] in one device call."""
+    dev = _device()
+    P = [_points(p, dev) for p in points_list]
+    return _host_split(ops.mesh_contains_batch(_device_meshes(meshes, dev), P, hash_resolution))
+
+
+def mesh_distance_batch(meshes, points_list, max_dist):
+    """[mesh_distance(m, p, max_dist) for m, p in zip(meshes, points_list)] in one device call."""
+    dev = _device()
+    P = [_points(p, dev) for p in points_list]
+    return _host_split(ops.mesh_distance_batch(_device_meshes(meshes, dev), P, max_dist))
+
+
+def compute_chamfer_distance_batch(gt_points_list, gen_meshes, offset, scale, num_mesh_samples=30000, seeds=None):
+    """[compute_chamfer_distance(g, m, offset, scale, num_mesh_samples, seed) for g, m, seed in zip(gt_points_list, gen_meshes, seeds)]:
+    the surface samples of every mesh in one device call, the nearest-neighbour searches one ls_knn_f32 call per mesh (on fresh tensors,
+    as the single function makes them), the means read back in one copy.  seeds=None: seed 0 for every mesh.  An empty mesh raises, as
+    the single function does."""
+    dev = _device()
+    M = len(gen_meshes)
+    seeds = [0] * M if seeds is None else list(seeds)
+    samples = ops.mesh_sample_batch(_device_meshes(gen_meshes, dev), int(num_mesh_samples), seeds)
+    means = []
+    for gt_points, (pts, _) in zip(gt_points_list, samples):
+        gt = _points(gt_points, dev)
+        gen = pts / scale - offset
+        c = (gt.min(0).values + gt.max(0).values) / 2 if gt.shape[0] else torch.zeros(3, dtype=torch.float64, device=dev)
+        a = (gt - c).float().reshape(1, -1, 3, 1).contiguous()
+        b = (gen - c).float().reshape(1, -1, 3, 1).contiguous()
+        _, d_ab = ops.knn(a, b, 1, return_dist=True)
+        _, d_ba = ops.knn(b, a, 1, return_dist=True)
+        means.append(torch.stack([d_ab.double().mean(), d_ba.double().mean()]))
+    return [tuple(v) for v in torch.stack(means).cpu().tolist()] if means else []
+
+
+def compute_sdf_recall_batch(meshes1, meshes2, thres=0.1):
+    """[compute_sdf_recall(m1, m2, thres) for m1, m2 in zip(meshes1, meshes2)] in one device call."""
+    return [float(np.isfinite(d).mean()) if len(d) else float("nan") for d in mesh_distance_batch(meshes1, [m.vertices for m in meshes2], thres)]
+
+
+def compute_volumetric_iou_batch(meshes1, meshes2, voxel_size=1. / 16):
+    """[compute_volumetric_iou(m1, m2) for m1, m2 in zip(meshes1, meshes2)] in one device call."""
+    return [float(i.mean()) if len(i) else float("nan") for i in check_mesh_contains_batch(meshes1, [m.vertices for m in meshes2])]
+
+
 def get_threshold_percentage(dist, thresholds):
     """evaluate.py:88-98: share of ``dist`` <= t for every t in ``thresholds``."""
     dist = np.asarray(dist)

@@ -210,15 +210,21 @@ def _recon_summary(cd, recall, iou=None):
     return out
 
 
+def _scored(preds):
+    """indices of the non-empty predicted meshes (an empty one is not scored)"""
+    return [i for i, m in enumerate(preds) if m.vertices.shape[0] != 0]
+
+
 @torch.no_grad()
-def eval_reconstruction(scenes, solver, gt_meshes):
+def eval_reconstruction(scenes, solver, gt_meshes, batched=False):
     """eval_flyingshape.py:176-213: every instance of every scene is encoded (one batch per scene), meshed from its code
     (``solver._mesh_from_latent``), moved back into its canonical frame by the inverse of the instance pose, and scored against its
     ground-truth mesh ``gt_meshes[scene][instance]``: cd1 + cd2 (compute_chamfer_distance), SDF recall at 0.05 of the GT vertices
     (compute_sdf_recall), V-IoU (compute_volumetric_iou).  An empty predicted mesh scores recall 0 and V-IoU 0 and has no Chamfer entry.
     ``scenes``: dicts with 'pc' [n,N,3] and 'transform' [n,4,4] (the reference's npz keys) or synth.make_scene_pair's 'ref' / 'ref_T'.
     -> {'chamfer_mean', 'sdf_recall@0.7', 'viou_recall@0.5', 'viou_mean', 'viou_median' (percent, as logged), 'cd', 'sdf_recall', 'viou',
-    'n_objects', 'n_empty'}."""
+    'n_objects', 'n_empty'}.  batched=True: all objects of a scene are meshed together (``solver._mesh_from_latent_batch``) and scored
+    with one call per metric (evaluate's *_batch functions) -- the same numbers."""
     from .evaluate import compute_chamfer_distance, compute_sdf_recall, compute_volumetric_iou
     from .mesh_extractor2 import make_mesh
     dev = next(solver.model.parameters()).device
@@ -227,6 +233,17 @@ def eval_reconstruction(scenes, solver, gt_meshes):
         pc = torch.as_tensor(sc["pc"] if "pc" in sc else sc["ref"]).to(dev).float().transpose(-1, -2).contiguous()
         pose = torch.as_tensor(sc["transform"] if "transform" in sc else sc["ref_T"]).double()
         codes = solver.model.encode(pc)
+        if batched:
+            preds = solver._mesh_from_latent_batch({k: codes[k].detach() for k in ("z_inv", "z_so3", "s", "t")})
+            invs = [inverse(pose[i][None])[0].numpy() for i in range(len(preds))]       # [3,4] each, as the per-object leg
+            preds = [make_mesh(np.asarray(p.vertices, np.float64) @ inv[:, :3].T + inv[:, 3], p.faces) for p, inv in zip(preds, invs)]
+            cd, rec, iou = _score_batch(preds, gts, with_iou=True)
+            n_obj += len(preds)
+            n_empty += len(preds) - len(cd)
+            cd_l += [a + b for a, b in cd]
+            rec_l += rec
+            iou_l += iou
+            continue
         for i in range(pc.shape[0]):
             code = {k: codes[k][i][None].detach() for k in ("z_inv", "z_so3", "s", "t")}
             pred = solver._mesh_from_latent(code)
@@ -247,13 +264,32 @@ def eval_reconstruction(scenes, solver, gt_meshes):
     return out
 
 
-def eval_3rscan_reconstruction(dataset, solver, optim=True):
+def _score_batch(preds, gts, with_iou):
+    """the per-object scores of the reconstruction legs for one scene, one device call per metric: -> ([(cd1, cd2)] of the non-empty
+    meshes, recall per object, V-IoU per object or None); an empty mesh scores recall 0 and V-IoU 0"""
+    from .evaluate import compute_chamfer_distance_batch, compute_sdf_recall_batch, compute_volumetric_iou_batch
+    live = _scored(preds)
+    P, G = [preds[i] for i in live], [gts[i] for i in live]
+    cd = compute_chamfer_distance_batch(G, P, offset=0, scale=1)
+    rec, iou = [0.0] * len(preds), [0.0] * len(preds)
+    for i, r in zip(live, compute_sdf_recall_batch(P, G, 0.05)):
+        rec[i] = r
+    if not with_iou:
+        return cd, rec, None
+    for i, v in zip(live, compute_volumetric_iou_batch(P, G)):
+        iou[i] = v
+    return cd, rec, iou
+
+
+def eval_3rscan_reconstruction(dataset, solver, optim=True, batched=False):
     """eval_3rscan.py:466-502 over a ``rscan.Dataset_3RScan``: every kept instance of every reference scan is encoded from its padded
     cloud (``model.encode_fps``), its code refined against the cloud (``solver._optimize_code``, when ``optim``; a code whose loss never
     improved stays as encoded), meshed (``solver._mesh_from_latent``) and scored against ``<root>/val_set_recon/<ref_id>/objectId_<k>.ply``:
     one-way Chamfer cd1 = compute_chamfer_distance(gt, pred, 0, 1)[0] and SDF recall = compute_sdf_recall(pred, gt, 0.05).  An empty
     predicted mesh scores recall 0 and has no Chamfer entry.  -> {'chamfer_1way_mean', 'sdf_recall@0.7' (percent): the two numbers the
-    reference logs, 'cd', 'sdf_recall' (per object), 'n_objects', 'n_empty'}."""
+    reference logs, 'cd', 'sdf_recall' (per object), 'n_objects', 'n_empty'}.  batched=True: the instances of a scene are encoded in one
+    batch, refined together (``solver._optimize_code_batch``, which agrees with the per-instance refinement to ~1e-5), meshed together
+    (``solver._mesh_from_latent_batch``) and scored with one call per metric."""
     import os.path as osp
     from .evaluate import compute_chamfer_distance, compute_sdf_recall
     from .mesh_extractor2 import make_mesh
@@ -264,6 +300,22 @@ def eval_3rscan_reconstruction(dataset, solver, optim=True):
         ref_id = scene["reference"]
         ref, _ = dataset._get_scene(i_s)
         if ref is None:
+            continue
+        if batched:
+            n = ref["pc"].shape[0]
+            gts = [make_mesh(*load_ply_mesh(osp.join(recon_gt, ref_id, f"objectId_{int(ref['objectId'][i])}.ply"))) for i in range(n)]
+            with torch.no_grad():
+                codes = solver.model.encode_fps(ref["pc"], ref["pc_mask"])
+            if optim:
+                # the final values are written back into `codes` whether or not an instance improved -- as _optimize_code does for the
+                # per-object leg, where `codes` is meshed when the loss never improved
+                solver._optimize_code_batch(codes, [ref["pc"][i].T[ref["pc_mask"][i].reshape(-1).bool()] for i in range(n)])
+            preds = solver._mesh_from_latent_batch(codes)
+            cd, rec, _ = _score_batch(preds, gts, with_iou=False)
+            n_obj += n
+            n_empty += n - len(cd)
+            cd_l += [a for a, _ in cd]
+            rec_l += rec
             continue
         for i in range(ref["pc"].shape[0]):
             oid = int(ref["objectId"][i])

@@ -12,7 +12,7 @@ import torch
 from .. import ops
 from ..lib_math.torch_se3 import Rt_to_SE3, inverse, transform
 from ..mesh_extractor2 import Generator3D as Generator3D_MC
-from ..model_utils import fps, load_ckpt_from_log, mesh_from_latent
+from ..model_utils import fps, load_ckpt_from_log, mesh_from_latent, place_mesh
 from .matcher_new import eq_seq_matcher, nn_matcher, sequential_matcher, sim3_seq_matcher, sinkhorn_matcher
 from .pose_estimation import kabsch_transformation_estimation
 
@@ -245,6 +245,25 @@ class More_Solver:
             raise ValueError("More_Solver: cfg has no 'mesh_extractor' section")
         return mesh_from_latent(self.mesh_extractor, latent_code, self.model.decoder)
 
+    def _mesh_from_latent_batch(self, codes, threads=None, group=16):
+        """_mesh_from_latent for every row of the code dict ``codes`` ([B,...] tensors): mesh i equals
+        ``_mesh_from_latent(slice_code_dict(codes, i))``.  ``group`` instances at a time mesh canonically (t = 0, s = 1) with their MISE
+        rounds in lock-step (Generator3D.generate_from_latent_batch: one lattice-sized MISE buffer per instance of a group, decimation on
+        ``threads`` host threads), then every mesh is scaled and moved as mesh_from_latent does (model_utils.place_mesh)."""
+        if self.mesh_extractor is None:
+            raise ValueError("More_Solver: cfg has no 'mesh_extractor' section")
+        B = codes["z_inv"].shape[0]
+        t_host, s_host = codes["t"].detach().cpu(), codes["s"].detach().cpu()
+        meshes = []
+        for g0 in range(0, B, group):
+            g1 = min(B, g0 + group)
+            canon = {k: codes[k][g0:g1].detach() for k in ("z_so3", "z_inv")}
+            canon["t"] = torch.zeros_like(codes["t"][g0:g1])             # canonical pose, as model_utils.py:296-298
+            canon["s"] = torch.ones_like(codes["s"][g0:g1])
+            part = self.mesh_extractor.generate_from_latent_batch(canon, self.model.decoder, threads=threads)
+            meshes += [place_mesh(m, t_host[i], s_host[i]) for i, m in zip(range(g0, g1), part)]
+        return meshes
+
     def _mesh_from_pc(self, pc):
         """more_solver.py:60-69."""
         pc_down, _ = fps(pc, K=self.cfg["shape_priors"]["n_input_point"])
@@ -358,26 +377,11 @@ def solve_end2end_batch(solver, pairs, mesh=False, optim=False, sharded=False, o
             out["registration"][i] = T[k:k + 1]
             cur = {key: out["_res_codes"][key][j][None] for key in ("z_so3", "z_inv", "s", "t")}
             out["codes"][i] = solver._transform_latent(cur, inverse(T[k:k + 1]))
-        if mesh:
-            import numpy as np
-            group = 16                                     # instances whose MISE rounds advance in lock-step
-            own = [slots[k] for k in mine]
-            for g0 in range(0, len(own), group):
-                part = own[g0:g0 + group]
-                cl = [outs[p]["codes"][i] for p, i, _ in part]
-                canon = {k: torch.cat([c[k] for c in cl], 0) for k in ("z_so3", "z_inv")}
-                canon["t"] = torch.zeros_like(torch.cat([c["t"] for c in cl], 0))   # canonical pose, as model_utils.py:296-298
-                canon["s"] = torch.ones_like(torch.cat([c["s"] for c in cl], 0))
-                meshes = solver.mesh_extractor.generate_from_latent_batch(canon, solver.model.decoder)
-                for (p, i, _), c, msh in zip(part, cl, meshes):
-                    tsfm = np.eye(4) * c["s"].squeeze().item()
-                    tsfm[-1, -1] = 1
-                    tsfm[:3, 3] = c["t"].squeeze().view(-1).detach().cpu().numpy()
-                    if hasattr(msh, "apply_transform"):
-                        msh.apply_transform(tsfm)
-                    else:
-                        msh.vertices = msh.vertices @ tsfm[:3, :3].T + tsfm[:3, 3]
-                    outs[p]["mesh_lst"][i] = msh
+        own = [slots[k] for k in mine]
+        if mesh and own:
+            cl = [outs[p]["codes"][i] for p, i, _ in own]
+            for (p, i, _), msh in zip(own, solver._mesh_from_latent_batch({k: torch.cat([c[k] for c in cl], 0) for k in ("z_so3", "z_inv", "s", "t")})):
+                outs[p]["mesh_lst"][i] = msh
     for out in outs:
         del out["_res_codes"]
     return outs

@@ -8,6 +8,8 @@ face order, float64 coordinates); ``extract_mesh`` is mesh_extractor2.py:161-214
 (all off in the released settings).
 """
 import ctypes
+import os
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -167,9 +169,15 @@ class Generator3D:
             active = [b for b, _ in live]
         return [m.to_dense_device().to(torch.float64) if on_device else m.to_dense() for m in mises]
 
-    def generate_from_latent_batch(self, codes, F):
-        """Meshes of B codes (batched MISE rounds, then marching cubes per instance)."""
-        return [self.extract_mesh(g, None, None) for g in self.eval_grid_batch(codes, F, on_device=True)]
+    def generate_from_latent_batch(self, codes, F, threads=None):
+        """Meshes of B codes: batched MISE rounds, marching cubes per instance, then the decimation of every non-empty mesh on a thread
+        pool (simplify_mesh_arrays_batch; ``threads`` as there).  Mesh i equals extract_mesh of instance i's grid."""
+        arrays = [self._mc_arrays(g) for g in self.eval_grid_batch(codes, F, on_device=True)]
+        if self.simplify_nfaces is not None:             # :205-208, an empty mesh is returned as it is (:196-197)
+            live = [i for i, (v, _) in enumerate(arrays) if v.shape[0] != 0]
+            for i, vf in zip(live, simplify_mesh_arrays_batch([arrays[i] for i in live], self.simplify_nfaces, 5.0, threads=threads)):
+                arrays[i] = vf
+        return [make_mesh(v, t) for v, t in arrays]
 
     def generate_from_latent(self, c, F, **kwargs):
         """mesh_extractor2.py:60-74."""
@@ -178,6 +186,15 @@ class Generator3D:
     def extract_mesh(self, occ_hat, z, c=None, stats_dict=None):
         """mesh_extractor2.py:161-214: pad with -1e6 (watertight), marching cubes at the logit threshold, undo the library's 0.5
         shift and the padding, normalise to the bounding box."""
+        vertices, triangles = self._mc_arrays(occ_hat)
+        if vertices.shape[0] == 0:                       # mesh_extractor2.py:196-197: an empty mesh is returned as it is
+            return make_mesh(vertices, triangles)
+        if self.simplify_nfaces is not None:             # :205-208 -- the released configs set 5000 / 100000
+            vertices, triangles = simplify_mesh_arrays(vertices, triangles, self.simplify_nfaces, 5.0)
+        return make_mesh(vertices, triangles)
+
+    def _mc_arrays(self, occ_hat):
+        """extract_mesh up to the decimation: (vertices float64 [nv,3], faces int64 [nf,3]) numpy, in the normalised frame."""
         if self.with_normals or self.refinement_step > 0:
             # Off in every released configuration (configs/more_3rscan.yaml:19-26, room4cates.yaml:32-39) -- and not runnable in the reference on this call
             # path either: generate_from_latent hands the code DICT on as `c`, estimate_normals does `c.unsqueeze(0)` (mesh_extractor2.py:231: AttributeError
@@ -200,11 +217,7 @@ class Generator3D:
         vertices -= 1
         vertices /= np.array([n_x - 1, n_y - 1, n_z - 1])
         vertices = box_size * (vertices - 0.5)
-        if vertices.shape[0] == 0:                       # mesh_extractor2.py:196-197: an empty mesh is returned as it is
-            return make_mesh(vertices, triangles)
-        if self.simplify_nfaces is not None:             # :205-208 -- the released configs set 5000 / 100000
-            vertices, triangles = simplify_mesh_arrays(vertices, triangles, self.simplify_nfaces, 5.0)
-        return make_mesh(vertices, triangles)
+        return vertices, triangles
 
 
 def marching_cubes(volume, isovalue):
@@ -244,6 +257,29 @@ def simplify_mesh_arrays(vertices, faces, f_target=10000, agressiveness=7.0, ini
     check(load().ls_simplify_mesh_f64_host(P(v.ctypes.data), v.shape[0], P(f.ctypes.data), f.shape[0], int(f_target), float(agressiveness),
                                            int(initial_border), P(vo.ctypes.data), P(fo.ctypes.data), P(counts.ctypes.data)), "ls_simplify_mesh_f64_host")
     return vo[: counts[0]].copy(), fo[: counts[1]].copy()
+
+
+def default_threads():
+    """Host threads of simplify_mesh_arrays_batch: OMP_NUM_THREADS when set, else min(16, the CPUs this process may run on)."""
+    env = os.environ.get("OMP_NUM_THREADS", "").strip()
+    if env:
+        return max(1, int(env))
+    return min(16, len(os.sched_getaffinity(0)))
+
+
+def simplify_mesh_arrays_batch(meshes, f_target, agressiveness=7.0, threads=None):
+    """[simplify_mesh_arrays(v, f, f_target, agressiveness) for v, f in meshes] on a pool of ``threads`` host threads (None:
+    default_threads()).  The meshes are independent and the decimation keeps no shared state (ctypes releases the GIL during the call),
+    so the result does not depend on the thread count.  meshes: (vertices, faces) pairs or objects with .vertices / .faces."""
+    pairs = [(m.vertices, m.faces) if hasattr(m, "vertices") else tuple(m) for m in meshes]
+    n = default_threads() if threads is None else int(threads)
+    if n < 1:
+        raise ValueError(f"simplify_mesh_arrays_batch: threads must be >= 1, got {n}")
+    load()   # resolve the library once, before the workers use it
+    if n == 1 or len(pairs) <= 1:
+        return [simplify_mesh_arrays(v, f, f_target, agressiveness) for v, f in pairs]
+    with ThreadPoolExecutor(max_workers=min(n, len(pairs))) as ex:
+        return list(ex.map(lambda vf: simplify_mesh_arrays(vf[0], vf[1], f_target, agressiveness), pairs))
 
 
 def simplify_mesh(mesh, f_target=10000, agressiveness=7.0):

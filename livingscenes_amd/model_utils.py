@@ -247,6 +247,13 @@ def mesh_from_latent(extractor, latent_code, decoder):
         mesh = extractor.generate_from_latent(latent_code, decoder)
     finally:
         latent_code["t"], latent_code["s"] = centroid, scale
+    return place_mesh(mesh, centroid, scale)
+
+
+def place_mesh(mesh, centroid, scale):
+    """model_utils.py:299-305: scale the canonical mesh by ``scale`` and move it to ``centroid`` (one instance's code entries, any shape
+    that squeezes to a scalar / 3 values), in place -> mesh."""
+    import numpy as np
     tsfm = np.eye(4) * scale.squeeze().item()
     tsfm[-1, -1] = 1
     tsfm[:3, 3] = centroid.squeeze().view(-1).detach().cpu().numpy()

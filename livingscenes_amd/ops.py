@@ -3,6 +3,7 @@ torch only provides device memory and the current stream.  No CPU fallback anywh
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -569,3 +570,91 @@ def mesh_sample(V, F, count, seed=0):
     call(dev, "ls_mesh_sample_f64", ptr(V), V.shape[0], ptr(F), F.shape[0], int(count), ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)),
          ptr(pts), ptr(face), ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev))
     return pts, face
+
+
+# ---- ragged batches of meshes (ls_mesh_*_batch_f64): one call for M meshes, every mesh's result bit-identical to the single form
+def _offsets(sizes):
+    """int64 host offsets [M+1] of consecutive ranges of the given sizes"""
+    off = np.zeros(len(sizes) + 1, dtype=np.int64)
+    np.cumsum(np.asarray(sizes, dtype=np.int64), out=off[1:])
+    return off
+
+
+def _pack_meshes(meshes):
+    """meshes: list of (V [nv,3] float64, F [nf,3] int32) HIP tensors, indices local to each mesh -> (V, vert_off, F, face_off) packed back
+    to back, with no host read.  As for the single forms, the caller range-checks the faces (evaluate._device_meshes); an index outside
+    its own mesh gives what the single op gives on that mesh."""
+    Vs, Fs = zip(*[_mesh_dev(V, F) for V, F in meshes]) if meshes else ((), ())
+    for i, V in enumerate(Vs):
+        if V.shape[0] >= 2 ** 31:
+            raise ValueError(f"mesh {i} has {V.shape[0]} vertices: the mesh operators index vertices with int32 (nv < 2^31)")
+    dev = Vs[0].device if Vs else torch.device("cuda", torch.cuda.current_device())
+    V = torch.cat(Vs, 0) if Vs else torch.zeros(0, 3, dtype=torch.float64, device=dev)
+    F = torch.cat(Fs, 0) if Fs else torch.zeros(0, 3, dtype=torch.int32, device=dev)
+    return V, _offsets([v.shape[0] for v in Vs]), F, _offsets([f.shape[0] for f in Fs])
+
+
+def _pack_points(points_list, M, dev):
+    if len(points_list) != M:
+        raise ValueError(f"{len(points_list)} point sets for {M} meshes")
+    P = [p.to(device=dev, dtype=torch.float64).reshape(-1, 3) for p in points_list]
+    return (torch.cat(P, 0) if P else torch.zeros(0, 3, dtype=torch.float64, device=dev)).contiguous(), _offsets([p.shape[0] for p in P])
+
+
+def _hptr(a):
+    return ctypes.c_void_p(a.ctypes.data)
+
+
+def _binned_batch(name, ws_bytes, meshes, points_list, extra, dtype):
+    """ragged form of _binned: one sizing call (one host read) for the whole batch -> list of per-mesh outputs (views of one tensor)"""
+    if not meshes:
+        return []
+    V, vo, F, fo = _pack_meshes(meshes)
+    dev = V.device
+    P, po = _pack_points(points_list, len(meshes), dev)
+    out = torch.empty(P.shape[0], dtype=dtype, device=dev)
+    counts = torch.empty(1, dtype=torch.int64, device=dev)
+    ws = _scratch(ws_bytes(len(meshes), F.shape[0]), dev)
+    nbytes = 0 if ws is None else ws.numel()
+    head = (len(meshes), ptr(V), V.shape[0], _hptr(vo), ptr(F), F.shape[0], _hptr(fo), ptr(P), P.shape[0], _hptr(po)) + tuple(extra)
+    call(dev, name, *head, ptr(out), None, 0, ptr(counts), ptr(ws), nbytes, stream_ptr(dev))
+    entries = torch.empty(max(int(counts.item()), 1), dtype=torch.int32, device=dev)
+    call(dev, name, *head, ptr(out), ptr(entries), entries.numel(), ptr(counts), ptr(ws), nbytes, stream_ptr(dev))
+    return list(torch.split(out, np.diff(po).tolist()))
+
+
+def mesh_contains_batch(meshes, points_list, hash_resolution=512):
+    """mesh_contains on M meshes in one call: meshes = list of (V [nv,3] float64, F [nf,3] int32), points_list = M point sets [n,3]
+    -> list of M bool tensors, element i bit-identical to mesh_contains(*meshes[i], points_list[i], hash_resolution)."""
+    R = int(hash_resolution)
+    return _binned_batch("ls_mesh_contains_batch_f64", lambda M, nf: load().ls_mesh_contains_batch_workspace_bytes(M, nf, R), meshes, points_list,
+                         [R], torch.bool)
+
+
+def mesh_distance_batch(meshes, points_list, max_dist):
+    """mesh_distance on M meshes in one call (one max_dist) -> list of M float64 tensors, each bit-identical to the single form."""
+    return _binned_batch("ls_mesh_distance_batch_f64", lambda M, nf: load().ls_mesh_distance_batch_workspace_bytes(M, nf), meshes, points_list,
+                         [float(max_dist)], torch.float64)
+
+
+def mesh_sample_batch(meshes, counts, seeds=None):
+    """mesh_sample on M meshes in one call: counts = int or M ints (0 allowed), seeds = M ints (None: 0 for every mesh) -> list of M
+    (points [count,3] float64, face index [count] int64 local to the mesh), each bit-identical to mesh_sample(*meshes[i], counts[i], seeds[i])."""
+    M = len(meshes)
+    counts = [int(counts)] * M if isinstance(counts, (int, np.integer)) else [int(c) for c in counts]
+    seeds = [0] * M if seeds is None else [int(s) & (2 ** 64 - 1) for s in seeds]
+    if len(counts) != M or len(seeds) != M:
+        raise ValueError(f"{len(counts)} counts / {len(seeds)} seeds for {M} meshes")
+    if M == 0:
+        return []
+    V, vo, F, fo = _pack_meshes(meshes)
+    dev = V.device
+    co = _offsets(counts)
+    n = int(co[-1])
+    pts = torch.empty(n, 3, dtype=torch.float64, device=dev)
+    face = torch.empty(n, dtype=torch.int64, device=dev)
+    sd = torch.tensor(np.asarray(seeds, dtype=np.uint64).view(np.int64), device=dev)
+    ws = _scratch(load().ls_mesh_sample_batch_workspace_bytes(M, F.shape[0]), dev)
+    call(dev, "ls_mesh_sample_batch_f64", M, ptr(V), V.shape[0], _hptr(vo), ptr(F), F.shape[0], _hptr(fo), n, _hptr(co), ptr(sd), ptr(pts),
+         ptr(face), ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev))
+    return list(zip(torch.split(pts, counts), torch.split(face, counts)))
