@@ -13,6 +13,7 @@
 //   emit faces (own vertices by rank, inherited ones from the owning neighbour's base + rank).
 // Coordinates carry the library's +0.5 offset (marchingcubes.h:41: lower + dx*i + dx/2), which extract_mesh undoes.
 #include "ls_common.h"
+#include "ls_scan.h"
 #include "mc_tables.h"
 
 namespace ls {
@@ -84,21 +85,8 @@ __global__ __launch_bounds__(256) void mc_count_kernel(const double* __restrict_
 }
 // pass 2: exclusive scan of the workgroup sums (one workgroup); totals -> counts_out[0] = vertices, [1] = faces
 __global__ __launch_bounds__(1024) void mc_scan_kernel(u64* blk, int nblk, long long* counts_out) {
-    __shared__ u64 part[1024];
-    const int t = threadIdx.x, per = (nblk + 1023) / 1024;
-    u64 s = 0;
-    for (int u = 0; u < per; ++u) { const int i = t * per + u; if (i < nblk) s += blk[i]; }
-    part[t] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const u64 v = t >= o ? part[t - o] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    u64 run = t ? part[t - 1] : 0;
-    for (int u = 0; u < per; ++u) { const int i = t * per + u; if (i < nblk) { const u64 c = blk[i]; blk[i] = run; run += c; } }
-    if (t == 1023) { counts_out[0] = (long long)(part[1023] >> 32); counts_out[1] = (long long)(part[1023] & 0xFFFFFFFFull) / 3; }
+    const u64 total = scan_top_block<u64>(blk, nblk);
+    if (threadIdx.x == 1023) { counts_out[0] = (long long)(total >> 32); counts_out[1] = (long long)(total & 0xFFFFFFFFull) / 3; }
 }
 // pass 3: per-cube bases (vertex base, face-index base) + the vertices
 __global__ __launch_bounds__(256) void mc_vertex_kernel(const double* __restrict__ vol, McDims d, double iso,

@@ -11,18 +11,21 @@
 //                          folded barycentric pair; the uniforms come from a counter-based hash (splitmix64) of (seed, 3 i + k).
 // The binned ops follow ls_marching_cubes_f64's convention for data-dependent sizes: a call with entries == NULL writes the number of
 // bin entries to the device integer count_out and stops; the caller allocates that many and repeats the call.
-// ls_mesh_*_batch_f64 run the same device functions on M meshes stored back to back (host int64 offsets, checked on the host and copied to the
-// workspace): per-face / per-point kernels find their mesh by binary search of the offsets, the bounding boxes and the sampler's top-level scans
-// run one workgroup per mesh, so the number of launches does not depend on M.  Per mesh the result is bit-identical to the single op: contains
-// builds each mesh's own R^2 hash over its own box; distance gives each mesh a grid of at most a^3 cells, a^3 <= 8 nf (the minimum over a
-// superset of a point's candidate triangles is the same value, and its cell still lists every triangle closer than max_dist); the sampler
-// scans each mesh in its own blocks of SCAN_PER_BLOCK faces with its own top-level tree, as scan<double, double, true> does on that mesh.
+// ls_mesh_*_batch_f64 run the same kernels on M meshes stored back to back (host int64 offsets, checked on the host and copied to the
+// workspace).  Every kernel and every launch sequence is written once, for a mesh locator: with OneMesh a thread's mesh is the call's
+// arguments, with RaggedMeshes per-face / per-point kernels find their mesh by binary search of the offsets.  The bounding boxes and the
+// sampler's top-level scans run one workgroup per mesh, so the number of launches does not depend on M.  Per mesh the result is bit-identical
+// to the single op: contains builds each mesh's own R^2 hash over its own box; distance gives each mesh of a batch a grid of at most a^3
+// cells, a^3 <= 8 nf, where the single op takes up to 128^3 (the minimum over a superset of a point's candidate triangles is the same value,
+// and its cell still lists every triangle closer than max_dist); the sampler scans each mesh in its own blocks of SCAN_PER_BLOCK faces with
+// its own top-level tree.
 #include <algorithm>
 #include <climits>
 #include <cmath>
 #include <vector>
 
 #include "ls_common.h"
+#include "ls_scan.h"
 
 // bit-identity with numpy's float64 arithmetic: no contraction of a * b + c into an fma anywhere in this file
 #pragma clang fp contract(off)
@@ -87,37 +90,11 @@ __global__ __launch_bounds__(SCAN_T) void scan_reduce_kernel(const In* __restric
     scan_reduce_block<In, T>(x, n, blockIdx.x, blk + blockIdx.x);
 }
 
-// exclusive scan of the nblk block sums in place; total_out (nullable) = sum of everything
-template <typename T>
-__device__ void scan_top_block(T* __restrict__ blk, int nblk, long long* __restrict__ total_out) {   // 1024 threads
-    __shared__ T lds[1024];
-    const int tid = threadIdx.x;
-    const int per = (nblk + 1023) / 1024;
-    const int b0 = tid * per;
-    T s = T(0);
-    for (int k = 0; k < per; ++k)
-        if (b0 + k < nblk) s += blk[b0 + k];
-    lds[tid] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const T a = tid >= o ? lds[tid - o] : T(0);
-        __syncthreads();
-        lds[tid] += a;
-        __syncthreads();
-    }
-    T run = tid > 0 ? lds[tid - 1] : T(0);
-    for (int k = 0; k < per; ++k)
-        if (b0 + k < nblk) {
-            const T v = blk[b0 + k];
-            blk[b0 + k] = run;
-            run += v;
-        }
-    if (tid == 1023 && total_out) *total_out = (long long)lds[1023];
-}
-
+// exclusive scan of the nblk block sums in place (ls_scan.h); total_out = sum of everything
 template <typename T>
 __global__ __launch_bounds__(1024) void scan_top_kernel(T* __restrict__ blk, int nblk, long long* __restrict__ total_out) {
-    scan_top_block<T>(blk, nblk, total_out);
+    const T total = scan_top_block<T>(blk, nblk);
+    if (threadIdx.x == 1023) *total_out = (long long)total;
 }
 
 // out[i] = prefix of x over block b: exclusive (INCL = false) or inclusive, blk_b (the scanned sum of the blocks before b) added
@@ -153,6 +130,88 @@ static void scan(const In* x, long long n, T* blk, T* out, long long* total_out,
     hipLaunchKernelGGL((scan_top_kernel<T>), dim3(1), dim3(1024), 0, st, blk, nblk, total_out);
     hipLaunchKernelGGL((scan_apply_kernel<In, T, INCL>), dim3(nblk), dim3(SCAN_T), 0, st, x, n, blk, out);
 }
+
+// ------------------------------------------------------------------------------------------------ which mesh: one, or one of a ragged batch
+// Mesh m of a batch owns V[vert_off[m] .. vert_off[m+1]), F[face_off[m] .. face_off[m+1]) (indices local to the mesh) and the points /
+// samples [pt_off[m] .. pt_off[m+1]).  The device copy of the offsets (offs) is OFF_ARRAYS arrays of M + 1 int64 back to back; OFF_AUX is
+// the mesh's first distance-grid cell (distance) or first scan block (sampler), OFF_AXIS the cells per axis of its distance grid at most.
+enum { OFF_V = 0, OFF_F, OFF_P, OFF_AUX, OFF_AXIS, OFF_ARRAYS };
+
+// the mesh m with off[m] <= i < off[m + 1] (i < off[M]; meshes with an empty range are never the owner)
+__device__ __forceinline__ int owner(const long long* __restrict__ off, int M, long long i) {
+    int lo = 0, hi = M - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= i) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+__host__ __device__ inline unsigned long long splitmix_mix(unsigned long long z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+// the sampler's key for a seed
+__host__ __device__ inline unsigned long long sample_key(unsigned long long seed) { return splitmix_mix(seed + 0x9E3779B97F4A7C15ull); }
+
+struct MeshRef {
+    const double* V;
+    int nv;
+    const int32_t* F;
+    int nf;
+    long long f0;   // global index of the mesh's first face
+};
+
+// Every kernel below takes a locator by value and asks it which mesh a face, point, sample or scan block belongs to and where that mesh's
+// data starts.  The locator of the single ops holds plain values: no offsets on the device, nothing to upload.
+struct OneMesh {
+    const double* V;
+    int nv;
+    const int32_t* F;
+    int nf;
+    long long n;              // points or samples
+    unsigned long long skey;  // sampler: sample_key(seed)
+    __device__ long long faces() const { return nf; }
+    __device__ long long points() const { return n; }
+    __device__ int face_owner(long long) const { return 0; }
+    __device__ int point_owner(long long) const { return 0; }
+    __device__ int block_owner(long long) const { return 0; }
+    __device__ MeshRef mesh(int) const { return {V, nv, F, nf, 0}; }
+    __device__ long long aux0(int) const { return 0; }      // first distance-grid cell / first scan block of the mesh
+    __device__ int scan_blocks(int) const { return (nf + SCAN_PER_BLOCK - 1) / SCAN_PER_BLOCK; }
+    __device__ long long point0(int) const { return 0; }    // first point / sample of the mesh
+    __device__ bool empty(int) const { return false; }      // no faces: the host returned earlier
+    __device__ int axis_cap(int) const { return DIST_GRID_AXIS; }
+    __device__ unsigned long long key(int) const { return skey; }
+};
+
+struct RaggedMeshes {
+    const double* V;
+    const int32_t* F;
+    const long long* offs;    // device copy of the offsets
+    int M;
+    long long nf_total, n_total;
+    const unsigned long long* seeds;   // sampler: device [M]
+    __device__ const long long* off(int k) const { return offs + (size_t)k * (M + 1); }
+    __device__ long long faces() const { return nf_total; }
+    __device__ long long points() const { return n_total; }
+    __device__ int face_owner(long long g) const { return owner(off(OFF_F), M, g); }
+    __device__ int point_owner(long long i) const { return owner(off(OFF_P), M, i); }
+    __device__ int block_owner(long long b) const { return owner(off(OFF_AUX), M, b); }
+    __device__ MeshRef mesh(int m) const {
+        const long long* vo = off(OFF_V);
+        const long long* fo = off(OFF_F);
+        return {V + vo[m] * 3, (int)(vo[m + 1] - vo[m]), F + fo[m] * 3, (int)(fo[m + 1] - fo[m]), fo[m]};
+    }
+    __device__ long long aux0(int m) const { return off(OFF_AUX)[m]; }
+    __device__ int scan_blocks(int m) const { return (int)(off(OFF_AUX)[m + 1] - off(OFF_AUX)[m]); }
+    __device__ long long point0(int m) const { return off(OFF_P)[m]; }
+    __device__ bool empty(int m) const { return off(OFF_F)[m + 1] == off(OFF_F)[m]; }
+    __device__ int axis_cap(int m) const { return (int)off(OFF_AXIS)[m]; }
+    __device__ unsigned long long key(int m) const { return sample_key(seeds[m]); }
+};
 
 // ------------------------------------------------------------------------------------------------ mesh set-up
 // corner c of face f; false (and nothing read) when the face refers to a vertex that does not exist
@@ -222,9 +281,12 @@ __device__ void bbox_block(const double* __restrict__ V, int nv, const int32_t* 
     prm->valid = sbad[0] & 1 ? -1 : valid;
 }
 
-__global__ __launch_bounds__(1024) void bbox_kernel(const double* __restrict__ V, int nv, const int32_t* __restrict__ F, int nf, int R,
-                                                    double max_dist, Params* __restrict__ prm) {
-    bbox_block(V, nv, F, nf, R, max_dist, DIST_GRID_AXIS, prm);
+// one workgroup per mesh: prm[m] (max_dist > 0: with its distance grid)
+template <class Meshes>
+__global__ __launch_bounds__(1024) void bbox_kernel(Meshes L, int R, double max_dist, Params* __restrict__ prm) {
+    const int m = blockIdx.x;
+    const MeshRef r = L.mesh(m);
+    bbox_block(r.V, r.nv, r.F, r.nf, R, max_dist, L.axis_cap(m), prm + m);
 }
 
 // ------------------------------------------------------------------------------------------------ point in mesh (inside_mesh.py + triangle_hash.pyx)
@@ -265,13 +327,17 @@ __device__ __forceinline__ void contains_prep_face(const double* __restrict__ V,
         for (int y = cl.y0; y <= cl.y1; ++y) atomicAdd(&cell_count[(size_t)x * R + y], 1);
 }
 
-__global__ __launch_bounds__(256) void contains_prep_kernel(const double* __restrict__ V, int nv, const int32_t* __restrict__ F, int nf, int R,
-                                                            const Params* __restrict__ prm, double* __restrict__ tri, Cells2* __restrict__ tcell,
-                                                            int* __restrict__ cell_count) {
-    const int f = blockIdx.x * 256 + threadIdx.x;
-    if (f >= nf || prm->valid != 1) return;
-    const Params p = *prm;
-    contains_prep_face(V, nv, F, f, R, p, tri + (size_t)f * 9, tcell + f, cell_count);
+// mesh m's hash is cells [m R^2, (m + 1) R^2); rows of tri / tcell and the bin entries are global face indices
+template <class Meshes>
+__global__ __launch_bounds__(256) void contains_prep_kernel(Meshes L, int R, const Params* __restrict__ prm, double* __restrict__ tri,
+                                                            Cells2* __restrict__ tcell, int* __restrict__ cell_count) {
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= L.faces()) return;
+    const int m = L.face_owner(g);
+    if (prm[m].valid != 1) return;
+    const Params p = prm[m];
+    const MeshRef r = L.mesh(m);
+    contains_prep_face(r.V, r.nv, r.F, (int)(g - r.f0), R, p, tri + (size_t)g * 9, tcell + g, cell_count + (size_t)m * R * R);
 }
 
 // entries of cell c: entries[start[c] .. start[c] + count[c]); cursor (zeroed) counts the slots taken.  Nothing is written at or past cap.
@@ -285,12 +351,16 @@ __device__ __forceinline__ void contains_fill_face(const Cells2 cl, int R, int32
         }
 }
 
-__global__ __launch_bounds__(256) void contains_fill_kernel(int nf, int R, const Params* __restrict__ prm, const Cells2* __restrict__ tcell,
+template <class Meshes>
+__global__ __launch_bounds__(256) void contains_fill_kernel(Meshes L, int R, const Params* __restrict__ prm, const Cells2* __restrict__ tcell,
                                                             const long long* __restrict__ start, int* __restrict__ cursor,
                                                             int32_t* __restrict__ entries, long long cap) {
-    const int f = blockIdx.x * 256 + threadIdx.x;
-    if (f >= nf || prm->valid != 1) return;
-    contains_fill_face(tcell[f], R, f, start, cursor, entries, cap);
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= L.faces()) return;
+    const int m = L.face_owner(g);
+    if (prm[m].valid != 1) return;
+    const size_t base = (size_t)m * R * R;
+    contains_fill_face(tcell[g], R, (int32_t)g, start + base, cursor + base, entries, cap);
 }
 
 // one point (q [3]) against the triangles of its hash cell: parity of the strict 2-D hits above and below it (inside_mesh.py:39-154).
@@ -342,14 +412,17 @@ __device__ bool contains_point(const double* __restrict__ q, int R, const Params
     return inside;
 }
 
-__global__ __launch_bounds__(256) void contains_query_kernel(const double* __restrict__ P, long long n, int R, const Params* __restrict__ prm,
+template <class Meshes>
+__global__ __launch_bounds__(256) void contains_query_kernel(Meshes L, const double* __restrict__ P, int R, const Params* __restrict__ prm,
                                                              const double* __restrict__ tri, const long long* __restrict__ start,
                                                              const int* __restrict__ count, const int32_t* __restrict__ entries,
                                                              const long long* __restrict__ total, long long cap, uint8_t* __restrict__ out) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const Params p = *prm;
-    const bool inside = p.valid == 1 && *total <= cap && contains_point(P + i * 3, R, p, tri, start, count, entries);
+    if (i >= L.points()) return;
+    const int m = L.point_owner(i);
+    const Params p = prm[m];
+    const size_t base = (size_t)m * R * R;
+    const bool inside = !L.empty(m) && p.valid == 1 && *total <= cap && contains_point(P + i * 3, R, p, tri, start + base, count + base, entries);
     out[i] = inside ? 1 : 0;
 }
 
@@ -382,13 +455,17 @@ __device__ __forceinline__ void dist_prep_face(const double* __restrict__ V, int
             for (int z = cl.lo[2]; z <= cl.hi[2]; ++z) atomicAdd(&cell_count[((size_t)x * p.g[1] + y) * p.g[2] + z], 1);
 }
 
-__global__ __launch_bounds__(256) void dist_prep_kernel(const double* __restrict__ V, int nv, const int32_t* __restrict__ F, int nf, double max_dist,
-                                                        const Params* __restrict__ prm, double* __restrict__ tri, Cells3* __restrict__ tcell,
-                                                        int* __restrict__ cell_count) {
-    const int f = blockIdx.x * 256 + threadIdx.x;
-    if (f >= nf || prm->valid < 0) return;
-    const Params p = *prm;
-    dist_prep_face(V, nv, F, f, max_dist, p, tri + (size_t)f * 9, tcell + f, cell_count);
+// mesh m's grid is the cells from L.aux0(m)
+template <class Meshes>
+__global__ __launch_bounds__(256) void dist_prep_kernel(Meshes L, double max_dist, const Params* __restrict__ prm, double* __restrict__ tri,
+                                                        Cells3* __restrict__ tcell, int* __restrict__ cell_count) {
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= L.faces()) return;
+    const int m = L.face_owner(g);
+    if (prm[m].valid < 0) return;
+    const Params p = prm[m];
+    const MeshRef r = L.mesh(m);
+    dist_prep_face(r.V, r.nv, r.F, (int)(g - r.f0), max_dist, p, tri + (size_t)g * 9, tcell + g, cell_count + L.aux0(m));
 }
 
 __device__ __forceinline__ void dist_fill_face(const Cells3 cl, int gy, int gz, int32_t id, const long long* __restrict__ start, int* __restrict__ cursor,
@@ -402,12 +479,16 @@ __device__ __forceinline__ void dist_fill_face(const Cells3 cl, int gy, int gz, 
             }
 }
 
-__global__ __launch_bounds__(256) void dist_fill_kernel(int nf, const Params* __restrict__ prm, const Cells3* __restrict__ tcell,
+template <class Meshes>
+__global__ __launch_bounds__(256) void dist_fill_kernel(Meshes L, const Params* __restrict__ prm, const Cells3* __restrict__ tcell,
                                                         const long long* __restrict__ start, int* __restrict__ cursor, int32_t* __restrict__ entries,
                                                         long long cap) {
-    const int f = blockIdx.x * 256 + threadIdx.x;
-    if (f >= nf || prm->valid < 0) return;
-    dist_fill_face(tcell[f], prm->g[1], prm->g[2], f, start, cursor, entries, cap);
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= L.faces()) return;
+    const int m = L.face_owner(g);
+    if (prm[m].valid < 0) return;
+    const long long base = L.aux0(m);
+    dist_fill_face(tcell[g], prm[m].g[1], prm[m].g[2], (int32_t)g, start + base, cursor + base, entries, cap);
 }
 
 __device__ __forceinline__ double dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
@@ -488,14 +569,18 @@ __device__ double dist_point(const double* __restrict__ P3, double max_dist, con
     return d < max_dist ? d : INFINITY;
 }
 
-__global__ __launch_bounds__(256) void dist_query_kernel(const double* __restrict__ P, long long n, double max_dist, const Params* __restrict__ prm,
+template <class Meshes>
+__global__ __launch_bounds__(256) void dist_query_kernel(Meshes L, const double* __restrict__ P, double max_dist, const Params* __restrict__ prm,
                                                          const double* __restrict__ tri, const long long* __restrict__ start,
                                                          const int* __restrict__ count, const int32_t* __restrict__ entries,
                                                          const long long* __restrict__ total, long long cap, double* __restrict__ out) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const Params p = *prm;
-    out[i] = dist_point(P + i * 3, max_dist, p, p.valid >= 0 && *total <= cap, tri, start, count, entries);
+    if (i >= L.points()) return;
+    const int m = L.point_owner(i);
+    if (L.empty(m)) { out[i] = INFINITY; return; }   // an empty mesh is infinitely far away
+    const Params p = prm[m];
+    const long long base = L.aux0(m);
+    out[i] = dist_point(P + i * 3, max_dist, p, p.valid >= 0 && *total <= cap, tri, start + base, count + base, entries);
 }
 
 __global__ __launch_bounds__(256) void fill_f64_kernel(double* __restrict__ out, long long n, double v) {
@@ -504,12 +589,7 @@ __global__ __launch_bounds__(256) void fill_f64_kernel(double* __restrict__ out,
 }
 
 // ------------------------------------------------------------------------------------------------ surface sampling (trimesh.sample.sample_surface)
-__host__ __device__ inline unsigned long long splitmix_mix(unsigned long long z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-// uniform in [0, 1): the top 53 bits of splitmix64's output for counter j of stream `seed`
+// uniform in [0, 1): the top 53 bits of splitmix64's output for counter j of the stream with key sample_key(seed)
 __device__ __forceinline__ double uniform(unsigned long long key, unsigned long long j) {
     return (double)(splitmix_mix(key + (j + 1ull) * 0x9E3779B97F4A7C15ull) >> 11) * 0x1.0p-53;
 }
@@ -524,11 +604,37 @@ __device__ __forceinline__ double face_area(const double* __restrict__ V, int nv
     return sqrt(cx * cx + cy * cy + cz * cz) / 2.0;
 }
 
-__global__ __launch_bounds__(256) void area_kernel(const double* __restrict__ V, int nv, const int32_t* __restrict__ F, int nf,
-                                                   double* __restrict__ area) {
-    const int f = blockIdx.x * 256 + threadIdx.x;
-    if (f >= nf) return;
-    area[f] = face_area(V, nv, F, f);
+template <class Meshes>
+__global__ __launch_bounds__(256) void area_kernel(Meshes L, double* __restrict__ area) {
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= L.faces()) return;
+    const MeshRef r = L.mesh(L.face_owner(g));
+    area[g] = face_area(r.V, r.nv, r.F, (int)(g - r.f0));
+}
+
+// each mesh's inclusive scan of its face areas: its own blocks of SCAN_PER_BLOCK faces (block sums blk[L.aux0(m) ...]), then one top-level
+// workgroup per mesh, then the prefixes -- the three steps of scan() above, per mesh
+template <class Meshes>
+__global__ __launch_bounds__(SCAN_T) void area_scan_reduce_kernel(Meshes L, const double* __restrict__ area, double* __restrict__ blk) {
+    const int m = L.block_owner(blockIdx.x);
+    const MeshRef r = L.mesh(m);
+    scan_reduce_block<double, double>(area + r.f0, r.nf, blockIdx.x - L.aux0(m), blk + blockIdx.x);
+}
+
+template <class Meshes>
+__global__ __launch_bounds__(1024) void area_scan_top_kernel(Meshes L, double* __restrict__ blk) {
+    const int m = blockIdx.x;
+    const int nblk = L.scan_blocks(m);
+    if (nblk == 0) return;   // a mesh nobody samples
+    scan_top_block<double>(blk + L.aux0(m), nblk);
+}
+
+template <class Meshes>
+__global__ __launch_bounds__(SCAN_T) void area_scan_apply_kernel(Meshes L, const double* __restrict__ area, const double* __restrict__ blk,
+                                                                 double* __restrict__ cum) {
+    const int m = L.block_owner(blockIdx.x);
+    const MeshRef r = L.mesh(m);
+    scan_apply_block<double, double, true>(area + r.f0, r.nf, blockIdx.x - L.aux0(m), blk[blockIdx.x], cum + r.f0);
 }
 
 // sample i of a mesh (cum: its inclusive cumulative face areas): point pts3 [3], local face index *face_i (face_i nullable)
@@ -552,179 +658,14 @@ __device__ __forceinline__ void sample_one(const double* __restrict__ V, int nv,
     if (face_i) *face_i = lo;
 }
 
-__global__ __launch_bounds__(256) void sample_kernel(const double* __restrict__ V, int nv, const int32_t* __restrict__ F, int nf,
-                                                     const double* __restrict__ cum, long long count, unsigned long long key,
-                                                     double* __restrict__ pts, int64_t* __restrict__ face_out) {
+template <class Meshes>
+__global__ __launch_bounds__(256) void sample_kernel(Meshes L, const double* __restrict__ cum, double* __restrict__ pts,
+                                                     int64_t* __restrict__ face_out) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    sample_one(V, nv, F, nf, cum, key, i, pts + i * 3, face_out ? face_out + i : nullptr);
-}
-
-// ------------------------------------------------------------------------------------------------ ragged batches of meshes
-// Mesh m of a batch owns V[vert_off[m] .. vert_off[m+1]), F[face_off[m] .. face_off[m+1]) (indices local to the mesh) and the points /
-// samples [pt_off[m] .. pt_off[m+1]).  The device copy of the offsets (offs) is OFF_ARRAYS arrays of M + 1 int64 back to back; OFF_AUX is
-// the mesh's first distance-grid cell (distance) or first scan block (sampler), OFF_AXIS the cells per axis of its distance grid at most.
-enum { OFF_V = 0, OFF_F, OFF_P, OFF_AUX, OFF_AXIS, OFF_ARRAYS };
-
-__device__ __forceinline__ const long long* off_arr(const long long* offs, int M, int k) { return offs + (size_t)k * (M + 1); }
-
-// the mesh m with off[m] <= i < off[m + 1] (i < off[M]; meshes with an empty range are never the owner)
-__device__ __forceinline__ int owner(const long long* __restrict__ off, int M, long long i) {
-    int lo = 0, hi = M - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= i) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
-struct MeshRef {
-    const double* V;
-    int nv;
-    const int32_t* F;
-    int nf;
-    long long f0;   // global index of the mesh's first face
-};
-__device__ __forceinline__ MeshRef mesh_ref(const double* V, const int32_t* F, const long long* offs, int M, int m) {
-    const long long* vo = off_arr(offs, M, OFF_V);
-    const long long* fo = off_arr(offs, M, OFF_F);
-    return {V + vo[m] * 3, (int)(vo[m + 1] - vo[m]), F + fo[m] * 3, (int)(fo[m + 1] - fo[m]), fo[m]};
-}
-
-// one workgroup per mesh: its Params (max_dist > 0: its distance grid, at most offs[OFF_AXIS][m] cells per axis)
-__global__ __launch_bounds__(1024) void bbox_batch_kernel(const double* __restrict__ V, const int32_t* __restrict__ F, const long long* __restrict__ offs,
-                                                          int M, int R, double max_dist, Params* __restrict__ prm) {
-    const int m = blockIdx.x;
-    const MeshRef r = mesh_ref(V, F, offs, M, m);
-    bbox_block(r.V, r.nv, r.F, r.nf, R, max_dist, max_dist > 0 ? (int)off_arr(offs, M, OFF_AXIS)[m] : DIST_GRID_AXIS, prm + m);
-}
-
-// contains: mesh m's hash is cells [m R^2, (m + 1) R^2); bin entries are global face indices (rows of tri)
-__global__ __launch_bounds__(256) void contains_prep_batch_kernel(const double* __restrict__ V, const int32_t* __restrict__ F,
-                                                                  const long long* __restrict__ offs, int M, long long nf_total, int R,
-                                                                  const Params* __restrict__ prm, double* __restrict__ tri, Cells2* __restrict__ tcell,
-                                                                  int* __restrict__ cell_count) {
-    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (g >= nf_total) return;
-    const int m = owner(off_arr(offs, M, OFF_F), M, g);
-    if (prm[m].valid != 1) return;
-    const Params p = prm[m];
-    const MeshRef r = mesh_ref(V, F, offs, M, m);
-    contains_prep_face(r.V, r.nv, r.F, (int)(g - r.f0), R, p, tri + (size_t)g * 9, tcell + g, cell_count + (size_t)m * R * R);
-}
-
-__global__ __launch_bounds__(256) void contains_fill_batch_kernel(const long long* __restrict__ offs, int M, long long nf_total, int R,
-                                                                  const Params* __restrict__ prm, const Cells2* __restrict__ tcell,
-                                                                  const long long* __restrict__ start, int* __restrict__ cursor,
-                                                                  int32_t* __restrict__ entries, long long cap) {
-    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (g >= nf_total) return;
-    const int m = owner(off_arr(offs, M, OFF_F), M, g);
-    if (prm[m].valid != 1) return;
-    const size_t base = (size_t)m * R * R;
-    contains_fill_face(tcell[g], R, (int32_t)g, start + base, cursor + base, entries, cap);
-}
-
-__global__ __launch_bounds__(256) void contains_query_batch_kernel(const double* __restrict__ P, const long long* __restrict__ offs, int M,
-                                                                   long long n_total, int R, const Params* __restrict__ prm,
-                                                                   const double* __restrict__ tri, const long long* __restrict__ start,
-                                                                   const int* __restrict__ count, const int32_t* __restrict__ entries,
-                                                                   const long long* __restrict__ total, long long cap, uint8_t* __restrict__ out) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_total) return;
-    const int m = owner(off_arr(offs, M, OFF_P), M, i);
-    const long long* fo = off_arr(offs, M, OFF_F);
-    const Params p = prm[m];
-    const size_t base = (size_t)m * R * R;
-    const bool inside = fo[m + 1] > fo[m] && p.valid == 1 && *total <= cap && contains_point(P + i * 3, R, p, tri, start + base, count + base, entries);
-    out[i] = inside ? 1 : 0;
-}
-
-// distance: mesh m's grid is cells [offs[OFF_AUX][m], offs[OFF_AUX][m + 1])
-__global__ __launch_bounds__(256) void dist_prep_batch_kernel(const double* __restrict__ V, const int32_t* __restrict__ F, const long long* __restrict__ offs,
-                                                              int M, long long nf_total, double max_dist, const Params* __restrict__ prm,
-                                                              double* __restrict__ tri, Cells3* __restrict__ tcell, int* __restrict__ cell_count) {
-    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (g >= nf_total) return;
-    const int m = owner(off_arr(offs, M, OFF_F), M, g);
-    if (prm[m].valid < 0) return;
-    const Params p = prm[m];
-    const MeshRef r = mesh_ref(V, F, offs, M, m);
-    dist_prep_face(r.V, r.nv, r.F, (int)(g - r.f0), max_dist, p, tri + (size_t)g * 9, tcell + g, cell_count + off_arr(offs, M, OFF_AUX)[m]);
-}
-
-__global__ __launch_bounds__(256) void dist_fill_batch_kernel(const long long* __restrict__ offs, int M, long long nf_total, const Params* __restrict__ prm,
-                                                              const Cells3* __restrict__ tcell, const long long* __restrict__ start,
-                                                              int* __restrict__ cursor, int32_t* __restrict__ entries, long long cap) {
-    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (g >= nf_total) return;
-    const int m = owner(off_arr(offs, M, OFF_F), M, g);
-    if (prm[m].valid < 0) return;
-    const long long base = off_arr(offs, M, OFF_AUX)[m];
-    dist_fill_face(tcell[g], prm[m].g[1], prm[m].g[2], (int32_t)g, start + base, cursor + base, entries, cap);
-}
-
-__global__ __launch_bounds__(256) void dist_query_batch_kernel(const double* __restrict__ P, const long long* __restrict__ offs, int M, long long n_total,
-                                                               double max_dist, const Params* __restrict__ prm, const double* __restrict__ tri,
-                                                               const long long* __restrict__ start, const int* __restrict__ count,
-                                                               const int32_t* __restrict__ entries, const long long* __restrict__ total, long long cap,
-                                                               double* __restrict__ out) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_total) return;
-    const int m = owner(off_arr(offs, M, OFF_P), M, i);
-    const long long* fo = off_arr(offs, M, OFF_F);
-    if (fo[m + 1] == fo[m]) { out[i] = INFINITY; return; }   // an empty mesh is infinitely far away
-    const Params p = prm[m];
-    const long long base = off_arr(offs, M, OFF_AUX)[m];
-    out[i] = dist_point(P + i * 3, max_dist, p, p.valid >= 0 && *total <= cap, tri, start + base, count + base, entries);
-}
-
-// sampler: face areas of every mesh, then each mesh's inclusive scan exactly as scan<double, double, true> on that mesh alone -- its own
-// blocks of SCAN_PER_BLOCK faces (block sums blk[offs[OFF_AUX][m] ...]) and one top-level workgroup per mesh
-__global__ __launch_bounds__(256) void area_batch_kernel(const double* __restrict__ V, const int32_t* __restrict__ F, const long long* __restrict__ offs,
-                                                         int M, long long nf_total, double* __restrict__ area) {
-    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (g >= nf_total) return;
-    const MeshRef r = mesh_ref(V, F, offs, M, owner(off_arr(offs, M, OFF_F), M, g));
-    area[g] = face_area(r.V, r.nv, r.F, (int)(g - r.f0));
-}
-
-__global__ __launch_bounds__(SCAN_T) void scan_reduce_batch_kernel(const double* __restrict__ area, const long long* __restrict__ offs, int M,
-                                                                   double* __restrict__ blk) {
-    const long long* bo = off_arr(offs, M, OFF_AUX);
-    const long long* fo = off_arr(offs, M, OFF_F);
-    const int m = owner(bo, M, blockIdx.x);
-    scan_reduce_block<double, double>(area + fo[m], fo[m + 1] - fo[m], blockIdx.x - bo[m], blk + blockIdx.x);
-}
-
-__global__ __launch_bounds__(1024) void scan_top_batch_kernel(double* __restrict__ blk, const long long* __restrict__ offs, int M) {
-    const long long* bo = off_arr(offs, M, OFF_AUX);
-    const int m = blockIdx.x;
-    const int nblk = (int)(bo[m + 1] - bo[m]);
-    if (nblk == 0) return;
-    scan_top_block<double>(blk + bo[m], nblk, nullptr);
-}
-
-__global__ __launch_bounds__(SCAN_T) void scan_apply_batch_kernel(const double* __restrict__ area, const long long* __restrict__ offs, int M,
-                                                                  const double* __restrict__ blk, double* __restrict__ cum) {
-    const long long* bo = off_arr(offs, M, OFF_AUX);
-    const long long* fo = off_arr(offs, M, OFF_F);
-    const int m = owner(bo, M, blockIdx.x);
-    scan_apply_block<double, double, true>(area + fo[m], fo[m + 1] - fo[m], blockIdx.x - bo[m], blk[blockIdx.x], cum + fo[m]);
-}
-
-__global__ __launch_bounds__(256) void sample_batch_kernel(const double* __restrict__ V, const int32_t* __restrict__ F, const long long* __restrict__ offs,
-                                                           int M, long long count_total, const double* __restrict__ cum,
-                                                           const unsigned long long* __restrict__ seeds, double* __restrict__ pts,
-                                                           int64_t* __restrict__ face_out) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count_total) return;
-    const long long* co = off_arr(offs, M, OFF_P);
-    const int m = owner(co, M, i);
-    const MeshRef r = mesh_ref(V, F, offs, M, m);
-    sample_one(r.V, r.nv, r.F, r.nf, cum + r.f0, splitmix_mix(seeds[m] + 0x9E3779B97F4A7C15ull), i - co[m], pts + i * 3,
-               face_out ? face_out + i : nullptr);
+    if (i >= L.points()) return;
+    const int m = L.point_owner(i);
+    const MeshRef r = L.mesh(m);
+    sample_one(r.V, r.nv, r.F, r.nf, cum + r.f0, L.key(m), i - L.point0(m), pts + i * 3, face_out ? face_out + i : nullptr);
 }
 
 }  // namespace mm
@@ -744,17 +685,20 @@ struct Layout {   // carve a workspace in 256-byte aligned pieces
     }
 };
 struct BinWs {
-    Params* prm;
+    long long* offs;   // a batch: the device copy of the offsets
+    Params* prm;       // [M]
     double* tri;
     void* tcell;
     int* cell_count;
     long long* start;
     long long* blk;
 };
-BinWs bin_layout(char* ws, int nf, long long cells, size_t cell_rec, size_t* bytes) {
+// n_offs: OFF_ARRAYS * (M + 1) for a batch, 0 (no bytes) for one mesh
+BinWs bin_layout(char* ws, size_t n_offs, int M, long long nf, long long cells, size_t cell_rec, size_t* bytes) {
     Layout L;
     BinWs w;
-    w.prm = L.take<Params>(ws, 1);
+    w.offs = L.take<long long>(ws, n_offs);
+    w.prm = L.take<Params>(ws, (size_t)M);
     w.tri = L.take<double>(ws, (size_t)nf * 9);
     w.tcell = L.take<char>(ws, (size_t)nf * cell_rec);
     w.cell_count = L.take<int>(ws, (size_t)cells);
@@ -763,29 +707,78 @@ BinWs bin_layout(char* ws, int nf, long long cells, size_t cell_rec, size_t* byt
     if (bytes) *bytes = L.off;
     return w;
 }
-
-// ---- ragged batches (host side)
-struct BatchWs {
+struct SampleWs {
     long long* offs;
-    Params* prm;
-    double* tri;
-    void* tcell;
-    int* cell_count;
-    long long* start;
-    long long* blk;
+    double* area;
+    double* cum;
+    double* blk;
 };
-BatchWs batch_bin_layout(char* ws, int M, long long nf_total, long long cells, size_t cell_rec, size_t* bytes) {
+SampleWs sample_layout(char* ws, size_t n_offs, long long nf, long long nblk, size_t* bytes) {
     Layout L;
-    BatchWs w;
-    w.offs = L.take<long long>(ws, (size_t)OFF_ARRAYS * (M + 1));
-    w.prm = L.take<Params>(ws, (size_t)M);
-    w.tri = L.take<double>(ws, (size_t)nf_total * 9);
-    w.tcell = L.take<char>(ws, (size_t)nf_total * cell_rec);
-    w.cell_count = L.take<int>(ws, (size_t)cells);
-    w.start = L.take<long long>(ws, (size_t)cells);
-    w.blk = L.take<long long>(ws, (size_t)scan_blocks(cells));
+    SampleWs w;
+    w.offs = L.take<long long>(ws, n_offs);
+    w.area = L.take<double>(ws, (size_t)nf);
+    w.cum = L.take<double>(ws, (size_t)nf);
+    w.blk = L.take<double>(ws, (size_t)nblk);
     if (bytes) *bytes = L.off;
     return w;
+}
+size_t n_offs(int M) { return (size_t)OFF_ARRAYS * (M + 1); }
+
+// ---- the launch sequences, one per metric: M meshes located by L, nf faces and n points (samples) in all, w the carved workspace
+template <class Meshes>
+int contains_launch(const Meshes& L, int M, long long nf, const double* points, long long n, int R, const BinWs& w, uint8_t* inside_out,
+                    int32_t* entries, long long cap_entries, long long* count_out, hipStream_t st) {
+    const long long cells = (long long)M * R * R;
+    Cells2* tcell = (Cells2*)w.tcell;
+    const int fb = cdiv(nf, 256);
+    LS_HIP_CHECK(hipMemsetAsync(w.cell_count, 0, (size_t)cells * sizeof(int), st));
+    hipLaunchKernelGGL(bbox_kernel<Meshes>, dim3(M), dim3(1024), 0, st, L, R, 0.0, w.prm);
+    hipLaunchKernelGGL(contains_prep_kernel<Meshes>, dim3(fb), dim3(256), 0, st, L, R, w.prm, w.tri, tcell, w.cell_count);
+    scan<int, long long, false>(w.cell_count, cells, w.blk, w.start, count_out, st);
+    LS_LAUNCH_CHECK();
+    if (!entries) return LS_OK;   // sizing call: one entry count for all the meshes
+    // the fill takes its slots with a zeroed cursor in cell_count, which ends equal to the counts the query reads
+    LS_HIP_CHECK(hipMemsetAsync(w.cell_count, 0, (size_t)cells * sizeof(int), st));
+    hipLaunchKernelGGL(contains_fill_kernel<Meshes>, dim3(fb), dim3(256), 0, st, L, R, w.prm, tcell, w.start, w.cell_count, entries, cap_entries);
+    if (n > 0)
+        hipLaunchKernelGGL(contains_query_kernel<Meshes>, dim3(cdiv(n, 256)), dim3(256), 0, st, L, points, R, w.prm, w.tri, w.start, w.cell_count,
+                           entries, count_out, cap_entries, inside_out);
+    LS_LAUNCH_CHECK();
+    return LS_OK;
+}
+
+template <class Meshes>
+int distance_launch(const Meshes& L, int M, long long nf, const double* points, long long n, double max_dist, long long cells, const BinWs& w,
+                    double* dist_out, int32_t* entries, long long cap_entries, long long* count_out, hipStream_t st) {
+    Cells3* tcell = (Cells3*)w.tcell;
+    const int fb = cdiv(nf, 256);
+    LS_HIP_CHECK(hipMemsetAsync(w.cell_count, 0, (size_t)cells * sizeof(int), st));
+    hipLaunchKernelGGL(bbox_kernel<Meshes>, dim3(M), dim3(1024), 0, st, L, 2, max_dist, w.prm);
+    hipLaunchKernelGGL(dist_prep_kernel<Meshes>, dim3(fb), dim3(256), 0, st, L, max_dist, w.prm, w.tri, tcell, w.cell_count);
+    scan<int, long long, false>(w.cell_count, cells, w.blk, w.start, count_out, st);
+    LS_LAUNCH_CHECK();
+    if (!entries) return LS_OK;
+    LS_HIP_CHECK(hipMemsetAsync(w.cell_count, 0, (size_t)cells * sizeof(int), st));
+    hipLaunchKernelGGL(dist_fill_kernel<Meshes>, dim3(fb), dim3(256), 0, st, L, w.prm, tcell, w.start, w.cell_count, entries, cap_entries);
+    if (n > 0)
+        hipLaunchKernelGGL(dist_query_kernel<Meshes>, dim3(cdiv(n, 256)), dim3(256), 0, st, L, points, max_dist, w.prm, w.tri, w.start,
+                           w.cell_count, entries, count_out, cap_entries, dist_out);
+    LS_LAUNCH_CHECK();
+    return LS_OK;
+}
+
+// nblk scan blocks in all (> 0: some mesh is sampled, and it has faces)
+template <class Meshes>
+int sample_launch(const Meshes& L, int M, long long nf, int nblk, long long count, const SampleWs& w, double* points_out, int64_t* face_out,
+                  hipStream_t st) {
+    hipLaunchKernelGGL(area_kernel<Meshes>, dim3(cdiv(nf, 256)), dim3(256), 0, st, L, w.area);
+    hipLaunchKernelGGL(area_scan_reduce_kernel<Meshes>, dim3(nblk), dim3(SCAN_T), 0, st, L, w.area, w.blk);
+    hipLaunchKernelGGL(area_scan_top_kernel<Meshes>, dim3(M), dim3(1024), 0, st, L, w.blk);
+    hipLaunchKernelGGL(area_scan_apply_kernel<Meshes>, dim3(nblk), dim3(SCAN_T), 0, st, L, w.area, w.blk, w.cum);
+    hipLaunchKernelGGL(sample_kernel<Meshes>, dim3(cdiv(count, 256)), dim3(256), 0, st, L, w.cum, points_out, face_out);
+    LS_LAUNCH_CHECK();
+    return LS_OK;
 }
 
 // off[0] = 0, never decreasing, at most per_max per mesh, ending at total
@@ -842,7 +835,7 @@ extern "C" {
 size_t ls_mesh_contains_workspace_bytes(int nf, int hash_resolution) {
     if (nf < 0 || hash_resolution < 2 || hash_resolution > MAX_HASH_RES) return 0;
     size_t b;
-    bin_layout(nullptr, nf, (long long)hash_resolution * hash_resolution, sizeof(Cells2), &b);
+    bin_layout(nullptr, 0, 1, nf, (long long)hash_resolution * hash_resolution, sizeof(Cells2), &b);
     return b;
 }
 
@@ -863,34 +856,18 @@ int ls_mesh_contains_f64(const double* vertices, int nv, const int32_t* faces, i
         return LS_OK;
     }
     const int R = hash_resolution;
-    const long long cells = (long long)R * R;
     if (!workspace || workspace_bytes < ls_mesh_contains_workspace_bytes(nf, R)) {
         set_error("mesh_contains: workspace too small (need ls_mesh_contains_workspace_bytes(%d, %d))", nf, R);
         return LS_ERR_WORKSPACE;
     }
-    BinWs w = bin_layout((char*)workspace, nf, cells, sizeof(Cells2), nullptr);
-    Cells2* tcell = (Cells2*)w.tcell;
-    const int fb = (int)cdiv(nf, 256);
-    LS_HIP_CHECK(hipMemsetAsync(w.cell_count, 0, (size_t)cells * sizeof(int), st));
-    hipLaunchKernelGGL(bbox_kernel, dim3(1), dim3(1024), 0, st, vertices, nv, faces, nf, R, 0.0, w.prm);
-    hipLaunchKernelGGL(contains_prep_kernel, dim3(fb), dim3(256), 0, st, vertices, nv, faces, nf, R, w.prm, w.tri, tcell, w.cell_count);
-    scan<int, long long, false>(w.cell_count, cells, w.blk, w.start, count_out, st);
-    LS_LAUNCH_CHECK();
-    if (!entries) return LS_OK;   // sizing call
-    // the fill takes its slots with a zeroed cursor in cell_count, which ends equal to the counts the query reads
-    LS_HIP_CHECK(hipMemsetAsync(w.cell_count, 0, (size_t)cells * sizeof(int), st));
-    hipLaunchKernelGGL(contains_fill_kernel, dim3(fb), dim3(256), 0, st, nf, R, w.prm, tcell, w.start, w.cell_count, entries, cap_entries);
-    if (n > 0)
-        hipLaunchKernelGGL(contains_query_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, points, n, R, w.prm, w.tri, w.start, w.cell_count,
-                           entries, count_out, cap_entries, inside_out);
-    LS_LAUNCH_CHECK();
-    return LS_OK;
+    const BinWs w = bin_layout((char*)workspace, 0, 1, nf, (long long)R * R, sizeof(Cells2), nullptr);
+    return contains_launch(OneMesh{vertices, nv, faces, nf, n, 0}, 1, nf, points, n, R, w, inside_out, entries, cap_entries, count_out, st);
 }
 
 size_t ls_mesh_distance_workspace_bytes(int nf) {
     if (nf < 0) return 0;
     size_t b;
-    bin_layout(nullptr, nf, DIST_CELLS, sizeof(Cells3), &b);
+    bin_layout(nullptr, 0, 1, nf, DIST_CELLS, sizeof(Cells3), &b);
     return b;
 }
 
@@ -914,31 +891,16 @@ int ls_mesh_distance_f64(const double* vertices, int nv, const int32_t* faces, i
         set_error("mesh_distance: workspace too small (need ls_mesh_distance_workspace_bytes(%d))", nf);
         return LS_ERR_WORKSPACE;
     }
-    BinWs w = bin_layout((char*)workspace, nf, DIST_CELLS, sizeof(Cells3), nullptr);
-    Cells3* tcell = (Cells3*)w.tcell;
-    const int fb = (int)cdiv(nf, 256);
-    LS_HIP_CHECK(hipMemsetAsync(w.cell_count, 0, (size_t)DIST_CELLS * sizeof(int), st));
-    hipLaunchKernelGGL(bbox_kernel, dim3(1), dim3(1024), 0, st, vertices, nv, faces, nf, 2, max_dist, w.prm);
-    hipLaunchKernelGGL(dist_prep_kernel, dim3(fb), dim3(256), 0, st, vertices, nv, faces, nf, max_dist, w.prm, w.tri, tcell, w.cell_count);
-    scan<int, long long, false>(w.cell_count, DIST_CELLS, w.blk, w.start, count_out, st);
-    LS_LAUNCH_CHECK();
-    if (!entries) return LS_OK;
-    LS_HIP_CHECK(hipMemsetAsync(w.cell_count, 0, (size_t)DIST_CELLS * sizeof(int), st));
-    hipLaunchKernelGGL(dist_fill_kernel, dim3(fb), dim3(256), 0, st, nf, w.prm, tcell, w.start, w.cell_count, entries, cap_entries);
-    if (n > 0)
-        hipLaunchKernelGGL(dist_query_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, points, n, max_dist, w.prm, w.tri, w.start, w.cell_count,
-                           entries, count_out, cap_entries, dist_out);
-    LS_LAUNCH_CHECK();
-    return LS_OK;
+    const BinWs w = bin_layout((char*)workspace, 0, 1, nf, DIST_CELLS, sizeof(Cells3), nullptr);
+    return distance_launch(OneMesh{vertices, nv, faces, nf, n, 0}, 1, nf, points, n, max_dist, DIST_CELLS, w, dist_out, entries, cap_entries,
+                           count_out, st);
 }
 
 size_t ls_mesh_sample_workspace_bytes(int nf) {
     if (nf < 0) return 0;
-    Layout L;
-    L.take<double>(nullptr, (size_t)nf);
-    L.take<double>(nullptr, (size_t)nf);
-    L.take<double>(nullptr, (size_t)scan_blocks(nf));
-    return L.off;
+    size_t b;
+    sample_layout(nullptr, 0, nf, scan_blocks(nf), &b);
+    return b;
 }
 
 int ls_mesh_sample_f64(const double* vertices, int nv, const int32_t* faces, int nf, long long count, unsigned long long seed,
@@ -951,25 +913,17 @@ int ls_mesh_sample_f64(const double* vertices, int nv, const int32_t* faces, int
         set_error("mesh_sample: workspace too small (need ls_mesh_sample_workspace_bytes(%d))", nf);
         return LS_ERR_WORKSPACE;
     }
-    hipStream_t st = (hipStream_t)stream;
-    Layout L;
-    char* ws = (char*)workspace;
-    double* area = L.take<double>(ws, (size_t)nf);
-    double* cum = L.take<double>(ws, (size_t)nf);
-    double* blk = L.take<double>(ws, (size_t)scan_blocks(nf));
-    hipLaunchKernelGGL(area_kernel, dim3(cdiv(nf, 256)), dim3(256), 0, st, vertices, nv, faces, nf, area);
-    scan<double, double, true>(area, nf, blk, cum, nullptr, st);
-    hipLaunchKernelGGL(sample_kernel, dim3(cdiv(count, 256)), dim3(256), 0, st, vertices, nv, faces, nf, cum, count,
-                       splitmix_mix(seed + 0x9E3779B97F4A7C15ull), points_out, face_out);
-    LS_LAUNCH_CHECK();
-    return LS_OK;
+    const int nblk = (int)scan_blocks(nf);
+    const SampleWs w = sample_layout((char*)workspace, 0, nf, nblk, nullptr);
+    return sample_launch(OneMesh{vertices, nv, faces, nf, count, sample_key(seed)}, 1, nf, nblk, count, w, points_out, face_out,
+                         (hipStream_t)stream);
 }
 
 // ---- ragged batches: every mesh's result is bit-identical to the single-mesh op on that mesh alone
 size_t ls_mesh_contains_batch_workspace_bytes(int M, long long nf_total, int hash_resolution) {
     if (M < 0 || nf_total < 0 || nf_total > INT_MAX || hash_resolution < 2 || hash_resolution > MAX_HASH_RES) return 0;
     size_t b;
-    batch_bin_layout(nullptr, M, nf_total, (long long)M * hash_resolution * hash_resolution, sizeof(Cells2), &b);
+    bin_layout(nullptr, n_offs(M), M, nf_total, (long long)M * hash_resolution * hash_resolution, sizeof(Cells2), &b);
     return b;
 }
 
@@ -999,34 +953,18 @@ int ls_mesh_contains_batch_f64(int M, const double* vertices, long long nv_total
         set_error("%s: workspace too small (need ls_mesh_contains_batch_workspace_bytes(%d, %lld, %d))", op, M, nf_total, R);
         return LS_ERR_WORKSPACE;
     }
-    const long long cells = (long long)M * R * R;
-    BatchWs w = batch_bin_layout((char*)workspace, M, nf_total, cells, sizeof(Cells2), nullptr);
-    Cells2* tcell = (Cells2*)w.tcell;
-    const int fb = cdiv(nf_total, 256);
+    const BinWs w = bin_layout((char*)workspace, n_offs(M), M, nf_total, (long long)M * R * R, sizeof(Cells2), nullptr);
     // pageable host memory: the copy has read the offsets when it returns
     const std::vector<long long> offs = pack_offsets(M, vert_off, face_off, pt_off, nullptr, nullptr);
     LS_HIP_CHECK(hipMemcpyAsync(w.offs, offs.data(), offs.size() * sizeof(long long), hipMemcpyHostToDevice, st));
-    LS_HIP_CHECK(hipMemsetAsync(w.cell_count, 0, (size_t)cells * sizeof(int), st));
-    hipLaunchKernelGGL(bbox_batch_kernel, dim3(M), dim3(1024), 0, st, vertices, faces, w.offs, M, R, 0.0, w.prm);
-    hipLaunchKernelGGL(contains_prep_batch_kernel, dim3(fb), dim3(256), 0, st, vertices, faces, w.offs, M, nf_total, R, w.prm, w.tri, tcell,
-                       w.cell_count);
-    scan<int, long long, false>(w.cell_count, cells, w.blk, w.start, count_out, st);
-    LS_LAUNCH_CHECK();
-    if (!entries) return LS_OK;   // sizing call: one entry count for the whole batch
-    LS_HIP_CHECK(hipMemsetAsync(w.cell_count, 0, (size_t)cells * sizeof(int), st));
-    hipLaunchKernelGGL(contains_fill_batch_kernel, dim3(fb), dim3(256), 0, st, w.offs, M, nf_total, R, w.prm, tcell, w.start, w.cell_count, entries,
-                       cap_entries);
-    if (n_total > 0)
-        hipLaunchKernelGGL(contains_query_batch_kernel, dim3(cdiv(n_total, 256)), dim3(256), 0, st, points, w.offs, M, n_total, R, w.prm, w.tri,
-                           w.start, w.cell_count, entries, count_out, cap_entries, inside_out);
-    LS_LAUNCH_CHECK();
-    return LS_OK;
+    return contains_launch(RaggedMeshes{vertices, faces, w.offs, M, nf_total, n_total, nullptr}, M, nf_total, points, n_total, R, w, inside_out,
+                           entries, cap_entries, count_out, st);
 }
 
 size_t ls_mesh_distance_batch_workspace_bytes(int M, long long nf_total) {
     if (M < 0 || nf_total < 0 || nf_total > INT_MAX) return 0;
     size_t b;
-    batch_bin_layout(nullptr, M, nf_total, 8 * nf_total + M, sizeof(Cells3), &b);
+    bin_layout(nullptr, n_offs(M), M, nf_total, 8 * nf_total + M, sizeof(Cells3), &b);
     return b;
 }
 
@@ -1061,36 +999,18 @@ int ls_mesh_distance_batch_f64(int M, const double* vertices, long long nv_total
         cell_off[m + 1] = cell_off[m] + axis[m] * axis[m] * axis[m];
     }
     const long long cells = cell_off[M];   // <= 8 nf_total + M
-    BatchWs w = batch_bin_layout((char*)workspace, M, nf_total, cells, sizeof(Cells3), nullptr);
-    Cells3* tcell = (Cells3*)w.tcell;
-    const int fb = cdiv(nf_total, 256);
+    const BinWs w = bin_layout((char*)workspace, n_offs(M), M, nf_total, cells, sizeof(Cells3), nullptr);
     const std::vector<long long> offs = pack_offsets(M, vert_off, face_off, pt_off, cell_off.data(), axis.data());
     LS_HIP_CHECK(hipMemcpyAsync(w.offs, offs.data(), offs.size() * sizeof(long long), hipMemcpyHostToDevice, st));
-    LS_HIP_CHECK(hipMemsetAsync(w.cell_count, 0, (size_t)cells * sizeof(int), st));
-    hipLaunchKernelGGL(bbox_batch_kernel, dim3(M), dim3(1024), 0, st, vertices, faces, w.offs, M, 2, max_dist, w.prm);
-    hipLaunchKernelGGL(dist_prep_batch_kernel, dim3(fb), dim3(256), 0, st, vertices, faces, w.offs, M, nf_total, max_dist, w.prm, w.tri, tcell,
-                       w.cell_count);
-    scan<int, long long, false>(w.cell_count, cells, w.blk, w.start, count_out, st);
-    LS_LAUNCH_CHECK();
-    if (!entries) return LS_OK;
-    LS_HIP_CHECK(hipMemsetAsync(w.cell_count, 0, (size_t)cells * sizeof(int), st));
-    hipLaunchKernelGGL(dist_fill_batch_kernel, dim3(fb), dim3(256), 0, st, w.offs, M, nf_total, w.prm, tcell, w.start, w.cell_count, entries,
-                       cap_entries);
-    if (n_total > 0)
-        hipLaunchKernelGGL(dist_query_batch_kernel, dim3(cdiv(n_total, 256)), dim3(256), 0, st, points, w.offs, M, n_total, max_dist, w.prm, w.tri,
-                           w.start, w.cell_count, entries, count_out, cap_entries, dist_out);
-    LS_LAUNCH_CHECK();
-    return LS_OK;
+    return distance_launch(RaggedMeshes{vertices, faces, w.offs, M, nf_total, n_total, nullptr}, M, nf_total, points, n_total, max_dist, cells, w,
+                           dist_out, entries, cap_entries, count_out, st);
 }
 
 size_t ls_mesh_sample_batch_workspace_bytes(int M, long long nf_total) {
     if (M < 0 || nf_total < 0 || nf_total > INT_MAX) return 0;
-    Layout L;
-    L.take<long long>(nullptr, (size_t)OFF_ARRAYS * (M + 1));
-    L.take<double>(nullptr, (size_t)nf_total);
-    L.take<double>(nullptr, (size_t)nf_total);
-    L.take<double>(nullptr, (size_t)(scan_blocks(nf_total) + M));   // sum over meshes of scan_blocks(nf_m)
-    return L.off;
+    size_t b;
+    sample_layout(nullptr, n_offs(M), nf_total, scan_blocks(nf_total) + M, &b);   // at least the sum over meshes of scan_blocks(nf_m)
+    return b;
 }
 
 int ls_mesh_sample_batch_f64(int M, const double* vertices, long long nv_total, const long long* vert_off, const int32_t* faces, long long nf_total,
@@ -1116,23 +1036,11 @@ int ls_mesh_sample_batch_f64(int M, const double* vertices, long long nv_total, 
         return LS_ERR_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    Layout L;
-    char* ws = (char*)workspace;
-    long long* d_offs = L.take<long long>(ws, (size_t)OFF_ARRAYS * (M + 1));
-    double* area = L.take<double>(ws, (size_t)nf_total);
-    double* cum = L.take<double>(ws, (size_t)nf_total);
-    double* blk = L.take<double>(ws, (size_t)(scan_blocks(nf_total) + M));
+    const SampleWs w = sample_layout((char*)workspace, n_offs(M), nf_total, scan_blocks(nf_total) + M, nullptr);
     const std::vector<long long> offs = pack_offsets(M, vert_off, face_off, count_off, blk_off.data(), nullptr);
-    LS_HIP_CHECK(hipMemcpyAsync(d_offs, offs.data(), offs.size() * sizeof(long long), hipMemcpyHostToDevice, st));
-    const int nblk = (int)blk_off[M];   // > 0: some mesh is sampled, and it has faces
-    hipLaunchKernelGGL(area_batch_kernel, dim3(cdiv(nf_total, 256)), dim3(256), 0, st, vertices, faces, d_offs, M, nf_total, area);
-    hipLaunchKernelGGL(scan_reduce_batch_kernel, dim3(nblk), dim3(SCAN_T), 0, st, area, d_offs, M, blk);
-    hipLaunchKernelGGL(scan_top_batch_kernel, dim3(M), dim3(1024), 0, st, blk, d_offs, M);
-    hipLaunchKernelGGL(scan_apply_batch_kernel, dim3(nblk), dim3(SCAN_T), 0, st, area, d_offs, M, blk, cum);
-    hipLaunchKernelGGL(sample_batch_kernel, dim3(cdiv(count_total, 256)), dim3(256), 0, st, vertices, faces, d_offs, M, count_total, cum, seeds,
-                       points_out, face_out);
-    LS_LAUNCH_CHECK();
-    return LS_OK;
+    LS_HIP_CHECK(hipMemcpyAsync(w.offs, offs.data(), offs.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+    return sample_launch(RaggedMeshes{vertices, faces, w.offs, M, nf_total, count_total, seeds}, M, nf_total, (int)blk_off[M], count_total, w,
+                         points_out, face_out, st);
 }
 
 }  // extern "C"

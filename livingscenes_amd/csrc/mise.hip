@@ -15,6 +15,7 @@
 // the reference's (tests/golden/mise.npz; the ORDER of a round's queries is ascending lattice index instead of the
 // reference's insertion order -- the field is point-wise, so it cannot matter).
 #include "ls_common.h"
+#include "ls_scan.h"
 
 namespace ls {
 
@@ -89,21 +90,8 @@ __global__ __launch_bounds__(256) void mise_count_kernel(MiseDev d, long long np
     if (threadIdx.x == 0) d.blk[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 __global__ __launch_bounds__(1024) void mise_scan_kernel(int* blk, int nblk, int* count_out) {   // exclusive scan, one workgroup
-    __shared__ int part[1024];
-    const int t = threadIdx.x, per = (nblk + 1023) / 1024;
-    int s = 0;
-    for (int u = 0; u < per; ++u) { const int i = t * per + u; if (i < nblk) s += blk[i]; }
-    part[t] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const int v = t >= o ? part[t - o] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int run = t ? part[t - 1] : 0;
-    for (int u = 0; u < per; ++u) { const int i = t * per + u; if (i < nblk) { const int c = blk[i]; blk[i] = run; run += c; } }
-    if (t == 1023) { blk[nblk] = part[1023]; *count_out = part[1023]; }
+    const int total = scan_top_block<int>(blk, nblk);
+    if (threadIdx.x == 1023) { blk[nblk] = total; *count_out = total; }
 }
 __global__ __launch_bounds__(256) void mise_emit_kernel(MiseDev d, long long npts, float box_size, int32_t* idx_out, float* pts_out,
                                                         int cap) {

@@ -44,18 +44,28 @@ def _points(x, device):
     return t.to(device=device, dtype=torch.float64).reshape(-1, 3).contiguous()
 
 
+def _device_meshes(meshes, device, one=False):
+    """[(V [nv,3] float64, F [nf,3] int32)] on the device; the int64 faces meshes carry are range-checked per mesh (one host read for all of
+    them) and narrowed here.  An error names the mesh by its position unless there is only the one."""
+    out = []
+    for i, mesh in enumerate(meshes):
+        V = _points(mesh.vertices, device)
+        f = mesh.faces
+        F = f.detach().to(device=device, dtype=torch.int64) if torch.is_tensor(f) else torch.from_numpy(np.asarray(f, dtype=np.int64)).to(device)
+        if V.shape[0] >= 2 ** 31:
+            raise ValueError(f"mesh{'' if one else f' {i}'} has {V.shape[0]} vertices: the mesh operators index vertices with int32 (nv < 2^31)")
+        out.append((V, F.reshape(-1, 3)))
+    live = [i for i, (_, F) in enumerate(out) if F.numel()]
+    if live:
+        lim = torch.stack([torch.stack([out[i][1].min(), out[i][1].max()]) for i in live]).cpu().tolist()
+        for i, (lo, hi) in zip(live, lim):
+            if lo < 0 or hi >= out[i][0].shape[0]:
+                raise ValueError(f"mesh{'' if one else f' {i}:'} faces index vertices outside [0, {out[i][0].shape[0]})")
+    return [(V, F.to(torch.int32).contiguous()) for V, F in out]
+
+
 def _device_mesh(mesh, device):
-    """(V [nv,3] float64, F [nf,3] int32) on the device; the int64 faces meshes carry are range-checked and narrowed here."""
-    V = _points(mesh.vertices, device)
-    f = mesh.faces
-    F = f.detach().to(device=device, dtype=torch.int64) if torch.is_tensor(f) else torch.from_numpy(np.asarray(f, dtype=np.int64)).to(device)
-    F = F.reshape(-1, 3)
-    nv = V.shape[0]
-    if nv >= 2 ** 31:
-        raise ValueError(f"mesh has {nv} vertices: the mesh operators index vertices with int32 (nv < 2^31)")
-    if F.numel() and (int(F.min()) < 0 or int(F.max()) >= nv):
-        raise ValueError(f"mesh faces index vertices outside [0, {nv})")
-    return V, F.to(torch.int32).contiguous()
+    return _device_meshes([mesh], device, one=True)[0]
 
 
 def check_mesh_contains(mesh, points, hash_resolution=512):
@@ -74,6 +84,17 @@ def _sample(mesh, count, seed, device):
     return ops.mesh_sample(V, F, count, seed)[0]
 
 
+def _chamfer_means(gt_points, gen, dev):
+    """the two directed mean squared nearest-neighbour distances between gt_points and gen [n,3] float64, as float64 scalars on the device"""
+    gt = _points(gt_points, dev)
+    c = (gt.min(0).values + gt.max(0).values) / 2 if gt.shape[0] else torch.zeros(3, dtype=torch.float64, device=dev)
+    a = (gt - c).float().reshape(1, -1, 3, 1).contiguous()
+    b = (gen - c).float().reshape(1, -1, 3, 1).contiguous()
+    _, d_ab = ops.knn(a, b, 1, return_dist=True)
+    _, d_ba = ops.knn(b, a, 1, return_dist=True)
+    return d_ab.double().mean(), d_ba.double().mean()
+
+
 def compute_chamfer_distance(gt_points, gen_mesh, offset, scale, num_mesh_samples=30000, seed=0):
     """evaluate.py:12-40: (gt_to_gen, gen_to_gt) = mean squared nearest-neighbour distance from the points of ``gt_points.vertices`` to
     ``num_mesh_samples`` area-weighted samples of ``gen_mesh`` (moved by ``/ scale - offset``), and back.
@@ -83,14 +104,8 @@ def compute_chamfer_distance(gt_points, gen_mesh, offset, scale, num_mesh_sample
     centred on the middle of gt's bounding box in float64 before the fp32 nearest-neighbour search (ls_knn_f32, K = 1; distances do not
     change, and scans sit metres from the origin), and the means are accumulated in float64."""
     dev = _device()
-    gt = _points(gt_points, dev)
-    gen = _sample(gen_mesh, int(num_mesh_samples), seed, dev) / scale - offset
-    c = (gt.min(0).values + gt.max(0).values) / 2 if gt.shape[0] else torch.zeros(3, dtype=torch.float64, device=dev)
-    a = (gt - c).float().reshape(1, -1, 3, 1).contiguous()
-    b = (gen - c).float().reshape(1, -1, 3, 1).contiguous()
-    _, d_ab = ops.knn(a, b, 1, return_dist=True)
-    _, d_ba = ops.knn(b, a, 1, return_dist=True)
-    return float(d_ab.double().mean()), float(d_ba.double().mean())
+    gt_to_gen, gen_to_gt = _chamfer_means(gt_points, _sample(gen_mesh, int(num_mesh_samples), seed, dev) / scale - offset, dev)
+    return float(gt_to_gen), float(gen_to_gt)
 
 
 def mesh_distance(mesh, points, max_dist):
@@ -119,25 +134,6 @@ def compute_volumetric_iou(mesh1, mesh2, voxel_size=1. / 16):
 # ------------------------------------------------------------------------------------------------ the same metrics on many meshes per call
 # Element i of every *_batch function equals the per-mesh function on pair i, bit for bit: one ragged device call per metric (csrc/meshmetrics.hip,
 # ls_mesh_*_batch_f64) and one host read per batch instead of one per mesh.
-def _device_meshes(meshes, device):
-    """_device_mesh for a list of meshes: the int64 faces are range-checked per mesh (one host read for the batch) before narrowing."""
-    out = []
-    for i, mesh in enumerate(meshes):
-        V = _points(mesh.vertices, device)
-        f = mesh.faces
-        F = f.detach().to(device=device, dtype=torch.int64) if torch.is_tensor(f) else torch.from_numpy(np.asarray(f, dtype=np.int64)).to(device)
-        if V.shape[0] >= 2 ** 31:
-            raise ValueError(f"mesh {i} has {V.shape[0]} vertices: the mesh operators index vertices with int32 (nv < 2^31)")
-        out.append((V, F.reshape(-1, 3)))
-    live = [i for i, (_, F) in enumerate(out) if F.numel()]
-    if live:
-        lim = torch.stack([torch.stack([out[i][1].min(), out[i][1].max()]) for i in live]).cpu().tolist()
-        for i, (lo, hi) in zip(live, lim):
-            if lo < 0 or hi >= out[i][0].shape[0]:
-                raise ValueError(f"mesh {i}: faces index vertices outside [0, {out[i][0].shape[0]})")
-    return [(V, F.to(torch.int32).contiguous()) for V, F in out]
-
-
 def _host_split(parts):
     """per-mesh device results -> per-mesh numpy arrays, one device-to-host copy"""
     if not parts:
@@ -169,16 +165,7 @@ def compute_chamfer_distance_batch(gt_points_list, gen_meshes, offset, scale, nu
     M = len(gen_meshes)
     seeds = [0] * M if seeds is None else list(seeds)
     samples = ops.mesh_sample_batch(_device_meshes(gen_meshes, dev), int(num_mesh_samples), seeds)
-    means = []
-    for gt_points, (pts, _) in zip(gt_points_list, samples):
-        gt = _points(gt_points, dev)
-        gen = pts / scale - offset
-        c = (gt.min(0).values + gt.max(0).values) / 2 if gt.shape[0] else torch.zeros(3, dtype=torch.float64, device=dev)
-        a = (gt - c).float().reshape(1, -1, 3, 1).contiguous()
-        b = (gen - c).float().reshape(1, -1, 3, 1).contiguous()
-        _, d_ab = ops.knn(a, b, 1, return_dist=True)
-        _, d_ba = ops.knn(b, a, 1, return_dist=True)
-        means.append(torch.stack([d_ab.double().mean(), d_ba.double().mean()]))
+    means = [torch.stack(_chamfer_means(gt_points, pts / scale - offset, dev)) for gt_points, (pts, _) in zip(gt_points_list, samples)]
     return [tuple(v) for v in torch.stack(means).cpu().tolist()] if means else []
 
 

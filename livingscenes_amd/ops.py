@@ -527,18 +527,20 @@ def _mesh_dev(V, F):
     return V.contiguous(), F.contiguous()
 
 
-def _binned(name, ws_bytes, V, F, points, extra, out):
-    """Sizing call (entries = NULL -> bin entry count on the device), allocation, real call -- ls_marching_cubes_f64's convention."""
-    dev = V.device
+def _sized_call(dev, name, head, out, ws_bytes):
+    """Sizing call (entries = NULL -> bin entry count on the device), host read, allocation, real call -- ls_marching_cubes_f64's convention."""
     counts = torch.empty(1, dtype=torch.int64, device=dev)
     ws = _scratch(ws_bytes, dev)
     nbytes = 0 if ws is None else ws.numel()
-    head = (ptr(V), V.shape[0], ptr(F), F.shape[0], ptr(points), points.shape[0]) + tuple(extra)
     call(dev, name, *head, ptr(out), None, 0, ptr(counts), ptr(ws), nbytes, stream_ptr(dev))
-    n_entries = int(counts.item())
-    entries = torch.empty(max(n_entries, 1), dtype=torch.int32, device=dev)
+    entries = torch.empty(max(int(counts.item()), 1), dtype=torch.int32, device=dev)
     call(dev, name, *head, ptr(out), ptr(entries), entries.numel(), ptr(counts), ptr(ws), nbytes, stream_ptr(dev))
     return out
+
+
+def _binned(name, ws_bytes, V, F, points, extra, out):
+    head = (ptr(V), V.shape[0], ptr(F), F.shape[0], ptr(points), points.shape[0]) + tuple(extra)
+    return _sized_call(V.device, name, head, out, ws_bytes)
 
 
 def mesh_contains(V, F, points, hash_resolution=512):
@@ -613,13 +615,8 @@ def _binned_batch(name, ws_bytes, meshes, points_list, extra, dtype):
     dev = V.device
     P, po = _pack_points(points_list, len(meshes), dev)
     out = torch.empty(P.shape[0], dtype=dtype, device=dev)
-    counts = torch.empty(1, dtype=torch.int64, device=dev)
-    ws = _scratch(ws_bytes(len(meshes), F.shape[0]), dev)
-    nbytes = 0 if ws is None else ws.numel()
     head = (len(meshes), ptr(V), V.shape[0], _hptr(vo), ptr(F), F.shape[0], _hptr(fo), ptr(P), P.shape[0], _hptr(po)) + tuple(extra)
-    call(dev, name, *head, ptr(out), None, 0, ptr(counts), ptr(ws), nbytes, stream_ptr(dev))
-    entries = torch.empty(max(int(counts.item()), 1), dtype=torch.int32, device=dev)
-    call(dev, name, *head, ptr(out), ptr(entries), entries.numel(), ptr(counts), ptr(ws), nbytes, stream_ptr(dev))
+    _sized_call(dev, name, head, out, ws_bytes(len(meshes), F.shape[0]))
     return list(torch.split(out, np.diff(po).tolist()))
 
 

@@ -80,6 +80,101 @@ def test_mesh_entry_points_validate_arguments_without_device(lib):
     assert lib.ls_mesh_sample_f64(P(16), 8, P(16), 100, 10, 1, P(16), None, P(16), sws - 1, None) == -3
 
 
+# ---- the workspace sizes are part of the C contract: pinned to the values of the first release of these operators
+WS_NF = (0, 1, 100, 4096, 4097, 10 ** 6, -1)      # -1: rejected (0 bytes)
+WS_R = (2, 64, 512, 4096, 1, 4097)                # 1, 4097: rejected
+WS_M = (0, 1, 5, 128, -1)                         # -1: rejected
+WS_DISTANCE = (  # [nf]
+    25170176, 25170688, 25180160, 25563392, 25563904, 121170176, 0,
+)
+WS_SAMPLE = (  # [nf]
+    0, 768, 2304, 65792, 66304, 16002048, 0,
+)
+WS_CONTAINS = (  # [nf][R]
+    1024, 49664, 3146496, 201359616, 0, 0,
+    1536, 50176, 3147008, 201360128, 0, 0,
+    10240, 58880, 3155712, 201368832, 0, 0,
+    361472, 410112, 3506944, 201720064, 0, 0,
+    361984, 410624, 3507456, 201720576, 0, 0,
+    88001024, 88049664, 91146496, 289359616, 0, 0,
+    0, 0, 0, 0, 0, 0,
+)
+WS_DISTANCE_BATCH = (  # [nf][M]
+    256, 1280, 2048, 30720, 0,
+    1536, 1792, 2560, 31744, 0,
+    20224, 20736, 21504, 50432, 0,
+    786944, 787712, 788480, 817152, 0,
+    787968, 788224, 788992, 818176, 0,
+    192016128, 192016896, 192017664, 192046336, 0,
+    0, 0, 0, 0, 0,
+)
+WS_SAMPLE_BATCH = (  # [nf][M]
+    256, 512, 512, 6400, 0,
+    1024, 1024, 1024, 7168, 0,
+    2560, 2560, 2560, 8704, 0,
+    66048, 66048, 66048, 72192, 0,
+    66560, 66560, 66560, 72704, 0,
+    16002304, 16002304, 16002304, 16008448, 0,
+    0, 0, 0, 0, 0,
+)
+WS_CONTAINS_BATCH = (  # [nf][M][R]
+    256, 256, 256, 256, 0, 0,
+    1280, 49920, 3146752, 201359872, 0, 0,
+    2048, 247296, 15732480, 1006798080, 0, 0,
+    35328, 6321408, 402747648, 25774027008, 0, 0,
+    0, 0, 0, 0, 0, 0,
+    768, 768, 768, 768, 0, 0,
+    1792, 50432, 3147264, 201360384, 0, 0,
+    2560, 247808, 15732992, 1006798592, 0, 0,
+    35840, 6321920, 402748160, 25774027520, 0, 0,
+    0, 0, 0, 0, 0, 0,
+    9472, 9472, 9472, 9472, 0, 0,
+    10496, 59136, 3155968, 201369088, 0, 0,
+    11264, 256512, 15741696, 1006807296, 0, 0,
+    44544, 6330624, 402756864, 25774036224, 0, 0,
+    0, 0, 0, 0, 0, 0,
+    360704, 360704, 360704, 360704, 0, 0,
+    361728, 410368, 3507200, 201720320, 0, 0,
+    362496, 607744, 16092928, 1007158528, 0, 0,
+    395776, 6681856, 403108096, 25774387456, 0, 0,
+    0, 0, 0, 0, 0, 0,
+    361216, 361216, 361216, 361216, 0, 0,
+    362240, 410880, 3507712, 201720832, 0, 0,
+    363008, 608256, 16093440, 1007159040, 0, 0,
+    396288, 6682368, 403108608, 25774387968, 0, 0,
+    0, 0, 0, 0, 0, 0,
+    88000256, 88000256, 88000256, 88000256, 0, 0,
+    88001280, 88049920, 91146752, 289359872, 0, 0,
+    88002048, 88247296, 103732480, 1094798080, 0, 0,
+    88035328, 94321408, 490747648, 25862027008, 0, 0,
+    0, 0, 0, 0, 0, 0,
+    0, 0, 0, 0, 0, 0,
+    0, 0, 0, 0, 0, 0,
+    0, 0, 0, 0, 0, 0,
+    0, 0, 0, 0, 0, 0,
+    0, 0, 0, 0, 0, 0,
+)
+
+
+def test_mesh_workspace_sizes_are_pinned(lib):
+    it = {k: iter(v) for k, v in (("d", WS_DISTANCE), ("s", WS_SAMPLE), ("c", WS_CONTAINS), ("db", WS_DISTANCE_BATCH), ("sb", WS_SAMPLE_BATCH),
+                                  ("cb", WS_CONTAINS_BATCH))}
+    for nf in WS_NF:
+        assert lib.ls_mesh_distance_workspace_bytes(nf) == next(it["d"]), nf
+        assert lib.ls_mesh_sample_workspace_bytes(nf) == next(it["s"]), nf
+        for R in WS_R:
+            assert lib.ls_mesh_contains_workspace_bytes(nf, R) == next(it["c"]), (nf, R)
+        for M in WS_M:
+            assert lib.ls_mesh_distance_batch_workspace_bytes(M, nf) == next(it["db"]), (M, nf)
+            assert lib.ls_mesh_sample_batch_workspace_bytes(M, nf) == next(it["sb"]), (M, nf)
+            for R in WS_R:
+                assert lib.ls_mesh_contains_batch_workspace_bytes(M, nf, R) == next(it["cb"]), (M, nf, R)
+    assert all(next(i, None) is None for i in it.values())
+    # every rejected argument gives 0, every accepted one a multiple of 256
+    for (nf, R), b in zip([(nf, R) for nf in WS_NF for R in WS_R], WS_CONTAINS):
+        assert (b == 0) == (nf < 0 or R in (1, 4097)) and b % 256 == 0
+
+
 def test_python_metrics_refuse_cpu_and_bad_meshes():
     import torch
     from livingscenes_amd import _lib, evaluate, ops
