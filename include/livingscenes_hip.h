@@ -200,6 +200,43 @@ int ls_kabsch_codes_f32(const float* x1, const float* off1, const int64_t* sel1,
  * matcher_new.py:150-156 / :196-202.   src [n,P,3], tgt [m,P,3] -> res [n,m] */
 int ls_kabsch_residual_matrix_f32(const float* src, const float* tgt, int n, int m, int P, float* res, void* stream);
 
+/* ---- Ragged batches of matching problems: P problems per call, stored back to back (the convention of ls_mesh_*_batch_f64).
+ * Problem p owns the source rows [src_off[p], src_off[p+1]) and the target rows [tgt_off[p], tgt_off[p+1]) of the packed arrays; its
+ * score (residual) block is row-major n_p x m_p and starts at entry sum_{q<p} n_q m_q of the packed `scores` (`res`); matches0 [n_total]
+ * and matches1 [m_total] hold indices LOCAL to the problem, -1 = unmatched.  src_off / tgt_off: HOST int64 arrays of P + 1 entries (P >= 1),
+ * starting at 0, never decreasing, ending at n_total / m_total: checked, with errors that name the problem, and copied into the workspace
+ * on the stream.  A problem with n_p == 0 or m_p == 0 is allowed: it reads nothing, owns no scores, and every match of its non-empty side
+ * is -1 (the single ops refuse empty problems).  FOR EVERY PROBLEM EVERY OUTPUT IS BIT-IDENTICAL TO THE SINGLE OP ON THAT PROBLEM ALONE:
+ * the same kernels, each problem with the launch choices the single op makes for its size.  The number of kernel launches does not depend
+ * on P; no host synchronisation, no allocation.  *_batch_workspace_bytes: 0 for P <= 0 or a negative total; a missing or short workspace
+ * is LS_ERR_WORKSPACE. */
+/* ls_cosine_scores_f32 (matcher_new.py:110-120) per problem: m0 [n_total,D], m1 [m_total,D] -> packed scores.  1 launch, or 2 when a problem
+ * has more than 4096 entries (the single op's two forms: each problem's entries are formed the way the single op forms them). */
+size_t ls_cosine_scores_batch_workspace_bytes(int P, long long n_total, long long m_total);
+int ls_cosine_scores_batch_f32(int P, const float* m0, long long n_total, const long long* src_off, const float* m1, long long m_total,
+                               const long long* tgt_off, int D, float* scores, void* workspace, size_t workspace_bytes, void* stream);
+/* ls_greedy_match_f32 (matcher_new.py:121-136, :166-181, :212-227) per problem; the packed `scores` are DESTROYED.  One workgroup per problem,
+ * at most one launch per kernel class (n_p m_p <= 64 | <= 1024 | larger): every problem runs the kernel the single op gives it. */
+size_t ls_greedy_match_batch_workspace_bytes(int P, long long n_total, long long m_total);
+int ls_greedy_match_batch_f32(int P, float* scores, long long n_total, const long long* src_off, long long m_total, const long long* tgt_off,
+                              int64_t* matches0, int64_t* matches1, void* workspace, size_t workspace_bytes, void* stream);
+/* ls_nn_match_f32 (matcher_new.py:89-98, find_nn :73-83, mutual_check :100-105) per problem: one launch, one workgroup per problem, the LDS
+ * of the largest problem (a problem beyond the single op's limit is refused, and named, before anything is enqueued). */
+size_t ls_nn_match_batch_workspace_bytes(int P, long long n_total, long long m_total);
+int ls_nn_match_batch_f32(int P, const float* scores, long long n_total, const long long* src_off, long long m_total, const long long* tgt_off,
+                          int64_t* matches0, int64_t* matches1, void* workspace, size_t workspace_bytes, void* stream);
+/* ls_sinkhorn_match_f32 (matcher_new.py:49-71, log_optimal_transport :20-40) per problem; score_divisor, alpha, iters and match_threshold
+ * hold for the whole batch.  One launch, as ls_nn_match_batch_f32. */
+size_t ls_sinkhorn_match_batch_workspace_bytes(int P, long long n_total, long long m_total);
+int ls_sinkhorn_match_batch_f32(int P, const float* scores, long long n_total, const long long* src_off, long long m_total, const long long* tgt_off,
+                                float score_divisor, float alpha, int iters, float match_threshold, int64_t* matches0, int64_t* matches1,
+                                void* workspace, size_t workspace_bytes, void* stream);
+/* ls_kabsch_residual_matrix_f32 (res_mat of matcher_new.py:150-156 / :196-202) per problem: src [n_total,C,3], tgt [m_total,C,3] (C pseudo-points
+ * per code) -> packed res.  One launch, one wave per (i, j) pair. */
+size_t ls_kabsch_residual_matrix_batch_workspace_bytes(int P, long long n_total, long long m_total);
+int ls_kabsch_residual_matrix_batch_f32(int P, const float* src, long long n_total, const long long* src_off, const float* tgt, long long m_total,
+                                        const long long* tgt_off, int C, float* res, void* workspace, size_t workspace_bytes, void* stream);
+
 /* pytorch3d.ops.iterative_closest_point(X, Y, init_transform=SimilarityTransform(R0,T0,1)) with default
  * arguments (100 iterations, relative_rmse_thr 1e-6), as called at lib_more/more_solver.py:182-187.
  * Row-vector convention Xt = X R + T.  X [b,n,3], Y [b,m,3], R0 [b,3,3], T0 [b,3] ->

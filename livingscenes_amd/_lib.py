@@ -75,6 +75,7 @@ _U = ctypes.c_uint
 _F = ctypes.c_float
 _D = ctypes.c_double
 _SZ = ctypes.c_size_t
+_LL = ctypes.c_longlong
 
 # name -> (restype, argtypes); every symbol include/livingscenes_hip.h declares
 class SoftminProblem(ctypes.Structure):
@@ -114,6 +115,17 @@ SIGNATURES = {
     "ls_kabsch_batched_f32": (_I, [_P, _P, _P, _I, _I, _U, _P, _P, _P, _P, _P]),
     "ls_kabsch_codes_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "ls_kabsch_residual_matrix_f32": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    # ragged batches of matching problems: (P, ..., n_total, src_off, ..., m_total, tgt_off, ..., workspace, workspace_bytes, stream)
+    "ls_cosine_scores_batch_workspace_bytes": (_SZ, [_I, _LL, _LL]),
+    "ls_cosine_scores_batch_f32": (_I, [_I, _P, _LL, _P, _P, _LL, _P, _I, _P, _P, _SZ, _P]),
+    "ls_greedy_match_batch_workspace_bytes": (_SZ, [_I, _LL, _LL]),
+    "ls_greedy_match_batch_f32": (_I, [_I, _P, _LL, _P, _LL, _P, _P, _P, _P, _SZ, _P]),
+    "ls_nn_match_batch_workspace_bytes": (_SZ, [_I, _LL, _LL]),
+    "ls_nn_match_batch_f32": (_I, [_I, _P, _LL, _P, _LL, _P, _P, _P, _P, _SZ, _P]),
+    "ls_sinkhorn_match_batch_workspace_bytes": (_SZ, [_I, _LL, _LL]),
+    "ls_sinkhorn_match_batch_f32": (_I, [_I, _P, _LL, _P, _LL, _P, _F, _F, _I, _F, _P, _P, _P, _SZ, _P]),
+    "ls_kabsch_residual_matrix_batch_workspace_bytes": (_SZ, [_I, _LL, _LL]),
+    "ls_kabsch_residual_matrix_batch_f32": (_I, [_I, _P, _LL, _P, _P, _LL, _P, _I, _P, _P, _SZ, _P]),
     "ls_icp_workspace_bytes": (_SZ, [_I, _I]),
     "ls_icp_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _U, _P, _P, _P, _P, _P, _SZ, _P]),
     "ls_model_create": (_I, [ctypes.POINTER(ModelDesc), _P, ctypes.POINTER(_P)]),

@@ -7,38 +7,92 @@
 // All three are launch-latency-bound at the reference's sizes (32x32 scores, 256-point pseudo clouds), so each is a
 // single launch over the whole batch: one workgroup for the matcher loop (no host round trips: the reference's
 // .nonzero() syncs every iteration), one WAVE per Kabsch problem with the 3x3 SVD done in registers.
+//
+// One matching problem (the single ops) or a ragged batch of P problems (ls_*_batch_f32): every kernel and every launch sequence is
+// written once, for a problem locator.  With OneProblem a thread's problem is the call's arguments; with RaggedProblems a workgroup
+// takes the problem its block index names, and a wave of the per-entry kernels finds its problem by binary search of the offsets.
+#include <vector>
+
 #include "ls_common.h"
+#include "ls_ragged.h"
 #include "svd3.h"
 
 namespace ls {
 
+// ---------------------------------------------------------------------------------------------- which problem: one, or one of a ragged batch
+// Problem p of a batch owns the source rows [src_off[p], src_off[p+1]) and the target rows [tgt_off[p], tgt_off[p+1]); its n x m score
+// block starts at entry ent_off[p] = sum_{q<p} n_q m_q of the packed scores, its n + m inverse row norms at row_off[p] = src_off[p] +
+// tgt_off[p].  The device copy of the offsets (offs) is those MOFF_ARRAYS arrays of P + 1 int64 back to back, followed by P problem ids:
+// the problems of each greedy class (one wave | four waves | 1024 threads) in ascending order, class after class.
+enum { MOFF_SRC = 0, MOFF_TGT, MOFF_ENT, MOFF_ROW, MOFF_ARRAYS };
+
+struct Problem {
+    int n, m;
+    long long s0, t0;   // first source / target row
+    long long e0;       // first score entry
+    long long r0;       // first inverse row norm
+};
+
+// the locator of the single ops holds plain values: no offsets on the device, nothing to upload
+struct OneProblem {
+    int n, m;
+    __device__ long long entries() const { return (long long)n * m; }
+    __device__ long long rows() const { return (long long)n + m; }
+    __device__ int entry_owner(long long) const { return 0; }
+    __device__ int row_owner(long long) const { return 0; }
+    __device__ int block_problem(int) const { return 0; }
+    __device__ Problem problem(int) const { return {n, m, 0, 0, 0, 0}; }
+};
+
+struct RaggedProblems {
+    const long long* offs;   // device copy of the offsets
+    const long long* ids;    // workgroup b works on problem ids[b] (null: on problem b)
+    int P;
+    __device__ const long long* off(int k) const { return offs + (size_t)k * (P + 1); }
+    __device__ long long entries() const { return off(MOFF_ENT)[P]; }
+    __device__ long long rows() const { return off(MOFF_ROW)[P]; }
+    __device__ int entry_owner(long long e) const { return owner(off(MOFF_ENT), P, e); }
+    __device__ int row_owner(long long r) const { return owner(off(MOFF_ROW), P, r); }
+    __device__ int block_problem(int b) const { return ids ? (int)ids[b] : b; }
+    __device__ Problem problem(int p) const {
+        const long long s0 = off(MOFF_SRC)[p], t0 = off(MOFF_TGT)[p];
+        return {(int)(off(MOFF_SRC)[p + 1] - s0), (int)(off(MOFF_TGT)[p + 1] - t0), s0, t0, off(MOFF_ENT)[p], off(MOFF_ROW)[p]};
+    }
+};
+
 // ---------------------------------------------------------------------------------------------- scores
-__global__ __launch_bounds__(256) void cosine_scores_kernel(const float* __restrict__ m0, const float* __restrict__ m1, int n,
-                                                            int m, int D, float* __restrict__ inv_norm, float* __restrict__ S,
-                                                            int phase) {
+// phase 0: the inverse row norms; phase 1: the entries, from those norms -- but an entry of a problem of at most 4096 entries forms its two
+// norms itself, as the single op does for such a problem (a batch mixes sizes); phase 2: every entry forms its norms itself
+template <class Problems>
+__global__ __launch_bounds__(256) void cosine_scores_kernel(Problems L, const float* __restrict__ m0, const float* __restrict__ m1, int D,
+                                                            float* __restrict__ inv_norm, float* __restrict__ S, int phase) {
     LS_LATENCY_CRITICAL();
     const int lane = threadIdx.x & 63;
-    const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (phase == 0) {  // one wave per row of [m0; m1]: 1 / max(|row|, 1e-12)
-        if (w >= n + m) return;
-        const float* r = w < n ? m0 + (size_t)w * D : m1 + (size_t)(w - n) * D;
+    const long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (phase == 0) {  // one wave per row of [m0; m1] of a problem: 1 / max(|row|, 1e-12)
+        if (w >= L.rows()) return;
+        const Problem q = L.problem(L.row_owner(w));
+        const long long l = w - q.r0;
+        const float* r = l < q.n ? m0 + (size_t)(q.s0 + l) * D : m1 + (size_t)(q.t0 + l - q.n) * D;
         float s = 0.f;
         for (int c = lane; c < D; c += 64) s += r[c] * r[c];
         s = wave_sum(s);
         if (lane == 0) inv_norm[w] = 1.0f / fmaxf(sqrtf(s), 1e-12f);
     } else {           // one wave per score entry
-        if (w >= n * m) return;
-        const int i = w / m, j = w % m;
-        const float* a = m0 + (size_t)i * D;
-        const float* b = m1 + (size_t)j * D;
+        if (w >= L.entries()) return;
+        const Problem q = L.problem(L.entry_owner(w));
+        const int e = (int)(w - q.e0), n = q.n, m = q.m;
+        const int i = e / m, j = e % m;
+        const float* a = m0 + (size_t)(q.s0 + i) * D;
+        const float* b = m1 + (size_t)(q.t0 + j) * D;
         float ia, ib;
-        if (phase == 2) {   // single-launch form (small problems): the entry's wave forms both norms itself -- the same sums in the same order as phase 0
+        if (phase == 2 || (long long)n * m <= 4096) {   // single-launch form (small problems): the entry's wave forms both norms itself -- the same sums in the same order as phase 0
             float sa = 0.f, sb = 0.f;
 #pragma unroll 4
             for (int c = lane; c < D; c += 64) { sa += a[c] * a[c]; sb += b[c] * b[c]; }
             sa = wave_sum(sa); sb = wave_sum(sb);
             ia = 1.0f / fmaxf(sqrtf(sa), 1e-12f); ib = 1.0f / fmaxf(sqrtf(sb), 1e-12f);
-        } else { ia = inv_norm[i]; ib = inv_norm[n + j]; }
+        } else { ia = inv_norm[q.r0 + i]; ib = inv_norm[q.r0 + n + j]; }
         float s = 0.f;
 #pragma unroll 4
         for (int c = lane; c < D; c += 64) s += (a[c] * ia) * (b[c] * ib);
@@ -50,8 +104,15 @@ __global__ __launch_bounds__(256) void cosine_scores_kernel(const float* __restr
 // ---------------------------------------------------------------------------------------------- greedy loop
 // S [n,m] in global (L2-resident), destroyed.  Deleted rows/columns are tracked with alive flags; "first
 // row-major arg-max of the shrunken matrix" == lexicographically smallest (row, col) among alive maxima.
-__global__ __launch_bounds__(1024) void greedy_match_kernel(float* __restrict__ S, int n, int m, long long* __restrict__ m0,
-                                                            long long* __restrict__ m1) {
+// One workgroup per problem (all three greedy kernels): workgroup b works on problem L.block_problem(b).
+template <class Problems>
+__global__ __launch_bounds__(1024) void greedy_match_kernel(Problems L, float* __restrict__ S_all, long long* __restrict__ m0_all,
+                                                            long long* __restrict__ m1_all) {
+    const Problem q = L.problem(L.block_problem(blockIdx.x));
+    const int n = q.n, m = q.m;
+    float* __restrict__ S = S_all + q.e0;
+    long long* __restrict__ m0 = m0_all + q.s0;
+    long long* __restrict__ m1 = m1_all + q.t0;
     extern __shared__ int alive[];  // [n] rows | [m] cols
     __shared__ float redv[16];
     __shared__ int redi[16];
@@ -140,9 +201,15 @@ __device__ __forceinline__ int gm_wave_min(int v) {
     v = min(v, gm_dpp<0x143, 0xC>(v));
     return __builtin_amdgcn_readlane(v, 63);
 }
-__global__ __launch_bounds__(64) void greedy_match_wave_kernel(const float* __restrict__ S, int n, int m, long long* __restrict__ m0,
-                                                              long long* __restrict__ m1) {
+template <class Problems>
+__global__ __launch_bounds__(64) void greedy_match_wave_kernel(Problems L, const float* __restrict__ S_all, long long* __restrict__ m0_all,
+                                                              long long* __restrict__ m1_all) {
     LS_LATENCY_CRITICAL();
+    const Problem q = L.problem(L.block_problem(blockIdx.x));
+    const int n = q.n, m = q.m;    // (an empty problem of a batch: nothing is read, every match is -1)
+    const float* __restrict__ S = S_all + q.e0;
+    long long* __restrict__ m0 = m0_all + q.s0;
+    long long* __restrict__ m1 = m1_all + q.t0;
     const int lane = threadIdx.x;
     const int total = n * m;
     float v[16];
@@ -188,9 +255,15 @@ __global__ __launch_bounds__(64) void greedy_match_wave_kernel(const float* __re
 // the divided maximum (a correctly rounded division by one positive denominator is monotone), so only the matrix maximum and the first position that
 // holds the divided maximum are reduced; a non-positive or non-finite denominator (all scores <= -1e-5) takes the three-reduction form.  The matches are
 // collected in LDS and written once.  Same arithmetic on every entry, same tie rule: identical matches (tests/test_hip_parity.py, test_hip_surface.py).
-__global__ __launch_bounds__(256) void greedy_match_quad_kernel(const float* __restrict__ S, int n, int m, long long* __restrict__ m0,
-                                                                long long* __restrict__ m1) {
+template <class Problems>
+__global__ __launch_bounds__(256) void greedy_match_quad_kernel(Problems L, const float* __restrict__ S_all, long long* __restrict__ m0_all,
+                                                                long long* __restrict__ m1_all) {
     LS_LATENCY_CRITICAL();
+    const Problem q = L.problem(L.block_problem(blockIdx.x));
+    const int n = q.n, m = q.m;
+    const float* __restrict__ S = S_all + q.e0;
+    long long* __restrict__ m0 = m0_all + q.s0;
+    long long* __restrict__ m1 = m1_all + q.t0;
     __shared__ float lmx[4], lmx2[4];
     __shared__ int lpos[4];
     __shared__ int lm[2048];     // matches of the rows | of the columns (n, m <= 1024)
@@ -253,8 +326,10 @@ __global__ __launch_bounds__(256) void greedy_match_quad_kernel(const float* __r
 
 // ---------------------------------------------------------------------------------------------- Kabsch
 // one wave per problem; problem p pairs cloud x1[i1(p)] with x2[i2(p)]:
-//   pair_mode 0: i1 = i2 = p (batched Kabsch);  pair_mode 1: p = i*m + j -> (i, j) (residual matrix)
-__global__ __launch_bounds__(256) void kabsch_kernel(const float* __restrict__ x1, const float* __restrict__ x2,
+//   pair_m == 0: i1 = i2 = p (batched Kabsch);  pair_m > 0: p is entry i*m + j of the residual matrix of a matching problem of L -> its
+//   source set i, its target set j
+template <class Problems>
+__global__ __launch_bounds__(256) void kabsch_kernel(Problems L, const float* __restrict__ x1, const float* __restrict__ x2,
                                                      const float* __restrict__ weights, int nprob, int n, int pair_m,
                                                      int raw_weights, float eps, float* __restrict__ Rout, float* __restrict__ tout,
                                                      float* __restrict__ res, float* __restrict__ res_mean,
@@ -267,7 +342,13 @@ __global__ __launch_bounds__(256) void kabsch_kernel(const float* __restrict__ x
     const int lane = threadIdx.x & 63;
     const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (p >= nprob) return;
-    int i1 = pair_m > 0 ? p / pair_m : p, i2 = pair_m > 0 ? p % pair_m : p;
+    int i1 = p, i2 = p;
+    if (pair_m > 0) {
+        const Problem q = L.problem(L.entry_owner(p));
+        const int e = (int)(p - q.e0);
+        i1 = (int)q.s0 + e / q.m;
+        i2 = (int)q.t0 + e % q.m;
+    }
     if (sel1) i1 = (int)max(sel1[p], 0ll);
     if (sel2) i2 = (int)max(sel2[p], 0ll);
     const float* a0 = x1 + (size_t)i1 * n * 3;
@@ -362,28 +443,40 @@ __global__ __launch_bounds__(256) void kabsch_kernel(const float* __restrict__ x
     if (res_mean) { rs = wave_sum(rs); if (lane == 0) res_mean[p] = rs / (float)n; }
 }
 
-int cosine_scores_launch(const float* m0, const float* m1, int n, int m, int D, float* inv_norm_ws, float* S, hipStream_t st) {
-    if ((long long)n * m <= 4096) {   // latency-bound: one launch, every entry's wave recomputes its two row norms (bit-identical to the two-launch form)
-        hipLaunchKernelGGL(cosine_scores_kernel, dim3(cdiv((long long)n * m, 4)), dim3(256), 0, st, m0, m1, n, m, D, inv_norm_ws, S, 2);
+// ---------------------------------------------------------------------------------------------- launch sequences (one problem or a batch)
+// any_large: some problem has more than 4096 entries
+template <class Problems>
+int cosine_scores_run(const Problems& L, long long rows, long long entries, bool any_large, const float* m0, const float* m1, int D, float* inv_norm_ws,
+                      float* S, hipStream_t st) {
+    if (!any_large) {   // latency-bound: one launch, every entry's wave recomputes its two row norms (bit-identical to the two-launch form)
+        hipLaunchKernelGGL(cosine_scores_kernel<Problems>, dim3(cdiv(entries, 4)), dim3(256), 0, st, L, m0, m1, D, inv_norm_ws, S, 2);
         LS_LAUNCH_CHECK();
         return LS_OK;
     }
-    hipLaunchKernelGGL(cosine_scores_kernel, dim3(cdiv(n + m, 4)), dim3(256), 0, st, m0, m1, n, m, D, inv_norm_ws, S, 0);
-    hipLaunchKernelGGL(cosine_scores_kernel, dim3(cdiv((long long)n * m, 4)), dim3(256), 0, st, m0, m1, n, m, D, inv_norm_ws, S, 1);
+    hipLaunchKernelGGL(cosine_scores_kernel<Problems>, dim3(cdiv(rows, 4)), dim3(256), 0, st, L, m0, m1, D, inv_norm_ws, S, 0);
+    hipLaunchKernelGGL(cosine_scores_kernel<Problems>, dim3(cdiv(entries, 4)), dim3(256), 0, st, L, m0, m1, D, inv_norm_ws, S, 1);
     LS_LAUNCH_CHECK();
     return LS_OK;
 }
-int greedy_match_launch(float* S, int n, int m, long long* m0, long long* m1, hipStream_t st) {
-    if ((long long)n * m <= 1024) {
-        if (n * m <= 64) hipLaunchKernelGGL(greedy_match_wave_kernel, dim3(1), dim3(64), 0, st, S, n, m, m0, m1);
-        else hipLaunchKernelGGL(greedy_match_quad_kernel, dim3(1), dim3(256), 0, st, S, n, m, m0, m1);
-        LS_LAUNCH_CHECK();
-        return LS_OK;
-    }
-    LS_REQUIRE((size_t)(n + m) * sizeof(int) <= 48 * 1024, "greedy_match: n+m=%d too large", n + m);
-    hipLaunchKernelGGL(greedy_match_kernel, dim3(1), dim3(1024), (size_t)(n + m) * sizeof(int), st, S, n, m, m0, m1);
+// the three greedy kernels by n * m: <= 64 one wave, <= 1024 four waves, larger 1024 threads with lds = (n + m) ints (of the largest problem)
+enum { GREEDY_WAVE = 0, GREEDY_QUAD, GREEDY_BLOCK, GREEDY_CLASSES };
+inline int greedy_class(long long n, long long m) { return n * m <= 64 ? GREEDY_WAVE : (n * m <= 1024 ? GREEDY_QUAD : GREEDY_BLOCK); }
+template <class Problems>
+int greedy_match_run(const Problems& L, int cls, int count, size_t lds, float* S, long long* m0, long long* m1, hipStream_t st) {
+    if (cls == GREEDY_WAVE) hipLaunchKernelGGL(greedy_match_wave_kernel<Problems>, dim3(count), dim3(64), 0, st, L, S, m0, m1);
+    else if (cls == GREEDY_QUAD) hipLaunchKernelGGL(greedy_match_quad_kernel<Problems>, dim3(count), dim3(256), 0, st, L, S, m0, m1);
+    else hipLaunchKernelGGL(greedy_match_kernel<Problems>, dim3(count), dim3(1024), lds, st, L, S, m0, m1);
     LS_LAUNCH_CHECK();
     return LS_OK;
+}
+
+int cosine_scores_launch(const float* m0, const float* m1, int n, int m, int D, float* inv_norm_ws, float* S, hipStream_t st) {
+    return cosine_scores_run(OneProblem{n, m}, (long long)n + m, (long long)n * m, (long long)n * m > 4096, m0, m1, D, inv_norm_ws, S, st);
+}
+int greedy_match_launch(float* S, int n, int m, long long* m0, long long* m1, hipStream_t st) {
+    const int cls = greedy_class(n, m);
+    if (cls == GREEDY_BLOCK) LS_REQUIRE((size_t)(n + m) * sizeof(int) <= 48 * 1024, "greedy_match: n+m=%d too large", n + m);
+    return greedy_match_run(OneProblem{n, m}, cls, 1, (size_t)(n + m) * sizeof(int), S, m0, m1, st);
 }
 // ---------------------------------------------------------------------------------------------- mutual-NN and Sinkhorn assignment
 // nn_matcher            /root/reference/lib_more/matcher_new.py:85-107   (find_nn without thresholds, two mutual checks)
@@ -394,11 +487,23 @@ int greedy_match_launch(float* S, int n, int m, long long* m0, long long* m1, hi
 // eight lanes share a row (column), one barrier per half-iteration.  Ties: the FIRST maximum (lowest index), as torch.max / topk return on the reference's
 // devices for the sizes in question.  logsumexp as ATen computes it: max, log(sum exp(x - max)) + max (an all -inf row keeps max = 0).
 // mode 0 = mutual nearest neighbours on `S`; mode 1 = Sinkhorn on S / div.
-__global__ __launch_bounds__(1024) void assign_kernel(const float* __restrict__ S, int n, int m, int mode, float div, float alpha, int iters, float thr,
-                                                      long long* __restrict__ m0, long long* __restrict__ m1) {
+// One workgroup per problem; the LDS pointers are laid out from the problem's own n, m (the launch's dynamic LDS is that of its largest problem).
+template <class Problems>
+__global__ __launch_bounds__(1024) void assign_kernel(Problems L, const float* __restrict__ S_all, int mode, float div, float alpha, int iters, float thr,
+                                                      long long* __restrict__ m0_all, long long* __restrict__ m1_all) {
     LS_LATENCY_CRITICAL();
     extern __shared__ float az[];
+    const Problem q = L.problem(L.block_problem(blockIdx.x));
+    const int n = q.n, m = q.m;
+    const float* __restrict__ S = S_all + q.e0;
+    long long* __restrict__ m0 = m0_all + q.s0;
+    long long* __restrict__ m1 = m1_all + q.t0;
     const int tid = threadIdx.x, g = tid & 7, grp = tid >> 3;
+    if (n == 0 || m == 0) {   // an empty problem of a batch (the single ops refuse it): nothing to read, nothing matched
+        for (int i = tid; i < n; i += 1024) m0[i] = -1;
+        for (int j = tid; j < m; j += 1024) m1[j] = -1;
+        return;
+    }
     const int R = mode ? n + 1 : n, C = mode ? m + 1 : m, ld = C | 1;
     float* Z = az;                     // [R][ld]
     float* u = Z + (size_t)R * ld;     // [R]
@@ -494,19 +599,164 @@ size_t assign_lds_bytes(int n, int m, int mode) {
     const size_t R = mode ? n + 1 : n, C = mode ? m + 1 : m, ld = C | 1;
     return (R * ld + R + C + (size_t)n + 2 * (size_t)n + (size_t)m) * 4;
 }
-int assign_launch(const float* S, int n, int m, int mode, float div, float alpha, int iters, float thr, long long* m0, long long* m1, hipStream_t st) {
-    const size_t lds = assign_lds_bytes(n, m, mode);
-    LS_REQUIRE(lds <= 150 * 1024, "%s: a %d x %d problem needs %zu bytes of LDS (at most 153600: about 190 x 190)", mode ? "sinkhorn_match" : "nn_match", n, m, lds);
-    if (lds > 64 * 1024) LS_HIP_CHECK(hipFuncSetAttribute((const void*)assign_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(assign_kernel, dim3(1), dim3(1024), lds, st, S, n, m, mode, div, alpha, iters, thr, m0, m1);
+constexpr size_t ASSIGN_LDS_MAX = 150 * 1024;
+template <class Problems>
+int assign_run(const Problems& L, int count, size_t lds, const float* S, int mode, float div, float alpha, int iters, float thr, long long* m0,
+               long long* m1, hipStream_t st) {
+    if (lds > 64 * 1024)
+        LS_HIP_CHECK(hipFuncSetAttribute((const void*)assign_kernel<Problems>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(assign_kernel<Problems>, dim3(count), dim3(1024), lds, st, L, S, mode, div, alpha, iters, thr, m0, m1);
     LS_LAUNCH_CHECK();
     return LS_OK;
+}
+int assign_launch(const float* S, int n, int m, int mode, float div, float alpha, int iters, float thr, long long* m0, long long* m1, hipStream_t st) {
+    const size_t lds = assign_lds_bytes(n, m, mode);
+    LS_REQUIRE(lds <= ASSIGN_LDS_MAX, "%s: a %d x %d problem needs %zu bytes of LDS (at most 153600: about 190 x 190)", mode ? "sinkhorn_match" : "nn_match", n, m, lds);
+    return assign_run(OneProblem{n, m}, 1, lds, S, mode, div, alpha, iters, thr, m0, m1, st);
 }
 int kabsch_launch(const float* x1, const float* x2, const float* w, int nprob, int n, int pair_m, int raw_weights, float* R, float* t,
                   float* res, float* res_mean, int32_t* flags, hipStream_t st, const float* off1, const float* off2, const long long* sel1,
                   const long long* sel2) {
-    hipLaunchKernelGGL(kabsch_kernel, dim3(cdiv(nprob, 4)), dim3(256), 0, st, x1, x2, w, nprob, n, pair_m, raw_weights, 1e-7f, R, t, res,
-                       res_mean, flags, off1, off2, sel1, sel2);
+    hipLaunchKernelGGL(kabsch_kernel<OneProblem>, dim3(cdiv(nprob, 4)), dim3(256), 0, st, OneProblem{pair_m > 0 ? nprob / pair_m : 0, pair_m}, x1, x2, w,
+                       nprob, n, pair_m, raw_weights, 1e-7f, R, t, res, res_mean, flags, off1, off2, sel1, sel2);
+    LS_LAUNCH_CHECK();
+    return LS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- ragged batches
+// Every problem's result is bit-identical to the single op on that problem alone: the same kernels, the same launch choices per problem.
+// The argument checks run before the first HIP call (no device is needed to be told what is wrong with the offsets).
+size_t match_batch_workspace_bytes(int P, long long n_total, long long m_total, int with_norms) {
+    if (P <= 0 || n_total < 0 || m_total < 0) return 0;
+    const size_t offs = ((size_t)MOFF_ARRAYS * (P + 1) + (size_t)P) * sizeof(long long);
+    return ((offs + 255) / 256) * 256 + (with_norms ? (size_t)(n_total + m_total) * sizeof(float) : 0);
+}
+
+namespace {
+struct Batch {
+    RaggedProblems L;
+    float* inv_norm;
+    long long rows, entries;
+    int cls_count[GREEDY_CLASSES], cls_first[GREEDY_CLASSES];
+    size_t greedy_lds;    // of the largest problem of the 1024-thread class
+    bool any_large;       // some problem has more than 4096 entries
+    std::vector<long long> host;   // what upload() copies: the offsets and the class lists
+    int upload(hipStream_t st) const { return upload_offsets(const_cast<long long*>(L.offs), host, st); }
+};
+
+// the checks every batch entry shares, and the batch's layout in its workspace; nothing is enqueued
+int batch_setup(const char* op, int P, long long n_total, const long long* src_off, long long m_total, const long long* tgt_off, void* ws,
+                size_t ws_bytes, int with_norms, Batch* b) {
+    LS_REQUIRE(P > 0 && n_total >= 0 && m_total >= 0, "%s: P %d, n_total %lld, m_total %lld", op, P, n_total, m_total);
+    int rc = check_ranges(op, "problem", "src_off", P, src_off, n_total, INT_MAX);
+    if (rc != LS_OK) return rc;
+    rc = check_ranges(op, "problem", "tgt_off", P, tgt_off, m_total, INT_MAX);
+    if (rc != LS_OK) return rc;
+    LS_REQUIRE(n_total + m_total <= INT_MAX, "%s: %lld rows in the batch, at most %d", op, n_total + m_total, INT_MAX);
+    std::vector<long long> ent(P + 1, 0), row(P + 1, 0);
+    std::vector<int> cls(P);
+    *b = Batch{};
+    for (int p = 0; p < P; ++p) {
+        const long long n = src_off[p + 1] - src_off[p], m = tgt_off[p + 1] - tgt_off[p];
+        LS_REQUIRE(n * m <= INT_MAX, "%s: problem %d: %lld x %lld scores, at most %d per problem", op, p, n, m, INT_MAX);
+        ent[p + 1] = ent[p] + n * m;
+        LS_REQUIRE(ent[p + 1] <= INT_MAX, "%s: problem %d: the batch's scores pass %d entries", op, p, INT_MAX);
+        row[p + 1] = src_off[p + 1] + tgt_off[p + 1];
+        cls[p] = greedy_class(n, m);
+        b->cls_count[cls[p]]++;
+        if (cls[p] == GREEDY_BLOCK) b->greedy_lds = std::max(b->greedy_lds, (size_t)(n + m) * sizeof(int));
+        if (n * m > 4096) b->any_large = true;
+    }
+    const size_t need = match_batch_workspace_bytes(P, n_total, m_total, with_norms);
+    if (!ws || ws_bytes < need) {
+        set_error("%s: workspace %zu < required %zu", op, ws ? ws_bytes : (size_t)0, need);
+        return LS_ERR_WORKSPACE;
+    }
+    b->host = pack_offsets(P, {src_off, tgt_off, ent.data(), row.data()});
+    b->host.resize(b->host.size() + P);
+    int at[GREEDY_CLASSES];
+    for (int c = 0, first = 0; c < GREEDY_CLASSES; first += b->cls_count[c], ++c) at[c] = b->cls_first[c] = first;
+    for (int p = 0; p < P; ++p) b->host[(size_t)MOFF_ARRAYS * (P + 1) + at[cls[p]]++] = p;
+    b->L = RaggedProblems{(const long long*)ws, nullptr, P};
+    b->inv_norm = with_norms ? (float*)((char*)ws + match_batch_workspace_bytes(P, 0, 0, 0)) : nullptr;
+    b->rows = row[P];
+    b->entries = ent[P];
+    return LS_OK;
+}
+}  // namespace
+
+int cosine_scores_batch_launch(int P, const float* m0, long long n_total, const long long* src_off, const float* m1, long long m_total,
+                               const long long* tgt_off, int D, float* S, void* ws, size_t ws_bytes, hipStream_t st) {
+    const char* op = "cosine_scores_batch";
+    LS_REQUIRE(D > 0, "%s: D = %d", op, D);
+    Batch b;
+    int rc = batch_setup(op, P, n_total, src_off, m_total, tgt_off, ws, ws_bytes, 1, &b);
+    if (rc != LS_OK) return rc;
+    if (b.entries == 0) return LS_OK;   // every problem is empty: no scores
+    LS_REQUIRE(m0 && m1 && S, "%s: null argument", op);
+    rc = b.upload(st);
+    if (rc != LS_OK) return rc;
+    return cosine_scores_run(b.L, b.rows, b.entries, b.any_large, m0, m1, D, b.inv_norm, S, st);
+}
+
+int greedy_match_batch_launch(int P, float* S, long long n_total, const long long* src_off, long long m_total, const long long* tgt_off,
+                              long long* m0, long long* m1, void* ws, size_t ws_bytes, hipStream_t st) {
+    const char* op = "greedy_match_batch";
+    Batch b;
+    int rc = batch_setup(op, P, n_total, src_off, m_total, tgt_off, ws, ws_bytes, 0, &b);
+    if (rc != LS_OK) return rc;
+    LS_REQUIRE((S || b.entries == 0) && (m0 || n_total == 0) && (m1 || m_total == 0), "%s: null argument", op);
+    if (b.greedy_lds > 48 * 1024)
+        for (int p = 0; p < P; ++p) {
+            const long long n = src_off[p + 1] - src_off[p], m = tgt_off[p + 1] - tgt_off[p];
+            LS_REQUIRE(greedy_class(n, m) != GREEDY_BLOCK || (size_t)(n + m) * sizeof(int) <= 48 * 1024, "%s: problem %d: n+m=%lld too large", op, p, n + m);
+        }
+    rc = b.upload(st);
+    if (rc != LS_OK) return rc;
+    for (int c = 0; c < GREEDY_CLASSES; ++c) {   // at most one launch per class; empty problems ride in the one-wave class
+        if (b.cls_count[c] == 0) continue;
+        RaggedProblems L = b.L;
+        L.ids = b.L.offs + (size_t)MOFF_ARRAYS * (P + 1) + b.cls_first[c];
+        rc = greedy_match_run(L, c, b.cls_count[c], b.greedy_lds, S, m0, m1, st);
+        if (rc != LS_OK) return rc;
+    }
+    return LS_OK;
+}
+
+int assign_batch_launch(int P, const float* S, long long n_total, const long long* src_off, long long m_total, const long long* tgt_off, int mode,
+                        float div, float alpha, int iters, float thr, long long* m0, long long* m1, void* ws, size_t ws_bytes, hipStream_t st) {
+    const char* op = mode ? "sinkhorn_match_batch" : "nn_match_batch";
+    Batch b;
+    int rc = batch_setup(op, P, n_total, src_off, m_total, tgt_off, ws, ws_bytes, 0, &b);
+    if (rc != LS_OK) return rc;
+    LS_REQUIRE((S || b.entries == 0) && (m0 || n_total == 0) && (m1 || m_total == 0), "%s: null argument", op);
+    size_t lds = 0;   // of the largest problem
+    for (int p = 0; p < P; ++p) {
+        const int n = (int)(src_off[p + 1] - src_off[p]), m = (int)(tgt_off[p + 1] - tgt_off[p]);
+        if (n == 0 || m == 0) continue;
+        const size_t need = assign_lds_bytes(n, m, mode);
+        LS_REQUIRE(need <= ASSIGN_LDS_MAX, "%s: problem %d: a %d x %d problem needs %zu bytes of LDS (at most 153600: about 190 x 190)", op, p, n, m, need);
+        lds = std::max(lds, need);
+    }
+    rc = b.upload(st);
+    if (rc != LS_OK) return rc;
+    return assign_run(b.L, P, lds, S, mode, div, alpha, iters, thr, m0, m1, st);
+}
+
+int kabsch_residual_matrix_batch_launch(int P, const float* src, long long n_total, const long long* src_off, const float* tgt, long long m_total,
+                                        const long long* tgt_off, int C, float* res, void* ws, size_t ws_bytes, hipStream_t st) {
+    const char* op = "kabsch_residual_matrix_batch";
+    LS_REQUIRE(C > 0, "%s: C = %d", op, C);
+    Batch b;
+    int rc = batch_setup(op, P, n_total, src_off, m_total, tgt_off, ws, ws_bytes, 0, &b);
+    if (rc != LS_OK) return rc;
+    if (b.entries == 0) return LS_OK;
+    LS_REQUIRE(src && tgt && res, "%s: null argument", op);
+    rc = b.upload(st);
+    if (rc != LS_OK) return rc;
+    hipLaunchKernelGGL(kabsch_kernel<RaggedProblems>, dim3(cdiv(b.entries, 4)), dim3(256), 0, st, b.L, src, tgt, (const float*)nullptr, (int)b.entries,
+                       C, 1, 0, 1e-7f, (float*)nullptr, (float*)nullptr, (float*)nullptr, res, (int32_t*)nullptr, (const float*)nullptr,
+                       (const float*)nullptr, (const long long*)nullptr, (const long long*)nullptr);
     LS_LAUNCH_CHECK();
     return LS_OK;
 }

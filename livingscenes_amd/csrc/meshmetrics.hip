@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "ls_common.h"
+#include "ls_ragged.h"
 #include "ls_scan.h"
 
 // bit-identity with numpy's float64 arithmetic: no contraction of a * b + c into an fma anywhere in this file
@@ -137,16 +138,7 @@ static void scan(const In* x, long long n, T* blk, T* out, long long* total_out,
 // the mesh's first distance-grid cell (distance) or first scan block (sampler), OFF_AXIS the cells per axis of its distance grid at most.
 enum { OFF_V = 0, OFF_F, OFF_P, OFF_AUX, OFF_AXIS, OFF_ARRAYS };
 
-// the mesh m with off[m] <= i < off[m + 1] (i < off[M]; meshes with an empty range are never the owner)
-__device__ __forceinline__ int owner(const long long* __restrict__ off, int M, long long i) {
-    int lo = 0, hi = M - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= i) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
+// owner(off, M, i) (ls_ragged.h): the mesh m with off[m] <= i < off[m + 1]; meshes with an empty range are never the owner
 
 __host__ __device__ inline unsigned long long splitmix_mix(unsigned long long z) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -783,14 +775,7 @@ int sample_launch(const Meshes& L, int M, long long nf, int nblk, long long coun
 
 // off[0] = 0, never decreasing, at most per_max per mesh, ending at total
 int check_ranges(const char* op, const char* what, int M, const long long* off, long long total, long long per_max) {
-    LS_REQUIRE(off, "%s: null %s", op, what);
-    LS_REQUIRE(off[0] == 0, "%s: %s[0] is %lld, not 0", op, what, off[0]);
-    for (int m = 0; m < M; ++m) {
-        LS_REQUIRE(off[m + 1] >= off[m], "%s: mesh %d: %s decreases (%lld -> %lld)", op, m, what, off[m], off[m + 1]);
-        LS_REQUIRE(off[m + 1] - off[m] <= per_max, "%s: mesh %d: %lld rows in %s, at most %lld per mesh", op, m, off[m + 1] - off[m], what, per_max);
-    }
-    LS_REQUIRE(off[M] == total, "%s: mesh %d: %s ends at %lld, which disagrees with the total %lld", op, M - 1, what, off[M], total);
-    return LS_OK;
+    return ls::check_ranges(op, "mesh", what, M, off, total, per_max);
 }
 
 // the argument checks of the single-mesh ops, per mesh
@@ -809,14 +794,10 @@ int check_meshes(const char* op, int M, const double* V, long long nv_total, con
     return LS_OK;
 }
 
-// the device copy of the offsets (aux, axis: nullable, zeros)
+// the device copy of the offsets (aux, axis: nullable, zeros), in the order of OFF_*
 std::vector<long long> pack_offsets(int M, const long long* vert_off, const long long* face_off, const long long* pt_off, const long long* aux,
                                     const long long* axis) {
-    std::vector<long long> o((size_t)OFF_ARRAYS * (M + 1), 0);
-    const long long* src[OFF_ARRAYS] = {vert_off, face_off, pt_off, aux, axis};
-    for (int k = 0; k < OFF_ARRAYS; ++k)
-        if (src[k]) std::copy(src[k], src[k] + M + 1, o.begin() + (size_t)k * (M + 1));
-    return o;
+    return ls::pack_offsets(M, {vert_off, face_off, pt_off, aux, axis});
 }
 
 // cells per axis of a mesh's distance grid in a batch: the largest a <= DIST_GRID_AXIS with a^3 <= 8 nf, at least 1 -- so the grids of
@@ -954,9 +935,8 @@ int ls_mesh_contains_batch_f64(int M, const double* vertices, long long nv_total
         return LS_ERR_WORKSPACE;
     }
     const BinWs w = bin_layout((char*)workspace, n_offs(M), M, nf_total, (long long)M * R * R, sizeof(Cells2), nullptr);
-    // pageable host memory: the copy has read the offsets when it returns
-    const std::vector<long long> offs = pack_offsets(M, vert_off, face_off, pt_off, nullptr, nullptr);
-    LS_HIP_CHECK(hipMemcpyAsync(w.offs, offs.data(), offs.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+    rc = upload_offsets(w.offs, pack_offsets(M, vert_off, face_off, pt_off, nullptr, nullptr), st);
+    if (rc != LS_OK) return rc;
     return contains_launch(RaggedMeshes{vertices, faces, w.offs, M, nf_total, n_total, nullptr}, M, nf_total, points, n_total, R, w, inside_out,
                            entries, cap_entries, count_out, st);
 }
@@ -1000,8 +980,8 @@ int ls_mesh_distance_batch_f64(int M, const double* vertices, long long nv_total
     }
     const long long cells = cell_off[M];   // <= 8 nf_total + M
     const BinWs w = bin_layout((char*)workspace, n_offs(M), M, nf_total, cells, sizeof(Cells3), nullptr);
-    const std::vector<long long> offs = pack_offsets(M, vert_off, face_off, pt_off, cell_off.data(), axis.data());
-    LS_HIP_CHECK(hipMemcpyAsync(w.offs, offs.data(), offs.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+    rc = upload_offsets(w.offs, pack_offsets(M, vert_off, face_off, pt_off, cell_off.data(), axis.data()), st);
+    if (rc != LS_OK) return rc;
     return distance_launch(RaggedMeshes{vertices, faces, w.offs, M, nf_total, n_total, nullptr}, M, nf_total, points, n_total, max_dist, cells, w,
                            dist_out, entries, cap_entries, count_out, st);
 }
@@ -1037,8 +1017,8 @@ int ls_mesh_sample_batch_f64(int M, const double* vertices, long long nv_total, 
     }
     hipStream_t st = (hipStream_t)stream;
     const SampleWs w = sample_layout((char*)workspace, n_offs(M), nf_total, scan_blocks(nf_total) + M, nullptr);
-    const std::vector<long long> offs = pack_offsets(M, vert_off, face_off, count_off, blk_off.data(), nullptr);
-    LS_HIP_CHECK(hipMemcpyAsync(w.offs, offs.data(), offs.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+    rc = upload_offsets(w.offs, pack_offsets(M, vert_off, face_off, count_off, blk_off.data(), nullptr), st);
+    if (rc != LS_OK) return rc;
     return sample_launch(RaggedMeshes{vertices, faces, w.offs, M, nf_total, count_total, seeds}, M, nf_total, (int)blk_off[M], count_total, w,
                          points_out, face_out, st);
 }

@@ -93,6 +93,14 @@ int greedy_match_launch(float*, int, int, long long*, long long*, hipStream_t);
 int assign_launch(const float*, int, int, int, float, float, int, float, long long*, long long*, hipStream_t);
 int kabsch_launch(const float*, const float*, const float*, int, int, int, int, float*, float*, float*, float*, int32_t*, hipStream_t,
                   const float* off1 = nullptr, const float* off2 = nullptr, const long long* sel1 = nullptr, const long long* sel2 = nullptr);
+size_t match_batch_workspace_bytes(int P, long long n_total, long long m_total, int with_norms);
+int cosine_scores_batch_launch(int, const float*, long long, const long long*, const float*, long long, const long long*, int, float*, void*, size_t,
+                               hipStream_t);
+int greedy_match_batch_launch(int, float*, long long, const long long*, long long, const long long*, long long*, long long*, void*, size_t, hipStream_t);
+int assign_batch_launch(int, const float*, long long, const long long*, long long, const long long*, int, float, float, int, float, long long*,
+                        long long*, void*, size_t, hipStream_t);
+int kabsch_residual_matrix_batch_launch(int, const float*, long long, const long long*, const float*, long long, const long long*, int, float*, void*,
+                                        size_t, hipStream_t);
 size_t icp_workspace_bytes(int b, int n);
 int icp_run(const float*, const float*, const float*, const float*, int, int, int, int, float, unsigned, float*, float*, float*,
             int32_t*, void*, size_t, hipStream_t);
@@ -627,6 +635,42 @@ int ls_kabsch_codes_f32(const float* x1, const float* off1, const int64_t* sel1,
 int ls_kabsch_residual_matrix_f32(const float* src, const float* tgt, int n, int m, int P, float* res, void* stream) {
     LS_REQUIRE(n > 0 && m > 0 && P > 0, "kabsch_residual_matrix: empty problem");
     return kabsch_launch(src, tgt, nullptr, n * m, P, m, 0, nullptr, nullptr, nullptr, res, nullptr, (hipStream_t)stream);
+}
+// ---- ragged batches of matching problems (match.hip): every problem's result is bit-identical to the single op on that problem alone
+size_t ls_cosine_scores_batch_workspace_bytes(int P, long long n_total, long long m_total) { return match_batch_workspace_bytes(P, n_total, m_total, 1); }
+size_t ls_greedy_match_batch_workspace_bytes(int P, long long n_total, long long m_total) { return match_batch_workspace_bytes(P, n_total, m_total, 0); }
+size_t ls_nn_match_batch_workspace_bytes(int P, long long n_total, long long m_total) { return match_batch_workspace_bytes(P, n_total, m_total, 0); }
+size_t ls_sinkhorn_match_batch_workspace_bytes(int P, long long n_total, long long m_total) {
+    return match_batch_workspace_bytes(P, n_total, m_total, 0);
+}
+size_t ls_kabsch_residual_matrix_batch_workspace_bytes(int P, long long n_total, long long m_total) {
+    return match_batch_workspace_bytes(P, n_total, m_total, 0);
+}
+int ls_cosine_scores_batch_f32(int P, const float* m0, long long n_total, const long long* src_off, const float* m1, long long m_total,
+                               const long long* tgt_off, int D, float* scores, void* workspace, size_t workspace_bytes, void* stream) {
+    return cosine_scores_batch_launch(P, m0, n_total, src_off, m1, m_total, tgt_off, D, scores, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int ls_greedy_match_batch_f32(int P, float* scores, long long n_total, const long long* src_off, long long m_total, const long long* tgt_off,
+                              int64_t* matches0, int64_t* matches1, void* workspace, size_t workspace_bytes, void* stream) {
+    return greedy_match_batch_launch(P, scores, n_total, src_off, m_total, tgt_off, (long long*)matches0, (long long*)matches1, workspace,
+                                     workspace_bytes, (hipStream_t)stream);
+}
+int ls_nn_match_batch_f32(int P, const float* scores, long long n_total, const long long* src_off, long long m_total, const long long* tgt_off,
+                          int64_t* matches0, int64_t* matches1, void* workspace, size_t workspace_bytes, void* stream) {
+    return assign_batch_launch(P, scores, n_total, src_off, m_total, tgt_off, 0, 1.0f, 0.0f, 0, 0.0f, (long long*)matches0, (long long*)matches1,
+                               workspace, workspace_bytes, (hipStream_t)stream);
+}
+int ls_sinkhorn_match_batch_f32(int P, const float* scores, long long n_total, const long long* src_off, long long m_total, const long long* tgt_off,
+                                float score_divisor, float alpha, int iters, float match_threshold, int64_t* matches0, int64_t* matches1,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    LS_REQUIRE(iters >= 0 && score_divisor != 0.0f, "sinkhorn_match_batch: iters=%d score_divisor=%g", iters, (double)score_divisor);
+    return assign_batch_launch(P, scores, n_total, src_off, m_total, tgt_off, 1, score_divisor, alpha, iters, match_threshold, (long long*)matches0,
+                               (long long*)matches1, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int ls_kabsch_residual_matrix_batch_f32(int P, const float* src, long long n_total, const long long* src_off, const float* tgt, long long m_total,
+                                        const long long* tgt_off, int C, float* res, void* workspace, size_t workspace_bytes, void* stream) {
+    return kabsch_residual_matrix_batch_launch(P, src, n_total, src_off, tgt, m_total, tgt_off, C, res, workspace, workspace_bytes,
+                                               (hipStream_t)stream);
 }
 size_t ls_icp_workspace_bytes(int b, int n) { return icp_workspace_bytes(b, n); }
 int ls_icp_f32(const float* X, const float* Y, const float* R0, const float* T0, int b, int n, int m, int max_iter,

@@ -18,10 +18,12 @@ def scene_recall(ratios):
 
 
 @torch.no_grad()
-def eval_matching(scenes, solver, method="sequential"):
-    """scenes: list of dicts from synth.make_scene_pair.  -> metrics dict (eval_flyingshape.py:62-107)."""
+def eval_matching(scenes, solver, method="sequential", batched=False):
+    """scenes: list of dicts from synth.make_scene_pair.  -> metrics dict (eval_flyingshape.py:62-107).  batched=True: the scenes are
+    encoded as before, then matched in ONE solver._solve_object_matching_batch call (same metrics)."""
     n_correct = n_total = 0
     ratios = []
+    pending = []
     for sc in scenes:
         dev = next(solver.model.parameters()).device
         ref = sc["ref"].to(dev).transpose(1, 2).contiguous()
@@ -30,7 +32,11 @@ def eval_matching(scenes, solver, method="sequential"):
         code = solver.model.encode(torch.cat([ref, res], 0))
         cr = {k: v[:n] for k, v in code.items()}
         cs = {k: v[n:] for k, v in code.items()}
-        m = solver._solve_object_matching(cr, cs, method)["matches0"]
+        pending.append((cr, cs) if batched else solver._solve_object_matching(cr, cs, method)["matches0"])
+    if batched and pending:
+        pending = [r["matches0"] for r in solver._solve_object_matching_batch([cr for cr, _ in pending], [cs for _, cs in pending], method)]
+    for sc, m in zip(scenes, pending):
+        n = sc["ref"].shape[0]
         ok = int((m == torch.arange(n, device=m.device)).sum())
         n_correct += ok
         n_total += n
@@ -91,11 +97,13 @@ def disambiguate(pred_ids, gt_ids, ambiguity, max_hops=200):
 
 
 @torch.no_grad()
-def eval_3rscan_matching(dataset, solver, method_list=("sequential",)):
+def eval_3rscan_matching(dataset, solver, method_list=("sequential",), batched=False):
     """Object matching between the reference scan and every rescan of each scene of a ``rscan.Dataset_3RScan``
     (eval_3rscan.py:232-335): object-level recall over the instances present in both scans (all / static / dynamic, the split
     coming from the rescan's rigid annotations), and scene-level recall = share of (scene, rescan) pairs whose hit ratio reaches
-    75 / 50 / 25 %.  Codes come from ``model.encode_fps`` on the padded clouds, matches from ``solver._solve_object_matching``."""
+    75 / 50 / 25 %.  Codes come from ``model.encode_fps`` on the padded clouds, matches from ``solver._solve_object_matching``.
+    batched=True: the codes of every (scene, rescan) are collected first, then each method matches all of them in ONE
+    ``solver._solve_object_matching_batch`` call (same metrics)."""
     model = solver.model
     n_methods = len(method_list)
     n_total = 0
@@ -103,6 +111,36 @@ def eval_3rscan_matching(dataset, solver, method_list=("sequential",)):
     scene_total = np.zeros(3)
     scene_count = np.zeros(3)      # hits @75, @50, @25
     tot_dyn = cor_dyn = tot_sta = cor_sta = 0
+
+    def score(scene, ref_ids, rescan, m0s):    # m0s: the matches0 of every method for this (scene, rescan)
+        nonlocal n_total, scene_total, tot_dyn, cor_dyn, tot_sta, cor_sta
+        res_ids = rescan["objectId"]
+        moving = set(int(v) for v in rescan["moving_ids"].tolist())
+        valid = torch.tensor([int(i) in set(res_ids.tolist()) for i in ref_ids.tolist()], device=ref_ids.device)
+        moving_mask = torch.tensor([int(i) in moving for i in ref_ids.tolist()], device=ref_ids.device)
+        for mi, method in enumerate(method_list):
+            m0 = m0s[mi].to(ref_ids.device)
+            matched = res_ids[m0.clamp(min=0)]
+            if len(scene.get("ambiguity", [])) != 0:
+                matched = disambiguate(matched.view(-1), ref_ids, scene["ambiguity"])
+            matched = torch.where(m0 != -1, matched, torch.full_like(matched, -1))
+            hit = matched == ref_ids
+            n_match = int(valid.sum())
+            ok = int(hit[valid].sum())
+            n_correct[mi] += ok
+            n_total += n_match
+            scene_total += 1
+            ratio = ok / n_match if n_match else 0.0
+            if ratio >= 0.75:
+                scene_count[:] += 1
+            elif ratio >= 0.5:
+                scene_count[1:] += 1
+            elif ratio >= 0.25:
+                scene_count[2:] += 1
+            tot_dyn += int((valid & moving_mask).sum()); cor_dyn += int(hit[valid & moving_mask].sum())
+            tot_sta += int((valid & ~moving_mask).sum()); cor_sta += int(hit[valid & ~moving_mask].sum())
+
+    pending = []   # batched: (scene, ref ids, rescan, ref codes, rescan codes) of every (scene, rescan)
     for i_s, scene in enumerate(dataset.scene_list):
         ref, rescans = dataset._get_scene(i_s)
         if ref is None or len(rescans) == 0:
@@ -111,31 +149,14 @@ def eval_3rscan_matching(dataset, solver, method_list=("sequential",)):
         ref_ids = ref["objectId"]
         for rescan in rescans:
             codes = model.encode_fps(rescan["pc"], rescan["pc_mask"])
-            res_ids = rescan["objectId"]
-            moving = set(int(v) for v in rescan["moving_ids"].tolist())
-            valid = torch.tensor([int(i) in set(res_ids.tolist()) for i in ref_ids.tolist()], device=ref_ids.device)
-            moving_mask = torch.tensor([int(i) in moving for i in ref_ids.tolist()], device=ref_ids.device)
-            for mi, method in enumerate(method_list):
-                m0 = solver._solve_object_matching(ref_codes, codes, method)["matches0"].to(ref_ids.device)
-                matched = res_ids[m0.clamp(min=0)]
-                if len(scene.get("ambiguity", [])) != 0:
-                    matched = disambiguate(matched.view(-1), ref_ids, scene["ambiguity"])
-                matched = torch.where(m0 != -1, matched, torch.full_like(matched, -1))
-                hit = matched == ref_ids
-                n_match = int(valid.sum())
-                ok = int(hit[valid].sum())
-                n_correct[mi] += ok
-                n_total += n_match
-                scene_total += 1
-                ratio = ok / n_match if n_match else 0.0
-                if ratio >= 0.75:
-                    scene_count[:] += 1
-                elif ratio >= 0.5:
-                    scene_count[1:] += 1
-                elif ratio >= 0.25:
-                    scene_count[2:] += 1
-                tot_dyn += int((valid & moving_mask).sum()); cor_dyn += int(hit[valid & moving_mask].sum())
-                tot_sta += int((valid & ~moving_mask).sum()); cor_sta += int(hit[valid & ~moving_mask].sum())
+            if batched:
+                pending.append((scene, ref_ids, rescan, ref_codes, codes))
+            else:
+                score(scene, ref_ids, rescan, [solver._solve_object_matching(ref_codes, codes, method)["matches0"] for method in method_list])
+    if pending:
+        per_method = [solver._solve_object_matching_batch([r[3] for r in pending], [r[4] for r in pending], method) for method in method_list]
+        for k, (scene, ref_ids, rescan, _, _) in enumerate(pending):
+            score(scene, ref_ids, rescan, [res[k]["matches0"] for res in per_method])
     per_method_total = n_total / max(n_methods, 1)
     pct = lambda a, b: 100.0 * a / b if b else float("nan")
     out = {f"object_recall[{m}]": pct(n_correct[i], per_method_total) for i, m in enumerate(method_list)}

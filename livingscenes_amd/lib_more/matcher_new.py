@@ -73,3 +73,51 @@ def sinkhorn_matcher(desc0, desc1, desc_dim=256, match_threshold=0.0):
     a, b = ops.sinkhorn_match(ops.cosine_scores(desc0[0].T.contiguous(), desc1[0].T.contiguous()), desc_dim ** 0.5, alpha=1.0, iters=100,
                               match_threshold=match_threshold)
     return {"matches0": a.squeeze(), "matches1": b.squeeze()}
+
+
+# ------------------------------------------------------------------------------------------------ many problems per call
+# The batched forms (an extension the reference lacks): lists in the calling convention of the single forms -> list of {'matches0',
+# 'matches1'}, entry p equal in values and shapes to the single function on problem p.  One ragged launch sequence per stage for all
+# problems (ls_*_batch_f32); a problem with no source or no target instances is allowed (every match -1).
+def _as_dicts(pairs, squeeze=False):
+    return [{"matches0": a.squeeze() if squeeze else a, "matches1": b.squeeze() if squeeze else b} for a, b in pairs]
+
+
+def sequential_matcher_batch(m0_list, m1_list):
+    """sequential_matcher on every (m0_list[p], m1_list[p])."""
+    S, sizes = ops.cosine_scores_batch(m0_list, m1_list, packed=True)
+    return _as_dicts(ops.greedy_match_batch(S, sizes))
+
+
+def _residuals_batch(src_codes_list, tgt_codes_list):
+    return ops.kabsch_residual_matrix_batch([c["z_so3"].detach() for c in src_codes_list], [c["z_so3"].detach() for c in tgt_codes_list], packed=True)
+
+
+def sim3_seq_matcher_batch(src_codes_list, tgt_codes_list):
+    """sim3_seq_matcher on every (src_codes_list[p], tgt_codes_list[p])."""
+    sim, sizes = ops.cosine_scores_batch([c["z_inv"].detach() for c in src_codes_list], [c["z_inv"].detach() for c in tgt_codes_list], packed=True)
+    res, _ = _residuals_batch(src_codes_list, tgt_codes_list)
+    return _as_dicts(ops.greedy_match_batch(sim / (res + 1e-5), sizes))
+
+
+def eq_seq_matcher_batch(src_codes_list, tgt_codes_list):
+    """eq_seq_matcher on every (src_codes_list[p], tgt_codes_list[p])."""
+    res, sizes = _residuals_batch(src_codes_list, tgt_codes_list)
+    return _as_dicts(ops.greedy_match_batch(1 / (res + 1e-5), sizes))
+
+
+def _desc_scores_batch(desc0_list, desc1_list):
+    """cosine scores of descriptors in the reference's transposed convention [1,D,n]"""
+    return ops.cosine_scores_batch([d[0].T for d in desc0_list], [d[0].T for d in desc1_list], packed=True)
+
+
+def nn_matcher_batch(desc0_list, desc1_list):
+    """nn_matcher on every (desc0_list[p], desc1_list[p]), desc [1,D,n]."""
+    S, sizes = _desc_scores_batch(desc0_list, desc1_list)
+    return _as_dicts(ops.nn_match_batch(S, sizes), squeeze=True)
+
+
+def sinkhorn_matcher_batch(desc0_list, desc1_list, desc_dim=256, match_threshold=0.0):
+    """sinkhorn_matcher on every (desc0_list[p], desc1_list[p]); desc_dim and match_threshold hold for the whole batch."""
+    S, sizes = _desc_scores_batch(desc0_list, desc1_list)
+    return _as_dicts(ops.sinkhorn_match_batch(S, desc_dim ** 0.5, alpha=1.0, iters=100, match_threshold=match_threshold, sizes=sizes), squeeze=True)

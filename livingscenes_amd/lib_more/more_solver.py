@@ -13,7 +13,8 @@ from .. import ops
 from ..lib_math.torch_se3 import Rt_to_SE3, inverse, transform
 from ..mesh_extractor2 import Generator3D as Generator3D_MC
 from ..model_utils import fps, load_ckpt_from_log, mesh_from_latent, place_mesh
-from .matcher_new import eq_seq_matcher, nn_matcher, sequential_matcher, sim3_seq_matcher, sinkhorn_matcher
+from .matcher_new import (eq_seq_matcher, eq_seq_matcher_batch, nn_matcher, nn_matcher_batch, sequential_matcher, sequential_matcher_batch,
+                          sim3_seq_matcher, sim3_seq_matcher_batch, sinkhorn_matcher, sinkhorn_matcher_batch)
 from .pose_estimation import kabsch_transformation_estimation
 
 
@@ -44,6 +45,25 @@ class More_Solver:
             return sim3_seq_matcher(src_codes, tgt_codes)
         if method == "eq_seq":
             return eq_seq_matcher(src_codes, tgt_codes)
+
+    def _solve_object_matching_batch(self, src_codes_list, tgt_codes_list, method):
+        """_solve_object_matching for MANY scene pairs in one ragged call per stage (the reference matches one pair at a time):
+        -> list of {'matches0', 'matches1'}, entry p equal to _solve_object_matching(src_codes_list[p], tgt_codes_list[p], method)."""
+        if len(src_codes_list) != len(tgt_codes_list):
+            raise ValueError(f"{len(src_codes_list)} source scenes for {len(tgt_codes_list)} target scenes")
+        if not src_codes_list:
+            return []
+        if method in ("nn", "sinkhorn"):
+            inv_src = [c["z_inv"].detach().T[None] for c in src_codes_list]
+            inv_tgt = [c["z_inv"].detach().T[None] for c in tgt_codes_list]
+            return nn_matcher_batch(inv_src, inv_tgt) if method == "nn" else sinkhorn_matcher_batch(inv_src, inv_tgt)
+        if method == "sequential":
+            return sequential_matcher_batch([c["z_inv"].detach() for c in src_codes_list], [c["z_inv"].detach() for c in tgt_codes_list])
+        if method == "sim3_seq":
+            return sim3_seq_matcher_batch(src_codes_list, tgt_codes_list)
+        if method == "eq_seq":
+            return eq_seq_matcher_batch(src_codes_list, tgt_codes_list)
+        raise ValueError(f"unknown matching method {method!r}")
 
     # -------------------------------------------------------------------------------------------- registration
     def _register_from_codes(self, code1, code2):
@@ -314,13 +334,15 @@ def _scene_clouds(scene):
     return [pc.T[mask.reshape(-1).bool()] for pc, mask in zip(scene["pc"], scene["pc_mask"])]
 
 
-def solve_end2end_batch(solver, pairs, mesh=False, optim=False, sharded=False, optim_chunk=128):
+def solve_end2end_batch(solver, pairs, mesh=False, optim=False, sharded=False, optim_chunk=128, match_batched=False):
     """Batched form of More_Solver._solve_end2end over MANY (reference scan, rescan) pairs -- an extension the reference lacks
     (eval_3rscan.py walks the scenes one pair at a time): every scan of every pair goes through ONE ragged FPS launch and ONE
     encoder batch, every matched pair of every scene through ONE registration batch (ragged FPS, encode, Kabsch, ICP; optim=True:
     the 400-step refinement in lock-step, optim_chunk pairs per call).  The ragged FPS runs one workgroup per raw cloud (18 ms for a
     60 000-point cloud), so a single scene pair leaves the GPU idle; hundreds of clouds per launch fill it.  Returns one dict per
-    pair, as _solve_end2end.
+    pair, as _solve_end2end.  match_batched=True: the matcher of all scene pairs is ONE batched call as well
+    (solver._solve_object_matching_batch) with one host read of the packed matches; the default calls solver._solve_object_matching
+    per scene pair.  Same results either way.
 
     sharded=True (one process per GPU, torch.distributed initialised; SURVEY.md 8e, eval_3rscan.py:337-463 sharded over the node):
     the flat (scene, instance) list is block-partitioned over the ranks for FPS + encode and the codes all-gathered (4.1 KB each);
@@ -349,14 +371,25 @@ def solve_end2end_batch(solver, pairs, mesh=False, optim=False, sharded=False, o
     for cl in clouds:
         starts.append(starts[-1] + len(cl))
     outs, reg1, reg2, slots = [], [], [], []
+    scene_codes = [({k: v[starts[a]:starts[a + 1]] for k, v in codes.items()}, {k: v[starts[b]:starts[b + 1]] for k, v in codes.items()})
+                   for a, b in where]
+    if match_batched:   # (sharded: replicated on every rank, like the per-scene matchers)
+        all_m0 = [m["matches0"] for m in solver._solve_object_matching_batch([cr for cr, _ in scene_codes], [cs for _, cs in scene_codes],
+                                                                             "sequential")]
+        flat_m0 = torch.cat([m.reshape(-1) for m in all_m0]).tolist() if all_m0 else []     # the one host read of the matcher leg
+    taken = 0
     for p, (a, b) in enumerate(where):
-        cr = {k: v[starts[a]:starts[a + 1]] for k, v in codes.items()}
-        cs = {k: v[starts[b]:starts[b + 1]] for k, v in codes.items()}
-        m0 = solver._solve_object_matching(cr, cs, "sequential")["matches0"]
+        cr, cs = scene_codes[p]
         n = len(clouds[a])
+        if match_batched:
+            m0, m0_host = all_m0[p], flat_m0[taken:taken + n]
+            taken += n
+        else:
+            m0 = solver._solve_object_matching(cr, cs, "sequential")["matches0"]
+            m0_host = m0.tolist()
         out = {"ref_pc_lst": clouds[a], "rescan_pc_lst": clouds[b], "matches": m0, "registration": [None] * n, "codes": [None] * n,
                "mesh_lst": [None] * n, "_res_codes": cs}
-        for i, j in enumerate(m0.tolist()):
+        for i, j in enumerate(m0_host):
             if j >= 0:
                 reg1.append(clouds[a][i]); reg2.append(clouds[b][j]); slots.append((p, i, j))
         outs.append(out)

@@ -163,6 +163,132 @@ def sinkhorn_match(scores, score_divisor, alpha=1.0, iters=100, match_threshold=
     return m0, m1
 
 
+# ---- ragged batches of matching problems (ls_*_batch_f32): one call for P problems, every problem's result bit-identical to the single form.
+# Offsets come from shapes (sizes), never from the device.  A problem with n == 0 or m == 0 is allowed: no scores, every match -1.
+def _match_sizes(sizes):
+    sizes = [(int(n), int(m)) for n, m in sizes]
+    if any(n < 0 or m < 0 for n, m in sizes):
+        raise ValueError(f"negative problem size in {sizes}")
+    return sizes
+
+
+def _match_offsets(sizes):
+    return _offsets([n for n, _ in sizes]), _offsets([m for _, m in sizes])
+
+
+def _pack_rows(x, sizes, side, what):
+    """list of [rows_p, ...] tensors, or a packed [rows_total, ...] tensor whose rows `sizes` divides -> (packed float32 contiguous, sizes of the side)"""
+    if torch.is_tensor(x):
+        if sizes is None:
+            raise ValueError(f"{what}: a packed tensor needs sizes=[(n_p, m_p), ...]")
+        rows = [s[side] for s in _match_sizes(sizes)]
+        if x.shape[0] != sum(rows):
+            raise ValueError(f"{what}: {x.shape[0]} packed rows, the sizes add up to {sum(rows)}")
+        return _f32(x), rows
+    xs = list(x)
+    if not xs:
+        raise ValueError(f"{what}: empty list of problems")
+    tails = {tuple(t.shape[1:]) for t in xs}
+    if len(tails) != 1:
+        raise ValueError(f"{what}: the problems of one call share their row shape (descriptor width), got {sorted(tails)}")
+    return _f32(torch.cat([_f32(t) for t in xs], 0)), [t.shape[0] for t in xs]
+
+
+def _pack_scores(scores, sizes, what, copy=False):
+    """list of [n_p, m_p] score matrices, or a packed 1-D tensor plus sizes -> (packed float32 [sum n_p m_p], sizes)"""
+    if torch.is_tensor(scores):
+        if sizes is None:
+            raise ValueError(f"{what}: packed scores need sizes=[(n_p, m_p), ...]")
+        sizes = _match_sizes(sizes)
+        S = _f32(scores.reshape(-1))
+        if S.numel() != sum(n * m for n, m in sizes):
+            raise ValueError(f"{what}: {S.numel()} packed scores, the sizes add up to {sum(n * m for n, m in sizes)}")
+        return (S.clone() if copy and S.data_ptr() == scores.data_ptr() else S), sizes
+    mats = list(scores)
+    if not mats:
+        raise ValueError(f"{what}: empty list of problems")
+    if any(t.dim() != 2 for t in mats):
+        raise ValueError(f"{what}: every problem's scores are a matrix [n, m]")
+    return torch.cat([_f32(t).reshape(-1) for t in mats], 0), [tuple(t.shape) for t in mats]     # (cat: always a new tensor)
+
+
+def _split_scores(S, sizes):
+    """packed scores -> per-problem [n_p, m_p] views"""
+    return [part.view(n, m) for part, (n, m) in zip(torch.split(S, [n * m for n, m in sizes]), sizes)]
+
+
+def _split_matches(m0, m1, sizes):
+    return list(zip(torch.split(m0, [n for n, _ in sizes]), torch.split(m1, [m for _, m in sizes])))
+
+
+def _match_batch_call(name, dev, sizes, head_of, outs):
+    """workspace query + the call: head_of(n_total, so, m_total, to) -> the arguments between P and the outputs"""
+    P = len(sizes)
+    so, to = _match_offsets(sizes)
+    nt, mt = int(so[-1]), int(to[-1])
+    ws = _scratch(getattr(load(), name.replace("_f32", "_workspace_bytes"))(P, nt, mt), dev)
+    call(dev, name, P, *head_of(nt, _hptr(so), mt, _hptr(to)), *[ptr(o) for o in outs], ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev))
+
+
+def cosine_scores_batch(m0, m1, sizes=None, packed=False):
+    """cosine_scores on P problems in one call: m0 / m1 = lists of [n_p, D] / [m_p, D] tensors, or packed [n_total, D] / [m_total, D] tensors
+    plus sizes = [(n_p, m_p), ...] -> list of P [n_p, m_p] views of one packed tensor (packed=True: that tensor and the sizes), problem p
+    bit-identical to cosine_scores(m0_p, m1_p)."""
+    M0, ns = _pack_rows(m0, sizes, 0, "cosine_scores_batch")
+    M1, ms = _pack_rows(m1, sizes, 1, "cosine_scores_batch")
+    if M0.dim() != 2 or M1.dim() != 2 or M0.shape[1] != M1.shape[1]:
+        raise ValueError(f"cosine_scores_batch: descriptors [n, D] of one width on both sides, got {tuple(M0.shape)} and {tuple(M1.shape)}")
+    if len(ns) != len(ms):
+        raise ValueError(f"cosine_scores_batch: {len(ns)} source sets for {len(ms)} target sets")
+    sizes = list(zip(ns, ms))
+    S = torch.empty(sum(n * m for n, m in sizes), dtype=torch.float32, device=M0.device)
+    _match_batch_call("ls_cosine_scores_batch_f32", M0.device, sizes,
+                      lambda nt, so, mt, to: (ptr(M0), nt, so, ptr(M1), mt, to, M0.shape[1]), [S])
+    return (S, sizes) if packed else _split_scores(S, sizes)
+
+
+def _assign_batch(name, scores, sizes, extra, copy):
+    S, sizes = _pack_scores(scores, sizes, name, copy=copy)
+    dev = S.device
+    m0 = torch.empty(sum(n for n, _ in sizes), dtype=torch.int64, device=dev)
+    m1 = torch.empty(sum(m for _, m in sizes), dtype=torch.int64, device=dev)
+    _match_batch_call(name, dev, sizes, lambda nt, so, mt, to: (ptr(S), nt, so, mt, to) + tuple(extra), [m0, m1])
+    return _split_matches(m0, m1, sizes)
+
+
+def greedy_match_batch(scores, sizes=None):
+    """greedy_match on P problems in one call: scores = list of [n_p, m_p] matrices, or the packed scores plus sizes -> list of P
+    (matches0 [n_p], matches1 [m_p]) int64 views, indices local to the problem.  Works on its own copy: the caller's scores are untouched."""
+    return _assign_batch("ls_greedy_match_batch_f32", scores, sizes, (), copy=True)
+
+
+def nn_match_batch(scores, sizes=None):
+    """nn_match on P problems in one call (arguments and result as greedy_match_batch)."""
+    return _assign_batch("ls_nn_match_batch_f32", scores, sizes, (), copy=False)
+
+
+def sinkhorn_match_batch(scores, score_divisor, alpha=1.0, iters=100, match_threshold=0.0, sizes=None):
+    """sinkhorn_match on P problems in one call; score_divisor, alpha, iters and match_threshold hold for the whole batch."""
+    return _assign_batch("ls_sinkhorn_match_batch_f32", scores, sizes, (float(score_divisor), float(alpha), int(iters), float(match_threshold)),
+                         copy=False)
+
+
+def kabsch_residual_matrix_batch(src, tgt, sizes=None, packed=False):
+    """kabsch_residual_matrix on P problems in one call: src / tgt = lists of [n_p, C, 3] / [m_p, C, 3] tensors, or packed tensors plus sizes
+    -> list of P [n_p, m_p] views of one packed tensor (packed=True: that tensor and the sizes)."""
+    A, ns = _pack_rows(src, sizes, 0, "kabsch_residual_matrix_batch")
+    B, ms = _pack_rows(tgt, sizes, 1, "kabsch_residual_matrix_batch")
+    if A.dim() != 3 or A.shape[2] != 3 or A.shape[1:] != B.shape[1:]:
+        raise ValueError(f"kabsch_residual_matrix_batch: point sets [n, C, 3] of one C on both sides, got {tuple(A.shape)} and {tuple(B.shape)}")
+    if len(ns) != len(ms):
+        raise ValueError(f"kabsch_residual_matrix_batch: {len(ns)} source sets for {len(ms)} target sets")
+    sizes = list(zip(ns, ms))
+    res = torch.empty(sum(n * m for n, m in sizes), dtype=torch.float32, device=A.device)
+    _match_batch_call("ls_kabsch_residual_matrix_batch_f32", A.device, sizes,
+                      lambda nt, so, mt, to: (ptr(A), nt, so, ptr(B), mt, to, A.shape[1]), [res])
+    return (res, sizes) if packed else _split_scores(res, sizes)
+
+
 def kabsch(x1, x2, weights=None, return_flags=False, raw_weights=False):
     """x1,x2 [b,n,3] -> R [b,3,3], t [b,3,1], res [b,n] (, status [b] int32: _lib.KABSCH_*).  raw_weights: use `weights` as
     they are instead of normalising them (pose_estimation.py:52-54)."""
