@@ -23,7 +23,7 @@
 // Thread mapping: one wave per destination point, lanes = channels (coalesced 256-B row segments per
 // neighbour and xyz component), channel chunks of 64; attention heads are 16 consecutive channels = one
 // 16-lane DPP row, so head sums / soft-max reductions are 4-step row shuffles.
-#include "ls_common.h"
+#include "ls_launch.h"
 
 namespace ls {
 

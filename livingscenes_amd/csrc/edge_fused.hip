@@ -38,7 +38,7 @@
 // life, issue-stalled behind its own MFMAs 28 %, issuing 28 %; the matrix pipes are busy 20 % of the launch.  With 8 waves per CU (242 - 254 VGPRs, 52 - 69 KB
 // of LDS) nothing overlaps a workgroup's GEMM phase with another's attention phase except by chance; the structural remedy -- a persistent
 // workgroup per instance whose MFMA waves run one head group ahead of its VALU waves -- is the next step, not a tweak of this one.
-#include "ls_common.h"
+#include "ls_launch.h"
 
 namespace ls {
 

@@ -11,7 +11,7 @@
 //   * fps_block_kernel: 1024 threads per instance, min-distances in VGPRs (<= 64 per thread), points
 //     re-read from L2 each step, two-level (wave shuffle + LDS) arg-max.  Used for raw clouds up to 65536 pts.
 // Tie rule everywhere: larger value wins, equal values -> smaller index wins (== first arg-max).
-#include "ls_common.h"
+#include "ls_launch.h"
 
 namespace ls {
 
@@ -621,3 +621,15 @@ int fps_dispatch(const float* pts, const int32_t* lengths, int B, int N, int K, 
 }
 
 }  // namespace ls
+
+using namespace ls;
+extern "C" {
+size_t ls_fps_workspace_bytes(int B, int N, int K) {
+    (void)K;
+    return (B > 0 && N > 0) ? fps_scratch_bytes_per_cloud(N) * (size_t)B : 0;
+}
+int ls_fps_f32(const float* pts, const int32_t* lengths, int B, int N, int K, unsigned flags, int32_t* idx_out, float* pts_out,
+               void* workspace, size_t workspace_bytes, void* stream) {
+    return fps_dispatch(pts, lengths, B, N, K, flags, idx_out, pts_out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+}  // extern "C"

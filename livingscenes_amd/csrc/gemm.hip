@@ -25,7 +25,7 @@
 // that every lane fetches its four k-values with ONE ds_read_b128; A and B use the same permutation, so the
 // product is unchanged.  Next-tile global loads are issued before the MFMA block (register double buffer).
 #include <atomic>
-#include "ls_common.h"
+#include "ls_launch.h"
 #include <string.h>
 #include <algorithm>
 
@@ -2072,3 +2072,53 @@ int gemm_dispatch_small(const float* A, int lda, const float* W, int ldw, const 
 }
 
 }  // namespace ls
+
+using namespace ls;
+extern "C" {
+size_t ls_gemm_workspace_bytes(int M, int N, int K) {
+    return (M > 0 && N > 0 && K > 0 && K % 4 == 0) ? gemm_scratch_floats(M, N, K) * sizeof(float) : 0;
+}
+int ls_gemm_f32(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N, int K,
+                int relu, void* workspace, size_t workspace_bytes, void* stream) {
+    const size_t sb = (lda % 4 == 0 && ldw % 4 == 0) ? ls_gemm_workspace_bytes(M, N, K) : 0;
+    if (!sb) return gemm_dispatch(A, lda, W, ldw, bias, out, ldc, M, N, K, relu, (hipStream_t)stream);
+    if (sb > workspace_bytes || !workspace) {   // split-K slabs of an under-filled, long-K problem
+        set_error("gemm: workspace %zu < required %zu (ls_gemm_workspace_bytes)", workspace_bytes, sb);
+        return LS_ERR_WORKSPACE;
+    }
+    return gemm_dispatch_ws(A, lda, W, ldw, bias, out, ldc, M, N, K, relu, (float*)workspace, (hipStream_t)stream);
+}
+int ls_gemm_rowmax_parts(int N) { return N > 0 ? gemm_rowmax_parts(N) : 0; }
+int ls_gemm_f32_ex(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N, int K,
+                   int relu, const float* a_rowmax, int a_parts, const float* w_rowmax, float* out_rowmax, void* workspace,
+                   size_t workspace_bytes, void* stream) {
+    LS_REQUIRE(!a_rowmax || a_parts >= 1, "gemm_ex: a_rowmax needs a_parts >= 1");
+    GemmAux ax;
+    ax.a_rowmax = a_rowmax; ax.a_parts = a_rowmax ? a_parts : 0; ax.w_rowmax = w_rowmax; ax.out_rowmax = out_rowmax;
+    const size_t sb = (workspace && lda % 4 == 0 && ldw % 4 == 0) ? ls_gemm_workspace_bytes(M, N, K) : 0;
+    LS_REQUIRE(!(sb && out_rowmax), "gemm_ex: a split-K launch (M=%d N=%d K=%d with a workspace) writes no out_rowmax: pass workspace = NULL", M, N, K);
+    if (!sb) return gemm_dispatch(A, lda, W, ldw, bias, out, ldc, M, N, K, relu, (hipStream_t)stream, ax);
+    if (sb > workspace_bytes) { set_error("gemm_ex: workspace %zu < required %zu (ls_gemm_workspace_bytes)", workspace_bytes, sb); return LS_ERR_WORKSPACE; }
+    return gemm_dispatch_ws(A, lda, W, ldw, bias, out, ldc, M, N, K, relu, (float*)workspace, (hipStream_t)stream, ax);
+}
+int ls_rowmax_f32(const float* X, int rows, int K, int ld, float* out, void* stream) {
+    LS_REQUIRE(X && out && rows > 0 && K > 0 && ld >= K, "rowmax: bad argument");
+    return gemm_rowmax_launch(X, rows, K, ld, out, (hipStream_t)stream);
+}
+size_t ls_gemm_w_planes_bytes(int N, int K) { return (N > 0 && K > 0 && gemm_w_planes_useful(K)) ? gemm_w_planes_bytes((size_t)N, K) : 0; }
+int ls_gemm_presplit_w_f32(const float* W, int ldw, int N, int K, const float* w_rowmax, void* planes, size_t planes_bytes, void* stream) {
+    LS_REQUIRE(W && w_rowmax && planes && N > 0 && K > 0 && ldw >= K && ldw % 4 == 0, "gemm_presplit_w: bad argument");
+    LS_REQUIRE(gemm_w_planes_useful(K), "gemm_presplit_w: no kernel reads planes at K = %d (ls_gemm_w_planes_bytes returns 0)", K);
+    if (planes_bytes < gemm_w_planes_bytes((size_t)N, K)) { set_error("gemm_presplit_w: planes %zu < required %zu (ls_gemm_w_planes_bytes)", planes_bytes, gemm_w_planes_bytes((size_t)N, K)); return LS_ERR_WORKSPACE; }
+    return gemm_presplit_w_launch(W, N, K, ldw, w_rowmax, planes, (hipStream_t)stream);
+}
+int ls_gemm_f32_planes(const float* A, int lda, const float* W, int ldw, const void* w_planes, const float* bias, float* out, int ldc, int M, int N,
+                       int K, int relu, const float* a_rowmax, int a_parts, const float* w_rowmax, float* out_rowmax, void* stream) {
+    LS_REQUIRE(w_planes && w_rowmax, "gemm_planes: w_planes and w_rowmax are required (ls_gemm_presplit_w_f32)");
+    LS_REQUIRE(!a_rowmax || a_parts >= 1, "gemm_planes: a_rowmax needs a_parts >= 1");
+    LS_REQUIRE(gemm_w_planes_useful(K), "gemm_planes: no kernel reads planes at K = %d", K);
+    GemmAux ax;
+    ax.a_rowmax = a_rowmax; ax.a_parts = a_rowmax ? a_parts : 0; ax.w_rowmax = w_rowmax; ax.out_rowmax = out_rowmax; ax.w_planes = w_planes;
+    return gemm_dispatch(A, lda, W, ldw, bias, out, ldc, M, N, K, relu, (hipStream_t)stream, ax);
+}
+}  // extern "C"

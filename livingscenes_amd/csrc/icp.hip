@@ -163,20 +163,22 @@ __global__ __launch_bounds__(1024) void icp_kernel(const float* __restrict__ X, 
     }
 }
 
-size_t icp_workspace_bytes(int, int) { return 256; }
+}  // namespace ls
 
-int icp_run(const float* X, const float* Y, const float* R0, const float* T0, int b, int n, int m, int max_iter, float thr,
-            unsigned flags, float* R, float* T, float* rmse, int32_t* iters_out, void*, size_t, hipStream_t st) {
+using namespace ls;
+extern "C" {
+size_t ls_icp_workspace_bytes(int, int) { return 256; }
+int ls_icp_f32(const float* X, const float* Y, const float* R0, const float* T0, int b, int n, int m, int max_iter, float rel_rmse_thr,
+               unsigned flags, float* R, float* T, float* rmse, int32_t* iters_out, void*, size_t, void* stream) {
     LS_REQUIRE(b > 0 && n > 0 && m > 0 && max_iter > 0, "icp: empty problem");
     LS_REQUIRE(n <= 1024 * ICP_PT, "icp: source cloud too large (n=%d, max %d)", n, 1024 * ICP_PT);
     LS_REQUIRE((size_t)m * 12 <= 120 * 1024, "icp: target cloud too large for LDS (m=%d, max 10240)", m);
     const size_t smem = (size_t)m * 3 * sizeof(float);
     if (flags & LS_FLAG_CONTRACT_FMA)
-        hipLaunchKernelGGL(icp_kernel<true>, dim3(b), dim3(1024), smem, st, X, Y, R0, T0, n, m, max_iter, thr, R, T, rmse, iters_out);
+        hipLaunchKernelGGL(icp_kernel<true>, dim3(b), dim3(1024), smem, (hipStream_t)stream, X, Y, R0, T0, n, m, max_iter, rel_rmse_thr, R, T, rmse, iters_out);
     else
-        hipLaunchKernelGGL(icp_kernel<false>, dim3(b), dim3(1024), smem, st, X, Y, R0, T0, n, m, max_iter, thr, R, T, rmse, iters_out);
+        hipLaunchKernelGGL(icp_kernel<false>, dim3(b), dim3(1024), smem, (hipStream_t)stream, X, Y, R0, T0, n, m, max_iter, rel_rmse_thr, R, T, rmse, iters_out);
     LS_LAUNCH_CHECK();
     return LS_OK;
 }
-
-}  // namespace ls
+}  // extern "C"

@@ -21,6 +21,7 @@
 // Roofline: VALU-bound (3 VALU ops per pair-dim without FMA, 2 with): algorithmic bytes per instance-layer
 // are (Nd+Ns)*3C*4 + Nd*K*4, three orders of magnitude below the VALU time.
 #include "knn_common.h"
+#include "ls_launch.h"
 
 namespace ls {
 
@@ -249,17 +250,10 @@ static size_t knn_partial_bytes(int B, int Nd, int Ns) {
     const int sp = knn_choose_splits(B, Nd, Ns);
     return sp > 1 ? (size_t)B * Nd * sp * 16 * sizeof(u64) : 0;
 }
-// the fused MFMA-filtered kernel (knn_mfma.hip) takes the C == 32 / 64 calls whose candidates fit it, unless the caller forces the all-VALU kernel
-int knn_sweep_max_ns();
-static bool knn_uses_sweep(int C, bool /*seeded*/, int Ns, unsigned flags) {
+static bool knn_uses_sweep(int C, bool /*seeded*/, int Ns, unsigned flags) {   // the fused MFMA-filtered kernel (knn_mfma.hip)
     if (!(C == 32 || C == 64) || (flags & LS_FLAG_KNN_VALU_ONLY)) return false;
     return Ns >= 1 && ((Ns + 31) & ~31) <= knn_sweep_max_ns();
 }
-size_t knn_sweep_scratch_bytes(int B, int Nd, int dst_n, int Ns, int C);
-int knn_sweep_launch(const float*, const float*, const int32_t*, int, int, int, int, int, int, bool, int32_t*, float*, const int32_t*, int,
-                     int, void*, hipStream_t);
-int knn_xyz_launch(const float*, const float*, const int32_t*, int, int, int, int, int, bool, int32_t*, float*, hipStream_t);
-int knn_small_launch(const float*, const float*, const int32_t*, int, int, int, int, int, int, bool, int32_t*, float*, hipStream_t);
 size_t knn_scratch_bytes(int B, int Nd, int dst_n, int Ns, int C, bool seeded, unsigned flags) {
     if (knn_uses_sweep(C, seeded, Ns, flags)) return knn_sweep_scratch_bytes(B, Nd, dst_n, Ns, C);
     return knn_partial_bytes(B, Nd, Ns);
@@ -309,3 +303,23 @@ int knn_dispatch(const float* dst, const float* src, const int32_t* dst_rows, in
 }
 
 }  // namespace ls
+
+using namespace ls;
+extern "C" {
+size_t ls_knn_workspace_bytes(int B, int Nd, int dst_n, int Ns, int C, int seeded, unsigned flags) {
+    if (B <= 0 || Nd <= 0 || Ns <= 0 || dst_n <= 0) return 0;
+    return knn_scratch_bytes(B, Nd, dst_n, Ns, C, seeded != 0, flags);
+}
+int ls_knn_f32(const float* dst, const float* src, const int32_t* dst_rows, const int32_t* seed_idx, int B, int Nd, int dst_n, int Ns,
+               int C, int K, unsigned flags, int32_t* idx_out, float* dist_out, void* workspace, size_t workspace_bytes, void* stream) {
+    LS_REQUIRE(B > 0 && Nd > 0 && Ns > 0 && dst_n > 0, "knn: empty problem (B=%d Nd=%d Ns=%d)", B, Nd, Ns);
+    LS_REQUIRE(K >= 1 && K <= 16, "knn: K=%d unsupported (1..16)", K);
+    LS_REQUIRE(C == 1 || C % 32 == 0, "knn: C=%d must be 1 or a multiple of 32", C);
+    const size_t sb = knn_scratch_bytes(B, Nd, dst_n, Ns, C, seed_idx != nullptr, flags);
+    if (sb > workspace_bytes || (sb && !workspace)) {
+        set_error("knn: workspace %zu < required %zu (ls_knn_workspace_bytes)", workspace_bytes, sb);
+        return LS_ERR_WORKSPACE;
+    }
+    return knn_dispatch(dst, src, dst_rows, B, Nd, dst_n, Ns, C, K, flags, idx_out, dist_out, workspace, seed_idx, Nd, 0, (hipStream_t)stream);
+}
+}  // extern "C"

@@ -290,5 +290,16 @@ __device__ __forceinline__ unsigned kth_smallest_upper_bound(unsigned v, int K) 
     CX<31>(v, lane); CX<8>(v, lane); CX<4>(v, lane); CX<2>(v, lane); CX<1>(v, lane);                                   \
     CX<63>(v, lane); CX<16>(v, lane); CX<8>(v, lane); CX<4>(v, lane); CX<2>(v, lane); CX<1>(v, lane);
 
+// ---- host functions that knn.hip (knn_dispatch, knn_scratch_bytes) calls in the other two k-NN files
+// knn_mfma.hip
+int knn_sweep_max_ns();
+size_t knn_sweep_scratch_bytes(int B, int Nd, int dst_n, int Ns, int C);
+int knn_sweep_launch(const float* dst, const float* src, const int32_t* dst_rows, int B, int Nd, int dst_n, int Ns, int C, int K, bool fma,
+                     int32_t* idx_out, float* dist_out, const int32_t* seed_idx, int seed_n, int seed_by_row, void* scratch, hipStream_t st);
+// knn_xyz.hip
+int knn_xyz_launch(const float* dst, const float* src, const int32_t* dst_rows, int B, int Nd, int dst_n, int Ns, int K, bool fma, int32_t* idx_out,
+                   float* dist_out, hipStream_t st);
+int knn_small_launch(const float* dst, const float* src, const int32_t* dst_rows, int B, int Nd, int dst_n, int Ns, int C, int K, bool fma,
+                     int32_t* idx_out, float* dist_out, hipStream_t st);
 
 }  // namespace ls

@@ -16,6 +16,7 @@
 // layer's lists as thresholds, sweep, finish; or image, cosine store, select) that handed seed keys, survivor lists and pair cosines to each
 // other through HBM (150 MB moved for 54 MB compulsory at layer 1); they are gone (docs/history.md).
 #include "knn_common.h"
+#include "ls_launch.h"
 
 namespace ls {
 

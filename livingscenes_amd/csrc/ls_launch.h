@@ -1,0 +1,97 @@
+// ls_launch.h -- the library's only internal interface: every host function that one translation unit defines and another calls, declared
+// once, with its default arguments.  Included by the file that defines a function and by every file that calls it, so a definition that
+// drifts from its declaration fails where it is made.  (The k-NN files' own cross-calls are in knn_common.h; set_error is in ls_common.h.)
+#pragma once
+#include "ls_common.h"
+
+namespace ls {
+
+// ---- knn.hip
+int knn_dispatch(const float* dst, const float* src, const int32_t* dst_rows, int B, int Nd, int dst_n, int Ns, int C, int K, unsigned flags, int32_t* idx_out,
+                 float* dist_out, void* scratch, const int32_t* seed_idx, int seed_n, int seed_by_row, hipStream_t st);
+size_t knn_scratch_bytes(int B, int Nd, int dst_n, int Ns, int C, bool seeded, unsigned flags);
+bool knn_would_sweep(int C, int Ns, unsigned flags);
+// ---- knn_mfma.hip
+int knn_sweep_stats_launch(const void* scratch, int B, int Nd, int dst_n, int Ns, unsigned long long* out, hipStream_t st);
+// ---- fps.hip
+int fps_dispatch(const float* pts, const int32_t* lengths, int B, int N, int K, unsigned flags, int32_t* idx_out, float* pts_out, void* ws, size_t ws_bytes,
+                 hipStream_t st);
+size_t fps_scratch_bytes_per_cloud(int N);
+// ---- gemm.hip
+int gemm_mode();
+int gemm_dispatch(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N, int K, int relu, hipStream_t st,
+                  GemmAux aux = GemmAux());
+int gemm_dispatch_gather(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N, int K, int relu,
+                         const int32_t* a_rows, int gNd, int gNs, hipStream_t st, GemmAux aux = GemmAux());
+int gemm_dispatch_ws(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N, int K, int relu, float* scratch,
+                     hipStream_t st, GemmAux aux = GemmAux());
+int gemm_dispatch_small(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N, int K, int relu, float* scratch,
+                        hipStream_t st);
+int gemm_dispatch_fast2(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N, int K, int relu, hipStream_t st);
+int gemm_dispatch_masked(const float* A, int lda, const float* W, int ldw, float* out, int ldc, int M, int N, int K, const float* mask, int pieces, hipStream_t st,
+                         GemmAux aux = GemmAux());
+size_t gemm_scratch_floats(int M, int N, int K);
+bool gemm_vn_supported(int M, int C, int K);
+bool gemm_vn_streams(int M, int C, int K, int lda, int npts, const GemmAux& aux);
+int gemm_vn_dispatch(const float* A, int lda, const float* W, int ldw, const float* G, int ldg, float* out, int M, int C, int K, int npts, float oms, hipStream_t st,
+                     GemmAux aux = GemmAux());
+int gemm_rowmax_launch(const float* W, int rows, int K, int ldw, float* out, hipStream_t st);
+int gemm_rowmax_parts(int N);
+size_t gemm_w_planes_bytes(size_t rows, int K);
+bool gemm_w_planes_useful(int K);
+int gemm_presplit_w_launch(const float* W, int rows, int K, int ldw, const float* rowmax, void* planes, hipStream_t st);
+// ---- edge.hip
+int edge_l0_launch(const float* pts, const int32_t* knn, const float* w0, int B, int N, int Co, float neg_slope, float* out, hipStream_t st);
+int edge_pool_launch(const float* T, int ldt, const float* Tq, int ldq, int NQ, int qvr, const int32_t* knn, const int32_t* dst_rows, int B, int Nd, int Ns, int Co,
+                     float neg_slope, float* out, hipStream_t st);
+int edge_attn_launch(const float* T, int ldt, const float* Tq, int ldq, int NQ, int qvr, const int32_t* knn, const int32_t* dst_rows, int B, int Nd, int Ns, int Co,
+                     int head_c, float neg_slope, float* out, hipStream_t st, float* rowmax = nullptr, float* colsum = nullptr);
+bool edge_attn_emits_rowmax(int Co, int ldt, int ldq);
+bool edge_attn_fq_supported(int Co, int Cin);
+bool edge_attn_fq_fits(int B, int Ns, int ldt);
+int edge_attn_fq_launch(const float* T, int ldt, const float* cur, int Cin, const void* wq_planes, const int32_t* knn, const int32_t* dst_rows, int B, int Nd,
+                        int Ns, int Co, int head_c, float neg_slope, float* out, hipStream_t st, float* rowmax = nullptr, float* colsum = nullptr);
+int edge_attn_fq_points_per_wg(int Co);
+size_t edge_wq_planes_bytes(int Co, int Cin);
+int edge_presplit_wq_launch(const float* Wq, int Co, int Cin, void* planes, hipStream_t st);
+// ---- edge_fused.hip: attention layers with 32 destination points (released layers 5 / 6) -- table slices formed and consumed in LDS
+bool edge_ft_supported(int Co, int Cin, int Ns, int Nd, int head_c, bool has_rows);
+size_t edge_ft_w_bytes(int Co, int Cin);
+int edge_ft_presplit_w_launch(const float* W, int Co, int Cin, void* planes, hipStream_t st);
+size_t edge_ft_scratch_bytes(int B, int Ns, int Nd, int Cin, int Co, bool has_rows);
+int edge_ft_prep_launch(const float* cur, const int32_t* dst_rows, int B, int Ns, int Nd, int Cin, int Co, void* scratch, hipStream_t st);
+int edge_ft_attn_launch(const void* wplanes, const int32_t* knn, bool has_rows, int B, int Ns, int Nd, int Cin, int Co, float neg_slope, void* scratch, float* out,
+                        float* rowmax, hipStream_t st, float* colsum = nullptr);
+int edge_ft_rowmax_parts(int Co, int Cin);
+// ---- pointwise.hip
+int prologue_launch(const float* x, int B, int N, float* pts, float* centroid, float* scale0, float* unused, hipStream_t st);
+size_t prologue_scratch_floats(int B);
+int transpose_cloud_launch(const float* x, int B, int N, float* pts, hipStream_t st);
+int mean_points_launch(const float* f, int B, int N, int C, float* out, hipStream_t st);
+int glob_mean_gemv_launch(const float* f, int B, int N, int C, const float* W, int col0, int ncols, float* G, int ldg, hipStream_t st, int npoints = 0);
+int vn_act_rows_launch(const float* T, int ldt, const float* G, int ldg, int B, int N, int C, float neg_slope, float* out, hipStream_t st);
+int tail_launch(const float* Tc, int ldc, int B, int NP, int Cd, const float* inv_t, const float* fc0_t, const float* misc, float neg_slope, float scale_factor,
+                int center_pred, int center_scale, const float* centroid, const float* scale0, float* z_so3, float* z_inv, float* s_out, float* t_out,
+                hipStream_t st);
+int scatter_codes_launch(const float* packed, int B, int c, float* z_so3, float* z_inv, float* s, float* t, hipStream_t st);
+// ---- sdf.hip
+int sdf_prep_launch(const float* inv_t, const float* so3_t, const float* wlen, const float* bias, const float* z_so3, const float* z_inv, int B, int L, int out_dim,
+                    float* A, float* beff, bool xyz, hipStream_t st);
+int sdf_affine_launch(const float* query, const float* s, const float* t, const float* A, const float* beff, int B, int M, int out_dim, int ldh, int accumulate,
+                      float* h, bool xyz, hipStream_t st, float* rowmax = nullptr);
+int sdf_affine_rows_launch(const float* query, const int32_t* row_inst, const float* s, const float* t, const float* A, const float* beff, long long R, int out_dim,
+                           int ldh, int accumulate, float* h, bool xyz, hipStream_t st, float* rowmax = nullptr);
+int sdf_affine_rowmax_parts(int out_dim);
+int sdf_out_launch(const float* h, int ldh, int width, const float* w, const float* bias, long long rows, float* sdf, hipStream_t st);
+int sdf_out_bwd_launch(const float* g, const float* sdf, const float* w, const float* h, int ldh, int width, long long rows, float* dz, hipStream_t st,
+                       float* rowmax = nullptr, const float* wmax = nullptr);
+int relu_mask_launch(float* dh, const float* h, long long rows, int cols, int ld, hipStream_t st);
+int sdf_affine_bwd_launch(const float* query, const float* s, const float* t, const float* dz, const float* A, int B, int M, int out_dim, int ldh, int accumulate,
+                          float* dA, float* dbeff, float* dQ, bool need_code, bool xyz, hipStream_t st);
+int sdf_code_grad_launch(const float* so3_t0, const float* inv_t0, const float* dA0, const float* db0, const float* so3_t1, const float* inv_t1, const float* dA1,
+                         const float* db1, int B, int L, int out_dim, float* g_so3, float* g_inv, bool xyz, hipStream_t st);
+int sdf_query_grad_launch(const float* query, const float* s, const float* t, const float* dQ, int B, int M, float* g_query, float* g_t, float* g_s, bool xyz,
+                          hipStream_t st);
+int transpose_launch(const float* W, int rows, int cols, float* Wt, hipStream_t st);
+
+}  // namespace ls

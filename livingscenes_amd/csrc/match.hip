@@ -470,14 +470,6 @@ int greedy_match_run(const Problems& L, int cls, int count, size_t lds, float* S
     return LS_OK;
 }
 
-int cosine_scores_launch(const float* m0, const float* m1, int n, int m, int D, float* inv_norm_ws, float* S, hipStream_t st) {
-    return cosine_scores_run(OneProblem{n, m}, (long long)n + m, (long long)n * m, (long long)n * m > 4096, m0, m1, D, inv_norm_ws, S, st);
-}
-int greedy_match_launch(float* S, int n, int m, long long* m0, long long* m1, hipStream_t st) {
-    const int cls = greedy_class(n, m);
-    if (cls == GREEDY_BLOCK) LS_REQUIRE((size_t)(n + m) * sizeof(int) <= 48 * 1024, "greedy_match: n+m=%d too large", n + m);
-    return greedy_match_run(OneProblem{n, m}, cls, 1, (size_t)(n + m) * sizeof(int), S, m0, m1, st);
-}
 // ---------------------------------------------------------------------------------------------- mutual-NN and Sinkhorn assignment
 // nn_matcher            /root/reference/lib_more/matcher_new.py:85-107   (find_nn without thresholds, two mutual checks)
 // sinkhorn_matcher      matcher_new.py:20-71                             (SuperGlue's log-space optimal transport with a dustbin row / column, 100
@@ -609,24 +601,11 @@ int assign_run(const Problems& L, int count, size_t lds, const float* S, int mod
     LS_LAUNCH_CHECK();
     return LS_OK;
 }
-int assign_launch(const float* S, int n, int m, int mode, float div, float alpha, int iters, float thr, long long* m0, long long* m1, hipStream_t st) {
-    const size_t lds = assign_lds_bytes(n, m, mode);
-    LS_REQUIRE(lds <= ASSIGN_LDS_MAX, "%s: a %d x %d problem needs %zu bytes of LDS (at most 153600: about 190 x 190)", mode ? "sinkhorn_match" : "nn_match", n, m, lds);
-    return assign_run(OneProblem{n, m}, 1, lds, S, mode, div, alpha, iters, thr, m0, m1, st);
-}
-int kabsch_launch(const float* x1, const float* x2, const float* w, int nprob, int n, int pair_m, int raw_weights, float* R, float* t,
-                  float* res, float* res_mean, int32_t* flags, hipStream_t st, const float* off1, const float* off2, const long long* sel1,
-                  const long long* sel2) {
-    hipLaunchKernelGGL(kabsch_kernel<OneProblem>, dim3(cdiv(nprob, 4)), dim3(256), 0, st, OneProblem{pair_m > 0 ? nprob / pair_m : 0, pair_m}, x1, x2, w,
-                       nprob, n, pair_m, raw_weights, 1e-7f, R, t, res, res_mean, flags, off1, off2, sel1, sel2);
-    LS_LAUNCH_CHECK();
-    return LS_OK;
-}
 
 // ---------------------------------------------------------------------------------------------- ragged batches
 // Every problem's result is bit-identical to the single op on that problem alone: the same kernels, the same launch choices per problem.
 // The argument checks run before the first HIP call (no device is needed to be told what is wrong with the offsets).
-size_t match_batch_workspace_bytes(int P, long long n_total, long long m_total, int with_norms) {
+static size_t match_batch_workspace_bytes(int P, long long n_total, long long m_total, int with_norms) {
     if (P <= 0 || n_total < 0 || m_total < 0) return 0;
     const size_t offs = ((size_t)MOFF_ARRAYS * (P + 1) + (size_t)P) * sizeof(long long);
     return ((offs + 255) / 256) * 256 + (with_norms ? (size_t)(n_total + m_total) * sizeof(float) : 0);
@@ -685,8 +664,74 @@ int batch_setup(const char* op, int P, long long n_total, const long long* src_o
 }
 }  // namespace
 
-int cosine_scores_batch_launch(int P, const float* m0, long long n_total, const long long* src_off, const float* m1, long long m_total,
-                               const long long* tgt_off, int D, float* S, void* ws, size_t ws_bytes, hipStream_t st) {
+}  // namespace ls
+
+using namespace ls;
+extern "C" {   // (a static helper that two or three exports share stands above the first of them)
+size_t ls_cosine_scores_workspace_bytes(int n, int m) { return (n > 0 && m > 0) ? (size_t)(n + m) * sizeof(float) : 0; }
+int ls_cosine_scores_f32(const float* m0, const float* m1, int n, int m, int D, float* scores, void* workspace, size_t workspace_bytes, void* stream) {
+    LS_REQUIRE(n > 0 && m > 0 && D > 0, "cosine_scores: empty problem");
+    LS_REQUIRE(m0 && m1 && scores, "cosine_scores: null argument");
+    if (!workspace || workspace_bytes < ls_cosine_scores_workspace_bytes(n, m)) {   // the n + m inverse row norms
+        set_error("cosine_scores: workspace %zu < required %zu", workspace_bytes, ls_cosine_scores_workspace_bytes(n, m));
+        return LS_ERR_WORKSPACE;
+    }
+    return cosine_scores_run(OneProblem{n, m}, (long long)n + m, (long long)n * m, (long long)n * m > 4096, m0, m1, D, (float*)workspace, scores,
+                             (hipStream_t)stream);
+}
+int ls_greedy_match_f32(float* scores, int n, int m, int64_t* matches0, int64_t* matches1, void* stream) {
+    LS_REQUIRE(n > 0 && m > 0, "greedy_match: empty problem");
+    const int cls = greedy_class(n, m);
+    if (cls == GREEDY_BLOCK) LS_REQUIRE((size_t)(n + m) * sizeof(int) <= 48 * 1024, "greedy_match: n+m=%d too large", n + m);
+    return greedy_match_run(OneProblem{n, m}, cls, 1, (size_t)(n + m) * sizeof(int), scores, (long long*)matches0, (long long*)matches1, (hipStream_t)stream);
+}
+static int assign_launch(const float* S, int n, int m, int mode, float div, float alpha, int iters, float thr, long long* m0, long long* m1, hipStream_t st) {
+    const size_t lds = assign_lds_bytes(n, m, mode);
+    LS_REQUIRE(lds <= ASSIGN_LDS_MAX, "%s: a %d x %d problem needs %zu bytes of LDS (at most 153600: about 190 x 190)", mode ? "sinkhorn_match" : "nn_match", n, m, lds);
+    return assign_run(OneProblem{n, m}, 1, lds, S, mode, div, alpha, iters, thr, m0, m1, st);
+}
+int ls_nn_match_f32(const float* scores, int n, int m, int64_t* matches0, int64_t* matches1, void* stream) {
+    LS_REQUIRE(n > 0 && m > 0 && scores && matches0 && matches1, "nn_match: empty problem or null argument");
+    return assign_launch(scores, n, m, 0, 1.0f, 0.0f, 0, 0.0f, (long long*)matches0, (long long*)matches1, (hipStream_t)stream);
+}
+int ls_sinkhorn_match_f32(const float* scores, int n, int m, float score_divisor, float alpha, int iters, float match_threshold, int64_t* matches0,
+                          int64_t* matches1, void* stream) {
+    LS_REQUIRE(n > 0 && m > 0 && scores && matches0 && matches1, "sinkhorn_match: empty problem or null argument");
+    LS_REQUIRE(iters >= 0 && score_divisor != 0.0f, "sinkhorn_match: iters=%d score_divisor=%g", iters, (double)score_divisor);
+    return assign_launch(scores, n, m, 1, score_divisor, alpha, iters, match_threshold, (long long*)matches0, (long long*)matches1, (hipStream_t)stream);
+}
+static int kabsch_launch(const float* x1, const float* x2, const float* w, int nprob, int n, int pair_m, int raw_weights, float* R, float* t,
+                         float* res, float* res_mean, int32_t* flags, hipStream_t st, const float* off1 = nullptr, const float* off2 = nullptr,
+                         const long long* sel1 = nullptr, const long long* sel2 = nullptr) {
+    hipLaunchKernelGGL(kabsch_kernel<OneProblem>, dim3(cdiv(nprob, 4)), dim3(256), 0, st, OneProblem{pair_m > 0 ? nprob / pair_m : 0, pair_m}, x1, x2, w,
+                       nprob, n, pair_m, raw_weights, 1e-7f, R, t, res, res_mean, flags, off1, off2, sel1, sel2);
+    LS_LAUNCH_CHECK();
+    return LS_OK;
+}
+int ls_kabsch_batched_f32(const float* x1, const float* x2, const float* weights, int b, int n, unsigned flags, float* R, float* t,
+                          float* res, int32_t* flags_out, void* stream) {
+    LS_REQUIRE(b > 0 && n > 0, "kabsch: empty problem");
+    LS_REQUIRE(x1 && x2 && R && t, "kabsch: null argument");
+    return kabsch_launch(x1, x2, weights, b, n, 0, (flags & LS_FLAG_KABSCH_RAW_WEIGHTS) ? 1 : 0, R, t, res, nullptr, flags_out, (hipStream_t)stream);
+}
+int ls_kabsch_codes_f32(const float* x1, const float* off1, const int64_t* sel1, const float* x2, const float* off2, const int64_t* sel2, int b,
+                        int n, float* R, float* t, float* res, int32_t* flags_out, void* stream) {
+    LS_REQUIRE(b > 0 && n > 0, "kabsch_codes: empty problem");
+    LS_REQUIRE(x1 && x2 && R && t, "kabsch_codes: null argument");
+    return kabsch_launch(x1, x2, nullptr, b, n, 0, 0, R, t, res, nullptr, flags_out, (hipStream_t)stream, off1, off2, (const long long*)sel1, (const long long*)sel2);
+}
+int ls_kabsch_residual_matrix_f32(const float* src, const float* tgt, int n, int m, int P, float* res, void* stream) {
+    LS_REQUIRE(n > 0 && m > 0 && P > 0, "kabsch_residual_matrix: empty problem");
+    return kabsch_launch(src, tgt, nullptr, n * m, P, m, 0, nullptr, nullptr, nullptr, res, nullptr, (hipStream_t)stream);
+}
+// ---- ragged batches
+size_t ls_cosine_scores_batch_workspace_bytes(int P, long long n_total, long long m_total) { return match_batch_workspace_bytes(P, n_total, m_total, 1); }
+size_t ls_greedy_match_batch_workspace_bytes(int P, long long n_total, long long m_total) { return match_batch_workspace_bytes(P, n_total, m_total, 0); }
+size_t ls_nn_match_batch_workspace_bytes(int P, long long n_total, long long m_total) { return match_batch_workspace_bytes(P, n_total, m_total, 0); }
+size_t ls_sinkhorn_match_batch_workspace_bytes(int P, long long n_total, long long m_total) { return match_batch_workspace_bytes(P, n_total, m_total, 0); }
+size_t ls_kabsch_residual_matrix_batch_workspace_bytes(int P, long long n_total, long long m_total) { return match_batch_workspace_bytes(P, n_total, m_total, 0); }
+int ls_cosine_scores_batch_f32(int P, const float* m0, long long n_total, const long long* src_off, const float* m1, long long m_total,
+                               const long long* tgt_off, int D, float* S, void* ws, size_t ws_bytes, void* stream) {
     const char* op = "cosine_scores_batch";
     LS_REQUIRE(D > 0, "%s: D = %d", op, D);
     Batch b;
@@ -694,13 +739,12 @@ int cosine_scores_batch_launch(int P, const float* m0, long long n_total, const 
     if (rc != LS_OK) return rc;
     if (b.entries == 0) return LS_OK;   // every problem is empty: no scores
     LS_REQUIRE(m0 && m1 && S, "%s: null argument", op);
-    rc = b.upload(st);
+    rc = b.upload((hipStream_t)stream);
     if (rc != LS_OK) return rc;
-    return cosine_scores_run(b.L, b.rows, b.entries, b.any_large, m0, m1, D, b.inv_norm, S, st);
+    return cosine_scores_run(b.L, b.rows, b.entries, b.any_large, m0, m1, D, b.inv_norm, S, (hipStream_t)stream);
 }
-
-int greedy_match_batch_launch(int P, float* S, long long n_total, const long long* src_off, long long m_total, const long long* tgt_off,
-                              long long* m0, long long* m1, void* ws, size_t ws_bytes, hipStream_t st) {
+int ls_greedy_match_batch_f32(int P, float* S, long long n_total, const long long* src_off, long long m_total, const long long* tgt_off,
+                              int64_t* m0, int64_t* m1, void* ws, size_t ws_bytes, void* stream) {
     const char* op = "greedy_match_batch";
     Batch b;
     int rc = batch_setup(op, P, n_total, src_off, m_total, tgt_off, ws, ws_bytes, 0, &b);
@@ -711,20 +755,19 @@ int greedy_match_batch_launch(int P, float* S, long long n_total, const long lon
             const long long n = src_off[p + 1] - src_off[p], m = tgt_off[p + 1] - tgt_off[p];
             LS_REQUIRE(greedy_class(n, m) != GREEDY_BLOCK || (size_t)(n + m) * sizeof(int) <= 48 * 1024, "%s: problem %d: n+m=%lld too large", op, p, n + m);
         }
-    rc = b.upload(st);
+    rc = b.upload((hipStream_t)stream);
     if (rc != LS_OK) return rc;
     for (int c = 0; c < GREEDY_CLASSES; ++c) {   // at most one launch per class; empty problems ride in the one-wave class
         if (b.cls_count[c] == 0) continue;
         RaggedProblems L = b.L;
         L.ids = b.L.offs + (size_t)MOFF_ARRAYS * (P + 1) + b.cls_first[c];
-        rc = greedy_match_run(L, c, b.cls_count[c], b.greedy_lds, S, m0, m1, st);
+        rc = greedy_match_run(L, c, b.cls_count[c], b.greedy_lds, S, (long long*)m0, (long long*)m1, (hipStream_t)stream);
         if (rc != LS_OK) return rc;
     }
     return LS_OK;
 }
-
-int assign_batch_launch(int P, const float* S, long long n_total, const long long* src_off, long long m_total, const long long* tgt_off, int mode,
-                        float div, float alpha, int iters, float thr, long long* m0, long long* m1, void* ws, size_t ws_bytes, hipStream_t st) {
+static int assign_batch_launch(int P, const float* S, long long n_total, const long long* src_off, long long m_total, const long long* tgt_off, int mode,
+                               float div, float alpha, int iters, float thr, long long* m0, long long* m1, void* ws, size_t ws_bytes, hipStream_t st) {
     const char* op = mode ? "sinkhorn_match_batch" : "nn_match_batch";
     Batch b;
     int rc = batch_setup(op, P, n_total, src_off, m_total, tgt_off, ws, ws_bytes, 0, &b);
@@ -742,9 +785,20 @@ int assign_batch_launch(int P, const float* S, long long n_total, const long lon
     if (rc != LS_OK) return rc;
     return assign_run(b.L, P, lds, S, mode, div, alpha, iters, thr, m0, m1, st);
 }
-
-int kabsch_residual_matrix_batch_launch(int P, const float* src, long long n_total, const long long* src_off, const float* tgt, long long m_total,
-                                        const long long* tgt_off, int C, float* res, void* ws, size_t ws_bytes, hipStream_t st) {
+int ls_nn_match_batch_f32(int P, const float* scores, long long n_total, const long long* src_off, long long m_total, const long long* tgt_off,
+                          int64_t* matches0, int64_t* matches1, void* workspace, size_t workspace_bytes, void* stream) {
+    return assign_batch_launch(P, scores, n_total, src_off, m_total, tgt_off, 0, 1.0f, 0.0f, 0, 0.0f, (long long*)matches0, (long long*)matches1,
+                               workspace, workspace_bytes, (hipStream_t)stream);
+}
+int ls_sinkhorn_match_batch_f32(int P, const float* scores, long long n_total, const long long* src_off, long long m_total, const long long* tgt_off,
+                                float score_divisor, float alpha, int iters, float match_threshold, int64_t* matches0, int64_t* matches1,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    LS_REQUIRE(iters >= 0 && score_divisor != 0.0f, "sinkhorn_match_batch: iters=%d score_divisor=%g", iters, (double)score_divisor);
+    return assign_batch_launch(P, scores, n_total, src_off, m_total, tgt_off, 1, score_divisor, alpha, iters, match_threshold, (long long*)matches0,
+                               (long long*)matches1, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int ls_kabsch_residual_matrix_batch_f32(int P, const float* src, long long n_total, const long long* src_off, const float* tgt, long long m_total,
+                                        const long long* tgt_off, int C, float* res, void* ws, size_t ws_bytes, void* stream) {
     const char* op = "kabsch_residual_matrix_batch";
     LS_REQUIRE(C > 0, "%s: C = %d", op, C);
     Batch b;
@@ -752,13 +806,12 @@ int kabsch_residual_matrix_batch_launch(int P, const float* src, long long n_tot
     if (rc != LS_OK) return rc;
     if (b.entries == 0) return LS_OK;
     LS_REQUIRE(src && tgt && res, "%s: null argument", op);
-    rc = b.upload(st);
+    rc = b.upload((hipStream_t)stream);
     if (rc != LS_OK) return rc;
-    hipLaunchKernelGGL(kabsch_kernel<RaggedProblems>, dim3(cdiv(b.entries, 4)), dim3(256), 0, st, b.L, src, tgt, (const float*)nullptr, (int)b.entries,
+    hipLaunchKernelGGL(kabsch_kernel<RaggedProblems>, dim3(cdiv(b.entries, 4)), dim3(256), 0, (hipStream_t)stream, b.L, src, tgt, (const float*)nullptr, (int)b.entries,
                        C, 1, 0, 1e-7f, (float*)nullptr, (float*)nullptr, (float*)nullptr, res, (int32_t*)nullptr, (const float*)nullptr,
                        (const float*)nullptr, (const long long*)nullptr, (const long long*)nullptr);
     LS_LAUNCH_CHECK();
     return LS_OK;
 }
-
-}  // namespace ls
+}  // extern "C"

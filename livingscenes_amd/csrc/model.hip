@@ -1,12 +1,13 @@
-// model.hip -- the C ABI: model handle, leaf-operator exports and the two composite hot-path entry points
-// (ls_encode = Shape_Prior.encode, ls_sdf_decode = FieldWrapper.forward).  Host code only enqueues work on the
-// caller's stream (plus one library-owned side stream for the FPS chain); it never synchronises the device.
+// model.hip -- the model's part of the C ABI: version / error / device count, the model handle and its options, the per-layer operator exports, profiling
+// and the two composite hot-path entry points (ls_encode = Shape_Prior.encode, ls_sdf_decode = FieldWrapper.forward).  Leaf operators are exported at the
+// end of the file that holds their kernels; what this file calls in other translation units is declared in ls_launch.h.  Host code only enqueues work on
+// the caller's stream (plus one library-owned side stream for the FPS chain); it never synchronises the device.
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
 
-#include "ls_common.h"
+#include "ls_launch.h"
 
 namespace ls {
 
@@ -17,93 +18,6 @@ void set_error(const char* fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
-
-// kernels / launchers defined in the other translation units
-int knn_dispatch(const float*, const float*, const int32_t*, int, int, int, int, int, int, unsigned, int32_t*, float*, void*, const int32_t*, int, int,
-                 hipStream_t);
-size_t knn_scratch_bytes(int B, int Nd, int dst_n, int Ns, int C, bool seeded, unsigned flags);
-bool knn_would_sweep(int C, int Ns, unsigned flags);
-int knn_sweep_stats_launch(const void* scratch, int B, int Nd, int dst_n, int Ns, unsigned long long* out, hipStream_t st);
-int fps_dispatch(const float*, const int32_t*, int, int, int, unsigned, int32_t*, float*, void*, size_t, hipStream_t);
-size_t fps_scratch_bytes_per_cloud(int N);
-int gemm_dispatch(const float*, int, const float*, int, const float*, float*, int, int, int, int, int, hipStream_t, GemmAux aux = GemmAux());
-int gemm_rowmax_launch(const float* W, int rows, int K, int ldw, float* out, hipStream_t st);
-int gemm_rowmax_parts(int N);
-size_t gemm_w_planes_bytes(size_t rows, int K);
-bool gemm_w_planes_useful(int K);
-int gemm_presplit_w_launch(const float* W, int rows, int K, int ldw, const float* rowmax, void* planes, hipStream_t st);
-int sdf_affine_rowmax_parts(int out_dim);
-int edge_l0_launch(const float*, const int32_t*, const float*, int, int, int, float, float*, hipStream_t);
-int edge_pool_launch(const float*, int, const float*, int, int, int, const int32_t*, const int32_t*, int, int, int, int, float, float*, hipStream_t);
-int edge_attn_launch(const float*, int, const float*, int, int, int, const int32_t*, const int32_t*, int, int, int, int, int, float, float*, hipStream_t, float* rowmax = nullptr,
-                     float* colsum = nullptr);
-bool edge_attn_emits_rowmax(int Co, int ldt, int ldq);
-bool edge_attn_fq_supported(int Co, int Cin);
-bool edge_attn_fq_fits(int B, int Ns, int ldt);
-int edge_attn_fq_launch(const float*, int, const float*, int, const void*, const int32_t*, const int32_t*, int, int, int, int, int, float, float*, hipStream_t, float* rowmax = nullptr,
-                        float* colsum = nullptr);
-int edge_attn_fq_points_per_wg(int Co);
-size_t edge_wq_planes_bytes(int Co, int Cin);
-// edge_fused.hip: attention layers with 32 destination points (released layers 5 / 6) -- table slices formed and consumed in LDS
-bool edge_ft_supported(int Co, int Cin, int Ns, int Nd, int head_c, bool has_rows);
-size_t edge_ft_w_bytes(int Co, int Cin);
-int edge_ft_presplit_w_launch(const float* W, int Co, int Cin, void* planes, hipStream_t st);
-size_t edge_ft_scratch_bytes(int B, int Ns, int Nd, int Cin, int Co, bool has_rows);
-int edge_ft_prep_launch(const float* cur, const int32_t* dst_rows, int B, int Ns, int Nd, int Cin, int Co, void* scratch, hipStream_t st);
-int edge_ft_attn_launch(const void* wplanes, const int32_t* knn, bool has_rows, int B, int Ns, int Nd, int Cin, int Co, float neg_slope, void* scratch,
-                        float* out, float* rowmax, hipStream_t st, float* colsum = nullptr);
-int edge_ft_rowmax_parts(int Co, int Cin);
-int edge_presplit_wq_launch(const float* Wq, int Co, int Cin, void* planes, hipStream_t st);
-int gemm_dispatch_gather(const float*, int, const float*, int, const float*, float*, int, int, int, int, int, const int32_t*, int, int, hipStream_t, GemmAux aux = GemmAux());
-int gemm_dispatch_ws(const float*, int, const float*, int, const float*, float*, int, int, int, int, int, float*, hipStream_t, GemmAux aux = GemmAux());
-int gemm_dispatch_small(const float*, int, const float*, int, const float*, float*, int, int, int, int, int, float*, hipStream_t);
-bool gemm_vn_supported(int M, int C, int K);
-bool gemm_vn_streams(int M, int C, int K, int lda, int npts, const GemmAux& aux);
-int gemm_mode();
-int gemm_vn_dispatch(const float*, int, const float*, int, const float*, int, float*, int, int, int, int, float, hipStream_t, GemmAux aux = GemmAux());
-int gemm_dispatch_fast2(const float*, int, const float*, int, const float*, float*, int, int, int, int, int, hipStream_t);
-int gemm_dispatch_masked(const float*, int, const float*, int, float*, int, int, int, int, const float*, int, hipStream_t, GemmAux aux = GemmAux());
-size_t gemm_scratch_floats(int M, int N, int K);
-int prologue_launch(const float*, int, int, float*, float*, float*, float*, hipStream_t);
-size_t prologue_scratch_floats(int B);
-int transpose_cloud_launch(const float*, int, int, float*, hipStream_t);
-int mean_points_launch(const float*, int, int, int, float*, hipStream_t);
-int glob_mean_gemv_launch(const float*, int, int, int, const float*, int, int, float*, int, hipStream_t, int npoints = 0);
-int vn_act_rows_launch(const float*, int, const float*, int, int, int, int, float, float*, hipStream_t);
-int tail_launch(const float*, int, int, int, int, const float*, const float*, const float*, float, float, int, int, const float*,
-                const float*, float*, float*, float*, float*, hipStream_t);
-int sdf_prep_launch(const float*, const float*, const float*, const float*, const float*, const float*, int, int, int, float*,
-                    float*, bool, hipStream_t);
-int sdf_affine_launch(const float*, const float*, const float*, const float*, const float*, int, int, int, int, int, float*,
-                      bool, hipStream_t, float* rowmax = nullptr);
-int sdf_out_launch(const float*, int, int, const float*, const float*, long long, float*, hipStream_t);
-int sdf_affine_rows_launch(const float*, const int32_t*, const float*, const float*, const float*, const float*, long long, int, int, int,
-                           float*, bool, hipStream_t, float* rowmax = nullptr);
-int sdf_out_bwd_launch(const float*, const float*, const float*, const float*, int, int, long long, float*, hipStream_t, float* rowmax = nullptr,
-                       const float* wmax = nullptr);
-int relu_mask_launch(float*, const float*, long long, int, int, hipStream_t);
-int sdf_affine_bwd_launch(const float*, const float*, const float*, const float*, const float*, int, int, int, int, int, float*, float*,
-                          float*, bool, bool, hipStream_t);
-int sdf_code_grad_launch(const float*, const float*, const float*, const float*, const float*, const float*, const float*, const float*,
-                         int, int, int, float*, float*, bool, hipStream_t);
-int sdf_query_grad_launch(const float*, const float*, const float*, const float*, int, int, float*, float*, float*, bool, hipStream_t);
-int transpose_launch(const float*, int, int, float*, hipStream_t);
-int cosine_scores_launch(const float*, const float*, int, int, int, float*, float*, hipStream_t);
-int greedy_match_launch(float*, int, int, long long*, long long*, hipStream_t);
-int assign_launch(const float*, int, int, int, float, float, int, float, long long*, long long*, hipStream_t);
-int kabsch_launch(const float*, const float*, const float*, int, int, int, int, float*, float*, float*, float*, int32_t*, hipStream_t,
-                  const float* off1 = nullptr, const float* off2 = nullptr, const long long* sel1 = nullptr, const long long* sel2 = nullptr);
-size_t match_batch_workspace_bytes(int P, long long n_total, long long m_total, int with_norms);
-int cosine_scores_batch_launch(int, const float*, long long, const long long*, const float*, long long, const long long*, int, float*, void*, size_t,
-                               hipStream_t);
-int greedy_match_batch_launch(int, float*, long long, const long long*, long long, const long long*, long long*, long long*, void*, size_t, hipStream_t);
-int assign_batch_launch(int, const float*, long long, const long long*, long long, const long long*, int, float, float, int, float, long long*,
-                        long long*, void*, size_t, hipStream_t);
-int kabsch_residual_matrix_batch_launch(int, const float*, long long, const long long*, const float*, long long, const long long*, int, float*, void*,
-                                        size_t, hipStream_t);
-size_t icp_workspace_bytes(int b, int n);
-int icp_run(const float*, const float*, const float*, const float*, int, int, int, int, float, unsigned, float*, float*, float*,
-            int32_t*, void*, size_t, hipStream_t);
 
 }  // namespace ls
 
@@ -518,168 +432,6 @@ int ls_device_count(void) {
     return n;
 }
 
-// ------------------------------------------------------------------------------------------------ leaf exports
-size_t ls_knn_workspace_bytes(int B, int Nd, int dst_n, int Ns, int C, int seeded, unsigned flags) {
-    if (B <= 0 || Nd <= 0 || Ns <= 0 || dst_n <= 0) return 0;
-    return knn_scratch_bytes(B, Nd, dst_n, Ns, C, seeded != 0, flags);
-}
-int ls_knn_f32(const float* dst, const float* src, const int32_t* dst_rows, const int32_t* seed_idx, int B, int Nd, int dst_n, int Ns,
-               int C, int K, unsigned flags, int32_t* idx_out, float* dist_out, void* workspace, size_t workspace_bytes, void* stream) {
-    LS_REQUIRE(B > 0 && Nd > 0 && Ns > 0 && dst_n > 0, "knn: empty problem (B=%d Nd=%d Ns=%d)", B, Nd, Ns);
-    LS_REQUIRE(K >= 1 && K <= 16, "knn: K=%d unsupported (1..16)", K);
-    LS_REQUIRE(C == 1 || C % 32 == 0, "knn: C=%d must be 1 or a multiple of 32", C);
-    const size_t sb = knn_scratch_bytes(B, Nd, dst_n, Ns, C, seed_idx != nullptr, flags);
-    if (sb > workspace_bytes || (sb && !workspace)) {
-        set_error("knn: workspace %zu < required %zu (ls_knn_workspace_bytes)", workspace_bytes, sb);
-        return LS_ERR_WORKSPACE;
-    }
-    return knn_dispatch(dst, src, dst_rows, B, Nd, dst_n, Ns, C, K, flags, idx_out, dist_out, workspace, seed_idx, Nd, 0, (hipStream_t)stream);
-}
-size_t ls_fps_workspace_bytes(int B, int N, int K) {
-    (void)K;
-    return (B > 0 && N > 0) ? fps_scratch_bytes_per_cloud(N) * (size_t)B : 0;
-}
-int ls_fps_f32(const float* pts, const int32_t* lengths, int B, int N, int K, unsigned flags, int32_t* idx_out, float* pts_out,
-               void* workspace, size_t workspace_bytes, void* stream) {
-    return fps_dispatch(pts, lengths, B, N, K, flags, idx_out, pts_out, workspace, workspace_bytes, (hipStream_t)stream);
-}
-size_t ls_gemm_workspace_bytes(int M, int N, int K) {
-    return (M > 0 && N > 0 && K > 0 && K % 4 == 0) ? gemm_scratch_floats(M, N, K) * sizeof(float) : 0;
-}
-int ls_gemm_f32(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N, int K,
-                int relu, void* workspace, size_t workspace_bytes, void* stream) {
-    const size_t sb = (lda % 4 == 0 && ldw % 4 == 0) ? ls_gemm_workspace_bytes(M, N, K) : 0;
-    if (!sb) return gemm_dispatch(A, lda, W, ldw, bias, out, ldc, M, N, K, relu, (hipStream_t)stream);
-    if (sb > workspace_bytes || !workspace) {   // split-K slabs of an under-filled, long-K problem
-        set_error("gemm: workspace %zu < required %zu (ls_gemm_workspace_bytes)", workspace_bytes, sb);
-        return LS_ERR_WORKSPACE;
-    }
-    return gemm_dispatch_ws(A, lda, W, ldw, bias, out, ldc, M, N, K, relu, (float*)workspace, (hipStream_t)stream);
-}
-int ls_gemm_rowmax_parts(int N) { return N > 0 ? gemm_rowmax_parts(N) : 0; }
-int ls_gemm_f32_ex(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N, int K,
-                   int relu, const float* a_rowmax, int a_parts, const float* w_rowmax, float* out_rowmax, void* workspace,
-                   size_t workspace_bytes, void* stream) {
-    LS_REQUIRE(!a_rowmax || a_parts >= 1, "gemm_ex: a_rowmax needs a_parts >= 1");
-    GemmAux ax;
-    ax.a_rowmax = a_rowmax; ax.a_parts = a_rowmax ? a_parts : 0; ax.w_rowmax = w_rowmax; ax.out_rowmax = out_rowmax;
-    const size_t sb = (workspace && lda % 4 == 0 && ldw % 4 == 0) ? ls_gemm_workspace_bytes(M, N, K) : 0;
-    LS_REQUIRE(!(sb && out_rowmax), "gemm_ex: a split-K launch (M=%d N=%d K=%d with a workspace) writes no out_rowmax: pass workspace = NULL", M, N, K);
-    if (!sb) return gemm_dispatch(A, lda, W, ldw, bias, out, ldc, M, N, K, relu, (hipStream_t)stream, ax);
-    if (sb > workspace_bytes) { set_error("gemm_ex: workspace %zu < required %zu (ls_gemm_workspace_bytes)", workspace_bytes, sb); return LS_ERR_WORKSPACE; }
-    return gemm_dispatch_ws(A, lda, W, ldw, bias, out, ldc, M, N, K, relu, (float*)workspace, (hipStream_t)stream, ax);
-}
-int ls_rowmax_f32(const float* X, int rows, int K, int ld, float* out, void* stream) {
-    LS_REQUIRE(X && out && rows > 0 && K > 0 && ld >= K, "rowmax: bad argument");
-    return gemm_rowmax_launch(X, rows, K, ld, out, (hipStream_t)stream);
-}
-size_t ls_gemm_w_planes_bytes(int N, int K) { return (N > 0 && K > 0 && gemm_w_planes_useful(K)) ? gemm_w_planes_bytes((size_t)N, K) : 0; }
-int ls_gemm_presplit_w_f32(const float* W, int ldw, int N, int K, const float* w_rowmax, void* planes, size_t planes_bytes, void* stream) {
-    LS_REQUIRE(W && w_rowmax && planes && N > 0 && K > 0 && ldw >= K && ldw % 4 == 0, "gemm_presplit_w: bad argument");
-    LS_REQUIRE(gemm_w_planes_useful(K), "gemm_presplit_w: no kernel reads planes at K = %d (ls_gemm_w_planes_bytes returns 0)", K);
-    if (planes_bytes < gemm_w_planes_bytes((size_t)N, K)) { set_error("gemm_presplit_w: planes %zu < required %zu (ls_gemm_w_planes_bytes)", planes_bytes, gemm_w_planes_bytes((size_t)N, K)); return LS_ERR_WORKSPACE; }
-    return gemm_presplit_w_launch(W, N, K, ldw, w_rowmax, planes, (hipStream_t)stream);
-}
-int ls_gemm_f32_planes(const float* A, int lda, const float* W, int ldw, const void* w_planes, const float* bias, float* out, int ldc, int M, int N,
-                       int K, int relu, const float* a_rowmax, int a_parts, const float* w_rowmax, float* out_rowmax, void* stream) {
-    LS_REQUIRE(w_planes && w_rowmax, "gemm_planes: w_planes and w_rowmax are required (ls_gemm_presplit_w_f32)");
-    LS_REQUIRE(!a_rowmax || a_parts >= 1, "gemm_planes: a_rowmax needs a_parts >= 1");
-    LS_REQUIRE(gemm_w_planes_useful(K), "gemm_planes: no kernel reads planes at K = %d", K);
-    GemmAux ax;
-    ax.a_rowmax = a_rowmax; ax.a_parts = a_rowmax ? a_parts : 0; ax.w_rowmax = w_rowmax; ax.out_rowmax = out_rowmax; ax.w_planes = w_planes;
-    return gemm_dispatch(A, lda, W, ldw, bias, out, ldc, M, N, K, relu, (hipStream_t)stream, ax);
-}
-int ls_encode_prologue_f32(const float* x, int B, int N, float* pts_out, float* centroid_out, float* scale0_out, void* stream) {
-    LS_REQUIRE(B > 0, "prologue: empty batch");
-    return prologue_launch(x, B, N, pts_out, centroid_out, scale0_out, nullptr, (hipStream_t)stream);
-}
-size_t ls_cosine_scores_workspace_bytes(int n, int m) { return (n > 0 && m > 0) ? (size_t)(n + m) * sizeof(float) : 0; }
-int ls_cosine_scores_f32(const float* m0, const float* m1, int n, int m, int D, float* scores, void* workspace, size_t workspace_bytes,
-                         void* stream) {
-    LS_REQUIRE(n > 0 && m > 0 && D > 0, "cosine_scores: empty problem");
-    LS_REQUIRE(m0 && m1 && scores, "cosine_scores: null argument");
-    if (!workspace || workspace_bytes < ls_cosine_scores_workspace_bytes(n, m)) {   // the n + m inverse row norms
-        set_error("cosine_scores: workspace %zu < required %zu", workspace_bytes, ls_cosine_scores_workspace_bytes(n, m));
-        return LS_ERR_WORKSPACE;
-    }
-    return cosine_scores_launch(m0, m1, n, m, D, (float*)workspace, scores, (hipStream_t)stream);
-}
-int ls_greedy_match_f32(float* scores, int n, int m, int64_t* matches0, int64_t* matches1, void* stream) {
-    LS_REQUIRE(n > 0 && m > 0, "greedy_match: empty problem");
-    return greedy_match_launch(scores, n, m, (long long*)matches0, (long long*)matches1, (hipStream_t)stream);
-}
-int ls_nn_match_f32(const float* scores, int n, int m, int64_t* matches0, int64_t* matches1, void* stream) {
-    LS_REQUIRE(n > 0 && m > 0 && scores && matches0 && matches1, "nn_match: empty problem or null argument");
-    return assign_launch(scores, n, m, 0, 1.0f, 0.0f, 0, 0.0f, (long long*)matches0, (long long*)matches1, (hipStream_t)stream);
-}
-int ls_sinkhorn_match_f32(const float* scores, int n, int m, float score_divisor, float alpha, int iters, float match_threshold, int64_t* matches0,
-                          int64_t* matches1, void* stream) {
-    LS_REQUIRE(n > 0 && m > 0 && scores && matches0 && matches1, "sinkhorn_match: empty problem or null argument");
-    LS_REQUIRE(iters >= 0 && score_divisor != 0.0f, "sinkhorn_match: iters=%d score_divisor=%g", iters, (double)score_divisor);
-    return assign_launch(scores, n, m, 1, score_divisor, alpha, iters, match_threshold, (long long*)matches0, (long long*)matches1, (hipStream_t)stream);
-}
-int ls_kabsch_batched_f32(const float* x1, const float* x2, const float* weights, int b, int n, unsigned flags, float* R, float* t,
-                          float* res, int32_t* flags_out, void* stream) {
-    LS_REQUIRE(b > 0 && n > 0, "kabsch: empty problem");
-    LS_REQUIRE(x1 && x2 && R && t, "kabsch: null argument");
-    return kabsch_launch(x1, x2, weights, b, n, 0, (flags & LS_FLAG_KABSCH_RAW_WEIGHTS) ? 1 : 0, R, t, res, nullptr, flags_out,
-                         (hipStream_t)stream);
-}
-int ls_kabsch_codes_f32(const float* x1, const float* off1, const int64_t* sel1, const float* x2, const float* off2, const int64_t* sel2, int b,
-                        int n, float* R, float* t, float* res, int32_t* flags_out, void* stream) {
-    LS_REQUIRE(b > 0 && n > 0, "kabsch_codes: empty problem");
-    LS_REQUIRE(x1 && x2 && R && t, "kabsch_codes: null argument");
-    return kabsch_launch(x1, x2, nullptr, b, n, 0, 0, R, t, res, nullptr, flags_out, (hipStream_t)stream, off1, off2, (const long long*)sel1,
-                         (const long long*)sel2);
-}
-int ls_kabsch_residual_matrix_f32(const float* src, const float* tgt, int n, int m, int P, float* res, void* stream) {
-    LS_REQUIRE(n > 0 && m > 0 && P > 0, "kabsch_residual_matrix: empty problem");
-    return kabsch_launch(src, tgt, nullptr, n * m, P, m, 0, nullptr, nullptr, nullptr, res, nullptr, (hipStream_t)stream);
-}
-// ---- ragged batches of matching problems (match.hip): every problem's result is bit-identical to the single op on that problem alone
-size_t ls_cosine_scores_batch_workspace_bytes(int P, long long n_total, long long m_total) { return match_batch_workspace_bytes(P, n_total, m_total, 1); }
-size_t ls_greedy_match_batch_workspace_bytes(int P, long long n_total, long long m_total) { return match_batch_workspace_bytes(P, n_total, m_total, 0); }
-size_t ls_nn_match_batch_workspace_bytes(int P, long long n_total, long long m_total) { return match_batch_workspace_bytes(P, n_total, m_total, 0); }
-size_t ls_sinkhorn_match_batch_workspace_bytes(int P, long long n_total, long long m_total) {
-    return match_batch_workspace_bytes(P, n_total, m_total, 0);
-}
-size_t ls_kabsch_residual_matrix_batch_workspace_bytes(int P, long long n_total, long long m_total) {
-    return match_batch_workspace_bytes(P, n_total, m_total, 0);
-}
-int ls_cosine_scores_batch_f32(int P, const float* m0, long long n_total, const long long* src_off, const float* m1, long long m_total,
-                               const long long* tgt_off, int D, float* scores, void* workspace, size_t workspace_bytes, void* stream) {
-    return cosine_scores_batch_launch(P, m0, n_total, src_off, m1, m_total, tgt_off, D, scores, workspace, workspace_bytes, (hipStream_t)stream);
-}
-int ls_greedy_match_batch_f32(int P, float* scores, long long n_total, const long long* src_off, long long m_total, const long long* tgt_off,
-                              int64_t* matches0, int64_t* matches1, void* workspace, size_t workspace_bytes, void* stream) {
-    return greedy_match_batch_launch(P, scores, n_total, src_off, m_total, tgt_off, (long long*)matches0, (long long*)matches1, workspace,
-                                     workspace_bytes, (hipStream_t)stream);
-}
-int ls_nn_match_batch_f32(int P, const float* scores, long long n_total, const long long* src_off, long long m_total, const long long* tgt_off,
-                          int64_t* matches0, int64_t* matches1, void* workspace, size_t workspace_bytes, void* stream) {
-    return assign_batch_launch(P, scores, n_total, src_off, m_total, tgt_off, 0, 1.0f, 0.0f, 0, 0.0f, (long long*)matches0, (long long*)matches1,
-                               workspace, workspace_bytes, (hipStream_t)stream);
-}
-int ls_sinkhorn_match_batch_f32(int P, const float* scores, long long n_total, const long long* src_off, long long m_total, const long long* tgt_off,
-                                float score_divisor, float alpha, int iters, float match_threshold, int64_t* matches0, int64_t* matches1,
-                                void* workspace, size_t workspace_bytes, void* stream) {
-    LS_REQUIRE(iters >= 0 && score_divisor != 0.0f, "sinkhorn_match_batch: iters=%d score_divisor=%g", iters, (double)score_divisor);
-    return assign_batch_launch(P, scores, n_total, src_off, m_total, tgt_off, 1, score_divisor, alpha, iters, match_threshold, (long long*)matches0,
-                               (long long*)matches1, workspace, workspace_bytes, (hipStream_t)stream);
-}
-int ls_kabsch_residual_matrix_batch_f32(int P, const float* src, long long n_total, const long long* src_off, const float* tgt, long long m_total,
-                                        const long long* tgt_off, int C, float* res, void* workspace, size_t workspace_bytes, void* stream) {
-    return kabsch_residual_matrix_batch_launch(P, src, n_total, src_off, tgt, m_total, tgt_off, C, res, workspace, workspace_bytes,
-                                               (hipStream_t)stream);
-}
-size_t ls_icp_workspace_bytes(int b, int n) { return icp_workspace_bytes(b, n); }
-int ls_icp_f32(const float* X, const float* Y, const float* R0, const float* T0, int b, int n, int m, int max_iter,
-               float rel_rmse_thr, unsigned flags, float* R, float* T, float* rmse, int32_t* iters_out, void* workspace,
-               size_t workspace_bytes, void* stream) {
-    return icp_run(X, Y, R0, T0, b, n, m, max_iter, rel_rmse_thr, flags, R, T, rmse, iters_out, workspace, workspace_bytes,
-                   (hipStream_t)stream);
-}
-
 // ------------------------------------------------------------------------------------------------ model
 int ls_model_create(const ls_model_desc* desc, const float* blob_host, ls_model_t** out) {
     LS_REQUIRE(desc && blob_host && out, "model_create: null argument");
@@ -947,7 +699,6 @@ static int encode_enqueue(ls_model_t* m, const EncPlan& p, const float* x, int B
                         z_so3, z_inv, s_out, t_out, st, cur_rm, cur_rm_parts);
 }
 
-namespace ls { int scatter_codes_launch(const float* packed, int B, int c, float* z_so3, float* z_inv, float* s, float* t, hipStream_t st); }
 
 // One encode = ~170 kernel launches, 1.35 ms of host time per 64-instance step in round 1 (the GPU needs 1.6 ms).  The launch
 // sequence depends only on (B, N, flags, workspace), so it is CAPTURED once per such key into a hipGraph (stream capture incl. the

@@ -1,6 +1,6 @@
 // pointwise.hip -- the small HBM-bound kernels around the edge-conv: encode prologue, per-instance mean,
 // point-wise VN activation (residual global conv), and the encoder tail (conv_c pooling + the four heads).
-#include "ls_common.h"
+#include "ls_launch.h"
 
 namespace ls {
 
@@ -559,3 +559,11 @@ int tail_launch(const float* Tc, int ldc, int B, int NP, int Cd, const float* in
 }
 
 }  // namespace ls
+
+using namespace ls;
+extern "C" {
+int ls_encode_prologue_f32(const float* x, int B, int N, float* pts_out, float* centroid_out, float* scale0_out, void* stream) {
+    LS_REQUIRE(B > 0, "prologue: empty batch");
+    return prologue_launch(x, B, N, pts_out, centroid_out, scale0_out, nullptr, (hipStream_t)stream);
+}
+}  // extern "C"

@@ -15,7 +15,7 @@
 // u = [z_inv | query] with the RAW query: W u + b = W_xyz query + (b + W_z z_inv).  The same per-instance rank-4 map serves with
 // A = [W_xyz | 0], applied to the query itself (no t, s, |q|); every kernel below that touches the query or the code comes in both kinds
 // (template flag XYZ), one arithmetic path per kind.
-#include "ls_common.h"
+#include "ls_launch.h"
 
 namespace ls {
 
