@@ -24,6 +24,7 @@
 // neighbour and xyz component), channel chunks of 64; attention heads are 16 consecutive channels = one
 // 16-lane DPP row, so head sums / soft-max reductions are 4-step row shuffles.
 #include "ls_launch.h"
+#include "ls_device.h"
 
 namespace ls {
 
@@ -253,86 +254,7 @@ __global__ __launch_bounds__(256) void edge_attn_kernel(const float* __restrict_
 // (Co = 64/128/256/512 -> 16/32/64/64 lanes, 4/2/1/1 points per wave), an attention head (16 channels) is one DPP
 // quad, and the per-head scores for all 16 neighbours stay in the quad's registers, so the soft-max over neighbours
 // needs no cross-lane traffic and no LDS at all.
-// LS_DPP_NOP=n (dev builds only, scripts/diag/pk_hazard_repro.sh): n + 1 wait states between the instruction that produces a DPP operand and the DPP
-// instruction that reads it from other lanes -- the s_nop sweep of the reproducibility defect described at edge_attn_v4_kernel
-#ifdef LS_DPP_NOP
-#define LS_DPP_STR2(x) #x
-#define LS_DPP_STR(x) LS_DPP_STR2(x)
-#define LS_DPP_FENCE(v) asm volatile("s_nop " LS_DPP_STR(LS_DPP_NOP) : "+v"(v))
-#else
-#define LS_DPP_FENCE(v)
-#endif
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-    LS_DPP_FENCE(v);
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float quad_sum(float v) { return dpp_add<0x4E>(dpp_add<0xB1>(v)); }
-template <int LPP>
-__device__ __forceinline__ float group_sum(float v) {  // all-reduce over aligned groups of LPP lanes
-    v = quad_sum(v);
-    v = dpp_add<0x141>(v);  // row_half_mirror
-    v = dpp_add<0x140>(v);  // row_mirror -> 16-lane sum in every lane
-    if constexpr (LPP >= 32) v += __shfl_xor(v, 16, 64);
-    if constexpr (LPP >= 64) v += __shfl_xor(v, 32, 64);
-    return v;
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_maxf(float v) {
-    LS_DPP_FENCE(v);
-    return fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, 0xF, 0xF, false)));
-}
-template <int LPP>
-__device__ __forceinline__ float group_max(float v) {  // all-reduce (max) over aligned groups of LPP lanes
-    v = dpp_maxf<0x140>(dpp_maxf<0x141>(dpp_maxf<0x4E>(dpp_maxf<0xB1>(v))));
-    if constexpr (LPP >= 32) v = fmaxf(v, __shfl_xor(v, 16, 64));
-    if constexpr (LPP >= 64) v = fmaxf(v, __shfl_xor(v, 32, 64));
-    return v;
-}
-__device__ __forceinline__ float amax_f4(const float4& v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
-
-// 1 / max(sqrt(ss), 1e-12) (channel_equi_vec_normalize's Frobenius norm, vec_layers.py:24-31) as ONE v_rsq_f32 on the clamped square
-// instead of a correctly rounded sqrt + IEEE division (~18 issue slots per neighbour in the K branch); 1 ulp, far inside the tolerance
-__device__ __forceinline__ float inv_fro(float ss) { return __builtin_amdgcn_rsqf(fmaxf(ss, 1e-24f)); }
-
-struct F43 { float4 x, y, z; };  // one xyz triple for four channels
-__device__ __forceinline__ F43 ld43(const float* p, int ldt) {
-    F43 r;
-    r.x = *reinterpret_cast<const float4*>(p);
-    r.y = *reinterpret_cast<const float4*>(p + ldt);
-    r.z = *reinterpret_cast<const float4*>(p + 2 * ldt);
-    return r;
-}
-__device__ __forceinline__ F43 add43(const F43& a, const F43& b) {
-    F43 r;
-    r.x = make_float4(a.x.x + b.x.x, a.x.y + b.x.y, a.x.z + b.x.z, a.x.w + b.x.w);
-    r.y = make_float4(a.y.x + b.y.x, a.y.y + b.y.y, a.y.z + b.y.z, a.y.w + b.y.w);
-    r.z = make_float4(a.z.x + b.z.x, a.z.y + b.z.y, a.z.z + b.z.z, a.z.w + b.z.w);
-    return r;
-}
-// VN activation on four channels in place (y := act(y, k))
-__device__ __forceinline__ void act43(F43& y, const F43& k, float oms) {
-    vn_act(y.x.x, y.y.x, y.z.x, k.x.x, k.y.x, k.z.x, oms);
-    vn_act(y.x.y, y.y.y, y.z.y, k.x.y, k.y.y, k.z.y, oms);
-    vn_act(y.x.z, y.y.z, y.z.z, k.x.z, k.y.z, k.z.z, oms);
-    vn_act(y.x.w, y.y.w, y.z.w, k.x.w, k.y.w, k.z.w, oms);
-}
-// (explicit fma chain, in this order: see vn_act in ls_common.h)
-__device__ __forceinline__ float dot43(const F43& a, const F43& b) {
-    float s = a.x.x * b.x.x;
-    s = __builtin_fmaf(a.y.x, b.y.x, s); s = __builtin_fmaf(a.z.x, b.z.x, s);
-    s = __builtin_fmaf(a.x.y, b.x.y, s); s = __builtin_fmaf(a.y.y, b.y.y, s); s = __builtin_fmaf(a.z.y, b.z.y, s);
-    s = __builtin_fmaf(a.x.z, b.x.z, s); s = __builtin_fmaf(a.y.z, b.y.z, s); s = __builtin_fmaf(a.z.z, b.z.z, s);
-    s = __builtin_fmaf(a.x.w, b.x.w, s); s = __builtin_fmaf(a.y.w, b.y.w, s); s = __builtin_fmaf(a.z.w, b.z.w, s);
-    return s;
-}
-// acc += w * y on an xyz triple of four channels
-__device__ __forceinline__ void fma43(F43& acc, float w, const F43& y) {
-    acc.x.x = __builtin_fmaf(w, y.x.x, acc.x.x); acc.x.y = __builtin_fmaf(w, y.x.y, acc.x.y); acc.x.z = __builtin_fmaf(w, y.x.z, acc.x.z); acc.x.w = __builtin_fmaf(w, y.x.w, acc.x.w);
-    acc.y.x = __builtin_fmaf(w, y.y.x, acc.y.x); acc.y.y = __builtin_fmaf(w, y.y.y, acc.y.y); acc.y.z = __builtin_fmaf(w, y.y.z, acc.y.z); acc.y.w = __builtin_fmaf(w, y.y.w, acc.y.w);
-    acc.z.x = __builtin_fmaf(w, y.z.x, acc.z.x); acc.z.y = __builtin_fmaf(w, y.z.y, acc.z.y); acc.z.z = __builtin_fmaf(w, y.z.z, acc.z.z); acc.z.w = __builtin_fmaf(w, y.z.w, acc.z.w);
-}
+// (dpp_add / dpp_max, quad_sum, group_sum / group_max, amax_f4, inv_fro and the F43 triple: ls_device.h; so is the LS_DPP_NOP development hook)
 
 // ---------------------------------------------------------------------------------------------- pool layers, float4 lanes (round 4)
 // edge_pool_kernel with a lane owning FOUR consecutive channels (16-byte gathers), a point = LPP = Co / 4 lanes, 64 / LPP points per wave: the
@@ -436,7 +358,7 @@ __global__ __launch_bounds__(256) void edge_attn_v4_kernel(const float* __restri
                                                            float oms, float inv_sqrt_dk, float* __restrict__ out, int total,
                                                            float* __restrict__ rowmax, float* __restrict__ colsum) {
     // colsum (nullable, NCH == 1 only) [total / PW][3][Co]: partial column sums of `out`, see attn_colsum
-    // rowmax (nullable) [total * 3]: max|out[row, :]| -- the operand range of the GEMM that reads `out` (gemm.hip, GemmAux)
+    // rowmax (nullable) [total * 3]: max|out[row, :]| -- the operand range of the GEMM that reads `out` (ls_common.h, GemmAux)
     constexpr int PPW = 64 / LPP;
     // lane-private LDS slots ([neighbour][thread]: conflict-free without padding -> 32 KB per chunk pair, five workgroups per CU):
     // head scores per chunk and |k|^2 per neighbour.  Keeping these arrays out of VGPRs lets the neighbour loops stay rolled
@@ -564,43 +486,14 @@ __global__ __launch_bounds__(256) void edge_attn_v4_kernel(const float* __restri
 // 32 x 32, two per wave -- into an LDS slab the phase then reads where the v4 kernel read Tq.  Cost: 144 - 288 MFMAs per workgroup
 // (4 - 8 us per launch chip-wide) and 33 KB of LDS (two workgroups per CU instead of five; measured neutral for the gather itself,
 // DESIGN.md 9).  The neighbour-side tables (P) are unchanged.
-typedef _Float16 eh8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 eh2_t __attribute__((ext_vector_type(2)));
-typedef float ef2_t __attribute__((ext_vector_type(2)));
-typedef float ef16_t __attribute__((ext_vector_type(16)));
-__device__ __forceinline__ void esplit_pair(ef2_t v, unsigned& h, unsigned& l) {
-    const eh2_t hv = __builtin_convertvector(v, eh2_t);
-    const eh2_t lv = __builtin_convertvector(v - __builtin_convertvector(hv, ef2_t), eh2_t);
-    h = __builtin_bit_cast(unsigned, hv);
-    l = __builtin_bit_cast(unsigned, lv);
-}
-// eight consecutive-k fp32 values -> the (hi, lo) MFMA operand fragments of this lane
-__device__ __forceinline__ void esplit8(const float* p, eh8_t& h, eh8_t& l) {
-    const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-    uint4 hh, ll;
-    esplit_pair(ef2_t{a.x, a.y}, hh.x, ll.x); esplit_pair(ef2_t{a.z, a.w}, hh.y, ll.y);
-    esplit_pair(ef2_t{b.x, b.y}, hh.z, ll.z); esplit_pair(ef2_t{b.z, b.w}, hh.w, ll.w);
-    h = __builtin_bit_cast(eh8_t, hh);
-    l = __builtin_bit_cast(eh8_t, ll);
-}
 
 // Wq [rows = 6 Co][Cin] fp32 -> (hi, lo) f16 pieces in MFMA-fragment-major order: [rows / 32 tiles][Cin / 16 steps][hi, lo][64 lanes] x 16 B,
 // lane = (row & 31) + 32 (k / 8 & 1), eight consecutive k: a wave fetches an operand fragment with ONE contiguous 1 KB load.  (Fetching
 // the fragments straight from the row-major fp32 weights -- 32 rows x 32 bytes per load instruction -- made the fused kernel 2x
 // slower than the un-fused one: every load instruction touched 32 cache lines.)  Built once per model (ls_model_create).
-// Operand range (gemm.hip, "operand range of the f16 split"): every weight row is multiplied by its own power of two before the split;
+// Operand range (ls_device.h, "operand range of the f16 split"): every weight row is multiplied by its own power of two before the split;
 // the inverse scales [rows] follow the planes.  The kernel scales its feature rows the same way and multiplies the accumulators by the
 // product of the two inverses -- the same exact scaling the table GEMM applies, so the two paths stay bit-identical.
-__device__ __forceinline__ void epow2_scale(float amax, float& s, float& inv) {
-    unsigned be = (__float_as_uint(amax) >> 23) & 0xffu;
-    be = be < 15u ? 15u : be;
-    s = __uint_as_float((268u - be) << 23);
-    inv = __uint_as_float((be - 14u) << 23);
-}
-template <int CTRL>
-__device__ __forceinline__ float edpp_fmax(float v) {
-    return fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, 0xF, 0xF, false)));
-}
 __global__ __launch_bounds__(64) void edge_presplit_wq_kernel(const float* __restrict__ W, int rows, int Cin, int KS, uint4* __restrict__ planes,
                                                                float* __restrict__ winv) {
     const int tile = blockIdx.x / KS, ks = blockIdx.x % KS, lane = threadIdx.x;
@@ -609,13 +502,13 @@ __global__ __launch_bounds__(64) void edge_presplit_wq_kernel(const float* __res
     float am = 0.f;
     for (int c = 0; c < Cin; ++c) am = fmaxf(am, fabsf(wr[c]));
     float sc, inv;
-    epow2_scale(am, sc, inv);
+    pow2_scale(am, sc, inv);
     if (ks == 0 && lane < 32 && n < rows) winv[n] = inv;
     __attribute__((aligned(16))) float v[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) v[c] = wr[k + c] * sc;
-    eh8_t h, l;
-    esplit8(v, h, l);
+    f16x8_t h, l;
+    split8_f16(v, h, l);
     planes[((size_t)blockIdx.x * 2) * 64 + lane] = __builtin_bit_cast(uint4, h);
     planes[((size_t)blockIdx.x * 2 + 1) * 64 + lane] = __builtin_bit_cast(uint4, l);
 }
@@ -683,13 +576,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void e
         }
         {   // the CIN / 4 = 8 | 16 threads of a row are an aligned lane group: row maximum by DPP, then the row's power of two
             float am = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
-            am = edpp_fmax<0x141>(edpp_fmax<0x4E>(edpp_fmax<0xB1>(am)));
-            if constexpr (CIN == 64) am = edpp_fmax<0x140>(am);
+            am = max8(am);
+            if constexpr (CIN == 64) am = dpp_max<0x140>(am);
             float sc, inv;
-            epow2_scale(am, sc, inv);
-            if (kq == 0) a_inv[r] = (__float_as_int(inv) >> 23) - 127;    // exponent of the exact power of two (gemm.hip: pow2_e / scale_pow2)
-            esplit_pair(ef2_t{v.x * sc, v.y * sc}, h.x, l.x);
-            esplit_pair(ef2_t{v.z * sc, v.w * sc}, h.y, l.y);
+            pow2_scale(am, sc, inv);
+            if (kq == 0) a_inv[r] = pow2_e(inv);    // exponent of the exact power of two (ls_device.h: pow2_e / scale_pow2)
+            split2_f16_pair(f32x2_t{v.x * sc, v.y * sc}, h.x, l.x);
+            split2_f16_pair(f32x2_t{v.z * sc, v.w * sc}, h.y, l.y);
         }
         *reinterpret_cast<uint2*>(&a_pl[0][r * ASTR + kq * 8]) = h;
         *reinterpret_cast<uint2*>(&a_pl[1][r * ASTR + kq * 8]) = l;
@@ -709,16 +602,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void e
         for (int u = 0; u < 2; ++u) {
             const int mt = MT == 2 ? u : 0, nt = MT == 2 ? wave : wave + 4 * u;
             const int aoff = (32 * mt + (lane & 31)) * ASTR + (lane >> 5) * 16;
-            ef16_t acc;
+            f32x16_t acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                const eh8_t ah = __builtin_bit_cast(eh8_t, *reinterpret_cast<const uint4*>(&a_pl[0][aoff + ks * 32]));
-                const eh8_t al = __builtin_bit_cast(eh8_t, *reinterpret_cast<const uint4*>(&a_pl[1][aoff + ks * 32]));
+                const f16x8_t ah = __builtin_bit_cast(f16x8_t, *reinterpret_cast<const uint4*>(&a_pl[0][aoff + ks * 32]));
+                const f16x8_t al = __builtin_bit_cast(f16x8_t, *reinterpret_cast<const uint4*>(&a_pl[1][aoff + ks * 32]));
                 // (MT == 2: both M-tiles of a wave use the same weight tile -- its fragments are loaded once, u = 0)
-                const eh8_t bh = __builtin_bit_cast(eh8_t, wfh[MT == 2 ? 0 : u][ks]);
-                const eh8_t bl = __builtin_bit_cast(eh8_t, wfl[MT == 2 ? 0 : u][ks]);
+                const f16x8_t bh = __builtin_bit_cast(f16x8_t, wfh[MT == 2 ? 0 : u][ks]);
+                const f16x8_t bl = __builtin_bit_cast(f16x8_t, wfl[MT == 2 ? 0 : u][ks]);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
@@ -726,11 +619,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void e
             // C/D map of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5); rows past the workgroup's points: dropped
             const int row0 = 32 * mt + 4 * (lane >> 5);
             float* sp = slab + row0 * SLD + 32 * nt + (lane & 31);
-            const int ce = (__float_as_int(winv[cb + 32 * nt + (lane & 31)]) >> 23) - 127;
+            const int ce = pow2_e(winv[cb + 32 * nt + (lane & 31)]);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int dr = (r & 3) + 8 * (r >> 2);
-                if (row0 + dr < ROWS) sp[dr * SLD] = __builtin_ldexpf(acc[r], a_inv[row0 + dr] + ce);   // acc * s_a^-1 * s_w^-1, exponents added as integers (as gemm.hip)
+                if (row0 + dr < ROWS) sp[dr * SLD] = scale_pow2(acc[r], a_inv[row0 + dr] + ce);   // acc * s_a^-1 * s_w^-1, exponents added as integers (as gemm.hip)
             }
         }
     };
@@ -870,7 +763,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void e
             *reinterpret_cast<float4*>(op + Co) = oy;
             *reinterpret_cast<float4*>(op + 2 * Co) = oz;
         }
-        if (rowmax) {   // wave-uniform: max|out[row, :]| for the GEMM that reads `out` (gemm.hip, GemmAux)
+        if (rowmax) {   // wave-uniform: max|out[row, :]| for the GEMM that reads `out` (ls_common.h, GemmAux)
             const float rmx = group_max<LPP>(amax_f4(ox)), rmy = group_max<LPP>(amax_f4(oy)), rmz = group_max<LPP>(amax_f4(oz));
             if (live && ll == 0) { float* rp = rowmax + (size_t)pid * 3; rp[0] = rmx; rp[1] = rmy; rp[2] = rmz; }
         }

@@ -20,8 +20,8 @@
 // (edge_ft_presplit_w_kernel: tile = (head, column-group pair), rows [lin 16 | dir 16], per-row power-of-two scale), the feature rows once per
 // layer call (edge_ft_prep_a_kernel: per-row power-of-two scale, (hi, lo) f16 planes) -- the same two-piece split, the same three products per
 // 16 k in the same order (l_a h_w, h_a h_w, h_a l_w) into one fp32 accumulator, ascending k, and the same integer-exponent scale in the epilogue as
-// gemm.hip (the row scales come from the exact row maxima; the table GEMM may be handed an upper bound by its producer, so the two paths agree
-// to fp32 round-off, not bit for bit).  The attention arithmetic uses the helpers of edge.hip (vn_act, dot43, fma43: every multiply-add spelled
+// gemm.hip, all taken from ls_device.h (the row scales come from the exact row maxima; the table GEMM may be handed an upper bound by its producer, so the two paths agree
+// to fp32 round-off, not bit for bit).  The attention arithmetic is that of edge.hip through the one copy in ls_device.h (vn_act, dot43, fma43: every multiply-add spelled
 // as an fma); what differs from edge_attn_v4_kernel is the ORDER in which the squared norms are summed over the channels (per head by a DPP quad
 // sum, then over the heads ascending, instead of one 64-lane tree).
 // [The numbers of this paragraph are those of the FIRST form of the GEMM phases (ft_gemm_phase: one 32 x 32 item at a time, resident W tile); the
@@ -39,40 +39,12 @@
 // of LDS) nothing overlaps a workgroup's GEMM phase with another's attention phase except by chance; the structural remedy -- a persistent
 // workgroup per instance whose MFMA waves run one head group ahead of its VALU waves -- is the next step, not a tweak of this one.
 #include "ls_launch.h"
+#include "ls_device.h"
 
 namespace ls {
 
 constexpr int FK = 16;            // neighbours per point
 constexpr int FND = 32;           // destination points per instance (the fused path's shape: layers 5 / 6 of the released schedule)
-typedef _Float16 fh8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 fh2_t __attribute__((ext_vector_type(2)));
-typedef float ff2_t __attribute__((ext_vector_type(2)));
-typedef float ff16_t __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ void fsplit_pair(ff2_t v, unsigned& h, unsigned& l) {
-    const fh2_t hv = __builtin_convertvector(v, fh2_t);
-    const fh2_t lv = __builtin_convertvector(v - __builtin_convertvector(hv, ff2_t), fh2_t);
-    h = __builtin_bit_cast(unsigned, hv);
-    l = __builtin_bit_cast(unsigned, lv);
-}
-// exact powers of two: s * amax in [2^14, 2^15), e = exponent of 1 / s  (gemm.hip: pow2_scale / pow2_e)
-__device__ __forceinline__ void fpow2(float amax, float& s, int& e_inv) {
-    unsigned be = (__float_as_uint(amax) >> 23) & 0xffu;
-    be = be < 15u ? 15u : be;
-    s = __uint_as_float((268u - be) << 23);
-    e_inv = (int)be - 14 - 127;
-}
-template <int CTRL>
-__device__ __forceinline__ float fdpp_max(float v) {
-    return fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, 0xF, 0xF, false)));
-}
-template <int CTRL>
-__device__ __forceinline__ float fdpp_add(float v) {
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float fquad_sum(float v) { return fdpp_add<0x4E>(fdpp_add<0xB1>(v)); }
-__device__ __forceinline__ float fquad_max(float v) { return fdpp_max<0x4E>(fdpp_max<0xB1>(v)); }
-__device__ __forceinline__ float finv_fro(float ss) { return __builtin_amdgcn_rsqf(fmaxf(ss, 1e-24f)); }
 
 // ---------------------------------------------------------------------------------------------------------------- operand images
 // Weight tiles.  W [10 Co][Cin] (column groups PV_lin PV_dir PK_lin PK_dir QV_lin QV_dir QK_lin QK_dir Qq_lin Qq_dir, edge.hip header).
@@ -87,14 +59,11 @@ __global__ __launch_bounds__(64) void edge_ft_presplit_w_kernel(const float* __r
     for (int c = 0; c < Cin; ++c) am = fmaxf(am, fabsf(wr[c]));
     float sc;
     int e;
-    fpow2(am, sc, e);
+    pow2_scale_e(am, sc, e);
     if (ks == 0 && lane < 32) wexp[T * 32 + r] = e;
     const int k = ks * 16 + 8 * (lane >> 5);
     uint4 h, l;
-    fsplit_pair(ff2_t{wr[k] * sc, wr[k + 1] * sc}, h.x, l.x);
-    fsplit_pair(ff2_t{wr[k + 2] * sc, wr[k + 3] * sc}, h.y, l.y);
-    fsplit_pair(ff2_t{wr[k + 4] * sc, wr[k + 5] * sc}, h.z, l.z);
-    fsplit_pair(ff2_t{wr[k + 6] * sc, wr[k + 7] * sc}, h.w, l.w);
+    split8_f16s(make_float4(wr[k], wr[k + 1], wr[k + 2], wr[k + 3]), make_float4(wr[k + 4], wr[k + 5], wr[k + 6], wr[k + 7]), sc, h, l);
     planes[((size_t)blockIdx.x * 2) * 64 + lane] = h;
     planes[((size_t)blockIdx.x * 2 + 1) * 64 + lane] = l;
 }
@@ -134,63 +103,23 @@ __global__ __launch_bounds__(256) void edge_ft_prep_a_kernel(const float* __rest
     for (int kk = 0; kk < KPW; ++kk)
 #pragma unroll
         for (int u = 0; u < 2; ++u)
-            am = fmaxf(am, fmaxf(fmaxf(fabsf(v[kk][u].x), fabsf(v[kk][u].y)), fmaxf(fabsf(v[kk][u].z), fabsf(v[kk][u].w))));
+            am = fmaxf(am, amax_f4(v[kk][u]));
     am = fmaxf(am, __shfl_xor(am, 32, 64));
     if (h == 0) lmax[w][j] = am;
     __syncthreads();
     am = fmaxf(fmaxf(lmax[0][j], lmax[1][j]), fmaxf(lmax[2][j], lmax[3][j]));
     float sc;
     int e;
-    fpow2(am, sc, e);
+    pow2_scale_e(am, sc, e);
     if (w == 0 && h == 0) aexp[R] = e;
 #pragma unroll
     for (int kk = 0; kk < KPW; ++kk) {
         uint4 hh, ll;
-        fsplit_pair(ff2_t{v[kk][0].x * sc, v[kk][0].y * sc}, hh.x, ll.x);
-        fsplit_pair(ff2_t{v[kk][0].z * sc, v[kk][0].w * sc}, hh.y, ll.y);
-        fsplit_pair(ff2_t{v[kk][1].x * sc, v[kk][1].y * sc}, hh.z, ll.z);
-        fsplit_pair(ff2_t{v[kk][1].z * sc, v[kk][1].w * sc}, hh.w, ll.w);
+        split8_f16s(v[kk][0], v[kk][1], sc, hh, ll);
         uint4* op = planes + (((size_t)blockIdx.x * KS + w * KPW + kk) * 2) * 64 + lane;
         op[0] = hh;
         op[64] = ll;
     }
-}
-
-// ---------------------------------------------------------------------------------------------------------------- shared pieces
-struct FT43 { float4 x, y, z; };
-__device__ __forceinline__ FT43 ft_lds43(const float* p, int sld) {
-    FT43 r;
-    r.x = *reinterpret_cast<const float4*>(p);
-    r.y = *reinterpret_cast<const float4*>(p + sld);
-    r.z = *reinterpret_cast<const float4*>(p + 2 * sld);
-    return r;
-}
-__device__ __forceinline__ FT43 ft_add43(const FT43& a, const FT43& b) {
-    FT43 r;
-    r.x = make_float4(a.x.x + b.x.x, a.x.y + b.x.y, a.x.z + b.x.z, a.x.w + b.x.w);
-    r.y = make_float4(a.y.x + b.y.x, a.y.y + b.y.y, a.y.z + b.y.z, a.y.w + b.y.w);
-    r.z = make_float4(a.z.x + b.z.x, a.z.y + b.z.y, a.z.z + b.z.z, a.z.w + b.z.w);
-    return r;
-}
-__device__ __forceinline__ void ft_act43(FT43& y, const FT43& k, float oms) {
-    vn_act(y.x.x, y.y.x, y.z.x, k.x.x, k.y.x, k.z.x, oms);
-    vn_act(y.x.y, y.y.y, y.z.y, k.x.y, k.y.y, k.z.y, oms);
-    vn_act(y.x.z, y.y.z, y.z.z, k.x.z, k.y.z, k.z.z, oms);
-    vn_act(y.x.w, y.y.w, y.z.w, k.x.w, k.y.w, k.z.w, oms);
-}
-// (explicit fma chain, the order of edge.hip's dot43)
-__device__ __forceinline__ float ft_dot43(const FT43& a, const FT43& b) {
-    float s = a.x.x * b.x.x;
-    s = __builtin_fmaf(a.y.x, b.y.x, s); s = __builtin_fmaf(a.z.x, b.z.x, s);
-    s = __builtin_fmaf(a.x.y, b.x.y, s); s = __builtin_fmaf(a.y.y, b.y.y, s); s = __builtin_fmaf(a.z.y, b.z.y, s);
-    s = __builtin_fmaf(a.x.z, b.x.z, s); s = __builtin_fmaf(a.y.z, b.y.z, s); s = __builtin_fmaf(a.z.z, b.z.z, s);
-    s = __builtin_fmaf(a.x.w, b.x.w, s); s = __builtin_fmaf(a.y.w, b.y.w, s); s = __builtin_fmaf(a.z.w, b.z.w, s);
-    return s;
-}
-__device__ __forceinline__ void ft_fma43(FT43& acc, float w, const FT43& y) {
-    acc.x.x = __builtin_fmaf(w, y.x.x, acc.x.x); acc.x.y = __builtin_fmaf(w, y.x.y, acc.x.y); acc.x.z = __builtin_fmaf(w, y.x.z, acc.x.z); acc.x.w = __builtin_fmaf(w, y.x.w, acc.x.w);
-    acc.y.x = __builtin_fmaf(w, y.y.x, acc.y.x); acc.y.y = __builtin_fmaf(w, y.y.y, acc.y.y); acc.y.z = __builtin_fmaf(w, y.y.z, acc.y.z); acc.y.w = __builtin_fmaf(w, y.y.w, acc.y.w);
-    acc.z.x = __builtin_fmaf(w, y.z.x, acc.z.x); acc.z.y = __builtin_fmaf(w, y.z.y, acc.z.y); acc.z.z = __builtin_fmaf(w, y.z.z, acc.z.z); acc.z.w = __builtin_fmaf(w, y.z.w, acc.z.w);
 }
 
 // One "job" of a phase: slab[rows of the instance][HG heads x (lin 16 | dir 16)] = A rows . W tile^T for weight pair `p` of the workgroup's heads.
@@ -217,24 +146,24 @@ __device__ __forceinline__ void ft_gemm_unit(const FtJob<KS>& jb, int tile0, int
     const char* ab = reinterpret_cast<const char*>(jb.a_planes + ((size_t)(jb.mt0 + tile0) * KS * 2) * 64);
     const char* wb = reinterpret_cast<const char*>(wplanes + ((size_t)T * KS * 2) * 64);
     const int we = wexp[T * 32 + (lane & 31)];
-    ff16_t acc[MPU];
+    f32x16_t acc[MPU];
 #pragma unroll
     for (int m = 0; m < MPU; ++m)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
     unsigned voff = (unsigned)lane * 16u;
     constexpr int KB = 2;   // k-steps per batch
-    struct Stage { fh8_t ah[MPU][KB], al[MPU][KB], bh[KB], bl[KB]; };
+    struct Stage { f16x8_t ah[MPU][KB], al[MPU][KB], bh[KB], bl[KB]; };
     auto load_stage = [&](Stage& sg, int k0) {
         asm volatile("" : "+v"(voff));
 #pragma unroll
         for (int u = 0; u < KB; ++u) {
-            sg.bh[u] = __builtin_bit_cast(fh8_t, *reinterpret_cast<const uint4*>(wb + (size_t)((k0 + u) * 2) * 1024 + voff));
-            sg.bl[u] = __builtin_bit_cast(fh8_t, *reinterpret_cast<const uint4*>(wb + (size_t)((k0 + u) * 2 + 1) * 1024 + voff));
+            sg.bh[u] = __builtin_bit_cast(f16x8_t, *reinterpret_cast<const uint4*>(wb + (size_t)((k0 + u) * 2) * 1024 + voff));
+            sg.bl[u] = __builtin_bit_cast(f16x8_t, *reinterpret_cast<const uint4*>(wb + (size_t)((k0 + u) * 2 + 1) * 1024 + voff));
 #pragma unroll
             for (int m = 0; m < MPU; ++m) {
-                sg.ah[m][u] = __builtin_bit_cast(fh8_t, *reinterpret_cast<const uint4*>(ab + (size_t)((m * KS + k0 + u) * 2) * 1024 + voff));
-                sg.al[m][u] = __builtin_bit_cast(fh8_t, *reinterpret_cast<const uint4*>(ab + (size_t)((m * KS + k0 + u) * 2 + 1) * 1024 + voff));
+                sg.ah[m][u] = __builtin_bit_cast(f16x8_t, *reinterpret_cast<const uint4*>(ab + (size_t)((m * KS + k0 + u) * 2) * 1024 + voff));
+                sg.al[m][u] = __builtin_bit_cast(f16x8_t, *reinterpret_cast<const uint4*>(ab + (size_t)((m * KS + k0 + u) * 2 + 1) * 1024 + voff));
             }
         }
     };
@@ -270,7 +199,7 @@ __device__ __forceinline__ void ft_gemm_unit(const FtJob<KS>& jb, int tile0, int
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int dr = (r & 3) + 8 * (r >> 2);
-            sp[dr * jb.sld] = __builtin_ldexpf(acc[m][r], ae[dr] + we);
+            sp[dr * jb.sld] = scale_pow2(acc[m][r], ae[dr] + we);
         }
     }
 }
@@ -325,7 +254,7 @@ __device__ __forceinline__ void ft_gemm_phase_shared(const FtJob<KS> (&jobs)[NJ]
     const char* ab = reinterpret_cast<const char*>(jobs[0].a_planes + ((size_t)jobs[0].mt0 * KS * 2) * 64);     // (every job: the same three M-tiles)
     const char* wb = reinterpret_cast<const char*>(wplanes + ((size_t)T * KS * 2) * 64);
     const int we = wexp[T * 32 + (lane & 31)];
-    ff16_t acc[3];
+    f32x16_t acc[3];
 #pragma unroll
     for (int m = 0; m < 3; ++m)
 #pragma unroll
@@ -356,15 +285,15 @@ __device__ __forceinline__ void ft_gemm_phase_shared(const FtJob<KS> (&jobs)[NJ]
         rb[(wave * 3 + 0) * 64 + lane] = S##_r0;                                                                                                   \
         rb[(wave * 3 + 1) * 64 + lane] = S##_r1;                                                                                                   \
         rb[(wave * 3 + 2) * 64 + lane] = S##_r2;                                                                                                   \
-        const fh8_t bh0 = __builtin_bit_cast(fh8_t, S##_w0), bl0 = __builtin_bit_cast(fh8_t, S##_w1), bh1 = __builtin_bit_cast(fh8_t, S##_w2),     \
-                    bl1 = __builtin_bit_cast(fh8_t, S##_w3);                                                                                       \
+        const f16x8_t bh0 = __builtin_bit_cast(f16x8_t, S##_w0), bl0 = __builtin_bit_cast(f16x8_t, S##_w1), bh1 = __builtin_bit_cast(f16x8_t, S##_w2),     \
+                    bl1 = __builtin_bit_cast(f16x8_t, S##_w3);                                                                                       \
         if ((BI) + 3 < NB) LS_FT_LOAD_BATCH(S, 2 * ((BI) + 3))                                                                                     \
         __syncthreads();                                                                                                                           \
         if (has_unit) {                                                                                                                            \
             _Pragma("unroll") for (int u = 0; u < 2; ++u) {                                                                                        \
-                const fh8_t bh = u ? bh1 : bh0, bl = u ? bl1 : bl0;                                                                                \
+                const f16x8_t bh = u ? bh1 : bh0, bl = u ? bl1 : bl0;                                                                                \
                 _Pragma("unroll") for (int m = 0; m < 3; ++m) {                                                                                    \
-                    const fh8_t ah = __builtin_bit_cast(fh8_t, rb[(u * 6 + m * 2) * 64 + lane]), al = __builtin_bit_cast(fh8_t, rb[(u * 6 + m * 2 + 1) * 64 + lane]); \
+                    const f16x8_t ah = __builtin_bit_cast(f16x8_t, rb[(u * 6 + m * 2) * 64 + lane]), al = __builtin_bit_cast(f16x8_t, rb[(u * 6 + m * 2 + 1) * 64 + lane]); \
                     acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[m], 0, 0, 0);                                                      \
                     acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[m], 0, 0, 0);                                                      \
                     acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[m], 0, 0, 0);                                                      \
@@ -392,7 +321,7 @@ __device__ __forceinline__ void ft_gemm_phase_shared(const FtJob<KS> (&jobs)[NJ]
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int dr = (r & 3) + 8 * (r >> 2);
-                sp[dr * jb.sld] = __builtin_ldexpf(acc[m][r], ae[dr] + we);
+                sp[dr * jb.sld] = scale_pow2(acc[m][r], ae[dr] + we);
             }
         }
     }
@@ -438,12 +367,12 @@ __global__ __launch_bounds__(256, 2) void edge_ft_qk_kernel(const uint4* __restr
     }
     __syncthreads();
     const int c4 = mp.hl * 32 + mp.ql * 4;
-    FT43 qf = ft_lds43(slab_q + (size_t)(3 * mp.n) * SLD + c4, SLD);
+    F43 qf = ld43(slab_q + (size_t)(3 * mp.n) * SLD + c4, SLD);
     {
-        const FT43 kd = ft_lds43(slab_q + (size_t)(3 * mp.n) * SLD + c4 + 16, SLD);
-        ft_act43(qf, kd, oms);
+        const F43 kd = ld43(slab_q + (size_t)(3 * mp.n) * SLD + c4 + 16, SLD);
+        act43(qf, kd, oms);
     }
-    const float ssq = fquad_sum(ft_dot43(qf, qf));
+    const float ssq = quad_sum(dot43(qf, qf));
     if (mp.ql == 0 && mp.k0 == 0) ssqp[((size_t)b * H + head) * FND + mp.n] = ssq;
     int nb[FK];
     {
@@ -462,18 +391,18 @@ __global__ __launch_bounds__(256, 2) void edge_ft_qk_kernel(const uint4* __restr
     }
     __syncthreads();
     {
-        const FT43 ql = ft_lds43(slab_q + (size_t)(3 * mp.n) * SLD + c4, SLD), qd = ft_lds43(slab_q + (size_t)(3 * mp.n) * SLD + c4 + 16, SLD);
+        const F43 ql = ld43(slab_q + (size_t)(3 * mp.n) * SLD + c4, SLD), qd = ld43(slab_q + (size_t)(3 * mp.n) * SLD + c4 + 16, SLD);
         float* so = scores + (((size_t)b * H + head) * FND + mp.n) * FK + mp.k0;
         float* ko = sskp + (((size_t)b * H + head) * FND + mp.n) * FK + mp.k0;
 #pragma unroll
         for (int k = 0; k < FK; ++k) {
             if (k < mp.kn) {
                 const float* pr = slab_p + (size_t)(3 * nb[k]) * SLD + c4;
-                FT43 y = ft_add43(ft_lds43(pr, SLD), ql);
-                const FT43 kd = ft_add43(ft_lds43(pr + 16, SLD), qd);
-                ft_act43(y, kd, oms);
-                const float s2 = fquad_sum(ft_dot43(y, y));
-                const float a = fquad_sum(ft_dot43(y, qf));
+                F43 y = add43(ld43(pr, SLD), ql);
+                const F43 kd = add43(ld43(pr + 16, SLD), qd);
+                act43(y, kd, oms);
+                const float s2 = quad_sum(dot43(y, y));
+                const float a = quad_sum(dot43(y, qf));
                 if (mp.ql == 0) { so[k] = a; ko[k] = s2; }
             }
         }
@@ -503,8 +432,8 @@ __global__ __launch_bounds__(256) void edge_ft_norms_kernel(const float* __restr
             for (int u = 0; u < 8; ++u) s += v[u];
         }
         for (; h < H; ++h) s += sp[(size_t)h * stride];
-        if (isk) invk[(size_t)b * FND * FK + e] = finv_fro(s);
-        else invq[(size_t)b * FND + (e - FND * FK)] = finv_fro(s);
+        if (isk) invk[(size_t)b * FND * FK + e] = inv_fro(s);
+        else invq[(size_t)b * FND + (e - FND * FK)] = inv_fro(s);
     }
 }
 
@@ -573,18 +502,18 @@ __global__ __launch_bounds__(256, 2) void edge_ft_v_kernel(const uint4* __restri
     }
     // ---- out = sum_k softmax_k * VecLNA_V(E[n, k])  (:208,216-219)
     const int c4 = mp.hl * 32 + mp.ql * 4;
-    FT43 acc;
+    F43 acc;
     acc.x = acc.y = acc.z = make_float4(0.f, 0.f, 0.f, 0.f);
     {
-        const FT43 ql = ft_lds43(slab_q + (size_t)(3 * mp.n) * SLD + c4, SLD), qd = ft_lds43(slab_q + (size_t)(3 * mp.n) * SLD + c4 + 16, SLD);
+        const F43 ql = ld43(slab_q + (size_t)(3 * mp.n) * SLD + c4, SLD), qd = ld43(slab_q + (size_t)(3 * mp.n) * SLD + c4 + 16, SLD);
 #pragma unroll
         for (int k = 0; k < FK; ++k) {
             if (k >= mp.k0 && k < mp.k0 + mp.kn) {
                 const float* pr = slab_p + (size_t)(3 * nb[k]) * SLD + c4;
-                FT43 y = ft_add43(ft_lds43(pr, SLD), ql);
-                const FT43 kd = ft_add43(ft_lds43(pr + 16, SLD), qd);
-                ft_act43(y, kd, oms);
-                ft_fma43(acc, wgt[k], y);
+                F43 y = add43(ld43(pr, SLD), ql);
+                const F43 kd = add43(ld43(pr + 16, SLD), qd);
+                act43(y, kd, oms);
+                fma43(acc, wgt[k], y);
             }
         }
     }
@@ -606,8 +535,7 @@ __global__ __launch_bounds__(256, 2) void edge_ft_v_kernel(const uint4* __restri
         *reinterpret_cast<float4*>(op + 2 * Co) = oz;
     }
     if (rowmax) {   // max |out[row, the workgroup's 16 HG channels]| -> part hg of the row's maxima (GemmAux: a_parts = Co / (16 HG))
-        auto amax4 = [](const float4& v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); };
-        float rx = fquad_max(amax4(ox)), ry = fquad_max(amax4(oy)), rz = fquad_max(amax4(oz));
+        float rx = quad_max(amax_f4(ox)), ry = quad_max(amax_f4(oy)), rz = quad_max(amax_f4(oz));
         if constexpr (HG == 2) {   // the two heads of a point sit four lanes apart
             rx = fmaxf(rx, __shfl_xor(rx, 4, 64)); ry = fmaxf(ry, __shfl_xor(ry, 4, 64)); rz = fmaxf(rz, __shfl_xor(rz, 4, 64));
         }

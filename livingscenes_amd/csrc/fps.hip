@@ -12,10 +12,10 @@
 //     re-read from L2 each step, two-level (wave shuffle + LDS) arg-max.  Used for raw clouds up to 65536 pts.
 // Tie rule everywhere: larger value wins, equal values -> smaller index wins (== first arg-max).
 #include "ls_launch.h"
+#include "ls_device.h"
 
 namespace ls {
 
-typedef float fps_f2 __attribute__((ext_vector_type(2)));
 template <bool FMA>
 __device__ __forceinline__ float dist3(float ax, float ay, float az, float bx, float by, float bz) {
 #pragma clang fp contract(off)
@@ -213,11 +213,11 @@ __global__ __launch_bounds__(256) void fps_quad_kernel(const float* __restrict__
         float dd[PPT];
         if constexpr (!FMA && PPT % 2 == 0) {
 #pragma clang fp contract(off)
-            const fps_f2 l2x = {lx, lx}, l2y = {ly, ly}, l2z = {lz0, lz0};
+            const f32x2_t l2x = {lx, lx}, l2y = {ly, ly}, l2z = {lz0, lz0};
 #pragma unroll
             for (int i = 0; i < PPT; i += 2) {
-                const fps_f2 dx = l2x - fps_f2{px[i], px[i + 1]}, dy = l2y - fps_f2{py[i], py[i + 1]}, dz = l2z - fps_f2{pz[i], pz[i + 1]};
-                fps_f2 d = dx * dx;
+                const f32x2_t dx = l2x - f32x2_t{px[i], px[i + 1]}, dy = l2y - f32x2_t{py[i], py[i + 1]}, dz = l2z - f32x2_t{pz[i], pz[i + 1]};
+                f32x2_t d = dx * dx;
                 d = d + dy * dy;
                 d = d + dz * dz;
                 dd[i] = d.x; dd[i + 1] = d.y;

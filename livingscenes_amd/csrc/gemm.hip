@@ -26,13 +26,12 @@
 // product is unchanged.  Next-tile global loads are issued before the MFMA block (register double buffer).
 #include <atomic>
 #include "ls_launch.h"
+#include "ls_device.h"
 #include <string.h>
 #include <algorithm>
 
 namespace ls {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
@@ -57,8 +56,7 @@ __device__ __forceinline__ void split3_bf16(const float4& v, uint2& p1, uint2& p
 }
 
 
-// ---- fp32 GEMM on the f16 matrix cores ("2 x f16 split", PIECES = 22).  a = h + l with h = f16(a) (11 significant bits) and
-// l = f16(a - h) (the residual is exact in fp32 and keeps 11 more bits while it is a normal f16): |a - (h + l)| <= 2^-22 |a|.  The
+// ---- fp32 GEMM on the f16 matrix cores ("2 x f16 split", PIECES = 22).  a = h + l, |a - (h + l)| <= 2^-22 |a| (ls_device.h: split2_f16_pair).  The
 // matrix core takes f16 subnormals as they are (scripts/ubench/f16_denorm.hip), so a residual below 2^-14 degrades gracefully: its
 // absolute error never exceeds 2^-25.  a b = h_a h_b + h_a l_b + l_a h_b + O(2^-21 |a b|): THREE v_mfma_f32_32x32x16_f16 per 16 k,
 // accumulated -- in the order l_a h_b, h_a h_b, h_a l_b, in every kernel of this file and in the fused attention kernel, which is what
@@ -67,60 +65,8 @@ __device__ __forceinline__ void split3_bf16(const float4& v, uint2& p1, uint2& p
 // result is as close as an fp32 FMA chain's (scripts/gemm_microbench.py --check on badly scaled operands: 6.6 - 9.6 units of
 // 2^-24 sum|a||w| at K = 32 .. 768; an fp32 FMA chain: 8 - 13 -- the fp32 accumulation error any fp32 GEMM carries) at half the
 // matrix-pipe time of the three-piece bf16 split and three VALU instructions per split value.  The f16 range is made to follow every
-// operand ROW by an exact power-of-two scale: "operand range of the f16 split" below.  LS_GEMM_MODE=bf16x3 keeps the six-MFMA split.
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ void split2_f16_pair(f32x2_t v, unsigned& h, unsigned& l) {
-    const f16x2_t hv = __builtin_convertvector(v, f16x2_t);
-    const f16x2_t lv = __builtin_convertvector(v - __builtin_convertvector(hv, f32x2_t), f16x2_t);
-    h = __builtin_bit_cast(unsigned, hv);
-    l = __builtin_bit_cast(unsigned, lv);
-}
-__device__ __forceinline__ void split2_f16(const float4& v, uint2& h, uint2& l) {
-    split2_f16_pair(f32x2_t{v.x, v.y}, h.x, l.x);
-    split2_f16_pair(f32x2_t{v.z, v.w}, h.y, l.y);
-}
-// ---- operand range of the f16 split.  f16 covers 2^-14 .. 65504, fp32 features and gradients do not stay there (a trained encoder's
-// conv_c outputs sit at ~1.5e-5 because the heads multiply by scale_factor = 64000, vec_dgcnn_atten.py:234-250; the gradients of the
-// pose refinement at 1e-6 .. 1e-8).  So every ROW of A and every row of W is multiplied by its own exact power of two before the split --
-// s = 2^(14 - floor(log2 max|row|)): the row's largest element lands in [2^14, 2^15), elements down to 2^-17 of it keep the full 22
-// bits (their residual is still a normal f16), below that the absolute error is at most 2^-39 of the row maximum -- 2^-15 of the
-// fp32 rounding of the row's largest term -- and the product of the two inverse scales multiplies the fp32 accumulators in
-// the epilogue.  Powers of two commute with every rounding in between, so for data that was in range before the result is
-// BIT-IDENTICAL to the unscaled split, any finite fp32 input is handled, and a row's result depends on that row's data only.
-// The row maxima come from (a) a pre-pass of the kernel over its own operand rows (default), or (b) caller-supplied arrays
-// (GemmAux: the decoder chains them from the previous layer's epilogue, weights carry theirs from ls_model_create), which may be
-// any upper bound: each factor of two of slack costs one bit at the bottom of the 17-binade window.
-// (struct GemmAux: ls_common.h)
-__device__ __forceinline__ float amax4(float m, const float4& v) {
-    return fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-}
-// exact powers of two: s * amax in [2^14, 2^15), inv = 1 / s.  amax = 0 (or fp32-subnormal) -> s = 2^126; Inf / NaN rows stay non-finite.
-__device__ __forceinline__ void pow2_scale(float amax, float& s, float& inv) {
-    unsigned be = (__float_as_uint(amax) >> 23) & 0xffu;
-    be = be < 15u ? 15u : be;
-    s = __uint_as_float((268u - be) << 23);
-    inv = __uint_as_float((be - 14u) << 23);
-}
-// The epilogue's acc * s_a^-1 * s_w^-1: both inverse scales are exact NORMAL powers of two (pow2_scale), so their exponents are kept as
-// integers (pow2_e), added, and applied by ONE v_ldexp_f32 -- exact wherever fp32 holds the result, rounded once into the subnormals, never
-// an intermediate overflow.  (Until round 4 the two floats were multiplied first: that product flushes to 0 below 2^-149 -- two operand rows
-// at ~1e-19 each -- although acc times it can be a normal number.)  In range the result is bit-identical to the multiply.
-__device__ __forceinline__ int pow2_e(float p) { return (__float_as_int(p) >> 23) - 127; }
-__device__ __forceinline__ float scale_pow2(float acc, int e) { return __builtin_ldexpf(acc, e); }
-template <int CTRL>
-__device__ __forceinline__ float dpp_fmax(float v) {
-    return fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, 0xF, 0xF, false)));
-}
-// max over aligned groups of 8 lanes (the 8 staging threads of one operand row) / 16 lanes, in every lane of the group
-__device__ __forceinline__ float max8(float v) { return dpp_fmax<0x141>(dpp_fmax<0x4E>(dpp_fmax<0xB1>(v))); }
-__device__ __forceinline__ float max16(float v) { return dpp_fmax<0x140>(max8(v)); }
-// split of s * v (s: the row's power of two); the multiply is spelled as packed fp32 (v_pk_mul_f32: the file is built without SLP vectorisation)
-__device__ __forceinline__ void split2_f16s(const float4& v, float s, uint2& h, uint2& l) {
-    const f32x2_t sv = {s, s};
-    split2_f16_pair(f32x2_t{v.x, v.y} * sv, h.x, l.x);
-    split2_f16_pair(f32x2_t{v.z, v.w} * sv, h.y, l.y);
-}
+// operand ROW by an exact power-of-two scale: "operand range of the f16 split" in ls_device.h.  LS_GEMM_MODE=bf16x3 keeps the six-MFMA split.
+// ---- operand range of the f16 split: ls_device.h (pow2_scale, pow2_e, scale_pow2; the split itself and max8 / max16 live there too)
 
 constexpr int GM = 128, GN = 128, GK = 16, GLD = 20;
 
@@ -221,7 +167,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
     out += (size_t)blockIdx.y * slab_stride;
 
     constexpr bool H2 = PIECES == 22;   // two f16 pieces (see split2_f16)
-    f32x16 acc[2][2];
+    f32x16_t acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -464,7 +410,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
     const int kbeg = blockIdx.y * kchunk, kend = min(K, kbeg + kchunk);
     out += (size_t)blockIdx.y * slab_stride;
 
-    f32x16 acc[2][2];
+    f32x16_t acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -708,7 +654,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void g
     const int tm = tile / ntiles_n, tn = tile % ntiles_n;
     const int m0 = tm * TM, n0 = tn * TN;
 
-    f32x16 acc[4][2];
+    f32x16_t acc[4][2];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -937,7 +883,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
     const int wm = wave >> 1, wn = wave & 1;
     const int kbeg = 0, kend = K;
 
-    f32x16 acc[2][2];
+    f32x16_t acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1205,7 +1151,7 @@ __global__ __launch_bounds__(256) void gemm_smallk_kernel(const float* __restric
         // (unconditional: the last iteration re-reads its own tile rather than branching around the loads)
         LS_LOAD_A_TILE(min(tm + per_n, ntiles_m - 1))
 
-        f32x16 acc[2][2];
+        f32x16_t acc[2][2];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1358,7 +1304,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
         __syncthreads();
         load_tile(min(tm + per_n, ntiles_m - 1));      // next A tile in flight under the MFMAs and the stores (last iteration: re-reads its own)
 
-        f32x16 acc[2][2];
+        f32x16_t acc[2][2];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1526,7 +1472,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
         __syncthreads();
         load_tile(min(tm + per_n, ntiles_m - 1));      // next A tile in flight under the MFMAs, the activation and the stores
 
-        f32x16 acc[2][2];
+        f32x16_t acc[2][2];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1745,7 +1691,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
         float sa, ia;
         pow2_scale(rma, sa, ia);
         const int ea_own = pow2_e(ia);
-        f32x16 acc[2];
+        f32x16_t acc[2];
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll

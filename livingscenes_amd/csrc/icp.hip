@@ -8,6 +8,7 @@
 // ORIGINAL X onto the matched points (means, 3x3 covariance / n, SVD, det fix), rmse, relative-improvement stop.
 // Each problem stops on its own criterion (a batched call == independent batch-1 reference calls).
 #include "ls_common.h"
+#include "ls_device.h"
 #include "svd3.h"
 
 namespace ls {
@@ -27,6 +28,7 @@ __device__ __forceinline__ float d3(float ax, float ay, float az, float bx, floa
     return d;
 }
 
+// (sixteen wave sums, left to right from 0: its own order of additions, not a wider block_sum_256 -- ls_device.h, merge rule)
 __device__ __forceinline__ float block_sum_1024(float v, float* red) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     v = wave_sum(v);

@@ -99,13 +99,13 @@ __global__ __launch_bounds__(256, 3) void knn_kernel(const float* __restrict__ d
 
     for (int s0 = s_begin; s0 < s_end; s0 += KNN_TS) {
         float acc[4][4];      // raw clouds (CC == 1)
-        f32x2 acc2[4][2];     // feature layers: [query][candidate pair] x (even, odd candidate)
+        f32x2_t acc2[4][2];     // feature layers: [query][candidate pair] x (even, odd candidate)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[i][j] = 0.0f;
 #pragma unroll
-            for (int j = 0; j < 2; ++j) acc2[i][j] = f32x2{0.0f, 0.0f};
+            for (int j = 0; j < 2; ++j) acc2[i][j] = f32x2_t{0.0f, 0.0f};
         }
 
         if constexpr (CC == 1) {
@@ -149,21 +149,21 @@ __global__ __launch_bounds__(256, 3) void knn_kernel(const float* __restrict__ d
 #pragma unroll 1
                 for (int d4 = 0; d4 < 3 * CC; d4 += 4) {
                     float4 qv[4];
-                    f32x2 cp[2][4];  // [candidate pair][dim] = (c_{2pm}.d, c_{2pm+1}.d)
+                    f32x2_t cp[2][4];  // [candidate pair][dim] = (c_{2pm}.d, c_{2pm+1}.d)
 #pragma unroll
                     for (int i = 0; i < 4; ++i) qv[i] = *reinterpret_cast<const float4*>(&lq[(ty * 4 + i) * ROW + d4]);
 #pragma unroll
                     for (int jj = 0; jj < 2; ++jj) {
                         const float4 lo = *reinterpret_cast<const float4*>(&lc[(tx + 16 * jj) * PR + d4 * 2]);
                         const float4 hi = *reinterpret_cast<const float4*>(&lc[(tx + 16 * jj) * PR + d4 * 2 + 4]);
-                        cp[jj][0] = f32x2{lo.x, lo.y}; cp[jj][1] = f32x2{lo.z, lo.w};
-                        cp[jj][2] = f32x2{hi.x, hi.y}; cp[jj][3] = f32x2{hi.z, hi.w};
+                        cp[jj][0] = f32x2_t{lo.x, lo.y}; cp[jj][1] = f32x2_t{lo.z, lo.w};
+                        cp[jj][2] = f32x2_t{hi.x, hi.y}; cp[jj][3] = f32x2_t{hi.z, hi.w};
                     }
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
 #pragma unroll
                         for (int jj = 0; jj < 2; ++jj) {
-                            f32x2 a = acc2[i][jj];  // canonical order j = c*3+x == LDS dim order
+                            f32x2_t a = acc2[i][jj];  // canonical order j = c*3+x == LDS dim order
                             a = accq2<FMA>(a, qv[i].x, cp[jj][0]); a = accq2<FMA>(a, qv[i].y, cp[jj][1]);
                             a = accq2<FMA>(a, qv[i].z, cp[jj][2]); a = accq2<FMA>(a, qv[i].w, cp[jj][3]);
                             acc2[i][jj] = a;

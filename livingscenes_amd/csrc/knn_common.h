@@ -1,6 +1,6 @@
 // knn_common.h -- pieces shared by the two k-NN kernels (knn.hip: all-VALU; knn_mfma.hip: MFMA-filtered)
 #pragma once
-#include "ls_common.h"
+#include "ls_device.h"
 
 namespace ls {
 
@@ -22,18 +22,17 @@ __device__ __forceinline__ float accq(float d, float a, float b) {
 }
 
 typedef unsigned long long u64;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // two canonical accumulations at once (two candidates, same query value): maps onto v_pk_add / v_pk_mul (/ v_pk_fma)
 template <bool FMA>
-__device__ __forceinline__ f32x2 accq2(f32x2 d, float q, f32x2 c) {
+__device__ __forceinline__ f32x2_t accq2(f32x2_t d, float q, f32x2_t c) {
 #pragma clang fp contract(off)
-    const f32x2 qq = {q, q};
-    const f32x2 diff = qq - c;
+    const f32x2_t qq = {q, q};
+    const f32x2_t diff = qq - c;
     if constexpr (FMA) {
         return __builtin_elementwise_fma(diff, diff, d);
     } else {
-        const f32x2 p = diff * diff;
+        const f32x2_t p = diff * diff;
         return d + p;
     }
 }

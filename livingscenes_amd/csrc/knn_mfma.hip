@@ -20,8 +20,6 @@
 
 namespace ls {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 
 // Canonical distance of 16 (query row, candidate row) pairs per wave-instruction stream.  A lane that walks its own 384-byte
 // rows makes every load touch 64 different cache lines for 16 useful bytes each (the vector L1 handles one line per cycle:
@@ -98,7 +96,7 @@ __device__ __forceinline__ float quad_pair_distance(const QuadRow<CC>& q0, const
 // ---------------------------------------------------------------------------------------------------------------------
 // 2'. f16 sweep.  The filter only has to be SAFE, not accurate, so S = q . s does not need fp32 operands: with the rows
 // centred on the instance centre (distances are translation invariant), scaled by an exact power of two PER ROW (largest element
-// -> [2^14, 2^15): the f16 window follows the row as in gemm.hip; the inverse scales multiply S back) and rounded to f16 (unit
+// -> [2^14, 2^15): the f16 window follows the row as in the GEMMs (ls_device.h: pow2_scale); the inverse scales multiply S back) and rounded to f16 (unit
 // roundoff u = 2^-11),
 //     |S~ - S| <= (2u + u^2) |q'||s'| <= (2^-11 + 2^-23) (|q'|^2 + |s'|^2)      (fp32 accumulation adds D 2^-23 of the same scale)
 // so  d^ = |q'|^2 + |s'|^2 - 2 S~  is within  eps_b (|q'|^2 + |s'|^2),  eps_b = 1.02 * 2^-10 + 6 (D+4) 2^-24 + 2^-20,  of the canonical
@@ -113,9 +111,6 @@ __device__ __forceinline__ float quad_pair_distance(const QuadRow<CC>& q0, const
 // per MFMA, no LDS staging, no workgroup barriers; the waves are independent (32 queries x a candidate range each) and any
 // (queries x splits) grid fills the chip.  Per-query hints live in a wave-private LDS bitmap (a pass that is a hint is not
 // recorded), survivors are appended through global counters.
-typedef _Float16 f16x8k __attribute__((ext_vector_type(8)));
-typedef _Float16 kh2_t __attribute__((ext_vector_type(2)));
-typedef float kf2_t __attribute__((ext_vector_type(2)));
 constexpr int KNN_CENTRE_ROWS = 16;
 // Round 4: the same image, one WORKGROUP per 32-row tile.  The one-wave form walks a row twice (maximum, then scale + convert) in KK dependent
 // steps of two loads each and leaves 2 waves per SIMD on the chip at the encoder's shapes (2 048 tiles): 17.5 us per layer for 25 MB in and
@@ -169,9 +164,9 @@ __global__ __launch_bounds__(64 * WPT) void knn_prep_f16_tile_kernel(const float
     __syncthreads();
 #pragma unroll
     for (int u = 0; u < WPT; ++u) amax = fmaxf(amax, lamax[u][j]);
-    unsigned be = (__float_as_uint(amax) >> 23) & 0xffu;
-    be = be < 15u ? 15u : be;
-    const float sc = live ? __uint_as_float((268u - be) << 23) : 0.f;
+    float sc;
+    const unsigned be = pow2_scale_be(amax, sc);     // the row's power of two (ls_device.h, "operand range of the f16 split")
+    sc = live ? sc : 0.f;
     unsigned short* op = out + ((((size_t)b * tpi + tile) * KK + w * KPW) * 64 + lane) * 8;
     float s = 0.f;
 #pragma unroll
@@ -181,7 +176,7 @@ __global__ __launch_bounds__(64 * WPT) void knn_prep_f16_tile_kernel(const float
         for (int i = 0; i < 4; ++i) {
             const float c0 = c[kk][2 * i], c1 = c[kk][2 * i + 1];
             s += c0 * c0 + c1 * c1;
-            const kh2_t hv = __builtin_convertvector(kf2_t{c0 * sc, c1 * sc}, kh2_t);     // round to nearest even
+            const f16x2_t hv = __builtin_convertvector(f32x2_t{c0 * sc, c1 * sc}, f16x2_t);     // round to nearest even (the hi piece alone: the filter needs no residual)
             pk[i] = __builtin_bit_cast(unsigned, hv);
         }
         uint4 wv;
@@ -196,7 +191,7 @@ __global__ __launch_bounds__(64 * WPT) void knn_prep_f16_tile_kernel(const float
 #pragma unroll
         for (int u = 1; u < WPT; ++u) t += lsum[u][j];
         norms[(size_t)b * N + r] = t;
-        iscale[(size_t)b * N + r] = __uint_as_float((be - 14u) << 23);
+        iscale[(size_t)b * N + r] = pow2_inv(be);
     }
 }
 // ---------------------------------------------------------------------------------------------------------------------
@@ -308,23 +303,23 @@ __global__ __launch_bounds__(64 * KF_WAVES, FMA ? 3 : 4) void knn_fused_kernel(c
     for (int i = tid; i < KF_QT * 64; i += 64 * KF_WAVES) (&L.hm[0][0])[i] = 0x7F800000u;
 
     // ---- 1. sweep: this wave's tiles, S in registers
-    f16x8k a[KK];
+    f16x8_t a[KK];
     {
         const int qi = q0 + l31;
         const int r = qi < Nd ? (dst_rows ? dst_rows[(size_t)b * Nd + qi] : qi) : 0;
         const unsigned short* ap = dqb + ((size_t)(r >> 5) * KK * 64 + lh * 32 + (r & 31)) * 8;
 #pragma unroll
-        for (int kk = 0; kk < KK; ++kk) a[kk] = __builtin_bit_cast(f16x8k, *reinterpret_cast<const uint4*>(ap + (size_t)kk * 512));
+        for (int kk = 0; kk < KK; ++kk) a[kk] = __builtin_bit_cast(f16x8_t, *reinterpret_cast<const uint4*>(ap + (size_t)kk * 512));
     }
-    f32x16 S[TPW];
+    f32x16_t S[TPW];
     float cns[TPW], cic[TPW];          // the tile's column: |s'|^2 and its inverse image scale (this lane's candidate)
     {
-        f16x8k bf[2][KK];
-        auto load_b = [&](int t, f16x8k (&dstb)[KK]) {
+        f16x8_t bf[2][KK];
+        auto load_b = [&](int t, f16x8_t (&dstb)[KK]) {
             const int tg = min(wave + KF_WAVES * t, ntiles - 1);
             const unsigned short* bp = sqb + ((size_t)tg * KK * 64 + lane) * 8;
 #pragma unroll
-            for (int kk = 0; kk < KK; ++kk) dstb[kk] = __builtin_bit_cast(f16x8k, *reinterpret_cast<const uint4*>(bp + (size_t)kk * 512));
+            for (int kk = 0; kk < KK; ++kk) dstb[kk] = __builtin_bit_cast(f16x8_t, *reinterpret_cast<const uint4*>(bp + (size_t)kk * 512));
         };
         load_b(0, bf[0]);
 #pragma unroll
@@ -353,22 +348,22 @@ __global__ __launch_bounds__(64 * KF_WAVES, FMA ? 3 : 4) void knn_fused_kernel(c
         // same IEEE operations per element as the scalar form (so the same survivors), 6 packed instead of 12 scalar instructions per pair, and a padding
         // column carries |s'|^2 = +inf instead of a select on the minimum: hi = +inf never wins, lo = NaN is masked by colv in the filter below.
         const int slot = (wave & 1) * 32 + l31;
-        kf2_t cn2[TPW], ci2[TPW];
+        f32x2_t cn2[TPW], ci2[TPW];
 #pragma unroll
-        for (int t = 0; t < TPW; ++t) { const float cn = colv[t] ? cns[t] : INFINITY; cn2[t] = kf2_t{cn, cn}; ci2[t] = kf2_t{cic[t], cic[t]}; }
-        const kf2_t eps2 = {eps, eps};
+        for (int t = 0; t < TPW; ++t) { const float cn = colv[t] ? cns[t] : INFINITY; cn2[t] = f32x2_t{cn, cn}; ci2[t] = f32x2_t{cic[t], cic[t]}; }
+        const f32x2_t eps2 = {eps, eps};
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {
             const int qr = (r & 3) + 8 * (r >> 2) + 4 * lh;       // r even: rows qr, qr + 1
-            const kf2_t qx = *reinterpret_cast<const kf2_t*>(&L.qnx[qr]), qy = *reinterpret_cast<const kf2_t*>(&L.qny[qr]);
+            const f32x2_t qx = *reinterpret_cast<const f32x2_t*>(&L.qnx[qr]), qy = *reinterpret_cast<const f32x2_t*>(&L.qny[qr]);
             float hm0 = INFINITY, hm1 = INFINITY;
 #pragma unroll
             for (int t = 0; t < TPW; ++t) {
-                const kf2_t nn = qx + cn2[t], w = qy * ci2[t];
-                const kf2_t sv = {S[t][r], S[t][r + 1]};
-                const kf2_t dh = __builtin_elementwise_fma(sv, w, nn), e = eps2 * nn;
-                const kf2_t hi = dh + e;
-                kf2_t lo = dh - e;
+                const f32x2_t nn = qx + cn2[t], w = qy * ci2[t];
+                const f32x2_t sv = {S[t][r], S[t][r + 1]};
+                const f32x2_t dh = __builtin_elementwise_fma(sv, w, nn), e = eps2 * nn;
+                const f32x2_t hi = dh + e;
+                f32x2_t lo = dh - e;
                 hm0 = fminf(hm0, hi.x); hm1 = fminf(hm1, hi.y);
                 asm volatile("" : "+v"(lo));      // (materialised here, as in the scalar form: sunk into the filter it keeps d^ and nn alive)
                 S[t][r] = lo.x; S[t][r + 1] = lo.y;

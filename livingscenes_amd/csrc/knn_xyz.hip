@@ -39,7 +39,7 @@ __global__ __launch_bounds__(256, 4) void knn_xyz_kernel(const float* __restrict
 
     // candidates as PAIRS (j, j + 8) -> packed fp32 math (v_pk_add / v_pk_mul: half the distance instructions; no MFMA in this
     // kernel, so the packed ops cost nothing extra).  Columns past Ns hold +inf: their distance is +inf and never passes.
-    f32x2 cx[8], cy[8], cz[8];
+    f32x2_t cx[8], cy[8], cz[8];
     auto load_chunk = [&](int c0) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -47,9 +47,9 @@ __global__ __launch_bounds__(256, 4) void knn_xyz_kernel(const float* __restrict
             const int la = min(ca, Ns - 1), lb = min(cb, Ns - 1);
             const float ax = sb[(size_t)la * 3 + 0], ay = sb[(size_t)la * 3 + 1], az = sb[(size_t)la * 3 + 2];
             const float bx = sb[(size_t)lb * 3 + 0], by = sb[(size_t)lb * 3 + 1], bz = sb[(size_t)lb * 3 + 2];
-            cx[j] = f32x2{ca < Ns ? ax : INFINITY, cb < Ns ? bx : INFINITY};
-            cy[j] = f32x2{ca < Ns ? ay : INFINITY, cb < Ns ? by : INFINITY};
-            cz[j] = f32x2{ca < Ns ? az : INFINITY, cb < Ns ? bz : INFINITY};
+            cx[j] = f32x2_t{ca < Ns ? ax : INFINITY, cb < Ns ? bx : INFINITY};
+            cy[j] = f32x2_t{ca < Ns ? ay : INFINITY, cb < Ns ? by : INFINITY};
+            cz[j] = f32x2_t{ca < Ns ? az : INFINITY, cb < Ns ? bz : INFINITY};
         }
     };
     if (single) load_chunk(0);
@@ -63,11 +63,11 @@ __global__ __launch_bounds__(256, 4) void knn_xyz_kernel(const float* __restrict
         u64 best = ~0ull;                                     // lanes 0..15: the sorted list so far
         for (int c0 = 0; c0 < Ns; c0 += KX_CH) {
             if (!single) load_chunk(c0);
-            f32x2 d[8];
+            f32x2_t d[8];
             unsigned mn = 0x7F800000u;                        // +inf
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                f32x2 a = accq2<FMA>(f32x2{0.0f, 0.0f}, qx, cx[j]);
+                f32x2_t a = accq2<FMA>(f32x2_t{0.0f, 0.0f}, qx, cx[j]);
                 a = accq2<FMA>(a, qy, cy[j]);
                 a = accq2<FMA>(a, qz, cz[j]);
                 d[j] = a;

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "ls_common.h"
+#include "ls_device.h"
 #include "ls_ragged.h"
 #include "svd3.h"
 

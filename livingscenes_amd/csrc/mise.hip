@@ -15,6 +15,7 @@
 // the reference's (tests/golden/mise.npz; the ORDER of a round's queries is ascending lattice index instead of the
 // reference's insertion order -- the field is point-wise, so it cannot matter).
 #include "ls_common.h"
+#include "ls_device.h"
 #include "ls_scan.h"
 
 namespace ls {

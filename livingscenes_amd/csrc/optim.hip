@@ -13,10 +13,12 @@
 // this build's documented definitions -- PARITY UNPINNED for them; the decoder gradients are pinned (sdf.hip).
 // Every reduction runs in a fixed order (no atomics): a pair's trajectory does not depend on which other pairs share the launch.
 #include "ls_common.h"
+#include "ls_device.h"
 #include <algorithm>
 
 namespace ls {
 
+// (the four wave sums left to right: rounds differently from pointwise.hip's pairwise block_sum_256, so the two stay apart -- ls_device.h, merge rule)
 __device__ __forceinline__ float block_sum_256_opt(float v, float* red) {   // fixed-order block reduction, result in every thread
     v = wave_sum(v);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

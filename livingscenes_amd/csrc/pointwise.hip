@@ -1,6 +1,7 @@
 // pointwise.hip -- the small HBM-bound kernels around the edge-conv: encode prologue, per-instance mean,
 // point-wise VN activation (residual global conv), and the encoder tail (conv_c pooling + the four heads).
 #include "ls_launch.h"
+#include "ls_device.h"
 
 namespace ls {
 
@@ -196,10 +197,7 @@ __global__ __launch_bounds__(256) void mean_points_kernel(const float* __restric
 // Until round 3 this took three launches (mean_points_kernel, a 192-row fp32-MFMA GEMM split along K, its reduce) of 5 - 14 us each on
 // the critical path of every layer >= 2; here a workgroup computes the instance's mean rows into LDS (same summation order as
 // mean_points_kernel where the layer is narrow) and then its block of columns, one column per lane, k ascending.
-// sum over aligned groups of 16 lanes, every lane receives it (quad_perm, quad_perm, row_half_mirror, row_mirror: fixed order)
-template <int CTRL>
-__device__ __forceinline__ float dpp_addf(float v) { return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true)); }
-__device__ __forceinline__ float sum16_dpp(float v) { return dpp_addf<0x140>(dpp_addf<0x141>(dpp_addf<0x4E>(dpp_addf<0xB1>(v)))); }
+// (group_sum<16>, ls_device.h: sum over aligned groups of 16 lanes, every lane receives it -- quad_perm, quad_perm, row_half_mirror, row_mirror: fixed order)
 __global__ __launch_bounds__(256) void glob_mean_gemv_kernel(const float* __restrict__ f, int N, int C, const float* __restrict__ W, int col0,
                                                              int cols_per_block, int ncols, float* __restrict__ G, int ldg, float inv) {
     LS_LATENCY_CRITICAL();
@@ -272,7 +270,7 @@ __global__ __launch_bounds__(256) void glob_mean_gemv_kernel(const float* __rest
         for (int u = 0; u < 2; ++u) {
             const int j = jb + 16 * u + jr;
 #pragma unroll
-            for (int x = 0; x < 3; ++x) a[u][x] = sum16_dpp(a[u][x]);
+            for (int x = 0; x < 3; ++x) a[u][x] = group_sum<16>(a[u][x]);
             if (kl == 0 && j < j1) {
                 float* gp = G + (size_t)b * 3 * ldg + col0 + j;
                 gp[0] = a[u][0]; gp[ldg] = a[u][1]; gp[2 * ldg] = a[u][2];
@@ -323,6 +321,7 @@ struct TailW {
     const float* misc;     // lin1 [h] | shortcut [Cd] | act2 dir [1]
 };
 
+// (the four wave sums pairwise, (r0 + r1) + (r2 + r3): rounds differently from optim.hip's left-to-right block_sum_256_opt, so the two stay apart -- ls_device.h, merge rule)
 __device__ __forceinline__ float block_sum_256(float v, float* red) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     v = wave_sum(v);

@@ -16,6 +16,7 @@
 // A = [W_xyz | 0], applied to the query itself (no t, s, |q|); every kernel below that touches the query or the code comes in both kinds
 // (template flag XYZ), one arithmetic path per kind.
 #include "ls_launch.h"
+#include "ls_device.h"
 
 namespace ls {
 
@@ -90,11 +91,7 @@ __device__ __forceinline__ float aff_row(const AffCols& c, float qx, float qy, f
         *reinterpret_cast<float4*>(hp) = v;
     } else v = make_float4(0.f, 0.f, 0.f, 0.f);
     float m = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
-    m = dpp_fmax_rm<0xB1, 0xF>(m);    // quad_perm [1,0,3,2]
-    m = dpp_fmax_rm<0x4E, 0xF>(m);    // quad_perm [2,3,0,1]
-    m = dpp_fmax_rm<0x141, 0xF>(m);   // row_half_mirror
-    m = dpp_fmax_rm<0x140, 0xF>(m);   // row_mirror
-    return m;
+    return max16(m);   // quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror
 }
 // XYZ: q = query (raw; s and t are not read), no |q|
 template <bool XYZ>

@@ -10,6 +10,7 @@
 // One wave per row i: the M columns are strided over the 64 lanes with an online (max, sum) pair per lane, combined by a wave
 // reduction; the gradient is accumulated un-normalised against the running max and rescaled whenever the max moves.
 #include "ls_common.h"
+#include "ls_device.h"
 
 namespace ls {
 

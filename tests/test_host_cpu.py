@@ -625,6 +625,21 @@ def test_packed_fp32_build_guard_fires_without_the_flag(tmp_path):
         B.check_packed_fp32(str(tmp_path))
 
 
+_CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "livingscenes_amd", "csrc")
+
+
+@pytest.mark.parametrize("header", sorted(f for f in os.listdir(_CSRC) if f.endswith(".h")))
+def test_every_csrc_header_compiles_on_its_own(header):
+    """A header under csrc/ includes what it uses: a translation unit of that one #include passes hipcc's syntax check, host and device pass."""
+    import shutil
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not (shutil.which(hipcc) or os.path.exists(hipcc)):
+        pytest.skip("no hipcc")
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-x", "hip", "-"],
+                       input=f'#include "{os.path.join(_CSRC, header)}"\n', capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
 def test_launcher_refuses_a_world_size_other_than_gpus(monkeypatch):
     """`--gpus N` is the number of ranks (livingscenes_amd/launch.py): under a launcher the world size must BE N, started
     plainly with N = 1 nothing is launched, and a nonsensical N is refused."""
