@@ -77,10 +77,8 @@ int scatter_codes_launch(const float* packed, int B, int c, float* z_so3, float*
 // ---- sdf.hip
 int sdf_prep_launch(const float* inv_t, const float* so3_t, const float* wlen, const float* bias, const float* z_so3, const float* z_inv, int B, int L, int out_dim,
                     float* A, float* beff, bool xyz, hipStream_t st);
-int sdf_affine_launch(const float* query, const float* s, const float* t, const float* A, const float* beff, int B, int M, int out_dim, int ldh, int accumulate,
-                      float* h, bool xyz, hipStream_t st, float* rowmax = nullptr);
-int sdf_affine_rows_launch(const float* query, const int32_t* row_inst, const float* s, const float* t, const float* A, const float* beff, long long R, int out_dim,
-                           int ldh, int accumulate, float* h, bool xyz, hipStream_t st, float* rowmax = nullptr);
+int sdf_affine_launch(const float* query, const int32_t* row_inst, const float* s, const float* t, const float* A, const float* beff, int B, long long rows,
+                      int out_dim, int ldh, int accumulate, float* h, bool xyz, hipStream_t st, float* rowmax = nullptr);
 int sdf_affine_rowmax_parts(int out_dim);
 int sdf_out_launch(const float* h, int ldh, int width, const float* w, const float* bias, long long rows, float* sdf, hipStream_t st);
 int sdf_out_bwd_launch(const float* g, const float* sdf, const float* w, const float* h, int ldh, int width, long long rows, float* dz, hipStream_t st,

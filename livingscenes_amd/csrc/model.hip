@@ -892,79 +892,83 @@ static size_t sdf_gemm_scratch(const ls_model_desc& d, long long rows) {
     return mx;
 }
 
-size_t ls_sdf_workspace_bytes(const ls_model_t* m, int B, int M) {
-    if (!m || m->d.dec_num_linear <= 0) return 0;
-    const size_t w = (size_t)m->d.dec_width;
-    size_t b = 0;
-    b += 2 * align_up((size_t)B * w * 4 * 4, 256);   // A0, A4
-    b += 2 * align_up((size_t)B * w * 4, 256);       // beff0, beff4
-    b += 2 * align_up((size_t)B * M * w * 4, 256);   // ping-pong activations
-    b += 2 * align_up((size_t)B * M * sdf_rm_parts((int)w) * 4, 256);   // row maxima of the activations (GemmAux)
-    return b;
-}
-// training form: every layer's activations are kept for the backward pass, plus its scratch
-size_t ls_sdf_train_workspace_bytes(const ls_model_t* m, int B, int M) {
-    if (!m || m->d.dec_num_linear <= 0) return 0;
-    const size_t w = (size_t)m->d.dec_width;
-    const int nl = m->d.dec_num_linear;
-    size_t b = 0;
-    b += 2 * align_up((size_t)B * w * 4 * 4, 256) + 2 * align_up((size_t)B * w * 4, 256);      // A0, A4, beff0, beff4
-    b += (size_t)(nl - 1) * align_up((size_t)B * M * w * 4, 256);                               // h_0 .. h_{nl-2}
-    b += 2 * align_up((size_t)B * M * w * 4, 256);                                              // dz ping-pong
-    b += 2 * align_up((size_t)B * w * 4 * 4, 256) + 2 * align_up((size_t)B * w * 4, 256);      // dA0, dA4, dbeff0, dbeff4
-    b += align_up((size_t)B * M * 4 * 4, 256);                                                  // dQ
-    b += align_up(sdf_gemm_scratch(m->d, (long long)B * M) * 4, 256) + 256;                      // split-K slabs (small M only)
-    b += 2 * align_up((size_t)B * M * sdf_rm_parts((int)w) * 4, 256);                           // row maxima of the activations / gradients (GemmAux)
-    return b;
-}
-
 struct SdfBuffers {
     float *A0, *A4, *b0, *b4;
     float* h[12];       // output of linear layer l (post-ReLU); inference: two ping-pong buffers
     float *dzA, *dzB, *dA0, *dA4, *db0, *db4, *dQ;
     float* gws;         // split-K scratch for the under-filled GEMMs (NULL when the grid is large enough)
     float* rm[2];       // row maxima of the activations / gradients, ping-pong: [rows][sdf_rm_parts(w)] (GemmAux)
+    size_t bytes;       // of the whole layout
 };
-static SdfBuffers sdf_buffers(const ls_model_desc& d, void* workspace, int B, int M, bool train, bool allow_splitk = true) {
+// The one statement of the decoder's workspace layout: B instances, `rows` query rows in all (B * M, or R of the ragged form).
+// A null `workspace` gives the byte total and pointers nobody reads.  train: every layer's activations are kept for the backward pass, plus its scratch.
+static SdfBuffers sdf_buffers(const ls_model_desc& d, void* workspace, int B, long long rows, bool train, bool allow_splitk = true) {
     SdfBuffers sb{};
     const int w = d.dec_width, nl = d.dec_num_linear;
-    char* ws = (char*)workspace;
+    const size_t R = (size_t)rows;
     size_t off = 0;
-    auto take = [&](size_t bytes) { float* p = (float*)(ws + off); off = align_up(off + bytes, 256); return p; };
+    auto take = [&](size_t bytes) { float* p = (float*)((uintptr_t)workspace + off); off = align_up(off + bytes, 256); return p; };
     sb.A0 = take((size_t)B * w * 16);
     sb.A4 = take((size_t)B * w * 16);
     sb.b0 = take((size_t)B * w * 4);
     sb.b4 = take((size_t)B * w * 4);
     if (!train) {
-        float* hA = take((size_t)B * M * w * 4);
-        float* hB = take((size_t)B * M * w * 4);
+        float* hA = take(R * w * 4);
+        float* hB = take(R * w * 4);
         for (int l = 0; l < nl - 1; ++l) sb.h[l] = (l & 1) ? hB : hA;
         // inference never splits K: a query's SDF must not depend on how many other queries share the call (MISE evaluates
         // the same lattice point in calls of very different sizes; split-K changes the fp32 summation order)
         sb.gws = nullptr;
-        sb.rm[0] = take((size_t)B * M * sdf_rm_parts(w) * 4);
-        sb.rm[1] = take((size_t)B * M * sdf_rm_parts(w) * 4);
-        return sb;
+    } else {
+        for (int l = 0; l < nl - 1; ++l) sb.h[l] = take(R * w * 4);
+        sb.dzA = take(R * w * 4);
+        sb.dzB = take(R * w * 4);
+        sb.dA0 = take((size_t)B * w * 16);
+        sb.dA4 = take((size_t)B * w * 16);
+        sb.db0 = take((size_t)B * w * 4);
+        sb.db4 = take((size_t)B * w * 4);
+        sb.dQ = take(R * 16);
+        // split-K slabs (small M only) and their 256-byte tail; the tail is reserved even where no GEMM splits (the size always counted it)
+        const size_t scratch = sdf_gemm_scratch(d, rows);
+        float* gws = take(scratch * 4 + 256);
+        sb.gws = scratch && allow_splitk ? gws : nullptr;
     }
-    for (int l = 0; l < nl - 1; ++l) sb.h[l] = take((size_t)B * M * w * 4);
-    sb.dzA = take((size_t)B * M * w * 4);
-    sb.dzB = take((size_t)B * M * w * 4);
-    sb.dA0 = take((size_t)B * w * 16);
-    sb.dA4 = take((size_t)B * w * 16);
-    sb.db0 = take((size_t)B * w * 4);
-    sb.db4 = take((size_t)B * w * 4);
-    sb.dQ = take((size_t)B * M * 16);
-    sb.gws = sdf_gemm_scratch(d, (long long)B * M) ? take(sdf_gemm_scratch(d, (long long)B * M) * 4 + 256) : nullptr;
-    if (!allow_splitk) sb.gws = nullptr;
-    sb.rm[0] = take((size_t)B * M * sdf_rm_parts(w) * 4);
-    sb.rm[1] = take((size_t)B * M * sdf_rm_parts(w) * 4);
+    sb.rm[0] = take(R * sdf_rm_parts(w) * 4);
+    sb.rm[1] = take(R * sdf_rm_parts(w) * 4);
+    sb.bytes = off;
     return sb;
 }
+static size_t sdf_bytes(const ls_model_t* m, int B, long long rows, bool train) {
+    return m && m->d.dec_num_linear > 0 ? sdf_buffers(m->d, nullptr, B, rows, train).bytes : 0;
+}
+size_t ls_sdf_workspace_bytes(const ls_model_t* m, int B, int M) { return sdf_bytes(m, B, (long long)B * M, false); }
+// Ragged batch: R query rows of B instances packed back to back (rows of one instance contiguous), row_inst[r] = instance of row r.
+size_t ls_sdf_rows_workspace_bytes(const ls_model_t* m, int B, long long R) { return sdf_bytes(m, B, R, false); }
+size_t ls_sdf_train_workspace_bytes(const ls_model_t* m, int B, int M) { return sdf_bytes(m, B, (long long)B * M, true); }
 
-// row_inst == nullptr: B instances x M rows each; else `M` = total rows R, row r belongs to instance row_inst[r]
+// Operand range of the decoder's GEMMs (gemm.hip, GemmAux): every kernel that writes an activation (forward) or a gradient (backward) also
+// writes its row maxima, and the GEMM that reads it takes them instead of scanning its A rows; the weights carry theirs from ls_model_create.
+// The maxima ping-pong between two buffers; the chain is off in the sdf_bf16x2 mode.
+struct RowMaxChain {
+    float* const* rm;
+    bool on;
+    int cur = 1, parts = 0;   // rm[cur] holds the maxima of the current operand, `parts` per row, when `have`
+    bool have = false;
+    // the GEMM about to be launched reads the current operand
+    void operand(GemmAux& ax) const { ax.a_rowmax = have ? rm[cur] : nullptr; ax.a_parts = have ? parts : 0; }
+    // the launch that produces the next operand writes its maxima, n per row, to the returned buffer (NULL: chain off)
+    float* emit(int n) {
+        if (!on) return nullptr;
+        cur ^= 1; parts = n; have = true;
+        return rm[cur];
+    }
+    // ... or writes none (a split-K launch)
+    void emit_none() { have = false; }
+};
+
+// row_inst == nullptr: B instances x rows / B rows each; else row r belongs to instance row_inst[r]
 static int sdf_forward(ls_model_t* m, const SdfBuffers& sb, const float* query, const float* z_so3, const float* z_inv, const float* s,
-                       const float* t, int B, int M, float* sdf, hipStream_t st, const int32_t* row_inst = nullptr) {
-    const long long rows = row_inst ? (long long)M : (long long)B * M;
+                       const float* t, int B, long long rows, float* sdf, hipStream_t st, const int32_t* row_inst = nullptr) {
     const ls_model_desc& d = m->d;
     const int w = d.dec_width, L = d.c_dim, nl = d.dec_num_linear, li = d.dec_latent_in;
     const bool xyz = dec_xyz(d);   // LS_DEC_XYZ: z_so3, s and t are not read
@@ -980,14 +984,9 @@ static int sdf_forward(ls_model_t* m, const SdfBuffers& sb, const float* query, 
     }
     if (rc != LS_OK) return rc;
     // layer 0: pure affine in (q, |q|) (LS_DEC_XYZ: in the raw query)
-    // operand range of the GEMMs (gemm.hip, GemmAux): every kernel that writes an activation also writes its row maxima, the GEMM that
-    // reads it takes them instead of scanning its A rows; the weights carry theirs from ls_model_create
-    const bool chain = !m->sdf_bf16x2;
-    bool have = chain;   // sb.rm[ri] holds the row maxima of h[l - 1], rm_parts per row
-    int ri = 0, rm_parts = sdf_affine_rowmax_parts(w);
+    RowMaxChain rmc{sb.rm, !m->sdf_bf16x2};
     { PROF(LS_K_SDF_AFFINE, 0, st);
-      rc = row_inst ? sdf_affine_rows_launch(query, row_inst, s, t, sb.A0, sb.b0, rows, w, w, 0, sb.h[0], xyz, st, chain ? sb.rm[0] : nullptr)
-                    : sdf_affine_launch(query, s, t, sb.A0, sb.b0, B, M, w, w, 0, sb.h[0], xyz, st, chain ? sb.rm[0] : nullptr); }
+      rc = sdf_affine_launch(query, row_inst, s, t, sb.A0, sb.b0, B, rows, w, w, 0, sb.h[0], xyz, st, rmc.emit(sdf_affine_rowmax_parts(w))); }
     if (rc != LS_OK) return rc;
     int kin = w;
     for (int l = 1; l < nl - 1; ++l) {
@@ -995,27 +994,21 @@ static int sdf_forward(ls_model_t* m, const SdfBuffers& sb, const float* query, 
         const float* cur = sb.h[l - 1];
         float* nxt = sb.h[l];
         GemmAux ax = aux_w(m, W + d.off_dec_w[l], outw, kin);
-        ax.a_rowmax = have ? sb.rm[ri] : nullptr;
-        ax.a_parts = have ? rm_parts : 0;
+        rmc.operand(ax);
         if (l == li) {
             { PROF(LS_K_GEMM_SDF, l, st);
               rc = (m->sdf_bf16x2 && !sb.gws) ? gemm_dispatch_fast2(cur, w, W + d.off_dec_w[l], kin, nullptr, nxt, w, (int)rows, outw, kin, 0, st)
                                               : gemm_dispatch_ws(cur, w, W + d.off_dec_w[l], kin, nullptr, nxt, w, (int)rows, outw, kin, 0, sb.gws, st, ax); }
             if (rc != LS_OK) return rc;
             PROF(LS_K_SDF_AFFINE, l, st);
-            float* rmo = chain ? sb.rm[ri ^ 1] : nullptr;
-            rc = row_inst ? sdf_affine_rows_launch(query, row_inst, s, t, sb.A4, sb.b4, rows, w, w, 1, nxt, xyz, st, rmo)
-                          : sdf_affine_launch(query, s, t, sb.A4, sb.b4, B, M, w, w, 1, nxt, xyz, st, rmo);
-            if (chain) { ri ^= 1; have = true; rm_parts = sdf_affine_rowmax_parts(w); }
+            rc = sdf_affine_launch(query, row_inst, s, t, sb.A4, sb.b4, B, rows, w, w, 1, nxt, xyz, st, rmc.emit(sdf_affine_rowmax_parts(w)));
         } else {
             PROF(LS_K_GEMM_SDF, l, st);
-            const bool emit = chain && !(sb.gws && gemm_scratch_floats((int)rows, outw, kin) > 0);   // a split-K launch writes no row maxima
-            if (emit) ax.out_rowmax = sb.rm[ri ^ 1];
+            if (sb.gws && gemm_scratch_floats((int)rows, outw, kin) > 0) rmc.emit_none();   // a split-K launch writes no row maxima
+            else ax.out_rowmax = rmc.emit(gemm_rowmax_parts(outw));
             rc = (m->sdf_bf16x2 && !sb.gws)
                      ? gemm_dispatch_fast2(cur, w, W + d.off_dec_w[l], kin, W + d.off_dec_b[l], nxt, w, (int)rows, outw, kin, 1, st)
                      : gemm_dispatch_ws(cur, w, W + d.off_dec_w[l], kin, W + d.off_dec_b[l], nxt, w, (int)rows, outw, kin, 1, sb.gws, st, ax);
-            if (emit) { ri ^= 1; rm_parts = gemm_rowmax_parts(outw); }
-            have = emit;
         }
         if (rc != LS_OK) return rc;
         kin = outw;
@@ -1024,62 +1017,44 @@ static int sdf_forward(ls_model_t* m, const SdfBuffers& sb, const float* query, 
     return sdf_out_launch(sb.h[nl - 2], w, kin, W + d.off_dec_w[nl - 1], W + d.off_dec_b[nl - 1], rows, sdf, st);
 }
 
-int ls_sdf_decode(ls_model_t* m, const float* query, const float* z_so3, const float* z_inv, const float* s, const float* t,
-                  int B, int M, float* sdf, void* workspace, size_t workspace_bytes, void* stream) {
-    LS_REQUIRE(m && query && z_inv && sdf && workspace && (dec_xyz(m->d) || (z_so3 && s && t)), "sdf_decode: null argument");
-    const ls_model_desc& d = m->d;
-    LS_REQUIRE(d.dec_num_linear >= 3, "sdf_decode: model has no decoder packed");
-    LS_REQUIRE(B > 0 && M > 0, "sdf_decode: empty problem");
-    const size_t need = ls_sdf_workspace_bytes(m, B, M);
-    if (workspace_bytes < need) { set_error("sdf_decode: workspace %zu < required %zu", workspace_bytes, need); return LS_ERR_WORKSPACE; }
-    return sdf_forward(m, sdf_buffers(d, workspace, B, M, false), query, z_so3, z_inv, s, t, B, M, sdf, (hipStream_t)stream);
+// The checks the decoder's entry points share; `op` names the operator in the messages.  args: the handle and the operator's pointers are
+// there (LS_DEC_XYZ reads no z_so3, s or t).  n: rows per instance, or all R rows of the ragged form.
+static int sdf_entry(const ls_model_t* m, const char* op, bool args, int B, long long n, bool ragged, bool train, size_t workspace_bytes) {
+    LS_REQUIRE(args, "%s: null argument", op);
+    LS_REQUIRE(m->d.dec_num_linear >= 3, "%s: model has no decoder packed", op);
+    if (ragged) LS_REQUIRE(B > 0 && n > 0 && n < (1ll << 31), "%s: empty or oversized problem", op);
+    else LS_REQUIRE(B > 0 && n > 0, "%s: empty problem", op);
+    const size_t need = sdf_bytes(m, B, ragged ? n : B * n, train);
+    if (workspace_bytes < need) { set_error("%s: workspace %zu < required %zu", op, workspace_bytes, need); return LS_ERR_WORKSPACE; }
+    return LS_OK;
 }
 
-// Ragged batch: R query rows of B instances packed back to back (rows of one instance contiguous), row_inst[r] = instance of row r.
-// Workspace: ls_sdf_rows_workspace_bytes(m, B, R).
-size_t ls_sdf_rows_workspace_bytes(const ls_model_t* m, int B, long long R) {
-    if (!m || m->d.dec_num_linear <= 0) return 0;
-    const size_t w = (size_t)m->d.dec_width;
-    size_t b = 2 * align_up((size_t)B * w * 4 * 4, 256) + 2 * align_up((size_t)B * w * 4, 256);
-    b += 2 * align_up((size_t)R * w * 4, 256);
-    b += 2 * align_up((size_t)R * sdf_rm_parts((int)w) * 4, 256);
-    return b;
+int ls_sdf_decode(ls_model_t* m, const float* query, const float* z_so3, const float* z_inv, const float* s, const float* t,
+                  int B, int M, float* sdf, void* workspace, size_t workspace_bytes, void* stream) {
+    const int rc = sdf_entry(m, "sdf_decode", m && query && z_inv && sdf && workspace && (dec_xyz(m->d) || (z_so3 && s && t)), B, M, false, false,
+                             workspace_bytes);
+    if (rc != LS_OK) return rc;
+    const long long rows = (long long)B * M;
+    return sdf_forward(m, sdf_buffers(m->d, workspace, B, rows, false), query, z_so3, z_inv, s, t, B, rows, sdf, (hipStream_t)stream);
 }
+
+// Workspace: ls_sdf_rows_workspace_bytes(m, B, R).
 int ls_sdf_decode_rows(ls_model_t* m, const float* query, const int32_t* row_inst, const float* z_so3, const float* z_inv, const float* s,
                        const float* t, int B, long long R, float* sdf, void* workspace, size_t workspace_bytes, void* stream) {
-    LS_REQUIRE(m && query && row_inst && z_inv && sdf && workspace && (dec_xyz(m->d) || (z_so3 && s && t)), "sdf_decode_rows: null argument");
-    const ls_model_desc& d = m->d;
-    LS_REQUIRE(d.dec_num_linear >= 3, "sdf_decode_rows: model has no decoder packed");
-    LS_REQUIRE(B > 0 && R > 0 && R < (1ll << 31), "sdf_decode_rows: empty or oversized problem");
-    const size_t need = ls_sdf_rows_workspace_bytes(m, B, R);
-    if (workspace_bytes < need) { set_error("sdf_decode_rows: workspace %zu < required %zu", workspace_bytes, need); return LS_ERR_WORKSPACE; }
-    // same buffer layout as the dense form with "M" = R rows shared by all instances
-    SdfBuffers sb{};
-    const int w = d.dec_width, nl = d.dec_num_linear;
-    char* ws = (char*)workspace;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { float* p = (float*)(ws + off); off = align_up(off + bytes, 256); return p; };
-    sb.A0 = take((size_t)B * w * 16); sb.A4 = take((size_t)B * w * 16);
-    sb.b0 = take((size_t)B * w * 4); sb.b4 = take((size_t)B * w * 4);
-    float* hA = take((size_t)R * w * 4);
-    float* hB = take((size_t)R * w * 4);
-    for (int l = 0; l < nl - 1; ++l) sb.h[l] = (l & 1) ? hB : hA;
-    sb.gws = nullptr;   // batch-invariant: no split-K (see sdf_buffers)
-    sb.rm[0] = take((size_t)R * sdf_rm_parts(w) * 4);
-    sb.rm[1] = take((size_t)R * sdf_rm_parts(w) * 4);
-    return sdf_forward(m, sb, query, z_so3, z_inv, s, t, B, (int)R, sdf, (hipStream_t)stream, row_inst);
+    const int rc = sdf_entry(m, "sdf_decode_rows", m && query && row_inst && z_inv && sdf && workspace && (dec_xyz(m->d) || (z_so3 && s && t)), B, R,
+                             true, false, workspace_bytes);
+    if (rc != LS_OK) return rc;
+    return sdf_forward(m, sdf_buffers(m->d, workspace, B, R, false), query, z_so3, z_inv, s, t, B, R, sdf, (hipStream_t)stream, row_inst);
 }
 
 // forward that keeps every layer's activations in `workspace` for ls_sdf_backward
 int ls_sdf_decode_train(ls_model_t* m, const float* query, const float* z_so3, const float* z_inv, const float* s, const float* t,
                         int B, int M, float* sdf, void* workspace, size_t workspace_bytes, void* stream) {
-    LS_REQUIRE(m && query && z_inv && sdf && workspace && (dec_xyz(m->d) || (z_so3 && s && t)), "sdf_decode_train: null argument");
-    const ls_model_desc& d = m->d;
-    LS_REQUIRE(d.dec_num_linear >= 3, "sdf_decode_train: model has no decoder packed");
-    LS_REQUIRE(B > 0 && M > 0, "sdf_decode_train: empty problem");
-    const size_t need = ls_sdf_train_workspace_bytes(m, B, M);
-    if (workspace_bytes < need) { set_error("sdf_decode_train: workspace %zu < required %zu", workspace_bytes, need); return LS_ERR_WORKSPACE; }
-    return sdf_forward(m, sdf_buffers(d, workspace, B, M, true, m->train_splitk), query, z_so3, z_inv, s, t, B, M, sdf, (hipStream_t)stream);
+    const int rc = sdf_entry(m, "sdf_decode_train", m && query && z_inv && sdf && workspace && (dec_xyz(m->d) || (z_so3 && s && t)), B, M, false, true,
+                             workspace_bytes);
+    if (rc != LS_OK) return rc;
+    const long long rows = (long long)B * M;
+    return sdf_forward(m, sdf_buffers(m->d, workspace, B, rows, true, m->train_splitk), query, z_so3, z_inv, s, t, B, rows, sdf, (hipStream_t)stream);
 }
 
 static int build_dec_wt(ls_model_t* m, hipStream_t st) {   // transposed main weights of layers 1 .. nl-2
@@ -1110,40 +1085,37 @@ static int build_dec_wt(ls_model_t* m, hipStream_t st) {   // transposed main we
 int ls_sdf_backward(ls_model_t* m, const float* query, const float* z_so3, const float* z_inv, const float* s, const float* t, int B,
                     int M, const float* sdf, const float* grad_sdf, void* workspace, size_t workspace_bytes, float* grad_query,
                     float* grad_z_so3, float* grad_z_inv, float* grad_s, float* grad_t, void* stream) {
-    LS_REQUIRE(m && query && z_inv && sdf && grad_sdf && workspace, "sdf_backward: null argument");
-    const bool xyz = dec_xyz(m->d);
-    LS_REQUIRE(xyz || (z_so3 && s && t && grad_s && grad_t), "sdf_backward: null argument");
+    int rc = sdf_entry(m, "sdf_backward",
+                       m && query && z_inv && sdf && grad_sdf && workspace && (dec_xyz(m->d) || (z_so3 && s && t && grad_s && grad_t)), B, M, false, true,
+                       workspace_bytes);
+    if (rc != LS_OK) return rc;
+    const ls_model_desc& d = m->d;
+    const bool xyz = dec_xyz(d);
     LS_REQUIRE(xyz || (grad_z_so3 != nullptr) == (grad_z_inv != nullptr), "sdf_backward: grad_z_so3 and grad_z_inv are given or omitted together");
     const bool need_code = grad_z_inv != nullptr;   // a pose refinement with a fixed code skips the code-gradient reductions
-    const ls_model_desc& d = m->d;
-    LS_REQUIRE(d.dec_num_linear >= 3, "sdf_backward: model has no decoder packed");
-    LS_REQUIRE(B > 0 && M > 0, "sdf_backward: empty problem");
-    const size_t need = ls_sdf_train_workspace_bytes(m, B, M);
-    if (workspace_bytes < need) { set_error("sdf_backward: workspace %zu < required %zu", workspace_bytes, need); return LS_ERR_WORKSPACE; }
     hipStream_t st = (hipStream_t)stream;
     if (xyz) {   // the invariant decoder does not read z_so3, s or t: their gradients are exact zeros
         if (grad_z_so3) LS_HIP_CHECK(hipMemsetAsync(grad_z_so3, 0, (size_t)B * d.c_dim * 3 * sizeof(float), st));
         if (grad_s) LS_HIP_CHECK(hipMemsetAsync(grad_s, 0, (size_t)B * sizeof(float), st));
         if (grad_t) LS_HIP_CHECK(hipMemsetAsync(grad_t, 0, (size_t)B * 3 * sizeof(float), st));
     }
-    int rc = build_dec_wt(m, st);
+    rc = build_dec_wt(m, st);
     if (rc != LS_OK) return rc;
-    const SdfBuffers sb = sdf_buffers(d, workspace, B, M, true, m->train_splitk);
+    const long long rows = (long long)B * M;
+    const SdfBuffers sb = sdf_buffers(d, workspace, B, rows, true, m->train_splitk);
     const int w = d.dec_width, L = d.c_dim, nl = d.dec_num_linear, li = d.dec_latent_in;
     const float* W = m->blob;
-    const long long rows = (long long)B * M;
     // widths: out_w[l] = padded output width of layer l
     int outw[12];
     for (int l = 0; l < nl; ++l) outw[l] = l == 0 ? w : dec_out(d, l);
     float* dz = sb.dzA;     // dz_l: gradient w.r.t. the pre-activation of layer l, row stride w
     float* other = sb.dzB;
     // last layer: dz_{nl-2}
-    // operand range (gemm.hip, GemmAux): dz carries its row maxima from kernel to kernel like the activations of the forward pass
-    const bool chain = !m->sdf_bf16x2;
+    // dz carries its row maxima (here: an upper bound, one per row) from kernel to kernel like the activations of the forward pass
+    RowMaxChain rmc{sb.rm, !m->sdf_bf16x2};
     const float* w8max = wmax_for(m, W + d.off_dec_w[nl - 1], 1, outw[nl - 2]);
-    bool have = chain && w8max;   // sb.rm[ri] holds the row maxima (or an upper bound) of dz, rm_parts per row
-    int ri = 0, rm_parts = 1;
-    rc = sdf_out_bwd_launch(grad_sdf, sdf, W + d.off_dec_w[nl - 1], sb.h[nl - 2], w, outw[nl - 2], rows, dz, st, have ? sb.rm[0] : nullptr, w8max);
+    rc = sdf_out_bwd_launch(grad_sdf, sdf, W + d.off_dec_w[nl - 1], sb.h[nl - 2], w, outw[nl - 2], rows, dz, st, rmc.emit(1), w8max);
+    if (!w8max) rmc.emit_none();   // (the launch writes no bound without the weight's maximum)
     if (rc != LS_OK) return rc;
     bool dq_started = false;
     for (int l = nl - 2; l >= 1; --l) {
@@ -1157,20 +1129,16 @@ int ls_sdf_backward(ls_model_t* m, const float* query, const float* z_so3, const
         // the ReLU derivative [h_{l-1} > 0] is applied in the GEMM's store when the launch does not split K (h and dh share the row stride w)
         const bool fuse_mask = !sb.gws && kin % 4 == 0;
         GemmAux ax = aux_w(m, m->dec_wt + m->dec_wt_off[l], kin, outw[l]);
-        ax.a_rowmax = have ? sb.rm[ri] : nullptr;
-        ax.a_parts = have ? rm_parts : 0;
+        rmc.operand(ax);
         if (fuse_mask) {
-            if (chain) ax.out_rowmax = sb.rm[ri ^ 1];   // after the mask
+            ax.out_rowmax = rmc.emit(gemm_rowmax_parts(kin));   // after the mask
             rc = gemm_dispatch_masked(dz, w, m->dec_wt + m->dec_wt_off[l], outw[l], other, w, (int)rows, kin, outw[l], sb.h[l - 1], m->sdf_bf16x2 ? 2 : 3, st, ax);
-            if (chain) { ri ^= 1; rm_parts = gemm_rowmax_parts(kin); have = true; }
         } else {
             // (an un-masked, possibly split-K launch: its maxima would still bound the masked values, but a split launch writes none)
-            const bool emit = chain && !(sb.gws && gemm_scratch_floats((int)rows, kin, outw[l]) > 0);
-            if (emit) ax.out_rowmax = sb.rm[ri ^ 1];
+            if (sb.gws && gemm_scratch_floats((int)rows, kin, outw[l]) > 0) rmc.emit_none();
+            else ax.out_rowmax = rmc.emit(gemm_rowmax_parts(kin));
             rc = gemm_dispatch_ws(dz, w, m->dec_wt + m->dec_wt_off[l], outw[l], nullptr, other, w, (int)rows, kin, outw[l], 0, sb.gws, st, ax);
             if (rc != LS_OK) return rc;
-            if (emit) { ri ^= 1; rm_parts = gemm_rowmax_parts(kin); }
-            have = emit;
             rc = relu_mask_launch(other, sb.h[l - 1], rows, kin, w, st);
         }
         if (rc != LS_OK) return rc;

@@ -15,6 +15,7 @@
 // u = [z_inv | query] with the RAW query: W u + b = W_xyz query + (b + W_z z_inv).  The same per-instance rank-4 map serves with
 // A = [W_xyz | 0], applied to the query itself (no t, s, |q|); every kernel below that touches the query or the code comes in both kinds
 // (template flag XYZ), one arithmetic path per kind.
+#include <type_traits>
 #include "ls_launch.h"
 #include "ls_device.h"
 
@@ -93,87 +94,91 @@ __device__ __forceinline__ float aff_row(const AffCols& c, float qx, float qy, f
     float m = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
     return max16(m);   // quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror
 }
+// q = (query - t) / s and |q|: the forward and the backward kernels must agree on these bit for bit
+struct NormQ {
+    float x, y, z, len;
+};
+__device__ __forceinline__ NormQ norm_query(const float* __restrict__ qp, float sc, float tx, float ty, float tz) {
+    NormQ q;
+    q.x = (qp[0] - tx) / sc; q.y = (qp[1] - ty) / sc; q.z = (qp[2] - tz) / sc;
+    q.len = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z);
+    return q;
+}
+// The kernel takes a row locator by value and asks it which slab the workgroup owns, which instance a row belongs to and where the row is.
+// (The locator sits where the dense form's `int M` did, and DenseRows forms b * M + r as that kernel did: its instantiations are the
+// dense kernel this one replaced instruction for instruction, the ragged ones differ from theirs in the argument loads only; history 23.)
+// DenseRows: B instances x M rows each, grid (column block, instance, slab); one instance per workgroup (kUniform: its columns, s and t
+// are loaded once, before the slab loop), rows indexed in 32 bits inside the instance.
+struct DenseRows {
+    int M;
+    typedef int idx_t;
+    static constexpr bool kUniform = true;
+    __device__ int slab() const { return blockIdx.z; }
+    __device__ int rows() const { return M; }
+    __device__ int inst(int) const { return blockIdx.y; }
+    __device__ size_t at(int r) const { return (size_t)inst(r) * M + r; }
+};
+// RaggedRows: R rows of SEVERAL instances packed back to back, row r belongs to instance row_inst[r] (batched MISE rounds, where every
+// instance contributes a different number of query points); grid (column block, slab).
+struct RaggedRows {
+    const int32_t* __restrict__ row_inst;
+    long long R;
+    typedef long long idx_t;
+    static constexpr bool kUniform = false;
+    __device__ long long slab() const { return blockIdx.y; }
+    __device__ long long rows() const { return R; }
+    __device__ int inst(long long r) const { return row_inst[r]; }
+    __device__ size_t at(long long r) const { return (size_t)r; }
+};
 // XYZ: q = query (raw; s and t are not read), no |q|
-template <bool XYZ>
+template <bool XYZ, class Rows>
 __global__ __launch_bounds__(256) void sdf_affine_kernel(const float* __restrict__ query, const float* __restrict__ s,
                                                          const float* __restrict__ t, const float* __restrict__ A,
-                                                         const float* __restrict__ beff, int M, int out_dim, int ldh,
-                                                         int accumulate, int rows_per_block, float* __restrict__ h,
-                                                         float* __restrict__ rowmax) {
+                                                         const float* __restrict__ beff, const Rows rows, int out_dim, int ldh, int accumulate,
+                                                         int rows_per_block, float* __restrict__ h, float* __restrict__ rowmax) {
     // rowmax (nullable) [rows][4 * gridDim.x]: max|h[row, 64-column group]| -- the operand range of the GEMM that reads h (gemm.hip, GemmAux)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int rm_parts = 4 * gridDim.x, rm_part = 4 * blockIdx.x + (lane >> 4);
-    const int b = blockIdx.y, o = blockIdx.x * 256 + lane * 4;
-    const int r0 = blockIdx.z * rows_per_block;
-    const bool on = o < out_dim;      // (out_dim % 4 == 0: a lane's four columns are all inside or all outside)
-    const AffCols c = aff_load(A, beff, b, out_dim, on ? o : 0);
-    float sc = 1.f, tx = 0.f, ty = 0.f, tz = 0.f;
-    if constexpr (!XYZ) { sc = s[b]; tx = t[b * 3]; ty = t[b * 3 + 1]; tz = t[b * 3 + 2]; }
-    const int r1 = min(M, r0 + rows_per_block);
-    for (int rb = r0; rb < r1; rb += 64) {
-        const int rl = min(rb + lane, r1 - 1);
-        const float* qp = query + ((size_t)b * M + rl) * 3;
-        float qxl, qyl, qzl, lenl = 0.f;
-        if constexpr (XYZ) { qxl = qp[0]; qyl = qp[1]; qzl = qp[2]; }
-        else {
-            qxl = (qp[0] - tx) / sc; qyl = (qp[1] - ty) / sc; qzl = (qp[2] - tz) / sc;
-            lenl = sqrtf(qxl * qxl + qyl * qyl + qzl * qzl);
-        }
-        const int nr = min(64, r1 - rb);
-        for (int j = wave; j < nr; j += 4) {
-            const int r = rb + j;
-            const float qx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qxl), j));
-            const float qy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qyl), j));
-            const float qz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qzl), j));
-            const float len = XYZ ? 0.f : __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lenl), j));
-            const float m = aff_row<XYZ>(c, qx, qy, qz, len, on, accumulate, h + ((size_t)b * M + r) * ldh + o);
-            if (rowmax && (lane & 15) == 15) rowmax[((size_t)b * M + r) * rm_parts + rm_part] = m;
-        }
-    }
-}
-
-// Ragged form: rows of SEVERAL instances packed back to back, row r belongs to instance row_inst[r] (batched MISE rounds, where
-// every instance contributes a different number of query points).  Same arithmetic as sdf_affine_kernel.
-template <bool XYZ>
-__global__ __launch_bounds__(256) void sdf_affine_rows_kernel(const float* __restrict__ query, const int32_t* __restrict__ row_inst,
-                                                              const float* __restrict__ s, const float* __restrict__ t,
-                                                              const float* __restrict__ A, const float* __restrict__ beff, long long R,
-                                                              int out_dim, int ldh, int accumulate, int rows_per_block,
-                                                              float* __restrict__ h, float* __restrict__ rowmax) {
+    typedef typename Rows::idx_t idx_t;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int rm_parts = 4 * gridDim.x, rm_part = 4 * blockIdx.x + (lane >> 4);
     const int o = blockIdx.x * 256 + lane * 4;
-    const long long r0 = (long long)blockIdx.y * rows_per_block;
-    const bool on = o < out_dim;
+    const bool on = o < out_dim;      // (out_dim % 4 == 0: a lane's four columns are all inside or all outside)
     const int ow = on ? o : 0;
-    const long long r1 = min(R, r0 + rows_per_block);
-    int bprev = -1;
+    const idx_t r0 = rows.slab() * rows_per_block;
+    const idx_t r1 = min(rows.rows(), r0 + rows_per_block);
+    int bcur = -1;
     AffCols c;
-    for (long long rb = r0; rb < r1; rb += 64) {   // lane l normalises row rb + l, the row loop reads it back (see sdf_affine_kernel)
-        const long long rl = min(rb + lane, r1 - 1);
-        const int bl = row_inst[rl];
-        const float* qp = query + (size_t)rl * 3;
-        float qxl, qyl, qzl, lenl = 0.f;
-        if constexpr (XYZ) { qxl = qp[0]; qyl = qp[1]; qzl = qp[2]; }
+    float sc = 1.f, tx = 0.f, ty = 0.f, tz = 0.f;
+    if constexpr (Rows::kUniform) {
+        bcur = rows.inst(r0);
+        c = aff_load(A, beff, bcur, out_dim, ow);
+        if constexpr (!XYZ) { sc = s[bcur]; tx = t[bcur * 3]; ty = t[bcur * 3 + 1]; tz = t[bcur * 3 + 2]; }
+    }
+    for (idx_t rb = r0; rb < r1; rb += 64) {
+        const idx_t rl = min(rb + lane, r1 - 1);
+        const int bl = rows.inst(rl);
+        const float* qp = query + rows.at(rl) * 3;
+        NormQ ql;
+        if constexpr (XYZ) { ql.x = qp[0]; ql.y = qp[1]; ql.z = qp[2]; ql.len = 0.f; }
         else {
-            const float sc = s[bl], tx = t[bl * 3], ty = t[bl * 3 + 1], tz = t[bl * 3 + 2];
-            qxl = (qp[0] - tx) / sc; qyl = (qp[1] - ty) / sc; qzl = (qp[2] - tz) / sc;
-            lenl = sqrtf(qxl * qxl + qyl * qyl + qzl * qzl);
+            if constexpr (!Rows::kUniform) { sc = s[bl]; tx = t[bl * 3]; ty = t[bl * 3 + 1]; tz = t[bl * 3 + 2]; }
+            ql = norm_query(qp, sc, tx, ty, tz);
         }
-        const int nr = (int)min((long long)64, r1 - rb);
+        const int nr = (int)min((idx_t)64, r1 - rb);
         for (int j = wave; j < nr; j += 4) {
-            const long long r = rb + j;
-            const int b = __builtin_amdgcn_readlane(bl, j);
-            if (b != bprev) {   // rows of an instance are contiguous: reloaded a handful of times per block
-                c = aff_load(A, beff, b, out_dim, ow);
-                bprev = b;
+            if constexpr (!Rows::kUniform) {
+                const int b = __builtin_amdgcn_readlane(bl, j);
+                if (b != bcur) {   // rows of an instance are contiguous: reloaded a handful of times per block
+                    c = aff_load(A, beff, b, out_dim, ow);
+                    bcur = b;
+                }
             }
-            const float qx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qxl), j));
-            const float qy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qyl), j));
-            const float qz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qzl), j));
-            const float len = XYZ ? 0.f : __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lenl), j));
-            const float m = aff_row<XYZ>(c, qx, qy, qz, len, on, accumulate, h + (size_t)r * ldh + o);
-            if (rowmax && (lane & 15) == 15) rowmax[(size_t)r * rm_parts + rm_part] = m;
+            const float qx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ql.x), j));
+            const float qy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ql.y), j));
+            const float qz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ql.z), j));
+            const float len = XYZ ? 0.f : __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ql.len), j));
+            const size_t row = rows.at(rb + j);
+            const float m = aff_row<XYZ>(c, qx, qy, qz, len, on, accumulate, h + row * ldh + o);
+            if (rowmax && (lane & 15) == 15) rowmax[row * rm_parts + rm_part] = m;
         }
     }
 }
@@ -261,11 +266,9 @@ __global__ __launch_bounds__(256) void sdf_affine_bwd_cols_kernel(const float* _
     const float sc = s[b], tx = t[b * 3], ty = t[b * 3 + 1], tz = t[b * 3 + 2];
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, bb = 0.f;
     for (int r = slice; r < M; r += 4) {
-        const float* qp = query + ((size_t)b * M + r) * 3;
-        const float qx = (qp[0] - tx) / sc, qy = (qp[1] - ty) / sc, qz = (qp[2] - tz) / sc;
-        const float len = sqrtf(qx * qx + qy * qy + qz * qz);
+        const NormQ q = norm_query(query + ((size_t)b * M + r) * 3, sc, tx, ty, tz);
         const float d = on ? dz[((size_t)b * M + r) * ldh + o] : 0.f;
-        a0 += d * qx; a1 += d * qy; a2 += d * qz; a3 += d * len; bb += d;
+        a0 += d * q.x; a1 += d * q.y; a2 += d * q.z; a3 += d * q.len; bb += d;
     }
     red[slice][lane][0] = a0; red[slice][lane][1] = a1; red[slice][lane][2] = a2; red[slice][lane][3] = a3; red[slice][lane][4] = bb;
     __syncthreads();
@@ -358,14 +361,12 @@ __global__ __launch_bounds__(256) void sdf_query_grad_kernel(const float* __rest
     float sx = 0.f, sy = 0.f, sz = 0.f, ss = 0.f;
     for (int r = tid; r < M; r += 256) {
         const size_t row = (size_t)b * M + r;
-        const float* qp = query + row * 3;
-        const float qx = (qp[0] - tx) / sc, qy = (qp[1] - ty) / sc, qz = (qp[2] - tz) / sc;
-        const float len = sqrtf(qx * qx + qy * qy + qz * qz);
+        const NormQ q = norm_query(query + row * 3, sc, tx, ty, tz);
         const float4 d = *reinterpret_cast<const float4*>(dQ + row * 4);
-        const float il = len > 0.f ? d.w / len : 0.f;
-        const float dx = d.x + il * qx, dy = d.y + il * qy, dzv = d.z + il * qz;
+        const float il = q.len > 0.f ? d.w / q.len : 0.f;
+        const float dx = d.x + il * q.x, dy = d.y + il * q.y, dzv = d.z + il * q.z;
         if (g_query) { g_query[row * 3] = dx / sc; g_query[row * 3 + 1] = dy / sc; g_query[row * 3 + 2] = dzv / sc; }
-        sx += dx; sy += dy; sz += dzv; ss += dx * qx + dy * qy + dzv * qz;
+        sx += dx; sy += dy; sz += dzv; ss += dx * q.x + dy * q.y + dzv * q.z;
     }
     sx = wave_sum(sx); sy = wave_sum(sy); sz = wave_sum(sz); ss = wave_sum(ss);
     if (lane == 0) { red[wave][0] = sx; red[wave][1] = sy; red[wave][2] = sz; red[wave][3] = ss; }
@@ -387,6 +388,13 @@ __global__ void transpose_kernel(const float* __restrict__ W, int rows, int cols
         if (bx + i < cols && by + tx < rows) Wt[(size_t)(bx + i) * rows + by + tx] = tile[tx][i];
 }
 
+// the decoder kind is a template flag of the kernels: launch(std::true_type) for LS_DEC_XYZ, launch(std::false_type) otherwise
+template <class F>
+static void by_kind(bool xyz, F launch) {
+    if (xyz) launch(std::true_type());
+    else launch(std::false_type());
+}
+
 int sdf_out_bwd_launch(const float* g, const float* sdf, const float* w, const float* h, int ldh, int width, long long rows, float* dz,
                        hipStream_t st, float* rowmax, const float* wmax) {
     if (!wmax) rowmax = nullptr;
@@ -403,12 +411,10 @@ int relu_mask_launch(float* dh, const float* h, long long rows, int cols, int ld
 int sdf_affine_bwd_launch(const float* query, const float* s, const float* t, const float* dz, const float* A, int B, int M, int out_dim,
                           int ldh, int accumulate, float* dA, float* dbeff, float* dQ, bool need_code, bool xyz, hipStream_t st) {
     // the reductions over the queries feed only the CODE gradient (a pose refinement with a fixed code does not need them)
-    if (need_code) {
-        if (xyz)
-            hipLaunchKernelGGL(sdf_affine_bwd_cols_kernel<true>, dim3(cdiv(out_dim, 64), B), dim3(256), 0, st, query, s, t, dz, M, out_dim, ldh, dA, dbeff);
-        else
-            hipLaunchKernelGGL(sdf_affine_bwd_cols_kernel<false>, dim3(cdiv(out_dim, 64), B), dim3(256), 0, st, query, s, t, dz, M, out_dim, ldh, dA, dbeff);
-    }
+    if (need_code)
+        by_kind(xyz, [&](auto K) {
+            hipLaunchKernelGGL(sdf_affine_bwd_cols_kernel<decltype(K)::value>, dim3(cdiv(out_dim, 64), B), dim3(256), 0, st, query, s, t, dz, M, out_dim, ldh, dA, dbeff);
+        });
     hipLaunchKernelGGL(sdf_affine_bwd_rows_kernel, dim3(cdiv((long long)B * M, 4)), dim3(256), 0, st, dz, A, M, out_dim, ldh, accumulate,
                        (long long)B * M, dQ);
     LS_LAUNCH_CHECK();
@@ -417,12 +423,10 @@ int sdf_affine_bwd_launch(const float* query, const float* s, const float* t, co
 int sdf_code_grad_launch(const float* so3_t0, const float* inv_t0, const float* dA0, const float* db0, const float* so3_t1,
                          const float* inv_t1, const float* dA1, const float* db1, int B, int L, int out_dim, float* g_so3, float* g_inv,
                          bool xyz, hipStream_t st) {
-    if (xyz)
-        hipLaunchKernelGGL(sdf_code_grad_kernel<true>, dim3(cdiv(L, 4), B), dim3(256), 0, st, so3_t0, inv_t0, dA0, db0, so3_t1, inv_t1, dA1, db1, L,
+    by_kind(xyz, [&](auto K) {
+        hipLaunchKernelGGL(sdf_code_grad_kernel<decltype(K)::value>, dim3(cdiv(L, 4), B), dim3(256), 0, st, so3_t0, inv_t0, dA0, db0, so3_t1, inv_t1, dA1, db1, L,
                            out_dim, g_so3, g_inv);
-    else
-        hipLaunchKernelGGL(sdf_code_grad_kernel<false>, dim3(cdiv(L, 4), B), dim3(256), 0, st, so3_t0, inv_t0, dA0, db0, so3_t1, inv_t1, dA1, db1, L,
-                           out_dim, g_so3, g_inv);
+    });
     LS_LAUNCH_CHECK();
     return LS_OK;
 }
@@ -447,46 +451,38 @@ int transpose_launch(const float* W, int rows, int cols, float* Wt, hipStream_t 
 // xyz (LS_DEC_XYZ): so3_t = W_xyz^T [3][out]; wlen and z_so3 are not read
 int sdf_prep_launch(const float* inv_t, const float* so3_t, const float* wlen, const float* bias, const float* z_so3,
                     const float* z_inv, int B, int L, int out_dim, float* A, float* beff, bool xyz, hipStream_t st) {
-    if (xyz)
-        hipLaunchKernelGGL(sdf_prep_kernel<true>, dim3(cdiv(out_dim, 256), B), dim3(256), 0, st, inv_t, so3_t, wlen, bias, z_so3, z_inv, L,
+    by_kind(xyz, [&](auto K) {
+        hipLaunchKernelGGL(sdf_prep_kernel<decltype(K)::value>, dim3(cdiv(out_dim, 256), B), dim3(256), 0, st, inv_t, so3_t, wlen, bias, z_so3, z_inv, L,
                            out_dim, A, beff);
-    else
-        hipLaunchKernelGGL(sdf_prep_kernel<false>, dim3(cdiv(out_dim, 256), B), dim3(256), 0, st, inv_t, so3_t, wlen, bias, z_so3, z_inv, L,
-                           out_dim, A, beff);
+    });
     LS_LAUNCH_CHECK();
     return LS_OK;
 }
-int sdf_affine_launch(const float* query, const float* s, const float* t, const float* A, const float* beff, int B, int M,
-                      int out_dim, int ldh, int accumulate, float* h, bool xyz, hipStream_t st, float* rowmax) {
+// row_inst == nullptr: B instances x rows / B rows each; else `rows` rows of B instances, row r belongs to instance row_inst[r]
+int sdf_affine_launch(const float* query, const int32_t* row_inst, const float* s, const float* t, const float* A, const float* beff, int B,
+                      long long rows, int out_dim, int ldh, int accumulate, float* h, bool xyz, hipStream_t st, float* rowmax) {
     const int rpb = 64;
     LS_REQUIRE(out_dim % 4 == 0 && ldh % 4 == 0, "sdf_affine: width %d / row stride %d must be multiples of 4", out_dim, ldh);
+    auto launch = [&](auto loc, dim3 grid) {
+        by_kind(xyz, [&](auto K) {
+            hipLaunchKernelGGL((sdf_affine_kernel<decltype(K)::value, decltype(loc)>), grid, dim3(256), 0, st, query, s, t, A, beff, loc, out_dim, ldh,
+                               accumulate, rpb, h, rowmax);
+        });
+    };
     // gridDim.y / .z are limited to 65535: say so instead of a generic launch failure (direct C-ABI callers; ops.sdf_decode chunks)
-    LS_REQUIRE(B <= 65535 && cdiv(M, rpb) <= 65535, "sdf_decode: B=%d or M=%d too large for one call (B <= 65535, M <= %d): split the queries", B, M,
-               65535 * rpb);
-    if (xyz)
-        hipLaunchKernelGGL(sdf_affine_kernel<true>, dim3(cdiv(out_dim, 256), B, cdiv(M, rpb)), dim3(256), 0, st, query, s, t, A, beff, M,
-                           out_dim, ldh, accumulate, rpb, h, rowmax);
-    else
-        hipLaunchKernelGGL(sdf_affine_kernel<false>, dim3(cdiv(out_dim, 256), B, cdiv(M, rpb)), dim3(256), 0, st, query, s, t, A, beff, M,
-                           out_dim, ldh, accumulate, rpb, h, rowmax);
+    if (row_inst) {
+        LS_REQUIRE(cdiv(rows, rpb) <= 65535, "sdf_decode_rows: R=%lld rows too many for one call (<= %d): split the rows", rows, 65535 * rpb);
+        launch(RaggedRows{row_inst, rows}, dim3(cdiv(out_dim, 256), (unsigned)cdiv(rows, rpb)));
+    } else {
+        const int M = (int)(rows / B);
+        LS_REQUIRE(B <= 65535 && cdiv(M, rpb) <= 65535, "sdf_decode: B=%d or M=%d too large for one call (B <= 65535, M <= %d): split the queries", B, M,
+                   65535 * rpb);
+        launch(DenseRows{M}, dim3(cdiv(out_dim, 256), B, cdiv(M, rpb)));
+    }
     LS_LAUNCH_CHECK();
     return LS_OK;
 }
 int sdf_affine_rowmax_parts(int out_dim) { return 4 * cdiv(out_dim, 256); }
-int sdf_affine_rows_launch(const float* query, const int32_t* row_inst, const float* s, const float* t, const float* A, const float* beff,
-                           long long R, int out_dim, int ldh, int accumulate, float* h, bool xyz, hipStream_t st, float* rowmax) {
-    const int rpb = 64;
-    LS_REQUIRE(out_dim % 4 == 0 && ldh % 4 == 0, "sdf_affine: width %d / row stride %d must be multiples of 4", out_dim, ldh);
-    LS_REQUIRE(cdiv(R, rpb) <= 65535, "sdf_decode_rows: R=%lld rows too many for one call (<= %d): split the rows", R, 65535 * rpb);
-    if (xyz)
-        hipLaunchKernelGGL(sdf_affine_rows_kernel<true>, dim3(cdiv(out_dim, 256), (unsigned)cdiv(R, rpb)), dim3(256), 0, st, query, row_inst, s, t,
-                           A, beff, R, out_dim, ldh, accumulate, rpb, h, rowmax);
-    else
-        hipLaunchKernelGGL(sdf_affine_rows_kernel<false>, dim3(cdiv(out_dim, 256), (unsigned)cdiv(R, rpb)), dim3(256), 0, st, query, row_inst, s, t,
-                           A, beff, R, out_dim, ldh, accumulate, rpb, h, rowmax);
-    LS_LAUNCH_CHECK();
-    return LS_OK;
-}
 int sdf_out_launch(const float* h, int ldh, int width, const float* w, const float* bias, long long rows, float* sdf,
                    hipStream_t st) {
     LS_REQUIRE(width % 4 == 0 && ldh % 4 == 0, "sdf_out: width/ldh must be multiples of 4");

@@ -853,6 +853,112 @@ def test_sdf_backward_vs_oracle_autograd(which, B, M):
     assert relerr(gq, ql.grad) < TOL
 
 
+# ------------------------------------------------------------------------------------------------ decoder: slab edges, workspace plan
+def _small_decoder_case(B, seed):
+    ecfg, dcfg = synth.small_encoder_cfg(), synth.small_decoder_cfg()
+    ew, dw = synth.make_encoder_weights(ecfg, 3), synth.make_decoder_weights(dcfg, 3)
+    g = torch.Generator().manual_seed(seed)
+    L = dcfg["latent_size"]
+    code = {"z_so3": torch.randn(B, L, 3, generator=g) * 0.05, "z_inv": torch.randn(B, L, generator=g) * 0.05,
+            "s": torch.rand(B, generator=g) * 0.5 + 0.75, "t": torch.randn(B, 1, 3, generator=g) * 0.1}
+    return _hip_model(ecfg, ew, dcfg, dw), dcfg, dw, code, g
+
+
+def test_sdf_decode_dense_slab_edges():
+    """ls_sdf_decode at M around the affine kernel's 64-row slab (one row, one short of a slab, a slab, one over, two slabs and one row):
+    each within TOL of the oracle, and each equal to the first M rows of the M = 129 call bit for bit."""
+    from oracle import net
+    B = 2
+    m, dcfg, dw, code, g = _small_decoder_case(B, 11)
+    q = synth.make_queries(B, 129, seed=11) * code["s"][:, None, None] + code["t"]
+    d = _dev()
+    dc = {k: v.to(d) for k, v in code.items()}
+    full = m.sdf_decode(q.to(d), dc["z_so3"], dc["z_inv"], dc["s"], dc["t"])
+    for M in (1, 63, 64, 65, 129):
+        qm = q[:, :M].contiguous()
+        sdf = m.sdf_decode(qm.to(d), dc["z_so3"], dc["z_inv"], dc["s"], dc["t"])
+        assert sdf.shape == (B, M)
+        assert relerr(sdf, net.field_query(dw, dcfg, qm, code)) < TOL, M
+        assert torch.equal(sdf, full[:, :M]), M
+
+
+@pytest.mark.parametrize("B,M", [(1, 1), (2, 65)])
+def test_sdf_train_and_backward_at_slab_edges(B, M):
+    """ls_sdf_decode_train / ls_sdf_backward at one row and at a slab plus one row: the SDF and the five gradients within TOL of the
+    oracle's autograd; with split-K off the training forward is ls_sdf_decode bit for bit."""
+    from livingscenes_amd import _lib
+    from oracle import net
+    m, dcfg, dw, code, g = _small_decoder_case(B, B * 31 + M)
+    q = synth.make_queries(B, M, seed=6) * code["s"][:, None, None] + code["t"]
+    gsdf = torch.randn(B, M, generator=g)
+    leaves = {k: v.clone().requires_grad_(True) for k, v in code.items()}
+    ql = q.clone().requires_grad_(True)
+    sdf_ref = net.field_query_with_grad(dw, dcfg, ql, leaves)
+    (sdf_ref * gsdf).sum().backward()
+    d = _dev()
+    args = (q.to(d), code["z_so3"].to(d), code["z_inv"].to(d), code["s"].to(d), code["t"].to(d))
+    sdf, saved = m.sdf_decode_train(*args)
+    assert relerr(sdf, sdf_ref.detach()) < TOL
+    gq, gso3, ginv, gs, gt = m.sdf_backward(saved, gsdf.to(d))
+    assert relerr(gso3, leaves["z_so3"].grad) < TOL
+    assert relerr(ginv, leaves["z_inv"].grad) < TOL
+    assert relerr(gt, leaves["t"].grad.reshape(B, 3)) < TOL
+    assert relerr(gs, leaves["s"].grad) < TOL
+    assert relerr(gq, ql.grad) < TOL
+    prev = m.set_option(_lib.OPT_SDF_TRAIN_SPLITK, 0)
+    try:
+        sdf_ns, _ = m.sdf_decode_train(*args)
+    finally:
+        m.set_option(_lib.OPT_SDF_TRAIN_SPLITK, prev)
+    assert torch.equal(sdf_ns, m.sdf_decode(*args))
+
+
+# bytes returned by ls_sdf_workspace_bytes / ls_sdf_rows_workspace_bytes / ls_sdf_train_workspace_bytes at ABI 107, per (B, M or R):
+# the layout is written once (sdf_buffers) and these pin what it adds up to.  (8, 4097) needs no split-K scratch; the training size
+# still carries the 256-byte tail of the slabs.
+_SDF_WS_BYTES = {
+    "small": {(1, 1): (6656, 6656, 16384), (3, 700): (2233344, 754688, 10884352), (8, 4097): (34652672, 4367872, 102343680)},
+    "full": {(1, 1): (37376, 37376, 166912), (3, 700): (13196288, 4460544, 97188096), (8, 4097): (204768256, 25811456, 1011041792)},
+}
+
+
+@pytest.mark.parametrize("which", ["small", "full"])
+def test_sdf_workspace_sizes_are_pinned_and_sufficient(which):
+    """The three decoder size functions return the recorded values; every entry point runs with exactly that many bytes and refuses
+    one byte fewer with LS_ERR_WORKSPACE and its message."""
+    from livingscenes_amd._lib import load, ptr, stream_ptr
+    ecfg, dcfg = (synth.small_encoder_cfg(), synth.small_decoder_cfg()) if which == "small" else (synth.default_encoder_cfg(), synth.default_decoder_cfg())
+    m = _hip_model(ecfg, synth.make_encoder_weights(ecfg, 3), dcfg, synth.make_decoder_weights(dcfg, 3))
+    lib, d, L = load(), _dev(), dcfg["latent_size"]
+    g = torch.Generator().manual_seed(5)
+    for (B, n), (dense, ragged, train) in _SDF_WS_BYTES[which].items():
+        assert lib.ls_sdf_workspace_bytes(m._h, B, n) == dense, (B, n)
+        assert lib.ls_sdf_rows_workspace_bytes(m._h, B, n) == ragged, (B, n)
+        assert lib.ls_sdf_train_workspace_bytes(m._h, B, n) == train, (B, n)
+        z_so3, z_inv = (torch.randn(B, L, 3, generator=g) * 0.05).to(d), (torch.randn(B, L, generator=g) * 0.05).to(d)
+        s, t = (torch.rand(B, generator=g) + 0.5).to(d), (torch.randn(B, 3, generator=g) * 0.1).to(d)
+        q = (torch.rand(B, n, 3, generator=g) - 0.5).to(d)
+        qr = q[0].contiguous()                                                    # n rows in all, spread over the B instances
+        ri = (torch.arange(n, dtype=torch.int64) * B // n).to(torch.int32).to(d)
+        out, outr = torch.empty(B, n, device=d), torch.empty(n, device=d)
+        calls = {
+            "sdf_decode": (dense, lambda ws, nb: lib.ls_sdf_decode(m._h, ptr(q), ptr(z_so3), ptr(z_inv), ptr(s), ptr(t), B, n, ptr(out), ptr(ws), nb, stream_ptr(d))),
+            "sdf_decode_rows": (ragged, lambda ws, nb: lib.ls_sdf_decode_rows(m._h, ptr(qr), ptr(ri), ptr(z_so3), ptr(z_inv), ptr(s), ptr(t), B, n, ptr(outr), ptr(ws), nb,
+                                                                               stream_ptr(d))),
+            "sdf_decode_train": (train, lambda ws, nb: lib.ls_sdf_decode_train(m._h, ptr(q), ptr(z_so3), ptr(z_inv), ptr(s), ptr(t), B, n, ptr(out), ptr(ws), nb,
+                                                                                 stream_ptr(d))),
+        }
+        with torch.cuda.device(d):
+            for op, (need, fn) in calls.items():
+                ws = torch.empty(need, dtype=torch.uint8, device=d)
+                assert fn(ws, need - 1) == -3, (op, B, n)                           # LS_ERR_WORKSPACE
+                assert lib.ls_last_error().decode() == f"{op}: workspace {need - 1} < required {need}", (op, B, n)
+                assert fn(ws, need) == 0, (op, B, n, lib.ls_last_error().decode())
+                torch.cuda.synchronize()
+                del ws
+        assert bool(torch.isfinite(out).all()) and bool(torch.isfinite(outr).all()), (B, n)
+
+
 # ------------------------------------------------------------------------------------------------ Sinkhorn (SURVEY 8 f-1, UNPINNED)
 @pytest.mark.parametrize("N,M,shift", [(1024, 1024, 0.05), (300, 517, 0.3), (64, 64, 0.0)])
 def test_sinkhorn_divergence_vs_oracle(N, M, shift):

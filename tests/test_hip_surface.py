@@ -758,6 +758,37 @@ def test_ragged_decode_and_batched_mise_equal_per_instance(small_prior):
         assert np.array_equal(grids[b], gen.eval_grid({k: v[b:b + 1] for k, v in canon.items()}, sp.decoder)), b
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["inner_deepsdf", "deepsdf"])
+def test_ragged_decode_at_slab_and_instance_edges(kind, small_prior):
+    """ls_sdf_decode_rows == ls_sdf_decode of each instance alone, bit for bit, where the affine kernel's 64-row slabs and the instance
+    boundaries meet: a boundary exactly on a slab edge, a one-row instance opening a slab, an instance without rows (its id is skipped,
+    as eval_grid_batch does when an octree finishes early), last slabs of 3 rows and of one row, several instance changes inside one
+    wave's stride, and a single row.  Width 128 leaves half the lanes of the 256-column block outside the layer."""
+    from livingscenes_amd.model_utils import Shape_Prior
+    d = _dev()
+    if kind == "inner_deepsdf":
+        sp = small_prior[0]
+    else:
+        ecfg, dcfg = synth.small_encoder_cfg(), synth.small_inv_decoder_cfg()
+        sp = Shape_Prior.from_state(ecfg, dcfg, synth.make_encoder_weights(ecfg, 4), synth.make_decoder_weights(dcfg, 4), device=d, n_pcl=128,
+                                    decoder_type="deepsdf")
+    codes = sp.encode(synth.make_instances(5, 128, seed=43).to(d))
+    hip = sp.hip_model()
+    g = torch.Generator().manual_seed(7)
+    for counts in ([64, 1, 0, 129, 1], [1, 1, 1, 61, 1], [0, 0, 1, 0, 0]):
+        qs = [(torch.rand(n, 3, generator=g) - 0.5).to(d) for n in counts]
+        inst = torch.cat([torch.full((n,), b, dtype=torch.int32) for b, n in enumerate(counts)]).to(d)
+        got = hip.sdf_decode_rows(torch.cat(qs, 0), inst, codes["z_so3"], codes["z_inv"], codes["s"], codes["t"])
+        assert got.shape == (sum(counts),)
+        o = 0
+        for b, n in enumerate(counts):
+            if n:
+                one = hip.sdf_decode(qs[b][None], codes["z_so3"][b:b + 1], codes["z_inv"][b:b + 1], codes["s"][b:b + 1], codes["t"][b:b + 1])
+                assert torch.equal(got[o:o + n], one[0]), (counts, b)
+            o += n
+
+
 # ------------------------------------------------------------------------------------------------ multi-GPU path on one device
 _SHARD_WORKER = r"""
 import os, sys, torch, torch.distributed as dist
