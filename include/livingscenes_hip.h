@@ -481,6 +481,27 @@ int ls_mise_update(void* state, int resolution_0, int depth, double threshold, c
 /* MISE.to_dense, mise.pyx:128-165 -> grid_out [(R+1)^3] float32 (the reference's float64 grid holds float32 values) */
 int ls_mise_to_dense(void* state, int resolution_0, int depth, float* grid_out, void* stream);
 
+/* B octrees per launch.  All octrees of a batch share (resolution_0, depth, threshold).  A batch state is B single states back to back,
+ * stride ls_mise_state_bytes() (a multiple of 256), followed by the block sums of the batched query: slice b of a batch state is a valid
+ * state for the single ops above, and ls_mise_batch_state_bytes() = B * ls_mise_state_bytes() + that tail (0 for arguments the batch ops
+ * refuse).  Every batch op is the single op on every slice, bit for bit, in a number of launches that does not depend on B.
+ * Limits: 1 <= B <= 65535 (the octree is a grid dimension of the launch) and B * (R+1)^3 < 2^31 (packed rows are counted in int32). */
+size_t ls_mise_batch_state_bytes(int B, int resolution_0, int depth);
+int ls_mise_init_batch(void* state, size_t state_bytes, int B, int resolution_0, int depth, void* stream);
+/* The unknown points of octree 0 first, in ascending lattice index, then those of octree 1, ...: idx_out [cap] int32 = lattice index within
+ * the octree, inst_out [cap] int32 = the octree (exactly the row_inst of ls_sdf_decode_rows), pts_out [cap,3] float32 by the formula of
+ * ls_mise_query.  off_out (DEVICE long long [B+1]): off_out[b] = first row of octree b, off_out[B] = the total -- always the full counts;
+ * nothing is written at or past row cap.  An octree without unknown points has an empty slice. */
+int ls_mise_query_batch(void* state, int B, int resolution_0, int depth, float box_size, int32_t* idx_out, int32_t* inst_out,
+                        float* pts_out, long long cap, long long* off_out, void* stream);
+/* values[i] belongs to lattice point idx[i] of octree inst[i] (a row naming no octree or no lattice point is dropped); then clear / mark /
+ * subdivide for every octree.  Per octree the result equals driving it alone through the loop above: an octree whose query came back empty
+ * is at a fixed point of the update (its last update subdivided nothing, so marking again reproduces the same marks). */
+int ls_mise_update_batch(void* state, int B, int resolution_0, int depth, double threshold, const int32_t* idx, const int32_t* inst,
+                         const float* values, long long n, void* stream);
+/* grid_out [B, R+1, R+1, R+1] float32 */
+int ls_mise_to_dense_batch(void* state, int B, int resolution_0, int depth, float* grid_out, void* stream);
+
 /* SURVEY.md 8 (f-2), second half: libmcubes.marching_cubes(volume, isovalue) as called by Generator3D.extract_mesh
  * (occnet_utils/mesh_extractor2.py:161-176; occnet_utils/utils/libmcubes/marchingcubes.h:23-196, marchingcubes.cpp:290-326,
  * pywrapper.cpp:90-108): volume [nx,ny,nz] float64 -> vertices [nv,3] float64 (with the library's +0.5 offset) and faces
@@ -491,6 +512,18 @@ size_t ls_mcubes_workspace_bytes(int nx, int ny, int nz);
 int ls_marching_cubes_f64(const double* volume, int nx, int ny, int nz, double isovalue, double* vertices, long long cap_v,
                           long long* faces, long long cap_f, long long* counts_out, void* workspace, size_t workspace_bytes,
                           void* stream);
+/* B volumes of one shape per launch: volumes [B,nx,ny,nz] float64.  Vertices and faces are packed mesh after mesh, in the reference's order
+ * inside each mesh, and face indices count from the mesh's own first vertex: slice b of the output is bit-identical to
+ * ls_marching_cubes_f64 on volume b.  off_out (DEVICE long long [2][B+1]): [0][b] = first vertex of mesh b, [1][b] = its first face,
+ * [.][B] = the totals -- always the full counts.  Sizing as above: a call with vertices = faces = NULL only fills off_out (read it once
+ * per batch); nothing at or past cap_v vertices / cap_f faces of the packed outputs is written.
+ * Limits: 1 <= B <= 65535, and the vertex / face-index bases stay int and share one 64-bit word while they are summed:
+ * 15 * B * nx*ny*nz < 2^31 (a cube makes at most 15 face indices, a mesh at most 3 vertices per sample; this implies
+ * 3 * B * ncubes < 2^31).  ls_mcubes_batch_workspace_bytes is 0 for arguments the op refuses. */
+size_t ls_mcubes_batch_workspace_bytes(int B, int nx, int ny, int nz);
+int ls_marching_cubes_batch_f64(const double* volumes, int B, int nx, int ny, int nz, double isovalue, double* vertices, long long cap_v,
+                                long long* faces, long long cap_f, long long* off_out, void* workspace, size_t workspace_bytes,
+                                void* stream);
 
 /* libsimplify.simplify_mesh(mesh, f_target, agressiveness) as called by Generator3D.extract_mesh with (mesh, simplify_nfaces, 5.0)
  * (occnet_utils/mesh_extractor2.py:205-208; occnet_utils/utils/libsimplify/__init__.py:7-17, simplify_mesh.pyx:34-88,

@@ -163,7 +163,14 @@ SIGNATURES = {
     "ls_mise_query": (_I, [_P, _I, _I, _F, _P, _P, _I, _P, _P]),
     "ls_mise_update": (_I, [_P, _I, _I, ctypes.c_double, _P, _P, _I, _P]),
     "ls_mise_to_dense": (_I, [_P, _I, _I, _P, _P]),
+    "ls_mise_batch_state_bytes": (_SZ, [_I, _I, _I]),
+    "ls_mise_init_batch": (_I, [_P, _SZ, _I, _I, _I, _P]),
+    "ls_mise_query_batch": (_I, [_P, _I, _I, _I, _F, _P, _P, _P, _LL, _P, _P]),
+    "ls_mise_update_batch": (_I, [_P, _I, _I, _I, _D, _P, _P, _P, _LL, _P]),
+    "ls_mise_to_dense_batch": (_I, [_P, _I, _I, _I, _P, _P]),
     "ls_mcubes_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "ls_mcubes_batch_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "ls_marching_cubes_batch_f64": (_I, [_P, _I, _I, _I, _I, _D, _P, _LL, _P, _LL, _P, _P, _SZ, _P]),
     "ls_marching_cubes_f64": (_I, [_P, _I, _I, _I, ctypes.c_double, _P, ctypes.c_longlong, _P, ctypes.c_longlong, _P, _P, _SZ, _P]),
     "ls_simplify_mesh_f64_host": (_I, [_P, ctypes.c_longlong, _P, ctypes.c_longlong, _I, ctypes.c_double, _I, _P, _P, _P]),
     "ls_mesh_contains_workspace_bytes": (_SZ, [_I, _I]),

@@ -78,6 +78,56 @@ class MISE:
         return self.to_dense_device().cpu().numpy().astype(np.float64)
 
 
+class MISEBatch:
+    """B octrees of one (resolution_0, depth, threshold) advancing in lock-step (csrc/mise.hip, the *_batch ops): a round is one query, one
+    decoder call on (pts, inst) as they come out of the query, one update -- the number of launches does not depend on B.  The state is B
+    ``MISE`` states back to back; every octree evolves exactly as a ``MISE`` of its own would."""
+
+    def __init__(self, B, resolution_0, depth, threshold, device="cuda"):
+        self.B, self.resolution_0, self.depth, self.threshold = int(B), int(resolution_0), int(depth), float(threshold)
+        self.resolution = self.resolution_0 << self.depth
+        self.device = torch.device(device)
+        nbytes = load().ls_mise_batch_state_bytes(self.B, self.resolution_0, self.depth)
+        if nbytes == 0:
+            raise ValueError(f"MISEBatch: B={B} resolution_0={resolution_0} depth={depth} unsupported")
+        self._state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self._off = torch.zeros(self.B + 1, dtype=torch.int64, device=self.device)
+        self._cap = self.B * int(load().ls_mise_lattice_points(self.resolution_0, self.depth))
+        self._idx = torch.empty(self._cap, dtype=torch.int32, device=self.device)
+        self._inst = torch.empty(self._cap, dtype=torch.int32, device=self.device)
+        self._pts = torch.empty(self._cap, 3, dtype=torch.float32, device=self.device)
+        self.reset()
+
+    def reset(self, threshold=None):
+        """Back to the initial lattice (the buffers are kept: one MISEBatch serves many batches)."""
+        if threshold is not None:
+            self.threshold = float(threshold)
+        call(self.device, "ls_mise_init_batch", ptr(self._state), self._state.numel(), self.B, self.resolution_0, self.depth,
+             stream_ptr(self.device))
+
+    def query_device(self, box_size=1.0):
+        """-> (idx [n] int32 lattice index within the octree, inst [n] int32 octree, pts [n,3] float32, offsets): device tensors (views), octree
+        after octree; ``offsets`` is a host list of B+1 integers (rows of octree b: offsets[b]:offsets[b+1]) -- the round's only host read."""
+        call(self.device, "ls_mise_query_batch", ptr(self._state), self.B, self.resolution_0, self.depth, float(box_size), ptr(self._idx),
+             ptr(self._inst), ptr(self._pts), self._cap, ptr(self._off), stream_ptr(self.device))
+        offsets = self._off.cpu().tolist()
+        n = offsets[-1]
+        return self._idx[:n], self._inst[:n], self._pts[:n], offsets
+
+    def update_device(self, idx, inst, values):
+        values = values.to(torch.float32).contiguous()
+        idx, inst = idx.to(torch.int32).contiguous(), inst.to(torch.int32).contiguous()
+        assert idx.shape[0] == values.shape[0] == inst.shape[0]
+        call(self.device, "ls_mise_update_batch", ptr(self._state), self.B, self.resolution_0, self.depth, ctypes.c_double(self.threshold),
+             ptr(idx), ptr(inst), ptr(values), int(idx.shape[0]), stream_ptr(self.device))
+
+    def to_dense_device(self):
+        G = self.resolution + 1
+        out = torch.empty(self.B, G, G, G, dtype=torch.float32, device=self.device)
+        call(self.device, "ls_mise_to_dense_batch", ptr(self._state), self.B, self.resolution_0, self.depth, ptr(out), stream_ptr(self.device))
+        return out
+
+
 class Generator3D:
     """mesh_extractor2.py:17-58 (constructor arguments kept); ``eval_grid`` = everything of ``__generate_from_latent__`` before
     ``extract_mesh``."""
@@ -131,48 +181,39 @@ class Generator3D:
 
     def eval_grid_batch(self, codes, F, on_device=False):
         """Value grids of SEVERAL instances at once (an extension: the reference extracts one mesh at a time).  codes: dict of
-        [B,...] tensors.  All MISE octrees advance in lock-step; each round the unknown points of every instance are packed into
+        [B,...] tensors.  All MISE octrees advance in lock-step (MISEBatch); each round the unknown points of every instance go into
         ONE ragged decoder call (ls_sdf_decode_rows), so the small late rounds and the per-round host round trip are shared.
         Returns a list of B float64 grids, each bit-identical to ``eval_grid`` on that instance."""
+        dense = self._eval_grid_batch_device(codes, F)
+        if on_device:
+            return list(dense.to(torch.float64))
+        return list(dense.cpu().numpy().astype(np.float64))
+
+    def _eval_grid_batch_device(self, codes, F):
+        """eval_grid_batch as ONE float32 device tensor [B,G,G,G] (the float64 grids hold float32 values)."""
         assert self.upsampling_steps > 0, "eval_grid_batch: MISE path only"
         B = codes["z_inv"].shape[0]
         threshold = np.log(self.threshold) - np.log(1.0 - self.threshold)
         box_size = 1 + self.padding
         hip = F._owner().hip_model()
-        pool = self.__dict__.setdefault("_mise_pool", [])
-        while len(pool) < B:
-            pool.append(MISE(self.resolution0, self.upsampling_steps, threshold, device=self.device))
-        mises = pool[:B]
-        for m in mises:
-            if (m.resolution_0, m.depth) != (self.resolution0, self.upsampling_steps):
-                raise ValueError("eval_grid_batch: resolution changed after the MISE pool was created")
-            m.reset(threshold)
-        active = list(range(B))
-        while active:
-            # launch every query first, read all counts back in one copy
-            for b in active:
-                m = mises[b]
-                call(m.device, "ls_mise_query", ptr(m._state), m.resolution_0, m.depth, float(box_size), ptr(m._idx), ptr(m._pts), m._cap,
-                                           ptr(m._count), stream_ptr(m.device))
-            counts = torch.cat([mises[b]._count for b in active]).cpu().tolist()
-            live = [(b, n) for b, n in zip(active, counts) if n > 0]
-            if not live:
+        key = (B, self.resolution0, self.upsampling_steps)
+        cache = self.__dict__.setdefault("_mise_batches", {})
+        if key not in cache:
+            cache[key] = MISEBatch(B, self.resolution0, self.upsampling_steps, threshold, device=self.device)
+        mise = cache[key]
+        mise.reset(threshold)
+        while True:
+            idx, inst, pts, offsets = mise.query_device(box_size)
+            if offsets[-1] == 0:
                 break
-            pts = torch.cat([mises[b]._pts[:n] for b, n in live], 0)
-            inst = torch.cat([torch.full((n,), b, dtype=torch.int32, device=pts.device) for b, n in live])
             sdf = hip.sdf_decode_rows(pts, inst, codes["z_so3"], codes["z_inv"], codes["s"], codes["t"])
-            logits = F.sdf2occ_factor * sdf
-            o = 0
-            for b, n in live:
-                mises[b].update_device(mises[b]._idx[:n], logits[o:o + n])
-                o += n
-            active = [b for b, _ in live]
-        return [m.to_dense_device().to(torch.float64) if on_device else m.to_dense() for m in mises]
+            mise.update_device(idx, inst, F.sdf2occ_factor * sdf)
+        return mise.to_dense_device()
 
     def generate_from_latent_batch(self, codes, F, threads=None):
-        """Meshes of B codes: batched MISE rounds, marching cubes per instance, then the decimation of every non-empty mesh on a thread
+        """Meshes of B codes: batched MISE rounds, one batched marching cubes, then the decimation of every non-empty mesh on a thread
         pool (simplify_mesh_arrays_batch; ``threads`` as there).  Mesh i equals extract_mesh of instance i's grid."""
-        arrays = [self._mc_arrays(g) for g in self.eval_grid_batch(codes, F, on_device=True)]
+        arrays = self._mc_arrays_batch(self._eval_grid_batch_device(codes, F))
         if self.simplify_nfaces is not None:             # :205-208, an empty mesh is returned as it is (:196-197)
             live = [i for i, (v, _) in enumerate(arrays) if v.shape[0] != 0]
             for i, vf in zip(live, simplify_mesh_arrays_batch([arrays[i] for i in live], self.simplify_nfaces, 5.0, threads=threads)):
@@ -195,13 +236,7 @@ class Generator3D:
 
     def _mc_arrays(self, occ_hat):
         """extract_mesh up to the decimation: (vertices float64 [nv,3], faces int64 [nf,3]) numpy, in the normalised frame."""
-        if self.with_normals or self.refinement_step > 0:
-            # Off in every released configuration (configs/more_3rscan.yaml:19-26, room4cates.yaml:32-39) -- and not runnable in the reference on this call
-            # path either: generate_from_latent hands the code DICT on as `c`, estimate_normals does `c.unsqueeze(0)` (mesh_extractor2.py:231: AttributeError
-            # on a dict) and refine_mesh starts with `self.model.eval()` (:257), an attribute Generator3D never sets (OccNet leftovers).  There is no reference
-            # behaviour to reproduce, so the switch is refused loudly instead of inventing one.
-            raise NotImplementedError("with_normals / refinement_step > 0: off in every released configuration and broken in the reference on the "
-                                      "generate_from_latent path (mesh_extractor2.py:231 c.unsqueeze on the code dict, :257 self.model) -- nothing to reproduce")
+        self._refuse_normals_and_refinement()
         n_x, n_y, n_z = occ_hat.shape
         box_size = 1 + self.padding
         threshold = np.log(self.threshold) - np.log(1.0 - self.threshold)
@@ -211,13 +246,40 @@ class Generator3D:
             vol = torch.as_tensor(np.asarray(occ_hat, np.float64), device=self.device)
         vol = torch.nn.functional.pad(vol, (1, 1, 1, 1, 1, 1), value=-1e6)
         vertices, triangles = marching_cubes(vol, threshold)
-        vertices = vertices.cpu().numpy()
-        triangles = triangles.cpu().numpy()
+        return self._normalise_vertices(vertices.cpu().numpy(), (n_x, n_y, n_z)), triangles.cpu().numpy()
+
+    def _mc_arrays_batch(self, grids):
+        """[_mc_arrays(g) for g in grids] for B device grids of one shape ([B,nx,ny,nz] tensor or a list of [nx,ny,nz] tensors): one padding
+        call, one batched marching cubes (marching_cubes_batch), one copy of the packed vertices and faces to the host."""
+        self._refuse_normals_and_refinement()
+        vol = grids if torch.is_tensor(grids) else torch.stack(list(grids))
+        if not vol.is_cuda:
+            raise ValueError("_mc_arrays_batch: the grids must live on the GPU (no CPU fallback)")
+        assert vol.dim() == 4, "_mc_arrays_batch: [B,nx,ny,nz]"
+        threshold = np.log(self.threshold) - np.log(1.0 - self.threshold)
+        vol = torch.nn.functional.pad(vol.to(torch.float64), (1, 1, 1, 1, 1, 1), value=-1e6)
+        verts, faces, vo, fo = _marching_cubes_packed(vol, threshold)
+        verts, faces = self._normalise_vertices(verts.cpu().numpy(), grids[0].shape), faces.cpu().numpy()   # element-wise: the same on a slice
+        return [(verts[vo[b]:vo[b + 1]], faces[fo[b]:fo[b + 1]]) for b in range(vol.shape[0])]
+
+    def _normalise_vertices(self, vertices, shape):
+        """mesh_extractor2.py:178-186: undo the library's 0.5 shift and the padding, normalise to the bounding box (in place)."""
+        n_x, n_y, n_z = shape
+        box_size = 1 + self.padding
         vertices -= 0.5
         vertices -= 1
         vertices /= np.array([n_x - 1, n_y - 1, n_z - 1])
         vertices = box_size * (vertices - 0.5)
-        return vertices, triangles
+        return vertices
+
+    def _refuse_normals_and_refinement(self):
+        if self.with_normals or self.refinement_step > 0:
+            # Off in every released configuration (configs/more_3rscan.yaml:19-26, room4cates.yaml:32-39) -- and not runnable in the reference on this call
+            # path either: generate_from_latent hands the code DICT on as `c`, estimate_normals does `c.unsqueeze(0)` (mesh_extractor2.py:231: AttributeError
+            # on a dict) and refine_mesh starts with `self.model.eval()` (:257), an attribute Generator3D never sets (OccNet leftovers).  There is no reference
+            # behaviour to reproduce, so the switch is refused loudly instead of inventing one.
+            raise NotImplementedError("with_normals / refinement_step > 0: off in every released configuration and broken in the reference on the "
+                                      "generate_from_latent path (mesh_extractor2.py:231 c.unsqueeze on the code dict, :257 self.model) -- nothing to reproduce")
 
 
 def marching_cubes(volume, isovalue):
@@ -242,6 +304,39 @@ def marching_cubes(volume, isovalue):
     if nv:
         call(dev, "ls_marching_cubes_f64", *args, ptr(verts), nv, ptr(faces), nf, ptr(counts), ptr(ws), ws_bytes, stream_ptr(dev))
     return verts, faces
+
+
+def marching_cubes_batch(volumes, isovalue):
+    """[marching_cubes(v, isovalue) for v in volumes] for a device tensor [B,nx,ny,nz] in one batched call (csrc/mcubes.hip,
+    ls_marching_cubes_batch_f64) -> list of B (vertices [nv,3] float64, faces [nf,3] int64), device tensors (views of the packed outputs),
+    each bit-identical to the single op: one sizing call, ONE host read of the offsets, one real call."""
+    verts, faces, vo, fo = _marching_cubes_packed(volumes, isovalue)
+    return [(verts[vo[b]:vo[b + 1]], faces[fo[b]:fo[b + 1]]) for b in range(len(vo) - 1)]
+
+
+def _marching_cubes_packed(volumes, isovalue):
+    """-> (vertices [sum nv,3], faces [sum nf,3], vertex offsets, face offsets): the meshes one after the other, offsets as host lists of B+1."""
+    vol = torch.as_tensor(volumes)
+    if not vol.is_cuda:
+        raise ValueError("marching_cubes_batch: the volumes must live on the GPU (no CPU fallback)")
+    vol = vol.to(torch.float64).contiguous()
+    assert vol.dim() == 4, "marching_cubes_batch: [B,nx,ny,nz]"
+    B, nx, ny, nz = vol.shape
+    iso = float(np.float32(isovalue))   # mcubes.pyx:22 declares `float isovalue`
+    dev = vol.device
+    ws_bytes = load().ls_mcubes_batch_workspace_bytes(B, nx, ny, nz)
+    if ws_bytes == 0:
+        raise ValueError(f"marching_cubes_batch: B={B} volumes of {nx} x {ny} x {nz} unsupported (include/livingscenes_hip.h: limits)")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    off = torch.zeros(2, B + 1, dtype=torch.int64, device=dev)
+    args = (ptr(vol), B, nx, ny, nz, ctypes.c_double(iso))
+    call(dev, "ls_marching_cubes_batch_f64", *args, None, 0, None, 0, ptr(off), ptr(ws), ws_bytes, stream_ptr(dev))
+    vo, fo = off.cpu().tolist()
+    verts = torch.empty(vo[B], 3, dtype=torch.float64, device=dev)
+    faces = torch.empty(fo[B], 3, dtype=torch.int64, device=dev)
+    if vo[B]:
+        call(dev, "ls_marching_cubes_batch_f64", *args, ptr(verts), vo[B], ptr(faces), fo[B], ptr(off), ptr(ws), ws_bytes, stream_ptr(dev))
+    return verts, faces, vo, fo
 
 
 def simplify_mesh_arrays(vertices, faces, f_target=10000, agressiveness=7.0, initial_border=1):

@@ -7,7 +7,7 @@
    call after warm-up, including the host read of the bin entry count the binned ops make.
 2. A synthetic scene of --objects instances (untrained decoder at the released extraction settings: resolution0 32, two up-sampling steps,
    simplify_nfaces 5000, iso-level = median logit) through the per-object leg (eval_grid, marching cubes, serial decimation, the three
-   per-mesh metrics) and the batched leg (eval_grid_batch in groups of 16, marching cubes, simplify_mesh_arrays_batch on
+   per-mesh metrics) and the batched leg (eval_grid_batch and _mc_arrays_batch in groups of 16, simplify_mesh_arrays_batch on
    mesh_extractor2.default_threads() host threads, the *_batch metrics), stage by stage."""
 import argparse
 import json
@@ -82,9 +82,8 @@ def scene_bench(out, n_obj):
     gts = [synth.canonical_mesh(1000 + i, res=64) for i in range(n_obj)]
     row = lambda i: {k: v[i:i + 1] for k, v in canon.items()}
     # warm-up of both legs on two objects
-    for g in gen.eval_grid_batch({k: v[:2] for k, v in canon.items()}, sp.decoder, on_device=True):
-        gen._mc_arrays(g)
-    gen.eval_grid(row(0), sp.decoder, on_device=True)
+    gen._mc_arrays_batch(gen.eval_grid_batch({k: v[:2] for k, v in canon.items()}, sp.decoder, on_device=True))
+    gen._mc_arrays(gen.eval_grid(row(0), sp.decoder, on_device=True))
 
     per = {"mise": 0.0, "marching_cubes": 0.0, "decimation": 0.0, "metrics": 0.0}
     faces_mc, faces_out = [], []
@@ -114,7 +113,9 @@ def scene_bench(out, n_obj):
     for g0 in range(0, n_obj, 16):
         grids += gen.eval_grid_batch({k: v[g0:g0 + 16] for k, v in canon.items()}, sp.decoder, on_device=True)
     t1 = sync_time()
-    arrays = [gen._mc_arrays(g) for g in grids]
+    arrays = []
+    for g0 in range(0, n_obj, 16):
+        arrays += gen._mc_arrays_batch(grids[g0:g0 + 16])
     t2 = sync_time()
     live = [i for i, (v, _) in enumerate(arrays) if len(v)]
     for i, vf in zip(live, me.simplify_mesh_arrays_batch([arrays[i] for i in live], 5000, 5.0)):
