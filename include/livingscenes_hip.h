@@ -597,6 +597,28 @@ int ls_mesh_sample_batch_f64(int M, const double* vertices, long long nv_total, 
                              const long long* face_off, long long count_total, const long long* count_off, const unsigned long long* seeds,
                              double* points_out, int64_t* face_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The registration metrics of the relocalisation evaluation on P (reference instance, rescan instance, predicted pose, ground-truth pose)
+ * tuples per call -- what eval_3rscan.py:384-401 / eval_flyingshape.py:136-148 compute pair by pair.  Pair p owns the rows
+ * [x_off[p], x_off[p+1]) of X [n_total,3] (pc1) and [y_off[p], y_off[p+1]) of Y [m_total,3] (pc2); pred, gt [P,3,4] are the (R | t) that map
+ * pc1 to pc2.  out [P,4] float64 = (rre_deg, rte, rmse, chamfer), the reference's definitions evaluated in float64 from the fp32 inputs:
+ *   rre_deg  lib_more/pose_estimation.py:157-180 rotation_error: 180/pi acos(clamp((tr(R_pred^T R_gt) - 1) / 2, -1, 1)); the symmetry fold
+ *            (eval_3rscan.py:387-393) stays with the caller
+ *   rte      lib_more/pose_estimation.py:183-196 translation_error: |t_pred - t_gt|
+ *   rmse     lib_more/pose_estimation.py:214-233 compute_transformation_error: sqrt((sum_x |pred x - gt x|^2 + sum_y |pred^-1 y - gt^-1 y|^2)
+ *            / (3 (n_p + m_p))), inverses (R^T | -R^T t)
+ *   chamfer  evaluate.py:111-123 chamfer_distance_torch on the rows 0, s, 2 s, ... (s = chamfer_stride; eval_3rscan.py:401 passes
+ *            inst[:, ::10]) of each cloud, read in place: mean_i min_j |pred x'_i - y'_j|^2 + mean_j min_i |y'_j - (pred o gt^-1) y'_i|^2
+ * x_off / y_off: HOST int64 arrays of P + 1 entries (P >= 1) starting at 0, never decreasing, ending at the totals, at most 2^31 - 1 rows per
+ * cloud and no empty cloud (the reference gives NaN): checked before the first HIP call, with errors that name the problem, and copied into the
+ * workspace on the stream.  No floating-point atomics: every sum is cut into chunks that depend on the pair alone and added in a fixed order,
+ * so a pair's four values are BIT-IDENTICAL alone, first, last or anywhere in a batch.  Four launches whatever P; no host synchronisation,
+ * no allocation.  ls_reg_metrics_batch_workspace_bytes: 0 for P < 1, a negative total or chamfer_stride < 1; a missing or short workspace
+ * is LS_ERR_WORKSPACE. */
+size_t ls_reg_metrics_batch_workspace_bytes(int P, long long n_total, long long m_total, int chamfer_stride);
+int ls_reg_metrics_batch(int P, const float* X, long long n_total, const long long* x_off, const float* Y, long long m_total, const long long* y_off,
+                         const float* pred, const float* gt, int chamfer_stride, double* out, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Live per-kernel timing (bench.py's roofline leg): while enabled, every kernel ls_encode / ls_sdf_decode
  * launches is bracketed by hipEvents on the stream it is launched on.  ls_profile_end synchronises those

@@ -32,6 +32,16 @@ def chamfer_distance_torch(src, ref, pred_tsfm, gt_tsfm):
     return dist_src.mean(dim=1) + dist_ref.mean(dim=1)
 
 
+def registration_metrics_batch(pcs1, pcs2, pred, gt, chamfer_stride=10, sizes=None):
+    """What the relocalisation loops compute per registered pair (eval_3rscan.py:384-401, eval_flyingshape.py:136-148), for P pairs in one
+    device call (ops.reg_metrics_batch, csrc/regmetrics.hip): pcs1 / pcs2 = lists of [n_p,3] / [m_p,3] clouds or packed tensors plus
+    sizes = [(n_p, m_p), ...], pred / gt [P,3,4] or [P,4,4] mapping pc1 to pc2 -> {'rre': rotation_error in degrees (the symmetry fold is the
+    caller's), 'rte': translation_error, 'rmse': compute_transformation_error, 'chamfer': chamfer_distance_torch on every
+    chamfer_stride-th point}, float64 [P] device tensors evaluated in float64."""
+    out = ops.reg_metrics_batch(pcs1, pcs2, pred, gt, chamfer_stride=chamfer_stride, sizes=sizes)
+    return {k: out[:, i] for i, k in enumerate(("rre", "rte", "rmse", "chamfer"))}
+
+
 # ------------------------------------------------------------------------------------------------ reconstruction metrics
 def _device():
     return torch.device("cuda", torch.cuda.current_device())

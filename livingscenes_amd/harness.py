@@ -47,9 +47,13 @@ def eval_matching(scenes, solver, method="sequential", batched=False):
 
 
 @torch.no_grad()
-def eval_relocalization(scenes, solver, icp=True):
-    """Pairwise registration of every (ref_i, rescan_i) instance pair (eval_flyingshape.py:110-173)."""
+def eval_relocalization(scenes, solver, icp=True, batched=False, chunk=128):
+    """Pairwise registration of every (ref_i, rescan_i) instance pair (eval_flyingshape.py:110-173).  batched=True: the pairs of ALL scenes
+    are registered in one ``solver._solve_pairwise_registration_batch`` call per ``chunk`` pairs and scored by ONE
+    ``evaluate.registration_metrics_batch`` call with one host read (rre, rte and te in float64); the same dict."""
     rre, rte, te, poses = [], [], [], []
+    if batched:
+        return _eval_relocalization_batched(scenes, solver, icp, chunk)
     for sc in scenes:
         dev = next(solver.model.parameters()).device
         ref, res = sc["ref"].to(dev), sc["rescan"].to(dev)
@@ -63,14 +67,43 @@ def eval_relocalization(scenes, solver, icp=True):
         pred = torch.cat([R, t], 2)
         poses.append(pred.cpu())
         te.append(torch.stack([compute_transformation_error(ref[i:i + 1], res[i:i + 1], pred[i:i + 1], gt[i:i + 1]) for i in range(n)]).cpu())
-    rre, rte, te = torch.cat(rre).numpy(), torch.cat(rte).numpy(), torch.cat(te).numpy()
+    return _relocalization_summary(torch.cat(rre).numpy(), torch.cat(rte).numpy(), torch.cat(te).numpy(), torch.cat(poses).numpy())
 
+
+def _relocalization_summary(rre, rte, te, poses):
     def med(x):
         return float(np.median(x)) if len(x) else float("nan")
     return {"recall_rre5": float((rre < 5).mean() * 100), "recall_rre10": float((rre < 10).mean() * 100),
             "median_rre_5": med(rre[rre < 5]), "median_rte_5": med(rte[rre < 5]), "te_cm_5": med(te[rre < 5]) * 100,
             "median_rre_all": med(rre), "rre": rre, "rte": rte, "te": te,
-            "poses": torch.cat(poses).numpy()}   # [n,3,4] predicted (R | t), for parity checks at matrix level
+            "poses": poses}   # [n,3,4] predicted (R | t), for parity checks at matrix level
+
+
+def _register_chunks(register, pcs1, pcs2, chunk):
+    """register(pcs1[c0:c1], pcs2[c0:c1]) -> (R, t) per ``chunk`` pairs, concatenated"""
+    Rs, ts = [], []
+    for c0 in range(0, len(pcs1), max(int(chunk), 1)):
+        R, t = register(pcs1[c0:c0 + chunk], pcs2[c0:c0 + chunk])
+        Rs.append(R), ts.append(t)
+    return torch.cat(Rs, 0), torch.cat(ts, 0)
+
+
+def _eval_relocalization_batched(scenes, solver, icp, chunk):
+    from . import evaluate
+    dev = next(solver.model.parameters()).device
+    pcs1, pcs2, gts = [], [], []
+    for sc in scenes:
+        ref, res = sc["ref"].to(dev), sc["rescan"].to(dev)
+        pcs1 += [ref[i] for i in range(ref.shape[0])]
+        pcs2 += [res[i] for i in range(ref.shape[0])]
+        gts.append(concatenate(sc["rescan_T"].to(dev)[:, :3], inverse(sc["ref_T"].to(dev)[:, :3])))
+    R, t = _register_chunks(lambda a, b: solver._solve_pairwise_registration_batch(a, b, icp=icp), pcs1, pcs2, chunk)
+    pred = torch.cat([R, t], 2)
+    m = evaluate.registration_metrics_batch(pcs1, pcs2, pred, torch.cat(gts, 0), chamfer_stride=10)
+    host = torch.cat([torch.stack([m["rre"], m["rte"], m["rmse"]], 1), pred.reshape(-1, 12).double()], 1).cpu().numpy()   # the one host read
+    r = host[:, 0]
+    rre = np.minimum(np.minimum(r, np.abs(180 - r)), np.abs(90 - r))  # symmetry fold (:140)
+    return _relocalization_summary(rre, host[:, 1], host[:, 2], host[:, 3:].reshape(-1, 3, 4).astype(np.float32))
 
 
 # ------------------------------------------------------------------------------------------------ 3RScan matching evaluation
@@ -166,17 +199,23 @@ def eval_3rscan_matching(dataset, solver, method_list=("sequential",), batched=F
 
 
 @torch.no_grad()
-def eval_3rscan_relocalization(dataset, solver, optim=True):
+def eval_3rscan_relocalization(dataset, solver, optim=True, batched=False, chunk=128):
     """Instance re-localisation over a ``rscan.Dataset_3RScan`` (eval_3rscan.py:337-456): for every annotated rigid instance that
     is present in both the reference scan and the rescan, register its reference cloud to its rescan cloud
     (``solver._solve_pairwise_registration``; the rescan is first moved back into its own frame with the inverse scene
     transform), then relative rotation error (folded by the annotation's symmetry class: 1 -> min(r, |180-r|), 2 -> also
     |90-r|), relative translation error, end-point RMSE and the chamfer distance of every tenth point.  Reported as the
     reference does: recall at RMSE < 0.1 m with the medians over RMSE < 0.2 m, recall at RRE < 10 deg with the medians over it,
-    median chamfer distance."""
+    median chamfer distance.
+    batched=True: every valid (scene, rescan, rigid) pair is collected first (same validity rule, same inverse scene transform, same
+    order), the pairs are registered ``chunk`` at a time in lock-step (``solver._solve_pairwise_registration_optim_batch`` when
+    ``optim``, else ``solver._solve_pairwise_registration_batch``), and all of them are scored by ONE
+    ``evaluate.registration_metrics_batch`` call with ONE host read; the symmetry fold and the summary are the host's.  Same keys."""
+    from . import evaluate
     from .evaluate import chamfer_distance_torch
     from .lib_math import torch_se3
     rre_l, rte_l, err_l, cd_l, shape_l = [], [], [], [], []
+    pend1, pend2, pend_gt, pend_sym = [], [], [], []
     for i_s, scene in enumerate(dataset.scene_list):
         ref, rescans = dataset._get_scene(i_s)
         if ref is None:
@@ -194,6 +233,10 @@ def eval_3rscan_relocalization(dataset, solver, optim=True):
                 b = res_ids.index(rigid.get("instance_rescan", rigid["instance_reference"]))
                 inst_ref = ref["pc"][a].T[ref["pc_mask"][a, 0]].unsqueeze(0).contiguous()
                 inst_res = pc[b].T[rescan["pc_mask"][b, 0]].unsqueeze(0).contiguous()
+                if batched:
+                    pend1.append(inst_ref[0]), pend2.append(inst_res[0]), pend_gt.append(gt[0, :3]), pend_sym.append(rigid.get("symmetry", 0))
+                    shape_l.append(ref["id_label"][[l[0] for l in ref["id_label"]].index(rigid["instance_reference"])][-1])
+                    continue
                 with torch.enable_grad():
                     R, t = solver._solve_pairwise_registration(inst_ref, inst_res, optim=optim)
                 rre = float(rotation_error(R, gt[:, :3, :3]))
@@ -208,6 +251,18 @@ def eval_3rscan_relocalization(dataset, solver, optim=True):
                 err_l.append(float(compute_transformation_error(inst_ref, inst_res, pred, gt)))
                 cd_l.append(float(chamfer_distance_torch(inst_ref[:, ::10].contiguous(), inst_res[:, ::10].contiguous(), pred, gt)))
                 shape_l.append(ref["id_label"][[l[0] for l in ref["id_label"]].index(rigid["instance_reference"])][-1])
+    if pend1:
+        register = solver._solve_pairwise_registration_optim_batch if optim else solver._solve_pairwise_registration_batch
+        with torch.enable_grad():
+            R, t = _register_chunks(register, pend1, pend2, chunk)
+        m = evaluate.registration_metrics_batch(pend1, pend2, torch.cat([R, t], 2), torch.stack(pend_gt), chamfer_stride=10)
+        host = torch.stack([m["rre"], m["rte"], m["rmse"], m["chamfer"]], 1).cpu().numpy()   # the one host read
+        for (r, te, err, cd), sym in zip(host.tolist(), pend_sym):
+            if sym == 1:
+                r = min(r, abs(180 - r))
+            elif sym == 2:
+                r = min(r, abs(180 - r), abs(90 - r))
+            rre_l.append(r), rte_l.append(te), err_l.append(err), cd_l.append(cd)
     rre, rte, err, cd = (np.asarray(v, dtype=np.float64) for v in (rre_l, rte_l, err_l, cd_l))
     med = lambda v, m: float(np.median(v[m])) if m.any() else float("nan")
     return {"n_pairs": int(len(rre)),

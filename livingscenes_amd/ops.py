@@ -289,6 +289,36 @@ def kabsch_residual_matrix_batch(src, tgt, sizes=None, packed=False):
     return (res, sizes) if packed else _split_scores(res, sizes)
 
 
+def _poses_3x4(g, P, what):
+    """[P,3,4] or [P,4,4] -> fp32 contiguous [P,3,4]"""
+    if g.dim() != 3 or g.shape[0] != P or g.shape[1] not in (3, 4) or g.shape[2] != 4:
+        raise ValueError(f"reg_metrics_batch: {what} must be [P,3,4] or [P,4,4] with P = {P}, got {tuple(g.shape)}")
+    return _f32(g[:, :3, :])
+
+
+def reg_metrics_batch(pcs1, pcs2, pred, gt, chamfer_stride=10, sizes=None):
+    """The registration metrics of P pairs in one call (ls_reg_metrics_batch): pcs1 / pcs2 = lists of [n_p,3] / [m_p,3] clouds (the reference
+    instance and the rescan instance), or packed [n_total,3] / [m_total,3] tensors plus sizes = [(n_p, m_p), ...]; pred, gt [P,3,4] or
+    [P,4,4] map pc1 to pc2 -> float64 [P,4] = (rre_deg, rte, rmse, chamfer) per pair: rotation_error (unfolded), translation_error,
+    compute_transformation_error and chamfer_distance_torch on every chamfer_stride-th row, in float64.  Row p is the same bits whatever
+    else is in the batch."""
+    X, ns = _pack_rows(pcs1, sizes, 0, "reg_metrics_batch")
+    Y, ms = _pack_rows(pcs2, sizes, 1, "reg_metrics_batch")
+    if X.dim() != 2 or Y.dim() != 2 or X.shape[1] != 3 or Y.shape[1] != 3:
+        raise ValueError(f"reg_metrics_batch: clouds are [n, 3], got {tuple(X.shape)} and {tuple(Y.shape)}")
+    if len(ns) != len(ms):
+        raise ValueError(f"reg_metrics_batch: {len(ns)} reference clouds for {len(ms)} rescan clouds")
+    P, dev = len(ns), X.device
+    pred, gt = _poses_3x4(pred.to(dev), P, "pred"), _poses_3x4(gt.to(dev), P, "gt")
+    xo, yo = _offsets(ns), _offsets(ms)
+    s = int(chamfer_stride)
+    out = torch.empty(P, 4, dtype=torch.float64, device=dev)
+    ws = _scratch(load().ls_reg_metrics_batch_workspace_bytes(P, X.shape[0], Y.shape[0], s), dev)
+    call(dev, "ls_reg_metrics_batch", P, ptr(X), X.shape[0], _hptr(xo), ptr(Y), Y.shape[0], _hptr(yo), ptr(pred), ptr(gt), s, ptr(out), ptr(ws),
+         0 if ws is None else ws.numel(), stream_ptr(dev))
+    return out
+
+
 def kabsch(x1, x2, weights=None, return_flags=False, raw_weights=False):
     """x1,x2 [b,n,3] -> R [b,3,3], t [b,3,1], res [b,n] (, status [b] int32: _lib.KABSCH_*).  raw_weights: use `weights` as
     they are instead of normalising them (pose_estimation.py:52-54)."""
