@@ -61,7 +61,8 @@ typedef enum {
  * library reads no development switches from the environment any more; 104: option 4 retired with the staged attention path, refused like
  * any unknown option; 105: the mesh metrics ls_mesh_contains_f64 / ls_mesh_distance_f64 / ls_mesh_sample_f64; 106: ls_model_desc.dec_input and
  * off_dec_xyz_t, the invariant decoder_type "deepsdf"; 107: the ragged multi-mesh metrics ls_mesh_contains_batch_f64 /
- * ls_mesh_distance_batch_f64 / ls_mesh_sample_batch_f64).  ls_version() returns the value the LIBRARY was built with; a
+ * ls_mesh_distance_batch_f64 / ls_mesh_sample_batch_f64; symbols added since -- ls_reg_metrics_batch, ls_mesh_cluster_f64 / ls_mesh_cluster_batch_f64 --
+ * change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
  * binding compares it with the header it was written against and refuses a mismatch (livingscenes_amd/_lib.py: load). */
 #define LS_ABI_VERSION 107
 int ls_version(void);
@@ -596,6 +597,51 @@ size_t ls_mesh_sample_batch_workspace_bytes(int M, long long nf_total);
 int ls_mesh_sample_batch_f64(int M, const double* vertices, long long nv_total, const long long* vert_off, const int32_t* faces, long long nf_total,
                              const long long* face_off, long long count_total, const long long* count_off, const unsigned long long* seeds,
                              double* points_out, int64_t* face_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Decimation on the device (csrc/meshcluster.hip): vertex clustering on a uniform grid with quadric-optimal representatives (Lindstrom
+ * 2000, regularised solve).  A SECOND decimator beside ls_simplify_mesh_f64_host, chosen explicitly: data-parallel and deterministic, it
+ * does not reproduce the reference's edge collapse.  vertices [nv,3] float64, faces [nf,3] int64 (local to the mesh), all on the device.
+ * Non-finite coordinates are not supported (every index stays in range, the output is unspecified).  Per mesh, in float64 and without
+ * contraction, with the sums taken in the stated order (tests/cluster_oracle.py is the same text as NumPy):
+ *   1. nf <= f_target (an empty mesh included): the output is the input unchanged, r = 0.
+ *   2. grid: lo = per-axis minimum over ALL vertices, ext = the largest axis extent (1 if it is 0); at resolution r, h = ext / r, the cell
+ *      of v is c_a = min(r - 1, (int)floor((v_a - lo_a) / h)) per axis, key = (c_x r + c_y) r + c_z.
+ *   3. resolution: n_keep(r) = faces whose three corners have three different keys.  lo = 1, hi = r_max; while lo < hi: mid = (lo + hi + 1) / 2,
+ *      n_keep(mid) <= f_target ? lo = mid : hi = mid - 1.  r* = lo -- defined by this procedure, monotonicity of n_keep is not assumed.
+ *   4. faces at r*: faces with two equal corner keys are dropped; the others are grouped by their UNORDERED key triple; a group with an even
+ *      number of members is dropped, one with an odd number keeps its member of lowest input index.  Output faces keep ascending input
+ *      order and their corner order.  (The map is simplicial, so cancelling in pairs keeps a surface closed mod 2 closed mod 2: ray-parity
+ *      tests such as ls_mesh_contains_f64 keep working.)
+ *   5. vertices: the output cells are those named by an output face, in ascending key order; a face's indices are the ranks of its cells.
+ *      xbar = the mean of all input vertices of the cell, summed in ascending vertex index.  The quadric about xbar runs over every corner
+ *      of every INPUT face (dropped ones included) whose key is the cell, in ascending (face, corner): n = (p1 - p0) x (p2 - p0), a = |n|,
+ *      skipped if a = 0, nh = n / a, A += a nh nh^T, g += a (nh . (p0 - xbar)) nh.  (A + 1e-3 tr(A) I) delta = g (delta = 0 if tr(A) = 0);
+ *      x = xbar + delta clamped per axis to the cell's box [lo_a + c_a h, lo_a + (c_a + 1) h].
+ * No floating-point atomics: a mesh's output bits are the same alone, in any batch and in any run.
+ * Limitation: two sheets closer than one cell map to the same triangles and cancel, so a thin part (a chair leg) can vanish where the edge
+ * collapse keeps it -- which is why this decimator is never a default.
+ * Conventions of ls_marching_cubes_f64: counts_out = DEVICE long long[2] {nv', nf'}, always the full counts; a call with vertices_out =
+ * faces_out = NULL (both or neither) writes only the counts and r_out; nothing at or past cap_v vertices / cap_f faces is written.  Caps
+ * that are too small are an error: where the host can tell (a mesh under the target is copied) the call is refused, otherwise the mesh's
+ * r_out is LS_ERR_INVALID.  r_out (DEVICE int, nullable here): r*, 0 for a copied mesh, or a negative ls_status for the mesh:
+ * LS_ERR_INVALID (a face index outside [0, nv) -- such faces are ignored -- or the caps), LS_ERR_WORKSPACE (the triple hash overflowed;
+ * it holds 2 f_target + 1 slots for at most f_target triples and its probe walk is bounded by the table, so this reports a defect, it
+ * never spins).  1 <= f_target, 1 <= r_max <= 256, nv + 3 nf <= INT_MAX.  The workspace is the caller's (the cell bitmap alone is
+ * r_max^3 bits per mesh: 2 MB at 256); everything is enqueued on the stream, and arguments are checked before the first launch. */
+size_t ls_mesh_cluster_workspace_bytes(long long nv, long long nf, int r_max);
+int ls_mesh_cluster_f64(const double* vertices, long long nv, const long long* faces, long long nf, int f_target, int r_max, double* vertices_out,
+                        long long cap_v, long long* faces_out, long long cap_f, long long* counts_out, int* r_out, void* workspace,
+                        size_t workspace_bytes, void* stream);
+/* M >= 1 meshes per call, stored back to back as for the mesh metrics (HOST int64 offsets of M + 1 entries, checked here -- the error names
+ * the mesh -- and copied into the workspace on the stream); f_target and r_max hold for every mesh.  The outputs are packed mesh after mesh
+ * with face indices local to each mesh; off_out (DEVICE long long [2][M+1]): [0][m] = first output vertex of mesh m, [1][m] = its first
+ * face, [.][M] = the totals, always the full counts; r_out DEVICE int [M].  Every mesh is BIT-IDENTICAL to ls_mesh_cluster_f64 on that
+ * mesh alone, and the number of launches does not depend on M.  ls_mesh_cluster_batch_workspace_bytes is 0 for arguments the op refuses. */
+size_t ls_mesh_cluster_batch_workspace_bytes(int M, long long nv_total, long long nf_total, int r_max);
+int ls_mesh_cluster_batch_f64(int M, const double* vertices, long long nv_total, const long long* vert_off, const long long* faces, long long nf_total,
+                              const long long* face_off, int f_target, int r_max, double* vertices_out, long long cap_v, long long* faces_out,
+                              long long cap_f, long long* off_out, int* r_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* The registration metrics of the relocalisation evaluation on P (reference instance, rescan instance, predicted pose, ground-truth pose)
  * tuples per call -- what eval_3rscan.py:384-401 / eval_flyingshape.py:136-148 compute pair by pair.  Pair p owns the rows

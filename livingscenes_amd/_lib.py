@@ -184,6 +184,11 @@ SIGNATURES = {
     "ls_mesh_distance_batch_workspace_bytes": (_SZ, [_I, ctypes.c_longlong]),
     "ls_mesh_distance_batch_f64": (_I, [_I, _P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _P, _D, _P, _P, ctypes.c_longlong, _P, _P, _SZ, _P]),
     "ls_mesh_sample_batch_workspace_bytes": (_SZ, [_I, ctypes.c_longlong]),
+    "ls_mesh_cluster_workspace_bytes": (_SZ, [ctypes.c_longlong, ctypes.c_longlong, _I]),
+    "ls_mesh_cluster_f64": (_I, [_P, ctypes.c_longlong, _P, ctypes.c_longlong, _I, _I, _P, ctypes.c_longlong, _P, ctypes.c_longlong, _P, _P, _P, _SZ, _P]),
+    "ls_mesh_cluster_batch_workspace_bytes": (_SZ, [_I, ctypes.c_longlong, ctypes.c_longlong, _I]),
+    "ls_mesh_cluster_batch_f64": (_I, [_I, _P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _P, _I, _I, _P, ctypes.c_longlong, _P, ctypes.c_longlong, _P, _P,
+                                   _P, _SZ, _P]),
     "ls_mesh_sample_batch_f64": (_I, [_I, _P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _P, ctypes.c_longlong, _P, _P, _P, _P, _P, _SZ, _P]),
     "ls_reg_metrics_batch_workspace_bytes": (_SZ, [_I, _LL, _LL, _I]),
     "ls_reg_metrics_batch": (_I, [_I, _P, _LL, _P, _P, _LL, _P, _P, _P, _I, _P, _P, _SZ, _P]),

@@ -4,8 +4,10 @@
 (csrc/mise.hip); ``Generator3D.eval_grid`` is the loop of ``__generate_from_latent__`` (mesh_extractor2.py:94-131): per
 round the unknown lattice points go straight from the MISE kernels into ``ls_sdf_decode`` and back -- no host round trip
 except the 4-byte point count.  ``marching_cubes`` mirrors ``libmcubes.marching_cubes`` (csrc/mcubes.hip: same vertex and
-face order, float64 coordinates); ``extract_mesh`` is mesh_extractor2.py:161-214 without normals / simplification / refinement
-(all off in the released settings).
+face order, float64 coordinates); ``extract_mesh`` is mesh_extractor2.py:161-214 without normals / refinement (off in the released
+settings).  Decimation: ``simplify_mesh_arrays`` is the reference's sequential edge collapse on the host (the default);
+``cluster_mesh_arrays`` / ``cluster_mesh_arrays_batch`` are a second decimator on the device (csrc/meshcluster.hip: vertex clustering
+with quadric-optimal representatives), chosen with ``Generator3D(simplify_method="cluster")``.
 """
 import ctypes
 import os
@@ -14,7 +16,9 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from ._lib import call, check, load, ptr, stream_ptr
+from ._lib import LsError, call, check, load, ptr, stream_ptr
+
+SIMPLIFY_METHODS = ("collapse", "cluster")
 
 
 class MISE:
@@ -133,7 +137,14 @@ class Generator3D:
     ``extract_mesh``."""
 
     def __init__(self, points_batch_size=100000, threshold=0.5, refinement_step=0, resolution0=16, upsampling_steps=3,
-                 with_normals=False, padding=0.1, sample=False, simplify_nfaces=None):
+                 with_normals=False, padding=0.1, sample=False, simplify_nfaces=None, simplify_method="collapse"):
+        """simplify_method (an extension): how a mesh is decimated to simplify_nfaces faces.  "collapse" (the default) is the reference's
+        quadric edge collapse on the host, bit-identical to it; "cluster" is the device decimator (cluster_mesh_arrays): vertex clustering
+        on the packed marching-cubes output, only the decimated mesh travels to the host.  It is never chosen implicitly: two sheets closer
+        than one grid cell cancel, so thin parts can vanish where the edge collapse keeps them."""
+        if simplify_method not in SIMPLIFY_METHODS:
+            raise ValueError(f"Generator3D: simplify_method must be one of {SIMPLIFY_METHODS}, got {simplify_method!r}")
+        self.simplify_method = simplify_method
         self.implicit_F = None
         self.device = "cuda"
         self.points_batch_size = points_batch_size
@@ -212,8 +223,11 @@ class Generator3D:
 
     def generate_from_latent_batch(self, codes, F, threads=None):
         """Meshes of B codes: batched MISE rounds, one batched marching cubes, then the decimation of every non-empty mesh on a thread
-        pool (simplify_mesh_arrays_batch; ``threads`` as there).  Mesh i equals extract_mesh of instance i's grid."""
-        arrays = self._mc_arrays_batch(self._eval_grid_batch_device(codes, F))
+        pool (simplify_mesh_arrays_batch; ``threads`` as there).  Mesh i equals extract_mesh of instance i's grid.  With
+        simplify_method "cluster" the packed marching-cubes output is decimated on the device in one call and ``threads`` is ignored."""
+        arrays = self._mc_arrays_batch(self._eval_grid_batch_device(codes, F), cluster=self._clusters())
+        if self._clusters():
+            return [make_mesh(v, t) for v, t in arrays]
         if self.simplify_nfaces is not None:             # :205-208, an empty mesh is returned as it is (:196-197)
             live = [i for i, (v, _) in enumerate(arrays) if v.shape[0] != 0]
             for i, vf in zip(live, simplify_mesh_arrays_batch([arrays[i] for i in live], self.simplify_nfaces, 5.0, threads=threads)):
@@ -227,15 +241,20 @@ class Generator3D:
     def extract_mesh(self, occ_hat, z, c=None, stats_dict=None):
         """mesh_extractor2.py:161-214: pad with -1e6 (watertight), marching cubes at the logit threshold, undo the library's 0.5
         shift and the padding, normalise to the bounding box."""
-        vertices, triangles = self._mc_arrays(occ_hat)
+        vertices, triangles = self._mc_arrays(occ_hat, cluster=self._clusters())
         if vertices.shape[0] == 0:                       # mesh_extractor2.py:196-197: an empty mesh is returned as it is
             return make_mesh(vertices, triangles)
-        if self.simplify_nfaces is not None:             # :205-208 -- the released configs set 5000 / 100000
+        if self.simplify_nfaces is not None and not self._clusters():   # :205-208 -- the released configs set 5000 / 100000
             vertices, triangles = simplify_mesh_arrays(vertices, triangles, self.simplify_nfaces, 5.0)
         return make_mesh(vertices, triangles)
 
-    def _mc_arrays(self, occ_hat):
-        """extract_mesh up to the decimation: (vertices float64 [nv,3], faces int64 [nf,3]) numpy, in the normalised frame."""
+    def _clusters(self):
+        return self.simplify_nfaces is not None and self.simplify_method == "cluster"
+
+    def _mc_arrays(self, occ_hat, cluster=False):
+        """extract_mesh up to the decimation: (vertices float64 [nv,3], faces int64 [nf,3]) numpy, in the normalised frame.
+        cluster=True: decimated on the device to simplify_nfaces faces, in the marching-cubes frame (the normalisation is a uniform scale
+        and a shift, so the cells correspond), before the copy to the host."""
         self._refuse_normals_and_refinement()
         n_x, n_y, n_z = occ_hat.shape
         box_size = 1 + self.padding
@@ -246,11 +265,14 @@ class Generator3D:
             vol = torch.as_tensor(np.asarray(occ_hat, np.float64), device=self.device)
         vol = torch.nn.functional.pad(vol, (1, 1, 1, 1, 1, 1), value=-1e6)
         vertices, triangles = marching_cubes(vol, threshold)
+        if cluster:
+            vertices, triangles = cluster_mesh_arrays(vertices, triangles, self.simplify_nfaces)
         return self._normalise_vertices(vertices.cpu().numpy(), (n_x, n_y, n_z)), triangles.cpu().numpy()
 
-    def _mc_arrays_batch(self, grids):
-        """[_mc_arrays(g) for g in grids] for B device grids of one shape ([B,nx,ny,nz] tensor or a list of [nx,ny,nz] tensors): one padding
-        call, one batched marching cubes (marching_cubes_batch), one copy of the packed vertices and faces to the host."""
+    def _mc_arrays_batch(self, grids, cluster=False):
+        """[_mc_arrays(g, cluster) for g in grids] for B device grids of one shape ([B,nx,ny,nz] tensor or a list of [nx,ny,nz] tensors): one
+        padding call, one batched marching cubes (marching_cubes_batch), with cluster=True one batched decimation of the packed meshes, one
+        copy of the packed vertices and faces to the host."""
         self._refuse_normals_and_refinement()
         vol = grids if torch.is_tensor(grids) else torch.stack(list(grids))
         if not vol.is_cuda:
@@ -259,6 +281,8 @@ class Generator3D:
         threshold = np.log(self.threshold) - np.log(1.0 - self.threshold)
         vol = torch.nn.functional.pad(vol.to(torch.float64), (1, 1, 1, 1, 1, 1), value=-1e6)
         verts, faces, vo, fo = _marching_cubes_packed(vol, threshold)
+        if cluster and vo[-1]:
+            verts, faces, vo, fo, _ = _cluster_packed(verts, vo, faces, fo, self.simplify_nfaces, 256)
         verts, faces = self._normalise_vertices(verts.cpu().numpy(), grids[0].shape), faces.cpu().numpy()   # element-wise: the same on a slice
         return [(verts[vo[b]:vo[b + 1]], faces[fo[b]:fo[b + 1]]) for b in range(vol.shape[0])]
 
@@ -337,6 +361,109 @@ def _marching_cubes_packed(volumes, isovalue):
     if vo[B]:
         call(dev, "ls_marching_cubes_batch_f64", *args, ptr(verts), vo[B], ptr(faces), fo[B], ptr(off), ptr(ws), ws_bytes, stream_ptr(dev))
     return verts, faces, vo, fo
+
+
+def _cluster_caps(nv, nf, f_target):
+    """Bounds on a mesh's output that need no sizing call: a mesh under the target is copied, else at most f_target faces remain and every
+    output vertex is both a corner of one of them and the cell of an input vertex."""
+    if nf <= f_target:
+        return nv, nf
+    return min(nv, 3 * f_target), f_target
+
+
+def _cluster_inputs(vertices, faces, f_target, r_max, what):
+    V, F = torch.as_tensor(vertices), torch.as_tensor(faces)
+    if not (V.is_cuda and F.is_cuda):
+        raise ValueError(f"{what}: vertices and faces must live on the GPU (no CPU fallback; simplify_mesh_arrays is the host decimator)")
+    f_target, r_max = int(f_target), int(r_max)
+    if f_target < 1 or not 1 <= r_max <= 256:
+        raise ValueError(f"{what}: f_target >= 1 and 1 <= r_max <= 256, got {f_target}, {r_max}")
+    return V.to(torch.float64).reshape(-1, 3).contiguous(), F.to(torch.int64).reshape(-1, 3).contiguous(), f_target, r_max
+
+
+def _cluster_status(what, r):
+    for m, rm in enumerate(r):
+        if rm < 0:
+            raise LsError(f"{what}: mesh {m}: " + {-1: "a face index outside the mesh's vertices, or outputs too small",
+                                                   -3: "the face hash overflowed"}.get(rm, f"status {rm}"))
+
+
+def cluster_mesh_arrays(vertices, faces, f_target, r_max=256, return_r=False):
+    """Decimation on the device (csrc/meshcluster.hip, ls_mesh_cluster_f64; include/livingscenes_hip.h holds the definition): vertex
+    clustering on the finest uniform grid of at most r_max cells per axis that leaves at most f_target faces, one quadric-optimal vertex
+    per cell.  vertices [nv,3], faces [nf,3] device tensors -> (vertices [nv',3] float64, faces [nf',3] int64) device tensors
+    (return_r: and the grid resolution r, 0 when nf <= f_target and the mesh is returned unchanged).  Deterministic: the same bits alone,
+    in a batch and in any run.  Not the reference's edge collapse: sheets closer than one cell cancel and thin parts can vanish."""
+    V, F, f_target, r_max = _cluster_inputs(vertices, faces, f_target, r_max, "cluster_mesh_arrays")
+    dev = V.device
+    nv, nf = V.shape[0], F.shape[0]
+    ws_bytes = load().ls_mesh_cluster_workspace_bytes(nv, nf, r_max)
+    if ws_bytes == 0:
+        raise ValueError(f"cluster_mesh_arrays: {nv} vertices, {nf} faces unsupported (include/livingscenes_hip.h: limits)")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    cap_v, cap_f = _cluster_caps(nv, nf, f_target)
+    verts = torch.empty(max(cap_v, 1), 3, dtype=torch.float64, device=dev)
+    tris = torch.empty(max(cap_f, 1), 3, dtype=torch.int64, device=dev)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    r = torch.zeros(1, dtype=torch.int32, device=dev)
+    call(dev, "ls_mesh_cluster_f64", ptr(V), nv, ptr(F), nf, f_target, r_max, ptr(verts), cap_v, ptr(tris), cap_f, ptr(counts), ptr(r), ptr(ws),
+         ws_bytes, stream_ptr(dev))
+    (nvo, nfo), r = counts.cpu().tolist(), int(r.cpu())   # the call's host read
+    _cluster_status("cluster_mesh_arrays", [r])
+    return (verts[:nvo], tris[:nfo], r) if return_r else (verts[:nvo], tris[:nfo])
+
+
+def cluster_mesh_arrays_batch(meshes, f_target, r_max=256, offsets=None, return_r=False):
+    """[cluster_mesh_arrays(v, f, f_target, r_max) for v, f in meshes] in ONE call (ls_mesh_cluster_batch_f64: the number of launches does
+    not depend on the number of meshes), every mesh bit-identical to the single call.  meshes: a list of (vertices, faces) device tensors
+    (or objects with .vertices / .faces), or -- with offsets = (vertex offsets, face offsets), host sequences of M + 1 integers -- the pair
+    (vertices [sum nv,3], faces [sum nf,3]) packed mesh after mesh with indices local to each mesh.  -> list of M (vertices, faces) device
+    tensors, views of the packed outputs (return_r: and the list of the M resolutions)."""
+    if offsets is None:
+        pairs = [(m.vertices, m.faces) if hasattr(m, "vertices") else tuple(m) for m in meshes]
+        if not pairs:
+            return ([], []) if return_r else []
+        Vs = [torch.as_tensor(v).reshape(-1, 3) for v, _ in pairs]
+        Fs = [torch.as_tensor(f).reshape(-1, 3) for _, f in pairs]
+        V, F = torch.cat([v.to(torch.float64) for v in Vs], 0), torch.cat([f.to(torch.int64) for f in Fs], 0)
+        vo = np.concatenate([[0], np.cumsum([v.shape[0] for v in Vs])]).tolist()
+        fo = np.concatenate([[0], np.cumsum([f.shape[0] for f in Fs])]).tolist()
+    else:
+        V, F = meshes
+        vo, fo = ([int(x) for x in o] for o in offsets)
+        if len(vo) != len(fo) or len(vo) < 1:
+            raise ValueError(f"cluster_mesh_arrays_batch: {len(vo)} vertex offsets, {len(fo)} face offsets")
+        if len(vo) == 1:
+            return ([], []) if return_r else []
+    verts, tris, ovo, ofo, r = _cluster_packed(V, vo, F, fo, f_target, r_max)
+    out = [(verts[ovo[m]:ovo[m + 1]], tris[ofo[m]:ofo[m + 1]]) for m in range(len(vo) - 1)]
+    return (out, r) if return_r else out
+
+
+def _cluster_packed(vertices, vert_off, faces, face_off, f_target, r_max):
+    """M >= 1 packed meshes (host offsets) -> (vertices, faces, vertex offsets, face offsets, r): the decimated meshes packed the same way,
+    offsets and resolutions as host lists.  One call, sized by _cluster_caps, and one host read."""
+    V, F, f_target, r_max = _cluster_inputs(vertices, faces, f_target, r_max, "cluster_mesh_arrays_batch")
+    dev = V.device
+    M = len(vert_off) - 1
+    vo, fo = np.ascontiguousarray(vert_off, np.int64), np.ascontiguousarray(face_off, np.int64)
+    ws_bytes = load().ls_mesh_cluster_batch_workspace_bytes(M, V.shape[0], F.shape[0], r_max)
+    if ws_bytes == 0:
+        raise ValueError(f"cluster_mesh_arrays_batch: {M} meshes, {V.shape[0]} vertices, {F.shape[0]} faces unsupported "
+                         "(include/livingscenes_hip.h: limits)")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    caps = [_cluster_caps(int(vo[m + 1] - vo[m]), int(fo[m + 1] - fo[m]), f_target) for m in range(M)]
+    cap_v, cap_f = sum(c[0] for c in caps), sum(c[1] for c in caps)
+    verts = torch.empty(max(cap_v, 1), 3, dtype=torch.float64, device=dev)
+    tris = torch.empty(max(cap_f, 1), 3, dtype=torch.int64, device=dev)
+    off = torch.zeros(2, M + 1, dtype=torch.int64, device=dev)
+    r = torch.zeros(M, dtype=torch.int32, device=dev)
+    P = ctypes.c_void_p
+    call(dev, "ls_mesh_cluster_batch_f64", M, ptr(V), V.shape[0], P(vo.ctypes.data), ptr(F), F.shape[0], P(fo.ctypes.data), f_target, r_max,
+         ptr(verts), cap_v, ptr(tris), cap_f, ptr(off), ptr(r), ptr(ws), ws_bytes, stream_ptr(dev))
+    (ovo, ofo), r = off.cpu().tolist(), r.cpu().tolist()   # the call's host read
+    _cluster_status("cluster_mesh_arrays_batch", r)
+    return verts[:ovo[M]], tris[:ofo[M]], ovo, ofo, r
 
 
 def simplify_mesh_arrays(vertices, faces, f_target=10000, agressiveness=7.0, initial_border=1):

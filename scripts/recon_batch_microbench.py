@@ -8,7 +8,10 @@
 2. A synthetic scene of --objects instances (untrained decoder at the released extraction settings: resolution0 32, two up-sampling steps,
    simplify_nfaces 5000, iso-level = median logit) through the per-object leg (eval_grid, marching cubes, serial decimation, the three
    per-mesh metrics) and the batched leg (eval_grid_batch and _mc_arrays_batch in groups of 16, simplify_mesh_arrays_batch on
-   mesh_extractor2.default_threads() host threads, the *_batch metrics), stage by stage."""
+   mesh_extractor2.default_threads() host threads, the *_batch metrics), stage by stage.
+3. The same scene through the batched leg twice in one run, decimated by the host edge collapse (simplify_method "collapse", the thread pool)
+   and by the device vertex clustering ("cluster", docs/history.md 26): ms per scene and stage, faces per mesh, and Chamfer / SDF recall /
+   V-IoU of both against the same ground truth (synthetic weights and analytic shapes: a comparison of the two decimators, not a result)."""
 import argparse
 import json
 import os
@@ -69,7 +72,7 @@ def ops_bench(out):
     out["ops"] = res
 
 
-def scene_bench(out, n_obj):
+def scene_setup(n_obj):
     ecfg, dcfg = synth.default_encoder_cfg(), synth.default_decoder_cfg()
     sp = Shape_Prior.from_state(ecfg, dcfg, synth.make_encoder_weights(ecfg, 0), synth.make_decoder_weights(dcfg, 0), device=dev)
     with torch.no_grad():
@@ -80,6 +83,11 @@ def scene_bench(out, n_obj):
     level = float(np.median(gen.eval_grid({k: v[:1] for k, v in canon.items()}, sp.decoder)))
     gen.threshold = 1.0 / (1.0 + np.exp(-level))
     gts = [synth.canonical_mesh(1000 + i, res=64) for i in range(n_obj)]
+    return sp, canon, gen, gts
+
+
+def scene_bench(out, n_obj):
+    sp, canon, gen, gts = scene_setup(n_obj)
     row = lambda i: {k: v[i:i + 1] for k, v in canon.items()}
     # warm-up of both legs on two objects
     gen._mc_arrays_batch(gen.eval_grid_batch({k: v[:2] for k, v in canon.items()}, sp.decoder, on_device=True))
@@ -136,11 +144,60 @@ def scene_bench(out, n_obj):
     print(json.dumps(out["scene"]), flush=True)
 
 
+def cluster_bench(out, n_obj):
+    """the batched leg with both decimators, stage by stage (groups of 16 instances, as the harness runs it)"""
+    sp, canon, gen, gts = scene_setup(n_obj)
+    logit = np.log(gen.threshold) - np.log(1.0 - gen.threshold)
+    groups = [{k: v[g0:g0 + 16] for k, v in canon.items()} for g0 in range(0, n_obj, 16)]
+    res = {"objects": n_obj, "host_threads": me.default_threads()}
+    for method in ("collapse", "cluster", "collapse", "cluster"):      # the first pass of each warms up
+        t = {"mise": 0.0, "marching_cubes": 0.0, "decimation": 0.0, "to_host": 0.0}
+        arrays, faces_mc = [], []
+        for codes in groups:
+            t0 = sync_time()
+            grids = gen._eval_grid_batch_device(codes, sp.decoder)
+            t1 = sync_time()
+            vol = torch.nn.functional.pad(grids.to(torch.float64), (1, 1, 1, 1, 1, 1), value=-1e6)
+            verts, faces, vo, fo = me._marching_cubes_packed(vol, logit)
+            t2 = sync_time()
+            faces_mc += np.diff(fo).tolist()
+            if method == "cluster":
+                verts, faces, vo, fo, _ = me._cluster_packed(verts, vo, faces, fo, 5000, 256)
+            t3 = sync_time()
+            hv, hf = gen._normalise_vertices(verts.cpu().numpy(), grids[0].shape), faces.cpu().numpy()
+            part = [(hv[vo[b]:vo[b + 1]], hf[fo[b]:fo[b + 1]]) for b in range(len(vo) - 1)]
+            t4 = sync_time()
+            if method == "collapse":
+                live = [i for i, (v, _) in enumerate(part) if len(v)]
+                for i, vf in zip(live, me.simplify_mesh_arrays_batch([part[i] for i in live], 5000, 5.0)):
+                    part[i] = vf
+            t5 = time.perf_counter()
+            arrays += part
+            for k, dt in zip(t, (t1 - t0, t2 - t1, (t3 - t2) + (t5 - t4), t4 - t3)):
+                t[k] += dt * 1e3
+        meshes = [me.make_mesh(v, f) for v, f in arrays]
+        live = [i for i, (v, _) in enumerate(arrays) if len(v)]
+        P, G = [meshes[i] for i in live], [gts[i] for i in live]
+        t0 = sync_time()
+        cd = evaluate.compute_chamfer_distance_batch(G, P, offset=0, scale=1)
+        rec = evaluate.compute_sdf_recall_batch(P, G, 0.05)
+        iou = evaluate.compute_volumetric_iou_batch(P, G)
+        t["metrics"] = (sync_time() - t0) * 1e3
+        t["total"] = sum(t.values())
+        nf = [len(f) for _, f in arrays]
+        res[method] = {"ms": t, "faces_mc_mean": float(np.mean(faces_mc)), "faces_out_mean": float(np.mean(nf)), "faces_out_min": int(min(nf)),
+                       "faces_out_max": int(max(nf)), "chamfer_mean": np.mean(np.asarray(cd, np.float64), 0).tolist(),
+                       "sdf_recall_mean": float(np.mean(rec)), "viou_mean": float(np.mean(iou))}
+    out["cluster_scene"] = res
+    print(json.dumps(res), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--objects", type=int, default=32)
     ap.add_argument("--skip-ops", action="store_true")
     ap.add_argument("--skip-scene", action="store_true")
+    ap.add_argument("--skip-cluster", action="store_true")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     out = {"device": torch.cuda.get_device_name(0), "cpus_available": len(os.sched_getaffinity(0)),
@@ -150,6 +207,8 @@ if __name__ == "__main__":
         ops_bench(out)
     if not a.skip_scene:
         scene_bench(out, a.objects)
+    if not a.skip_cluster:
+        cluster_bench(out, a.objects)
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:
