@@ -572,36 +572,26 @@ bool edge_ft_supported(int Co, int Cin, int Ns, int Nd, int head_c, bool has_row
     return false;
 }
 int edge_ft_heads_per_group(int Cin) { return Cin == 256 ? 2 : 1; }
-// scratch of one fused layer call (inside the layer's table area): A planes + exponents (source rows, and the selected destination rows
-// when the layer down-samples), raw scores, partial norms
-size_t edge_ft_scratch_bytes(int B, int Ns, int Nd, int Cin, int Co, bool has_rows) {
-    const size_t rp = (size_t)B * Ns * 3, rq = (size_t)B * Nd * 3, H = Co / 16;
-    size_t s = rp * Cin * 4 + rp * 4 + 512;
-    if (has_rows) s += rq * Cin * 4 + rq * 4 + 512;
-    s += 2 * ((size_t)B * H * Nd * FK * 4 + 256) + (size_t)B * H * Nd * 4 + 256;
-    s += (size_t)B * Nd * FK * 4 + 256 + (size_t)B * Nd * 4 + 256;       // the summed norms (invk, invq)
-    return s;
-}
-struct FtScratch { uint4* a_p; int* ae_p; uint4* a_q; int* ae_q; float* scores; float* sskp; float* ssqp; float* invk; float* invq; };
+// scratch of one fused layer call (inside the layer's table area): A planes (rows of Cin / 4 uint4) + exponents (source rows, and the selected
+// destination rows when the layer down-samples), raw scores, partial norms, the summed norms (invk, invq).  A null `scratch`: a sizing pass.
+struct FtScratch { uint4* a_p; int* ae_p; uint4* a_q; int* ae_q; float* scores; float* sskp; float* ssqp; float* invk; float* invq; size_t bytes; };
 static FtScratch ft_layout(void* scratch, int B, int Ns, int Nd, int Cin, int Co, bool has_rows) {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t rp = (size_t)B * Ns * 3, rq = (size_t)B * Nd * 3, H = Co / 16;
-    char* c = (char*)scratch;
+    Arena a(scratch);
     FtScratch s;
-    size_t off = 0;
-    s.a_p = (uint4*)(c + off); off = up(off + rp * Cin * 4);
-    s.ae_p = (int*)(c + off); off = up(off + rp * 4);
-    if (has_rows) {
-        s.a_q = (uint4*)(c + off); off = up(off + rq * Cin * 4);
-        s.ae_q = (int*)(c + off); off = up(off + rq * 4);
-    } else { s.a_q = s.a_p; s.ae_q = s.ae_p; }
-    s.scores = (float*)(c + off); off = up(off + (size_t)B * H * Nd * FK * 4);
-    s.sskp = (float*)(c + off); off = up(off + (size_t)B * H * Nd * FK * 4);
-    s.ssqp = (float*)(c + off); off = up(off + (size_t)B * H * Nd * 4);
-    s.invk = (float*)(c + off); off = up(off + (size_t)B * Nd * FK * 4);
-    s.invq = (float*)(c + off);
+    s.a_p = a.take<uint4>(rp * Cin / 4);
+    s.ae_p = a.take<int>(rp);
+    s.a_q = has_rows ? a.take<uint4>(rq * Cin / 4) : s.a_p;
+    s.ae_q = has_rows ? a.take<int>(rq) : s.ae_p;
+    s.scores = a.take<float>((size_t)B * H * Nd * FK);
+    s.sskp = a.take<float>((size_t)B * H * Nd * FK);
+    s.ssqp = a.take<float>((size_t)B * H * Nd);
+    s.invk = a.take<float>((size_t)B * Nd * FK);
+    s.invq = a.take<float>((size_t)B * Nd);
+    s.bytes = a.bytes();
     return s;
 }
+size_t edge_ft_scratch_bytes(int B, int Ns, int Nd, int Cin, int Co, bool has_rows) { return ft_layout(nullptr, B, Ns, Nd, Cin, Co, has_rows).bytes; }
 // the layer's operand image (launched where the table GEMM was: it depends on the features only, not on the graph)
 int edge_ft_prep_launch(const float* cur, const int32_t* dst_rows, int B, int Ns, int Nd, int Cin, int Co, void* scratch, hipStream_t st) {
     const bool has_rows = dst_rows != nullptr;

@@ -566,7 +566,7 @@ __global__ __launch_bounds__(NT) void fps_bucket_kernel(const float* __restrict_
 size_t fps_scratch_bytes_per_cloud(int N) {
     if (N <= 8192) return 0;
     size_t b = (size_t)N * (12 + 4 + 4) + (size_t)(FB_CELLS + FB_MAXB + 1) * 4;
-    return (b + 255) & ~(size_t)255;
+    return align256(b);
 }
 
 template <int PPL, bool FMA>

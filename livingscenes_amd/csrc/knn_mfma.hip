@@ -557,18 +557,16 @@ int knn_sweep_max_ns() { return KF_MAXNS; }
 // scratch of one call: per-query exact-distance counters | row norms (src, dst) | inverse row scales (src, dst) | f16 images (src, dst)
 struct KfScratch { float *nsrc, *ndst, *isrc, *idst; int32_t* cnt; unsigned short *sq, *dq; size_t bytes; };
 static KfScratch kf_layout(void* scratch, int B, int Nd, int dst_n, int Ns, int D, bool self) {
-    char* sc = (char*)scratch;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = sc + off; off = (off + bytes + 255) & ~(size_t)255; return p; };
+    Arena a(scratch);   // null: a sizing pass
     KfScratch k;
-    k.cnt = (int32_t*)take((size_t)B * Nd * sizeof(int32_t));      // (first: knn_sweep_stats_launch finds it whatever the rest looks like)
-    k.nsrc = (float*)take((size_t)B * Ns * sizeof(float));
-    k.ndst = self ? k.nsrc : (float*)take((size_t)B * dst_n * sizeof(float));
-    k.isrc = (float*)take((size_t)B * Ns * sizeof(float));
-    k.idst = self ? k.isrc : (float*)take((size_t)B * dst_n * sizeof(float));
-    k.sq = (unsigned short*)take((size_t)B * pad32(Ns) * D * sizeof(unsigned short));
-    k.dq = self ? k.sq : (unsigned short*)take((size_t)B * pad32(dst_n) * D * sizeof(unsigned short));
-    k.bytes = off;
+    k.cnt = a.take<int32_t>((size_t)B * Nd);      // (first: knn_sweep_stats_launch finds it whatever the rest looks like)
+    k.nsrc = a.take<float>((size_t)B * Ns);
+    k.ndst = self ? k.nsrc : a.take<float>((size_t)B * dst_n);
+    k.isrc = a.take<float>((size_t)B * Ns);
+    k.idst = self ? k.isrc : a.take<float>((size_t)B * dst_n);
+    k.sq = a.take<unsigned short>((size_t)B * pad32(Ns) * D);
+    k.dq = self ? k.sq : a.take<unsigned short>((size_t)B * pad32(dst_n) * D);
+    k.bytes = a.bytes();
     return k;
 }
 size_t knn_sweep_scratch_bytes(int B, int Nd, int dst_n, int Ns, int C) { return kf_layout(nullptr, B, Nd, dst_n, Ns, 3 * C, false).bytes; }

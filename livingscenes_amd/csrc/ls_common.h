@@ -8,6 +8,7 @@
 #include <limits.h>
 
 #include "../../include/livingscenes_hip.h"
+#include "ls_workspace.h"
 
 namespace ls {
 

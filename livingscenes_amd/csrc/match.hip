@@ -606,10 +606,19 @@ int assign_run(const Problems& L, int count, size_t lds, const float* S, int mod
 // ---------------------------------------------------------------------------------------------- ragged batches
 // Every problem's result is bit-identical to the single op on that problem alone: the same kernels, the same launch choices per problem.
 // The argument checks run before the first HIP call (no device is needed to be told what is wrong with the offsets).
+// The one statement of a batch's workspace: the device copy of the offsets and the class lists, then (cosine scores only) the inverse row norms.
+// A null ws: a sizing pass.  The size has always ended with the last norm, unpadded.
+struct BatchWs { long long* offs; float* inv_norm; size_t bytes; };
+static BatchWs batch_layout(void* ws, int P, long long n_total, long long m_total, int with_norms) {
+    Arena a(ws);
+    BatchWs w;
+    w.offs = a.take<long long>((size_t)MOFF_ARRAYS * (P + 1) + (size_t)P);
+    w.inv_norm = with_norms ? a.take<float>((size_t)(n_total + m_total)) : nullptr;
+    w.bytes = with_norms ? a.bytes_unpadded() : a.bytes();
+    return w;
+}
 static size_t match_batch_workspace_bytes(int P, long long n_total, long long m_total, int with_norms) {
-    if (P <= 0 || n_total < 0 || m_total < 0) return 0;
-    const size_t offs = ((size_t)MOFF_ARRAYS * (P + 1) + (size_t)P) * sizeof(long long);
-    return ((offs + 255) / 256) * 256 + (with_norms ? (size_t)(n_total + m_total) * sizeof(float) : 0);
+    return (P <= 0 || n_total < 0 || m_total < 0) ? 0 : batch_layout(nullptr, P, n_total, m_total, with_norms).bytes;
 }
 
 namespace {
@@ -647,9 +656,9 @@ int batch_setup(const char* op, int P, long long n_total, const long long* src_o
         if (cls[p] == GREEDY_BLOCK) b->greedy_lds = std::max(b->greedy_lds, (size_t)(n + m) * sizeof(int));
         if (n * m > 4096) b->any_large = true;
     }
-    const size_t need = match_batch_workspace_bytes(P, n_total, m_total, with_norms);
-    if (!ws || ws_bytes < need) {
-        set_error("%s: workspace %zu < required %zu", op, ws ? ws_bytes : (size_t)0, need);
+    const BatchWs w = batch_layout(ws, P, n_total, m_total, with_norms);
+    if (!ws || ws_bytes < w.bytes) {
+        set_error("%s: workspace %zu < required %zu", op, ws ? ws_bytes : (size_t)0, w.bytes);
         return LS_ERR_WORKSPACE;
     }
     b->host = pack_offsets(P, {src_off, tgt_off, ent.data(), row.data()});
@@ -657,8 +666,8 @@ int batch_setup(const char* op, int P, long long n_total, const long long* src_o
     int at[GREEDY_CLASSES];
     for (int c = 0, first = 0; c < GREEDY_CLASSES; first += b->cls_count[c], ++c) at[c] = b->cls_first[c] = first;
     for (int p = 0; p < P; ++p) b->host[(size_t)MOFF_ARRAYS * (P + 1) + at[cls[p]]++] = p;
-    b->L = RaggedProblems{(const long long*)ws, nullptr, P};
-    b->inv_norm = with_norms ? (float*)((char*)ws + match_batch_workspace_bytes(P, 0, 0, 0)) : nullptr;
+    b->L = RaggedProblems{w.offs, nullptr, P};
+    b->inv_norm = w.inv_norm;
     b->rows = row[P];
     b->entries = ent[P];
     return LS_OK;

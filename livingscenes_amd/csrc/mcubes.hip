@@ -256,16 +256,14 @@ struct McWorkspace {
 };
 static McWorkspace mc_workspace(void* workspace, int B, long long ncubes) {
     McWorkspace w{};
-    char* ws = (char*)workspace;
+    Arena a(workspace);   // null: a sizing pass
     const size_t n = (size_t)B * ncubes;
-    size_t off = 0;
-    auto take = [&](size_t b) { size_t o = off; off = (off + b + 255) & ~(size_t)255; return ws + o; };
     w.nblk = (int)((ncubes + MC_PER_BLOCK - 1) / MC_PER_BLOCK);
-    w.cfg = (unsigned char*)take(n);
-    w.vbase = (int*)take(n * 4);
-    w.pbase = (int*)take(n * 4);
-    w.blk = (u64*)take(((size_t)B * w.nblk + 1) * 8);
-    w.total = off;
+    w.cfg = a.take<unsigned char>(n);
+    w.vbase = a.take<int>(n);
+    w.pbase = a.take<int>(n);
+    w.blk = a.take<u64>((size_t)B * w.nblk + 1);
+    w.total = a.bytes();
     return w;
 }
 

@@ -41,8 +41,6 @@ struct Params {
     int cnt[MAX_PROBES];    // n_keep of the probes
 };
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // ------------------------------------------------------------------------------------------------ which mesh: one, or one of a ragged batch
 struct MeshRef {
     const double* V;
@@ -528,16 +526,6 @@ using namespace ls;
 using namespace ls::mcl;
 
 namespace {
-struct Layout {   // carve a workspace in 256-byte aligned pieces
-    size_t off = 0;
-    template <typename T>
-    T* take(char* base, size_t n) {
-        T* p = base ? (T*)(base + off) : nullptr;
-        off = align256(off + n * sizeof(T));
-        return p;
-    }
-};
-
 int blocks_per_mesh(int r_max) { return (int)scan_blocks(((long long)r_max * r_max * r_max + 31) / 32); }
 
 struct Ws {
@@ -558,46 +546,48 @@ struct Ws {
     long long* lstart;
     long long* lblk;
     int* entries;
-    size_t zero_begin, zero_end;   // bitmap .. lcount: cleared together
+    size_t zero_bytes;    // cnt .. lcount, padding included: cleared together
+    size_t bytes;         // of the whole layout
 };
 
 // the layout depends on (M, nv, nf, r_max) alone: 2 nf + M hash slots cover 2 min(nf_m, f_target) + 1 per mesh for any f_target
-Ws layout(char* ws, size_t n_offs, int M, long long nv, long long nf, int r_max, size_t* bytes) {
-    Layout L;
+// (ws null: a sizing pass)
+Ws layout(void* ws, size_t n_offs, int M, long long nv, long long nf, int r_max) {
+    Arena a(ws);
     Ws w;
     const size_t words = (size_t)M * blocks_per_mesh(r_max) * SCAN_PER_BLOCK;
-    w.offs = L.take<long long>(ws, n_offs);
-    w.prm = L.take<Params>(ws, (size_t)M);
-    w.off = L.take<long long>(ws, 2 * ((size_t)M + 1));
-    w.ftotal = L.take<long long>(ws, 1);
-    w.ltotal = L.take<long long>(ws, 1);
-    w.fkey = L.take<int>(ws, (size_t)nf * 3);
-    w.fstate = L.take<int>(ws, (size_t)nf);
-    w.keep = L.take<int>(ws, (size_t)nf);
-    w.fpos = L.take<long long>(ws, (size_t)nf);
-    w.fblk = L.take<long long>(ws, (size_t)scan_blocks(nf));
+    w.offs = a.take<long long>(n_offs);
+    w.prm = a.take<Params>((size_t)M);
+    w.off = a.take<long long>(2 * ((size_t)M + 1));
+    w.ftotal = a.take<long long>(1);
+    w.ltotal = a.take<long long>(1);
+    w.fkey = a.take<int>((size_t)nf * 3);
+    w.fstate = a.take<int>((size_t)nf);
+    w.keep = a.take<int>((size_t)nf);
+    w.fpos = a.take<long long>((size_t)nf);
+    w.fblk = a.take<long long>((size_t)scan_blocks(nf));
     w.slots = 2 * (size_t)nf + (size_t)M;
-    w.rep = L.take<int>(ws, w.slots);
-    w.mn = L.take<int>(ws, w.slots);
-    w.zero_begin = L.off;
-    w.cnt = L.take<int>(ws, w.slots);
-    w.bitmap = L.take<unsigned>(ws, words);
-    w.lcount = L.take<int>(ws, (size_t)nv);
-    w.zero_end = L.off;
-    w.wprefix = L.take<int>(ws, words);
-    w.bblk = L.take<int>(ws, (size_t)M * blocks_per_mesh(r_max));
-    w.cellkey = L.take<int>(ws, (size_t)nv);
-    w.lstart = L.take<long long>(ws, (size_t)nv);
-    w.lblk = L.take<long long>(ws, (size_t)scan_blocks(nv));
-    w.entries = L.take<int>(ws, (size_t)nv + 3 * (size_t)nf);
-    if (bytes) *bytes = L.off;
+    w.rep = a.take<int>(w.slots);
+    w.mn = a.take<int>(w.slots);
+    const size_t zero_begin = a.bytes();
+    w.cnt = a.take<int>(w.slots);
+    w.bitmap = a.take<unsigned>(words);
+    w.lcount = a.take<int>((size_t)nv);
+    w.zero_bytes = a.bytes() - zero_begin;
+    w.wprefix = a.take<int>(words);
+    w.bblk = a.take<int>((size_t)M * blocks_per_mesh(r_max));
+    w.cellkey = a.take<int>((size_t)nv);
+    w.lstart = a.take<long long>((size_t)nv);
+    w.lblk = a.take<long long>((size_t)scan_blocks(nv));
+    w.entries = a.take<int>((size_t)nv + 3 * (size_t)nf);
+    w.bytes = a.bytes();
     return w;
 }
 
 // the launch sequence: M meshes located by L, nv vertices and nf faces in all, `slots` hash slots in use.  Without outputs (a sizing
 // call) it stops once the offsets are written.
 template <class Meshes>
-int cluster_launch(const Meshes& L, int M, long long nv, long long nf, size_t slots, int f_target, int r_max, const Ws& w, char* base,
+int cluster_launch(const Meshes& L, int M, long long nv, long long nf, size_t slots, int f_target, int r_max, const Ws& w,
                    double* vertices_out, long long cap_v, long long* faces_out, long long cap_f, long long* off_out, long long* counts_out,
                    int* r_out, hipStream_t st) {
     const int bpm = blocks_per_mesh(r_max);
@@ -612,7 +602,7 @@ int cluster_launch(const Meshes& L, int M, long long nv, long long nf, size_t sl
         hipLaunchKernelGGL(resolve_kernel<Meshes>, dim3(cdiv(M, 256)), dim3(256), 0, st, L, M, w.prm, probes, f_target, r_max);
         LS_HIP_CHECK(hipMemsetAsync(w.rep, 0xFF, slots * sizeof(int), st));   // -1: free
         LS_HIP_CHECK(hipMemsetAsync(w.mn, 0x7F, slots * sizeof(int), st));    // above every face index
-        LS_HIP_CHECK(hipMemsetAsync(base + w.zero_begin, 0, w.zero_end - w.zero_begin, st));
+        LS_HIP_CHECK(hipMemsetAsync(w.cnt, 0, w.zero_bytes, st));
         hipLaunchKernelGGL(face_key_kernel<Meshes>, dim3(fb), dim3(256), 0, st, L, w.prm, w.fkey, w.fstate);
         hipLaunchKernelGGL(face_hash_kernel<Meshes>, dim3(fb), dim3(256), 0, st, L, w.prm, w.fkey, w.fstate, w.rep, w.cnt, w.mn);
         hipLaunchKernelGGL(face_select_kernel<Meshes>, dim3(fb), dim3(256), 0, st, L, w.prm, w.fkey, w.fstate, w.cnt, w.mn, wpm, w.bitmap, w.keep);
@@ -666,9 +656,7 @@ extern "C" {
 
 size_t ls_mesh_cluster_workspace_bytes(long long nv, long long nf, int r_max) {
     if (nv < 0 || nf < 0 || nv + 3 * nf > INT_MAX || r_max < 1 || r_max > R_MAX) return 0;
-    size_t b;
-    layout(nullptr, 0, 1, nv, nf, r_max, &b);
-    return b;
+    return layout(nullptr, 0, 1, nv, nf, r_max).bytes;
 }
 
 int ls_mesh_cluster_f64(const double* vertices, long long nv, const long long* faces, long long nf, int f_target, int r_max, double* vertices_out,
@@ -686,17 +674,15 @@ int ls_mesh_cluster_f64(const double* vertices, long long nv, const long long* f
         set_error("%s: workspace too small (need ls_mesh_cluster_workspace_bytes(%lld, %lld, %d))", op, nv, nf, r_max);
         return LS_ERR_WORKSPACE;
     }
-    const Ws w = layout((char*)workspace, 0, 1, nv, nf, r_max, nullptr);
+    const Ws w = layout(workspace, 0, 1, nv, nf, r_max);
     const long long T = table_slots(nf, f_target);
-    return cluster_launch(OneMesh{vertices, nv, faces, nf, T}, 1, nv, nf, (size_t)T, f_target, r_max, w, (char*)workspace, vertices_out, cap_v,
+    return cluster_launch(OneMesh{vertices, nv, faces, nf, T}, 1, nv, nf, (size_t)T, f_target, r_max, w, vertices_out, cap_v,
                           faces_out, cap_f, nullptr, counts_out, r_out, (hipStream_t)stream);
 }
 
 size_t ls_mesh_cluster_batch_workspace_bytes(int M, long long nv_total, long long nf_total, int r_max) {
     if (M < 1 || nv_total < 0 || nf_total < 0 || nv_total + 3 * nf_total > INT_MAX || r_max < 1 || r_max > R_MAX) return 0;
-    size_t b;
-    layout(nullptr, (size_t)OFF_ARRAYS * (M + 1), M, nv_total, nf_total, r_max, &b);
-    return b;
+    return layout(nullptr, (size_t)OFF_ARRAYS * (M + 1), M, nv_total, nf_total, r_max).bytes;
 }
 
 int ls_mesh_cluster_batch_f64(int M, const double* vertices, long long nv_total, const long long* vert_off, const long long* faces, long long nf_total,
@@ -729,11 +715,11 @@ int ls_mesh_cluster_batch_f64(int M, const double* vertices, long long nv_total,
         return LS_ERR_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    const Ws w = layout((char*)workspace, (size_t)OFF_ARRAYS * (M + 1), M, nv_total, nf_total, r_max, nullptr);
+    const Ws w = layout(workspace, (size_t)OFF_ARRAYS * (M + 1), M, nv_total, nf_total, r_max);
     rc = upload_offsets(w.offs, pack_offsets(M, {vert_off, face_off, slot_off.data()}), st);
     if (rc != LS_OK) return rc;
     return cluster_launch(RaggedMeshes{vertices, faces, w.offs, M, nv_total, nf_total}, M, nv_total, nf_total, (size_t)slot_off[M], f_target, r_max, w,
-                          (char*)workspace, vertices_out, cap_v, faces_out, cap_f, off_out, nullptr, r_out, st);
+                          vertices_out, cap_v, faces_out, cap_f, off_out, nullptr, r_out, st);
 }
 
 }  // extern "C"

@@ -49,8 +49,6 @@ struct Params {
 constexpr size_t PARAMS_BYTES = 256;
 static_assert(sizeof(Params) <= PARAMS_BYTES, "Params");
 
-__host__ __device__ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // ------------------------------------------------------------------------------------------------ which mesh: one, or one of a ragged batch
 // Mesh m of a batch owns V[vert_off[m] .. vert_off[m+1]), F[face_off[m] .. face_off[m+1]) (indices local to the mesh) and the points /
 // samples [pt_off[m] .. pt_off[m+1]).  The device copy of the offsets (offs) is OFF_ARRAYS arrays of M + 1 int64 back to back; OFF_AUX is
@@ -586,15 +584,6 @@ using namespace ls;
 using namespace ls::mm;
 
 namespace {
-struct Layout {   // carve a workspace in 256-byte aligned pieces
-    size_t off = 0;
-    template <typename T>
-    T* take(char* base, size_t n) {
-        T* p = base ? (T*)(base + off) : nullptr;
-        off = align256(off + n * sizeof(T));
-        return p;
-    }
-};
 struct BinWs {
     long long* offs;   // a batch: the device copy of the offsets
     Params* prm;       // [M]
@@ -603,19 +592,20 @@ struct BinWs {
     int* cell_count;
     long long* start;
     long long* blk;
+    size_t bytes;      // of the whole layout
 };
-// n_offs: OFF_ARRAYS * (M + 1) for a batch, 0 (no bytes) for one mesh
-BinWs bin_layout(char* ws, size_t n_offs, int M, long long nf, long long cells, size_t cell_rec, size_t* bytes) {
-    Layout L;
+// ws null: a sizing pass.  n_offs: OFF_ARRAYS * (M + 1) for a batch, 0 (no bytes) for one mesh
+BinWs bin_layout(void* ws, size_t n_offs, int M, long long nf, long long cells, size_t cell_rec) {
+    Arena a(ws);
     BinWs w;
-    w.offs = L.take<long long>(ws, n_offs);
-    w.prm = L.take<Params>(ws, (size_t)M);
-    w.tri = L.take<double>(ws, (size_t)nf * 9);
-    w.tcell = L.take<char>(ws, (size_t)nf * cell_rec);
-    w.cell_count = L.take<int>(ws, (size_t)cells);
-    w.start = L.take<long long>(ws, (size_t)cells);
-    w.blk = L.take<long long>(ws, (size_t)scan_blocks(cells));
-    if (bytes) *bytes = L.off;
+    w.offs = a.take<long long>(n_offs);
+    w.prm = a.take<Params>((size_t)M);
+    w.tri = a.take<double>((size_t)nf * 9);
+    w.tcell = a.take<char>((size_t)nf * cell_rec);
+    w.cell_count = a.take<int>((size_t)cells);
+    w.start = a.take<long long>((size_t)cells);
+    w.blk = a.take<long long>((size_t)scan_blocks(cells));
+    w.bytes = a.bytes();
     return w;
 }
 struct SampleWs {
@@ -623,15 +613,16 @@ struct SampleWs {
     double* area;
     double* cum;
     double* blk;
+    size_t bytes;
 };
-SampleWs sample_layout(char* ws, size_t n_offs, long long nf, long long nblk, size_t* bytes) {
-    Layout L;
+SampleWs sample_layout(void* ws, size_t n_offs, long long nf, long long nblk) {
+    Arena a(ws);
     SampleWs w;
-    w.offs = L.take<long long>(ws, n_offs);
-    w.area = L.take<double>(ws, (size_t)nf);
-    w.cum = L.take<double>(ws, (size_t)nf);
-    w.blk = L.take<double>(ws, (size_t)nblk);
-    if (bytes) *bytes = L.off;
+    w.offs = a.take<long long>(n_offs);
+    w.area = a.take<double>((size_t)nf);
+    w.cum = a.take<double>((size_t)nf);
+    w.blk = a.take<double>((size_t)nblk);
+    w.bytes = a.bytes();
     return w;
 }
 size_t n_offs(int M) { return (size_t)OFF_ARRAYS * (M + 1); }
@@ -734,9 +725,7 @@ extern "C" {
 
 size_t ls_mesh_contains_workspace_bytes(int nf, int hash_resolution) {
     if (nf < 0 || hash_resolution < 2 || hash_resolution > MAX_HASH_RES) return 0;
-    size_t b;
-    bin_layout(nullptr, 0, 1, nf, (long long)hash_resolution * hash_resolution, sizeof(Cells2), &b);
-    return b;
+    return bin_layout(nullptr, 0, 1, nf, (long long)hash_resolution * hash_resolution, sizeof(Cells2)).bytes;
 }
 
 int ls_mesh_contains_f64(const double* vertices, int nv, const int32_t* faces, int nf, const double* points, long long n, int hash_resolution,
@@ -760,15 +749,13 @@ int ls_mesh_contains_f64(const double* vertices, int nv, const int32_t* faces, i
         set_error("mesh_contains: workspace too small (need ls_mesh_contains_workspace_bytes(%d, %d))", nf, R);
         return LS_ERR_WORKSPACE;
     }
-    const BinWs w = bin_layout((char*)workspace, 0, 1, nf, (long long)R * R, sizeof(Cells2), nullptr);
+    const BinWs w = bin_layout(workspace, 0, 1, nf, (long long)R * R, sizeof(Cells2));
     return contains_launch(OneMesh{vertices, nv, faces, nf, n, 0}, 1, nf, points, n, R, w, inside_out, entries, cap_entries, count_out, st);
 }
 
 size_t ls_mesh_distance_workspace_bytes(int nf) {
     if (nf < 0) return 0;
-    size_t b;
-    bin_layout(nullptr, 0, 1, nf, DIST_CELLS, sizeof(Cells3), &b);
-    return b;
+    return bin_layout(nullptr, 0, 1, nf, DIST_CELLS, sizeof(Cells3)).bytes;
 }
 
 int ls_mesh_distance_f64(const double* vertices, int nv, const int32_t* faces, int nf, const double* points, long long n, double max_dist,
@@ -791,16 +778,14 @@ int ls_mesh_distance_f64(const double* vertices, int nv, const int32_t* faces, i
         set_error("mesh_distance: workspace too small (need ls_mesh_distance_workspace_bytes(%d))", nf);
         return LS_ERR_WORKSPACE;
     }
-    const BinWs w = bin_layout((char*)workspace, 0, 1, nf, DIST_CELLS, sizeof(Cells3), nullptr);
+    const BinWs w = bin_layout(workspace, 0, 1, nf, DIST_CELLS, sizeof(Cells3));
     return distance_launch(OneMesh{vertices, nv, faces, nf, n, 0}, 1, nf, points, n, max_dist, DIST_CELLS, w, dist_out, entries, cap_entries,
                            count_out, st);
 }
 
 size_t ls_mesh_sample_workspace_bytes(int nf) {
     if (nf < 0) return 0;
-    size_t b;
-    sample_layout(nullptr, 0, nf, scan_blocks(nf), &b);
-    return b;
+    return sample_layout(nullptr, 0, nf, scan_blocks(nf)).bytes;
 }
 
 int ls_mesh_sample_f64(const double* vertices, int nv, const int32_t* faces, int nf, long long count, unsigned long long seed,
@@ -814,7 +799,7 @@ int ls_mesh_sample_f64(const double* vertices, int nv, const int32_t* faces, int
         return LS_ERR_WORKSPACE;
     }
     const int nblk = (int)scan_blocks(nf);
-    const SampleWs w = sample_layout((char*)workspace, 0, nf, nblk, nullptr);
+    const SampleWs w = sample_layout(workspace, 0, nf, nblk);
     return sample_launch(OneMesh{vertices, nv, faces, nf, count, sample_key(seed)}, 1, nf, nblk, count, w, points_out, face_out,
                          (hipStream_t)stream);
 }
@@ -822,9 +807,7 @@ int ls_mesh_sample_f64(const double* vertices, int nv, const int32_t* faces, int
 // ---- ragged batches: every mesh's result is bit-identical to the single-mesh op on that mesh alone
 size_t ls_mesh_contains_batch_workspace_bytes(int M, long long nf_total, int hash_resolution) {
     if (M < 0 || nf_total < 0 || nf_total > INT_MAX || hash_resolution < 2 || hash_resolution > MAX_HASH_RES) return 0;
-    size_t b;
-    bin_layout(nullptr, n_offs(M), M, nf_total, (long long)M * hash_resolution * hash_resolution, sizeof(Cells2), &b);
-    return b;
+    return bin_layout(nullptr, n_offs(M), M, nf_total, (long long)M * hash_resolution * hash_resolution, sizeof(Cells2)).bytes;
 }
 
 int ls_mesh_contains_batch_f64(int M, const double* vertices, long long nv_total, const long long* vert_off, const int32_t* faces, long long nf_total,
@@ -853,7 +836,7 @@ int ls_mesh_contains_batch_f64(int M, const double* vertices, long long nv_total
         set_error("%s: workspace too small (need ls_mesh_contains_batch_workspace_bytes(%d, %lld, %d))", op, M, nf_total, R);
         return LS_ERR_WORKSPACE;
     }
-    const BinWs w = bin_layout((char*)workspace, n_offs(M), M, nf_total, (long long)M * R * R, sizeof(Cells2), nullptr);
+    const BinWs w = bin_layout(workspace, n_offs(M), M, nf_total, (long long)M * R * R, sizeof(Cells2));
     rc = upload_offsets(w.offs, pack_offsets(M, vert_off, face_off, pt_off, nullptr, nullptr), st);
     if (rc != LS_OK) return rc;
     return contains_launch(RaggedMeshes{vertices, faces, w.offs, M, nf_total, n_total, nullptr}, M, nf_total, points, n_total, R, w, inside_out,
@@ -862,9 +845,7 @@ int ls_mesh_contains_batch_f64(int M, const double* vertices, long long nv_total
 
 size_t ls_mesh_distance_batch_workspace_bytes(int M, long long nf_total) {
     if (M < 0 || nf_total < 0 || nf_total > INT_MAX) return 0;
-    size_t b;
-    bin_layout(nullptr, n_offs(M), M, nf_total, 8 * nf_total + M, sizeof(Cells3), &b);
-    return b;
+    return bin_layout(nullptr, n_offs(M), M, nf_total, 8 * nf_total + M, sizeof(Cells3)).bytes;
 }
 
 int ls_mesh_distance_batch_f64(int M, const double* vertices, long long nv_total, const long long* vert_off, const int32_t* faces, long long nf_total,
@@ -898,7 +879,7 @@ int ls_mesh_distance_batch_f64(int M, const double* vertices, long long nv_total
         cell_off[m + 1] = cell_off[m] + axis[m] * axis[m] * axis[m];
     }
     const long long cells = cell_off[M];   // <= 8 nf_total + M
-    const BinWs w = bin_layout((char*)workspace, n_offs(M), M, nf_total, cells, sizeof(Cells3), nullptr);
+    const BinWs w = bin_layout(workspace, n_offs(M), M, nf_total, cells, sizeof(Cells3));
     rc = upload_offsets(w.offs, pack_offsets(M, vert_off, face_off, pt_off, cell_off.data(), axis.data()), st);
     if (rc != LS_OK) return rc;
     return distance_launch(RaggedMeshes{vertices, faces, w.offs, M, nf_total, n_total, nullptr}, M, nf_total, points, n_total, max_dist, cells, w,
@@ -907,9 +888,7 @@ int ls_mesh_distance_batch_f64(int M, const double* vertices, long long nv_total
 
 size_t ls_mesh_sample_batch_workspace_bytes(int M, long long nf_total) {
     if (M < 0 || nf_total < 0 || nf_total > INT_MAX) return 0;
-    size_t b;
-    sample_layout(nullptr, n_offs(M), nf_total, scan_blocks(nf_total) + M, &b);   // at least the sum over meshes of scan_blocks(nf_m)
-    return b;
+    return sample_layout(nullptr, n_offs(M), nf_total, scan_blocks(nf_total) + M).bytes;   // at least the sum over meshes of scan_blocks(nf_m)
 }
 
 int ls_mesh_sample_batch_f64(int M, const double* vertices, long long nv_total, const long long* vert_off, const int32_t* faces, long long nf_total,
@@ -935,7 +914,7 @@ int ls_mesh_sample_batch_f64(int M, const double* vertices, long long nv_total, 
         return LS_ERR_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    const SampleWs w = sample_layout((char*)workspace, n_offs(M), nf_total, scan_blocks(nf_total) + M, nullptr);
+    const SampleWs w = sample_layout(workspace, n_offs(M), nf_total, scan_blocks(nf_total) + M);
     rc = upload_offsets(w.offs, pack_offsets(M, vert_off, face_off, count_off, blk_off.data(), nullptr), st);
     if (rc != LS_OK) return rc;
     return sample_launch(RaggedMeshes{vertices, faces, w.offs, M, nf_total, count_total, seeds}, M, nf_total, (int)blk_off[M], count_total, w,

@@ -22,28 +22,34 @@ namespace ls {
 
 struct MiseLayout {
     int res0, depth, R, G;
-    size_t o_val, o_known, o_exists, o_sub[8], o_pos[8], o_neg[8], o_blk, total;
+    size_t o_val, o_known, o_exists, o_sub[8], o_pos[8], o_neg[8], o_blk, total;   // one octree: offsets from its first byte
+    size_t o_batch_blk, batch_total;   // B octrees back to back, `total` bytes each, then the block sums of the batch
     long long npts;
     int nblk;
 };
 constexpr int MISE_PER_BLOCK = 4096;   // lattice points per compaction workgroup (256 threads x 16)
 
-static MiseLayout mise_layout(int res0, int depth) {
+// The one statement of a MISE state: offsets (an arena over a null base), since every octree of a batch has the same ones.  The block sums of
+// a batch, [B][nblk] + the total, follow the B octrees (every octree's own o_blk serves the single ops on that slice).
+static MiseLayout mise_layout(int res0, int depth, int B = 1) {
     MiseLayout L{};
     L.res0 = res0; L.depth = depth; L.R = res0 << depth; L.G = L.R + 1;
     L.npts = (long long)L.G * L.G * L.G;
-    size_t off = 0;
-    auto take = [&](size_t b) { size_t o = off; off = (off + b + 255) & ~(size_t)255; return o; };
-    L.o_val = take((size_t)L.npts * 4);
-    L.o_known = take((size_t)L.npts);
-    L.o_exists = take((size_t)L.npts);
+    L.nblk = (int)((L.npts + MISE_PER_BLOCK - 1) / MISE_PER_BLOCK);
+    Arena a(nullptr);
+    L.o_val = a.take_bytes((size_t)L.npts * 4);
+    L.o_known = a.take_bytes((size_t)L.npts);
+    L.o_exists = a.take_bytes((size_t)L.npts);
     for (int l = 0; l < depth; ++l) {
         const size_t n = (size_t)(res0 << l) * (res0 << l) * (res0 << l);
-        L.o_sub[l] = take(n); L.o_pos[l] = take(n); L.o_neg[l] = take(n);
+        L.o_sub[l] = a.take_bytes(n); L.o_pos[l] = a.take_bytes(n); L.o_neg[l] = a.take_bytes(n);
     }
-    L.nblk = (int)((L.npts + MISE_PER_BLOCK - 1) / MISE_PER_BLOCK);
-    L.o_blk = take((size_t)(L.nblk + 1) * 4);
-    L.total = off;
+    L.o_blk = a.take_bytes((size_t)(L.nblk + 1) * 4);
+    L.total = a.bytes();
+    Arena batch(nullptr);
+    batch.take_bytes((size_t)B * L.total);
+    L.o_batch_blk = batch.take_bytes(((size_t)B * L.nblk + 1) * 4);
+    L.batch_total = batch.bytes();
     return L;
 }
 
@@ -252,8 +258,6 @@ __global__ void mise_dense_axis_kernel(Grids g, float* __restrict__ out, int G, 
 
 // ---- launch sequences, written once for both locators
 static bool mise_config_ok(int res0, int depth) { return res0 >= 1 && depth >= 0 && depth <= 7 && ((long long)res0 << depth) <= 1024; }
-// the block sums of a batch, [B][nblk] + the total, follow the B octrees (every octree's own o_blk serves the single ops on that slice)
-static size_t mise_batch_bytes(const MiseLayout& L, int B) { return (size_t)B * L.total + ((((size_t)B * L.nblk + 1) * 4 + 255) & ~(size_t)255); }
 
 template <class Grids>
 static int mise_init_launch(Grids g, const MiseLayout& L, void* state, size_t bytes, hipStream_t st) {
@@ -317,9 +321,9 @@ long long ls_mise_lattice_points(int res0, int depth) {
 }
 size_t ls_mise_batch_state_bytes(int B, int res0, int depth) {
     if (!mise_config_ok(res0, depth) || B < 1 || B > MISE_MAX_BATCH) return 0;
-    const MiseLayout L = mise_layout(res0, depth);
+    const MiseLayout L = mise_layout(res0, depth, B);
     if ((long long)B * L.npts >= (1ll << 31)) return 0;
-    return mise_batch_bytes(L, B);
+    return L.batch_total;
 }
 
 #define MISE_REQUIRE_CONFIG(res0, depth) LS_REQUIRE(mise_config_ok(res0, depth), "mise: resolution_0=%d depth=%d unsupported", res0, depth)
@@ -340,11 +344,10 @@ int ls_mise_init(void* state, size_t state_bytes, int res0, int depth, void* str
 int ls_mise_init_batch(void* state, size_t state_bytes, int B, int res0, int depth, void* stream) {
     LS_REQUIRE(state != nullptr, "mise: null state");
     MISE_REQUIRE_CONFIG(res0, depth);
-    const MiseLayout L = mise_layout(res0, depth);
+    const MiseLayout L = mise_layout(res0, depth, B);
     MISE_REQUIRE_BATCH(B, L);
-    const size_t need = mise_batch_bytes(L, B);
-    if (state_bytes < need) { set_error("mise: batch state %zu < required %zu bytes", state_bytes, need); return LS_ERR_WORKSPACE; }
-    return mise_init_launch(GridBatch{B, L.total}, L, state, need, (hipStream_t)stream);
+    if (state_bytes < L.batch_total) { set_error("mise: batch state %zu < required %zu bytes", state_bytes, L.batch_total); return LS_ERR_WORKSPACE; }
+    return mise_init_launch(GridBatch{B, L.total}, L, state, L.batch_total, (hipStream_t)stream);
 }
 
 // Unknown lattice points in ascending lattice order: idx_out[cap] (linear index (x*G + y)*G + z), pts_out[cap,3] (the
@@ -363,9 +366,9 @@ int ls_mise_query_batch(void* state, int B, int res0, int depth, float box_size,
                         long long cap, long long* off_out, void* stream) {
     LS_REQUIRE(state && idx_out && inst_out && pts_out && off_out && cap >= 0, "mise_query_batch: null argument");
     MISE_REQUIRE_CONFIG(res0, depth);
-    const MiseLayout L = mise_layout(res0, depth);
+    const MiseLayout L = mise_layout(res0, depth, B);
     MISE_REQUIRE_BATCH(B, L);
-    return mise_query_launch(GridBatch{B, L.total}, B, L, state, (int*)((char*)state + (size_t)B * L.total), box_size, idx_out, inst_out, pts_out,
+    return mise_query_launch(GridBatch{B, L.total}, B, L, state, (int*)((char*)state + L.o_batch_blk), box_size, idx_out, inst_out, pts_out,
                              cap, nullptr, off_out, (hipStream_t)stream);
 }
 

@@ -95,7 +95,7 @@ struct ProfScope {
 };
 #define PROF(kind, layer, st) ProfScope _ps_##__LINE__(m, kind, layer, st)
 
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+static inline int pad4(int cols) { return (cols + 3) / 4 * 4; }   // a matrix's columns as whole float4s
 
 // ------------------------------------------------------------------------------------------------ plan
 struct EncPlan {
@@ -164,34 +164,33 @@ static int make_plan(const ls_model_desc& d, int B, int N, EncPlan& p) {
     LS_REQUIRE(d.num_knn == 16, "encoder: num_knn=%d unsupported (16)", d.num_knn);
     LS_REQUIRE(p.Ns[p.L - 1] >= 1, "encoder: bad schedule");
     p.NP = cur;
-    p.Cdp = (int)align_up((size_t)d.c_dim + 1, 4);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+    p.Cdp = pad4(d.c_dim + 1);
+    Arena a(nullptr);   // the plan stores offsets: encode_enqueue adds the workspace
     for (int l = 0; l <= p.nlevels; ++l) {
-        p.o_pts[l] = take((size_t)B * p.levelN[l] * 3 * 4);
-        p.o_fps[l] = take((size_t)B * p.levelN[l] * 4);
+        p.o_pts[l] = a.take_bytes((size_t)B * p.levelN[l] * 3 * 4);
+        p.o_fps[l] = a.take_bytes((size_t)B * p.levelN[l] * 4);
     }
-    p.o_centroid = take((size_t)B * 3 * 4);
-    p.o_scale0 = take((size_t)B * 4);
-    p.o_pro = take(prologue_scratch_floats(B) * 4);
-    p.o_knn = take((size_t)B * maxKnn * 4);
-    p.o_knn2 = take((size_t)B * maxKnn * 4);
-    p.o_knns = take(maxKs + 256);
-    p.o_fA = take((size_t)B * maxF * 4);
-    p.o_fB = take((size_t)B * maxF * 4);
-    p.o_msg = take((size_t)B * maxF * 4);
-    p.o_T = take((size_t)B * maxT * 4);
-    p.o_TG = take((size_t)B * maxTG * 4);
-    p.o_g = take((size_t)B * 3 * maxC * 4);
-    p.o_G = take((size_t)B * 3 * 4 * maxC * 4);
-    p.o_Tc = take((size_t)B * p.NP * 3 * p.Cdp * 4);
+    p.o_centroid = a.take_bytes((size_t)B * 3 * 4);
+    p.o_scale0 = a.take_bytes((size_t)B * 4);
+    p.o_pro = a.take_bytes(prologue_scratch_floats(B) * 4);
+    p.o_knn = a.take_bytes((size_t)B * maxKnn * 4);
+    p.o_knn2 = a.take_bytes((size_t)B * maxKnn * 4);
+    p.o_knns = a.take_bytes(maxKs + 256);
+    p.o_fA = a.take_bytes((size_t)B * maxF * 4);
+    p.o_fB = a.take_bytes((size_t)B * maxF * 4);
+    p.o_msg = a.take_bytes((size_t)B * maxF * 4);
+    p.o_T = a.take_bytes((size_t)B * maxT * 4);
+    p.o_TG = a.take_bytes((size_t)B * maxTG * 4);
+    p.o_g = a.take_bytes((size_t)B * 3 * maxC * 4);
+    p.o_G = a.take_bytes((size_t)B * 3 * 4 * maxC * 4);
+    p.o_Tc = a.take_bytes((size_t)B * p.NP * 3 * p.Cdp * 4);
     maxGws = std::max(maxGws, gemm_scratch_floats(B * p.NP * 3, p.Cdp, p.Co[p.L - 1]));
-    p.o_gws = take(maxGws * 4 + 256);
+    p.o_gws = a.take_bytes(maxGws * 4 + 256);
     // row maxima of the messages / layer outputs, chained into the GEMMs that read them (gemm.hip, GemmAux)
-    p.o_rm_msg = take((size_t)B * maxRm * 3 * 4);      // maxRm = max over the layers of Nd x parts (above)
-    p.o_rm_out[0] = take((size_t)B * maxRm * 3 * 4);
-    p.o_rm_out[1] = take((size_t)B * maxRm * 3 * 4);
-    p.o_cs = take((size_t)B * maxCs * 4);
+    p.o_rm_msg = a.take_bytes((size_t)B * maxRm * 3 * 4);      // maxRm = max over the layers of Nd x parts (above)
+    p.o_rm_out[0] = a.take_bytes((size_t)B * maxRm * 3 * 4);
+    p.o_rm_out[1] = a.take_bytes((size_t)B * maxRm * 3 * 4);
+    p.o_cs = a.take_bytes((size_t)B * maxCs * 4);
     // FPS scratch of the encoder's own down-sampling chain (fps.hip: exact bucket pruning for 8 193 .. 65 536 source points; 0 bytes below that).  The
     // levels run one after the other on one stream and share it.  (the chain passed no workspace, so an encode with N > 8192 failed in the
     // MIDDLE of the enqueue, after the side stream had forked.)
@@ -200,11 +199,11 @@ static int make_plan(const ls_model_desc& d, int B, int N, EncPlan& p) {
         LS_REQUIRE(p.levelN[l] <= 65536, "encoder: %d points at down-sampling level %d (FPS handles at most 65536)", p.levelN[l], l);
         p.fpsws_bytes = std::max(p.fpsws_bytes, fps_scratch_bytes_per_cloud(p.levelN[l]) * (size_t)B);
     }
-    p.o_fpsws = take(p.fpsws_bytes);
+    p.o_fpsws = a.take_bytes(p.fpsws_bytes);
     // staging of the captured-graph path: the graph reads x from / writes the codes to FIXED addresses inside the workspace
-    p.o_xin = take((size_t)B * 3 * N * 4);
-    p.o_out = take((size_t)B * (4 * (size_t)d.c_dim + 4) * 4);
-    p.total = off;
+    p.o_xin = a.take_bytes((size_t)B * 3 * N * 4);
+    p.o_out = a.take_bytes((size_t)B * (4 * (size_t)d.c_dim + 4) * 4);
+    p.total = a.bytes();
     return LS_OK;
 }
 
@@ -407,7 +406,7 @@ static int global_conv(ls_model* m, int i, const float* msg, int B, int Nd, floa
 static int encoder_tail(ls_model* m, const float* cur, int B, int NP, float* Tc, float* gws, const float* centroid, const float* scale0,
                         float* z_so3, float* z_inv, float* s_out, float* t_out, hipStream_t st, const float* rm_cur = nullptr, int rm_parts = 0) {
     const ls_model_desc& d = m->d;
-    const int Cl = d.feat_dim[d.num_layers - 1], Cdp = (int)align_up((size_t)d.c_dim + 1, 4);
+    const int Cl = d.feat_dim[d.num_layers - 1], Cdp = pad4(d.c_dim + 1);
     const float* W = m->blob;
     int rc;
     { PROF(LS_K_GEMM_TAIL, 0, st);
@@ -482,7 +481,7 @@ int ls_model_create(const ls_model_desc* desc, const float* blob_host, ls_model_
         for (int i = 1; i < d.num_layers; ++i) specs.push_back({m->blob + d.off_edge[i], (size_t)layer_ncols(d, i), layer_cin(d, i)});
         for (int i = d.res_global_start_layer; i < d.num_layers; ++i)
             if (i >= 0) specs.push_back({m->blob + d.off_glob[i], (size_t)4 * d.feat_dim[i], d.feat_dim[i]});
-        if (d.num_layers >= 1) specs.push_back({m->blob + d.off_convc, align_up((size_t)d.c_dim + 1, 4), d.feat_dim[d.num_layers - 1]});
+        if (d.num_layers >= 1) specs.push_back({m->blob + d.off_convc, (size_t)pad4(d.c_dim + 1), d.feat_dim[d.num_layers - 1]});
         if (d.dec_num_linear >= 3) {
             int kin = d.dec_width;
             for (int l = 1; l < d.dec_num_linear - 1; ++l) {
@@ -565,7 +564,7 @@ int ls_model_get_option(const ls_model_t* m, int option, int* value) {
 }
 
 size_t ls_encoder_workspace_bytes(const ls_model_t* m, int B, int N) {
-    if (!m) return 0;
+    if (!m || B <= 0) return 0;   // (B = 0 would reach the split-K choice with an empty GEMM: a division by zero)
     EncPlan p;
     if (make_plan(m->d, B, N, p) != LS_OK) return 0;
     return p.total;
@@ -769,9 +768,12 @@ static int check_layer(const ls_model_t* m, int layer, bool want_attn, const cha
     LS_REQUIRE((layer >= m->d.atten_start_layer) == want_attn, "%s: layer %d is %s layer", who, layer, want_attn ? "a mean-pool" : "an attention");
     return LS_OK;
 }
+// the workspace of an exported edge-conv layer is one piece: its table area (+ 4 floats the size has always counted)
 size_t ls_vn_edgeconv_workspace_bytes(const ls_model_t* m, int layer, int B, int Ns, int Nd, int has_dst_rows) {
     if (!m || layer < 0 || layer >= m->d.num_layers || B <= 0) return 0;
-    return align_up(edge_table_floats(m->d, layer, B, Ns, Nd, has_dst_rows != 0) * sizeof(float) + 16, 256);
+    Arena a(nullptr);
+    a.take<float>(edge_table_floats(m->d, layer, B, Ns, Nd, has_dst_rows != 0) + 4);
+    return a.bytes();
 }
 static int edgeconv_export(ls_model_t* m, int layer, const float* src_f, const int32_t* knn, const int32_t* dst_rows, int B, int Ns, int Nd,
                            float* out, void* workspace, size_t workspace_bytes, hipStream_t st, const char* who) {
@@ -809,58 +811,62 @@ int ls_vn_edgeconv_attn_f32(ls_model_t* m, int layer, const float* src_f, const 
     return edgeconv_export(m, layer, src_f, knn, dst_rows, B, Ns, Nd, out, workspace, workspace_bytes, (hipStream_t)stream, "vn_edgeconv_attn");
 }
 
-struct LnaPlan { size_t o_g, o_G, o_TG, o_gws, o_rm, total; };
-static LnaPlan lna_plan(const ls_model_desc& d, int layer, int B, int N) {
+struct LnaPlan { float *g, *G, *TG, *gws, *rm; size_t total; };
+static LnaPlan lna_plan(const ls_model_desc& d, void* workspace, int layer, int B, int N) {   // a null workspace: a sizing pass
     const size_t Co = (size_t)d.feat_dim[layer];
     LnaPlan q{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    q.o_g = take((size_t)B * 3 * Co * 4);
-    q.o_G = take((size_t)B * 3 * 4 * Co * 4);
-    q.o_TG = take((size_t)B * N * 3 * 2 * Co * 4);
-    q.o_gws = take(global_conv_gws_floats(d, layer, B, N) * 4 + 256);
-    q.o_rm = take((size_t)B * N * 3 * 4);
-    q.total = off;
+    Arena a(workspace);
+    q.g = a.take<float>((size_t)B * 3 * Co);
+    q.G = a.take<float>((size_t)B * 3 * 4 * Co);
+    q.TG = a.take<float>((size_t)B * N * 3 * 2 * Co);
+    q.gws = a.take<float>(global_conv_gws_floats(d, layer, B, N) + 64);   // split-K slabs and their 256-byte tail
+    q.rm = a.take<float>((size_t)B * N * 3);
+    q.total = a.bytes();
     return q;
 }
 size_t ls_vn_lna_workspace_bytes(const ls_model_t* m, int layer, int B, int N) {
     if (!m || layer < m->d.res_global_start_layer || layer >= m->d.num_layers || B <= 0 || N <= 0) return 0;
-    return lna_plan(m->d, layer, B, N).total;
+    return lna_plan(m->d, nullptr, layer, B, N).total;
 }
 int ls_vn_lna_f32(ls_model_t* m, int layer, const float* f, int B, int N, float* out, void* workspace, size_t workspace_bytes, void* stream) {
     LS_REQUIRE(m && f && out && workspace, "vn_lna: null argument");
     LS_REQUIRE(layer >= m->d.res_global_start_layer && layer < m->d.num_layers, "vn_lna: layer %d has no residual global conv", layer);
     LS_REQUIRE(B > 0 && N > 0, "vn_lna: empty problem");
-    const LnaPlan q = lna_plan(m->d, layer, B, N);
+    const LnaPlan q = lna_plan(m->d, workspace, layer, B, N);
     if (workspace_bytes < q.total) { set_error("vn_lna: workspace %zu < required %zu", workspace_bytes, q.total); return LS_ERR_WORKSPACE; }
-    char* ws = (char*)workspace;
     const float* rm = nullptr;
     if (m->glob_fuse == 2) {   // the message's exact row maxima, as the encoder's attention kernels hand them over (GemmAux::a_rowmax)
         const int Co = m->d.feat_dim[layer];
-        const int rc = gemm_rowmax_launch(f, B * N * 3, Co, Co, (float*)(ws + q.o_rm), (hipStream_t)stream);
+        const int rc = gemm_rowmax_launch(f, B * N * 3, Co, Co, q.rm, (hipStream_t)stream);
         if (rc != LS_OK) return rc;
-        rm = (const float*)(ws + q.o_rm);
+        rm = q.rm;
     }
-    return global_conv(m, layer, f, B, N, (float*)(ws + q.o_g), (float*)(ws + q.o_G), (float*)(ws + q.o_TG), (float*)(ws + q.o_gws), out,
-                       (hipStream_t)stream, rm);
+    return global_conv(m, layer, f, B, N, q.g, q.G, q.TG, q.gws, out, (hipStream_t)stream, rm);
 }
 
+// the workspace of the exported tail: conv_c's output, then the split-K slabs of that GEMM and their 256-byte tail.  A null workspace: a
+// sizing pass.  The size has always ended with that tail, unpadded.
+struct TailWs { float *Tc, *gws; size_t bytes; };
+static TailWs tail_ws_layout(const ls_model_desc& d, void* workspace, int B, int NP) {
+    const int Cl = d.feat_dim[d.num_layers - 1], Cdp = pad4(d.c_dim + 1);
+    Arena a(workspace);
+    TailWs w;
+    w.Tc = a.take<float>((size_t)B * NP * 3 * Cdp);
+    w.gws = a.take<float>(gemm_scratch_floats(B * NP * 3, Cdp, Cl) + 64);
+    w.bytes = a.bytes_unpadded();
+    return w;
+}
 size_t ls_encoder_tail_workspace_bytes(const ls_model_t* m, int B, int NP) {
-    if (!m || B <= 0 || NP <= 0) return 0;
-    const int Cl = m->d.feat_dim[m->d.num_layers - 1], Cdp = (int)align_up((size_t)m->d.c_dim + 1, 4);
-    return align_up((size_t)B * NP * 3 * Cdp * 4, 256) + gemm_scratch_floats(B * NP * 3, Cdp, Cl) * 4 + 256;
+    return (!m || B <= 0 || NP <= 0) ? 0 : tail_ws_layout(m->d, nullptr, B, NP).bytes;
 }
 int ls_encoder_tail_f32(ls_model_t* m, const float* f, const float* centroid, const float* scale0, int B, int NP, float* z_so3, float* z_inv,
                         float* s, float* t, void* workspace, size_t workspace_bytes, void* stream) {
     LS_REQUIRE(m && f && z_so3 && z_inv && s && t && workspace, "encoder_tail: null argument");
     LS_REQUIRE(B > 0 && NP > 0, "encoder_tail: empty problem");
     LS_REQUIRE((centroid == nullptr) == (scale0 == nullptr), "encoder_tail: centroid and scale0 go together");
-    const size_t need = ls_encoder_tail_workspace_bytes(m, B, NP);
-    if (workspace_bytes < need) { set_error("encoder_tail: workspace %zu < required %zu", workspace_bytes, need); return LS_ERR_WORKSPACE; }
-    const int Cdp = (int)align_up((size_t)m->d.c_dim + 1, 4);
-    float* Tc = (float*)workspace;
-    float* gws = (float*)((char*)workspace + align_up((size_t)B * NP * 3 * Cdp * 4, 256));
-    return encoder_tail(m, f, B, NP, Tc, gws, centroid, scale0, z_so3, z_inv, s, t, (hipStream_t)stream);
+    const TailWs w = tail_ws_layout(m->d, workspace, B, NP);
+    if (workspace_bytes < w.bytes) { set_error("encoder_tail: workspace %zu < required %zu", workspace_bytes, w.bytes); return LS_ERR_WORKSPACE; }
+    return encoder_tail(m, f, B, NP, w.Tc, w.gws, centroid, scale0, z_so3, z_inv, s, t, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------ SDF decode
@@ -870,7 +876,7 @@ static int dec_in_width(const ls_model_desc& d) { return dec_xyz(d) ? d.c_dim + 
 static int dec_out(const ls_model_desc& d, int l) {  // padded output width of linear layer l
     const int nl = d.dec_num_linear;
     if (l == nl - 1) return 1;
-    if (d.dec_latent_in >= 0 && l + 1 == d.dec_latent_in) return (int)align_up((size_t)(d.dec_width - dec_in_width(d)), 4);
+    if (d.dec_latent_in >= 0 && l + 1 == d.dec_latent_in) return pad4(d.dec_width - dec_in_width(d));
     return d.dec_width;
 }
 // the per-instance table of the code-fed layer l that multiplies the query (sdf_prep_launch's so3_t argument)
@@ -901,41 +907,40 @@ struct SdfBuffers {
     size_t bytes;       // of the whole layout
 };
 // The one statement of the decoder's workspace layout: B instances, `rows` query rows in all (B * M, or R of the ragged form).
-// A null `workspace` gives the byte total and pointers nobody reads.  train: every layer's activations are kept for the backward pass, plus its scratch.
+// A null `workspace` is a sizing pass: the byte total and null pointers.  train: every layer's activations are kept for the backward pass, plus its scratch.
 static SdfBuffers sdf_buffers(const ls_model_desc& d, void* workspace, int B, long long rows, bool train, bool allow_splitk = true) {
     SdfBuffers sb{};
     const int w = d.dec_width, nl = d.dec_num_linear;
     const size_t R = (size_t)rows;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { float* p = (float*)((uintptr_t)workspace + off); off = align_up(off + bytes, 256); return p; };
-    sb.A0 = take((size_t)B * w * 16);
-    sb.A4 = take((size_t)B * w * 16);
-    sb.b0 = take((size_t)B * w * 4);
-    sb.b4 = take((size_t)B * w * 4);
+    Arena a(workspace);
+    sb.A0 = a.take<float>((size_t)B * w * 4);
+    sb.A4 = a.take<float>((size_t)B * w * 4);
+    sb.b0 = a.take<float>((size_t)B * w);
+    sb.b4 = a.take<float>((size_t)B * w);
     if (!train) {
-        float* hA = take(R * w * 4);
-        float* hB = take(R * w * 4);
+        float* hA = a.take<float>(R * w);
+        float* hB = a.take<float>(R * w);
         for (int l = 0; l < nl - 1; ++l) sb.h[l] = (l & 1) ? hB : hA;
         // inference never splits K: a query's SDF must not depend on how many other queries share the call (MISE evaluates
         // the same lattice point in calls of very different sizes; split-K changes the fp32 summation order)
         sb.gws = nullptr;
     } else {
-        for (int l = 0; l < nl - 1; ++l) sb.h[l] = take(R * w * 4);
-        sb.dzA = take(R * w * 4);
-        sb.dzB = take(R * w * 4);
-        sb.dA0 = take((size_t)B * w * 16);
-        sb.dA4 = take((size_t)B * w * 16);
-        sb.db0 = take((size_t)B * w * 4);
-        sb.db4 = take((size_t)B * w * 4);
-        sb.dQ = take(R * 16);
+        for (int l = 0; l < nl - 1; ++l) sb.h[l] = a.take<float>(R * w);
+        sb.dzA = a.take<float>(R * w);
+        sb.dzB = a.take<float>(R * w);
+        sb.dA0 = a.take<float>((size_t)B * w * 4);
+        sb.dA4 = a.take<float>((size_t)B * w * 4);
+        sb.db0 = a.take<float>((size_t)B * w);
+        sb.db4 = a.take<float>((size_t)B * w);
+        sb.dQ = a.take<float>(R * 4);
         // split-K slabs (small M only) and their 256-byte tail; the tail is reserved even where no GEMM splits (the size always counted it)
         const size_t scratch = sdf_gemm_scratch(d, rows);
-        float* gws = take(scratch * 4 + 256);
+        float* gws = a.take<float>(scratch + 64);
         sb.gws = scratch && allow_splitk ? gws : nullptr;
     }
-    sb.rm[0] = take(R * sdf_rm_parts(w) * 4);
-    sb.rm[1] = take(R * sdf_rm_parts(w) * 4);
-    sb.bytes = off;
+    sb.rm[0] = a.take<float>(R * sdf_rm_parts(w));
+    sb.rm[1] = a.take<float>(R * sdf_rm_parts(w));
+    sb.bytes = a.bytes();
     return sb;
 }
 static size_t sdf_bytes(const ls_model_t* m, int B, long long rows, bool train) {

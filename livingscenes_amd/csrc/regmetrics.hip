@@ -41,7 +41,6 @@ static_assert(sizeof(Pose) == 512, "Pose");
 // the device copy of the offsets: OFF_ARRAYS arrays of P + 1 int64 back to back
 enum { OFF_X = 0, OFF_Y, OFF_EPE, OFF_NN, OFF_ARRAYS };
 
-__host__ __device__ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 __host__ __device__ inline long long cdivll(long long a, long long b) { return (a + b - 1) / b; }
 
 __device__ __forceinline__ void apply(const double* __restrict__ g, double x, double y, double z, double (&o)[3]) {
@@ -231,20 +230,16 @@ struct Ws {
     Pose* poses;
     double* epe_part;
     double* nn_part;
+    size_t bytes;   // of the whole layout
 };
-Ws layout(char* ws, int P, long long n_total, long long m_total, int s, size_t* bytes) {
-    size_t off = 0;
-    auto take = [&](size_t nbytes) {
-        char* p = ws ? ws + off : nullptr;
-        off = align256(off + nbytes);
-        return p;
-    };
+Ws layout(void* ws, int P, long long n_total, long long m_total, int s) {   // ws null: a sizing pass
+    Arena a(ws);
     Ws w;
-    w.offs = (long long*)take((size_t)OFF_ARRAYS * (P + 1) * sizeof(long long));
-    w.poses = (Pose*)take((size_t)P * sizeof(Pose));
-    w.epe_part = (double*)take((size_t)epe_chunks_max(P, n_total, m_total) * sizeof(double));
-    w.nn_part = (double*)take((size_t)nn_chunks_max(P, n_total, m_total, s) * sizeof(double));
-    if (bytes) *bytes = off;
+    w.offs = a.take<long long>((size_t)OFF_ARRAYS * (P + 1));
+    w.poses = a.take<Pose>((size_t)P);
+    w.epe_part = a.take<double>((size_t)epe_chunks_max(P, n_total, m_total));
+    w.nn_part = a.take<double>((size_t)nn_chunks_max(P, n_total, m_total, s));
+    w.bytes = a.bytes();
     return w;
 }
 }  // namespace
@@ -253,9 +248,7 @@ extern "C" {
 
 size_t ls_reg_metrics_batch_workspace_bytes(int P, long long n_total, long long m_total, int chamfer_stride) {
     if (P < 1 || n_total < 0 || m_total < 0 || chamfer_stride < 1) return 0;
-    size_t b;
-    layout(nullptr, P, n_total, m_total, chamfer_stride, &b);
-    return b;
+    return layout(nullptr, P, n_total, m_total, chamfer_stride).bytes;
 }
 
 int ls_reg_metrics_batch(int P, const float* X, long long n_total, const long long* x_off, const float* Y, long long m_total, const long long* y_off,
@@ -285,7 +278,7 @@ int ls_reg_metrics_batch(int P, const float* X, long long n_total, const long lo
         return LS_ERR_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    const Ws w = layout((char*)workspace, P, n_total, m_total, chamfer_stride, nullptr);
+    const Ws w = layout(workspace, P, n_total, m_total, chamfer_stride);
     rc = upload_offsets(w.offs, pack_offsets(P, {x_off, y_off, epe_off.data(), nn_off.data()}), st);
     if (rc != LS_OK) return rc;
     const int pb = cdiv(P, 64);

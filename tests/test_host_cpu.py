@@ -36,6 +36,51 @@ def test_abi_exports_every_declared_symbol(lib):
     assert lib.ls_version() >= 100
 
 
+def test_abi_table_types_match_the_header_prototypes():
+    """_lib.SIGNATURES is transcribed by hand from include/livingscenes_hip.h; the test above compares names only.  A `long long` or a `size_t`
+    typed as `int` in the table would load, pass every call that stays below 2^31 and corrupt the arguments after it silently -- so every
+    prototype's return and argument types are parsed from the header and compared with the table: pointers (arrays, handles, strings as
+    arguments) are c_void_p or a typed ctypes pointer, scalars the ctypes type of the same C type."""
+    from livingscenes_amd import _lib
+    hdr = open(os.path.join(REPO, "include", "livingscenes_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", "", hdr)
+    protos = re.findall(r"([A-Za-z_][\w \*]*?)\b(ls_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr)
+    scalars = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "unsigned int": ctypes.c_uint, "float": ctypes.c_float, "double": ctypes.c_double,
+               "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t, "unsigned long long": ctypes.c_ulonglong}
+
+    def of_header(decl, is_return=False):
+        """the C declaration of one parameter (its name included) or of the return type -> a ctypes type code, 'P' for every pointer"""
+        t = " ".join(re.sub(r"\bconst\b", " ", decl).replace("*", " * ").split())
+        if t.endswith("]"):
+            return "P"
+        if not is_return:
+            t = re.sub(r"\s*\b[A-Za-z_]\w*$", "", t)   # every parameter of the header is named: drop the name
+        if "*" in t:
+            return "z" if is_return and t == "char *" else "P"
+        return None if t == "void" else scalars[t]._type_
+
+    def of_table(c):
+        if c is None:
+            return None
+        if isinstance(c, type) and issubclass(c, ctypes._Pointer):
+            return "P"
+        return c._type_
+
+    assert len(protos) == len(_lib.SIGNATURES) and {p[1] for p in protos} == set(_lib.SIGNATURES)
+    wrong = []
+    for ret, name, args in protos:
+        args = args.strip()
+        want_args = [] if args in ("", "void") else [of_header(a) for a in args.split(",")]
+        res, argtypes = _lib.SIGNATURES[name]
+        if (of_header(ret, True), want_args) != (of_table(res), [of_table(a) for a in argtypes]):
+            wrong.append((name, of_header(ret, True), want_args, of_table(res), [of_table(a) for a in argtypes]))
+    assert not wrong, wrong
+    # the parser tells the widths apart (the test would be empty otherwise)
+    assert of_header("long long n") != of_header("int n") and of_header("size_t workspace_bytes") != of_header("int n")
+    assert of_header("const long long* off") == "P" and of_header("ls_model_t** out") == "P" and of_header("unsigned flags") == "I"
+
+
 def test_abi_fails_loudly_without_device(lib):
     if torch.cuda.is_available():
         pytest.skip("GPU present")
