@@ -1,7 +1,7 @@
 // gemm.hip -- out[M,N] = act(A[M,K] * W[N,K]^T + bias), fp32 in / fp32 out on the CDNA4 matrix cores.
 //
 // Kernels in this file (all 128 x 128 workgroup tiles, four waves as 2 x 2, 32 x 32 MFMA tiles):
-//   gemm_f32_kernel<false>          v_mfma_f32_32x32x2_f32, exact fp32 FMA chains (LS_GEMM_BF16X3=0, and the caller-designated latency GEMMs)
+//   gemm_f32_kernel<false>          v_mfma_f32_32x32x2_f32, exact fp32 FMA chains (LS_GEMM_MODE=fp32, and the caller-designated latency GEMMs)
 //   gemm_f32_kernel<true, 3 | 2>    fp32 products as three (two) bf16 pieces, six (three) v_mfma_f32_32x32x16_bf16 per 16 k (LS_GEMM_MODE=bf16x3)
 //   gemm_f32_kernel<true, 22>       fp32 products as two f16 pieces (h + residual), three v_mfma_f32_32x32x16_f16 into one accumulator: the DEFAULT arithmetic
 //   gemm_h2_kernel                  the same arithmetic as a double-buffered software pipeline (K >= 128)
@@ -9,6 +9,8 @@
 //   gemm_h2_smallk_kernel           the same arithmetic, persistent over the M-tiles of an N-tile (K = 32 / 64 table GEMMs)
 //   gemm_vn_kernel                  gemm_h2_kernel with the VN activation of the residual global conv as its epilogue
 //   gemm_smallk_kernel              fp32-MFMA persistent small-K kernel (fp32 mode only)
+// Which kernel runs a problem, on what grid, is decided by gemm_plan / gemm_vn_plan (gemm_plan.h: a pure host function, replayed on the CPU by
+// tests/test_gemm_plan_cpu.py); gemm_run / gemm_vn_run at the end of this file check the arguments and launch what the plan says.
 // The paragraph below describes the fp32-MFMA kernel the others grew from (tile shape, LDS layout, k permutation).
 //
 // This is the ONLY MFMA-shaped work on the path: the VecLinear channel contraction
@@ -1815,9 +1817,6 @@ __global__ __launch_bounds__(256) void gemm_presplit_w_kernel(const float* __res
     *reinterpret_cast<uint2*>(line + 64) = pl;
 }
 size_t gemm_w_planes_bytes(size_t rows, int K) { return rows * (size_t)K * 4; }
-// the kernels that read planes: gemm_h2_kernel<true, true>, gemm_w2_kernel<., true>.  Measured: -5 % at
-// the decoder shape (992 -> 941 us wide, 1198 -> 1128 us narrow), neutral at K = 512, +8 .. 15 % on the K = 128 / 256 tables: K >= 512 only
-bool gemm_w_planes_useful(int K) { return K >= 512 && K % 32 == 0; }
 int gemm_presplit_w_launch(const float* W, int rows, int K, int ldw, const float* rowmax, void* planes, hipStream_t st) {
     LS_REQUIRE(K % 8 == 0 && ((uintptr_t)planes % 16) == 0, "gemm_presplit_w: K must be a multiple of 8 and the planes 16-byte aligned (K=%d)", K);
     hipLaunchKernelGGL(gemm_presplit_w_kernel, dim3(cdiv((long long)rows * (K / 4), 256)), dim3(256), 0, st, W, rows, K, ldw, rowmax,
@@ -1837,215 +1836,166 @@ int gemm_mode() {
     return mode;
 }
 
-// Under-filled grids with a long K loop (the per-instance "mean" rows of the residual global conv: M = 3B rows against
-// K = C up to 512; conv_c) are pure latency: 32 workgroups x 16 dependent k-steps = 44 us for 0.2 GFLOP.  They are split
-// along K into slices written as partial slabs and combined by a second launch.
-static int gemm_choose_splits(int M, int N, int K) {
-    const int tiles = cdiv(M, GM) * cdiv(N, GN);
-    if (tiles >= 192 || K < 128 || N % 4 != 0) return 1;
-    int s2 = 512 / tiles;
-    if (s2 > K / 32) s2 = K / 32;
-    return s2 < 2 ? 1 : s2;
+static_assert(GM == GEMM_TILE && GN == GEMM_TILE && GK == GEMM_FP32_SLAB, "gemm_plan.h plans for these tiles");
+
+GemmTraits gemm_traits(const Gemm& g) {
+    GemmTraits t;
+    t.M = g.M; t.N = g.N; t.K = g.K; t.lda = g.lda; t.ldw = g.ldw;
+    t.mode = gemm_mode();
+    t.pieces = g.pieces;
+    t.gather = g.a_rows != nullptr; t.masked = g.mask != nullptr; t.may_split = g.scratch != nullptr; t.latency = g.latency;
+    t.has_planes = g.aux.w_planes && g.aux.w_rowmax;
+    t.wants_out_rowmax = g.aux.out_rowmax != nullptr;
+    return t;
 }
-size_t gemm_scratch_floats(int M, int N, int K) {
-    const int s2 = gemm_choose_splits(M, N, K);
-    return s2 > 1 ? (size_t)s2 * M * N : 0;
+GemmTraits gemm_traits(const GemmVn& g) {
+    GemmTraits t;
+    t.M = g.M; t.C = g.C; t.K = g.K; t.lda = g.lda; t.ldw = g.ldw; t.npts = g.npts;
+    t.mode = gemm_mode();
+    t.has_G_or_cs = g.G || g.aux.cs;
+    t.a_parts = g.aux.a_parts; t.has_a_rowmax = g.aux.a_rowmax != nullptr; t.has_w_rowmax = g.aux.w_rowmax != nullptr;
+    return t;
 }
 
-int gemm_dispatch_full(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N, int K,
-                       int relu, const int32_t* a_rows, int gNd, int gNs, float* scratch, hipStream_t st, bool latency_path = false,
-                       int pieces = 3, const float* mask = nullptr, GemmAux aux = GemmAux()) {
+// the policy is gemm_plan (gemm_plan.h); here: the argument checks and one launch per kernel family
+int gemm_run(const Gemm& g, hipStream_t st) {
+    const int M = g.M, N = g.N, K = g.K;
     LS_REQUIRE(M > 0 && N > 0 && K > 0, "gemm: empty problem (M=%d N=%d K=%d)", M, N, K);
-    LS_REQUIRE(K % 4 == 0 && lda % 4 == 0 && ldw % 4 == 0, "gemm: K, lda, ldw must be multiples of 4 (K=%d lda=%d ldw=%d)", K, lda, ldw);
-    LS_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0, "gemm: A and W must be 16-byte aligned");
-    const int tm = cdiv(M, GM), tn = cdiv(N, GN);
-    const bool split_on = gemm_mode() != 2;      // LS_GEMM_MODE=fp32: exact fp32 FMA chains on v_mfma_f32_32x32x2_f32
-    // (fp32 mode only: with three-piece bf16 products the tiled kernel below is faster on the K = 32 tables too -- 27.8 / 42.8 /
-    // 34.5 us vs 28.8 / 47.2 / 38.8 us for the three layer-1/2 shapes -- and the arithmetic then depends on nothing but K)
-    if (K == 32 && tm >= 16 && !split_on) {
-        // persistent small-K kernel: ~3 resident workgroups per CU, spread evenly over the N-tiles.  (The K = 64 instantiation
-        // needs 70 KB of LDS -> 2 workgroups per CU and measured SLOWER than the tiled kernel: 138 vs 110 us at the layer-3 shape.)
-        int per_n = cdiv(768, tn);
-        if (per_n > tm) per_n = tm;
-#define LS_SMALLK(KK, G)                                                                                                          \
-    hipLaunchKernelGGL((gemm_smallk_kernel<KK, G>), dim3(tn * per_n), dim3(256), 0, st, A, lda, W, ldw, bias, out, ldc, M, N, relu, tm, \
-                       per_n, a_rows, gNd, gNs)
-        if (a_rows) LS_SMALLK(32, true); else LS_SMALLK(32, false);
-#undef LS_SMALLK
-        LS_LAUNCH_CHECK();
-        return LS_OK;
+    LS_REQUIRE(K % 4 == 0 && g.lda % 4 == 0 && g.ldw % 4 == 0, "gemm: K, lda, ldw must be multiples of 4 (K=%d lda=%d ldw=%d)", K, g.lda, g.ldw);
+    LS_REQUIRE(((uintptr_t)g.A % 16) == 0 && ((uintptr_t)g.W % 16) == 0, "gemm: A and W must be 16-byte aligned");
+    const GemmPlan p = gemm_plan(gemm_traits(g));
+    const dim3 grid(p.grid_x, p.grid_y), block(p.block);
+    // (the instantiations are named below in the order the code object has always held them: the compiler emits them in the order of first mention)
+    decltype(&gemm_f32_kernel<false>) tiled = nullptr;   // the tiled kernels share one parameter list
+    switch (p.kernel) {
+    case GemmKernel::SMALLK32_GATHER:
+    case GemmKernel::SMALLK32: {
+        const auto fn = p.kernel == GemmKernel::SMALLK32_GATHER ? gemm_smallk_kernel<32, true> : gemm_smallk_kernel<32, false>;
+        hipLaunchKernelGGL(fn, grid, block, 0, st, g.A, g.lda, g.W, g.ldw, g.bias, g.out, g.ldc, M, N, g.relu, p.tm, p.per_n, g.a_rows, g.gNd, g.gNs);
+        break;
     }
-    // LS_GEMM_BF16X3=0: exact fp32 FMA chains on v_mfma_f32_32x32x2_f32 (A/B timing, bit-for-bit comparison with earlier builds)
-    // The arithmetic must not depend on M (a decode of one instance's points has to equal the same rows inside a batched decode),
-    // so the choice is the CALLER's: latency_path = a handful of tiles by construction (the per-instance mean rows of the global
-    // conv, M = 3B), where the fp32 kernel's shorter slab (16 k, no split arithmetic before the first MFMA) wins: 44 vs 112 us
-    // at M = 192, N = 1024, K = 512
-    const bool split = split_on && !latency_path;
-    // how an fp32 product is formed on the 16-bit matrix cores: 22 = two f16 pieces (three MFMAs per 16 k, the
-    // default), 3 = three bf16 pieces (six MFMAs, any fp32 range: LS_GEMM_MODE=bf16x3), 2 = two bf16 pieces (opt-in decode mode)
-    const bool wpl = aux.w_planes && aux.w_rowmax && K % 32 == 0 && K > 64;
-#define LS_H2_KERNEL (K <= 64 ? gemm_f32_kernel<true, 22> : (K % 32 == 0 ? (wpl ? gemm_h2_kernel<true, true> : gemm_h2_kernel<true, false>) : gemm_h2_kernel<false, false>))
-    const int default_pieces = gemm_mode() == 1 ? 3 : 22;
-    if (pieces == 3) pieces = default_pieces;
-    const int nsplit = (scratch && !mask) ? gemm_choose_splits(M, N, K) : 1;   // (a split launch writes no out_rowmax: callers check gemm_scratch_floats)
-    if (nsplit > 1) {
-        const int kq = split ? 32 : GK;
-        int kchunk = cdiv(cdiv(K, nsplit), kq) * kq;
-        const int ns = cdiv(K, kchunk);
-        const size_t slab = (size_t)M * N;
-        if (split && pieces == 22)
-            hipLaunchKernelGGL(LS_H2_KERNEL, dim3(tm * tn, ns), dim3(256), 0, st, A, lda, W, ldw, nullptr, scratch, N, M, N, K, 0, tn,
-                               a_rows, gNd, gNs, kchunk, slab, (const float*)nullptr, aux);
-        else if (split)
-            hipLaunchKernelGGL(gemm_f32_kernel<true>, dim3(tm * tn, ns), dim3(256), 0, st, A, lda, W, ldw, nullptr, scratch, N, M, N, K, 0, tn,
-                               a_rows, gNd, gNs, kchunk, slab, (const float*)nullptr, aux);
-        else
-            hipLaunchKernelGGL(gemm_f32_kernel<false>, dim3(tm * tn, ns), dim3(256), 0, st, A, lda, W, ldw, nullptr, scratch, N, M, N, K, 0, tn,
-                               a_rows, gNd, gNs, kchunk, slab, (const float*)nullptr, aux);
-        LS_LAUNCH_CHECK();
-        hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(cdiv((long long)M * (N / 4), 256)), dim3(256), 0, st, scratch, slab, ns, bias, out,
-                           ldc, M, N, relu);
-        LS_LAUNCH_CHECK();
-        return LS_OK;
+    case GemmKernel::H2_PLANES: tiled = gemm_h2_kernel<true, true>; break;
+    case GemmKernel::H2: tiled = gemm_h2_kernel<true, false>; break;
+    case GemmKernel::H2_ANYK: tiled = gemm_h2_kernel<false, false>; break;
+    case GemmKernel::F32_F16X2: tiled = gemm_f32_kernel<true, 22>; break;
+    case GemmKernel::F32_BF16X3: tiled = gemm_f32_kernel<true>; break;
+    case GemmKernel::F32_EXACT: tiled = gemm_f32_kernel<false>; break;
+    case GemmKernel::H2_SMALLK32_GATHER:
+    case GemmKernel::H2_SMALLK32:
+    case GemmKernel::H2_SMALLK64_GATHER:
+    case GemmKernel::H2_SMALLK64: {
+        const decltype(&gemm_h2_smallk_kernel<32, true>) sk[4] = {gemm_h2_smallk_kernel<32, true>, gemm_h2_smallk_kernel<32, false>,
+                                                                  gemm_h2_smallk_kernel<64, true>, gemm_h2_smallk_kernel<64, false>};
+        hipLaunchKernelGGL(sk[(int)p.kernel - (int)GemmKernel::H2_SMALLK32_GATHER], grid, block, 0, st, g.A, g.lda, g.W, g.ldw, g.bias, g.out, g.ldc, M, N,
+                           g.relu, p.tm, p.per_n, g.a_rows, g.gNd, g.gNs, g.aux);
+        break;
     }
-    // 256 x 256 tiles once they fill the chip (same arithmetic, bit-identical results).  Measured: the wide kernel wins when its grid fills whole
-    // rounds of the 256 CUs (one workgroup per CU): 480 tiles 88 -> 73 us, 768 tiles 355 -> 280 us, 3072 tiles 1186 -> 1002 us; ties at 384 tiles, loses below one round
-    const long long wtiles = (long long)cdiv(M, 256) * cdiv(N, 256);
-    const bool wide_on = wtiles >= 1024 || (wtiles >= 256 && wtiles * 100 >= 85 * 256 * cdiv(wtiles, 256));
-    if (split && pieces == 22 && tm >= 16 && !mask && (K == 32 || K == 64) && !aux.out_rowmax) {
-        int per_n = cdiv(512, tn);   // resident workgroups per CU x 256, spread evenly over the N-tiles
-        if (per_n > tm) per_n = tm;
-#define LS_H2SK(KK, G) hipLaunchKernelGGL((gemm_h2_smallk_kernel<KK, G>), dim3(tn * per_n), dim3(256), 0, st, A, lda, W, ldw, bias, out, ldc, M, N, relu, tm, per_n, a_rows, gNd, gNs, aux)
-        if (K == 32) { if (a_rows) LS_H2SK(32, true); else LS_H2SK(32, false); }
-        else { if (a_rows) LS_H2SK(64, true); else LS_H2SK(64, false); }
-#undef LS_H2SK
-    } else if (split && pieces == 22 && wide_on && !a_rows && K % 32 == 0 && K >= 128 && (unsigned long long)M * lda < (1ull << 30) &&
-               (unsigned long long)N * std::max(ldw, K) < (1ull << 30)) {   // (the wide kernel addresses its operands by 32-bit byte offsets)
-        const int wtm = cdiv(M, 256), wtn = cdiv(N, 256);
-        const size_t lds = 2 * 4 * 256 * 64 + 512 * sizeof(float);
+    case GemmKernel::W2:
+    case GemmKernel::W2_MASKED:
+    case GemmKernel::W2_PLANES:
+    case GemmKernel::W2_MASKED_PLANES: {
+        const decltype(&gemm_w2_kernel<false, false>) w2[4] = {gemm_w2_kernel<false, false>, gemm_w2_kernel<true, false>, gemm_w2_kernel<false, true>,
+                                                               gemm_w2_kernel<true, true>};
         // the dynamic-LDS opt-in is a per-DEVICE function attribute: one flag per device ordinal (a process may drive several GPUs)
         static std::atomic<unsigned long long> attr_devices{0};
         int dev_ord = 0;
         LS_HIP_CHECK(hipGetDevice(&dev_ord));
         const unsigned long long dev_bit = 1ull << (dev_ord & 63);
         if (!(attr_devices.load(std::memory_order_acquire) & dev_bit)) {
-#define LS_W2_ATTR(MK, PL) LS_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_w2_kernel<MK, PL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
-            LS_W2_ATTR(false, false); LS_W2_ATTR(true, false); LS_W2_ATTR(false, true); LS_W2_ATTR(true, true);
-#undef LS_W2_ATTR
+            for (const auto fn : w2) LS_HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
             attr_devices.fetch_or(dev_bit, std::memory_order_release);
         }
-#define LS_W2(MK, PL) hipLaunchKernelGGL((gemm_w2_kernel<MK, PL>), dim3(wtm * wtn), dim3(512), lds, st, A, lda, W, ldw, bias, out, ldc, M, N, K, relu, wtn, wtm * wtn, mask, aux)
-        if (mask) { if (wpl) LS_W2(true, true); else LS_W2(true, false); }
-        else { if (wpl) LS_W2(false, true); else LS_W2(false, false); }
-#undef LS_W2
-    } else if (split && pieces == 22)
-        hipLaunchKernelGGL(LS_H2_KERNEL, dim3(tm * tn), dim3(256), 0, st, A, lda, W, ldw, bias, out, ldc, M, N, K, relu, tn, a_rows,
-                           gNd, gNs, K, (size_t)0, mask, aux);
-    else if (split && pieces == 2)
-        hipLaunchKernelGGL((gemm_f32_kernel<true, 2>), dim3(tm * tn), dim3(256), 0, st, A, lda, W, ldw, bias, out, ldc, M, N, K, relu, tn, a_rows,
-                           gNd, gNs, K, (size_t)0, mask, aux);
-    else if (split)
-        hipLaunchKernelGGL(gemm_f32_kernel<true>, dim3(tm * tn), dim3(256), 0, st, A, lda, W, ldw, bias, out, ldc, M, N, K, relu, tn, a_rows,
-                           gNd, gNs, K, (size_t)0, mask, aux);
-    else
-        hipLaunchKernelGGL(gemm_f32_kernel<false>, dim3(tm * tn), dim3(256), 0, st, A, lda, W, ldw, bias, out, ldc, M, N, K, relu, tn, a_rows,
-                           gNd, gNs, K, (size_t)0, mask, aux);
+        hipLaunchKernelGGL(w2[(int)p.kernel - (int)GemmKernel::W2], grid, block, p.lds, st, g.A, g.lda, g.W, g.ldw, g.bias, g.out, g.ldc, M, N, K, g.relu, p.tn,
+                           p.tm * p.tn, g.mask, g.aux);
+        break;
+    }
+    case GemmKernel::F32_BF16X2: tiled = gemm_f32_kernel<true, 2>; break;
+    default: LS_REQUIRE(false, "gemm: no kernel planned (M=%d N=%d K=%d)", M, N, K);
+    }
+    if (tiled) {
+        // a split launch writes its K slices as partial slabs [ns][M][N] to the scratch; bias, activation and the store to `out` are the reduction's
+        const bool sk = p.nsplit > 1;
+        const size_t slab = (size_t)M * N;
+        hipLaunchKernelGGL(tiled, grid, block, 0, st, g.A, g.lda, g.W, g.ldw, sk ? nullptr : g.bias, sk ? g.scratch : g.out, sk ? N : g.ldc, M, N, K,
+                           sk ? 0 : g.relu, p.tn, g.a_rows, g.gNd, g.gNs, p.kchunk, sk ? slab : (size_t)0, sk ? nullptr : g.mask, g.aux);
+        if (sk) {
+            LS_LAUNCH_CHECK();
+            hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(p.reduce_grid), dim3(256), 0, st, g.scratch, slab, p.ns, g.bias, g.out, g.ldc, M, N, g.relu);
+        }
+    }
     LS_LAUNCH_CHECK();
     return LS_OK;
 }
-int gemm_dispatch_gather(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N,
-                         int K, int relu, const int32_t* a_rows, int gNd, int gNs, hipStream_t st, GemmAux aux) {
-    return gemm_dispatch_full(A, lda, W, ldw, bias, out, ldc, M, N, K, relu, a_rows, gNd, gNs, nullptr, st, false, 3, nullptr, aux);
-}
-int gemm_dispatch(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N,
-                  int K, int relu, hipStream_t st, GemmAux aux) {
-    return gemm_dispatch_full(A, lda, W, ldw, bias, out, ldc, M, N, K, relu, nullptr, 0, 0, nullptr, st, false, 3, nullptr, aux);
-}
-int gemm_dispatch_ws(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N,
-                     int K, int relu, float* scratch, hipStream_t st, GemmAux aux) {
-    return gemm_dispatch_full(A, lda, W, ldw, bias, out, ldc, M, N, K, relu, nullptr, 0, 0, scratch, st, false, 3, nullptr, aux);
-}
-// opt-in two-piece products (decoder throughput mode); never splits K
-int gemm_dispatch_fast2(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N,
-                        int K, int relu, hipStream_t st) {
-    return gemm_dispatch_full(A, lda, W, ldw, bias, out, ldc, M, N, K, relu, nullptr, 0, 0, nullptr, st, false, 2);
-}
-// out = (mask > 0) ? A W^T : 0 with `mask` laid out like `out` (never splits K); pieces = 3 | 2
-int gemm_dispatch_masked(const float* A, int lda, const float* W, int ldw, float* out, int ldc, int M, int N, int K, const float* mask, int pieces,
-                         hipStream_t st, GemmAux aux) {
-    return gemm_dispatch_full(A, lda, W, ldw, nullptr, out, ldc, M, N, K, 0, nullptr, 0, 0, nullptr, st, false, pieces, mask, aux);
-}
-// out [M = B * npts * 3, C] = VN-act(A W[0:C]^T + G lin part, A W[C:2C]^T + G dir part): see gemm_vn_kernel.  false = shape / mode not
-// supported (the caller runs GEMM + vn_act_rows instead)
-bool gemm_vn_supported(int M, int C, int K) {
-    return gemm_mode() == 0 && C % 64 == 0 && K % 4 == 0 && K >= 32 && M % 3 == 0;
-}
-// does gemm_vn_dispatch take the streaming kernel (gemm_vn_direct_kernel) for this problem?  Only then is GemmAux::cs honoured (model.hip: global_conv)
-bool gemm_vn_streams(int M, int C, int K, int lda, int npts, const GemmAux& aux) {
-    return gemm_vn_supported(M, C, K) && K == 64 && C == 64 && lda == K && npts % 8 == 0 && aux.a_rowmax && aux.a_parts > 0 && aux.w_rowmax &&
-           M >= 24 * 64;
-}
-int gemm_vn_dispatch(const float* A, int lda, const float* W, int ldw, const float* G, int ldg, float* out, int M, int C, int K, int npts, float oms,
-                     hipStream_t st, GemmAux aux) {
-    LS_REQUIRE(gemm_vn_supported(M, C, K) && lda % 4 == 0 && ldw % 4 == 0, "gemm_vn: unsupported shape (M=%d C=%d K=%d)", M, C, K);
-    const int tm = cdiv(M, 120), tn = C / 64;
-    if (gemm_vn_streams(M, C, K, lda, npts, aux) && (G || aux.cs)) {
-        const int B = M / (3 * npts), tiles_inst = npts / 8;
-        int wpi = cdiv(512, B);                                   // ~512 workgroups (two per CU), every one inside one instance
-        wpi = std::max(1, std::min(wpi, cdiv(tiles_inst, 2)));
-#define LS_VND(ONE) hipLaunchKernelGGL((gemm_vn_direct_kernel<64, ONE>), dim3(B * wpi), dim3(256), 0, st, A, W, ldw, G, ldg, out, npts, wpi, oms, aux, aux.cs, aux.cs_rows, 1.0f / (float)npts)
-        if (aux.a_parts == 1) LS_VND(true); else LS_VND(false);
-#undef LS_VND
-        LS_LAUNCH_CHECK();
-        return LS_OK;
+
+int gemm_vn_run(const GemmVn& g, hipStream_t st) {
+    const GemmPlan p = gemm_vn_plan(gemm_traits(g));
+    LS_REQUIRE(p.kernel != GemmKernel::NONE && g.lda % 4 == 0 && g.ldw % 4 == 0, "gemm_vn: unsupported shape (M=%d C=%d K=%d)", g.M, g.C, g.K);
+    const dim3 grid(p.grid_x), block(p.block);
+    switch (p.kernel) {
+    case GemmKernel::VN_DIRECT_ONEPART:
+    case GemmKernel::VN_DIRECT: {
+        const auto fn = p.kernel == GemmKernel::VN_DIRECT_ONEPART ? gemm_vn_direct_kernel<64, true> : gemm_vn_direct_kernel<64, false>;
+        hipLaunchKernelGGL(fn, grid, block, 0, st, g.A, g.W, g.ldw, g.G, g.ldg, g.out, g.npts, p.per_n, g.oms, g.aux, g.aux.cs, g.aux.cs_rows,
+                           1.0f / (float)g.npts);
+        break;
     }
-    if ((K == 32 || K == 64) && tm >= 16 && lda == K) {
-        int per_n = cdiv(512, tn);   // resident workgroups per CU x 256
-        if (per_n > tm) per_n = tm;
-        if (K == 32) hipLaunchKernelGGL(gemm_vn_smallk_kernel<32>, dim3(tn * per_n), dim3(256), 0, st, A, lda, W, ldw, G, ldg, out, M, C, npts, oms, tm, per_n, tn, aux);
-        else hipLaunchKernelGGL(gemm_vn_smallk_kernel<64>, dim3(tn * per_n), dim3(256), 0, st, A, lda, W, ldw, G, ldg, out, M, C, npts, oms, tm, per_n, tn, aux);
-        LS_LAUNCH_CHECK();
-        return LS_OK;
+    case GemmKernel::VN_SMALLK32:
+    case GemmKernel::VN_SMALLK64: {
+        const auto fn = p.kernel == GemmKernel::VN_SMALLK32 ? gemm_vn_smallk_kernel<32> : gemm_vn_smallk_kernel<64>;
+        hipLaunchKernelGGL(fn, grid, block, 0, st, g.A, g.lda, g.W, g.ldw, g.G, g.ldg, g.out, g.M, g.C, g.npts, g.oms, p.tm, p.per_n, p.tn, g.aux);
+        break;
     }
-    if (K % 32 == 0) hipLaunchKernelGGL(gemm_vn_kernel<true>, dim3(tm * tn), dim3(256), 0, st, A, lda, W, ldw, G, ldg, out, M, C, K, npts, oms, tn, aux);
-    else hipLaunchKernelGGL(gemm_vn_kernel<false>, dim3(tm * tn), dim3(256), 0, st, A, lda, W, ldw, G, ldg, out, M, C, K, npts, oms, tn, aux);
+    default: {
+        const auto fn = p.kernel == GemmKernel::VN ? gemm_vn_kernel<true> : gemm_vn_kernel<false>;
+        hipLaunchKernelGGL(fn, grid, block, 0, st, g.A, g.lda, g.W, g.ldw, g.G, g.ldg, g.out, g.M, g.C, g.K, g.npts, g.oms, p.tn, g.aux);
+    }
+    }
     LS_LAUNCH_CHECK();
     return LS_OK;
-}
-int gemm_dispatch_small(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N,
-                        int K, int relu, float* scratch, hipStream_t st) {
-    return gemm_dispatch_full(A, lda, W, ldw, bias, out, ldc, M, N, K, relu, nullptr, 0, 0, scratch, st, true);
 }
 
 }  // namespace ls
 
 using namespace ls;
+// The public GEMMs share one path: the plan of the problem says what workspace it needs.  optional: a NULL workspace means "do not split K"
+// (ls_gemm_f32_ex, ls_gemm_f32_planes) instead of an error.  Bad arguments need nothing here: gemm_run says what is wrong with them.
+static int gemm_public(const char* who, Gemm g, void* workspace, size_t workspace_bytes, bool optional, void* stream) {
+    GemmTraits t = gemm_traits(g);
+    t.may_split = workspace || !optional;
+    const bool args_ok = g.M > 0 && g.N > 0 && g.K > 0 && g.K % 4 == 0 && g.lda % 4 == 0 && g.ldw % 4 == 0;
+    const size_t need = args_ok ? gemm_plan(t).scratch_floats * sizeof(float) : 0;   // split-K slabs of an under-filled, long-K problem
+    LS_REQUIRE(!(need && g.aux.out_rowmax), "%s: a split-K launch (M=%d N=%d K=%d with a workspace) writes no out_rowmax: pass workspace = NULL", who, g.M,
+               g.N, g.K);
+    if (need && (need > workspace_bytes || !workspace)) {
+        set_error("%s: workspace %zu < required %zu (ls_gemm_workspace_bytes)", who, workspace_bytes, need);
+        return LS_ERR_WORKSPACE;
+    }
+    g.scratch = need ? (float*)workspace : nullptr;
+    return gemm_run(g, (hipStream_t)stream);
+}
+static Gemm gemm_public_problem(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N, int K, int relu,
+                                const float* a_rowmax, int a_parts, const float* w_rowmax, float* out_rowmax, const void* w_planes) {
+    Gemm g;
+    g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.out = out; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.relu = relu;
+    g.aux.a_rowmax = a_rowmax; g.aux.a_parts = a_rowmax ? a_parts : 0; g.aux.w_rowmax = w_rowmax; g.aux.out_rowmax = out_rowmax; g.aux.w_planes = w_planes;
+    return g;
+}
 extern "C" {
 size_t ls_gemm_workspace_bytes(int M, int N, int K) {
     return (M > 0 && N > 0 && K > 0 && K % 4 == 0) ? gemm_scratch_floats(M, N, K) * sizeof(float) : 0;
 }
 int ls_gemm_f32(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N, int K,
                 int relu, void* workspace, size_t workspace_bytes, void* stream) {
-    const size_t sb = (lda % 4 == 0 && ldw % 4 == 0) ? ls_gemm_workspace_bytes(M, N, K) : 0;
-    if (!sb) return gemm_dispatch(A, lda, W, ldw, bias, out, ldc, M, N, K, relu, (hipStream_t)stream);
-    if (sb > workspace_bytes || !workspace) {   // split-K slabs of an under-filled, long-K problem
-        set_error("gemm: workspace %zu < required %zu (ls_gemm_workspace_bytes)", workspace_bytes, sb);
-        return LS_ERR_WORKSPACE;
-    }
-    return gemm_dispatch_ws(A, lda, W, ldw, bias, out, ldc, M, N, K, relu, (float*)workspace, (hipStream_t)stream);
+    return gemm_public("gemm", gemm_public_problem(A, lda, W, ldw, bias, out, ldc, M, N, K, relu, nullptr, 0, nullptr, nullptr, nullptr), workspace,
+                       workspace_bytes, false, stream);
 }
 int ls_gemm_rowmax_parts(int N) { return N > 0 ? gemm_rowmax_parts(N) : 0; }
 int ls_gemm_f32_ex(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N, int K,
                    int relu, const float* a_rowmax, int a_parts, const float* w_rowmax, float* out_rowmax, void* workspace,
                    size_t workspace_bytes, void* stream) {
     LS_REQUIRE(!a_rowmax || a_parts >= 1, "gemm_ex: a_rowmax needs a_parts >= 1");
-    GemmAux ax;
-    ax.a_rowmax = a_rowmax; ax.a_parts = a_rowmax ? a_parts : 0; ax.w_rowmax = w_rowmax; ax.out_rowmax = out_rowmax;
-    const size_t sb = (workspace && lda % 4 == 0 && ldw % 4 == 0) ? ls_gemm_workspace_bytes(M, N, K) : 0;
-    LS_REQUIRE(!(sb && out_rowmax), "gemm_ex: a split-K launch (M=%d N=%d K=%d with a workspace) writes no out_rowmax: pass workspace = NULL", M, N, K);
-    if (!sb) return gemm_dispatch(A, lda, W, ldw, bias, out, ldc, M, N, K, relu, (hipStream_t)stream, ax);
-    if (sb > workspace_bytes) { set_error("gemm_ex: workspace %zu < required %zu (ls_gemm_workspace_bytes)", workspace_bytes, sb); return LS_ERR_WORKSPACE; }
-    return gemm_dispatch_ws(A, lda, W, ldw, bias, out, ldc, M, N, K, relu, (float*)workspace, (hipStream_t)stream, ax);
+    return gemm_public("gemm_ex", gemm_public_problem(A, lda, W, ldw, bias, out, ldc, M, N, K, relu, a_rowmax, a_parts, w_rowmax, out_rowmax, nullptr),
+                       workspace, workspace_bytes, true, stream);
 }
 int ls_rowmax_f32(const float* X, int rows, int K, int ld, float* out, void* stream) {
     LS_REQUIRE(X && out && rows > 0 && K > 0 && ld >= K, "rowmax: bad argument");
@@ -2063,8 +2013,7 @@ int ls_gemm_f32_planes(const float* A, int lda, const float* W, int ldw, const v
     LS_REQUIRE(w_planes && w_rowmax, "gemm_planes: w_planes and w_rowmax are required (ls_gemm_presplit_w_f32)");
     LS_REQUIRE(!a_rowmax || a_parts >= 1, "gemm_planes: a_rowmax needs a_parts >= 1");
     LS_REQUIRE(gemm_w_planes_useful(K), "gemm_planes: no kernel reads planes at K = %d", K);
-    GemmAux ax;
-    ax.a_rowmax = a_rowmax; ax.a_parts = a_rowmax ? a_parts : 0; ax.w_rowmax = w_rowmax; ax.out_rowmax = out_rowmax; ax.w_planes = w_planes;
-    return gemm_dispatch(A, lda, W, ldw, bias, out, ldc, M, N, K, relu, (hipStream_t)stream, ax);
+    return gemm_public("gemm_planes", gemm_public_problem(A, lda, W, ldw, bias, out, ldc, M, N, K, relu, a_rowmax, a_parts, w_rowmax, out_rowmax, w_planes),
+                       nullptr, 0, true, stream);
 }
 }  // extern "C"

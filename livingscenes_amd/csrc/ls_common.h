@@ -63,7 +63,7 @@ struct GemmAux {
     const float* w_rowmax = nullptr;   // [N]
     const void* w_planes = nullptr;    // pre-split W (gemm_presplit_w_launch): row n = K / 32 lines [hi: 32 f16 | lo: 32 f16] of s_n W[n, :], s_n from w_rowmax (required)
     float* out_rowmax = nullptr;       // [M][2 * cdiv(N, 128)]: max|out[row, 64-column block]| written by the epilogue (un-split launches only)
-    const float* cs = nullptr;         // gemm_vn_dispatch only: partial column sums of A ([instance][cs_rows][3][C], edge.hip: attn_colsum) -- the kernel forms the
+    const float* cs = nullptr;         // gemm_vn_run only: partial column sums of A ([instance][cs_rows][3][C], edge.hip: attn_colsum) -- the kernel forms the
     int cs_rows = 0;                   // mean part of the conv itself instead of reading G (gemm.hip: gemm_vn_direct_kernel); ignored where that kernel is not taken
 };
 

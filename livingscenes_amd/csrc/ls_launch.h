@@ -3,6 +3,7 @@
 // drifts from its declaration fails where it is made.  (The k-NN files' own cross-calls are in knn_common.h; set_error is in ls_common.h.)
 #pragma once
 #include "ls_common.h"
+#include "gemm_plan.h"
 
 namespace ls {
 
@@ -18,27 +19,39 @@ int fps_dispatch(const float* pts, const int32_t* lengths, int B, int N, int K, 
                  hipStream_t st);
 size_t fps_scratch_bytes_per_cloud(int N);
 // ---- gemm.hip
+// (gemm_plan.h: the kernel choice -- gemm_plan, gemm_vn_plan -- and its queries gemm_scratch_floats, gemm_w_planes_useful)
 int gemm_mode();
-int gemm_dispatch(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N, int K, int relu, hipStream_t st,
-                  GemmAux aux = GemmAux());
-int gemm_dispatch_gather(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N, int K, int relu,
-                         const int32_t* a_rows, int gNd, int gNs, hipStream_t st, GemmAux aux = GemmAux());
-int gemm_dispatch_ws(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N, int K, int relu, float* scratch,
-                     hipStream_t st, GemmAux aux = GemmAux());
-int gemm_dispatch_small(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N, int K, int relu, float* scratch,
-                        hipStream_t st);
-int gemm_dispatch_fast2(const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldc, int M, int N, int K, int relu, hipStream_t st);
-int gemm_dispatch_masked(const float* A, int lda, const float* W, int ldw, float* out, int ldc, int M, int N, int K, const float* mask, int pieces, hipStream_t st,
-                         GemmAux aux = GemmAux());
-size_t gemm_scratch_floats(int M, int N, int K);
-bool gemm_vn_supported(int M, int C, int K);
-bool gemm_vn_streams(int M, int C, int K, int lda, int npts, const GemmAux& aux);
-int gemm_vn_dispatch(const float* A, int lda, const float* W, int ldw, const float* G, int ldg, float* out, int M, int C, int K, int npts, float oms, hipStream_t st,
-                     GemmAux aux = GemmAux());
+// out [M, N] = act(A [M, K] W [N, K]^T + bias)
+struct Gemm {
+    const float* A = nullptr; int lda = 0;
+    const float* W = nullptr; int ldw = 0;
+    const float* bias = nullptr;
+    float* out = nullptr; int ldc = 0;
+    int M = 0, N = 0, K = 0, relu = 0;
+    const int32_t* a_rows = nullptr; int gNd = 0, gNs = 0;   // gather: row r of A is row a_rows[r] of its instance (gNd rows of gNs)
+    float* scratch = nullptr;      // gemm_scratch_floats(M, N, K) floats: the launch may split K
+    bool latency = false;          // a handful of tiles by construction: the short-slab fp32 kernel (gemm_plan.h)
+    int pieces = 3;                // 2: two-piece bf16 products (the decoder's opt-in throughput mode)
+    const float* mask = nullptr;   // laid out like `out`: out = (mask > 0) ? A W^T : 0; never splits K
+    GemmAux aux;
+};
+// out [M = B * npts * 3, C] = VN-act(A W[0:C]^T + G lin part, A W[C:2C]^T + G dir part), oms = 1 - negative slope
+struct GemmVn {
+    const float* A = nullptr; int lda = 0;
+    const float* W = nullptr; int ldw = 0;
+    const float* G = nullptr; int ldg = 0;
+    float* out = nullptr;
+    int M = 0, C = 0, K = 0, npts = 0;
+    float oms = 0.f;
+    GemmAux aux;
+};
+GemmTraits gemm_traits(const Gemm& g);
+GemmTraits gemm_traits(const GemmVn& g);
+int gemm_run(const Gemm& g, hipStream_t st);
+int gemm_vn_run(const GemmVn& g, hipStream_t st);   // gemm_vn_plan(gemm_traits(g)).kernel == NONE is an error: the caller runs GEMM + vn_act_rows
 int gemm_rowmax_launch(const float* W, int rows, int K, int ldw, float* out, hipStream_t st);
 int gemm_rowmax_parts(int N);
 size_t gemm_w_planes_bytes(size_t rows, int K);
-bool gemm_w_planes_useful(int K);
 int gemm_presplit_w_launch(const float* W, int rows, int K, int ldw, const float* rowmax, void* planes, hipStream_t st);
 // ---- edge.hip
 int edge_l0_launch(const float* pts, const int32_t* knn, const float* w0, int B, int N, int Co, float neg_slope, float* out, hipStream_t st);

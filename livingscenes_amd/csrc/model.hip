@@ -305,19 +305,19 @@ static int edge_tables(ls_model* m, int i, const float* cur, const int32_t* dst_
     // 32-point attention layers (edge_fused.hip): no table -- only the operand image of the feature rows (f16 fragment planes) is formed here
     if (et.Wt) return edge_ft_prep_launch(cur, dst_rows, B, Ns, Nd, Cin, d.feat_dim[i], T, gs);
     // attention layers 2 - 4 (fused): only the neighbour-side table; the destination side is computed inside the edge kernel (edge.hip)
-    GemmAux ax = aux_w(m, W, nc, Cin);
-    ax.a_rowmax = a_rowmax; ax.a_parts = a_parts;
-    if (et.cur) return gemm_dispatch(cur, Cin, W, Cin, nullptr, T, pc, B * Ns * 3, pc, Cin, 0, gs, ax);
-    if (dst_rows) {
-        // down-sampled layer: P table on all source points, Q table only on the FPS-selected destination points
-        int rc = gemm_dispatch(cur, Cin, W, Cin, nullptr, T, pc, B * Ns * 3, pc, Cin, 0, gs, ax);
-        GemmAux aq = ax;
-        if (aq.w_rowmax) aq.w_rowmax += pc;
-        if (aq.w_planes) aq.w_planes = static_cast<const char*>(aq.w_planes) + gemm_w_planes_bytes((size_t)pc, Cin);   // rows pc.. of the same matrix
-        if (rc == LS_OK) rc = gemm_dispatch_gather(cur, Cin, W + (size_t)pc * Cin, Cin, nullptr, const_cast<float*>(et.Tq), qc, B * Nd * 3, qc, Cin, 0, dst_rows, Nd, Ns, gs, aq);
-        return rc;
-    }
-    return gemm_dispatch(cur, Cin, W, Cin, nullptr, T, nc, B * Ns * 3, nc, Cin, 0, gs, ax);
+    Gemm g;   // the neighbour-side (P) columns, or the combined table, on all source points
+    g.A = cur; g.lda = Cin; g.W = W; g.ldw = Cin; g.out = T; g.M = B * Ns * 3; g.K = Cin;
+    g.N = g.ldc = (et.cur || dst_rows) ? pc : nc;
+    g.aux = aux_w(m, W, nc, Cin);
+    g.aux.a_rowmax = a_rowmax; g.aux.a_parts = a_parts;
+    int rc = gemm_run(g, gs);
+    if (et.cur || !dst_rows || rc != LS_OK) return rc;
+    // down-sampled layer: the destination-side (Q) table only on the FPS-selected destination points -- rows pc.. of the same matrix
+    g.W = W + (size_t)pc * Cin; g.out = const_cast<float*>(et.Tq); g.M = B * Nd * 3; g.N = g.ldc = qc;
+    g.a_rows = dst_rows; g.gNd = Nd; g.gNs = Ns;
+    if (g.aux.w_rowmax) g.aux.w_rowmax += pc;
+    if (g.aux.w_planes) g.aux.w_planes = static_cast<const char*>(g.aux.w_planes) + gemm_w_planes_bytes((size_t)pc, Cin);
+    return gemm_run(g, gs);
 }
 // gather + VN activation + mean-pool | attention of layer i >= 1 over the tables
 // rm_out (nullable) [B*Nd*3]: receives max|out[row, :]| when the kernel taken can write it; *rm_written says whether it did
@@ -370,33 +370,41 @@ static int global_conv(ls_model* m, int i, const float* msg, int B, int Nd, floa
     const float* Wg = m->blob + d.off_glob[i];
     if (rm_written) *rm_written = false;
     int rc;
-    if (m->glob_fuse && gemm_vn_supported(B * Nd * 3, Co, Co)) {
-        // per-instance part: mean over the points and its contraction with the W_b / Wd W_b rows in ONE launch (pointwise.hip) ...
-        GemmAux ax = aux_w(m, Wg, 2 * Co, Co);
-        ax.a_rowmax = rm_msg; ax.a_parts = rm_msg ? rm_msg_parts : 0;
-        ax.out_rowmax = rm_out;
+    GemmVn v;   // the conv as ONE launch: the per-point contraction + the VN activation (gemm.hip: gemm_vn_kernel / gemm_vn_smallk_kernel / gemm_vn_direct_kernel)
+    v.A = msg; v.lda = Co; v.W = Wg; v.ldw = Co; v.G = G; v.ldg = 4 * Co; v.out = out; v.M = B * Nd * 3; v.C = Co; v.K = Co; v.npts = Nd;
+    v.oms = 1.0f - d.neg_slope;
+    v.aux = aux_w(m, Wg, 2 * Co, Co);
+    v.aux.a_rowmax = rm_msg; v.aux.a_parts = rm_msg ? rm_msg_parts : 0;
+    v.aux.out_rowmax = rm_out;
+    if (cs && cs_rows > 0 && cs_rows <= 32) { v.aux.cs = cs; v.aux.cs_rows = cs_rows; }
+    const GemmPlan vp = gemm_vn_plan(gemm_traits(v));
+    if (m->glob_fuse && vp.kernel != GemmKernel::NONE) {
         // 64-channel layers with the producer's column sums: the streaming kernel finishes the mean and its contraction itself -- no mean launch
-        const bool self_mean = cs && cs_rows > 0 && cs_rows <= 32 && gemm_vn_streams(B * Nd * 3, Co, Co, Co, Nd, ax);
-        if (self_mean) { ax.cs = cs; ax.cs_rows = cs_rows; }
-        else {
+        if (!(v.aux.cs && vp.honours_cs)) {
+            // per-instance part: mean over the points and its contraction with the W_b / Wd W_b rows in ONE launch (pointwise.hip) ...
+            v.aux.cs = nullptr; v.aux.cs_rows = 0;
             PROF(LS_K_MEAN, i, st);
             rc = (cs && cs_rows > 0) ? glob_mean_gemv_launch(cs, B, cs_rows, Co, Wg, 2 * Co, 2 * Co, G, 4 * Co, st, Nd)
                                      : glob_mean_gemv_launch(msg, B, Nd, Co, Wg, 2 * Co, 2 * Co, G, 4 * Co, st);
             if (rc != LS_OK) return rc;
         }
-        // ... then ONE launch for the per-point contraction + the VN activation (gemm.hip: gemm_vn_kernel / gemm_vn_smallk_kernel / gemm_vn_direct_kernel)
+        // ... then the per-point launch
         PROF(LS_K_GEMM_GLOB, i, st);
         if (rm_written) *rm_written = rm_out != nullptr;
-        return gemm_vn_dispatch(msg, Co, Wg, Co, G, 4 * Co, out, B * Nd * 3, Co, Co, Nd, 1.0f - d.neg_slope, st, ax);
+        return gemm_vn_run(v, st);
     }
     { PROF(LS_K_MEAN, i, st); rc = mean_points_launch(msg, B, Nd, Co, g, st); }
     if (rc != LS_OK) return rc;
     {
         PROF(LS_K_GEMM_GLOB, i, st);
-        GemmAux ax = aux_w(m, Wg, 2 * Co, Co);
-        ax.a_rowmax = rm_msg; ax.a_parts = rm_msg ? rm_msg_parts : 0;
-        rc = gemm_dispatch_ws(msg, Co, Wg, Co, nullptr, TG, 2 * Co, B * Nd * 3, 2 * Co, Co, 0, gws, st, ax);
-        if (rc == LS_OK) rc = gemm_dispatch_small(g, Co, Wg, Co, nullptr, G, 4 * Co, B * 3, 4 * Co, Co, 0, gws, st);
+        Gemm pt;   // per point: msg against the W_a / Wd W_a rows
+        pt.A = msg; pt.lda = Co; pt.W = Wg; pt.ldw = Co; pt.out = TG; pt.ldc = 2 * Co; pt.M = B * Nd * 3; pt.N = 2 * Co; pt.K = Co; pt.scratch = gws;
+        pt.aux = v.aux;
+        pt.aux.out_rowmax = nullptr; pt.aux.cs = nullptr; pt.aux.cs_rows = 0;
+        rc = gemm_run(pt, st);
+        Gemm pi;   // per instance: the mean rows against all four row groups -- a handful of tiles by construction
+        pi.A = g; pi.lda = Co; pi.W = Wg; pi.ldw = Co; pi.out = G; pi.ldc = 4 * Co; pi.M = B * 3; pi.N = 4 * Co; pi.K = Co; pi.scratch = gws; pi.latency = true;
+        if (rc == LS_OK) rc = gemm_run(pi, st);
     }
     if (rc != LS_OK) return rc;
     PROF(LS_K_VN_ACT, i, st);
@@ -410,9 +418,11 @@ static int encoder_tail(ls_model* m, const float* cur, int B, int NP, float* Tc,
     const float* W = m->blob;
     int rc;
     { PROF(LS_K_GEMM_TAIL, 0, st);
-      GemmAux ax = aux_w(m, W + d.off_convc, Cdp, Cl);
-      ax.a_rowmax = rm_cur; ax.a_parts = rm_parts;
-      rc = gemm_dispatch_ws(cur, Cl, W + d.off_convc, Cl, nullptr, Tc, Cdp, B * NP * 3, Cdp, Cl, 0, gws, st, ax); }
+      Gemm g;
+      g.A = cur; g.lda = Cl; g.W = W + d.off_convc; g.ldw = Cl; g.out = Tc; g.ldc = Cdp; g.M = B * NP * 3; g.N = Cdp; g.K = Cl; g.scratch = gws;
+      g.aux = aux_w(m, g.W, Cdp, Cl);
+      g.aux.a_rowmax = rm_cur; g.aux.a_parts = rm_parts;
+      rc = gemm_run(g, st); }
     if (rc != LS_OK) return rc;
     PROF(LS_K_TAIL, 0, st);
     return tail_launch(Tc, Cdp, B, NP, d.c_dim, W + d.off_inv_t, W + d.off_c_fc0_t, W + d.off_c_misc, d.neg_slope, d.scale_factor,
@@ -993,27 +1003,29 @@ static int sdf_forward(ls_model_t* m, const SdfBuffers& sb, const float* query, 
     { PROF(LS_K_SDF_AFFINE, 0, st);
       rc = sdf_affine_launch(query, row_inst, s, t, sb.A0, sb.b0, B, rows, w, w, 0, sb.h[0], xyz, st, rmc.emit(sdf_affine_rowmax_parts(w))); }
     if (rc != LS_OK) return rc;
+    // opt-in two-piece products (decoder throughput mode); a launch that may split K keeps the default product
+    const bool two_piece = m->sdf_bf16x2 && !sb.gws;
     int kin = w;
     for (int l = 1; l < nl - 1; ++l) {
         const int outw = dec_out(d, l);
         const float* cur = sb.h[l - 1];
         float* nxt = sb.h[l];
-        GemmAux ax = aux_w(m, W + d.off_dec_w[l], outw, kin);
-        rmc.operand(ax);
+        Gemm g;
+        g.A = cur; g.lda = w; g.W = W + d.off_dec_w[l]; g.ldw = kin; g.out = nxt; g.ldc = w; g.M = (int)rows; g.N = outw; g.K = kin; g.scratch = sb.gws;
+        if (two_piece) g.pieces = 2;   // (takes no operand ranges or planes)
+        else { g.aux = aux_w(m, g.W, outw, kin); rmc.operand(g.aux); }
         if (l == li) {
             { PROF(LS_K_GEMM_SDF, l, st);
-              rc = (m->sdf_bf16x2 && !sb.gws) ? gemm_dispatch_fast2(cur, w, W + d.off_dec_w[l], kin, nullptr, nxt, w, (int)rows, outw, kin, 0, st)
-                                              : gemm_dispatch_ws(cur, w, W + d.off_dec_w[l], kin, nullptr, nxt, w, (int)rows, outw, kin, 0, sb.gws, st, ax); }
+              rc = gemm_run(g, st); }
             if (rc != LS_OK) return rc;
             PROF(LS_K_SDF_AFFINE, l, st);
             rc = sdf_affine_launch(query, row_inst, s, t, sb.A4, sb.b4, B, rows, w, w, 1, nxt, xyz, st, rmc.emit(sdf_affine_rowmax_parts(w)));
         } else {
             PROF(LS_K_GEMM_SDF, l, st);
-            if (sb.gws && gemm_scratch_floats((int)rows, outw, kin) > 0) rmc.emit_none();   // a split-K launch writes no row maxima
-            else ax.out_rowmax = rmc.emit(gemm_rowmax_parts(outw));
-            rc = (m->sdf_bf16x2 && !sb.gws)
-                     ? gemm_dispatch_fast2(cur, w, W + d.off_dec_w[l], kin, W + d.off_dec_b[l], nxt, w, (int)rows, outw, kin, 1, st)
-                     : gemm_dispatch_ws(cur, w, W + d.off_dec_w[l], kin, W + d.off_dec_b[l], nxt, w, (int)rows, outw, kin, 1, sb.gws, st, ax);
+            g.bias = W + d.off_dec_b[l]; g.relu = 1;
+            if (!gemm_plan(gemm_traits(g)).writes_out_rowmax) rmc.emit_none();
+            else g.aux.out_rowmax = rmc.emit(gemm_rowmax_parts(outw));
+            rc = gemm_run(g, st);
         }
         if (rc != LS_OK) return rc;
         kin = outw;
@@ -1133,16 +1145,21 @@ int ls_sdf_backward(ls_model_t* m, const float* query, const float* z_so3, const
         // dh_{l-1} [rows, kin] = dz_l [rows, out_l] . W_l [out_l][kin]  ==  dz_l . (Wt_l [kin][out_l])^T
         // the ReLU derivative [h_{l-1} > 0] is applied in the GEMM's store when the launch does not split K (h and dh share the row stride w)
         const bool fuse_mask = !sb.gws && kin % 4 == 0;
-        GemmAux ax = aux_w(m, m->dec_wt + m->dec_wt_off[l], kin, outw[l]);
-        rmc.operand(ax);
+        Gemm g;
+        g.A = dz; g.lda = w; g.W = m->dec_wt + m->dec_wt_off[l]; g.ldw = outw[l]; g.out = other; g.ldc = w; g.M = (int)rows; g.N = kin; g.K = outw[l];
+        g.aux = aux_w(m, g.W, kin, outw[l]);
+        rmc.operand(g.aux);
         if (fuse_mask) {
-            ax.out_rowmax = rmc.emit(gemm_rowmax_parts(kin));   // after the mask
-            rc = gemm_dispatch_masked(dz, w, m->dec_wt + m->dec_wt_off[l], outw[l], other, w, (int)rows, kin, outw[l], sb.h[l - 1], m->sdf_bf16x2 ? 2 : 3, st, ax);
+            g.mask = sb.h[l - 1];
+            if (m->sdf_bf16x2) g.pieces = 2;
+            g.aux.out_rowmax = rmc.emit(gemm_rowmax_parts(kin));   // after the mask
+            rc = gemm_run(g, st);
         } else {
             // (an un-masked, possibly split-K launch: its maxima would still bound the masked values, but a split launch writes none)
-            if (sb.gws && gemm_scratch_floats((int)rows, kin, outw[l]) > 0) rmc.emit_none();
-            else ax.out_rowmax = rmc.emit(gemm_rowmax_parts(kin));
-            rc = gemm_dispatch_ws(dz, w, m->dec_wt + m->dec_wt_off[l], outw[l], nullptr, other, w, (int)rows, kin, outw[l], 0, sb.gws, st, ax);
+            g.scratch = sb.gws;
+            if (!gemm_plan(gemm_traits(g)).writes_out_rowmax) rmc.emit_none();
+            else g.aux.out_rowmax = rmc.emit(gemm_rowmax_parts(kin));
+            rc = gemm_run(g, st);
             if (rc != LS_OK) return rc;
             rc = relu_mask_launch(other, sb.h[l - 1], rows, kin, w, st);
         }

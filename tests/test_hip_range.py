@@ -340,3 +340,25 @@ def test_decoder_forward_on_activations_outside_the_f16_range():
     out = ops.gemm(A.to(_dev()), W.to(_dev()), b.to(_dev()), relu=True).cpu()
     ref = (A.double() @ W.double().T + b.double()).clamp(min=0)
     assert torch.isfinite(out).all() and relerr(out, ref) < 2e-6
+
+
+def test_gemm_outputs_are_the_recorded_ones_in_every_mode():
+    """The kernel choice and the arguments the plan hands the kernels (csrc/gemm_plan.h: kchunk, slab stride, per_n, tn -- a kernel trace does
+    not show them): the small public cases of tests/tools/record_gemm_launches.py, through ls_gemm_f32 / _ex / _planes, must reproduce the
+    SHA-256 of every output recorded in tests/golden/gemm_launches.json from the library before its dispatch code became the plan.  No
+    atomics on any path: equality is exact.  The default mode in this process, bf16x3 and fp32 in a child each (the mode is read once)."""
+    import importlib.util
+    import os
+    import subprocess
+    import sys
+    tool = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools", "record_gemm_launches.py")
+    spec = importlib.util.spec_from_file_location("record_gemm_launches", tool)
+    rec = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rec)
+    mine = os.environ.get("LS_GEMM_MODE") if os.environ.get("LS_GEMM_MODE") in rec.MODES[1:] else rec.MODES[0]
+    wrong = rec.check_hashes(mine)
+    assert not wrong, f"{len(wrong)} outputs differ from the record (recorded, now): {dict(list(wrong.items())[:4])}"
+    for mode in rec.MODES:
+        if mode != mine:
+            p = subprocess.run([sys.executable, tool, "--check-hashes", mode], env=dict(os.environ, LS_GEMM_MODE=mode), capture_output=True, text=True)
+            assert p.returncode == 0, (mode, p.stdout[-2000:], p.stderr[-2000:])
