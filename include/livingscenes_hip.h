@@ -61,8 +61,8 @@ typedef enum {
  * library reads no development switches from the environment any more; 104: option 4 retired with the staged attention path, refused like
  * any unknown option; 105: the mesh metrics ls_mesh_contains_f64 / ls_mesh_distance_f64 / ls_mesh_sample_f64; 106: ls_model_desc.dec_input and
  * off_dec_xyz_t, the invariant decoder_type "deepsdf"; 107: the ragged multi-mesh metrics ls_mesh_contains_batch_f64 /
- * ls_mesh_distance_batch_f64 / ls_mesh_sample_batch_f64; symbols added since -- ls_reg_metrics_batch, ls_mesh_cluster_f64 / ls_mesh_cluster_batch_f64 --
- * change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
+ * ls_mesh_distance_batch_f64 / ls_mesh_sample_batch_f64; symbols added since -- ls_reg_metrics_batch, ls_mesh_cluster_f64 / ls_mesh_cluster_batch_f64,
+ * ls_cloud_merge_f32 / ls_cloud_merge_batch_f32 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
  * binding compares it with the header it was written against and refuses a mismatch (livingscenes_amd/_lib.py: load). */
 #define LS_ABI_VERSION 107
 int ls_version(void);
@@ -642,6 +642,41 @@ size_t ls_mesh_cluster_batch_workspace_bytes(int M, long long nv_total, long lon
 int ls_mesh_cluster_batch_f64(int M, const double* vertices, long long nv_total, const long long* vert_off, const long long* faces, long long nf_total,
                               const long long* face_off, int f_target, int r_max, double* vertices_out, long long cap_v, long long* faces_out,
                               long long cap_f, long long* off_out, int* r_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Scene memory (csrc/cloudmerge.hip): the cloud an instance keeps, merged with a registered new observation of it on a voxel grid.  AN
+ * EXTENSION BEYOND THE RELEASED REFERENCE: its README promises "a joint optimization algorithm that facilitates the accumulation of point
+ * clouds originating from the same instance", but more_solver.py:246-299 (_solve_end2end) matches and registers one (reference, rescan)
+ * pair and stops -- nothing carries an instance's points from one rescan to the next.  This is the step in between: pose-aligned merging
+ * with a bound on the growth (one point per voxel).  Definition, per problem (tests/merge_oracle.py is the same text as NumPy):
+ *   inputs      A [a,3] fp32 the kept cloud, B [b,3] fp32 the new observation, g [3,4] fp32 (R | t) taking B into A's frame (NULL: the
+ *               identity, and then B is used bit for bit), h > 0 the voxel edge.  All DEVICE pointers except h.  a = 0 and b = 0 are allowed.
+ *   candidates  in this order: the rows of A as given, then the rows of B transformed, y_a = ((R_a0 x_0 + R_a1 x_1) + R_a2 x_2) + t_a with
+ *               every product and every sum rounded to fp32 in that order (no fma).
+ *   cell        inv = (float)1 / (float)h, formed once on the host; c_a = floorf(y_a * inv) clamped to [-2^30, 2^30] and cast to int32 -- a
+ *               multiplication, not a division, in the kernel.  h and inv must be finite and positive.
+ *   non-finite  a candidate with a non-finite coordinate (after the transform) has no cell and is never kept.
+ *   keep        candidate i is kept iff no candidate j < i of the same problem has the same cell triple.  So points already in the
+ *               memory win over new ones, a cloud that is itself the output of a merge at the same h is kept whole, and
+ *               merge(merge(A, B), {}) == merge(A, B).
+ * Outputs, sized BY THE CALLER at the upper bound a + b rows (no sizing pass, no host synchronisation, no allocation): out_pts [.,3] the
+ * kept candidates in ascending candidate order (rows of A: the input bits; rows of B: the transformed point), out_src int32 their
+ * candidate index in [0, a + b) (>= a: it came from B), out_off DEVICE long long [2] = {0, n_out}.  status_out (DEVICE int, nullable):
+ * LS_OK, or LS_ERR_WORKSPACE if the cell table overflowed -- it holds 2 (a + b) slots for at most a + b cells and its probe walk is bounded
+ * by the table, so this reports a defect, it never spins.  a + b <= INT_MAX.  Integer atomics only: the output does not depend on the run. */
+size_t ls_cloud_merge_workspace_bytes(long long a, long long b);
+int ls_cloud_merge_f32(const float* A, long long a, const float* B, long long b, const float* g, float voxel, float* out_pts, int32_t* out_src,
+                       long long* out_off, int* status_out, void* workspace, size_t workspace_bytes, void* stream);
+/* P >= 1 problems per call: A [a_total,3] and B [b_total,3] hold the problems' rows back to back, a_off / b_off (HOST int64, P + 1 entries)
+ * and voxel (HOST float, P entries) are checked here -- starting at 0, never decreasing, ending at the totals, h finite and > 0; the error
+ * names the problem -- and copied into the workspace on the stream; g [P,3,4] DEVICE or NULL (identity for every problem).  The outputs
+ * are packed problem after problem: out_off DEVICE long long [P+1], out_src local to its problem, status_out DEVICE int [P] (nullable).
+ * a_total + b_total <= INT_MAX.  Every output of every problem is BIT-IDENTICAL to ls_cloud_merge_f32 on that problem alone, in any batch
+ * composition and in any run, and the number of launches does not depend on P.  The workspace queries return 0 for sizes the op refuses. */
+size_t ls_cloud_merge_batch_workspace_bytes(int P, long long a_total, long long b_total);
+int ls_cloud_merge_batch_f32(int P, const float* A, long long a_total, const long long* a_off, const float* B, long long b_total,
+                             const long long* b_off, const float* g, const float* voxel, float* out_pts, int32_t* out_src, long long* out_off,
+                             int* status_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* The registration metrics of the relocalisation evaluation on P (reference instance, rescan instance, predicted pose, ground-truth pose)
  * tuples per call -- what eval_3rscan.py:384-401 / eval_flyingshape.py:136-148 compute pair by pair.  Pair p owns the rows

@@ -220,12 +220,6 @@ __device__ __forceinline__ void sort3(const int* __restrict__ k, int (&s)[3]) {
     s[0] = a; s[1] = b; s[2] = c;
 }
 
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 // the hash of a mesh: slot s is claimed by the first face that writes its (global) index to rep[s]; faces with the same sorted triple
 // find it by comparing against the claimant's keys (written by the kernel before), count themselves and leave the lowest index in mn[s].
 // At most min(nf, f_target) triples go into 2 min(nf, f_target) + 1 slots; the walk ends after T slots whatever happens.

@@ -57,13 +57,8 @@ enum { OFF_V = 0, OFF_F, OFF_P, OFF_AUX, OFF_AXIS, OFF_ARRAYS };
 
 // owner(off, M, i) (ls_ragged.h): the mesh m with off[m] <= i < off[m + 1]; meshes with an empty range are never the owner
 
-__host__ __device__ inline unsigned long long splitmix_mix(unsigned long long z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-// the sampler's key for a seed
-__host__ __device__ inline unsigned long long sample_key(unsigned long long seed) { return splitmix_mix(seed + 0x9E3779B97F4A7C15ull); }
+// the sampler's key for a seed (mix64: ls_common.h)
+__host__ __device__ inline unsigned long long sample_key(unsigned long long seed) { return mix64(seed + 0x9E3779B97F4A7C15ull); }
 
 struct MeshRef {
     const double* V;
@@ -500,7 +495,7 @@ __global__ __launch_bounds__(256) void fill_f64_kernel(double* __restrict__ out,
 // ------------------------------------------------------------------------------------------------ surface sampling (trimesh.sample.sample_surface)
 // uniform in [0, 1): the top 53 bits of splitmix64's output for counter j of the stream with key sample_key(seed)
 __device__ __forceinline__ double uniform(unsigned long long key, unsigned long long j) {
-    return (double)(splitmix_mix(key + (j + 1ull) * 0x9E3779B97F4A7C15ull) >> 11) * 0x1.0p-53;
+    return (double)(mix64(key + (j + 1ull) * 0x9E3779B97F4A7C15ull) >> 11) * 0x1.0p-53;
 }
 
 // trimesh Trimesh.area_faces: |cross(v1 - v0, v2 - v0)| / 2, components written as np.cross does

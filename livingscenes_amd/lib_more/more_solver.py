@@ -259,6 +259,28 @@ class More_Solver:
         improved = improved.bool()
         return {k: code[k].detach() for k in ("z_inv", "z_so3", "s", "t")}, improved
 
+    def _accumulate_batch(self, mem_pcs, new_pcs, T, voxel=None):
+        """Scene memory, an extension beyond the released reference (its README promises "the accumulation of point clouds originating from
+        the same instance"; more_solver.py:246-299 stops after the registration): merge P kept instance clouds mem_pcs[p] [a_p,3] (in
+        the memory's frame) with the matched observations new_pcs[p] [b_p,3] in ONE ragged call (ops.cloud_merge_batch, csrc/cloudmerge.hip).
+        T [P,4,4] or [P,3,4] is the registration exactly as _solve_pairwise_registration* / Rt_to_SE3 return it: it maps memory -> rescan, so
+        the operator receives inverse(T), the inverse _solve_end2end forms for _transform_latent (T None: the observations are in the
+        memory's frame already and are used bit for bit).  A point is kept iff no earlier point of (memory rows, then transformed
+        observation rows) lies in its voxel, so what the memory holds always wins and an instance seen any number of times stays at one
+        point per voxel.  voxel: the edge in metres, default cfg['accumulate']['voxel_size'], else 0.01 -- AN UNMEASURED CHOICE: roughly a
+        third of the point spacing of a 1 024-point, 1 m object, so a sampled cloud passes nearly whole while repeated observations of a
+        surface do not pile up.  -> list of P merged clouds [n_p,3]."""
+        if voxel is None:
+            voxel = self.cfg.get("accumulate", {}).get("voxel_size", 0.01)
+        if len(mem_pcs) != len(new_pcs):
+            raise ValueError(f"{len(mem_pcs)} memory clouds for {len(new_pcs)} observations")
+        g = None
+        if T is not None:
+            if T.dim() != 3 or T.shape[0] != len(mem_pcs) or T.shape[1] not in (3, 4) or T.shape[2] != 4:
+                raise ValueError(f"T must be [P,4,4] or [P,3,4] with P = {len(mem_pcs)}, got {tuple(T.shape)}")
+            g = inverse(T.detach().float()).contiguous()
+        return [pts for pts, _ in ops.cloud_merge_batch([p.detach() for p in mem_pcs], [p.detach() for p in new_pcs], g=g, voxel=voxel)]
+
     def _mesh_from_latent(self, latent_code):
         """more_solver.py:37-58: mesh of the canonical shape (t = 0, s = 1), then scaled and moved to the instance pose."""
         if self.mesh_extractor is None:
@@ -418,6 +440,115 @@ def solve_end2end_batch(solver, pairs, mesh=False, optim=False, sharded=False, o
     for out in outs:
         del out["_res_codes"]
     return outs
+
+
+def sequence_plan(n_mem, matches0, n_new=None, n_new_points=None):
+    """The index bookkeeping of one solve_sequence step, as a pure function: matches0[i] is the rescan instance matched to memory slot i
+    (-1: none), as _solve_object_matching(memory codes, rescan codes) returns it; n_new = instances in the rescan (None: unknown).
+      pairs         [(memory slot, rescan instance)] in slot order: pair k is problem k of the registration and of the merge
+      updated       the slots a match updates (their cloud goes through the merge); the others keep cloud and code
+      reencode      the updated slots whose cloud changed -- n_new_points[k] > 0 for pair k (None: not known yet, every updated slot)
+      unmatched_new the rescan instances no slot was matched to (None without n_new): their frame relative to the memory is unknown, so
+                    they are reported and left out"""
+    m0 = [int(j) for j in matches0]
+    if len(m0) != n_mem:
+        raise ValueError(f"{len(m0)} matches for {n_mem} memory slots")
+    pairs = [(i, j) for i, j in enumerate(m0) if j >= 0]
+    taken = [j for _, j in pairs]
+    if len(set(taken)) != len(taken):
+        raise ValueError(f"a rescan instance is matched to more than one memory slot: {m0}")
+    if n_new is not None and any(j >= n_new for j in taken):
+        raise ValueError(f"a match names a rescan instance >= {n_new}: {m0}")
+    if n_new_points is not None and len(n_new_points) != len(pairs):
+        raise ValueError(f"{len(n_new_points)} point counts for {len(pairs)} pairs")
+    updated = [i for i, _ in pairs]
+    return {"pairs": pairs, "updated": updated,
+            "reencode": updated if n_new_points is None else [i for i, k in zip(updated, n_new_points) if int(k) > 0],
+            "unmatched_new": None if n_new is None else [j for j in range(n_new) if j not in set(taken)]}
+
+
+_CODE_KEYS = ("z_so3", "z_inv", "s", "t")
+
+
+def _encode_clouds(model, clouds):
+    """encode_fps of a list of clouds [n_i,3]: padded to the longest, one ragged FPS launch, one encoder batch (as solve_end2end_batch pads)"""
+    dev = clouds[0].device
+    nmax = max(c.shape[0] for c in clouds)
+    buf = torch.zeros(len(clouds), 3, nmax, device=dev)
+    mask = torch.zeros(len(clouds), 1, nmax, dtype=torch.bool, device=dev)
+    for i, c in enumerate(clouds):
+        buf[i, :, : c.shape[0]] = c.T
+        mask[i, :, : c.shape[0]] = True
+    return model.encode_fps(buf, mask)
+
+
+def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, optimize_codes=False):
+    """A reference scan followed by SEVERAL rescans, with a memory that carries every instance's points from one rescan to the next -- an
+    extension beyond the released reference (more_solver.py:246-299 solves one (reference, rescan) pair and drops the rescan's points).
+    ref and every rescan: {'pc' [n,3,Nmax], 'pc_mask'} as _solve_end2end takes them.
+
+    Memory: one cloud per instance of ``ref`` in the reference frame plus its code.  The clouds are _scene_clouds(ref) passed once through
+    the merge against an empty observation, so the memory is one point per voxel from the first step on (a merged cloud is kept whole by
+    every later merge at the same voxel); the codes are encode_fps(ref).  The number of slots never changes.
+    Per rescan, in order: encode it (one ragged FPS, one encoder batch); _solve_object_matching(memory codes, rescan codes); ONE
+    _solve_pairwise_registration(_optim)_batch call over the matched pairs; ONE _accumulate_batch call; the slots whose cloud grew are
+    re-encoded (one ragged FPS, one encoder batch: their code is encode_fps of the merged cloud); optimize_codes: ONE _optimize_code_batch
+    call on those slots, an instance keeping the optimised code where its loss improved (the reference's best_code rule).  Rescan
+    instances without a match are left out of the memory -- their frame relative to the reference is unknown -- and reported; memory
+    slots without a match stay as they are.
+
+    -> (steps, memory).  steps[k]: the dict of _solve_end2end for rescan k against the memory as it was BEFORE the step (ref_pc_lst,
+    rescan_pc_lst, matches, registration, codes = the rescan's codes moved to the reference frame, mesh_lst = None per slot: meshes are
+    made of the final memory) plus merged_sizes [n] (points per slot after the step), n_new_points [n] (points the step added) and
+    unmatched_rescan (rescan instance indices).  memory: {'clouds': list of [n_i,3], 'codes': code dict of n rows, 'meshes':
+    _mesh_from_latent_batch(codes) if mesh else None}.  voxel: see More_Solver._accumulate_batch."""
+    model = solver.model
+    n_in = solver.cfg["shape_priors"]["n_input_point"]
+    raw = _scene_clouds(ref)
+    n = len(raw)
+    mem = solver._accumulate_batch(raw, [c[:0] for c in raw], None, voxel=voxel)
+    for i, c in enumerate(mem):
+        if c.shape[0] < n_in:
+            raise ValueError(f"solve_sequence: instance {i} keeps {c.shape[0]} of {raw[i].shape[0]} points at this voxel size, fewer than the "
+                             f"{n_in} the encoder samples: the voxel is too coarse for this cloud")
+    ref_codes = model.encode_fps(ref["pc"], ref["pc_mask"])
+    codes = {k: ref_codes[k].detach().clone() for k in _CODE_KEYS}
+    steps = []
+    for rescan in rescans:
+        res_full = _scene_clouds(rescan)
+        res_codes = model.encode_fps(rescan["pc"], rescan["pc_mask"])
+        m0 = solver._solve_object_matching(codes, res_codes, "sequential")["matches0"]
+        plan = sequence_plan(n, m0.tolist(), len(res_full))
+        pairs = plan["pairs"]
+        out = {"ref_pc_lst": list(mem), "rescan_pc_lst": res_full, "matches": m0, "registration": [None] * n, "codes": [None] * n,
+               "mesh_lst": [None] * n, "n_new_points": [0] * n, "unmatched_rescan": plan["unmatched_new"]}
+        if pairs:
+            src, tgt = [mem[i] for i, _ in pairs], [res_full[j] for _, j in pairs]
+            R, t = solver._solve_pairwise_registration_optim_batch(src, tgt) if optim else solver._solve_pairwise_registration_batch(src, tgt)
+            T = Rt_to_SE3(R, t)
+            merged = solver._accumulate_batch(src, tgt, T, voxel=voxel)
+            grew = [c.shape[0] - a.shape[0] for c, a in zip(merged, src)]     # the memory's rows are kept whole: the rest came from the rescan
+            for k, (i, j) in enumerate(pairs):
+                out["registration"][i] = T[k:k + 1]
+                cur = {key: res_codes[key][j][None] for key in _CODE_KEYS}
+                out["codes"][i] = solver._transform_latent(cur, inverse(T[k:k + 1]))
+                out["n_new_points"][i] = grew[k]
+                mem[i] = merged[k]
+            again = sequence_plan(n, m0.tolist(), len(res_full), grew)["reencode"]
+            if again:
+                new = _encode_clouds(model, [mem[i] for i in again])
+                new = {k: new[k].detach().clone() for k in _CODE_KEYS}
+                if optimize_codes:
+                    enc = {k: v.clone() for k, v in new.items()}
+                    opt, improved = solver._optimize_code_batch(new, [mem[i] for i in again])
+                    new = {k: torch.where(improved.view(-1, *([1] * (enc[k].dim() - 1))), opt[k], enc[k]) for k in _CODE_KEYS}
+                rows = torch.tensor(again, device=codes["z_inv"].device)
+                for k in _CODE_KEYS:
+                    codes[k][rows] = new[k].to(codes[k].dtype)
+        out["merged_sizes"] = [c.shape[0] for c in mem]
+        steps.append(out)
+    memory = {"clouds": mem, "codes": codes, "meshes": solver._mesh_from_latent_batch(codes) if mesh else None}
+    return steps, memory
 
 
 def _se3_exp(xi):  # host twin of the retraction in csrc/optim.hip (tests compare both with torch.matrix_exp)

@@ -811,3 +811,78 @@ def mesh_sample_batch(meshes, counts, seeds=None):
     call(dev, "ls_mesh_sample_batch_f64", M, ptr(V), V.shape[0], _hptr(vo), ptr(F), F.shape[0], _hptr(fo), n, _hptr(co), ptr(sd), ptr(pts),
          ptr(face), ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev))
     return list(zip(torch.split(pts, counts), torch.split(face, counts)))
+
+
+# ------------------------------------------------------------------------------------------------ scene memory (csrc/cloudmerge.hip)
+def _merge_cloud(x, what):
+    if not torch.is_tensor(x) or x.device.type != "cuda" or x.dtype != torch.float32:
+        kind = f"{x.device.type} {x.dtype}" if torch.is_tensor(x) else type(x).__name__
+        raise _lib.LsError(f"cloud_merge: {what} must be an fp32 HIP (cuda) tensor, got {kind}: the MI355X path has no CPU fallback and converts nothing")
+    if x.dim() != 2 or x.shape[1] != 3:
+        raise ValueError(f"cloud_merge: {what} is [n, 3], got {tuple(x.shape)}")
+    return x.contiguous()
+
+
+def cloud_merge_batch(As, Bs, g=None, *, voxel, packed=False):
+    """ls_cloud_merge_batch_f32: As / Bs = lists of P kept clouds [a_p,3] and new observations [b_p,3] (fp32 HIP tensors, empty ones allowed),
+    g [P,3,4] or [P,4,4] taking B_p into A_p's frame (None: identity, B bit for bit), voxel = one edge or P edges.  Candidates are A_p's rows then
+    B_p's transformed rows; one is kept iff no earlier candidate of its problem lies in the same voxel (include/livingscenes_hip.h)
+    -> list of P (pts [n_p,3], src [n_p] int32: the candidate index, >= a_p: from B), views of one packed tensor; packed=True: (pts, src, off)
+    with off the host int64 offsets [P+1].  One call, one host read (the offsets), whatever P."""
+    As, Bs = [_merge_cloud(x, "A") for x in As], [_merge_cloud(x, "B") for x in Bs]
+    P = len(As)
+    if len(Bs) != P:
+        raise ValueError(f"cloud_merge: {P} kept clouds for {len(Bs)} new observations")
+    if P == 0:
+        raise ValueError("cloud_merge: no problem given")
+    dev = As[0].device
+    vox = np.full(P, float(voxel), dtype=np.float32) if np.ndim(voxel) == 0 else np.ascontiguousarray(voxel, dtype=np.float32).reshape(-1)
+    if vox.shape[0] != P:
+        raise ValueError(f"cloud_merge: {vox.shape[0]} voxel edges for {P} problems")
+    if g is not None:
+        if not torch.is_tensor(g) or g.dim() != 3 or g.shape[0] != P or g.shape[1] not in (3, 4) or g.shape[2] != 4:
+            raise ValueError(f"cloud_merge: g must be [P,3,4] or [P,4,4] with P = {P}, got {tuple(g.shape) if torch.is_tensor(g) else type(g).__name__}")
+        g = _f32(g.to(dev)[:, :3, :])
+    A = torch.cat(As, 0) if P > 1 else As[0]
+    B = torch.cat(Bs, 0) if P > 1 else Bs[0]
+    ao, bo = _offsets([x.shape[0] for x in As]), _offsets([x.shape[0] for x in Bs])
+    n = A.shape[0] + B.shape[0]
+    pts = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    src = torch.empty(n, dtype=torch.int32, device=dev)
+    meta = torch.empty(P + 1 + (P + 1) // 2, dtype=torch.int64, device=dev)   # out_off [P+1] int64, then status [P] int32: one host read
+    status = ctypes.c_void_p(meta.data_ptr() + (P + 1) * 8)
+    ws = _scratch(load().ls_cloud_merge_batch_workspace_bytes(P, A.shape[0], B.shape[0]), dev)
+    call(dev, "ls_cloud_merge_batch_f32", P, ptr(A), A.shape[0], _hptr(ao), ptr(B), B.shape[0], _hptr(bo), ptr(g), _hptr(vox), ptr(pts), ptr(src),
+         ptr(meta), status, ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev))
+    host = meta.cpu().numpy()
+    off, st = host[:P + 1], host[P + 1:].view(np.int32)[:P]
+    if st.any():
+        raise _lib.LsError(f"cloud_merge: problem {int(np.flatnonzero(st)[0])}: status {int(st[np.flatnonzero(st)[0]])} (the cell table overflowed: a defect)")
+    n_out = int(off[P])
+    if packed:
+        return pts[:n_out], src[:n_out], off
+    sizes = np.diff(off).tolist()
+    return list(zip(torch.split(pts[:n_out], sizes), torch.split(src[:n_out], sizes)))
+
+
+def cloud_merge(A, B, g=None, *, voxel):
+    """ls_cloud_merge_f32: the kept cloud A [a,3] and the new observation B [b,3] (fp32 HIP tensors), g [3,4] or [4,4] taking B into A's
+    frame (None: identity) -> (pts [n,3], src [n] int32): A's rows, then B's transformed rows, each kept iff no earlier one lies in the same
+    voxel of edge `voxel`.  Bit-identical to the same problem inside any cloud_merge_batch."""
+    A, B = _merge_cloud(A, "A"), _merge_cloud(B, "B")
+    dev = A.device
+    if g is not None:
+        if not torch.is_tensor(g) or tuple(g.shape) not in ((3, 4), (4, 4)):
+            raise ValueError(f"cloud_merge: g must be [3,4] or [4,4], got {tuple(g.shape) if torch.is_tensor(g) else type(g).__name__}")
+        g = _f32(g.to(dev)[:3, :])
+    n = A.shape[0] + B.shape[0]
+    pts = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    src = torch.empty(n, dtype=torch.int32, device=dev)
+    meta = torch.empty(3, dtype=torch.int64, device=dev)                      # out_off [2], then the status
+    ws = _scratch(load().ls_cloud_merge_workspace_bytes(A.shape[0], B.shape[0]), dev)
+    call(dev, "ls_cloud_merge_f32", ptr(A), A.shape[0], ptr(B), B.shape[0], ptr(g), float(voxel), ptr(pts), ptr(src), ptr(meta),
+         ctypes.c_void_p(meta.data_ptr() + 16), ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev))
+    host = meta.cpu().numpy()
+    if host[2:].view(np.int32)[0] != 0:
+        raise _lib.LsError(f"cloud_merge: status {int(host[2:].view(np.int32)[0])} (the cell table overflowed: a defect)")
+    return pts[:int(host[1])], src[:int(host[1])]
