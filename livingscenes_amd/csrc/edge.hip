@@ -771,42 +771,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void e
     }
 }
 
-// can this layer shape take the fused kernel?
-bool edge_attn_fq_supported(int Co, int Cin) { return (Co == 64 && (Cin == 32 || Cin == 64)) || (Co == 128 && Cin == 64); }
-bool edge_attn_fq_fits(int B, int Ns, int ldt) {   // the table is addressed by 32-bit byte offsets formed with a 24-bit multiply
-    return (unsigned long long)B * Ns * 3ull * ldt * 4ull < (1ull << 32) && (unsigned long long)B * Ns < (1ull << 24) && 3ull * ldt * 4ull < (1ull << 24) &&
-           Ns < 65536;      // (+ neighbour indices packed two per register)
-}
-// points per workgroup of the fused kernel = rows of `colsum` per Nd / this many points (0: shape not served)
-int edge_attn_fq_points_per_wg(int Co) { return Co == 64 ? 16 : Co == 128 ? 8 : 0; }
-int edge_attn_fq_launch(const float* T, int ldt, const float* cur, int Cin, const void* wq_planes, const int32_t* knn, const int32_t* dst_rows, int B,
-                        int Nd, int Ns, int Co, int head_c, float neg_slope, float* out, hipStream_t st, float* rowmax, float* colsum) {
-    LS_REQUIRE(!colsum || (edge_attn_fq_points_per_wg(Co) > 0 && Nd % edge_attn_fq_points_per_wg(Co) == 0), "edge_attn_fq: column sums need Nd %% %d == 0 (Nd=%d)",
-               edge_attn_fq_points_per_wg(Co), Nd);
-    LS_REQUIRE(head_c == 16 && edge_attn_fq_supported(Co, Cin) && ldt % 4 == 0 && wq_planes, "edge_attn_fq: unsupported shape (Co=%d Cin=%d ldt=%d)", Co, Cin, ldt);
-    LS_REQUIRE(edge_attn_fq_fits(B, Ns, ldt), "edge_attn_fq: the table is addressed by 32-bit byte offsets (B=%d Ns=%d ldt=%d)", B, Ns, ldt);
-    const float isd = 1.0f / sqrtf(3.0f * head_c), oms = 1.0f - neg_slope;
-    const int total = B * Nd;
-#define LS_FQ(LPP, CIN) hipLaunchKernelGGL((edge_attn_fq_kernel<LPP, CIN>), dim3(cdiv(total, 4 * (64 / LPP))), dim3(256), 0, st, T, ldt, cur, (const uint4*)wq_planes, knn, dst_rows, Nd, Ns, oms, isd, out, total, rowmax, colsum)
-    if (Co == 64 && Cin == 32) LS_FQ(16, 32);
-    else if (Co == 64) LS_FQ(16, 64);
-    else LS_FQ(32, 64);
-#undef LS_FQ
-    LS_LAUNCH_CHECK();
-    return LS_OK;
-}
-
-template <int LPP, int NCH>
-static int launch_attn_v4(const float* T, int ldt, const float* Tq, int ldq, int NQ, int qvr, const int32_t* knn,
-                          const int32_t* dst_rows, int B, int Nd, int Ns, int Co, float neg_slope, float isd, float* out,
-                          hipStream_t st, float* rowmax, float* colsum = nullptr) {
-    const int total = B * Nd, ppb = 4 * (64 / LPP);
-    hipLaunchKernelGGL((edge_attn_v4_kernel<LPP, NCH>), dim3(cdiv(total, ppb)), dim3(256), 0, st, T, ldt, Tq, ldq, NQ, qvr, knn,
-                       dst_rows, Nd, Ns, Co, 1.0f - neg_slope, isd, out, total, rowmax, colsum);
-    LS_LAUNCH_CHECK();
-    return LS_OK;
-}
-
 int edge_l0_launch(const float* pts, const int32_t* knn, const float* w0, int B, int N, int Co, float neg_slope, float* out,
                    hipStream_t st) {
     const int total = B * N;
@@ -815,47 +779,41 @@ int edge_l0_launch(const float* pts, const int32_t* knn, const float* w0, int B,
     return LS_OK;
 }
 
-int edge_pool_launch(const float* T, int ldt, const float* Tq, int ldq, int NQ, int qvr, const int32_t* knn,
-                     const int32_t* dst_rows, int B, int Nd, int Ns, int Co, float neg_slope, float* out, hipStream_t st) {
-    const int total = B * Nd;
-    const bool off32 = edge_attn_fq_fits(B, Ns, ldt);
-    if (off32 && ldt % 4 == 0 && ldq % 4 == 0 && (Co == 32 || Co == 64)) {   // (the float4 kernel addresses the table by 32-bit byte offsets)
-        if (Co == 32)
-            hipLaunchKernelGGL((edge_pool_v4_kernel<8>), dim3(cdiv(total, 32)), dim3(256), 0, st, T, ldt, Tq, ldq, NQ, qvr, knn, dst_rows, Nd, Ns, 1.0f - neg_slope, out, total);
-        else
-            hipLaunchKernelGGL((edge_pool_v4_kernel<16>), dim3(cdiv(total, 16)), dim3(256), 0, st, T, ldt, Tq, ldq, NQ, qvr, knn, dst_rows, Nd, Ns, 1.0f - neg_slope, out, total);
-        LS_LAUNCH_CHECK();
-        return LS_OK;
+// gather + VN activation + mean-pool | attention of one layer over its tables: launches what the plan names (edge_plan.h)
+int edge_run(const Edge& e, const EdgePlan& p, hipStream_t st) {
+    if (p.kernel == EdgeKernel::FT_128 || p.kernel == EdgeKernel::FT_256) return edge_ft_attn_launch(e, p, st);
+    const float *T = e.T, *Tq = e.T + p.q_off;
+    const int total = e.B * e.Nd, Nd = e.Nd, Ns = e.Ns, Co = e.Co;
+    const float oms = 1.0f - e.neg_slope, isd = 1.0f / sqrtf(3.0f * e.head_c);
+    float* rowmax = p.rowmax_parts ? e.rowmax : nullptr;
+    float* colsum = p.cs_rows ? e.colsum : nullptr;
+    const dim3 grid(p.grid), block(p.block);
+    LS_REQUIRE(p.kernel < EdgeKernel::ATTN || (e.head_c == 16 && Co % 16 == 0 && p.lds <= 64 * 1024),
+               "edge_attn: head width must be 16 and divide Co, Co at most 512 (head_c=%d Co=%d)", e.head_c, Co);
+#define LS_POOL(K) hipLaunchKernelGGL(K, grid, block, 0, st, T, p.ldp, Tq, p.ldq, p.NQ, p.qvr, e.knn, e.dst_rows, Nd, Ns, oms, e.out, total)
+#define LS_V4(LPP, NCH) hipLaunchKernelGGL((edge_attn_v4_kernel<LPP, NCH>), grid, block, 0, st, T, p.ldp, Tq, p.ldq, p.NQ, p.qvr, e.knn, e.dst_rows, Nd, Ns, Co, oms, isd, e.out, total, rowmax, colsum)
+#define LS_FQ(LPP, CIN) hipLaunchKernelGGL((edge_attn_fq_kernel<LPP, CIN>), grid, block, 0, st, T, p.ldp, e.cur, (const uint4*)e.planes, e.knn, e.dst_rows, Nd, Ns, oms, isd, e.out, total, rowmax, colsum)
+    switch (p.kernel) {   // (templates in the order they have always been instantiated: it is the order of the kernels in the code object)
+    case EdgeKernel::ATTN_FQ_16_32: LS_FQ(16, 32); break;
+    case EdgeKernel::ATTN_FQ_16_64: LS_FQ(16, 64); break;
+    case EdgeKernel::ATTN_FQ_32_64: LS_FQ(32, 64); break;
+    case EdgeKernel::POOL_V4_8: LS_POOL(edge_pool_v4_kernel<8>); break;
+    case EdgeKernel::POOL_V4_16: LS_POOL(edge_pool_v4_kernel<16>); break;
+    case EdgeKernel::POOL:
+        hipLaunchKernelGGL(edge_pool_kernel, grid, block, 0, st, T, p.ldp, Tq, p.ldq, p.NQ, p.qvr, e.knn, e.dst_rows, Nd, Ns, Co, oms, e.out, total);
+        break;
+    case EdgeKernel::ATTN_V4_16: LS_V4(16, 1); break;
+    case EdgeKernel::ATTN_V4_32: LS_V4(32, 1); break;
+    case EdgeKernel::ATTN_V4_64: LS_V4(64, 1); break;
+    case EdgeKernel::ATTN_V4_64X2: LS_V4(64, 2); break;
+    case EdgeKernel::ATTN:
+        hipLaunchKernelGGL(edge_attn_kernel, grid, block, p.lds, st, T, p.ldp, Tq, p.ldq, p.NQ, p.qvr, e.knn, e.dst_rows, Nd, Ns, Co, oms, isd, e.out, total);
+        break;
+    default: LS_REQUIRE(false, "edge_run: the plan names no kernel of edge.hip");
     }
-    const int ppb = (Co <= 32) ? 8 : 4;
-    hipLaunchKernelGGL(edge_pool_kernel, dim3(cdiv(total, ppb)), dim3(256), 0, st, T, ldt, Tq, ldq, NQ, qvr, knn, dst_rows, Nd, Ns,
-                       Co, 1.0f - neg_slope, out, total);
-    LS_LAUNCH_CHECK();
-    return LS_OK;
-}
-
-// does edge_attn_launch write the row maxima of its output for this shape? (the float4-lane kernels do, the generic one does not)
-bool edge_attn_emits_rowmax(int Co, int ldt, int ldq) { return ldt % 4 == 0 && ldq % 4 == 0 && (Co == 64 || Co == 128 || Co == 256 || Co == 512); }
-int edge_attn_launch(const float* T, int ldt, const float* Tq, int ldq, int NQ, int qvr, const int32_t* knn,
-                     const int32_t* dst_rows, int B, int Nd, int Ns, int Co, int head_c, float neg_slope, float* out,
-                     hipStream_t st, float* rowmax, float* colsum) {
-    // colsum (nullable): partial column sums, one row per edge_attn_fq_points_per_wg(Co) points (Co = 64 / 128 with 16-byte-aligned tables only)
-    LS_REQUIRE(!colsum || (ldt % 4 == 0 && ldq % 4 == 0 && edge_attn_fq_points_per_wg(Co) > 0 && Nd % edge_attn_fq_points_per_wg(Co) == 0),
-               "edge_attn: no column sums for this shape (Co=%d Nd=%d)", Co, Nd);
-    LS_REQUIRE(!rowmax || edge_attn_emits_rowmax(Co, ldt, ldq), "edge_attn: no row maxima from the generic kernel (Co=%d)", Co);
-    LS_REQUIRE(head_c == 16 && Co % 16 == 0, "edge_attn: head width must be 16 and divide Co (head_c=%d Co=%d)", head_c, Co);
-    const float isd = 1.0f / sqrtf(3.0f * head_c);
-    if (ldt % 4 == 0 && ldq % 4 == 0) {
-        if (Co == 64) return launch_attn_v4<16, 1>(T, ldt, Tq, ldq, NQ, qvr, knn, dst_rows, B, Nd, Ns, Co, neg_slope, isd, out, st, rowmax, colsum);
-        if (Co == 128) return launch_attn_v4<32, 1>(T, ldt, Tq, ldq, NQ, qvr, knn, dst_rows, B, Nd, Ns, Co, neg_slope, isd, out, st, rowmax, colsum);
-        if (Co == 256) return launch_attn_v4<64, 1>(T, ldt, Tq, ldq, NQ, qvr, knn, dst_rows, B, Nd, Ns, Co, neg_slope, isd, out, st, rowmax);
-        if (Co == 512) return launch_attn_v4<64, 2>(T, ldt, Tq, ldq, NQ, qvr, knn, dst_rows, B, Nd, Ns, Co, neg_slope, isd, out, st, rowmax);
-    }
-    const int total = B * Nd;
-    const size_t smem = (size_t)4 * (3 * Co + 2 * (Co / 16) * EK) * sizeof(float);
-    LS_REQUIRE(smem <= 64 * 1024, "edge_attn: Co=%d too wide", Co);
-    hipLaunchKernelGGL(edge_attn_kernel, dim3(cdiv(total, 4)), dim3(256), smem, st, T, ldt, Tq, ldq, NQ, qvr, knn, dst_rows, Nd, Ns,
-                       Co, 1.0f - neg_slope, isd, out, total);
+#undef LS_POOL
+#undef LS_V4
+#undef LS_FQ
     LS_LAUNCH_CHECK();
     return LS_OK;
 }

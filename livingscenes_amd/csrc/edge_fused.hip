@@ -565,78 +565,54 @@ __global__ __launch_bounds__(256, 2) void edge_ft_v_kernel(const uint4* __restri
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-bool edge_ft_supported(int Co, int Cin, int Ns, int Nd, int head_c, bool has_rows) {
-    if (head_c != 16 || Nd != FND) return false;
-    if (Cin == 128 && Ns == 128 && has_rows && Co % 16 == 0) return true;         // layer 5 of the released schedule
-    if (Cin == 256 && Ns == 32 && !has_rows && Co % 32 == 0) return true;         // layer 6
-    return false;
+// scratch of one fused layer call (inside the layer's table area; sized and placed by edge_plan.h: edge_ft_layout)
+static_assert(FND == EDGE_FT_ND && FK == EDGE_K, "edge_plan.h sizes the scratch for these");
+struct FtScratch { uint4* a_p; int* ae_p; uint4* a_q; int* ae_q; float* scores; float* sskp; float* ssqp; float* invk; float* invq; };
+static FtScratch ft_scratch(void* scratch, const EdgeFtLayout& l) {
+    char* b = (char*)scratch;
+    return FtScratch{(uint4*)(b + l.a_p), (int*)(b + l.ae_p), (uint4*)(b + l.a_q), (int*)(b + l.ae_q), (float*)(b + l.scores), (float*)(b + l.sskp),
+                     (float*)(b + l.ssqp), (float*)(b + l.invk), (float*)(b + l.invq)};
 }
-int edge_ft_heads_per_group(int Cin) { return Cin == 256 ? 2 : 1; }
-// scratch of one fused layer call (inside the layer's table area): A planes (rows of Cin / 4 uint4) + exponents (source rows, and the selected
-// destination rows when the layer down-samples), raw scores, partial norms, the summed norms (invk, invq).  A null `scratch`: a sizing pass.
-struct FtScratch { uint4* a_p; int* ae_p; uint4* a_q; int* ae_q; float* scores; float* sskp; float* ssqp; float* invk; float* invq; size_t bytes; };
-static FtScratch ft_layout(void* scratch, int B, int Ns, int Nd, int Cin, int Co, bool has_rows) {
-    const size_t rp = (size_t)B * Ns * 3, rq = (size_t)B * Nd * 3, H = Co / 16;
-    Arena a(scratch);
-    FtScratch s;
-    s.a_p = a.take<uint4>(rp * Cin / 4);
-    s.ae_p = a.take<int>(rp);
-    s.a_q = has_rows ? a.take<uint4>(rq * Cin / 4) : s.a_p;
-    s.ae_q = has_rows ? a.take<int>(rq) : s.ae_p;
-    s.scores = a.take<float>((size_t)B * H * Nd * FK);
-    s.sskp = a.take<float>((size_t)B * H * Nd * FK);
-    s.ssqp = a.take<float>((size_t)B * H * Nd);
-    s.invk = a.take<float>((size_t)B * Nd * FK);
-    s.invq = a.take<float>((size_t)B * Nd);
-    s.bytes = a.bytes();
-    return s;
-}
-size_t edge_ft_scratch_bytes(int B, int Ns, int Nd, int Cin, int Co, bool has_rows) { return ft_layout(nullptr, B, Ns, Nd, Cin, Co, has_rows).bytes; }
 // the layer's operand image (launched where the table GEMM was: it depends on the features only, not on the graph)
-int edge_ft_prep_launch(const float* cur, const int32_t* dst_rows, int B, int Ns, int Nd, int Cin, int Co, void* scratch, hipStream_t st) {
-    const bool has_rows = dst_rows != nullptr;
-    LS_REQUIRE(edge_ft_supported(Co, Cin, Ns, Nd, 16, has_rows), "edge_ft_prep: unsupported shape (Co=%d Cin=%d Ns=%d Nd=%d)", Co, Cin, Ns, Nd);
-    const FtScratch s = ft_layout(scratch, B, Ns, Nd, Cin, Co, has_rows);
-    if (Cin == 128) {
-        hipLaunchKernelGGL(edge_ft_prep_a_kernel<8>, dim3(B * Ns * 3 / 32), dim3(256), 0, st, cur, (const int32_t*)nullptr, Ns, Nd, s.a_p, s.ae_p);
+int edge_ft_prep_launch(const float* cur, const int32_t* dst_rows, int Ns, int Nd, void* scratch, const EdgePlan& p, hipStream_t st) {
+    const bool l5 = p.kernel == EdgeKernel::FT_128;
+    LS_REQUIRE(l5 || p.kernel == EdgeKernel::FT_256, "edge_ft_prep: the plan names no kernel of edge_fused.hip");
+    const FtScratch s = ft_scratch(scratch, p.ft);
+    if (l5) {
+        hipLaunchKernelGGL(edge_ft_prep_a_kernel<8>, dim3(p.prep_grid[0]), dim3(256), 0, st, cur, (const int32_t*)nullptr, Ns, Nd, s.a_p, s.ae_p);
         LS_LAUNCH_CHECK();
-        hipLaunchKernelGGL(edge_ft_prep_a_kernel<8>, dim3(B * Nd * 3 / 32), dim3(256), 0, st, cur, dst_rows, Ns, Nd, s.a_q, s.ae_q);
+        hipLaunchKernelGGL(edge_ft_prep_a_kernel<8>, dim3(p.prep_grid[1]), dim3(256), 0, st, cur, dst_rows, Ns, Nd, s.a_q, s.ae_q);
     } else {
-        hipLaunchKernelGGL(edge_ft_prep_a_kernel<16>, dim3(B * Ns * 3 / 32), dim3(256), 0, st, cur, (const int32_t*)nullptr, Ns, Nd, s.a_p, s.ae_p);
+        hipLaunchKernelGGL(edge_ft_prep_a_kernel<16>, dim3(p.prep_grid[0]), dim3(256), 0, st, cur, (const int32_t*)nullptr, Ns, Nd, s.a_p, s.ae_p);
     }
     LS_LAUNCH_CHECK();
     return LS_OK;
 }
-int edge_ft_attn_launch(const void* wplanes, const int32_t* knn, bool has_rows, int B, int Ns, int Nd, int Cin, int Co, float neg_slope, void* scratch,
-                        float* out, float* rowmax, hipStream_t st, float* colsum) {
-    LS_REQUIRE(edge_ft_supported(Co, Cin, Ns, Nd, 16, has_rows) && wplanes, "edge_ft_attn: unsupported shape (Co=%d Cin=%d Ns=%d Nd=%d)", Co, Cin, Ns, Nd);
-    const FtScratch s = ft_layout(scratch, B, Ns, Nd, Cin, Co, has_rows);
-    const int H = Co / 16, HG = edge_ft_heads_per_group(Cin), KS = Cin / 16;
-    const uint4* wp = (const uint4*)wplanes;
+int edge_ft_attn_launch(const Edge& e, const EdgePlan& p, hipStream_t st) {
+    const bool l5 = p.kernel == EdgeKernel::FT_128;
+    LS_REQUIRE((l5 || p.kernel == EdgeKernel::FT_256) && e.planes, "edge_ft_attn: the plan names no kernel of edge_fused.hip");
+    const FtScratch s = ft_scratch(const_cast<float*>(e.T), p.ft);
+    const int B = e.B, Co = e.Co, H = Co / 16, HG = edge_ft_heads_per_group(e.Cin), KS = e.Cin / 16;
+    float* rowmax = p.rowmax_parts ? e.rowmax : nullptr;
+    float* colsum = p.cs_rows ? e.colsum : nullptr;
+    const uint4* wp = (const uint4*)e.planes;
     const int* we = (const int*)(wp + (size_t)H * 5 * KS * 128);
-    const float oms = 1.0f - neg_slope, isd = 1.0f / sqrtf(3.0f * 16);
-    const dim3 grid((H / HG) * B);
+    const float oms = 1.0f - e.neg_slope, isd = 1.0f / sqrtf(3.0f * 16);
+    const dim3 grid(p.grid);
     // workgroup order: instance major (an instance's head groups side by side on an XCD: its A image stays in that XCD's L2 and is read by all of
     // them) or head-group major (the 64 instances of one W slice side by side).  Measured (us per launch, q/k | v): layer 5 36.9 | 41.6 instance
     // major vs 54.9 | 60.6 head major; layer 6 59.2 | 46.6 vs 65.9 | 48.1 -- the A fragments are the stream that matters: instance major.
-    if (Cin == 128) {
-        hipLaunchKernelGGL((edge_ft_qk_kernel<128, 128, 1>), grid, dim3(256), 0, st, s.a_p, s.ae_p, s.a_q, s.ae_q, wp, we, knn, B, H, oms, s.scores, s.sskp, s.ssqp);
-        LS_LAUNCH_CHECK();
-        hipLaunchKernelGGL(edge_ft_norms_kernel, dim3(B), dim3(256), 0, st, s.sskp, s.ssqp, H, s.invk, s.invq);
-        LS_LAUNCH_CHECK();
-        hipLaunchKernelGGL((edge_ft_v_kernel<128, 128, 1>), grid, dim3(256), 0, st, s.a_p, s.ae_p, s.a_q, s.ae_q, wp, we, knn, B, H, oms, isd, s.scores, s.invk,
-                           s.invq, out, Co, rowmax, H / HG, colsum);
-    } else {
-        hipLaunchKernelGGL((edge_ft_qk_kernel<256, 32, 2>), grid, dim3(256), 0, st, s.a_p, s.ae_p, s.a_q, s.ae_q, wp, we, knn, B, H, oms, s.scores, s.sskp, s.ssqp);
-        LS_LAUNCH_CHECK();
-        hipLaunchKernelGGL(edge_ft_norms_kernel, dim3(B), dim3(256), 0, st, s.sskp, s.ssqp, H, s.invk, s.invq);
-        LS_LAUNCH_CHECK();
-        hipLaunchKernelGGL((edge_ft_v_kernel<256, 32, 2>), grid, dim3(256), 0, st, s.a_p, s.ae_p, s.a_q, s.ae_q, wp, we, knn, B, H, oms, isd, s.scores, s.invk,
-                           s.invq, out, Co, rowmax, H / HG, colsum);
-    }
+#define LS_FT(CIN, NS, HG_)                                                                                                                                    \
+    hipLaunchKernelGGL((edge_ft_qk_kernel<CIN, NS, HG_>), grid, dim3(256), 0, st, s.a_p, s.ae_p, s.a_q, s.ae_q, wp, we, e.knn, B, H, oms, s.scores, s.sskp, s.ssqp); \
+    LS_LAUNCH_CHECK();                                                                                                                                         \
+    hipLaunchKernelGGL(edge_ft_norms_kernel, dim3(B), dim3(256), 0, st, s.sskp, s.ssqp, H, s.invk, s.invq);                                                    \
+    LS_LAUNCH_CHECK();                                                                                                                                         \
+    hipLaunchKernelGGL((edge_ft_v_kernel<CIN, NS, HG_>), grid, dim3(256), 0, st, s.a_p, s.ae_p, s.a_q, s.ae_q, wp, we, e.knn, B, H, oms, isd, s.scores, s.invk,  \
+                       s.invq, e.out, Co, rowmax, H / HG, colsum)
+    if (l5) { LS_FT(128, 128, 1); } else { LS_FT(256, 32, 2); }
+#undef LS_FT
     LS_LAUNCH_CHECK();
     return LS_OK;
 }
-int edge_ft_rowmax_parts(int Co, int Cin) { return Co / 16 / edge_ft_heads_per_group(Cin); }
 
 }  // namespace ls

@@ -4,6 +4,7 @@
 #pragma once
 #include "ls_common.h"
 #include "gemm_plan.h"
+#include "edge_plan.h"
 
 namespace ls {
 
@@ -55,27 +56,25 @@ size_t gemm_w_planes_bytes(size_t rows, int K);
 int gemm_presplit_w_launch(const float* W, int rows, int K, int ldw, const float* rowmax, void* planes, hipStream_t st);
 // ---- edge.hip
 int edge_l0_launch(const float* pts, const int32_t* knn, const float* w0, int B, int N, int Co, float neg_slope, float* out, hipStream_t st);
-int edge_pool_launch(const float* T, int ldt, const float* Tq, int ldq, int NQ, int qvr, const int32_t* knn, const int32_t* dst_rows, int B, int Nd, int Ns, int Co,
-                     float neg_slope, float* out, hipStream_t st);
-int edge_attn_launch(const float* T, int ldt, const float* Tq, int ldq, int NQ, int qvr, const int32_t* knn, const int32_t* dst_rows, int B, int Nd, int Ns, int Co,
-                     int head_c, float neg_slope, float* out, hipStream_t st, float* rowmax = nullptr, float* colsum = nullptr);
-bool edge_attn_emits_rowmax(int Co, int ldt, int ldq);
-bool edge_attn_fq_supported(int Co, int Cin);
-bool edge_attn_fq_fits(int B, int Ns, int ldt);
-int edge_attn_fq_launch(const float* T, int ldt, const float* cur, int Cin, const void* wq_planes, const int32_t* knn, const int32_t* dst_rows, int B, int Nd,
-                        int Ns, int Co, int head_c, float neg_slope, float* out, hipStream_t st, float* rowmax = nullptr, float* colsum = nullptr);
-int edge_attn_fq_points_per_wg(int Co);
+// layer i >= 1 over its table area, launched as edge_plan (edge_plan.h) says; rowmax [B*Nd*3][rowmax_parts] and colsum [B][cs_rows][3][Co] are
+// written where the plan says so
+struct Edge {
+    const float* T = nullptr;            // the table area, formed as the same plan says (the table-free path's scratch)
+    const float* cur = nullptr;          // the layer's input [B, Ns, 3, Cin]: the fused destination side reads it
+    const void* planes = nullptr;        // wq_planes (ATTN_FQ_*) / wt_planes (FT_*) of the layer
+    const int32_t *knn = nullptr, *dst_rows = nullptr;
+    int B = 0, Ns = 0, Nd = 0, Cin = 0, Co = 0, head_c = 0;
+    float neg_slope = 0.f;
+    float *out = nullptr, *rowmax = nullptr, *colsum = nullptr;
+};
+int edge_run(const Edge& e, const EdgePlan& p, hipStream_t st);
 size_t edge_wq_planes_bytes(int Co, int Cin);
 int edge_presplit_wq_launch(const float* Wq, int Co, int Cin, void* planes, hipStream_t st);
 // ---- edge_fused.hip: attention layers with 32 destination points (released layers 5 / 6) -- table slices formed and consumed in LDS
-bool edge_ft_supported(int Co, int Cin, int Ns, int Nd, int head_c, bool has_rows);
 size_t edge_ft_w_bytes(int Co, int Cin);
 int edge_ft_presplit_w_launch(const float* W, int Co, int Cin, void* planes, hipStream_t st);
-size_t edge_ft_scratch_bytes(int B, int Ns, int Nd, int Cin, int Co, bool has_rows);
-int edge_ft_prep_launch(const float* cur, const int32_t* dst_rows, int B, int Ns, int Nd, int Cin, int Co, void* scratch, hipStream_t st);
-int edge_ft_attn_launch(const void* wplanes, const int32_t* knn, bool has_rows, int B, int Ns, int Nd, int Cin, int Co, float neg_slope, void* scratch, float* out,
-                        float* rowmax, hipStream_t st, float* colsum = nullptr);
-int edge_ft_rowmax_parts(int Co, int Cin);
+int edge_ft_prep_launch(const float* cur, const int32_t* dst_rows, int Ns, int Nd, void* scratch, const EdgePlan& p, hipStream_t st);
+int edge_ft_attn_launch(const Edge& e, const EdgePlan& p, hipStream_t st);
 // ---- pointwise.hip
 int prologue_launch(const float* x, int B, int N, float* pts, float* centroid, float* scale0, float* unused, hipStream_t st);
 size_t prologue_scratch_floats(int B);

@@ -97,10 +97,14 @@ struct ProfScope {
 
 static inline int pad4(int cols) { return (cols + 3) / 4 * 4; }   // a matrix's columns as whole float4s
 
+// a layer's widths: input channels and table columns (mean-pool: 2 Co neighbour-side + 2 Co destination-side, attention: 4 Co + 6 Co); output channels: d.feat_dim[i]
+static inline int layer_cin(const ls_model_desc& d, int i) { return i == 0 ? 1 : d.feat_dim[i - 1]; }
+static inline int layer_ncols(const ls_model_desc& d, int i) { return i == 0 ? 0 : (i >= d.atten_start_layer ? 10 : 4) * d.feat_dim[i]; }
+
 // ------------------------------------------------------------------------------------------------ plan
 struct EncPlan {
     int L = 0;
-    int Ns[LS_MAX_LAYERS], Nd[LS_MAX_LAYERS], Cin[LS_MAX_LAYERS], Co[LS_MAX_LAYERS], ncols[LS_MAX_LAYERS], level[LS_MAX_LAYERS];
+    int Ns[LS_MAX_LAYERS], Nd[LS_MAX_LAYERS], level[LS_MAX_LAYERS];
     int nlevels = 0, levelN[LS_MAX_LAYERS + 1];
     int NP = 0, Cdp = 0;
     // workspace offsets (bytes)
@@ -131,35 +135,29 @@ static int make_plan(const ls_model_desc& d, int B, int N, EncPlan& p) {
         // behaviour there is pytorch3d's padding convention, unpinned): refuse instead of reading out of bounds
         LS_REQUIRE(p.Ns[i] >= d.num_knn, "encoder: layer %d has %d source points < num_knn=%d (N=%d too small for the schedule)", i,
                    p.Ns[i], d.num_knn, N);
-        p.Cin[i] = i == 0 ? 1 : d.feat_dim[i - 1];
-        p.Co[i] = d.feat_dim[i];
+        const int Cin = layer_cin(d, i), Co = d.feat_dim[i];
         const bool attn = i >= d.atten_start_layer;
-        p.ncols[i] = i == 0 ? 0 : (attn ? 10 : 4) * p.Co[i];
-        LS_REQUIRE(p.Co[i] % 16 == 0, "encoder: feat_dim[%d]=%d must be a multiple of 16", i, p.Co[i]);
-        if (i > 0) LS_REQUIRE(p.Cin[i] % 32 == 0, "encoder: feat_dim[%d]=%d must be a multiple of 32 (k-NN chunking)", i - 1, p.Cin[i]);
-        maxF = std::max(maxF, (size_t)p.Nd[i] * 3 * p.Co[i]);
-        {   // combined table over the source points, or split P (source points) + Q (destination points) tables
-            const int pc = (attn ? 4 : 2) * p.Co[i], qc = p.ncols[i] - pc;
-            const size_t need = (f > 1) ? (size_t)p.Ns[i] * 3 * pc + (size_t)p.Nd[i] * 3 * qc : (size_t)p.Ns[i] * 3 * p.ncols[i];
-            maxT = std::max(maxT, need);
-        }
-        maxTG = std::max(maxTG, (size_t)p.Nd[i] * 3 * 2 * p.Co[i]);
-        maxC = std::max(maxC, (size_t)p.Co[i]);
+        LS_REQUIRE(Co % 16 == 0, "encoder: feat_dim[%d]=%d must be a multiple of 16", i, Co);
+        if (i > 0) LS_REQUIRE(Cin % 32 == 0, "encoder: feat_dim[%d]=%d must be a multiple of 32 (k-NN chunking)", i - 1, Cin);
+        maxF = std::max(maxF, (size_t)p.Nd[i] * 3 * Co);
+        if (i > 0) maxT = std::max(maxT, edge_table_floats(attn, Co, 1, p.Ns[i], p.Nd[i], f > 1));   // per instance
+        maxTG = std::max(maxTG, (size_t)p.Nd[i] * 3 * 2 * Co);
+        maxC = std::max(maxC, (size_t)Co);
         // row maxima of a layer's message / output: one part per 32 channels + 1, or -- where the table-free path of the 32-point layers may run
         // (edge_fused.hip) -- one per head group; sized per LAYER (round 4 sized Nd and the parts by separate maxima, which only held because
         // the released schedule has wide early layers: ADVICE r4)
         if (i >= d.res_global_start_layer) {
-            size_t parts = (size_t)p.Co[i] / 32 + 1;
-            if (i > 0 && attn && (p.Cin[i] == 128 || p.Cin[i] == 256)) parts = std::max(parts, (size_t)edge_ft_rowmax_parts(p.Co[i], p.Cin[i]));
+            size_t parts = (size_t)Co / 32 + 1;
+            if (i > 0 && attn && edge_ft_shape(Co, Cin, d.atten_head_c)) parts = std::max(parts, (size_t)edge_ft_rowmax_parts(Co, Cin));
             maxRm = std::max(maxRm, (size_t)p.Nd[i] * parts);
             // partial column sums of the message from the attention kernel that wrote it (global_conv): at most one row per 8 points
-            maxCs = std::max(maxCs, (size_t)(p.Nd[i] / 8 + 1) * 3 * p.Co[i]);
+            maxCs = std::max(maxCs, (size_t)(p.Nd[i] / 8 + 1) * 3 * Co);
         }
         // split-K slabs of the under-filled GEMMs (residual global conv: per-point part and per-instance mean part)
-        maxGws = std::max(maxGws, std::max(gemm_scratch_floats(B * p.Nd[i] * 3, 2 * p.Co[i], p.Co[i]), gemm_scratch_floats(B * 3, 4 * p.Co[i], p.Co[i])));
+        maxGws = std::max(maxGws, std::max(gemm_scratch_floats(B * p.Nd[i] * 3, 2 * Co, Co), gemm_scratch_floats(B * 3, 4 * Co, Co)));
         maxKnn = std::max(maxKnn, (size_t)p.Nd[i] * 16);
-        maxKs = std::max(maxKs, std::max(knn_scratch_bytes(B, p.Nd[i], p.Ns[i], p.Ns[i], p.Cin[i], true, 0u),
-                                        knn_scratch_bytes(B, p.Nd[i], p.Ns[i], p.Ns[i], p.Cin[i], false, 0u)));
+        maxKs = std::max(maxKs, std::max(knn_scratch_bytes(B, p.Nd[i], p.Ns[i], p.Ns[i], Cin, true, 0u),
+                                        knn_scratch_bytes(B, p.Nd[i], p.Ns[i], p.Ns[i], Cin, false, 0u)));
     }
     LS_REQUIRE(d.num_knn == 16, "encoder: num_knn=%d unsupported (16)", d.num_knn);
     LS_REQUIRE(p.Ns[p.L - 1] >= 1, "encoder: bad schedule");
@@ -184,7 +182,7 @@ static int make_plan(const ls_model_desc& d, int B, int N, EncPlan& p) {
     p.o_g = a.take_bytes((size_t)B * 3 * maxC * 4);
     p.o_G = a.take_bytes((size_t)B * 3 * 4 * maxC * 4);
     p.o_Tc = a.take_bytes((size_t)B * p.NP * 3 * p.Cdp * 4);
-    maxGws = std::max(maxGws, gemm_scratch_floats(B * p.NP * 3, p.Cdp, p.Co[p.L - 1]));
+    maxGws = std::max(maxGws, gemm_scratch_floats(B * p.NP * 3, p.Cdp, d.feat_dim[p.L - 1]));
     p.o_gws = a.take_bytes(maxGws * 4 + 256);
     // row maxima of the messages / layer outputs, chained into the GEMMs that read them (gemm.hip, GemmAux)
     p.o_rm_msg = a.take_bytes((size_t)B * maxRm * 3 * 4);      // maxRm = max over the layers of Nd x parts (above)
@@ -255,104 +253,53 @@ static int wmax_register(ls_model* m, const std::vector<WSpec>& specs, float** p
 
 // ------------------------------------------------------------------------------------------------ layer pieces
 // (shared by ls_encode and the per-operator exports ls_vn_edgeconv_* / ls_vn_lna_f32 / ls_encoder_tail_f32)
-static inline int layer_cin(const ls_model_desc& d, int i) { return i == 0 ? 1 : d.feat_dim[i - 1]; }
-static inline int layer_ncols(const ls_model_desc& d, int i) { return i == 0 ? 0 : (i >= d.atten_start_layer ? 10 : 4) * d.feat_dim[i]; }
-static inline int layer_pcols(const ls_model_desc& d, int i) { return (i >= d.atten_start_layer ? 4 : 2) * d.feat_dim[i]; }
-// floats of the per-point table(s) of edge-conv layer i: one combined table over the source points, or (destination points
-// selected by FPS rows) a neighbour-side table on the source points + a destination-side table on the selected points
-static size_t edge_table_floats(const ls_model_desc& d, int i, int B, int Ns, int Nd, bool rows) {
-    if (i == 0) return 0;
-    const int nc = layer_ncols(d, i), pc = layer_pcols(d, i);
-    return rows ? (size_t)B * 3 * ((size_t)Ns * pc + (size_t)Nd * (nc - pc)) : (size_t)B * Ns * 3 * nc;
-}
-struct EdgeTables { const float* Tq; int ldp, ldq, NQ, qvr; const float* cur = nullptr; const void* Wq = nullptr; int Cin = 0;
-                    const void* Wt = nullptr; };   // Wt != null: no table at all (edge_fused.hip); the table area holds that path's scratch   // cur != null: destination side fused into the edge kernel
-
-// where the table(s) of layer i live in T and how the edge kernel reads them (no launch)
-static bool edge_fused(const ls_model* m, int i) {
-    // LS_OPT_EDGE_FUSE_Q = 0: destination side as table columns.  The fused kernel forms its products from f16 pieces like the default GEMM
-    // mode; under LS_GEMM_MODE=bf16x3 / fp32 (any fp32 range, or the fp32-MFMA kernels) the table path is kept so that every product of the layer
-    // is formed the same way
-    return m->fuse_q && gemm_mode() == 0 && m->wq_planes[i];
-}
-// table-free path of the 32-point attention layers (edge_fused.hip).  LS_OPT_EDGE_FUSE_T = 0: the table GEMM + edge_attn_v4_kernel pair; like the
-// destination-side fusion it forms its products from f16 pieces, so the table path is kept under LS_GEMM_MODE=bf16x3 / fp32.
-static bool edge_fused_t(const ls_model* m, int i, int B, int Ns, int Nd, bool has_rows) {
+// what edge-conv layer i >= 1 of a call launches (edge_plan.h: the one statement of the choice).  glob: a residual global conv follows, which
+// takes the row maxima and (LS_OPT_GLOB_FUSE) the partial column sums of the message from the kernel that wrote it
+static EdgePlan layer_edge_plan(const ls_model* m, int i, int B, int Ns, int Nd, bool has_rows, bool glob) {
     const ls_model_desc& d = m->d;
-    if (!m->fuse_t || gemm_mode() != 0 || !m->wt_planes[i] || i < d.atten_start_layer) return false;
-    const int Cin = layer_cin(d, i), Co = d.feat_dim[i];
-    return edge_ft_supported(Co, Cin, Ns, Nd, d.atten_head_c, has_rows) &&
-           edge_ft_scratch_bytes(B, Ns, Nd, Cin, Co, has_rows) <= edge_table_floats(d, i, B, Ns, Nd, has_rows) * sizeof(float);
+    EdgeTraits t;
+    t.attn = i >= d.atten_start_layer; t.Cin = layer_cin(d, i); t.Co = d.feat_dim[i]; t.head_c = d.atten_head_c;
+    t.B = B; t.Ns = Ns; t.Nd = Nd; t.has_rows = has_rows;
+    t.mode = gemm_mode();
+    t.fuse_q = m->fuse_q; t.fuse_t = m->fuse_t; t.has_wq = m->wq_planes[i] != nullptr; t.has_wt = m->wt_planes[i] != nullptr;
+    t.want_rowmax = glob; t.want_colsum = glob && m->glob_fuse;
+    return edge_plan(t);
 }
-static EdgeTables edge_tables_layout(const ls_model* m, int i, const float* cur, const int32_t* dst_rows, int B, int Ns, int Nd, float* T) {
-    const ls_model_desc& d = m->d;
-    const int Cin = layer_cin(d, i), nc = layer_ncols(d, i), pc = layer_pcols(d, i);
-    if (edge_fused_t(m, i, B, Ns, Nd, dst_rows != nullptr)) { EdgeTables e{nullptr, 0, 0, 0, 0, cur, nullptr, Cin}; e.Wt = m->wt_planes[i]; return e; }
-    // (the fused kernel gathers table rows by 32-bit byte offsets: a batch whose neighbour-side table reaches 4 GB takes the table path)
-    if (edge_fused(m, i) && edge_attn_fq_fits(B, Ns, pc)) return EdgeTables{nullptr, pc, 0, 0, 0, cur, m->wq_planes[i], Cin};
-    if (dst_rows) return EdgeTables{T + (size_t)B * Ns * 3 * pc, pc, nc - pc, Nd, 0};
-    return EdgeTables{T + pc, nc, nc, Ns, 1};
-}
-// the folded VN-Linear contraction of layer i >= 1 (edge.hip header): cur [B,Ns,3,Cin] -> table(s) in T
+// the table side of the plan: the folded VN-Linear contraction of layer i >= 1 (edge.hip header), cur [B,Ns,3,Cin] -> table(s) in T
 // a_rowmax (nullable) [B*Ns*3][a_parts]: row maxima of `cur` from the kernel that wrote it (GemmAux)
-static int edge_tables(ls_model* m, int i, const float* cur, const int32_t* dst_rows, int B, int Ns, int Nd, float* T, hipStream_t gs,
-                       EdgeTables& et, const float* a_rowmax = nullptr, int a_parts = 0) {
+static int edge_tables_run(ls_model* m, int i, const EdgePlan& ep, const float* cur, const int32_t* dst_rows, int B, int Ns, int Nd, float* T, hipStream_t gs,
+                           const float* a_rowmax = nullptr, int a_parts = 0) {
     const ls_model_desc& d = m->d;
-    const int Cin = layer_cin(d, i), nc = layer_ncols(d, i), pc = layer_pcols(d, i), qc = nc - pc;
+    const int Cin = layer_cin(d, i);
     const float* W = m->blob + d.off_edge[i];
-    et = edge_tables_layout(m, i, cur, dst_rows, B, Ns, Nd, T);
     PROF(LS_K_GEMM_EDGE, i, gs);
     // 32-point attention layers (edge_fused.hip): no table -- only the operand image of the feature rows (f16 fragment planes) is formed here
-    if (et.Wt) return edge_ft_prep_launch(cur, dst_rows, B, Ns, Nd, Cin, d.feat_dim[i], T, gs);
-    // attention layers 2 - 4 (fused): only the neighbour-side table; the destination side is computed inside the edge kernel (edge.hip)
+    if (ep.n_gemm == 0) return edge_ft_prep_launch(cur, dst_rows, Ns, Nd, T, ep, gs);
     Gemm g;   // the neighbour-side (P) columns, or the combined table, on all source points
     g.A = cur; g.lda = Cin; g.W = W; g.ldw = Cin; g.out = T; g.M = B * Ns * 3; g.K = Cin;
-    g.N = g.ldc = (et.cur || dst_rows) ? pc : nc;
-    g.aux = aux_w(m, W, nc, Cin);
+    g.N = g.ldc = ep.gemm_n[0];
+    g.aux = aux_w(m, W, layer_ncols(d, i), Cin);
     g.aux.a_rowmax = a_rowmax; g.aux.a_parts = a_parts;
     int rc = gemm_run(g, gs);
-    if (et.cur || !dst_rows || rc != LS_OK) return rc;
-    // down-sampled layer: the destination-side (Q) table only on the FPS-selected destination points -- rows pc.. of the same matrix
-    g.W = W + (size_t)pc * Cin; g.out = const_cast<float*>(et.Tq); g.M = B * Nd * 3; g.N = g.ldc = qc;
+    if (ep.n_gemm == 1 || rc != LS_OK) return rc;
+    // down-sampled layer: the destination-side (Q) table only on the FPS-selected destination points -- the following rows of the same matrix
+    const int pc = ep.gemm_n[0];
+    g.W = W + (size_t)pc * Cin; g.out = T + ep.q_off; g.M = B * Nd * 3; g.N = g.ldc = ep.gemm_n[1];
     g.a_rows = dst_rows; g.gNd = Nd; g.gNs = Ns;
     if (g.aux.w_rowmax) g.aux.w_rowmax += pc;
     if (g.aux.w_planes) g.aux.w_planes = static_cast<const char*>(g.aux.w_planes) + gemm_w_planes_bytes((size_t)pc, Cin);
     return gemm_run(g, gs);
 }
-// gather + VN activation + mean-pool | attention of layer i >= 1 over the tables
-// rm_out (nullable) [B*Nd*3]: receives max|out[row, :]| when the kernel taken can write it; *rm_written says whether it did
-static int edge_apply(ls_model* m, int i, const float* T, const EdgeTables& et, const int32_t* knn, const int32_t* dst_rows, int B, int Nd,
-                      int Ns, float* out, hipStream_t st, float* rm_out = nullptr, bool* rm_written = nullptr, int* rm_parts = nullptr,
-                      float* cs_out = nullptr, int* cs_rows = nullptr) {
-    // cs_out (nullable): receives partial column sums of `out` ([B][*cs_rows][3][Co], *cs_rows = 0: the kernel taken writes none) -- global_conv
+// gather + VN activation + mean-pool | attention of layer i >= 1 over the tables; rowmax / colsum: where the plan's side products go
+static int edge_layer_run(ls_model* m, int i, const EdgePlan& ep, const float* T, const float* cur, const int32_t* knn, const int32_t* dst_rows, int B, int Ns,
+                          int Nd, float* out, hipStream_t st, float* rowmax = nullptr, float* colsum = nullptr) {
     const ls_model_desc& d = m->d;
-    const int Co = d.feat_dim[i];
-    if (rm_written) *rm_written = false;
-    if (rm_parts) *rm_parts = 1;
-    if (cs_rows) *cs_rows = 0;
-    if (!cs_rows || !m->glob_fuse) cs_out = nullptr;
-    if (i >= d.atten_start_layer) {
-        PROF(LS_K_EDGE_ATTN, i, st);
-        if (et.Wt) {   // rm_out (if any) must hold [B*Nd*3][edge_ft_rowmax_parts] floats: one maximum per head group and row
-            if (rm_written) *rm_written = rm_out != nullptr;
-            if (rm_parts) *rm_parts = edge_ft_rowmax_parts(Co, et.Cin);
-            if (cs_out) *cs_rows = 1;
-            return edge_ft_attn_launch(et.Wt, knn, dst_rows != nullptr, B, Ns, Nd, et.Cin, Co, d.neg_slope, const_cast<float*>(T), out, rm_out, st, cs_out);
-        }
-        if (et.cur) {
-            if (rm_written) *rm_written = rm_out != nullptr;
-            const int pw = edge_attn_fq_points_per_wg(Co);
-            if (cs_out && pw > 0 && Nd % pw == 0) *cs_rows = Nd / pw; else cs_out = nullptr;
-            return edge_attn_fq_launch(T, et.ldp, et.cur, et.Cin, et.Wq, knn, dst_rows, B, Nd, Ns, Co, d.atten_head_c, d.neg_slope, out, st, rm_out, cs_out);
-        }
-        if (!edge_attn_emits_rowmax(Co, et.ldp, et.ldq)) rm_out = nullptr;
-        if (rm_written) *rm_written = rm_out != nullptr;
-        const int pw = edge_attn_fq_points_per_wg(Co);   // (the float4-lane kernel of Co = 64 / 128 shares the fused kernel's point map and column sums)
-        if (cs_out && pw > 0 && Nd % pw == 0 && et.ldp % 4 == 0 && et.ldq % 4 == 0) *cs_rows = Nd / pw; else cs_out = nullptr;
-        return edge_attn_launch(T, et.ldp, et.Tq, et.ldq, et.NQ, et.qvr, knn, dst_rows, B, Nd, Ns, Co, d.atten_head_c, d.neg_slope, out, st, rm_out, cs_out);
-    }
-    PROF(LS_K_EDGE_POOL, i, st);
-    return edge_pool_launch(T, et.ldp, et.Tq, et.ldq, et.NQ, et.qvr, knn, dst_rows, B, Nd, Ns, Co, d.neg_slope, out, st);
+    Edge e;
+    e.T = T; e.cur = cur; e.planes = ep.n_gemm == 0 ? m->wt_planes[i] : m->wq_planes[i]; e.knn = knn; e.dst_rows = dst_rows;
+    e.B = B; e.Ns = Ns; e.Nd = Nd; e.Cin = layer_cin(d, i); e.Co = d.feat_dim[i]; e.head_c = d.atten_head_c; e.neg_slope = d.neg_slope;
+    e.out = out; e.rowmax = rowmax; e.colsum = colsum;
+    PROF(i >= d.atten_start_layer ? LS_K_EDGE_ATTN : LS_K_EDGE_POOL, i, st);
+    return edge_run(e, ep, st);
 }
 // residual global conv of layer i (vec_dgcnn_atten.py:222-225): out = VecLNA_G(cat(msg, mean_n msg))
 static size_t global_conv_gws_floats(const ls_model_desc& d, int i, int B, int Nd) {
@@ -364,7 +311,7 @@ static size_t global_conv_gws_floats(const ls_model_desc& d, int i, int B, int N
 static int global_conv(ls_model* m, int i, const float* msg, int B, int Nd, float* g, float* G, float* TG, float* gws, float* out, hipStream_t st,
                        const float* rm_msg = nullptr, float* rm_out = nullptr, bool* rm_written = nullptr, int rm_msg_parts = 1, const float* cs = nullptr,
                        int cs_rows = 0) {
-    // cs (nullable) [B][cs_rows][3][Co]: partial column sums of msg from the kernel that wrote it (edge_apply): the mean is finished from them
+    // cs (nullable) [B][cs_rows][3][Co]: partial column sums of msg from the kernel that wrote it (edge_plan.h: cs_rows): the mean is finished from them
     const ls_model_desc& d = m->d;
     const int Co = d.feat_dim[i];
     const float* Wg = m->blob + d.off_glob[i];
@@ -469,20 +416,19 @@ int ls_model_create(const ls_model_desc* desc, const float* blob_host, ls_model_
     if (e == hipSuccess) e = hipMalloc((void**)&m->knn_stats, sizeof(unsigned long long) * 2 * LS_MAX_LAYERS);
     if (e == hipSuccess) e = hipMemset(m->knn_stats, 0, sizeof(unsigned long long) * 2 * LS_MAX_LAYERS);
     if (e != hipSuccess) { set_error("model_create: %s", hipGetErrorString(e)); ls_model_destroy(m); return LS_ERR_HIP; }
-    for (int i = desc->atten_start_layer; i < desc->num_layers && i >= 1; ++i) {   // table-free 32-point layers (edge_fused.hip): the shapes it has kernels for
+    for (int i = desc->atten_start_layer; i < desc->num_layers && i >= 1; ++i) {   // attention layers: weight planes for the shapes the fused kernels serve (edge_plan.h)
         const int Co = desc->feat_dim[i], Cin = layer_cin(*desc, i);
-        if (desc->atten_head_c != 16 || !((Cin == 128 && Co % 16 == 0) || (Cin == 256 && Co % 32 == 0))) continue;
-        e = hipMalloc(&m->wt_planes[i], edge_ft_w_bytes(Co, Cin));
+        const float* W = m->blob + desc->off_edge[i];
+        int rc = LS_OK;
+        if (edge_ft_shape(Co, Cin, desc->atten_head_c)) {   // table-free 32-point layers (edge_fused.hip)
+            e = hipMalloc(&m->wt_planes[i], edge_ft_w_bytes(Co, Cin));
+            if (e == hipSuccess) rc = edge_ft_presplit_w_launch(W, Co, Cin, m->wt_planes[i], nullptr);
+        }
+        if (e == hipSuccess && rc == LS_OK && edge_attn_fq_shape(Co, Cin, desc->atten_head_c)) {   // destination side inside the edge kernel (edge.hip)
+            e = hipMalloc(&m->wq_planes[i], edge_wq_planes_bytes(Co, Cin));
+            if (e == hipSuccess) rc = edge_presplit_wq_launch(W + (size_t)4 * Co * Cin, Co, Cin, m->wq_planes[i], nullptr);   // (its rows follow the 4 Co neighbour-side rows)
+        }
         if (e != hipSuccess) { set_error("model_create: %s", hipGetErrorString(e)); ls_model_destroy(m); return LS_ERR_HIP; }
-        const int rc = edge_ft_presplit_w_launch(m->blob + desc->off_edge[i], Co, Cin, m->wt_planes[i], nullptr);
-        if (rc != LS_OK || hipDeviceSynchronize() != hipSuccess) { ls_model_destroy(m); return LS_ERR_HIP; }
-    }
-    for (int i = desc->atten_start_layer; i < desc->num_layers && i >= 1; ++i) {
-        const int Co = desc->feat_dim[i], Cin = layer_cin(*desc, i);
-        if (desc->atten_head_c != 16 || !edge_attn_fq_supported(Co, Cin)) continue;
-        e = hipMalloc(&m->wq_planes[i], edge_wq_planes_bytes(Co, Cin));
-        if (e != hipSuccess) { set_error("model_create: %s", hipGetErrorString(e)); ls_model_destroy(m); return LS_ERR_HIP; }
-        const int rc = edge_presplit_wq_launch(m->blob + desc->off_edge[i] + (size_t)layer_pcols(*desc, i) * Cin, Co, Cin, m->wq_planes[i], nullptr);
         if (rc != LS_OK || hipDeviceSynchronize() != hipSuccess) { ls_model_destroy(m); return LS_ERR_HIP; }
     }
     {   // row maxima of every matrix the GEMMs read (GemmAux::w_rowmax)
@@ -642,7 +588,7 @@ static int encode_enqueue(ls_model_t* m, const EncPlan& p, const float* x, int B
             if (p.nlevels > 0 && !joined && m->fps_side) LS_HIP_CHECK(hipStreamWaitEvent(st, m->ev_join, 0));
             return LS_OK;
         }
-        const int Ns = p.Ns[i], Nd = p.Nd[i], Co = p.Co[i];
+        const int Ns = p.Ns[i], Nd = p.Nd[i], Co = d.feat_dim[i];
         const int32_t* dst_rows = nullptr;
         if (p.level[i] >= 0) {
             if (m->fps_side) LS_HIP_CHECK(hipStreamWaitEvent(st, m->ev_fps[p.level[i]], 0));   // this layer's level only
@@ -655,8 +601,7 @@ static int encode_enqueue(ls_model_t* m, const EncPlan& p, const float* x, int B
         const bool attn = i >= d.atten_start_layer;
         const bool glob = i >= d.res_global_start_layer;
         float* mp = glob ? msg : nxt;
-        bool msg_rm = false;
-        int msg_rm_parts = 1, msg_cs_rows = 0;
+        int msg_rm_parts = 0, msg_cs_rows = 0;   // side products of the kernel that wrote the message (0: none)
         if (i == 0) {
             { PROF(LS_K_KNN, i, st); rc = knn_dispatch(pts0, pts0, nullptr, B, Nd, Ns, Ns, 1, 16, flags, knn, nullptr, ws + p.o_knns, nullptr, 0, 0, st); }
             if (rc != LS_OK) return rc;
@@ -664,7 +609,8 @@ static int encode_enqueue(ls_model_t* m, const EncPlan& p, const float* x, int B
             { PROF(LS_K_EDGE_L0, i, st); rc = edge_l0_launch(pts0, knn, W + d.off_l0, B, Ns, Co, d.neg_slope, mp, st); }
             if (rc != LS_OK) return rc;
         } else {
-            const int Cin = p.Cin[i];
+            const int Cin = layer_cin(d, i);
+            const EdgePlan ep = layer_edge_plan(m, i, B, Ns, Nd, dst_rows != nullptr, glob);
             // fork: the table GEMM(s) depend only on the layer input, like the k-NN -> run them on side2 (matrix cores /
             // HBM writes) concurrently with the VALU-bound k-NN on the caller's stream; join before the edge kernel.
             hipStream_t gs = m->overlap_gemm ? m->side2 : st;
@@ -672,8 +618,7 @@ static int encode_enqueue(ls_model_t* m, const EncPlan& p, const float* x, int B
                 LS_HIP_CHECK(hipEventRecord(m->ev_feat[i], st));
                 LS_HIP_CHECK(hipStreamWaitEvent(gs, m->ev_feat[i], 0));
             }
-            EdgeTables et;
-            rc = edge_tables(m, i, cur, dst_rows, B, Ns, Nd, T, gs, et, cur_rm, cur_rm_parts);
+            rc = edge_tables_run(m, i, ep, cur, dst_rows, B, Ns, Nd, T, gs, cur_rm, cur_rm_parts);
             if (rc != LS_OK) return rc;
             if (m->overlap_gemm) LS_HIP_CHECK(hipEventRecord(m->ev_tab[i], gs));
             {   // (no hints: the fused k-NN kernel derives its thresholds from its own sweep -- knn_mfma.hip)
@@ -687,14 +632,14 @@ static int encode_enqueue(ls_model_t* m, const EncPlan& p, const float* x, int B
                 if (rc != LS_OK) return rc;
             }
             if (m->overlap_gemm) LS_HIP_CHECK(hipStreamWaitEvent(st, m->ev_tab[i], 0));
-            rc = edge_apply(m, i, T, et, knn, dst_rows, B, Nd, Ns, mp, st, glob ? F(p.o_rm_msg) : nullptr, &msg_rm, &msg_rm_parts,
-                            glob ? F(p.o_cs) : nullptr, &msg_cs_rows);
+            rc = edge_layer_run(m, i, ep, T, cur, knn, dst_rows, B, Ns, Nd, mp, st, F(p.o_rm_msg), F(p.o_cs));
             if (rc != LS_OK) return rc;
+            msg_rm_parts = ep.rowmax_parts; msg_cs_rows = ep.cs_rows;
         }
         cur_rm = nullptr; cur_rm_parts = 0;
         if (glob) {
             bool out_rm = false;
-            rc = global_conv(m, i, msg, B, Nd, F(p.o_g), F(p.o_G), F(p.o_TG), F(p.o_gws), nxt, st, msg_rm ? F(p.o_rm_msg) : nullptr,
+            rc = global_conv(m, i, msg, B, Nd, F(p.o_g), F(p.o_G), F(p.o_TG), F(p.o_gws), nxt, st, msg_rm_parts ? F(p.o_rm_msg) : nullptr,
                              F(p.o_rm_out[i & 1]), &out_rm, msg_rm_parts, F(p.o_cs), msg_cs_rows);
             if (rc != LS_OK) return rc;
             if (out_rm) { cur_rm = F(p.o_rm_out[i & 1]); cur_rm_parts = Co / 32; }
@@ -782,7 +727,7 @@ static int check_layer(const ls_model_t* m, int layer, bool want_attn, const cha
 size_t ls_vn_edgeconv_workspace_bytes(const ls_model_t* m, int layer, int B, int Ns, int Nd, int has_dst_rows) {
     if (!m || layer < 0 || layer >= m->d.num_layers || B <= 0) return 0;
     Arena a(nullptr);
-    a.take<float>(edge_table_floats(m->d, layer, B, Ns, Nd, has_dst_rows != 0) + 4);
+    a.take<float>((layer == 0 ? 0 : edge_table_floats(layer >= m->d.atten_start_layer, m->d.feat_dim[layer], B, Ns, Nd, has_dst_rows != 0)) + 4);
     return a.bytes();
 }
 static int edgeconv_export(ls_model_t* m, int layer, const float* src_f, const int32_t* knn, const int32_t* dst_rows, int B, int Ns, int Nd,
@@ -797,16 +742,11 @@ static int edgeconv_export(ls_model_t* m, int layer, const float* src_f, const i
     }
     const size_t need = ls_vn_edgeconv_workspace_bytes(m, layer, B, Ns, Nd, dst_rows != nullptr);
     if (!workspace || workspace_bytes < need) { set_error("%s: workspace %zu < required %zu", who, workspace_bytes, need); return LS_ERR_WORKSPACE; }
-    EdgeTables et;
-    int rc = LS_OK;
-    if (m->debug_edge == 2) {   // LS_OPT_DEBUG_EDGE: the tables are already in the workspace
-        et = edge_tables_layout(m, layer, src_f, dst_rows, B, Ns, Nd, (float*)workspace);
-    } else {
-        rc = edge_tables(m, layer, src_f, dst_rows, B, Ns, Nd, (float*)workspace, st, et);
-    }
-    if (rc != LS_OK) return rc;
-    if (m->debug_edge == 1) return LS_OK;
-    return edge_apply(m, layer, (const float*)workspace, et, knn, dst_rows, B, Nd, Ns, out, st);
+    const EdgePlan ep = layer_edge_plan(m, layer, B, Ns, Nd, dst_rows != nullptr, false);
+    // LS_OPT_DEBUG_EDGE = 2: the tables are already in the workspace; 1: the tables only
+    const int rc = m->debug_edge == 2 ? LS_OK : edge_tables_run(m, layer, ep, src_f, dst_rows, B, Ns, Nd, (float*)workspace, st);
+    if (rc != LS_OK || m->debug_edge == 1) return rc;
+    return edge_layer_run(m, layer, ep, (const float*)workspace, src_f, knn, dst_rows, B, Ns, Nd, out, st);
 }
 int ls_vn_edgeconv_pool_f32(ls_model_t* m, int layer, const float* src_f, const int32_t* knn, const int32_t* dst_rows, int B, int Ns, int Nd,
                             float* out, void* workspace, size_t workspace_bytes, void* stream) {

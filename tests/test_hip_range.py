@@ -362,3 +362,27 @@ def test_gemm_outputs_are_the_recorded_ones_in_every_mode():
         if mode != mine:
             p = subprocess.run([sys.executable, tool, "--check-hashes", mode], env=dict(os.environ, LS_GEMM_MODE=mode), capture_output=True, text=True)
             assert p.returncode == 0, (mode, p.stdout[-2000:], p.stderr[-2000:])
+
+
+def test_edgeconv_and_encode_outputs_are_the_recorded_ones_in_every_mode():
+    """What an edge-conv layer launches (csrc/edge_plan.h) and the arguments the plan hands its kernels and table GEMMs (leading dimensions, the
+    destination side's offset, the scratch layout of the table-free path -- a kernel trace does not show them): the cases of
+    tests/tools/record_gemm_launches.py --family edge, HipModel.edgeconv per layer and whole ls_encode calls, must reproduce the SHA-256 of every
+    output recorded in tests/golden/edge_launches.json from the library before the layers' dispatch code became the plan.  No floating-point
+    atomics on any path: equality is exact.  The default mode in this process, bf16x3 and fp32 in a child each (the mode is read once)."""
+    import importlib.util
+    import os
+    import subprocess
+    import sys
+    tool = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools", "record_gemm_launches.py")
+    spec = importlib.util.spec_from_file_location("record_gemm_launches", tool)
+    rec = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rec)
+    mine = os.environ.get("LS_GEMM_MODE") if os.environ.get("LS_GEMM_MODE") in rec.MODES[1:] else rec.MODES[0]
+    wrong = rec.check_edge_hashes(mine)
+    assert not wrong, f"{len(wrong)} outputs differ from the record (recorded, now): {dict(list(wrong.items())[:4])}"
+    for mode in rec.MODES:
+        if mode != mine:
+            p = subprocess.run([sys.executable, tool, "--family", "edge", "--check-hashes", mode], env=dict(os.environ, LS_GEMM_MODE=mode), capture_output=True,
+                               text=True)
+            assert p.returncode == 0, (mode, p.stdout[-2000:], p.stderr[-2000:])

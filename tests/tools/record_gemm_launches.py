@@ -1,6 +1,7 @@
 """Record which GEMM kernels the library launches, and with what grid, on a fixed ladder of problems.
 
-    python tests/tools/record_gemm_launches.py [--out PATH]        -> tests/golden/gemm_launches.json   (GPU, rocprofv3 on the PATH)
+    python tests/tools/record_gemm_launches.py [--out PATH]                 -> tests/golden/gemm_launches.json   (GPU, rocprofv3 on the PATH)
+    python tests/tools/record_gemm_launches.py --family edge [--out PATH]   -> tests/golden/edge_launches.json   (the edge-conv layers, below)
 
 The wide, the tiled and the persistent kernels agree to the bit by design, so no numerical test sees a change of the kernel CHOICE; it only
 shows as a slower benchmark line.  The choice is therefore recorded from the library BEFORE a change to the dispatch code (csrc/gemm_plan.h)
@@ -11,7 +12,11 @@ How: one child process per arithmetic mode (LS_GEMM_MODE is read once per proces
 `rocprofv3 --kernel-trace` run (CSV, no counters, under a time limit).  The worker walks ladder() / model_ladder() in order and brackets every
 case with a marker launch (ls_rowmax_f32 on MARKER_ROWS rows: a grid no case produces; the count of markers is checked).  The launches between
 a case's two markers whose kernel name starts with ls::gemm_ are the record, operand preparation (gemm_rowmax_kernel, gemm_presplit_w_kernel)
-left out.  ladder() / model_ladder() are the one statement of the cases, shared with the tests."""
+left out.  ladder() / model_ladder() are the one statement of the cases, shared with the tests.
+
+--family edge records the encoder's edge-conv layers the same way (csrc/edge_plan.h; tests/test_edge_plan_cpu.py, tests/test_hip_range.py):
+edge_ladder() runs HipModel.edgeconv per layer and whole ls_encode calls; the record keeps the kernels of edge.hip / edge_fused.hip and the two
+mean kernels of the global conv (their grid is the only visible trace of the column sums), counts the table GEMMs, and hashes every output."""
 import argparse
 import binascii
 import csv
@@ -27,6 +32,7 @@ REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), "..", ".."))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 GOLDEN = os.path.join(REPO, "tests", "golden", "gemm_launches.json")
+GOLDENS = {"gemm": GOLDEN, "edge": os.path.join(REPO, "tests", "golden", "edge_launches.json")}
 MODES = ("f16", "bf16x3", "fp32")          # GemmTraits::mode 0 / 1 / 2; the first is the default (no LS_GEMM_MODE)
 MARKER_ROWS = 52                            # 13 workgroups of gemm_rowmax_kernel
 TEST_MAX_OUT = 1 << 22                      # outputs up to 4 M floats are hashed (tests/test_hip_range.py runs these cases), plus TEST_WIDE
@@ -38,6 +44,15 @@ UNITS = {"kernels": "[demangled name up to the parameter list, workgroup (x, y, 
                   "tests/tools/record_gemm_launches.py; per arithmetic mode the launches in order",
          "sha256": "of the output's bytes, row-major [M][N] float32; operands from numpy.random.default_rng(crc32(case key))",
          "status": "the entry point's return value where it is not 0 (a refusal: no launch)"}
+
+
+EDGE_UNITS = {"kernels": UNITS["kernels"].replace("gemm_w2_kernel", "edge_attn_kernel"),
+              "launch": UNITS["launch"],
+              "cases": "by key; edge_ladder() of tests/tools/record_gemm_launches.py states the handle, the layer and the sizes behind a key, edge_traits() the "
+                       "EdgeTraits; per arithmetic mode the launches of the kernels of edge.hip / edge_fused.hip and of glob_mean_gemv_kernel / mean_points_kernel: "
+                       "in order for edgeconv(...), sorted for encode(...) (two side streams make the trace's order vary)",
+              "tables": "edgeconv(...) only: how many GEMM launches formed the case's tables",
+              "sha256": "of the output's bytes (encode: z_so3, z_inv, s, t one after the other); inputs from numpy.random.default_rng(crc32(case key))"}
 
 
 def cdiv(a, b):
@@ -258,25 +273,46 @@ def sdf_traits(model, rows, x2, train_splitk):
     return fwd + bwd
 
 
-def run_model(models, key, model, op, args, options):
+def model_cfgs(which):
+    """'released' / 'small' as record_workspace_bytes.py builds them; 'pool64' / 'pool96': the small model with feat_dim[1] = 64 / 96."""
+    import record_workspace_bytes as rwb
+    if which in rwb.MODELS:
+        return rwb.model_cfgs(which)
+    ecfg, dcfg = rwb.model_cfgs("small")
+    return dict(ecfg, feat_dim=[32, int(which[4:]), 32, 64]), dcfg
+
+
+def make_model(which):
+    import torch
+    from livingscenes_amd import ops, packing, synth
+    ecfg, dcfg = model_cfgs(which)
+    desc, blob = packing.pack_model(synth.make_encoder_weights(ecfg, 0), ecfg, synth.make_decoder_weights(dcfg, 0), dcfg)
+    return ecfg, ops.HipModel(desc, blob, torch.device("cuda:0"))
+
+
+def run_model(models, key, model, op, args, options, want_hash=False):
     import numpy as np
     import torch
     from livingscenes_amd import _lib
-    import record_workspace_bytes as rwb
     if model not in models:
-        models[model] = rwb.make_model(model)
+        models[model] = make_model(model)
     ecfg, m = models[model]
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(_seed(key))
     rnd = lambda *s: torch.from_numpy(rng.standard_normal(s, dtype=np.float32)).to(dev)
     prev = {k: m.set_option(getattr(_lib, k), v) for k, v in options.items()}
+    out = None
     try:
         if op == "edgeconv":
             i, B, Ns, Nd, rows = args
             src = rnd(B, Ns, 3, ecfg["feat_dim"][i - 1])
             knn = torch.from_numpy(rng.integers(0, Ns, (B, Nd, 16), dtype=np.int32)).to(dev)
             dst = torch.from_numpy(np.stack([rng.permutation(Ns)[:Nd] for _ in range(B)]).astype(np.int32)).to(dev) if rows else None
-            marker(); m.edgeconv(i, src, knn, dst); marker()
+            marker(); out = m.edgeconv(i, src, knn, dst); marker()
+        elif op == "encode":
+            B, N = args
+            x = rnd(B, 3, N)
+            marker(); out = torch.cat([o.reshape(-1) for o in m.encode(x)]); marker()
         elif op == "lna":
             i, B, N = args
             f = rnd(B, N, 3, ecfg["feat_dim"][i])
@@ -301,22 +337,75 @@ def run_model(models, key, model, op, args, options):
         for k, v in prev.items():
             m.set_option(getattr(_lib, k), v)
     torch.cuda.synchronize()
-    return 0, None
+    return 0, hashlib.sha256(out.cpu().numpy().tobytes()).hexdigest() if want_hash else None
+
+
+# ------------------------------------------------------------------------------------------------ the edge-conv layers (--family edge)
+ENCODE_B, ENCODE_N = 2, (1024, 1008, 512)   # 1024: table-free layers, column sums everywhere; 1008: Nd = 504 / 126 / 31; 512: layer 6 has 16 source points
+
+
+def edge_ladder():
+    """[(key, model, op, args, options)], the same in every mode.  (a) HipModel.edgeconv with LS_OPT_EDGE_FUSE_Q / _T each 0 and 1: the released
+    layers 1 - 6 at B = 2 and one more B across the 16-tile edge of the table GEMM (K = 32 / 64: 3 B Ns / 128 = 12 | 24, 12 | 18); layers 5 / 6 with
+    32 destination points of 128 sources + rows, of 32 sources without rows, and with 31; the small model's layers 2 (Co = 32: the generic
+    attention kernel) and 3; layer 1 at 64 / 96 channels (edge_pool_v4_kernel<16>, the generic pool kernel).  (b) whole ls_encode calls."""
+    shapes = [("released", 1, B, 512, 512) for B in (1, 2)] + [("released", 1, 2, 100, 100)]
+    shapes += [("released", 2, B, 512, 256) for B in (1, 2)] + [("released", 2, 2, 500, 250)]
+    shapes += [("released", 3, B, 512, 512) for B in (1, 2)]
+    shapes += [("released", 4, B, 256, 64) for B in (2, 3)]
+    for i in (5, 6):
+        shapes += [("released", i, 2, 128, 32), ("released", i, 2, 32, 32), ("released", i, 2, 124, 31), ("released", i, 2, 31, 31)]
+    shapes += [("small", 2, 2, 256, 128), ("small", 3, 2, 128, 128), ("pool64", 1, 2, 256, 256), ("pool96", 1, 2, 256, 256)]
+    c = []
+    for model, i, B, Ns, Nd in shapes:
+        for fq in (0, 1):
+            for ft in (0, 1):
+                c.append((f"edgeconv({model}, layer={i}, B={B}, Ns={Ns}, Nd={Nd}, fuse_q={fq}, fuse_t={ft})", model, "edgeconv", (i, B, Ns, Nd, int(Ns != Nd)),
+                          {"OPT_EDGE_FUSE_Q": fq, "OPT_EDGE_FUSE_T": ft}))
+    c += [(f"encode(released, B={ENCODE_B}, N={N})", "released", "encode", (ENCODE_B, N), {}) for N in ENCODE_N]
+    return c
+
+
+def edge_traits(ecfg, mode, i, B, Ns, Nd, rows, fuse_q=1, fuse_t=1, encode=False, glob_fuse=1):
+    """EdgeTraits (csrc/edge_plan.h) of layer i >= 1 of a handle built from ecfg.  The handle holds the destination-side / table-free planes
+    where the header's two shape predicates say so (tests/tools/edge_plan_dump.cpp fills them in); the export wants no side products, an
+    encode wants row maxima and (LS_OPT_GLOB_FUSE != 0) column sums from the layers with a residual global conv."""
+    glob = bool(encode and i >= ecfg["res_global_start_layer"])
+    return dict(mode=MODES.index(mode), attn=int(i >= ecfg["atten_start_layer"]), Cin=ecfg["feat_dim"][i - 1], Co=ecfg["feat_dim"][i],
+                head_c=ecfg["atten_multi_head_c"], B=B, Ns=Ns, Nd=Nd, has_rows=int(rows), fuse_q=fuse_q, fuse_t=fuse_t, want_rowmax=int(glob),
+                want_colsum=int(glob and glob_fuse))
 
 
 # ------------------------------------------------------------------------------------------------ worker (under the trace) and collector
-def cases_of(mode):
-    """[(key, traits, runner)] of one mode's process, in launch order: the public ladder, then the model ladder."""
+def cases_of(mode, family="gemm"):
+    """[(key, traits, runner)] of one mode's process, in launch order: the public ladder, then the model ladder (edge: edge_ladder())."""
+    if family == "edge":
+        return [(k, None, ("model", k, mdl, op, a, o, True)) for k, mdl, op, a, o in edge_ladder()]
     out = [(k, [t], ("public", k, e, t)) for k, e, t in ladder()]
     out += [(k, tr, ("model", k, mdl, op, a, o)) for k, mdl, op, a, o, tr in model_ladder(mode)]
     return out
 
 
-def worker(mode, sidecar):
+def check_edge_hashes(mode):
+    """Run edge_ladder() in this process (which must be in arithmetic mode `mode`) -> {key: (recorded, now)} of the outputs that differ."""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    want, models, wrong = load("edge"), {}, {}
+    try:
+        for key, _, run in cases_of(mode, "edge"):
+            sha = run_model(models, *run[1:])[1]
+            if want[f"{mode}:{key}"]["sha256"] not in (None, sha):      # (None: the case was not reproducible when it was recorded)
+                wrong[key] = (want[f"{mode}:{key}"]["sha256"], sha)
+    finally:
+        for _, m in models.values():
+            m.close()
+    return wrong
+
+
+def worker(mode, sidecar, family):
     import torch
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     models, rec = {}, []
-    for key, traits, run in cases_of(mode):
+    for key, traits, run in cases_of(mode, family):
         if run[0] == "public":
             status, sha = run_public(*run[1:])
         else:
@@ -360,15 +449,22 @@ def is_marker(l):
     return l[0] == "ls::gemm_rowmax_kernel" and l[1][0] == cdiv(MARKER_ROWS, 4) * 256
 
 
+def is_gemm(l):
+    return l[0].startswith("ls::gemm_") and not l[0].startswith(("ls::gemm_rowmax_kernel", "ls::gemm_presplit_w_kernel"))
+
+
+def is_edge(l):
+    return l[0].startswith(("ls::edge_", "ls::glob_mean_gemv_kernel", "ls::mean_points_kernel"))
+
+
 def segment(launches, ncases):
     """The launches between the 2 k-th and the 2 k + 1-st marker belong to case k."""
     marks = [i for i, l in enumerate(launches) if is_marker(l)]
     assert len(marks) == 2 * ncases, f"{len(marks)} marker launches in the trace, {2 * ncases} expected"
-    keep = lambda l: l[0].startswith("ls::gemm_") and not l[0].startswith(("ls::gemm_rowmax_kernel", "ls::gemm_presplit_w_kernel"))
-    return [[l for l in launches[marks[2 * k] + 1:marks[2 * k + 1]] if keep(l)] for k in range(ncases)]
+    return [launches[marks[2 * k] + 1:marks[2 * k + 1]] for k in range(ncases)]
 
 
-def record(timeout=600):
+def record(family="gemm", timeout=600):
     cases = {}
     for mode in MODES:
         with tempfile.TemporaryDirectory(prefix="ls_gemm_trace_") as tmp:
@@ -378,18 +474,24 @@ def record(timeout=600):
             if mode != MODES[0]:
                 env["LS_GEMM_MODE"] = mode
             cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", os.path.join(tmp, "trace"), "--",
-                   sys.executable, os.path.abspath(__file__), "--worker", mode, "--sidecar", sidecar]
+                   sys.executable, os.path.abspath(__file__), "--worker", mode, "--sidecar", sidecar, "--family", family]
             subprocess.run(cmd, check=True, env=env, cwd=REPO, timeout=timeout)
             with open(sidecar) as f:
                 rec = json.load(f)
             for r, launches in zip(rec, segment(read_trace(os.path.join(tmp, "trace")), len(rec))):
-                cases[f"{mode}:{r['key']}"] = {"status": r["status"], "launches": launches, "sha256": r["sha256"]}
+                c = cases[f"{mode}:{r['key']}"] = {"status": r["status"], "launches": [l for l in launches if is_gemm(l)], "sha256": r["sha256"]}
+                if family == "edge":
+                    c["launches"] = [l for l in launches if is_edge(l)]
+                    if r["key"].startswith("encode("):
+                        c["launches"].sort()
+                    else:
+                        c["tables"] = sum(1 for l in launches if is_gemm(l))
         print(f"mode {mode}: {len(rec)} cases", flush=True)
     return cases
 
 
-def dump(cases, path):
-    """{"mode:key": {status, launches, sha256}} -> the file: one line per case key, the modes side by side, kernels by index."""
+def dump(cases, path, units=UNITS):
+    """{"mode:key": {status, launches, sha256[, tables]}} -> the file: one line per case key, the modes side by side, kernels by index."""
     kernels = sorted({(l[0], tuple(l[2]), l[3]) for v in cases.values() for l in v["launches"]})
     out = {}
     for mk, v in cases.items():
@@ -401,17 +503,19 @@ def dump(cases, path):
             c.setdefault("sha256", {})[mode] = v["sha256"]
         if v["status"]:
             c.setdefault("status", {})[mode] = v["status"]
+        if "tables" in v:
+            c.setdefault("tables", {})[mode] = v["tables"]
     js = lambda v: json.dumps(v, sort_keys=True, separators=(",", ":"))
     with open(path, "w") as f:
-        f.write('{"units": ' + json.dumps(UNITS, sort_keys=True, indent=1) + ',\n"kernels": [\n')
+        f.write('{"units": ' + json.dumps(units, sort_keys=True, indent=1) + ',\n"kernels": [\n')
         f.write(",\n".join(js([k[0], list(k[1]), k[2]]) for k in kernels) + '],\n"cases": {\n')
         f.write(",\n".join(json.dumps(k) + ":" + js(v) for k, v in sorted(out.items())))
         f.write("\n}}\n")
 
 
-def load(path=GOLDEN):
-    """The file -> {"mode:key": {status, launches, sha256}} as record() returns it."""
-    with open(path) as f:
+def load(family="gemm", path=None):
+    """The file -> {"mode:key": {status, launches, sha256[, tables]}} as record() returns it."""
+    with open(path or GOLDENS[family]) as f:
         rec = json.load(f)
     cases = {}
     for key, c in rec["cases"].items():
@@ -419,6 +523,8 @@ def load(path=GOLDEN):
             if mode in c:
                 launches = [[rec["kernels"][k][0], [gx, gy, 1], rec["kernels"][k][1], rec["kernels"][k][2]] for k, gx, gy in c[mode]]
                 cases[f"{mode}:{key}"] = {"status": c.get("status", {}).get(mode, 0), "launches": launches, "sha256": c.get("sha256", {}).get(mode)}
+                if "tables" in c:
+                    cases[f"{mode}:{key}"]["tables"] = c["tables"][mode]
     return cases
 
 
@@ -427,15 +533,16 @@ if __name__ == "__main__":
     ap.add_argument("--out")
     ap.add_argument("--worker", choices=MODES)
     ap.add_argument("--sidecar")
+    ap.add_argument("--family", choices=sorted(GOLDENS), default="gemm")
     ap.add_argument("--check-hashes", choices=MODES, help="compare the small public cases' outputs with the record (the process is in that mode)")
     a = ap.parse_args()
     if a.check_hashes:
-        bad = check_hashes(a.check_hashes)
+        bad = check_edge_hashes(a.check_hashes) if a.family == "edge" else check_hashes(a.check_hashes)
         print(f"{len(bad)} cases differ from the record (recorded, now): {dict(list(bad.items())[:6])}")
         sys.exit(1 if bad else 0)
     elif a.worker:
-        worker(a.worker, a.sidecar)
+        worker(a.worker, a.sidecar, a.family)
     else:
-        rec = record()
-        dump(rec, a.out or GOLDEN)
-        print(f"{len(rec)} cases -> {a.out or GOLDEN}")
+        rec = record(a.family)
+        dump(rec, a.out or GOLDENS[a.family], EDGE_UNITS if a.family == "edge" else UNITS)
+        print(f"{len(rec)} cases -> {a.out or GOLDENS[a.family]}")
