@@ -62,7 +62,7 @@ typedef enum {
  * any unknown option; 105: the mesh metrics ls_mesh_contains_f64 / ls_mesh_distance_f64 / ls_mesh_sample_f64; 106: ls_model_desc.dec_input and
  * off_dec_xyz_t, the invariant decoder_type "deepsdf"; 107: the ragged multi-mesh metrics ls_mesh_contains_batch_f64 /
  * ls_mesh_distance_batch_f64 / ls_mesh_sample_batch_f64; symbols added since -- ls_reg_metrics_batch, ls_mesh_cluster_f64 / ls_mesh_cluster_batch_f64,
- * ls_cloud_merge_f32 / ls_cloud_merge_batch_f32 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
+ * ls_cloud_merge_f32 / ls_cloud_merge_batch_f32, ls_cloud_nearest_f32 / ls_cloud_nearest_batch_f32 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
  * binding compares it with the header it was written against and refuses a mismatch (livingscenes_amd/_lib.py: load). */
 #define LS_ABI_VERSION 107
 int ls_version(void);
@@ -677,6 +677,48 @@ size_t ls_cloud_merge_batch_workspace_bytes(int P, long long a_total, long long 
 int ls_cloud_merge_batch_f32(int P, const float* A, long long a_total, const long long* a_off, const float* B, long long b_total,
                              const long long* b_off, const float* g, const float* voxel, float* out_pts, int32_t* out_src, long long* out_off,
                              int* status_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Scene memory, the question before a merge (csrc/cloudnear.hip): does a registered observation lie on what the memory holds?  Fixed-radius
+ * nearest neighbour between a kept cloud and a posed observation, with the overlap statistics of the pair.  AN EXTENSION BEYOND THE
+ * RELEASED REFERENCE, like the merge: the reference has no such step.  Definition, per problem (tests/nearest_oracle.py is the same text as
+ * NumPy):
+ *   inputs      A [a,3] fp32 the kept cloud (targets), B [b,3] fp32 the observation (queries), g [3,4] fp32 (R | t) taking B into A's frame
+ *               (NULL: the identity, and then B is used bit for bit), r > 0 the radius.  All DEVICE pointers except r.  a = 0 and b = 0 are
+ *               allowed.
+ *   queries     y_a = ((R_a0 x_0 + R_a1 x_1) + R_a2 x_2) + t_a, the expression and rounding of ls_cloud_merge_f32: every product and every
+ *               sum rounded to fp32 in that order (no fma).
+ *   cells       of edge r, by the merge's rule for targets and queries alike: inv = (float)1 / r, formed once on the host; c_a =
+ *               floorf(x_a * inv) clamped to [-2^30, 2^30] and cast to int32.  A row with a non-finite coordinate has no cell: such a
+ *               target is never a neighbour, such a query has no neighbour.  r, inv and r2 must be finite and positive.
+ *   distance    d2(i,j) = ((dx dx + dy dy) + dz dz) with dx = y_0 - A[j][0] and so on, every operation rounded to fp32 in that order;
+ *               r2 = r r rounded to fp32 on the host.
+ *   neighbour   of query i: among the targets j whose cell differs from the query's cell by at most 1 on every axis and whose
+ *               d2(i,j) <= r2, the one that is least under the order (d2, j): ties go to the lowest index.
+ * The cell condition is PART OF THE DEFINITION, not an approximation of it: it makes the 27-cell search exact, and differs from the pure
+ * radius test only where a coordinate difference lies within rounding of r (r = 0.25, target (-1e-30, 0, 0), query (0.25, 0, 0):
+ * d2 == r2 == 0.0625, the cells are -1 and 1, the query has no neighbour).
+ * Outputs: nn_idx int32 [b] the neighbour's row in A, local to the problem (-1: none); nn_d2 float [b] its d2 (+inf: none); counts
+ * long long [3] = (finite queries, queries with a neighbour, targets that are the neighbour of at least one query); sum_d2 double [1] the
+ * float64 sum of the nn_d2 of the queries that have a neighbour, by the per-problem rule of ls_reg_metrics_batch: chunks of 256 queries of
+ * the problem, each added in a fixed order, the partials added in chunk order -- no floating-point atomics.  status_out (DEVICE int,
+ * nullable): LS_OK, or LS_ERR_WORKSPACE if the cell table overflowed -- it holds 2 a slots for at most a cells and its probe walks are
+ * bounded by the table, so this reports a defect, it never spins.  a + b <= INT_MAX.  No host synchronisation, no allocation; the
+ * workspace is the caller's (ls_cloud_nearest_workspace_bytes: at most 96 bytes per target row and 1 byte per 16 query rows, plus the
+ * alignment of its pieces).  Integer atomics only: every output is the same bits in any run. */
+size_t ls_cloud_nearest_workspace_bytes(long long a, long long b);
+int ls_cloud_nearest_f32(const float* A, long long a, const float* B, long long b, const float* g, float radius, int32_t* nn_idx, float* nn_d2,
+                         long long* counts, double* sum_d2, int* status_out, void* workspace, size_t workspace_bytes, void* stream);
+/* P >= 1 problems per call, with the conventions of ls_cloud_merge_batch_f32: A [a_total,3] and B [b_total,3] hold the problems' rows back
+ * to back, a_off / b_off (HOST int64, P + 1 entries) and radius (HOST float, P entries) are checked here before the first HIP call -- the
+ * error names the problem -- and copied into the workspace on the stream; g [P,3,4] DEVICE or NULL.  nn_idx / nn_d2 [b_total] are packed
+ * problem after problem (nn_idx local to its problem), counts DEVICE long long [P,3], sum_d2 DEVICE double [P], status_out DEVICE int [P]
+ * (nullable).  a_total + b_total <= INT_MAX.  Every output of every problem is BIT-IDENTICAL to ls_cloud_nearest_f32 on that problem
+ * alone, in any batch composition and in any run, and the number of launches does not depend on P.  The workspace queries return 0 for
+ * sizes the op refuses. */
+size_t ls_cloud_nearest_batch_workspace_bytes(int P, long long a_total, long long b_total);
+int ls_cloud_nearest_batch_f32(int P, const float* A, long long a_total, const long long* a_off, const float* B, long long b_total,
+                               const long long* b_off, const float* g, const float* radius, int32_t* nn_idx, float* nn_d2, long long* counts,
+                               double* sum_d2, int* status_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* The registration metrics of the relocalisation evaluation on P (reference instance, rescan instance, predicted pose, ground-truth pose)
  * tuples per call -- what eval_3rscan.py:384-401 / eval_flyingshape.py:136-148 compute pair by pair.  Pair p owns the rows

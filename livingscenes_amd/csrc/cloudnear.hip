@@ -1,0 +1,422 @@
+// cloudnear.hip -- scene memory: fixed-radius nearest neighbour between the cloud an instance keeps (A, the targets) and a posed observation of
+// it (B, the queries), with the overlap statistics of the pair.  The definition is in include/livingscenes_hip.h (ls_cloud_nearest_f32) and,
+// as NumPy, in tests/nearest_oracle.py; this file follows it to the letter:
+//   queries     the rows of B under the pose g (R | t): y_a = ((R_a0 x_0 + R_a1 x_1) + R_a2 x_2) + t_a in fp32, every product and sum rounded
+//               (no contraction in this file, the expression of cloudmerge.hip); g == NULL: the rows of B bit for bit
+//   cell        of edge r, for targets and queries alike: c_a = (int)clamp(floorf(x_a inv), -2^30, 2^30), inv = 1.0f / r formed once on the
+//               host; a row with a non-finite coordinate has no cell: such a target is never a neighbour, such a query has none
+//   distance    d2 = ((dx dx + dy dy) + dz dz), dx = y_0 - A[j][0] ..., every operation rounded to fp32; r2 = r r rounded on the host
+//   neighbour   of query i: among the targets j whose cell differs from the query's by at most 1 on every axis and with d2 <= r2, the least
+//               under (d2, j)
+// Method: the merge's open-addressing table, 2 a_p slots per problem.  A target claims an empty slot for its cell with an integer CAS or finds
+// the slot of its cell, at most over the whole table; the atomic count of a slot hands every target its rank in the cell.  Count -> scan
+// (ls_scan.h) -> fill puts the members of every cell back to back as (x, y, z, index).  One thread per query then walks the 27 cells around
+// its own -- each by a probe walk that ends at the cell or at an empty slot -- and keeps the minimum under (d2, j) in registers: which slot a
+// cell got and the order of its members depend on the race, the minimum does not.  The sum of the distances follows the per-problem rule of
+// regmetrics.hip: a workgroup owns one chunk of QUERY_CHUNK queries of ONE problem, adds it in a fixed LDS tree and writes one float64
+// partial; the last kernel adds a problem's partials in chunk order.  Integer atomics only, and only on the table: a problem's outputs are
+// the same bits alone, in any batch and in any run.  The kernels that need the problem are written once, for a problem locator (OneNear /
+// RaggedNear, as OneCloud / RaggedClouds of cloudmerge.hip); the number of launches does not depend on P.
+#include <climits>
+#include <cmath>
+#include <vector>
+
+#include "ls_common.h"
+#include "ls_ragged.h"
+#include "ls_scan.h"
+
+// the arithmetic of the definition as written: no contraction of a * b + c into an fma anywhere in this file
+#pragma clang fp contract(off)
+
+namespace ls {
+namespace cnr {
+
+constexpr int NO_CELL = INT_MIN;              // [0] of a cell triple: the row has no cell / the slot is empty (cells are clamped to [-2^30, 2^30])
+constexpr unsigned NO_SLOT = 0xFFFFFFFFu;     // slot_of[i]: the target is in no slot (no cell, or the table overflowed)
+constexpr float CELL_MAX = 1073741824.0f;     // 2^30
+constexpr int QUERY_CHUNK = 256;              // queries per workgroup, one per thread: the chunk of the float64 sum
+
+// ------------------------------------------------------------------------------------------------ which problem: one, or one of a ragged batch
+struct NearRef {
+    const float* B;        // the problem's queries
+    long long a, b;        // its targets and queries
+    const float* g;        // [3,4] or null
+    float inv, r2;
+    long long a0, b0;      // global index of its first target / first query; its table: 2 a slots from slot 2 a0
+    long long q0, q1;      // its chunks of queries
+};
+
+struct OneNear {
+    const float* B;
+    long long a, b;
+    const float* g;
+    float inv, r2;
+    __device__ int target_owner(long long) const { return 0; }
+    __device__ int chunk_owner(long long) const { return 0; }
+    __device__ NearRef problem(int) const { return {B, a, b, g, inv, r2, 0, 0, 0, (b + QUERY_CHUNK - 1) / QUERY_CHUNK}; }
+};
+
+enum { OFF_A = 0, OFF_B, OFF_Q, OFF_ARRAYS };   // the device copy of a batch's offsets: rows of A, rows of B, chunks of queries
+
+struct RaggedNear {
+    const float* B;
+    const float* g;            // [P,3,4] or null
+    const long long* offs;
+    const float* inv;          // [P]
+    const float* r2;           // [P]
+    int P;
+    __device__ const long long* off(int k) const { return offs + (size_t)k * (P + 1); }
+    __device__ int target_owner(long long i) const { return owner(off(OFF_A), P, i); }
+    __device__ int chunk_owner(long long c) const { return owner(off(OFF_Q), P, c); }
+    __device__ NearRef problem(int p) const {
+        const long long *ao = off(OFF_A), *bo = off(OFF_B), *qo = off(OFF_Q);
+        return {B + bo[p] * 3, ao[p + 1] - ao[p], bo[p + 1] - bo[p], g ? g + (size_t)p * 12 : nullptr, inv[p], r2[p], ao[p], bo[p], qo[p], qo[p + 1]};
+    }
+};
+
+__device__ __forceinline__ bool cell_of(const float (&y)[3], float inv, int (&c)[3]) {
+    const bool finite = isfinite(y[0]) && isfinite(y[1]) && isfinite(y[2]);
+    for (int k = 0; k < 3; ++k) c[k] = finite ? (int)fminf(fmaxf(floorf(y[k] * inv), -CELL_MAX), CELL_MAX) : NO_CELL;
+    return finite;
+}
+
+// the first slot of a cell's probe walk in a table of T slots (T < 2^32)
+__device__ __forceinline__ long long first_slot(int c0, int c1, int c2, long long T) {
+    const unsigned long long hsh = mix64(mix64(((unsigned long long)(unsigned)c0 << 32) | (unsigned)c1) + (unsigned long long)(unsigned)c2);
+    return (long long)(((hsh >> 32) * (unsigned long long)T) >> 32);
+}
+
+// tcell [a_total,3]: the targets' cells (NO_CELL in [0]: none)
+template <class Near>
+__global__ __launch_bounds__(256) void tcell_kernel(Near L, const float* __restrict__ A, long long a_total, int* __restrict__ tcell) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a_total) return;
+    const NearRef C = L.problem(L.target_owner(i));
+    const float y[3] = {A[i * 3 + 0], A[i * 3 + 1], A[i * 3 + 2]};
+    int c[3];
+    cell_of(y, C.inv, c);
+    for (int k = 0; k < 3; ++k) tcell[i * 3 + k] = c[k];
+}
+
+// the table of a problem: slot s holds the GLOBAL index of the target that claimed it for its cell (-1: free) and never changes again, so all
+// targets of a cell meet in one slot; cnt[s] counts them and hands each its rank.  A problem has at most a_p cells for 2 a_p slots; the walk
+// ends after T slots whatever happens.
+template <class Near>
+__global__ __launch_bounds__(256) void claim_kernel(Near L, long long a_total, const int* __restrict__ tcell, int* __restrict__ table,
+                                                    int* __restrict__ cnt, unsigned* __restrict__ slot_of, int* __restrict__ rank,
+                                                    int* __restrict__ status) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a_total) return;
+    const int c0 = tcell[i * 3 + 0], c1 = tcell[i * 3 + 1], c2 = tcell[i * 3 + 2];
+    if (c0 == NO_CELL) {
+        slot_of[i] = NO_SLOT;
+        return;
+    }
+    const int p = L.target_owner(i);
+    const NearRef C = L.problem(p);
+    const long long t0 = 2 * C.a0, T = 2 * C.a;
+    const int me = (int)i;
+    long long s = first_slot(c0, c1, c2, T);
+    unsigned found = NO_SLOT;
+    for (long long step = 0; step < T; ++step) {
+        const long long slot = t0 + s;
+        int occupant = atomicCAS(&table[slot], -1, me);
+        if (occupant == -1) occupant = me;
+        const int* oc = tcell + (long long)occupant * 3;                 // the slot is mine: my own cell
+        if ((oc[0] == c0) & (oc[1] == c1) & (oc[2] == c2)) {
+            found = (unsigned)slot;
+            break;
+        }
+        if (++s == T) s = 0;
+    }
+    slot_of[i] = found;
+    if (found == NO_SLOT) status[p] = LS_ERR_WORKSPACE;
+    else rank[i] = atomicAdd(&cnt[found], 1);
+}
+
+// slots[s] = (cell of the slot, first member): what a query's probe step reads in one load ([0] == NO_CELL: the slot is empty)
+__global__ __launch_bounds__(256) void slot_kernel(long long n_slots, const int* __restrict__ table, const int* __restrict__ tcell,
+                                                   const int* __restrict__ start, int4* __restrict__ slots) {
+    const long long s = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (s >= n_slots) return;
+    const int rep = table[s];
+    int4 v = {NO_CELL, 0, 0, 0};
+    if (rep >= 0) v = {tcell[(long long)rep * 3 + 0], tcell[(long long)rep * 3 + 1], tcell[(long long)rep * 3 + 2], start[s]};
+    slots[s] = v;
+}
+
+// members: the targets of every cell back to back as (x, y, z, global index), the order inside a cell as the ranks fell
+__global__ __launch_bounds__(256) void fill_kernel(const float* __restrict__ A, long long a_total, const unsigned* __restrict__ slot_of,
+                                                   const int* __restrict__ rank, const int* __restrict__ start, float4* __restrict__ members) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a_total) return;
+    const unsigned s = slot_of[i];
+    if (s == NO_SLOT) return;
+    members[(long long)start[s] + rank[i]] = make_float4(A[i * 3 + 0], A[i * 3 + 1], A[i * 3 + 2], __int_as_float((int)i));
+}
+
+// workgroup = one chunk of QUERY_CHUNK queries of one problem, one thread per query.  part[chunk] = the float64 sum of the chunk's nn_d2 in a
+// fixed order, part_cnt[chunk] = (finite queries, queries with a neighbour).
+template <class Near>
+__global__ __launch_bounds__(QUERY_CHUNK) void query_kernel(Near L, const int4* __restrict__ slots, const int* __restrict__ cnt,
+                                                            const float4* __restrict__ members, unsigned char* __restrict__ hit,
+                                                            int* __restrict__ nn_idx, float* __restrict__ nn_d2, double* __restrict__ part,
+                                                            int2* __restrict__ part_cnt) {
+    __shared__ double lds[QUERY_CHUNK];
+    const NearRef C = L.problem(L.chunk_owner(blockIdx.x));
+    const long long qi = ((long long)blockIdx.x - C.q0) * QUERY_CHUNK + threadIdx.x;
+    const bool live = qi < C.b;
+    bool finite = false;
+    int best_j = INT_MAX;
+    float best = INFINITY;
+    if (live) {
+        const float* __restrict__ x = C.B + qi * 3;
+        const float x0 = x[0], x1 = x[1], x2 = x[2];
+        float y[3] = {x0, x1, x2};
+        if (C.g)
+            for (int r = 0; r < 3; ++r) y[r] = ((C.g[r * 4 + 0] * x0 + C.g[r * 4 + 1] * x1) + C.g[r * 4 + 2] * x2) + C.g[r * 4 + 3];
+        int c[3];
+        finite = cell_of(y, C.inv, c);
+        const long long t0 = 2 * C.a0, T = 2 * C.a;
+        if (finite && T > 0) {
+            for (int k = 0; k < 27; ++k) {
+                const int n0 = c[0] + k / 9 - 1, n1 = c[1] + (k / 3) % 3 - 1, n2 = c[2] + k % 3 - 1;   // |c| <= 2^30: no overflow
+                long long s = first_slot(n0, n1, n2, T);
+                for (long long step = 0; step < T; ++step) {
+                    const int4 sl = slots[t0 + s];
+                    if (sl.x == NO_CELL) break;                        // an empty slot ends the walk: the cell has no target
+                    if (sl.x == n0 && sl.y == n1 && sl.z == n2) {
+                        const float4* __restrict__ m = members + sl.w;
+                        const int count = cnt[t0 + s];
+                        for (int e = 0; e < count; ++e) {
+                            const float4 t = m[e];
+                            const float dx = y[0] - t.x, dy = y[1] - t.y, dz = y[2] - t.z;
+                            const float d2 = (dx * dx + dy * dy) + dz * dz;
+                            const int j = __float_as_int(t.w);
+                            if (d2 <= C.r2 && (d2 < best || (d2 == best && j < best_j))) {
+                                best = d2;
+                                best_j = j;
+                            }
+                        }
+                        break;
+                    }
+                    if (++s == T) s = 0;
+                }
+            }
+        }
+    }
+    const bool has = best_j != INT_MAX;
+    if (has) hit[best_j] = 1;                                          // every writer writes the same byte
+    if (live) {
+        nn_idx[C.b0 + qi] = has ? (int)(best_j - C.a0) : -1;
+        nn_d2[C.b0 + qi] = best;
+    }
+    const int n_finite = __syncthreads_count(finite), n_has = __syncthreads_count(has);
+    lds[threadIdx.x] = has ? (double)best : 0.0;
+    __syncthreads();
+    for (int o = QUERY_CHUNK / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) lds[threadIdx.x] += lds[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = lds[0];
+        part_cnt[blockIdx.x] = make_int2(n_finite, n_has);
+    }
+}
+
+// workgroup = one problem: counts (the integer partials and the hit flags, any order) and sum_d2 (the float64 partials in chunk order)
+template <class Near>
+__global__ __launch_bounds__(256) void final_kernel(Near L, const unsigned char* __restrict__ hit, const double* __restrict__ part,
+                                                    const int2* __restrict__ part_cnt, const int* __restrict__ status,
+                                                    long long* __restrict__ counts, double* __restrict__ sum_d2, int* __restrict__ status_out) {
+    __shared__ long long lds[3][256];
+    const int p = blockIdx.x;
+    const NearRef C = L.problem(p);
+    long long v[3] = {0, 0, 0};
+    for (long long q = C.q0 + threadIdx.x; q < C.q1; q += 256) {
+        v[0] += part_cnt[q].x;
+        v[1] += part_cnt[q].y;
+    }
+    for (long long j = threadIdx.x; j < C.a; j += 256) v[2] += hit[C.a0 + j];
+    for (int k = 0; k < 3; ++k) lds[k][threadIdx.x] = v[k];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o)
+            for (int k = 0; k < 3; ++k) lds[k][threadIdx.x] += lds[k][threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x < 3) counts[(size_t)p * 3 + threadIdx.x] = lds[threadIdx.x][0];
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (long long q = C.q0; q < C.q1; ++q) s += part[q];
+        sum_d2[p] = s;
+        if (status_out) status_out[p] = status[p];
+    }
+}
+
+}  // namespace cnr
+}  // namespace ls
+
+using namespace ls;
+using namespace ls::cnr;
+
+namespace {
+inline long long chunks_of(long long b) { return (b + QUERY_CHUNK - 1) / QUERY_CHUNK; }
+
+struct Ws {
+    long long* offs;          // a batch: the device copy of the offsets
+    float* inv;               // a batch: [P]
+    float* r2;                // a batch: [P]
+    int* status;              // [P]
+    long long* total;         // the scan's total: targets with a cell
+    int* tcell;               // [a,3]
+    int* table;               // [2 a]
+    int* cnt;                 // [2 a]
+    int* start;               // [2 a]
+    int* blk;                 // the scan's block sums
+    int4* slots;              // [2 a]
+    unsigned* slot_of;        // [a]
+    int* rank;                // [a]
+    float4* members;          // [a]
+    unsigned char* hit;       // [a]
+    double* part;             // one per chunk of queries
+    int2* part_cnt;           // one per chunk of queries
+    size_t bytes;             // of the whole layout
+};
+
+// the layout depends on (P, a, b) alone (ws null: a sizing pass; n_offs = 0: a single problem); sum_p ceil(b_p / c) <= floor(b / c) + P
+Ws layout(void* ws, size_t n_offs, int P, long long a, long long b) {
+    Arena ar(ws);
+    Ws w;
+    const size_t chunks = (size_t)(b / QUERY_CHUNK + P);
+    w.offs = ar.take<long long>(n_offs);
+    w.inv = ar.take<float>(n_offs ? (size_t)P : 0);
+    w.r2 = ar.take<float>(n_offs ? (size_t)P : 0);
+    w.status = ar.take<int>((size_t)P);
+    w.total = ar.take<long long>(1);
+    w.tcell = ar.take<int>((size_t)a * 3);
+    w.table = ar.take<int>((size_t)a * 2);
+    w.cnt = ar.take<int>((size_t)a * 2);
+    w.start = ar.take<int>((size_t)a * 2);
+    w.blk = ar.take<int>((size_t)scan_blocks(2 * a));
+    w.slots = ar.take<int4>((size_t)a * 2);
+    w.slot_of = ar.take<unsigned>((size_t)a);
+    w.rank = ar.take<int>((size_t)a);
+    w.members = ar.take<float4>((size_t)a);
+    w.hit = ar.take<unsigned char>((size_t)a);
+    w.part = ar.take<double>(chunks);
+    w.part_cnt = ar.take<int2>(chunks);
+    w.bytes = ar.bytes();
+    return w;
+}
+
+// the launch sequence: P problems located by L, a targets, b queries and `chunks` chunks of queries in all
+template <class Near>
+int nearest_launch(const Near& L, int P, const float* A, long long a, long long b, long long chunks, const Ws& w, int* nn_idx, float* nn_d2,
+                   long long* counts, double* sum_d2, int* status_out, hipStream_t st) {
+    LS_HIP_CHECK(hipMemsetAsync(w.status, 0, (size_t)P * sizeof(int), st));               // LS_OK
+    if (a > 0) {
+        const int nb = cdiv(a, 256);
+        LS_HIP_CHECK(hipMemsetAsync(w.table, 0xFF, (size_t)a * 2 * sizeof(int), st));     // -1: free
+        LS_HIP_CHECK(hipMemsetAsync(w.cnt, 0, (size_t)a * 2 * sizeof(int), st));
+        LS_HIP_CHECK(hipMemsetAsync(w.hit, 0, (size_t)a, st));
+        hipLaunchKernelGGL(tcell_kernel<Near>, dim3(nb), dim3(256), 0, st, L, A, a, w.tcell);
+        hipLaunchKernelGGL(claim_kernel<Near>, dim3(nb), dim3(256), 0, st, L, a, w.tcell, w.table, w.cnt, w.slot_of, w.rank, w.status);
+        scan<int, int, false>(w.cnt, 2 * a, w.blk, w.start, w.total, st);
+        hipLaunchKernelGGL(slot_kernel, dim3(cdiv(2 * a, 256)), dim3(256), 0, st, 2 * a, w.table, w.tcell, w.start, w.slots);
+        hipLaunchKernelGGL(fill_kernel, dim3(nb), dim3(256), 0, st, A, a, w.slot_of, w.rank, w.start, w.members);
+    }
+    if (chunks > 0)
+        hipLaunchKernelGGL(query_kernel<Near>, dim3((unsigned)chunks), dim3(QUERY_CHUNK), 0, st, L, w.slots, w.cnt, w.members, w.hit, nn_idx, nn_d2,
+                           w.part, w.part_cnt);
+    hipLaunchKernelGGL(final_kernel<Near>, dim3(P), dim3(256), 0, st, L, w.hit, w.part, w.part_cnt, w.status, counts, sum_d2, status_out);
+    LS_LAUNCH_CHECK();
+    return LS_OK;
+}
+
+// inv = 1.0f / r and r2 = r * r, the two roundings of the definition; all three finite and positive
+int radius_terms(const char* op, int p, float r, float* inv, float* r2) {
+    LS_REQUIRE(std::isfinite(r) && r > 0.0f, "%s: problem %d: the radius must be finite and > 0, got %g", op, p, (double)r);
+    *inv = 1.0f / r;
+    LS_REQUIRE(std::isfinite(*inv), "%s: problem %d: 1 / radius overflows fp32 (radius %g)", op, p, (double)r);
+    *r2 = r * r;
+    LS_REQUIRE(std::isfinite(*r2) && *r2 > 0.0f, "%s: problem %d: radius^2 is not a finite positive fp32 (radius %g)", op, p, (double)r);
+    return LS_OK;
+}
+
+int check_common(const char* op, long long a, long long b, const float* A, const float* B, const int* nn_idx, const float* nn_d2,
+                 const long long* counts, const double* sum_d2) {
+    LS_REQUIRE(a >= 0 && b >= 0, "%s: negative size (%lld kept rows, %lld query rows)", op, a, b);
+    LS_REQUIRE(a + b <= INT_MAX, "%s: %lld + %lld rows exceed %d (int row indices)", op, a, b, INT_MAX);
+    LS_REQUIRE((a == 0 || A) && (b == 0 || B), "%s: null A / B with %lld and %lld rows", op, a, b);
+    LS_REQUIRE(counts && sum_d2 && (b == 0 || (nn_idx && nn_d2)), "%s: null nn_idx / nn_d2 / counts / sum_d2", op);
+    return LS_OK;
+}
+}  // namespace
+
+extern "C" {
+
+size_t ls_cloud_nearest_workspace_bytes(long long a, long long b) {
+    if (a < 0 || b < 0 || a + b > INT_MAX) return 0;
+    return layout(nullptr, 0, 1, a, b).bytes;
+}
+
+int ls_cloud_nearest_f32(const float* A, long long a, const float* B, long long b, const float* g, float radius, int32_t* nn_idx, float* nn_d2,
+                         long long* counts, double* sum_d2, int* status_out, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* op = "cloud_nearest";
+    int rc = check_common(op, a, b, A, B, nn_idx, nn_d2, counts, sum_d2);
+    if (rc != LS_OK) return rc;
+    float inv, r2;
+    rc = radius_terms(op, 0, radius, &inv, &r2);
+    if (rc != LS_OK) return rc;
+    const size_t need = ls_cloud_nearest_workspace_bytes(a, b);
+    if (!workspace || workspace_bytes < need) {
+        set_error("%s: workspace %zu < required %zu (ls_cloud_nearest_workspace_bytes(%lld, %lld))", op, workspace ? workspace_bytes : (size_t)0, need,
+                  a, b);
+        return LS_ERR_WORKSPACE;
+    }
+    const Ws w = layout(workspace, 0, 1, a, b);
+    return nearest_launch(OneNear{B, a, b, g, inv, r2}, 1, A, a, b, chunks_of(b), w, nn_idx, nn_d2, counts, sum_d2, status_out, (hipStream_t)stream);
+}
+
+size_t ls_cloud_nearest_batch_workspace_bytes(int P, long long a_total, long long b_total) {
+    if (P < 1 || a_total < 0 || b_total < 0 || a_total + b_total > INT_MAX) return 0;
+    return layout(nullptr, (size_t)OFF_ARRAYS * (P + 1), P, a_total, b_total).bytes;
+}
+
+int ls_cloud_nearest_batch_f32(int P, const float* A, long long a_total, const long long* a_off, const float* B, long long b_total,
+                               const long long* b_off, const float* g, const float* radius, int32_t* nn_idx, float* nn_d2, long long* counts,
+                               double* sum_d2, int* status_out, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* op = "cloud_nearest_batch";
+    LS_REQUIRE(P >= 1, "%s: P must be at least 1, got %d", op, P);
+    int rc = check_common(op, a_total, b_total, A, B, nn_idx, nn_d2, counts, sum_d2);
+    if (rc != LS_OK) return rc;
+    rc = check_ranges(op, "problem", "a_off", P, a_off, a_total, INT_MAX);
+    if (rc != LS_OK) return rc;
+    rc = check_ranges(op, "problem", "b_off", P, b_off, b_total, INT_MAX);
+    if (rc != LS_OK) return rc;
+    LS_REQUIRE(radius, "%s: null radius", op);
+    std::vector<long long> q_off(P + 1, 0);
+    std::vector<float> inv(P), r2(P);
+    for (int p = 0; p < P; ++p) {
+        q_off[p + 1] = q_off[p] + chunks_of(b_off[p + 1] - b_off[p]);
+        rc = radius_terms(op, p, radius[p], &inv[p], &r2[p]);
+        if (rc != LS_OK) return rc;
+    }
+    const size_t need = ls_cloud_nearest_batch_workspace_bytes(P, a_total, b_total);
+    if (!workspace || workspace_bytes < need) {
+        set_error("%s: workspace %zu < required %zu (ls_cloud_nearest_batch_workspace_bytes(%d, %lld, %lld))", op,
+                  workspace ? workspace_bytes : (size_t)0, need, P, a_total, b_total);
+        return LS_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const Ws w = layout(workspace, (size_t)OFF_ARRAYS * (P + 1), P, a_total, b_total);
+    rc = upload_offsets(w.offs, pack_offsets(P, {a_off, b_off, q_off.data()}), st);
+    if (rc != LS_OK) return rc;
+    LS_HIP_CHECK(hipMemcpyAsync(w.inv, inv.data(), (size_t)P * sizeof(float), hipMemcpyHostToDevice, st));   // pageable: read when it returns
+    LS_HIP_CHECK(hipMemcpyAsync(w.r2, r2.data(), (size_t)P * sizeof(float), hipMemcpyHostToDevice, st));
+    return nearest_launch(RaggedNear{B, g, w.offs, w.inv, w.r2, P}, P, A, a_total, b_total, q_off[P], w, nn_idx, nn_d2, counts, sum_d2, status_out,
+                          st);
+}
+
+}  // extern "C"

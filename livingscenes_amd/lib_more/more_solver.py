@@ -6,6 +6,7 @@ forward / backward and the Sinkhorn softmins in the HIP library; torchlie / geom
 update and the Sinkhorn divergence of that branch follow this build's documented definitions (parity unpinned); mesh extraction (_mesh_from_latent / _mesh_from_pc, 8 f-2) runs MISE and marching cubes on the device
 (livingscenes_amd/mesh_extractor2.py)."""
 import logging
+import math
 
 import torch
 
@@ -281,6 +282,40 @@ class More_Solver:
             g = inverse(T.detach().float()).contiguous()
         return [pts for pts, _ in ops.cloud_merge_batch([p.detach() for p in mem_pcs], [p.detach() for p in new_pcs], g=g, voxel=voxel)]
 
+    def _overlap_batch(self, mem_pcs, new_pcs, T, radius=None):
+        """Scene memory, the question before a merge (an extension beyond the released reference, like _accumulate_batch): how well do P
+        registered observations new_pcs[p] [b_p,3] agree with the kept clouds mem_pcs[p] [a_p,3]?  ONE ragged fixed-radius nearest-neighbour
+        call (ops.cloud_nearest_batch, csrc/cloudnear.hip).  T [P,4,4] or [P,3,4] is the registration exactly as
+        _solve_pairwise_registration* / Rt_to_SE3 return it: it maps memory -> rescan, so the operator receives inverse(T), exactly as
+        _accumulate_batch does (T None: the observations are in the memory's frame already).  radius: default
+        cfg['accumulate']['overlap_radius'], else 2 * voxel with the voxel of _accumulate_batch -- A DERIVED DEFAULT, not a tuned one: a
+        point the merge drops shares a voxel of edge h with a kept one, so a perfectly registered re-observation of a surface the memory
+        already holds lies within sqrt(3) h < 2 h of a kept point.
+        -> dict of per-pair lists: overlap = matched / finite observation points (0.0 with no finite point), rmse = sqrt(sum d2 / matched)
+        (nan with none), memory_seen = memory points that are some observation point's neighbour / a_p (0.0 for an empty memory), counts =
+        the raw int64 triples (finite queries, matched, memory points hit), nn_idx [b_p] int32 = the memory row nearest to every
+        observation point within the radius, -1: none -- the points that are new."""
+        acc = self.cfg.get("accumulate", {})
+        if radius is None:
+            radius = acc.get("overlap_radius", 2 * acc.get("voxel_size", 0.01))
+        if len(mem_pcs) != len(new_pcs):
+            raise ValueError(f"{len(mem_pcs)} memory clouds for {len(new_pcs)} observations")
+        g = None
+        if T is not None:
+            if T.dim() != 3 or T.shape[0] != len(mem_pcs) or T.shape[1] not in (3, 4) or T.shape[2] != 4:
+                raise ValueError(f"T must be [P,4,4] or [P,3,4] with P = {len(mem_pcs)}, got {tuple(T.shape)}")
+            g = inverse(T.detach().float()).contiguous()
+        res = ops.cloud_nearest_batch([p.detach() for p in mem_pcs], [p.detach() for p in new_pcs], g=g, radius=radius)
+        out = {"overlap": [], "rmse": [], "memory_seen": [], "counts": [], "nn_idx": []}
+        for mem_pc, (idx, _, counts, sum_d2) in zip(mem_pcs, res):
+            finite, matched, seen = (int(c) for c in counts)
+            out["overlap"].append(matched / finite if finite else 0.0)
+            out["rmse"].append(math.sqrt(sum_d2 / matched) if matched else float("nan"))
+            out["memory_seen"].append(seen / mem_pc.shape[0] if mem_pc.shape[0] else 0.0)
+            out["counts"].append(counts)
+            out["nn_idx"].append(idx)
+        return out
+
     def _mesh_from_latent(self, latent_code):
         """more_solver.py:37-58: mesh of the canonical shape (t = 0, s = 1), then scaled and moved to the instance pose."""
         if self.mesh_extractor is None:
@@ -442,14 +477,18 @@ def solve_end2end_batch(solver, pairs, mesh=False, optim=False, sharded=False, o
     return outs
 
 
-def sequence_plan(n_mem, matches0, n_new=None, n_new_points=None):
+def sequence_plan(n_mem, matches0, n_new=None, n_new_points=None, accepted=None):
     """The index bookkeeping of one solve_sequence step, as a pure function: matches0[i] is the rescan instance matched to memory slot i
     (-1: none), as _solve_object_matching(memory codes, rescan codes) returns it; n_new = instances in the rescan (None: unknown).
       pairs         [(memory slot, rescan instance)] in slot order: pair k is problem k of the registration and of the merge
       updated       the slots a match updates (their cloud goes through the merge); the others keep cloud and code
       reencode      the updated slots whose cloud changed -- n_new_points[k] > 0 for pair k (None: not known yet, every updated slot)
       unmatched_new the rescan instances no slot was matched to (None without n_new): their frame relative to the memory is unknown, so
-                    they are reported and left out"""
+                    they are reported and left out
+    accepted (one bool per pair, None: no gate): the pairs the overlap gate of solve_sequence lets into the merge.  A rejected pair stays in
+    `pairs` (it was registered) but leaves `updated` / `reencode`, n_new_points then has one entry per ACCEPTED pair, and the dict gains
+      rejected      the slots whose pair was rejected: they keep cloud and code
+    With accepted None the dict is exactly the four entries above."""
     m0 = [int(j) for j in matches0]
     if len(m0) != n_mem:
         raise ValueError(f"{len(m0)} matches for {n_mem} memory slots")
@@ -459,12 +498,17 @@ def sequence_plan(n_mem, matches0, n_new=None, n_new_points=None):
         raise ValueError(f"a rescan instance is matched to more than one memory slot: {m0}")
     if n_new is not None and any(j >= n_new for j in taken):
         raise ValueError(f"a match names a rescan instance >= {n_new}: {m0}")
-    if n_new_points is not None and len(n_new_points) != len(pairs):
-        raise ValueError(f"{len(n_new_points)} point counts for {len(pairs)} pairs")
-    updated = [i for i, _ in pairs]
-    return {"pairs": pairs, "updated": updated,
+    if accepted is not None and len(accepted) != len(pairs):
+        raise ValueError(f"{len(accepted)} accepted flags for {len(pairs)} pairs")
+    updated = [i for k, (i, _) in enumerate(pairs) if accepted is None or accepted[k]]
+    if n_new_points is not None and len(n_new_points) != len(updated):
+        raise ValueError(f"{len(n_new_points)} point counts for {len(updated)} {'pairs' if accepted is None else 'accepted pairs'}")
+    plan = {"pairs": pairs, "updated": updated,
             "reencode": updated if n_new_points is None else [i for i, k in zip(updated, n_new_points) if int(k) > 0],
             "unmatched_new": None if n_new is None else [j for j in range(n_new) if j not in set(taken)]}
+    if accepted is not None:
+        plan["rejected"] = [i for k, (i, _) in enumerate(pairs) if not accepted[k]]
+    return plan
 
 
 _CODE_KEYS = ("z_so3", "z_inv", "s", "t")
@@ -482,7 +526,7 @@ def _encode_clouds(model, clouds):
     return model.encode_fps(buf, mask)
 
 
-def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, optimize_codes=False):
+def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, optimize_codes=False, overlap_radius=None, min_overlap=None):
     """A reference scan followed by SEVERAL rescans, with a memory that carries every instance's points from one rescan to the next -- an
     extension beyond the released reference (more_solver.py:246-299 solves one (reference, rescan) pair and drops the rescan's points).
     ref and every rescan: {'pc' [n,3,Nmax], 'pc_mask'} as _solve_end2end takes them.
@@ -501,7 +545,16 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
     rescan_pc_lst, matches, registration, codes = the rescan's codes moved to the reference frame, mesh_lst = None per slot: meshes are
     made of the final memory) plus merged_sizes [n] (points per slot after the step), n_new_points [n] (points the step added) and
     unmatched_rescan (rescan instance indices).  memory: {'clouds': list of [n_i,3], 'codes': code dict of n rows, 'meshes':
-    _mesh_from_latent_batch(codes) if mesh else None}.  voxel: see More_Solver._accumulate_batch."""
+    _mesh_from_latent_batch(codes) if mesh else None}.  voxel: see More_Solver._accumulate_batch.
+
+    The overlap gate (opt-in: with overlap_radius and min_overlap both None no search is made and the step dicts are as above).  With either
+    given, ONE More_Solver._overlap_batch call over the matched pairs follows the registration batch (overlap_radius None: its derived
+    default, 2 * voxel) and the step also reports overlap, overlap_rmse, memory_seen (lists of n, None for unmatched slots) and rejected
+    (slots).  Pairs with overlap < min_overlap (None: nothing is rejected, the figures are only reported) are left out of the ONE
+    _accumulate_batch call: a rejected slot keeps its cloud and code, gets n_new_points 0 and is not re-encoded; its registration and codes
+    entries are still reported.  min_overlap HAS NO DEFAULT AND NONE IS RECOMMENDED: no trained checkpoint exists here to measure one
+    against, so the threshold is the caller's to choose."""
+    gate = overlap_radius is not None or min_overlap is not None
     model = solver.model
     n_in = solver.cfg["shape_priors"]["n_input_point"]
     raw = _scene_clouds(ref)
@@ -526,15 +579,31 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
             src, tgt = [mem[i] for i, _ in pairs], [res_full[j] for _, j in pairs]
             R, t = solver._solve_pairwise_registration_optim_batch(src, tgt) if optim else solver._solve_pairwise_registration_batch(src, tgt)
             T = Rt_to_SE3(R, t)
-            merged = solver._accumulate_batch(src, tgt, T, voxel=voxel)
-            grew = [c.shape[0] - a.shape[0] for c, a in zip(merged, src)]     # the memory's rows are kept whole: the rest came from the rescan
+            accepted = None
+            if gate:
+                radius = overlap_radius
+                if radius is None and voxel is not None:
+                    radius = solver.cfg.get("accumulate", {}).get("overlap_radius", 2 * voxel)
+                ov = solver._overlap_batch(src, tgt, T, radius=radius)
+                accepted = [min_overlap is None or o >= min_overlap for o in ov["overlap"]]
+                out.update({"overlap": [None] * n, "overlap_rmse": [None] * n, "memory_seen": [None] * n})
+                for k, (i, _) in enumerate(pairs):
+                    out["overlap"][i], out["overlap_rmse"][i], out["memory_seen"][i] = ov["overlap"][k], ov["rmse"][k], ov["memory_seen"][k]
+                out["rejected"] = sequence_plan(n, m0.tolist(), len(res_full), accepted=accepted)["rejected"]
             for k, (i, j) in enumerate(pairs):
                 out["registration"][i] = T[k:k + 1]
                 cur = {key: res_codes[key][j][None] for key in _CODE_KEYS}
                 out["codes"][i] = solver._transform_latent(cur, inverse(T[k:k + 1]))
-                out["n_new_points"][i] = grew[k]
-                mem[i] = merged[k]
-            again = sequence_plan(n, m0.tolist(), len(res_full), grew)["reencode"]
+            keep = [k for k in range(len(pairs)) if accepted is None or accepted[k]]
+            grew = []
+            if keep:
+                sel = torch.tensor(keep, device=T.device)
+                merged = solver._accumulate_batch([src[k] for k in keep], [tgt[k] for k in keep], T if accepted is None else T[sel], voxel=voxel)
+                grew = [c.shape[0] - src[k].shape[0] for c, k in zip(merged, keep)]   # the memory's rows are kept whole: the rest came from the rescan
+                for c, k, d in zip(merged, keep, grew):
+                    out["n_new_points"][pairs[k][0]] = d
+                    mem[pairs[k][0]] = c
+            again = sequence_plan(n, m0.tolist(), len(res_full), grew, accepted=accepted)["reencode"]
             if again:
                 new = _encode_clouds(model, [mem[i] for i in again])
                 new = {k: new[k].detach().clone() for k in _CODE_KEYS}
@@ -545,6 +614,8 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
                 rows = torch.tensor(again, device=codes["z_inv"].device)
                 for k in _CODE_KEYS:
                     codes[k][rows] = new[k].to(codes[k].dtype)
+        elif gate:
+            out.update({"overlap": [None] * n, "overlap_rmse": [None] * n, "memory_seen": [None] * n, "rejected": []})
         out["merged_sizes"] = [c.shape[0] for c in mem]
         steps.append(out)
     memory = {"clouds": mem, "codes": codes, "meshes": solver._mesh_from_latent_batch(codes) if mesh else None}

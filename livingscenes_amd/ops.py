@@ -886,3 +886,81 @@ def cloud_merge(A, B, g=None, *, voxel):
     if host[2:].view(np.int32)[0] != 0:
         raise _lib.LsError(f"cloud_merge: status {int(host[2:].view(np.int32)[0])} (the cell table overflowed: a defect)")
     return pts[:int(host[1])], src[:int(host[1])]
+
+
+# ------------------------------------------------------------------------------------------------ scene memory: radius search (csrc/cloudnear.hip)
+def _near_cloud(x, what):
+    if not torch.is_tensor(x) or x.device.type != "cuda" or x.dtype != torch.float32:
+        kind = f"{x.device.type} {x.dtype}" if torch.is_tensor(x) else type(x).__name__
+        raise _lib.LsError(f"cloud_nearest: {what} must be an fp32 HIP (cuda) tensor, got {kind}: the MI355X path has no CPU fallback and converts nothing")
+    if x.dim() != 2 or x.shape[1] != 3:
+        raise ValueError(f"cloud_nearest: {what} is [n, 3], got {tuple(x.shape)}")
+    return x.contiguous()
+
+
+def _near_meta(meta, P):
+    """the one host read of a call: counts [P,3] int64, sum_d2 [P] float64, status [P] int32 from the int64 words of `meta`"""
+    host = meta.cpu().numpy()
+    st = host[4 * P:].view(np.int32)[:P]
+    if st.any():
+        raise _lib.LsError(f"cloud_nearest: problem {int(np.flatnonzero(st)[0])}: status {int(st[np.flatnonzero(st)[0]])} (the cell table overflowed: a defect)")
+    return host[:3 * P].reshape(P, 3).copy(), host[3 * P:4 * P].view(np.float64).copy()
+
+
+def cloud_nearest_batch(As, Bs, g=None, *, radius, packed=False):
+    """ls_cloud_nearest_batch_f32: As / Bs = lists of P kept clouds [a_p,3] (targets) and observations [b_p,3] (queries; fp32 HIP tensors,
+    empty ones allowed), g [P,3,4] or [P,4,4] taking B_p into A_p's frame (None: identity, B bit for bit), radius = one radius or P radii.
+    The neighbour of a query is the target within `radius` -- and within one cell of edge `radius` on every axis -- that is least under
+    (d2, index) (include/livingscenes_hip.h) -> list of P (idx [b_p] int32: the row of A_p, -1 for none; d2 [b_p] fp32, +inf for none;
+    counts: host int64 [3] = finite queries, queries with a neighbour, targets that are somebody's neighbour; sum_d2: float, the float64 sum
+    of the finite d2), idx / d2 views of one packed tensor; packed=True: (idx, d2, counts [P,3], sum_d2 [P], b_off) with the host int64
+    query offsets [P+1].  One call, one host read (counts, sums and status), whatever P."""
+    As, Bs = [_near_cloud(x, "A") for x in As], [_near_cloud(x, "B") for x in Bs]
+    P = len(As)
+    if len(Bs) != P:
+        raise ValueError(f"cloud_nearest: {P} kept clouds for {len(Bs)} observations")
+    if P == 0:
+        raise ValueError("cloud_nearest: no problem given")
+    dev = As[0].device
+    rad = np.full(P, float(radius), dtype=np.float32) if np.ndim(radius) == 0 else np.ascontiguousarray(radius, dtype=np.float32).reshape(-1)
+    if rad.shape[0] != P:
+        raise ValueError(f"cloud_nearest: {rad.shape[0]} radii for {P} problems")
+    if g is not None:
+        if not torch.is_tensor(g) or g.dim() != 3 or g.shape[0] != P or g.shape[1] not in (3, 4) or g.shape[2] != 4:
+            raise ValueError(f"cloud_nearest: g must be [P,3,4] or [P,4,4] with P = {P}, got {tuple(g.shape) if torch.is_tensor(g) else type(g).__name__}")
+        g = _f32(g.to(dev)[:, :3, :])
+    A = torch.cat(As, 0) if P > 1 else As[0]
+    B = torch.cat(Bs, 0) if P > 1 else Bs[0]
+    ao, bo = _offsets([x.shape[0] for x in As]), _offsets([x.shape[0] for x in Bs])
+    idx = torch.empty(B.shape[0], dtype=torch.int32, device=dev)
+    d2 = torch.empty(B.shape[0], dtype=torch.float32, device=dev)
+    meta = torch.empty(4 * P + (P + 1) // 2, dtype=torch.int64, device=dev)   # counts [P,3] int64, sum_d2 [P] float64, status [P] int32
+    ws = _scratch(load().ls_cloud_nearest_batch_workspace_bytes(P, A.shape[0], B.shape[0]), dev)
+    call(dev, "ls_cloud_nearest_batch_f32", P, ptr(A), A.shape[0], _hptr(ao), ptr(B), B.shape[0], _hptr(bo), ptr(g), _hptr(rad), ptr(idx), ptr(d2),
+         ptr(meta), ctypes.c_void_p(meta.data_ptr() + 24 * P), ctypes.c_void_p(meta.data_ptr() + 32 * P), ptr(ws), 0 if ws is None else ws.numel(),
+         stream_ptr(dev))
+    counts, sums = _near_meta(meta, P)
+    if packed:
+        return idx, d2, counts, sums, bo
+    sizes = np.diff(bo).tolist()
+    return [(i, d, counts[p], float(sums[p])) for p, (i, d) in enumerate(zip(torch.split(idx, sizes), torch.split(d2, sizes)))]
+
+
+def cloud_nearest(A, B, g=None, *, radius):
+    """ls_cloud_nearest_f32: the kept cloud A [a,3] (targets) and the observation B [b,3] (queries; fp32 HIP tensors), g [3,4] or [4,4]
+    taking B into A's frame (None: identity) -> (idx [b] int32, d2 [b] fp32, counts host int64 [3], sum_d2 float) as cloud_nearest_batch
+    describes them.  Bit-identical to the same problem inside any cloud_nearest_batch."""
+    A, B = _near_cloud(A, "A"), _near_cloud(B, "B")
+    dev = A.device
+    if g is not None:
+        if not torch.is_tensor(g) or tuple(g.shape) not in ((3, 4), (4, 4)):
+            raise ValueError(f"cloud_nearest: g must be [3,4] or [4,4], got {tuple(g.shape) if torch.is_tensor(g) else type(g).__name__}")
+        g = _f32(g.to(dev)[:3, :])
+    idx = torch.empty(B.shape[0], dtype=torch.int32, device=dev)
+    d2 = torch.empty(B.shape[0], dtype=torch.float32, device=dev)
+    meta = torch.empty(5, dtype=torch.int64, device=dev)                      # counts [3], sum_d2, then the status
+    ws = _scratch(load().ls_cloud_nearest_workspace_bytes(A.shape[0], B.shape[0]), dev)
+    call(dev, "ls_cloud_nearest_f32", ptr(A), A.shape[0], ptr(B), B.shape[0], ptr(g), float(radius), ptr(idx), ptr(d2), ptr(meta),
+         ctypes.c_void_p(meta.data_ptr() + 24), ctypes.c_void_p(meta.data_ptr() + 32), ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev))
+    counts, sums = _near_meta(meta, 1)
+    return idx, d2, counts[0], float(sums[0])
