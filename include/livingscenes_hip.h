@@ -62,7 +62,7 @@ typedef enum {
  * any unknown option; 105: the mesh metrics ls_mesh_contains_f64 / ls_mesh_distance_f64 / ls_mesh_sample_f64; 106: ls_model_desc.dec_input and
  * off_dec_xyz_t, the invariant decoder_type "deepsdf"; 107: the ragged multi-mesh metrics ls_mesh_contains_batch_f64 /
  * ls_mesh_distance_batch_f64 / ls_mesh_sample_batch_f64; symbols added since -- ls_reg_metrics_batch, ls_mesh_cluster_f64 / ls_mesh_cluster_batch_f64,
- * ls_cloud_merge_f32 / ls_cloud_merge_batch_f32, ls_cloud_nearest_f32 / ls_cloud_nearest_batch_f32 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
+ * ls_cloud_merge_f32 / ls_cloud_merge_batch_f32, ls_cloud_nearest_f32 / ls_cloud_nearest_batch_f32, ls_cloud_icp_f32 / ls_cloud_icp_batch_f32 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
  * binding compares it with the header it was written against and refuses a mismatch (livingscenes_amd/_lib.py: load). */
 #define LS_ABI_VERSION 107
 int ls_version(void);
@@ -719,6 +719,60 @@ size_t ls_cloud_nearest_batch_workspace_bytes(int P, long long a_total, long lon
 int ls_cloud_nearest_batch_f32(int P, const float* A, long long a_total, const long long* a_off, const float* B, long long b_total,
                                const long long* b_off, const float* g, const float* radius, int32_t* nn_idx, float* nn_d2, long long* counts,
                                double* sum_d2, int* status_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Scene memory, the pose both of the above trust (csrc/cloudnear.hip): trimmed ICP of an observation onto the kept cloud, on the search's
+ * grid and at full resolution.  AN EXTENSION BEYOND THE RELEASED REFERENCE, like the merge and the search: the reference registers two
+ * 1 024-point samples (pytorch3d's ICP, every source point paired with its nearest target) and has no memory to register against.  Here
+ * the observation B moves onto the complete kept cloud A, and only correspondences within r count, so the part of A the view does not see
+ * pulls on nothing.  Definition, per problem (tests/icp_oracle.py is the same text as NumPy), with the conventions of ls_cloud_nearest_f32:
+ *   inputs      A [a,3] fp32 (targets), B [b,3] fp32 (queries), g0 [3,4] fp32 taking B into A's frame (NULL: the identity MATRIX, which
+ *               goes through the query expression like any other pose), r > 0; host scalars max_iter >= 0, rel_thr >= 0 finite (double),
+ *               min_matched >= 3.  g_0 = g0, and for k = 0, 1, ...:
+ *   search      exactly ls_cloud_nearest_f32(A, B, g_k, r): the same query expression and rounding, cells of edge r, d2 and neighbour
+ *               under (d2, j).  f_k = finite queries, n_k = matched queries, S_k = the float64 sum of the matched nn_d2 by the chunk rule
+ *               of the search (256 queries per chunk in a fixed tree, partials in chunk order).
+ *   cost        E_k = (S_k + (f_k - n_k) (double)r2) / f_k in float64 in that order; f_k = 0: E_k = 0.  This is the truncated quadratic
+ *               sum_i min(d_i^2, r^2) / f.  The neighbours within r are exact (any target within r lies within one cell per axis), so
+ *               neither the assignment nor the Kabsch step can raise it, although the matched set changes -- which the rmse of the matched
+ *               points alone does not promise: it can rise when more points match.
+ *   stop tests  in this order, each with g_out = g_k and iters = k: n_k < min_matched: LS_ICP_STARVED; k >= 1 and
+ *               E_{k-1} - E_k <= rel_thr E_{k-1}: LS_ICP_CONVERGED; k == max_iter: LS_ICP_MAX_ITER.  At most max_iter updates and
+ *               max_iter + 1 searches.
+ *   update      over the matched queries, the ORIGINAL row x_i of B and its neighbour a_j, in float64 with the products formed in float64
+ *               from the fp32 inputs (exact): sum x [3], sum a [3], sum x a^T [9], each by the chunk rule (a fixed order inside a chunk
+ *               of 256 queries, partials in chunk order; no floating-point atomics).  mu_x = sum x / n, mu_a = sum a / n,
+ *               H = sum x a^T - (sum x)(sum a)^T / n; R = the rotation of ls_kabsch_batched_f32 for the covariance H (x -> a), rounded to
+ *               fp32; t = mu_a - R_fp32 mu_x in float64, rounded to fp32; g_{k+1} = (R | t).  If that solver reports anything but
+ *               LS_KABSCH_OK (rank < 2 as it decides it: an exactly collinear or coincident matched set, or non-finite sums):
+ *               LS_ICP_DEGENERATE, g_out = g_k, iters = k.  The UNCENTRED moments are a float64 choice: with coordinates up to a few
+ *               hundred object extents from the origin the cancellation in H stays far below one fp32 ulp of the result.
+ * Outputs: g_out [3,4] fp32; stop int32 (LS_ICP_*); iters int32; and the complete result of the final search -- nn_idx [b], nn_d2 [b],
+ * counts [3], sum_d2 -- which are BIT FOR BIT what ls_cloud_nearest_f32(A, B, g_out, r) returns (it is the last search of the loop, not
+ * one more); status_out as there.  Optional trace (both nullable): g_trace float [max_iter+1, 12] = g_k and stat_trace double
+ * [max_iter+1, 3] = (f_k, n_k, S_k); the rows k <= iters are written, the others are left alone.
+ * By construction: every output of a problem is the same bits alone, in any batch composition and in any run; a problem that has stopped
+ * is frozen -- later iterations of its batch neither read nor write it; the number of launches depends on max_iter alone (2 max_iter + 5
+ * after the grid build), not on P and not on when problems stop; no host synchronisation, no allocation, no waiting between workgroups,
+ * and every loop on the device is bounded by the table size, the member count or the chunk count.  The workspace is the search's plus the
+ * poses and one record of 15 float64 per chunk of queries; the queries return 0 for sizes the op refuses. */
+#define LS_ICP_CONVERGED 0  /* the cost fell by no more than rel_thr of itself */
+#define LS_ICP_MAX_ITER 1   /* max_iter updates were made */
+#define LS_ICP_STARVED 2    /* fewer than min_matched correspondences within r */
+#define LS_ICP_DEGENERATE 3 /* the matched pairs do not determine a rotation */
+size_t ls_cloud_icp_workspace_bytes(long long a, long long b);
+int ls_cloud_icp_f32(const float* A, long long a, const float* B, long long b, const float* g0, float radius, int max_iter, double rel_thr,
+                     int min_matched, float* g_out, int32_t* stop, int32_t* iters, int32_t* nn_idx, float* nn_d2, long long* counts, double* sum_d2,
+                     int* status_out, float* g_trace, double* stat_trace, void* workspace, size_t workspace_bytes, void* stream);
+/* P >= 1 problems per call with the conventions of ls_cloud_nearest_batch_f32: a_off / b_off / radius are HOST arrays, checked with
+ * max_iter, rel_thr and min_matched (shared by the batch) before the first HIP call -- the error names the problem; g0 [P,3,4] DEVICE or
+ * NULL.  g_out [P,3,4], stop / iters [P], nn_idx / nn_d2 [b_total] packed, counts [P,3], sum_d2 [P], status_out [P] (nullable), g_trace
+ * [P, max_iter+1, 12] and stat_trace [P, max_iter+1, 3] (nullable), all DEVICE.  Every output of every problem is BIT-IDENTICAL to
+ * ls_cloud_icp_f32 on that problem alone. */
+size_t ls_cloud_icp_batch_workspace_bytes(int P, long long a_total, long long b_total);
+int ls_cloud_icp_batch_f32(int P, const float* A, long long a_total, const long long* a_off, const float* B, long long b_total,
+                           const long long* b_off, const float* g0, const float* radius, int max_iter, double rel_thr, int min_matched,
+                           float* g_out, int32_t* stop, int32_t* iters, int32_t* nn_idx, float* nn_d2, long long* counts, double* sum_d2,
+                           int* status_out, float* g_trace, double* stat_trace, void* workspace, size_t workspace_bytes, void* stream);
 
 /* The registration metrics of the relocalisation evaluation on P (reference instance, rescan instance, predicted pose, ground-truth pose)
  * tuples per call -- what eval_3rscan.py:384-401 / eval_flyingshape.py:136-148 compute pair by pair.  Pair p owns the rows

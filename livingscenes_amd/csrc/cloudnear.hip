@@ -17,6 +17,11 @@
 // partial; the last kernel adds a problem's partials in chunk order.  Integer atomics only, and only on the table: a problem's outputs are
 // the same bits alone, in any batch and in any run.  The kernels that need the problem are written once, for a problem locator (OneNear /
 // RaggedNear, as OneCloud / RaggedClouds of cloudmerge.hip); the number of launches does not depend on P.
+// The same grid serves the trimmed ICP of the scene memory (ls_cloud_icp_f32, an extension beyond the released reference like the search
+// itself; tests/icp_oracle.py): the grid is built once over the memory, then every iteration repeats the search under the current pose --
+// the per-query walk is one __device__ function for both -- with the float64 moments of the matched pairs per chunk, and one workgroup per
+// problem adds the chunk records in order, applies the stop tests and solves the 3x3 Kabsch problem (svd3.h).  A stopped problem is frozen:
+// its workgroups exit at once, so the launches depend on max_iter alone and nothing waits on the host or on another workgroup.
 #include <climits>
 #include <cmath>
 #include <vector>
@@ -24,6 +29,7 @@
 #include "ls_common.h"
 #include "ls_ragged.h"
 #include "ls_scan.h"
+#include "svd3.h"
 
 // the arithmetic of the definition as written: no contraction of a * b + c into an fma anywhere in this file
 #pragma clang fp contract(off)
@@ -155,6 +161,71 @@ __global__ __launch_bounds__(256) void fill_kernel(const float* __restrict__ A, 
     members[(long long)start[s] + rank[i]] = make_float4(A[i * 3 + 0], A[i * 3 + 1], A[i * 3 + 2], __int_as_float((int)i));
 }
 
+// a query row under the pose: y_a = ((R_a0 x_0 + R_a1 x_1) + R_a2 x_2) + t_a (g null: the row bit for bit)
+__device__ __forceinline__ void pose_row(const float* __restrict__ g, float x0, float x1, float x2, float (&y)[3]) {
+    y[0] = x0, y[1] = x1, y[2] = x2;
+    if (g)
+        for (int r = 0; r < 3; ++r) y[r] = ((g[r * 4 + 0] * x0 + g[r * 4 + 1] * x1) + g[r * 4 + 2] * x2) + g[r * 4 + 3];
+}
+
+// the neighbour of the query y of cell c: the 27 cells around c, each by a probe walk that ends at the cell or at an empty slot; the minimum
+// under (d2, j) with the global index j (INT_MAX: none) and the neighbour's coordinates.  Written once, for the search and for the ICP.
+__device__ __forceinline__ void walk_cells(const NearRef& C, const float (&y)[3], const int (&c)[3], const int4* __restrict__ slots,
+                                           const int* __restrict__ cnt, const float4* __restrict__ members, float& best, int& best_j,
+                                           float (&best_a)[3]) {
+    const long long t0 = 2 * C.a0, T = 2 * C.a;
+    for (int k = 0; k < 27; ++k) {
+        const int n0 = c[0] + k / 9 - 1, n1 = c[1] + (k / 3) % 3 - 1, n2 = c[2] + k % 3 - 1;   // |c| <= 2^30: no overflow
+        long long s = first_slot(n0, n1, n2, T);
+        for (long long step = 0; step < T; ++step) {
+            const int4 sl = slots[t0 + s];
+            if (sl.x == NO_CELL) break;                        // an empty slot ends the walk: the cell has no target
+            if (sl.x == n0 && sl.y == n1 && sl.z == n2) {
+                const float4* __restrict__ m = members + sl.w;
+                const int count = cnt[t0 + s];
+                for (int e = 0; e < count; ++e) {
+                    const float4 t = m[e];
+                    const float dx = y[0] - t.x, dy = y[1] - t.y, dz = y[2] - t.z;
+                    const float d2 = (dx * dx + dy * dy) + dz * dz;
+                    const int j = __float_as_int(t.w);
+                    if (d2 <= C.r2 && (d2 < best || (d2 == best && j < best_j))) {
+                        best = d2;
+                        best_j = j;
+                        best_a[0] = t.x, best_a[1] = t.y, best_a[2] = t.z;
+                    }
+                }
+                break;
+            }
+            if (++s == T) s = 0;
+        }
+    }
+}
+
+// one thread's query of problem C under the pose g: finite?, and its neighbour
+__device__ __forceinline__ bool query_one(const NearRef& C, const float* __restrict__ g, long long qi, const int4* __restrict__ slots,
+                                          const int* __restrict__ cnt, const float4* __restrict__ members, float (&x)[3], float& best,
+                                          int& best_j, float (&best_a)[3]) {
+    const float* __restrict__ row = C.B + qi * 3;
+    x[0] = row[0], x[1] = row[1], x[2] = row[2];
+    float y[3];
+    pose_row(g, x[0], x[1], x[2], y);
+    int c[3];
+    const bool finite = cell_of(y, C.inv, c);
+    if (finite && C.a > 0) walk_cells(C, y, c, slots, cnt, members, best, best_j, best_a);
+    return finite;
+}
+
+// the float64 sum of a chunk, one value per thread, in the fixed LDS tree of the definition -> every thread
+__device__ __forceinline__ double chunk_sum(double (&lds)[QUERY_CHUNK], double v) {
+    lds[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = QUERY_CHUNK / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) lds[threadIdx.x] += lds[threadIdx.x + o];
+        __syncthreads();
+    }
+    return lds[0];
+}
+
 // workgroup = one chunk of QUERY_CHUNK queries of one problem, one thread per query.  part[chunk] = the float64 sum of the chunk's nn_d2 in a
 // fixed order, part_cnt[chunk] = (finite queries, queries with a neighbour).
 template <class Near>
@@ -168,43 +239,8 @@ __global__ __launch_bounds__(QUERY_CHUNK) void query_kernel(Near L, const int4* 
     const bool live = qi < C.b;
     bool finite = false;
     int best_j = INT_MAX;
-    float best = INFINITY;
-    if (live) {
-        const float* __restrict__ x = C.B + qi * 3;
-        const float x0 = x[0], x1 = x[1], x2 = x[2];
-        float y[3] = {x0, x1, x2};
-        if (C.g)
-            for (int r = 0; r < 3; ++r) y[r] = ((C.g[r * 4 + 0] * x0 + C.g[r * 4 + 1] * x1) + C.g[r * 4 + 2] * x2) + C.g[r * 4 + 3];
-        int c[3];
-        finite = cell_of(y, C.inv, c);
-        const long long t0 = 2 * C.a0, T = 2 * C.a;
-        if (finite && T > 0) {
-            for (int k = 0; k < 27; ++k) {
-                const int n0 = c[0] + k / 9 - 1, n1 = c[1] + (k / 3) % 3 - 1, n2 = c[2] + k % 3 - 1;   // |c| <= 2^30: no overflow
-                long long s = first_slot(n0, n1, n2, T);
-                for (long long step = 0; step < T; ++step) {
-                    const int4 sl = slots[t0 + s];
-                    if (sl.x == NO_CELL) break;                        // an empty slot ends the walk: the cell has no target
-                    if (sl.x == n0 && sl.y == n1 && sl.z == n2) {
-                        const float4* __restrict__ m = members + sl.w;
-                        const int count = cnt[t0 + s];
-                        for (int e = 0; e < count; ++e) {
-                            const float4 t = m[e];
-                            const float dx = y[0] - t.x, dy = y[1] - t.y, dz = y[2] - t.z;
-                            const float d2 = (dx * dx + dy * dy) + dz * dz;
-                            const int j = __float_as_int(t.w);
-                            if (d2 <= C.r2 && (d2 < best || (d2 == best && j < best_j))) {
-                                best = d2;
-                                best_j = j;
-                            }
-                        }
-                        break;
-                    }
-                    if (++s == T) s = 0;
-                }
-            }
-        }
-    }
+    float best = INFINITY, x[3], best_a[3];
+    if (live) finite = query_one(C, C.g, qi, slots, cnt, members, x, best, best_j, best_a);
     const bool has = best_j != INT_MAX;
     if (has) hit[best_j] = 1;                                          // every writer writes the same byte
     if (live) {
@@ -212,14 +248,9 @@ __global__ __launch_bounds__(QUERY_CHUNK) void query_kernel(Near L, const int4* 
         nn_d2[C.b0 + qi] = best;
     }
     const int n_finite = __syncthreads_count(finite), n_has = __syncthreads_count(has);
-    lds[threadIdx.x] = has ? (double)best : 0.0;
-    __syncthreads();
-    for (int o = QUERY_CHUNK / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) lds[threadIdx.x] += lds[threadIdx.x + o];
-        __syncthreads();
-    }
+    const double sum = chunk_sum(lds, has ? (double)best : 0.0);
     if (threadIdx.x == 0) {
-        part[blockIdx.x] = lds[0];
+        part[blockIdx.x] = sum;
         part_cnt[blockIdx.x] = make_int2(n_finite, n_has);
     }
 }
@@ -254,6 +285,158 @@ __global__ __launch_bounds__(256) void final_kernel(Near L, const unsigned char*
     }
 }
 
+// ------------------------------------------------------------------------------------------------ trimmed ICP on the same grid (ls_cloud_icp_f32)
+// The state of a problem between two launches: its pose g_k and E_{k-1} in the workspace, stop[p] (ICP_RUNNING until a stop test holds) and
+// iters[p] in the caller's arrays.  A launch of iteration k touches the problems that still run and no other.
+constexpr int ICP_RUNNING = -1;
+constexpr int N_MOM = 15;                     // per chunk: sum x [3], sum a [3], sum x a^T [9], float64
+
+__global__ __launch_bounds__(256) void icp_init_kernel(int P, const float* __restrict__ g0, float* __restrict__ gk, double* __restrict__ e_prev,
+                                                       int* __restrict__ stop, int* __restrict__ iters) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= P * 12) return;
+    gk[i] = g0 ? g0[i] : ((i % 12) % 5 == 0 ? 1.0f : 0.0f);           // NULL: the identity as a matrix
+    if (i % 12 == 0) {
+        e_prev[i / 12] = 0.0;
+        stop[i / 12] = ICP_RUNNING;
+        iters[i / 12] = 0;
+    }
+}
+
+// the sum of a wave in a fixed tree (lane l with l + 32, l + 16, ..., l + 1) -> lane 0
+__device__ __forceinline__ double wave_tree_f64(double v) {
+    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);
+    return v;
+}
+
+// The search of iteration k: query_kernel under g_k, for the chunks of the problems that still run.  Besides nn_idx / nn_d2 / part /
+// part_cnt -- the same values by the same code, so the last search of a problem IS its final search -- one record of N_MOM float64 moments
+// per chunk over the matched queries: the ORIGINAL row x of B and its neighbour a, products formed in float64 (exact: 24 x 24 bits).  The
+// moments go through a fixed tree inside every wave and a fixed tree over the four waves: 480 bytes of LDS instead of 30 KB.
+template <class Near>
+__global__ __launch_bounds__(QUERY_CHUNK) void icp_search_kernel(Near L, const int* __restrict__ stop, const float* __restrict__ gk,
+                                                                 const int4* __restrict__ slots, const int* __restrict__ cnt,
+                                                                 const float4* __restrict__ members, int* __restrict__ nn_idx,
+                                                                 float* __restrict__ nn_d2, double* __restrict__ part,
+                                                                 int2* __restrict__ part_cnt, double* __restrict__ mom) {
+    __shared__ double lds[QUERY_CHUNK];
+    __shared__ double wave_part[N_MOM][QUERY_CHUNK / kWave];
+    const int p = L.chunk_owner(blockIdx.x);
+    if (stop[p] != ICP_RUNNING) return;                                // the whole workgroup: a stopped problem is frozen
+    const NearRef C = L.problem(p);
+    const long long qi = ((long long)blockIdx.x - C.q0) * QUERY_CHUNK + threadIdx.x;
+    const bool live = qi < C.b;
+    bool finite = false;
+    int best_j = INT_MAX;
+    float best = INFINITY, x[3] = {0.f, 0.f, 0.f}, a[3] = {0.f, 0.f, 0.f};
+    if (live) finite = query_one(C, gk + (size_t)p * 12, qi, slots, cnt, members, x, best, best_j, a);
+    const bool has = best_j != INT_MAX;
+    if (live) {
+        nn_idx[C.b0 + qi] = has ? (int)(best_j - C.a0) : -1;
+        nn_d2[C.b0 + qi] = best;
+    }
+    const int n_finite = __syncthreads_count(finite), n_has = __syncthreads_count(has);
+    const double sum = chunk_sum(lds, has ? (double)best : 0.0);
+    double m[N_MOM];
+    for (int r = 0; r < 3; ++r) {
+        m[r] = has ? (double)x[r] : 0.0;
+        m[3 + r] = has ? (double)a[r] : 0.0;
+    }
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) m[6 + r * 3 + c] = m[r] * m[3 + c];
+    const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+    for (int e = 0; e < N_MOM; ++e) {
+        const double v = wave_tree_f64(m[e]);
+        if (lane == 0) wave_part[e][wave] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < N_MOM) {
+        const double* v = wave_part[threadIdx.x];
+        mom[(size_t)blockIdx.x * N_MOM + threadIdx.x] = (v[0] + v[1]) + (v[2] + v[3]);
+    }
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = sum;
+        part_cnt[blockIdx.x] = make_int2(n_finite, n_has);
+    }
+}
+
+// workgroup (one wave) = one problem that still runs, after the search of iteration k: the chunk records added in chunk order (lane e the
+// e-th float64 quantity, two lanes the counts), then one lane applies the stop tests of the definition or solves for g_{k+1}.
+template <class Near>
+__global__ __launch_bounds__(kWave) void icp_solve_kernel(Near L, int k, int max_iter, double rel_thr, int min_matched,
+                                                          const double* __restrict__ part, const int2* __restrict__ part_cnt,
+                                                          const double* __restrict__ mom, float* __restrict__ gk, double* __restrict__ e_prev,
+                                                          int* __restrict__ stop, int* __restrict__ iters, float* __restrict__ g_out,
+                                                          float* __restrict__ g_trace, double* __restrict__ stat_trace) {
+    __shared__ double sums[N_MOM + 1];
+    __shared__ long long cnts[2];
+    const int p = blockIdx.x;
+    if (stop[p] != ICP_RUNNING) return;
+    const NearRef C = L.problem(p);
+    const int e = threadIdx.x;
+    if (e < N_MOM) {
+        double s = 0.0;
+        for (long long q = C.q0; q < C.q1; ++q) s += mom[(size_t)q * N_MOM + e];
+        sums[e] = s;
+    } else if (e == N_MOM) {
+        double s = 0.0;
+        for (long long q = C.q0; q < C.q1; ++q) s += part[q];         // the sum_d2 of final_kernel
+        sums[N_MOM] = s;
+    } else if (e < N_MOM + 3) {
+        long long s = 0;
+        for (long long q = C.q0; q < C.q1; ++q) s += e == N_MOM + 1 ? part_cnt[q].x : part_cnt[q].y;
+        cnts[e - N_MOM - 1] = s;
+    }
+    __syncthreads();
+    if (e != 0) return;
+    float* g = gk + (size_t)p * 12;
+    const long long f = cnts[0], n = cnts[1];
+    const double S = sums[N_MOM];
+    const double E = f > 0 ? (S + (double)(f - n) * (double)C.r2) / (double)f : 0.0;
+    if (g_trace)
+        for (int i = 0; i < 12; ++i) g_trace[((size_t)p * (max_iter + 1) + k) * 12 + i] = g[i];
+    if (stat_trace) {
+        double* st = stat_trace + ((size_t)p * (max_iter + 1) + k) * 3;
+        st[0] = (double)f, st[1] = (double)n, st[2] = S;
+    }
+    int why = ICP_RUNNING;
+    float R[9];
+    double mx[3], ma[3];
+    if (n < min_matched) why = LS_ICP_STARVED;
+    else if (k >= 1 && e_prev[p] - E <= rel_thr * e_prev[p]) why = LS_ICP_CONVERGED;
+    else if (k == max_iter) why = LS_ICP_MAX_ITER;
+    else {
+        const double dn = (double)n;
+        double H[9];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) H[r * 3 + c] = sums[6 + r * 3 + c] - (sums[r] * sums[3 + c]) / dn;
+        for (int r = 0; r < 3; ++r) mx[r] = sums[r] / dn, ma[r] = sums[3 + r] / dn;
+        if (kabsch_rotation(H, R) != LS_KABSCH_OK) why = LS_ICP_DEGENERATE;
+    }
+    if (why != ICP_RUNNING) {
+        stop[p] = why;
+        iters[p] = k;
+        for (int i = 0; i < 12; ++i) g_out[(size_t)p * 12 + i] = g[i];
+        return;
+    }
+    for (int r = 0; r < 3; ++r) {
+        const double Rm = ((double)R[r * 3 + 0] * mx[0] + (double)R[r * 3 + 1] * mx[1]) + (double)R[r * 3 + 2] * mx[2];
+        for (int c = 0; c < 3; ++c) g[r * 4 + c] = R[r * 3 + c];
+        g[r * 4 + 3] = (float)(ma[r] - Rm);
+    }
+    e_prev[p] = E;
+}
+
+// after the loop: the targets that are a neighbour in the final search of their problem
+template <class Near>
+__global__ __launch_bounds__(QUERY_CHUNK) void icp_mark_kernel(Near L, const int* __restrict__ nn_idx, unsigned char* __restrict__ hit) {
+    const NearRef C = L.problem(L.chunk_owner(blockIdx.x));
+    const long long qi = ((long long)blockIdx.x - C.q0) * QUERY_CHUNK + threadIdx.x;
+    if (qi >= C.b) return;
+    const int j = nn_idx[C.b0 + qi];
+    if (j >= 0) hit[C.a0 + j] = 1;
+}
+
 }  // namespace cnr
 }  // namespace ls
 
@@ -281,11 +464,15 @@ struct Ws {
     unsigned char* hit;       // [a]
     double* part;             // one per chunk of queries
     int2* part_cnt;           // one per chunk of queries
+    float* gk;                // the ICP: [P,12] the pose of the current iteration
+    double* e_prev;           // the ICP: [P] the cost of the previous iteration
+    double* mom;              // the ICP: N_MOM per chunk of queries
     size_t bytes;             // of the whole layout
 };
 
-// the layout depends on (P, a, b) alone (ws null: a sizing pass; n_offs = 0: a single problem); sum_p ceil(b_p / c) <= floor(b / c) + P
-Ws layout(void* ws, size_t n_offs, int P, long long a, long long b) {
+// the layout depends on (P, a, b) alone (ws null: a sizing pass; n_offs = 0: a single problem); sum_p ceil(b_p / c) <= floor(b / c) + P.
+// The ICP's pieces follow the search's, so its workspace is the search's and then its own state and one moment record per chunk.
+Ws layout(void* ws, size_t n_offs, int P, long long a, long long b, bool icp = false) {
     Arena ar(ws);
     Ws w;
     const size_t chunks = (size_t)(b / QUERY_CHUNK + P);
@@ -306,14 +493,16 @@ Ws layout(void* ws, size_t n_offs, int P, long long a, long long b) {
     w.hit = ar.take<unsigned char>((size_t)a);
     w.part = ar.take<double>(chunks);
     w.part_cnt = ar.take<int2>(chunks);
+    w.gk = ar.take<float>(icp ? (size_t)P * 12 : 0);
+    w.e_prev = ar.take<double>(icp ? (size_t)P : 0);
+    w.mom = ar.take<double>(icp ? chunks * N_MOM : 0);
     w.bytes = ar.bytes();
     return w;
 }
 
-// the launch sequence: P problems located by L, a targets, b queries and `chunks` chunks of queries in all
+// the grid over the targets of P problems located by L: the table, the members of every cell back to back, the hit flags cleared
 template <class Near>
-int nearest_launch(const Near& L, int P, const float* A, long long a, long long b, long long chunks, const Ws& w, int* nn_idx, float* nn_d2,
-                   long long* counts, double* sum_d2, int* status_out, hipStream_t st) {
+int grid_launch(const Near& L, int P, const float* A, long long a, const Ws& w, hipStream_t st) {
     LS_HIP_CHECK(hipMemsetAsync(w.status, 0, (size_t)P * sizeof(int), st));               // LS_OK
     if (a > 0) {
         const int nb = cdiv(a, 256);
@@ -326,11 +515,61 @@ int nearest_launch(const Near& L, int P, const float* A, long long a, long long 
         hipLaunchKernelGGL(slot_kernel, dim3(cdiv(2 * a, 256)), dim3(256), 0, st, 2 * a, w.table, w.tcell, w.start, w.slots);
         hipLaunchKernelGGL(fill_kernel, dim3(nb), dim3(256), 0, st, A, a, w.slot_of, w.rank, w.start, w.members);
     }
+    return LS_OK;
+}
+
+// the launch sequence: P problems located by L, a targets, b queries and `chunks` chunks of queries in all
+template <class Near>
+int nearest_launch(const Near& L, int P, const float* A, long long a, long long b, long long chunks, const Ws& w, int* nn_idx, float* nn_d2,
+                   long long* counts, double* sum_d2, int* status_out, hipStream_t st) {
+    const int rc = grid_launch(L, P, A, a, w, st);
+    if (rc != LS_OK) return rc;
     if (chunks > 0)
         hipLaunchKernelGGL(query_kernel<Near>, dim3((unsigned)chunks), dim3(QUERY_CHUNK), 0, st, L, w.slots, w.cnt, w.members, w.hit, nn_idx, nn_d2,
                            w.part, w.part_cnt);
     hipLaunchKernelGGL(final_kernel<Near>, dim3(P), dim3(256), 0, st, L, w.hit, w.part, w.part_cnt, w.status, counts, sum_d2, status_out);
     LS_LAUNCH_CHECK();
+    return LS_OK;
+}
+
+struct IcpArgs {
+    int max_iter;
+    double rel_thr;
+    int min_matched;
+    float* g_out;
+    int* stop;
+    int* iters;
+    float* g_trace;
+    double* stat_trace;
+};
+
+// the ICP's launch sequence: the grid once, then max_iter + 1 times (search, solve) -- the problems that have stopped exit at once -- then
+// the hit flags and the counts of the final searches.  2 max_iter + 5 kernels after the grid build, whatever P and whenever problems stop.
+template <class Near>
+int icp_launch(const Near& L, int P, const float* A, long long a, long long chunks, const float* g0, const IcpArgs& I, const Ws& w, int* nn_idx,
+               float* nn_d2, long long* counts, double* sum_d2, int* status_out, hipStream_t st) {
+    const int rc = grid_launch(L, P, A, a, w, st);
+    if (rc != LS_OK) return rc;
+    hipLaunchKernelGGL(icp_init_kernel, dim3(cdiv((long long)P * 12, 256)), dim3(256), 0, st, P, g0, w.gk, w.e_prev, I.stop, I.iters);
+    for (int k = 0; k <= I.max_iter; ++k) {
+        if (chunks > 0)
+            hipLaunchKernelGGL(icp_search_kernel<Near>, dim3((unsigned)chunks), dim3(QUERY_CHUNK), 0, st, L, I.stop, w.gk, w.slots, w.cnt, w.members,
+                               nn_idx, nn_d2, w.part, w.part_cnt, w.mom);
+        hipLaunchKernelGGL(icp_solve_kernel<Near>, dim3(P), dim3(kWave), 0, st, L, k, I.max_iter, I.rel_thr, I.min_matched, w.part, w.part_cnt, w.mom,
+                           w.gk, w.e_prev, I.stop, I.iters, I.g_out, I.g_trace, I.stat_trace);
+    }
+    if (chunks > 0) hipLaunchKernelGGL(icp_mark_kernel<Near>, dim3((unsigned)chunks), dim3(QUERY_CHUNK), 0, st, L, nn_idx, w.hit);
+    hipLaunchKernelGGL(final_kernel<Near>, dim3(P), dim3(256), 0, st, L, w.hit, w.part, w.part_cnt, w.status, counts, sum_d2, status_out);
+    LS_LAUNCH_CHECK();
+    return LS_OK;
+}
+
+int check_icp(const char* op, const IcpArgs& I) {
+    LS_REQUIRE(I.max_iter >= 0, "%s: max_iter must be >= 0, got %d", op, I.max_iter);
+    LS_REQUIRE(I.max_iter < INT_MAX, "%s: max_iter %d: max_iter + 1 searches do not fit an int", op, I.max_iter);
+    LS_REQUIRE(std::isfinite(I.rel_thr) && I.rel_thr >= 0.0, "%s: rel_thr must be finite and >= 0, got %g", op, I.rel_thr);
+    LS_REQUIRE(I.min_matched >= 3, "%s: min_matched must be >= 3 (a rotation needs three correspondences), got %d", op, I.min_matched);
+    LS_REQUIRE(I.g_out && I.stop && I.iters, "%s: null g_out / stop / iters", op);
     return LS_OK;
 }
 
@@ -350,6 +589,43 @@ int check_common(const char* op, long long a, long long b, const float* A, const
     LS_REQUIRE(a + b <= INT_MAX, "%s: %lld + %lld rows exceed %d (int row indices)", op, a, b, INT_MAX);
     LS_REQUIRE((a == 0 || A) && (b == 0 || B), "%s: null A / B with %lld and %lld rows", op, a, b);
     LS_REQUIRE(counts && sum_d2 && (b == 0 || (nn_idx && nn_d2)), "%s: null nn_idx / nn_d2 / counts / sum_d2", op);
+    return LS_OK;
+}
+
+// what a batch entry derives on the host: the chunk offsets and the radius terms of every problem
+struct BatchHost {
+    std::vector<long long> q_off;
+    std::vector<float> inv, r2;
+};
+
+// the host checks of a batch, all before the first HIP call; the errors name the problem
+int check_batch(const char* op, int P, const float* A, long long a_total, const long long* a_off, const float* B, long long b_total,
+                const long long* b_off, const float* radius, const int* nn_idx, const float* nn_d2, const long long* counts, const double* sum_d2,
+                BatchHost* h) {
+    LS_REQUIRE(P >= 1, "%s: P must be at least 1, got %d", op, P);
+    int rc = check_common(op, a_total, b_total, A, B, nn_idx, nn_d2, counts, sum_d2);
+    if (rc != LS_OK) return rc;
+    rc = check_ranges(op, "problem", "a_off", P, a_off, a_total, INT_MAX);
+    if (rc != LS_OK) return rc;
+    rc = check_ranges(op, "problem", "b_off", P, b_off, b_total, INT_MAX);
+    if (rc != LS_OK) return rc;
+    LS_REQUIRE(radius, "%s: null radius", op);
+    h->q_off.assign(P + 1, 0);
+    h->inv.resize(P);
+    h->r2.resize(P);
+    for (int p = 0; p < P; ++p) {
+        h->q_off[p + 1] = h->q_off[p] + chunks_of(b_off[p + 1] - b_off[p]);
+        rc = radius_terms(op, p, radius[p], &h->inv[p], &h->r2[p]);
+        if (rc != LS_OK) return rc;
+    }
+    return LS_OK;
+}
+
+int upload_batch(const Ws& w, int P, const long long* a_off, const long long* b_off, const BatchHost& h, hipStream_t st) {
+    const int rc = upload_offsets(w.offs, pack_offsets(P, {a_off, b_off, h.q_off.data()}), st);
+    if (rc != LS_OK) return rc;
+    LS_HIP_CHECK(hipMemcpyAsync(w.inv, h.inv.data(), (size_t)P * sizeof(float), hipMemcpyHostToDevice, st));   // pageable: read when it returns
+    LS_HIP_CHECK(hipMemcpyAsync(w.r2, h.r2.data(), (size_t)P * sizeof(float), hipMemcpyHostToDevice, st));
     return LS_OK;
 }
 }  // namespace
@@ -388,21 +664,9 @@ int ls_cloud_nearest_batch_f32(int P, const float* A, long long a_total, const l
                                const long long* b_off, const float* g, const float* radius, int32_t* nn_idx, float* nn_d2, long long* counts,
                                double* sum_d2, int* status_out, void* workspace, size_t workspace_bytes, void* stream) {
     const char* op = "cloud_nearest_batch";
-    LS_REQUIRE(P >= 1, "%s: P must be at least 1, got %d", op, P);
-    int rc = check_common(op, a_total, b_total, A, B, nn_idx, nn_d2, counts, sum_d2);
+    BatchHost h;
+    int rc = check_batch(op, P, A, a_total, a_off, B, b_total, b_off, radius, nn_idx, nn_d2, counts, sum_d2, &h);
     if (rc != LS_OK) return rc;
-    rc = check_ranges(op, "problem", "a_off", P, a_off, a_total, INT_MAX);
-    if (rc != LS_OK) return rc;
-    rc = check_ranges(op, "problem", "b_off", P, b_off, b_total, INT_MAX);
-    if (rc != LS_OK) return rc;
-    LS_REQUIRE(radius, "%s: null radius", op);
-    std::vector<long long> q_off(P + 1, 0);
-    std::vector<float> inv(P), r2(P);
-    for (int p = 0; p < P; ++p) {
-        q_off[p + 1] = q_off[p] + chunks_of(b_off[p + 1] - b_off[p]);
-        rc = radius_terms(op, p, radius[p], &inv[p], &r2[p]);
-        if (rc != LS_OK) return rc;
-    }
     const size_t need = ls_cloud_nearest_batch_workspace_bytes(P, a_total, b_total);
     if (!workspace || workspace_bytes < need) {
         set_error("%s: workspace %zu < required %zu (ls_cloud_nearest_batch_workspace_bytes(%d, %lld, %lld))", op,
@@ -411,12 +675,68 @@ int ls_cloud_nearest_batch_f32(int P, const float* A, long long a_total, const l
     }
     hipStream_t st = (hipStream_t)stream;
     const Ws w = layout(workspace, (size_t)OFF_ARRAYS * (P + 1), P, a_total, b_total);
-    rc = upload_offsets(w.offs, pack_offsets(P, {a_off, b_off, q_off.data()}), st);
+    rc = upload_batch(w, P, a_off, b_off, h, st);
     if (rc != LS_OK) return rc;
-    LS_HIP_CHECK(hipMemcpyAsync(w.inv, inv.data(), (size_t)P * sizeof(float), hipMemcpyHostToDevice, st));   // pageable: read when it returns
-    LS_HIP_CHECK(hipMemcpyAsync(w.r2, r2.data(), (size_t)P * sizeof(float), hipMemcpyHostToDevice, st));
-    return nearest_launch(RaggedNear{B, g, w.offs, w.inv, w.r2, P}, P, A, a_total, b_total, q_off[P], w, nn_idx, nn_d2, counts, sum_d2, status_out,
+    return nearest_launch(RaggedNear{B, g, w.offs, w.inv, w.r2, P}, P, A, a_total, b_total, h.q_off[P], w, nn_idx, nn_d2, counts, sum_d2, status_out,
                           st);
+}
+
+size_t ls_cloud_icp_workspace_bytes(long long a, long long b) {
+    if (a < 0 || b < 0 || a + b > INT_MAX) return 0;
+    return layout(nullptr, 0, 1, a, b, true).bytes;
+}
+
+int ls_cloud_icp_f32(const float* A, long long a, const float* B, long long b, const float* g0, float radius, int max_iter, double rel_thr,
+                     int min_matched, float* g_out, int32_t* stop, int32_t* iters, int32_t* nn_idx, float* nn_d2, long long* counts, double* sum_d2,
+                     int* status_out, float* g_trace, double* stat_trace, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* op = "cloud_icp";
+    const IcpArgs I{max_iter, rel_thr, min_matched, g_out, stop, iters, g_trace, stat_trace};
+    int rc = check_common(op, a, b, A, B, nn_idx, nn_d2, counts, sum_d2);
+    if (rc != LS_OK) return rc;
+    float inv, r2;
+    rc = radius_terms(op, 0, radius, &inv, &r2);
+    if (rc != LS_OK) return rc;
+    rc = check_icp(op, I);
+    if (rc != LS_OK) return rc;
+    const size_t need = ls_cloud_icp_workspace_bytes(a, b);
+    if (!workspace || workspace_bytes < need) {
+        set_error("%s: workspace %zu < required %zu (ls_cloud_icp_workspace_bytes(%lld, %lld))", op, workspace ? workspace_bytes : (size_t)0, need, a,
+                  b);
+        return LS_ERR_WORKSPACE;
+    }
+    const Ws w = layout(workspace, 0, 1, a, b, true);
+    return icp_launch(OneNear{B, a, b, nullptr, inv, r2}, 1, A, a, chunks_of(b), g0, I, w, nn_idx, nn_d2, counts, sum_d2, status_out,
+                      (hipStream_t)stream);
+}
+
+size_t ls_cloud_icp_batch_workspace_bytes(int P, long long a_total, long long b_total) {
+    if (P < 1 || a_total < 0 || b_total < 0 || a_total + b_total > INT_MAX) return 0;
+    return layout(nullptr, (size_t)OFF_ARRAYS * (P + 1), P, a_total, b_total, true).bytes;
+}
+
+int ls_cloud_icp_batch_f32(int P, const float* A, long long a_total, const long long* a_off, const float* B, long long b_total,
+                           const long long* b_off, const float* g0, const float* radius, int max_iter, double rel_thr, int min_matched,
+                           float* g_out, int32_t* stop, int32_t* iters, int32_t* nn_idx, float* nn_d2, long long* counts, double* sum_d2,
+                           int* status_out, float* g_trace, double* stat_trace, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* op = "cloud_icp_batch";
+    const IcpArgs I{max_iter, rel_thr, min_matched, g_out, stop, iters, g_trace, stat_trace};
+    BatchHost h;
+    int rc = check_batch(op, P, A, a_total, a_off, B, b_total, b_off, radius, nn_idx, nn_d2, counts, sum_d2, &h);
+    if (rc != LS_OK) return rc;
+    rc = check_icp(op, I);
+    if (rc != LS_OK) return rc;
+    const size_t need = ls_cloud_icp_batch_workspace_bytes(P, a_total, b_total);
+    if (!workspace || workspace_bytes < need) {
+        set_error("%s: workspace %zu < required %zu (ls_cloud_icp_batch_workspace_bytes(%d, %lld, %lld))", op,
+                  workspace ? workspace_bytes : (size_t)0, need, P, a_total, b_total);
+        return LS_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const Ws w = layout(workspace, (size_t)OFF_ARRAYS * (P + 1), P, a_total, b_total, true);
+    rc = upload_batch(w, P, a_off, b_off, h, st);
+    if (rc != LS_OK) return rc;
+    return icp_launch(RaggedNear{B, nullptr, w.offs, w.inv, w.r2, P}, P, A, a_total, h.q_off[P], g0, I, w, nn_idx, nn_d2, counts, sum_d2, status_out,
+                      st);
 }
 
 }  // extern "C"

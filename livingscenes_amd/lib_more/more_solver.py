@@ -260,7 +260,23 @@ class More_Solver:
         improved = improved.bool()
         return {k: code[k].detach() for k in ("z_inv", "z_so3", "s", "t")}, improved
 
-    def _accumulate_batch(self, mem_pcs, new_pcs, T, voxel=None):
+    @staticmethod
+    def _memory_pose(T, g, P):
+        """the pose the scene-memory operators receive (observation -> memory frame) from either the registration T (memory -> rescan, as
+        _solve_pairwise_registration* / Rt_to_SE3 return it: inverse(T)) or g, that pose given directly; both None: None"""
+        if T is not None and g is not None:
+            raise ValueError("give the registration T (memory -> rescan) or the memory-frame pose g (rescan -> memory), not both")
+        if g is not None:
+            if g.dim() != 3 or g.shape[0] != P or g.shape[1] not in (3, 4) or g.shape[2] != 4:
+                raise ValueError(f"g must be [P,4,4] or [P,3,4] with P = {P}, got {tuple(g.shape)}")
+            return g.detach().float().contiguous()
+        if T is None:
+            return None
+        if T.dim() != 3 or T.shape[0] != P or T.shape[1] not in (3, 4) or T.shape[2] != 4:
+            raise ValueError(f"T must be [P,4,4] or [P,3,4] with P = {P}, got {tuple(T.shape)}")
+        return inverse(T.detach().float()).contiguous()
+
+    def _accumulate_batch(self, mem_pcs, new_pcs, T, voxel=None, g=None):
         """Scene memory, an extension beyond the released reference (its README promises "the accumulation of point clouds originating from
         the same instance"; more_solver.py:246-299 stops after the registration): merge P kept instance clouds mem_pcs[p] [a_p,3] (in
         the memory's frame) with the matched observations new_pcs[p] [b_p,3] in ONE ragged call (ops.cloud_merge_batch, csrc/cloudmerge.hip).
@@ -270,19 +286,17 @@ class More_Solver:
         observation rows) lies in its voxel, so what the memory holds always wins and an instance seen any number of times stays at one
         point per voxel.  voxel: the edge in metres, default cfg['accumulate']['voxel_size'], else 0.01 -- AN UNMEASURED CHOICE: roughly a
         third of the point spacing of a 1 024-point, 1 m object, so a sampled cloud passes nearly whole while repeated observations of a
-        surface do not pile up.  -> list of P merged clouds [n_p,3]."""
+        surface do not pile up.  g (keyword, [P,4,4] or [P,3,4]): the pose rescan -> memory given directly instead of T -- what
+        _refine_on_memory_batch returns, so a refined pose reaches the merge without an inverse of an inverse; T and g together are an error.
+        -> list of P merged clouds [n_p,3]."""
         if voxel is None:
             voxel = self.cfg.get("accumulate", {}).get("voxel_size", 0.01)
         if len(mem_pcs) != len(new_pcs):
             raise ValueError(f"{len(mem_pcs)} memory clouds for {len(new_pcs)} observations")
-        g = None
-        if T is not None:
-            if T.dim() != 3 or T.shape[0] != len(mem_pcs) or T.shape[1] not in (3, 4) or T.shape[2] != 4:
-                raise ValueError(f"T must be [P,4,4] or [P,3,4] with P = {len(mem_pcs)}, got {tuple(T.shape)}")
-            g = inverse(T.detach().float()).contiguous()
+        g = self._memory_pose(T, g, len(mem_pcs))
         return [pts for pts, _ in ops.cloud_merge_batch([p.detach() for p in mem_pcs], [p.detach() for p in new_pcs], g=g, voxel=voxel)]
 
-    def _overlap_batch(self, mem_pcs, new_pcs, T, radius=None):
+    def _overlap_batch(self, mem_pcs, new_pcs, T, radius=None, g=None):
         """Scene memory, the question before a merge (an extension beyond the released reference, like _accumulate_batch): how well do P
         registered observations new_pcs[p] [b_p,3] agree with the kept clouds mem_pcs[p] [a_p,3]?  ONE ragged fixed-radius nearest-neighbour
         call (ops.cloud_nearest_batch, csrc/cloudnear.hip).  T [P,4,4] or [P,3,4] is the registration exactly as
@@ -290,7 +304,8 @@ class More_Solver:
         _accumulate_batch does (T None: the observations are in the memory's frame already).  radius: default
         cfg['accumulate']['overlap_radius'], else 2 * voxel with the voxel of _accumulate_batch -- A DERIVED DEFAULT, not a tuned one: a
         point the merge drops shares a voxel of edge h with a kept one, so a perfectly registered re-observation of a surface the memory
-        already holds lies within sqrt(3) h < 2 h of a kept point.
+        already holds lies within sqrt(3) h < 2 h of a kept point.  g (keyword): the pose rescan -> memory given directly instead of T,
+        as for _accumulate_batch; T and g together are an error.
         -> dict of per-pair lists: overlap = matched / finite observation points (0.0 with no finite point), rmse = sqrt(sum d2 / matched)
         (nan with none), memory_seen = memory points that are some observation point's neighbour / a_p (0.0 for an empty memory), counts =
         the raw int64 triples (finite queries, matched, memory points hit), nn_idx [b_p] int32 = the memory row nearest to every
@@ -300,14 +315,15 @@ class More_Solver:
             radius = acc.get("overlap_radius", 2 * acc.get("voxel_size", 0.01))
         if len(mem_pcs) != len(new_pcs):
             raise ValueError(f"{len(mem_pcs)} memory clouds for {len(new_pcs)} observations")
-        g = None
-        if T is not None:
-            if T.dim() != 3 or T.shape[0] != len(mem_pcs) or T.shape[1] not in (3, 4) or T.shape[2] != 4:
-                raise ValueError(f"T must be [P,4,4] or [P,3,4] with P = {len(mem_pcs)}, got {tuple(T.shape)}")
-            g = inverse(T.detach().float()).contiguous()
+        g = self._memory_pose(T, g, len(mem_pcs))
         res = ops.cloud_nearest_batch([p.detach() for p in mem_pcs], [p.detach() for p in new_pcs], g=g, radius=radius)
+        return self._overlap_figures(mem_pcs, res)
+
+    @staticmethod
+    def _overlap_figures(mem_pcs, searches):
+        """the dict of _overlap_batch from per-pair search results (idx, d2, counts, sum_d2)"""
         out = {"overlap": [], "rmse": [], "memory_seen": [], "counts": [], "nn_idx": []}
-        for mem_pc, (idx, _, counts, sum_d2) in zip(mem_pcs, res):
+        for mem_pc, (idx, _, counts, sum_d2) in zip(mem_pcs, searches):
             finite, matched, seen = (int(c) for c in counts)
             out["overlap"].append(matched / finite if finite else 0.0)
             out["rmse"].append(math.sqrt(sum_d2 / matched) if matched else float("nan"))
@@ -315,6 +331,36 @@ class More_Solver:
             out["counts"].append(counts)
             out["nn_idx"].append(idx)
         return out
+
+    def _refine_on_memory_batch(self, mem_pcs, new_pcs, T, radius, **kw):
+        """Scene memory, the pose the merge and the overlap gate trust (an extension beyond the released reference, like both): refine P
+        registrations on the memory itself, at full resolution, in ONE ragged call (ops.cloud_icp_batch, csrc/cloudnear.hip) -- trimmed
+        ICP of the observation new_pcs[p] [b_p,3] onto the kept cloud mem_pcs[p] [a_p,3], only correspondences within `radius` counting,
+        so the part of the memory a partial view does not see pulls on nothing.  T [P,4,4] or [P,3,4] maps memory -> rescan, as
+        everywhere; the operator gets inverse(T) as its initial pose: the partial view moves onto the complete cloud.  kw: max_iter,
+        rel_thr, min_matched of ops.cloud_icp_batch (its defaults are ops.icp's, pytorch3d's: inherited, not tuned).  `radius` HAS NO
+        DEFAULT: it must exceed the error of the registration it starts from, which no trained checkpoint exists here to measure.
+        -> (T' [P,4,4] = inverse(g_out); a problem that made no update -- iters 0 -- keeps the caller's T bit for bit,
+            dict: g [P,3,4] (g_out, rescan -> memory: what _accumulate_batch / _overlap_batch take as g=), stop, iters (host int32 [P])
+            and the entries of _overlap_batch (overlap, rmse, memory_seen, counts, nn_idx) formed from the final search of the
+            refinement, which is the search _overlap_batch(g=g_out, radius=radius) would make)."""
+        P = len(mem_pcs)
+        if len(new_pcs) != P:
+            raise ValueError(f"{P} memory clouds for {len(new_pcs)} observations")
+        if T is None or T.dim() != 3 or T.shape[0] != P or T.shape[1] not in (3, 4) or T.shape[2] != 4:
+            raise ValueError(f"T must be [P,4,4] or [P,3,4] with P = {P}, got {None if T is None else tuple(T.shape)}")
+        res = ops.cloud_icp_batch([p.detach() for p in mem_pcs], [p.detach() for p in new_pcs], g=self._memory_pose(T, None, P), radius=radius,
+                                  packed=True, **kw)
+        last_row = T.new_tensor([0.0, 0.0, 0.0, 1.0]).expand(P, 1, 4)
+        T4 = T.detach() if T.shape[1] == 4 else torch.cat([T.detach(), last_row], 1)
+        moved = torch.tensor((res["iters"] > 0).tolist(), device=T.device)
+        T_new = torch.where(moved.view(P, 1, 1), torch.cat([inverse(res["g"]).to(T4), last_row], 1), T4)
+        sizes = [int(b1 - b0) for b0, b1 in zip(res["b_off"][:-1], res["b_off"][1:])]
+        searches = [(i, d, res["counts"][p], float(res["sum_d2"][p]))
+                    for p, (i, d) in enumerate(zip(torch.split(res["idx"], sizes), torch.split(res["d2"], sizes)))]
+        info = {"g": res["g"], "stop": res["stop"], "iters": res["iters"]}
+        info.update(self._overlap_figures(mem_pcs, searches))
+        return T_new, info
 
     def _mesh_from_latent(self, latent_code):
         """more_solver.py:37-58: mesh of the canonical shape (t = 0, s = 1), then scaled and moved to the instance pose."""
@@ -526,7 +572,8 @@ def _encode_clouds(model, clouds):
     return model.encode_fps(buf, mask)
 
 
-def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, optimize_codes=False, overlap_radius=None, min_overlap=None):
+def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, optimize_codes=False, overlap_radius=None, min_overlap=None,
+                   refine_radius=None):
     """A reference scan followed by SEVERAL rescans, with a memory that carries every instance's points from one rescan to the next -- an
     extension beyond the released reference (more_solver.py:246-299 solves one (reference, rescan) pair and drops the rescan's points).
     ref and every rescan: {'pc' [n,3,Nmax], 'pc_mask'} as _solve_end2end takes them.
@@ -553,7 +600,17 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
     (slots).  Pairs with overlap < min_overlap (None: nothing is rejected, the figures are only reported) are left out of the ONE
     _accumulate_batch call: a rejected slot keeps its cloud and code, gets n_new_points 0 and is not re-encoded; its registration and codes
     entries are still reported.  min_overlap HAS NO DEFAULT AND NONE IS RECOMMENDED: no trained checkpoint exists here to measure one
-    against, so the threshold is the caller's to choose."""
+    against, so the threshold is the caller's to choose.
+
+    The refinement on the memory (opt-in: with refine_radius None nothing below happens and the step dicts are as above).  With a number,
+    ONE More_Solver._refine_on_memory_batch call over the matched pairs follows the registration batch: trimmed ICP of every rescan
+    instance onto the memory cloud of its slot, at full resolution, correspondences within refine_radius only.  `registration` and `codes`
+    then use the refined T', and the step gains refine_stop, refine_iters (lists of n, None for unmatched slots; LS_ICP_* values) and
+    registration_init (the registration before the refinement).  The merge receives the refined pose directly (g=, no inverse of an
+    inverse).  With the overlap gate on as well, its figures are the refinement's own final search when overlap_radius equals
+    refine_radius -- no second search -- and otherwise come from one _overlap_batch(g=g_out) call.  refine_radius HAS NO DEFAULT AND
+    NONE IS RECOMMENDED, like min_overlap: it must exceed the error of the initial registration, and no trained checkpoint exists here to
+    measure that."""
     gate = overlap_radius is not None or min_overlap is not None
     model = solver.model
     n_in = solver.cfg["shape_priors"]["n_input_point"]
@@ -575,16 +632,30 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
         pairs = plan["pairs"]
         out = {"ref_pc_lst": list(mem), "rescan_pc_lst": res_full, "matches": m0, "registration": [None] * n, "codes": [None] * n,
                "mesh_lst": [None] * n, "n_new_points": [0] * n, "unmatched_rescan": plan["unmatched_new"]}
+        if refine_radius is not None:
+            out.update({"refine_stop": [None] * n, "refine_iters": [None] * n, "registration_init": [None] * n})
         if pairs:
             src, tgt = [mem[i] for i, _ in pairs], [res_full[j] for _, j in pairs]
             R, t = solver._solve_pairwise_registration_optim_batch(src, tgt) if optim else solver._solve_pairwise_registration_batch(src, tgt)
             T = Rt_to_SE3(R, t)
+            refined = None
+            if refine_radius is not None:
+                T_init = T
+                T, refined = solver._refine_on_memory_batch(src, tgt, T_init, refine_radius)
+                for k, (i, _) in enumerate(pairs):
+                    out["refine_stop"][i], out["refine_iters"][i] = int(refined["stop"][k]), int(refined["iters"][k])
+                    out["registration_init"][i] = T_init[k:k + 1]
             accepted = None
             if gate:
                 radius = overlap_radius
                 if radius is None and voxel is not None:
                     radius = solver.cfg.get("accumulate", {}).get("overlap_radius", 2 * voxel)
-                ov = solver._overlap_batch(src, tgt, T, radius=radius)
+                if refined is None:
+                    ov = solver._overlap_batch(src, tgt, T, radius=radius)
+                elif radius is not None and float(radius) == float(refine_radius):
+                    ov = refined                                      # the refinement's final search is this search
+                else:
+                    ov = solver._overlap_batch(src, tgt, None, radius=radius, g=refined["g"])
                 accepted = [min_overlap is None or o >= min_overlap for o in ov["overlap"]]
                 out.update({"overlap": [None] * n, "overlap_rmse": [None] * n, "memory_seen": [None] * n})
                 for k, (i, _) in enumerate(pairs):
@@ -598,7 +669,11 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
             grew = []
             if keep:
                 sel = torch.tensor(keep, device=T.device)
-                merged = solver._accumulate_batch([src[k] for k in keep], [tgt[k] for k in keep], T if accepted is None else T[sel], voxel=voxel)
+                if refined is None:
+                    merged = solver._accumulate_batch([src[k] for k in keep], [tgt[k] for k in keep], T if accepted is None else T[sel], voxel=voxel)
+                else:
+                    merged = solver._accumulate_batch([src[k] for k in keep], [tgt[k] for k in keep], None, voxel=voxel,
+                                                      g=refined["g"] if accepted is None else refined["g"][sel])
                 grew = [c.shape[0] - src[k].shape[0] for c, k in zip(merged, keep)]   # the memory's rows are kept whole: the rest came from the rescan
                 for c, k, d in zip(merged, keep, grew):
                     out["n_new_points"][pairs[k][0]] = d

@@ -889,22 +889,54 @@ def cloud_merge(A, B, g=None, *, voxel):
 
 
 # ------------------------------------------------------------------------------------------------ scene memory: radius search (csrc/cloudnear.hip)
-def _near_cloud(x, what):
+def _near_cloud(x, what, op="cloud_nearest"):
     if not torch.is_tensor(x) or x.device.type != "cuda" or x.dtype != torch.float32:
         kind = f"{x.device.type} {x.dtype}" if torch.is_tensor(x) else type(x).__name__
-        raise _lib.LsError(f"cloud_nearest: {what} must be an fp32 HIP (cuda) tensor, got {kind}: the MI355X path has no CPU fallback and converts nothing")
+        raise _lib.LsError(f"{op}: {what} must be an fp32 HIP (cuda) tensor, got {kind}: the MI355X path has no CPU fallback and converts nothing")
     if x.dim() != 2 or x.shape[1] != 3:
-        raise ValueError(f"cloud_nearest: {what} is [n, 3], got {tuple(x.shape)}")
+        raise ValueError(f"{op}: {what} is [n, 3], got {tuple(x.shape)}")
     return x.contiguous()
 
 
-def _near_meta(meta, P):
-    """the one host read of a call: counts [P,3] int64, sum_d2 [P] float64, status [P] int32 from the int64 words of `meta`"""
+def _near_meta(meta, P, op="cloud_nearest"):
+    """the one host read of a call: counts [P,3] int64, sum_d2 [P] float64, status [P] int32 and the int32 words after it from the int64
+    words of `meta`"""
     host = meta.cpu().numpy()
-    st = host[4 * P:].view(np.int32)[:P]
+    tail = host[4 * P:].view(np.int32)
+    st = tail[:P]
     if st.any():
-        raise _lib.LsError(f"cloud_nearest: problem {int(np.flatnonzero(st)[0])}: status {int(st[np.flatnonzero(st)[0]])} (the cell table overflowed: a defect)")
-    return host[:3 * P].reshape(P, 3).copy(), host[3 * P:4 * P].view(np.float64).copy()
+        raise _lib.LsError(f"{op}: problem {int(np.flatnonzero(st)[0])}: status {int(st[np.flatnonzero(st)[0]])} (the cell table overflowed: a defect)")
+    return host[:3 * P].reshape(P, 3).copy(), host[3 * P:4 * P].view(np.float64).copy(), tail[P:].copy()
+
+
+def _near_batch_args(op, As, Bs, g, radius):
+    """the argument checks and the packing of a ragged batch of (kept cloud, observation) problems -> (P, dev, A, B, a_off, b_off, radii, g)"""
+    As, Bs = [_near_cloud(x, "A", op) for x in As], [_near_cloud(x, "B", op) for x in Bs]
+    P = len(As)
+    if len(Bs) != P:
+        raise ValueError(f"{op}: {P} kept clouds for {len(Bs)} observations")
+    if P == 0:
+        raise ValueError(f"{op}: no problem given")
+    dev = As[0].device
+    rad = np.full(P, float(radius), dtype=np.float32) if np.ndim(radius) == 0 else np.ascontiguousarray(radius, dtype=np.float32).reshape(-1)
+    if rad.shape[0] != P:
+        raise ValueError(f"{op}: {rad.shape[0]} radii for {P} problems")
+    if g is not None:
+        if not torch.is_tensor(g) or g.dim() != 3 or g.shape[0] != P or g.shape[1] not in (3, 4) or g.shape[2] != 4:
+            raise ValueError(f"{op}: g must be [P,3,4] or [P,4,4] with P = {P}, got {tuple(g.shape) if torch.is_tensor(g) else type(g).__name__}")
+        g = _f32(g.to(dev)[:, :3, :])
+    A = torch.cat(As, 0) if P > 1 else As[0]
+    B = torch.cat(Bs, 0) if P > 1 else Bs[0]
+    return P, dev, A, B, _offsets([x.shape[0] for x in As]), _offsets([x.shape[0] for x in Bs]), rad, g
+
+
+def _near_one_args(op, A, B, g):
+    A, B = _near_cloud(A, "A", op), _near_cloud(B, "B", op)
+    if g is not None:
+        if not torch.is_tensor(g) or tuple(g.shape) not in ((3, 4), (4, 4)):
+            raise ValueError(f"{op}: g must be [3,4] or [4,4], got {tuple(g.shape) if torch.is_tensor(g) else type(g).__name__}")
+        g = _f32(g.to(A.device)[:3, :])
+    return A, B, g
 
 
 def cloud_nearest_batch(As, Bs, g=None, *, radius, packed=False):
@@ -915,23 +947,7 @@ def cloud_nearest_batch(As, Bs, g=None, *, radius, packed=False):
     counts: host int64 [3] = finite queries, queries with a neighbour, targets that are somebody's neighbour; sum_d2: float, the float64 sum
     of the finite d2), idx / d2 views of one packed tensor; packed=True: (idx, d2, counts [P,3], sum_d2 [P], b_off) with the host int64
     query offsets [P+1].  One call, one host read (counts, sums and status), whatever P."""
-    As, Bs = [_near_cloud(x, "A") for x in As], [_near_cloud(x, "B") for x in Bs]
-    P = len(As)
-    if len(Bs) != P:
-        raise ValueError(f"cloud_nearest: {P} kept clouds for {len(Bs)} observations")
-    if P == 0:
-        raise ValueError("cloud_nearest: no problem given")
-    dev = As[0].device
-    rad = np.full(P, float(radius), dtype=np.float32) if np.ndim(radius) == 0 else np.ascontiguousarray(radius, dtype=np.float32).reshape(-1)
-    if rad.shape[0] != P:
-        raise ValueError(f"cloud_nearest: {rad.shape[0]} radii for {P} problems")
-    if g is not None:
-        if not torch.is_tensor(g) or g.dim() != 3 or g.shape[0] != P or g.shape[1] not in (3, 4) or g.shape[2] != 4:
-            raise ValueError(f"cloud_nearest: g must be [P,3,4] or [P,4,4] with P = {P}, got {tuple(g.shape) if torch.is_tensor(g) else type(g).__name__}")
-        g = _f32(g.to(dev)[:, :3, :])
-    A = torch.cat(As, 0) if P > 1 else As[0]
-    B = torch.cat(Bs, 0) if P > 1 else Bs[0]
-    ao, bo = _offsets([x.shape[0] for x in As]), _offsets([x.shape[0] for x in Bs])
+    P, dev, A, B, ao, bo, rad, g = _near_batch_args("cloud_nearest", As, Bs, g, radius)
     idx = torch.empty(B.shape[0], dtype=torch.int32, device=dev)
     d2 = torch.empty(B.shape[0], dtype=torch.float32, device=dev)
     meta = torch.empty(4 * P + (P + 1) // 2, dtype=torch.int64, device=dev)   # counts [P,3] int64, sum_d2 [P] float64, status [P] int32
@@ -939,7 +955,7 @@ def cloud_nearest_batch(As, Bs, g=None, *, radius, packed=False):
     call(dev, "ls_cloud_nearest_batch_f32", P, ptr(A), A.shape[0], _hptr(ao), ptr(B), B.shape[0], _hptr(bo), ptr(g), _hptr(rad), ptr(idx), ptr(d2),
          ptr(meta), ctypes.c_void_p(meta.data_ptr() + 24 * P), ctypes.c_void_p(meta.data_ptr() + 32 * P), ptr(ws), 0 if ws is None else ws.numel(),
          stream_ptr(dev))
-    counts, sums = _near_meta(meta, P)
+    counts, sums, _ = _near_meta(meta, P)
     if packed:
         return idx, d2, counts, sums, bo
     sizes = np.diff(bo).tolist()
@@ -950,17 +966,87 @@ def cloud_nearest(A, B, g=None, *, radius):
     """ls_cloud_nearest_f32: the kept cloud A [a,3] (targets) and the observation B [b,3] (queries; fp32 HIP tensors), g [3,4] or [4,4]
     taking B into A's frame (None: identity) -> (idx [b] int32, d2 [b] fp32, counts host int64 [3], sum_d2 float) as cloud_nearest_batch
     describes them.  Bit-identical to the same problem inside any cloud_nearest_batch."""
-    A, B = _near_cloud(A, "A"), _near_cloud(B, "B")
+    A, B, g = _near_one_args("cloud_nearest", A, B, g)
     dev = A.device
-    if g is not None:
-        if not torch.is_tensor(g) or tuple(g.shape) not in ((3, 4), (4, 4)):
-            raise ValueError(f"cloud_nearest: g must be [3,4] or [4,4], got {tuple(g.shape) if torch.is_tensor(g) else type(g).__name__}")
-        g = _f32(g.to(dev)[:3, :])
     idx = torch.empty(B.shape[0], dtype=torch.int32, device=dev)
     d2 = torch.empty(B.shape[0], dtype=torch.float32, device=dev)
     meta = torch.empty(5, dtype=torch.int64, device=dev)                      # counts [3], sum_d2, then the status
     ws = _scratch(load().ls_cloud_nearest_workspace_bytes(A.shape[0], B.shape[0]), dev)
     call(dev, "ls_cloud_nearest_f32", ptr(A), A.shape[0], ptr(B), B.shape[0], ptr(g), float(radius), ptr(idx), ptr(d2), ptr(meta),
          ctypes.c_void_p(meta.data_ptr() + 24), ctypes.c_void_p(meta.data_ptr() + 32), ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev))
-    counts, sums = _near_meta(meta, 1)
+    counts, sums, _ = _near_meta(meta, 1)
     return idx, d2, counts[0], float(sums[0])
+
+
+# ------------------------------------------------------------------------------------------------ scene memory: trimmed ICP on the search's grid
+ICP_STOP = ("converged", "max_iter", "starved", "degenerate")   # LS_ICP_* of include/livingscenes_hip.h, by value
+
+
+def _icp_buffers(P, b, dev, max_iter, trace):
+    """the outputs of an ICP call: idx, d2, g_out, the traces (or None) and `meta` -- counts [P,3] int64, sum_d2 [P] float64, then status, stop
+    and iters [P] int32 each -- with the pointers into it: one host read per call"""
+    idx = torch.empty(b, dtype=torch.int32, device=dev)
+    d2 = torch.empty(b, dtype=torch.float32, device=dev)
+    g_out = torch.empty(P, 3, 4, dtype=torch.float32, device=dev)
+    meta = torch.empty(4 * P + (3 * P + 1) // 2, dtype=torch.int64, device=dev)
+    at = [ctypes.c_void_p(meta.data_ptr() + o) for o in (0, 24 * P, 32 * P, 36 * P, 40 * P)]   # counts, sum_d2, status, stop, iters
+    g_trace = torch.zeros(P, max_iter + 1, 12, dtype=torch.float32, device=dev) if trace else None
+    stat_trace = torch.zeros(P, max_iter + 1, 3, dtype=torch.float64, device=dev) if trace else None
+    return idx, d2, g_out, meta, at, g_trace, stat_trace
+
+
+def cloud_icp_batch(As, Bs, g=None, *, radius, max_iter=100, rel_thr=1e-6, min_matched=3, trace=False, packed=False):
+    """ls_cloud_icp_batch_f32 (an extension beyond the released reference, like cloud_merge and cloud_nearest): trimmed ICP of P observations
+    Bs[p] [b_p,3] onto the kept clouds As[p] [a_p,3] on cloud_nearest's grid, at full resolution.  g [P,3,4] or [P,4,4] is the initial pose
+    taking B_p into A_p's frame (None: the identity), radius = one radius or P radii: only correspondences within it count, so the part of
+    A_p the observation does not see pulls on nothing.  Per iteration: cloud_nearest under the current pose, the truncated-quadratic cost
+    E = (sum d2 + unmatched r^2) / finite, the stop tests (fewer than min_matched matches: starved; E fell by <= rel_thr E: converged;
+    max_iter updates made), else a float64 Kabsch update from the matched pairs (include/livingscenes_hip.h has the definition to the bit).
+    max_iter = 100 and rel_thr = 1e-6 are the defaults of ops.icp, which are pytorch3d's: INHERITED, NOT TUNED.
+    -> list of P dicts: g [3,4] fp32 (device), stop (int, LS_ICP_*; ICP_STOP names them), iters (int), and the final search exactly as
+    cloud_nearest(A_p, B_p, g, radius) returns it: idx, d2, counts (host int64 [3]), sum_d2 (float); trace=True adds g_trace
+    [max_iter+1,12] and stat_trace [max_iter+1,3] float64 = (finite, matched, sum d2) per iteration (device; rows <= iters are written).
+    packed=True: one dict of the packed tensors (g [P,3,4], stop / iters int32 [P], counts [P,3], sum_d2 [P], ...) plus b_off.  One call,
+    one host read (counts, sums, status, stop, iters), whatever P and however many iterations."""
+    op = "cloud_icp"
+    P, dev, A, B, ao, bo, rad, g = _near_batch_args(op, As, Bs, g, radius)
+    max_iter = int(max_iter)
+    idx, d2, g_out, meta, at, g_trace, stat_trace = _icp_buffers(P, B.shape[0], dev, max(max_iter, 0), trace)
+    ws = _scratch(load().ls_cloud_icp_batch_workspace_bytes(P, A.shape[0], B.shape[0]), dev)
+    call(dev, "ls_cloud_icp_batch_f32", P, ptr(A), A.shape[0], _hptr(ao), ptr(B), B.shape[0], _hptr(bo), ptr(g), _hptr(rad), max_iter,
+         float(rel_thr), int(min_matched), ptr(g_out), at[3], at[4], ptr(idx), ptr(d2), at[0], at[1], at[2], ptr(g_trace), ptr(stat_trace), ptr(ws),
+         0 if ws is None else ws.numel(), stream_ptr(dev))
+    counts, sums, tail = _near_meta(meta, P, op)
+    stop, iters = tail[:P], tail[P:2 * P]
+    if packed:
+        out = {"g": g_out, "stop": stop, "iters": iters, "idx": idx, "d2": d2, "counts": counts, "sum_d2": sums, "b_off": bo}
+        if trace:
+            out.update(g_trace=g_trace, stat_trace=stat_trace)
+        return out
+    sizes = np.diff(bo).tolist()
+    res = []
+    for p, (i, d) in enumerate(zip(torch.split(idx, sizes), torch.split(d2, sizes))):
+        res.append({"g": g_out[p], "stop": int(stop[p]), "iters": int(iters[p]), "idx": i, "d2": d, "counts": counts[p], "sum_d2": float(sums[p])})
+        if trace:
+            res[-1].update(g_trace=g_trace[p], stat_trace=stat_trace[p])
+    return res
+
+
+def cloud_icp(A, B, g=None, *, radius, max_iter=100, rel_thr=1e-6, min_matched=3, trace=False):
+    """ls_cloud_icp_f32: trimmed ICP of the observation B [b,3] onto the kept cloud A [a,3] (fp32 HIP tensors), g [3,4] or [4,4] the initial
+    pose taking B into A's frame (None: identity) -> the dict cloud_icp_batch describes.  max_iter = 100 and rel_thr = 1e-6 are ops.icp's
+    defaults, pytorch3d's: inherited, not tuned.  Bit-identical to the same problem inside any cloud_icp_batch."""
+    op = "cloud_icp"
+    A, B, g = _near_one_args(op, A, B, g)
+    dev = A.device
+    max_iter = int(max_iter)
+    idx, d2, g_out, meta, at, g_trace, stat_trace = _icp_buffers(1, B.shape[0], dev, max(max_iter, 0), trace)
+    ws = _scratch(load().ls_cloud_icp_workspace_bytes(A.shape[0], B.shape[0]), dev)
+    call(dev, "ls_cloud_icp_f32", ptr(A), A.shape[0], ptr(B), B.shape[0], ptr(g), float(radius), max_iter, float(rel_thr), int(min_matched),
+         ptr(g_out), at[3], at[4], ptr(idx), ptr(d2), at[0], at[1], at[2], ptr(g_trace), ptr(stat_trace), ptr(ws), 0 if ws is None else ws.numel(),
+         stream_ptr(dev))
+    counts, sums, tail = _near_meta(meta, 1, op)
+    out = {"g": g_out[0], "stop": int(tail[0]), "iters": int(tail[1]), "idx": idx, "d2": d2, "counts": counts[0], "sum_d2": float(sums[0])}
+    if trace:
+        out.update(g_trace=g_trace[0], stat_trace=stat_trace[0])
+    return out
