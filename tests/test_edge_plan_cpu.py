@@ -155,3 +155,39 @@ def test_the_32_bit_offset_limits_by_their_arithmetic(plan):
     res = plan([t(1, ok), t(1, over), t(0, ok), t(0, over)])
     assert [r[0][0][0] for r in res] == ["ls::edge_attn_fq_kernel<16, 32>", "ls::edge_attn_v4_kernel<16, 1>", "ls::edge_pool_v4_kernel<8>", "ls::edge_pool_kernel"]
     assert [r[1] for r in res] == [1, 2, 2, 2]
+
+
+def test_the_float64_ladder_reaches_every_enumerator(plan):
+    """tests/tools/edge_vs_float64.py: the cases tests/test_hip_edge_layers_f64.py holds to the float64 layer oracle.  In the default mode the
+    kernels the plan names for them are all thirteen ENUMERATORS; under bf16x3 and fp32 every case plans a table kernel (a table GEMM or two,
+    none of the fused or table-free forms).  This keeps the ladder honest when the plan changes.  The one branch no case takes is
+    edge_off32_fits() == false: it needs a table of 4 GB or more (test_the_32_bit_offset_limits_by_their_arithmetic holds it by its arithmetic)."""
+    lad = _tool("edge_vs_float64")
+    cases = [c for c in lad.ladder() if c[2] >= 1]
+    assert len(cases) > 60 and {c[2] for c in lad.ladder()} == set(range(7))
+    names = {r[0][-1][0] for r in plan([lad.traits(c, lad.MODES[0]) for c in cases])}
+    assert names == set(ENUMERATORS), (names - set(ENUMERATORS), set(ENUMERATORS) - names)
+    fused = tuple(n for n in ENUMERATORS if "_fq_" in n or "_ft_" in n)
+    for mode in lad.MODES[1:]:
+        res = plan([lad.traits(c, mode) for c in cases])
+        wrong = [c[0] for c, r in zip(cases, res) if r[1] not in (1, 2) or r[1] != 1 + c[3][3] or r[0][-1][0] in fused or len(r[0]) != 1]
+        assert not wrong, (mode, wrong[:4])
+
+
+def test_the_reduced_schedules_plan_the_kernels_with_side_products(rec, plan):
+    """The encodes of tests/test_hip_edge_layers_f64.py (edge_vs_float64.reduced_cfg): what their layers >= 2 launch inside ls_encode, and
+    whether row maxima and column sums are written."""
+    lad, rwb = _tool("edge_vs_float64"), _tool("record_workspace_bytes")
+    got = {}
+    for name, N in lad.REDUCED:
+        cfg = lad.reduced_cfg(name)
+        sizes = rwb.layer_sizes(cfg, N)
+        for fq in (1, 0):
+            res = plan([rec.edge_traits(cfg, "f16", i, 3, *sizes[i], fuse_q=fq, encode=True) for i in range(1, cfg["num_layers"])])
+            got[(name, N, fq)] = [(r[0][-1][0].replace("ls::edge_", "").replace("_kernel", ""), r[2] > 0, r[3] > 0) for r in res]
+    for fq in (1, 0):
+        assert got[("ft256", 32, fq)] == [("pool", False, False), ("ft_v<256, 32, 2>", True, True)]
+        assert got[("ft128", 128, fq)] == [("pool", False, False), ("ft_v<128, 128, 1>", True, True)]
+    for N, cs in ((64, True), (72, False)):
+        assert got[("fq", N, 1)] == [("pool_v4<8>", False, False)] + [(f"attn_fq<{k}>", True, cs) for k in ("16, 32", "16, 64", "32, 64")]
+        assert got[("fq", N, 0)] == [("pool_v4<8>", False, False)] + [(f"attn_v4<{k}, 1>", True, cs) for k in (16, 16, 32)]
