@@ -62,7 +62,8 @@ typedef enum {
  * any unknown option; 105: the mesh metrics ls_mesh_contains_f64 / ls_mesh_distance_f64 / ls_mesh_sample_f64; 106: ls_model_desc.dec_input and
  * off_dec_xyz_t, the invariant decoder_type "deepsdf"; 107: the ragged multi-mesh metrics ls_mesh_contains_batch_f64 /
  * ls_mesh_distance_batch_f64 / ls_mesh_sample_batch_f64; symbols added since -- ls_reg_metrics_batch, ls_mesh_cluster_f64 / ls_mesh_cluster_batch_f64,
- * ls_cloud_merge_f32 / ls_cloud_merge_batch_f32, ls_cloud_nearest_f32 / ls_cloud_nearest_batch_f32, ls_cloud_icp_f32 / ls_cloud_icp_batch_f32 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
+ * ls_cloud_merge_f32 / ls_cloud_merge_batch_f32, ls_cloud_nearest_f32 / ls_cloud_nearest_batch_f32, ls_cloud_icp_f32 / ls_cloud_icp_batch_f32,
+ * ls_cloud_normals_f32 / ls_cloud_normals_batch_f32, ls_cloud_icp_plane_f32 / ls_cloud_icp_plane_batch_f32 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
  * binding compares it with the header it was written against and refuses a mismatch (livingscenes_amd/_lib.py: load). */
 #define LS_ABI_VERSION 107
 int ls_version(void);
@@ -773,6 +774,82 @@ int ls_cloud_icp_batch_f32(int P, const float* A, long long a_total, const long 
                            const long long* b_off, const float* g0, const float* radius, int max_iter, double rel_thr, int min_matched,
                            float* g_out, int32_t* stop, int32_t* iters, int32_t* nn_idx, float* nn_d2, long long* counts, double* sum_d2,
                            int* status_out, float* g_trace, double* stat_trace, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Scene memory, a normal per kept point (csrc/cloudnear.hip): what the point-to-plane metric below needs and the memory does not hold.  AN
+ * EXTENSION BEYOND THE RELEASED REFERENCE, like the merge, the search and the ICP.  Definition, per problem (tests/normals_oracle.py is the
+ * same text as NumPy), with the conventions of ls_cloud_nearest_f32 -- cells of edge r, inv = 1.0f / r and r2 = r r formed on the host, all
+ * three finite and positive.  For every row i of A [a,3] that has a cell:
+ *   neighbours  the rows j of the same problem, i itself included, whose cell differs from i's by at most 1 on every axis and with
+ *               d2 <= r2, dx = A[i][0] - A[j][0] and so on, d2 = ((dx dx + dy dy) + dz dz) in fp32: the search's expression with the query
+ *               A[i] and no pose.  m_i is their number.
+ *   moments     u = dx inv in fp32, q = (int)rintf(u 32768.0f) per axis (|q| <= 2^15); s1 [3] = sum q and s2 [6] = sum q_a q_b in int64
+ *               (below 2^61 for any a <= INT_MAX).  The order of a cell's members depends on a race, so no float sum over them could be
+ *               reproducible; these integer sums are, and NumPy's int64 gives the same integers.
+ *   covariance  C_ab = (double)s2_ab - ((double)s1_a (double)s1_b) / (double)m_i, in this order, in float64.
+ *   eigenvalues lmin <= lmid <= lmax of the symmetric C by cyclic Jacobi in float64.
+ *   validity    the row is valid iff m_i >= min_nbrs, lmax > 0 and lmid > 2^-40 lmax: a coincident or collinear neighbourhood has no
+ *               normal.  min_nbrs >= 1 is the caller's; the rank rule does the real work.
+ *   normal      the unit eigenvector of lmin, rounded to fp32, with the sign that makes its component of largest fp32 magnitude (the first
+ *               such) positive.  The sign is a convention only: point-to-plane does not depend on it.
+ * Outputs: normals float [a,3]; nbr_cnt int32 [a] = m_i; variation float [a] = lmin / ((lmin + lmid) + lmax) in float64, rounded: the
+ * surface variation, for callers who want to leave edges and corners out; an invalid row has the normal (0, 0, 0) and variation 0, a row
+ * without a cell (a non-finite coordinate) also nbr_cnt 0; counts long long [2] = (rows with a cell, valid rows); status_out as in the search.
+ * One thread per row walks the 27 cells of the search's grid with ten integer accumulators in registers; 2 launches after the grid build.
+ * No host synchronisation, no allocation, integer atomics only and only on the table: every output is the same bits in any run. */
+size_t ls_cloud_normals_workspace_bytes(long long a);
+int ls_cloud_normals_f32(const float* A, long long a, float radius, int min_nbrs, float* normals, int32_t* nbr_cnt, float* variation,
+                         long long* counts, int* status_out, void* workspace, size_t workspace_bytes, void* stream);
+/* P >= 1 problems per call with the conventions of ls_cloud_nearest_batch_f32: a_off (HOST int64, P + 1 entries) and radius (HOST float,
+ * P entries) are checked before the first HIP call -- the error names the problem; min_nbrs is shared by the batch; empty problems are
+ * allowed.  normals [a_total,3], nbr_cnt / variation [a_total], counts [P,2], status_out [P] (nullable), all DEVICE.  Every output of every
+ * problem is BIT-IDENTICAL to ls_cloud_normals_f32 on that problem alone, and the number of launches does not depend on P. */
+size_t ls_cloud_normals_batch_workspace_bytes(int P, long long a_total);
+int ls_cloud_normals_batch_f32(int P, const float* A, long long a_total, const long long* a_off, const float* radius, int min_nbrs,
+                               float* normals, int32_t* nbr_cnt, float* variation, long long* counts, int* status_out, void* workspace,
+                               size_t workspace_bytes, void* stream);
+
+/* Scene memory, the trimmed ICP with the point-to-plane metric (csrc/cloudnear.hip).  AN EXTENSION BEYOND THE RELEASED REFERENCE, like
+ * ls_cloud_icp_f32, whose loop this is: a partial view registered point-to-point onto one point per voxel of a SURFACE slides along it
+ * slowly; the distance to the tangent plane of the neighbour lets it slide.  The arguments are those of ls_cloud_icp_f32 plus N [a,3] fp32
+ * (DEVICE) after A: the targets' normals, a zero row meaning "no normal".  The normals are an INPUT, so the operator does not depend on how
+ * they were made (ls_cloud_normals_f32 is one way).  Definition, per problem (tests/plane_icp_oracle.py is the same text as NumPy), g_0 as
+ * in ls_cloud_icp_f32, for k = 0, 1, ...:
+ *   search      exactly ls_cloud_nearest_f32(A, B, g_k, r) -> f_k, n_k, S_k, nn_idx, nn_d2, as in ls_cloud_icp_f32.
+ *   planar      a matched query is planar iff its neighbour's row of N is not (0, 0, 0); w_k is their number.  With y the posed row as the
+ *               search formed it (fp32), a the neighbour and n its normal, all converted to float64:
+ *               rho = ((y_0 - a_0) n_0 + (y_1 - a_1) n_1) + (y_2 - a_2) n_2, Q_k = sum rho^2 over the planar matches by the chunk rule.
+ *   cost        E_k = (Q_k + (f_k - w_k) (double)r2) / f_k, 0 for f_k = 0: the truncated quadratic again, since rho^2 <= d2 <= r2 for
+ *               unit normals.
+ *   stop tests  those of ls_cloud_icp_f32 in the same order, each keeping g_k, with min_matched applied to w_k: w_k < min_matched:
+ *               LS_ICP_STARVED; k >= 1 and E_{k-1} - E_k <= rel_thr E_{k-1}: LS_ICP_CONVERGED; k == max_iter: LS_ICP_MAX_ITER.  THE
+ *               LINEARISED STEP IS NOT GUARANTEED TO LOWER E: there is no line search and no damping, and a step that raises E ends the
+ *               loop as LS_ICP_CONVERGED at the next test, with the pose that step produced.  The trace shows E.
+ *   update      minimise sum (rho + omega . (y x n) + v . n)^2 over the planar matches: J = (n, y x n) in R^6 in float64, the twist order
+ *               (v, omega) of ls_se3_adam_step_f32; M = sum J J^T (21 unique entries), b = -sum J rho.  With Q these are 28 float64
+ *               quantities per chunk, added by the rule of ls_cloud_icp_f32 (a fixed tree in each wave, a fixed tree over the four waves,
+ *               one record per chunk, the records in chunk order).  Coordinates are not centred: the float64 choice of ls_cloud_icp_f32.
+ *               M xi = b by Cholesky in float64 in a fixed order; a pivot that is not > 1e-12 times the original diagonal entry, or any
+ *               non-finite value: LS_ICP_DEGENERATE, g_k is kept (one plane, or all normals parallel, is the exact case).
+ *   retraction  Delta = exp(xi) in float64 by Rodrigues with the left Jacobian for the translation (first order below theta = 1e-6);
+ *               R' = R_Delta R_k, t' = R_Delta t_k + t_Delta; R' is projected onto SO(3) by the rotation of ls_kabsch_batched_f32 for
+ *               R'^T (its polar factor) and both are rounded to fp32: every g_k is orthonormal to fp32 rounding.
+ * Outputs: those of ls_cloud_icp_f32 -- the final search is bit for bit ls_cloud_nearest_f32(A, B, g_out, r), the last search of the loop
+ * -- plus planar long long [1] = w and sum_rho2 double [1] = Q of that search; stat_trace double [max_iter+1, 5] = (f_k, n_k, S_k, w_k,
+ * Q_k).  Launches: 2 max_iter + 5 after the grid build, as there; a stopped problem is frozen.  The workspace is that of ls_cloud_icp_f32
+ * with a record of 28 float64 and one more int per chunk of queries. */
+size_t ls_cloud_icp_plane_workspace_bytes(long long a, long long b);
+int ls_cloud_icp_plane_f32(const float* A, const float* N, long long a, const float* B, long long b, const float* g0, float radius, int max_iter,
+                           double rel_thr, int min_matched, float* g_out, int32_t* stop, int32_t* iters, int32_t* nn_idx, float* nn_d2,
+                           long long* counts, double* sum_d2, long long* planar, double* sum_rho2, int* status_out, float* g_trace,
+                           double* stat_trace, void* workspace, size_t workspace_bytes, void* stream);
+/* P >= 1 problems per call with the conventions of ls_cloud_icp_batch_f32; N [a_total,3] packed like A, planar / sum_rho2 [P], stat_trace
+ * [P, max_iter+1, 5].  Every output of every problem is BIT-IDENTICAL to ls_cloud_icp_plane_f32 on that problem alone. */
+size_t ls_cloud_icp_plane_batch_workspace_bytes(int P, long long a_total, long long b_total);
+int ls_cloud_icp_plane_batch_f32(int P, const float* A, const float* N, long long a_total, const long long* a_off, const float* B,
+                                 long long b_total, const long long* b_off, const float* g0, const float* radius, int max_iter, double rel_thr,
+                                 int min_matched, float* g_out, int32_t* stop, int32_t* iters, int32_t* nn_idx, float* nn_d2, long long* counts,
+                                 double* sum_d2, long long* planar, double* sum_rho2, int* status_out, float* g_trace, double* stat_trace,
+                                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* The registration metrics of the relocalisation evaluation on P (reference instance, rescan instance, predicted pose, ground-truth pose)
  * tuples per call -- what eval_3rscan.py:384-401 / eval_flyingshape.py:136-148 compute pair by pair.  Pair p owns the rows

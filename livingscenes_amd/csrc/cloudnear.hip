@@ -22,6 +22,12 @@
 // the per-query walk is one __device__ function for both -- with the float64 moments of the matched pairs per chunk, and one workgroup per
 // problem adds the chunk records in order, applies the stop tests and solves the 3x3 Kabsch problem (svd3.h).  A stopped problem is frozen:
 // its workgroups exit at once, so the launches depend on max_iter alone and nothing waits on the host or on another workgroup.
+// Two more extensions on the same grid.  The normals of the kept cloud (ls_cloud_normals_f32; tests/normals_oracle.py): one thread per
+// target walks the 27 cells around its own with the target as the query and adds INTEGER moments of the neighbours' offsets -- the member
+// order depends on the race, an integer sum does not -- then the covariance and its eigenvectors in float64 (svd3.h).  And the same ICP
+// loop with the point-to-plane metric (ls_cloud_icp_plane_f32; tests/plane_icp_oracle.py): the search and the solve kernel are templates on
+// the metric, which says what a match adds to its chunk's record (15 moments for Kabsch | 28 for the 6 x 6 normal equations) and how
+// g_{k+1} follows from the sums (kabsch_rotation | Cholesky, exp, polar factor).
 #include <climits>
 #include <cmath>
 #include <vector>
@@ -168,11 +174,11 @@ __device__ __forceinline__ void pose_row(const float* __restrict__ g, float x0, 
         for (int r = 0; r < 3; ++r) y[r] = ((g[r * 4 + 0] * x0 + g[r * 4 + 1] * x1) + g[r * 4 + 2] * x2) + g[r * 4 + 3];
 }
 
-// the neighbour of the query y of cell c: the 27 cells around c, each by a probe walk that ends at the cell or at an empty slot; the minimum
-// under (d2, j) with the global index j (INT_MAX: none) and the neighbour's coordinates.  Written once, for the search and for the ICP.
-__device__ __forceinline__ void walk_cells(const NearRef& C, const float (&y)[3], const int (&c)[3], const int4* __restrict__ slots,
-                                           const int* __restrict__ cnt, const float4* __restrict__ members, float& best, int& best_j,
-                                           float (&best_a)[3]) {
+// the 27 cells around c, each by a probe walk that ends at the cell or at an empty slot: visit(member) for every target in them, in an order
+// that depends on the race.  Written once, for the search, for the ICP and for the normals.
+template <class Visit>
+__device__ __forceinline__ void walk_cells(const NearRef& C, const int (&c)[3], const int4* __restrict__ slots, const int* __restrict__ cnt,
+                                           const float4* __restrict__ members, Visit&& visit) {
     const long long t0 = 2 * C.a0, T = 2 * C.a;
     for (int k = 0; k < 27; ++k) {
         const int n0 = c[0] + k / 9 - 1, n1 = c[1] + (k / 3) % 3 - 1, n2 = c[2] + k % 3 - 1;   // |c| <= 2^30: no overflow
@@ -183,17 +189,7 @@ __device__ __forceinline__ void walk_cells(const NearRef& C, const float (&y)[3]
             if (sl.x == n0 && sl.y == n1 && sl.z == n2) {
                 const float4* __restrict__ m = members + sl.w;
                 const int count = cnt[t0 + s];
-                for (int e = 0; e < count; ++e) {
-                    const float4 t = m[e];
-                    const float dx = y[0] - t.x, dy = y[1] - t.y, dz = y[2] - t.z;
-                    const float d2 = (dx * dx + dy * dy) + dz * dz;
-                    const int j = __float_as_int(t.w);
-                    if (d2 <= C.r2 && (d2 < best || (d2 == best && j < best_j))) {
-                        best = d2;
-                        best_j = j;
-                        best_a[0] = t.x, best_a[1] = t.y, best_a[2] = t.z;
-                    }
-                }
+                for (int e = 0; e < count; ++e) visit(m[e]);
                 break;
             }
             if (++s == T) s = 0;
@@ -201,17 +197,33 @@ __device__ __forceinline__ void walk_cells(const NearRef& C, const float (&y)[3]
     }
 }
 
-// one thread's query of problem C under the pose g: finite?, and its neighbour
+// the neighbour of the query y of cell c: the minimum under (d2, j) over the 27 cells, with the global index j (INT_MAX: none) and the
+// neighbour's coordinates
+__device__ __forceinline__ void nearest_in_cells(const NearRef& C, const float (&y)[3], const int (&c)[3], const int4* __restrict__ slots,
+                                                 const int* __restrict__ cnt, const float4* __restrict__ members, float& best, int& best_j,
+                                                 float (&best_a)[3]) {
+    walk_cells(C, c, slots, cnt, members, [&](const float4 t) {
+        const float dx = y[0] - t.x, dy = y[1] - t.y, dz = y[2] - t.z;
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        const int j = __float_as_int(t.w);
+        if (d2 <= C.r2 && (d2 < best || (d2 == best && j < best_j))) {
+            best = d2;
+            best_j = j;
+            best_a[0] = t.x, best_a[1] = t.y, best_a[2] = t.z;
+        }
+    });
+}
+
+// one thread's query of problem C under the pose g: finite?, the posed row y as the search forms it, and its neighbour
 __device__ __forceinline__ bool query_one(const NearRef& C, const float* __restrict__ g, long long qi, const int4* __restrict__ slots,
-                                          const int* __restrict__ cnt, const float4* __restrict__ members, float (&x)[3], float& best,
-                                          int& best_j, float (&best_a)[3]) {
+                                          const int* __restrict__ cnt, const float4* __restrict__ members, float (&x)[3], float (&y)[3],
+                                          float& best, int& best_j, float (&best_a)[3]) {
     const float* __restrict__ row = C.B + qi * 3;
     x[0] = row[0], x[1] = row[1], x[2] = row[2];
-    float y[3];
     pose_row(g, x[0], x[1], x[2], y);
     int c[3];
     const bool finite = cell_of(y, C.inv, c);
-    if (finite && C.a > 0) walk_cells(C, y, c, slots, cnt, members, best, best_j, best_a);
+    if (finite && C.a > 0) nearest_in_cells(C, y, c, slots, cnt, members, best, best_j, best_a);
     return finite;
 }
 
@@ -239,8 +251,8 @@ __global__ __launch_bounds__(QUERY_CHUNK) void query_kernel(Near L, const int4* 
     const bool live = qi < C.b;
     bool finite = false;
     int best_j = INT_MAX;
-    float best = INFINITY, x[3], best_a[3];
-    if (live) finite = query_one(C, C.g, qi, slots, cnt, members, x, best, best_j, best_a);
+    float best = INFINITY, x[3], y[3], best_a[3];
+    if (live) finite = query_one(C, C.g, qi, slots, cnt, members, x, y, best, best_j, best_a);
     const bool has = best_j != INT_MAX;
     if (has) hit[best_j] = 1;                                          // every writer writes the same byte
     if (live) {
@@ -285,11 +297,106 @@ __global__ __launch_bounds__(256) void final_kernel(Near L, const unsigned char*
     }
 }
 
+// ------------------------------------------------------------------------------------------------ normals of the kept cloud (ls_cloud_normals_f32)
+constexpr float MOMENT_SCALE = 32768.0f;      // 2^15: dx / r in units of 2^-15, |q| <= 2^15, so a sum of q_a q_b over < 2^31 neighbours stays below 2^61
+
+// One thread per target i that has a cell: the walk of the search with the query A[i] and no pose.  The neighbours' offsets as integers
+// q = rint((dx inv) 2^15), their first and second moments in int64 -- the order of a cell's members depends on the race, an integer sum
+// does not -- the covariance in float64 from the integers, its eigenvalues by Jacobi (svd3.h), the validity rule and the sign rule of the
+// definition.  Ten accumulators in registers, no LDS.
+template <class Near>
+__global__ __launch_bounds__(256) void normals_kernel(Near L, const float* __restrict__ A, long long a_total, const int* __restrict__ tcell,
+                                                      const int4* __restrict__ slots, const int* __restrict__ cnt,
+                                                      const float4* __restrict__ members, int min_nbrs, float* __restrict__ normals,
+                                                      int* __restrict__ nbr_cnt, float* __restrict__ variation) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a_total) return;
+    const int c[3] = {tcell[i * 3 + 0], tcell[i * 3 + 1], tcell[i * 3 + 2]};
+    int m = 0;
+    float nrm[3] = {0.f, 0.f, 0.f}, var = 0.f;
+    if (c[0] != NO_CELL) {
+        const NearRef C = L.problem(L.target_owner(i));
+        const float y[3] = {A[i * 3 + 0], A[i * 3 + 1], A[i * 3 + 2]};
+        long long s1[3] = {0, 0, 0}, s2[6] = {0, 0, 0, 0, 0, 0};
+        walk_cells(C, c, slots, cnt, members, [&](const float4 t) {
+            const float dx = y[0] - t.x, dy = y[1] - t.y, dz = y[2] - t.z;
+            const float d2 = (dx * dx + dy * dy) + dz * dz;
+            if (d2 <= C.r2) {
+                const long long q0 = (int)rintf((dx * C.inv) * MOMENT_SCALE), q1 = (int)rintf((dy * C.inv) * MOMENT_SCALE),
+                                q2 = (int)rintf((dz * C.inv) * MOMENT_SCALE);
+                ++m;
+                s1[0] += q0, s1[1] += q1, s1[2] += q2;
+                s2[0] += q0 * q0, s2[1] += q0 * q1, s2[2] += q0 * q2, s2[3] += q1 * q1, s2[4] += q1 * q2, s2[5] += q2 * q2;
+            }
+        });
+        if (m >= min_nbrs && m > 0) {
+            const double dm = (double)m, d1[3] = {(double)s1[0], (double)s1[1], (double)s1[2]};
+            const double Cv[6] = {(double)s2[0] - (d1[0] * d1[0]) / dm, (double)s2[1] - (d1[0] * d1[1]) / dm, (double)s2[2] - (d1[0] * d1[2]) / dm,
+                                  (double)s2[3] - (d1[1] * d1[1]) / dm, (double)s2[4] - (d1[1] * d1[2]) / dm, (double)s2[5] - (d1[2] * d1[2]) / dm};
+            double lam[3], V[3][3];
+            sym_eig3(Cv, lam, V);
+            int lo = 0, hi = 0;
+            for (int k = 1; k < 3; ++k) {
+                if (lam[k] < lam[lo]) lo = k;
+                if (lam[k] > lam[hi]) hi = k;
+            }
+            if (hi == lo) hi = (lo + 1) % 3;                            // three equal eigenvalues
+            const int mid = 3 - lo - hi;
+            if (lam[hi] > 0.0 && lam[mid] > 0x1p-40 * lam[hi]) {
+                const double len = sqrt((V[0][lo] * V[0][lo] + V[1][lo] * V[1][lo]) + V[2][lo] * V[2][lo]);
+                for (int k = 0; k < 3; ++k) nrm[k] = (float)(V[k][lo] / len);
+                int big = 0;                                           // the first component of largest magnitude is positive
+                for (int k = 1; k < 3; ++k)
+                    if (fabsf(nrm[k]) > fabsf(nrm[big])) big = k;
+                const bool flip = nrm[big] < 0.f;
+                for (int k = 0; k < 3; ++k) nrm[k] = nrm[k] == 0.f ? 0.f : (flip ? -nrm[k] : nrm[k]);
+                var = (float)(lam[lo] / ((lam[lo] + lam[mid]) + lam[hi]));
+            }
+        }
+    }
+    for (int k = 0; k < 3; ++k) normals[i * 3 + k] = nrm[k];
+    nbr_cnt[i] = m;
+    variation[i] = var;
+}
+
+// workgroup = one problem: counts [2] = (rows with a cell: they are their own neighbour, rows with a normal), any order -- integers
+template <class Near>
+__global__ __launch_bounds__(256) void normals_final_kernel(Near L, const float* __restrict__ normals, const int* __restrict__ nbr_cnt,
+                                                            const int* __restrict__ status, long long* __restrict__ counts,
+                                                            int* __restrict__ status_out) {
+    __shared__ long long lds[2][256];
+    const int p = blockIdx.x;
+    const NearRef C = L.problem(p);
+    long long v[2] = {0, 0};
+    for (long long j = C.a0 + threadIdx.x; j < C.a0 + C.a; j += 256) {
+        v[0] += nbr_cnt[j] > 0;
+        v[1] += normals[j * 3 + 0] != 0.f || normals[j * 3 + 1] != 0.f || normals[j * 3 + 2] != 0.f;
+    }
+    for (int k = 0; k < 2; ++k) lds[k][threadIdx.x] = v[k];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o)
+            for (int k = 0; k < 2; ++k) lds[k][threadIdx.x] += lds[k][threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x < 2) counts[(size_t)p * 2 + threadIdx.x] = lds[threadIdx.x][0];
+    if (threadIdx.x == 0 && status_out) status_out[p] = status[p];
+}
+
 // ------------------------------------------------------------------------------------------------ trimmed ICP on the same grid (ls_cloud_icp_f32)
 // The state of a problem between two launches: its pose g_k and E_{k-1} in the workspace, stop[p] (ICP_RUNNING until a stop test holds) and
 // iters[p] in the caller's arrays.  A launch of iteration k touches the problems that still run and no other.
 constexpr int ICP_RUNNING = -1;
-constexpr int N_MOM = 15;                     // per chunk: sum x [3], sum a [3], sum x a^T [9], float64
+// The two metrics of the loop.  A metric says what a matched query adds to the record of float64 moments of its chunk, and how g_{k+1}
+// follows from the sums; the search, the chunk rule, the stop tests and the freezing are written once for both.
+struct PointMetric {                          // ls_cloud_icp_f32: sum x [3], sum a [3], sum x a^T [9] -> Kabsch
+    static constexpr bool PLANE = false;
+    static constexpr int N_MOM = 15, N_STAT = 3;
+};
+struct PlaneMetric {                          // ls_cloud_icp_plane_f32: Q = sum rho^2, sum J rho [6], sum J J^T [21, the upper triangle by rows] -> Cholesky
+    static constexpr bool PLANE = true;
+    static constexpr int N_MOM = 28, N_STAT = 5;
+};
 
 __global__ __launch_bounds__(256) void icp_init_kernel(int P, const float* __restrict__ g0, float* __restrict__ gk, double* __restrict__ e_prev,
                                                        int* __restrict__ stop, int* __restrict__ iters) {
@@ -309,16 +416,37 @@ __device__ __forceinline__ double wave_tree_f64(double v) {
     return v;
 }
 
+// what a planar match adds: y the posed row as the search formed it, a its neighbour, n the neighbour's normal, all as float64; every
+// product of two of them is exact in float64 (24 x 24 bits), the sums and the products with rho are rounded once each
+__device__ __forceinline__ void plane_moments(bool planar, const float (&y)[3], const float (&a)[3], const float (&n)[3],
+                                              double (&m)[PlaneMetric::N_MOM]) {
+    double yd[3], ad[3], J[6];
+    for (int r = 0; r < 3; ++r) yd[r] = planar ? (double)y[r] : 0.0, ad[r] = planar ? (double)a[r] : 0.0, J[r] = planar ? (double)n[r] : 0.0;
+    const double rho = ((yd[0] - ad[0]) * J[0] + (yd[1] - ad[1]) * J[1]) + (yd[2] - ad[2]) * J[2];
+    J[3] = yd[1] * J[2] - yd[2] * J[1];
+    J[4] = yd[2] * J[0] - yd[0] * J[2];
+    J[5] = yd[0] * J[1] - yd[1] * J[0];
+    m[0] = rho * rho;
+    for (int r = 0; r < 6; ++r) m[1 + r] = J[r] * rho;
+    int e = 7;
+    for (int r = 0; r < 6; ++r)
+        for (int c = r; c < 6; ++c) m[e++] = J[r] * J[c];
+}
+
 // The search of iteration k: query_kernel under g_k, for the chunks of the problems that still run.  Besides nn_idx / nn_d2 / part /
 // part_cnt -- the same values by the same code, so the last search of a problem IS its final search -- one record of N_MOM float64 moments
-// per chunk over the matched queries: the ORIGINAL row x of B and its neighbour a, products formed in float64 (exact: 24 x 24 bits).  The
-// moments go through a fixed tree inside every wave and a fixed tree over the four waves: 480 bytes of LDS instead of 30 KB.
-template <class Near>
+// per chunk over the matched queries.  Point metric: the ORIGINAL row x of B and its neighbour a, products formed in float64 (exact:
+// 24 x 24 bits).  Plane metric: a matched query gathers the normal row of its neighbour from N (packed like A); the match is planar iff
+// that row is not zero, part_w[chunk] counts them.  The moments go through a fixed tree inside every wave and a fixed tree over the four
+// waves: under 1 KB of LDS instead of 30 KB and more.
+template <class Near, class Metric>
 __global__ __launch_bounds__(QUERY_CHUNK) void icp_search_kernel(Near L, const int* __restrict__ stop, const float* __restrict__ gk,
                                                                  const int4* __restrict__ slots, const int* __restrict__ cnt,
-                                                                 const float4* __restrict__ members, int* __restrict__ nn_idx,
-                                                                 float* __restrict__ nn_d2, double* __restrict__ part,
-                                                                 int2* __restrict__ part_cnt, double* __restrict__ mom) {
+                                                                 const float4* __restrict__ members, const float* __restrict__ N,
+                                                                 int* __restrict__ nn_idx, float* __restrict__ nn_d2,
+                                                                 double* __restrict__ part, int2* __restrict__ part_cnt,
+                                                                 int* __restrict__ part_w, double* __restrict__ mom) {
+    constexpr int N_MOM = Metric::N_MOM;
     __shared__ double lds[QUERY_CHUNK];
     __shared__ double wave_part[N_MOM][QUERY_CHUNK / kWave];
     const int p = L.chunk_owner(blockIdx.x);
@@ -328,8 +456,8 @@ __global__ __launch_bounds__(QUERY_CHUNK) void icp_search_kernel(Near L, const i
     const bool live = qi < C.b;
     bool finite = false;
     int best_j = INT_MAX;
-    float best = INFINITY, x[3] = {0.f, 0.f, 0.f}, a[3] = {0.f, 0.f, 0.f};
-    if (live) finite = query_one(C, gk + (size_t)p * 12, qi, slots, cnt, members, x, best, best_j, a);
+    float best = INFINITY, x[3] = {0.f, 0.f, 0.f}, y[3] = {0.f, 0.f, 0.f}, a[3] = {0.f, 0.f, 0.f};
+    if (live) finite = query_one(C, gk + (size_t)p * 12, qi, slots, cnt, members, x, y, best, best_j, a);
     const bool has = best_j != INT_MAX;
     if (live) {
         nn_idx[C.b0 + qi] = has ? (int)(best_j - C.a0) : -1;
@@ -338,12 +466,22 @@ __global__ __launch_bounds__(QUERY_CHUNK) void icp_search_kernel(Near L, const i
     const int n_finite = __syncthreads_count(finite), n_has = __syncthreads_count(has);
     const double sum = chunk_sum(lds, has ? (double)best : 0.0);
     double m[N_MOM];
-    for (int r = 0; r < 3; ++r) {
-        m[r] = has ? (double)x[r] : 0.0;
-        m[3 + r] = has ? (double)a[r] : 0.0;
+    if constexpr (Metric::PLANE) {
+        float n[3] = {0.f, 0.f, 0.f};
+        if (has)
+            for (int r = 0; r < 3; ++r) n[r] = N[(long long)best_j * 3 + r];
+        const bool planar = has && (n[0] != 0.f || n[1] != 0.f || n[2] != 0.f);
+        const int n_planar = __syncthreads_count(planar);
+        if (threadIdx.x == 0) part_w[blockIdx.x] = n_planar;
+        plane_moments(planar, y, a, n, m);
+    } else {
+        for (int r = 0; r < 3; ++r) {
+            m[r] = has ? (double)x[r] : 0.0;
+            m[3 + r] = has ? (double)a[r] : 0.0;
+        }
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) m[6 + r * 3 + c] = m[r] * m[3 + c];
     }
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) m[6 + r * 3 + c] = m[r] * m[3 + c];
     const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
     for (int e = 0; e < N_MOM; ++e) {
         const double v = wave_tree_f64(m[e]);
@@ -360,16 +498,109 @@ __global__ __launch_bounds__(QUERY_CHUNK) void icp_search_kernel(Near L, const i
     }
 }
 
+// the Kabsch update of the point metric from the 15 sums over n matches: false = the solver reports anything but LS_KABSCH_OK
+__device__ __forceinline__ bool point_update(const double* sums, long long n, float* g) {
+    const double dn = (double)n;
+    double H[9], mx[3], ma[3];
+    float R[9];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) H[r * 3 + c] = sums[6 + r * 3 + c] - (sums[r] * sums[3 + c]) / dn;
+    for (int r = 0; r < 3; ++r) mx[r] = sums[r] / dn, ma[r] = sums[3 + r] / dn;
+    if (kabsch_rotation(H, R) != LS_KABSCH_OK) return false;
+    for (int r = 0; r < 3; ++r) {
+        const double Rm = ((double)R[r * 3 + 0] * mx[0] + (double)R[r * 3 + 1] * mx[1]) + (double)R[r * 3 + 2] * mx[2];
+        for (int c = 0; c < 3; ++c) g[r * 4 + c] = R[r * 3 + c];
+        g[r * 4 + 3] = (float)(ma[r] - Rm);
+    }
+    return true;
+}
+
+// The point-to-plane update from the 28 sums: M xi = b by Cholesky in float64 in a fixed order (column by column, every inner sum from
+// k = 0 upwards), xi = (v, omega); Delta = exp(xi) by Rodrigues with the left Jacobian for the translation (first order below
+// theta = 1e-6); R' = R_Delta R_k, t' = R_Delta t_k + t_Delta in float64; R' onto SO(3) by kabsch_rotation(R'^T), its polar factor;
+// rounded to fp32.  false (g untouched) = a pivot that is not > 1e-12 times its original diagonal entry, or anything non-finite.
+__device__ __forceinline__ bool plane_update(const double* sums, float* g) {
+    double L[6][6], b[6], z[6], xi[6];
+    {
+        int e = 7;
+        for (int r = 0; r < 6; ++r)
+            for (int c = r; c < 6; ++c) L[c][r] = sums[e++];            // the lower triangle holds M, then L in place
+        for (int r = 0; r < 6; ++r) b[r] = -sums[1 + r];
+    }
+    for (int j = 0; j < 6; ++j) {
+        const double mjj = L[j][j];
+        double d = mjj;
+        for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
+        if (!isfinite(d) || !(d > 1e-12 * mjj)) return false;
+        const double l = sqrt(d);
+        L[j][j] = l;
+        for (int i = j + 1; i < 6; ++i) {
+            double v = L[i][j];
+            for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
+            L[i][j] = v / l;
+        }
+    }
+    for (int i = 0; i < 6; ++i) {
+        double v = b[i];
+        for (int k = 0; k < i; ++k) v -= L[i][k] * z[k];
+        z[i] = v / L[i][i];
+    }
+    for (int i = 5; i >= 0; --i) {
+        double v = z[i];
+        for (int k = i + 1; k < 6; ++k) v -= L[k][i] * xi[k];
+        xi[i] = v / L[i][i];
+    }
+    for (int i = 0; i < 6; ++i)
+        if (!isfinite(xi[i])) return false;
+    const double w0 = xi[3], w1 = xi[4], w2 = xi[5];
+    const double th = sqrt((w0 * w0 + w1 * w1) + w2 * w2);
+    const double K[3][3] = {{0.0, -w2, w1}, {w2, 0.0, -w0}, {-w1, w0, 0.0}};
+    double ca = 1.0, cb = 0.5, cc = 0.0, cd = 0.0;                      // R_Delta = I + ca K + cd K^2, V = I + cb K + cc K^2
+    if (!(th < 1e-6)) {
+        ca = sin(th) / th;
+        cb = cd = (1.0 - cos(th)) / (th * th);
+        cc = (th - sin(th)) / (th * th * th);
+    }
+    double Rd[3][3], Vd[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            const double kk = (K[r][0] * K[0][c] + K[r][1] * K[1][c]) + K[r][2] * K[2][c], id = r == c ? 1.0 : 0.0;
+            Rd[r][c] = (id + ca * K[r][c]) + cd * kk;
+            Vd[r][c] = (id + cb * K[r][c]) + cc * kk;
+        }
+    double H[9], t[3];
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c)                                       // H = R'^T
+            H[c * 3 + r] = (Rd[r][0] * (double)g[0 * 4 + c] + Rd[r][1] * (double)g[1 * 4 + c]) + Rd[r][2] * (double)g[2 * 4 + c];
+        const double rt = (Rd[r][0] * (double)g[3] + Rd[r][1] * (double)g[7]) + Rd[r][2] * (double)g[11];
+        const double td = (Vd[r][0] * xi[0] + Vd[r][1] * xi[1]) + Vd[r][2] * xi[2];
+        t[r] = rt + td;
+        if (!isfinite(t[r])) return false;
+    }
+    float R[9];
+    if (kabsch_rotation(H, R) != LS_KABSCH_OK) return false;
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) g[r * 4 + c] = R[r * 3 + c];
+        g[r * 4 + 3] = (float)t[r];
+    }
+    return true;
+}
+
 // workgroup (one wave) = one problem that still runs, after the search of iteration k: the chunk records added in chunk order (lane e the
-// e-th float64 quantity, two lanes the counts), then one lane applies the stop tests of the definition or solves for g_{k+1}.
-template <class Near>
+// e-th float64 quantity, three lanes the counts), then one lane applies the stop tests of the definition or solves for g_{k+1}.  The plane
+// metric counts w, the planar matches, where the point metric counts n, and its cost takes Q = sum rho^2 where that takes S.
+template <class Near, class Metric>
 __global__ __launch_bounds__(kWave) void icp_solve_kernel(Near L, int k, int max_iter, double rel_thr, int min_matched,
                                                           const double* __restrict__ part, const int2* __restrict__ part_cnt,
-                                                          const double* __restrict__ mom, float* __restrict__ gk, double* __restrict__ e_prev,
-                                                          int* __restrict__ stop, int* __restrict__ iters, float* __restrict__ g_out,
-                                                          float* __restrict__ g_trace, double* __restrict__ stat_trace) {
+                                                          const int* __restrict__ part_w, const double* __restrict__ mom,
+                                                          float* __restrict__ gk, double* __restrict__ e_prev, int* __restrict__ stop,
+                                                          int* __restrict__ iters, float* __restrict__ g_out, long long* __restrict__ planar,
+                                                          double* __restrict__ sum_rho2, float* __restrict__ g_trace,
+                                                          double* __restrict__ stat_trace) {
+    constexpr int N_MOM = Metric::N_MOM, N_STAT = Metric::N_STAT;
+    static_assert(N_MOM + 4 <= kWave, "one lane per quantity");
     __shared__ double sums[N_MOM + 1];
-    __shared__ long long cnts[2];
+    __shared__ long long cnts[3];
     const int p = blockIdx.x;
     if (stop[p] != ICP_RUNNING) return;
     const NearRef C = L.problem(p);
@@ -386,44 +617,45 @@ __global__ __launch_bounds__(kWave) void icp_solve_kernel(Near L, int k, int max
         long long s = 0;
         for (long long q = C.q0; q < C.q1; ++q) s += e == N_MOM + 1 ? part_cnt[q].x : part_cnt[q].y;
         cnts[e - N_MOM - 1] = s;
+    } else if (e == N_MOM + 3) {
+        long long s = 0;
+        if constexpr (Metric::PLANE)
+            for (long long q = C.q0; q < C.q1; ++q) s += part_w[q];
+        cnts[2] = s;
     }
     __syncthreads();
     if (e != 0) return;
     float* g = gk + (size_t)p * 12;
-    const long long f = cnts[0], n = cnts[1];
-    const double S = sums[N_MOM];
-    const double E = f > 0 ? (S + (double)(f - n) * (double)C.r2) / (double)f : 0.0;
+    const long long f = cnts[0], n = cnts[1], w = Metric::PLANE ? cnts[2] : n;
+    const double S = sums[N_MOM], Q = Metric::PLANE ? sums[0] : S;
+    const double E = f > 0 ? (Q + (double)(f - w) * (double)C.r2) / (double)f : 0.0;
     if (g_trace)
         for (int i = 0; i < 12; ++i) g_trace[((size_t)p * (max_iter + 1) + k) * 12 + i] = g[i];
     if (stat_trace) {
-        double* st = stat_trace + ((size_t)p * (max_iter + 1) + k) * 3;
+        double* st = stat_trace + ((size_t)p * (max_iter + 1) + k) * N_STAT;
         st[0] = (double)f, st[1] = (double)n, st[2] = S;
+        if constexpr (Metric::PLANE) st[3] = (double)w, st[4] = Q;
     }
     int why = ICP_RUNNING;
-    float R[9];
-    double mx[3], ma[3];
-    if (n < min_matched) why = LS_ICP_STARVED;
+    float g_next[12];
+    for (int i = 0; i < 12; ++i) g_next[i] = g[i];
+    if (w < min_matched) why = LS_ICP_STARVED;
     else if (k >= 1 && e_prev[p] - E <= rel_thr * e_prev[p]) why = LS_ICP_CONVERGED;
     else if (k == max_iter) why = LS_ICP_MAX_ITER;
     else {
-        const double dn = (double)n;
-        double H[9];
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) H[r * 3 + c] = sums[6 + r * 3 + c] - (sums[r] * sums[3 + c]) / dn;
-        for (int r = 0; r < 3; ++r) mx[r] = sums[r] / dn, ma[r] = sums[3 + r] / dn;
-        if (kabsch_rotation(H, R) != LS_KABSCH_OK) why = LS_ICP_DEGENERATE;
+        bool ok;
+        if constexpr (Metric::PLANE) ok = plane_update(sums, g_next);
+        else ok = point_update(sums, n, g_next);
+        if (!ok) why = LS_ICP_DEGENERATE;
     }
     if (why != ICP_RUNNING) {
         stop[p] = why;
         iters[p] = k;
         for (int i = 0; i < 12; ++i) g_out[(size_t)p * 12 + i] = g[i];
+        if constexpr (Metric::PLANE) planar[p] = w, sum_rho2[p] = Q;
         return;
     }
-    for (int r = 0; r < 3; ++r) {
-        const double Rm = ((double)R[r * 3 + 0] * mx[0] + (double)R[r * 3 + 1] * mx[1]) + (double)R[r * 3 + 2] * mx[2];
-        for (int c = 0; c < 3; ++c) g[r * 4 + c] = R[r * 3 + c];
-        g[r * 4 + 3] = (float)(ma[r] - Rm);
-    }
+    for (int i = 0; i < 12; ++i) g[i] = g_next[i];
     e_prev[p] = E;
 }
 
@@ -466,13 +698,15 @@ struct Ws {
     int2* part_cnt;           // one per chunk of queries
     float* gk;                // the ICP: [P,12] the pose of the current iteration
     double* e_prev;           // the ICP: [P] the cost of the previous iteration
-    double* mom;              // the ICP: N_MOM per chunk of queries
+    double* mom;              // the ICP: the metric's N_MOM per chunk of queries
+    int* part_w;              // the plane ICP: one per chunk of queries
     size_t bytes;             // of the whole layout
 };
 
 // the layout depends on (P, a, b) alone (ws null: a sizing pass; n_offs = 0: a single problem); sum_p ceil(b_p / c) <= floor(b / c) + P.
-// The ICP's pieces follow the search's, so its workspace is the search's and then its own state and one moment record per chunk.
-Ws layout(void* ws, size_t n_offs, int P, long long a, long long b, bool icp = false) {
+// The ICP's pieces follow the search's, so its workspace is the search's and then its own state and one moment record per chunk (n_mom:
+// the metric's N_MOM; 0: no ICP); the plane metric's count of planar matches per chunk comes last, so the point ICP's layout is what it was.
+Ws layout(void* ws, size_t n_offs, int P, long long a, long long b, int n_mom = 0) {
     Arena ar(ws);
     Ws w;
     const size_t chunks = (size_t)(b / QUERY_CHUNK + P);
@@ -493,9 +727,10 @@ Ws layout(void* ws, size_t n_offs, int P, long long a, long long b, bool icp = f
     w.hit = ar.take<unsigned char>((size_t)a);
     w.part = ar.take<double>(chunks);
     w.part_cnt = ar.take<int2>(chunks);
-    w.gk = ar.take<float>(icp ? (size_t)P * 12 : 0);
-    w.e_prev = ar.take<double>(icp ? (size_t)P : 0);
-    w.mom = ar.take<double>(icp ? chunks * N_MOM : 0);
+    w.gk = ar.take<float>(n_mom ? (size_t)P * 12 : 0);
+    w.e_prev = ar.take<double>(n_mom ? (size_t)P : 0);
+    w.mom = ar.take<double>(chunks * (size_t)n_mom);
+    w.part_w = ar.take<int>(n_mom == PlaneMetric::N_MOM ? chunks : 0);
     w.bytes = ar.bytes();
     return w;
 }
@@ -541,11 +776,14 @@ struct IcpArgs {
     int* iters;
     float* g_trace;
     double* stat_trace;
+    const float* N = nullptr;          // the plane metric: the targets' normals, packed like A
+    long long* planar = nullptr;       // the plane metric: [P] the planar matches of the final search
+    double* sum_rho2 = nullptr;        // the plane metric: [P] their sum of rho^2
 };
 
 // the ICP's launch sequence: the grid once, then max_iter + 1 times (search, solve) -- the problems that have stopped exit at once -- then
 // the hit flags and the counts of the final searches.  2 max_iter + 5 kernels after the grid build, whatever P and whenever problems stop.
-template <class Near>
+template <class Metric, class Near>
 int icp_launch(const Near& L, int P, const float* A, long long a, long long chunks, const float* g0, const IcpArgs& I, const Ws& w, int* nn_idx,
                float* nn_d2, long long* counts, double* sum_d2, int* status_out, hipStream_t st) {
     const int rc = grid_launch(L, P, A, a, w, st);
@@ -553,10 +791,10 @@ int icp_launch(const Near& L, int P, const float* A, long long a, long long chun
     hipLaunchKernelGGL(icp_init_kernel, dim3(cdiv((long long)P * 12, 256)), dim3(256), 0, st, P, g0, w.gk, w.e_prev, I.stop, I.iters);
     for (int k = 0; k <= I.max_iter; ++k) {
         if (chunks > 0)
-            hipLaunchKernelGGL(icp_search_kernel<Near>, dim3((unsigned)chunks), dim3(QUERY_CHUNK), 0, st, L, I.stop, w.gk, w.slots, w.cnt, w.members,
-                               nn_idx, nn_d2, w.part, w.part_cnt, w.mom);
-        hipLaunchKernelGGL(icp_solve_kernel<Near>, dim3(P), dim3(kWave), 0, st, L, k, I.max_iter, I.rel_thr, I.min_matched, w.part, w.part_cnt, w.mom,
-                           w.gk, w.e_prev, I.stop, I.iters, I.g_out, I.g_trace, I.stat_trace);
+            hipLaunchKernelGGL((icp_search_kernel<Near, Metric>), dim3((unsigned)chunks), dim3(QUERY_CHUNK), 0, st, L, I.stop, w.gk, w.slots, w.cnt,
+                               w.members, I.N, nn_idx, nn_d2, w.part, w.part_cnt, w.part_w, w.mom);
+        hipLaunchKernelGGL((icp_solve_kernel<Near, Metric>), dim3(P), dim3(kWave), 0, st, L, k, I.max_iter, I.rel_thr, I.min_matched, w.part,
+                           w.part_cnt, w.part_w, w.mom, w.gk, w.e_prev, I.stop, I.iters, I.g_out, I.planar, I.sum_rho2, I.g_trace, I.stat_trace);
     }
     if (chunks > 0) hipLaunchKernelGGL(icp_mark_kernel<Near>, dim3((unsigned)chunks), dim3(QUERY_CHUNK), 0, st, L, nn_idx, w.hit);
     hipLaunchKernelGGL(final_kernel<Near>, dim3(P), dim3(256), 0, st, L, w.hit, w.part, w.part_cnt, w.status, counts, sum_d2, status_out);
@@ -570,6 +808,36 @@ int check_icp(const char* op, const IcpArgs& I) {
     LS_REQUIRE(std::isfinite(I.rel_thr) && I.rel_thr >= 0.0, "%s: rel_thr must be finite and >= 0, got %g", op, I.rel_thr);
     LS_REQUIRE(I.min_matched >= 3, "%s: min_matched must be >= 3 (a rotation needs three correspondences), got %d", op, I.min_matched);
     LS_REQUIRE(I.g_out && I.stop && I.iters, "%s: null g_out / stop / iters", op);
+    return LS_OK;
+}
+
+int check_plane(const char* op, long long a, const IcpArgs& I) {
+    LS_REQUIRE(a == 0 || I.N, "%s: null N with %lld kept rows", op, a);
+    LS_REQUIRE(I.planar && I.sum_rho2, "%s: null planar / sum_rho2", op);
+    return LS_OK;
+}
+
+int check_normals(const char* op, long long a, const float* A, int min_nbrs, const float* normals, const int* nbr_cnt, const float* variation,
+                  const long long* counts) {
+    LS_REQUIRE(a >= 0, "%s: negative size (%lld kept rows)", op, a);
+    LS_REQUIRE(a <= INT_MAX, "%s: %lld rows exceed %d (int row indices)", op, a, INT_MAX);
+    LS_REQUIRE(a == 0 || (A && normals && nbr_cnt && variation), "%s: null A / normals / nbr_cnt / variation with %lld rows", op, a);
+    LS_REQUIRE(counts, "%s: null counts", op);
+    LS_REQUIRE(min_nbrs >= 1, "%s: min_nbrs must be >= 1, got %d", op, min_nbrs);
+    return LS_OK;
+}
+
+// the normals' launch sequence: the grid, one thread per target, the counts -- 2 kernels after the grid build, whatever P
+template <class Near>
+int normals_launch(const Near& L, int P, const float* A, long long a, int min_nbrs, const Ws& w, float* normals, int* nbr_cnt, float* variation,
+                   long long* counts, int* status_out, hipStream_t st) {
+    const int rc = grid_launch(L, P, A, a, w, st);
+    if (rc != LS_OK) return rc;
+    if (a > 0)
+        hipLaunchKernelGGL(normals_kernel<Near>, dim3(cdiv(a, 256)), dim3(256), 0, st, L, A, a, w.tcell, w.slots, w.cnt, w.members, min_nbrs, normals,
+                           nbr_cnt, variation);
+    hipLaunchKernelGGL(normals_final_kernel<Near>, dim3(P), dim3(256), 0, st, L, normals, nbr_cnt, w.status, counts, status_out);
+    LS_LAUNCH_CHECK();
     return LS_OK;
 }
 
@@ -683,7 +951,7 @@ int ls_cloud_nearest_batch_f32(int P, const float* A, long long a_total, const l
 
 size_t ls_cloud_icp_workspace_bytes(long long a, long long b) {
     if (a < 0 || b < 0 || a + b > INT_MAX) return 0;
-    return layout(nullptr, 0, 1, a, b, true).bytes;
+    return layout(nullptr, 0, 1, a, b, PointMetric::N_MOM).bytes;
 }
 
 int ls_cloud_icp_f32(const float* A, long long a, const float* B, long long b, const float* g0, float radius, int max_iter, double rel_thr,
@@ -704,14 +972,14 @@ int ls_cloud_icp_f32(const float* A, long long a, const float* B, long long b, c
                   b);
         return LS_ERR_WORKSPACE;
     }
-    const Ws w = layout(workspace, 0, 1, a, b, true);
-    return icp_launch(OneNear{B, a, b, nullptr, inv, r2}, 1, A, a, chunks_of(b), g0, I, w, nn_idx, nn_d2, counts, sum_d2, status_out,
+    const Ws w = layout(workspace, 0, 1, a, b, PointMetric::N_MOM);
+    return icp_launch<PointMetric>(OneNear{B, a, b, nullptr, inv, r2}, 1, A, a, chunks_of(b), g0, I, w, nn_idx, nn_d2, counts, sum_d2, status_out,
                       (hipStream_t)stream);
 }
 
 size_t ls_cloud_icp_batch_workspace_bytes(int P, long long a_total, long long b_total) {
     if (P < 1 || a_total < 0 || b_total < 0 || a_total + b_total > INT_MAX) return 0;
-    return layout(nullptr, (size_t)OFF_ARRAYS * (P + 1), P, a_total, b_total, true).bytes;
+    return layout(nullptr, (size_t)OFF_ARRAYS * (P + 1), P, a_total, b_total, PointMetric::N_MOM).bytes;
 }
 
 int ls_cloud_icp_batch_f32(int P, const float* A, long long a_total, const long long* a_off, const float* B, long long b_total,
@@ -732,11 +1000,135 @@ int ls_cloud_icp_batch_f32(int P, const float* A, long long a_total, const long 
         return LS_ERR_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    const Ws w = layout(workspace, (size_t)OFF_ARRAYS * (P + 1), P, a_total, b_total, true);
+    const Ws w = layout(workspace, (size_t)OFF_ARRAYS * (P + 1), P, a_total, b_total, PointMetric::N_MOM);
     rc = upload_batch(w, P, a_off, b_off, h, st);
     if (rc != LS_OK) return rc;
-    return icp_launch(RaggedNear{B, nullptr, w.offs, w.inv, w.r2, P}, P, A, a_total, h.q_off[P], g0, I, w, nn_idx, nn_d2, counts, sum_d2, status_out,
+    return icp_launch<PointMetric>(RaggedNear{B, nullptr, w.offs, w.inv, w.r2, P}, P, A, a_total, h.q_off[P], g0, I, w, nn_idx, nn_d2, counts, sum_d2, status_out,
                       st);
+}
+
+size_t ls_cloud_icp_plane_workspace_bytes(long long a, long long b) {
+    if (a < 0 || b < 0 || a + b > INT_MAX) return 0;
+    return layout(nullptr, 0, 1, a, b, PlaneMetric::N_MOM).bytes;
+}
+
+int ls_cloud_icp_plane_f32(const float* A, const float* N, long long a, const float* B, long long b, const float* g0, float radius, int max_iter,
+                           double rel_thr, int min_matched, float* g_out, int32_t* stop, int32_t* iters, int32_t* nn_idx, float* nn_d2,
+                           long long* counts, double* sum_d2, long long* planar, double* sum_rho2, int* status_out, float* g_trace,
+                           double* stat_trace, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* op = "cloud_icp_plane";
+    const IcpArgs I{max_iter, rel_thr, min_matched, g_out, stop, iters, g_trace, stat_trace, N, planar, sum_rho2};
+    int rc = check_common(op, a, b, A, B, nn_idx, nn_d2, counts, sum_d2);
+    if (rc != LS_OK) return rc;
+    rc = check_plane(op, a, I);
+    if (rc != LS_OK) return rc;
+    float inv, r2;
+    rc = radius_terms(op, 0, radius, &inv, &r2);
+    if (rc != LS_OK) return rc;
+    rc = check_icp(op, I);
+    if (rc != LS_OK) return rc;
+    const size_t need = ls_cloud_icp_plane_workspace_bytes(a, b);
+    if (!workspace || workspace_bytes < need) {
+        set_error("%s: workspace %zu < required %zu (ls_cloud_icp_plane_workspace_bytes(%lld, %lld))", op, workspace ? workspace_bytes : (size_t)0,
+                  need, a, b);
+        return LS_ERR_WORKSPACE;
+    }
+    const Ws w = layout(workspace, 0, 1, a, b, PlaneMetric::N_MOM);
+    return icp_launch<PlaneMetric>(OneNear{B, a, b, nullptr, inv, r2}, 1, A, a, chunks_of(b), g0, I, w, nn_idx, nn_d2, counts, sum_d2, status_out,
+                                   (hipStream_t)stream);
+}
+
+size_t ls_cloud_icp_plane_batch_workspace_bytes(int P, long long a_total, long long b_total) {
+    if (P < 1 || a_total < 0 || b_total < 0 || a_total + b_total > INT_MAX) return 0;
+    return layout(nullptr, (size_t)OFF_ARRAYS * (P + 1), P, a_total, b_total, PlaneMetric::N_MOM).bytes;
+}
+
+int ls_cloud_icp_plane_batch_f32(int P, const float* A, const float* N, long long a_total, const long long* a_off, const float* B,
+                                 long long b_total, const long long* b_off, const float* g0, const float* radius, int max_iter, double rel_thr,
+                                 int min_matched, float* g_out, int32_t* stop, int32_t* iters, int32_t* nn_idx, float* nn_d2, long long* counts,
+                                 double* sum_d2, long long* planar, double* sum_rho2, int* status_out, float* g_trace, double* stat_trace,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    const char* op = "cloud_icp_plane_batch";
+    const IcpArgs I{max_iter, rel_thr, min_matched, g_out, stop, iters, g_trace, stat_trace, N, planar, sum_rho2};
+    BatchHost h;
+    int rc = check_batch(op, P, A, a_total, a_off, B, b_total, b_off, radius, nn_idx, nn_d2, counts, sum_d2, &h);
+    if (rc != LS_OK) return rc;
+    rc = check_plane(op, a_total, I);
+    if (rc != LS_OK) return rc;
+    rc = check_icp(op, I);
+    if (rc != LS_OK) return rc;
+    const size_t need = ls_cloud_icp_plane_batch_workspace_bytes(P, a_total, b_total);
+    if (!workspace || workspace_bytes < need) {
+        set_error("%s: workspace %zu < required %zu (ls_cloud_icp_plane_batch_workspace_bytes(%d, %lld, %lld))", op,
+                  workspace ? workspace_bytes : (size_t)0, need, P, a_total, b_total);
+        return LS_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const Ws w = layout(workspace, (size_t)OFF_ARRAYS * (P + 1), P, a_total, b_total, PlaneMetric::N_MOM);
+    rc = upload_batch(w, P, a_off, b_off, h, st);
+    if (rc != LS_OK) return rc;
+    return icp_launch<PlaneMetric>(RaggedNear{B, nullptr, w.offs, w.inv, w.r2, P}, P, A, a_total, h.q_off[P], g0, I, w, nn_idx, nn_d2, counts,
+                                   sum_d2, status_out, st);
+}
+
+size_t ls_cloud_normals_workspace_bytes(long long a) {
+    if (a < 0 || a > INT_MAX) return 0;
+    return layout(nullptr, 0, 1, a, 0).bytes;
+}
+
+int ls_cloud_normals_f32(const float* A, long long a, float radius, int min_nbrs, float* normals, int32_t* nbr_cnt, float* variation,
+                         long long* counts, int* status_out, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* op = "cloud_normals";
+    int rc = check_normals(op, a, A, min_nbrs, normals, nbr_cnt, variation, counts);
+    if (rc != LS_OK) return rc;
+    float inv, r2;
+    rc = radius_terms(op, 0, radius, &inv, &r2);
+    if (rc != LS_OK) return rc;
+    const size_t need = ls_cloud_normals_workspace_bytes(a);
+    if (!workspace || workspace_bytes < need) {
+        set_error("%s: workspace %zu < required %zu (ls_cloud_normals_workspace_bytes(%lld))", op, workspace ? workspace_bytes : (size_t)0, need, a);
+        return LS_ERR_WORKSPACE;
+    }
+    const Ws w = layout(workspace, 0, 1, a, 0);
+    return normals_launch(OneNear{nullptr, a, 0, nullptr, inv, r2}, 1, A, a, min_nbrs, w, normals, nbr_cnt, variation, counts, status_out,
+                          (hipStream_t)stream);
+}
+
+size_t ls_cloud_normals_batch_workspace_bytes(int P, long long a_total) {
+    if (P < 1 || a_total < 0 || a_total > INT_MAX) return 0;
+    return layout(nullptr, (size_t)OFF_ARRAYS * (P + 1), P, a_total, 0).bytes;
+}
+
+int ls_cloud_normals_batch_f32(int P, const float* A, long long a_total, const long long* a_off, const float* radius, int min_nbrs,
+                               float* normals, int32_t* nbr_cnt, float* variation, long long* counts, int* status_out, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    const char* op = "cloud_normals_batch";
+    LS_REQUIRE(P >= 1, "%s: P must be at least 1, got %d", op, P);
+    int rc = check_normals(op, a_total, A, min_nbrs, normals, nbr_cnt, variation, counts);
+    if (rc != LS_OK) return rc;
+    rc = check_ranges(op, "problem", "a_off", P, a_off, a_total, INT_MAX);
+    if (rc != LS_OK) return rc;
+    LS_REQUIRE(radius, "%s: null radius", op);
+    BatchHost h;                                                         // no queries: every problem has no rows of B and no chunks
+    h.q_off.assign(P + 1, 0);
+    h.inv.resize(P);
+    h.r2.resize(P);
+    for (int p = 0; p < P; ++p) {
+        rc = radius_terms(op, p, radius[p], &h.inv[p], &h.r2[p]);
+        if (rc != LS_OK) return rc;
+    }
+    const size_t need = ls_cloud_normals_batch_workspace_bytes(P, a_total);
+    if (!workspace || workspace_bytes < need) {
+        set_error("%s: workspace %zu < required %zu (ls_cloud_normals_batch_workspace_bytes(%d, %lld))", op,
+                  workspace ? workspace_bytes : (size_t)0, need, P, a_total);
+        return LS_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const Ws w = layout(workspace, (size_t)OFF_ARRAYS * (P + 1), P, a_total, 0);
+    rc = upload_batch(w, P, a_off, h.q_off.data(), h, st);
+    if (rc != LS_OK) return rc;
+    return normals_launch(RaggedNear{nullptr, nullptr, w.offs, w.inv, w.r2, P}, P, A, a_total, min_nbrs, w, normals, nbr_cnt, variation, counts,
+                          status_out, st);
 }
 
 }  // extern "C"

@@ -90,5 +90,38 @@ __device__ __forceinline__ int kabsch_rotation(const double H[9], float R[9]) {
     return 0;
 }
 
+// Eigen-decomposition of the symmetric 3x3 matrix C = (xx, xy, xz, yy, yz, zz) by cyclic Jacobi in fp64 in registers: V^T C V = diag(lam),
+// the columns of V orthonormal; lam is NOT sorted.  A zero off-diagonal entry is never rotated, so an exactly zero row and column (an
+// axis-aligned plane) keeps its eigenvalue 0 and its axis exactly.  The sweeps end when the off-diagonal entries are below 2^-70 of the
+// diagonal's magnitude, at most 12 of them (the convergence is quadratic: 5 suffice in practice).
+__device__ __forceinline__ void sym_eig3(const double C[6], double lam[3], double V[3][3]) {
+    double A[3][3] = {{C[0], C[1], C[2]}, {C[1], C[3], C[4]}, {C[2], C[4], C[5]}};
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) V[i][j] = (i == j) ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 12; ++sweep) {
+        const double off = fabs(A[0][1]) + fabs(A[0][2]) + fabs(A[1][2]), dia = fabs(A[0][0]) + fabs(A[1][1]) + fabs(A[2][2]);
+        if (!(off > 0x1p-70 * dia)) break;
+        for (int p = 0; p < 2; ++p)
+            for (int q = p + 1; q < 3; ++q) {
+                const double apq = A[p][q];
+                if (apq == 0.0) continue;
+                const double zeta = (A[q][q] - A[p][p]) / (2.0 * apq);
+                const double tt = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                const double c = 1.0 / sqrt(1.0 + tt * tt), s = c * tt;
+                for (int i = 0; i < 3; ++i) {                            // A <- A J, V <- V J
+                    const double ap = A[i][p], aq = A[i][q];
+                    A[i][p] = c * ap - s * aq; A[i][q] = s * ap + c * aq;
+                    const double vp = V[i][p], vq = V[i][q];
+                    V[i][p] = c * vp - s * vq; V[i][q] = s * vp + c * vq;
+                }
+                for (int i = 0; i < 3; ++i) {                            // A <- J^T A
+                    const double ap = A[p][i], aq = A[q][i];
+                    A[p][i] = c * ap - s * aq; A[q][i] = s * ap + c * aq;
+                }
+                A[p][q] = A[q][p] = 0.0;                                 // what the rotation was chosen for
+            }
+    }
+    for (int i = 0; i < 3; ++i) lam[i] = A[i][i];
+}
 
 }  // namespace ls

@@ -332,7 +332,18 @@ class More_Solver:
             out["nn_idx"].append(idx)
         return out
 
-    def _refine_on_memory_batch(self, mem_pcs, new_pcs, T, radius, **kw):
+    def _memory_normals_batch(self, mem_pcs, radius=None, min_nbrs=5):
+        """Scene memory, a normal per kept point (an extension beyond the released reference, like _accumulate_batch): ONE ragged call
+        (ops.cloud_normals_batch, csrc/cloudnear.hip) over the P kept clouds mem_pcs[p] [a_p,3].  radius: default 3 * the voxel of
+        _accumulate_batch (cfg['accumulate']['voxel_size'], else 0.01) -- A DERIVED DEFAULT, not a tuned one: at one point per voxel of
+        edge h on a surface, a ball of radius 3 h holds about 9 pi = 28 points.  min_nbrs = 5 is NOT TUNED; the rank rule of the operator
+        does the real work.  -> list of P (normals [a_p,3], nbr_cnt [a_p] int32, variation [a_p], counts host int64 [2]) as
+        ops.cloud_normals_batch returns them: a row without a normal is (0, 0, 0)."""
+        if radius is None:
+            radius = 3 * self.cfg.get("accumulate", {}).get("voxel_size", 0.01)
+        return ops.cloud_normals_batch([p.detach() for p in mem_pcs], radius=radius, min_nbrs=min_nbrs)
+
+    def _refine_on_memory_batch(self, mem_pcs, new_pcs, T, radius, metric="point", normal_radius=None, **kw):
         """Scene memory, the pose the merge and the overlap gate trust (an extension beyond the released reference, like both): refine P
         registrations on the memory itself, at full resolution, in ONE ragged call (ops.cloud_icp_batch, csrc/cloudnear.hip) -- trimmed
         ICP of the observation new_pcs[p] [b_p,3] onto the kept cloud mem_pcs[p] [a_p,3], only correspondences within `radius` counting,
@@ -343,14 +354,26 @@ class More_Solver:
         -> (T' [P,4,4] = inverse(g_out); a problem that made no update -- iters 0 -- keeps the caller's T bit for bit,
             dict: g [P,3,4] (g_out, rescan -> memory: what _accumulate_batch / _overlap_batch take as g=), stop, iters (host int32 [P])
             and the entries of _overlap_batch (overlap, rmse, memory_seen, counts, nn_idx) formed from the final search of the
-            refinement, which is the search _overlap_batch(g=g_out, radius=radius) would make)."""
+            refinement, which is the search _overlap_batch(g=g_out, radius=radius) would make).
+        metric "plane": the point-to-plane metric instead -- ONE _memory_normals_batch(mem_pcs, normal_radius) call, then ONE
+        ops.cloud_icp_plane_batch call with the same arguments (its min_matched defaults to 6 and counts planar matches); the dict gains
+        planar (host int64 [P]).  The normals are recomputed at every call and each of the two operators builds its own grid over the
+        memory: accepted, not optimised.  There is no fallback to the point metric: a starved or degenerate problem keeps the caller's T,
+        as any problem with iters 0 does, and stop says why."""
+        if metric not in ("point", "plane"):
+            raise ValueError(f"metric must be 'point' or 'plane', got {metric!r}")
         P = len(mem_pcs)
         if len(new_pcs) != P:
             raise ValueError(f"{P} memory clouds for {len(new_pcs)} observations")
         if T is None or T.dim() != 3 or T.shape[0] != P or T.shape[1] not in (3, 4) or T.shape[2] != 4:
             raise ValueError(f"T must be [P,4,4] or [P,3,4] with P = {P}, got {None if T is None else tuple(T.shape)}")
-        res = ops.cloud_icp_batch([p.detach() for p in mem_pcs], [p.detach() for p in new_pcs], g=self._memory_pose(T, None, P), radius=radius,
-                                  packed=True, **kw)
+        if metric == "plane":
+            normals = [nrm for nrm, _, _, _ in self._memory_normals_batch(mem_pcs, radius=normal_radius)]
+            res = ops.cloud_icp_plane_batch([p.detach() for p in mem_pcs], normals, [p.detach() for p in new_pcs], g=self._memory_pose(T, None, P),
+                                            radius=radius, packed=True, **kw)
+        else:
+            res = ops.cloud_icp_batch([p.detach() for p in mem_pcs], [p.detach() for p in new_pcs], g=self._memory_pose(T, None, P), radius=radius,
+                                      packed=True, **kw)
         last_row = T.new_tensor([0.0, 0.0, 0.0, 1.0]).expand(P, 1, 4)
         T4 = T.detach() if T.shape[1] == 4 else torch.cat([T.detach(), last_row], 1)
         moved = torch.tensor((res["iters"] > 0).tolist(), device=T.device)
@@ -359,6 +382,8 @@ class More_Solver:
         searches = [(i, d, res["counts"][p], float(res["sum_d2"][p]))
                     for p, (i, d) in enumerate(zip(torch.split(res["idx"], sizes), torch.split(res["d2"], sizes)))]
         info = {"g": res["g"], "stop": res["stop"], "iters": res["iters"]}
+        if metric == "plane":
+            info["planar"] = res["planar"]
         info.update(self._overlap_figures(mem_pcs, searches))
         return T_new, info
 
@@ -573,7 +598,7 @@ def _encode_clouds(model, clouds):
 
 
 def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, optimize_codes=False, overlap_radius=None, min_overlap=None,
-                   refine_radius=None):
+                   refine_radius=None, refine_metric="point", normal_radius=None):
     """A reference scan followed by SEVERAL rescans, with a memory that carries every instance's points from one rescan to the next -- an
     extension beyond the released reference (more_solver.py:246-299 solves one (reference, rescan) pair and drops the rescan's points).
     ref and every rescan: {'pc' [n,3,Nmax], 'pc_mask'} as _solve_end2end takes them.
@@ -610,7 +635,14 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
     inverse).  With the overlap gate on as well, its figures are the refinement's own final search when overlap_radius equals
     refine_radius -- no second search -- and otherwise come from one _overlap_batch(g=g_out) call.  refine_radius HAS NO DEFAULT AND
     NONE IS RECOMMENDED, like min_overlap: it must exceed the error of the initial registration, and no trained checkpoint exists here to
-    measure that."""
+    measure that.  refine_metric "plane" (with refine_radius; without it a ValueError) refines with the point-to-plane metric:
+    More_Solver._refine_on_memory_batch(metric="plane", normal_radius=normal_radius), the normals of the memory recomputed at every step.
+    There is NO FALLBACK to the point metric: a pair whose refinement starves or is degenerate keeps the registration it came with, as
+    any pair with refine_iters 0 does, and refine_stop reports it.  "point" is the path above, untouched."""
+    if refine_metric not in ("point", "plane"):
+        raise ValueError(f"solve_sequence: refine_metric must be 'point' or 'plane', got {refine_metric!r}")
+    if refine_metric == "plane" and refine_radius is None:
+        raise ValueError("solve_sequence: refine_metric 'plane' needs refine_radius: without it there is no refinement to choose a metric for")
     gate = overlap_radius is not None or min_overlap is not None
     model = solver.model
     n_in = solver.cfg["shape_priors"]["n_input_point"]
@@ -641,7 +673,10 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
             refined = None
             if refine_radius is not None:
                 T_init = T
-                T, refined = solver._refine_on_memory_batch(src, tgt, T_init, refine_radius)
+                if refine_metric == "plane":
+                    T, refined = solver._refine_on_memory_batch(src, tgt, T_init, refine_radius, metric="plane", normal_radius=normal_radius)
+                else:
+                    T, refined = solver._refine_on_memory_batch(src, tgt, T_init, refine_radius)
                 for k, (i, _) in enumerate(pairs):
                     out["refine_stop"][i], out["refine_iters"][i] = int(refined["stop"][k]), int(refined["iters"][k])
                     out["registration_init"][i] = T_init[k:k + 1]

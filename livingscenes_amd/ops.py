@@ -1050,3 +1050,160 @@ def cloud_icp(A, B, g=None, *, radius, max_iter=100, rel_thr=1e-6, min_matched=3
     if trace:
         out.update(g_trace=g_trace[0], stat_trace=stat_trace[0])
     return out
+
+
+# ------------------------------------------------------------------------------------------------ scene memory: normals and the point-to-plane ICP
+def _normals_out(P, a, dev):
+    """the outputs of a normals call and `meta` -- counts [P,2] int64, then status [P] int32 -- with the pointer to the status"""
+    normals = torch.empty(a, 3, dtype=torch.float32, device=dev)
+    cnt = torch.empty(a, dtype=torch.int32, device=dev)
+    var = torch.empty(a, dtype=torch.float32, device=dev)
+    meta = torch.empty(2 * P + (P + 1) // 2, dtype=torch.int64, device=dev)
+    return normals, cnt, var, meta, ctypes.c_void_p(meta.data_ptr() + 16 * P)
+
+
+def _normals_meta(meta, P, op):
+    host = meta.cpu().numpy()
+    st = host[2 * P:].view(np.int32)[:P]
+    if st.any():
+        raise _lib.LsError(f"{op}: problem {int(np.flatnonzero(st)[0])}: status {int(st[np.flatnonzero(st)[0]])} (the cell table overflowed: a defect)")
+    return host[:2 * P].reshape(P, 2).copy()
+
+
+def cloud_normals_batch(As, *, radius, min_nbrs=5, packed=False):
+    """ls_cloud_normals_batch_f32 (an extension beyond the released reference, like cloud_merge, cloud_nearest and cloud_icp): a normal per
+    row of the P kept clouds As[p] [a_p,3] (fp32 HIP tensors, empty ones allowed) from the rows within `radius` of it (one radius or P
+    radii) on cloud_nearest's grid: integer moments of the neighbours' offsets, the covariance and its eigenvalues in float64
+    (include/livingscenes_hip.h has the definition to the bit).  A row is valid iff it has at least min_nbrs neighbours (itself included)
+    and they are neither coincident nor collinear; min_nbrs = 5 IS NOT TUNED -- the rank rule does the real work.
+    -> list of P (normals [a_p,3] fp32: unit, the component of largest magnitude positive, (0, 0, 0) for an invalid row; nbr_cnt [a_p]
+    int32; variation [a_p] fp32 = lmin / (lmin + lmid + lmax); counts: host int64 [2] = rows with a cell, valid rows), views of packed
+    tensors; packed=True: (normals, nbr_cnt, variation, counts [P,2], a_off).  One call, one host read, whatever P."""
+    op = "cloud_normals"
+    As = [_near_cloud(x, "A", op) for x in As]
+    P = len(As)
+    if P == 0:
+        raise ValueError(f"{op}: no problem given")
+    dev = As[0].device
+    rad = np.full(P, float(radius), dtype=np.float32) if np.ndim(radius) == 0 else np.ascontiguousarray(radius, dtype=np.float32).reshape(-1)
+    if rad.shape[0] != P:
+        raise ValueError(f"{op}: {rad.shape[0]} radii for {P} problems")
+    A = torch.cat(As, 0) if P > 1 else As[0]
+    ao = _offsets([x.shape[0] for x in As])
+    normals, cnt, var, meta, status = _normals_out(P, A.shape[0], dev)
+    ws = _scratch(load().ls_cloud_normals_batch_workspace_bytes(P, A.shape[0]), dev)
+    call(dev, "ls_cloud_normals_batch_f32", P, ptr(A), A.shape[0], _hptr(ao), _hptr(rad), int(min_nbrs), ptr(normals), ptr(cnt), ptr(var), ptr(meta),
+         status, ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev))
+    counts = _normals_meta(meta, P, op)
+    if packed:
+        return normals, cnt, var, counts, ao
+    sizes = np.diff(ao).tolist()
+    return [(n, c, v, counts[p]) for p, (n, c, v) in enumerate(zip(torch.split(normals, sizes), torch.split(cnt, sizes), torch.split(var, sizes)))]
+
+
+def cloud_normals(A, *, radius, min_nbrs=5):
+    """ls_cloud_normals_f32: the kept cloud A [a,3] (fp32 HIP tensor) -> (normals [a,3] fp32, nbr_cnt [a] int32, variation [a] fp32, counts
+    host int64 [2]) as cloud_normals_batch describes them (min_nbrs = 5 is not tuned).  Bit-identical to the same problem inside any
+    cloud_normals_batch."""
+    op = "cloud_normals"
+    A = _near_cloud(A, "A", op)
+    dev = A.device
+    normals, cnt, var, meta, status = _normals_out(1, A.shape[0], dev)
+    ws = _scratch(load().ls_cloud_normals_workspace_bytes(A.shape[0]), dev)
+    call(dev, "ls_cloud_normals_f32", ptr(A), A.shape[0], float(radius), int(min_nbrs), ptr(normals), ptr(cnt), ptr(var), ptr(meta), status, ptr(ws),
+         0 if ws is None else ws.numel(), stream_ptr(dev))
+    return normals, cnt, var, _normals_meta(meta, 1, op)[0]
+
+
+def _plane_normals(x, A, op):
+    x = _near_cloud(x, "N", op)
+    if x.shape[0] != A.shape[0] or x.device != A.device:
+        raise ValueError(f"{op}: N is {tuple(x.shape)} on {x.device} for A {tuple(A.shape)} on {A.device}: one normal row per kept row")
+    return x
+
+
+def _plane_buffers(P, b, dev, max_iter, trace):
+    """_icp_buffers for the plane metric: `meta` also holds planar [P] int64 and sum_rho2 [P] float64 before the int32 words, and the
+    statistics trace has five columns"""
+    idx = torch.empty(b, dtype=torch.int32, device=dev)
+    d2 = torch.empty(b, dtype=torch.float32, device=dev)
+    g_out = torch.empty(P, 3, 4, dtype=torch.float32, device=dev)
+    meta = torch.empty(6 * P + (3 * P + 1) // 2, dtype=torch.int64, device=dev)
+    # counts, sum_d2, planar, sum_rho2, status, stop, iters
+    at = [ctypes.c_void_p(meta.data_ptr() + o) for o in (0, 24 * P, 32 * P, 40 * P, 48 * P, 52 * P, 56 * P)]
+    g_trace = torch.zeros(P, max_iter + 1, 12, dtype=torch.float32, device=dev) if trace else None
+    stat_trace = torch.zeros(P, max_iter + 1, 5, dtype=torch.float64, device=dev) if trace else None
+    return idx, d2, g_out, meta, at, g_trace, stat_trace
+
+
+def _plane_meta(meta, P, op):
+    """the one host read: counts [P,3], sum_d2 [P], planar [P], sum_rho2 [P], stop [P], iters [P]"""
+    host = meta.cpu().numpy()
+    tail = host[6 * P:].view(np.int32)
+    st = tail[:P]
+    if st.any():
+        raise _lib.LsError(f"{op}: problem {int(np.flatnonzero(st)[0])}: status {int(st[np.flatnonzero(st)[0]])} (the cell table overflowed: a defect)")
+    return (host[:3 * P].reshape(P, 3).copy(), host[3 * P:4 * P].view(np.float64).copy(), host[4 * P:5 * P].copy(),
+            host[5 * P:6 * P].view(np.float64).copy(), tail[P:2 * P].copy(), tail[2 * P:3 * P].copy())
+
+
+def cloud_icp_plane_batch(As, Ns, Bs, g=None, *, radius, max_iter=100, rel_thr=1e-6, min_matched=6, trace=False, packed=False):
+    """ls_cloud_icp_plane_batch_f32 (an extension beyond the released reference, like cloud_icp): the trimmed ICP of cloud_icp_batch with
+    the point-to-plane metric.  Ns[p] [a_p,3] are the normals of the kept rows As[p] (cloud_normals makes them; a zero row means "no
+    normal"); the other arguments are cloud_icp_batch's.  Per iteration: cloud_nearest under the current pose; a match is planar iff its
+    neighbour has a normal; E = (sum rho^2 + (finite - planar) r^2) / finite with rho the distance to the neighbour's tangent plane; the
+    stop tests of cloud_icp on the PLANAR count (min_matched = 6: six unknowns); else the 6 x 6 normal equations of the linearised step in
+    float64, Cholesky (a failed pivot: degenerate -- one plane, or all normals parallel), exp of the twist, the rotation re-orthonormalised.
+    The linearised step is not guaranteed to lower E: there is no line search and no damping, and a step that raises E ends the loop as
+    converged with the pose it produced.  max_iter and rel_thr are cloud_icp's defaults: inherited, not tuned.
+    -> list of P dicts as cloud_icp_batch returns them plus planar (int) and sum_rho2 (float) of the final search; trace=True adds g_trace
+    [max_iter+1,12] and stat_trace [max_iter+1,5] = (finite, matched, sum d2, planar, sum rho^2).  packed=True: one dict of packed tensors."""
+    op = "cloud_icp_plane"
+    P, dev, A, B, ao, bo, rad, g = _near_batch_args(op, As, Bs, g, radius)
+    if len(Ns) != P:
+        raise ValueError(f"{op}: {P} kept clouds for {len(Ns)} arrays of normals")
+    Ns = [_plane_normals(n, a, op) for n, a in zip(Ns, As)]
+    N = torch.cat(Ns, 0) if P > 1 else Ns[0]
+    max_iter = int(max_iter)
+    idx, d2, g_out, meta, at, g_trace, stat_trace = _plane_buffers(P, B.shape[0], dev, max(max_iter, 0), trace)
+    ws = _scratch(load().ls_cloud_icp_plane_batch_workspace_bytes(P, A.shape[0], B.shape[0]), dev)
+    call(dev, "ls_cloud_icp_plane_batch_f32", P, ptr(A), ptr(N), A.shape[0], _hptr(ao), ptr(B), B.shape[0], _hptr(bo), ptr(g), _hptr(rad), max_iter,
+         float(rel_thr), int(min_matched), ptr(g_out), at[5], at[6], ptr(idx), ptr(d2), at[0], at[1], at[2], at[3], at[4], ptr(g_trace),
+         ptr(stat_trace), ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev))
+    counts, sums, planar, rho2, stop, iters = _plane_meta(meta, P, op)
+    if packed:
+        out = {"g": g_out, "stop": stop, "iters": iters, "idx": idx, "d2": d2, "counts": counts, "sum_d2": sums, "planar": planar,
+               "sum_rho2": rho2, "b_off": bo}
+        if trace:
+            out.update(g_trace=g_trace, stat_trace=stat_trace)
+        return out
+    sizes = np.diff(bo).tolist()
+    res = []
+    for p, (i, d) in enumerate(zip(torch.split(idx, sizes), torch.split(d2, sizes))):
+        res.append({"g": g_out[p], "stop": int(stop[p]), "iters": int(iters[p]), "idx": i, "d2": d, "counts": counts[p], "sum_d2": float(sums[p]),
+                    "planar": int(planar[p]), "sum_rho2": float(rho2[p])})
+        if trace:
+            res[-1].update(g_trace=g_trace[p], stat_trace=stat_trace[p])
+    return res
+
+
+def cloud_icp_plane(A, N, B, g=None, *, radius, max_iter=100, rel_thr=1e-6, min_matched=6, trace=False):
+    """ls_cloud_icp_plane_f32: the point-to-plane trimmed ICP of the observation B [b,3] onto the kept cloud A [a,3] with the normals N [a,3]
+    (fp32 HIP tensors), g [3,4] or [4,4] the initial pose (None: identity) -> the dict cloud_icp_plane_batch describes.  Bit-identical to
+    the same problem inside any cloud_icp_plane_batch."""
+    op = "cloud_icp_plane"
+    A, B, g = _near_one_args(op, A, B, g)
+    N = _plane_normals(N, A, op)
+    dev = A.device
+    max_iter = int(max_iter)
+    idx, d2, g_out, meta, at, g_trace, stat_trace = _plane_buffers(1, B.shape[0], dev, max(max_iter, 0), trace)
+    ws = _scratch(load().ls_cloud_icp_plane_workspace_bytes(A.shape[0], B.shape[0]), dev)
+    call(dev, "ls_cloud_icp_plane_f32", ptr(A), ptr(N), A.shape[0], ptr(B), B.shape[0], ptr(g), float(radius), max_iter, float(rel_thr),
+         int(min_matched), ptr(g_out), at[5], at[6], ptr(idx), ptr(d2), at[0], at[1], at[2], at[3], at[4], ptr(g_trace), ptr(stat_trace), ptr(ws),
+         0 if ws is None else ws.numel(), stream_ptr(dev))
+    counts, sums, planar, rho2, stop, iters = _plane_meta(meta, 1, op)
+    out = {"g": g_out[0], "stop": int(stop[0]), "iters": int(iters[0]), "idx": idx, "d2": d2, "counts": counts[0], "sum_d2": float(sums[0]),
+           "planar": int(planar[0]), "sum_rho2": float(rho2[0])}
+    if trace:
+        out.update(g_trace=g_trace[0], stat_trace=stat_trace[0])
+    return out
