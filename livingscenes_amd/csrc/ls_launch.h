@@ -82,6 +82,7 @@ int transpose_cloud_launch(const float* x, int B, int N, float* pts, hipStream_t
 int mean_points_launch(const float* f, int B, int N, int C, float* out, hipStream_t st);
 int glob_mean_gemv_launch(const float* f, int B, int N, int C, const float* W, int col0, int ncols, float* G, int ldg, hipStream_t st, int npoints = 0);
 int vn_act_rows_launch(const float* T, int ldt, const float* G, int ldg, int B, int N, int C, float neg_slope, float* out, hipStream_t st);
+int tail_check(int Cd);   // what tail_launch serves (its own first line): asked before anything that feeds it is enqueued
 int tail_launch(const float* Tc, int ldc, int B, int NP, int Cd, const float* inv_t, const float* fc0_t, const float* misc, float neg_slope, float scale_factor,
                 int center_pred, int center_scale, const float* centroid, const float* scale0, float* z_so3, float* z_inv, float* s_out, float* t_out,
                 hipStream_t st);

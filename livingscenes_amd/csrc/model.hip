@@ -363,7 +363,8 @@ static int encoder_tail(ls_model* m, const float* cur, int B, int NP, float* Tc,
     const ls_model_desc& d = m->d;
     const int Cl = d.feat_dim[d.num_layers - 1], Cdp = pad4(d.c_dim + 1);
     const float* W = m->blob;
-    int rc;
+    int rc = tail_check(d.c_dim);   // a refusal of tail_launch must not leave conv_c enqueued behind it
+    if (rc != LS_OK) return rc;
     { PROF(LS_K_GEMM_TAIL, 0, st);
       Gemm g;
       g.A = cur; g.lda = Cl; g.W = W + d.off_convc; g.ldw = Cl; g.out = Tc; g.ldc = Cdp; g.M = B * NP * 3; g.N = Cdp; g.K = Cl; g.scratch = gws;

@@ -544,10 +544,14 @@ int vn_act_rows_launch(const float* T, int ldt, const float* G, int ldg, int B, 
     LS_LAUNCH_CHECK();
     return LS_OK;
 }
+int tail_check(int Cd) {
+    LS_REQUIRE(Cd > 0 && Cd <= 1024 && Cd % 2 == 0, "tail: c_dim=%d unsupported (even, <= 1024)", Cd);
+    return LS_OK;
+}
 int tail_launch(const float* Tc, int ldc, int B, int NP, int Cd, const float* inv_t, const float* fc0_t, const float* misc,
                 float neg_slope, float scale_factor, int center_pred, int center_scale, const float* centroid,
                 const float* scale0, float* z_so3, float* z_inv, float* s_out, float* t_out, hipStream_t st) {
-    LS_REQUIRE(Cd <= 1024 && Cd % 2 == 0, "tail: c_dim=%d unsupported (even, <= 1024)", Cd);
+    if (const int rc = tail_check(Cd)) return rc;
     TailW w{inv_t, fc0_t, misc};
     const size_t smem = (size_t)(3 * Cd + 3 * NP + 3 * (Cd / 2) + 15 * Cd) * sizeof(float);   // X | kdir | H | gemv partials + result
     if (smem > 64 * 1024) LS_HIP_CHECK(hipFuncSetAttribute((const void*)tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));   // c_dim > ~800
