@@ -1,18 +1,13 @@
 // cloudmerge.hip -- scene memory: the cloud an instance keeps (A) and a registered new observation of it (B) merged on a voxel grid, first
-// point of a cell wins.  The definition is in include/livingscenes_hip.h (ls_cloud_merge_f32) and, as NumPy, in tests/merge_oracle.py; this
-// file follows it to the letter:
-//   candidates  the rows of A as given, then the rows of B under the pose g (R | t): y_a = ((R_a0 x_0 + R_a1 x_1) + R_a2 x_2) + t_a in fp32,
-//               every product and sum rounded (no contraction in this file); g == NULL: the rows of B bit for bit
-//   cell        c_a = (int)clamp(floorf(y_a inv), -2^30, 2^30), inv = 1.0f / h formed once on the host; a candidate with a non-finite
-//               coordinate has no cell and is never kept
+// point of a cell wins.  The definition is in include/livingscenes_hip.h (ls_cloud_merge_f32) and, as NumPy, in tests/merge_oracle.py; the
+// pose, the cell, the table and its claim walk are those of cloud_grid.h.  What this file adds:
+//   candidates  the rows of A as given, then the rows of B under the pose g
 //   keep        candidate i is kept iff no candidate j < i of its problem has the same cell triple
 //   output      the kept candidates of every problem back to back in ascending candidate order: point, candidate index, offsets
-// Method: an open-addressing table of 2 n_p slots per problem holds candidate indices.  A thread claims an empty slot with an integer CAS; on
-// an occupied slot it compares the occupant's cell (written by the kernel before) with its own and either lowers the slot to its index
-// (atomicMin) or probes on, at most over the whole table.  Which candidate claimed a slot depends on the race, the minimum it ends with does
-// not, and a slot never changes its cell -- so all candidates of a cell meet in one slot.  Then flag, scan (ls_scan.h), scatter.  Integer
-// atomics only: a problem's output is the same bits alone, in any batch and in any run.  Every kernel is written once, for a problem locator
-// (OneCloud / RaggedClouds, as the meshes of meshcluster.hip); the number of launches does not depend on P.
+// Method: a table of 2 n_p slots per problem holds candidate indices.  After the claim walk a thread lowers its cell's slot to its own
+// index (atomicMin): which candidate claimed a slot depends on the race, the minimum it ends with does not.  Then flag, scan (ls_scan.h),
+// scatter.  Integer atomics only: a problem's output is the same bits alone, in any batch and in any run.  Every kernel is written once,
+// for a problem locator (OneCloud / RaggedClouds, as the meshes of meshcluster.hip); the number of launches does not depend on P.
 #include <climits>
 #include <cmath>
 #include <vector>
@@ -23,13 +18,11 @@
 
 // the arithmetic of the definition as written: no contraction of a * b + c into an fma anywhere in this file
 #pragma clang fp contract(off)
+#include "cloud_grid.h"
 
 namespace ls {
 namespace cmg {
-
-constexpr int NO_CELL = INT_MIN;              // cell[i][0] of a candidate without a cell (cells are clamped to [-2^30, 2^30])
-constexpr unsigned NO_SLOT = 0xFFFFFFFFu;     // slot_of[i]: the candidate is in no slot (no cell, or the table overflowed)
-constexpr float CELL_MAX = 1073741824.0f;     // 2^30
+using namespace cloud;
 
 // ------------------------------------------------------------------------------------------------ which problem: one, or one of a ragged batch
 struct CloudRef {
@@ -84,12 +77,7 @@ __device__ __forceinline__ void candidate(const CloudRef& C, long long i, float 
         return;
     }
     const float* __restrict__ x = C.B + (i - C.a) * 3;
-    const float x0 = x[0], x1 = x[1], x2 = x[2];
-    if (!C.g) {
-        y[0] = x0; y[1] = x1; y[2] = x2;
-        return;
-    }
-    for (int r = 0; r < 3; ++r) y[r] = ((C.g[r * 4 + 0] * x0 + C.g[r * 4 + 1] * x1) + C.g[r * 4 + 2] * x2) + C.g[r * 4 + 3];
+    pose_row(C.g, x[0], x[1], x[2], y);
 }
 
 // cell [n,3]: the candidates' cells (NO_CELL in [0]: none)
@@ -101,13 +89,12 @@ __global__ __launch_bounds__(256) void cell_kernel(Clouds L, int* __restrict__ c
     float y[3];
     candidate(C, i - C.c0, y);
     int c[3];
-    const bool finite = isfinite(y[0]) && isfinite(y[1]) && isfinite(y[2]);
-    for (int k = 0; k < 3; ++k) c[k] = finite ? (int)fminf(fmaxf(floorf(y[k] * C.inv), -CELL_MAX), CELL_MAX) : NO_CELL;
+    cell_of(y, C.inv, c);
     for (int k = 0; k < 3; ++k) cell[i * 3 + k] = c[k];
 }
 
 // the table of a problem: slot s holds the lowest LOCAL index seen so far of the candidates of one cell (-1: free).  A problem has at most
-// n_p cells for 2 n_p slots; the walk ends after T slots whatever happens.
+// n_p cells for 2 n_p slots.
 template <class Clouds>
 __global__ __launch_bounds__(256) void hash_kernel(Clouds L, const int* __restrict__ cell, int* __restrict__ table, unsigned* __restrict__ slot_of,
                                                    int* __restrict__ status) {
@@ -121,21 +108,9 @@ __global__ __launch_bounds__(256) void hash_kernel(Clouds L, const int* __restri
     const int p = L.cand_owner(i);
     const CloudRef C = L.cloud(p);
     const int me = (int)(i - C.c0);
-    const unsigned long long hsh = mix64(mix64(((unsigned long long)(unsigned)c0 << 32) | (unsigned)c1) + (unsigned long long)(unsigned)c2);
-    long long s = (long long)(((hsh >> 32) * (unsigned long long)C.T) >> 32);   // in [0, T): T < 2^32
-    unsigned found = NO_SLOT;
-    for (long long step = 0; step < C.T; ++step) {
-        const long long slot = C.t0 + s;
-        int occupant = atomicCAS(&table[slot], -1, me);
-        if (occupant == -1) occupant = me;
-        const int* __restrict__ oc = cell + (C.c0 + occupant) * 3;
-        if (occupant == me || (oc[0] == c0 && oc[1] == c1 && oc[2] == c2)) {
-            if (occupant > me) atomicMin(&table[slot], me);   // a slot's index only ever falls: below me already, nothing to do
-            found = (unsigned)slot;
-            break;
-        }
-        if (++s == C.T) s = 0;
-    }
+    int occupant;
+    const unsigned found = claim_slot(table, C.t0, C.T, cell + C.c0 * 3, c0, c1, c2, me, occupant);
+    if (found != NO_SLOT && occupant > me) atomicMin(&table[found], me);   // a slot's index only ever falls: below me already, nothing to do
     slot_of[i] = found;
     if (found == NO_SLOT) status[p] = LS_ERR_WORKSPACE;
 }
@@ -235,14 +210,6 @@ int merge_launch(const Clouds& L, int P, long long n, const Ws& w, float* out_pt
     return LS_OK;
 }
 
-// inv = 1.0f / h, the one rounding of the definition; h (and so inv) finite and positive
-int voxel_inverse(const char* op, int p, float h, float* inv) {
-    LS_REQUIRE(std::isfinite(h) && h > 0.0f, "%s: problem %d: the voxel edge must be finite and > 0, got %g", op, p, (double)h);
-    *inv = 1.0f / h;
-    LS_REQUIRE(std::isfinite(*inv), "%s: problem %d: 1 / voxel overflows fp32 (voxel %g)", op, p, (double)h);
-    return LS_OK;
-}
-
 int check_common(const char* op, long long a, long long b, const float* A, const float* B, const float* out_pts, const int* out_src,
                  const long long* out_off) {
     LS_REQUIRE(a >= 0 && b >= 0, "%s: negative size (%lld kept rows, %lld new rows)", op, a, b);
@@ -266,14 +233,10 @@ int ls_cloud_merge_f32(const float* A, long long a, const float* B, long long b,
     int rc = check_common(op, a, b, A, B, out_pts, out_src, out_off);
     if (rc != LS_OK) return rc;
     float inv;
-    rc = voxel_inverse(op, 0, voxel, &inv);
+    rc = check_edge(op, 0, "voxel edge", "voxel", voxel, &inv);
     if (rc != LS_OK) return rc;
-    const size_t need = ls_cloud_merge_workspace_bytes(a, b);
-    if (!workspace || workspace_bytes < need) {
-        set_error("%s: workspace %zu < required %zu (ls_cloud_merge_workspace_bytes(%lld, %lld))", op, workspace ? workspace_bytes : (size_t)0, need, a,
-                  b);
-        return LS_ERR_WORKSPACE;
-    }
+    rc = check_workspace(op, workspace, workspace_bytes, ls_cloud_merge_workspace_bytes(a, b), 0, a, b);
+    if (rc != LS_OK) return rc;
     const Ws w = layout(workspace, 0, 1, a + b);
     return merge_launch(OneCloud{A, a, B, b, g, inv}, 1, a + b, w, out_pts, out_src, out_off, status_out, (hipStream_t)stream);
 }
@@ -299,15 +262,11 @@ int ls_cloud_merge_batch_f32(int P, const float* A, long long a_total, const lon
     std::vector<float> inv(P);
     for (int p = 0; p < P; ++p) {
         c_off[p + 1] = a_off[p + 1] + b_off[p + 1];
-        rc = voxel_inverse(op, p, voxel[p], &inv[p]);
+        rc = check_edge(op, p, "voxel edge", "voxel", voxel[p], &inv[p]);
         if (rc != LS_OK) return rc;
     }
-    const size_t need = ls_cloud_merge_batch_workspace_bytes(P, a_total, b_total);
-    if (!workspace || workspace_bytes < need) {
-        set_error("%s: workspace %zu < required %zu (ls_cloud_merge_batch_workspace_bytes(%d, %lld, %lld))", op,
-                  workspace ? workspace_bytes : (size_t)0, need, P, a_total, b_total);
-        return LS_ERR_WORKSPACE;
-    }
+    rc = check_workspace(op, workspace, workspace_bytes, ls_cloud_merge_batch_workspace_bytes(P, a_total, b_total), P, a_total, b_total);
+    if (rc != LS_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const Ws w = layout(workspace, (size_t)OFF_ARRAYS * (P + 1), P, a_total + b_total);
     rc = upload_offsets(w.offs, pack_offsets(P, {a_off, b_off, c_off.data()}), st);

@@ -1,33 +1,28 @@
 // cloudnear.hip -- scene memory: fixed-radius nearest neighbour between the cloud an instance keeps (A, the targets) and a posed observation of
 // it (B, the queries), with the overlap statistics of the pair.  The definition is in include/livingscenes_hip.h (ls_cloud_nearest_f32) and,
-// as NumPy, in tests/nearest_oracle.py; this file follows it to the letter:
-//   queries     the rows of B under the pose g (R | t): y_a = ((R_a0 x_0 + R_a1 x_1) + R_a2 x_2) + t_a in fp32, every product and sum rounded
-//               (no contraction in this file, the expression of cloudmerge.hip); g == NULL: the rows of B bit for bit
-//   cell        of edge r, for targets and queries alike: c_a = (int)clamp(floorf(x_a inv), -2^30, 2^30), inv = 1.0f / r formed once on the
-//               host; a row with a non-finite coordinate has no cell: such a target is never a neighbour, such a query has none
+// as NumPy, in tests/nearest_oracle.py; the pose, the cell (of edge r, for targets and queries alike), the table and its claim walk are
+// those of cloud_grid.h.  What this file adds:
 //   distance    d2 = ((dx dx + dy dy) + dz dz), dx = y_0 - A[j][0] ..., every operation rounded to fp32; r2 = r r rounded on the host
 //   neighbour   of query i: among the targets j whose cell differs from the query's by at most 1 on every axis and with d2 <= r2, the least
-//               under (d2, j)
-// Method: the merge's open-addressing table, 2 a_p slots per problem.  A target claims an empty slot for its cell with an integer CAS or finds
-// the slot of its cell, at most over the whole table; the atomic count of a slot hands every target its rank in the cell.  Count -> scan
-// (ls_scan.h) -> fill puts the members of every cell back to back as (x, y, z, index).  One thread per query then walks the 27 cells around
-// its own -- each by a probe walk that ends at the cell or at an empty slot -- and keeps the minimum under (d2, j) in registers: which slot a
+//               under (d2, j); a target without a cell is never a neighbour, a query without one has none
+// Method: a table of 2 a_p slots per problem; the atomic count of a slot hands every target of its cell a rank.  Count -> scan (ls_scan.h)
+// -> fill puts the members of every cell back to back as (x, y, z, index).  One thread per query then walks the 27 cells around its own
+// -- each by a probe walk that ends at the cell or at an empty slot -- and keeps the minimum under (d2, j) in registers: which slot a
 // cell got and the order of its members depend on the race, the minimum does not.  The sum of the distances follows the per-problem rule of
 // regmetrics.hip: a workgroup owns one chunk of QUERY_CHUNK queries of ONE problem, adds it in a fixed LDS tree and writes one float64
 // partial; the last kernel adds a problem's partials in chunk order.  Integer atomics only, and only on the table: a problem's outputs are
-// the same bits alone, in any batch and in any run.  The kernels that need the problem are written once, for a problem locator (OneNear /
-// RaggedNear, as OneCloud / RaggedClouds of cloudmerge.hip); the number of launches does not depend on P.
-// The same grid serves the trimmed ICP of the scene memory (ls_cloud_icp_f32, an extension beyond the released reference like the search
-// itself; tests/icp_oracle.py): the grid is built once over the memory, then every iteration repeats the search under the current pose --
-// the per-query walk is one __device__ function for both -- with the float64 moments of the matched pairs per chunk, and one workgroup per
-// problem adds the chunk records in order, applies the stop tests and solves the 3x3 Kabsch problem (svd3.h).  A stopped problem is frozen:
-// its workgroups exit at once, so the launches depend on max_iter alone and nothing waits on the host or on another workgroup.
-// Two more extensions on the same grid.  The normals of the kept cloud (ls_cloud_normals_f32; tests/normals_oracle.py): one thread per
-// target walks the 27 cells around its own with the target as the query and adds INTEGER moments of the neighbours' offsets -- the member
-// order depends on the race, an integer sum does not -- then the covariance and its eigenvectors in float64 (svd3.h).  And the same ICP
-// loop with the point-to-plane metric (ls_cloud_icp_plane_f32; tests/plane_icp_oracle.py): the search and the solve kernel are templates on
-// the metric, which says what a match adds to its chunk's record (15 moments for Kabsch | 28 for the 6 x 6 normal equations) and how
-// g_{k+1} follows from the sums (kabsch_rotation | Cholesky, exp, polar factor).
+// the same bits alone, in any batch and in any run.
+// Three more operators on the same grid, all extensions beyond the released reference like the search itself.  The trimmed ICP
+// (ls_cloud_icp_f32; tests/icp_oracle.py): the grid is built once over the memory, then every iteration repeats the search under the
+// current pose -- search_chunk is one __device__ function for both -- with the float64 moments of the matched pairs per chunk, and one
+// workgroup per problem adds the chunk records in order, applies the stop tests and solves the 3x3 Kabsch problem (svd3.h).  A stopped
+// problem is frozen: its workgroups exit at once, so the launches depend on max_iter alone and nothing waits on the host or on another
+// workgroup.  The normals of the kept cloud (ls_cloud_normals_f32; tests/normals_oracle.py): one thread per target walks the 27 cells
+// around its own and adds INTEGER moments of the neighbours' offsets, then the covariance and its eigenvectors in float64.  And the ICP
+// loop with the point-to-plane metric (ls_cloud_icp_plane_f32; tests/plane_icp_oracle.py): the search and the solve kernel are templates
+// on the metric, which says what a match adds to its chunk's record and how g_{k+1} follows from the sums.
+// An operator on this grid is a kernel templated on the problem locator (OneNear / RaggedNear), a launch function after grid_launch, and
+// an entry that describes its call (NearCall) and hands the launch to near_run: every check, size and upload of the entry path is there.
 #include <climits>
 #include <cmath>
 #include <vector>
@@ -39,13 +34,12 @@
 
 // the arithmetic of the definition as written: no contraction of a * b + c into an fma anywhere in this file
 #pragma clang fp contract(off)
+#include "cloud_grid.h"
 
 namespace ls {
 namespace cnr {
+using namespace cloud;
 
-constexpr int NO_CELL = INT_MIN;              // [0] of a cell triple: the row has no cell / the slot is empty (cells are clamped to [-2^30, 2^30])
-constexpr unsigned NO_SLOT = 0xFFFFFFFFu;     // slot_of[i]: the target is in no slot (no cell, or the table overflowed)
-constexpr float CELL_MAX = 1073741824.0f;     // 2^30
 constexpr int QUERY_CHUNK = 256;              // queries per workgroup, one per thread: the chunk of the float64 sum
 
 // ------------------------------------------------------------------------------------------------ which problem: one, or one of a ragged batch
@@ -86,18 +80,6 @@ struct RaggedNear {
     }
 };
 
-__device__ __forceinline__ bool cell_of(const float (&y)[3], float inv, int (&c)[3]) {
-    const bool finite = isfinite(y[0]) && isfinite(y[1]) && isfinite(y[2]);
-    for (int k = 0; k < 3; ++k) c[k] = finite ? (int)fminf(fmaxf(floorf(y[k] * inv), -CELL_MAX), CELL_MAX) : NO_CELL;
-    return finite;
-}
-
-// the first slot of a cell's probe walk in a table of T slots (T < 2^32)
-__device__ __forceinline__ long long first_slot(int c0, int c1, int c2, long long T) {
-    const unsigned long long hsh = mix64(mix64(((unsigned long long)(unsigned)c0 << 32) | (unsigned)c1) + (unsigned long long)(unsigned)c2);
-    return (long long)(((hsh >> 32) * (unsigned long long)T) >> 32);
-}
-
 // tcell [a_total,3]: the targets' cells (NO_CELL in [0]: none)
 template <class Near>
 __global__ __launch_bounds__(256) void tcell_kernel(Near L, const float* __restrict__ A, long long a_total, int* __restrict__ tcell) {
@@ -111,8 +93,7 @@ __global__ __launch_bounds__(256) void tcell_kernel(Near L, const float* __restr
 }
 
 // the table of a problem: slot s holds the GLOBAL index of the target that claimed it for its cell (-1: free) and never changes again, so all
-// targets of a cell meet in one slot; cnt[s] counts them and hands each its rank.  A problem has at most a_p cells for 2 a_p slots; the walk
-// ends after T slots whatever happens.
+// targets of a cell meet in one slot; cnt[s] counts them and hands each its rank.  A problem has at most a_p cells for 2 a_p slots.
 template <class Near>
 __global__ __launch_bounds__(256) void claim_kernel(Near L, long long a_total, const int* __restrict__ tcell, int* __restrict__ table,
                                                     int* __restrict__ cnt, unsigned* __restrict__ slot_of, int* __restrict__ rank,
@@ -126,21 +107,8 @@ __global__ __launch_bounds__(256) void claim_kernel(Near L, long long a_total, c
     }
     const int p = L.target_owner(i);
     const NearRef C = L.problem(p);
-    const long long t0 = 2 * C.a0, T = 2 * C.a;
-    const int me = (int)i;
-    long long s = first_slot(c0, c1, c2, T);
-    unsigned found = NO_SLOT;
-    for (long long step = 0; step < T; ++step) {
-        const long long slot = t0 + s;
-        int occupant = atomicCAS(&table[slot], -1, me);
-        if (occupant == -1) occupant = me;
-        const int* oc = tcell + (long long)occupant * 3;                 // the slot is mine: my own cell
-        if ((oc[0] == c0) & (oc[1] == c1) & (oc[2] == c2)) {
-            found = (unsigned)slot;
-            break;
-        }
-        if (++s == T) s = 0;
-    }
+    int occupant;
+    const unsigned found = claim_slot(table, 2 * C.a0, 2 * C.a, tcell, c0, c1, c2, (int)i, occupant);
     slot_of[i] = found;
     if (found == NO_SLOT) status[p] = LS_ERR_WORKSPACE;
     else rank[i] = atomicAdd(&cnt[found], 1);
@@ -165,13 +133,6 @@ __global__ __launch_bounds__(256) void fill_kernel(const float* __restrict__ A, 
     const unsigned s = slot_of[i];
     if (s == NO_SLOT) return;
     members[(long long)start[s] + rank[i]] = make_float4(A[i * 3 + 0], A[i * 3 + 1], A[i * 3 + 2], __int_as_float((int)i));
-}
-
-// a query row under the pose: y_a = ((R_a0 x_0 + R_a1 x_1) + R_a2 x_2) + t_a (g null: the row bit for bit)
-__device__ __forceinline__ void pose_row(const float* __restrict__ g, float x0, float x1, float x2, float (&y)[3]) {
-    y[0] = x0, y[1] = x1, y[2] = x2;
-    if (g)
-        for (int r = 0; r < 3; ++r) y[r] = ((g[r * 4 + 0] * x0 + g[r * 4 + 1] * x1) + g[r * 4 + 2] * x2) + g[r * 4 + 3];
 }
 
 // the 27 cells around c, each by a probe walk that ends at the cell or at an empty slot: visit(member) for every target in them, in an order
@@ -238,23 +199,23 @@ __device__ __forceinline__ double chunk_sum(double (&lds)[QUERY_CHUNK], double v
     return lds[0];
 }
 
-// workgroup = one chunk of QUERY_CHUNK queries of one problem, one thread per query.  part[chunk] = the float64 sum of the chunk's nn_d2 in a
-// fixed order, part_cnt[chunk] = (finite queries, queries with a neighbour).
-template <class Near>
-__global__ __launch_bounds__(QUERY_CHUNK) void query_kernel(Near L, const int4* __restrict__ slots, const int* __restrict__ cnt,
-                                                            const float4* __restrict__ members, unsigned char* __restrict__ hit,
-                                                            int* __restrict__ nn_idx, float* __restrict__ nn_d2, double* __restrict__ part,
-                                                            int2* __restrict__ part_cnt) {
-    __shared__ double lds[QUERY_CHUNK];
-    const NearRef C = L.problem(L.chunk_owner(blockIdx.x));
+// The search of the chunk blockIdx.x -- QUERY_CHUNK queries of the one problem C, one thread per query, under the pose g -- by the whole
+// workgroup: nn_idx / nn_d2 of the query, part[chunk] = the float64 sum of the chunk's nn_d2 in a fixed order, part_cnt[chunk] = (finite
+// queries, queries with a neighbour).  Written once for the search and for every iteration of the ICP: the last search of a problem IS
+// its final search.  What it leaves in its thread: best_j, the global index of the neighbour (the caller sets INT_MAX: none), the query's
+// row x, the posed row y as the search formed it and the neighbour's coordinates a, untouched where the thread has no query
+// -> the thread has a neighbour.  The caller's plain locals by reference and the caller's LDS array, not a struct by value and an array
+// of its own: measured, the struct cost the point ICP's search 4 us of 308 per launch on small problems (docs/history.md, section 35).
+__device__ __forceinline__ bool search_chunk(const NearRef& C, const float* __restrict__ g, const int4* __restrict__ slots,
+                                             const int* __restrict__ cnt, const float4* __restrict__ members, int* __restrict__ nn_idx,
+                                             float* __restrict__ nn_d2, double* __restrict__ part, int2* __restrict__ part_cnt,
+                                             double (&lds)[QUERY_CHUNK], int& best_j, float (&x)[3], float (&y)[3], float (&a)[3]) {
     const long long qi = ((long long)blockIdx.x - C.q0) * QUERY_CHUNK + threadIdx.x;
     const bool live = qi < C.b;
     bool finite = false;
-    int best_j = INT_MAX;
-    float best = INFINITY, x[3], y[3], best_a[3];
-    if (live) finite = query_one(C, C.g, qi, slots, cnt, members, x, y, best, best_j, best_a);
+    float best = INFINITY;
+    if (live) finite = query_one(C, g, qi, slots, cnt, members, x, y, best, best_j, a);
     const bool has = best_j != INT_MAX;
-    if (has) hit[best_j] = 1;                                          // every writer writes the same byte
     if (live) {
         nn_idx[C.b0 + qi] = has ? (int)(best_j - C.a0) : -1;
         nn_d2[C.b0 + qi] = best;
@@ -264,6 +225,33 @@ __global__ __launch_bounds__(QUERY_CHUNK) void query_kernel(Near L, const int4* 
     if (threadIdx.x == 0) {
         part[blockIdx.x] = sum;
         part_cnt[blockIdx.x] = make_int2(n_finite, n_has);
+    }
+    return has;
+}
+
+// workgroup = one chunk of queries under the problem's own pose; hit[j] = target j is somebody's neighbour
+template <class Near>
+__global__ __launch_bounds__(QUERY_CHUNK) void query_kernel(Near L, const int4* __restrict__ slots, const int* __restrict__ cnt,
+                                                            const float4* __restrict__ members, unsigned char* __restrict__ hit,
+                                                            int* __restrict__ nn_idx, float* __restrict__ nn_d2, double* __restrict__ part,
+                                                            int2* __restrict__ part_cnt) {
+    const NearRef C = L.problem(L.chunk_owner(blockIdx.x));
+    __shared__ double lds[QUERY_CHUNK];
+    int best_j = INT_MAX;
+    float x[3], y[3], a[3];
+    if (search_chunk(C, C.g, slots, cnt, members, nn_idx, nn_d2, part, part_cnt, lds, best_j, x, y, a))
+        hit[best_j] = 1;                                               // every writer writes the same byte
+}
+
+// the totals of K counters over the 256 threads of a workgroup, v[k] of every thread -> lds[k][0]
+template <int K>
+__device__ __forceinline__ void count_tree(long long (&lds)[K][256], const long long (&v)[K]) {
+    for (int k = 0; k < K; ++k) lds[k][threadIdx.x] = v[k];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o)
+            for (int k = 0; k < K; ++k) lds[k][threadIdx.x] += lds[k][threadIdx.x + o];
+        __syncthreads();
     }
 }
 
@@ -281,13 +269,7 @@ __global__ __launch_bounds__(256) void final_kernel(Near L, const unsigned char*
         v[1] += part_cnt[q].y;
     }
     for (long long j = threadIdx.x; j < C.a; j += 256) v[2] += hit[C.a0 + j];
-    for (int k = 0; k < 3; ++k) lds[k][threadIdx.x] = v[k];
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o)
-            for (int k = 0; k < 3; ++k) lds[k][threadIdx.x] += lds[k][threadIdx.x + o];
-        __syncthreads();
-    }
+    count_tree(lds, v);
     if (threadIdx.x < 3) counts[(size_t)p * 3 + threadIdx.x] = lds[threadIdx.x][0];
     if (threadIdx.x == 0) {
         double s = 0.0;
@@ -372,13 +354,7 @@ __global__ __launch_bounds__(256) void normals_final_kernel(Near L, const float*
         v[0] += nbr_cnt[j] > 0;
         v[1] += normals[j * 3 + 0] != 0.f || normals[j * 3 + 1] != 0.f || normals[j * 3 + 2] != 0.f;
     }
-    for (int k = 0; k < 2; ++k) lds[k][threadIdx.x] = v[k];
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o)
-            for (int k = 0; k < 2; ++k) lds[k][threadIdx.x] += lds[k][threadIdx.x + o];
-        __syncthreads();
-    }
+    count_tree(lds, v);
     if (threadIdx.x < 2) counts[(size_t)p * 2 + threadIdx.x] = lds[threadIdx.x][0];
     if (threadIdx.x == 0 && status_out) status_out[p] = status[p];
 }
@@ -433,9 +409,8 @@ __device__ __forceinline__ void plane_moments(bool planar, const float (&y)[3], 
         for (int c = r; c < 6; ++c) m[e++] = J[r] * J[c];
 }
 
-// The search of iteration k: query_kernel under g_k, for the chunks of the problems that still run.  Besides nn_idx / nn_d2 / part /
-// part_cnt -- the same values by the same code, so the last search of a problem IS its final search -- one record of N_MOM float64 moments
-// per chunk over the matched queries.  Point metric: the ORIGINAL row x of B and its neighbour a, products formed in float64 (exact:
+// The search of iteration k: search_chunk under g_k, for the chunks of the problems that still run, and one record of N_MOM float64
+// moments per chunk over the matched queries.  Point metric: the ORIGINAL row x of B and its neighbour a, products formed in float64 (exact:
 // 24 x 24 bits).  Plane metric: a matched query gathers the normal row of its neighbour from N (packed like A); the match is planar iff
 // that row is not zero, part_w[chunk] counts them.  The moments go through a fixed tree inside every wave and a fixed tree over the four
 // waves: under 1 KB of LDS instead of 30 KB and more.
@@ -452,19 +427,9 @@ __global__ __launch_bounds__(QUERY_CHUNK) void icp_search_kernel(Near L, const i
     const int p = L.chunk_owner(blockIdx.x);
     if (stop[p] != ICP_RUNNING) return;                                // the whole workgroup: a stopped problem is frozen
     const NearRef C = L.problem(p);
-    const long long qi = ((long long)blockIdx.x - C.q0) * QUERY_CHUNK + threadIdx.x;
-    const bool live = qi < C.b;
-    bool finite = false;
     int best_j = INT_MAX;
-    float best = INFINITY, x[3] = {0.f, 0.f, 0.f}, y[3] = {0.f, 0.f, 0.f}, a[3] = {0.f, 0.f, 0.f};
-    if (live) finite = query_one(C, gk + (size_t)p * 12, qi, slots, cnt, members, x, y, best, best_j, a);
-    const bool has = best_j != INT_MAX;
-    if (live) {
-        nn_idx[C.b0 + qi] = has ? (int)(best_j - C.a0) : -1;
-        nn_d2[C.b0 + qi] = best;
-    }
-    const int n_finite = __syncthreads_count(finite), n_has = __syncthreads_count(has);
-    const double sum = chunk_sum(lds, has ? (double)best : 0.0);
+    float x[3] = {0.f, 0.f, 0.f}, y[3] = {0.f, 0.f, 0.f}, a[3] = {0.f, 0.f, 0.f};
+    const bool has = search_chunk(C, gk + (size_t)p * 12, slots, cnt, members, nn_idx, nn_d2, part, part_cnt, lds, best_j, x, y, a);
     double m[N_MOM];
     if constexpr (Metric::PLANE) {
         float n[3] = {0.f, 0.f, 0.f};
@@ -491,10 +456,6 @@ __global__ __launch_bounds__(QUERY_CHUNK) void icp_search_kernel(Near L, const i
     if (threadIdx.x < N_MOM) {
         const double* v = wave_part[threadIdx.x];
         mom[(size_t)blockIdx.x * N_MOM + threadIdx.x] = (v[0] + v[1]) + (v[2] + v[3]);
-    }
-    if (threadIdx.x == 0) {
-        part[blockIdx.x] = sum;
-        part_cnt[blockIdx.x] = make_int2(n_finite, n_has);
     }
 }
 
@@ -841,16 +802,6 @@ int normals_launch(const Near& L, int P, const float* A, long long a, int min_nb
     return LS_OK;
 }
 
-// inv = 1.0f / r and r2 = r * r, the two roundings of the definition; all three finite and positive
-int radius_terms(const char* op, int p, float r, float* inv, float* r2) {
-    LS_REQUIRE(std::isfinite(r) && r > 0.0f, "%s: problem %d: the radius must be finite and > 0, got %g", op, p, (double)r);
-    *inv = 1.0f / r;
-    LS_REQUIRE(std::isfinite(*inv), "%s: problem %d: 1 / radius overflows fp32 (radius %g)", op, p, (double)r);
-    *r2 = r * r;
-    LS_REQUIRE(std::isfinite(*r2) && *r2 > 0.0f, "%s: problem %d: radius^2 is not a finite positive fp32 (radius %g)", op, p, (double)r);
-    return LS_OK;
-}
-
 int check_common(const char* op, long long a, long long b, const float* A, const float* B, const int* nn_idx, const float* nn_d2,
                  const long long* counts, const double* sum_d2) {
     LS_REQUIRE(a >= 0 && b >= 0, "%s: negative size (%lld kept rows, %lld query rows)", op, a, b);
@@ -860,187 +811,189 @@ int check_common(const char* op, long long a, long long b, const float* A, const
     return LS_OK;
 }
 
-// what a batch entry derives on the host: the chunk offsets and the radius terms of every problem
-struct BatchHost {
-    std::vector<long long> q_off;
-    std::vector<float> inv, r2;
+// One call of an operator on the grid, as its entry describes it: the single form or a ragged batch of P problems, a targets and b
+// queries in all (an operator without queries: has_b false, b = 0), the radius of every problem.
+struct NearCall {
+    const char* op;
+    bool batch;
+    int P;                       // a batch: its problems
+    const float* A;
+    long long a;
+    const long long* a_off;      // a batch: [P+1]
+    bool has_b;
+    const float* B;
+    long long b;
+    const long long* b_off;      // a batch with queries: [P+1]
+    const float* g;              // the locator's pose: [3,4] / [P,3,4] or null
+    const float* radius;         // a batch: [P]; the single form: the address of its one radius
+    int n_mom;                   // the ICP: the metric's N_MOM; 0: no ICP
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+
+    // the two forms an entry fills, every field by name; an operator without queries passes no B and clears has_b
+    static NearCall one(const char* op, const float* A, long long a, const float* B, long long b, const float* g, const float* radius,
+                        int n_mom, void* workspace, size_t workspace_bytes, void* stream) {
+        NearCall c{};
+        c.op = op, c.batch = false, c.P = 1;
+        c.A = A, c.a = a, c.a_off = nullptr;
+        c.has_b = true, c.B = B, c.b = b, c.b_off = nullptr;
+        c.g = g, c.radius = radius, c.n_mom = n_mom;
+        c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = stream;
+        return c;
+    }
+    static NearCall ragged(const char* op, int P, const float* A, long long a_total, const long long* a_off, const float* B, long long b_total,
+                           const long long* b_off, const float* g, const float* radius, int n_mom, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+        NearCall c = one(op, A, a_total, B, b_total, g, radius, n_mom, workspace, workspace_bytes, stream);
+        c.batch = true, c.P = P, c.a_off = a_off, c.b_off = b_off;
+        return c;
+    }
 };
 
-// the host checks of a batch, all before the first HIP call; the errors name the problem
-int check_batch(const char* op, int P, const float* A, long long a_total, const long long* a_off, const float* B, long long b_total,
-                const long long* b_off, const float* radius, const int* nn_idx, const float* nn_d2, const long long* counts, const double* sum_d2,
-                BatchHost* h) {
-    LS_REQUIRE(P >= 1, "%s: P must be at least 1, got %d", op, P);
-    int rc = check_common(op, a_total, b_total, A, B, nn_idx, nn_d2, counts, sum_d2);
-    if (rc != LS_OK) return rc;
-    rc = check_ranges(op, "problem", "a_off", P, a_off, a_total, INT_MAX);
-    if (rc != LS_OK) return rc;
-    rc = check_ranges(op, "problem", "b_off", P, b_off, b_total, INT_MAX);
-    if (rc != LS_OK) return rc;
-    LS_REQUIRE(radius, "%s: null radius", op);
-    h->q_off.assign(P + 1, 0);
-    h->inv.resize(P);
-    h->r2.resize(P);
-    for (int p = 0; p < P; ++p) {
-        h->q_off[p + 1] = h->q_off[p] + chunks_of(b_off[p + 1] - b_off[p]);
-        rc = radius_terms(op, p, radius[p], &h->inv[p], &h->r2[p]);
-        if (rc != LS_OK) return rc;
-    }
-    return LS_OK;
+// every size query: 0 for sizes no call accepts
+size_t near_bytes(bool batch, int P, long long a, long long b, int n_mom) {
+    if ((batch && P < 1) || a < 0 || b < 0 || a + b > INT_MAX) return 0;
+    return layout(nullptr, batch ? (size_t)OFF_ARRAYS * (P + 1) : 0, batch ? P : 1, a, b, n_mom).bytes;
 }
 
-int upload_batch(const Ws& w, int P, const long long* a_off, const long long* b_off, const BatchHost& h, hipStream_t st) {
-    const int rc = upload_offsets(w.offs, pack_offsets(P, {a_off, b_off, h.q_off.data()}), st);
+// The entry path of every operator, all checks before the first HIP call and in one order: sizes() -- the operator's checks of its sizes
+// and pointers -- the offsets of a batch, the radius terms and the chunks of every problem (the errors name the problem), checks() -- the
+// operator's other arguments -- and the workspace; then the layout, for a batch the upload of what the locator reads, and
+// launch(locator, P, layout, chunks, stream).  The single form uploads nothing and allocates nothing on the host.
+template <class Sizes, class Checks, class Launch>
+int near_run(const NearCall& c, Sizes&& sizes, Checks&& checks, Launch&& launch) {
+    const char* op = c.op;
+    LS_REQUIRE(!c.batch || c.P >= 1, "%s: P must be at least 1, got %d", op, c.P);
+    const int P = c.batch ? c.P : 1;
+    int rc = sizes();
     if (rc != LS_OK) return rc;
-    LS_HIP_CHECK(hipMemcpyAsync(w.inv, h.inv.data(), (size_t)P * sizeof(float), hipMemcpyHostToDevice, st));   // pageable: read when it returns
-    LS_HIP_CHECK(hipMemcpyAsync(w.r2, h.r2.data(), (size_t)P * sizeof(float), hipMemcpyHostToDevice, st));
-    return LS_OK;
+    if (c.batch) {
+        rc = check_ranges(op, "problem", "a_off", P, c.a_off, c.a, INT_MAX);
+        if (rc != LS_OK) return rc;
+        if (c.has_b) rc = check_ranges(op, "problem", "b_off", P, c.b_off, c.b, INT_MAX);
+        if (rc != LS_OK) return rc;
+        LS_REQUIRE(c.radius, "%s: null radius", op);
+    }
+    std::vector<long long> q_off(c.batch ? P + 1 : 0, 0);               // a batch: the chunk offsets; without queries also its b_off
+    std::vector<float> terms(c.batch ? 2 * (size_t)P : 0);
+    float one[2];
+    float *inv = c.batch ? terms.data() : one, *r2 = inv + P;
+    long long chunks = 0;
+    for (int p = 0; p < P; ++p) {
+        if (c.has_b) chunks += chunks_of(c.batch ? c.b_off[p + 1] - c.b_off[p] : c.b);
+        if (c.batch) q_off[p + 1] = chunks;
+        rc = check_edge(op, p, "radius", "radius", c.radius[p], &inv[p], &r2[p]);
+        if (rc != LS_OK) return rc;
+    }
+    rc = checks();
+    if (rc != LS_OK) return rc;
+    rc = check_workspace(op, c.workspace, c.workspace_bytes, near_bytes(c.batch, c.P, c.a, c.b, c.n_mom), c.batch ? P : 0, c.a, c.has_b ? c.b : -1);
+    if (rc != LS_OK) return rc;
+    const Ws w = layout(c.workspace, c.batch ? (size_t)OFF_ARRAYS * (P + 1) : 0, P, c.a, c.b, c.n_mom);
+    hipStream_t st = (hipStream_t)c.stream;
+    if (!c.batch) return launch(OneNear{c.B, c.a, c.b, c.g, inv[0], r2[0]}, P, w, chunks, st);
+    rc = upload_offsets(w.offs, pack_offsets(P, {c.a_off, c.has_b ? c.b_off : q_off.data(), q_off.data()}), st);
+    if (rc != LS_OK) return rc;
+    LS_HIP_CHECK(hipMemcpyAsync(w.inv, inv, (size_t)P * sizeof(float), hipMemcpyHostToDevice, st));   // pageable: read when it returns
+    LS_HIP_CHECK(hipMemcpyAsync(w.r2, r2, (size_t)P * sizeof(float), hipMemcpyHostToDevice, st));
+    return launch(RaggedNear{c.B, c.g, w.offs, w.inv, w.r2, P}, P, w, chunks, st);
+}
+
+const auto no_checks = [] { return LS_OK; };
+
+// the entry of the search
+int nearest_entry(const NearCall& c, int* nn_idx, float* nn_d2, long long* counts, double* sum_d2, int* status_out) {
+    return near_run(
+        c, [&] { return check_common(c.op, c.a, c.b, c.A, c.B, nn_idx, nn_d2, counts, sum_d2); }, no_checks,
+        [&](const auto& L, int P, const Ws& w, long long chunks, hipStream_t st) {
+            return nearest_launch(L, P, c.A, c.a, c.b, chunks, w, nn_idx, nn_d2, counts, sum_d2, status_out, st);
+        });
+}
+
+// the entry of the ICP under either metric, from the pose g0 (the locator has none).  The plane metric's own pointers are checked with
+// the sizes in the single form and after the radii in a batch.
+template <class Metric>
+int icp_entry(const NearCall& c, const float* g0, const IcpArgs& I, int* nn_idx, float* nn_d2, long long* counts, double* sum_d2, int* status_out) {
+    const auto plane = [&] { return Metric::PLANE ? check_plane(c.op, c.a, I) : LS_OK; };
+    return near_run(
+        c,
+        [&] {
+            const int rc = check_common(c.op, c.a, c.b, c.A, c.B, nn_idx, nn_d2, counts, sum_d2);
+            return rc != LS_OK || c.batch ? rc : plane();
+        },
+        [&] {
+            const int rc = c.batch ? plane() : LS_OK;
+            return rc != LS_OK ? rc : check_icp(c.op, I);
+        },
+        [&](const auto& L, int P, const Ws& w, long long chunks, hipStream_t st) {
+            return icp_launch<Metric>(L, P, c.A, c.a, chunks, g0, I, w, nn_idx, nn_d2, counts, sum_d2, status_out, st);
+        });
+}
+
+// the entry of the normals: no queries
+int normals_entry(const NearCall& c, int min_nbrs, float* normals, int* nbr_cnt, float* variation, long long* counts, int* status_out) {
+    return near_run(
+        c, [&] { return check_normals(c.op, c.a, c.A, min_nbrs, normals, nbr_cnt, variation, counts); }, no_checks,
+        [&](const auto& L, int P, const Ws& w, long long, hipStream_t st) {
+            return normals_launch(L, P, c.A, c.a, min_nbrs, w, normals, nbr_cnt, variation, counts, status_out, st);
+        });
 }
 }  // namespace
 
 extern "C" {
 
-size_t ls_cloud_nearest_workspace_bytes(long long a, long long b) {
-    if (a < 0 || b < 0 || a + b > INT_MAX) return 0;
-    return layout(nullptr, 0, 1, a, b).bytes;
+size_t ls_cloud_nearest_workspace_bytes(long long a, long long b) { return near_bytes(false, 1, a, b, 0); }
+size_t ls_cloud_nearest_batch_workspace_bytes(int P, long long a_total, long long b_total) { return near_bytes(true, P, a_total, b_total, 0); }
+size_t ls_cloud_icp_workspace_bytes(long long a, long long b) { return near_bytes(false, 1, a, b, PointMetric::N_MOM); }
+size_t ls_cloud_icp_batch_workspace_bytes(int P, long long a_total, long long b_total) {
+    return near_bytes(true, P, a_total, b_total, PointMetric::N_MOM);
 }
+size_t ls_cloud_icp_plane_workspace_bytes(long long a, long long b) { return near_bytes(false, 1, a, b, PlaneMetric::N_MOM); }
+size_t ls_cloud_icp_plane_batch_workspace_bytes(int P, long long a_total, long long b_total) {
+    return near_bytes(true, P, a_total, b_total, PlaneMetric::N_MOM);
+}
+size_t ls_cloud_normals_workspace_bytes(long long a) { return near_bytes(false, 1, a, 0, 0); }
+size_t ls_cloud_normals_batch_workspace_bytes(int P, long long a_total) { return near_bytes(true, P, a_total, 0, 0); }
 
 int ls_cloud_nearest_f32(const float* A, long long a, const float* B, long long b, const float* g, float radius, int32_t* nn_idx, float* nn_d2,
                          long long* counts, double* sum_d2, int* status_out, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* op = "cloud_nearest";
-    int rc = check_common(op, a, b, A, B, nn_idx, nn_d2, counts, sum_d2);
-    if (rc != LS_OK) return rc;
-    float inv, r2;
-    rc = radius_terms(op, 0, radius, &inv, &r2);
-    if (rc != LS_OK) return rc;
-    const size_t need = ls_cloud_nearest_workspace_bytes(a, b);
-    if (!workspace || workspace_bytes < need) {
-        set_error("%s: workspace %zu < required %zu (ls_cloud_nearest_workspace_bytes(%lld, %lld))", op, workspace ? workspace_bytes : (size_t)0, need,
-                  a, b);
-        return LS_ERR_WORKSPACE;
-    }
-    const Ws w = layout(workspace, 0, 1, a, b);
-    return nearest_launch(OneNear{B, a, b, g, inv, r2}, 1, A, a, b, chunks_of(b), w, nn_idx, nn_d2, counts, sum_d2, status_out, (hipStream_t)stream);
-}
-
-size_t ls_cloud_nearest_batch_workspace_bytes(int P, long long a_total, long long b_total) {
-    if (P < 1 || a_total < 0 || b_total < 0 || a_total + b_total > INT_MAX) return 0;
-    return layout(nullptr, (size_t)OFF_ARRAYS * (P + 1), P, a_total, b_total).bytes;
+    const NearCall c = NearCall::one("cloud_nearest", A, a, B, b, g, &radius, 0, workspace, workspace_bytes, stream);
+    return nearest_entry(c, nn_idx, nn_d2, counts, sum_d2, status_out);
 }
 
 int ls_cloud_nearest_batch_f32(int P, const float* A, long long a_total, const long long* a_off, const float* B, long long b_total,
                                const long long* b_off, const float* g, const float* radius, int32_t* nn_idx, float* nn_d2, long long* counts,
                                double* sum_d2, int* status_out, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* op = "cloud_nearest_batch";
-    BatchHost h;
-    int rc = check_batch(op, P, A, a_total, a_off, B, b_total, b_off, radius, nn_idx, nn_d2, counts, sum_d2, &h);
-    if (rc != LS_OK) return rc;
-    const size_t need = ls_cloud_nearest_batch_workspace_bytes(P, a_total, b_total);
-    if (!workspace || workspace_bytes < need) {
-        set_error("%s: workspace %zu < required %zu (ls_cloud_nearest_batch_workspace_bytes(%d, %lld, %lld))", op,
-                  workspace ? workspace_bytes : (size_t)0, need, P, a_total, b_total);
-        return LS_ERR_WORKSPACE;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const Ws w = layout(workspace, (size_t)OFF_ARRAYS * (P + 1), P, a_total, b_total);
-    rc = upload_batch(w, P, a_off, b_off, h, st);
-    if (rc != LS_OK) return rc;
-    return nearest_launch(RaggedNear{B, g, w.offs, w.inv, w.r2, P}, P, A, a_total, b_total, h.q_off[P], w, nn_idx, nn_d2, counts, sum_d2, status_out,
-                          st);
-}
-
-size_t ls_cloud_icp_workspace_bytes(long long a, long long b) {
-    if (a < 0 || b < 0 || a + b > INT_MAX) return 0;
-    return layout(nullptr, 0, 1, a, b, PointMetric::N_MOM).bytes;
+    const NearCall c = NearCall::ragged("cloud_nearest_batch", P, A, a_total, a_off, B, b_total, b_off, g, radius, 0, workspace, workspace_bytes, stream);
+    return nearest_entry(c, nn_idx, nn_d2, counts, sum_d2, status_out);
 }
 
 int ls_cloud_icp_f32(const float* A, long long a, const float* B, long long b, const float* g0, float radius, int max_iter, double rel_thr,
                      int min_matched, float* g_out, int32_t* stop, int32_t* iters, int32_t* nn_idx, float* nn_d2, long long* counts, double* sum_d2,
                      int* status_out, float* g_trace, double* stat_trace, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* op = "cloud_icp";
+    const NearCall c = NearCall::one("cloud_icp", A, a, B, b, nullptr, &radius, PointMetric::N_MOM, workspace, workspace_bytes, stream);
     const IcpArgs I{max_iter, rel_thr, min_matched, g_out, stop, iters, g_trace, stat_trace};
-    int rc = check_common(op, a, b, A, B, nn_idx, nn_d2, counts, sum_d2);
-    if (rc != LS_OK) return rc;
-    float inv, r2;
-    rc = radius_terms(op, 0, radius, &inv, &r2);
-    if (rc != LS_OK) return rc;
-    rc = check_icp(op, I);
-    if (rc != LS_OK) return rc;
-    const size_t need = ls_cloud_icp_workspace_bytes(a, b);
-    if (!workspace || workspace_bytes < need) {
-        set_error("%s: workspace %zu < required %zu (ls_cloud_icp_workspace_bytes(%lld, %lld))", op, workspace ? workspace_bytes : (size_t)0, need, a,
-                  b);
-        return LS_ERR_WORKSPACE;
-    }
-    const Ws w = layout(workspace, 0, 1, a, b, PointMetric::N_MOM);
-    return icp_launch<PointMetric>(OneNear{B, a, b, nullptr, inv, r2}, 1, A, a, chunks_of(b), g0, I, w, nn_idx, nn_d2, counts, sum_d2, status_out,
-                      (hipStream_t)stream);
-}
-
-size_t ls_cloud_icp_batch_workspace_bytes(int P, long long a_total, long long b_total) {
-    if (P < 1 || a_total < 0 || b_total < 0 || a_total + b_total > INT_MAX) return 0;
-    return layout(nullptr, (size_t)OFF_ARRAYS * (P + 1), P, a_total, b_total, PointMetric::N_MOM).bytes;
+    return icp_entry<PointMetric>(c, g0, I, nn_idx, nn_d2, counts, sum_d2, status_out);
 }
 
 int ls_cloud_icp_batch_f32(int P, const float* A, long long a_total, const long long* a_off, const float* B, long long b_total,
                            const long long* b_off, const float* g0, const float* radius, int max_iter, double rel_thr, int min_matched,
                            float* g_out, int32_t* stop, int32_t* iters, int32_t* nn_idx, float* nn_d2, long long* counts, double* sum_d2,
                            int* status_out, float* g_trace, double* stat_trace, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* op = "cloud_icp_batch";
+    const NearCall c = NearCall::ragged("cloud_icp_batch", P, A, a_total, a_off, B, b_total, b_off, nullptr, radius, PointMetric::N_MOM, workspace,
+                                        workspace_bytes, stream);
     const IcpArgs I{max_iter, rel_thr, min_matched, g_out, stop, iters, g_trace, stat_trace};
-    BatchHost h;
-    int rc = check_batch(op, P, A, a_total, a_off, B, b_total, b_off, radius, nn_idx, nn_d2, counts, sum_d2, &h);
-    if (rc != LS_OK) return rc;
-    rc = check_icp(op, I);
-    if (rc != LS_OK) return rc;
-    const size_t need = ls_cloud_icp_batch_workspace_bytes(P, a_total, b_total);
-    if (!workspace || workspace_bytes < need) {
-        set_error("%s: workspace %zu < required %zu (ls_cloud_icp_batch_workspace_bytes(%d, %lld, %lld))", op,
-                  workspace ? workspace_bytes : (size_t)0, need, P, a_total, b_total);
-        return LS_ERR_WORKSPACE;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const Ws w = layout(workspace, (size_t)OFF_ARRAYS * (P + 1), P, a_total, b_total, PointMetric::N_MOM);
-    rc = upload_batch(w, P, a_off, b_off, h, st);
-    if (rc != LS_OK) return rc;
-    return icp_launch<PointMetric>(RaggedNear{B, nullptr, w.offs, w.inv, w.r2, P}, P, A, a_total, h.q_off[P], g0, I, w, nn_idx, nn_d2, counts, sum_d2, status_out,
-                      st);
-}
-
-size_t ls_cloud_icp_plane_workspace_bytes(long long a, long long b) {
-    if (a < 0 || b < 0 || a + b > INT_MAX) return 0;
-    return layout(nullptr, 0, 1, a, b, PlaneMetric::N_MOM).bytes;
+    return icp_entry<PointMetric>(c, g0, I, nn_idx, nn_d2, counts, sum_d2, status_out);
 }
 
 int ls_cloud_icp_plane_f32(const float* A, const float* N, long long a, const float* B, long long b, const float* g0, float radius, int max_iter,
                            double rel_thr, int min_matched, float* g_out, int32_t* stop, int32_t* iters, int32_t* nn_idx, float* nn_d2,
                            long long* counts, double* sum_d2, long long* planar, double* sum_rho2, int* status_out, float* g_trace,
                            double* stat_trace, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* op = "cloud_icp_plane";
+    const NearCall c = NearCall::one("cloud_icp_plane", A, a, B, b, nullptr, &radius, PlaneMetric::N_MOM, workspace, workspace_bytes, stream);
     const IcpArgs I{max_iter, rel_thr, min_matched, g_out, stop, iters, g_trace, stat_trace, N, planar, sum_rho2};
-    int rc = check_common(op, a, b, A, B, nn_idx, nn_d2, counts, sum_d2);
-    if (rc != LS_OK) return rc;
-    rc = check_plane(op, a, I);
-    if (rc != LS_OK) return rc;
-    float inv, r2;
-    rc = radius_terms(op, 0, radius, &inv, &r2);
-    if (rc != LS_OK) return rc;
-    rc = check_icp(op, I);
-    if (rc != LS_OK) return rc;
-    const size_t need = ls_cloud_icp_plane_workspace_bytes(a, b);
-    if (!workspace || workspace_bytes < need) {
-        set_error("%s: workspace %zu < required %zu (ls_cloud_icp_plane_workspace_bytes(%lld, %lld))", op, workspace ? workspace_bytes : (size_t)0,
-                  need, a, b);
-        return LS_ERR_WORKSPACE;
-    }
-    const Ws w = layout(workspace, 0, 1, a, b, PlaneMetric::N_MOM);
-    return icp_launch<PlaneMetric>(OneNear{B, a, b, nullptr, inv, r2}, 1, A, a, chunks_of(b), g0, I, w, nn_idx, nn_d2, counts, sum_d2, status_out,
-                                   (hipStream_t)stream);
-}
-
-size_t ls_cloud_icp_plane_batch_workspace_bytes(int P, long long a_total, long long b_total) {
-    if (P < 1 || a_total < 0 || b_total < 0 || a_total + b_total > INT_MAX) return 0;
-    return layout(nullptr, (size_t)OFF_ARRAYS * (P + 1), P, a_total, b_total, PlaneMetric::N_MOM).bytes;
+    return icp_entry<PlaneMetric>(c, g0, I, nn_idx, nn_d2, counts, sum_d2, status_out);
 }
 
 int ls_cloud_icp_plane_batch_f32(int P, const float* A, const float* N, long long a_total, const long long* a_off, const float* B,
@@ -1048,87 +1001,25 @@ int ls_cloud_icp_plane_batch_f32(int P, const float* A, const float* N, long lon
                                  int min_matched, float* g_out, int32_t* stop, int32_t* iters, int32_t* nn_idx, float* nn_d2, long long* counts,
                                  double* sum_d2, long long* planar, double* sum_rho2, int* status_out, float* g_trace, double* stat_trace,
                                  void* workspace, size_t workspace_bytes, void* stream) {
-    const char* op = "cloud_icp_plane_batch";
+    const NearCall c = NearCall::ragged("cloud_icp_plane_batch", P, A, a_total, a_off, B, b_total, b_off, nullptr, radius, PlaneMetric::N_MOM,
+                                        workspace, workspace_bytes, stream);
     const IcpArgs I{max_iter, rel_thr, min_matched, g_out, stop, iters, g_trace, stat_trace, N, planar, sum_rho2};
-    BatchHost h;
-    int rc = check_batch(op, P, A, a_total, a_off, B, b_total, b_off, radius, nn_idx, nn_d2, counts, sum_d2, &h);
-    if (rc != LS_OK) return rc;
-    rc = check_plane(op, a_total, I);
-    if (rc != LS_OK) return rc;
-    rc = check_icp(op, I);
-    if (rc != LS_OK) return rc;
-    const size_t need = ls_cloud_icp_plane_batch_workspace_bytes(P, a_total, b_total);
-    if (!workspace || workspace_bytes < need) {
-        set_error("%s: workspace %zu < required %zu (ls_cloud_icp_plane_batch_workspace_bytes(%d, %lld, %lld))", op,
-                  workspace ? workspace_bytes : (size_t)0, need, P, a_total, b_total);
-        return LS_ERR_WORKSPACE;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const Ws w = layout(workspace, (size_t)OFF_ARRAYS * (P + 1), P, a_total, b_total, PlaneMetric::N_MOM);
-    rc = upload_batch(w, P, a_off, b_off, h, st);
-    if (rc != LS_OK) return rc;
-    return icp_launch<PlaneMetric>(RaggedNear{B, nullptr, w.offs, w.inv, w.r2, P}, P, A, a_total, h.q_off[P], g0, I, w, nn_idx, nn_d2, counts,
-                                   sum_d2, status_out, st);
-}
-
-size_t ls_cloud_normals_workspace_bytes(long long a) {
-    if (a < 0 || a > INT_MAX) return 0;
-    return layout(nullptr, 0, 1, a, 0).bytes;
+    return icp_entry<PlaneMetric>(c, g0, I, nn_idx, nn_d2, counts, sum_d2, status_out);
 }
 
 int ls_cloud_normals_f32(const float* A, long long a, float radius, int min_nbrs, float* normals, int32_t* nbr_cnt, float* variation,
                          long long* counts, int* status_out, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* op = "cloud_normals";
-    int rc = check_normals(op, a, A, min_nbrs, normals, nbr_cnt, variation, counts);
-    if (rc != LS_OK) return rc;
-    float inv, r2;
-    rc = radius_terms(op, 0, radius, &inv, &r2);
-    if (rc != LS_OK) return rc;
-    const size_t need = ls_cloud_normals_workspace_bytes(a);
-    if (!workspace || workspace_bytes < need) {
-        set_error("%s: workspace %zu < required %zu (ls_cloud_normals_workspace_bytes(%lld))", op, workspace ? workspace_bytes : (size_t)0, need, a);
-        return LS_ERR_WORKSPACE;
-    }
-    const Ws w = layout(workspace, 0, 1, a, 0);
-    return normals_launch(OneNear{nullptr, a, 0, nullptr, inv, r2}, 1, A, a, min_nbrs, w, normals, nbr_cnt, variation, counts, status_out,
-                          (hipStream_t)stream);
-}
-
-size_t ls_cloud_normals_batch_workspace_bytes(int P, long long a_total) {
-    if (P < 1 || a_total < 0 || a_total > INT_MAX) return 0;
-    return layout(nullptr, (size_t)OFF_ARRAYS * (P + 1), P, a_total, 0).bytes;
+    NearCall c = NearCall::one("cloud_normals", A, a, nullptr, 0, nullptr, &radius, 0, workspace, workspace_bytes, stream);
+    c.has_b = false;
+    return normals_entry(c, min_nbrs, normals, nbr_cnt, variation, counts, status_out);
 }
 
 int ls_cloud_normals_batch_f32(int P, const float* A, long long a_total, const long long* a_off, const float* radius, int min_nbrs,
                                float* normals, int32_t* nbr_cnt, float* variation, long long* counts, int* status_out, void* workspace,
                                size_t workspace_bytes, void* stream) {
-    const char* op = "cloud_normals_batch";
-    LS_REQUIRE(P >= 1, "%s: P must be at least 1, got %d", op, P);
-    int rc = check_normals(op, a_total, A, min_nbrs, normals, nbr_cnt, variation, counts);
-    if (rc != LS_OK) return rc;
-    rc = check_ranges(op, "problem", "a_off", P, a_off, a_total, INT_MAX);
-    if (rc != LS_OK) return rc;
-    LS_REQUIRE(radius, "%s: null radius", op);
-    BatchHost h;                                                         // no queries: every problem has no rows of B and no chunks
-    h.q_off.assign(P + 1, 0);
-    h.inv.resize(P);
-    h.r2.resize(P);
-    for (int p = 0; p < P; ++p) {
-        rc = radius_terms(op, p, radius[p], &h.inv[p], &h.r2[p]);
-        if (rc != LS_OK) return rc;
-    }
-    const size_t need = ls_cloud_normals_batch_workspace_bytes(P, a_total);
-    if (!workspace || workspace_bytes < need) {
-        set_error("%s: workspace %zu < required %zu (ls_cloud_normals_batch_workspace_bytes(%d, %lld))", op,
-                  workspace ? workspace_bytes : (size_t)0, need, P, a_total);
-        return LS_ERR_WORKSPACE;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const Ws w = layout(workspace, (size_t)OFF_ARRAYS * (P + 1), P, a_total, 0);
-    rc = upload_batch(w, P, a_off, h.q_off.data(), h, st);
-    if (rc != LS_OK) return rc;
-    return normals_launch(RaggedNear{nullptr, nullptr, w.offs, w.inv, w.r2, P}, P, A, a_total, min_nbrs, w, normals, nbr_cnt, variation, counts,
-                          status_out, st);
+    NearCall c = NearCall::ragged("cloud_normals_batch", P, A, a_total, a_off, nullptr, 0, nullptr, nullptr, radius, 0, workspace, workspace_bytes, stream);
+    c.has_b = false;
+    return normals_entry(c, min_nbrs, normals, nbr_cnt, variation, counts, status_out);
 }
 
 }  // extern "C"

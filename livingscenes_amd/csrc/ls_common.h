@@ -69,7 +69,7 @@ struct GemmAux {
 
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
-// the finaliser of splitmix64: the bit mixer of the bounded hash tables (meshcluster.hip, cloudmerge.hip) and of the counter-based uniforms (meshmetrics.hip)
+// the finaliser of splitmix64: the bit mixer of the bounded hash tables (meshcluster.hip; cloud_grid.h for cloudmerge.hip and cloudnear.hip) and of the counter-based uniforms (meshmetrics.hip)
 __host__ __device__ inline unsigned long long mix64(unsigned long long z) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;

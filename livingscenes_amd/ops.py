@@ -813,14 +813,96 @@ def mesh_sample_batch(meshes, counts, seeds=None):
     return list(zip(torch.split(pts, counts), torch.split(face, counts)))
 
 
-# ------------------------------------------------------------------------------------------------ scene memory (csrc/cloudmerge.hip)
-def _merge_cloud(x, what):
+# ------------------------------------------------------------------------------------------------ scene memory (csrc/cloud_grid.h, cloudmerge.hip, cloudnear.hip)
+# The ten wrappers share one binding scheme: _cloud / _pose / _poses / _per_problem check the arguments, _pack puts a list of clouds back
+# to back, _Meta holds the per-problem outputs that the host reads, and _icp_result assembles what the four ICP wrappers return.
+def _cloud(x, what, op):
     if not torch.is_tensor(x) or x.device.type != "cuda" or x.dtype != torch.float32:
         kind = f"{x.device.type} {x.dtype}" if torch.is_tensor(x) else type(x).__name__
-        raise _lib.LsError(f"cloud_merge: {what} must be an fp32 HIP (cuda) tensor, got {kind}: the MI355X path has no CPU fallback and converts nothing")
+        raise _lib.LsError(f"{op}: {what} must be an fp32 HIP (cuda) tensor, got {kind}: the MI355X path has no CPU fallback and converts nothing")
     if x.dim() != 2 or x.shape[1] != 3:
-        raise ValueError(f"cloud_merge: {what} is [n, 3], got {tuple(x.shape)}")
+        raise ValueError(f"{op}: {what} is [n, 3], got {tuple(x.shape)}")
     return x.contiguous()
+
+
+def _pose(g, op, dev):
+    """the pose of a single problem: [3,4] or [4,4] (None stays None) -> [3,4] fp32 on dev"""
+    if g is None:
+        return None
+    if not torch.is_tensor(g) or tuple(g.shape) not in ((3, 4), (4, 4)):
+        raise ValueError(f"{op}: g must be [3,4] or [4,4], got {tuple(g.shape) if torch.is_tensor(g) else type(g).__name__}")
+    return _f32(g.to(dev)[:3, :])
+
+
+def _poses(g, op, P, dev):
+    """the poses of a batch: [P,3,4] or [P,4,4] (None stays None) -> [P,3,4] fp32 on dev"""
+    if g is None:
+        return None
+    if not torch.is_tensor(g) or g.dim() != 3 or g.shape[0] != P or g.shape[1] not in (3, 4) or g.shape[2] != 4:
+        raise ValueError(f"{op}: g must be [P,3,4] or [P,4,4] with P = {P}, got {tuple(g.shape) if torch.is_tensor(g) else type(g).__name__}")
+    return _f32(g.to(dev)[:, :3, :])
+
+
+def _per_problem(v, P, op, noun):
+    """one value or P values -> host fp32 [P]"""
+    v = np.full(P, float(v), dtype=np.float32) if np.ndim(v) == 0 else np.ascontiguousarray(v, dtype=np.float32).reshape(-1)
+    if v.shape[0] != P:
+        raise ValueError(f"{op}: {v.shape[0]} {noun} for {P} problems")
+    return v
+
+
+def _pack(xs):
+    """a list of clouds -> (the clouds back to back, host int64 offsets)"""
+    return (torch.cat(xs, 0) if len(xs) > 1 else xs[0]), _offsets([x.shape[0] for x in xs])
+
+
+def _pairs(op, As, Bs, g, edge, observations="observations", edges="radii"):
+    """the argument checks and the packing of a ragged batch of (kept cloud, observation) problems -> (P, dev, A, a_off, B, b_off, edges, g)"""
+    As, Bs = [_cloud(x, "A", op) for x in As], [_cloud(x, "B", op) for x in Bs]
+    P = len(As)
+    if len(Bs) != P:
+        raise ValueError(f"{op}: {P} kept clouds for {len(Bs)} {observations}")
+    if P == 0:
+        raise ValueError(f"{op}: no problem given")
+    dev = As[0].device
+    edge = _per_problem(edge, P, op, edges)
+    g = _poses(g, op, P, dev)
+    return (P, dev) + _pack(As) + _pack(Bs) + (edge, g)
+
+
+class _Meta:
+    """The per-problem outputs of a call that the host reads, packed into ONE int64 device tensor -- one host read per call.  fields:
+    (name, dtype, entries per problem[, further entries]) in their order in the tensor, the 8-byte ones first."""
+
+    def __init__(self, P, dev, fields):
+        self.P, self.at, n = P, {}, 0
+        for name, dtype, per, *more in fields:
+            count = per * P + sum(more)
+            self.at[name] = (n, np.dtype(dtype), count, per)
+            n += count * np.dtype(dtype).itemsize
+        self.buf = torch.empty((n + 7) // 8, dtype=torch.int64, device=dev)
+
+    def ptr(self, name):
+        return ctypes.c_void_p(self.buf.data_ptr() + self.at[name][0])
+
+    def read(self, op, name_problem=True):
+        """the host read -> {name: array [P] or [P, per]}; raises on a status that is not LS_OK"""
+        host = self.buf.cpu().numpy().view(np.uint8)
+        out = {}
+        for name, (o, dtype, count, per) in self.at.items():
+            v = host[o:o + count * dtype.itemsize].view(dtype).copy()
+            out[name] = v.reshape(self.P, per) if per > 1 else v
+        st = out.pop("status")
+        if st.any():
+            p = int(np.flatnonzero(st)[0])
+            raise _lib.LsError(f"{op}: " + (f"problem {p}: " if name_problem else "") + f"status {int(st[p])} (the cell table overflowed: a defect)")
+        return out
+
+
+def _cloud_call(dev, name, sizes, *args):
+    """the entry `name` with the scratch that its size query asks for at `sizes`: every entry ends in (workspace, bytes, stream)"""
+    ws = _scratch(getattr(load(), name.replace("_f32", "_workspace_bytes"))(*sizes), dev)
+    call(dev, name, *args, ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev))
 
 
 def cloud_merge_batch(As, Bs, g=None, *, voxel, packed=False):
@@ -829,35 +911,14 @@ def cloud_merge_batch(As, Bs, g=None, *, voxel, packed=False):
     B_p's transformed rows; one is kept iff no earlier candidate of its problem lies in the same voxel (include/livingscenes_hip.h)
     -> list of P (pts [n_p,3], src [n_p] int32: the candidate index, >= a_p: from B), views of one packed tensor; packed=True: (pts, src, off)
     with off the host int64 offsets [P+1].  One call, one host read (the offsets), whatever P."""
-    As, Bs = [_merge_cloud(x, "A") for x in As], [_merge_cloud(x, "B") for x in Bs]
-    P = len(As)
-    if len(Bs) != P:
-        raise ValueError(f"cloud_merge: {P} kept clouds for {len(Bs)} new observations")
-    if P == 0:
-        raise ValueError("cloud_merge: no problem given")
-    dev = As[0].device
-    vox = np.full(P, float(voxel), dtype=np.float32) if np.ndim(voxel) == 0 else np.ascontiguousarray(voxel, dtype=np.float32).reshape(-1)
-    if vox.shape[0] != P:
-        raise ValueError(f"cloud_merge: {vox.shape[0]} voxel edges for {P} problems")
-    if g is not None:
-        if not torch.is_tensor(g) or g.dim() != 3 or g.shape[0] != P or g.shape[1] not in (3, 4) or g.shape[2] != 4:
-            raise ValueError(f"cloud_merge: g must be [P,3,4] or [P,4,4] with P = {P}, got {tuple(g.shape) if torch.is_tensor(g) else type(g).__name__}")
-        g = _f32(g.to(dev)[:, :3, :])
-    A = torch.cat(As, 0) if P > 1 else As[0]
-    B = torch.cat(Bs, 0) if P > 1 else Bs[0]
-    ao, bo = _offsets([x.shape[0] for x in As]), _offsets([x.shape[0] for x in Bs])
+    P, dev, A, ao, B, bo, vox, g = _pairs("cloud_merge", As, Bs, g, voxel, "new observations", "voxel edges")
     n = A.shape[0] + B.shape[0]
     pts = torch.empty(n, 3, dtype=torch.float32, device=dev)
     src = torch.empty(n, dtype=torch.int32, device=dev)
-    meta = torch.empty(P + 1 + (P + 1) // 2, dtype=torch.int64, device=dev)   # out_off [P+1] int64, then status [P] int32: one host read
-    status = ctypes.c_void_p(meta.data_ptr() + (P + 1) * 8)
-    ws = _scratch(load().ls_cloud_merge_batch_workspace_bytes(P, A.shape[0], B.shape[0]), dev)
-    call(dev, "ls_cloud_merge_batch_f32", P, ptr(A), A.shape[0], _hptr(ao), ptr(B), B.shape[0], _hptr(bo), ptr(g), _hptr(vox), ptr(pts), ptr(src),
-         ptr(meta), status, ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev))
-    host = meta.cpu().numpy()
-    off, st = host[:P + 1], host[P + 1:].view(np.int32)[:P]
-    if st.any():
-        raise _lib.LsError(f"cloud_merge: problem {int(np.flatnonzero(st)[0])}: status {int(st[np.flatnonzero(st)[0]])} (the cell table overflowed: a defect)")
+    m = _Meta(P, dev, [("off", np.int64, 1, 1), ("status", np.int32, 1)])
+    _cloud_call(dev, "ls_cloud_merge_batch_f32", (P, A.shape[0], B.shape[0]), P, ptr(A), A.shape[0], _hptr(ao), ptr(B), B.shape[0], _hptr(bo),
+                ptr(g), _hptr(vox), ptr(pts), ptr(src), m.ptr("off"), m.ptr("status"))
+    off = m.read("cloud_merge")["off"]
     n_out = int(off[P])
     if packed:
         return pts[:n_out], src[:n_out], off
@@ -869,74 +930,21 @@ def cloud_merge(A, B, g=None, *, voxel):
     """ls_cloud_merge_f32: the kept cloud A [a,3] and the new observation B [b,3] (fp32 HIP tensors), g [3,4] or [4,4] taking B into A's
     frame (None: identity) -> (pts [n,3], src [n] int32): A's rows, then B's transformed rows, each kept iff no earlier one lies in the same
     voxel of edge `voxel`.  Bit-identical to the same problem inside any cloud_merge_batch."""
-    A, B = _merge_cloud(A, "A"), _merge_cloud(B, "B")
+    op = "cloud_merge"
+    A, B = _cloud(A, "A", op), _cloud(B, "B", op)
     dev = A.device
-    if g is not None:
-        if not torch.is_tensor(g) or tuple(g.shape) not in ((3, 4), (4, 4)):
-            raise ValueError(f"cloud_merge: g must be [3,4] or [4,4], got {tuple(g.shape) if torch.is_tensor(g) else type(g).__name__}")
-        g = _f32(g.to(dev)[:3, :])
+    g = _pose(g, op, dev)
     n = A.shape[0] + B.shape[0]
     pts = torch.empty(n, 3, dtype=torch.float32, device=dev)
     src = torch.empty(n, dtype=torch.int32, device=dev)
-    meta = torch.empty(3, dtype=torch.int64, device=dev)                      # out_off [2], then the status
-    ws = _scratch(load().ls_cloud_merge_workspace_bytes(A.shape[0], B.shape[0]), dev)
-    call(dev, "ls_cloud_merge_f32", ptr(A), A.shape[0], ptr(B), B.shape[0], ptr(g), float(voxel), ptr(pts), ptr(src), ptr(meta),
-         ctypes.c_void_p(meta.data_ptr() + 16), ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev))
-    host = meta.cpu().numpy()
-    if host[2:].view(np.int32)[0] != 0:
-        raise _lib.LsError(f"cloud_merge: status {int(host[2:].view(np.int32)[0])} (the cell table overflowed: a defect)")
-    return pts[:int(host[1])], src[:int(host[1])]
+    m = _Meta(1, dev, [("off", np.int64, 1, 1), ("status", np.int32, 1)])
+    _cloud_call(dev, "ls_cloud_merge_f32", (A.shape[0], B.shape[0]), ptr(A), A.shape[0], ptr(B), B.shape[0], ptr(g), float(voxel), ptr(pts),
+                ptr(src), m.ptr("off"), m.ptr("status"))
+    n_out = int(m.read(op, name_problem=False)["off"][1])
+    return pts[:n_out], src[:n_out]
 
 
-# ------------------------------------------------------------------------------------------------ scene memory: radius search (csrc/cloudnear.hip)
-def _near_cloud(x, what, op="cloud_nearest"):
-    if not torch.is_tensor(x) or x.device.type != "cuda" or x.dtype != torch.float32:
-        kind = f"{x.device.type} {x.dtype}" if torch.is_tensor(x) else type(x).__name__
-        raise _lib.LsError(f"{op}: {what} must be an fp32 HIP (cuda) tensor, got {kind}: the MI355X path has no CPU fallback and converts nothing")
-    if x.dim() != 2 or x.shape[1] != 3:
-        raise ValueError(f"{op}: {what} is [n, 3], got {tuple(x.shape)}")
-    return x.contiguous()
-
-
-def _near_meta(meta, P, op="cloud_nearest"):
-    """the one host read of a call: counts [P,3] int64, sum_d2 [P] float64, status [P] int32 and the int32 words after it from the int64
-    words of `meta`"""
-    host = meta.cpu().numpy()
-    tail = host[4 * P:].view(np.int32)
-    st = tail[:P]
-    if st.any():
-        raise _lib.LsError(f"{op}: problem {int(np.flatnonzero(st)[0])}: status {int(st[np.flatnonzero(st)[0]])} (the cell table overflowed: a defect)")
-    return host[:3 * P].reshape(P, 3).copy(), host[3 * P:4 * P].view(np.float64).copy(), tail[P:].copy()
-
-
-def _near_batch_args(op, As, Bs, g, radius):
-    """the argument checks and the packing of a ragged batch of (kept cloud, observation) problems -> (P, dev, A, B, a_off, b_off, radii, g)"""
-    As, Bs = [_near_cloud(x, "A", op) for x in As], [_near_cloud(x, "B", op) for x in Bs]
-    P = len(As)
-    if len(Bs) != P:
-        raise ValueError(f"{op}: {P} kept clouds for {len(Bs)} observations")
-    if P == 0:
-        raise ValueError(f"{op}: no problem given")
-    dev = As[0].device
-    rad = np.full(P, float(radius), dtype=np.float32) if np.ndim(radius) == 0 else np.ascontiguousarray(radius, dtype=np.float32).reshape(-1)
-    if rad.shape[0] != P:
-        raise ValueError(f"{op}: {rad.shape[0]} radii for {P} problems")
-    if g is not None:
-        if not torch.is_tensor(g) or g.dim() != 3 or g.shape[0] != P or g.shape[1] not in (3, 4) or g.shape[2] != 4:
-            raise ValueError(f"{op}: g must be [P,3,4] or [P,4,4] with P = {P}, got {tuple(g.shape) if torch.is_tensor(g) else type(g).__name__}")
-        g = _f32(g.to(dev)[:, :3, :])
-    A = torch.cat(As, 0) if P > 1 else As[0]
-    B = torch.cat(Bs, 0) if P > 1 else Bs[0]
-    return P, dev, A, B, _offsets([x.shape[0] for x in As]), _offsets([x.shape[0] for x in Bs]), rad, g
-
-
-def _near_one_args(op, A, B, g):
-    A, B = _near_cloud(A, "A", op), _near_cloud(B, "B", op)
-    if g is not None:
-        if not torch.is_tensor(g) or tuple(g.shape) not in ((3, 4), (4, 4)):
-            raise ValueError(f"{op}: g must be [3,4] or [4,4], got {tuple(g.shape) if torch.is_tensor(g) else type(g).__name__}")
-        g = _f32(g.to(A.device)[:3, :])
-    return A, B, g
+_NEAR_META = [("counts", np.int64, 3), ("sum_d2", np.float64, 1), ("status", np.int32, 1)]
 
 
 def cloud_nearest_batch(As, Bs, g=None, *, radius, packed=False):
@@ -947,52 +955,77 @@ def cloud_nearest_batch(As, Bs, g=None, *, radius, packed=False):
     counts: host int64 [3] = finite queries, queries with a neighbour, targets that are somebody's neighbour; sum_d2: float, the float64 sum
     of the finite d2), idx / d2 views of one packed tensor; packed=True: (idx, d2, counts [P,3], sum_d2 [P], b_off) with the host int64
     query offsets [P+1].  One call, one host read (counts, sums and status), whatever P."""
-    P, dev, A, B, ao, bo, rad, g = _near_batch_args("cloud_nearest", As, Bs, g, radius)
+    P, dev, A, ao, B, bo, rad, g = _pairs("cloud_nearest", As, Bs, g, radius)
     idx = torch.empty(B.shape[0], dtype=torch.int32, device=dev)
     d2 = torch.empty(B.shape[0], dtype=torch.float32, device=dev)
-    meta = torch.empty(4 * P + (P + 1) // 2, dtype=torch.int64, device=dev)   # counts [P,3] int64, sum_d2 [P] float64, status [P] int32
-    ws = _scratch(load().ls_cloud_nearest_batch_workspace_bytes(P, A.shape[0], B.shape[0]), dev)
-    call(dev, "ls_cloud_nearest_batch_f32", P, ptr(A), A.shape[0], _hptr(ao), ptr(B), B.shape[0], _hptr(bo), ptr(g), _hptr(rad), ptr(idx), ptr(d2),
-         ptr(meta), ctypes.c_void_p(meta.data_ptr() + 24 * P), ctypes.c_void_p(meta.data_ptr() + 32 * P), ptr(ws), 0 if ws is None else ws.numel(),
-         stream_ptr(dev))
-    counts, sums, _ = _near_meta(meta, P)
+    m = _Meta(P, dev, _NEAR_META)
+    _cloud_call(dev, "ls_cloud_nearest_batch_f32", (P, A.shape[0], B.shape[0]), P, ptr(A), A.shape[0], _hptr(ao), ptr(B), B.shape[0], _hptr(bo),
+                ptr(g), _hptr(rad), ptr(idx), ptr(d2), m.ptr("counts"), m.ptr("sum_d2"), m.ptr("status"))
+    f = m.read("cloud_nearest")
     if packed:
-        return idx, d2, counts, sums, bo
+        return idx, d2, f["counts"], f["sum_d2"], bo
     sizes = np.diff(bo).tolist()
-    return [(i, d, counts[p], float(sums[p])) for p, (i, d) in enumerate(zip(torch.split(idx, sizes), torch.split(d2, sizes)))]
+    return [(i, d, f["counts"][p], float(f["sum_d2"][p])) for p, (i, d) in enumerate(zip(torch.split(idx, sizes), torch.split(d2, sizes)))]
 
 
 def cloud_nearest(A, B, g=None, *, radius):
     """ls_cloud_nearest_f32: the kept cloud A [a,3] (targets) and the observation B [b,3] (queries; fp32 HIP tensors), g [3,4] or [4,4]
     taking B into A's frame (None: identity) -> (idx [b] int32, d2 [b] fp32, counts host int64 [3], sum_d2 float) as cloud_nearest_batch
     describes them.  Bit-identical to the same problem inside any cloud_nearest_batch."""
-    A, B, g = _near_one_args("cloud_nearest", A, B, g)
+    op = "cloud_nearest"
+    A, B = _cloud(A, "A", op), _cloud(B, "B", op)
     dev = A.device
+    g = _pose(g, op, dev)
     idx = torch.empty(B.shape[0], dtype=torch.int32, device=dev)
     d2 = torch.empty(B.shape[0], dtype=torch.float32, device=dev)
-    meta = torch.empty(5, dtype=torch.int64, device=dev)                      # counts [3], sum_d2, then the status
-    ws = _scratch(load().ls_cloud_nearest_workspace_bytes(A.shape[0], B.shape[0]), dev)
-    call(dev, "ls_cloud_nearest_f32", ptr(A), A.shape[0], ptr(B), B.shape[0], ptr(g), float(radius), ptr(idx), ptr(d2), ptr(meta),
-         ctypes.c_void_p(meta.data_ptr() + 24), ctypes.c_void_p(meta.data_ptr() + 32), ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev))
-    counts, sums, _ = _near_meta(meta, 1)
-    return idx, d2, counts[0], float(sums[0])
+    m = _Meta(1, dev, _NEAR_META)
+    _cloud_call(dev, "ls_cloud_nearest_f32", (A.shape[0], B.shape[0]), ptr(A), A.shape[0], ptr(B), B.shape[0], ptr(g), float(radius), ptr(idx),
+                ptr(d2), m.ptr("counts"), m.ptr("sum_d2"), m.ptr("status"))
+    f = m.read(op)
+    return idx, d2, f["counts"][0], float(f["sum_d2"][0])
 
 
 # ------------------------------------------------------------------------------------------------ scene memory: trimmed ICP on the search's grid
 ICP_STOP = ("converged", "max_iter", "starved", "degenerate")   # LS_ICP_* of include/livingscenes_hip.h, by value
 
 
-def _icp_buffers(P, b, dev, max_iter, trace):
-    """the outputs of an ICP call: idx, d2, g_out, the traces (or None) and `meta` -- counts [P,3] int64, sum_d2 [P] float64, then status, stop
-    and iters [P] int32 each -- with the pointers into it: one host read per call"""
+_PLANE_META = [("planar", np.int64, 1), ("sum_rho2", np.float64, 1)]
+_ICP_SCALARS = {"stop": int, "iters": int, "sum_d2": float, "planar": int, "sum_rho2": float}   # what a per-problem dict holds as Python numbers
+
+
+def _icp_result(out, bo, traces, packed):
+    """what an ICP wrapper returns, for either metric.  out: the packed outputs by name, device tensors and host arrays [P, ...];
+    packed: `out` with b_off (and the traces) -> else the list of P dicts, idx / d2 split at the query offsets bo."""
+    if packed:
+        out["b_off"] = bo
+    out.update(traces)
+    if packed:
+        return out
+    sizes = np.diff(bo).tolist()
+    out["idx"], out["d2"] = torch.split(out["idx"], sizes), torch.split(out["d2"], sizes)
+    return [{k: _ICP_SCALARS[k](v[p]) if k in _ICP_SCALARS else v[p] for k, v in out.items()} for p in range(len(sizes))]
+
+
+def _icp(op, name, head, sizes, P, dev, bo, max_iter, rel_thr, min_matched, trace, packed, plane=False):
+    """The call of the ICP entry `name` of the operator `op`.  head: the entry's arguments up to the radius, sizes: those of its size query,
+    bo: the host offsets of the queries; plane: the point-to-plane metric, with planar / sum_rho2 and five columns of statistics."""
+    max_iter, b = int(max_iter), int(bo[-1])
     idx = torch.empty(b, dtype=torch.int32, device=dev)
     d2 = torch.empty(b, dtype=torch.float32, device=dev)
     g_out = torch.empty(P, 3, 4, dtype=torch.float32, device=dev)
-    meta = torch.empty(4 * P + (3 * P + 1) // 2, dtype=torch.int64, device=dev)
-    at = [ctypes.c_void_p(meta.data_ptr() + o) for o in (0, 24 * P, 32 * P, 36 * P, 40 * P)]   # counts, sum_d2, status, stop, iters
-    g_trace = torch.zeros(P, max_iter + 1, 12, dtype=torch.float32, device=dev) if trace else None
-    stat_trace = torch.zeros(P, max_iter + 1, 3, dtype=torch.float64, device=dev) if trace else None
-    return idx, d2, g_out, meta, at, g_trace, stat_trace
+    traces = {}
+    if trace:
+        traces = {"g_trace": torch.zeros(P, max(max_iter, 0) + 1, 12, dtype=torch.float32, device=dev),
+                  "stat_trace": torch.zeros(P, max(max_iter, 0) + 1, 5 if plane else 3, dtype=torch.float64, device=dev)}
+    extra = _PLANE_META if plane else []
+    m = _Meta(P, dev, _NEAR_META[:2] + extra + [("status", np.int32, 1), ("stop", np.int32, 1), ("iters", np.int32, 1)])
+    _cloud_call(dev, name, sizes, *head, max_iter, float(rel_thr), int(min_matched), ptr(g_out), m.ptr("stop"), m.ptr("iters"), ptr(idx), ptr(d2),
+                m.ptr("counts"), m.ptr("sum_d2"), *[m.ptr(k) for k, _, _ in extra], m.ptr("status"), ptr(traces.get("g_trace")),
+                ptr(traces.get("stat_trace")))
+    f = m.read(op)
+    out = {"g": g_out, "stop": f["stop"], "iters": f["iters"], "idx": idx, "d2": d2, "counts": f["counts"], "sum_d2": f["sum_d2"]}
+    out.update({k: f[k] for k, _, _ in extra})
+    return _icp_result(out, bo, traces, packed)
 
 
 def cloud_icp_batch(As, Bs, g=None, *, radius, max_iter=100, rel_thr=1e-6, min_matched=3, trace=False, packed=False):
@@ -1009,27 +1042,9 @@ def cloud_icp_batch(As, Bs, g=None, *, radius, max_iter=100, rel_thr=1e-6, min_m
     packed=True: one dict of the packed tensors (g [P,3,4], stop / iters int32 [P], counts [P,3], sum_d2 [P], ...) plus b_off.  One call,
     one host read (counts, sums, status, stop, iters), whatever P and however many iterations."""
     op = "cloud_icp"
-    P, dev, A, B, ao, bo, rad, g = _near_batch_args(op, As, Bs, g, radius)
-    max_iter = int(max_iter)
-    idx, d2, g_out, meta, at, g_trace, stat_trace = _icp_buffers(P, B.shape[0], dev, max(max_iter, 0), trace)
-    ws = _scratch(load().ls_cloud_icp_batch_workspace_bytes(P, A.shape[0], B.shape[0]), dev)
-    call(dev, "ls_cloud_icp_batch_f32", P, ptr(A), A.shape[0], _hptr(ao), ptr(B), B.shape[0], _hptr(bo), ptr(g), _hptr(rad), max_iter,
-         float(rel_thr), int(min_matched), ptr(g_out), at[3], at[4], ptr(idx), ptr(d2), at[0], at[1], at[2], ptr(g_trace), ptr(stat_trace), ptr(ws),
-         0 if ws is None else ws.numel(), stream_ptr(dev))
-    counts, sums, tail = _near_meta(meta, P, op)
-    stop, iters = tail[:P], tail[P:2 * P]
-    if packed:
-        out = {"g": g_out, "stop": stop, "iters": iters, "idx": idx, "d2": d2, "counts": counts, "sum_d2": sums, "b_off": bo}
-        if trace:
-            out.update(g_trace=g_trace, stat_trace=stat_trace)
-        return out
-    sizes = np.diff(bo).tolist()
-    res = []
-    for p, (i, d) in enumerate(zip(torch.split(idx, sizes), torch.split(d2, sizes))):
-        res.append({"g": g_out[p], "stop": int(stop[p]), "iters": int(iters[p]), "idx": i, "d2": d, "counts": counts[p], "sum_d2": float(sums[p])})
-        if trace:
-            res[-1].update(g_trace=g_trace[p], stat_trace=stat_trace[p])
-    return res
+    P, dev, A, ao, B, bo, rad, g = _pairs(op, As, Bs, g, radius)
+    head = (P, ptr(A), A.shape[0], _hptr(ao), ptr(B), B.shape[0], _hptr(bo), ptr(g), _hptr(rad))
+    return _icp(op, "ls_cloud_icp_batch_f32", head, (P, A.shape[0], B.shape[0]), P, dev, bo, max_iter, rel_thr, min_matched, trace, packed)
 
 
 def cloud_icp(A, B, g=None, *, radius, max_iter=100, rel_thr=1e-6, min_matched=3, trace=False):
@@ -1037,37 +1052,22 @@ def cloud_icp(A, B, g=None, *, radius, max_iter=100, rel_thr=1e-6, min_matched=3
     pose taking B into A's frame (None: identity) -> the dict cloud_icp_batch describes.  max_iter = 100 and rel_thr = 1e-6 are ops.icp's
     defaults, pytorch3d's: inherited, not tuned.  Bit-identical to the same problem inside any cloud_icp_batch."""
     op = "cloud_icp"
-    A, B, g = _near_one_args(op, A, B, g)
+    A, B = _cloud(A, "A", op), _cloud(B, "B", op)
     dev = A.device
-    max_iter = int(max_iter)
-    idx, d2, g_out, meta, at, g_trace, stat_trace = _icp_buffers(1, B.shape[0], dev, max(max_iter, 0), trace)
-    ws = _scratch(load().ls_cloud_icp_workspace_bytes(A.shape[0], B.shape[0]), dev)
-    call(dev, "ls_cloud_icp_f32", ptr(A), A.shape[0], ptr(B), B.shape[0], ptr(g), float(radius), max_iter, float(rel_thr), int(min_matched),
-         ptr(g_out), at[3], at[4], ptr(idx), ptr(d2), at[0], at[1], at[2], ptr(g_trace), ptr(stat_trace), ptr(ws), 0 if ws is None else ws.numel(),
-         stream_ptr(dev))
-    counts, sums, tail = _near_meta(meta, 1, op)
-    out = {"g": g_out[0], "stop": int(tail[0]), "iters": int(tail[1]), "idx": idx, "d2": d2, "counts": counts[0], "sum_d2": float(sums[0])}
-    if trace:
-        out.update(g_trace=g_trace[0], stat_trace=stat_trace[0])
-    return out
+    g = _pose(g, op, dev)
+    head = (ptr(A), A.shape[0], ptr(B), B.shape[0], ptr(g), float(radius))
+    return _icp(op, "ls_cloud_icp_f32", head, (A.shape[0], B.shape[0]), 1, dev, _offsets([B.shape[0]]), max_iter, rel_thr, min_matched, trace, False)[0]
 
 
 # ------------------------------------------------------------------------------------------------ scene memory: normals and the point-to-plane ICP
-def _normals_out(P, a, dev):
-    """the outputs of a normals call and `meta` -- counts [P,2] int64, then status [P] int32 -- with the pointer to the status"""
+def _normals(op, name, head, sizes, P, dev, a):
+    """the call of the normals' entry `name` of the operator `op` -> (normals, nbr_cnt, variation, counts [P,2])"""
     normals = torch.empty(a, 3, dtype=torch.float32, device=dev)
     cnt = torch.empty(a, dtype=torch.int32, device=dev)
     var = torch.empty(a, dtype=torch.float32, device=dev)
-    meta = torch.empty(2 * P + (P + 1) // 2, dtype=torch.int64, device=dev)
-    return normals, cnt, var, meta, ctypes.c_void_p(meta.data_ptr() + 16 * P)
-
-
-def _normals_meta(meta, P, op):
-    host = meta.cpu().numpy()
-    st = host[2 * P:].view(np.int32)[:P]
-    if st.any():
-        raise _lib.LsError(f"{op}: problem {int(np.flatnonzero(st)[0])}: status {int(st[np.flatnonzero(st)[0]])} (the cell table overflowed: a defect)")
-    return host[:2 * P].reshape(P, 2).copy()
+    m = _Meta(P, dev, [("counts", np.int64, 2), ("status", np.int32, 1)])
+    _cloud_call(dev, name, sizes, *head, ptr(normals), ptr(cnt), ptr(var), m.ptr("counts"), m.ptr("status"))
+    return normals, cnt, var, m.read(op)["counts"]
 
 
 def cloud_normals_batch(As, *, radius, min_nbrs=5, packed=False):
@@ -1080,21 +1080,15 @@ def cloud_normals_batch(As, *, radius, min_nbrs=5, packed=False):
     int32; variation [a_p] fp32 = lmin / (lmin + lmid + lmax); counts: host int64 [2] = rows with a cell, valid rows), views of packed
     tensors; packed=True: (normals, nbr_cnt, variation, counts [P,2], a_off).  One call, one host read, whatever P."""
     op = "cloud_normals"
-    As = [_near_cloud(x, "A", op) for x in As]
+    As = [_cloud(x, "A", op) for x in As]
     P = len(As)
     if P == 0:
         raise ValueError(f"{op}: no problem given")
     dev = As[0].device
-    rad = np.full(P, float(radius), dtype=np.float32) if np.ndim(radius) == 0 else np.ascontiguousarray(radius, dtype=np.float32).reshape(-1)
-    if rad.shape[0] != P:
-        raise ValueError(f"{op}: {rad.shape[0]} radii for {P} problems")
-    A = torch.cat(As, 0) if P > 1 else As[0]
-    ao = _offsets([x.shape[0] for x in As])
-    normals, cnt, var, meta, status = _normals_out(P, A.shape[0], dev)
-    ws = _scratch(load().ls_cloud_normals_batch_workspace_bytes(P, A.shape[0]), dev)
-    call(dev, "ls_cloud_normals_batch_f32", P, ptr(A), A.shape[0], _hptr(ao), _hptr(rad), int(min_nbrs), ptr(normals), ptr(cnt), ptr(var), ptr(meta),
-         status, ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev))
-    counts = _normals_meta(meta, P, op)
+    rad = _per_problem(radius, P, op, "radii")
+    A, ao = _pack(As)
+    normals, cnt, var, counts = _normals(op, "ls_cloud_normals_batch_f32", (P, ptr(A), A.shape[0], _hptr(ao), _hptr(rad), int(min_nbrs)),
+                                         (P, A.shape[0]), P, dev, A.shape[0])
     if packed:
         return normals, cnt, var, counts, ao
     sizes = np.diff(ao).tolist()
@@ -1106,45 +1100,17 @@ def cloud_normals(A, *, radius, min_nbrs=5):
     host int64 [2]) as cloud_normals_batch describes them (min_nbrs = 5 is not tuned).  Bit-identical to the same problem inside any
     cloud_normals_batch."""
     op = "cloud_normals"
-    A = _near_cloud(A, "A", op)
-    dev = A.device
-    normals, cnt, var, meta, status = _normals_out(1, A.shape[0], dev)
-    ws = _scratch(load().ls_cloud_normals_workspace_bytes(A.shape[0]), dev)
-    call(dev, "ls_cloud_normals_f32", ptr(A), A.shape[0], float(radius), int(min_nbrs), ptr(normals), ptr(cnt), ptr(var), ptr(meta), status, ptr(ws),
-         0 if ws is None else ws.numel(), stream_ptr(dev))
-    return normals, cnt, var, _normals_meta(meta, 1, op)[0]
+    A = _cloud(A, "A", op)
+    normals, cnt, var, counts = _normals(op, "ls_cloud_normals_f32", (ptr(A), A.shape[0], float(radius), int(min_nbrs)), (A.shape[0],), 1,
+                                         A.device, A.shape[0])
+    return normals, cnt, var, counts[0]
 
 
 def _plane_normals(x, A, op):
-    x = _near_cloud(x, "N", op)
+    x = _cloud(x, "N", op)
     if x.shape[0] != A.shape[0] or x.device != A.device:
         raise ValueError(f"{op}: N is {tuple(x.shape)} on {x.device} for A {tuple(A.shape)} on {A.device}: one normal row per kept row")
     return x
-
-
-def _plane_buffers(P, b, dev, max_iter, trace):
-    """_icp_buffers for the plane metric: `meta` also holds planar [P] int64 and sum_rho2 [P] float64 before the int32 words, and the
-    statistics trace has five columns"""
-    idx = torch.empty(b, dtype=torch.int32, device=dev)
-    d2 = torch.empty(b, dtype=torch.float32, device=dev)
-    g_out = torch.empty(P, 3, 4, dtype=torch.float32, device=dev)
-    meta = torch.empty(6 * P + (3 * P + 1) // 2, dtype=torch.int64, device=dev)
-    # counts, sum_d2, planar, sum_rho2, status, stop, iters
-    at = [ctypes.c_void_p(meta.data_ptr() + o) for o in (0, 24 * P, 32 * P, 40 * P, 48 * P, 52 * P, 56 * P)]
-    g_trace = torch.zeros(P, max_iter + 1, 12, dtype=torch.float32, device=dev) if trace else None
-    stat_trace = torch.zeros(P, max_iter + 1, 5, dtype=torch.float64, device=dev) if trace else None
-    return idx, d2, g_out, meta, at, g_trace, stat_trace
-
-
-def _plane_meta(meta, P, op):
-    """the one host read: counts [P,3], sum_d2 [P], planar [P], sum_rho2 [P], stop [P], iters [P]"""
-    host = meta.cpu().numpy()
-    tail = host[6 * P:].view(np.int32)
-    st = tail[:P]
-    if st.any():
-        raise _lib.LsError(f"{op}: problem {int(np.flatnonzero(st)[0])}: status {int(st[np.flatnonzero(st)[0]])} (the cell table overflowed: a defect)")
-    return (host[:3 * P].reshape(P, 3).copy(), host[3 * P:4 * P].view(np.float64).copy(), host[4 * P:5 * P].copy(),
-            host[5 * P:6 * P].view(np.float64).copy(), tail[P:2 * P].copy(), tail[2 * P:3 * P].copy())
 
 
 def cloud_icp_plane_batch(As, Ns, Bs, g=None, *, radius, max_iter=100, rel_thr=1e-6, min_matched=6, trace=False, packed=False):
@@ -1159,32 +1125,13 @@ def cloud_icp_plane_batch(As, Ns, Bs, g=None, *, radius, max_iter=100, rel_thr=1
     -> list of P dicts as cloud_icp_batch returns them plus planar (int) and sum_rho2 (float) of the final search; trace=True adds g_trace
     [max_iter+1,12] and stat_trace [max_iter+1,5] = (finite, matched, sum d2, planar, sum rho^2).  packed=True: one dict of packed tensors."""
     op = "cloud_icp_plane"
-    P, dev, A, B, ao, bo, rad, g = _near_batch_args(op, As, Bs, g, radius)
+    P, dev, A, ao, B, bo, rad, g = _pairs(op, As, Bs, g, radius)
     if len(Ns) != P:
         raise ValueError(f"{op}: {P} kept clouds for {len(Ns)} arrays of normals")
-    Ns = [_plane_normals(n, a, op) for n, a in zip(Ns, As)]
-    N = torch.cat(Ns, 0) if P > 1 else Ns[0]
-    max_iter = int(max_iter)
-    idx, d2, g_out, meta, at, g_trace, stat_trace = _plane_buffers(P, B.shape[0], dev, max(max_iter, 0), trace)
-    ws = _scratch(load().ls_cloud_icp_plane_batch_workspace_bytes(P, A.shape[0], B.shape[0]), dev)
-    call(dev, "ls_cloud_icp_plane_batch_f32", P, ptr(A), ptr(N), A.shape[0], _hptr(ao), ptr(B), B.shape[0], _hptr(bo), ptr(g), _hptr(rad), max_iter,
-         float(rel_thr), int(min_matched), ptr(g_out), at[5], at[6], ptr(idx), ptr(d2), at[0], at[1], at[2], at[3], at[4], ptr(g_trace),
-         ptr(stat_trace), ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev))
-    counts, sums, planar, rho2, stop, iters = _plane_meta(meta, P, op)
-    if packed:
-        out = {"g": g_out, "stop": stop, "iters": iters, "idx": idx, "d2": d2, "counts": counts, "sum_d2": sums, "planar": planar,
-               "sum_rho2": rho2, "b_off": bo}
-        if trace:
-            out.update(g_trace=g_trace, stat_trace=stat_trace)
-        return out
-    sizes = np.diff(bo).tolist()
-    res = []
-    for p, (i, d) in enumerate(zip(torch.split(idx, sizes), torch.split(d2, sizes))):
-        res.append({"g": g_out[p], "stop": int(stop[p]), "iters": int(iters[p]), "idx": i, "d2": d, "counts": counts[p], "sum_d2": float(sums[p]),
-                    "planar": int(planar[p]), "sum_rho2": float(rho2[p])})
-        if trace:
-            res[-1].update(g_trace=g_trace[p], stat_trace=stat_trace[p])
-    return res
+    N, _ = _pack([_plane_normals(n, a, op) for n, a in zip(Ns, As)])
+    head = (P, ptr(A), ptr(N), A.shape[0], _hptr(ao), ptr(B), B.shape[0], _hptr(bo), ptr(g), _hptr(rad))
+    return _icp(op, "ls_cloud_icp_plane_batch_f32", head, (P, A.shape[0], B.shape[0]), P, dev, bo, max_iter, rel_thr, min_matched, trace, packed,
+                plane=True)
 
 
 def cloud_icp_plane(A, N, B, g=None, *, radius, max_iter=100, rel_thr=1e-6, min_matched=6, trace=False):
@@ -1192,18 +1139,10 @@ def cloud_icp_plane(A, N, B, g=None, *, radius, max_iter=100, rel_thr=1e-6, min_
     (fp32 HIP tensors), g [3,4] or [4,4] the initial pose (None: identity) -> the dict cloud_icp_plane_batch describes.  Bit-identical to
     the same problem inside any cloud_icp_plane_batch."""
     op = "cloud_icp_plane"
-    A, B, g = _near_one_args(op, A, B, g)
-    N = _plane_normals(N, A, op)
+    A, B = _cloud(A, "A", op), _cloud(B, "B", op)
     dev = A.device
-    max_iter = int(max_iter)
-    idx, d2, g_out, meta, at, g_trace, stat_trace = _plane_buffers(1, B.shape[0], dev, max(max_iter, 0), trace)
-    ws = _scratch(load().ls_cloud_icp_plane_workspace_bytes(A.shape[0], B.shape[0]), dev)
-    call(dev, "ls_cloud_icp_plane_f32", ptr(A), ptr(N), A.shape[0], ptr(B), B.shape[0], ptr(g), float(radius), max_iter, float(rel_thr),
-         int(min_matched), ptr(g_out), at[5], at[6], ptr(idx), ptr(d2), at[0], at[1], at[2], at[3], at[4], ptr(g_trace), ptr(stat_trace), ptr(ws),
-         0 if ws is None else ws.numel(), stream_ptr(dev))
-    counts, sums, planar, rho2, stop, iters = _plane_meta(meta, 1, op)
-    out = {"g": g_out[0], "stop": int(stop[0]), "iters": int(iters[0]), "idx": idx, "d2": d2, "counts": counts[0], "sum_d2": float(sums[0]),
-           "planar": int(planar[0]), "sum_rho2": float(rho2[0])}
-    if trace:
-        out.update(g_trace=g_trace[0], stat_trace=stat_trace[0])
-    return out
+    g = _pose(g, op, dev)
+    N = _plane_normals(N, A, op)
+    head = (ptr(A), ptr(N), A.shape[0], ptr(B), B.shape[0], ptr(g), float(radius))
+    return _icp(op, "ls_cloud_icp_plane_f32", head, (A.shape[0], B.shape[0]), 1, dev, _offsets([B.shape[0]]), max_iter, rel_thr, min_matched, trace,
+                False, plane=True)[0]

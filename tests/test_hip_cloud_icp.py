@@ -14,8 +14,6 @@ device's own traced (f, n, S): the same expression, so the same decision.  The f
 ops.cloud_nearest at g_out and with the twin.  Between the single op and the batch every output is compared bit for bit.  The
 solve_sequence tests run untrained weights with the registration replaced by perturbed ground truth, and make no accuracy claim."""
 import math
-import os
-import re
 
 import numpy as np
 import pytest
@@ -24,29 +22,12 @@ import torch
 import icp_oracle as io
 import merge_oracle as mo
 import nearest_oracle as no
+from cloud_testlib import (CODE_KEYS, GATE_KEYS, REFINE_KEYS, STEP_KEYS, TILE, F, _bits, _dev, _g, _scene, _solver, _t,
+                           small_prior)  # noqa: F401 (small_prior is a fixture)
 from livingscenes_amd import synth
 from test_cloud_icp_cpu import _inv, _pose, _rot, twin_bound, twin_case
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-F = np.float32
-
-
-def _dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-def _t(x):
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 3)).to(_dev())
-
-
-def _g(g):
-    return None if g is None else torch.from_numpy(np.ascontiguousarray(g, dtype=np.float32)).to(_dev())
-
-
-def _bits(x):
-    return np.ascontiguousarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x).view(np.uint32)
 
 
 def _host(res):
@@ -128,14 +109,7 @@ def _final(A, B, r, res, what=""):
     assert abs(res["sum_d2"] - tw[3]) <= int(tw[2][1]) * 2.0 ** -52 * tw[3], (what, res["sum_d2"], tw[3])
 
 
-def _scan_tile():
-    src = open(os.path.join(REPO, "livingscenes_amd", "csrc", "ls_scan.h")).read()
-    t, items = (int(re.search(rf"\b{k}\s*=\s*(\d+)", src).group(1)) for k in ("SCAN_T", "SCAN_ITEMS"))
-    return t * items
-
-
 # ------------------------------------------------------------------------------------------------ size edges, P = 1
-TILE = _scan_tile()
 SIZES = [(0, 0), (0, 5), (5, 0), (2, 2), (3, 3), (300, 255), (300, 256), (300, 257), (TILE // 2, 300), (TILE // 2 + 1, 300), (TILE + 1, 513),
          (2 ** 13 + 1, 2 ** 13 + 1)]
 
@@ -338,11 +312,6 @@ def test_errors_name_the_problem(batch):
 
 
 # ------------------------------------------------------------------------------------------------ the layers above
-def _solver(model, cfg=None):
-    from livingscenes_amd.lib_more.more_solver import More_Solver
-    base = {"shape_priors": {"n_input_point": 128, "prior_name": "chair", "ckpt_dir": ""}, "fps": {"n_init": 1}}
-    base.update(cfg or {})
-    return More_Solver(base, model=model)
 
 
 def _pose_error(T, T_true, pts):
@@ -408,25 +377,6 @@ def test_refine_on_memory_batch():
         solver._refine_on_memory_batch(mems, news[:1], T, 0.04)
     with pytest.raises(ValueError):
         solver._refine_on_memory_batch(mems, news, None, 0.04)
-
-
-@pytest.fixture(scope="module")
-def small_prior():
-    from livingscenes_amd.model_utils import Shape_Prior
-    ecfg, dcfg = synth.small_encoder_cfg(), synth.small_decoder_cfg()
-    ew, dw = synth.make_encoder_weights(ecfg, 4), synth.make_decoder_weights(dcfg, 4)
-    return Shape_Prior.from_state(ecfg, dcfg, ew, dw, device=_dev(), n_pcl=128)
-
-
-def _scene(x):
-    x = x.to(_dev())
-    return {"pc": x.transpose(1, 2).contiguous(), "pc_mask": torch.ones(x.shape[0], 1, x.shape[1], dtype=torch.bool, device=x.device)}
-
-
-STEP_KEYS = {"ref_pc_lst", "rescan_pc_lst", "matches", "registration", "codes", "mesh_lst", "merged_sizes", "n_new_points", "unmatched_rescan"}
-GATE_KEYS = {"overlap", "overlap_rmse", "memory_seen", "rejected"}
-REFINE_KEYS = {"refine_stop", "refine_iters", "registration_init"}
-CODE_KEYS = ("z_so3", "z_inv", "s", "t")
 
 
 def _counted(monkeypatch, solver, truth):

@@ -6,31 +6,16 @@ only tolerance in this file is the coverage bound of the _accumulate_batch test,
 with a kept one (the diagonal is sqrt(3) h), and 1e-5 covers the fp32 transform there and back of coordinates below 4 (a few ulp of 2.4e-7
 each).  The solve_sequence test runs untrained weights and makes no accuracy claim."""
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import merge_oracle as mo
+from cloud_testlib import CODE_KEYS, STEP_KEYS, TILE, _bits, _dev, _pose, _scene, _solver, _t, small_prior  # noqa: F401 (small_prior is a fixture)
 from livingscenes_amd import synth
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-
-
-def _dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-def _t(x):
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 3)).to(_dev())
-
-
-def _bits(x):
-    return np.ascontiguousarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x).view(np.uint32)
 
 
 def _single(A, B, g, h):
@@ -50,24 +35,7 @@ def _check(A, B, g, h, what=""):
     return got
 
 
-def _rot(rng):
-    q, r = np.linalg.qr(rng.standard_normal((3, 3)))
-    q = q * np.sign(np.diag(r))
-    return q * np.sign(np.linalg.det(q))
-
-
-def _pose(rng, t=1.0):
-    return np.concatenate([_rot(rng), rng.uniform(-t, t, (3, 1))], 1).astype(np.float32)
-
-
-def _scan_tile():
-    src = open(os.path.join(REPO, "livingscenes_amd", "csrc", "ls_scan.h")).read()
-    t, items = (int(re.search(rf"\b{k}\s*=\s*(\d+)", src).group(1)) for k in ("SCAN_T", "SCAN_ITEMS"))
-    return t * items
-
-
 # ------------------------------------------------------------------------------------------------ size edges, P = 1
-TILE = _scan_tile()
 K = 13          # the table-size edge: n = 2^K and 2^K + 1 candidates (tables of 2^(K+1) and 2^(K+1) + 2 slots)
 SIZES = [(0, 0), (0, 1), (1, 0), (1, 1), (255, 1), (256, 1), (200, 57)] + \
         [(TILE - 1 - 100, 100), (TILE - 100, 100), (TILE + 1 - 100, 100), (TILE, TILE - 1), (TILE, TILE), (TILE + 1, TILE)] + \
@@ -283,11 +251,6 @@ def test_large_and_idempotent():
 
 
 # ------------------------------------------------------------------------------------------------ the layers above
-def _solver(model, cfg=None):
-    from livingscenes_amd.lib_more.more_solver import More_Solver
-    base = {"shape_priors": {"n_input_point": 128, "prior_name": "chair", "ckpt_dir": ""}, "fps": {"n_init": 1}}
-    base.update(cfg or {})
-    return More_Solver(base, model=model)
 
 
 def test_accumulate_batch_known_pose_covers_the_shape():
@@ -316,24 +279,6 @@ def test_accumulate_batch_known_pose_covers_the_shape():
             assert float(reach) <= math.sqrt(3) * h + 1e-5
     assert solver._accumulate_batch(mems, news, T, voxel=0.05)[0].shape[0] < merged[0].shape[0]          # an explicit voxel goes before the cfg's
     assert _solver(object())._accumulate_batch(mems, news, T)[0].shape[0] > merged[0].shape[0]      # the default voxel, 0.01
-
-
-@pytest.fixture(scope="module")
-def small_prior():
-    from livingscenes_amd.model_utils import Shape_Prior
-    ecfg, dcfg = synth.small_encoder_cfg(), synth.small_decoder_cfg()
-    ew, dw = synth.make_encoder_weights(ecfg, 4), synth.make_decoder_weights(dcfg, 4)
-    return Shape_Prior.from_state(ecfg, dcfg, ew, dw, device=_dev(), n_pcl=128)
-
-
-def _scene(x):
-    """[n,N,3] -> the scene dict of _solve_end2end"""
-    x = x.to(_dev())
-    return {"pc": x.transpose(1, 2).contiguous(), "pc_mask": torch.ones(x.shape[0], 1, x.shape[1], dtype=torch.bool, device=x.device)}
-
-
-STEP_KEYS = {"ref_pc_lst", "rescan_pc_lst", "matches", "registration", "codes", "mesh_lst", "merged_sizes", "n_new_points", "unmatched_rescan"}
-CODE_KEYS = ("z_so3", "z_inv", "s", "t")
 
 
 def test_solve_sequence_memory(small_prior):

@@ -8,8 +8,6 @@ single op and the batch sum_d2 is compared bit for bit.  _overlap_batch's rmse =
 halves the sum's error and adds, with the division, one rounding of 2^-53 each.  The solve_sequence tests run untrained weights with the
 registration replaced, as the merge's identity test does, and make no accuracy claim."""
 import math
-import os
-import re
 
 import numpy as np
 import pytest
@@ -17,28 +15,11 @@ import torch
 
 import merge_oracle as mo
 import nearest_oracle as no
+from cloud_testlib import (CODE_KEYS, GATE_KEYS, STEP_KEYS, TILE, F, _bits, _dev, _g, _pose, _scene, _solver, _t,
+                           small_prior)  # noqa: F401 (small_prior is a fixture)
 from livingscenes_amd import synth
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-F = np.float32
-
-
-def _dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-def _t(x):
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 3)).to(_dev())
-
-
-def _g(g):
-    return None if g is None else torch.from_numpy(np.ascontiguousarray(g, dtype=np.float32)).to(_dev())
-
-
-def _bits(x):
-    return np.ascontiguousarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x).view(np.uint32)
 
 
 def _host(res):
@@ -75,24 +56,7 @@ def _check(A, B, g, r, what=""):
     return got
 
 
-def _rot(rng):
-    q, r = np.linalg.qr(rng.standard_normal((3, 3)))
-    q = q * np.sign(np.diag(r))
-    return q * np.sign(np.linalg.det(q))
-
-
-def _pose(rng, t=1.0):
-    return np.concatenate([_rot(rng), rng.uniform(-t, t, (3, 1))], 1).astype(np.float32)
-
-
-def _scan_tile():
-    src = open(os.path.join(REPO, "livingscenes_amd", "csrc", "ls_scan.h")).read()
-    t, items = (int(re.search(rf"\b{k}\s*=\s*(\d+)", src).group(1)) for k in ("SCAN_T", "SCAN_ITEMS"))
-    return t * items
-
-
 # ------------------------------------------------------------------------------------------------ size edges, P = 1
-TILE = _scan_tile()
 # the scanned array is the per-slot count of the 2 a table: its tile edges are at a = TILE / 2 and a = TILE; 256 and 257: the chunk of queries
 SIZES = [(0, 0), (0, 1), (1, 0), (1, 1), (255, 1), (256, 1), (1, 257), (200, 57)] + \
         [(TILE // 2 - 1, 300), (TILE // 2, 300), (TILE // 2 + 1, 300), (TILE - 1, 256), (TILE, 255), (TILE + 1, 513)] + \
@@ -309,11 +273,6 @@ def test_memory_sized_case():
 
 
 # ------------------------------------------------------------------------------------------------ the layers above
-def _solver(model, cfg=None):
-    from livingscenes_amd.lib_more.more_solver import More_Solver
-    base = {"shape_priors": {"n_input_point": 128, "prior_name": "chair", "ckpt_dir": ""}, "fps": {"n_init": 1}}
-    base.update(cfg or {})
-    return More_Solver(base, model=model)
 
 
 def _overlap_against(ov, k, twin, a):
@@ -380,25 +339,6 @@ def test_overlap_batch_known_pose():
         solver._overlap_batch(mems, news[:1], T)
     with pytest.raises(ValueError):
         solver._overlap_batch(mems, news, T[:1])
-
-
-@pytest.fixture(scope="module")
-def small_prior():
-    from livingscenes_amd.model_utils import Shape_Prior
-    ecfg, dcfg = synth.small_encoder_cfg(), synth.small_decoder_cfg()
-    ew, dw = synth.make_encoder_weights(ecfg, 4), synth.make_decoder_weights(dcfg, 4)
-    return Shape_Prior.from_state(ecfg, dcfg, ew, dw, device=_dev(), n_pcl=128)
-
-
-def _scene(x):
-    """[n,N,3] -> the scene dict of _solve_end2end"""
-    x = x.to(_dev())
-    return {"pc": x.transpose(1, 2).contiguous(), "pc_mask": torch.ones(x.shape[0], 1, x.shape[1], dtype=torch.bool, device=x.device)}
-
-
-STEP_KEYS = {"ref_pc_lst", "rescan_pc_lst", "matches", "registration", "codes", "mesh_lst", "merged_sizes", "n_new_points", "unmatched_rescan"}
-GATE_KEYS = {"overlap", "overlap_rmse", "memory_seen", "rejected"}
-CODE_KEYS = ("z_so3", "z_inv", "s", "t")
 
 
 def _counted(monkeypatch, solver, shift=(0.0, 0.0, 0.0)):

@@ -29,14 +29,14 @@ import icp_oracle as io
 import nearest_oracle as no
 import normals_oracle as nmo
 import plane_icp_oracle as po
+from cloud_testlib import (GATE_KEYS, REFINE_KEYS, STEP_KEYS, TILE, F, _bits, _dev, _g, _scene, _solver, _t,
+                           small_prior)  # noqa: F401 (small_prior is a fixture)
 from livingscenes_amd import synth
 from test_cloud_icp_cpu import _inv, _pose, _rot
 from test_cloud_plane_cpu import OFFSET, SHEET_R, eigen_gap_ok, hand_cases, sheet, surface_case
-from test_hip_cloud_icp import (GATE_KEYS, REFINE_KEYS, STEP_KEYS, TILE, _bits, _compose, _counted, _dev, _g, _perturbed, _scene, _solver,
-                                _step_values_equal, _t, small_prior)  # noqa: F401 (small_prior is a fixture)
+from test_hip_cloud_icp import _compose, _counted, _perturbed, _step_values_equal
 
 pytestmark = pytest.mark.gpu
-F = np.float32
 
 
 # ------------------------------------------------------------------------------------------------ normals
