@@ -63,7 +63,7 @@ typedef enum {
  * off_dec_xyz_t, the invariant decoder_type "deepsdf"; 107: the ragged multi-mesh metrics ls_mesh_contains_batch_f64 /
  * ls_mesh_distance_batch_f64 / ls_mesh_sample_batch_f64; symbols added since -- ls_reg_metrics_batch, ls_mesh_cluster_f64 / ls_mesh_cluster_batch_f64,
  * ls_cloud_merge_f32 / ls_cloud_merge_batch_f32, ls_cloud_nearest_f32 / ls_cloud_nearest_batch_f32, ls_cloud_icp_f32 / ls_cloud_icp_batch_f32,
- * ls_cloud_normals_f32 / ls_cloud_normals_batch_f32, ls_cloud_icp_plane_f32 / ls_cloud_icp_plane_batch_f32 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
+ * ls_cloud_normals_f32 / ls_cloud_normals_batch_f32, ls_cloud_icp_plane_f32 / ls_cloud_icp_plane_batch_f32, ls_cloud_project_f32 / ls_cloud_project_batch_f32 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
  * binding compares it with the header it was written against and refuses a mismatch (livingscenes_amd/_lib.py: load). */
 #define LS_ABI_VERSION 107
 int ls_version(void);
@@ -807,6 +807,42 @@ size_t ls_cloud_normals_batch_workspace_bytes(int P, long long a_total);
 int ls_cloud_normals_batch_f32(int P, const float* A, long long a_total, const long long* a_off, const float* radius, int min_nbrs,
                                float* normals, int32_t* nbr_cnt, float* variation, long long* counts, int* status_out, void* workspace,
                                size_t workspace_bytes, void* stream);
+
+/* Scene memory, one projection of a kept cloud onto its local planes (csrc/cloudnear.hip): the repair step of a consolidation on request --
+ * a kept point carries the sensor noise of the scan that delivered it, and the plane through its neighbourhood averages that noise out.
+ * AN EXTENSION BEYOND THE RELEASED REFERENCE, like the normals, whose neighbourhood this is.  It MOVES kept points, which no merge does, so
+ * nothing calls it unasked.  Definition, per problem (tests/project_oracle.py is the same text as NumPy).  For every row i of A [a,3] that
+ * has a cell: the neighbours, m_i, the integer moments s1 / s2, the covariance, the eigenvalues and the validity rule of
+ * ls_cloud_normals_f32, exactly.  Then, all in float64, for a valid row:
+ *   normal      n_k = V[k][lo] / len, the unit eigenvector of lmin BEFORE any fp32 rounding; no sign rule: the result does not depend on it
+ *   offset      unit = 1.0 / ((double)inv 32768.0); d_k = ((double)s1_k / (double)m_i) unit: the row minus the centroid of its
+ *               neighbourhood, from the integers, so the same near the origin and 300 m from it
+ *   distance    s = (d_0 n_0 + d_1 n_1) + d_2 n_2: the signed distance of the row to the plane through the centroid
+ *   variation   lmin / ((lmin + lmid) + lmax), as in the normals but not rounded
+ * state int32 [a], out_pts float [a,3], shift float [a]:
+ *   0  no cell (a non-finite coordinate)                                         out_pts = the input row bit for bit, shift 0
+ *   1  no plane (the validity rule fails)                                        out_pts = the input row bit for bit, shift 0
+ *   2  held: variation > (double)max_variation or |s| > (double)max_shift        out_pts = the input row bit for bit, shift (float)|s|
+ *   3  moved: out_pts_k = (float)((double)A[i]_k - s n_k)                        shift (float)|s|
+ * variation <= 1/3 by construction, so max_variation >= 1/3 is "no limit", as max_shift = +inf is.  counts long long [4] = the rows per
+ * state; sum_shift2 double [1] = the sum of s^2 over the moved rows by the chunk rule of ls_cloud_nearest_f32 (chunks of 256 rows in a
+ * fixed tree, the partials in chunk order, no floating-point atomics); status_out as in the search.  Every row is projected from the INPUT
+ * positions (a Jacobi step), so out_pts must not overlap A: refused on the host, like a radius that is not finite and > 0, min_nbrs < 1,
+ * and a max_variation or max_shift that is NaN or < 0.  One thread per row walks the 27 cells; 2 launches after the grid build.  No host
+ * synchronisation, no allocation, integer atomics only and only on the table: every output is the same bits in any run.  The workspace
+ * is the normals' plus 8 bytes per chunk of 256 rows. */
+size_t ls_cloud_project_workspace_bytes(long long a);
+int ls_cloud_project_f32(const float* A, long long a, float radius, int min_nbrs, float max_variation, float max_shift, float* out_pts,
+                         int32_t* state, float* shift, long long* counts, double* sum_shift2, int* status_out, void* workspace,
+                         size_t workspace_bytes, void* stream);
+/* P >= 1 problems per call with the conventions of ls_cloud_normals_batch_f32: a_off and radius are HOST arrays, checked before the first
+ * HIP call -- the error names the problem; min_nbrs, max_variation and max_shift are shared by the batch; empty problems are allowed.
+ * out_pts [a_total,3], state / shift [a_total], counts [P,4], sum_shift2 [P], status_out [P] (nullable), all DEVICE.  Every output of every
+ * problem is BIT-IDENTICAL to ls_cloud_project_f32 on that problem alone, and the number of launches does not depend on P. */
+size_t ls_cloud_project_batch_workspace_bytes(int P, long long a_total);
+int ls_cloud_project_batch_f32(int P, const float* A, long long a_total, const long long* a_off, const float* radius, int min_nbrs,
+                               float max_variation, float max_shift, float* out_pts, int32_t* state, float* shift, long long* counts,
+                               double* sum_shift2, int* status_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Scene memory, the trimmed ICP with the point-to-plane metric (csrc/cloudnear.hip).  AN EXTENSION BEYOND THE RELEASED REFERENCE, like
  * ls_cloud_icp_f32, whose loop this is: a partial view registered point-to-point onto one point per voxel of a SURFACE slides along it

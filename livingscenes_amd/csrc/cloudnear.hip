@@ -21,6 +21,10 @@
 // around its own and adds INTEGER moments of the neighbours' offsets, then the covariance and its eigenvectors in float64.  And the ICP
 // loop with the point-to-plane metric (ls_cloud_icp_plane_f32; tests/plane_icp_oracle.py): the search and the solve kernel are templates
 // on the metric, which says what a match adds to its chunk's record and how g_{k+1} follows from the sums.
+// A fourth, the projection of the kept cloud onto its local planes (ls_cloud_project_f32; tests/project_oracle.py): the neighbourhood,
+// the moments and the eigen-decomposition of the normals -- local_plane is one __device__ function for both -- then in float64 the
+// distance of the row to the plane through the centroid of its neighbours and the row moved onto it, from the input positions; the sum
+// of the squared distances by the chunk rule of the search, over chunks of the kept rows.
 // An operator on this grid is a kernel templated on the problem locator (OneNear / RaggedNear), a launch function after grid_launch, and
 // an entry that describes its call (NearCall) and hands the launch to near_run: every check, size and upload of the entry path is there.
 #include <climits>
@@ -282,10 +286,43 @@ __global__ __launch_bounds__(256) void final_kernel(Near L, const unsigned char*
 // ------------------------------------------------------------------------------------------------ normals of the kept cloud (ls_cloud_normals_f32)
 constexpr float MOMENT_SCALE = 32768.0f;      // 2^15: dx / r in units of 2^-15, |q| <= 2^15, so a sum of q_a q_b over < 2^31 neighbours stays below 2^61
 
-// One thread per target i that has a cell: the walk of the search with the query A[i] and no pose.  The neighbours' offsets as integers
-// q = rint((dx inv) 2^15), their first and second moments in int64 -- the order of a cell's members depends on the race, an integer sum
-// does not -- the covariance in float64 from the integers, its eigenvalues by Jacobi (svd3.h), the validity rule and the sign rule of the
-// definition.  Ten accumulators in registers, no LDS.
+// The local plane of the row y of cell c, for the normals and for the projection: the walk of the search with the query y and no pose,
+// the neighbours' offsets as integers q = rint((dx inv) 2^15), their first and second moments in int64 -- the order of a cell's members
+// depends on the race, an integer sum does not -- the covariance in float64 from the integers, its eigenvalues by Jacobi (svd3.h) and
+// the validity rule of the definition.  Ten accumulators in registers, no LDS.  m = the neighbours (the caller sets 0) and s1 their
+// first moments; where the row is valid also lam, V and the places lo / mid / hi of the least, middle and largest eigenvalue -> valid
+__device__ __forceinline__ bool local_plane(const NearRef& C, const int (&c)[3], const float (&y)[3], const int4* __restrict__ slots,
+                                            const int* __restrict__ cnt, const float4* __restrict__ members, int min_nbrs, int& m,
+                                            long long (&s1)[3], double (&lam)[3], double (&V)[3][3], int& lo, int& mid, int& hi) {
+    long long s2[6] = {0, 0, 0, 0, 0, 0};
+    walk_cells(C, c, slots, cnt, members, [&](const float4 t) {
+        const float dx = y[0] - t.x, dy = y[1] - t.y, dz = y[2] - t.z;
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        if (d2 <= C.r2) {
+            const long long q0 = (int)rintf((dx * C.inv) * MOMENT_SCALE), q1 = (int)rintf((dy * C.inv) * MOMENT_SCALE),
+                            q2 = (int)rintf((dz * C.inv) * MOMENT_SCALE);
+            ++m;
+            s1[0] += q0, s1[1] += q1, s1[2] += q2;
+            s2[0] += q0 * q0, s2[1] += q0 * q1, s2[2] += q0 * q2, s2[3] += q1 * q1, s2[4] += q1 * q2, s2[5] += q2 * q2;
+        }
+    });
+    if (m < min_nbrs || m <= 0) return false;
+    const double dm = (double)m, d1[3] = {(double)s1[0], (double)s1[1], (double)s1[2]};
+    const double Cv[6] = {(double)s2[0] - (d1[0] * d1[0]) / dm, (double)s2[1] - (d1[0] * d1[1]) / dm, (double)s2[2] - (d1[0] * d1[2]) / dm,
+                          (double)s2[3] - (d1[1] * d1[1]) / dm, (double)s2[4] - (d1[1] * d1[2]) / dm, (double)s2[5] - (d1[2] * d1[2]) / dm};
+    sym_eig3(Cv, lam, V);
+    lo = 0, hi = 0;
+    for (int k = 1; k < 3; ++k) {
+        if (lam[k] < lam[lo]) lo = k;
+        if (lam[k] > lam[hi]) hi = k;
+    }
+    if (hi == lo) hi = (lo + 1) % 3;                                    // three equal eigenvalues
+    mid = 3 - lo - hi;
+    return lam[hi] > 0.0 && lam[mid] > 0x1p-40 * lam[hi];
+}
+
+// One thread per target i that has a cell: its local plane, then the unit eigenvector of the least eigenvalue rounded to fp32 under the
+// sign rule of the definition, and the surface variation.
 template <class Near>
 __global__ __launch_bounds__(256) void normals_kernel(Near L, const float* __restrict__ A, long long a_total, const int* __restrict__ tcell,
                                                       const int4* __restrict__ slots, const int* __restrict__ cnt,
@@ -299,41 +336,18 @@ __global__ __launch_bounds__(256) void normals_kernel(Near L, const float* __res
     if (c[0] != NO_CELL) {
         const NearRef C = L.problem(L.target_owner(i));
         const float y[3] = {A[i * 3 + 0], A[i * 3 + 1], A[i * 3 + 2]};
-        long long s1[3] = {0, 0, 0}, s2[6] = {0, 0, 0, 0, 0, 0};
-        walk_cells(C, c, slots, cnt, members, [&](const float4 t) {
-            const float dx = y[0] - t.x, dy = y[1] - t.y, dz = y[2] - t.z;
-            const float d2 = (dx * dx + dy * dy) + dz * dz;
-            if (d2 <= C.r2) {
-                const long long q0 = (int)rintf((dx * C.inv) * MOMENT_SCALE), q1 = (int)rintf((dy * C.inv) * MOMENT_SCALE),
-                                q2 = (int)rintf((dz * C.inv) * MOMENT_SCALE);
-                ++m;
-                s1[0] += q0, s1[1] += q1, s1[2] += q2;
-                s2[0] += q0 * q0, s2[1] += q0 * q1, s2[2] += q0 * q2, s2[3] += q1 * q1, s2[4] += q1 * q2, s2[5] += q2 * q2;
-            }
-        });
-        if (m >= min_nbrs && m > 0) {
-            const double dm = (double)m, d1[3] = {(double)s1[0], (double)s1[1], (double)s1[2]};
-            const double Cv[6] = {(double)s2[0] - (d1[0] * d1[0]) / dm, (double)s2[1] - (d1[0] * d1[1]) / dm, (double)s2[2] - (d1[0] * d1[2]) / dm,
-                                  (double)s2[3] - (d1[1] * d1[1]) / dm, (double)s2[4] - (d1[1] * d1[2]) / dm, (double)s2[5] - (d1[2] * d1[2]) / dm};
-            double lam[3], V[3][3];
-            sym_eig3(Cv, lam, V);
-            int lo = 0, hi = 0;
-            for (int k = 1; k < 3; ++k) {
-                if (lam[k] < lam[lo]) lo = k;
-                if (lam[k] > lam[hi]) hi = k;
-            }
-            if (hi == lo) hi = (lo + 1) % 3;                            // three equal eigenvalues
-            const int mid = 3 - lo - hi;
-            if (lam[hi] > 0.0 && lam[mid] > 0x1p-40 * lam[hi]) {
-                const double len = sqrt((V[0][lo] * V[0][lo] + V[1][lo] * V[1][lo]) + V[2][lo] * V[2][lo]);
-                for (int k = 0; k < 3; ++k) nrm[k] = (float)(V[k][lo] / len);
-                int big = 0;                                           // the first component of largest magnitude is positive
-                for (int k = 1; k < 3; ++k)
-                    if (fabsf(nrm[k]) > fabsf(nrm[big])) big = k;
-                const bool flip = nrm[big] < 0.f;
-                for (int k = 0; k < 3; ++k) nrm[k] = nrm[k] == 0.f ? 0.f : (flip ? -nrm[k] : nrm[k]);
-                var = (float)(lam[lo] / ((lam[lo] + lam[mid]) + lam[hi]));
-            }
+        long long s1[3] = {0, 0, 0};
+        double lam[3], V[3][3];
+        int lo, mid, hi;
+        if (local_plane(C, c, y, slots, cnt, members, min_nbrs, m, s1, lam, V, lo, mid, hi)) {
+            const double len = sqrt((V[0][lo] * V[0][lo] + V[1][lo] * V[1][lo]) + V[2][lo] * V[2][lo]);
+            for (int k = 0; k < 3; ++k) nrm[k] = (float)(V[k][lo] / len);
+            int big = 0;                                               // the first component of largest magnitude is positive
+            for (int k = 1; k < 3; ++k)
+                if (fabsf(nrm[k]) > fabsf(nrm[big])) big = k;
+            const bool flip = nrm[big] < 0.f;
+            for (int k = 0; k < 3; ++k) nrm[k] = nrm[k] == 0.f ? 0.f : (flip ? -nrm[k] : nrm[k]);
+            var = (float)(lam[lo] / ((lam[lo] + lam[mid]) + lam[hi]));
         }
     }
     for (int k = 0; k < 3; ++k) normals[i * 3 + k] = nrm[k];
@@ -357,6 +371,78 @@ __global__ __launch_bounds__(256) void normals_final_kernel(Near L, const float*
     count_tree(lds, v);
     if (threadIdx.x < 2) counts[(size_t)p * 2 + threadIdx.x] = lds[threadIdx.x][0];
     if (threadIdx.x == 0 && status_out) status_out[p] = status[p];
+}
+
+// ------------------------------------------------------------------------------------------------ projection onto the local planes (ls_cloud_project_f32)
+enum { PROJ_NO_CELL = 0, PROJ_NO_PLANE, PROJ_HELD, PROJ_MOVED, PROJ_STATES };
+
+// workgroup = one chunk of QUERY_CHUNK rows of ONE problem's kept cloud (the locator's queries ARE its targets: b = a, b0 = a0), one
+// thread per row: its local plane as the normals form it, then in float64 the unit normal before any fp32 rounding, the row minus the
+// centroid of its neighbourhood from the integer moments, and s, its signed distance to the plane through the centroid.  Every row is
+// projected from the INPUT positions and written to out_pts (a Jacobi step).  part[chunk] = the sum of s^2 over the chunk's moved rows.
+template <class Near>
+__global__ __launch_bounds__(QUERY_CHUNK) void project_kernel(Near L, const float* __restrict__ A, const int* __restrict__ tcell,
+                                                              const int4* __restrict__ slots, const int* __restrict__ cnt,
+                                                              const float4* __restrict__ members, int min_nbrs, double max_variation,
+                                                              double max_shift, float* __restrict__ out_pts, int* __restrict__ state,
+                                                              float* __restrict__ shift, double* __restrict__ part) {
+    __shared__ double lds[QUERY_CHUNK];
+    const NearRef C = L.problem(L.chunk_owner(blockIdx.x));
+    const long long qi = ((long long)blockIdx.x - C.q0) * QUERY_CHUNK + threadIdx.x;
+    double moved2 = 0.0;
+    if (qi < C.a) {
+        const long long i = C.a0 + qi;
+        const int c[3] = {tcell[i * 3 + 0], tcell[i * 3 + 1], tcell[i * 3 + 2]};
+        const float y[3] = {A[i * 3 + 0], A[i * 3 + 1], A[i * 3 + 2]};
+        float out[3] = {y[0], y[1], y[2]}, sh = 0.f;
+        int what = PROJ_NO_CELL;
+        if (c[0] != NO_CELL) {
+            int m = 0, lo, mid, hi;
+            long long s1[3] = {0, 0, 0};
+            double lam[3], V[3][3];
+            what = PROJ_NO_PLANE;
+            if (local_plane(C, c, y, slots, cnt, members, min_nbrs, m, s1, lam, V, lo, mid, hi)) {
+                const double len = sqrt((V[0][lo] * V[0][lo] + V[1][lo] * V[1][lo]) + V[2][lo] * V[2][lo]);
+                const double n[3] = {V[0][lo] / len, V[1][lo] / len, V[2][lo] / len};
+                const double unit = 1.0 / ((double)C.inv * (double)MOMENT_SCALE), dm = (double)m;
+                const double d[3] = {((double)s1[0] / dm) * unit, ((double)s1[1] / dm) * unit, ((double)s1[2] / dm) * unit};
+                const double s = (d[0] * n[0] + d[1] * n[1]) + d[2] * n[2];
+                const double var = lam[lo] / ((lam[lo] + lam[mid]) + lam[hi]);
+                sh = (float)fabs(s);
+                what = (var > max_variation || fabs(s) > max_shift) ? PROJ_HELD : PROJ_MOVED;
+                if (what == PROJ_MOVED) {
+                    for (int k = 0; k < 3; ++k) out[k] = (float)((double)y[k] - s * n[k]);
+                    moved2 = s * s;
+                }
+            }
+        }
+        for (int k = 0; k < 3; ++k) out_pts[i * 3 + k] = out[k];
+        state[i] = what;
+        shift[i] = sh;
+    }
+    const double sum = chunk_sum(lds, moved2);
+    if (threadIdx.x == 0) part[blockIdx.x] = sum;
+}
+
+// workgroup = one problem: counts [4] = the rows per state (integers, any order) and sum_shift2 (the float64 partials in chunk order)
+template <class Near>
+__global__ __launch_bounds__(256) void project_final_kernel(Near L, const int* __restrict__ state, const double* __restrict__ part,
+                                                            const int* __restrict__ status, long long* __restrict__ counts,
+                                                            double* __restrict__ sum_shift2, int* __restrict__ status_out) {
+    __shared__ long long lds[PROJ_STATES][256];
+    const int p = blockIdx.x;
+    const NearRef C = L.problem(p);
+    long long v[PROJ_STATES] = {0, 0, 0, 0};
+    for (long long j = C.a0 + threadIdx.x; j < C.a0 + C.a; j += 256)
+        for (int k = 0; k < PROJ_STATES; ++k) v[k] += state[j] == k;
+    count_tree(lds, v);
+    if (threadIdx.x < PROJ_STATES) counts[(size_t)p * PROJ_STATES + threadIdx.x] = lds[threadIdx.x][0];
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (long long q = C.q0; q < C.q1; ++q) s += part[q];
+        sum_shift2[p] = s;
+        if (status_out) status_out[p] = status[p];
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ trimmed ICP on the same grid (ls_cloud_icp_f32)
@@ -667,7 +753,9 @@ struct Ws {
 // the layout depends on (P, a, b) alone (ws null: a sizing pass; n_offs = 0: a single problem); sum_p ceil(b_p / c) <= floor(b / c) + P.
 // The ICP's pieces follow the search's, so its workspace is the search's and then its own state and one moment record per chunk (n_mom:
 // the metric's N_MOM; 0: no ICP); the plane metric's count of planar matches per chunk comes last, so the point ICP's layout is what it was.
-Ws layout(void* ws, size_t n_offs, int P, long long a, long long b, int n_mom = 0) {
+// row_chunks: an operator without queries (b = 0) whose workgroups own chunks of A's rows and leave one float64 each -- `part` holds
+// those chunks and nothing else changes, so its workspace is the normals' plus 8 bytes per chunk of rows.
+Ws layout(void* ws, size_t n_offs, int P, long long a, long long b, int n_mom = 0, bool row_chunks = false) {
     Arena ar(ws);
     Ws w;
     const size_t chunks = (size_t)(b / QUERY_CHUNK + P);
@@ -686,7 +774,7 @@ Ws layout(void* ws, size_t n_offs, int P, long long a, long long b, int n_mom = 
     w.rank = ar.take<int>((size_t)a);
     w.members = ar.take<float4>((size_t)a);
     w.hit = ar.take<unsigned char>((size_t)a);
-    w.part = ar.take<double>(chunks);
+    w.part = ar.take<double>(row_chunks ? (size_t)(a / QUERY_CHUNK + P) : chunks);
     w.part_cnt = ar.take<int2>(chunks);
     w.gk = ar.take<float>(n_mom ? (size_t)P * 12 : 0);
     w.e_prev = ar.take<double>(n_mom ? (size_t)P : 0);
@@ -802,6 +890,48 @@ int normals_launch(const Near& L, int P, const float* A, long long a, int min_nb
     return LS_OK;
 }
 
+struct ProjectArgs {
+    int min_nbrs;
+    float max_variation, max_shift;
+    float* out_pts;
+    int* state;
+    float* shift;
+    long long* counts;
+    double* sum_shift2;
+};
+
+int check_project_sizes(const char* op, long long a, const float* A, const ProjectArgs& J) {
+    LS_REQUIRE(a >= 0, "%s: negative size (%lld kept rows)", op, a);
+    LS_REQUIRE(a <= INT_MAX, "%s: %lld rows exceed %d (int row indices)", op, a, INT_MAX);
+    LS_REQUIRE(a == 0 || (A && J.out_pts && J.state && J.shift), "%s: null A / out_pts / state / shift with %lld rows", op, a);
+    LS_REQUIRE(J.counts && J.sum_shift2, "%s: null counts / sum_shift2", op);
+    LS_REQUIRE(a == 0 || (J.out_pts + a * 3 <= A || A + a * 3 <= J.out_pts),
+               "%s: out_pts overlaps A: every row is projected from the input positions, so the operator cannot work in place", op);
+    return LS_OK;
+}
+
+int check_project(const char* op, const ProjectArgs& J) {
+    LS_REQUIRE(J.min_nbrs >= 1, "%s: min_nbrs must be >= 1, got %d", op, J.min_nbrs);
+    LS_REQUIRE(J.max_variation >= 0.0f, "%s: max_variation must be >= 0 and not NaN (1/3 and above: no limit), got %g", op, (double)J.max_variation);
+    LS_REQUIRE(J.max_shift >= 0.0f, "%s: max_shift must be >= 0 and not NaN (+inf: no limit), got %g", op, (double)J.max_shift);
+    return LS_OK;
+}
+
+// the projection's launch sequence: the grid, one thread per row in chunks of one problem, the counts and sums -- 2 kernels after the
+// grid build, whatever P
+template <class Near>
+int project_launch(const Near& L, int P, const float* A, long long a, long long chunks, const ProjectArgs& J, const Ws& w, int* status_out,
+                   hipStream_t st) {
+    const int rc = grid_launch(L, P, A, a, w, st);
+    if (rc != LS_OK) return rc;
+    if (chunks > 0)
+        hipLaunchKernelGGL(project_kernel<Near>, dim3((unsigned)chunks), dim3(QUERY_CHUNK), 0, st, L, A, w.tcell, w.slots, w.cnt, w.members, J.min_nbrs,
+                           (double)J.max_variation, (double)J.max_shift, J.out_pts, J.state, J.shift, w.part);
+    hipLaunchKernelGGL(project_final_kernel<Near>, dim3(P), dim3(256), 0, st, L, J.state, w.part, w.status, J.counts, J.sum_shift2, status_out);
+    LS_LAUNCH_CHECK();
+    return LS_OK;
+}
+
 int check_common(const char* op, long long a, long long b, const float* A, const float* B, const int* nn_idx, const float* nn_d2,
                  const long long* counts, const double* sum_d2) {
     LS_REQUIRE(a >= 0 && b >= 0, "%s: negative size (%lld kept rows, %lld query rows)", op, a, b);
@@ -827,6 +957,7 @@ struct NearCall {
     const float* g;              // the locator's pose: [3,4] / [P,3,4] or null
     const float* radius;         // a batch: [P]; the single form: the address of its one radius
     int n_mom;                   // the ICP: the metric's N_MOM; 0: no ICP
+    bool row_chunks;             // no queries, but workgroups that own chunks of A's rows: the locator's queries are its targets (B = A, b = a)
     void* workspace;
     size_t workspace_bytes;
     void* stream;
@@ -838,7 +969,7 @@ struct NearCall {
         c.op = op, c.batch = false, c.P = 1;
         c.A = A, c.a = a, c.a_off = nullptr;
         c.has_b = true, c.B = B, c.b = b, c.b_off = nullptr;
-        c.g = g, c.radius = radius, c.n_mom = n_mom;
+        c.g = g, c.radius = radius, c.n_mom = n_mom, c.row_chunks = false;
         c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = stream;
         return c;
     }
@@ -852,9 +983,9 @@ struct NearCall {
 };
 
 // every size query: 0 for sizes no call accepts
-size_t near_bytes(bool batch, int P, long long a, long long b, int n_mom) {
+size_t near_bytes(bool batch, int P, long long a, long long b, int n_mom, bool row_chunks = false) {
     if ((batch && P < 1) || a < 0 || b < 0 || a + b > INT_MAX) return 0;
-    return layout(nullptr, batch ? (size_t)OFF_ARRAYS * (P + 1) : 0, batch ? P : 1, a, b, n_mom).bytes;
+    return layout(nullptr, batch ? (size_t)OFF_ARRAYS * (P + 1) : 0, batch ? P : 1, a, b, n_mom, row_chunks).bytes;
 }
 
 // The entry path of every operator, all checks before the first HIP call and in one order: sizes() -- the operator's checks of its sizes
@@ -875,29 +1006,32 @@ int near_run(const NearCall& c, Sizes&& sizes, Checks&& checks, Launch&& launch)
         if (rc != LS_OK) return rc;
         LS_REQUIRE(c.radius, "%s: null radius", op);
     }
-    std::vector<long long> q_off(c.batch ? P + 1 : 0, 0);               // a batch: the chunk offsets; without queries also its b_off
+    std::vector<long long> q_off(c.batch ? P + 1 : 0, 0);               // a batch: the chunk offsets; without queries or row chunks also its b_off
     std::vector<float> terms(c.batch ? 2 * (size_t)P : 0);
     float one[2];
     float *inv = c.batch ? terms.data() : one, *r2 = inv + P;
     long long chunks = 0;
     for (int p = 0; p < P; ++p) {
         if (c.has_b) chunks += chunks_of(c.batch ? c.b_off[p + 1] - c.b_off[p] : c.b);
+        if (c.row_chunks) chunks += chunks_of(c.batch ? c.a_off[p + 1] - c.a_off[p] : c.a);
         if (c.batch) q_off[p + 1] = chunks;
         rc = check_edge(op, p, "radius", "radius", c.radius[p], &inv[p], &r2[p]);
         if (rc != LS_OK) return rc;
     }
     rc = checks();
     if (rc != LS_OK) return rc;
-    rc = check_workspace(op, c.workspace, c.workspace_bytes, near_bytes(c.batch, c.P, c.a, c.b, c.n_mom), c.batch ? P : 0, c.a, c.has_b ? c.b : -1);
+    rc = check_workspace(op, c.workspace, c.workspace_bytes, near_bytes(c.batch, c.P, c.a, c.b, c.n_mom, c.row_chunks), c.batch ? P : 0, c.a,
+                         c.has_b ? c.b : -1);
     if (rc != LS_OK) return rc;
-    const Ws w = layout(c.workspace, c.batch ? (size_t)OFF_ARRAYS * (P + 1) : 0, P, c.a, c.b, c.n_mom);
+    const Ws w = layout(c.workspace, c.batch ? (size_t)OFF_ARRAYS * (P + 1) : 0, P, c.a, c.b, c.n_mom, c.row_chunks);
     hipStream_t st = (hipStream_t)c.stream;
-    if (!c.batch) return launch(OneNear{c.B, c.a, c.b, c.g, inv[0], r2[0]}, P, w, chunks, st);
-    rc = upload_offsets(w.offs, pack_offsets(P, {c.a_off, c.has_b ? c.b_off : q_off.data(), q_off.data()}), st);
+    const float* Q = c.row_chunks ? c.A : c.B;                          // the locator's queries
+    if (!c.batch) return launch(OneNear{Q, c.a, c.row_chunks ? c.a : c.b, c.g, inv[0], r2[0]}, P, w, chunks, st);
+    rc = upload_offsets(w.offs, pack_offsets(P, {c.a_off, c.has_b ? c.b_off : c.row_chunks ? c.a_off : q_off.data(), q_off.data()}), st);
     if (rc != LS_OK) return rc;
     LS_HIP_CHECK(hipMemcpyAsync(w.inv, inv, (size_t)P * sizeof(float), hipMemcpyHostToDevice, st));   // pageable: read when it returns
     LS_HIP_CHECK(hipMemcpyAsync(w.r2, r2, (size_t)P * sizeof(float), hipMemcpyHostToDevice, st));
-    return launch(RaggedNear{c.B, c.g, w.offs, w.inv, w.r2, P}, P, w, chunks, st);
+    return launch(RaggedNear{Q, c.g, w.offs, w.inv, w.r2, P}, P, w, chunks, st);
 }
 
 const auto no_checks = [] { return LS_OK; };
@@ -937,6 +1071,16 @@ int normals_entry(const NearCall& c, int min_nbrs, float* normals, int* nbr_cnt,
         c, [&] { return check_normals(c.op, c.a, c.A, min_nbrs, normals, nbr_cnt, variation, counts); }, no_checks,
         [&](const auto& L, int P, const Ws& w, long long, hipStream_t st) {
             return normals_launch(L, P, c.A, c.a, min_nbrs, w, normals, nbr_cnt, variation, counts, status_out, st);
+        });
+}
+
+// the entry of the projection: no queries, chunks of the kept rows
+int project_entry(NearCall c, const ProjectArgs& J, int* status_out) {
+    c.has_b = false, c.row_chunks = true;
+    return near_run(
+        c, [&] { return check_project_sizes(c.op, c.a, c.A, J); }, [&] { return check_project(c.op, J); },
+        [&](const auto& L, int P, const Ws& w, long long chunks, hipStream_t st) {
+            return project_launch(L, P, c.A, c.a, chunks, J, w, status_out, st);
         });
 }
 }  // namespace
@@ -1020,6 +1164,24 @@ int ls_cloud_normals_batch_f32(int P, const float* A, long long a_total, const l
     NearCall c = NearCall::ragged("cloud_normals_batch", P, A, a_total, a_off, nullptr, 0, nullptr, nullptr, radius, 0, workspace, workspace_bytes, stream);
     c.has_b = false;
     return normals_entry(c, min_nbrs, normals, nbr_cnt, variation, counts, status_out);
+}
+
+size_t ls_cloud_project_workspace_bytes(long long a) { return near_bytes(false, 1, a, 0, 0, true); }
+size_t ls_cloud_project_batch_workspace_bytes(int P, long long a_total) { return near_bytes(true, P, a_total, 0, 0, true); }
+
+int ls_cloud_project_f32(const float* A, long long a, float radius, int min_nbrs, float max_variation, float max_shift, float* out_pts,
+                         int32_t* state, float* shift, long long* counts, double* sum_shift2, int* status_out, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    const NearCall c = NearCall::one("cloud_project", A, a, nullptr, 0, nullptr, &radius, 0, workspace, workspace_bytes, stream);
+    return project_entry(c, ProjectArgs{min_nbrs, max_variation, max_shift, out_pts, state, shift, counts, sum_shift2}, status_out);
+}
+
+int ls_cloud_project_batch_f32(int P, const float* A, long long a_total, const long long* a_off, const float* radius, int min_nbrs,
+                               float max_variation, float max_shift, float* out_pts, int32_t* state, float* shift, long long* counts,
+                               double* sum_shift2, int* status_out, void* workspace, size_t workspace_bytes, void* stream) {
+    const NearCall c = NearCall::ragged("cloud_project_batch", P, A, a_total, a_off, nullptr, 0, nullptr, nullptr, radius, 0, workspace,
+                                        workspace_bytes, stream);
+    return project_entry(c, ProjectArgs{min_nbrs, max_variation, max_shift, out_pts, state, shift, counts, sum_shift2}, status_out);
 }
 
 }  // extern "C"

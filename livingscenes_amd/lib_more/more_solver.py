@@ -343,6 +343,38 @@ class More_Solver:
             radius = 3 * self.cfg.get("accumulate", {}).get("voxel_size", 0.01)
         return ops.cloud_normals_batch([p.detach() for p in mem_pcs], radius=radius, min_nbrs=min_nbrs)
 
+    def _consolidate_batch(self, mem_pcs, radius=None, voxel=None, min_nbrs=5, max_variation=1 / 3, max_shift=float("inf")):
+        """Scene memory, a consolidation on request (an extension beyond the released reference, like _accumulate_batch): the memory
+        keeps the first point of every voxel with the sensor noise of the scan that delivered it, and noisy rescans fill the voxels on
+        both sides of the true surface.  ONE ops.cloud_project_batch call (csrc/cloudnear.hip) projects every kept point of the P clouds
+        mem_pcs[p] [a_p,3] onto the plane of its neighbourhood, from the input positions; ONE ops.cloud_merge_batch call of the projected
+        clouds against empty observations at `voxel` (the merge unchanged: first wins, one point per voxel) drops the rows that now share
+        a voxel.  It MOVES kept points, which no merge does, so nothing calls it unasked; and a projection shrinks a curved surface a
+        little each time, so it is meant to run ONCE, not after every merge (solve_sequence's docstring has the figures).
+        voxel: as _accumulate_batch (cfg['accumulate']['voxel_size'], else 0.01).  radius: default 3 * voxel, the default of
+        _memory_normals_batch -- A DERIVED DEFAULT, not tuned: about 9 pi = 28 points at one point per voxel on a surface.  min_nbrs,
+        max_variation (1/3: no limit) and max_shift (inf: no limit) are ops.cloud_project_batch's: no value of either limit is recommended.
+        -> (list of P consolidated clouds [n_p,3],
+            dict of per-slot lists: rows_before, rows_after, moved, held, no_plane (rows per state of the projection) and rms_shift =
+            sqrt(sum_shift2 / moved), the RMS distance the moved rows travelled (nan when nothing moved))."""
+        if voxel is None:
+            voxel = self.cfg.get("accumulate", {}).get("voxel_size", 0.01)
+        if radius is None:
+            radius = 3 * voxel
+        clouds = [p.detach() for p in mem_pcs]
+        proj = ops.cloud_project_batch(clouds, radius=radius, min_nbrs=min_nbrs, max_variation=max_variation, max_shift=max_shift)
+        merged = ops.cloud_merge_batch([pts for pts, _, _, _, _ in proj], [c[:0] for c in clouds], voxel=voxel)
+        info = {"rows_before": [], "rows_after": [], "moved": [], "held": [], "no_plane": [], "rms_shift": []}
+        for c, (_, _, _, counts, sum_shift2), (pts, _) in zip(clouds, proj, merged):
+            moved = int(counts[3])
+            info["rows_before"].append(c.shape[0])
+            info["rows_after"].append(pts.shape[0])
+            info["moved"].append(moved)
+            info["held"].append(int(counts[2]))
+            info["no_plane"].append(int(counts[1]))
+            info["rms_shift"].append(math.sqrt(sum_shift2 / moved) if moved else float("nan"))
+        return [pts for pts, _ in merged], info
+
     def _refine_on_memory_batch(self, mem_pcs, new_pcs, T, radius, metric="point", normal_radius=None, **kw):
         """Scene memory, the pose the merge and the overlap gate trust (an extension beyond the released reference, like both): refine P
         registrations on the memory itself, at full resolution, in ONE ragged call (ops.cloud_icp_batch, csrc/cloudnear.hip) -- trimmed
@@ -598,7 +630,8 @@ def _encode_clouds(model, clouds):
 
 
 def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, optimize_codes=False, overlap_radius=None, min_overlap=None,
-                   refine_radius=None, refine_metric="point", normal_radius=None):
+                   refine_radius=None, refine_metric="point", normal_radius=None, consolidate=False, consolidate_radius=None,
+                   consolidate_max_variation=1 / 3, consolidate_max_shift=float("inf")):
     """A reference scan followed by SEVERAL rescans, with a memory that carries every instance's points from one rescan to the next -- an
     extension beyond the released reference (more_solver.py:246-299 solves one (reference, rescan) pair and drops the rescan's points).
     ref and every rescan: {'pc' [n,3,Nmax], 'pc_mask'} as _solve_end2end takes them.
@@ -638,7 +671,22 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
     measure that.  refine_metric "plane" (with refine_radius; without it a ValueError) refines with the point-to-plane metric:
     More_Solver._refine_on_memory_batch(metric="plane", normal_radius=normal_radius), the normals of the memory recomputed at every step.
     There is NO FALLBACK to the point metric: a pair whose refinement starves or is degenerate keeps the registration it came with, as
-    any pair with refine_iters 0 does, and refine_stop reports it.  "point" is the path above, untouched."""
+    any pair with refine_iters 0 does, and refine_stop reports it.  "point" is the path above, untouched.
+
+    The consolidation (opt-in: with consolidate False nothing below happens and every returned object is what it is without the
+    arguments).  With True, ONE More_Solver._consolidate_batch call over all slots runs AFTER THE LAST RESCAN (radius consolidate_radius,
+    None: its derived default 3 * voxel; consolidate_max_variation and consolidate_max_shift are its limits, 1/3 and inf: none): every
+    kept point is projected once onto the plane of its neighbourhood and the projected cloud is merged again at the same voxel.  It is
+    NEVER run between rescans, because a plane fit on a curved surface shrinks it, and the shrinkage accumulates.  A CPU EXPERIMENT (NumPy
+    twins in float64, not the operator and not a device run; a sphere of radius 0.4 m, sigma = 0.002 noise, voxel 0.01 m, 20 000 points
+    per scan, one reference scan and five rescans merged at the true pose): the memory's RMS distance to the sphere is 2.27e-3 after the
+    six scans and 5.4e-4 after one projection at r = 0.02 (30 211 rows, 21 288 after the re-merge); projecting after EVERY rescan instead
+    gives 6.4e-4 after the first step and 8.4e-4 after the fifth at r = 0.02, and 6.5e-4 rising to 1.78e-3 at r = 0.03.  A caller who
+    wants the per-step alternative has More_Solver._consolidate_batch, at their own risk.  A slot whose consolidated cloud would have
+    fewer than n_input_point rows keeps its cloud and code and is reported; the other slots take their consolidated cloud and are
+    re-encoded in ONE _encode_clouds call (the encoder's code of the consolidated cloud: optimize_codes does not run again).  memory
+    gains 'consolidation': the dict of _consolidate_batch (per-slot lists rows_before, rows_after, moved, held, no_plane, rms_shift;
+    the figures of a kept slot are those of the cloud it did not take) plus kept_as_is (slots)."""
     if refine_metric not in ("point", "plane"):
         raise ValueError(f"solve_sequence: refine_metric must be 'point' or 'plane', got {refine_metric!r}")
     if refine_metric == "plane" and refine_radius is None:
@@ -728,7 +776,22 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
             out.update({"overlap": [None] * n, "overlap_rmse": [None] * n, "memory_seen": [None] * n, "rejected": []})
         out["merged_sizes"] = [c.shape[0] for c in mem]
         steps.append(out)
+    consolidation = None
+    if consolidate:
+        cons, consolidation = solver._consolidate_batch(mem, radius=consolidate_radius, voxel=voxel, max_variation=consolidate_max_variation,
+                                                        max_shift=consolidate_max_shift)
+        consolidation["kept_as_is"] = [i for i, c in enumerate(cons) if c.shape[0] < n_in]
+        taken = [i for i, c in enumerate(cons) if c.shape[0] >= n_in]
+        for i in taken:
+            mem[i] = cons[i]
+        if taken:
+            new = _encode_clouds(model, [mem[i] for i in taken])
+            rows = torch.tensor(taken, device=codes["z_inv"].device)
+            for k in _CODE_KEYS:
+                codes[k][rows] = new[k].detach().to(codes[k].dtype)
     memory = {"clouds": mem, "codes": codes, "meshes": solver._mesh_from_latent_batch(codes) if mesh else None}
+    if consolidate:
+        memory["consolidation"] = consolidation
     return steps, memory
 
 

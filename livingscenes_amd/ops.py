@@ -814,7 +814,7 @@ def mesh_sample_batch(meshes, counts, seeds=None):
 
 
 # ------------------------------------------------------------------------------------------------ scene memory (csrc/cloud_grid.h, cloudmerge.hip, cloudnear.hip)
-# The ten wrappers share one binding scheme: _cloud / _pose / _poses / _per_problem check the arguments, _pack puts a list of clouds back
+# The twelve wrappers share one binding scheme: _cloud / _pose / _poses / _per_problem check the arguments, _pack puts a list of clouds back
 # to back, _Meta holds the per-problem outputs that the host reads, and _icp_result assembles what the four ICP wrappers return.
 def _cloud(x, what, op):
     if not torch.is_tensor(x) or x.device.type != "cuda" or x.dtype != torch.float32:
@@ -1104,6 +1104,62 @@ def cloud_normals(A, *, radius, min_nbrs=5):
     normals, cnt, var, counts = _normals(op, "ls_cloud_normals_f32", (ptr(A), A.shape[0], float(radius), int(min_nbrs)), (A.shape[0],), 1,
                                          A.device, A.shape[0])
     return normals, cnt, var, counts[0]
+
+
+def _project(op, name, head, sizes, P, dev, a):
+    """the call of the projection's entry `name` of the operator `op` -> (points, state, shift, counts [P,4], sum_shift2 [P])"""
+    pts = torch.empty(a, 3, dtype=torch.float32, device=dev)
+    state = torch.empty(a, dtype=torch.int32, device=dev)
+    shift = torch.empty(a, dtype=torch.float32, device=dev)
+    m = _Meta(P, dev, [("counts", np.int64, 4), ("sum_shift2", np.float64, 1), ("status", np.int32, 1)])
+    _cloud_call(dev, name, sizes, *head, ptr(pts), ptr(state), ptr(shift), m.ptr("counts"), m.ptr("sum_shift2"), m.ptr("status"))
+    f = m.read(op)
+    return pts, state, shift, f["counts"], f["sum_shift2"]
+
+
+PROJECT_STATE = ("no_cell", "no_plane", "held", "moved")   # the values of `state`, by value
+
+
+def cloud_project_batch(As, *, radius, min_nbrs=5, max_variation=1 / 3, max_shift=float("inf"), packed=False):
+    """ls_cloud_project_batch_f32 (an extension beyond the released reference, like cloud_normals, whose neighbourhood it uses): ONE
+    projection of every row of the P kept clouds As[p] [a_p,3] (fp32 HIP tensors, empty ones allowed) onto the plane through the centroid
+    of the rows within `radius` of it (one radius or P radii), normal to the eigenvector of the least eigenvalue of their covariance:
+    integer moments, the rest in float64 (include/livingscenes_hip.h has the definition to the bit).  Every row is projected from the
+    input positions; the inputs are not written.  A row whose neighbourhood has no plane (fewer than min_nbrs rows, coincident, collinear)
+    stays; so does one with variation = lmin / (lmin + lmid + lmax) > max_variation (an edge or a corner) or a distance to its plane >
+    max_shift.  max_variation = 1/3 IS "NO LIMIT", because variation <= 1/3 by construction, and max_shift = inf is no limit either: NO
+    VALUE OF EITHER IS RECOMMENDED, none has been measured on real scans.  min_nbrs = 5 is cloud_normals': not tuned.
+    -> list of P (points [a_p,3] fp32; state [a_p] int32: 0 no cell, 1 no plane, 2 held, 3 moved (PROJECT_STATE names them); shift [a_p]
+    fp32: the distance to the plane, 0 in states 0 and 1; counts: host int64 [4] = rows per state; sum_shift2: float, the float64 sum of
+    the squared distances of the moved rows), views of packed tensors; packed=True: (points, state, shift, counts [P,4], sum_shift2 [P],
+    a_off).  One call, one host read, whatever P."""
+    op = "cloud_project"
+    As = [_cloud(x, "A", op) for x in As]
+    P = len(As)
+    if P == 0:
+        raise ValueError(f"{op}: no problem given")
+    dev = As[0].device
+    rad = _per_problem(radius, P, op, "radii")
+    A, ao = _pack(As)
+    pts, state, shift, counts, sums = _project(op, "ls_cloud_project_batch_f32", (P, ptr(A), A.shape[0], _hptr(ao), _hptr(rad), int(min_nbrs),
+                                                                                 float(max_variation), float(max_shift)),
+                                               (P, A.shape[0]), P, dev, A.shape[0])
+    if packed:
+        return pts, state, shift, counts, sums, ao
+    sizes = np.diff(ao).tolist()
+    return [(x, s, d, counts[p], float(sums[p]))
+            for p, (x, s, d) in enumerate(zip(torch.split(pts, sizes), torch.split(state, sizes), torch.split(shift, sizes)))]
+
+
+def cloud_project(A, *, radius, min_nbrs=5, max_variation=1 / 3, max_shift=float("inf")):
+    """ls_cloud_project_f32: the kept cloud A [a,3] (fp32 HIP tensor) -> (points [a,3] fp32, state [a] int32, shift [a] fp32, counts host
+    int64 [4], sum_shift2 float) as cloud_project_batch describes them (max_variation = 1/3 is "no limit": by construction
+    variation <= 1/3; min_nbrs = 5 is not tuned).  Bit-identical to the same problem inside any cloud_project_batch."""
+    op = "cloud_project"
+    A = _cloud(A, "A", op)
+    pts, state, shift, counts, sums = _project(op, "ls_cloud_project_f32", (ptr(A), A.shape[0], float(radius), int(min_nbrs), float(max_variation),
+                                                                           float(max_shift)), (A.shape[0],), 1, A.device, A.shape[0])
+    return pts, state, shift, counts[0], float(sums[0])
 
 
 def _plane_normals(x, A, op):
