@@ -1,12 +1,11 @@
-// knn_common.h -- pieces shared by the two k-NN kernels (knn.hip: all-VALU; knn_mfma.hip: MFMA-filtered)
+// knn_common.h -- device pieces shared by the k-NN kernels (knn.hip: all-VALU tiles; knn_mfma.hip: MFMA-filtered; knn_xyz.hip: raw clouds and
+// small problems), and the kernel-side launchers knn_run (knn.hip) calls.  Which kernel runs on what grid is decided in knn_plan.h alone.
 #pragma once
 #include "ls_device.h"
+#include "knn_plan.h"
 
 namespace ls {
 
-constexpr int KNN_TQ = 64;   // queries per workgroup
-constexpr int KNN_TS = 64;   // candidates per tile
-constexpr int KNN_MAXK = 16;
 constexpr int KNN_LD = KNN_TS + 4;  // distance-tile row stride (floats), multiple of 4 for 16-byte rows
 
 template <bool FMA>
@@ -289,16 +288,17 @@ __device__ __forceinline__ unsigned kth_smallest_upper_bound(unsigned v, int K) 
     CX<31>(v, lane); CX<8>(v, lane); CX<4>(v, lane); CX<2>(v, lane); CX<1>(v, lane);                                   \
     CX<63>(v, lane); CX<16>(v, lane); CX<8>(v, lane); CX<4>(v, lane); CX<2>(v, lane); CX<1>(v, lane);
 
-// ---- host functions that knn.hip (knn_dispatch, knn_scratch_bytes) calls in the other two k-NN files
-// knn_mfma.hip
-int knn_sweep_max_ns();
-size_t knn_sweep_scratch_bytes(int B, int Nd, int dst_n, int Ns, int C);
-int knn_sweep_launch(const float* dst, const float* src, const int32_t* dst_rows, int B, int Nd, int dst_n, int Ns, int C, int K, bool fma,
-                     int32_t* idx_out, float* dist_out, const int32_t* seed_idx, int seed_n, int seed_by_row, void* scratch, hipStream_t st);
-// knn_xyz.hip
-int knn_xyz_launch(const float* dst, const float* src, const int32_t* dst_rows, int B, int Nd, int dst_n, int Ns, int K, bool fma, int32_t* idx_out,
-                   float* dist_out, hipStream_t st);
-int knn_small_launch(const float* dst, const float* src, const int32_t* dst_rows, int B, int Nd, int dst_n, int Ns, int C, int K, bool fma,
-                     int32_t* idx_out, float* dist_out, hipStream_t st);
+// ---- one k-NN build (knn_dispatch fills it in) and the kernel-side launchers: each launches what the plan names for its enumerators, decides nothing
+struct Knn {
+    const float *dst = nullptr, *src = nullptr;
+    const int32_t* dst_rows = nullptr;
+    int B = 0, Nd = 0, dst_n = 0, Ns = 0, C = 0, K = 0;
+    bool fma = false;
+    int32_t* idx_out = nullptr; float* dist_out = nullptr; void* scratch = nullptr;
+    const int32_t* seed_idx = nullptr; int seed_n = 0, seed_by_row = 0;   // hints: the tile kernel alone reads them
+};
+int knn_fused_run(const Knn& k, const KnnPlan& p, hipStream_t st);   // knn_mfma.hip: FUSED_*
+int knn_xyz_run(const Knn& k, const KnnPlan& p, hipStream_t st);     // knn_xyz.hip: XYZ_*
+int knn_small_run(const Knn& k, const KnnPlan& p, hipStream_t st);   // knn_xyz.hip: SMALL
 
 }  // namespace ls

@@ -15,6 +15,7 @@
 // decides what is worth computing.  History: rounds 2 - 4 ran this as four to five launches per layer (image, seed distances of the previous
 // layer's lists as thresholds, sweep, finish; or image, cosine store, select) that handed seed keys, survivor lists and pair cosines to each
 // other through HBM (150 MB moved for 54 MB compulsory at layer 1); they are gone (docs/history.md).
+// (When this kernel runs, its TPW, its grids and its scratch layout: knn_plan.h.  knn_fused_run launches what it names.)
 #include "knn_common.h"
 #include "ls_launch.h"
 
@@ -218,10 +219,7 @@ __global__ __launch_bounds__(64 * WPT) void knn_prep_f16_tile_kernel(const float
 #ifndef LS_KF_PK
 #define LS_KF_PK 1
 #endif
-constexpr int KF_QT = 32;        // queries per workgroup (one 32-row MFMA operand)
-constexpr int KF_WAVES = 8;
-constexpr int KF_LCAP = 64;      // survivors per query that go through the flat exact phase (one 64-lane sorting pass)
-constexpr int KF_MAXNS = KF_WAVES * 4 * 32;   // at most four tiles per wave
+constexpr int KF_LCAP = 64;      // survivors per query that go through the flat exact phase (one 64-lane sorting pass); KF_QT, KF_WAVES, KF_MAXNS: knn_plan.h
 
 template <int CC>
 struct KfLds {
@@ -540,71 +538,45 @@ __global__ __launch_bounds__(64 * KF_WAVES, FMA ? 3 : 4) void knn_fused_kernel(c
     }
 }
 
-static inline size_t pad32(size_t n) { return (n + 31) & ~(size_t)31; }
 // the f16 image of `f` ([B, N, D] rows, centre from the first rows of fc): D = 96 / 192 (C = 32 / 64)
-static int knn_prep_launch(const float* f, const float* fc, int Nc, int B, int N, int Npad, int D, unsigned short* out, float* norms, float* iscale, hipStream_t st) {
-    const int tiles = B * (Npad / 32);
-    if (D == 96)
-        hipLaunchKernelGGL((knn_prep_f16_tile_kernel<6, 3>), dim3(tiles), dim3(192), 0, st, f, fc, Nc, N, Npad, out, norms, iscale, (int32_t*)nullptr, 0LL);
-    else
-        hipLaunchKernelGGL((knn_prep_f16_tile_kernel<12, 4>), dim3(tiles), dim3(256), 0, st, f, fc, Nc, N, Npad, out, norms, iscale, (int32_t*)nullptr, 0LL);
+static int knn_prep_launch(const float* f, const float* fc, int Nc, int N, int Npad, int D, unsigned short* out, float* norms, float* iscale, unsigned grid,
+                           unsigned block, hipStream_t st) {
+    hipLaunchKernelGGL((D == 96 ? knn_prep_f16_tile_kernel<6, 3> : knn_prep_f16_tile_kernel<12, 4>), dim3(grid), dim3(block), 0, st, f, fc, Nc, N, Npad, out, norms, iscale,
+                       (int32_t*)nullptr, 0LL);
     LS_LAUNCH_CHECK();
     return LS_OK;
 }
-// largest candidate set the fused kernel takes (four 32-candidate tiles per wave); beyond it knn.hip's all-VALU kernel runs (knn_uses_sweep)
-int knn_sweep_max_ns() { return KF_MAXNS; }
-
-// scratch of one call: per-query exact-distance counters | row norms (src, dst) | inverse row scales (src, dst) | f16 images (src, dst)
-struct KfScratch { float *nsrc, *ndst, *isrc, *idst; int32_t* cnt; unsigned short *sq, *dq; size_t bytes; };
-static KfScratch kf_layout(void* scratch, int B, int Nd, int dst_n, int Ns, int D, bool self) {
-    Arena a(scratch);   // null: a sizing pass
-    KfScratch k;
-    k.cnt = a.take<int32_t>((size_t)B * Nd);      // (first: knn_sweep_stats_launch finds it whatever the rest looks like)
-    k.nsrc = a.take<float>((size_t)B * Ns);
-    k.ndst = self ? k.nsrc : a.take<float>((size_t)B * dst_n);
-    k.isrc = a.take<float>((size_t)B * Ns);
-    k.idst = self ? k.isrc : a.take<float>((size_t)B * dst_n);
-    k.sq = a.take<unsigned short>((size_t)B * pad32(Ns) * D);
-    k.dq = self ? k.sq : a.take<unsigned short>((size_t)B * pad32(dst_n) * D);
-    k.bytes = a.bytes();
-    return k;
-}
-size_t knn_sweep_scratch_bytes(int B, int Nd, int dst_n, int Ns, int C) { return kf_layout(nullptr, B, Nd, dst_n, Ns, 3 * C, false).bytes; }
 
 template <int CC>
-static int knn_sweep_launch_t(const float* dst, const float* src, const int32_t* dst_rows, int B, int Nd, int dst_n, int Ns, int K, bool fma,
-                              int32_t* idx_out, float* dist_out, void* scratch, hipStream_t st) {
+static int knn_fused_run_t(const Knn& k, const KnnPlan& p, hipStream_t st) {
     constexpr int D = 3 * CC;
-    const KfScratch k = kf_layout(scratch, B, Nd, dst_n, Ns, D, dst == src);
-    const int ns_pad = (int)pad32(Ns), dst_npad = (int)pad32(dst_n);
-    int rc = knn_prep_launch(src, src, Ns, B, Ns, ns_pad, D, k.sq, k.nsrc, k.isrc, st);
+    char* base = (char*)k.scratch;
+    const KnnFusedLayout& l = p.fl;     // (knn_plan.h: the one statement of the scratch layout)
+    float *nsrc = (float*)(base + l.nsrc), *ndst = (float*)(base + l.ndst), *isrc = (float*)(base + l.isrc), *idst = (float*)(base + l.idst);
+    unsigned short *sq = (unsigned short*)(base + l.sq), *dq = (unsigned short*)(base + l.dq);
+    int32_t* cnt = (int32_t*)(base + l.cnt);
+    int rc = knn_prep_launch(k.src, k.src, k.Ns, k.Ns, p.ns_pad, D, sq, nsrc, isrc, p.prep_grid[0], p.prep_block, st);
+    if (rc == LS_OK && p.prep_grid[1])   // same centre for both sets: the candidates' first rows
+        rc = knn_prep_launch(k.dst, k.src, k.Ns, k.dst_n, p.dst_npad, D, dq, ndst, idst, p.prep_grid[1], p.prep_block, st);
     if (rc != LS_OK) return rc;
-    if (dst != src) {   // same centre for both sets: the candidates' first rows
-        rc = knn_prep_launch(dst, src, Ns, B, dst_n, dst_npad, D, k.dq, k.ndst, k.idst, st);
-        if (rc != LS_OK) return rc;
-    }
-    const int qtiles = cdiv(Nd, KF_QT), tpw = cdiv(ns_pad / 32, KF_WAVES);
     const float epsF = 1.02f * 0.0009765625f + 6.0f * (float)(D + 4) * 5.9604645e-8f + 9.5367431640625e-7f + 4.76837158203125e-7f;   // eps_b of the f16 image + 2^-21 (d^, lo, hi)
-#define LS_KF(T) do { if (fma) hipLaunchKernelGGL((knn_fused_kernel<CC, true, T>), dim3(B * qtiles), dim3(64 * KF_WAVES), 0, st, dst, src, dst_rows, k.dq, k.sq, k.ndst, k.nsrc, k.idst, k.isrc, Nd, dst_n, dst_npad, Ns, ns_pad, K, qtiles, epsF, idx_out, dist_out, k.cnt); \
-                   else hipLaunchKernelGGL((knn_fused_kernel<CC, false, T>), dim3(B * qtiles), dim3(64 * KF_WAVES), 0, st, dst, src, dst_rows, k.dq, k.sq, k.ndst, k.nsrc, k.idst, k.isrc, Nd, dst_n, dst_npad, Ns, ns_pad, K, qtiles, epsF, idx_out, dist_out, k.cnt); } while (0)
-    if (tpw <= 1) LS_KF(1); else if (tpw == 2) LS_KF(2); else LS_KF(4);
-#undef LS_KF
+    const auto kernel = p.tpw == 1 ? (k.fma ? knn_fused_kernel<CC, true, 1> : knn_fused_kernel<CC, false, 1>)
+                      : p.tpw == 2 ? (k.fma ? knn_fused_kernel<CC, true, 2> : knn_fused_kernel<CC, false, 2>)
+                                   : (k.fma ? knn_fused_kernel<CC, true, 4> : knn_fused_kernel<CC, false, 4>);
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.block), 0, st, k.dst, k.src, k.dst_rows, dq, sq, ndst, nsrc, idst, isrc, k.Nd, k.dst_n, p.dst_npad, k.Ns, p.ns_pad, k.K,
+                       p.qtiles, epsF, k.idx_out, k.dist_out, cnt);
     LS_LAUNCH_CHECK();
     return LS_OK;
 }
 
-// hints (seed_idx: the previous layer's lists) are accepted for the caller's sake and IGNORED: the fused kernel derives its thresholds from the
-// sweep itself, and hints never influenced a result
-int knn_sweep_launch(const float* dst, const float* src, const int32_t* dst_rows, int B, int Nd, int dst_n, int Ns, int C, int K,
-                     bool fma, int32_t* idx_out, float* dist_out, const int32_t* /*seed_idx*/, int /*seed_n*/, int /*seed_by_row*/, void* scratch,
-                     hipStream_t st) {
-    LS_REQUIRE(C == 32 || C == 64, "knn_sweep: only C == 32 / 64 layers are supported (C=%d)", C);
-    LS_REQUIRE((int)pad32(Ns) <= KF_MAXNS && K <= KNN_MAXK, "knn_sweep: Ns=%d K=%d beyond the fused kernel (Ns <= %d, K <= 16)", Ns, K, KF_MAXNS);
-    if (C == 32) return knn_sweep_launch_t<32>(dst, src, dst_rows, B, Nd, dst_n, Ns, K, fma, idx_out, dist_out, scratch, st);
-    return knn_sweep_launch_t<64>(dst, src, dst_rows, B, Nd, dst_n, Ns, K, fma, idx_out, dist_out, scratch, st);
+// (hints are ignored: the fused kernel derives its thresholds from the sweep itself, and hints never influenced a result)
+int knn_fused_run(const Knn& k, const KnnPlan& p, hipStream_t st) {
+    LS_REQUIRE(k.C == 32 || k.C == 64, "knn_sweep: only C == 32 / 64 layers are supported (C=%d)", k.C);
+    LS_REQUIRE(p.ns_pad <= KF_MAXNS && k.K <= KNN_MAXK, "knn_sweep: Ns=%d K=%d beyond the fused kernel (Ns <= %d, K <= 16)", k.Ns, k.K, KF_MAXNS);
+    return k.C == 32 ? knn_fused_run_t<32>(k, p, st) : knn_fused_run_t<64>(k, p, st);
 }
 
-// Exact-phase statistics of the LAST fused call that used `scratch` (bench.py's hardware-utilisation roofline; profiled passes only):
+// Exact-phase statistics of the LAST fused call that used `scratch` (KnnPlan::stats; the counters are the scratch's first piece; bench.py's hardware-utilisation roofline; profiled passes only):
 // out[0] += sum over the queries of the candidates that were given a canonical distance (stored by the kernel as -(count + 1); a query that
 // overflowed its list scanned all Ns), out[1] += the number of queries.
 __global__ __launch_bounds__(256) void knn_stats_kernel(const int32_t* __restrict__ surv_cnt, long long nq, unsigned long long* __restrict__ out) {
@@ -617,9 +589,8 @@ __global__ __launch_bounds__(256) void knn_stats_kernel(const int32_t* __restric
     if ((threadIdx.x & 63) == 0) atomicAdd(&out[0], s);
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&out[1], (unsigned long long)nq);
 }
-int knn_sweep_stats_launch(const void* scratch, int B, int Nd, int dst_n, int Ns, unsigned long long* out, hipStream_t st) {
+int knn_sweep_stats_launch(const void* scratch, int B, int Nd, unsigned long long* out, hipStream_t st) {
     const size_t nq = (size_t)B * Nd;
-    (void)dst_n; (void)Ns;
     hipLaunchKernelGGL(knn_stats_kernel, dim3((unsigned)std::min<size_t>(cdiv((long long)nq, 256), 256)), dim3(256), 0, st, (const int32_t*)scratch, (long long)nq, out);
     LS_LAUNCH_CHECK();
     return LS_OK;

@@ -16,11 +16,10 @@
 // No barriers, no tiles, no insertion loop; exact by construction (everything <= an upper bound of the K-th key is sorted by
 // the full lexicographic key).  Encoder layer-0 shape (64 x 1024 x 1024): 164 -> 67 us (rocprofv3); ~750 wave instructions
 // per query (distances 150, threshold network 125, compaction 270, key network 200) = VALU-issue bound.
+// (Which raw-cloud instantiation runs, the queries per wave and both grids: knn_plan.h.  knn_xyz_run / knn_small_run launch what it names.)
 #include "knn_common.h"
 
 namespace ls {
-
-constexpr int KX_CH = 1024;   // candidates per chunk (16 per lane)
 
 template <bool FMA, bool SINGLE>
 __global__ __launch_bounds__(256, 4) void knn_xyz_kernel(const float* __restrict__ dst, const float* __restrict__ src,
@@ -119,22 +118,13 @@ __global__ __launch_bounds__(256, 4) void knn_xyz_kernel(const float* __restrict
     }
 }
 
-int knn_xyz_launch(const float* dst, const float* src, const int32_t* dst_rows, int B, int Nd, int dst_n, int Ns, int K, bool fma,
-                   int32_t* idx_out, float* dist_out, hipStream_t st) {
-    // queries per wave: 16 amortises the candidate registers; fewer when the launch would not fill the 256 CUs
-    int qpw = 16;
-    while (qpw > 1 && (long long)B * cdiv(Nd, 4 * qpw) < 1024) qpw >>= 1;
-    const int qblocks = cdiv(Nd, 4 * qpw);
-    const bool single = Ns <= KX_CH;
-#define LS_KX(F, S) hipLaunchKernelGGL((knn_xyz_kernel<F, S>), dim3(B * qblocks), dim3(256), 0, st, dst, src, dst_rows, Nd, dst_n, Ns, K, \
-                                       idx_out, dist_out, qpw, qblocks)
-    if (fma) { if (single) LS_KX(true, true); else LS_KX(true, false); }
-    else { if (single) LS_KX(false, true); else LS_KX(false, false); }
-#undef LS_KX
+int knn_xyz_run(const Knn& k, const KnnPlan& p, hipStream_t st) {
+    const bool single = p.kernel == KnnKernel::XYZ_SINGLE;
+    const auto kernel = k.fma ? (single ? knn_xyz_kernel<true, true> : knn_xyz_kernel<true, false>) : (single ? knn_xyz_kernel<false, true> : knn_xyz_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.block), 0, st, k.dst, k.src, k.dst_rows, k.Nd, k.dst_n, k.Ns, k.K, k.idx_out, k.dist_out, p.qpw, p.qblocks);
     LS_LAUNCH_CHECK();
     return LS_OK;
 }
-
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Small feature-space problems (encoder layers 5 and 6: 32 queries x 128 / 32 candidates per instance, D = 384 / 768).
@@ -145,7 +135,7 @@ int knn_xyz_launch(const float* dst, const float* src, const int32_t* dst_rows, 
 // and adds the twelve terms in canonical order (j = c*3 + x), so no LDS transpose is needed.  Selection: the 8 x 32 distance
 // tile goes through LDS to two waves whose 16-lane rows merge it (knn_common.h).  Same arithmetic chain, same keys.
 __device__ __forceinline__ int cdiv_dev(int a, int b) { return (a + b - 1) / b; }
-constexpr int KSM_Q = 8, KSM_S = 32, KSM_CCH = 128;
+constexpr int KSM_S = 32, KSM_CCH = 128;   // candidates per pass, channels per pass (KSM_Q queries per workgroup: knn_plan.h)
 constexpr int KSM_ROW = 3 * KSM_CCH + 4;     // floats; (ROW / 4) odd -> the 16 lanes of a ds_read_b128 group hit distinct banks
 
 template <bool FMA>
@@ -245,16 +235,10 @@ __global__ __launch_bounds__(256, 2) void knn_small_kernel(const float* __restri
     }
 }
 
-int knn_small_launch(const float* dst, const float* src, const int32_t* dst_rows, int B, int Nd, int dst_n, int Ns, int C, int K, bool fma,
-                     int32_t* idx_out, float* dist_out, hipStream_t st) {
-    LS_REQUIRE(C % 4 == 0, "knn_small: C=%d must be a multiple of 4", C);
-    const int qblocks = cdiv(Nd, KSM_Q);
-    if (fma)
-        hipLaunchKernelGGL(knn_small_kernel<true>, dim3(B * qblocks), dim3(256), 0, st, dst, src, dst_rows, Nd, dst_n, Ns, C, K, idx_out,
-                           dist_out, qblocks);
-    else
-        hipLaunchKernelGGL(knn_small_kernel<false>, dim3(B * qblocks), dim3(256), 0, st, dst, src, dst_rows, Nd, dst_n, Ns, C, K, idx_out,
-                           dist_out, qblocks);
+int knn_small_run(const Knn& k, const KnnPlan& p, hipStream_t st) {
+    LS_REQUIRE(k.C % 4 == 0, "knn_small: C=%d must be a multiple of 4", k.C);
+    hipLaunchKernelGGL(k.fma ? knn_small_kernel<true> : knn_small_kernel<false>, dim3(p.grid), dim3(p.block), 0, st, k.dst, k.src, k.dst_rows, k.Nd, k.dst_n, k.Ns,
+                       k.C, k.K, k.idx_out, k.dist_out, p.qblocks);
     LS_LAUNCH_CHECK();
     return LS_OK;
 }

@@ -5,16 +5,26 @@
 #include "ls_common.h"
 #include "gemm_plan.h"
 #include "edge_plan.h"
+#include "knn_plan.h"
 
 namespace ls {
 
 // ---- knn.hip
 int knn_dispatch(const float* dst, const float* src, const int32_t* dst_rows, int B, int Nd, int dst_n, int Ns, int C, int K, unsigned flags, int32_t* idx_out,
                  float* dist_out, void* scratch, const int32_t* seed_idx, int seed_n, int seed_by_row, hipStream_t st);
-size_t knn_scratch_bytes(int B, int Nd, int dst_n, int Ns, int C, bool seeded, unsigned flags);
-bool knn_would_sweep(int C, int Ns, unsigned flags);
+size_t knn_scratch_bytes(int B, int Nd, int dst_n, int Ns, int C, unsigned flags);
+// (knn_plan.h: the kernel choice) the traits of a knn_dispatch call with these arguments; self: dst == src
+inline KnnTraits knn_traits(bool self, int B, int Nd, int dst_n, int Ns, int C, int K, unsigned flags, bool seeded, bool has_scratch) {
+    KnnTraits t;
+    t.B = B; t.Nd = Nd; t.dst_n = dst_n; t.Ns = Ns; t.C = C; t.K = K;
+    t.fma = (flags & LS_FLAG_CONTRACT_FMA) != 0;
+    t.valu_only = (flags & LS_FLAG_KNN_VALU_ONLY) != 0;
+    t.seeded = seeded; t.self = self; t.has_scratch = has_scratch;
+    return t;
+}
 // ---- knn_mfma.hip
-int knn_sweep_stats_launch(const void* scratch, int B, int Nd, int dst_n, int Ns, unsigned long long* out, hipStream_t st);
+// the exact-phase counters of the last call on `scratch` whose plan says stats, added to out[0..1]
+int knn_sweep_stats_launch(const void* scratch, int B, int Nd, unsigned long long* out, hipStream_t st);
 // ---- fps.hip
 int fps_dispatch(const float* pts, const int32_t* lengths, int B, int N, int K, unsigned flags, int32_t* idx_out, float* pts_out, void* ws, size_t ws_bytes,
                  hipStream_t st);

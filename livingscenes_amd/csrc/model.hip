@@ -156,8 +156,7 @@ static int make_plan(const ls_model_desc& d, int B, int N, EncPlan& p) {
         // split-K slabs of the under-filled GEMMs (residual global conv: per-point part and per-instance mean part)
         maxGws = std::max(maxGws, std::max(gemm_scratch_floats(B * p.Nd[i] * 3, 2 * Co, Co), gemm_scratch_floats(B * 3, 4 * Co, Co)));
         maxKnn = std::max(maxKnn, (size_t)p.Nd[i] * 16);
-        maxKs = std::max(maxKs, std::max(knn_scratch_bytes(B, p.Nd[i], p.Ns[i], p.Ns[i], Cin, true, 0u),
-                                        knn_scratch_bytes(B, p.Nd[i], p.Ns[i], p.Ns[i], Cin, false, 0u)));
+        maxKs = std::max(maxKs, knn_scratch_bytes(B, p.Nd[i], p.Ns[i], p.Ns[i], Cin, 0u));
     }
     LS_REQUIRE(d.num_knn == 16, "encoder: num_knn=%d unsupported (16)", d.num_knn);
     LS_REQUIRE(p.Ns[p.L - 1] >= 1, "encoder: bad schedule");
@@ -627,9 +626,9 @@ static int encode_enqueue(ls_model_t* m, const EncPlan& p, const float* x, int B
                 rc = knn_dispatch(cur, cur, dst_rows, B, Nd, Ns, Ns, Cin, 16, flags, knn, nullptr, ws + p.o_knns, nullptr, 0, 0, st);
             }
             if (rc != LS_OK) return rc;
-            if (m->profiling && m->knn_stats && knn_would_sweep(Cin, Ns, flags)) {
+            if (m->profiling && m->knn_stats && knn_plan(knn_traits(true, B, Nd, Ns, Ns, Cin, 16, flags, false, true)).stats) {   // (the plan of the call above)
                 // (outside the launch's event bracket) how many candidates got a canonical distance: ls_profile_knn_stats
-                rc = knn_sweep_stats_launch(ws + p.o_knns, B, Nd, Ns, Ns, m->knn_stats + 2 * i, st);
+                rc = knn_sweep_stats_launch(ws + p.o_knns, B, Nd, m->knn_stats + 2 * i, st);
                 if (rc != LS_OK) return rc;
             }
             if (m->overlap_gemm) LS_HIP_CHECK(hipStreamWaitEvent(st, m->ev_tab[i], 0));

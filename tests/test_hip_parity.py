@@ -197,6 +197,39 @@ def test_knn_dst_rows_and_self():
     assert (idx[:, :, 0].cpu().numpy() == sel).all()  # a point is its own nearest neighbour
 
 
+def _launch_recorder():
+    import importlib.util
+    import sys
+    tools = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools")
+    if tools not in sys.path:
+        sys.path.insert(0, tools)
+    spec = importlib.util.spec_from_file_location("record_gemm_launches", os.path.join(tools, "record_gemm_launches.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+_REC = _launch_recorder()
+
+
+@pytest.fixture(scope="module")
+def knn_record():
+    return _REC.load("knn")
+
+
+@pytest.mark.parametrize("key,case", _REC.knn_ladder(), ids=[k for k, _ in _REC.knn_ladder()])
+def test_knn_plan_ladder_bit_exact(key, case, knn_record):
+    """Both sides of every boundary of csrc/knn_plan.h (tests/test_knn_plan_cpu.py holds the launches themselves to the same record): indices and
+    distances bit-equal to the oracle, and to what the library gave before the plan existed (tests/golden/knn_launches.json)."""
+    from oracle import canon
+    dst, src, rows, seeds, q = _REC.knn_inputs(key, case)
+    ref, refd = canon.knn_c(q, src, 16, contract=case["contract"], return_dist=True)
+    idx, dist = _REC.knn_call(case, dst, src, rows, seeds)
+    assert (ref >= 0).all()      # every case has at least 16 candidates
+    assert np.array_equal(idx, ref) and np.array_equal(dist, refd)
+    assert _REC.knn_sha(idx, dist) == knn_record[f"{_REC.MODES[0]}:{key}"]["sha256"]
+
+
 # ------------------------------------------------------------------------------------------------ FPS
 @pytest.mark.parametrize("contract", [0, 1])
 @pytest.mark.parametrize("N,K", [(128, 32), (200, 70), (256, 64), (512, 128), (1024, 512), (1500, 300), (2048, 600), (5000, 1024), (20000, 1024)])

@@ -2,6 +2,7 @@
 
     python tests/tools/record_gemm_launches.py [--out PATH]                 -> tests/golden/gemm_launches.json   (GPU, rocprofv3 on the PATH)
     python tests/tools/record_gemm_launches.py --family edge [--out PATH]   -> tests/golden/edge_launches.json   (the edge-conv layers, below)
+    python tests/tools/record_gemm_launches.py --family knn [--out PATH]    -> tests/golden/knn_launches.json    (the k-NN builds, below)
 
 The wide, the tiled and the persistent kernels agree to the bit by design, so no numerical test sees a change of the kernel CHOICE; it only
 shows as a slower benchmark line.  The choice is therefore recorded from the library BEFORE a change to the dispatch code (csrc/gemm_plan.h)
@@ -16,7 +17,11 @@ left out.  ladder() / model_ladder() are the one statement of the cases, shared 
 
 --family edge records the encoder's edge-conv layers the same way (csrc/edge_plan.h; tests/test_edge_plan_cpu.py, tests/test_hip_range.py):
 edge_ladder() runs HipModel.edgeconv per layer and whole ls_encode calls; the record keeps the kernels of edge.hip / edge_fused.hip and the two
-mean kernels of the global conv (their grid is the only visible trace of the column sums), counts the table GEMMs, and hashes every output."""
+mean kernels of the global conv (their grid is the only visible trace of the column sums), counts the table GEMMs, and hashes every output.
+
+--family knn records ops.knn (ls_knn_f32) on knn_ladder(): both sides of every boundary of csrc/knn_plan.h at the smallest size that reaches it
+(tests/test_knn_plan_cpu.py replays the plan, tests/test_hip_parity.py holds every case to the oracle and to the recorded hash).  The k-NN
+kernels do not read LS_GEMM_MODE: one process, filed under the default mode."""
 import argparse
 import binascii
 import csv
@@ -32,7 +37,7 @@ REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), "..", ".."))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 GOLDEN = os.path.join(REPO, "tests", "golden", "gemm_launches.json")
-GOLDENS = {"gemm": GOLDEN, "edge": os.path.join(REPO, "tests", "golden", "edge_launches.json")}
+GOLDENS = {"gemm": GOLDEN, "edge": os.path.join(REPO, "tests", "golden", "edge_launches.json"), "knn": os.path.join(REPO, "tests", "golden", "knn_launches.json")}
 MODES = ("f16", "bf16x3", "fp32")          # GemmTraits::mode 0 / 1 / 2; the first is the default (no LS_GEMM_MODE)
 MARKER_ROWS = 52                            # 13 workgroups of gemm_rowmax_kernel
 TEST_MAX_OUT = 1 << 22                      # outputs up to 4 M floats are hashed (tests/test_hip_range.py runs these cases), plus TEST_WIDE
@@ -53,6 +58,13 @@ EDGE_UNITS = {"kernels": UNITS["kernels"].replace("gemm_w2_kernel", "edge_attn_k
                        "in order for edgeconv(...), sorted for encode(...) (two side streams make the trace's order vary)",
               "tables": "edgeconv(...) only: how many GEMM launches formed the case's tables",
               "sha256": "of the output's bytes (encode: z_so3, z_inv, s, t one after the other); inputs from numpy.random.default_rng(crc32(case key))"}
+
+
+KNN_UNITS = {"kernels": UNITS["kernels"].replace(" (LDS: the static part; the dynamic LDS of gemm_w2_kernel does not show)", ""),
+             "launch": UNITS["launch"],
+             "cases": "by key; knn_ladder() of tests/tools/record_gemm_launches.py states the sizes and the data behind a key, knn_traits() the KnnTraits; the "
+                      "launches of the kernels of knn.hip / knn_mfma.hip / knn_xyz.hip in order (one process: the k-NN kernels have no arithmetic modes)",
+             "sha256": "of the bytes of idx [B][Nd][16] int32, then dist [B][Nd][16] float32; inputs from knn_inputs()"}
 
 
 def cdiv(a, b):
@@ -376,11 +388,103 @@ def edge_traits(ecfg, mode, i, B, Ns, Nd, rows, fuse_q=1, fuse_t=1, encode=False
                 want_colsum=int(glob and glob_fuse))
 
 
+# ------------------------------------------------------------------------------------------------ the k-NN builds (--family knn)
+def knn_ladder():
+    """[(key, case)]: case = the sizes of one ops.knn call with K = 16.  self: the queries are rows of the candidate set (dst is src; through
+    dst_rows where Nd != Ns); otherwise dst is a set of its own of dst_n rows (rows: Nd of them through dst_rows).  Every shape with contract 0
+    and 1 (LS_FLAG_CONTRACT_FMA)."""
+    def case(B, Nd, Ns, C, self=0, dst_n=None, seeded=0, valu_only=0):
+        dst_n = Ns if self else (dst_n or Nd)
+        return dict(B=B, Nd=Nd, dst_n=dst_n, Ns=Ns, C=C, self=self, rows=int(dst_n != Nd), seeded=seeded, valu_only=valu_only)
+    shapes = []
+    # raw clouds (C = 1): one chunk of 1024 candidates | two; queries per wave 1 (7 queries), 16 (B cdiv(Nd, 64) = 1024), 8 (512)
+    shapes += [case(2, 40, 1024, 1), case(2, 40, 1025, 1), case(1, 7, 100, 1), case(16, 4096, 100, 1), case(16, 2048, 100, 1)]
+    # 32 | 33 queries: the small kernel against the fused one (C = 32 / 64) or the tile kernel (C = 128 / 256); seeded, 32 queries take the fused one
+    shapes += [case(2, Nd, Ns, C) for C, Ns in ((32, 128), (64, 128), (128, 128), (256, 32)) for Nd in (32, 33)]
+    shapes += [case(2, 32, 128, 32, seeded=1)]
+    # the fused kernel's candidate tiles per wave: 8 | 9, 16 | 17, 24 | 25 tiles of 32; 1024 candidates still fused, 1025 tiled (17 tiles of 64: 16 splits asked,
+    # 9 of two tiles run); 1000 pads to 1024; LS_FLAG_KNN_VALU_ONLY; one call with a destination set of its own (77 rows, 40 of them queried)
+    for C in (32, 64):
+        shapes += [case(2, 40, Ns, C, self=1) for Ns in (256, 257, 512, 513, 768, 769, 1024, 1025, 1000)]
+        shapes += [case(2, 40, 300, C, self=1, valu_only=1)]
+    shapes += [case(2, 40, 300, 32, dst_n=77)]
+    # the tile kernel (C = 96): one candidate tile | two (two splits); 18 tiles on 2 workgroups: 16 splits asked, 9 of two tiles run; 512 workgroups: never
+    # split; 510 and 256: cdiv(256, workgroups) = 1, not split either; 254: two splits; seeded with LS_FLAG_KNN_VALU_ONLY: hints, and the merge drops what
+    # it meets twice
+    shapes += [case(2, 33, 64, 96), case(2, 33, 65, 96), case(1, 70, 1100, 96), case(256, 128, 130, 96), case(255, 128, 130, 96), case(128, 128, 130, 96),
+               case(127, 128, 130, 96), case(2, 70, 130, 64, seeded=1, valu_only=1)]
+    c = []
+    for s in shapes:
+        for contract in (0, 1):
+            d = dict(s, contract=contract)
+            c.append(("knn(" + ", ".join(f"{k}={v}" for k, v in d.items() if v or k in ("B", "Nd", "Ns", "C", "contract")) + ")", d))
+    assert len({k for k, _ in c}) == len(c)
+    return c
+
+
+def knn_traits(case, has_scratch=1):
+    """KnnTraits (csrc/knn_plan.h) of a knn_ladder() case.  ops.knn hands over the workspace the sizing call asks for; where that is nothing,
+    no choice depends on it."""
+    return dict(B=case["B"], Nd=case["Nd"], dst_n=case["dst_n"], Ns=case["Ns"], C=case["C"], K=16, fma=case["contract"], valu_only=case["valu_only"],
+                seeded=case["seeded"], self=case["self"], has_scratch=has_scratch)
+
+
+def knn_inputs(key, case):
+    """numpy (dst or None for self, src, dst_rows or None, seeds or None, the query rows [B][Nd][3][C] for the oracle): the conventions of
+    test_knn_bit_exact -- candidate 7 of instance 0 repeats candidate 2 (a tie: the lower index wins), its query 0 is that row (distance 0)."""
+    import numpy as np
+    B, Nd, dst_n, Ns, C = (case[k] for k in ("B", "Nd", "dst_n", "Ns", "C"))
+    rng = np.random.default_rng(_seed(key))
+    src = rng.standard_normal((B, Ns, 3, C)).astype(np.float32)
+    src[0, 7] = src[0, 2]
+    dst = None if case["self"] else rng.standard_normal((B, dst_n, 3, C)).astype(np.float32)
+    rows = np.stack([rng.permutation(dst_n)[:Nd] for _ in range(B)]).astype(np.int32) if case["rows"] else None
+    if case["self"]:
+        if rows is not None:
+            rows[0, 0] = 2
+    else:
+        dst[0, rows[0, 0] if rows is not None else 0] = src[0, 2]
+    seeds = None
+    if case["seeded"]:     # hints: in and out of range, one repeated; a result never depends on them
+        seeds = rng.integers(-3, Ns + 5, (B, Nd, 16)).astype(np.int32)
+        seeds[:, :, 1] = seeds[:, :, 0]
+    from_set = src if case["self"] else dst
+    q = from_set if rows is None else np.stack([from_set[b][rows[b]] for b in range(B)])
+    return dst, src, rows, seeds, q
+
+
+def knn_call(case, dst, src, rows, seeds):
+    """ops.knn on the current device -> (idx, dist) as numpy."""
+    import torch
+    from livingscenes_amd import _lib, ops
+    dev = torch.device("cuda:0")
+    up = lambda a: None if a is None else torch.from_numpy(a).to(dev)
+    s = up(src)
+    d = s if dst is None else up(dst)
+    flags = (_lib.FLAG_CONTRACT_FMA if case["contract"] else 0) | (_lib.FLAG_KNN_VALU_ONLY if case["valu_only"] else 0)
+    idx, dist = ops.knn(d, s, 16, dst_rows=up(rows), flags=flags, return_dist=True, seeds=up(seeds))
+    return idx.cpu().numpy(), dist.cpu().numpy()
+
+
+def knn_sha(idx, dist):
+    return hashlib.sha256(idx.tobytes() + dist.tobytes()).hexdigest()
+
+
+def run_knn(key, case):
+    dst, src, rows, seeds, _ = knn_inputs(key, case)
+    marker()
+    idx, dist = knn_call(case, dst, src, rows, seeds)      # (the copies back to the host synchronise: the closing marker comes after the case's launches)
+    marker()
+    return 0, knn_sha(idx, dist)
+
+
 # ------------------------------------------------------------------------------------------------ worker (under the trace) and collector
 def cases_of(mode, family="gemm"):
     """[(key, traits, runner)] of one mode's process, in launch order: the public ladder, then the model ladder (edge: edge_ladder())."""
     if family == "edge":
         return [(k, None, ("model", k, mdl, op, a, o, True)) for k, mdl, op, a, o in edge_ladder()]
+    if family == "knn":
+        return [(k, None, ("knn", k, c)) for k, c in knn_ladder()]
     out = [(k, [t], ("public", k, e, t)) for k, e, t in ladder()]
     out += [(k, tr, ("model", k, mdl, op, a, o)) for k, mdl, op, a, o, tr in model_ladder(mode)]
     return out
@@ -408,6 +512,8 @@ def worker(mode, sidecar, family):
     for key, traits, run in cases_of(mode, family):
         if run[0] == "public":
             status, sha = run_public(*run[1:])
+        elif run[0] == "knn":
+            status, sha = run_knn(*run[1:])
         else:
             status, sha = run_model(models, *run[1:])
         rec.append({"key": key, "status": status, "sha256": sha})
@@ -457,6 +563,10 @@ def is_edge(l):
     return l[0].startswith(("ls::edge_", "ls::glob_mean_gemv_kernel", "ls::mean_points_kernel"))
 
 
+def is_knn(l):
+    return l[0].startswith("ls::knn_")
+
+
 def segment(launches, ncases):
     """The launches between the 2 k-th and the 2 k + 1-st marker belong to case k."""
     marks = [i for i, l in enumerate(launches) if is_marker(l)]
@@ -466,7 +576,7 @@ def segment(launches, ncases):
 
 def record(family="gemm", timeout=600):
     cases = {}
-    for mode in MODES:
+    for mode in (MODES[:1] if family == "knn" else MODES):
         with tempfile.TemporaryDirectory(prefix="ls_gemm_trace_") as tmp:
             sidecar = os.path.join(tmp, "cases.json")
             env = dict(os.environ)
@@ -480,6 +590,8 @@ def record(family="gemm", timeout=600):
                 rec = json.load(f)
             for r, launches in zip(rec, segment(read_trace(os.path.join(tmp, "trace")), len(rec))):
                 c = cases[f"{mode}:{r['key']}"] = {"status": r["status"], "launches": [l for l in launches if is_gemm(l)], "sha256": r["sha256"]}
+                if family == "knn":
+                    c["launches"] = [l for l in launches if is_knn(l)]
                 if family == "edge":
                     c["launches"] = [l for l in launches if is_edge(l)]
                     if r["key"].startswith("encode("):
@@ -544,5 +656,5 @@ if __name__ == "__main__":
         worker(a.worker, a.sidecar, a.family)
     else:
         rec = record(a.family)
-        dump(rec, a.out or GOLDENS[a.family], EDGE_UNITS if a.family == "edge" else UNITS)
+        dump(rec, a.out or GOLDENS[a.family], {"edge": EDGE_UNITS, "knn": KNN_UNITS}.get(a.family, UNITS))
         print(f"{len(rec)} cases -> {a.out or GOLDENS[a.family]}")
