@@ -63,7 +63,8 @@ typedef enum {
  * off_dec_xyz_t, the invariant decoder_type "deepsdf"; 107: the ragged multi-mesh metrics ls_mesh_contains_batch_f64 /
  * ls_mesh_distance_batch_f64 / ls_mesh_sample_batch_f64; symbols added since -- ls_reg_metrics_batch, ls_mesh_cluster_f64 / ls_mesh_cluster_batch_f64,
  * ls_cloud_merge_f32 / ls_cloud_merge_batch_f32, ls_cloud_nearest_f32 / ls_cloud_nearest_batch_f32, ls_cloud_icp_f32 / ls_cloud_icp_batch_f32,
- * ls_cloud_normals_f32 / ls_cloud_normals_batch_f32, ls_cloud_icp_plane_f32 / ls_cloud_icp_plane_batch_f32, ls_cloud_project_f32 / ls_cloud_project_batch_f32 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
+ * ls_cloud_normals_f32 / ls_cloud_normals_batch_f32, ls_cloud_icp_plane_f32 / ls_cloud_icp_plane_batch_f32, ls_cloud_project_f32 / ls_cloud_project_batch_f32,
+ * ls_mesh_render_depth_f64 / ls_mesh_render_depth_batch_f64, ls_depth_points_f32 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
  * binding compares it with the header it was written against and refuses a mismatch (livingscenes_amd/_lib.py: load). */
 #define LS_ABI_VERSION 107
 int ls_version(void);
@@ -598,6 +599,63 @@ size_t ls_mesh_sample_batch_workspace_bytes(int M, long long nf_total);
 int ls_mesh_sample_batch_f64(int M, const double* vertices, long long nv_total, const long long* vert_off, const int32_t* faces, long long nf_total,
                              const long long* face_off, long long count_total, const long long* count_off, const unsigned long long* seeds,
                              double* points_out, int64_t* face_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Depth views of triangle meshes and their back-projection (csrc/meshrender.hip, csrc/render_plan.h): the device counterpart of the
+ * reference's utils/render.py (render_depth / pointcloud), which renders with pyrender's OpenGL rasteriser.  PARITY WITH THAT RASTERISER
+ * IS NOT PINNED (pyrender is not available to the tests); the semantics are defined here and tests/render_oracle.py is the same text as
+ * NumPy, which the kernels reproduce bit for bit.  Everything is float64 unless stated, no contraction anywhere.
+ * Per view: world_to_cam E [3,4] (camera: x right, y down, z forward), intrinsics (fx, fy, cx, cy); per call H, W, znear > 0.
+ * Per (view, face), corners i = 0, 1, 2 at (x, y, z):
+ *   1. c_i = ((E[:,0] x + E[:,1] y) + E[:,2] z) + E[:,3]
+ *   2. near test: the face is dropped for the view if any c_i.z < znear or is not finite (no clipping)                    -> counts[2]
+ *   3. u_i = fx (c_i.x / c_i.z) + cx, v_i = fy (c_i.y / c_i.z) + cy
+ *   4. snap to 1/256 pixel: xs_i = (int64) floor(u_i 256 + 0.5), ys_i likewise; the face is dropped if a value is not finite or exceeds
+ *      2^24 in magnitude (every edge function then stays below 2^53)                                                    -> counts[3]
+ *   5. pixel box px in [ceil(min xs / 256), floor(max xs / 256)] clipped to [0, W-1], py likewise (floor / ceil division of negative
+ *      integers included); a face that got here with A != 0 (below; A is the same at every pixel) is counted             -> counts[1]
+ *   6. at pixel (px, py): X = 256 px, Y = 256 py (the ray goes through the INTEGER pixel coordinate, so ls_depth_points_f32 is the exact
+ *      inverse); edge(i,j) = (xs_j - xs_i)(Y - ys_i) - (ys_j - ys_i)(X - xs_i) in int64; e0 = edge(1,2), e1 = edge(2,0), e2 = edge(0,1),
+ *      A = e0 + e1 + e2.  Covered iff A != 0 and (all three >= 0 or all three <= 0): no back-face culling, inclusive edges -- integer edge
+ *      functions are exactly antisymmetric, so both faces at a shared edge cover its pixels and there are no cracks.
+ *      z = A / ((e0 iz_0 + e1 iz_1) + e2 iz_2) with iz_i = 1.0 / c_i.z (perspective-correct), d = (float) z.
+ *   7. the pixel's winner is the minimum of the key (bits of d as uint32) << 32 | face index (local to the mesh): nearest depth, on equal
+ *      fp32 depth the lower face index.
+ * Outputs (DEVICE): depth_out [views,H,W] fp32 (0: nothing hit, pyrender's convention), face_out [views,H,W] int32 (-1: none), counts_out
+ * [views,4] = pixels hit, faces counted at step 5, faces dropped at the near test, faces dropped at the snap; status_out [1] = LS_OK, or
+ * LS_ERR_INVALID when a face names a vertex outside its mesh (the images are then unspecified; the binding raises).
+ * vertices [nv,3] float64, faces [nf,3] int32, world_to_cam [views,3,4] and intrinsics [views,4] float64, all DEVICE.  nf = 0 and
+ * n_views = 0 are allowed.  views H W < 2^31 and views nf < 2^31, znear finite and > 0: refused on the host otherwise.
+ * Launches: three memsets (the key image, the counts, the status), the rasteriser -- one thread per (view, face) does steps 1 - 5 and walks
+ * a box of at most RENDER_SMALL_BOX pixels itself; the larger boxes of a wave are walked by its 64 lanes together --, the strip pass -- in a
+ * call with few items the large boxes are walked there instead, one wave per (64 items, strip of the image); otherwise one idle workgroup
+ * -- and the resolve pass.  Their number depends on nothing.  No host synchronisation, no allocation; the only atomics are atomicMin on the 64-bit key and one
+ * integer add per wave, view and counter: every output is the same bits in any run.  The workspace is the key image: 8 views H W bytes. */
+size_t ls_mesh_render_depth_workspace_bytes(int n_views, int height, int width);
+int ls_mesh_render_depth_f64(const double* vertices, int nv, const int32_t* faces, int nf, int n_views, const double* world_to_cam,
+                             const double* intrinsics, int height, int width, double znear, float* depth_out, int32_t* face_out,
+                             long long* counts_out, int* status_out, void* workspace, size_t workspace_bytes, void* stream);
+/* M meshes stored back to back as in ls_mesh_contains_batch_f64 (vert_off / face_off: HOST int64 [M+1], faces local to their mesh), mesh m
+ * rendered into the views [view_off[m], view_off[m+1]) (HOST int64 [M+1]) of the views_total images; one H x W and one znear per call.  The
+ * offsets are checked on the host before the first HIP call and copied to the workspace.  A mesh with no views and a mesh with no faces
+ * are allowed (its views come out empty).  Every image is BIT-IDENTICAL to ls_mesh_render_depth_f64 on that mesh alone, and the number of
+ * launches does not depend on M.  The workspace depends on (M, views_total, H, W) alone: the key image and the offsets. */
+size_t ls_mesh_render_depth_batch_workspace_bytes(int M, long long views_total, int height, int width);
+int ls_mesh_render_depth_batch_f64(int M, const double* vertices, long long nv_total, const long long* vert_off, const int32_t* faces,
+                                   long long nf_total, const long long* face_off, long long views_total, const long long* view_off,
+                                   const double* world_to_cam, const double* intrinsics, int height, int width, double znear, float* depth_out,
+                                   int32_t* face_out, long long* counts_out, int* status_out, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+/* The back-projection of `views` depth maps (the reference's pointcloud plus the move to another frame): depth [views,H,W] fp32,
+ * intrinsics [views,4] float64, cam_to_world M [views,3,4] float64 or NULL (the camera frame), all DEVICE.  Per view, every pixel with
+ * d > 0 in ascending py W + px (the order of np.where):
+ *   xc = ((px - cx) / fx) d, yc = ((py - cy) / fy) d, zc = d;  p = ((M[:,0] xc + M[:,1] yc) + M[:,2] zc) + M[:,3], rounded to fp32
+ * pts_out [views H W,3] fp32 and pix_out [views H W] int32 (the pixel index py W + px) are sized by the caller for every pixel; the rows
+ * of view v are [off_out[v], off_out[v+1]), off_out [views+1] int64 DEVICE.  Flag, two-level scan, scatter: 6 launches, no host
+ * synchronisation, no atomics.  views H W is at most 2^24 (the scan's reach). */
+size_t ls_depth_points_workspace_bytes(long long views, int height, int width);
+int ls_depth_points_f32(const float* depth, long long views, int height, int width, const double* intrinsics, const double* cam_to_world,
+                        float* pts_out, int32_t* pix_out, long long* off_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Decimation on the device (csrc/meshcluster.hip): vertex clustering on a uniform grid with quadric-optimal representatives (Lindstrom

@@ -190,6 +190,12 @@ SIGNATURES = {
     "ls_mesh_cluster_batch_f64": (_I, [_I, _P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _P, _I, _I, _P, ctypes.c_longlong, _P, ctypes.c_longlong, _P, _P,
                                    _P, _SZ, _P]),
     "ls_mesh_sample_batch_f64": (_I, [_I, _P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _P, ctypes.c_longlong, _P, _P, _P, _P, _P, _SZ, _P]),
+    "ls_mesh_render_depth_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "ls_mesh_render_depth_f64": (_I, [_P, _I, _P, _I, _I, _P, _P, _I, _I, _D, _P, _P, _P, _P, _P, _SZ, _P]),
+    "ls_mesh_render_depth_batch_workspace_bytes": (_SZ, [_I, _LL, _I, _I]),
+    "ls_mesh_render_depth_batch_f64": (_I, [_I, _P, _LL, _P, _P, _LL, _P, _LL, _P, _P, _P, _I, _I, _D, _P, _P, _P, _P, _P, _SZ, _P]),
+    "ls_depth_points_workspace_bytes": (_SZ, [_LL, _I, _I]),
+    "ls_depth_points_f32": (_I, [_P, _LL, _I, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "ls_reg_metrics_batch_workspace_bytes": (_SZ, [_I, _LL, _LL, _I]),
     "ls_reg_metrics_batch": (_I, [_I, _P, _LL, _P, _P, _LL, _P, _P, _P, _I, _P, _P, _SZ, _P]),
     "ls_cloud_merge_workspace_bytes": (_SZ, [_LL, _LL]),

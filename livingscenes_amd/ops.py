@@ -813,6 +813,128 @@ def mesh_sample_batch(meshes, counts, seeds=None):
     return list(zip(torch.split(pts, counts), torch.split(face, counts)))
 
 
+# ------------------------------------------------------------------------------------------------ depth views (csrc/meshrender.hip)
+def _f64_dev(x, what, op, tail, views=None):
+    """a float64 HIP tensor [views, *tail] (a single [*tail] is shared by the views when `views` is given)"""
+    if not torch.is_tensor(x) or x.device.type != "cuda":
+        kind = f"{x.device.type} {x.dtype}" if torch.is_tensor(x) else type(x).__name__
+        raise _lib.LsError(f"{op}: {what} must be a HIP (cuda) tensor, got {kind}: the MI355X path has no CPU fallback")
+    if views is not None and tuple(x.shape) == tail:
+        x = x.expand((views,) + tail)
+    if tuple(x.shape[1:]) != tail or (views is not None and x.shape[0] != views):
+        raise ValueError(f"{op}: {what} is [views, {', '.join(map(str, tail))}]" + (f" with views = {views}" if views is not None else "") +
+                         f", got {tuple(x.shape)}")
+    return x.to(torch.float64).contiguous()
+
+
+def _render_args(op, world_to_cam, intrinsics, height, width, znear):
+    E = _f64_dev(world_to_cam, "world_to_cam", op, (3, 4))
+    K = _f64_dev(intrinsics, "intrinsics", op, (4,), E.shape[0])
+    H, W, znear = int(height), int(width), float(znear)
+    if H < 1 or W < 1:
+        raise ValueError(f"{op}: the image must have at least one pixel, got {H} x {W}")
+    if E.shape[0] * H * W >= 2 ** 31:
+        raise ValueError(f"{op}: {E.shape[0]} views of {H} x {W} pixels: the renderer ranks pixels with int32 (views * height * width < 2^31)")
+    if not (0 < znear < float("inf")):
+        raise ValueError(f"{op}: znear must be positive and finite, got {znear}")
+    return E, K, H, W, znear
+
+
+def _render_out(op, views, H, W, dev):
+    depth = torch.empty(views, H, W, dtype=torch.float32, device=dev)
+    face = torch.empty(views, H, W, dtype=torch.int32, device=dev)
+    return depth, face, _Meta(1, dev, [("counts", np.int64, 0, 4 * views), ("status", np.int32, 1)])
+
+
+def _render_read(op, m, views):
+    """the call's one host read: the counts; a face that names a vertex outside its mesh is an error of the call"""
+    host = m.buf.cpu().numpy().view(np.uint8)
+    o = m.at["status"][0]
+    if host[o:o + 4].view(np.int32)[0] != 0:
+        raise _lib.LsError(f"{op}: a face names a vertex outside its mesh")
+    return torch.from_numpy(host[:views * 32].view(np.int64).reshape(views, 4).copy())
+
+
+def mesh_render_depth(V, F, world_to_cam, intrinsics, height, width, znear=0.05):
+    """ls_mesh_render_depth_f64: depth views of one mesh (V [nv,3] float64, F [nf,3] int32, HIP tensors).  world_to_cam [views,3,4] float64
+    takes world points into the camera frame (x right, y down, z forward), intrinsics [views,4] or [4] = (fx, fy, cx, cy), HIP tensors too.
+    -> (depth [views,H,W] fp32, 0 = nothing hit; face [views,H,W] int32, -1 = none; counts [views,4] int64 on the HOST: pixels hit, faces
+    that reached the pixel box with a non-zero area, faces dropped at the near test, faces dropped at the snap).  The definition is in
+    include/livingscenes_hip.h; tests/render_oracle.py is the same text as NumPy and the outputs equal it bit for bit.  One host read."""
+    op = "mesh_render_depth"
+    V, F = _mesh_dev(V, F)
+    E, K, H, W, znear = _render_args(op, world_to_cam, intrinsics, height, width, znear)
+    dev, views = V.device, E.shape[0]
+    depth, face, m = _render_out(op, views, H, W, dev)
+    ws = _scratch(load().ls_mesh_render_depth_workspace_bytes(views, H, W), dev)
+    call(dev, "ls_mesh_render_depth_f64", ptr(V), V.shape[0], ptr(F), F.shape[0], views, ptr(E), ptr(K), H, W, znear, ptr(depth), ptr(face),
+         m.ptr("counts"), m.ptr("status"), ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev))
+    return depth, face, _render_read(op, m, views)
+
+
+def mesh_render_depth_batch(meshes, world_to_cam, intrinsics, height, width, znear=0.05):
+    """ls_mesh_render_depth_batch_f64: meshes = list of M (V, F); world_to_cam = list of M HIP tensors [views_m,3,4] (zero views allowed),
+    intrinsics = [4] shared, or a list of M tensors [views_m,4] -> list of M (depth, face, counts), mesh m bit-identical to
+    mesh_render_depth(*meshes[m], world_to_cam[m], ...).  One device call and one host read whatever M."""
+    op = "mesh_render_depth_batch"
+    M = len(meshes)
+    if len(world_to_cam) != M:
+        raise ValueError(f"{op}: {len(world_to_cam)} camera sets for {M} meshes")
+    if M == 0:
+        return []
+    Vp, vo, Fp, fo = _pack_meshes(meshes)
+    dev = Vp.device
+    Es = [_f64_dev(e, "world_to_cam", op, (3, 4)) for e in world_to_cam]
+    nviews = [e.shape[0] for e in Es]
+    if torch.is_tensor(intrinsics):
+        Ks = [_f64_dev(intrinsics, "intrinsics", op, (4,), n) for n in nviews]
+    else:
+        if len(intrinsics) != M:
+            raise ValueError(f"{op}: {len(intrinsics)} intrinsics for {M} meshes")
+        Ks = [_f64_dev(k, "intrinsics", op, (4,), n) for k, n in zip(intrinsics, nviews)]
+    E, K, H, W, znear = _render_args(op, torch.cat(Es, 0), torch.cat(Ks, 0), height, width, znear)
+    views, wo = E.shape[0], _offsets(nviews)
+    depth, face, m = _render_out(op, views, H, W, dev)
+    ws = _scratch(load().ls_mesh_render_depth_batch_workspace_bytes(M, views, H, W), dev)
+    call(dev, "ls_mesh_render_depth_batch_f64", M, ptr(Vp), Vp.shape[0], _hptr(vo), ptr(Fp), Fp.shape[0], _hptr(fo), views, _hptr(wo), ptr(E),
+         ptr(K), H, W, znear, ptr(depth), ptr(face), m.ptr("counts"), m.ptr("status"), ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev))
+    counts = _render_read(op, m, views)
+    return list(zip(torch.split(depth, nviews), torch.split(face, nviews), torch.split(counts, nviews)))
+
+
+def depth_points(depth, intrinsics, cam_to_world=None, packed=False):
+    """ls_depth_points_f32: the back-projection of depth maps (the reference's utils/render.py pointcloud, plus the move to another frame).
+    depth [views,H,W] fp32, intrinsics [views,4] or [4] float64 = (fx, fy, cx, cy), cam_to_world [views,3,4] float64 or None (the points
+    stay in the camera frame: x right, y down, z forward); HIP tensors.  Per view every pixel with depth > 0 in ascending row-major order
+    -> list of views (pts [n,3] fp32, pix [n] int32: the pixel index py * W + px), views of one packed tensor; packed=True: (pts, pix, off)
+    with off the host int64 offsets [views+1].  One call, one host read (the offsets)."""
+    op = "depth_points"
+    if not torch.is_tensor(depth) or depth.device.type != "cuda" or depth.dtype != torch.float32:
+        kind = f"{depth.device.type} {depth.dtype}" if torch.is_tensor(depth) else type(depth).__name__
+        raise _lib.LsError(f"{op}: depth must be an fp32 HIP (cuda) tensor, got {kind}: the MI355X path has no CPU fallback and converts nothing")
+    if depth.dim() != 3 or depth.shape[1] < 1 or depth.shape[2] < 1:
+        raise ValueError(f"{op}: depth is [views, H, W] with at least one pixel, got {tuple(depth.shape)}")
+    depth = depth.contiguous()
+    dev, (views, H, W) = depth.device, depth.shape
+    K = _f64_dev(intrinsics, "intrinsics", op, (4,), views)
+    Mw = None if cam_to_world is None else _f64_dev(cam_to_world, "cam_to_world", op, (3, 4), views)
+    n = views * H * W
+    if n > 2 ** 24:
+        raise ValueError(f"{op}: {views} views of {H} x {W} pixels: at most 2^24 pixels per call")
+    pts = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    pix = torch.empty(n, dtype=torch.int32, device=dev)
+    off = torch.empty(views + 1, dtype=torch.int64, device=dev)
+    ws = _scratch(load().ls_depth_points_workspace_bytes(views, H, W), dev)
+    call(dev, "ls_depth_points_f32", ptr(depth), views, H, W, ptr(K), ptr(Mw), ptr(pts), ptr(pix), ptr(off), ptr(ws),
+         0 if ws is None else ws.numel(), stream_ptr(dev))
+    off = off.cpu().numpy()
+    n_out = int(off[views])
+    if packed:
+        return pts[:n_out], pix[:n_out], off
+    sizes = np.diff(off).tolist()
+    return list(zip(torch.split(pts[:n_out], sizes), torch.split(pix[:n_out], sizes)))
+
+
 # ------------------------------------------------------------------------------------------------ scene memory (csrc/cloud_grid.h, cloudmerge.hip, cloudnear.hip)
 # The twelve wrappers share one binding scheme: _cloud / _pose / _poses / _per_problem check the arguments, _pack puts a list of clouds back
 # to back, _Meta holds the per-problem outputs that the host reads, and _icp_result assembles what the four ICP wrappers return.

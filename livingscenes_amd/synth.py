@@ -260,3 +260,21 @@ def make_raw_scan(shapes, seed, pmin=1024, pmax=60000, device=None):
     if device is not None:
         pc, mask = pc.to(device), mask.to(device)
     return {"pc": pc, "pc_mask": mask}, sum(c.shape[0] for c in clouds)
+
+
+def make_partial_views(seeds, n_views, res=48, noise=0.0, view_seed=0, device="cuda"):
+    """Partial scans as a depth sensor makes them: n_views depth views of canonical_mesh(seed, res) for every seed, rendered in ONE device
+    call at the reference's camera settings (livingscenes_amd.render: 100 x 100 pixels, f = 100, the camera 1.5 from the origin) and
+    back-projected into the shape's canonical frame.  Shape i's cameras are render.gen_random_poses(n_views, view_seed * 100003 + seeds[i]).
+    noise > 0 adds seeded Gaussian jitter of that standard deviation to every point.
+    -> list per shape of dict(clouds = n_views fp32 tensors [n_j,3] on `device`, poses = [n_views,4,4] float64 camera-to-world poses)."""
+    from . import render
+    seeds = [int(s) for s in seeds]
+    meshes = [canonical_mesh(s, res=res, device=device) for s in seeds]
+    out = []
+    for s, (clouds, poses) in zip(seeds, render.render_depth_batch(meshes, n_views, [int(view_seed) * 100003 + s for s in seeds])):
+        if noise > 0:
+            rng = _rng(int(view_seed) * 100003 + s, "partial_noise")
+            clouds = [c + torch.from_numpy((noise * rng.standard_normal(tuple(c.shape))).astype(np.float32)).to(c.device) for c in clouds]
+        out.append(dict(clouds=list(clouds), poses=np.stack(poses) if poses else np.zeros((0, 4, 4))))
+    return out
