@@ -64,7 +64,7 @@ typedef enum {
  * ls_mesh_distance_batch_f64 / ls_mesh_sample_batch_f64; symbols added since -- ls_reg_metrics_batch, ls_mesh_cluster_f64 / ls_mesh_cluster_batch_f64,
  * ls_cloud_merge_f32 / ls_cloud_merge_batch_f32, ls_cloud_nearest_f32 / ls_cloud_nearest_batch_f32, ls_cloud_icp_f32 / ls_cloud_icp_batch_f32,
  * ls_cloud_normals_f32 / ls_cloud_normals_batch_f32, ls_cloud_icp_plane_f32 / ls_cloud_icp_plane_batch_f32, ls_cloud_project_f32 / ls_cloud_project_batch_f32,
- * ls_mesh_render_depth_f64 / ls_mesh_render_depth_batch_f64, ls_depth_points_f32 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
+ * ls_mesh_render_depth_f64 / ls_mesh_render_depth_batch_f64, ls_depth_points_f32, ls_cloud_carve_f32 / ls_cloud_carve_batch_f32 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
  * binding compares it with the header it was written against and refuses a mismatch (livingscenes_amd/_lib.py: load). */
 #define LS_ABI_VERSION 107
 int ls_version(void);
@@ -901,6 +901,67 @@ size_t ls_cloud_project_batch_workspace_bytes(int P, long long a_total);
 int ls_cloud_project_batch_f32(int P, const float* A, long long a_total, const long long* a_off, const float* radius, int min_nbrs,
                                float max_variation, float max_shift, float* out_pts, int32_t* state, float* shift, long long* counts,
                                double* sum_shift2, int* status_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Scene memory, kept points carved out of observed free space (csrc/cloudcarve.hip, csrc/carve_plan.h): the one operator that REMOVES
+ * points.  AN EXTENSION BEYOND THE RELEASED REFERENCE, like the merge.  A depth image says where there is nothing: every pixel is a ray
+ * that reached its depth without hitting anything on the way.  A kept row that a posed depth view looks THROUGH lies in observed free
+ * space and may be dropped; a row the view confirms, a row it cannot see and a row it cannot judge stay.  The output is a subsequence of
+ * the input: rows and bits are untouched, nothing is averaged or moved; float64 comparisons and integer counts, no sums.
+ * Inputs: the kept cloud A [a,3] fp32; `views` depth images depth [views,H,W] fp32, 0 = the ray hit nothing (the renderer's convention);
+ * intrinsics [views,4] float64 = (fx, fy, cx, cy); world_to_cam E [views,3,4] float64 FROM THE FRAME OF A (composing a camera with a
+ * registration is the caller's work); all DEVICE.  Definition per (row i, view v) (tests/carve_oracle.py is the same text as NumPy).
+ * Everything is float64 and nothing is contracted; x is the fp32 row widened.
+ *   1. c = ((E[:,0] x_0 + E[:,1] x_1) + E[:,2] x_2) + E[:,3].
+ *   2. OUT if a component of c is not finite or c.z < znear.
+ *   3. u = fx (c.x / c.z) + cx and v = fy (c.y / c.z) + cy.  qx = floor(u + 0.5), qy = floor(v + 0.5): the ray of pixel q goes through the
+ *      integer coordinate, as in ls_depth_points_f32.  OUT unless 0 <= qx <= W - 1 and 0 <= qy <= H - 1; the comparison is made on the
+ *      doubles, so NaN fails it.
+ *   4. Over the window pixels (qx + dx, qy + dy), |dx|, |dy| <= k = window, that lie inside the image (n_in of them), let
+ *      d = (double) depth[v, y, x], lo = d - tol and hi = d + tol.  Each pixel is exactly one of:
+ *        empty   !(d > 0), so 0, negative and NaN count as empty
+ *        front   c.z < lo
+ *        behind  c.z > hi
+ *        hit     otherwise, both ends inclusive
+ *   5. The state of the (row, view), uint8:
+ *        1 SEEN      if n_hit > 0
+ *        2 FREE      else if n_front + (empty_is_free ? n_empty : 0) == n_in
+ *        3 OCCLUDED  else if n_behind > 0 and n_front == 0
+ *        4 MIXED     else
+ *      and 0 is OUT.
+ * Per row: seen_i and free_i are the numbers of views in those states.  ROW i IS DROPPED IFF free_i >= min_free AND seen_i <= max_seen.
+ * A non-finite row is OUT everywhere and therefore stays.  The nearest-pixel rounding of step 3 moves the ray by up to half a pixel, so
+ * the window defaults to 1 in the bindings (derived).  NO tol IS RECOMMENDED, and no min_free or max_seen: none has been measured on real
+ * scans.
+ * Outputs (DEVICE): out_pts [a,3] fp32, the kept rows in order, the same bits; out_src [a] int32, the row's index in its problem; out_off
+ * [2] int64 = (0, kept rows); seen, free [a] int32; counts [4] int64 = rows with seen >= 1, rows with free >= 1, rows dropped, rows OUT
+ * in every view (every row, when there is no view); view_counts [views,5] int64, the histogram of the five states by value; state, uint8
+ * [views,a], NULL: not written; status_out [1] (nullable): LS_OK.  a = 0 and views = 0 are allowed; with no views nothing is dropped.
+ * Refused on the host before the first HIP call, with a message that names the problem: tol not finite or < 0, znear not finite or <= 0,
+ * window outside {0, 1, 2}, min_free < 1, max_seen < 0, empty_is_free outside {0, 1}, H or W < 1, a beyond the scan's reach (2^24 rows).
+ * A workgroup owns one chunk of 256 rows of one problem, so the problem's views are the same for the whole workgroup; one thread per row
+ * loops over the views and gathers at most (2k+1)^2 pixels per view; then flag, scan, scatter as in the merge.  The histograms are one
+ * integer add per wave, view and state, from a ballot.  Launches, whatever P and the number of views: with rows, 2 memsets (counts,
+ * view_counts; the latter only with views) and 6 kernels (carve, the scan's three, scatter, offsets); without rows, at most 4 memsets
+ * and no kernel.  No host synchronisation, no allocation, no floating-point atomics: every output is the same bits in any run.  The
+ * workspace depends on (a, views) alone -- in fact on a: two int32 per row and the scan's block sums; 0 for refused sizes. */
+size_t ls_cloud_carve_workspace_bytes(long long a, long long views);
+int ls_cloud_carve_f32(const float* A, long long a, const float* depth, long long views, int height, int width, const double* intrinsics,
+                       const double* world_to_cam, double tol, double znear, int window, int min_free, int max_seen, int empty_is_free,
+                       float* out_pts, int32_t* out_src, long long* out_off, int32_t* seen, int32_t* free_views, long long* counts,
+                       long long* view_counts, uint8_t* state, int* status_out, void* workspace, size_t workspace_bytes, void* stream);
+/* P >= 1 problems per call: problem p owns the rows [a_off[p], a_off[p+1]) of A and the views [view_off[p], view_off[p+1]) of the
+ * views_total images; a_off and view_off are HOST int64 [P+1], checked before the first HIP call -- the error names the problem -- and
+ * copied into the workspace.  One H x W and one set of scalars per call.  A problem with no rows or no views is allowed.  out_pts / out_src
+ * hold the kept rows of every problem back to back, problem p's at [out_off[p], out_off[p+1]), out_off [P+1]; seen / free [a_total];
+ * counts [P,4]; view_counts [views_total,5]; state: problem p's block is [V_p, a_p], the blocks back to back; status_out [P] (nullable).
+ * Every output of every problem is BIT-IDENTICAL to ls_cloud_carve_f32 on that problem alone, and the number of launches does not depend
+ * on P.  The workspace depends on (P, a_total, views_total) alone. */
+size_t ls_cloud_carve_batch_workspace_bytes(int P, long long a_total, long long views_total);
+int ls_cloud_carve_batch_f32(int P, const float* A, long long a_total, const long long* a_off, const float* depth, long long views_total,
+                             const long long* view_off, int height, int width, const double* intrinsics, const double* world_to_cam, double tol,
+                             double znear, int window, int min_free, int max_seen, int empty_is_free, float* out_pts, int32_t* out_src,
+                             long long* out_off, int32_t* seen, int32_t* free_views, long long* counts, long long* view_counts, uint8_t* state,
+                             int* status_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Scene memory, the trimmed ICP with the point-to-plane metric (csrc/cloudnear.hip).  AN EXTENSION BEYOND THE RELEASED REFERENCE, like
  * ls_cloud_icp_f32, whose loop this is: a partial view registered point-to-point onto one point per voxel of a SURFACE slides along it

@@ -375,6 +375,50 @@ class More_Solver:
             info["rms_shift"].append(math.sqrt(sum_shift2 / moved) if moved else float("nan"))
         return [pts for pts, _ in merged], info
 
+    @staticmethod
+    def _memory_cameras(world_to_cam, to_obs):
+        """world_to_cam [V,3,4] float64 of the observation's frame composed with to_obs [3,4] float64 (memory -> observation; None: the
+        views are in the memory's frame already) -> world_to_cam from the memory's frame, float64"""
+        E = world_to_cam.to(torch.float64)
+        if to_obs is None:
+            return E.contiguous()
+        M = to_obs.to(E.device)
+        return torch.cat([E[:, :, :3] @ M[:, :3], E[:, :, :3] @ M[:, 3:4] + E[:, :, 3:4]], dim=-1).contiguous()
+
+    def _carve_batch(self, mem_pcs, views, T=None, g=None, *, tol, window=1, min_free=1, max_seen=0, empty="unknown", znear=0.05):
+        """Scene memory, the one step that REMOVES kept points (an extension beyond the released reference, like _accumulate_batch): carve
+        P kept clouds mem_pcs[p] [a_p,3] (in the memory's frame) by posed depth views of the matched observations in ONE ragged call
+        (ops.cloud_carve_batch, csrc/cloudcarve.hip).  A kept point that a view looks THROUGH lies in observed free space and is dropped;
+        a point a view confirms, a point it cannot see and a point it cannot judge stay.  views[p] = dict(depth [V,H,W] fp32, intrinsics
+        [V,4] or [4], world_to_cam [V,3,4]) in the OBSERVATION's frame (HIP tensors).  T [P,4,4] or [P,3,4] is the registration as
+        _solve_pairwise_registration* return it (memory -> rescan), or g (keyword-compatible with _accumulate_batch: rescan -> memory, what
+        _refine_on_memory_batch returns); T and g together are an error, both None: the views are in the memory's frame.  The cameras
+        the operator receives are world_to_cam o T, or world_to_cam o inverse(g), formed in float64.  window = 1 is ops.cloud_carve_batch's
+        derived default; tol HAS NO DEFAULT AND NONE IS RECOMMENDED, nor any min_free or max_seen: none has been measured on real scans.
+        -> (list of P carved clouds [n_p,3]: subsequences of mem_pcs[p], the same bits,
+            dict: src (list of P int32 [n_p]: the kept rows), n_carved (list of P ints), seen / free (lists of P int32 [a_p]), counts (host
+            int64 [P,4]) and view_counts (list of P host int64 [V_p,5]) as ops.cloud_carve_batch returns them)."""
+        P = len(mem_pcs)
+        if len(views) != P:
+            raise ValueError(f"{P} memory clouds for {len(views)} sets of views")
+        if T is not None and g is not None:
+            raise ValueError("give the registration T (memory -> rescan) or the memory-frame pose g (rescan -> memory), not both")
+        to_obs = None
+        for name, pose in (("T", T), ("g", g)):
+            if pose is None:
+                continue
+            if pose.dim() != 3 or pose.shape[0] != P or pose.shape[1] not in (3, 4) or pose.shape[2] != 4:
+                raise ValueError(f"{name} must be [P,4,4] or [P,3,4] with P = {P}, got {tuple(pose.shape)}")
+            to_obs = pose.detach().to(torch.float64)[:, :3, :]
+            if name == "g":
+                to_obs = inverse(to_obs)
+        cams = [self._memory_cameras(v["world_to_cam"], None if to_obs is None else to_obs[p]) for p, v in enumerate(views)]
+        res, f = ops.cloud_carve_batch([p.detach() for p in mem_pcs], [v["depth"] for v in views], [v["intrinsics"] for v in views], cams,
+                                       tol=tol, window=window, min_free=min_free, max_seen=max_seen, empty=empty, znear=znear)
+        f["src"] = [s for _, s in res]
+        f["n_carved"] = [int(c) for c in f["counts"][:, 2]]
+        return [pts for pts, _ in res], f
+
     def _refine_on_memory_batch(self, mem_pcs, new_pcs, T, radius, metric="point", normal_radius=None, **kw):
         """Scene memory, the pose the merge and the overlap gate trust (an extension beyond the released reference, like both): refine P
         registrations on the memory itself, at full resolution, in ONE ragged call (ops.cloud_icp_batch, csrc/cloudnear.hip) -- trimmed
@@ -631,7 +675,8 @@ def _encode_clouds(model, clouds):
 
 def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, optimize_codes=False, overlap_radius=None, min_overlap=None,
                    refine_radius=None, refine_metric="point", normal_radius=None, consolidate=False, consolidate_radius=None,
-                   consolidate_max_variation=1 / 3, consolidate_max_shift=float("inf")):
+                   consolidate_max_variation=1 / 3, consolidate_max_shift=float("inf"), carve_tol=None, carve_window=1, carve_min_free=1,
+                   carve_max_seen=0, carve_empty="unknown"):
     """A reference scan followed by SEVERAL rescans, with a memory that carries every instance's points from one rescan to the next -- an
     extension beyond the released reference (more_solver.py:246-299 solves one (reference, rescan) pair and drops the rescan's points).
     ref and every rescan: {'pc' [n,3,Nmax], 'pc_mask'} as _solve_end2end takes them.
@@ -686,7 +731,20 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
     fewer than n_input_point rows keeps its cloud and code and is reported; the other slots take their consolidated cloud and are
     re-encoded in ONE _encode_clouds call (the encoder's code of the consolidated cloud: optimize_codes does not run again).  memory
     gains 'consolidation': the dict of _consolidate_batch (per-slot lists rows_before, rows_after, moved, held, no_plane, rms_shift;
-    the figures of a kept slot are those of the cloud it did not take) plus kept_as_is (slots)."""
+    the figures of a kept slot are those of the cloud it did not take) plus kept_as_is (slots).
+
+    The carve (opt-in: with carve_tol None nothing below happens and every step dict and the memory are what they are without the
+    arguments).  Every operator above adds points or moves them; a point once kept is otherwise never replaced, so a wrong match or an ICP
+    in a local minimum writes a misplaced copy of an object into a slot for good, and an object that has changed keeps its old points.
+    With a number, a rescan may carry 'views': one entry per rescan instance, None allowed, else dict(depth [V,H,W] fp32, intrinsics,
+    world_to_cam [V,3,4]) in the RESCAN's frame (synth.make_partial_views(with_depth=True) makes such dicts).  After the registration, the
+    refinement and the gate, and BEFORE the merge, ONE More_Solver._carve_batch call over the accepted pairs that have views drops the
+    kept points those views look through, under the pose the merge will use (tol = carve_tol, window, min_free, max_seen and empty =
+    carve_*).  A slot takes its carved cloud unless that cloud has fewer than n_input_point rows; then it keeps its cloud and is
+    reported.  The merge runs on the carved memory; a slot that shrank or grew is re-encoded in the step's one re-encode call.  The step
+    gains n_carved [n] (rows the step removed per slot) and carve_kept_as_is (slots).  carve_window = 1 is derived (the nearest-pixel
+    rounding moves a ray by up to half a pixel).  carve_tol HAS NO DEFAULT AND NONE IS RECOMMENDED, nor any carve_min_free or
+    carve_max_seen: no real scans are available here to measure one on, and the effect on matching is unmeasured."""
     if refine_metric not in ("point", "plane"):
         raise ValueError(f"solve_sequence: refine_metric must be 'point' or 'plane', got {refine_metric!r}")
     if refine_metric == "plane" and refine_radius is None:
@@ -712,6 +770,8 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
         pairs = plan["pairs"]
         out = {"ref_pc_lst": list(mem), "rescan_pc_lst": res_full, "matches": m0, "registration": [None] * n, "codes": [None] * n,
                "mesh_lst": [None] * n, "n_new_points": [0] * n, "unmatched_rescan": plan["unmatched_new"]}
+        if carve_tol is not None:
+            out.update({"n_carved": [0] * n, "carve_kept_as_is": []})
         if refine_radius is not None:
             out.update({"refine_stop": [None] * n, "refine_iters": [None] * n, "registration_init": [None] * n})
         if pairs:
@@ -749,6 +809,21 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
                 cur = {key: res_codes[key][j][None] for key in _CODE_KEYS}
                 out["codes"][i] = solver._transform_latent(cur, inverse(T[k:k + 1]))
             keep = [k for k in range(len(pairs)) if accepted is None or accepted[k]]
+            rviews = rescan.get("views") if carve_tol is not None else None
+            seeing = [k for k in keep if rviews is not None and rviews[pairs[k][1]] is not None]
+            if seeing:                                                # the accepted pairs with views, under the pose the merge will use
+                sel = torch.tensor(seeing, device=T.device)
+                carved, _ = solver._carve_batch([src[k] for k in seeing], [rviews[pairs[k][1]] for k in seeing],
+                                                T=T[sel] if refined is None else None, g=None if refined is None else refined["g"][sel],
+                                                tol=carve_tol, window=carve_window, min_free=carve_min_free, max_seen=carve_max_seen,
+                                                empty=carve_empty)
+                for c, k in zip(carved, seeing):
+                    i = pairs[k][0]
+                    if c.shape[0] < n_in:
+                        out["carve_kept_as_is"].append(i)
+                        continue
+                    out["n_carved"][i] = src[k].shape[0] - c.shape[0]
+                    src[k] = mem[i] = c
             grew = []
             if keep:
                 sel = torch.tensor(keep, device=T.device)
@@ -761,7 +836,8 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
                 for c, k, d in zip(merged, keep, grew):
                     out["n_new_points"][pairs[k][0]] = d
                     mem[pairs[k][0]] = c
-            again = sequence_plan(n, m0.tolist(), len(res_full), grew, accepted=accepted)["reencode"]
+            changed = grew if carve_tol is None else [d + out["n_carved"][pairs[k][0]] for d, k in zip(grew, keep)]   # rows added or removed
+            again = sequence_plan(n, m0.tolist(), len(res_full), changed, accepted=accepted)["reencode"]
             if again:
                 new = _encode_clouds(model, [mem[i] for i in again])
                 new = {k: new[k].detach().clone() for k in _CODE_KEYS}

@@ -936,7 +936,7 @@ def depth_points(depth, intrinsics, cam_to_world=None, packed=False):
 
 
 # ------------------------------------------------------------------------------------------------ scene memory (csrc/cloud_grid.h, cloudmerge.hip, cloudnear.hip)
-# The twelve wrappers share one binding scheme: _cloud / _pose / _poses / _per_problem check the arguments, _pack puts a list of clouds back
+# The fourteen wrappers (the carve's two, further down, included) share one binding scheme: _cloud / _pose / _poses / _per_problem check the arguments, _pack puts a list of clouds back
 # to back, _Meta holds the per-problem outputs that the host reads, and _icp_result assembles what the four ICP wrappers return.
 def _cloud(x, what, op):
     if not torch.is_tensor(x) or x.device.type != "cuda" or x.dtype != torch.float32:
@@ -1282,6 +1282,121 @@ def cloud_project(A, *, radius, min_nbrs=5, max_variation=1 / 3, max_shift=float
     pts, state, shift, counts, sums = _project(op, "ls_cloud_project_f32", (ptr(A), A.shape[0], float(radius), int(min_nbrs), float(max_variation),
                                                                            float(max_shift)), (A.shape[0],), 1, A.device, A.shape[0])
     return pts, state, shift, counts[0], float(sums[0])
+
+
+# ------------------------------------------------------------------------------------------------ scene memory: carving by depth views (csrc/cloudcarve.hip)
+CARVE_STATE = ("out", "seen", "free", "occluded", "mixed")   # the values of `state`, by value
+_CARVE_EMPTY = {"unknown": 0, "free": 1}
+
+
+def _carve_views(op, depth, intrinsics, world_to_cam, dev):
+    """the views of one problem: depth [V,H,W] fp32, intrinsics [V,4] or [4] and world_to_cam [V,3,4] float64, HIP tensors on dev"""
+    if not torch.is_tensor(depth) or depth.device.type != "cuda" or depth.dtype != torch.float32:
+        kind = f"{depth.device.type} {depth.dtype}" if torch.is_tensor(depth) else type(depth).__name__
+        raise _lib.LsError(f"{op}: depth must be an fp32 HIP (cuda) tensor, got {kind}: the MI355X path has no CPU fallback and converts nothing")
+    if depth.dim() != 3 or depth.shape[1] < 1 or depth.shape[2] < 1:
+        raise ValueError(f"{op}: depth is [views, H, W] with at least one pixel, got {tuple(depth.shape)}")
+    if depth.device != dev:
+        raise ValueError(f"{op}: depth is on {depth.device}, the kept cloud on {dev}")
+    V = depth.shape[0]
+    return depth.contiguous(), _f64_dev(intrinsics, "intrinsics", op, (4,), V), _f64_dev(world_to_cam, "world_to_cam", op, (3, 4), V)
+
+
+def _carve_scalars(op, tol, znear, window, min_free, max_seen, empty):
+    if empty not in _CARVE_EMPTY:
+        raise ValueError(f"{op}: empty must be 'unknown' or 'free', got {empty!r}")
+    return float(tol), float(znear), int(window), int(min_free), int(max_seen), _CARVE_EMPTY[empty]
+
+
+def _carve(op, name, head, sizes, scalars, P, dev, a, views, n_state):
+    """the call of the carve's entry `name` of the operator `op` -> (pts, src, off [P+1], dict of seen, free, counts [P,4], view_counts
+    [views,5] and state (device uint8, or None))"""
+    pts = torch.empty(a, 3, dtype=torch.float32, device=dev)
+    src = torch.empty(a, dtype=torch.int32, device=dev)
+    seen = torch.empty(a, dtype=torch.int32, device=dev)
+    free = torch.empty(a, dtype=torch.int32, device=dev)
+    state = None if n_state is None else torch.empty(n_state, dtype=torch.uint8, device=dev)
+    m = _Meta(P, dev, [("off", np.int64, 1, 1), ("counts", np.int64, 4), ("view_counts", np.int64, 0, 5 * views), ("status", np.int32, 1)])
+    _cloud_call(dev, name, sizes, *head, *scalars, ptr(pts), ptr(src), m.ptr("off"), ptr(seen), ptr(free), m.ptr("counts"), m.ptr("view_counts"),
+                ptr(state), m.ptr("status"))
+    f = m.read(op)
+    n_out = int(f["off"][P])
+    return pts[:n_out], src[:n_out], f["off"], {"seen": seen, "free": free, "counts": f["counts"].reshape(P, 4),
+                                                 "view_counts": f["view_counts"].reshape(views, 5), "state": state}
+
+
+def cloud_carve_batch(As, depths, intrinsics, world_to_cam, *, tol, window=1, min_free=1, max_seen=0, empty="unknown", znear=0.05,
+                      return_state=False, packed=False):
+    """ls_cloud_carve_batch_f32 (an extension beyond the released reference, like cloud_merge; the one operator of the scene memory that
+    REMOVES points): As = list of P kept clouds [a_p,3] (fp32 HIP tensors, empty ones allowed); depths / intrinsics / world_to_cam =
+    lists of P: depth views [V_p,H,W] fp32 (0 = the ray hit nothing; one H x W per call, V_p = 0 allowed), intrinsics [V_p,4] or [4]
+    float64 = (fx, fy, cx, cy), world_to_cam [V_p,3,4] float64 FROM THE FRAME OF As[p] (composing a camera with a registration is the
+    caller's work).  Per (row, view) the see-through test of include/livingscenes_hip.h: the row's ray is rounded to its nearest pixel,
+    and over the (2 window + 1)^2 pixels around it the row is seen (within tol of some depth), free (in front of every depth by more
+    than tol; empty="free": pixels that hit nothing count as looked through too, "unknown": they do not), occluded, mixed, or out of
+    the view.  A row is dropped iff at least min_free views look through it and at most max_seen views see it.  window = 1 is DERIVED
+    (the rounding moves the ray by up to half a pixel); tol HAS NO DEFAULT AND NONE IS RECOMMENDED, nor any min_free or max_seen: none
+    has been measured on real scans.
+    -> (list of P (pts [n_p,3]: the kept rows in order, the same bits; src [n_p] int32: their rows in As[p]), views of one packed tensor,
+        dict: seen / free = lists of P int32 [a_p] (views per row in those states), counts host int64 [P,4] = rows seen at least once,
+        rows free at least once, rows dropped, rows out of every view; view_counts = list of P host int64 [V_p,5], the rows per state
+        (CARVE_STATE names them); return_state=True: state = list of P uint8 [V_p,a_p]).
+    packed=True: (pts, src, off) with the host int64 offsets [P+1], and the dict's entries packed (state: the blocks back to back, flat)
+    plus a_off and view_off.  One call, one host read, whatever P and however many views."""
+    op = "cloud_carve"
+    As = [_cloud(x, "A", op) for x in As]
+    P = len(As)
+    if P == 0:
+        raise ValueError(f"{op}: no problem given")
+    if not (len(depths) == len(world_to_cam) == P) or (not torch.is_tensor(intrinsics) and len(intrinsics) != P):
+        raise ValueError(f"{op}: {P} kept clouds for {len(depths)} sets of depth views and {len(world_to_cam)} sets of cameras")
+    dev = As[0].device
+    Ks = [intrinsics] * P if torch.is_tensor(intrinsics) else list(intrinsics)
+    vw = [_carve_views(op, d, k, e, dev) for d, k, e in zip(depths, Ks, world_to_cam)]
+    if len({tuple(d.shape[1:]) for d, _, _ in vw}) != 1:
+        raise ValueError(f"{op}: one H x W per call, got {sorted({tuple(d.shape[1:]) for d, _, _ in vw})}")
+    scalars = _carve_scalars(op, tol, znear, window, min_free, max_seen, empty)
+    A, ao = _pack(As)
+    D, K, E = (torch.cat(t, 0) if P > 1 else t[0] for t in zip(*vw))
+    nviews = [d.shape[0] for d, _, _ in vw]
+    vo = _offsets(nviews)
+    views, (H, W) = D.shape[0], D.shape[1:]
+    n_state = sum(a.shape[0] * v for a, v in zip(As, nviews)) if return_state else None
+    pts, src, off, f = _carve(op, "ls_cloud_carve_batch_f32", (P, ptr(A), A.shape[0], _hptr(ao), ptr(D), views, _hptr(vo), H, W, ptr(K), ptr(E)),
+                              (P, A.shape[0], views), scalars, P, dev, A.shape[0], views, n_state)
+    if packed:
+        f.update({"a_off": ao, "view_off": vo})
+        return pts, src, off, f
+    rows = np.diff(ao).tolist()
+    f["seen"], f["free"] = list(torch.split(f["seen"], rows)), list(torch.split(f["free"], rows))
+    f["view_counts"] = [f["view_counts"][vo[p]:vo[p + 1]] for p in range(P)]
+    if return_state:
+        f["state"] = [s.reshape(v, a) for s, v, a in zip(torch.split(f["state"], [a * v for a, v in zip(rows, nviews)]), nviews, rows)]
+    else:
+        del f["state"]
+    sizes = np.diff(off).tolist()
+    return list(zip(torch.split(pts, sizes), torch.split(src, sizes))), f
+
+
+def cloud_carve(A, depth, intrinsics, world_to_cam, *, tol, window=1, min_free=1, max_seen=0, empty="unknown", znear=0.05, return_state=False):
+    """ls_cloud_carve_f32: the kept cloud A [a,3] (fp32 HIP tensor) carved by the depth views depth [V,H,W] fp32 with intrinsics [V,4] or
+    [4] and world_to_cam [V,3,4] float64 from A's frame -> (pts [n,3], src [n] int32, dict: seen / free int32 [a], counts host int64 [4],
+    view_counts host int64 [V,5]; return_state=True: state uint8 [V,a]) as cloud_carve_batch describes them (window = 1 is derived; no tol,
+    min_free or max_seen is recommended).  Bit-identical to the same problem inside any cloud_carve_batch."""
+    op = "cloud_carve"
+    A = _cloud(A, "A", op)
+    dev = A.device
+    D, K, E = _carve_views(op, depth, intrinsics, world_to_cam, dev)
+    scalars = _carve_scalars(op, tol, znear, window, min_free, max_seen, empty)
+    a, (views, H, W) = A.shape[0], D.shape
+    pts, src, _, f = _carve(op, "ls_cloud_carve_f32", (ptr(A), a, ptr(D), views, H, W, ptr(K), ptr(E)), (a, views), scalars, 1, dev, a, views,
+                            a * views if return_state else None)
+    f["counts"] = f["counts"][0]
+    if return_state:
+        f["state"] = f["state"].reshape(views, a)
+    else:
+        del f["state"]
+    return pts, src, f
 
 
 def _plane_normals(x, A, op):

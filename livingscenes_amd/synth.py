@@ -262,19 +262,32 @@ def make_raw_scan(shapes, seed, pmin=1024, pmax=60000, device=None):
     return {"pc": pc, "pc_mask": mask}, sum(c.shape[0] for c in clouds)
 
 
-def make_partial_views(seeds, n_views, res=48, noise=0.0, view_seed=0, device="cuda"):
+def make_partial_views(seeds, n_views, res=48, noise=0.0, view_seed=0, device="cuda", with_depth=False):
     """Partial scans as a depth sensor makes them: n_views depth views of canonical_mesh(seed, res) for every seed, rendered in ONE device
     call at the reference's camera settings (livingscenes_amd.render: 100 x 100 pixels, f = 100, the camera 1.5 from the origin) and
     back-projected into the shape's canonical frame.  Shape i's cameras are render.gen_random_poses(n_views, view_seed * 100003 + seeds[i]).
     noise > 0 adds seeded Gaussian jitter of that standard deviation to every point.
-    -> list per shape of dict(clouds = n_views fp32 tensors [n_j,3] on `device`, poses = [n_views,4,4] float64 camera-to-world poses)."""
+    -> list per shape of dict(clouds = n_views fp32 tensors [n_j,3] on `device`, poses = [n_views,4,4] float64 camera-to-world poses).
+    with_depth=True: each dict also carries what the scene memory's carve takes (ops.cloud_carve, More_Solver._carve_batch): depth
+    [n_views,H,W] fp32 (the rendered maps, 0 = nothing hit, without the noise), intrinsics [4] float64 and world_to_cam [n_views,3,4]
+    float64 from the shape's canonical frame, HIP tensors."""
     from . import render
     seeds = [int(s) for s in seeds]
     meshes = [canonical_mesh(s, res=res, device=device) for s in seeds]
+    view_seeds = [int(view_seed) * 100003 + s for s in seeds]
+    if with_depth:   # the same call render_depth_batch makes, with the depth maps kept
+        pose_lists = [render.gen_random_poses(n_views, s) for s in view_seeds] if meshes else []
+        rendered = [(pcls, poses, depth) for (pcls, depth), poses in zip(render._render(meshes, pose_lists, render._device()) if meshes else [],
+                                                                         pose_lists)]
+    else:
+        rendered = [(pcls, poses, None) for pcls, poses in render.render_depth_batch(meshes, n_views, view_seeds)]
     out = []
-    for s, (clouds, poses) in zip(seeds, render.render_depth_batch(meshes, n_views, [int(view_seed) * 100003 + s for s in seeds])):
+    for s, (clouds, poses, depth) in zip(seeds, rendered):
         if noise > 0:
             rng = _rng(int(view_seed) * 100003 + s, "partial_noise")
             clouds = [c + torch.from_numpy((noise * rng.standard_normal(tuple(c.shape))).astype(np.float32)).to(c.device) for c in clouds]
         out.append(dict(clouds=list(clouds), poses=np.stack(poses) if poses else np.zeros((0, 4, 4))))
+        if with_depth:
+            E = np.stack([render.world_to_cam(p) for p in poses]) if poses else np.zeros((0, 3, 4))
+            out[-1].update(depth=depth, intrinsics=render._intrinsics(depth.device), world_to_cam=torch.from_numpy(E).to(depth.device))
     return out
