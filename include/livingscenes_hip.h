@@ -378,7 +378,8 @@ int ls_encoder_tail_f32(ls_model_t* m, const float* f, const float* centroid, co
 
 /* FieldWrapper.forward(query, None, code, return_sdf=True), decoder_type "inner_deepsdf":
  * model_utils.py:230-263 + DeepSDF_Decoder.forward, deepsdf_decoder.py:78-123.
- *   query [B,M,3], z_so3 [B,c,3], z_inv [B,c], s [B], t [B,3] -> sdf [B,M] */
+ *   query [B,M,3], z_so3 [B,c,3], z_inv [B,c], s [B], t [B,3] -> sdf [B,M]
+ * B * M < 2^31 rows per call (here and in ls_sdf_decode_train / ls_sdf_backward): more is refused before anything is sized or enqueued. */
 size_t ls_sdf_workspace_bytes(const ls_model_t* m, int B, int M);
 int ls_sdf_decode(ls_model_t* m, const float* query, const float* z_so3, const float* z_inv, const float* s,
                   const float* t, int B, int M, float* sdf, void* workspace, size_t workspace_bytes, void* stream);

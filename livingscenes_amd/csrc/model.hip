@@ -981,6 +981,8 @@ static int sdf_entry(const ls_model_t* m, const char* op, bool args, int B, long
     LS_REQUIRE(m->d.dec_num_linear >= 3, "%s: model has no decoder packed", op);
     if (ragged) LS_REQUIRE(B > 0 && n > 0 && n < (1ll << 31), "%s: empty or oversized problem", op);
     else LS_REQUIRE(B > 0 && n > 0, "%s: empty problem", op);
+    // the GEMMs and their split-K sizing take the row count as an int (Gemm::M, gemm_scratch_floats): said here, before anything is sized
+    if (!ragged) LS_REQUIRE((long long)B * n < (1ll << 31), "%s: B=%d x M=%lld rows too many for one call (< 2^31): split the queries", op, B, n);
     const size_t need = sdf_bytes(m, B, ragged ? n : B * n, train);
     if (workspace_bytes < need) { set_error("%s: workspace %zu < required %zu", op, workspace_bytes, need); return LS_ERR_WORKSPACE; }
     return LS_OK;

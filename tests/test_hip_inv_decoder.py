@@ -8,6 +8,7 @@ import pytest
 import torch
 import yaml
 
+import sdf_oracle
 from livingscenes_amd import _lib, synth
 
 pytestmark = pytest.mark.gpu
@@ -55,22 +56,9 @@ def _codes(f, requires_grad=False):
 
 
 def _mlp64(dw, dcfg, query, z_inv):
-    """deepsdf_decoder.py:78-123 with model_utils.py:247-250's input, restated in fp64 torch on the CPU (weight norm folded in fp64)."""
-    B, M, _ = query.shape
-    x0 = torch.cat([z_inv[:, None, :].expand(B, M, z_inv.shape[-1]), query], -1).reshape(B * M, -1)
-    x, nl = x0, len(dcfg["dims"]) + 1
-    for layer in range(nl):
-        if layer in dcfg["latent_in"]:
-            x = torch.cat([x, x0], 1)
-        if layer in dcfg["norm_layers"]:
-            g, v = dw[f"lin{layer}.weight_g"].double(), dw[f"lin{layer}.weight_v"].double()
-            W = g * v / v.norm(dim=1, keepdim=True)
-        else:
-            W = dw[f"lin{layer}.weight"].double()
-        x = x @ W.T + dw[f"lin{layer}.bias"].double()
-        if layer < nl - 1:
-            x = torch.relu(x)
-    return torch.tanh(x).reshape(B, M)
+    """deepsdf_decoder.py:78-123 with model_utils.py:247-250's input in fp64 on the CPU (weight norm folded in fp64), autograd enabled: the
+    'xyz' kind of tests/sdf_oracle.py"""
+    return sdf_oracle.field_with_grad(dw, dcfg, query, {"z_inv": z_inv}, torch.float64, "xyz")
 
 
 # ------------------------------------------------------------------------------------------------ loader + forward vs the reference

@@ -261,10 +261,16 @@ def _scratch_floats(M, N, K):   # only to say whether the decoder's training wor
 def sdf_traits(model, rows, x2, train_splitk):
     """The decoder's GEMMs (model.hip: sdf_forward, ls_sdf_backward); train_splitk None = inference."""
     from livingscenes_amd import synth
-    ecfg, dcfg = (synth.default_encoder_cfg(), synth.default_decoder_cfg()) if model == "released" else (synth.small_encoder_cfg(), synth.small_decoder_cfg())
-    w, nl, li = dcfg["dims"][0], len(dcfg["dims"]) + 1, dcfg["latent_in"][0]
+    dcfg = synth.default_decoder_cfg() if model == "released" else synth.small_decoder_cfg()
+    return sdf_traits_of(dcfg, rows, x2, train_splitk)
+
+
+def sdf_traits_of(dcfg, rows, x2, train_splitk):
+    """sdf_traits for any decoder configuration packing.pack_model takes: the width, the depth and the skip (none: latent_in = []) come from
+    dcfg, the width of the decoder input u from latent_size + pe_dim"""
+    w, nl, li = dcfg["dims"][0], len(dcfg["dims"]) + 1, (list(dcfg["latent_in"]) + [-1])[0]
     pad4 = lambda v: (v + 3) // 4 * 4
-    outw = [w] + [pad4(w - (2 * ecfg["c_dim"] + 1)) if l + 1 == li else w for l in range(1, nl - 1)]
+    outw = [w] + [pad4(w - (dcfg["latent_size"] + dcfg["pe_dim"])) if l + 1 == li else w for l in range(1, nl - 1)]
     pl = lambda K: int(K >= 512 and K % 32 == 0)
     layers = [(l, outw[l - 1], outw[l]) for l in range(1, nl - 1)]
     gws = bool(train_splitk) and any(_scratch_floats(rows, o, k) or _scratch_floats(rows, k, o) for _, k, o in layers)
