@@ -64,7 +64,8 @@ typedef enum {
  * ls_mesh_distance_batch_f64 / ls_mesh_sample_batch_f64; symbols added since -- ls_reg_metrics_batch, ls_mesh_cluster_f64 / ls_mesh_cluster_batch_f64,
  * ls_cloud_merge_f32 / ls_cloud_merge_batch_f32, ls_cloud_nearest_f32 / ls_cloud_nearest_batch_f32, ls_cloud_icp_f32 / ls_cloud_icp_batch_f32,
  * ls_cloud_normals_f32 / ls_cloud_normals_batch_f32, ls_cloud_icp_plane_f32 / ls_cloud_icp_plane_batch_f32, ls_cloud_project_f32 / ls_cloud_project_batch_f32,
- * ls_mesh_render_depth_f64 / ls_mesh_render_depth_batch_f64, ls_depth_points_f32, ls_cloud_carve_f32 / ls_cloud_carve_batch_f32 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
+ * ls_mesh_render_depth_f64 / ls_mesh_render_depth_batch_f64, ls_depth_points_f32, ls_cloud_carve_f32 / ls_cloud_carve_batch_f32,
+ * ls_depth_fuse_f32 / ls_depth_fuse_batch_f32, ls_tsdf_volume_f64 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
  * binding compares it with the header it was written against and refuses a mismatch (livingscenes_amd/_lib.py: load). */
 #define LS_ABI_VERSION 107
 int ls_version(void);
@@ -963,6 +964,60 @@ int ls_cloud_carve_batch_f32(int P, const float* A, long long a_total, const lon
                              double znear, int window, int min_free, int max_seen, int empty_is_free, float* out_pts, int32_t* out_src,
                              long long* out_off, int32_t* seen, int32_t* free_views, long long* counts, long long* view_counts, uint8_t* state,
                              int* status_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Scene memory, posed depth views fused into a truncated signed distance volume per instance (csrc/depthfuse.hip, csrc/fuse_plan.h).  AN
+ * EXTENSION BEYOND THE RELEASED REFERENCE, like the merge and the carve.  The carve asks of a kept point whether a view looks through it;
+ * the fusion asks it of every sample of a grid and keeps the answer as a distance: averaged over all views, the zero set of the volume is
+ * the surface that was OBSERVED (ls_tsdf_volume_f64 reads the volume out), sensor noise averages out, and a free-space
+ * observation pulls a stale surface away as the carve drops a stale point.
+ * State per problem: two int32 volumes [nx,ny,nz], k fastest as marching cubes reads a volume: sum, the quantised distances, and n, the
+ * observation count.  Both are updated IN PLACE; a fresh state is all zeros.  Grid per problem: origin[3] (the centre of voxel (0,0,0)),
+ * voxel h > 0 and trunc > 0, float64, HOST; one (nx,ny,nz) per call.  Views: depth [views,H,W] fp32, 0 = the ray hit nothing (the
+ * renderer's convention); intrinsics [views,4] float64 = (fx, fy, cx, cy); world_to_cam E [views,3,4] float64 FROM THE GRID'S FRAME
+ * (composing a camera with a registration is the caller's work); all DEVICE.  Definition per voxel (i_0,i_1,i_2) and view v, the views in
+ * the call's order (tests/fuse_oracle.py is the same text as NumPy).  Everything is float64 and nothing is contracted.
+ *   1. x_a = origin_a + h * (double)i_a, one multiply and one add.  c = ((E[:,0] x_0 + E[:,1] x_1) + E[:,2] x_2) + E[:,3].
+ *   2. OUT if a component of c is not finite or c.z < znear.
+ *   3. u, v and the pixel q = floor(. + 0.5) exactly as step 3 of ls_cloud_carve_f32.  OUT unless q is inside the image.
+ *   4. d = (double) depth[v, qy, qx].  EMPTY if !(d > 0), so 0, negative and NaN.  With empty_is_free an EMPTY voxel-view is taken with
+ *      t = +1 (step 6: q = 16384) and counted as FREE; otherwise it is skipped.
+ *   5. s = d - c.z, the PROJECTIVE distance along the optical axis.  OCCLUDED, and skipped, if s < -trunc.
+ *   6. t = min(s, trunc) / trunc, so t is in [-1, 1]; q = (int) floor(t * 16384 + 0.5).  The class is NEAR if s <= trunc, else FREE.
+ *   7. SATURATED, and skipped, if n == 65535.
+ *   8. Otherwise sum += q and n += 1.  |sum| <= 65535 * 16384 < 2^30.
+ * THE UPDATE IS INTEGER, so the state does not depend on the order of the views, on how they are split over calls, or on the batch; only
+ * a saturated voxel depends on the order, and the order is the call's.
+ * view_counts [views,6] int64 (DEVICE) is the histogram of OUT, EMPTY (skipped), OCCLUDED, NEAR, FREE and SATURATED, by value 0 .. 5, over
+ * the voxels of the view's problem; every row sums to nx ny nz.
+ * Refused on the host before the first HIP call: voxel, trunc or znear not finite or <= 0, a non-finite origin -- the error names the
+ * problem --, dims < 1, H or W < 1, P nx ny nz >= 2^31, empty_is_free outside {0, 1}, a view_off that does not start at 0, decreases or
+ * does not end at the number of views.
+ * A workgroup owns 256 consecutive voxels of one problem; one thread per voxel keeps (sum, n) in registers, loops over its problem's
+ * views, and reads and writes its state once; a view's E and K are wave-uniform; the histogram is one integer add per wave, view and class
+ * from a ballot.  Launches, whatever P and the number of views: the copy of the host arrays into the workspace, 1 memset (view_counts)
+ * and 1 kernel; a call without views does nothing.  No host synchronisation, no allocation, no floating-point atomics.  The workspace
+ * holds the device copy of view_off and the grids: a function of its arguments alone (in fact of P), 0 for refused sizes.
+ * NO voxel, trunc OR min_obs IS RECOMMENDED: none has been measured on real scans. */
+size_t ls_depth_fuse_workspace_bytes(int nx, int ny, int nz, long long views);
+int ls_depth_fuse_f32(int32_t* sum, int32_t* n, int nx, int ny, int nz, const double* origin, double voxel, double trunc, const float* depth,
+                      long long views, int height, int width, const double* intrinsics, const double* world_to_cam, double znear, int empty_is_free,
+                      long long* view_counts, void* workspace, size_t workspace_bytes, void* stream);
+/* P >= 1 problems per call: sum, n [P,nx,ny,nz]; problem p owns the views [view_off[p], view_off[p+1]) of the views_total images.  origin
+ * [P,3], voxel [P], trunc [P] (float64) and view_off [P+1] (int64) are HOST arrays, checked before the first HIP call and copied into the
+ * workspace.  One H x W, one znear and one empty_is_free per call.  A problem without views changes nothing.  The state of every problem
+ * is BIT-IDENTICAL to ls_depth_fuse_f32 on that problem alone (which is this entry with P = 1). */
+size_t ls_depth_fuse_batch_workspace_bytes(int P, int nx, int ny, int nz, long long views_total);
+int ls_depth_fuse_batch_f32(int P, int32_t* sum, int32_t* n, int nx, int ny, int nz, const double* origin, const double* voxel, const double* trunc,
+                            const float* depth, long long views_total, const long long* view_off, int height, int width, const double* intrinsics,
+                            const double* world_to_cam, double znear, int empty_is_free, long long* view_counts, void* workspace,
+                            size_t workspace_bytes, void* stream);
+/* State to volume, per sample of sum, n [B,nx,ny,nz]: valid = n >= min_obs (min_obs >= 1); D = (double)sum / ((double)n * 16384.0) where
+ * valid, else EXACTLY +1.0.  volume_out float64 and valid_out uint8 [B,nx,ny,nz]; counts_out [B,3] int64 = valid samples, valid samples
+ * with D <= 0, samples with n == 0 (all DEVICE).  1 memset and 1 kernel.  Filling what was never observed with +1 puts a second shell
+ * where the truncation band ends: a mesher of this volume must drop every cube that has a corner with valid_out == 0 (NOT PART OF THIS
+ * LIBRARY YET: ls_marching_cubes_f64 takes no mask). */
+int ls_tsdf_volume_f64(const int32_t* sum, const int32_t* n, int B, int nx, int ny, int nz, int min_obs, double* volume_out, uint8_t* valid_out,
+                       long long* counts_out, void* stream);
 
 /* Scene memory, the trimmed ICP with the point-to-plane metric (csrc/cloudnear.hip).  AN EXTENSION BEYOND THE RELEASED REFERENCE, like
  * ls_cloud_icp_f32, whose loop this is: a partial view registered point-to-point onto one point per voxel of a SURFACE slides along it

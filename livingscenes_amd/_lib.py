@@ -227,6 +227,11 @@ SIGNATURES = {
     "ls_cloud_carve_batch_workspace_bytes": (_SZ, [_I, _LL, _LL]),
     "ls_cloud_carve_batch_f32": (_I, [_I, _P, _LL, _P, _P, _LL, _P, _I, _I, _P, _P, _D, _D, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                       _SZ, _P]),
+    "ls_depth_fuse_workspace_bytes": (_SZ, [_I, _I, _I, _LL]),
+    "ls_depth_fuse_f32": (_I, [_P, _P, _I, _I, _I, _P, _D, _D, _P, _LL, _I, _I, _P, _P, _D, _I, _P, _P, _SZ, _P]),
+    "ls_depth_fuse_batch_workspace_bytes": (_SZ, [_I, _I, _I, _I, _LL]),
+    "ls_depth_fuse_batch_f32": (_I, [_I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _LL, _P, _I, _I, _P, _P, _D, _I, _P, _P, _SZ, _P]),
+    "ls_tsdf_volume_f64": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "ls_profile_begin": (_I, [_P]),
     "ls_profile_end": (_I, [_P, ctypes.POINTER(ProfileEntry), _I, ctypes.POINTER(ctypes.c_int)]),
 }

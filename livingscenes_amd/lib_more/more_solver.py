@@ -419,6 +419,59 @@ class More_Solver:
         f["n_carved"] = [int(c) for c in f["counts"][:, 2]]
         return [pts for pts, _ in res], f
 
+    @staticmethod
+    def _fusion_grids(clouds, res, trunc_voxels=4):
+        """Scene memory, the grids the depth fusion works on (an extension beyond the released reference, like _carve_batch): one cubic grid
+        of res^3 samples per cloud [n_p,3], in float64 on the host.  With the bounding box of the cloud, h = (largest extent) /
+        (res - 1 - 2 trunc_voxels), the grid is centred on the box: origin = centre - h (res - 1) / 2 (the centre of voxel (0,0,0)), and
+        trunc = trunc_voxels h.  The padding equals the truncation band, which is DERIVED: a surface on a face of the box keeps its whole
+        band inside the grid.  trunc_voxels = 4 is AN UNMEASURED DEFAULT (what the CPU experiment of DESIGN.md used); no res is
+        recommended.  res < 2 trunc_voxels + 2 is refused.  -> dict(origin [P,3], voxel [P], trunc [P]: host float64 tensors, dims)."""
+        res, trunc_voxels = int(res), int(trunc_voxels)
+        if trunc_voxels < 1 or res < 2 * trunc_voxels + 2:
+            raise ValueError(f"_fusion_grids: res must be at least 2 * trunc_voxels + 2 = {2 * max(trunc_voxels, 1) + 2} with trunc_voxels >= 1, "
+                             f"got res = {res}, trunc_voxels = {trunc_voxels}")
+        origin, voxel = [], []
+        for p, c in enumerate(clouds):
+            if c.shape[0] == 0:
+                raise ValueError(f"_fusion_grids: cloud {p} is empty: it has no bounding box")
+            c64 = c.detach().to(torch.float64)
+            lo, hi = c64.min(0).values.cpu(), c64.max(0).values.cpu()
+            h = (hi - lo).max() / float(res - 1 - 2 * trunc_voxels)
+            origin.append((lo + hi) / 2 - h * float(res - 1) / 2)
+            voxel.append(h)
+        voxel = torch.stack(voxel)
+        return {"origin": torch.stack(origin), "voxel": voxel, "trunc": float(trunc_voxels) * voxel, "dims": (res, res, res)}
+
+    def _fuse_batch(self, fusion, views, T=None, g=None, empty="unknown", znear=0.05):
+        """Scene memory, the surface side of the carve (an extension beyond the released reference): fuse posed depth views of the matched
+        observations into the truncated signed distance state of P instances, IN PLACE, in ONE ragged call (ops.depth_fuse_batch,
+        csrc/depthfuse.hip).  fusion = dict(sum, n: int32 [P,res,res,res] HIP tensors -- ops.tsdf_state --, origin [P,3], voxel [P],
+        trunc [P]: host float64, as _fusion_grids makes them), the grids in the memory's frame.  views[p] = dict(depth [V,H,W] fp32,
+        intrinsics [V,4] or [4], world_to_cam [V,3,4]) in the OBSERVATION's frame, or None: the slot is left as it is.  T, g: exactly the
+        conventions of _carve_batch (T: memory -> rescan, g: rescan -> memory, not both, both None: the views are in the memory's frame);
+        the cameras the operator receives are _memory_cameras(world_to_cam, T) or (world_to_cam, inverse(g)), formed in float64.
+        -> list of P device int64 [V_p,6]: voxels per class of ops.FUSE_CLASS and view."""
+        P = fusion["sum"].shape[0]
+        if len(views) != P:
+            raise ValueError(f"{P} fusion states for {len(views)} sets of views")
+        if T is not None and g is not None:
+            raise ValueError("give the registration T (memory -> rescan) or the memory-frame pose g (rescan -> memory), not both")
+        to_obs = None
+        for name, pose in (("T", T), ("g", g)):
+            if pose is None:
+                continue
+            if pose.dim() != 3 or pose.shape[0] != P or pose.shape[1] not in (3, 4) or pose.shape[2] != 4:
+                raise ValueError(f"{name} must be [P,4,4] or [P,3,4] with P = {P}, got {tuple(pose.shape)}")
+            to_obs = pose.detach().to(torch.float64)[:, :3, :]
+            if name == "g":
+                to_obs = inverse(to_obs)
+        cams = [None if v is None else self._memory_cameras(v["world_to_cam"], None if to_obs is None else to_obs[p]) for p, v in enumerate(views)]
+        shared = next((v["intrinsics"] for v in views if v is not None), None)
+        return ops.depth_fuse_batch((fusion["sum"], fusion["n"]), [None if v is None else v["depth"] for v in views],
+                                    [shared if v is None else v["intrinsics"] for v in views], cams, origin=fusion["origin"],
+                                    voxel=fusion["voxel"], trunc=fusion["trunc"], empty=empty, znear=znear)
+
     def _refine_on_memory_batch(self, mem_pcs, new_pcs, T, radius, metric="point", normal_radius=None, **kw):
         """Scene memory, the pose the merge and the overlap gate trust (an extension beyond the released reference, like both): refine P
         registrations on the memory itself, at full resolution, in ONE ragged call (ops.cloud_icp_batch, csrc/cloudnear.hip) -- trimmed
@@ -676,7 +729,7 @@ def _encode_clouds(model, clouds):
 def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, optimize_codes=False, overlap_radius=None, min_overlap=None,
                    refine_radius=None, refine_metric="point", normal_radius=None, consolidate=False, consolidate_radius=None,
                    consolidate_max_variation=1 / 3, consolidate_max_shift=float("inf"), carve_tol=None, carve_window=1, carve_min_free=1,
-                   carve_max_seen=0, carve_empty="unknown"):
+                   carve_max_seen=0, carve_empty="unknown", fuse_res=None, fuse_trunc_voxels=4, fuse_empty="unknown"):
     """A reference scan followed by SEVERAL rescans, with a memory that carries every instance's points from one rescan to the next -- an
     extension beyond the released reference (more_solver.py:246-299 solves one (reference, rescan) pair and drops the rescan's points).
     ref and every rescan: {'pc' [n,3,Nmax], 'pc_mask'} as _solve_end2end takes them.
@@ -744,7 +797,19 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
     reported.  The merge runs on the carved memory; a slot that shrank or grew is re-encoded in the step's one re-encode call.  The step
     gains n_carved [n] (rows the step removed per slot) and carve_kept_as_is (slots).  carve_window = 1 is derived (the nearest-pixel
     rounding moves a ray by up to half a pixel).  carve_tol HAS NO DEFAULT AND NONE IS RECOMMENDED, nor any carve_min_free or
-    carve_max_seen: no real scans are available here to measure one on, and the effect on matching is unmeasured."""
+    carve_max_seen: no real scans are available here to measure one on, and the effect on matching is unmeasured.
+
+    The fusion (opt-in: with fuse_res None nothing below happens and every returned object is what it is without the arguments).  The
+    only mesh above is the decoder's idea of the object; with an int, the memory also carries what was OBSERVED as a distance field: one
+    truncated signed distance state of fuse_res^3 samples per slot, in the reference frame.  The grids are
+    More_Solver._fusion_grids(memory clouds after the initial merge, fuse_res, fuse_trunc_voxels) and never change.  ref['views'], if
+    present (one entry per instance, None allowed, dicts as for the carve), is fused under the identity.  Per rescan, ONE
+    More_Solver._fuse_batch call fuses the accepted pairs that carry 'views', after the registration, the refinement and the gate, under
+    the pose the merge uses; it does not depend on carve_tol.  The step gains n_fused_views [n].  memory gains 'fusion': dict(sum, n:
+    int32 [n,res,res,res] device tensors, origin, voxel, trunc: host float64); ops.tsdf_volume reads the volume and its valid flags
+    out of (sum, n).  NOT BUILT YET: a mesh of that volume -- it needs a marching cubes that drops cubes with an unobserved corner,
+    which the library does not have.  fuse_trunc_voxels = 4 is AN UNMEASURED DEFAULT; NO fuse_res IS RECOMMENDED: no real scans are
+    available here to measure one on, and what the fused volume does for anything downstream is unmeasured."""
     if refine_metric not in ("point", "plane"):
         raise ValueError(f"solve_sequence: refine_metric must be 'point' or 'plane', got {refine_metric!r}")
     if refine_metric == "plane" and refine_radius is None:
@@ -761,6 +826,12 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
                              f"{n_in} the encoder samples: the voxel is too coarse for this cloud")
     ref_codes = model.encode_fps(ref["pc"], ref["pc_mask"])
     codes = {k: ref_codes[k].detach().clone() for k in _CODE_KEYS}
+    fusion = None
+    if fuse_res is not None:
+        fusion = solver._fusion_grids(mem, fuse_res, fuse_trunc_voxels)
+        fusion["sum"], fusion["n"] = ops.tsdf_state(n, fusion.pop("dims"), mem[0].device)
+        if ref.get("views") is not None:
+            solver._fuse_batch(fusion, list(ref["views"]), empty=fuse_empty)
     steps = []
     for rescan in rescans:
         res_full = _scene_clouds(rescan)
@@ -772,6 +843,8 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
                "mesh_lst": [None] * n, "n_new_points": [0] * n, "unmatched_rescan": plan["unmatched_new"]}
         if carve_tol is not None:
             out.update({"n_carved": [0] * n, "carve_kept_as_is": []})
+        if fusion is not None:
+            out["n_fused_views"] = [0] * n
         if refine_radius is not None:
             out.update({"refine_stop": [None] * n, "refine_iters": [None] * n, "registration_init": [None] * n})
         if pairs:
@@ -824,6 +897,20 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
                         continue
                     out["n_carved"][i] = src[k].shape[0] - c.shape[0]
                     src[k] = mem[i] = c
+            fviews = rescan.get("views") if fusion is not None else None
+            fusing = [k for k in keep if fviews is not None and fviews[pairs[k][1]] is not None]
+            if fusing:                                                # the accepted pairs with views, under the pose the merge uses
+                slot_views, slot_pose = [None] * n, [None] * n
+                for k in fusing:
+                    i = pairs[k][0]
+                    slot_views[i] = fviews[pairs[k][1]]
+                    slot_pose[i] = (T[k] if refined is None else refined["g"][k]).detach().to(torch.float64)[:3, :]
+                    out["n_fused_views"][i] = int(slot_views[i]["depth"].shape[0])
+                # all n slots go into the one call, so that a slot is its own problem of the state; a slot without views is skipped by the
+                # operator and composes no camera: its row of `poses` is a placeholder that nothing reads
+                eye = torch.eye(4, dtype=torch.float64, device=T.device)[:3, :]
+                poses = torch.stack([eye if q is None else q.to(T.device) for q in slot_pose])
+                solver._fuse_batch(fusion, slot_views, T=poses if refined is None else None, g=None if refined is None else poses, empty=fuse_empty)
             grew = []
             if keep:
                 sel = torch.tensor(keep, device=T.device)
@@ -868,6 +955,8 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
     memory = {"clouds": mem, "codes": codes, "meshes": solver._mesh_from_latent_batch(codes) if mesh else None}
     if consolidate:
         memory["consolidation"] = consolidation
+    if fusion is not None:
+        memory["fusion"] = fusion
     return steps, memory
 
 

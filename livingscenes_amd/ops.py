@@ -1399,6 +1399,144 @@ def cloud_carve(A, depth, intrinsics, world_to_cam, *, tol, window=1, min_free=1
     return pts, src, f
 
 
+# ------------------------------------------------------------------------------------------------ depth fusion (csrc/depthfuse.hip)
+FUSE_CLASS = ("out", "empty", "occluded", "near", "free", "saturated")   # the columns of view_counts, by value
+
+
+def tsdf_state(P, dims, device="cuda"):
+    """a fresh fusion state for P problems: (sum, n), int32 zeros [P,nx,ny,nz] on `device` (ls_depth_fuse_f32 updates them in place)"""
+    P, dims = int(P), tuple(int(d) for d in dims)
+    if P < 1 or len(dims) != 3 or min(dims) < 1 or P * dims[0] * dims[1] * dims[2] >= 2 ** 31:
+        raise ValueError(f"tsdf_state: P >= 1 problems of dims (nx, ny, nz) >= 1 with P * nx * ny * nz < 2^31, got P = {P}, dims = {dims}")
+    return tuple(torch.zeros((P,) + dims, dtype=torch.int32, device=device) for _ in range(2))
+
+
+def _fuse_state(op, state, batch):
+    """state = (sum, n): int32 HIP tensors of one shape, [P,nx,ny,nz] (batch) or [nx,ny,nz] -> (sum, n, P, dims); nothing is copied"""
+    if not isinstance(state, (tuple, list)) or len(state) != 2:
+        raise ValueError(f"{op}: state is the pair (sum, n) that tsdf_state returns")
+    for name, t in zip(("state sum", "state n"), state):
+        if not torch.is_tensor(t) or t.device.type != "cuda" or t.dtype != torch.int32:
+            kind = f"{t.device.type} {t.dtype}" if torch.is_tensor(t) else type(t).__name__
+            raise _lib.LsError(f"{op}: {name} must be an int32 HIP (cuda) tensor, got {kind}: the MI355X path has no CPU fallback and converts nothing")
+        if t.dim() != (4 if batch else 3) or t.numel() == 0:
+            raise ValueError(f"{op}: {name} is {'[P,nx,ny,nz]' if batch else '[nx,ny,nz]'}, got {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{op}: {name} must be contiguous: it is updated in place")
+    S, N = state
+    if S.shape != N.shape or S.device != N.device:
+        raise ValueError(f"{op}: state sum is {tuple(S.shape)} on {S.device}, state n {tuple(N.shape)} on {N.device}")
+    return S, N, (S.shape[0] if batch else 1), tuple(S.shape[-3:])
+
+
+def _fuse_grid(op, P, origin, voxel, trunc=None):
+    """origin [P,3] (or [3]), voxel and trunc one value or P -> host float64 arrays [P,3], [P], [P]"""
+    o = torch.as_tensor(origin).detach().cpu().numpy() if torch.is_tensor(origin) else np.asarray(origin)
+    o = np.ascontiguousarray(o, dtype=np.float64)
+    if o.shape == (3,):
+        o = np.ascontiguousarray(np.broadcast_to(o, (P, 3)))
+    if o.shape != (P, 3):
+        raise ValueError(f"{op}: origin is [P,3] with P = {P}, got {o.shape}")
+    out = [o]
+    for name, v in (("voxel", voxel), ("trunc", trunc)):
+        if v is None:
+            continue
+        v = v.detach().cpu().numpy() if torch.is_tensor(v) else v
+        v = np.full(P, float(v), dtype=np.float64) if np.ndim(v) == 0 else np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+        if v.shape[0] != P:
+            raise ValueError(f"{op}: {v.shape[0]} values of {name} for {P} problems")
+        out.append(v)
+    return out
+
+
+def _fuse_empty(op, empty):
+    if empty not in _CARVE_EMPTY:
+        raise ValueError(f"{op}: empty must be 'unknown' or 'free', got {empty!r}")
+    return _CARVE_EMPTY[empty]
+
+
+def depth_fuse_batch(state, depths, intrinsics, world_to_cam, *, origin, voxel, trunc, empty="unknown", znear=0.05):
+    """ls_depth_fuse_batch_f32 (an extension beyond the released reference, like cloud_carve): posed depth views fused into the truncated
+    signed distance state of P instances IN PLACE.  state = (sum, n) int32 HIP tensors [P,nx,ny,nz] (tsdf_state); depths / intrinsics /
+    world_to_cam = lists of P: depth views [V_p,H,W] fp32 (0 = the ray hit nothing; one H x W per call; V_p = 0 or None: the problem is
+    left as it is), intrinsics [V_p,4] or [4] float64, world_to_cam [V_p,3,4] float64 FROM THE GRID'S FRAME; origin [P,3] (the centre
+    of voxel (0,0,0)), voxel and trunc (one value or P), host float64.  Per voxel and view the definition of
+    include/livingscenes_hip.h: the projective distance d - c.z at the nearest pixel, truncated to [-1, 1] and added as an integer, so
+    the state does not depend on the order of the views, on how they are split over calls or on the batch.  empty="free": pixels that
+    hit nothing count as free space (t = +1), "unknown": they are skipped.  NO voxel OR trunc IS RECOMMENDED: none has been measured
+    on real scans.  -> list of P device int64 [V_p,6]: voxels per class of FUSE_CLASS and view.  One call, no host read."""
+    op = "depth_fuse_batch"
+    S, N, P, dims = _fuse_state(op, state, True)
+    dev = S.device
+    if not (len(depths) == len(world_to_cam) == P) or (not torch.is_tensor(intrinsics) and len(intrinsics) != P):
+        raise ValueError(f"{op}: {P} problems in state for {len(depths)} sets of depth views and {len(world_to_cam)} sets of cameras")
+    o, h, tr = _fuse_grid(op, P, origin, voxel, trunc)
+    eif, znear = _fuse_empty(op, empty), float(znear)
+    Ks = [intrinsics] * P if torch.is_tensor(intrinsics) else list(intrinsics)
+    vw = [None if d is None else _carve_views(op, d, k, e, dev) for d, k, e in zip(depths, Ks, world_to_cam)]
+    shapes = sorted({tuple(v[0].shape[1:]) for v in vw if v is not None})
+    if len(shapes) > 1:
+        raise ValueError(f"{op}: one H x W per call, got {shapes}")
+    nviews = [0 if v is None else v[0].shape[0] for v in vw]
+    vo = _offsets(nviews)
+    views = int(vo[P])
+    if views == 0:
+        return [torch.zeros(0, 6, dtype=torch.int64, device=dev) for _ in range(P)]
+    have = [v for v in vw if v is not None and v[0].shape[0]]
+    D, K, E = (torch.cat(t, 0) if len(have) > 1 else t[0] for t in zip(*have))
+    H, W = shapes[0]
+    vc = torch.empty(views, 6, dtype=torch.int64, device=dev)
+    ws_bytes = load().ls_depth_fuse_batch_workspace_bytes(P, *dims, views)
+    if ws_bytes == 0:
+        raise ValueError(f"{op}: P = {P} problems of dims {dims} with {views} views unsupported (include/livingscenes_hip.h: P nx ny nz < 2^31)")
+    ws = _scratch(ws_bytes, dev)
+    call(dev, "ls_depth_fuse_batch_f32", P, ptr(S), ptr(N), *dims, _hptr(o), _hptr(h), _hptr(tr), ptr(D), views, _hptr(vo), H, W, ptr(K), ptr(E),
+         znear, eif, ptr(vc), ptr(ws), ws.numel(), stream_ptr(dev))
+    return list(torch.split(vc, nviews))
+
+
+def depth_fuse(state, depth, intrinsics, world_to_cam, *, origin, voxel, trunc, empty="unknown", znear=0.05):
+    """ls_depth_fuse_f32: the views depth [V,H,W] fp32 with intrinsics [V,4] or [4] and world_to_cam [V,3,4] float64 from the grid's frame
+    fused into state = (sum, n), int32 HIP tensors [nx,ny,nz] (a slice of tsdf_state), IN PLACE; origin [3], voxel and trunc host float64.
+    -> device int64 [V,6], the voxels per class of FUSE_CLASS, as depth_fuse_batch describes them (no voxel or trunc is recommended).
+    Bit-identical to the same problem inside any depth_fuse_batch, and to the same views in any order or split over calls."""
+    op = "depth_fuse"
+    S, N, _, dims = _fuse_state(op, state, False)
+    dev = S.device
+    o, h, tr = _fuse_grid(op, 1, origin, voxel, trunc)
+    eif, znear = _fuse_empty(op, empty), float(znear)
+    D, K, E = _carve_views(op, depth, intrinsics, world_to_cam, dev)
+    views, H, W = D.shape
+    vc = torch.empty(views, 6, dtype=torch.int64, device=dev)
+    if views == 0:
+        return vc
+    ws_bytes = load().ls_depth_fuse_workspace_bytes(*dims, views)
+    if ws_bytes == 0:
+        raise ValueError(f"{op}: dims {dims} with {views} views unsupported (include/livingscenes_hip.h: nx ny nz < 2^31)")
+    ws = _scratch(ws_bytes, dev)
+    call(dev, "ls_depth_fuse_f32", ptr(S), ptr(N), *dims, _hptr(o), float(h[0]), float(tr[0]), ptr(D), views, H, W, ptr(K), ptr(E), znear, eif,
+         ptr(vc), ptr(ws), ws.numel(), stream_ptr(dev))
+    return vc
+
+
+def tsdf_volume(state, min_obs=1):
+    """ls_tsdf_volume_f64: state = (sum, n) int32 HIP tensors [P,nx,ny,nz] or [nx,ny,nz] -> (volume float64, valid uint8, of the state's
+    shape; counts device int64 [P,3] or [3] = valid samples, valid samples with D <= 0, samples never observed).  A sample is valid iff
+    n >= min_obs (>= 1); D = sum / (n * 16384) where valid, else exactly +1.0.  NO min_obs IS RECOMMENDED: 1 is the least, unmeasured."""
+    op = "tsdf_volume"
+    batch = isinstance(state, (tuple, list)) and len(state) == 2 and torch.is_tensor(state[0]) and state[0].dim() == 4
+    S, N, P, dims = _fuse_state(op, state, batch)
+    min_obs = int(min_obs)
+    if min_obs < 1:
+        raise ValueError(f"{op}: min_obs must be >= 1, got {min_obs}")
+    dev = S.device
+    vol = torch.empty(S.shape, dtype=torch.float64, device=dev)
+    valid = torch.empty(S.shape, dtype=torch.uint8, device=dev)
+    counts = torch.empty(P, 3, dtype=torch.int64, device=dev)
+    call(dev, "ls_tsdf_volume_f64", ptr(S), ptr(N), P, *dims, min_obs, ptr(vol), ptr(valid), ptr(counts), stream_ptr(dev))
+    return vol, valid, (counts if batch else counts[0])
+
+
 def _plane_normals(x, A, op):
     x = _cloud(x, "N", op)
     if x.shape[0] != A.shape[0] or x.device != A.device:
