@@ -65,7 +65,7 @@ typedef enum {
  * ls_cloud_merge_f32 / ls_cloud_merge_batch_f32, ls_cloud_nearest_f32 / ls_cloud_nearest_batch_f32, ls_cloud_icp_f32 / ls_cloud_icp_batch_f32,
  * ls_cloud_normals_f32 / ls_cloud_normals_batch_f32, ls_cloud_icp_plane_f32 / ls_cloud_icp_plane_batch_f32, ls_cloud_project_f32 / ls_cloud_project_batch_f32,
  * ls_mesh_render_depth_f64 / ls_mesh_render_depth_batch_f64, ls_depth_points_f32, ls_cloud_carve_f32 / ls_cloud_carve_batch_f32,
- * ls_depth_fuse_f32 / ls_depth_fuse_batch_f32, ls_tsdf_volume_f64 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
+ * ls_depth_fuse_f32 / ls_depth_fuse_batch_f32, ls_tsdf_volume_f64, ls_tsdf_mesh_f64 / ls_tsdf_mesh_batch_f64 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
  * binding compares it with the header it was written against and refuses a mismatch (livingscenes_amd/_lib.py: load). */
 #define LS_ABI_VERSION 107
 int ls_version(void);
@@ -1014,10 +1014,52 @@ int ls_depth_fuse_batch_f32(int P, int32_t* sum, int32_t* n, int nx, int ny, int
 /* State to volume, per sample of sum, n [B,nx,ny,nz]: valid = n >= min_obs (min_obs >= 1); D = (double)sum / ((double)n * 16384.0) where
  * valid, else EXACTLY +1.0.  volume_out float64 and valid_out uint8 [B,nx,ny,nz]; counts_out [B,3] int64 = valid samples, valid samples
  * with D <= 0, samples with n == 0 (all DEVICE).  1 memset and 1 kernel.  Filling what was never observed with +1 puts a second shell
- * where the truncation band ends: a mesher of this volume must drop every cube that has a corner with valid_out == 0 (NOT PART OF THIS
- * LIBRARY YET: ls_marching_cubes_f64 takes no mask). */
+ * where the truncation band ends: a mesher of this volume must drop every cube that has a corner with valid_out == 0.
+ * ls_marching_cubes_f64 takes no mask; ls_tsdf_mesh_f64 below meshes the STATE and needs no volume. */
 int ls_tsdf_volume_f64(const int32_t* sum, const int32_t* n, int B, int nx, int ny, int nz, int min_obs, double* volume_out, uint8_t* valid_out,
                        long long* counts_out, void* stream);
+
+/* Scene memory, the mesh of a fused state where it was OBSERVED (csrc/tsdfmesh.hip, csrc/tsdfmesh_plan.h).  AN EXTENSION BEYOND THE
+ * RELEASED REFERENCE, like the fusion.  Marching cubes of the state at isovalue 0 (not an argument), restricted to what was seen; no float64
+ * volume is materialised and there is no compaction step.  Inputs per problem: sum, n int32 [nx,ny,nz] (DEVICE, read only), min_obs >= 1,
+ * origin[3] and voxel > 0 (float64, HOST).  Definition (tests/fuse_oracle.py: mesh is the same text as NumPy, tests/tsdf_mesh_oracle.py the
+ * local rule of step 3):
+ *   1. sample   valid iff n >= min_obs; D = (double)sum / ((double)n * 16384.0) where valid (ls_tsdf_volume_f64's value; an invalid sample
+ *               reads +1 in the pattern and in nothing else).
+ *   2. cube     the (nx-1)(ny-1)(nz-1) cubes in C order, the pattern from D <= 0 on the eight corners in ls_marching_cubes_f64's corner
+ *               order.  A cube is KEPT iff all eight corners are valid; a kept cube emits the triangles of its row of the triangle table,
+ *               in table order; a dropped cube emits none.
+ *   3. vertex   libmcubes creates the vertex of a crossed edge in the first cube that owns it: every cube owns its edges 6, 5, 10 and, on
+ *               the low faces of the volume, the otherwise inherited ones.  A created vertex is CARRIED iff a kept cube names it: its own
+ *               cube, or, for the edges 6, 5, 10, one of the up to three other cubes around that lattice edge.  Both ends of a carried
+ *               edge are valid: NO POSITION EVER READS AN UNOBSERVED SAMPLE.  The owner of a carried vertex need not be a kept cube.
+ *   4. order    the carried vertices in libmcubes' creation order (owner cubes in C order; inside a cube 6, 5, 10, 0, 1, 2, 3, 4, 7, 8, 9,
+ *               11): the vertices ls_marching_cubes_f64 would number, with the ones no kept face names left out.
+ *   5. position the libmcubes interpolation on D with the +0.5 offset, x = (f2 == f1) ? (x2 + x1) / 2 : (x2 - x1) * (0 - f1) / (f2 - f1) + x1,
+ *               then (V - 0.5) * voxel + origin as three separate operations, nothing contracted: the result is exact, not approximate.
+ *   6. faces    indices count from the mesh's own first vertex.
+ * Calling convention of ls_marching_cubes_batch_f64: off_out (DEVICE long long [2][P+1]) = first vertex / first face of every mesh and the
+ * totals, always the FULL counts; nothing is written at or past cap_v vertices / cap_f faces of the packed outputs; vertices = faces = NULL
+ * is a sizing call.  stats_out (DEVICE long long [P][3], may be NULL) = kept cubes, dropped cubes whose pattern holds a crossing, valid
+ * samples.  A problem without a kept cube yields an empty mesh and the ones after it are unaffected; a dim < 2 zeroes off_out.
+ * Refused on the host before the first HIP call, the problem named where there is one: dims < 1, P outside 1 .. 65535,
+ * 15 P nx ny nz >= 2^31 (int bases), min_obs < 1, voxel not finite or <= 0, a non-finite origin, a negative capacity, vertices without
+ * faces or the reverse, a short workspace (LS_ERR_WORKSPACE).
+ * Passes, one launch each whatever P: classify (4096 samples per workgroup, k on consecutive lanes, 8 gathers of (sum, n) -> pattern and kept
+ * bit, 16 bit per cube; the statistics are three integer atomics per workgroup), count (the carried mask per cube from the kept bits of its neighbours; vertices << 32 | face indices summed per workgroup
+ * of 4096 cubes), one scan over the workgroup sums of the batch, vertices (per-cube bases, positions), faces (final indices: own vertices
+ * by rank, inherited ones from the owner's base plus the rank among the owner's CARRIED vertices).  Also the copy of the host grids into
+ * the workspace and, with stats_out, 1 memset.  hipGetLastError() is read after EVERY launch and the error names the pass.  No host
+ * synchronisation, no allocation, no floating-point atomics.  The workspace is a function of (P, nx, ny, nz) alone, 0 for refused sizes.
+ * The single entry is the batch of one problem, BIT-IDENTICAL.  NO min_obs IS RECOMMENDED: 1 is the least, unmeasured on real scans. */
+size_t ls_tsdf_mesh_workspace_bytes(int nx, int ny, int nz);
+int ls_tsdf_mesh_f64(const int32_t* sum, const int32_t* n, int nx, int ny, int nz, int min_obs, const double* origin, double voxel, double* vertices,
+                     long long cap_v, long long* faces, long long cap_f, long long* off_out, long long* stats_out, void* workspace,
+                     size_t workspace_bytes, void* stream);
+size_t ls_tsdf_mesh_batch_workspace_bytes(int P, int nx, int ny, int nz);
+int ls_tsdf_mesh_batch_f64(int P, const int32_t* sum, const int32_t* n, int nx, int ny, int nz, int min_obs, const double* origin, const double* voxel,
+                           double* vertices, long long cap_v, long long* faces, long long cap_f, long long* off_out, long long* stats_out,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* Scene memory, the trimmed ICP with the point-to-plane metric (csrc/cloudnear.hip).  AN EXTENSION BEYOND THE RELEASED REFERENCE, like
  * ls_cloud_icp_f32, whose loop this is: a partial view registered point-to-point onto one point per voxel of a SURFACE slides along it

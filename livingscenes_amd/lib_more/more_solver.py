@@ -472,6 +472,20 @@ class More_Solver:
                                     [shared if v is None else v["intrinsics"] for v in views], cams, origin=fusion["origin"],
                                     voxel=fusion["voxel"], trunc=fusion["trunc"], empty=empty, znear=znear)
 
+    @staticmethod
+    def _observed_mesh_batch(fusion, min_obs=1):
+        """Scene memory, the one mesh the memory can stand behind (an extension beyond the released reference, like _fuse_batch): the fused
+        states of P instances meshed where they were OBSERVED, in ONE batched call (ops.tsdf_mesh_batch, csrc/tsdfmesh.hip).  fusion =
+        the dict of _fuse_batch (sum, n, origin, voxel).  A cube with a corner seen fewer than min_obs times emits nothing, so the mesh has
+        holes where nothing looked and no second shell at the end of the truncation band.  -> list of P make_mesh(vertices, faces) in the
+        memory's frame, the arrays copied to the host ONCE for the whole batch; None for an instance whose mesh is empty.  NO min_obs IS
+        RECOMMENDED: 1 is the least, unmeasured on real scans."""
+        from ..mesh_extractor2 import make_mesh
+        verts, faces, vo, fo, _ = ops.tsdf_mesh_batch((fusion["sum"], fusion["n"]), origin=fusion["origin"], voxel=fusion["voxel"], min_obs=min_obs,
+                                                      packed=True)
+        verts, faces = verts.cpu().numpy(), faces.cpu().numpy()
+        return [make_mesh(verts[vo[p]:vo[p + 1]], faces[fo[p]:fo[p + 1]]) if fo[p + 1] > fo[p] else None for p in range(len(vo) - 1)]
+
     def _refine_on_memory_batch(self, mem_pcs, new_pcs, T, radius, metric="point", normal_radius=None, **kw):
         """Scene memory, the pose the merge and the overlap gate trust (an extension beyond the released reference, like both): refine P
         registrations on the memory itself, at full resolution, in ONE ragged call (ops.cloud_icp_batch, csrc/cloudnear.hip) -- trimmed
@@ -729,7 +743,8 @@ def _encode_clouds(model, clouds):
 def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, optimize_codes=False, overlap_radius=None, min_overlap=None,
                    refine_radius=None, refine_metric="point", normal_radius=None, consolidate=False, consolidate_radius=None,
                    consolidate_max_variation=1 / 3, consolidate_max_shift=float("inf"), carve_tol=None, carve_window=1, carve_min_free=1,
-                   carve_max_seen=0, carve_empty="unknown", fuse_res=None, fuse_trunc_voxels=4, fuse_empty="unknown"):
+                   carve_max_seen=0, carve_empty="unknown", fuse_res=None, fuse_trunc_voxels=4, fuse_empty="unknown", fuse_mesh=False,
+                   fuse_min_obs=1):
     """A reference scan followed by SEVERAL rescans, with a memory that carries every instance's points from one rescan to the next -- an
     extension beyond the released reference (more_solver.py:246-299 solves one (reference, rescan) pair and drops the rescan's points).
     ref and every rescan: {'pc' [n,3,Nmax], 'pc_mask'} as _solve_end2end takes them.
@@ -807,13 +822,17 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
     More_Solver._fuse_batch call fuses the accepted pairs that carry 'views', after the registration, the refinement and the gate, under
     the pose the merge uses; it does not depend on carve_tol.  The step gains n_fused_views [n].  memory gains 'fusion': dict(sum, n:
     int32 [n,res,res,res] device tensors, origin, voxel, trunc: host float64); ops.tsdf_volume reads the volume and its valid flags
-    out of (sum, n).  NOT BUILT YET: a mesh of that volume -- it needs a marching cubes that drops cubes with an unobserved corner,
-    which the library does not have.  fuse_trunc_voxels = 4 is AN UNMEASURED DEFAULT; NO fuse_res IS RECOMMENDED: no real scans are
-    available here to measure one on, and what the fused volume does for anything downstream is unmeasured."""
+    out of (sum, n).  fuse_mesh=True (it needs fuse_res; without one a ValueError) meshes that state ONCE, after the last step: memory
+    gains 'observed_meshes', More_Solver._observed_mesh_batch(fusion, fuse_min_obs): one mesh per slot in the reference frame, of
+    the cubes whose eight corners were observed at least fuse_min_obs times, None for a slot nothing kept.  With fuse_mesh False the
+    memory has no such key.  fuse_trunc_voxels = 4 is AN UNMEASURED DEFAULT; NO fuse_res IS RECOMMENDED, and no fuse_min_obs: no real scans are
+    available here to measure one on, and what the fused volume or its mesh does for anything downstream is unmeasured."""
     if refine_metric not in ("point", "plane"):
         raise ValueError(f"solve_sequence: refine_metric must be 'point' or 'plane', got {refine_metric!r}")
     if refine_metric == "plane" and refine_radius is None:
         raise ValueError("solve_sequence: refine_metric 'plane' needs refine_radius: without it there is no refinement to choose a metric for")
+    if fuse_mesh and fuse_res is None:
+        raise ValueError("solve_sequence: fuse_mesh needs fuse_res: without a fused state there is nothing to mesh")
     gate = overlap_radius is not None or min_overlap is not None
     model = solver.model
     n_in = solver.cfg["shape_priors"]["n_input_point"]
@@ -957,6 +976,8 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
         memory["consolidation"] = consolidation
     if fusion is not None:
         memory["fusion"] = fusion
+        if fuse_mesh:
+            memory["observed_meshes"] = solver._observed_mesh_batch(fusion, fuse_min_obs)
     return steps, memory
 
 

@@ -1537,6 +1537,63 @@ def tsdf_volume(state, min_obs=1):
     return vol, valid, (counts if batch else counts[0])
 
 
+MESH_COUNT = ("kept_cubes", "dropped_crossed_cubes", "valid_samples")   # the columns of tsdf_mesh's counts, by value
+
+
+def _tsdf_mesh_packed(op, single, state, origin, voxel, min_obs):
+    """-> (vertices [sum nv,3] float64, faces [sum nf,3] int64, vertex offsets, face offsets: host lists of P+1, counts device int64 [P,3])"""
+    S, N, P, dims = _fuse_state(op, state, not single)
+    min_obs = int(min_obs)
+    if min_obs < 1:
+        raise ValueError(f"{op}: min_obs must be >= 1, got {min_obs}")
+    o, h = _fuse_grid(op, P, origin, voxel)
+    dev = S.device
+    name = "ls_tsdf_mesh" if single else "ls_tsdf_mesh_batch"
+    ws_bytes = getattr(load(), name + "_workspace_bytes")(*(() if single else (P,)), *dims)
+    if ws_bytes == 0:
+        raise ValueError(f"{op}: P = {P} problems of dims {dims} unsupported (include/livingscenes_hip.h: P <= 65535, 15 P nx ny nz < 2^31)")
+    ws = _scratch(ws_bytes, dev)
+    off = torch.zeros(2, P + 1, dtype=torch.int64, device=dev)
+    counts = torch.empty(P, 3, dtype=torch.int64, device=dev)
+    head = (ptr(S), ptr(N), *dims, min_obs, _hptr(o), float(h[0]) if single else _hptr(h))
+    if not single:
+        head = (P,) + head
+    call(dev, name + "_f64", *head, None, 0, None, 0, ptr(off), None, ptr(ws), ws.numel(), stream_ptr(dev))
+    vo, fo = off.cpu().tolist()                                          # the one host read
+    verts = torch.empty(vo[P], 3, dtype=torch.float64, device=dev)
+    faces = torch.empty(fo[P], 3, dtype=torch.int64, device=dev)
+    # the real call also when the meshes are empty: it fills the counts (and writes nothing into the empty outputs)
+    call(dev, name + "_f64", *head, ptr(verts) if vo[P] else None, vo[P], ptr(faces) if vo[P] else None, fo[P], ptr(off), ptr(counts), ptr(ws),
+         ws.numel(), stream_ptr(dev))
+    return verts, faces, vo, fo, counts
+
+
+def tsdf_mesh_batch(state, *, origin, voxel, min_obs=1, packed=False):
+    """ls_tsdf_mesh_batch_f64 (an extension beyond the released reference, like depth_fuse): the fused states of P instances meshed where
+    they were OBSERVED.  state = (sum, n) int32 HIP tensors [P,nx,ny,nz] (tsdf_state, depth_fuse_batch); origin [P,3] or [3], voxel (one
+    value or P): host float64, the grids the views were fused on.  Marching cubes at 0 of D = sum / (n * 16384) over the cubes whose eight
+    corners have n >= min_obs, with exactly the vertices those cubes name, in libmcubes' order, at (V - 0.5) * voxel + origin: the
+    definition of include/livingscenes_hip.h, by equality.  No float64 volume is made and nothing is compacted afterwards.
+    -> (list of P (vertices [nv,3] float64, faces [nf,3] int64) device tensors, views of the packed outputs, face indices local to their
+    mesh; counts device int64 [P,3], the columns of MESH_COUNT: kept cubes, dropped cubes that hold a crossing, valid samples).
+    packed=True -> (vertices, faces, vertex offsets, face offsets: host lists of P+1, counts).  One sizing call, ONE host read of the
+    offsets, one real call.  An instance nothing kept yields an empty mesh.  DO NOT index a device tensor with the faces before they have
+    been range-checked on the host: faces < nv is what the tests assert there.  NO min_obs IS RECOMMENDED: 1 is the least, unmeasured
+    on real scans."""
+    verts, faces, vo, fo, counts = _tsdf_mesh_packed("tsdf_mesh_batch", False, state, origin, voxel, min_obs)
+    if packed:
+        return verts, faces, vo, fo, counts
+    return [(verts[vo[p]:vo[p + 1]], faces[fo[p]:fo[p + 1]]) for p in range(len(vo) - 1)], counts
+
+
+def tsdf_mesh(state, *, origin, voxel, min_obs=1):
+    """ls_tsdf_mesh_f64: state = (sum, n) int32 HIP tensors [nx,ny,nz] (a slice of tsdf_state), origin [3] and voxel host float64 ->
+    (vertices [nv,3] float64, faces [nf,3] int64, counts device int64 [3] of MESH_COUNT), as tsdf_mesh_batch describes them and
+    bit-identical to the same problem inside any batch.  NO min_obs IS RECOMMENDED: 1 is the least, unmeasured on real scans."""
+    verts, faces, _, _, counts = _tsdf_mesh_packed("tsdf_mesh", True, state, origin, voxel, min_obs)
+    return verts, faces, counts[0]
+
+
 def _plane_normals(x, A, op):
     x = _cloud(x, "N", op)
     if x.shape[0] != A.shape[0] or x.device != A.device:
