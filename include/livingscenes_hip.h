@@ -65,7 +65,8 @@ typedef enum {
  * ls_cloud_merge_f32 / ls_cloud_merge_batch_f32, ls_cloud_nearest_f32 / ls_cloud_nearest_batch_f32, ls_cloud_icp_f32 / ls_cloud_icp_batch_f32,
  * ls_cloud_normals_f32 / ls_cloud_normals_batch_f32, ls_cloud_icp_plane_f32 / ls_cloud_icp_plane_batch_f32, ls_cloud_project_f32 / ls_cloud_project_batch_f32,
  * ls_mesh_render_depth_f64 / ls_mesh_render_depth_batch_f64, ls_depth_points_f32, ls_cloud_carve_f32 / ls_cloud_carve_batch_f32,
- * ls_depth_fuse_f32 / ls_depth_fuse_batch_f32, ls_tsdf_volume_f64, ls_tsdf_mesh_f64 / ls_tsdf_mesh_batch_f64 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
+ * ls_depth_fuse_f32 / ls_depth_fuse_batch_f32, ls_tsdf_volume_f64, ls_tsdf_mesh_f64 / ls_tsdf_mesh_batch_f64,
+ * ls_tsdf_sample_f32 / ls_tsdf_sample_batch_f32, ls_tsdf_icp_f32 / ls_tsdf_icp_batch_f32 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
  * binding compares it with the header it was written against and refuses a mismatch (livingscenes_amd/_lib.py: load). */
 #define LS_ABI_VERSION 107
 int ls_version(void);
@@ -1060,6 +1061,89 @@ size_t ls_tsdf_mesh_batch_workspace_bytes(int P, int nx, int ny, int nz);
 int ls_tsdf_mesh_batch_f64(int P, const int32_t* sum, const int32_t* n, int nx, int ny, int nz, int min_obs, const double* origin, const double* voxel,
                            double* vertices, long long cap_v, long long* faces, long long cap_f, long long* off_out, long long* stats_out,
                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* Scene memory, the fused state READ at a point (csrc/tsdficp.hip).  AN EXTENSION BEYOND THE RELEASED REFERENCE, like ls_depth_fuse_f32,
+ * whose state (sum, n int32 [nx,ny,nz], DEVICE) and grid (origin [3], voxel h, trunc: float64, HOST, origin the centre of voxel (0,0,0))
+ * these are.  min_obs >= 1; queries B [b,3] fp32 (DEVICE); pose g [3,4] fp32 (DEVICE), rescan -> memory, NULL: B bit for bit.
+ * Definition, per query (csrc/tsdfsample_plan.h is this text as pure C++, tests/tsdf_sample_oracle.py as NumPy); everything after step 1
+ * is float64 and nothing is contracted:
+ *   1 posed query   y_a = ((R_a0 x_0 + R_a1 x_1) + R_a2 x_2) + t_a in fp32, every product and sum rounded: the expression of
+ *                   ls_cloud_merge_f32; yd = (double) y.
+ *   2 grid coord.   u_a = (yd_a - origin_a) / h.  State OUT (0) if a component of y is not finite, if a dimension is below 2 (no cell), or
+ *                   unless 0 <= u_a <= n_a - 1 on every axis.  Else the base index i_a = min((int) floor(u_a), n_a - 2) -- the far face
+ *                   belongs to the last cell -- and f_a = u_a - (double) i_a.
+ *   3 corners       the eight samples (i_0 + alpha, i_1 + beta, i_2 + gamma), each valid iff n >= min_obs, D = sum / (n * 16384) as in
+ *                   ls_tsdf_volume_f64.  State UNSEEN (1) if any corner is invalid -- no value ever reads an unobserved sample -- else
+ *                   SAMPLED (2).
+ *   4 value         with lerp(a, b, f) = a + f * (b - a): along axis 2, a[alpha beta] = lerp(D[alpha beta 0], D[alpha beta 1], f_2); along
+ *                   axis 1, b[alpha] = lerp(a[alpha 0], a[alpha 1], f_1); along axis 0, v = lerp(b[0], b[1], f_0).  phi = trunc * v, metres.
+ *   5 gradient      the exact derivative of that interpolant, which is affine in every f_a:
+ *                   G_2 = lerp_0(lerp_1(D[alpha beta 1] - D[alpha beta 0])): first over beta with f_1, then over alpha with f_0;
+ *                   G_1 = lerp_0(lerp_2(D[alpha 1 gamma] - D[alpha 0 gamma])): first over gamma with f_2, then over alpha with f_0;
+ *                   G_0 = lerp_1(lerp_2(D[1 beta gamma] - D[0 beta gamma])): first over gamma with f_2, then over beta with f_1;
+ *                   grad_a = (trunc / h) * G_a, trunc / h formed once per problem on the host.  The gradient is NOT normalised.
+ *   6 outputs       OUT and UNSEEN queries write phi = +trunc and grad = 0.
+ * Outputs (DEVICE): phi double [b], grad double [b,3], state uint8 [b], counts long long [3] = finite queries, queries inside the grid
+ * (not OUT), SAMPLED queries; sum_phi2 double [1] = the sum of phi^2 over the SAMPLED queries by the chunk rule of ls_cloud_icp_f32: a
+ * workgroup owns 256 consecutive queries of ONE problem, a fixed tree inside each wave of 64 (lane l with l + 32, l + 16, ..., l + 1), a
+ * fixed tree over the four waves ((w0 + w1) + (w2 + w3)), one record per chunk, the records added in chunk order.  No atomics.
+ * Refused on the host before the first HIP call, the error naming the problem: dims < 1, P nx ny nz >= 2^31, min_obs < 1, b < 0 or
+ * > 2^31 - 1, null pointers, an origin that is not finite, voxel or trunc not finite and > 0, trunc / voxel not finite, bad offsets.
+ * Launches: the copy of the host arrays into the workspace and 2 kernels, whatever P; no host synchronisation, no allocation;
+ * hipGetLastError() is read after every launch and the error names the pass.  The workspace is a function of (P, b) alone, 0 for refused
+ * sizes.  Queries arrive in no spatial order, so the corner gathers are scattered; they are not sorted here.  NO min_obs IS RECOMMENDED. */
+#define LS_SAMPLE_OUT 0
+#define LS_SAMPLE_UNSEEN 1
+#define LS_SAMPLE_SAMPLED 2
+size_t ls_tsdf_sample_workspace_bytes(int nx, int ny, int nz, long long b);
+int ls_tsdf_sample_f32(const int32_t* sum, const int32_t* n, int nx, int ny, int nz, int min_obs, const double* origin, double voxel, double trunc,
+                       const float* B, long long b, const float* g, double* phi, double* grad, uint8_t* state, long long* counts, double* sum_phi2,
+                       void* workspace, size_t workspace_bytes, void* stream);
+/* P >= 1 problems per call: one (nx, ny, nz) per call, sum / n [P,nx,ny,nz], origin [P,3], voxel [P], trunc [P] (HOST), B [b_total,3] with
+ * b_off HOST int64 [P+1] (empty problems allowed), g [P,3,4] or NULL, counts [P,3], sum_phi2 [P].  Every output of every problem is
+ * BIT-IDENTICAL to ls_tsdf_sample_f32 on that problem alone: the single entry is the batch of one problem. */
+size_t ls_tsdf_sample_batch_workspace_bytes(int P, int nx, int ny, int nz, long long b_total);
+int ls_tsdf_sample_batch_f32(int P, const int32_t* sum, const int32_t* n, int nx, int ny, int nz, int min_obs, const double* origin,
+                             const double* voxel, const double* trunc, const float* B, long long b_total, const long long* b_off, const float* g,
+                             double* phi, double* grad, uint8_t* state, long long* counts, double* sum_phi2, void* workspace, size_t workspace_bytes,
+                             void* stream);
+
+/* Scene memory, a rescan REGISTERED onto the fused state without any search (csrc/tsdficp.hip; Bylow, Sturm, Kerl, Kahl, Cremers, RSS
+ * 2013).  AN EXTENSION BEYOND THE RELEASED REFERENCE.  The arguments are those of ls_tsdf_sample_f32 with g0 (NULL: the identity as a
+ * matrix) in the place of g, plus max_iter, rel_thr, min_matched (>= 3) as in ls_cloud_icp_plane_f32.  Per problem, g_0 as in
+ * ls_cloud_icp_f32, for k = 0, 1, ...:
+ *   sample      exactly ls_tsdf_sample_f32 under g_k -> f_k (finite), w_k (SAMPLED), Q_k = sum phi^2 by the chunk rule.
+ *   cost        E_k = (Q_k + (f_k - w_k) trunc^2) / f_k, 0 for f_k = 0: the truncated quadratic of ls_cloud_icp_f32 with trunc in the place
+ *               of r.  A query in saturated free space has phi = trunc and grad = 0: it costs what an unsampled one costs and pulls on
+ *               nothing.
+ *   stop tests  those of ls_cloud_icp_plane_f32 in its order, each keeping g_k, min_matched applied to w_k: w_k < min_matched:
+ *               LS_ICP_STARVED; k >= 1 and E_{k-1} - E_k <= rel_thr E_{k-1}: LS_ICP_CONVERGED; k == max_iter: LS_ICP_MAX_ITER.
+ *   update      minimise sum (phi + omega . (y x grad) + v . grad)^2 over the SAMPLED queries: J = (grad, yd x grad) in the twist order
+ *               (v, omega); the 28 float64 moments (phi^2, J phi [6], J J^T [21, the upper triangle by rows]) per chunk, added by the chunk
+ *               rule, in the record layout of ls_cloud_icp_plane_f32.  THE GRADIENT IS NOT NORMALISED, NOTHING IS WEIGHTED, AND THERE IS NO
+ *               LINE SEARCH AND NO DAMPING: a step that raises E ends the loop as LS_ICP_CONVERGED at the next test, with the pose that
+ *               step produced.
+ *   solve and retraction  exactly those of ls_cloud_icp_plane_f32 (one text, csrc/se3_gn.h): Cholesky in float64 in a fixed order, a pivot
+ *               that is not > 1e-12 times the original diagonal entry or any non-finite value: LS_ICP_DEGENERATE, g_k is kept (the state
+ *               of one plane, all gradients parallel, is the exact case); exp of the twist; R' onto SO(3); rounded to fp32.
+ * Outputs: g_out [3,4] fp32, stop int32 (LS_ICP_*), iters int32, and the complete result of the final sample -- phi, grad, state, counts,
+ * sum_phi2 -- bit for bit ls_tsdf_sample_f32 at g_out: a stopped problem is frozen (its sample workgroups return at once), so these are
+ * its last live sample's.  Optional traces: g_trace float [max_iter+1, 12], stat_trace double [max_iter+1, 3] = (f_k, w_k, Q_k); rows
+ * past the stop are left alone.  Launches: the copy and 2 max_iter + 4 kernels, whatever P and whenever problems stop; no host
+ * synchronisation, no allocation, no atomics.  The start error must lie within trunc.  NO SETTING IS RECOMMENDED. */
+size_t ls_tsdf_icp_workspace_bytes(int nx, int ny, int nz, long long b);
+int ls_tsdf_icp_f32(const int32_t* sum, const int32_t* n, int nx, int ny, int nz, int min_obs, const double* origin, double voxel, double trunc,
+                    const float* B, long long b, const float* g0, int max_iter, double rel_thr, int min_matched, float* g_out, int32_t* stop,
+                    int32_t* iters, double* phi, double* grad, uint8_t* state, long long* counts, double* sum_phi2, float* g_trace,
+                    double* stat_trace, void* workspace, size_t workspace_bytes, void* stream);
+/* P >= 1 problems per call with the conventions of ls_tsdf_sample_batch_f32; g0 [P,3,4] or NULL, g_out [P,3,4], stop / iters [P], g_trace
+ * [P, max_iter+1, 12], stat_trace [P, max_iter+1, 3].  Every output of every problem is BIT-IDENTICAL to ls_tsdf_icp_f32 on it alone. */
+size_t ls_tsdf_icp_batch_workspace_bytes(int P, int nx, int ny, int nz, long long b_total);
+int ls_tsdf_icp_batch_f32(int P, const int32_t* sum, const int32_t* n, int nx, int ny, int nz, int min_obs, const double* origin, const double* voxel,
+                          const double* trunc, const float* B, long long b_total, const long long* b_off, const float* g0, int max_iter,
+                          double rel_thr, int min_matched, float* g_out, int32_t* stop, int32_t* iters, double* phi, double* grad, uint8_t* state,
+                          long long* counts, double* sum_phi2, float* g_trace, double* stat_trace, void* workspace, size_t workspace_bytes,
+                          void* stream);
 
 /* Scene memory, the trimmed ICP with the point-to-plane metric (csrc/cloudnear.hip).  AN EXTENSION BEYOND THE RELEASED REFERENCE, like
  * ls_cloud_icp_f32, whose loop this is: a partial view registered point-to-point onto one point per voxel of a SURFACE slides along it

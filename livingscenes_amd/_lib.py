@@ -236,6 +236,15 @@ SIGNATURES = {
     "ls_tsdf_mesh_f64": (_I, [_P, _P, _I, _I, _I, _I, _P, _D, _P, _LL, _P, _LL, _P, _P, _P, _SZ, _P]),
     "ls_tsdf_mesh_batch_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "ls_tsdf_mesh_batch_f64": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _LL, _P, _LL, _P, _P, _P, _SZ, _P]),
+    "ls_tsdf_sample_workspace_bytes": (_SZ, [_I, _I, _I, _LL]),
+    "ls_tsdf_sample_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _D, _D, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "ls_tsdf_sample_batch_workspace_bytes": (_SZ, [_I, _I, _I, _I, _LL]),
+    "ls_tsdf_sample_batch_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "ls_tsdf_icp_workspace_bytes": (_SZ, [_I, _I, _I, _LL]),
+    "ls_tsdf_icp_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _D, _D, _P, _LL, _P, _I, _D, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "ls_tsdf_icp_batch_workspace_bytes": (_SZ, [_I, _I, _I, _I, _LL]),
+    "ls_tsdf_icp_batch_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _LL, _P, _P, _I, _D, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                   _SZ, _P]),
     "ls_profile_begin": (_I, [_P]),
     "ls_profile_end": (_I, [_P, ctypes.POINTER(ProfileEntry), _I, ctypes.POINTER(ctypes.c_int)]),
 }

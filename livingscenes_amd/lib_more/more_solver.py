@@ -530,6 +530,37 @@ class More_Solver:
         info.update(self._overlap_figures(mem_pcs, searches))
         return T_new, info
 
+    def _refine_on_fusion_batch(self, fusion, new_pcs, T, min_obs=1, **kw):
+        """Scene memory, the registration that needs no search (an extension beyond the released reference, like _refine_on_memory_batch,
+        whose conventions these are): refine P registrations on the FUSED STATE of their instances in ONE call (ops.tsdf_icp_batch,
+        csrc/tsdficp.hip; Bylow et al. 2013) -- every posed point of new_pcs[p] [b_p,3] reads the eight samples around it and their
+        gradient, and the pose minimises the sum of the squared distances.  fusion = the dict of _fuse_batch (sum, n: int32
+        [P,res,res,res]; origin, voxel, trunc), the grids in the memory's frame; min_obs as everywhere on that state.  T [P,4,4] or
+        [P,3,4] maps memory -> rescan; the operator gets inverse(T) as its initial pose.  kw: max_iter, rel_thr, min_matched of
+        ops.tsdf_icp_batch (inherited, not tuned).  The band is the fusion's trunc: the error of the registration this starts from must
+        lie within it, which no trained checkpoint exists here to measure.
+        -> (T' [P,4,4] = inverse(g_out); a problem that made no update -- iters 0 -- keeps the caller's T bit for bit,
+            dict: g [P,3,4] (g_out, rescan -> memory: what _accumulate_batch / _overlap_batch / _fuse_batch take as g=), stop, iters (host
+            int32 [P]), sampled (list of P: sampled / finite observation points of the final sample, 0.0 with no finite point), rms_phi
+            (list of P: sqrt(sum phi^2 / sampled), nan with none) and counts (host int64 [P,3]: finite, inside the grid, sampled)).
+        There is no fallback: a starved or degenerate problem keeps the caller's T, as any problem with iters 0 does, and stop says why."""
+        P = fusion["sum"].shape[0]
+        if len(new_pcs) != P:
+            raise ValueError(f"{P} fusion states for {len(new_pcs)} observations")
+        if T is None or T.dim() != 3 or T.shape[0] != P or T.shape[1] not in (3, 4) or T.shape[2] != 4:
+            raise ValueError(f"T must be [P,4,4] or [P,3,4] with P = {P}, got {None if T is None else tuple(T.shape)}")
+        res = ops.tsdf_icp_batch((fusion["sum"], fusion["n"]), [p.detach() for p in new_pcs], g=self._memory_pose(T, None, P), origin=fusion["origin"],
+                                 voxel=fusion["voxel"], trunc=fusion["trunc"], min_obs=min_obs, packed=True, **kw)
+        last_row = T.new_tensor([0.0, 0.0, 0.0, 1.0]).expand(P, 1, 4)
+        T4 = T.detach() if T.shape[1] == 4 else torch.cat([T.detach(), last_row], 1)
+        moved = torch.tensor((res["iters"] > 0).tolist(), device=T.device)
+        T_new = torch.where(moved.view(P, 1, 1), torch.cat([inverse(res["g"]).to(T4), last_row], 1), T4)
+        info = {"g": res["g"], "stop": res["stop"], "iters": res["iters"], "counts": res["counts"], "sampled": [], "rms_phi": []}
+        for (finite, _, sampled), q in zip(res["counts"].tolist(), res["sum_phi2"].tolist()):
+            info["sampled"].append(sampled / finite if finite else 0.0)
+            info["rms_phi"].append(math.sqrt(q / sampled) if sampled else float("nan"))
+        return T_new, info
+
     def _mesh_from_latent(self, latent_code):
         """more_solver.py:37-58: mesh of the canonical shape (t = 0, s = 1), then scaled and moved to the instance pose."""
         if self.mesh_extractor is None:
@@ -785,6 +816,14 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
     More_Solver._refine_on_memory_batch(metric="plane", normal_radius=normal_radius), the normals of the memory recomputed at every step.
     There is NO FALLBACK to the point metric: a pair whose refinement starves or is degenerate keeps the registration it came with, as
     any pair with refine_iters 0 does, and refine_stop reports it.  "point" is the path above, untouched.
+    refine_metric "tsdf" registers on the FUSED STATE instead of the point memory (it needs fuse_res, and refuses a refine_radius: its
+    band is the fusion's trunc; both are ValueErrors raised before any device work): ONE More_Solver._refine_on_fusion_batch call over
+    the matched pairs follows the registration batch, on the state as it stands BEFORE this rescan is fused, with min_obs =
+    fuse_min_obs.  Every posed point reads eight samples and their gradient: no search, no grid build, no normals.  The refined pose
+    goes to the gate, the carve, the merge and the fuse exactly as the cloud refinement's does, the step gains the same refine_stop,
+    refine_iters and registration_init, and the gate always makes its own _overlap_batch(g=g_out) search.  A slot whose state holds no
+    observation yet (no ref['views'] and no earlier rescan) starves and keeps its registration.  NO SETTING IS RECOMMENDED: the error
+    of the registration it starts from must lie within trunc, and nothing here can measure a real one.
 
     The consolidation (opt-in: with consolidate False nothing below happens and every returned object is what it is without the
     arguments).  With True, ONE More_Solver._consolidate_batch call over all slots runs AFTER THE LAST RESCAN (radius consolidate_radius,
@@ -827,12 +866,17 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
     the cubes whose eight corners were observed at least fuse_min_obs times, None for a slot nothing kept.  With fuse_mesh False the
     memory has no such key.  fuse_trunc_voxels = 4 is AN UNMEASURED DEFAULT; NO fuse_res IS RECOMMENDED, and no fuse_min_obs: no real scans are
     available here to measure one on, and what the fused volume or its mesh does for anything downstream is unmeasured."""
-    if refine_metric not in ("point", "plane"):
-        raise ValueError(f"solve_sequence: refine_metric must be 'point' or 'plane', got {refine_metric!r}")
+    if refine_metric not in ("point", "plane", "tsdf"):
+        raise ValueError(f"solve_sequence: refine_metric must be 'point', 'plane' or 'tsdf', got {refine_metric!r}")
     if refine_metric == "plane" and refine_radius is None:
         raise ValueError("solve_sequence: refine_metric 'plane' needs refine_radius: without it there is no refinement to choose a metric for")
     if fuse_mesh and fuse_res is None:
         raise ValueError("solve_sequence: fuse_mesh needs fuse_res: without a fused state there is nothing to mesh")
+    if refine_metric == "tsdf" and fuse_res is None:
+        raise ValueError("solve_sequence: refine_metric 'tsdf' needs fuse_res: without a fused state there is nothing to register against")
+    if refine_metric == "tsdf" and refine_radius is not None:
+        raise ValueError("solve_sequence: refine_metric 'tsdf' takes no refine_radius: its band is the fusion's trunc")
+    refining = refine_radius is not None or refine_metric == "tsdf"
     gate = overlap_radius is not None or min_overlap is not None
     model = solver.model
     n_in = solver.cfg["shape_priors"]["n_input_point"]
@@ -864,16 +908,28 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
             out.update({"n_carved": [0] * n, "carve_kept_as_is": []})
         if fusion is not None:
             out["n_fused_views"] = [0] * n
-        if refine_radius is not None:
+        if refining:
             out.update({"refine_stop": [None] * n, "refine_iters": [None] * n, "registration_init": [None] * n})
         if pairs:
             src, tgt = [mem[i] for i, _ in pairs], [res_full[j] for _, j in pairs]
             R, t = solver._solve_pairwise_registration_optim_batch(src, tgt) if optim else solver._solve_pairwise_registration_batch(src, tgt)
             T = Rt_to_SE3(R, t)
             refined = None
-            if refine_radius is not None:
+            if refining:
                 T_init = T
-                if refine_metric == "plane":
+                if refine_metric == "tsdf":
+                    # all n slots go into the one call, so that a slot is its own problem of the state, as for the fuse: a slot without a
+                    # pair has no observation, starves at once and is not read.  The state is the one BEFORE this rescan is fused.
+                    slot_pcs, slot_T = [tgt[0][:0]] * n, torch.eye(4, dtype=T.dtype, device=T.device).repeat(n, 1, 1)
+                    slots = [i for i, _ in pairs]
+                    rows = torch.tensor(slots, device=T.device)
+                    for k, i in enumerate(slots):
+                        slot_pcs[i] = tgt[k]
+                    slot_T[rows] = T_init
+                    T, refined = solver._refine_on_fusion_batch(fusion, slot_pcs, slot_T, min_obs=fuse_min_obs)
+                    T = T[rows]
+                    refined = {"g": refined["g"][rows], "stop": refined["stop"][slots], "iters": refined["iters"][slots]}
+                elif refine_metric == "plane":
                     T, refined = solver._refine_on_memory_batch(src, tgt, T_init, refine_radius, metric="plane", normal_radius=normal_radius)
                 else:
                     T, refined = solver._refine_on_memory_batch(src, tgt, T_init, refine_radius)
@@ -887,7 +943,7 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
                     radius = solver.cfg.get("accumulate", {}).get("overlap_radius", 2 * voxel)
                 if refined is None:
                     ov = solver._overlap_batch(src, tgt, T, radius=radius)
-                elif radius is not None and float(radius) == float(refine_radius):
+                elif refine_radius is not None and radius is not None and float(radius) == float(refine_radius):
                     ov = refined                                      # the refinement's final search is this search
                 else:
                     ov = solver._overlap_batch(src, tgt, None, radius=radius, g=refined["g"])

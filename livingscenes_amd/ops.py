@@ -1634,3 +1634,147 @@ def cloud_icp_plane(A, N, B, g=None, *, radius, max_iter=100, rel_thr=1e-6, min_
     head = (ptr(A), ptr(N), A.shape[0], ptr(B), B.shape[0], ptr(g), float(radius))
     return _icp(op, "ls_cloud_icp_plane_f32", head, (A.shape[0], B.shape[0]), 1, dev, _offsets([B.shape[0]]), max_iter, rel_thr, min_matched, trace,
                 False, plane=True)[0]
+
+
+# ------------------------------------------------------------------------------------------------ the fused state read and registered against (csrc/tsdficp.hip)
+SAMPLE_STATE = ("out", "unseen", "sampled")                 # the values of a query's state, by value
+SAMPLE_COUNT = ("finite", "inside", "sampled")              # the columns of tsdf_sample's counts, by value
+_SAMPLE_META = [("counts", np.int64, 3), ("sum_phi2", np.float64, 1)]
+
+
+def _tsdf_queries(op, single, state, B, g, origin, voxel, trunc, min_obs):
+    """the argument checks of the four wrappers -> (S, N, P, dims, dev, B packed, host b_off, g [P,3,4] or [3,4] or None, o, h, tr, min_obs)"""
+    S, N, P, dims = _fuse_state(op, state, not single)
+    dev = S.device
+    min_obs = int(min_obs)
+    if min_obs < 1:
+        raise ValueError(f"{op}: min_obs must be >= 1, got {min_obs}")
+    o, h, tr = _fuse_grid(op, P, origin, voxel, trunc)
+    if single:
+        B = _cloud(B, "B", op)
+        bo = _offsets([B.shape[0]])
+        g = _pose(g, op, dev)
+    else:
+        Bs = [_cloud(x, "B", op) for x in B]
+        if len(Bs) != P:
+            raise ValueError(f"{op}: {P} problems in state for {len(Bs)} arrays of queries")
+        B, bo = _pack(Bs)
+        g = _poses(g, op, P, dev)
+    if B.device != dev:
+        raise ValueError(f"{op}: the state is on {dev}, B on {B.device}")
+    return S, N, P, dims, dev, B, bo, g, o, h, tr, min_obs
+
+
+def _tsdf_call(op, single, S, N, P, dims, dev, B, bo, g, o, h, tr, min_obs, tail, outs):
+    """the entry of `op` with the scratch its size query asks for; tail: the ICP's scalars, outs: the output pointers in the entry's order"""
+    name = "ls_" + op
+    b = B.shape[0]
+    ws_bytes = getattr(load(), name + "_workspace_bytes")(*(() if single else (P,)), *dims, b)
+    if ws_bytes == 0:
+        raise ValueError(f"{op}: P = {P} problems of dims {dims} with {b} queries unsupported (include/livingscenes_hip.h: P nx ny nz < 2^31)")
+    ws = _scratch(ws_bytes, dev)
+    if single:
+        head = (ptr(S), ptr(N), *dims, min_obs, _hptr(o), float(h[0]), float(tr[0]), ptr(B), b, ptr(g))
+    else:
+        head = (P, ptr(S), ptr(N), *dims, min_obs, _hptr(o), _hptr(h), _hptr(tr), ptr(B), b, _hptr(bo), ptr(g))
+    call(dev, name + "_f32", *head, *tail, *outs, ptr(ws), ws.numel(), stream_ptr(dev))
+
+
+def _tsdf_sample(op, single, state, B, g, origin, voxel, trunc, min_obs, packed):
+    S, N, P, dims, dev, B, bo, g, o, h, tr, min_obs = _tsdf_queries(op, single, state, B, g, origin, voxel, trunc, min_obs)
+    b = B.shape[0]
+    phi = torch.empty(b, dtype=torch.float64, device=dev)
+    grad = torch.empty(b, 3, dtype=torch.float64, device=dev)
+    st = torch.empty(b, dtype=torch.uint8, device=dev)
+    m = _Meta(P, dev, _SAMPLE_META + [("status", np.int32, 1)])
+    m.buf.zero_()                                                        # the entries have no status: LS_OK
+    _tsdf_call(op, single, S, N, P, dims, dev, B, bo, g, o, h, tr, min_obs, (), (ptr(phi), ptr(grad), ptr(st), m.ptr("counts"), m.ptr("sum_phi2")))
+    f = m.read(op)
+    if single:
+        return phi, grad, st, f["counts"][0], float(f["sum_phi2"][0])
+    if packed:
+        return phi, grad, st, f["counts"], f["sum_phi2"], bo
+    sizes = np.diff(bo).tolist()
+    return [(x, y, z, f["counts"][p], float(f["sum_phi2"][p]))
+            for p, (x, y, z) in enumerate(zip(torch.split(phi, sizes), torch.split(grad, sizes), torch.split(st, sizes)))]
+
+
+def tsdf_sample_batch(state, Bs, g=None, *, origin, voxel, trunc, min_obs=1, packed=False):
+    """ls_tsdf_sample_batch_f32 (an extension beyond the released reference, like depth_fuse): the fused states of P instances READ at
+    posed points.  state = (sum, n) int32 HIP tensors [P,nx,ny,nz] (tsdf_state, depth_fuse_batch); Bs = list of P query arrays [b_p,3]
+    (fp32 HIP tensors, empty ones allowed); g [P,3,4] or [P,4,4] taking B_p into the grid's frame (None: B bit for bit); origin [P,3]
+    or [3], voxel, trunc (one value or P): host float64, the grids the views were fused on.  Per query the definition of
+    include/livingscenes_hip.h: the posed row in fp32, its cell, and -- only where all eight corners have n >= min_obs -- the trilinear
+    value phi of the truncated distance in METRES and the exact gradient of that interpolant (not normalised), float64.  A query outside
+    the grid ("out") or with an unobserved corner ("unseen") gets phi = +trunc, grad = 0: no value ever reads an unobserved sample.
+    -> list of P (phi [b_p] float64, grad [b_p,3] float64, state [b_p] uint8 of SAMPLE_STATE, counts host int64 [3] of SAMPLE_COUNT,
+    sum_phi2 float: the float64 sum of phi^2 over the sampled queries); packed=True: (phi, grad, state, counts [P,3], sum_phi2 [P], b_off).
+    One call, one host read, whatever P.  NO min_obs IS RECOMMENDED: 1 is the least, unmeasured on real scans."""
+    return _tsdf_sample("tsdf_sample_batch", False, state, Bs, g, origin, voxel, trunc, min_obs, packed)
+
+
+def tsdf_sample(state, B, g=None, *, origin, voxel, trunc, min_obs=1):
+    """ls_tsdf_sample_f32: state = (sum, n) int32 HIP tensors [nx,ny,nz] (a slice of tsdf_state), B [b,3] fp32, g [3,4] or [4,4] or None,
+    origin [3], voxel and trunc host float64 -> (phi [b] float64, grad [b,3] float64, state [b] uint8, counts host int64 [3], sum_phi2
+    float) as tsdf_sample_batch describes them, bit-identical to the same problem inside any batch.  NO min_obs IS RECOMMENDED."""
+    return _tsdf_sample("tsdf_sample", True, state, B, g, origin, voxel, trunc, min_obs, False)
+
+
+_TSDF_ICP_SCALARS = {"stop": int, "iters": int, "sum_phi2": float}
+
+
+def _tsdf_icp(op, single, state, B, g, origin, voxel, trunc, min_obs, max_iter, rel_thr, min_matched, trace, packed):
+    S, N, P, dims, dev, B, bo, g, o, h, tr, min_obs = _tsdf_queries(op, single, state, B, g, origin, voxel, trunc, min_obs)
+    b, max_iter = B.shape[0], int(max_iter)
+    phi = torch.empty(b, dtype=torch.float64, device=dev)
+    grad = torch.empty(b, 3, dtype=torch.float64, device=dev)
+    st = torch.empty(b, dtype=torch.uint8, device=dev)
+    g_out = torch.empty(P, 3, 4, dtype=torch.float32, device=dev)
+    traces = {}
+    if trace:
+        traces = {"g_trace": torch.zeros(P, max(max_iter, 0) + 1, 12, dtype=torch.float32, device=dev),
+                  "stat_trace": torch.zeros(P, max(max_iter, 0) + 1, 3, dtype=torch.float64, device=dev)}
+    m = _Meta(P, dev, _SAMPLE_META + [("status", np.int32, 1), ("stop", np.int32, 1), ("iters", np.int32, 1)])
+    m.buf.zero_()
+    _tsdf_call(op, single, S, N, P, dims, dev, B, bo, g, o, h, tr, min_obs, (max_iter, float(rel_thr), int(min_matched)),
+               (ptr(g_out), m.ptr("stop"), m.ptr("iters"), ptr(phi), ptr(grad), ptr(st), m.ptr("counts"), m.ptr("sum_phi2"),
+                ptr(traces.get("g_trace")), ptr(traces.get("stat_trace"))))
+    f = m.read(op)
+    out = {"g": g_out, "stop": f["stop"], "iters": f["iters"], "phi": phi, "grad": grad, "state": st, "counts": f["counts"], "sum_phi2": f["sum_phi2"]}
+    if packed:
+        out["b_off"] = bo
+    out.update(traces)
+    if packed:
+        return out
+    sizes = np.diff(bo).tolist()
+    for k in ("phi", "grad", "state"):
+        out[k] = torch.split(out[k], sizes)
+    res = [{k: _TSDF_ICP_SCALARS[k](v[p]) if k in _TSDF_ICP_SCALARS else v[p] for k, v in out.items()} for p in range(P)]
+    return res[0] if single else res
+
+
+def tsdf_icp_batch(state, Bs, g=None, *, origin, voxel, trunc, min_obs=1, max_iter=100, rel_thr=1e-6, min_matched=6, trace=False, packed=False):
+    """ls_tsdf_icp_batch_f32 (an extension beyond the released reference, like cloud_icp_plane): P observations Bs[p] [b_p,3] registered
+    onto the fused states of their instances without any search (Bylow et al., RSS 2013).  state, origin, voxel, trunc, min_obs:
+    tsdf_sample_batch's; g [P,3,4] or [P,4,4] is the initial pose taking B_p into the grid's frame (None: the identity).  Per iteration:
+    tsdf_sample under the current pose; E = (sum phi^2 + (finite - sampled) trunc^2) / finite, the truncated quadratic of cloud_icp
+    with trunc in the place of the radius; the stop tests of cloud_icp_plane on the SAMPLED count (min_matched = 6: six unknowns); else
+    the 6 x 6 normal equations of sum (phi + omega . (y x grad) + v . grad)^2 in float64, Cholesky (a failed pivot: degenerate -- the
+    state of one plane, all gradients parallel), exp of the twist, the rotation re-orthonormalised: the solver text of cloud_icp_plane.
+    The gradient is NOT normalised, nothing is weighted, and there is no line search and no damping: a step that raises E ends the loop
+    as converged with the pose it produced.  A query in saturated free space has phi = trunc and grad = 0: it costs what an unsampled
+    one costs and pulls on nothing.  The start error must lie within trunc.  max_iter = 100 and rel_thr = 1e-6 are ops.icp's defaults,
+    pytorch3d's: INHERITED, NOT TUNED.
+    -> list of P dicts: g [3,4] fp32 (device), stop (int, LS_ICP_*; ICP_STOP names them), iters (int), and the final sample exactly as
+    tsdf_sample(state_p, B_p, g, ...) returns it: phi, grad, state, counts (host int64 [3]), sum_phi2 (float); trace=True adds g_trace
+    [max_iter+1,12] and stat_trace [max_iter+1,3] float64 = (finite, sampled, sum phi^2) per iteration (device; rows <= iters are
+    written).  packed=True: one dict of the packed tensors plus b_off.  One call, one host read, whatever P and however many iterations.
+    NO min_obs IS RECOMMENDED."""
+    return _tsdf_icp("tsdf_icp_batch", False, state, Bs, g, origin, voxel, trunc, min_obs, max_iter, rel_thr, min_matched, trace, packed)
+
+
+def tsdf_icp(state, B, g=None, *, origin, voxel, trunc, min_obs=1, max_iter=100, rel_thr=1e-6, min_matched=6, trace=False):
+    """ls_tsdf_icp_f32: the observation B [b,3] registered onto the fused state (sum, n) [nx,ny,nz] -> the dict tsdf_icp_batch describes.
+    max_iter = 100 and rel_thr = 1e-6 are ops.icp's defaults, pytorch3d's: inherited, not tuned.  Bit-identical to the same problem
+    inside any tsdf_icp_batch.  NO min_obs IS RECOMMENDED."""
+    return _tsdf_icp("tsdf_icp", True, state, B, g, origin, voxel, trunc, min_obs, max_iter, rel_thr, min_matched, trace, False)
