@@ -368,6 +368,17 @@ int ls_vn_edgeconv_attn_f32(ls_model_t* m, int layer, const float* src_f, const 
 size_t ls_vn_lna_workspace_bytes(const ls_model_t* m, int layer, int B, int N);
 int ls_vn_lna_f32(ls_model_t* m, int layer, const float* f, int B, int N, float* out, void* workspace, size_t workspace_bytes,
                   void* stream);
+/* ls_vn_lna_f32 with the side products the encoder passes between its layers (same workspace):
+ *   a_rowmax [B*N*3][a_parts] or NULL: max over the parts bounds max|f[row, :]|, as the kernel that wrote f would hand it over
+ *     (NULL: as ls_vn_lna_f32);  out_rowmax [B*N*3][C/32] or NULL: receives max|out[row, 32 q .. 32 q + 31]| where the one-launch
+ *     form of the conv runs; *rowmax_written (nullable) says whether it did. */
+int ls_vn_lna_ex_f32(ls_model_t* m, int layer, const float* f, int B, int N, const float* a_rowmax, int a_parts, float* out_rowmax,
+                     int* rowmax_written, float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* The per-instance half of that conv alone: G[b][x][col0 + j] = < mean f[b][.][x][:], W[col0 + j][:] >, j < ncols.
+ *   f [B,N,3,C], W [>= col0 + ncols rows][C], G [B*3][ldg]; C % 4 == 0.  npoints == 0: the mean of the N rows;  npoints > 0: f holds N
+ *   rows of partial column sums over npoints points per instance, the mean is their sum / npoints. */
+int ls_glob_mean_gemv_f32(const float* f, int B, int N, int C, const float* W, int col0, int ncols, float* G, int ldg, int npoints,
+                          void* stream);
 
 /* The encoder's heads (vec_dgcnn_atten.py:231-250): conv_c VecLNA (shared direction) -> mean over the NP points -> z_so3 =
  * channel_equi_vec_normalize, scale = mean_c |x_c| * scale_factor, z_inv = <cevn(fc_inv x), z_so3>, center = VecResBlock

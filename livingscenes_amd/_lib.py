@@ -147,6 +147,8 @@ SIGNATURES = {
     "ls_vn_edgeconv_attn_f32": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _SZ, _P]),
     "ls_vn_lna_workspace_bytes": (_SZ, [_P, _I, _I, _I]),
     "ls_vn_lna_f32": (_I, [_P, _I, _P, _I, _I, _P, _P, _SZ, _P]),
+    "ls_vn_lna_ex_f32": (_I, [_P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P, _SZ, _P]),
+    "ls_glob_mean_gemv_f32": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P]),
     "ls_encoder_tail_workspace_bytes": (_SZ, [_P, _I, _I]),
     "ls_encoder_tail_f32": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
     "ls_sdf_workspace_bytes": (_SZ, [_P, _I, _I]),
@@ -249,6 +251,9 @@ SIGNATURES = {
     "ls_profile_end": (_I, [_P, ctypes.POINTER(ProfileEntry), _I, ctypes.POINTER(ctypes.c_int)]),
 }
 
+# symbols added without an ABI change: a library built from an earlier commit (LS_LIB_PATH A/B builds) may lack them and still loads
+LATE_SYMBOLS = ("ls_vn_lna_ex_f32", "ls_glob_mean_gemv_f32")
+
 _lib = None
 
 
@@ -261,6 +266,8 @@ def load():
                           "There is no CPU fallback for the HIP operators.")
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
+            if name in LATE_SYMBOLS and not hasattr(lib, name):
+                continue
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -254,14 +254,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
 #pragma unroll
                 for (int h = 0; h < NST; ++h) { ma[h] = amax4(ma[h], ra[h]); mw[h] = amax4(mw[h], rb[h]); }
             }
+        if (!pre_a) {   // (a row past M: row 0's parts are read in its place and dropped)
+            size_t ar[NST];
+#pragma unroll
+            for (int h = 0; h < NST; ++h) ar[h] = (size_t)(arow[h] >= 0 ? arow[h] : 0);
+            rowmax_fold(aux.a_rowmax, ar, aux.a_parts, ma);
+#pragma unroll
+            for (int h = 0; h < NST; ++h) ma[h] = arow[h] >= 0 ? ma[h] : 0.f;
+        }
 #pragma unroll
         for (int h = 0; h < NST; ++h) {
             const int r = sr0 + h * RSTEP;
             if (pre_a) ma[h] = max8(ma[h]);
-            else {
-                ma[h] = 0.f;
-                if (arow[h] >= 0) for (int q = 0; q < aux.a_parts; ++q) ma[h] = fmaxf(ma[h], aux.a_rowmax[(size_t)arow[h] * aux.a_parts + q]);
-            }
             if (pre_w) mw[h] = max8(mw[h]);
             else mw[h] = n0 + r < N ? aux.w_rowmax[n0 + r] : 0.f;
             float ia, iw;
@@ -427,17 +431,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
     float4 ra[4], rb[4];
     const float* arow[4];
     const float* brow[4];
+    size_t ar[4];   // the (source) row indices behind arow / brow: the row maxima are indexed by them
+    int br[4];
 #pragma unroll
     for (int h = 0; h < 4; ++h) {
-        const int gm = min(m0 + sr0 + h * 32, M - 1), gn = min(n0 + sr0 + h * 32, N - 1);
-        size_t r = (size_t)gm;
+        const int gm = min(m0 + sr0 + h * 32, M - 1);
+        br[h] = min(n0 + sr0 + h * 32, N - 1);
+        ar[h] = (size_t)gm;
         if (a_rows) {
             const int pt = gm / 3, x = gm - pt * 3;
             const int bb = pt / gNd;
-            r = ((size_t)bb * gNs + a_rows[pt]) * 3 + x;
+            ar[h] = ((size_t)bb * gNs + a_rows[pt]) * 3 + x;
         }
-        arow[h] = A + r * lda;
-        brow[h] = W + (size_t)gn * ldw;
+        arow[h] = A + ar[h] * lda;
+        brow[h] = W + (size_t)br[h] * ldw;
     }
     auto kof = [&](int k0) { return KAL ? min(k0, kend - 32) + sk : min(k0 + sk, kend - 4); };
     auto gload_a = [&](int k0) {
@@ -503,13 +510,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
     };
     // operand range: one exact power of two per staged row (GemmAux), from the caller's row maxima or a pre-pass over the rows
     float ma[4] = {0.f, 0.f, 0.f, 0.f}, mw[4] = {0.f, 0.f, 0.f, 0.f};
-    if (aux.a_rowmax) {
+    if (aux.w_rowmax) {   // (requested first: in flight with the parts of the A rows)
 #pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            const float* rp = aux.a_rowmax + (size_t)((arow[h] - A) / lda) * aux.a_parts;
-            for (int q = 0; q < aux.a_parts; ++q) ma[h] = fmaxf(ma[h], rp[q]);
-        }
-    } else {
+        for (int h = 0; h < 4; ++h) mw[h] = aux.w_rowmax[br[h]];
+    }
+    if (aux.a_rowmax) rowmax_fold(aux.a_rowmax, ar, aux.a_parts, ma);
+    else {
         for (int k0 = kbeg; k0 < kend; k0 += 32) {
             gload_a(k0);
 #pragma unroll
@@ -518,10 +524,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
 #pragma unroll
         for (int h = 0; h < 4; ++h) ma[h] = max8(ma[h]);
     }
-    if (aux.w_rowmax) {
-#pragma unroll
-        for (int h = 0; h < 4; ++h) mw[h] = aux.w_rowmax[(brow[h] - W) / ldw];
-    } else if constexpr (!WPL) {
+    if constexpr (!WPL) if (!aux.w_rowmax) {
         for (int k0 = kbeg; k0 < kend; k0 += 32) {
             gload_b(k0);
 #pragma unroll
@@ -732,11 +735,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void g
     };
     float ma[4] = {0.f, 0.f, 0.f, 0.f}, mw[4] = {0.f, 0.f, 0.f, 0.f};
     if (aux.a_rowmax) {
+        size_t ar[4];
 #pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            const float* rp = aux.a_rowmax + (size_t)min(m0 + sr0 + h * 64, M - 1) * aux.a_parts;
-            for (int q = 0; q < aux.a_parts; ++q) ma[h] = fmaxf(ma[h], rp[q]);
-        }
+        for (int h = 0; h < 4; ++h) ar[h] = (size_t)min(m0 + sr0 + h * 64, M - 1);
+        rowmax_fold(aux.a_rowmax, ar, aux.a_parts, ma);
     } else {
         for (int k0 = 0; k0 < K; k0 += 32) {
             gload_a(k0);
@@ -900,12 +902,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
     float4 ra[4], rb[4];
     const float* arow[4];
     const float* brow[4];
+    size_t ar[4];   // the row indices behind arow / brow: the row maxima are indexed by them
+    int br[4];
 #pragma unroll
     for (int h = 0; h < 4; ++h) {
         // staged row sr0 + 32 h = row sr0 of M-tile h; staged W row = tile column sr0 + 32 h = (wn = h >> 1, lin | dir = h & 1, channel sr0)
-        const int gm = min(m0 + h * TR + min(sr0, TR - 1), M - 1);
-        arow[h] = A + (size_t)gm * lda;
-        brow[h] = W + (size_t)((h & 1) * C + c0 + 32 * (h >> 1) + sr0) * ldw;
+        ar[h] = (size_t)min(m0 + h * TR + min(sr0, TR - 1), M - 1);
+        br[h] = (h & 1) * C + c0 + 32 * (h >> 1) + sr0;
+        arow[h] = A + ar[h] * lda;
+        brow[h] = W + (size_t)br[h] * ldw;
     }
     auto kof = [&](int k0) { return KAL ? min(k0, kend - 32) + sk : min(k0 + sk, kend - 4); };
     auto gload_a = [&](int k0) {
@@ -940,13 +945,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
     // operand range: one exact power of two per staged row (GemmAux), from the caller's row maxima or a pre-pass over the rows
     float sa[4] = {1.f, 1.f, 1.f, 1.f}, sw[4] = {1.f, 1.f, 1.f, 1.f};
     float ma[4] = {0.f, 0.f, 0.f, 0.f}, mw[4] = {0.f, 0.f, 0.f, 0.f};
-    if (aux.a_rowmax) {
+    if (aux.w_rowmax) {   // (requested first: in flight with the parts of the A rows)
 #pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            const float* rp = aux.a_rowmax + (size_t)((arow[h] - A) / lda) * aux.a_parts;
-            for (int q = 0; q < aux.a_parts; ++q) ma[h] = fmaxf(ma[h], rp[q]);
-        }
-    } else {
+        for (int h = 0; h < 4; ++h) mw[h] = aux.w_rowmax[br[h]];
+    }
+    if (aux.a_rowmax) rowmax_fold(aux.a_rowmax, ar, aux.a_parts, ma);
+    else {
         for (int k0 = kbeg; k0 < kend; k0 += 32) {
             gload_a(k0);
 #pragma unroll
@@ -955,10 +959,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
 #pragma unroll
         for (int h = 0; h < 4; ++h) ma[h] = max8(ma[h]);
     }
-    if (aux.w_rowmax) {
-#pragma unroll
-        for (int h = 0; h < 4; ++h) mw[h] = aux.w_rowmax[(brow[h] - W) / ldw];
-    } else {
+    if (!aux.w_rowmax) {
         for (int k0 = kbeg; k0 < kend; k0 += 32) {
             gload_b(k0);
 #pragma unroll
@@ -1027,6 +1028,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
     // epilogue: each wave stages a 32-row M-tile x its 64 columns (lin 32 | dir 32) in LDS, then activates ten points x 32 channels
     float* stg = reinterpret_cast<float*>(smem) + wave * STG;
     const int col_l = lane & 31, rowh = (lane >> 5) * 4;
+    // the G terms of an M-tile: six values for each of a lane's five items (item it = point 2 it + (lane >> 5) of the tile, channel lane & 31), requested in ONE
+    // batch with the instance clamped to the last one, not predicated (the lesson at csv in gemm_vn_direct_kernel: inside the unrolled item loop `if (grow < M)`
+    // made every item a branch with its own wait -- ten L2 round trips in series per wave).  Tile 0's are requested here and arrive under its LDS staging, tile
+    // 1's before tile 0 is activated.  The instance of a point: ONE (scalar) division per M-tile -- a tile starts at a whole point (TR = 30 rows) -- then the
+    // remainder walks two points per item, so that a ten-point tile may span any number of instances (npts < 10).
+    const int blast = ((M - 1) / 3) / npts;   // the last instance
+    float g[2][5][6];
+#define LS_VN_LOAD_G(I)                                                                                                                   \
+    {                                                                                                                                     \
+        const int p0 = __builtin_amdgcn_readfirstlane(m0 / 3 + (wm * 2 + (I)) * (TR / 3));   /* first point of the M-tile */               \
+        int bi = p0 / npts, pr = p0 - bi * npts + (lane >> 5);                                                                            \
+        _Pragma("unroll") for (int it = 0; it < 5; ++it) {                                                                                \
+            if (it) { pr += 2; if (pr >= npts) { pr -= npts; ++bi; } }                                                                    \
+            if (pr >= npts) { pr -= npts; ++bi; }                                                                                         \
+            const float* gp = G + (size_t)min(bi, blast) * 3 * ldg + 2 * C + c0 + 32 * wn + col_l;                                        \
+            g[I][it][0] = gp[0]; g[I][it][1] = gp[ldg]; g[I][it][2] = gp[2 * ldg];                                                        \
+            g[I][it][3] = gp[C]; g[I][it][4] = gp[ldg + C]; g[I][it][5] = gp[2 * ldg + C];                                                \
+        }                                                                                                                                 \
+    }
+    LS_VN_LOAD_G(0)
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
 #pragma unroll
@@ -1046,22 +1067,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
         __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
         __builtin_amdgcn_wave_barrier();
         const int row0 = m0 + (wm * 2 + i) * TR;       // first row of this M-tile
+        if (i == 0) LS_VN_LOAD_G(1)
 #pragma unroll
         for (int it = 0; it < 5; ++it) {
             const int item = it * 64 + lane, pl = item >> 5, c = item & 31;   // point 0..9 of the tile, channel
             const int grow = row0 + 3 * pl;
-            float y0 = 0.f, y1 = 0.f, y2 = 0.f;
+            const float* sp = stg + 3 * pl * 68 + c;
+            float y0 = sp[0] + g[i][it][0], y1 = sp[68] + g[i][it][1], y2 = sp[136] + g[i][it][2];
+            const float k0 = sp[32] + g[i][it][3], k1 = sp[68 + 32] + g[i][it][4], k2 = sp[136 + 32] + g[i][it][5];
+            vn_act(y0, y1, y2, k0, k1, k2, oms);   // (rows past M: computed from the clamped operands, never stored)
             if (grow < M) {
-                const int ch = c0 + 32 * wn + c;
-                const float* g = G + (size_t)((grow / 3) / npts) * 3 * ldg + 2 * C + ch;
-                const float* sp = stg + 3 * pl * 68 + c;
-                y0 = sp[0] + g[0]; y1 = sp[68] + g[ldg]; y2 = sp[136] + g[2 * ldg];
-                const float k0 = sp[32] + g[C], k1 = sp[68 + 32] + g[ldg + C], k2 = sp[136 + 32] + g[2 * ldg + C];
-                vn_act(y0, y1, y2, k0, k1, k2, oms);
-                float* op = out + (size_t)grow * C + ch;
+                float* op = out + (size_t)grow * C + c0 + 32 * wn + c;
                 op[0] = y0; op[C] = y1; op[2 * C] = y2;
             }
-            if (aux.out_rowmax) {   // wave-uniform; [M][C / 32]: max|out[row, this wave's 32 channels]| (the half-wave of a point)
+            if (aux.out_rowmax) {   // wave-uniform; [M][C / 32]: max|out[row, this wave's 32 channels]| (the half-wave of a point; stored for rows below M only)
                 float m0_ = max16(fabsf(y0)), m1_ = max16(fabsf(y1)), m2_ = max16(fabsf(y2));
                 m0_ = fmaxf(m0_, __shfl_xor(m0_, 16, 64)); m1_ = fmaxf(m1_, __shfl_xor(m1_, 16, 64)); m2_ = fmaxf(m2_, __shfl_xor(m2_, 16, 64));
                 if (c == 0 && grow < M) {
@@ -1072,6 +1091,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
         }
         __builtin_amdgcn_wave_barrier();
     }
+#undef LS_VN_LOAD_G
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1456,12 +1476,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
     for (; tm < ntiles_m; tm += per_n) {
         const int m0 = tm * 4 * TR;
         __syncthreads();                               // previous tile's staging and scale reads are done (and the W planes are written)
+        float mrow[4] = {0.f, 0.f, 0.f, 0.f};
+        if (aux.a_rowmax) {
+            const size_t ar[4] = {(size_t)arow[0], (size_t)arow[1], (size_t)arow[2], (size_t)arow[3]};
+            rowmax_fold(aux.a_rowmax, ar, aux.a_parts, mrow);
+        }
 #pragma unroll
         for (int h = 0; h < 4; ++h) {
-            float sa, ia, ma = 0.f;
-            if (aux.a_rowmax) {
-                for (int q = 0; q < aux.a_parts; ++q) ma = fmaxf(ma, aux.a_rowmax[(size_t)arow[h] * aux.a_parts + q]);
-            } else {
+            float sa, ia, ma = mrow[h];
+            if (!aux.a_rowmax) {
 #pragma unroll
                 for (int sl = 0; sl < NSL; ++sl) ma = amax4(ma, ra[sl][h]);
                 ma = max8(ma);
@@ -1606,7 +1629,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
     {                                                                                                                                 \
         const size_t R0 = ((size_t)b * tiles_inst + (T)) * 24;                                                                        \
         if constexpr (ONEPART) MA = aux.a_rowmax[R0 + rofs];                                                                          \
-        else { MA = 0.f; for (int q = 0; q < aux.a_parts; ++q) MA = fmaxf(MA, aux.a_rowmax[(R0 + rofs) * aux.a_parts + q]); }         \
+        else { const size_t ar_[1] = {R0 + rofs}; float m_[1]; rowmax_fold(aux.a_rowmax, ar_, aux.a_parts, m_); MA = m_[0]; }        \
         const float4* ap = reinterpret_cast<const float4*>(A + R0 * C) + lane;                                                        \
         _Pragma("unroll") for (int i = 0; i < 6; ++i) RA[i] = ap[i * 64];                                                             \
     }
@@ -1773,9 +1796,13 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(const float* __
     if (i >= (long long)M * n4) return;
     const int m = (int)(i / n4), n = (int)(i % n4) * 4;
     float4 a = *reinterpret_cast<const float4*>(slabs + (size_t)m * N + n);
-    for (int s2 = 1; s2 < nsplit; ++s2) {
-        const float4 v = *reinterpret_cast<const float4*>(slabs + (size_t)s2 * slab_stride + (size_t)m * N + n);
-        a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+    for (int s0 = 1; s0 < nsplit; s0 += 4) {   // four slices requested per wait (slice index clamped, not predicated), added in ascending order
+        float4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const float4*>(slabs + (size_t)min(s0 + u, nsplit - 1) * slab_stride + (size_t)m * N + n);
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (s0 + u < nsplit) { a.x += v[u].x; a.y += v[u].y; a.z += v[u].z; a.w += v[u].w; }
     }
     if (bias) { a.x += bias[n]; a.y += bias[n + 1]; a.z += bias[n + 2]; a.w += bias[n + 3]; }
     if (relu) { a.x = fmaxf(a.x, 0.f); a.y = fmaxf(a.y, 0.f); a.z = fmaxf(a.z, 0.f); a.w = fmaxf(a.w, 0.f); }

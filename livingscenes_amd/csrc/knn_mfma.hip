@@ -140,11 +140,20 @@ __global__ __launch_bounds__(64 * WPT) void knn_prep_f16_tile_kernel(const float
         const int nc = min(Nc, KNN_CENTRE_ROWS);
         const float* cp = fc + (size_t)b * Nc * D + w * DW + lane;
         if (lane < DW) {
+            // all sixteen values requested first, at a row clamped into the nc rows (as a loop of four loads per trip this was four dependent round trips
+            // in front of the pass); then the same additions: whole groups of four rows into s0 .. s3, the last nc % 4 rows into s0
+            float v[KNN_CENTRE_ROWS];
+#pragma unroll
+            for (int rr = 0; rr < KNN_CENTRE_ROWS; ++rr) v[rr] = cp[(size_t)min(rr, max(nc - 1, 0)) * D];
             float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-            for (int rr = 0; rr + 3 < nc; rr += 4) {
-                s0 += cp[(size_t)rr * D]; s1 += cp[(size_t)(rr + 1) * D]; s2 += cp[(size_t)(rr + 2) * D]; s3 += cp[(size_t)(rr + 3) * D];
+#pragma unroll
+            for (int rr = 0; rr < KNN_CENTRE_ROWS; rr += 4) {
+                if (rr + 3 < nc) { s0 += v[rr]; s1 += v[rr + 1]; s2 += v[rr + 2]; s3 += v[rr + 3]; }
+                else {
+#pragma unroll
+                    for (int u = 0; u < 3; ++u) if (rr + u < nc) s0 += v[rr + u];
+                }
             }
-            for (int rr = nc & ~3; rr < nc; ++rr) s0 += cp[(size_t)rr * D];
             lmu[w][lane] = ((s0 + s1) + (s2 + s3)) / (float)nc;
         }
         __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the slot is wave-private

@@ -105,6 +105,51 @@ __device__ __forceinline__ float amax4(float m, const float4& v) {
 }
 __device__ __forceinline__ float amax_f4(const float4& v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
 
+// m[r] = max(0, max_q rm[row[r] * parts + q]), r < NR: the parts of NR rows' maxima (GemmAux::a_rowmax) folded, the loads of ALL rows requested before
+// the first is used (the loop `for q: m = fmaxf(m, rp[q])` per row compiles to one load and one full wait per part and row: 64 dependent round trips in
+// front of a tile at parts = 16).  A trip covers sixteen parts of every row as four 16-byte loads where the rows' parts are 16-byte aligned (parts % 4 == 0
+// and an aligned array), eight parts as dwords otherwise; the part index is CLAMPED to the row's last part, not predicated -- max does not mind a repeated
+// value, nothing past row * parts + parts - 1 is read, and the trip stays one basic block (gemm_vn_direct_kernel, csv: a conditional load is a branch with
+// its own wait).  The encoder's parts (1, 2, 4, 8, 16) are one trip; a larger run-time `parts` (ls_gemm_ex) loops with one wait per trip.  The maximum is
+// exact in any order, and fmaxf drops a NaN on either side, as the sequential loop did.
+template <int NR>
+__device__ __forceinline__ void rowmax_fold(const float* __restrict__ rm, const size_t (&row)[NR], int parts, float (&m)[NR]) {
+#pragma unroll
+    for (int r = 0; r < NR; ++r) m[r] = 0.f;
+    if (parts == 1) {
+        float v[NR];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) v[r] = rm[row[r]];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) m[r] = fmaxf(m[r], v[r]);
+    } else if ((parts & 3) == 0 && (reinterpret_cast<uintptr_t>(rm) & 15) == 0) {
+        const int p4 = parts >> 2;
+        for (int q = 0; q < p4; q += 4) {
+            float4 v[NR][4];
+#pragma unroll
+            for (int r = 0; r < NR; ++r)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[r][j] = reinterpret_cast<const float4*>(rm + row[r] * parts)[min(q + j, p4 - 1)];
+#pragma unroll
+            for (int r = 0; r < NR; ++r)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) m[r] = fmaxf(m[r], fmaxf(fmaxf(v[r][j].x, v[r][j].y), fmaxf(v[r][j].z, v[r][j].w)));
+        }
+    } else {
+        for (int q = 0; q < parts; q += 8) {
+            float v[NR][8];
+#pragma unroll
+            for (int r = 0; r < NR; ++r)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[r][j] = rm[row[r] * parts + min(q + j, parts - 1)];
+#pragma unroll
+            for (int r = 0; r < NR; ++r)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) m[r] = fmaxf(m[r], v[r][j]);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------- the two-piece f16 split
 // a = h + l with h = f16(a) (11 significant bits) and l = f16(a - h) (the residual is exact in fp32 and keeps 11 more bits while it is a
 // normal f16): |a - (h + l)| <= 2^-22 |a|.  What the kernels do with the pieces (three MFMAs per 16 k, their order): gemm.hip, "2 x f16 split".

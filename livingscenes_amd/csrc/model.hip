@@ -793,6 +793,23 @@ int ls_vn_lna_f32(ls_model_t* m, int layer, const float* f, int B, int N, float*
     }
     return global_conv(m, layer, f, B, N, q.g, q.G, q.TG, q.gws, out, (hipStream_t)stream, rm);
 }
+int ls_vn_lna_ex_f32(ls_model_t* m, int layer, const float* f, int B, int N, const float* a_rowmax, int a_parts, float* out_rowmax, int* rowmax_written,
+                     float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!a_rowmax && !out_rowmax) {
+        if (rowmax_written) *rowmax_written = 0;
+        return ls_vn_lna_f32(m, layer, f, B, N, out, workspace, workspace_bytes, stream);
+    }
+    LS_REQUIRE(m && f && out && workspace, "vn_lna_ex: null argument");
+    LS_REQUIRE(layer >= m->d.res_global_start_layer && layer < m->d.num_layers, "vn_lna_ex: layer %d has no residual global conv", layer);
+    LS_REQUIRE(B > 0 && N > 0, "vn_lna_ex: empty problem");
+    LS_REQUIRE(!a_rowmax || a_parts >= 1, "vn_lna_ex: a_rowmax needs a_parts >= 1");
+    const LnaPlan q = lna_plan(m->d, workspace, layer, B, N);
+    if (workspace_bytes < q.total) { set_error("vn_lna_ex: workspace %zu < required %zu", workspace_bytes, q.total); return LS_ERR_WORKSPACE; }
+    bool written = false;
+    const int rc = global_conv(m, layer, f, B, N, q.g, q.G, q.TG, q.gws, out, (hipStream_t)stream, a_rowmax, out_rowmax, &written, a_rowmax ? a_parts : 1);
+    if (rowmax_written) *rowmax_written = written;
+    return rc;
+}
 
 // the workspace of the exported tail: conv_c's output, then the split-K slabs of that GEMM and their 256-byte tail.  A null workspace: a
 // sizing pass.  The size has always ended with that tail, unpadded.

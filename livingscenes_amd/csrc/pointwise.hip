@@ -191,6 +191,27 @@ __global__ __launch_bounds__(256) void mean_points_kernel(const float* __restric
 }
 
 // ---------------------------------------------------------------------------------------------- mean over points + its VecLinear
+// (two helpers of glob_mean_gemv_kernel's weight walk first)
+// acc[x] += < lmean[x][k .. k + 3], w >, x < 3: one fma chain per output, x, y, z, w in turn
+__device__ __forceinline__ void gemv_fma3(float (&acc)[3], const float4& w, const float* lmean, int C, int k) {
+    const float4 m0 = *reinterpret_cast<const float4*>(&lmean[k]), m1 = *reinterpret_cast<const float4*>(&lmean[C + k]),
+                 m2 = *reinterpret_cast<const float4*>(&lmean[2 * C + k]);
+    acc[0] = __builtin_fmaf(m0.x, w.x, acc[0]); acc[0] = __builtin_fmaf(m0.y, w.y, acc[0]); acc[0] = __builtin_fmaf(m0.z, w.z, acc[0]); acc[0] = __builtin_fmaf(m0.w, w.w, acc[0]);
+    acc[1] = __builtin_fmaf(m1.x, w.x, acc[1]); acc[1] = __builtin_fmaf(m1.y, w.y, acc[1]); acc[1] = __builtin_fmaf(m1.z, w.z, acc[1]); acc[1] = __builtin_fmaf(m1.w, w.w, acc[1]);
+    acc[2] = __builtin_fmaf(m2.x, w.x, acc[2]); acc[2] = __builtin_fmaf(m2.y, w.y, acc[2]); acc[2] = __builtin_fmaf(m2.z, w.z, acc[2]); acc[2] = __builtin_fmaf(m2.w, w.w, acc[2]);
+}
+// T whole trips (k, k + 64, ...) of the two weight rows w0, w1 of a lane group: 2 T loads requested, then the chains in ascending k
+template <int T>
+__device__ __forceinline__ void gemv_trips(const float* __restrict__ w0, const float* __restrict__ w1, const float* lmean, int C, int k, float (&a0)[3], float (&a1)[3]) {
+    float4 v0[T], v1[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) { v0[t] = *reinterpret_cast<const float4*>(w0 + k + 64 * t); v1[t] = *reinterpret_cast<const float4*>(w1 + k + 64 * t); }
+    __builtin_amdgcn_sched_barrier(0);   // (without it the scheduler sinks most of the loads between the chains: three to five in flight instead of 2 T)
+#pragma unroll
+    for (int t = 0; t < T; ++t) gemv_fma3(a0, v0[t], lmean, C, k + 64 * t);
+#pragma unroll
+    for (int t = 0; t < T; ++t) gemv_fma3(a1, v1[t], lmean, C, k + 64 * t);
+}
 // The per-instance half of the residual global conv (vec_dgcnn_atten.py:222-225: VecLNA_G(cat(f, mean_n f))): the part of the
 // contraction that multiplies the MEAN feature is the same for every point of an instance,
 //     G[b][x][n] = sum_k mean_n f[b][n][x][k] * W[n][k]        n in [col0, col0 + ncols)  (the W_b / Wd W_b rows of the folded matrix)
@@ -222,50 +243,75 @@ __global__ __launch_bounds__(256) void glob_mean_gemv_kernel(const float* __rest
             *reinterpret_cast<float4*>(&lmean[c4 * 4]) = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
         }
         __syncthreads();
-    } else
-    for (int cb = 0; cb < row; cb += 64) {     // 64 columns of the [N, 3C] matrix at a time: 16 float4 groups x 16 row slices
-        const int col = cb + cg * 4;
-        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (col < row) {
-            const float* p = f + (size_t)b * N * row + col;
-#pragma unroll 8
-            for (int n = rs; n < N; n += 16) {
-                const float4 v = *reinterpret_cast<const float4*>(p + (size_t)n * row);
-                s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-            }
-        }
-        part[rs][cg] = s;
-        __syncthreads();
-        if (rs == 0 && col < row) {
-            float4 t = part[0][cg];
+    } else {
+        // 64 columns of the [N, 3C] matrix at a time: 16 float4 groups x 16 row slices, the slices combined in ascending order
+        auto combine = [&](int col, const float4& s) {
+            part[rs][cg] = s;
+            __syncthreads();
+            if (rs == 0 && col < row) {
+                float4 t = part[0][cg];
 #pragma unroll
-            for (int r = 1; r < 16; ++r) { const float4 v = part[r][cg]; t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w; }
-            *reinterpret_cast<float4*>(&lmean[col]) = make_float4(t.x * inv, t.y * inv, t.z * inv, t.w * inv);
+                for (int r = 1; r < 16; ++r) { const float4 v = part[r][cg]; t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w; }
+                *reinterpret_cast<float4*>(&lmean[col]) = make_float4(t.x * inv, t.y * inv, t.z * inv, t.w * inv);
+            }
+            __syncthreads();
+        };
+        if (N <= 16) {
+            // at most one row per slice (the producer's partial column sums at layers 2 - 4): the values of all chunks (row < 512: at most eight) are
+            // requested before the first barrier, at a clamped address -- chunk by chunk this was one round trip per chunk, two barriers apart
+            float4 pv[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) pv[c] = *reinterpret_cast<const float4*>(f + ((size_t)b * N + min(rs, N - 1)) * row + min(c * 64 + cg * 4, row - 4));
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                if (c * 64 >= row) break;
+                const int col = c * 64 + cg * 4;
+                float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (col < row && rs < N) { s.x += pv[c].x; s.y += pv[c].y; s.z += pv[c].z; s.w += pv[c].w; }
+                combine(col, s);
+            }
+        } else
+        for (int cb = 0; cb < row; cb += 64) {
+            const int col = cb + cg * 4;
+            float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (col < row) {
+                const float* p = f + (size_t)b * N * row + col;
+#pragma unroll 8
+                for (int n = rs; n < N; n += 16) {
+                    const float4 v = *reinterpret_cast<const float4*>(p + (size_t)n * row);
+                    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+                }
+            }
+            combine(col, s);
         }
-        __syncthreads();
     }
     // columns: SIXTEEN lanes own a column and walk its weight row together (lane l takes k = 4 l, 4 l + 64, ...: every load instruction reads whole
     // contiguous row segments), three partial dot products per lane, summed over the sixteen lanes on the DPP network.  (Until round 5 a lane owned a
     // column and read ITS row 16 bytes at a time: each of those loads is its own L2 transaction -- 26 us at layer 6 for 2 MB of weights.)
     const int j0 = blockIdx.y * cols_per_block, j1 = min(ncols, j0 + cols_per_block);
+    // The walk is C / 64 WHOLE trips of all sixteen lanes plus one trip of the lanes with 4 l + 64 (C / 64) < C: uniform trip counts.  (Written as
+    // `for (k = 4 l; k < C; k += 64)` the count depends on the lane, the unroll pragma is ignored and every trip is one 16-byte load, a full wait and twelve
+    // FMAs: sixteen dependent round trips per workgroup at C = 512.)  The whole trips go in batches of 8, 4, 2, 1 (gemv_trips: the loads of a batch, both
+    // columns, before its first FMA) -- one batch at C = 128, 256, 512 -- and the last trip's load is requested ahead of them at an address clamped into the
+    // row; a lane without a last trip leaves its accumulators alone.  Each accumulator keeps its order: k ascending, x, y, z, w within a float4.
     const int kl = lane & 15, jr = wave * 4 + (lane >> 4);
+    const int nfull = C >> 6, krem = 4 * kl + 64 * nfull;
     for (int jb = j0; jb < j1; jb += 32) {          // two columns per lane group and trip: more loads in flight
         float a[2][3];
+        const float* wr[2];
+        float4 wrem[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-            const int j = jb + 16 * u + jr;
-            const float* wr = W + (size_t)(col0 + min(j, j1 - 1)) * C;
+            wr[u] = W + (size_t)(col0 + min(jb + 16 * u + jr, j1 - 1)) * C;
+            wrem[u] = *reinterpret_cast<const float4*>(wr[u] + min(krem, C - 4));
             a[u][0] = a[u][1] = a[u][2] = 0.f;
-#pragma unroll 8
-            for (int k = 4 * kl; k < C; k += 64) {
-                const float4 w = *reinterpret_cast<const float4*>(wr + k);
-                const float4 m0 = *reinterpret_cast<const float4*>(&lmean[k]), m1 = *reinterpret_cast<const float4*>(&lmean[C + k]),
-                             m2 = *reinterpret_cast<const float4*>(&lmean[2 * C + k]);
-                a[u][0] = __builtin_fmaf(m0.x, w.x, a[u][0]); a[u][0] = __builtin_fmaf(m0.y, w.y, a[u][0]); a[u][0] = __builtin_fmaf(m0.z, w.z, a[u][0]); a[u][0] = __builtin_fmaf(m0.w, w.w, a[u][0]);
-                a[u][1] = __builtin_fmaf(m1.x, w.x, a[u][1]); a[u][1] = __builtin_fmaf(m1.y, w.y, a[u][1]); a[u][1] = __builtin_fmaf(m1.z, w.z, a[u][1]); a[u][1] = __builtin_fmaf(m1.w, w.w, a[u][1]);
-                a[u][2] = __builtin_fmaf(m2.x, w.x, a[u][2]); a[u][2] = __builtin_fmaf(m2.y, w.y, a[u][2]); a[u][2] = __builtin_fmaf(m2.z, w.z, a[u][2]); a[u][2] = __builtin_fmaf(m2.w, w.w, a[u][2]);
-            }
         }
+        int k = 4 * kl;
+        for (int t0 = 0; t0 + 8 <= nfull; t0 += 8, k += 64 * 8) gemv_trips<8>(wr[0], wr[1], lmean, C, k, a[0], a[1]);
+        if (nfull & 4) { gemv_trips<4>(wr[0], wr[1], lmean, C, k, a[0], a[1]); k += 64 * 4; }
+        if (nfull & 2) { gemv_trips<2>(wr[0], wr[1], lmean, C, k, a[0], a[1]); k += 64 * 2; }
+        if (nfull & 1) gemv_trips<1>(wr[0], wr[1], lmean, C, k, a[0], a[1]);
+        if (krem < C) { gemv_fma3(a[0], wrem[0], lmean, C, krem); gemv_fma3(a[1], wrem[1], lmean, C, krem); }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int j = jb + 16 * u + jr;
@@ -565,6 +611,12 @@ int tail_launch(const float* Tc, int ldc, int B, int NP, int Cd, const float* in
 
 using namespace ls;
 extern "C" {
+int ls_glob_mean_gemv_f32(const float* f, int B, int N, int C, const float* W, int col0, int ncols, float* G, int ldg, int npoints, void* stream) {
+    LS_REQUIRE(f && W && G, "glob_mean_gemv: null argument");
+    LS_REQUIRE(B > 0 && N > 0 && C > 0 && col0 >= 0 && ncols > 0 && ldg >= col0 + ncols && npoints >= 0, "glob_mean_gemv: bad shape (B=%d N=%d C=%d col0=%d ncols=%d ldg=%d npoints=%d)",
+               B, N, C, col0, ncols, ldg, npoints);
+    return glob_mean_gemv_launch(f, B, N, C, W, col0, ncols, G, ldg, (hipStream_t)stream, npoints);
+}
 int ls_encode_prologue_f32(const float* x, int B, int N, float* pts_out, float* centroid_out, float* scale0_out, void* stream) {
     LS_REQUIRE(B > 0, "prologue: empty batch");
     return prologue_launch(x, B, N, pts_out, centroid_out, scale0_out, nullptr, (hipStream_t)stream);
