@@ -66,7 +66,8 @@ typedef enum {
  * ls_cloud_normals_f32 / ls_cloud_normals_batch_f32, ls_cloud_icp_plane_f32 / ls_cloud_icp_plane_batch_f32, ls_cloud_project_f32 / ls_cloud_project_batch_f32,
  * ls_mesh_render_depth_f64 / ls_mesh_render_depth_batch_f64, ls_depth_points_f32, ls_cloud_carve_f32 / ls_cloud_carve_batch_f32,
  * ls_depth_fuse_f32 / ls_depth_fuse_batch_f32, ls_tsdf_volume_f64, ls_tsdf_mesh_f64 / ls_tsdf_mesh_batch_f64,
- * ls_tsdf_sample_f32 / ls_tsdf_sample_batch_f32, ls_tsdf_icp_f32 / ls_tsdf_icp_batch_f32 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
+ * ls_tsdf_sample_f32 / ls_tsdf_sample_batch_f32, ls_tsdf_icp_f32 / ls_tsdf_icp_batch_f32,
+ * ls_tsdf_draw_f32 / ls_tsdf_draw_batch_f32, ls_tsdf_fit_loss_f64 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
  * binding compares it with the header it was written against and refuses a mismatch (livingscenes_amd/_lib.py: load). */
 #define LS_ABI_VERSION 107
 int ls_version(void);
@@ -1155,6 +1156,60 @@ int ls_tsdf_icp_batch_f32(int P, const int32_t* sum, const int32_t* n, int nx, i
                           double rel_thr, int min_matched, float* g_out, int32_t* stop, int32_t* iters, double* phi, double* grad, uint8_t* state,
                           long long* counts, double* sum_phi2, float* g_trace, double* stat_trace, void* workspace, size_t workspace_bytes,
                           void* stream);
+
+/* Scene memory, the fused state as a TRAINING SIGNAL for the latent codes (csrc/tsdffit.hip; off-surface samples and the clamp of free
+ * space: Park et al., DeepSDF, CVPR 2019).  AN EXTENSION BEYOND THE RELEASED REFERENCE, whose code optimisation is supervised by
+ * MSE(sdf(points), 0) alone.  Definition (csrc/tsdffit_plan.h is the same text as C++, tests/tsdf_fit_oracle.py as NumPy).
+ *
+ * THE DRAW, per problem: state sum / n int32 [nx,ny,nz], k fastest (DEVICE), origin [3], voxel, trunc (HOST doubles), a seed (uint64).
+ *   eligibility  a lattice sample is eligible iff n >= min_obs (min_obs >= 1).
+ *   kinds        FREE (2) iff sum == n * 16384: every view that looked saw the sample at or beyond +trunc (the projective distance is
+ *                clamped on that side only).  Every other eligible sample is BAND (1): ls_depth_fuse_f32 never records less than -1 (an
+ *                occluded sample is skipped), so D = -1 is an exact value, not a clamp.  Integer comparisons only.
+ *   lists        the eligible samples of a kind in linear index order form a list of length L.
+ *   quotas       a quota m (n_band or n_free, each >= 0, N = n_band + n_free >= 1) takes T = min(L, m) of them, one per stratum: stratum
+ *                j is the list ranks [floor(j L / T), floor((j + 1) L / T)), of width w_j >= 1; the rank taken is
+ *                floor(j L / T) + ((r_j * w_j) >> 32) in 64-bit unsigned arithmetic, r_j = the top 32 bits of
+ *                mix64(key + (j + 1) * 0x9E3779B97F4A7C15), key = mix64(seed + kind * 0x9E3779B97F4A7C15), mix64 the finaliser of
+ *                splitmix64.  The ranks are distinct and ascending, and with L <= m every sample is taken.
+ *   outputs      (DEVICE) columns [0, n_band) for the band and [n_band, N) for free space: points float [N,3] = the float64
+ *                origin_a + voxel * index_a of each axis rounded once to fp32; target double [N] = trunc * sum / (n * 16384), metres;
+ *                kind uint8 [N]; index int32 [N] = the linear sample index; counts long long [3] = eligible, band, free samples.  A
+ *                column beyond T is a PAD (0): the position of lattice sample 0, target 0, index -1.
+ * A problem's draw depends on its own state, grid and seed only.  Refused on the host before the first HIP call: dims < 1,
+ * P nx ny nz >= 2^31, nx ny nz above 4096 blocks of 4096 samples (the scan of a problem's block counts is one workgroup; the error names
+ * the bound), min_obs < 1, a negative quota, N = 0, P N >= 2^31, P > 65535, null pointers, a grid that ls_depth_fuse_f32 refuses.
+ * Launches: the copy of the host arrays into the workspace and 3 kernels (classify, scan, resolve), whatever P; no host
+ * synchronisation, no allocation, no atomics.  The ranks are resolved by a search over the scanned block counts and two mask words per
+ * 64 samples: no compact list is written.  The workspace is a function of (P, nx, ny, nz), 0 for refused sizes.
+ * NO QUOTA AND NO min_obs IS RECOMMENDED: nothing here can measure one. */
+#define LS_FIT_PAD 0
+#define LS_FIT_BAND 1
+#define LS_FIT_FREE 2
+size_t ls_tsdf_draw_workspace_bytes(int nx, int ny, int nz);
+int ls_tsdf_draw_f32(const int32_t* sum, const int32_t* n, int nx, int ny, int nz, int min_obs, const double* origin, double voxel, double trunc,
+                     long long n_band, long long n_free, unsigned long long seed, float* points, double* target, uint8_t* kind, int32_t* index, long long* counts,
+                     void* workspace, size_t workspace_bytes, void* stream);
+/* P >= 1 problems per call: one (nx, ny, nz) and one pair of quotas per call, sum / n [P,nx,ny,nz], origin [P,3], voxel [P], trunc [P],
+ * seeds [P] (HOST), points [P,N,3], target / kind / index [P,N], counts [P,3].  Every output of every problem is BIT-IDENTICAL to
+ * ls_tsdf_draw_f32 on that problem alone, wherever it stands in the batch: the single entry is the batch of one problem. */
+size_t ls_tsdf_draw_batch_workspace_bytes(int P, int nx, int ny, int nz);
+int ls_tsdf_draw_batch_f32(int P, const int32_t* sum, const int32_t* n, int nx, int ny, int nz, int min_obs, const double* origin, const double* voxel,
+                           const double* trunc, long long n_band, long long n_free, const unsigned long long* seeds, float* points, double* target, uint8_t* kind,
+                           int32_t* index, long long* counts, void* workspace, size_t workspace_bytes, void* stream);
+/* THE LOSS, in the decoder's own units.  THIS BUILD'S DEFINITION, pinned by no test of the reference: the decoder's value times the
+ * instance's scale s is a metric distance.  It follows the reference's training loss, which compares the decoder's output with distances
+ * in the normalised frame; the reference's point loss MSE(sdf, 0) is the special case target = 0.  Inputs (DEVICE): sdf float [P,N],
+ * s float [P], trunc double [P], target double [P,N], kind uint8 [P,N] (LS_FIT_*).  With u = (double) sdf:
+ *   BAND e = u - target / (double) s;   FREE e = min(u - trunc / (double) s, 0.0), a one-sided hinge;   PAD e = 0.
+ * m_p = the number of non-PAD columns.  loss[p] (double) = (sum of e^2 by the chunk rule of ls_tsdf_sample_f32: chunks of 256 columns,
+ * a fixed tree in each wave of 64, a fixed tree over the four waves, the records added in chunk order from 0.0) / m_p, 0.0 where
+ * m_p = 0; grad[p,i] = (float)(2 e / m_p), 0 where m_p = 0.  Optional min_loss double [P] and improved int32 [P]: where
+ * loss < min_loss, min_loss = loss and improved = 1, the bookkeeping of ls_mse_f32.  NO WEIGHT BETWEEN THE KINDS (the quotas set the
+ * balance), NO CLAMP OF THE BAND ERROR, AND s IS NOT OPTIMISED (the reference's loop does not move it either).  One launch for any P,
+ * one workgroup per chunk; the workgroup of a problem's chunk 0 adds that problem's records in order.  No atomics. */
+int ls_tsdf_fit_loss_f64(const float* sdf, const float* s, const double* trunc, const double* target, const uint8_t* kind, int P, int N, double* loss,
+                         float* grad, double* min_loss, int32_t* improved, void* stream);
 
 /* Scene memory, the trimmed ICP with the point-to-plane metric (csrc/cloudnear.hip).  AN EXTENSION BEYOND THE RELEASED REFERENCE, like
  * ls_cloud_icp_f32, whose loop this is: a partial view registered point-to-point onto one point per voxel of a SURFACE slides along it

@@ -76,6 +76,7 @@ _F = ctypes.c_float
 _D = ctypes.c_double
 _SZ = ctypes.c_size_t
 _LL = ctypes.c_longlong
+_U64 = ctypes.c_ulonglong
 
 # name -> (restype, argtypes); every symbol include/livingscenes_hip.h declares
 class SoftminProblem(ctypes.Structure):
@@ -247,6 +248,11 @@ SIGNATURES = {
     "ls_tsdf_icp_batch_workspace_bytes": (_SZ, [_I, _I, _I, _I, _LL]),
     "ls_tsdf_icp_batch_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _LL, _P, _P, _I, _D, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                    _SZ, _P]),
+    "ls_tsdf_draw_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "ls_tsdf_draw_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _D, _D, _LL, _LL, _U64, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "ls_tsdf_draw_batch_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "ls_tsdf_draw_batch_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _LL, _LL, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "ls_tsdf_fit_loss_f64": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "ls_profile_begin": (_I, [_P]),
     "ls_profile_end": (_I, [_P, ctypes.POINTER(ProfileEntry), _I, ctypes.POINTER(ctypes.c_int)]),
 }

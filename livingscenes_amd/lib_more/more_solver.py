@@ -8,6 +8,8 @@ update and the Sinkhorn divergence of that branch follow this build's documented
 import logging
 import math
 
+import numpy as np
+
 import torch
 
 from .. import ops
@@ -259,6 +261,75 @@ class More_Solver:
             code["t"].copy_(t.reshape(code["t"].shape))
         improved = improved.bool()
         return {k: code[k].detach() for k in ("z_inv", "z_so3", "s", "t")}, improved
+
+    def _optimize_code_on_fusion_batch(self, code, fusion, slots=None, n_band=None, n_free=None, n_steps=200, min_obs=1, seed=0):
+        """Scene memory, the FUSED STATE as the training signal of the code optimisation (an extension beyond the released reference, whose
+        only supervision is MSE(sdf(points), 0): the surface, which says nothing about which side is outside nor about the space the
+        cameras looked through; off-surface samples and the clamp of free space are DeepSDF's, Park et al. 2019).  The loop of
+        _optimize_code_batch with the _sample call replaced by ONE draw (ops.tsdf_draw_batch, csrc/tsdffit.hip) and ops.mse by
+        ops.tsdf_fit_loss: equality with the fused distance inside the band, a one-sided hinge "at least trunc" in observed free space,
+        both in the decoder's units (THIS BUILD'S DEFINITION: the decoder's value times s is a metric distance).  Everything else is the
+        same: the parameter groups and learning rates, the x0.1 at step 160, the inv_only case of decoder_type "deepsdf", split-K off, the
+        write-back, the same four launches per Adam step.  `code` holds P rows; fusion = the dict of _fuse_batch (sum, n: int32
+        [n,res,res,res]; origin, voxel, trunc); slots = the P slots of the fusion the rows belong to (None: the fusion has P slots, in
+        order).  n_band / n_free default to n_input_point // 2 each -- DERIVED, NOT TUNED: the decoder batch then has the size the point
+        path gives it.  The seed of slot i is seed + i, so a slot's draw does not depend on which other slots are optimised with it.  No
+        weight between the kinds, no clamp of the band error, and s is not optimised (the reference's loop does not move it either).
+        -> (code dict of the final values, improved [P] bool, report: dict of per-row lists loss_first, loss_last (float64: the loss at
+        the first and at the last step), n_band, n_free (columns actually taken)).  A slot whose state holds no eligible sample has no
+        column: its loss is 0, its gradient 0, it never improves and keeps its code.  NO QUOTA, min_obs OR fuse_res IS RECOMMENDED, and
+        whether the fitted code matches or meshes better than the point-fitted one is unmeasured: nothing here can measure it."""
+        from .. import _lib
+        n_in = self.cfg["shape_priors"]["n_input_point"]
+        n_band = n_in // 2 if n_band is None else int(n_band)
+        n_free = n_in // 2 if n_free is None else int(n_free)
+        P = code["z_inv"].shape[0]
+        slots = list(range(fusion["sum"].shape[0])) if slots is None else [int(i) for i in slots]
+        if len(slots) != P:
+            raise ValueError(f"{P} code rows for {len(slots)} slots of the fusion")
+        S, N = fusion["sum"], fusion["n"]
+        dev = S.device
+        origin, voxel, trunc = (np.asarray(fusion[k], dtype=np.float64) for k in ("origin", "voxel", "trunc"))
+        if slots != list(range(S.shape[0])):
+            rows = torch.tensor(slots, device=dev)
+            S, N = S[rows].contiguous(), N[rows].contiguous()
+            origin, voxel, trunc = origin[slots], voxel[slots], trunc[slots]
+        pc, target, kind, _, counts = ops.tsdf_draw_batch((S, N), origin=origin, voxel=voxel, trunc=trunc, n_band=n_band, n_free=n_free,
+                                                          seeds=np.array([int(seed) + i for i in slots], dtype=np.uint64), min_obs=min_obs)
+        trunc_dev = torch.as_tensor(np.ascontiguousarray(trunc), device=dev)
+        z_inv = code["z_inv"].detach().float().contiguous().clone()
+        t = code["t"].detach().float().reshape(P, 3).contiguous().clone()
+        z_so3 = code["z_so3"].detach().float().contiguous().clone()
+        s_ = code["s"].detach().float().contiguous()
+        s_row = s_.reshape(P).contiguous()
+        hip = self.model.hip_model()
+        inv_only = hip.desc.dec_input == _lib.DEC_XYZ
+        opt = ops.Adam([(z_inv, 1e-5)] if inv_only else [(z_inv, 1e-5), (t, 1e-4), (z_so3, 5e-4)])   # more_solver.py:199-203
+        min_loss = torch.full((P,), 100.0, dtype=torch.float64, device=dev)   # :205
+        improved = torch.zeros(P, dtype=torch.int32, device=dev)
+        first = last = torch.zeros(P, dtype=torch.float64, device=dev)
+        prev_split = hip.set_option(_lib.OPT_SDF_TRAIN_SPLITK, 0)
+        try:
+            # per step the four launches of _optimize_code_batch: decoder forward, the loss + its gradient + the best-loss bookkeeping,
+            # decoder backward w.r.t. the code, ONE Adam launch -- no autograd graph, no ATen kernel, no host read inside the loop
+            for i in range(n_steps):
+                sdf, saved = hip.sdf_decode_train(pc, z_so3, z_inv, s_, t)
+                last, gsdf = ops.tsdf_fit_loss(sdf, s_row, trunc_dev, target, kind, min_loss, improved)
+                if i == 0:
+                    first = last
+                _, gso3, ginv, _, gt = hip.sdf_backward(saved, gsdf, need_query_grad=False)
+                opt.step([ginv] if inv_only else [ginv, gt, gso3], lr_scale=0.1 if i >= 160 else 1.0)   # MultiStepLR([160], 0.1) (:204)
+        finally:
+            hip.set_option(_lib.OPT_SDF_TRAIN_SPLITK, prev_split)
+        with torch.no_grad():
+            code["z_inv"].copy_(z_inv.reshape(code["z_inv"].shape))
+            code["z_so3"].copy_(z_so3.reshape(code["z_so3"].shape))
+            code["t"].copy_(t.reshape(code["t"].shape))
+        report = {"loss_first": first.cpu().tolist(), "loss_last": last.cpu().tolist(),
+                  "n_band": np.minimum(counts[:, 1], n_band).tolist(), "n_free": np.minimum(counts[:, 2], n_free).tolist()}
+        # a slot without a column has loss 0.0, which is below the starting min_loss: it did not improve, it has nothing to fit
+        improved = improved.bool() & torch.as_tensor(counts[:, 0] > 0, device=dev)
+        return {k: code[k].detach() for k in ("z_inv", "z_so3", "s", "t")}, improved, report
 
     @staticmethod
     def _memory_pose(T, g, P):
@@ -775,7 +846,7 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
                    refine_radius=None, refine_metric="point", normal_radius=None, consolidate=False, consolidate_radius=None,
                    consolidate_max_variation=1 / 3, consolidate_max_shift=float("inf"), carve_tol=None, carve_window=1, carve_min_free=1,
                    carve_max_seen=0, carve_empty="unknown", fuse_res=None, fuse_trunc_voxels=4, fuse_empty="unknown", fuse_mesh=False,
-                   fuse_min_obs=1):
+                   fuse_min_obs=1, code_fit_band=None, code_fit_free=None, code_fit_seed=0):
     """A reference scan followed by SEVERAL rescans, with a memory that carries every instance's points from one rescan to the next -- an
     extension beyond the released reference (more_solver.py:246-299 solves one (reference, rescan) pair and drops the rescan's points).
     ref and every rescan: {'pc' [n,3,Nmax], 'pc_mask'} as _solve_end2end takes them.
@@ -865,7 +936,24 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
     gains 'observed_meshes', More_Solver._observed_mesh_batch(fusion, fuse_min_obs): one mesh per slot in the reference frame, of
     the cubes whose eight corners were observed at least fuse_min_obs times, None for a slot nothing kept.  With fuse_mesh False the
     memory has no such key.  fuse_trunc_voxels = 4 is AN UNMEASURED DEFAULT; NO fuse_res IS RECOMMENDED, and no fuse_min_obs: no real scans are
-    available here to measure one on, and what the fused volume or its mesh does for anything downstream is unmeasured."""
+    available here to measure one on, and what the fused volume or its mesh does for anything downstream is unmeasured.
+
+    The fit to the fused state (opt-in: optimize_codes False and True behave exactly as above).  optimize_codes="tsdf" (it needs fuse_res;
+    without one a ValueError raised before any device work, as any value other than False, True and "tsdf" is) replaces the step's
+    _optimize_code_batch call by ONE More_Solver._optimize_code_on_fusion_batch call on the re-encoded slots, AFTER the step's fuse, so the
+    state includes this rescan: code_fit_band / code_fit_free columns per slot (None: n_input_point // 2 each, derived: the decoder
+    batch of the point path) drawn out of the slot's state with min_obs = fuse_min_obs and the call seed code_fit_seed + step * n (slot
+    i: that plus i), held to the fused distance inside the band and to "at least trunc" in observed free space.  A slot keeps the
+    optimised code where its loss improved; a slot whose state holds no observation has nothing to fit and keeps its code.  The step
+    gains code_fit: the report of the call (per-slot lists loss_first, loss_last, n_band, n_free of n entries, None for slots not
+    optimised; None for a step that optimised nothing).  NO QUOTA IS RECOMMENDED, nor any min_obs or fuse_res for fitting: no real scans
+    and no trained model are available here, and nothing here can measure the effect on matching or on the meshes."""
+    if isinstance(optimize_codes, (bool, np.bool_)):
+        optimize_codes = bool(optimize_codes)
+    elif not (isinstance(optimize_codes, str) and optimize_codes == "tsdf"):
+        raise ValueError(f"solve_sequence: optimize_codes must be False, True or 'tsdf', got {optimize_codes!r}")
+    if optimize_codes == "tsdf" and fuse_res is None:
+        raise ValueError("solve_sequence: optimize_codes 'tsdf' needs fuse_res: without a fused state there is nothing to fit the codes to")
     if refine_metric not in ("point", "plane", "tsdf"):
         raise ValueError(f"solve_sequence: refine_metric must be 'point', 'plane' or 'tsdf', got {refine_metric!r}")
     if refine_metric == "plane" and refine_radius is None:
@@ -896,7 +984,7 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
         if ref.get("views") is not None:
             solver._fuse_batch(fusion, list(ref["views"]), empty=fuse_empty)
     steps = []
-    for rescan in rescans:
+    for step_no, rescan in enumerate(rescans):
         res_full = _scene_clouds(rescan)
         res_codes = model.encode_fps(rescan["pc"], rescan["pc_mask"])
         m0 = solver._solve_object_matching(codes, res_codes, "sequential")["matches0"]
@@ -910,6 +998,8 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
             out["n_fused_views"] = [0] * n
         if refining:
             out.update({"refine_stop": [None] * n, "refine_iters": [None] * n, "registration_init": [None] * n})
+        if optimize_codes == "tsdf":
+            out["code_fit"] = None
         if pairs:
             src, tgt = [mem[i] for i, _ in pairs], [res_full[j] for _, j in pairs]
             R, t = solver._solve_pairwise_registration_optim_batch(src, tgt) if optim else solver._solve_pairwise_registration_batch(src, tgt)
@@ -1005,7 +1095,16 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
                 new = {k: new[k].detach().clone() for k in _CODE_KEYS}
                 if optimize_codes:
                     enc = {k: v.clone() for k, v in new.items()}
-                    opt, improved = solver._optimize_code_batch(new, [mem[i] for i in again])
+                    if optimize_codes == "tsdf":
+                        opt, improved, fit = solver._optimize_code_on_fusion_batch(new, fusion, slots=again, n_band=code_fit_band,
+                                                                                   n_free=code_fit_free, min_obs=fuse_min_obs,
+                                                                                   seed=code_fit_seed + step_no * n)
+                        out["code_fit"] = {key: [None] * n for key in fit}
+                        for key, vals in fit.items():
+                            for i, v in zip(again, vals):
+                                out["code_fit"][key][i] = v
+                    else:
+                        opt, improved = solver._optimize_code_batch(new, [mem[i] for i in again])
                     new = {k: torch.where(improved.view(-1, *([1] * (enc[k].dim() - 1))), opt[k], enc[k]) for k in _CODE_KEYS}
                 rows = torch.tensor(again, device=codes["z_inv"].device)
                 for k in _CODE_KEYS:

@@ -1778,3 +1778,92 @@ def tsdf_icp(state, B, g=None, *, origin, voxel, trunc, min_obs=1, max_iter=100,
     max_iter = 100 and rel_thr = 1e-6 are ops.icp's defaults, pytorch3d's: inherited, not tuned.  Bit-identical to the same problem
     inside any tsdf_icp_batch.  NO min_obs IS RECOMMENDED."""
     return _tsdf_icp("tsdf_icp", True, state, B, g, origin, voxel, trunc, min_obs, max_iter, rel_thr, min_matched, trace, False)
+
+
+# ------------------------------------------------------------------------------------------------ the fused state as a training signal (csrc/tsdffit.hip)
+FIT_KIND = ("pad", "band", "free")                         # the values of a column's kind, by value
+DRAW_COUNT = ("eligible", "band", "free")                  # the columns of tsdf_draw's counts, by value
+
+
+def _tsdf_draw(op, single, state, origin, voxel, trunc, n_band, n_free, seeds, min_obs):
+    S, N, P, dims = _fuse_state(op, state, not single)
+    dev = S.device
+    min_obs, n_band, n_free = int(min_obs), int(n_band), int(n_free)
+    if min_obs < 1:
+        raise ValueError(f"{op}: min_obs must be >= 1, got {min_obs}")
+    if n_band < 0 or n_free < 0 or n_band + n_free < 1:
+        raise ValueError(f"{op}: quotas n_band, n_free >= 0 with n_band + n_free >= 1, got {n_band}, {n_free}")
+    o, h, tr = _fuse_grid(op, P, origin, voxel, trunc)
+    sd = np.asarray(seeds.detach().cpu().numpy() if torch.is_tensor(seeds) else seeds)
+    if sd.ndim == 0:
+        sd = sd.reshape(1)
+    if sd.shape != (P,) or sd.dtype.kind not in "iu" or (sd.dtype.kind == "i" and (sd < 0).any()):
+        raise ValueError(f"{op}: seeds are {P} non-negative integers (uint64), one per problem, got {sd.dtype} {sd.shape}")
+    sd = np.ascontiguousarray(sd, dtype=np.uint64)
+    cols = n_band + n_free
+    name = "ls_" + op
+    ws_bytes = getattr(load(), name + "_workspace_bytes")(*(() if single else (P,)), *dims)
+    if ws_bytes == 0 or P * cols >= 2 ** 31:
+        raise ValueError(f"{op}: P = {P} problems of dims {dims} with {cols} columns unsupported (include/livingscenes_hip.h: P nx ny nz < 2^31, "
+                         "nx ny nz <= 4096 blocks of 4096 samples, P <= 65535, P (n_band + n_free) < 2^31)")
+    ws = _scratch(ws_bytes, dev)
+    points = torch.empty(P, cols, 3, dtype=torch.float32, device=dev)
+    target = torch.empty(P, cols, dtype=torch.float64, device=dev)
+    kind = torch.empty(P, cols, dtype=torch.uint8, device=dev)
+    index = torch.empty(P, cols, dtype=torch.int32, device=dev)
+    counts = torch.empty(P, 3, dtype=torch.int64, device=dev)
+    outs = (ptr(points), ptr(target), ptr(kind), ptr(index), ptr(counts), ptr(ws), ws.numel(), stream_ptr(dev))
+    if single:
+        call(dev, name + "_f32", ptr(S), ptr(N), *dims, min_obs, _hptr(o), float(h[0]), float(tr[0]), n_band, n_free, int(sd[0]), *outs)
+        return points[0], target[0], kind[0], index[0], counts[0].cpu().numpy()
+    call(dev, name + "_f32", P, ptr(S), ptr(N), *dims, min_obs, _hptr(o), _hptr(h), _hptr(tr), n_band, n_free, _hptr(sd), *outs)
+    return points, target, kind, index, counts.cpu().numpy()
+
+
+def tsdf_draw_batch(state, *, origin, voxel, trunc, n_band, n_free, seeds, min_obs=1):
+    """ls_tsdf_draw_batch_f32 (an extension beyond the released reference, like tsdf_icp): a fixed-size, deterministic set of training
+    samples drawn out of the fused states of P instances.  state = (sum, n) int32 HIP tensors [P,nx,ny,nz] (tsdf_state, depth_fuse_batch);
+    origin [P,3] or [3], voxel, trunc (one value or P): host float64, the grids the views were fused on; seeds: P uint64.  A lattice
+    sample with n >= min_obs is FREE iff sum == n * 16384 (every view that looked saw it at or beyond +trunc), else BAND.  Of each kind's
+    list, in linear index order, a quota (n_band, n_free; the same for every problem) takes one sample per stratum, chosen by a
+    splitmix64 stream of the problem's seed: the definition of include/livingscenes_hip.h, by equality.  A list shorter than its quota
+    is taken whole and the remaining columns are PAD.
+    -> (points fp32 [P,N,3], target float64 [P,N] in metres, kind uint8 [P,N] of FIT_KIND, index int32 [P,N] (-1: PAD): device tensors,
+    columns [0, n_band) the band and [n_band, N) free space; counts host int64 [P,3] of DRAW_COUNT).  One call, three kernels and one
+    host read (the counts), whatever P.  A problem's draw does not depend on the batch.  NO QUOTA AND NO min_obs IS RECOMMENDED."""
+    return _tsdf_draw("tsdf_draw_batch", False, state, origin, voxel, trunc, n_band, n_free, seeds, min_obs)
+
+
+def tsdf_draw(state, *, origin, voxel, trunc, n_band, n_free, seeds, min_obs=1):
+    """ls_tsdf_draw_f32: state = (sum, n) int32 HIP tensors [nx,ny,nz] (a slice of tsdf_state), origin [3], voxel and trunc host float64,
+    seeds one uint64 -> (points [N,3], target [N], kind [N], index [N], counts host int64 [3]) as tsdf_draw_batch describes them,
+    bit-identical to the same problem anywhere inside any batch.  NO QUOTA AND NO min_obs IS RECOMMENDED."""
+    return _tsdf_draw("tsdf_draw", True, state, origin, voxel, trunc, n_band, n_free, seeds, min_obs)
+
+
+def tsdf_fit_loss(sdf, s, trunc, target, kind, min_loss=None, improved=None):
+    """ls_tsdf_fit_loss_f64: the loss that holds the decoder to a draw, in the decoder's own units -- THIS BUILD'S DEFINITION: the
+    decoder's value times s is a metric distance.  sdf fp32 [P,N], s fp32 [P], trunc float64 [P], target float64 [P,N], kind uint8 [P,N]
+    (HIP tensors; tsdf_draw_batch makes the last two).  BAND: e = sdf - target / s; FREE: e = min(sdf - trunc / s, 0), a one-sided
+    hinge; PAD: 0; float64.  -> (loss float64 [P] = sum e^2 / m_p over the m_p non-PAD columns, 0 where there is none;
+    grad fp32 [P,N] = 2 e / m_p).  min_loss float64 [P] / improved int32 [P] (optional) are updated in place where the loss improved,
+    as ops.mse does.  No weight between the kinds, no clamp of the band error; MSE(sdf, 0) is the case target = 0, all BAND."""
+    op = "tsdf_fit_loss"
+    sdf = _f32(sdf)
+    if sdf.dim() != 2 or sdf.numel() == 0:
+        raise ValueError(f"{op}: sdf is [P,N], got {tuple(sdf.shape)}")
+    P, N = sdf.shape
+    dev = sdf.device
+    for name, t, dtype, shape in (("s", s, torch.float32, (P,)), ("trunc", trunc, torch.float64, (P,)), ("target", target, torch.float64, (P, N)),
+                                  ("kind", kind, torch.uint8, (P, N)), ("min_loss", min_loss, torch.float64, (P,)),
+                                  ("improved", improved, torch.int32, (P,))):
+        if t is None and name in ("min_loss", "improved"):
+            continue
+        if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+            got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+            raise ValueError(f"{op}: {name} must be a contiguous {dtype} tensor {shape} on {dev}, got {got}")
+    loss = torch.empty(P, dtype=torch.float64, device=dev)
+    grad = torch.empty_like(sdf)
+    call(dev, "ls_tsdf_fit_loss_f64", ptr(sdf), ptr(s), ptr(trunc), ptr(target), ptr(kind), P, N, ptr(loss), ptr(grad), ptr(min_loss), ptr(improved),
+         stream_ptr(dev))
+    return loss, grad
