@@ -67,7 +67,8 @@ typedef enum {
  * ls_mesh_render_depth_f64 / ls_mesh_render_depth_batch_f64, ls_depth_points_f32, ls_cloud_carve_f32 / ls_cloud_carve_batch_f32,
  * ls_depth_fuse_f32 / ls_depth_fuse_batch_f32, ls_tsdf_volume_f64, ls_tsdf_mesh_f64 / ls_tsdf_mesh_batch_f64,
  * ls_tsdf_sample_f32 / ls_tsdf_sample_batch_f32, ls_tsdf_icp_f32 / ls_tsdf_icp_batch_f32,
- * ls_tsdf_draw_f32 / ls_tsdf_draw_batch_f32, ls_tsdf_fit_loss_f64 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
+ * ls_tsdf_draw_f32 / ls_tsdf_draw_batch_f32, ls_tsdf_fit_loss_f64,
+ * ls_tsdf_raycast_f64 / ls_tsdf_raycast_batch_f64, ls_depth_compare_f32 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
  * binding compares it with the header it was written against and refuses a mismatch (livingscenes_amd/_lib.py: load). */
 #define LS_ABI_VERSION 107
 int ls_version(void);
@@ -1210,6 +1211,75 @@ int ls_tsdf_draw_batch_f32(int P, const int32_t* sum, const int32_t* n, int nx, 
  * one workgroup per chunk; the workgroup of a problem's chunk 0 adds that problem's records in order.  No atomics. */
 int ls_tsdf_fit_loss_f64(const float* sdf, const float* s, const double* trunc, const double* target, const uint8_t* kind, int P, int N, double* loss,
                          float* grad, double* min_loss, int32_t* improved, void* stream);
+
+/* Scene memory, the fused state SEEN FROM A CAMERA (csrc/tsdfray.hip; the raycast of Newcombe et al., KinectFusion, ISMAR 2011).  AN
+ * EXTENSION BEYOND THE RELEASED REFERENCE, like the fusion.  Definition (csrc/tsdfray_plan.h is the same text as C++,
+ * tests/tsdf_ray_oracle.py as NumPy).
+ *
+ * Per problem: state sum / n int32 [nx,ny,nz], k fastest (DEVICE), origin [3], voxel h, trunc (HOST doubles, the grid
+ * ls_depth_fuse_f32 accepts, trunc / h finite), min_obs >= 1.  Per view (DEVICE doubles): cam_to_world M [3,4], camera to the grid's
+ * frame with camera x right, y down, z forward -- the convention of ls_depth_points_f32, so a raycast depth map goes straight back into
+ * ls_depth_points_f32, ls_cloud_carve_f32 and ls_depth_fuse_f32 -- and intrinsics (fx, fy, cx, cy).  Per call: height, width, znear > 0,
+ * step in voxels with 1/16 <= step <= 1.  Per pixel (px, py), the ray through the integer pixel coordinate, float64 throughout, no
+ * a * b + c contracted:
+ *   1 ray      rx = (px - cx) / fx, ry = (py - cy) / fy; a_a = (M[a,3] - origin_a) / h; b_a = ((M[a,0] rx + M[a,1] ry) + M[a,2]) / h.
+ *              The grid coordinate at camera depth z is u_a(z) = a_a + z b_a: the ray parameter IS the depth.
+ *   2 slab     against [0, n_a - 1] on every axis: an axis with b_a == 0 imposes no bound if 0 <= a_a <= n_a - 1 and else makes the
+ *              pixel OUTSIDE; any other axis gives the quotients (0 - a_a) / b_a and (n_a - 1 - a_a) / b_a, their minimum and maximum;
+ *              z_in = max(znear, the largest minimum), z_out = the smallest maximum.  OUTSIDE: a value that is not finite, a dimension
+ *              below 2, max |b_a| = 0, or !(z_in <= z_out).
+ *   3 march    dz = step / max |b_a| (no axis advances more than `step` voxels per sample); K = floor((z_out - z_in) / dz), capped at
+ *              ceil((max n_a - 1) / step) + 1 (reached only by a camera so far away that its quotients round coarser than the grid);
+ *              the samples are z_k = z_in + (double) k dz, k = 0 .. K, never accumulated: an integer trip count known before the loop.
+ *   4 sample   u_a clamped to [0, n_a - 1], i_a = min((int) floor(u_a), n_a - 2), f_a = u_a - i_a, then the value of
+ *              ls_tsdf_sample_f32 on the eight corners: SAMPLED with (phi, grad phi), or UNSEEN (a corner with n < min_obs).
+ *   5 state    walk k upward and stop at the first SAMPLED sample with phi_k <= 0: HIT if sample k - 1 exists, was SAMPLED and had
+ *              phi_{k-1} > 0, with z* = z_{k-1} + dz (phi_{k-1} / (phi_{k-1} - phi_k)); BEHIND otherwise (the first thing known along
+ *              the ray is the inside of something, or the crossing lay in unobserved space).  Never stopped: FREE if every sample was
+ *              SAMPLED (the memory looked all along this ray and found nothing), else UNSEEN.
+ *   6 outputs  a HIT: depth = (float) z*; one more sample at z*: where it is SAMPLED with g.g > 0 the normal is
+ *              (float)(grad_a / sqrt((g0 g0 + g1 g1) + g2 g2)), in the grid's frame, pointing out of the surface, else (0, 0, 0).
+ *              Every other pixel: depth 0 (the renderer's "nothing") and normal 0.
+ * NO secant iteration and NO empty-space skipping.  Outputs (DEVICE): depth float [views,H,W], normal float [views,H,W,3], state uint8
+ * [views,H,W] (LS_RAY_*), counts long long [views,5], the histogram of the states.  Depth, state and counts are the same bits as the
+ * NumPy twin; so is the normal on an MI355X with this toolchain (one device float64 sqrt, one division, one rounding to fp32: the
+ * rounding of the device's sqrt is pinned nowhere in this project, so this is what the tests observe and hold, not a promise of hipcc).
+ * Refused on the host before the first HIP call: dims < 1, P nx ny nz >= 2^31, min_obs < 1, views < 0, an empty image,
+ * views * H * W >= 2^31, znear not finite or <= 0, step outside [1/16, 1], more than 2^20 samples per ray, a grid that
+ * ls_tsdf_sample_f32 refuses, null pointers, bad offsets.  Launches: the copy of the host arrays into the workspace, one memset (counts)
+ * and one kernel, whatever P and the number of views; no floating-point atomics, one integer add per wave, view and state.  The workspace
+ * is a function of P alone, 0 for refused sizes.  step = 0.5 in the bindings is UNMEASURED; what is derived: step <= 1 keeps consecutive
+ * samples in the same or an adjacent cell, and the band is 2 trunc / h >= 2 voxels thick. */
+#define LS_RAY_OUTSIDE 0
+#define LS_RAY_FREE 1
+#define LS_RAY_UNSEEN 2
+#define LS_RAY_BEHIND 3
+#define LS_RAY_HIT 4
+size_t ls_tsdf_raycast_workspace_bytes(int nx, int ny, int nz, long long views, int height, int width);
+int ls_tsdf_raycast_f64(const int32_t* sum, const int32_t* n, int nx, int ny, int nz, int min_obs, const double* origin, double voxel, double trunc,
+                        const double* cam_to_world, const double* intrinsics, long long views, int height, int width, double znear, double step,
+                        float* depth, float* normal, uint8_t* state, long long* counts, void* workspace, size_t workspace_bytes, void* stream);
+/* P >= 1 problems per call: one (nx, ny, nz), one H x W, one znear and one step per call, sum / n [P,nx,ny,nz], origin [P,3], voxel [P],
+ * trunc [P], ragged views by HOST view_off [P+1] (a problem without views is allowed).  Every output of every view is BIT-IDENTICAL to
+ * ls_tsdf_raycast_f64 on its problem alone, wherever it stands in the batch: the single entry is the batch of one problem. */
+size_t ls_tsdf_raycast_batch_workspace_bytes(int P, int nx, int ny, int nz, long long views_total, int height, int width);
+int ls_tsdf_raycast_batch_f64(int P, const int32_t* sum, const int32_t* n, int nx, int ny, int nz, int min_obs, const double* origin,
+                              const double* voxel, const double* trunc, const double* cam_to_world, const double* intrinsics, long long views_total,
+                              const long long* view_off, int height, int width, double znear, double step, float* depth, float* normal, uint8_t* state,
+                              long long* counts, void* workspace, size_t workspace_bytes, void* stream);
+/* THE VIEW COMPARISON, per pixel: observed depth d_obs (fp32), the predicted (depth, state) of a raycast, tol > 0 (HOST double):
+ *   NO_OBS when !(d_obs > 0) (0, negative, NaN); UNKNOWN when the prediction is not a HIT; otherwise s = (double) d_obs - (double) d_pred:
+ *   AGREE when |s| <= tol, IN_FRONT when s < -tol (something new stands before the memory's surface), THROUGH when s > tol (the view sees
+ *   past a surface the memory holds).  Comparisons and integer counts only.
+ * observed / depth float [views,H,W], state uint8 [views,H,W] -> cls uint8 [views,H,W] (LS_VIEW_*), counts long long [views,5].  One
+ * memset and one kernel; it needs no workspace, so it has no size query.  NO tol IS RECOMMENDED: nothing here can measure one. */
+#define LS_VIEW_NO_OBS 0
+#define LS_VIEW_UNKNOWN 1
+#define LS_VIEW_AGREE 2
+#define LS_VIEW_IN_FRONT 3
+#define LS_VIEW_THROUGH 4
+int ls_depth_compare_f32(const float* observed, const float* depth, const uint8_t* state, long long views, int height, int width, double tol,
+                         uint8_t* cls, long long* counts, void* stream);
 
 /* Scene memory, the trimmed ICP with the point-to-plane metric (csrc/cloudnear.hip).  AN EXTENSION BEYOND THE RELEASED REFERENCE, like
  * ls_cloud_icp_f32, whose loop this is: a partial view registered point-to-point onto one point per voxel of a SURFACE slides along it

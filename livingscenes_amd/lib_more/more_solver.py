@@ -544,6 +544,90 @@ class More_Solver:
                                     voxel=fusion["voxel"], trunc=fusion["trunc"], empty=empty, znear=znear)
 
     @staticmethod
+    def _to_observation(P, T, g):
+        """the conventions of _carve_batch / _fuse_batch: T (memory -> rescan) or g (rescan -> memory), not both -> memory -> observation
+        [P,3,4] float64, or None when both are None (the views are in the memory's frame)"""
+        if T is not None and g is not None:
+            raise ValueError("give the registration T (memory -> rescan) or the memory-frame pose g (rescan -> memory), not both")
+        to_obs = None
+        for name, pose in (("T", T), ("g", g)):
+            if pose is None:
+                continue
+            if pose.dim() != 3 or pose.shape[0] != P or pose.shape[1] not in (3, 4) or pose.shape[2] != 4:
+                raise ValueError(f"{name} must be [P,4,4] or [P,3,4] with P = {P}, got {tuple(pose.shape)}")
+            to_obs = pose.detach().to(torch.float64)[:, :3, :]
+            if name == "g":
+                to_obs = inverse(to_obs)
+        return to_obs
+
+    def _predict_views_batch(self, fusion, cameras, T=None, g=None, *, height=None, width=None, min_obs=1, step=0.5, znear=0.05):
+        """Scene memory, what the fused state LOOKS LIKE from a camera (an extension beyond the released reference, like _fuse_batch, whose
+        inverse it is; the raycast of KinectFusion): depth, normal and state images of P instances in ONE ragged call
+        (ops.tsdf_raycast_batch, csrc/tsdfray.hip).  fusion = the dict of _fuse_batch.  cameras[p] = dict(world_to_cam [V,3,4],
+        intrinsics [V,4] or [4]) in the OBSERVATION's frame (HIP tensors; a views dict of the carve will do), or None: no view of that
+        slot.  T, g: exactly the conventions of _fuse_batch; the memory-frame camera is _memory_cameras(world_to_cam, T) or
+        (world_to_cam, inverse(g)), and its inverse [R^T | -R^T t] -- the camera-to-memory matrix the operator takes -- is formed in
+        float64 ON THE HOST.  height, width: None takes them from the first camera dict that carries 'depth'.
+        -> list of P: None for a slot without views, else dict(depth fp32 [V,H,W] (0: no hit; it goes straight back into depth_points,
+        the carve and the fuse), normal fp32 [V,H,W,3] in the memory's frame, state uint8 [V,H,W] of ops.RAY_STATE, counts int64 [V,5]:
+        device tensors; cam_to_world float64 [V,3,4], the matrices the operator received).  step = 0.5 IS AN UNMEASURED DEFAULT; NO
+        min_obs IS RECOMMENDED."""
+        P = fusion["sum"].shape[0]
+        if len(cameras) != P:
+            raise ValueError(f"{P} fusion states for {len(cameras)} sets of cameras")
+        to_obs = self._to_observation(P, T, g)
+        if height is None or width is None:
+            shaped = next((c["depth"] for c in cameras if c is not None and c.get("depth") is not None), None)
+            if shaped is None:
+                raise ValueError("_predict_views_batch: give height and width, or a camera dict that carries 'depth'")
+            height, width = int(shaped.shape[-2]), int(shaped.shape[-1])
+        dev = fusion["sum"].device
+        Ms = [None] * P
+        for p, c in enumerate(cameras):
+            if c is None:
+                continue
+            E = self._memory_cameras(c["world_to_cam"], None if to_obs is None else to_obs[p]).cpu()
+            Rt = E[:, :, :3].transpose(1, 2)
+            Ms[p] = torch.cat([Rt, -(Rt @ E[:, :, 3:4])], dim=-1).contiguous().to(dev)
+        shared = next((c["intrinsics"] for c in cameras if c is not None), None)
+        res = ops.tsdf_raycast_batch((fusion["sum"], fusion["n"]), Ms, [shared if c is None else c["intrinsics"] for c in cameras], height, width,
+                                     origin=fusion["origin"], voxel=fusion["voxel"], trunc=fusion["trunc"], min_obs=min_obs, step=step, znear=znear)
+        return [None if Ms[p] is None else dict(depth=d, normal=nrm, state=st, counts=cnt, cam_to_world=Ms[p]) for p, (d, nrm, st, cnt) in enumerate(res)]
+
+    def _view_agreement_batch(self, fusion, views, T=None, g=None, *, tol, min_obs=1, step=0.5, znear=0.05):
+        """Scene memory, the view-space gate of the fused path (an extension beyond the released reference): does an observed depth view
+        AGREE with what the fused state predicts at its camera under a pose?  views[p] = dict(depth [V,H,W] fp32, intrinsics,
+        world_to_cam [V,3,4]) in the OBSERVATION's frame, or None; T, g as for _fuse_batch.  ONE _predict_views_batch call at the views'
+        own cameras and ONE ops.depth_compare call over all of them: two operator calls and one host read for the whole batch.  Per pixel
+        with an observation and a predicted hit: agree (within tol), in_front (the observation is more than tol nearer: something new
+        stands before the memory's surface) or through (more than tol farther: the view sees past a surface the memory holds).
+        -> dict of per-slot lists: agree = AGREE / (AGREE + IN_FRONT + THROUGH) (None for a slot without views or without a comparable
+        pixel), through, in_front (pixel counts; None without views) and counts (host int64 [5] of ops.VIEW_CLASS summed over the
+        slot's views; None without views).  tol HAS NO DEFAULT AND NONE IS RECOMMENDED: nothing here can measure one on real scans;
+        step = 0.5 is the raycast's unmeasured default."""
+        P = fusion["sum"].shape[0]
+        if len(views) != P:
+            raise ValueError(f"{P} fusion states for {len(views)} sets of views")
+        out = {"agree": [None] * P, "through": [None] * P, "in_front": [None] * P, "counts": [None] * P}
+        have = [p for p, v in enumerate(views) if v is not None and v["depth"].shape[0] > 0]
+        if not have:
+            return out
+        pred = self._predict_views_batch(fusion, [views[p] if p in have else None for p in range(P)], T, g, min_obs=min_obs, step=step, znear=znear)
+        cat = (lambda ts: torch.cat(ts, 0) if len(ts) > 1 else ts[0])                       # noqa: E731
+        _, counts = ops.depth_compare(cat([views[p]["depth"].contiguous() for p in have]), cat([pred[p]["depth"] for p in have]),
+                                      cat([pred[p]["state"] for p in have]), tol=tol)
+        counts = counts.cpu().numpy()
+        at = 0
+        for p in have:
+            V = views[p]["depth"].shape[0]
+            c = counts[at:at + V].sum(0)
+            at += V
+            den = int(c[2] + c[3] + c[4])
+            out["agree"][p] = float(c[2]) / float(den) if den else None
+            out["through"][p], out["in_front"][p], out["counts"][p] = int(c[4]), int(c[3]), c
+        return out
+
+    @staticmethod
     def _observed_mesh_batch(fusion, min_obs=1):
         """Scene memory, the one mesh the memory can stand behind (an extension beyond the released reference, like _fuse_batch): the fused
         states of P instances meshed where they were OBSERVED, in ONE batched call (ops.tsdf_mesh_batch, csrc/tsdfmesh.hip).  fusion =
@@ -947,7 +1031,19 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
     optimised code where its loss improved; a slot whose state holds no observation has nothing to fit and keeps its code.  The step
     gains code_fit: the report of the call (per-slot lists loss_first, loss_last, n_band, n_free of n entries, None for slots not
     optimised; None for a step that optimised nothing).  NO QUOTA IS RECOMMENDED, nor any min_obs or fuse_res for fitting: no real scans
-    and no trained model are available here, and nothing here can measure the effect on matching or on the meshes."""
+    and no trained model are available here, and nothing here can measure the effect on matching or on the meshes.
+
+    The view gate of the fused state (the rescan's depth views compared with what the state predicts at their cameras) is
+    solve_sequence_view_gated below: this function with two more arguments.  It is a function of its own so that this parameter list,
+    which callers and tests rely on, stays as it is."""
+    return _solve_sequence(None, None, **locals())
+
+
+def _solve_sequence(view_tol, min_view_agreement, solver, ref, rescans, optim, mesh, voxel, optimize_codes, overlap_radius, min_overlap, refine_radius,
+                    refine_metric, normal_radius, consolidate, consolidate_radius, consolidate_max_variation, consolidate_max_shift, carve_tol,
+                    carve_window, carve_min_free, carve_max_seen, carve_empty, fuse_res, fuse_trunc_voxels, fuse_empty, fuse_mesh, fuse_min_obs,
+                    code_fit_band, code_fit_free, code_fit_seed):
+    """the one body of solve_sequence (view_tol None) and solve_sequence_view_gated: every argument given, the defaults are solve_sequence's"""
     if isinstance(optimize_codes, (bool, np.bool_)):
         optimize_codes = bool(optimize_codes)
     elif not (isinstance(optimize_codes, str) and optimize_codes == "tsdf"):
@@ -964,6 +1060,8 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
         raise ValueError("solve_sequence: refine_metric 'tsdf' needs fuse_res: without a fused state there is nothing to register against")
     if refine_metric == "tsdf" and refine_radius is not None:
         raise ValueError("solve_sequence: refine_metric 'tsdf' takes no refine_radius: its band is the fusion's trunc")
+    if view_tol is not None and fuse_res is None:
+        raise ValueError("solve_sequence_view_gated: view_tol needs fuse_res: without a fused state there is no predicted view to compare with")
     refining = refine_radius is not None or refine_metric == "tsdf"
     gate = overlap_radius is not None or min_overlap is not None
     model = solver.model
@@ -1000,6 +1098,10 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
             out.update({"refine_stop": [None] * n, "refine_iters": [None] * n, "registration_init": [None] * n})
         if optimize_codes == "tsdf":
             out["code_fit"] = None
+        if view_tol is not None:
+            out.update({"view_agree": [None] * n, "view_through": [None] * n, "view_in_front": [None] * n})
+            if min_view_agreement is not None and not gate:
+                out["rejected"] = []
         if pairs:
             src, tgt = [mem[i] for i, _ in pairs], [res_full[j] for _, j in pairs]
             R, t = solver._solve_pairwise_registration_optim_batch(src, tgt) if optim else solver._solve_pairwise_registration_batch(src, tgt)
@@ -1042,6 +1144,23 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
                 for k, (i, _) in enumerate(pairs):
                     out["overlap"][i], out["overlap_rmse"][i], out["memory_seen"][i] = ov["overlap"][k], ov["rmse"][k], ov["memory_seen"][k]
                 out["rejected"] = sequence_plan(n, m0.tolist(), len(res_full), accepted=accepted)["rejected"]
+            vviews = rescan.get("views") if view_tol is not None else None
+            viewing = [k for k in range(len(pairs)) if vviews is not None and vviews[pairs[k][1]] is not None]
+            if viewing:                                               # the matched pairs with views, on the state BEFORE this rescan is fused
+                slot_views, slot_pose = [None] * n, [None] * n
+                for k in viewing:
+                    slot_views[pairs[k][0]] = vviews[pairs[k][1]]
+                    slot_pose[pairs[k][0]] = (T[k] if refined is None else refined["g"][k]).detach().to(torch.float64)[:3, :]
+                eye = torch.eye(4, dtype=torch.float64, device=T.device)[:3, :]
+                poses = torch.stack([eye if q is None else q.to(T.device) for q in slot_pose])   # a slot without views: a placeholder nothing reads
+                va = solver._view_agreement_batch(fusion, slot_views, T=poses if refined is None else None, g=None if refined is None else poses,
+                                                  tol=view_tol, min_obs=fuse_min_obs)
+                for key in ("agree", "through", "in_front"):
+                    out["view_" + key] = va[key]
+                if min_view_agreement is not None:
+                    passed = [va["agree"][i] is None or va["agree"][i] >= min_view_agreement for i, _ in pairs]
+                    accepted = passed if accepted is None else [a and b for a, b in zip(accepted, passed)]
+                    out["rejected"] = sequence_plan(n, m0.tolist(), len(res_full), accepted=accepted)["rejected"]
             for k, (i, j) in enumerate(pairs):
                 out["registration"][i] = T[k:k + 1]
                 cur = {key: res_codes[key][j][None] for key in _CODE_KEYS}
@@ -1134,6 +1253,31 @@ def solve_sequence(solver, ref, rescans, optim=False, mesh=False, voxel=None, op
         if fuse_mesh:
             memory["observed_meshes"] = solver._observed_mesh_batch(fusion, fuse_min_obs)
     return steps, memory
+
+
+def solve_sequence_view_gated(solver, ref, rescans, *, view_tol, min_view_agreement=None, **kw):
+    """solve_sequence(solver, ref, rescans, **kw) with the view gate of the fused state (an extension beyond the released reference, like
+    the fusion).  kw: any keyword argument of solve_sequence, with its defaults; everything that function's docstring says holds.
+
+    The overlap gate asks whether the rescan's points lie near kept points; the fused state can be asked the sharper question whether the
+    rescan's depth views SEE what the state predicts at their cameras.  view_tol > 0 (it needs fuse_res; a ValueError raised before any
+    device work otherwise, as for a view_tol that is not > 0): the matched pairs whose rescan
+    instance carries 'views' go into ONE More_Solver._view_agreement_batch call (a raycast of the state at the views' own cameras and a
+    per-pixel comparison with their depth maps: two operator calls), after the refinement, on the state as it stands BEFORE this rescan
+    is fused, under the pose the merge will use, with min_obs = fuse_min_obs.  The step gains view_agree (agreeing pixels over the
+    pixels that have both an observation and a predicted hit), view_through (pixels that look more than view_tol PAST a surface the
+    memory holds) and view_in_front (pixels more than view_tol before it): lists of n, None for slots without views or, for view_agree,
+    without a comparable pixel.  With min_view_agreement given, a pair whose view_agree is a number below it joins `rejected` exactly as
+    a pair below min_overlap does (no carve, no merge, no fuse, no re-encode); a pair whose view_agree is None is not rejected; where
+    both gates are given a pair must pass both.  NO view_tol AND NO min_view_agreement IS RECOMMENDED: no real scans are available here
+    to measure one on, and a state that holds no observation yet (no ref['views'], no earlier rescan) predicts nothing and rejects
+    nothing."""
+    import inspect
+    if view_tol is None or not float(view_tol) > 0.0:
+        raise ValueError(f"solve_sequence_view_gated: view_tol must be > 0, got {view_tol!r}")
+    args = inspect.signature(solve_sequence).bind(solver, ref, rescans, **kw)
+    args.apply_defaults()
+    return _solve_sequence(view_tol, min_view_agreement, **args.arguments)
 
 
 def _se3_exp(xi):  # host twin of the retraction in csrc/optim.hip (tests compare both with torch.matrix_exp)

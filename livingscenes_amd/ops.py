@@ -1867,3 +1867,114 @@ def tsdf_fit_loss(sdf, s, trunc, target, kind, min_loss=None, improved=None):
     call(dev, "ls_tsdf_fit_loss_f64", ptr(sdf), ptr(s), ptr(trunc), ptr(target), ptr(kind), P, N, ptr(loss), ptr(grad), ptr(min_loss), ptr(improved),
          stream_ptr(dev))
     return loss, grad
+
+
+# ------------------------------------------------------------------------------------------------ the fused state seen from a camera (csrc/tsdfray.hip)
+RAY_STATE = ("outside", "free", "unseen", "behind", "hit")               # the values of a pixel's state, by value
+VIEW_CLASS = ("no_obs", "unknown", "agree", "in_front", "through")      # the values of a compared pixel's class, by value
+
+
+def _ray_cameras(op, cam_to_world, intrinsics, dev):
+    """the cameras of one problem: cam_to_world [V,3,4] and intrinsics [V,4] or [4], float64 HIP tensors on dev (None: no view)"""
+    if cam_to_world is None:
+        return None
+    M = _f64_dev(cam_to_world, "cam_to_world", op, (3, 4))
+    K = _f64_dev(intrinsics, "intrinsics", op, (4,), M.shape[0])
+    if M.device != dev or K.device != dev:
+        raise ValueError(f"{op}: the state is on {dev}, cam_to_world on {M.device}, intrinsics on {K.device}")
+    return M, K
+
+
+def _tsdf_raycast(op, single, state, cam_to_world, intrinsics, height, width, origin, voxel, trunc, min_obs, step, znear, packed):
+    S, N, P, dims = _fuse_state(op, state, not single)
+    dev = S.device
+    min_obs, H, W, step, znear = int(min_obs), int(height), int(width), float(step), float(znear)
+    if min_obs < 1:
+        raise ValueError(f"{op}: min_obs must be >= 1, got {min_obs}")
+    if H < 1 or W < 1:
+        raise ValueError(f"{op}: the image must have at least one pixel, got {H} x {W}")
+    o, h, tr = _fuse_grid(op, P, origin, voxel, trunc)
+    if single:
+        cams = [_ray_cameras(op, cam_to_world, intrinsics, dev)]
+        if cams[0] is None:
+            raise ValueError(f"{op}: cam_to_world is [views,3,4], got None")
+    else:
+        if len(cam_to_world) != P or (not torch.is_tensor(intrinsics) and len(intrinsics) != P):
+            raise ValueError(f"{op}: {P} problems in state for {len(cam_to_world)} sets of cameras")
+        Ks = [intrinsics] * P if torch.is_tensor(intrinsics) else list(intrinsics)
+        cams = [_ray_cameras(op, m, k, dev) for m, k in zip(cam_to_world, Ks)]
+    nviews = [0 if c is None else c[0].shape[0] for c in cams]
+    vo = _offsets(nviews)
+    views = int(vo[P])
+    name = "ls_" + op
+    ws_bytes = getattr(load(), name + "_workspace_bytes")(*(() if single else (P,)), *dims, views, H, W)
+    if ws_bytes == 0:
+        raise ValueError(f"{op}: P = {P} problems of dims {dims} with {views} views of {H} x {W} unsupported (include/livingscenes_hip.h: "
+                         "P nx ny nz < 2^31, views * height * width < 2^31)")
+    ws = _scratch(ws_bytes, dev)
+    depth = torch.empty(views, H, W, dtype=torch.float32, device=dev)
+    normal = torch.empty(views, H, W, 3, dtype=torch.float32, device=dev)
+    st = torch.empty(views, H, W, dtype=torch.uint8, device=dev)
+    counts = torch.empty(views, 5, dtype=torch.int64, device=dev)
+    have = [c for c in cams if c is not None and c[0].shape[0]]
+    M, K = (torch.cat(t, 0) if len(have) > 1 else t[0] for t in zip(*have)) if have else (None, None)
+    outs = (H, W, znear, step, ptr(depth), ptr(normal), ptr(st), ptr(counts), ptr(ws), ws.numel(), stream_ptr(dev))
+    if single:
+        call(dev, name + "_f64", ptr(S), ptr(N), *dims, min_obs, _hptr(o), float(h[0]), float(tr[0]), ptr(M), ptr(K), views, *outs)
+        return depth, normal, st, counts
+    call(dev, name + "_f64", P, ptr(S), ptr(N), *dims, min_obs, _hptr(o), _hptr(h), _hptr(tr), ptr(M), ptr(K), views, _hptr(vo), *outs)
+    if packed:
+        return depth, normal, st, counts, vo
+    return list(zip(torch.split(depth, nviews), torch.split(normal, nviews), torch.split(st, nviews), torch.split(counts, nviews)))
+
+
+def tsdf_raycast_batch(state, cam_to_world, intrinsics, height, width, *, origin, voxel, trunc, min_obs=1, step=0.5, znear=0.05, packed=False):
+    """ls_tsdf_raycast_batch_f64 (an extension beyond the released reference, like depth_fuse; the raycast of KinectFusion): the fused
+    states of P instances SEEN from posed cameras.  state = (sum, n) int32 HIP tensors [P,nx,ny,nz] (tsdf_state, depth_fuse_batch);
+    cam_to_world = list of P float64 HIP tensors [V_p,3,4] taking the CAMERA frame (x right, y down, z forward, the convention of
+    depth_points) into the grid's frame (V_p = 0 or None: no view of that problem); intrinsics = a list of P [V_p,4] or [4], or one [4]
+    tensor for all: (fx, fy, cx, cy); one height x width per call; origin [P,3] or [3], voxel, trunc (one value or P): host float64, the
+    grids the views were fused on.  Per pixel the definition of include/livingscenes_hip.h: the ray through the integer pixel coordinate,
+    parametrised by the camera depth, clipped to the grid, marched in steps of `step` voxels along its fastest axis; at every sample the
+    value of tsdf_sample; the first sample at or below 0 after a positive one is a HIT, whose depth is the linear interpolation between
+    the two (no secant iteration, no empty-space skipping) and whose normal is the unit gradient there, in the grid's frame.
+    -> list of P (depth fp32 [V_p,H,W] (0: no hit), normal fp32 [V_p,H,W,3], state uint8 [V_p,H,W] of RAY_STATE, counts int64 [V_p,5],
+    the histogram of the states): device tensors; packed=True: (depth, normal, state, counts, view_off) over all views.  One call, no
+    host read, whatever P.  "free" says the memory looked all along the ray and found nothing, "unseen" that it never looked somewhere
+    along it, "behind" that the first thing known is the inside of something.  step = 0.5 IS AN UNMEASURED DEFAULT (derived: step <= 1
+    keeps consecutive samples in the same or an adjacent cell; the band is 2 trunc / voxel >= 2 voxels thick); NO min_obs IS RECOMMENDED."""
+    return _tsdf_raycast("tsdf_raycast_batch", False, state, cam_to_world, intrinsics, height, width, origin, voxel, trunc, min_obs, step, znear, packed)
+
+
+def tsdf_raycast(state, cam_to_world, intrinsics, height, width, *, origin, voxel, trunc, min_obs=1, step=0.5, znear=0.05):
+    """ls_tsdf_raycast_f64: state = (sum, n) int32 HIP tensors [nx,ny,nz] (a slice of tsdf_state), cam_to_world [V,3,4] and intrinsics
+    [V,4] or [4] float64 HIP tensors, origin [3], voxel and trunc host float64 -> (depth [V,H,W], normal [V,H,W,3], state [V,H,W], counts
+    [V,5]) as tsdf_raycast_batch describes them, bit-identical to the same problem inside any batch.  step = 0.5 IS AN UNMEASURED
+    DEFAULT; NO min_obs IS RECOMMENDED."""
+    return _tsdf_raycast("tsdf_raycast", True, state, cam_to_world, intrinsics, height, width, origin, voxel, trunc, min_obs, step, znear, False)
+
+
+def depth_compare(observed, depth, state, *, tol):
+    """ls_depth_compare_f32: an observed depth view against a predicted one (tsdf_raycast's depth and state), per pixel.  observed, depth
+    fp32 [V,H,W], state uint8 [V,H,W], HIP tensors; tol > 0 in the depth's unit.  no_obs: the observation is not > 0; unknown: the
+    prediction is not a hit; else with s = observed - predicted in float64: agree |s| <= tol, in_front s < -tol (something new stands
+    before the memory's surface), through s > tol (the view sees past a surface the memory holds).  -> (cls uint8 [V,H,W] of VIEW_CLASS,
+    counts int64 [V,5]): device tensors, no host read.  Comparisons and integer counts only.  NO tol IS RECOMMENDED."""
+    op = "depth_compare"
+    tol = float(tol)
+    if not tol > 0.0:
+        raise ValueError(f"{op}: tol must be > 0, got {tol}")
+    if not torch.is_tensor(observed) or observed.device.type != "cuda" or observed.dim() != 3 or observed.shape[1] < 1 or observed.shape[2] < 1:
+        raise ValueError(f"{op}: observed is an fp32 HIP (cuda) tensor [views, H, W] with at least one pixel")
+    dev, shape = observed.device, tuple(observed.shape)
+    for name, t, dtype in (("observed", observed, torch.float32), ("depth", depth, torch.float32), ("state", state, torch.uint8)):
+        if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+            got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+            raise ValueError(f"{op}: {name} must be a contiguous {dtype} tensor {shape} on {dev}, got {got}")
+    V, H, W = shape
+    if V * H * W >= 2 ** 31:
+        raise ValueError(f"{op}: {V} views of {H} x {W} pixels unsupported (views * height * width < 2^31)")
+    cls = torch.empty(shape, dtype=torch.uint8, device=dev)
+    counts = torch.empty(V, 5, dtype=torch.int64, device=dev)
+    call(dev, "ls_depth_compare_f32", ptr(observed), ptr(depth), ptr(state), V, H, W, tol, ptr(cls), ptr(counts), stream_ptr(dev))
+    return cls, counts
