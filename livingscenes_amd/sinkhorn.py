@@ -101,7 +101,9 @@ def divergence_batch(x, y, blur=0.05, scaling=0.5, lmax=None, return_need=False)
     if lmax is None:
         lmax = int(need)                                                                               # the one host read
     k = torch.arange(lmax, device=x.device)[None]                                                      # [1,L]
-    e_mid = (2 * diam.log()[:, None] + (k - 1).clamp_min(0) * (2 * math.log(scaling))).exp()           # d^2 scaling^(2 (k - 1))
+    # d^2 scaling^(2 (k - 1)); the exponent in double throughout (an integer tensor times a Python float is a float32 tensor, and a float32
+    # k log(scaling) put one schedule in eight a float32 ulp off epsilon_schedule's in some entry)
+    e_mid = (2 * diam.log()[:, None] + (k - 1).clamp_min(0).double() * (2 * math.log(scaling))).exp()
     eps_tab = torch.where(k == 0, (diam ** 2)[:, None], e_mid)
     eps_tab = torch.where(k == (nj + 1)[:, None], torch.full_like(eps_tab, blur ** 2), eps_tab)
     eps_tab = torch.where(k > (nj + 1)[:, None], torch.zeros_like(eps_tab), eps_tab).float().t().contiguous()   # [L,P]; 0 = schedule ended
