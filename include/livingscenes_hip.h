@@ -68,7 +68,8 @@ typedef enum {
  * ls_depth_fuse_f32 / ls_depth_fuse_batch_f32, ls_tsdf_volume_f64, ls_tsdf_mesh_f64 / ls_tsdf_mesh_batch_f64,
  * ls_tsdf_sample_f32 / ls_tsdf_sample_batch_f32, ls_tsdf_icp_f32 / ls_tsdf_icp_batch_f32,
  * ls_tsdf_draw_f32 / ls_tsdf_draw_batch_f32, ls_tsdf_fit_loss_f64,
- * ls_tsdf_raycast_f64 / ls_tsdf_raycast_batch_f64, ls_depth_compare_f32 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
+ * ls_tsdf_raycast_f64 / ls_tsdf_raycast_batch_f64, ls_depth_compare_f32,
+ * ls_depth_normals_f32, ls_depth_fuse_weighted_f32 / ls_depth_fuse_weighted_batch_f32 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
  * binding compares it with the header it was written against and refuses a mismatch (livingscenes_amd/_lib.py: load). */
 #define LS_ABI_VERSION 107
 int ls_version(void);
@@ -1280,6 +1281,74 @@ int ls_tsdf_raycast_batch_f64(int P, const int32_t* sum, const int32_t* n, int n
 #define LS_VIEW_THROUGH 4
 int ls_depth_compare_f32(const float* observed, const float* depth, const uint8_t* state, long long views, int height, int width, double tol,
                          uint8_t* cls, long long* counts, void* stream);
+
+/* Scene memory, a normal per pixel of a depth view (csrc/depthplane.hip, csrc/plane_plan.h).  AN EXTENSION BEYOND THE RELEASED
+ * REFERENCE, like the fusion; what the weighted fuse below reads its planes from.  Inputs: depth [views,H,W] fp32 (DEVICE), intrinsics
+ * [views,4] float64 = (fx, fy, cx, cy) (DEVICE), max_jump [views] float64 > 0 (HOST, copied into the workspace as the fuse copies its
+ * grids).  Definition per view and pixel (x, y) (tests/plane_oracle.py is the same text as NumPy).  Everything is float64 and nothing is
+ * contracted.
+ *   1. d = (double) depth[v, y, x].  NO_DEPTH unless d is finite and > 0 (so 0, negative, NaN and inf).
+ *   2. P(x, y) = (d * ((double)x - cx) / fx, d * ((double)y - cy) / fy, d): the product first, then the quotient.
+ *   3. A neighbour is usable iff it is inside the image, is a depth pixel by step 1 and |d_nb - d| <= max_jump.
+ *   4. a = P(x+1, y) - P(x-1, y) if both neighbours are usable, else P(x+1, y) - P(x, y), else P(x, y) - P(x-1, y), else none; b likewise
+ *      along y.  NO_NEIGHBOUR if a or b is missing.
+ *   5. m = a x b, every product rounded on its own; mm = (m_x m_x + m_y m_y) + m_z m_z.  DEGENERATE if mm is 0 or not finite.
+ *   6. n = m / sqrt(mm); t = (n_x P_x + n_y P_y) + n_z P_z.  DEGENERATE if t == 0; n = -n if t > 0, so the normal faces the camera.
+ *   7. VALID: normals_out = the three float64 components rounded once to fp32.
+ * normals_out [views,H,W,3] fp32 is (0, 0, 0) unless VALID; state_out [views,H,W] uint8 = NO_DEPTH 0, VALID 1, NO_NEIGHBOUR 2,
+ * DEGENERATE 3, by value; counts_out [views,4] int64 is their histogram (all DEVICE).
+ * Refused on the host before the first HIP call: H or W < 1, views < 0, views H W >= 2^31, a max_jump that is not finite or <= 0 -- the
+ * error names the view --, null pointers with views > 0.
+ * One thread per pixel; a workgroup stays inside one view, so its intrinsics and max_jump are wave-uniform; the histogram is one integer
+ * add per wave, view and state from a ballot.  Launches, whatever the number of views: the copy of max_jump into the workspace, 1 memset
+ * (counts_out) and 1 kernel.  No host synchronisation, no allocation, no floating-point atomics.  The workspace holds the device copy of
+ * max_jump: a function of its arguments alone, 0 for refused sizes.  NO max_jump IS RECOMMENDED: none has been measured on real scans. */
+size_t ls_depth_normals_workspace_bytes(long long views, int height, int width);
+int ls_depth_normals_f32(const float* depth, long long views, int height, int width, const double* intrinsics, const double* max_jump,
+                         float* normals_out, uint8_t* state_out, long long* counts_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Scene memory, the depth fusion with integer weights and a point-to-plane value inside the band (csrc/depthplane.hip,
+ * csrc/plane_plan.h).  AN EXTENSION BEYOND THE RELEASED REFERENCE, opt-in beside ls_depth_fuse_f32, whose state, grids, views and
+ * refusals it shares.  Why: on the analytic sphere most of the fused field's error comes from the t = +1 votes of pixels that hit
+ * nothing, cast with the weight of a surface observation onto voxels that hug the silhouette; the 1 / cos overstatement of the projective
+ * distance comes second.  The arguments are those of ls_depth_fuse_f32 plus normals [views,H,W,3] fp32 (DEVICE, nullable:
+ * ls_depth_normals_f32 of the same views, in the CAMERA frame) and weights[4] = (w_plane, w_proj, w_free, w_empty), HOST ints, each in
+ * 1 .. 255.  Definition per voxel and view, the views in the call's order (tests/plane_oracle.py).  Everything is float64 and nothing
+ * is contracted.
+ *   1 - 5. literally steps 1 - 5 of ls_depth_fuse_f32: x, c, OUT, the pixel (qx, qy), d, EMPTY, s = d - c.z, OCCLUDED if s < -trunc on
+ *      the PROJECTIVE s.  With empty_is_free an EMPTY voxel-view is taken with q = 16384 and w = w_empty and counted as FREE.
+ *   6. FREE if s > trunc: q = 16384, w = w_free.  The band is decided projectively: a plane distance is wrong far from its pixel.
+ *   7. NEAR, |s| <= trunc.  NEAR_PLANE if normals is given and the pixel's normal n is usable (three finite components, not all zero):
+ *      p = P(qx, qy) as in step 2 of ls_depth_normals_f32; s_n = ((n_x (c_x - p_x) + n_y (c_y - p_y)) + n_z (c_z - p_z));
+ *      value = clamp(s_n, -trunc, trunc) (a NaN reads -trunc); w = w_plane.  Otherwise NEAR_PROJ: value = s, w = w_proj.
+ *      In both cases q = (int) floor(value / trunc * 16384 + 0.5).
+ *   8. SATURATED, and skipped, if n + w > 65535.
+ *   9. Otherwise sum += w * q and n += w.  |sum| <= n * 16384, n <= 65535, and sum == n * 16384 iff every vote was free: every reader of
+ *      a fused state runs on a weighted one as it is, and min_obs becomes a weight threshold.
+ * THE UPDATE IS INTEGER, so the state does not depend on the order of the views, on how they are split over calls, or on the batch; only
+ * a saturated voxel depends on the order, and the order is the call's.  With normals NULL and weights (any, 1, 1, 1) the state is BIT FOR
+ * BIT that of ls_depth_fuse_f32.
+ * view_counts [views,7] int64 (DEVICE) is the histogram of OUT, EMPTY (skipped), OCCLUDED, NEAR_PLANE, NEAR_PROJ, FREE and SATURATED, by
+ * value 0 .. 6, over the voxels of the view's problem; every row sums to nx ny nz.
+ * Refused on the host before the first HIP call: whatever ls_depth_fuse_f32 refuses, null weights, a weight outside 1 .. 255.
+ * The kernel has the shape of the fuse's: a workgroup owns 256 consecutive voxels of one problem, one thread per voxel keeps (sum, n) in
+ * registers over its problem's views; E, K, the weights and the image bases are wave-uniform; one depth gather per voxel-view and three
+ * normal gathers per NEAR one.  Launches, whatever P and the number of views: the copy of the host arrays into the workspace, 1 memset
+ * (view_counts) and 1 kernel; a call without views does nothing.  No host synchronisation, no allocation, no floating-point atomics.
+ * NO WEIGHTS ARE RECOMMENDED: 64 : 1 comes from one synthetic sphere, nothing has been measured on real scans. */
+size_t ls_depth_fuse_weighted_workspace_bytes(int nx, int ny, int nz, long long views);
+int ls_depth_fuse_weighted_f32(int32_t* sum, int32_t* n, int nx, int ny, int nz, const double* origin, double voxel, double trunc, const float* depth,
+                               const float* normals, long long views, int height, int width, const double* intrinsics, const double* world_to_cam,
+                               double znear, int empty_is_free, const int* weights, long long* view_counts, void* workspace, size_t workspace_bytes,
+                               void* stream);
+/* P >= 1 problems per call, as ls_depth_fuse_batch_f32: sum, n [P,nx,ny,nz]; problem p owns the views [view_off[p], view_off[p+1]) of the
+ * views_total images and of normals [views_total,H,W,3]; one set of weights per call.  The state of every problem is BIT-IDENTICAL to
+ * ls_depth_fuse_weighted_f32 on that problem alone (which is this entry with P = 1). */
+size_t ls_depth_fuse_weighted_batch_workspace_bytes(int P, int nx, int ny, int nz, long long views_total);
+int ls_depth_fuse_weighted_batch_f32(int P, int32_t* sum, int32_t* n, int nx, int ny, int nz, const double* origin, const double* voxel,
+                                     const double* trunc, const float* depth, const float* normals, long long views_total, const long long* view_off,
+                                     int height, int width, const double* intrinsics, const double* world_to_cam, double znear, int empty_is_free,
+                                     const int* weights, long long* view_counts, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Scene memory, the trimmed ICP with the point-to-plane metric (csrc/cloudnear.hip).  AN EXTENSION BEYOND THE RELEASED REFERENCE, like
  * ls_cloud_icp_f32, whose loop this is: a partial view registered point-to-point onto one point per voxel of a SURFACE slides along it

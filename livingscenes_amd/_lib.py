@@ -258,6 +258,12 @@ SIGNATURES = {
     "ls_tsdf_raycast_batch_workspace_bytes": (_SZ, [_I, _I, _I, _I, _LL, _I, _I]),
     "ls_tsdf_raycast_batch_f64": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _LL, _P, _I, _I, _D, _D, _P, _P, _P, _P, _P, _SZ, _P]),
     "ls_depth_compare_f32": (_I, [_P, _P, _P, _LL, _I, _I, _D, _P, _P, _P]),
+    "ls_depth_normals_workspace_bytes": (_SZ, [_LL, _I, _I]),
+    "ls_depth_normals_f32": (_I, [_P, _LL, _I, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "ls_depth_fuse_weighted_workspace_bytes": (_SZ, [_I, _I, _I, _LL]),
+    "ls_depth_fuse_weighted_f32": (_I, [_P, _P, _I, _I, _I, _P, _D, _D, _P, _P, _LL, _I, _I, _P, _P, _D, _I, _P, _P, _P, _SZ, _P]),
+    "ls_depth_fuse_weighted_batch_workspace_bytes": (_SZ, [_I, _I, _I, _I, _LL]),
+    "ls_depth_fuse_weighted_batch_f32": (_I, [_I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _LL, _P, _I, _I, _P, _P, _D, _I, _P, _P, _P, _SZ, _P]),
     "ls_profile_begin": (_I, [_P]),
     "ls_profile_end": (_I, [_P, ctypes.POINTER(ProfileEntry), _I, ctypes.POINTER(ctypes.c_int)]),
 }

@@ -1978,3 +1978,145 @@ def depth_compare(observed, depth, state, *, tol):
     counts = torch.empty(V, 5, dtype=torch.int64, device=dev)
     call(dev, "ls_depth_compare_f32", ptr(observed), ptr(depth), ptr(state), V, H, W, tol, ptr(cls), ptr(counts), stream_ptr(dev))
     return cls, counts
+
+
+# ------------------------------------------------------------------------------------------------ depth normals and the weighted fuse (csrc/depthplane.hip)
+DEPTH_NORMAL_STATE = ("no_depth", "valid", "no_neighbour", "degenerate")                               # the values of depth_normals' state
+FUSE_WEIGHTED_CLASS = ("out", "empty", "occluded", "near_plane", "near_proj", "free", "saturated")    # the columns of the weighted view_counts
+
+
+def depth_normals(depth, intrinsics, *, max_jump):
+    """ls_depth_normals_f32 (an extension beyond the released reference, like depth_fuse): a normal per pixel of depth views, in the
+    CAMERA frame.  depth [V,H,W] fp32 and intrinsics [V,4] or [4] float64, HIP tensors; max_jump > 0 (one value or V, host float64), in
+    the depth's unit.  Per pixel the definition of include/livingscenes_hip.h: the back-projected points of the left / right and upper /
+    lower neighbours whose depth differs by at most max_jump (central differences, one-sided beside a hole, an edge or a jump), their
+    cross product normalised in float64 and turned towards the camera, rounded once to fp32.
+    -> (normals fp32 [V,H,W,3], (0, 0, 0) unless valid; state uint8 [V,H,W] of DEPTH_NORMAL_STATE; counts int64 [V,4], the histogram of
+    the states): device tensors, one call, no host read.  NO max_jump IS RECOMMENDED: none has been measured on real scans."""
+    op = "depth_normals"
+    if not torch.is_tensor(depth) or depth.device.type != "cuda" or depth.dtype != torch.float32:
+        kind = f"{depth.device.type} {depth.dtype}" if torch.is_tensor(depth) else type(depth).__name__
+        raise _lib.LsError(f"{op}: depth must be an fp32 HIP (cuda) tensor, got {kind}: the MI355X path has no CPU fallback and converts nothing")
+    if depth.dim() != 3 or depth.shape[1] < 1 or depth.shape[2] < 1:
+        raise ValueError(f"{op}: depth is [views, H, W] with at least one pixel, got {tuple(depth.shape)}")
+    dev = depth.device
+    V, H, W = depth.shape
+    D, K = depth.contiguous(), _f64_dev(intrinsics, "intrinsics", op, (4,), V)
+    mj = max_jump.detach().cpu().numpy() if torch.is_tensor(max_jump) else max_jump
+    mj = np.full(V, float(mj), dtype=np.float64) if np.ndim(mj) == 0 else np.ascontiguousarray(mj, dtype=np.float64).reshape(-1)
+    if mj.shape[0] != V:
+        raise ValueError(f"{op}: {mj.shape[0]} values of max_jump for {V} views")
+    if not (np.isfinite(mj) & (mj > 0.0)).all():
+        raise ValueError(f"{op}: max_jump must be finite and > 0, got {mj[~(np.isfinite(mj) & (mj > 0.0))][0]}")
+    normals = torch.empty(V, H, W, 3, dtype=torch.float32, device=dev)
+    state = torch.empty(V, H, W, dtype=torch.uint8, device=dev)
+    counts = torch.empty(V, 4, dtype=torch.int64, device=dev)
+    if V == 0:
+        return normals, state, counts
+    ws_bytes = load().ls_depth_normals_workspace_bytes(V, H, W)
+    if ws_bytes == 0:
+        raise ValueError(f"{op}: {V} views of {H} x {W} pixels unsupported (include/livingscenes_hip.h: views * height * width < 2^31)")
+    ws = _scratch(ws_bytes, dev)
+    call(dev, "ls_depth_normals_f32", ptr(D), V, H, W, ptr(K), _hptr(mj), ptr(normals), ptr(state), ptr(counts), ptr(ws), ws.numel(), stream_ptr(dev))
+    return normals, state, counts
+
+
+def _fuse_weights(op, weights):
+    """weights = (w_plane, w_proj, w_free, w_empty): four integers in 1 .. 255 -> host int32 [4]"""
+    try:
+        w = [int(k) for k in weights]
+        exact = all(k == v for k, v in zip(w, weights))
+    except (TypeError, ValueError):
+        w, exact = [], False
+    if len(w) != 4 or not exact or min(w) < 1 or max(w) > 255:
+        raise ValueError(f"{op}: weights are four integers (w_plane, w_proj, w_free, w_empty), each in 1 .. 255, got {weights!r}")
+    return np.asarray(w, dtype=np.int32)
+
+
+def _fuse_normals(op, normals, D, dev):
+    """the normals of the views D [V,H,W]: None, or an fp32 HIP tensor [V,H,W,3] (depth_normals of the same views)"""
+    if normals is None:
+        return None
+    if not torch.is_tensor(normals) or normals.device.type != "cuda" or normals.dtype != torch.float32:
+        kind = f"{normals.device.type} {normals.dtype}" if torch.is_tensor(normals) else type(normals).__name__
+        raise _lib.LsError(f"{op}: normals must be an fp32 HIP (cuda) tensor, got {kind}: the MI355X path has no CPU fallback and converts nothing")
+    if tuple(normals.shape) != tuple(D.shape) + (3,) or normals.device != dev:
+        raise ValueError(f"{op}: normals is {tuple(D.shape) + (3,)} on {dev}, one per depth pixel, got {tuple(normals.shape)} on {normals.device}")
+    return normals.contiguous()
+
+
+def depth_fuse_weighted_batch(state, depths, intrinsics, world_to_cam, *, origin, voxel, trunc, weights, normals=None, empty="unknown", znear=0.05):
+    """ls_depth_fuse_weighted_batch_f32 (an extension beyond the released reference, opt-in beside depth_fuse_batch): posed depth views
+    fused into the truncated signed distance state of P instances IN PLACE, with integer weights and a point-to-plane value inside the
+    band.  state, depths, intrinsics, world_to_cam, origin, voxel, trunc, empty and znear as depth_fuse_batch takes them; weights =
+    (w_plane, w_proj, w_free, w_empty), four integers in 1 .. 255; normals = None, a list of P fp32 HIP tensors [V_p,H,W,3] (depth_normals
+    of the same views; None where the problem has no views) or ONE packed tensor [views_total,H,W,3] in the order of the views.  Per voxel
+    and view the definition of include/livingscenes_hip.h: the class and the band are the projective fuse's; a NEAR voxel-view whose
+    pixel has a normal takes the distance to that pixel's plane, clamped to the band, with w_plane, any other NEAR one the projective
+    distance with w_proj; free space counts w_free, an empty pixel taken as free w_empty; sum += w q, n += w.  The state format is the
+    fuse's: tsdf_volume, tsdf_mesh, tsdf_sample, tsdf_icp, tsdf_draw and tsdf_raycast read it as it is, min_obs being a weight threshold.
+    With normals=None and weights (any, 1, 1, 1) the state is bit for bit depth_fuse_batch's.  weights HAS NO DEFAULT AND NONE IS
+    RECOMMENDED: 64 : 1 comes from one synthetic sphere.  -> list of P device int64 [V_p,7]: voxels per class of FUSE_WEIGHTED_CLASS
+    and view.  One call, no host read."""
+    op = "depth_fuse_weighted_batch"
+    S, N, P, dims = _fuse_state(op, state, True)
+    dev = S.device
+    if not (len(depths) == len(world_to_cam) == P) or (not torch.is_tensor(intrinsics) and len(intrinsics) != P):
+        raise ValueError(f"{op}: {P} problems in state for {len(depths)} sets of depth views and {len(world_to_cam)} sets of cameras")
+    o, h, tr = _fuse_grid(op, P, origin, voxel, trunc)
+    eif, znear, wts = _fuse_empty(op, empty), float(znear), _fuse_weights(op, weights)
+    Ks = [intrinsics] * P if torch.is_tensor(intrinsics) else list(intrinsics)
+    vw = [None if d is None else _carve_views(op, d, k, e, dev) for d, k, e in zip(depths, Ks, world_to_cam)]
+    shapes = sorted({tuple(v[0].shape[1:]) for v in vw if v is not None})
+    if len(shapes) > 1:
+        raise ValueError(f"{op}: one H x W per call, got {shapes}")
+    nviews = [0 if v is None else v[0].shape[0] for v in vw]
+    vo = _offsets(nviews)
+    views = int(vo[P])
+    if views == 0:
+        return [torch.zeros(0, 7, dtype=torch.int64, device=dev) for _ in range(P)]
+    have = [v for v in vw if v is not None and v[0].shape[0]]
+    D, K, E = (torch.cat(t, 0) if len(have) > 1 else t[0] for t in zip(*have))
+    if normals is not None and not torch.is_tensor(normals):
+        if len(normals) != P:
+            raise ValueError(f"{op}: {P} problems in state for {len(normals)} sets of normals")
+        parts = [nr for nr, c in zip(normals, nviews) if c]
+        if any(nr is None for nr in parts):
+            raise ValueError(f"{op}: normals for every problem that has views, or for none")
+        normals = torch.cat(parts, 0) if len(parts) > 1 else parts[0]
+    Nr = _fuse_normals(op, normals, D, dev)
+    H, W = shapes[0]
+    vc = torch.empty(views, 7, dtype=torch.int64, device=dev)
+    ws_bytes = load().ls_depth_fuse_weighted_batch_workspace_bytes(P, *dims, views)
+    if ws_bytes == 0:
+        raise ValueError(f"{op}: P = {P} problems of dims {dims} with {views} views unsupported (include/livingscenes_hip.h: P nx ny nz < 2^31)")
+    ws = _scratch(ws_bytes, dev)
+    call(dev, "ls_depth_fuse_weighted_batch_f32", P, ptr(S), ptr(N), *dims, _hptr(o), _hptr(h), _hptr(tr), ptr(D), ptr(Nr), views, _hptr(vo), H, W,
+         ptr(K), ptr(E), znear, eif, _hptr(wts), ptr(vc), ptr(ws), ws.numel(), stream_ptr(dev))
+    return list(torch.split(vc, nviews))
+
+
+def depth_fuse_weighted(state, depth, intrinsics, world_to_cam, *, origin, voxel, trunc, weights, normals=None, empty="unknown", znear=0.05):
+    """ls_depth_fuse_weighted_f32: the views depth [V,H,W] fp32 with intrinsics [V,4] or [4] and world_to_cam [V,3,4] float64 from the
+    grid's frame fused into state = (sum, n), int32 HIP tensors [nx,ny,nz] (a slice of tsdf_state), IN PLACE, as
+    depth_fuse_weighted_batch describes it: weights = (w_plane, w_proj, w_free, w_empty) in 1 .. 255 (NO DEFAULT, NONE RECOMMENDED),
+    normals = None or fp32 [V,H,W,3] (depth_normals of the same views).  -> device int64 [V,7], the voxels per class of
+    FUSE_WEIGHTED_CLASS.  Bit-identical to the same problem inside any batch, and to the same views in any order or split over calls."""
+    op = "depth_fuse_weighted"
+    S, N, _, dims = _fuse_state(op, state, False)
+    dev = S.device
+    o, h, tr = _fuse_grid(op, 1, origin, voxel, trunc)
+    eif, znear, wts = _fuse_empty(op, empty), float(znear), _fuse_weights(op, weights)
+    D, K, E = _carve_views(op, depth, intrinsics, world_to_cam, dev)
+    Nr = _fuse_normals(op, normals, D, dev)
+    views, H, W = D.shape
+    vc = torch.empty(views, 7, dtype=torch.int64, device=dev)
+    if views == 0:
+        return vc
+    ws_bytes = load().ls_depth_fuse_weighted_workspace_bytes(*dims, views)
+    if ws_bytes == 0:
+        raise ValueError(f"{op}: dims {dims} with {views} views unsupported (include/livingscenes_hip.h: nx ny nz < 2^31)")
+    ws = _scratch(ws_bytes, dev)
+    call(dev, "ls_depth_fuse_weighted_f32", ptr(S), ptr(N), *dims, _hptr(o), float(h[0]), float(tr[0]), ptr(D), ptr(Nr), views, H, W, ptr(K), ptr(E),
+         znear, eif, _hptr(wts), ptr(vc), ptr(ws), ws.numel(), stream_ptr(dev))
+    return vc
