@@ -69,7 +69,8 @@ typedef enum {
  * ls_tsdf_sample_f32 / ls_tsdf_sample_batch_f32, ls_tsdf_icp_f32 / ls_tsdf_icp_batch_f32,
  * ls_tsdf_draw_f32 / ls_tsdf_draw_batch_f32, ls_tsdf_fit_loss_f64,
  * ls_tsdf_raycast_f64 / ls_tsdf_raycast_batch_f64, ls_depth_compare_f32,
- * ls_depth_normals_f32, ls_depth_fuse_weighted_f32 / ls_depth_fuse_weighted_batch_f32 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
+ * ls_depth_normals_f32, ls_depth_fuse_weighted_f32 / ls_depth_fuse_weighted_batch_f32,
+ * ls_tsdf_prior_rows_f32 / ls_tsdf_prior_rows_batch_f32, ls_tsdf_prior_vote_f32 / ls_tsdf_prior_vote_batch_f32 -- change no existing layout and keep 107).  ls_version() returns the value the LIBRARY was built with; a
  * binding compares it with the header it was written against and refuses a mismatch (livingscenes_amd/_lib.py: load). */
 #define LS_ABI_VERSION 107
 int ls_version(void);
@@ -1349,6 +1350,56 @@ int ls_depth_fuse_weighted_batch_f32(int P, int32_t* sum, int32_t* n, int nx, in
                                      const double* trunc, const float* depth, const float* normals, long long views_total, const long long* view_off,
                                      int height, int width, const double* intrinsics, const double* world_to_cam, double znear, int empty_is_free,
                                      const int* weights, long long* view_counts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Scene memory, the fused state COMPLETED by the shape prior's field (csrc/tsdfprior.hip).  AN EXTENSION BEYOND THE RELEASED REFERENCE,
+ * like the fusion: the decoder's value at the lattice samples the cameras left short of observations enters a SECOND state of the same
+ * format as integer votes, so ls_tsdf_mesh_f64, ls_tsdf_raycast_f64 and ls_tsdf_sample_f32 read the completed state unchanged.  The
+ * observed state is never written.  Definition (csrc/tsdfprior_plan.h is the same text as C++, tests/tsdf_prior_oracle.py as NumPy), for
+ * problem p with grid (origin, voxel h, trunc), scale s_p > 0, an integer prior weight w0 in 1 .. 65535, and a lattice sample with state
+ * (sum, n) and linear index i (k fastest):
+ *   1 weight   w = max(w0 - n, 0): the prior tops a sample up to w0 votes and fades out as observations arrive.  w > 0: ELIGIBLE.
+ *   2 row      the query row of an eligible sample: each axis the float64 origin_a + h * index_a of ls_depth_fuse_f32 rounded once to
+ *              fp32.  Rows in ascending i within a problem, problems in order: ONE packed list, row_off [P+1] its offsets; every row
+ *              carries row_inst = p and row_index = i (int32).  The rows of an instance are contiguous: the layout the ragged decoder
+ *              entry takes.
+ *   3 vote     with f the fp32 value the decoder returned for the row: d = (double) s_p * (double) f; t = d / trunc clamped to
+ *              [-1, 1]; q = (int) floor(t * 16384 + 0.5); sum' = sum + w q, n' = n + w.  THE CONVENTION OF ls_tsdf_fit_loss_f64: the
+ *              decoder's value times s is a metric distance with the sign of the fused distance.  A NaN f casts no vote: the sample
+ *              keeps (sum, n) and is counted; +-inf clamps to +-1.  A sample that is not eligible keeps (sum, n) bit for bit.
+ *   4 state    n' = max(n, w0) <= 65535 and |sum'| <= n' * 16384: the invariants of ls_depth_fuse_f32's state survive.
+ * Integer and float64 arithmetic only, nothing contracted: given the same f, the rows, their order, the counts and (sum', n') do not
+ * depend on the batch, on its order or on the run.  counts long long [P,4] = eligible, voted, skipped (NaN), untouched samples; the rows
+ * entry leaves voted and skipped 0.
+ * ls_tsdf_prior_rows_f32: n int32 [nx,ny,nz] (DEVICE, read only; the rows do not read sum), origin [3] and voxel (HOST doubles); outputs
+ * (DEVICE) points float [R,3], row_inst / row_index int32 [R], row_off long long [P+1] -- always the FULL offsets; nothing is written at
+ * or past cap_rows rows; points = row_inst = row_index = NULL is a sizing call (the convention of ls_tsdf_mesh_f64); counts may be NULL.
+ * ls_tsdf_prior_vote_f32: sum, n (DEVICE, read only), s and trunc (HOST doubles), values float [rows] (DEVICE) in the order of the rows
+ * entry; sum_out, n_out int32 [nx,ny,nz] (DEVICE), a SEPARATE pair, written for every sample.  An eligible sample finds its row as the
+ * rows entry did (block offset + popcount of the lower lanes): no index array is read.  A row at or past `rows` casts no vote.
+ * Refused on the host before the first HIP call, the problem named where there is one: dims < 1, P nx ny nz >= 2^31, nx ny nz above
+ * 4096 blocks of 4096 samples (the scan limit of ls_tsdf_draw_f32), P outside 1 .. 65535, weight outside 1 .. 65535, s not finite or
+ * <= 0, a grid that ls_depth_fuse_f32 refuses, null pointers, rows without their indices, a negative capacity, an output that aliases the
+ * input state, a short workspace (LS_ERR_WORKSPACE).  Both entries take the workspace of ls_tsdf_prior_rows(_batch)_workspace_bytes, a
+ * function of (P, nx, ny, nz), 0 for refused sizes: one ballot word per 64 samples and one count per block of 4096.
+ * Launches, whatever P: the copy of the host scalars into the workspace and classify, ONE scan over the block counts of the batch,
+ * emit (rows; none in a sizing call) or vote.  No host synchronisation, no allocation, no compact list; the voted / skipped counts are
+ * two integer atomics per workgroup.  NO WEIGHT IS RECOMMENDED: nothing here can measure one. */
+size_t ls_tsdf_prior_rows_workspace_bytes(int nx, int ny, int nz);
+int ls_tsdf_prior_rows_f32(const int32_t* n, int nx, int ny, int nz, int weight, const double* origin, double voxel, float* points, int32_t* row_inst,
+                           int32_t* row_index, long long cap_rows, long long* row_off, long long* counts, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int ls_tsdf_prior_vote_f32(const int32_t* sum, const int32_t* n, int nx, int ny, int nz, int weight, double s, double trunc, const float* values,
+                           long long rows, int32_t* sum_out, int32_t* n_out, long long* counts, void* workspace, size_t workspace_bytes, void* stream);
+/* P >= 1 problems per call: one (nx, ny, nz) and one weight per call, sum / n / sum_out / n_out [P,nx,ny,nz], origin [P,3], voxel, s,
+ * trunc [P] (HOST), counts [P,4]; the rows and the values of the batch are one packed list.  Every output of every problem is
+ * BIT-IDENTICAL to the single entry on that problem alone (row_inst apart, which names the problem): the single entry is the batch of one. */
+size_t ls_tsdf_prior_rows_batch_workspace_bytes(int P, int nx, int ny, int nz);
+int ls_tsdf_prior_rows_batch_f32(int P, const int32_t* n, int nx, int ny, int nz, int weight, const double* origin, const double* voxel, float* points,
+                                 int32_t* row_inst, int32_t* row_index, long long cap_rows, long long* row_off, long long* counts, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+int ls_tsdf_prior_vote_batch_f32(int P, const int32_t* sum, const int32_t* n, int nx, int ny, int nz, int weight, const double* s, const double* trunc,
+                                 const float* values, long long rows, int32_t* sum_out, int32_t* n_out, long long* counts, void* workspace,
+                                 size_t workspace_bytes, void* stream);
 
 /* Scene memory, the trimmed ICP with the point-to-plane metric (csrc/cloudnear.hip).  AN EXTENSION BEYOND THE RELEASED REFERENCE, like
  * ls_cloud_icp_f32, whose loop this is: a partial view registered point-to-point onto one point per voxel of a SURFACE slides along it

@@ -264,6 +264,12 @@ SIGNATURES = {
     "ls_depth_fuse_weighted_f32": (_I, [_P, _P, _I, _I, _I, _P, _D, _D, _P, _P, _LL, _I, _I, _P, _P, _D, _I, _P, _P, _P, _SZ, _P]),
     "ls_depth_fuse_weighted_batch_workspace_bytes": (_SZ, [_I, _I, _I, _I, _LL]),
     "ls_depth_fuse_weighted_batch_f32": (_I, [_I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _LL, _P, _I, _I, _P, _P, _D, _I, _P, _P, _P, _SZ, _P]),
+    "ls_tsdf_prior_rows_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "ls_tsdf_prior_rows_f32": (_I, [_P, _I, _I, _I, _I, _P, _D, _P, _P, _P, _LL, _P, _P, _P, _SZ, _P]),
+    "ls_tsdf_prior_vote_f32": (_I, [_P, _P, _I, _I, _I, _I, _D, _D, _P, _LL, _P, _P, _P, _P, _SZ, _P]),
+    "ls_tsdf_prior_rows_batch_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "ls_tsdf_prior_rows_batch_f32": (_I, [_I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _LL, _P, _P, _P, _SZ, _P]),
+    "ls_tsdf_prior_vote_batch_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _LL, _P, _P, _P, _P, _SZ, _P]),
     "ls_profile_begin": (_I, [_P]),
     "ls_profile_end": (_I, [_P, ctypes.POINTER(ProfileEntry), _I, ctypes.POINTER(ctypes.c_int)]),
 }

@@ -673,6 +673,67 @@ class More_Solver:
         verts, faces = verts.cpu().numpy(), faces.cpu().numpy()
         return [make_mesh(verts[vo[p]:vo[p + 1]], faces[fo[p]:fo[p + 1]]) if fo[p + 1] > fo[p] else None for p in range(len(vo) - 1)]
 
+    def _complete_fusion_batch(self, fusion, code, slots=None, *, weight, max_rows=1 << 20):
+        """Scene memory, ONE reconstruction per instance out of its two pictures (an extension beyond the released reference, like
+        _fuse_batch): the fused state where the cameras measured, the shape prior's field where they did not.  Three steps, no host
+        read of the volume: ops.tsdf_prior_rows_batch (csrc/tsdfprior.hip) turns the lattice samples with fewer than `weight`
+        observations into query rows, hip_model().sdf_decode_rows evaluates the decoder on them (the ragged entry: the rows of an
+        instance are contiguous; max_rows rows per decoder launch), ops.tsdf_complete_batch enters the values as weight - n integer
+        votes into a COPY of the state.  The fused state is never written.  `code` holds P rows (memory['codes'] for all slots);
+        fusion = the dict of _fuse_batch; slots = the P slots of the fusion the rows belong to (None: the fusion has P slots, in
+        order).  THIS BUILD'S DEFINITION, that of _optimize_code_on_fusion_batch: the decoder's value times the instance's scale s is
+        a metric distance.  With decoder_type "deepsdf" the decoder reads the raw query and s does not reach it; the convention is
+        kept all the same, exactly as ops.tsdf_fit_loss keeps it when the code is fitted to this state.
+        -> dict of the fusion's shape: sum, n (new int32 tensors [P,res,res,res]), origin, voxel, trunc (shared with the fusion, the
+        rows of `slots`), weight, counts (device int64 [P,4]: eligible, voted, skipped_nonfinite, untouched -- ops.PRIOR_COUNT) and
+        rows (the number of decoder queries).  Mesh it whole with min_obs = weight (_completed_mesh_batch).  weight HAS NO DEFAULT
+        AND NONE IS RECOMMENDED: 1 lets a single observation outvote the prior, which can leave a wall where a +trunc observation
+        meets a -trunc belief; larger weights blend.  Unmeasured: real scans, a trained model, any effect downstream."""
+        weight = ops._prior_weight("_complete_fusion_batch", weight)
+        P = code["z_inv"].shape[0]
+        slots = list(range(fusion["sum"].shape[0])) if slots is None else [int(i) for i in slots]
+        if len(slots) != P:
+            raise ValueError(f"{P} code rows for {len(slots)} slots of the fusion")
+        S, N = fusion["sum"], fusion["n"]
+        origin, voxel, trunc = (np.asarray(fusion[k], dtype=np.float64) for k in ("origin", "voxel", "trunc"))
+        if slots != list(range(S.shape[0])):
+            pick = torch.tensor(slots, device=S.device)
+            S, N = S[pick].contiguous(), N[pick].contiguous()
+            origin, voxel, trunc = origin[slots], voxel[slots], trunc[slots]
+        rows = ops.tsdf_prior_rows_batch((S, N), origin=origin, voxel=voxel, weight=weight, packed=True)
+        points, row_inst = rows[0], rows[1]
+        s_ = code["s"].detach().float().contiguous()
+        if points.shape[0]:
+            values = self.model.hip_model().sdf_decode_rows(points, row_inst, code["z_so3"].detach(), code["z_inv"].detach(), s_, code["t"].detach(),
+                                                            max_rows=max_rows)
+        else:
+            values = torch.empty(0, dtype=torch.float32, device=S.device)
+        (S2, N2), counts = ops.tsdf_complete_batch((S, N), values, rows, s=s_.reshape(P).double().cpu().numpy(), trunc=trunc, weight=weight)
+        return {"sum": S2, "n": N2, "origin": origin, "voxel": voxel, "trunc": trunc, "weight": weight, "counts": counts, "rows": int(points.shape[0])}
+
+    @staticmethod
+    def _completed_mesh_batch(fusion, completed):
+        """Scene memory, the closed mesh of a completed state with its provenance (no new kernel): ops.tsdf_mesh_batch of
+        completed = the dict of _complete_fusion_batch with min_obs = its weight -- every sample of a completed state holds at least
+        that many votes, so every cube is kept -- and, per vertex, whether it was MEASURED: ops.tsdf_sample_batch of the OBSERVED
+        state (fusion = the dict of _fuse_batch with the same slots) at the vertex cast to fp32, identity pose, min_obs = 1, reports
+        all eight corners of its cell seen.  -> list of P dicts {vertices float64 [nv,3], faces int64 [nf,3], vertex_observed bool
+        [nv]}: host arrays in the memory's frame, copied ONCE for the whole batch; None for an instance whose mesh is empty.  A face
+        all of whose vertices are observed is a measured one, the others are the prior's."""
+        state = (completed["sum"], completed["n"])
+        verts, faces, vo, fo, _ = ops.tsdf_mesh_batch(state, origin=completed["origin"], voxel=completed["voxel"], min_obs=int(completed["weight"]),
+                                                      packed=True)
+        P = len(vo) - 1
+        seen = torch.zeros(verts.shape[0], dtype=torch.bool, device=verts.device)
+        if verts.shape[0]:
+            q = verts.float()
+            out = ops.tsdf_sample_batch((fusion["sum"], fusion["n"]), [q[vo[p]:vo[p + 1]] for p in range(P)], None, origin=fusion["origin"],
+                                        voxel=fusion["voxel"], trunc=fusion["trunc"], min_obs=1, packed=True)
+            seen = out[2] == ops.SAMPLE_STATE.index("sampled")
+        verts, faces, seen = verts.cpu().numpy(), faces.cpu().numpy(), seen.cpu().numpy()
+        return [{"vertices": verts[vo[p]:vo[p + 1]], "faces": faces[fo[p]:fo[p + 1]], "vertex_observed": seen[vo[p]:vo[p + 1]]}
+                if fo[p + 1] > fo[p] else None for p in range(P)]
+
     def _refine_on_memory_batch(self, mem_pcs, new_pcs, T, radius, metric="point", normal_radius=None, **kw):
         """Scene memory, the pose the merge and the overlap gate trust (an extension beyond the released reference, like both): refine P
         registrations on the memory itself, at full resolution, in ONE ragged call (ops.cloud_icp_batch, csrc/cloudnear.hip) -- trimmed
@@ -1349,6 +1410,39 @@ def solve_sequence_weighted_fusion(solver, ref, rescans, *, fuse_weights, fuse_v
     args.apply_defaults()
     weighted = {"weights": tuple(int(w) for w in weights), "value": fuse_value, "max_jump": fuse_max_jump}
     return _solve_sequence(weighted, view_tol, min_view_agreement, **args.arguments)
+
+
+def solve_sequence_completed(solver, ref, rescans, *, complete_weight, complete_mesh=True, **kw):
+    """solve_sequence(solver, ref, rescans, **kw) and then ONE reconstruction per instance: the fused state COMPLETED by the shape
+    prior's field (an extension beyond the released reference, opt-in like the fusion itself).  kw: any keyword argument of
+    solve_sequence, with its defaults; with fuse_weights it goes through solve_sequence_weighted_fusion, else with view_tol through
+    solve_sequence_view_gated, and everything those functions' docstrings say holds.  It needs fuse_res: a ValueError raised before
+    any device work otherwise, as for a complete_weight that is no integer in 1 .. 65535.
+
+    After the last step ONE More_Solver._complete_fusion_batch call over all slots with memory['codes'] (rows -> decoder -> votes:
+    the fused state where the cameras measured, the decoder's value times s where fewer than complete_weight observations arrived)
+    and, with complete_mesh, ONE _completed_mesh_batch call.  memory gains `completed` (the dict of _complete_fusion_batch: a second
+    state of the fusion's format; memory['fusion'] is not written) and `completed_meshes` (list of n dicts {vertices, faces,
+    vertex_observed}, or None for an empty mesh; None without complete_mesh).  The steps and every other entry of memory are those of
+    the wrapped function, bit for bit.  With optimize_codes="tsdf" the codes that vote were fitted to the very state they complete.
+    complete_weight HAS NO DEFAULT AND NONE IS RECOMMENDED: unmeasured on real scans and with a trained model."""
+    weight = ops._prior_weight("solve_sequence_completed", complete_weight)
+    if kw.get("fuse_res") is None:
+        raise ValueError("solve_sequence_completed: the completion needs the fused state: give fuse_res")
+    if kw.get("fuse_weights") is not None:
+        steps, memory = solve_sequence_weighted_fusion(solver, ref, rescans, **kw)
+    elif kw.get("view_tol") is not None:
+        steps, memory = solve_sequence_view_gated(solver, ref, rescans, **kw)
+    else:
+        for k in ("fuse_weights", "view_tol"):
+            kw.pop(k, None)
+        if kw.get("min_view_agreement") is not None:
+            raise ValueError("solve_sequence_completed: min_view_agreement needs view_tol: without it no view is compared")
+        kw.pop("min_view_agreement", None)
+        steps, memory = solve_sequence(solver, ref, rescans, **kw)
+    memory["completed"] = solver._complete_fusion_batch(memory["fusion"], memory["codes"], weight=weight)
+    memory["completed_meshes"] = solver._completed_mesh_batch(memory["fusion"], memory["completed"]) if complete_mesh else None
+    return steps, memory
 
 
 def _se3_exp(xi):  # host twin of the retraction in csrc/optim.hip (tests compare both with torch.matrix_exp)

@@ -2120,3 +2120,129 @@ def depth_fuse_weighted(state, depth, intrinsics, world_to_cam, *, origin, voxel
     call(dev, "ls_depth_fuse_weighted_f32", ptr(S), ptr(N), *dims, _hptr(o), float(h[0]), float(tr[0]), ptr(D), ptr(Nr), views, H, W, ptr(K), ptr(E),
          znear, eif, _hptr(wts), ptr(vc), ptr(ws), ws.numel(), stream_ptr(dev))
     return vc
+
+
+# ------------------------------------------------------------------------------------------------ the fused state completed by the prior (csrc/tsdfprior.hip)
+PRIOR_COUNT = ("eligible", "voted", "skipped_nonfinite", "untouched")   # the columns of the counts, by value
+
+
+def _prior_weight(op, weight):
+    if isinstance(weight, bool) or not isinstance(weight, (int, np.integer)) or not 1 <= int(weight) <= 65535:
+        raise ValueError(f"{op}: weight is an integer in 1 .. 65535 (the votes the prior tops a sample up to; NONE IS RECOMMENDED), got {weight!r}")
+    return int(weight)
+
+
+def _prior_ws(op, single, P, dims, dev):
+    ws_bytes = getattr(load(), "ls_tsdf_prior_rows" + ("" if single else "_batch") + "_workspace_bytes")(*(() if single else (P,)), *dims)
+    if ws_bytes == 0:
+        raise ValueError(f"{op}: P = {P} problems of dims {dims} unsupported (include/livingscenes_hip.h: P nx ny nz < 2^31, "
+                         "nx ny nz <= 4096 blocks of 4096 samples, P <= 65535)")
+    return _scratch(ws_bytes, dev)
+
+
+def _tsdf_prior_rows(op, single, state, origin, voxel, weight, packed):
+    S, N, P, dims = _fuse_state(op, state, not single)
+    weight = _prior_weight(op, weight)
+    o, h = _fuse_grid(op, P, origin, voxel)
+    dev = S.device
+    ws = _prior_ws(op, single, P, dims, dev)
+    name = "ls_" + op + "_f32"
+    off = torch.zeros(P + 1, dtype=torch.int64, device=dev)
+    counts = torch.empty(P, 4, dtype=torch.int64, device=dev)
+    head = (ptr(N), *dims, weight, _hptr(o), float(h[0]) if single else _hptr(h))
+    if not single:
+        head = (P,) + head
+    call(dev, name, *head, None, None, None, 0, ptr(off), ptr(counts), ptr(ws), ws.numel(), stream_ptr(dev))
+    ro = off.cpu().tolist()                                              # the one host read
+    R = ro[P]
+    points = torch.empty(R, 3, dtype=torch.float32, device=dev)
+    inst = torch.empty(R, dtype=torch.int32, device=dev)
+    index = torch.empty(R, dtype=torch.int32, device=dev)
+    if R:
+        call(dev, name, *head, ptr(points), ptr(inst), ptr(index), R, ptr(off), ptr(counts), ptr(ws), ws.numel(), stream_ptr(dev))
+    if single:
+        counts = counts[0]
+    if packed or single:
+        return points, inst, index, ro, counts
+    cut = lambda t: [t[ro[p]:ro[p + 1]] for p in range(P)]                # noqa: E731
+    return cut(points), cut(inst), cut(index), ro, counts
+
+
+def tsdf_prior_rows_batch(state, *, origin, voxel, weight, packed=False):
+    """ls_tsdf_prior_rows_batch_f32 (an extension beyond the released reference, like depth_fuse): the lattice samples of P fused states
+    that the cameras left short of `weight` observations, as query rows for the shape prior.  state = (sum, n) int32 HIP tensors
+    [P,nx,ny,nz] (tsdf_state, depth_fuse_batch; read only); origin [P,3] or [3], voxel (one value or P): host float64, the grids the
+    views were fused on; weight: an integer in 1 .. 65535, NO DEFAULT AND NONE RECOMMENDED.  A sample is eligible iff weight - n > 0;
+    its row is the float64 position origin_a + voxel * index_a rounded once to fp32: the definition of include/livingscenes_hip.h, by
+    equality.  Rows in ascending linear index within a problem, problems in order, so the rows of an instance are contiguous: the
+    layout HipModel.sdf_decode_rows takes.
+    -> (points fp32 [R,3], row_inst int32 [R], row_index int32 [R]: device tensors; offsets: host list of P+1; counts device int64
+    [P,4], the columns of PRIOR_COUNT with voted and skipped still 0) with packed=True; packed=False: the first three as lists of P
+    views of the packed tensors.  One sizing call, ONE host read of the offsets, one real call (none where R = 0); no compact list and
+    no atomics on the way.  A problem's rows do not depend on the batch."""
+    return _tsdf_prior_rows("tsdf_prior_rows_batch", False, state, origin, voxel, weight, packed)
+
+
+def tsdf_prior_rows(state, *, origin, voxel, weight, packed=False):
+    """ls_tsdf_prior_rows_f32: state = (sum, n) int32 HIP tensors [nx,ny,nz] (a slice of tsdf_state), origin [3] and voxel host float64
+    -> (points [R,3], row_inst [R] (zeros), row_index [R], offsets [0, R], counts device int64 [4]) as tsdf_prior_rows_batch describes
+    them (packed changes nothing for one problem), bit-identical to the same problem anywhere inside any batch."""
+    return _tsdf_prior_rows("tsdf_prior_rows", True, state, origin, voxel, weight, packed)
+
+
+def _tsdf_complete(op, single, state, values, rows, s, trunc, weight):
+    S, N, P, dims = _fuse_state(op, state, not single)
+    weight = _prior_weight(op, weight)
+    dev = S.device
+    if not isinstance(rows, (tuple, list)) or len(rows) != 5:
+        raise ValueError(f"{op}: rows is what tsdf_prior_rows{'' if single else '_batch'} returned: (points, row_inst, row_index, offsets, counts)")
+    ro, rcounts = [int(v) for v in rows[3]], rows[4]
+    if len(ro) != P + 1 or ro[0] != 0 or any(b < a for a, b in zip(ro, ro[1:])):
+        raise ValueError(f"{op}: the offsets of rows are {P + 1} ascending values from 0 for {P} problems, got {ro}")
+    R = ro[P]
+    if not torch.is_tensor(values) or values.device.type != "cuda" or values.dtype != torch.float32:
+        kind = f"{values.device.type} {values.dtype}" if torch.is_tensor(values) else type(values).__name__
+        raise _lib.LsError(f"{op}: values must be an fp32 HIP (cuda) tensor, got {kind}: the MI355X path has no CPU fallback and converts nothing")
+    if values.dim() != 1 or values.shape[0] != R or values.device != dev or not values.is_contiguous():
+        raise ValueError(f"{op}: values is a contiguous [R] tensor on {dev} with R = {R}, the last offset of rows; got {tuple(values.shape)} on {values.device}")
+    sv = np.ascontiguousarray(s.detach().cpu().numpy() if torch.is_tensor(s) else s, dtype=np.float64).reshape(-1)
+    if sv.shape[0] == 1 and P > 1:
+        sv = np.full(P, sv[0], dtype=np.float64)
+    if sv.shape[0] != P or not (np.isfinite(sv) & (sv > 0)).all():
+        raise ValueError(f"{op}: s is {P} finite values > 0 (the scale of every instance), got {sv.tolist()}")
+    _, _, tr = _fuse_grid(op, P, np.zeros(3), 1.0, trunc)
+    if not (np.isfinite(tr) & (tr > 0)).all():
+        raise ValueError(f"{op}: trunc must be finite and > 0, got {tr.tolist()}")
+    if R == 0:                                                          # nothing to vote on: the completed state is a copy
+        counts = rcounts.clone() if torch.is_tensor(rcounts) else torch.as_tensor(np.asarray(rcounts), device=dev)
+        return (S.clone(), N.clone()), counts
+    ws = _prior_ws(op, single, P, dims, dev)
+    So, No = torch.empty_like(S), torch.empty_like(N)
+    counts = torch.empty(P, 4, dtype=torch.int64, device=dev)
+    tail = (ptr(values), R, ptr(So), ptr(No), ptr(counts), ptr(ws), ws.numel(), stream_ptr(dev))
+    if single:
+        call(dev, "ls_tsdf_prior_vote_f32", ptr(S), ptr(N), *dims, weight, float(sv[0]), float(tr[0]), *tail)
+        return (So, No), counts[0]
+    call(dev, "ls_tsdf_prior_vote_batch_f32", P, ptr(S), ptr(N), *dims, weight, _hptr(sv), _hptr(tr), *tail)
+    return (So, No), counts
+
+
+def tsdf_complete_batch(state, values, rows, *, s, trunc, weight):
+    """ls_tsdf_prior_vote_batch_f32: the shape prior's field entered into a COPY of P fused states as integer votes.  state = (sum, n)
+    int32 HIP tensors [P,nx,ny,nz], never written; rows: what tsdf_prior_rows_batch(state, weight=weight) returned (its offsets are
+    checked against values); values fp32 [R] on the device: the decoder's value of every row, in row order; s (one value or P; the
+    scale of every instance) and trunc (one value or P): host float64; weight as for the rows.  THE CONVENTION OF tsdf_fit_loss: the
+    decoder's value times s is a metric distance with the sign of the fused distance.  Per eligible sample, w = weight - n:
+    q = floor(clip(s f / trunc, -1, 1) * 16384 + 0.5), sum' = sum + w q, n' = n + w = weight; a NaN casts no vote, +-inf clamps; every
+    other sample keeps (sum, n) bit for bit: the definition of include/livingscenes_hip.h, by equality.
+    -> ((sum', n') new int32 tensors of the state's shape -- the format every tsdf_* operator reads, meshed whole with
+    min_obs = weight; counts device int64 [P,4] of PRIOR_COUNT).  One call, no host read; R = 0: two copies and no kernel.  An
+    eligible sample finds its row by block offset + popcount, so row_index is not read.  NO WEIGHT IS RECOMMENDED."""
+    return _tsdf_complete("tsdf_complete_batch", False, state, values, rows, s, trunc, weight)
+
+
+def tsdf_complete(state, values, rows, *, s, trunc, weight):
+    """ls_tsdf_prior_vote_f32: state = (sum, n) int32 HIP tensors [nx,ny,nz], values fp32 [R], rows what tsdf_prior_rows returned, s and
+    trunc host float64 -> ((sum', n'), counts device int64 [4]) as tsdf_complete_batch describes them, bit-identical to the same
+    problem inside any batch.  NO WEIGHT IS RECOMMENDED."""
+    return _tsdf_complete("tsdf_complete", True, state, values, rows, s, trunc, weight)
